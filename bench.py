@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — outer-iterations/sec of the INSIDER factorisation hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3] [--grid]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3] [--grid] [--dump-outputs DIR]
 
 A "step" is one outer iteration of the reference's optimize() (src/optimize.cpp:325-410): all covariate row
 updates, the column update and the amortised checkpoint work.  The timed region is ONE optimize() call of K outer
@@ -24,9 +24,10 @@ Prints ONE JSON line on rank 0:
   cd_kernel     the sweep kernel alone
   cpu_baseline  the CPU oracle (reference formulation) on a bounded gene sample, all host threads engaged
   grid          (--grid) BASELINE config 3 as written: tune() over lambda in {1,3,..,19} x alpha in {.2,.3,.4,.5}
+
+--dump-outputs DIR writes what the timed call returned to DIR/<name>.npy (float64, <= 64 MB; dump_outputs below): with the
+same arguments the inputs are the same in every run, so two builds can be compared output for output.
 """
-import os
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "32")   # before anything initialises the HIP runtime (see insider_amd/_lib.py: concurrent fits)
 import argparse
 import hashlib
 import json
@@ -62,7 +63,56 @@ def parse():
                     "K <= 32 register-resident sweeps, 33..63 one gene per wavefront, > 63 unsupported)")
     ap.add_argument("--seed", type=int, default=20240301)
     ap.add_argument("--opt", action="append", default=[], metavar="NAME=VALUE", help="library option (insider_hip_set_option), repeatable")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed call, write what it returned (row factors, "
+                    "column factor, loss / RMSEs, checkpoint trajectory; less what is NaN by definition) as DIR/<name>.npy in float64, at most 64 MB in all")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+DUMP_SAMPLE_SEED = 20240302
+# columns of a trajectory row (include/insider_hip.h: iter, train_rmse, test_rmse, SSE/2, row_reg/2, col_reg/2, l1_reg, loss,
+# delta_loss, decay) that are NaN by definition, left out of the dump so that every value it writes is finite: delta_loss
+# on the row of the inits (elsewhere the difference of consecutive losses), test_rmse when nothing is held out (tuning = 0)
+TRAJ_TEST_RMSE_COL, TRAJ_DELTA_LOSS_COL = 2, 8
+
+
+def dump_outputs(dirname, res, lo, p_total, rank, world, tuning=1):
+    """Write the timed call's results as float64 .npy files (bench.py --dump-outputs).  Rank 0 writes what every rank holds
+    alike (row factors, loss, RMSEs and the trajectory, less what is NaN by definition: delta_loss, and test_rmse when
+    tuning = 0); each rank writes its slab of the column factor (`column_factor`, with a `_rank<r>` suffix when N > 1).  A column factor over its share of the 64 MB budget is written as a fixed, seeded sample
+    of genes (the same sample whatever the run), with the global gene indices beside it in `column_factor_genes`."""
+    os.makedirs(dirname, exist_ok=True)
+    files = {}
+
+    def save(name, a):
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        np.save(os.path.join(dirname, name + ".npy"), a)
+        files[name] = list(a.shape)
+
+    if rank == 0:
+        for key, a in res["row_matrices"].items():
+            save(key, a)
+        held_out = tuning == 1
+        for key in ("loss", "train_rmse") + (("test_rmse",) if held_out else ()):
+            save(key, np.array([res[key]]))
+        save("traj", np.delete(res["traj"], [TRAJ_DELTA_LOSS_COL] + ([] if held_out else [TRAJ_TEST_RMSE_COL]), axis=1))
+    Cw = res["column_factor"]
+    suffix = f"_rank{rank}" if world > 1 else ""
+    K, p_loc = Cw.shape
+    budget = (DUMP_BUDGET_BYTES - (1 << 20)) // world          # 1 MB kept for the row factors and the trajectory
+    if 8 * K * p_loc <= budget:
+        save("column_factor" + suffix, Cw)
+    else:
+        # the sample is drawn over ALL genes and each rank keeps the part in its slab: one set of genes for any N
+        genes = np.sort(np.random.Generator(np.random.PCG64(DUMP_SAMPLE_SEED)).choice(
+            p_total, size=min(p_total, (DUMP_BUDGET_BYTES - (1 << 20)) // (8 * (K + 1))), replace=False))
+        genes = genes[(genes >= lo) & (genes < lo + p_loc)]
+        save("column_factor" + suffix, Cw[:, genes - lo])
+        save("column_factor_genes" + suffix, genes)
+    return files
 
 
 def host_cores():
@@ -295,7 +345,9 @@ def main():
         else:
             dist.init_process_group("nccl", device_id=torch.device("cuda", local_rank))
     import __graft_entry__ as ge
-    if rank == 0:
+    from insider_amd import _build
+    # build only a stale or missing library: the bench may run from a built tree its user cannot write to
+    if rank == 0 and _build.needs_build():
         ge.build()
     if world > 1:
         dist.barrier()
@@ -367,6 +419,7 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     assert res["iters"] == args.steps, (res["iters"], args.steps)
+    dumped = dump_outputs(args.dump_outputs, res, lo, p_total, rank, world, tuning) if args.dump_outputs else None
 
     def copy_bandwidth():
         """Device-to-device copy of 2 GiB (read + write counted), best of 5: what this box's HBM delivers to a plain copy,
@@ -542,6 +595,8 @@ def main():
             "library_source_sha": lib_sha, "sources_on_disk_sha": source_sha(),
             "setup_s": {"generate": t_gen, "upload_and_precompute": t_up},
         }
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "float64_shapes_rank0": dumped}
         if world > 1:      # the same problem on ONE GPU, from this repository's own single-GPU run (not measured in this job)
             try:
                 sj = json.load(open(os.path.join(ROOT, "profiles", "single_gpu.json")))

@@ -58,6 +58,8 @@ def needs_build(path=HIP_LIB):
 def build_library(force=False, extra_flags=(), out=HIP_LIB):
     """Compile the library for gfx950 (hipcc cross-compiles without a GPU).  Serialised across processes by a file lock:
     several ranks / test workers may find the same stale binary at once."""
+    if not force and not extra_flags and library_sha(out) == source_sha():
+        return False      # up to date: nothing is written, so a tree its user cannot write to still runs
     lock = open(os.path.join(_HERE, ".build.lock"), "w")      # (git-ignored: a runtime artefact)
     fcntl.flock(lock, fcntl.LOCK_EX)
     try:

@@ -59,10 +59,10 @@ def load():
     if not os.path.exists(LIB_PATH):
         raise InsiderError(ERR_NO_DEVICE, f"{LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; "
                                           f"g.build()'` (there is no CPU fallback)")
-    # Concurrent fits on one GPU (insider_hip_clone, tune(concurrent=k)) need their streams on DIFFERENT hardware queues: the
-    # HIP runtime multiplexes all streams of a process onto GPU_MAX_HW_QUEUES queues (default 4), and two fits whose main
-    # streams share a queue run one after the other.  Read by the runtime when it initialises: set before the first HIP call.
-    os.environ.setdefault("GPU_MAX_HW_QUEUES", "32")
+    # Concurrent fits on one GPU (insider_hip_clone, tune(concurrent=k)) overlap only as far as their streams land on
+    # DIFFERENT hardware queues: the HIP runtime multiplexes all streams of a process onto a fixed number of queues, and two
+    # fits whose main streams share a queue run one after the other.  That number belongs to the host's configuration; the
+    # library does not change it.
     lib = C.CDLL(LIB_PATH)
     dp, i32p, u8p = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_uint8)
     lib.insider_hip_version.restype = C.c_char_p

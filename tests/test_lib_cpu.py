@@ -270,3 +270,21 @@ def test_library_carries_the_hash_of_its_sources_and_a_stale_one_is_detected(tmp
     # a newer mtime on an up-to-date library changes nothing (the old rule would have trusted / distrusted it by time)
     os.utime(_build.HIP_LIB, None)
     assert not _build.needs_build()
+
+
+def test_build_of_a_current_tree_writes_nothing(lib, monkeypatch):
+    """build() and bench.py run from a built tree whose user may not write to it: with the library current, the build step
+    opens no file for writing (the build lock included)."""
+    import builtins
+    from insider_amd import _build
+    real_open = builtins.open
+
+    def read_only_open(path, mode="r", *a, **k):
+        if str(path).startswith(ROOT) and any(c in mode for c in "wax+"):
+            raise PermissionError(f"write to {path} in a current tree")
+        return real_open(path, mode, *a, **k)
+
+    monkeypatch.setattr(builtins, "open", read_only_open)
+    assert not _build.needs_build()
+    assert _build.build_library() is False
+    ge.build()

@@ -7,7 +7,6 @@ TAG=${1:-r05}
 R=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
-export GPU_MAX_HW_QUEUES=32
 cd /tmp && export TMPDIR=/tmp
 python3 -c "import sys; sys.path.insert(0, '$R'); import __graft_entry__ as g; g.build()" || exit 1
 B="python3 $R/bench.py"
@@ -27,7 +26,7 @@ python3 tools/iter_timeline.py $OUT/prof_c3 6 > $OUT/c3_steady_iteration_timelin
 python3 tools/trace_avg.py $OUT/prof_c3 > $OUT/c3_trace_avg.txt 2>&1
 python3 tools/slab_c4_probe.py 8 2>&1 | tail -1 > $OUT/slab8.log; cat $OUT/slab8.log
 bash tools/slab_trace.sh 0 > $OUT/slab8_timeline.txt 2>&1; tail -1 $OUT/slab8_timeline.txt
-bash tools/conc_probe.sh c1 6 32 2>&1 | tee $OUT/concurrent_grids.log
-bash tools/conc_probe.sh c2 4 32 2>&1 | tee -a $OUT/concurrent_grids.log
-bash tools/conc_probe.sh c3 2 32 2>&1 | tee -a $OUT/concurrent_grids.log
+bash tools/conc_probe.sh c1 6 2>&1 | tee $OUT/concurrent_grids.log
+bash tools/conc_probe.sh c2 4 2>&1 | tee -a $OUT/concurrent_grids.log
+bash tools/conc_probe.sh c3 2 2>&1 | tee -a $OUT/concurrent_grids.log
 echo PROFILE_DONE

@@ -28,7 +28,6 @@ import time
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "32")
 import __graft_entry__ as ge  # noqa: E402
 
 ge.build()

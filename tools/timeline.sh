@@ -6,7 +6,6 @@ LBL=$1; shift
 R=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$R/gpurun_out/${INSIDER_TAG:-r05}
 mkdir -p $OUT
-export GPU_MAX_HW_QUEUES=32
 cd /tmp && export TMPDIR=/tmp
 rm -rf $OUT/tl_$LBL
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/tl_$LBL -- python3 $R/bench.py --no-cpu-baseline "$@" > $OUT/tl_$LBL.json 2> $OUT/tl_$LBL.err || { tail -5 $OUT/tl_$LBL.err; exit 1; }
