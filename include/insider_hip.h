@@ -148,7 +148,8 @@ int insider_hip_comm_init(insider_hip_handle *h, const void *unique_id, int rank
  * the same steps in the same order — bit-identical iterates; 0 = one step per block), "cd_pass1" / "cd_pass_ratio" / "cd_cold_iters" (multi-pass column solves in the first
  * cd_cold_iters outer iterations of a call [default 3]: the register-resident sweep kernel stops at sweep cd_pass1 [64; 0 = one
  * pass], cd_pass1 x ratio [4], ..., re-packing the genes still running by their estimated remaining length between passes;
- * the iterates are bit-identical to the single-pass solve). */
+ * the iterates are bit-identical to the single-pass solve), "resid_stage_mb" (size in MB of the device buffer
+ * insider_hip_residual() copies the residual out through, default 256; at least 16 genes of the window). */
 int insider_hip_set_option(insider_hip_handle *h, const char *name, double value);
 
 /*
@@ -271,6 +272,36 @@ int insider_hip_optimize_continuous_v2(const double *data, int64_t n, int64_t p,
  */
 int insider_hip_masked_gram_cols(insider_hip_handle *h, const double *R, int K, double *G_out, double *q_out);
 int insider_hip_masked_gram_rows(insider_hip_handle *h, const double *C, int K, double *H_out, double *b_out);
+
+/*
+ * glm_interaction() (R/glm_interaction.R:2-30) on the resident data set: per-level coefficients and standard errors of
+ * interaction effects on the metagenes, without the residual matrix ever leaving the device.
+ *   Covariate blocks are numbered 0..c-1 (the categorical covariates) and, with inc_continuous = 1, c (the continuous
+ *   block): the order of A in insider_hip_optimize().  subtract holds one int32 flag per block (c + inc_continuous).
+ *   The residual is r_ij = X_ij - (sum_{b: subtract[b] != 0} u_b(i)) C[:, j] with u_b(i) = A_b[level_b(i)] for a
+ *   categorical block and u_c(i) = z_i B for the continuous one.  X is the handle's matrix as given to
+ *   insider_hip_create[_ex]: every entry, whatever the masks say (glm_interaction ignores train_indicator).
+ * insider_hip_residual — residual rows [row_begin, row_end) of X, written column-major ((row_end - row_begin) x p, leading
+ *   dimension row_end - row_begin) to host `out`.  The rows stream through a device buffer of option "resid_stage_mb"
+ *   (default 256) in slabs of genes.
+ * insider_hip_interaction_glm — group is an int32 vector of n ids in 0..G (0 = the sample is in no group; anything else:
+ *   INSIDER_ERR_ARG).  For every group g with m_g samples: G = C C', beta_g = G^-1 C mean_{i in g}(r_i),
+ *   RSS_g = sum_{i in g} ||r_i - C' beta_g||^2, dof_g = m_g p - rank, se_g = sqrt(RSS_g / dof_g diag(G^-1) / m_g).
+ *   coeff and se are G x K column-major (row g-1 for id g, like the factors), dof has G entries.  A group without samples
+ *   gives zero rows and dof 0.  A latent dimension whose row of C is exactly zero is dropped from G (rank counts the
+ *   others) and its coefficient and standard error are NaN (R's glm reports NA); any other pivot of the Cholesky
+ *   factorisation of the reduced G that is not larger than rank x machine epsilon times its diagonal entry returns
+ *   INSIDER_ERR_SOLVE.  p-values are left to the caller: 2 P(T_dof > |coeff / se|).
+ * Both work on any handle (clones included), on the handle's main stream, with a workspace of their own (allocated on first
+ * use, freed by insider_hip_destroy): nothing insider_hip_optimize() reads is touched, and an optimize() after them is
+ * bit-identical to one without.  K is bounded as in insider_hip_optimize() (1..63).  A sharded handle (world > 1) returns
+ * INSIDER_ERR_UNSUPPORTED.
+ */
+int insider_hip_residual(insider_hip_handle *h, double *const *A, const double *C, int inc_continuous, int K,
+                         const int32_t *subtract, int64_t row_begin, int64_t row_end, double *out);
+int insider_hip_interaction_glm(insider_hip_handle *h, double *const *A, const double *C, int inc_continuous, int K,
+                                const int32_t *subtract, const int32_t *group, int G, double *coeff, double *se,
+                                double *dof);
 
 /* Profile of the last insider_hip_optimize() call (option "profile" = 1), HIP-event timed on the library's stream.
  * out[0..11]: {column-side masked-Gram launches, total ms, row-side masked-Gram launches, total ms,

@@ -162,6 +162,64 @@ class InsiderData:
                     train_rmse=tr.value, test_rmse=te.value, loss=lo.value, traj=traj[: rows.value].copy(),
                     iters=iters.value)
 
+    def _posthoc_args(self, cfd_factors, column_factor, subtract, inc_continuous):
+        """K, the marshalled factors and the int32 subtract flags of the post-hoc calls (ERR_ARG on any mismatch)."""
+        if inc_continuous not in (0, 1):
+            raise InsiderError(_lib.ERR_ARG, "The value of prarameter inc_continuous can only be 0 or 1.")
+        K = int(np.asarray(column_factor).shape[0])
+        nb = self.c + int(inc_continuous)
+        sub = np.ones(nb, dtype=np.int32) if subtract is None else np.asarray(subtract).ravel()
+        if sub.shape != (nb,):
+            raise InsiderError(_lib.ERR_ARG, f"subtract must hold one flag per covariate block ({nb}), got {sub.size}")
+        sub = np.ascontiguousarray(sub != 0, dtype=np.int32)
+        A, Cw, Aptrs = self._marshal(cfd_factors, column_factor, K, inc_continuous)
+        return K, A, Cw, Aptrs, sub
+
+    def residual(self, cfd_factors, column_factor, subtract=None, rows=None, inc_continuous=0):
+        """Residual rows of the resident X minus the contributions of the covariate blocks flagged in ``subtract``
+        (insider_hip_residual; None = every block): an (rows) x p array.  ``rows`` = (begin, end) or a slice (default: all)."""
+        K, A, Cw, Aptrs, sub = self._posthoc_args(cfd_factors, column_factor, subtract, inc_continuous)
+        if rows is None:
+            rb, re_ = 0, self.n
+        elif isinstance(rows, slice):
+            if rows.step not in (None, 1):
+                raise InsiderError(_lib.ERR_ARG, "rows must be a contiguous window")
+            rb, re_, _ = rows.indices(self.n)
+        else:
+            rb, re_ = (int(v) for v in rows)
+        if not 0 <= rb <= re_ <= self.n:
+            raise InsiderError(_lib.ERR_ARG, f"rows must satisfy 0 <= begin <= end <= n = {self.n}")
+        out = np.empty((re_ - rb, self.p), dtype=np.float64, order="F")
+        _lib.check(_lib.load().insider_hip_residual(self._h, Aptrs, _lib.ptr(Cw), int(inc_continuous), K,
+                                                    _lib.ptr(sub, C.c_int32), rb, re_, _lib.ptr(out)))
+        return out
+
+    def interaction_glm(self, cfd_factors, column_factor, group, subtract=None, inc_continuous=0, n_groups=None):
+        """glm_interaction() on the resident data set (insider_hip_interaction_glm): ``group`` holds n ids in 0..G (0 = in
+        no group; G = ``n_groups``, default the largest id).  Returns (coeff, se, dof): G x K, G x K and G, row g-1 for id g;
+        empty groups give zero rows, latent dimensions whose row of C is zero give NaN columns."""
+        K, A, Cw, Aptrs, sub = self._posthoc_args(cfd_factors, column_factor, subtract, inc_continuous)
+        grp = np.asarray(group).ravel()
+        if grp.shape != (self.n,):
+            raise InsiderError(_lib.ERR_ARG, f"group must hold n = {self.n} ids")
+        if not np.issubdtype(grp.dtype, np.integer):
+            if not np.all(np.isfinite(grp)) or not np.array_equal(grp, np.round(grp)):
+                raise InsiderError(_lib.ERR_ARG, "group ids must be integers")
+        grp = np.ascontiguousarray(grp, dtype=np.int64)
+        G = int(grp.max(initial=0)) if n_groups is None else int(n_groups)
+        if G < 1:
+            raise InsiderError(_lib.ERR_ARG, "at least one group id must be positive")
+        if grp.min(initial=0) < 0 or grp.max(initial=0) > G:
+            raise InsiderError(_lib.ERR_ARG, f"group ids must be within 0..{G}")
+        grp = grp.astype(np.int32)
+        coeff = np.empty((G, K), dtype=np.float64, order="F")
+        se = np.empty((G, K), dtype=np.float64, order="F")
+        dof = np.empty(G, dtype=np.float64)
+        _lib.check(_lib.load().insider_hip_interaction_glm(self._h, Aptrs, _lib.ptr(Cw), int(inc_continuous), K,
+                                                           _lib.ptr(sub, C.c_int32), _lib.ptr(grp, C.c_int32), G,
+                                                           _lib.ptr(coeff), _lib.ptr(se), _lib.ptr(dof)))
+        return coeff, se, dof
+
     def masked_gram_cols(self, R):
         R = _lib.f64(R)
         K = R.shape[1]

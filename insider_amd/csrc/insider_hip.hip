@@ -6,6 +6,7 @@
 // dense kernels.  Everything is enqueued on one HIP stream; the host synchronises only at the reference's loss
 // checkpoints (every 10th iteration) and around the optional cross-rank all-reduce.
 #include "insider_kernels.hpp"
+#include "insider_posthoc.hpp"
 
 #include <rccl/rccl.h>
 
@@ -93,6 +94,10 @@ struct CovTables {   // per covariate, device
 
 
 }  // namespace
+
+// device workspace of the post-hoc calls (section "post-hoc interaction GLM")
+struct PostWs;
+void free_posthoc(PostWs *w);
 
 struct insider_hip_handle {
     int device = 0;
@@ -248,6 +253,10 @@ struct insider_hip_handle {
     // of the last optimize() / optimize_col(): genes whose elastic-net solve was ended by max_sweeps, not by convergence
     // (the reference has no cap, src/coordinate_descent.cpp:86-114), and the longest solve in sweeps
     int cap_hits = 0, max_gene_sweeps = 0;
+    // post-hoc interaction GLM / residual (insider_hip_residual, insider_hip_interaction_glm): a workspace of its own, so
+    // that nothing insider_hip_optimize() reads is touched; allocated on first use, grown on demand, freed with the handle
+    PostWs *post = nullptr;
+    double resid_stage_mb = 256.0;   // option "resid_stage_mb": size of the device buffer the residual is copied out through
 };
 
 namespace {
@@ -1735,6 +1744,8 @@ void insider_hip_destroy(insider_hip_handle *h)
     if (h->comm) { (void)ncclCommDestroy(h->comm); h->comm = nullptr; }
     clear_events(h);
     free_workspace(h);
+    free_posthoc(h->post);
+    h->post = nullptr;
     // the data set goes with its last user (insider_hip_clone shares it)
     if (!h->data_refs || h->data_refs->fetch_sub(1) == 1) {
         free_data_set(h);
@@ -1752,6 +1763,7 @@ int insider_hip_clone(insider_hip_handle *src, insider_hip_handle **out)
     HIPCHECK(hipSetDevice(src->device));
     insider_hip_handle *h = new insider_hip_handle(*src);   // every data-set field and option; the rest is reset below
     forget_workspace(h);                                    // (the copied pointers are the source's buffers)
+    h->post = nullptr;                                      // (likewise the post-hoc workspace)
     h->stream = h->side = h->side2 = h->side3 = h->lng = nullptr;
     h->ev_long_go = h->ev_long_done = h->ev_prep = h->ev_c_ready = h->ev_head = h->ev_a_ready = h->ev_qfull = h->ev_qheld = nullptr;
     h->ev_cd_done = h->ev_side_done = h->ev_tab = h->ev_q_early = nullptr;
@@ -2329,6 +2341,7 @@ int insider_hip_set_option(insider_hip_handle *h, const char *name, double value
     else if (s == "cd_pairs") h->cd_pairs = (int)value;           // 1 (default) = sweeps routed through the blocks of two coordinate steps (K <= 30; same iterates), 0 = one step per block
     else if (s == "cd_split") h->cd_split = (int)value;           // 2 = steady-state column steps run split (long genes first, on their own stream); 0 (default) = never (measured: no gain, see use_split)
     else if (s == "cd_long_frac") h->cd_long_frac = value;        // at most this fraction of the genes counts as long (default 0.03)
+    else if (s == "resid_stage_mb") h->resid_stage_mb = value;   // device buffer insider_hip_residual() copies out through (MB; at least 16 genes of the window)
     else if (s == "cd_variant") h->cd_variant = (int)value;   // 0 = register-resident (4 genes per wave; K <= 32, and 32 < K <= 48 with the third slot's columns in LDS), 1 = group kernel, 2 = row16 (LDS, K <= 48)
     else return fail(INSIDER_ERR_ARG, "unknown option " + s);
     return INSIDER_OK;
@@ -3005,6 +3018,304 @@ int insider_hip_get_profile(insider_hip_handle *h, double *out12)
     if (!h || !out12) return fail(INSIDER_ERR_ARG, "null");
     for (int i = 0; i < 12; ++i) out12[i] = h->prof[i];
     return INSIDER_OK;
+}
+
+}  // extern "C"
+
+// =================================================================================================================
+// post-hoc interaction GLM (glm_interaction(), R/glm_interaction.R:2-30) on the resident data set: the residual of the
+// subtracted covariate blocks and the per-group regression on the column factor (kernels: insider_posthoc.hpp).  Own
+// workspace and the handle's main stream only: nothing insider_hip_optimize() reads is written.
+// =================================================================================================================
+struct PostWs {
+    struct Buf { void *p = nullptr; size_t bytes = 0; };
+    // Ast: stacked row factors (SL x KPW, blocks not subtracted zero); U: n x KPW; cp: p x KPW; nz: K flags;
+    // part: slab partials of the per-sample statistics; stats: n x (K + 1); stage: residual copy-out buffer;
+    // gpart / gram: C C'; ints: host-built group tables; cpart / gsum: group sums; L / dinv / info: the factor;
+    // outs: coeff, se, dof
+    Buf Ast, U, cp, nz, part, stats, stage, gpart, gram, ints, cpart, gsum, L, dinv, info, outs;
+};
+
+void free_posthoc(PostWs *w)
+{
+    if (!w) return;
+    for (PostWs::Buf *b : {&w->Ast, &w->U, &w->cp, &w->nz, &w->part, &w->stats, &w->stage, &w->gpart, &w->gram, &w->ints,
+                           &w->cpart, &w->gsum, &w->L, &w->dinv, &w->info, &w->outs})
+        if (b->p) (void)hipFree(b->p);
+    delete w;
+}
+
+namespace {
+
+template <typename T>
+int ph_grow(PostWs::Buf &b, size_t count, T **out)
+{
+    const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
+    if (b.bytes < bytes) {
+        if (b.p) (void)hipFree(b.p);
+        b.p = nullptr;
+        b.bytes = 0;
+        HIPCHECK(hipMalloc(&b.p, bytes));
+        b.bytes = bytes;
+    }
+    *out = static_cast<T *>(b.p);
+    return INSIDER_OK;
+}
+
+int ph_check(insider_hip_handle *h, double *const *A, const double *C, int inc_continuous, int K, const int32_t *subtract)
+{
+    if (!h) return fail(INSIDER_ERR_ARG, "null handle");
+    if (!A || !C || !subtract) return fail(INSIDER_ERR_ARG, "null argument");
+    if (K < 1 || K > INSIDER_MAX_K) return fail(INSIDER_ERR_UNSUPPORTED, "K must be in 1..63");
+    if (inc_continuous != 0 && inc_continuous != 1)
+        return fail(INSIDER_ERR_ARG, "The value of prarameter inc_continuous can only be 0 or 1.");
+    if (inc_continuous == 1 && h->m == 0)
+        return fail(INSIDER_ERR_ARG, "inc_continuous = 1 needs a handle created with ctns_confounder (insider_hip_create_ex)");
+    if (inc_continuous == 0 && h->m > 0)
+        return fail(INSIDER_ERR_ARG, "this handle carries continuous covariates: pass inc_continuous = 1");
+    if (h->world > 1)
+        return fail(INSIDER_ERR_UNSUPPORTED, "the post-hoc calls need the whole matrix: not available on a sharded handle "
+                                             "(world > 1)");
+    for (int b = 0; b < h->c + inc_continuous; ++b)
+        if (subtract[b] && !A[b]) return fail(INSIDER_ERR_ARG, "null row factor of a subtracted block");
+    return INSIDER_OK;
+}
+
+// U (n x KPW) = the sum of the subtracted blocks' contributions, and C in the kernels' layout (cp, nz)
+int ph_prepare(insider_hip_handle *h, double *const *A, const double *C, int K, const int32_t *subtract, int KPW)
+{
+    if (!h->post) h->post = new PostWs();
+    PostWs &w = *h->post;
+    hipStream_t st = h->stream;
+    double *Ast = nullptr, *U = nullptr, *cp = nullptr, *tmp = nullptr;
+    int *nz = nullptr;
+    int rc;
+    if ((rc = ph_grow(w.Ast, (size_t)h->SL * KPW, &Ast))) return rc;
+    if ((rc = ph_grow(w.U, (size_t)h->n * KPW, &U))) return rc;
+    if ((rc = ph_grow(w.cp, (size_t)h->p * KPW, &cp))) return rc;
+    if ((rc = ph_grow(w.nz, 64, &nz))) return rc;
+    // the host factors go through the residual stage buffer (at least p K doubles)
+    if ((rc = ph_grow(w.stage, std::max<size_t>((size_t)h->p * K, (size_t)std::max(h->max_L, h->m) * K), &tmp))) return rc;
+    HIPCHECK(hipMemsetAsync(Ast, 0, (size_t)h->SL * KPW * sizeof(double), st));
+    for (int b = 0; b < h->c + (h->m > 0 ? 1 : 0); ++b) {
+        if (!subtract[b]) continue;
+        const int L = b < h->c ? h->n_levels[b] : h->m;
+        const int off = b < h->c ? h->lvl_off[b] : h->SLcat;
+        HIPCHECK(hipMemcpyAsync(tmp, A[b], (size_t)L * K * sizeof(double), hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_pack_A, dim3(cdiv((int64_t)L * KPW, 256)), dim3(256), 0, st, (const double *)tmp, L, K, KPW,
+                           Ast + (size_t)off * KPW);
+        KCHECK();
+        HIPCHECK(hipStreamSynchronize(st));   // tmp is reused
+    }
+    hipLaunchKernelGGL(k_build_R, dim3(cdiv(h->n * KPW, 256)), dim3(256), 0, st, (const int *)h->lev,
+                       (const int *)h->lvl_off_d, h->c, (int)h->n, (const double *)Ast, KPW, (const double *)h->Zc, h->m,
+                       h->SLcat, U);
+    KCHECK();
+    HIPCHECK(hipMemcpyAsync(tmp, C, (size_t)h->p * K * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHECK(hipMemsetAsync(nz, 0, 64 * sizeof(int), st));
+    hipLaunchKernelGGL(k_ph_pack_c, dim3(cdiv(h->p * KPW, 256)), dim3(256), 0, st, (const double *)tmp, h->p, K, KPW, cp, nz);
+    KCHECK();
+    HIPCHECK(hipStreamSynchronize(st));   // the stage buffer is free again
+    return INSIDER_OK;
+}
+
+#define PH_DISPATCH(NBV, ...)                                                            \
+    switch (NBV) {                                                                       \
+        case 1: { constexpr int NB_ = 1; constexpr int GT_ = 8; __VA_ARGS__; } break;    \
+        case 2: { constexpr int NB_ = 2; constexpr int GT_ = 4; __VA_ARGS__; } break;    \
+        case 3: { constexpr int NB_ = 3; constexpr int GT_ = 2; __VA_ARGS__; } break;    \
+        default: { constexpr int NB_ = 4; constexpr int GT_ = 2; __VA_ARGS__; } break;   \
+    }
+
+int residual_body(insider_hip_handle *h, double *const *A, const double *C, int inc_continuous, int K,
+                  const int32_t *subtract, int64_t row_begin, int64_t row_end, double *out)
+{
+    int rc = ph_check(h, A, C, inc_continuous, K, subtract);
+    if (rc) return rc;
+    if (row_begin < 0 || row_end > h->n || row_begin > row_end)
+        return fail(INSIDER_ERR_ARG, "rows must satisfy 0 <= row_begin <= row_end <= n");
+    const int64_t nrows = row_end - row_begin;
+    if (nrows == 0) return INSIDER_OK;
+    if (!out) return fail(INSIDER_ERR_ARG, "null output");
+    HIPCHECK(hipSetDevice(h->device));
+    const int NB = (K + 15) / 16, KPW = 16 * NB;
+    if ((rc = ph_prepare(h, A, C, K, subtract, KPW))) return rc;
+    // gene slabs of the window that fit the stage buffer (multiples of 16 genes, at least one tile)
+    const double cap = std::max(h->resid_stage_mb, 0.0) * 1048576.0;
+    int64_t gw = (int64_t)(cap / (8.0 * (double)nrows)) / 16 * 16;
+    gw = std::max<int64_t>(16, std::min<int64_t>(gw, round_up(h->p, 16)));
+    double *stage = nullptr;
+    if ((rc = ph_grow(h->post->stage, (size_t)nrows * gw, &stage))) return rc;
+    const double *U = static_cast<const double *>(h->post->U.p), *cp = static_cast<const double *>(h->post->cp.p);
+    const int row_blocks = cdiv(cdiv(nrows, 16), PH_WPB);
+    for (int64_t jb = 0; jb < h->p; jb += gw) {
+        const int64_t je = std::min<int64_t>(jb + gw, h->p);
+        PH_DISPATCH(NB, {
+            const size_t lds = (size_t)GT_ * 4 * NB_ * 64 * sizeof(double);
+            hipLaunchKernelGGL((k_resid_write<NB_, GT_>), dim3(row_blocks, cdiv(je - jb, 16 * GT_)), dim3(64 * PH_WPB), lds,
+                               h->stream, (const double *)h->X, h->ldn, row_begin, row_end, U, cp, K, jb, je, stage, nrows);
+        });
+        KCHECK();
+        HIPCHECK(hipMemcpyAsync(out + jb * nrows, stage, (size_t)nrows * (je - jb) * sizeof(double), hipMemcpyDeviceToHost,
+                                h->stream));
+        HIPCHECK(hipStreamSynchronize(h->stream));
+    }
+    return INSIDER_OK;
+}
+
+int interaction_glm_body(insider_hip_handle *h, double *const *A, const double *C, int inc_continuous, int K,
+                         const int32_t *subtract, const int32_t *group, int G, double *coeff, double *se, double *dof)
+{
+    int rc = ph_check(h, A, C, inc_continuous, K, subtract);
+    if (rc) return rc;
+    if (!group || !coeff || !se || !dof) return fail(INSIDER_ERR_ARG, "null argument");
+    if (G < 1) return fail(INSIDER_ERR_ARG, "G must be positive");
+    const int64_t n = h->n, p = h->p;
+    // group tables on the host: members by group (sample order inside a group), chunks of <= PH_CHUNK members
+    std::vector<int> cnt((size_t)G + 1, 0);
+    for (int64_t i = 0; i < n; ++i) {
+        const int32_t gi = group[i];
+        if (gi < 0 || gi > G) return fail(INSIDER_ERR_ARG, "group ids must be within 0..G");
+        cnt[gi]++;
+    }
+    std::vector<int> gptr((size_t)G + 1, 0);   // members of group id g + 1 (id 0 is no group)
+    for (int g = 0; g < G; ++g) gptr[g + 1] = gptr[g] + cnt[g + 1];
+    const int nmem = gptr[G];
+    std::vector<int> members(std::max(nmem, 1)), fill(gptr.begin(), gptr.end() - 1);
+    for (int64_t i = 0; i < n; ++i)
+        if (group[i] > 0) members[fill[group[i] - 1]++] = (int)i;
+    std::vector<int> ch_begin, ch_end, grp_chunk((size_t)G + 1, 0);
+    for (int g = 0; g < G; ++g) {
+        grp_chunk[g] = (int)ch_begin.size();
+        for (int b = gptr[g]; b < gptr[g + 1]; b += PH_CHUNK) {
+            ch_begin.push_back(b);
+            ch_end.push_back(std::min(b + PH_CHUNK, gptr[g + 1]));
+        }
+    }
+    grp_chunk[G] = (int)ch_begin.size();
+    const int nchunks = grp_chunk[G];
+    HIPCHECK(hipSetDevice(h->device));
+    const int NB = (K + 15) / 16, KPW = 16 * NB, ldw = K + 1;
+    if ((rc = ph_prepare(h, A, C, K, subtract, KPW))) return rc;
+    PostWs &w = *h->post;
+    hipStream_t st = h->stream;
+    // ---- one pass over X: per-sample w = C r and ss = ||r||^2, gene slabs summed in slab order ----------------------
+    const int ntiles = cdiv(n, 16), row_blocks = cdiv(ntiles, PH_WPB);
+    int64_t slab_len = 0;
+    int slabs = 1;
+    double *part = nullptr, *stats = nullptr;
+    PH_DISPATCH(NB, {
+        // enough blocks for every SIMD of the device several times over, slabs of whole staging rounds
+        const int want = std::max(1, std::min(64, cdiv(4 * h->n_simd, (int64_t)row_blocks * PH_WPB)));
+        slab_len = round_up(cdiv(p, want), 16 * GT_);
+        slabs = cdiv(p, slab_len);
+    });
+    if ((rc = ph_grow(w.part, (size_t)slabs * n * ldw, &part))) return rc;
+    if ((rc = ph_grow(w.stats, (size_t)n * ldw, &stats))) return rc;
+    const double *U = static_cast<const double *>(w.U.p), *cp = static_cast<const double *>(w.cp.p);
+    PH_DISPATCH(NB, {
+        const size_t lds = (size_t)2 * GT_ * 4 * NB_ * 64 * sizeof(double);
+        hipLaunchKernelGGL((k_resid_stats<NB_, GT_>), dim3(row_blocks, slabs), dim3(64 * PH_WPB), lds, st,
+                           (const double *)h->X, h->ldn, (int)n, p, U, cp, K, slab_len, part);
+    });
+    KCHECK();
+    hipLaunchKernelGGL(k_sum_partials, dim3(cdiv(n * ldw, 16)), dim3(256), 0, st, (const double *)part, slabs,
+                       (int)(n * ldw), stats);
+    KCHECK();
+    // ---- per-group sums -----------------------------------------------------------------------------------------------
+    int *ints = nullptr;
+    const size_t n_ints = (size_t)(G + 1) + members.size() + 2 * std::max(nchunks, 1) + (size_t)(G + 1);
+    if ((rc = ph_grow(w.ints, n_ints, &ints))) return rc;
+    int *d_gptr = ints, *d_mem = d_gptr + (G + 1), *d_cb = d_mem + members.size(), *d_ce = d_cb + std::max(nchunks, 1),
+        *d_gc = d_ce + std::max(nchunks, 1);
+    std::vector<int> packed;
+    packed.reserve(n_ints);
+    packed.insert(packed.end(), gptr.begin(), gptr.end());
+    packed.insert(packed.end(), members.begin(), members.end());
+    ch_begin.resize(std::max(nchunks, 1), 0);
+    ch_end.resize(std::max(nchunks, 1), 0);
+    packed.insert(packed.end(), ch_begin.begin(), ch_begin.end());
+    packed.insert(packed.end(), ch_end.begin(), ch_end.end());
+    packed.insert(packed.end(), grp_chunk.begin(), grp_chunk.end());
+    HIPCHECK(hipMemcpyAsync(ints, packed.data(), packed.size() * sizeof(int), hipMemcpyHostToDevice, st));
+    double *cpart = nullptr, *gsum = nullptr;
+    if ((rc = ph_grow(w.cpart, (size_t)std::max(nchunks, 1) * ldw, &cpart))) return rc;
+    if ((rc = ph_grow(w.gsum, (size_t)G * ldw, &gsum))) return rc;
+    if (nchunks > 0) {
+        hipLaunchKernelGGL(k_ph_chunk_sums, dim3(cdiv(nchunks, 4)), dim3(256), 0, st, (const double *)stats, ldw,
+                           (const int *)d_mem, (const int *)d_cb, (const int *)d_ce, nchunks, cpart);
+        KCHECK();
+    }
+    hipLaunchKernelGGL(k_ph_group_sums, dim3(G), dim3(256), 0, st, (const double *)cpart, ldw, (const int *)d_gc, gsum);
+    KCHECK();
+    // ---- G = C C', its reduced Cholesky factor, and every group's coefficients ------------------------------------------
+    const int gslabs = cdiv(p, MM_SLAB);
+    double *gpart = nullptr, *gram = nullptr, *L = nullptr, *dinv = nullptr, *outs = nullptr;
+    int *info = nullptr;
+    if ((rc = ph_grow(w.gpart, (size_t)gslabs * K * K, &gpart))) return rc;
+    if ((rc = ph_grow(w.gram, (size_t)K * K, &gram))) return rc;
+    if ((rc = ph_grow(w.L, (size_t)64 * 64, &L))) return rc;
+    if ((rc = ph_grow(w.dinv, 64, &dinv))) return rc;
+    if ((rc = ph_grow(w.info, 2 + 64, &info))) return rc;
+    if ((rc = ph_grow(w.outs, (size_t)2 * G * K + G, &outs))) return rc;
+    PH_DISPATCH(NB, {
+        (void)GT_;
+        hipLaunchKernelGGL((k_mm_reduce<NB_>), dim3(gslabs, cdiv(K, 16)), dim3(64), 0, st, cp, (int64_t)KPW, cp,
+                           (int64_t)KPW, (int)p, MM_SLAB, K, K, gpart, K);
+    });
+    KCHECK();
+    hipLaunchKernelGGL(k_sum_partials, dim3(cdiv(K * K, 16)), dim3(256), 0, st, (const double *)gpart, gslabs, K * K, gram);
+    KCHECK();
+    hipLaunchKernelGGL(k_glm_factor, dim3(1), dim3(64), 0, st, (const double *)gram, (const int *)w.nz.p, K, L, dinv, info);
+    KCHECK();
+    double *d_coeff = outs, *d_se = outs + (size_t)G * K, *d_dof = outs + (size_t)2 * G * K;
+    hipLaunchKernelGGL(k_glm_groups, dim3(G), dim3(64), 0, st, (const double *)gsum, ldw, (const int *)d_gptr, K, p,
+                       (const int *)w.nz.p, (const double *)L, (const double *)dinv, (const int *)info, G, d_coeff, d_se,
+                       d_dof);
+    KCHECK();
+    int hinfo[2] = {0, 0};
+    HIPCHECK(hipMemcpyAsync(hinfo, info, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipStreamSynchronize(st));
+    if (hinfo[0])
+        return fail(INSIDER_ERR_SOLVE, "insider_hip_interaction_glm: C C' restricted to the non-zero rows of C is singular to "
+                                       "working precision (pivot " + std::to_string(hinfo[0]) + " of " +
+                                       std::to_string(hinfo[1]) + "): the column factor has linearly dependent rows");
+    HIPCHECK(hipMemcpyAsync(coeff, d_coeff, (size_t)G * K * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipMemcpyAsync(se, d_se, (size_t)G * K * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipMemcpyAsync(dof, d_dof, (size_t)G * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipStreamSynchronize(st));
+    return INSIDER_OK;
+}
+
+// a failed call may leave work enqueued: drain the stream so that the next call starts clean
+int ph_finish(insider_hip_handle *h, int rc)
+{
+    if (rc != INSIDER_OK && h && h->stream) {
+        const std::string keep = g_err;
+        (void)hipSetDevice(h->device);
+        (void)hipStreamSynchronize(h->stream);
+        g_err = keep;
+    }
+    return rc;
+}
+
+#undef PH_DISPATCH
+
+}  // namespace
+
+extern "C" {
+
+int insider_hip_residual(insider_hip_handle *h, double *const *A, const double *C, int inc_continuous, int K,
+                         const int32_t *subtract, int64_t row_begin, int64_t row_end, double *out)
+{
+    return ph_finish(h, residual_body(h, A, C, inc_continuous, K, subtract, row_begin, row_end, out));
+}
+
+int insider_hip_interaction_glm(insider_hip_handle *h, double *const *A, const double *C, int inc_continuous, int K,
+                                const int32_t *subtract, const int32_t *group, int G, double *coeff, double *se,
+                                double *dof)
+{
+    return ph_finish(h, interaction_glm_body(h, A, C, inc_continuous, K, subtract, group, G, coeff, se, dof));
 }
 
 }  // extern "C"

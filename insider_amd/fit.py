@@ -4,11 +4,13 @@
     python -m insider_amd.fit --x X.npy --levels L.npy [--train-mask M.npy --test-mask T.npy] [--ctns Z.npy]
         --rank K --lambda 5 --alpha 0.4 [--partition 0|1] [--max-iter N] [--out DIR] [--out-format npy|flat]
     ... --tune --ranks 10 12 14 --lambdas 1 3 5 --alphas 0.2 0.4   # tune()'s rank sweep + lambda x alpha grid
+    ... --interaction 1 2 --interaction-glm 1   # then glm_interaction() on the device for covariate column 1 (0-based)
 
 Semantics are those of insider_amd.api (the mirror of R/insider.R): with masks given, `--partition 1` fits on the
 train entries (optimize(tuning = 1)) and reports the test RMSE; without masks (or `--partition 0`) every non-NA entry is
 used (fit()'s default, R/insider.R:190-216; NaN entries of X are the NA set).  Inits are N(0, 0.001^2)
-(R/utils.R:40-43) from --seed.  Output: A<i> (L_i x K), C (K x p) and result.json {train_rmse, test_rmse, loss,
+(R/utils.R:40-43) from --seed.  --interaction-glm COV adds interaction_coeff / interaction_pval (L_COV x K, glm_interaction()
+on the device against the residual of every other block).  Output: A<i> (L_i x K), C (K x p) and result.json {train_rmse, test_rmse, loss,
 iters, traj} in --out.  There is no CPU fallback: without a visible MI355X the command fails with the library's status.
 """
 import argparse
@@ -48,6 +50,10 @@ def parse(argv=None):
     ap.add_argument("--split-ratio", type=float, default=0.1)
     ap.add_argument("--out", default="insider_fit_out")
     ap.add_argument("--out-format", choices=("npy", "flat"), default=None)
+    ap.add_argument("--interaction-glm", type=int, default=None, metavar="COV",
+                    help="after the fit, glm_interaction() on the device for the levels of covariate column COV (0-based, "
+                         "after --interaction: its indicator is column 1) against the residual of every other block; "
+                         "writes interaction_coeff / interaction_pval (L x K) next to the factors")
     a = ap.parse_args(argv)
     if not a.flat and not (a.x and a.levels):
         ap.error("give --flat DIR or --x and --levels")
@@ -109,6 +115,7 @@ def main(argv=None):
     if partition == 0:                                                    # R/insider.R:207-208: train + test, "test" = NA
         tr, te = np.asfortranarray((tr | te) & ~na, dtype=np.uint8), np.asfortranarray(na, dtype=np.uint8)
     ds = api.InsiderData(X, lev, tr, te, device=a.device, ctns_confounder=Z)
+    ds_levels = np.asarray(lev, dtype=np.int32).reshape(n, -1)
     rng = np.random.default_rng(a.seed)
     K = a.rank
     A0 = [np.asfortranarray(api.init_parameters(int(L) * K, rng=rng).reshape((-1, K), order="F")) for L in ds.n_levels]
@@ -117,11 +124,28 @@ def main(argv=None):
     C0 = np.asfortranarray(api.init_parameters(K * p, rng=rng).reshape((K, -1), order="F"))
     res = ds.optimize(A0, C0, K, a.lam, a.lam, a.alpha, tuning=partition, global_tol=a.global_tol, sub_tol=a.sub_tol,
                       max_iter=a.max_iter, seed=a.seed, inc_continuous=1 if Z is not None else 0)
+    glm = None
+    if a.interaction_glm is not None:
+        from .posthoc import t_pvalues
+        cov = a.interaction_glm
+        if not 0 <= cov < ds.c:
+            raise SystemExit(f"--interaction-glm: COV must be in 0..{ds.c - 1}")
+        rows = list(res["row_matrices"].values())
+        coeff, se, dof = ds.interaction_glm(rows, res["column_factor"], ds_levels[:, cov],
+                                            subtract=[b != cov for b in range(len(rows))],
+                                            inc_continuous=1 if Z is not None else 0, n_groups=int(ds.n_levels[cov]))
+        glm = (coeff, t_pvalues(coeff, se, dof))
     ds.close()
     summary = dict(train_rmse=res["train_rmse"], test_rmse=None if np.isnan(res["test_rmse"]) else res["test_rmse"],
                    loss=res["loss"], iters=res["iters"], rank=K, **{"lambda": a.lam}, alpha=a.alpha, partition=partition,
                    n=n, p=p, n_levels=[int(v) for v in ds.n_levels], traj=np.where(np.isnan(res["traj"]), None, res["traj"]).tolist())
     flatio.write_result(a.out, fmt, list(res["row_matrices"].values()), res["column_factor"], summary)
+    if glm is not None:
+        for name, v in zip(("interaction_coeff", "interaction_pval"), glm):
+            if fmt == "npy":
+                np.save(os.path.join(a.out, name + ".npy"), np.asfortranarray(v))
+            else:
+                flatio.write_raw(os.path.join(a.out, name + ".f64"), v)
     print(json.dumps({k: summary[k] for k in ("train_rmse", "test_rmse", "loss", "iters")} | {"out": a.out}))
     return 0
 

@@ -1,0 +1,92 @@
+"""Host-side checks of the post-hoc interaction GLM (no GPU needed): argument validation before the library is called,
+the C ABI's own checks on a null handle, and the p-value helper."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import __graft_entry__ as ge
+from insider_amd import _lib, api, fit, posthoc
+
+
+@pytest.fixture(scope="module")
+def lib():
+    ge.build()
+    return _lib.load()
+
+
+def _fake(n=20, p=12, n_levels=(3, 2), m=0):
+    """An InsiderData with the shape facts of a resident data set but no handle: every check below must fire before the
+    library is reached."""
+    ds = object.__new__(api.InsiderData)
+    ds.n, ds.p, ds.c, ds.m = n, p, len(n_levels), m
+    ds.n_levels = np.asarray(n_levels, dtype=np.int32)
+    ds._h = C.c_void_p()
+    return ds
+
+
+def _status(fn):
+    with pytest.raises(_lib.InsiderError) as e:
+        fn()
+    return e.value.status
+
+
+def test_python_side_argument_checks():
+    ds = _fake()
+    K = 4
+    A = [np.zeros((3, K), order="F"), np.zeros((2, K), order="F")]
+    Cm = np.ones((K, 12), order="F")
+    group = np.tile([1, 2], 10)
+    assert _status(lambda: ds.interaction_glm([a[:, :3] for a in A], Cm, group)) == _lib.ERR_ARG      # K mismatch
+    assert _status(lambda: ds.interaction_glm(A, Cm, group, subtract=[1])) == _lib.ERR_ARG            # subtract length
+    assert _status(lambda: ds.interaction_glm(A, Cm, group, subtract=[1, 0, 1])) == _lib.ERR_ARG
+    assert _status(lambda: ds.interaction_glm(A, Cm, group, n_groups=1)) == _lib.ERR_ARG              # id 2 > G
+    assert _status(lambda: ds.interaction_glm(A, Cm, np.where(group == 2, -1, group))) == _lib.ERR_ARG
+    assert _status(lambda: ds.interaction_glm(A, Cm, np.zeros(20, dtype=int))) == _lib.ERR_ARG         # no group at all
+    assert _status(lambda: ds.interaction_glm(A, Cm, group[:-1])) == _lib.ERR_ARG
+    assert _status(lambda: ds.interaction_glm(A, Cm, group + 0.5)) == _lib.ERR_ARG
+    assert _status(lambda: ds.residual(A, Cm, rows=(0, 21))) == _lib.ERR_ARG                          # row_end > n
+    assert _status(lambda: ds.residual(A, Cm, rows=(5, 4))) == _lib.ERR_ARG
+    assert _status(lambda: ds.residual(A, Cm, rows=slice(0, 10, 2))) == _lib.ERR_ARG
+    assert _status(lambda: ds.residual(A, Cm, inc_continuous=2)) == _lib.ERR_ARG
+
+
+def test_c_abi_rejects_a_null_handle(lib):
+    K = 3
+    a = np.zeros((2, K))
+    Aptrs = (C.POINTER(C.c_double) * 1)(_lib.ptr(a))
+    Cm = np.zeros((K, 4))
+    sub = np.ones(1, dtype=np.int32)
+    grp = np.ones(2, dtype=np.int32)
+    out = np.zeros(64)
+    assert lib.insider_hip_residual(None, Aptrs, _lib.ptr(Cm), 0, K, _lib.ptr(sub, C.c_int32), 0, 1, _lib.ptr(out)) == \
+        _lib.ERR_ARG
+    assert b"null handle" in lib.insider_hip_last_error()
+    assert lib.insider_hip_interaction_glm(None, Aptrs, _lib.ptr(Cm), 0, K, _lib.ptr(sub, C.c_int32),
+                                           _lib.ptr(grp, C.c_int32), 1, _lib.ptr(out), _lib.ptr(out),
+                                           _lib.ptr(out)) == _lib.ERR_ARG
+
+
+def test_t_pvalues():
+    from scipy import stats
+    coeff = np.array([[1.0, -2.0, np.nan], [0.0, 0.0, 0.0]])
+    se = np.array([[0.5, 1.0, np.nan], [0.0, 0.0, 0.0]])
+    dof = np.array([30.0, 0.0])
+    pv = posthoc.t_pvalues(coeff, se, dof)
+    np.testing.assert_allclose(pv[0, :2], 2 * stats.t.sf([2.0, 2.0], 30.0), rtol=1e-15)
+    assert np.isnan(pv[0, 2])
+    assert np.all(pv[1] == 0)                                # empty group: the reference's matrix(0, ...) rows
+
+
+def test_glm_interaction_resident_checks_the_covariate():
+    obj = api.Insider(inc_continuous=0, _resident_fit=_fake())
+    with pytest.raises(ValueError, match="group_cov"):
+        posthoc.glm_interaction_resident(obj, 2)
+
+
+def test_cli_accepts_interaction_glm():
+    a = fit.parse(["--x", "X.npy", "--levels", "L.npy", "--rank", "3", "--lambda", "1", "--alpha", "0.1",
+                   "--interaction-glm", "1"])
+    assert a.interaction_glm == 1
+    assert fit.parse(["--x", "X.npy", "--levels", "L.npy", "--rank", "3", "--lambda", "1", "--alpha", "0.1"]).interaction_glm \
+        is None
