@@ -128,10 +128,7 @@ int insider_hip_comm_init(insider_hip_handle *h, const void *unique_id, int rank
  * entry, 2 = per-(covariate, level) terms with one table look-up per entry, 3 = per-(covariate, level) terms from the
  * gene's dense level-pair counts [falls back to 2 when a count exceeds one byte]; same results), "row_counts" (1, default = the merged row update takes its per-gene level sums from the dense
  * level-pair counts when they exist, 0 = from the entry lists; same results), "force_allreduce" (1 = call the all-reduce callback even
- * when world == 1: plumbing rehearsal), "cd_split" / "cd_long_frac" (2 = steady-state column steps run split: the genes predicted longest — whole buckets of the
- * launch order, at most cd_long_frac [0.03] of the genes — get their statistics and their solve on a stream of their own, ahead
- * of the others' statistics; bit-identical results; 0 [default] = off: measured, it does not shorten the step),
- * "row_fused" (1, default = the merged row update forms a level's equations and
+ * when world == 1: plumbing rehearsal), "row_fused" (1, default = the merged row update forms a level's equations and
  * solve in one launch; with tuning = 0 the whole unmasked row update of a covariate is that one launch; 0 = separate launches),
  * "list_fine" (1, default = the per-entry statistics kernel uses the 4x4x4 form of the f64 matrix instruction for 16 <= K <= 31
  * [fewer wasted outputs than 16 x 16 blocks], 0 = the 16x16x4 form; same sums in another order), "row_gemm" / "row_gemm_waves" (1, default = the per-level weighted Gram sums of a covariate with >= 49
@@ -141,9 +138,7 @@ int insider_hip_comm_init(insider_hip_handle *h, const void *unique_id, int rank
  * in four rotations from LDS, resident blocks whose waves draw genes by ticket; 0 = the 16x16x4 form; same sums to rounding),
  * "mm_fast" (1, default = the streaming products of the row phase [V = C A', S A, U'C, S'C: from 16384 rows on] stage their small
  * operand in LDS once per block and read the tall one in 16-byte pieces / several column tiles per wave; 0 = round 4's kernels;
- * same sums, the row products in another order), "join_lean" and "q_split" (0: experiments of round 5 that gained nothing — fewer
- * stream joins on the main chain [bits 1, 2, 4]; S A and S^held A in two parts, the first beside the last covariate's update),
- * "cd_pairs" (1, default = the register-resident sweep kernel [K <= 30] is routed through its blocks of TWO
+ * same sums, the row products in another order), "cd_pairs" (1, default = the register-resident sweep kernel [K <= 30] is routed through its blocks of TWO
  * coordinate steps wherever two consecutive coordinates of a sweep's order share a coordinate slot: a third fewer computed jumps,
  * the same steps in the same order — bit-identical iterates; 0 = one step per block), "cd_pass1" / "cd_pass_ratio" / "cd_cold_iters" (multi-pass column solves in the first
  * cd_cold_iters outer iterations of a call [default 3]: the register-resident sweep kernel stops at sweep cd_pass1 [64; 0 = one

@@ -920,10 +920,9 @@ struct RegWho {            // which gene a lane works for
 __device__ __forceinline__ RegWho reg_who(const ColArgs &a, int lane)
 {
     RegWho w;
-    const int row = lane >> 4, slot = (a.slot_begin ? *a.slot_begin : 0) + blockIdx.x * 4 + row;
+    const int row = lane >> 4, slot = blockIdx.x * 4 + row;
     w.i = lane & 15;
-    // a resumed pass (multi-pass solve) continues the genes the previous pass left unfinished: the first *pass_count of its
-    // order; a split solve's long-gene launch takes the first n_long slots, its majority launch starts at slot n_long
+    // a resumed pass (multi-pass solve) continues the genes the previous pass left unfinished: the first *pass_count of its order
     const int count = a.pass_count ? *a.pass_count : a.p;
     w.gene = slot < a.p && slot < count;
     const int sl = w.gene ? slot : 0;

@@ -59,12 +59,6 @@ struct ColFacArgs {
     int zt_stride, zt_off[CF_MAXC + 1];         // doubles per gene, offset of position t
     int m, SLcat;                               // continuous columns; their factor rows are Astack[SLcat .. SLcat + m)
     int pos_cov[CF_MAXC];                       // covariate (column of the level table) at position t
-    // split solves (k_col_paircnt): the long genes' records are formed first, from their list, so that their solve can start
-    // while the statistics of the others are still running; the launch over all genes then skips them
-    const int *list;                      // gene ids of this launch (null: all genes 0 .. p-1)
-    const int *list_count;                // ... of which the first *list_count are processed (null with list == null)
-    const uint16_t *skip_bkt;             // all-gene launch: skip gene j when skip_bkt[j] <= *skip_last (null: none)
-    const int *skip_last;
 };
 
 // Gc = M + M' for the lower blocks, XtX_j = R'R - Gc; qc and the sum of squares go into row KP - 1 of the record
@@ -251,14 +245,8 @@ __global__ void __launch_bounds__(WPB * 64) k_col_paircnt(ColFacArgs a)
         tabs[i] = r < a.tab_rows ? a.Astack[(size_t)q * KP + k] : 0.0;
     }
     __syncthreads();
-    int j = blockIdx.x * WPB + w;        // wave-uniform
-    if (a.list) {
-        if (j >= *a.list_count) return;
-        j = a.list[j];
-    } else {
-        if (j >= a.p) return;
-        if (a.skip_bkt && (int)a.skip_bkt[j] <= *a.skip_last) return;
-    }
+    const int j = blockIdx.x * WPB + w;        // wave-uniform
+    if (j >= a.p) return;
     const int g4 = lane >> 4, c16 = lane & 15;
     double qh[NB];                       // the epilogue's operands, requested now
 #pragma unroll
@@ -373,7 +361,7 @@ __global__ void __launch_bounds__(WPB * 64) k_col_paircnt(ColFacArgs a)
 // acc[bi][bj][x] of lane (g4, b, j) = M[16 bi + 4 ((b + x) & 3) + g4][16 bj + 4 b + j].
 // LDS: per wave two 16 x 17 tiles | R'R | table rows | factor rows [position][level / 4][bi][level % 4][16]
 template <int NB, int WPB, int MAXS, bool ZC = false>
-__global__ void __launch_bounds__(WPB * 64) k_col_paircnt4(ColFacArgs a, int nitems, unsigned *__restrict__ ticket, unsigned ticket_base, int npart, int cap)
+__global__ void __launch_bounds__(WPB * 64) k_col_paircnt4(ColFacArgs a, unsigned *__restrict__ ticket, unsigned ticket_base, int npart, int cap)
 {
     static_assert(NB <= 2, "accumulators of the 4x4x4 form");
     constexpr int KP = Geo<NB>::KP;
@@ -430,7 +418,7 @@ __global__ void __launch_bounds__(WPB * 64) k_col_paircnt4(ColFacArgs a, int nit
     // product beside it).  One atomic per wave and gene, requested before the wave starts on its current gene.  Atomics on ONE
     // address retire at one per ~7 ns on this part — 50000 of them are 0.35 ms, more than the kernel — so there are npart
     // counters on lines of their own: block b draws from counter b % npart (late blocks are spread over all of them), whose
-    // ticket t stands for gene t * npart + (b % npart), t < cap = ceil(nitems / npart).  The counters only ever grow: every
+    // ticket t stands for gene t * npart + (b % npart), t < cap = ceil(p / npart).  The counters only ever grow: every
     // wave ends on exactly one ticket >= cap, the grid is a multiple of npart, so a launch takes cap + (waves per counter)
     // tickets from each and the host knows the next launch's base without a reset.
     const int part = blockIdx.x % npart;
@@ -442,14 +430,8 @@ __global__ void __launch_bounds__(WPB * 64) k_col_paircnt4(ColFacArgs a, int nit
     };
     for (unsigned cur = take(), nxt; cur < (unsigned)cap; cur = nxt) {
     nxt = take();
-    if ((int)cur * npart + part >= nitems) continue;
-    int j = (int)cur * npart + part;   // wave-uniform
-    if (a.list) {
-        if (j >= *a.list_count) continue;
-        j = a.list[j];
-    } else {
-        if (a.skip_bkt && (int)a.skip_bkt[j] <= *a.skip_last) continue;
-    }
+    const int j = (int)cur * npart + part;   // wave-uniform
+    if (j >= a.p) continue;
     double qh[NB];
 #pragma unroll
     for (int bb = 0; bb < NB; ++bb) qh[bb] = a.Qheld[(size_t)j * KP + 16 * bb + c16];

@@ -119,13 +119,11 @@ struct insider_hip_handle {
     hipEvent_t ev_prep = nullptr;
     hipEvent_t ev_c_ready = nullptr;
     hipEvent_t ev_head = nullptr;     // recorded on side2 in front of the level Gram GEMM: the main chain's k_gene_u waits for it
-    int row_head = 1;                 // option "row_head": that wait (1 = on)
     std::vector<hipEvent_t> ev_w;
     double *lvl_sum_all = nullptr;    // [SLcat][STAT + 2 KP + 2]: the level records of every covariate
     bool w_ready = false;
     double *gram_part2 = nullptr, *sc_part2 = nullptr;   // partial-sum buffers of the side-stream products
-    hipEvent_t ev_a_ready = nullptr, ev_qfull = nullptr, ev_qheld = nullptr, ev_q_early = nullptr;
-    int q_kb = 0;                     // rows [0, q_kb) of the stacked factors already sit in Qfull / Qheld (launch_q_early); 0: none
+    hipEvent_t ev_a_ready = nullptr, ev_qfull = nullptr, ev_qheld = nullptr;
     bool qfull_pending = false;
     bool qheld_pending = false;       // Qheld = S^held A of the factored column statistics is being formed on side3 (phase_R)
     int64_t n = 0, p = 0, ldn = 0, ldp = 0;
@@ -189,14 +187,12 @@ struct insider_hip_handle {
     int *sweeps = nullptr, *failflag = nullptr;
     int *sweep_key = nullptr;   // smoothed sweep counts: the longest-first scheduling key (k_sched_bucket)
     unsigned long long *sweep_total = nullptr;
-    unsigned *pc4_ticket = nullptr;     // k_col_paircnt4's gene tickets (main launch, long-gene launch): counters that only grow
-    unsigned pc4_base[4] = {0, 0, 0, 0};   // ... and the value each set stands at when its next launch starts: [2 site + (one counter ? 1 : 0)]
+    unsigned *pc4_ticket = nullptr;     // k_col_paircnt4's gene tickets: counters that only grow
+    unsigned pc4_base[2] = {0, 0};      // ... and the value they stand at when the next launch starts: [one counter ? 1 : 0]
     // where the register-resident sweep kernel of the current K keeps its table of code blocks (K <= 32; 0 = not asked yet): the
     // order table holds absolute block addresses (insider_cd_reg.hpp), published by a probe launch of that kernel
     unsigned long long cd_code_base = 0, cd_pair_base = 0;
     unsigned long long *code_base_dev = nullptr;   // where the probe launch stores them (workspace)
-    int q_split = 0;                   // option "q_split" (experiment of round 5, off: no gain — the early parts slow the memory-bound kernels of the last update by what they save): Qfull / Qheld in two parts, the first beside the last block of the row phase (launch_q_early)
-    int join_lean = 0;                 // option "join_lean" (bits): 1 = ev_prep behind ev_w, 2 = ev_side_done behind ev_qfull (one stream join where two were), 4 = Qfull behind Qheld
     int mm_fast = 1;                   // option "mm_fast": the small dense products on k_mm_rows2 / k_mm_reduce2 (default; 2: two column tiles per wave in the reductions)
     int col_mfma4 = 1;                 // option "col_mfma4": pair-count statistics with the second product on v_mfma_f64_4x4x4 (k_col_paircnt4; default)
     int cd_pairs = 1;                  // option "cd_pairs": route the sweeps through the kernel's blocks of two coordinate steps (default)
@@ -211,18 +207,7 @@ struct insider_hip_handle {
     int *sched_cnt[2] = {nullptr, nullptr}, *sched_rank = nullptr;
     uint16_t *sched_bkt = nullptr;
     int sched_flip = 0;
-    // split column solves (steady-state outer iterations): the genes predicted longest — whole buckets of the launch order,
-    // at most cd_long_frac of the genes — get their statistics and their solve on a stream of their own, ahead of everyone
-    // else's statistics: the solve of the longest gene is the critical path of the column step (a sequential recurrence of
-    // sweeps x K steps x ~44 ns), and it no longer waits for the statistics of the other genes
-    int *sched_long = nullptr;        // device: {n_long, last long bucket} of the current gene_perm (k_sched_scatter)
-    bool sched_long_valid = false;
     int n_simd = 1024;                // SIMDs of the device (4 per CU)
-    int cd_split = 0;                 // option "cd_split"
-    double cd_long_frac = 0.03;       // option "cd_long_frac"
-    hipStream_t lng = nullptr;
-    hipEvent_t ev_long_go = nullptr, ev_long_done = nullptr;
-    bool long_pending = false;
     // multi-pass column solves in the cold outer iterations (CdParams::sweep_limit): saved state of the unfinished genes,
     // their estimated remaining lengths (two buffers, alternating between passes) and the order of the next pass
     double *cd_hsave = nullptr, *cd_isave = nullptr;
@@ -265,7 +250,7 @@ namespace {
 // stream's kernels wrote must reach the other stream's kernels (device scope: every kernel boundary does that), not the host
 constexpr unsigned EV_SYNC = hipEventDisableTiming | hipEventDisableSystemFence;
 
-constexpr int PC4_PARTS = 16;        // ticket counters of k_col_paircnt4 per launch site
+constexpr int PC4_PARTS = 16;        // ticket counters of k_col_paircnt4
 constexpr int MM_FAST_MIN = 16384;   // rows from which k_mm_rows2 / k_mm_reduce2 run (below: the staging and the longer waves cost more than they save; c1: 5000 genes)
 constexpr int MM_SLAB = 128;  // rows per partial of the reduction products (insider_mm.hpp)
 
@@ -279,7 +264,7 @@ std::vector<void **> workspace_slots(insider_hip_handle *h)
     add(h->U); add(h->Ylvl); add(h->wpart); add(h->Vlev); add(h->Qheld); add(h->eq); add(h->sse_train); add(h->sse_test); add(h->b2);
     add(h->b1); add(h->loss_buf); add(h->stage); add(h->wg_part); add(h->wg_pair); add(h->sweeps); add(h->sweep_key); add(h->failflag);
     add(h->sweep_total); add(h->pc4_ticket); add(h->order_buf[0]); add(h->order_buf[1]); add(h->gene_perm); add(h->sched_cnt[0]); add(h->sched_cnt[1]);
-    add(h->sched_rank); add(h->sched_bkt); add(h->sched_long); add(h->cd_hsave); add(h->cd_isave); add(h->cd_pass_slot);
+    add(h->sched_rank); add(h->sched_bkt); add(h->cd_hsave); add(h->cd_isave); add(h->cd_pass_slot);
     add(h->cd_pass_perm[0]); add(h->cd_pass_perm[1]); add(h->cd_pass_cnt); add(h->code_base_dev);
     for (int e = 0; e < insider_hip_handle::EARLY; ++e) add(h->perm_early[e]);
     return v;
@@ -292,7 +277,6 @@ void forget_workspace(insider_hip_handle *h)
     h->order = nullptr;
     h->order_rows = 0;
     h->cd_code_base = h->cd_pair_base = 0;
-    h->sched_long_valid = false;
     for (int e = 0; e < insider_hip_handle::EARLY; ++e) h->have_early[e] = false;
     h->have_perm = false;
     h->K = 0;
@@ -419,15 +403,14 @@ int ensure_workspace(insider_hip_handle *h, int K)
     // [0] a system was singular, [1] ridge genes wait for the general route, [2] genes stopped by max_sweeps, [3] longest solve
     if ((rc = dmalloc(&h->failflag, 4))) return rc;
     if ((rc = dmalloc(&h->sweep_total, 256))) return rc;
-    if ((rc = dmalloc(&h->pc4_ticket, (size_t)2 * (PC4_PARTS + 1) * 32))) return rc;   // (a 128-byte line per counter)
-    HIPCHECK(hipMemsetAsync(h->pc4_ticket, 0, (size_t)2 * (PC4_PARTS + 1) * 32 * sizeof(unsigned), h->stream));
+    if ((rc = dmalloc(&h->pc4_ticket, (size_t)(PC4_PARTS + 1) * 32))) return rc;   // (a 128-byte line per counter)
+    HIPCHECK(hipMemsetAsync(h->pc4_ticket, 0, (size_t)(PC4_PARTS + 1) * 32 * sizeof(unsigned), h->stream));
     for (unsigned &b : h->pc4_base) b = 0;
     if ((rc = dmalloc(&h->gene_perm, (size_t)h->p))) return rc;
     if ((rc = dmalloc(&h->sched_cnt[0], (size_t)SCHED_BUCKETS))) return rc;
     if ((rc = dmalloc(&h->sched_cnt[1], (size_t)SCHED_BUCKETS))) return rc;
     if ((rc = dmalloc(&h->sched_rank, (size_t)h->p))) return rc;
     if ((rc = dmalloc(&h->sched_bkt, (size_t)h->p))) return rc;
-    if ((rc = dmalloc(&h->sched_long, 2))) return rc;
     if ((rc = dmalloc(&h->sweep_key, (size_t)h->p))) return rc;
     if ((rc = dmalloc(&h->cd_hsave, (size_t)h->p * KP))) return rc;
     if ((rc = dmalloc(&h->cd_isave, (size_t)h->p * KP))) return rc;
@@ -440,9 +423,7 @@ int ensure_workspace(insider_hip_handle *h, int K)
         if ((rc = dmalloc(&h->perm_early[e], (size_t)h->p))) return rc;
     HIPCHECK(hipMemsetAsync(h->sched_cnt[0], 0, SCHED_BUCKETS * sizeof(int), h->stream));
     HIPCHECK(hipMemsetAsync(h->sched_cnt[1], 0, SCHED_BUCKETS * sizeof(int), h->stream));
-    HIPCHECK(hipMemsetAsync(h->sched_long, 0, 2 * sizeof(int), h->stream));
     h->sched_flip = 0;
-    h->sched_long_valid = false;
     h->have_perm = false;
     // rows of the padded factor buffers beyond K must stay zero: C rows are gathered with pitch KP and the
     // pad genes of the transposed layout index rows p..ldp-1
@@ -504,28 +485,21 @@ bool mm_rows2_fits(const insider_hip_handle *h, int64_t ldx, int M, int Kd)
 {
     return h->mm_fast && M >= MM_FAST_MIN && ldx % 2 == 0 && (size_t)4 * cdiv(Kd, 16) * h->NB * 64 * sizeof(double) <= 64 * 1024;
 }
-// k_begin / k_end: a window of the inner dimension (columns of X, rows of W), k_begin even; accumulate: out += the window's
-// product.  Only with k_mm_rows2 (mm_rows2_fits); the default is the whole product
 int launch_mm_rows_kp(insider_hip_handle *h, const double *X, int64_t ldx, int M, int Kd, const double *W, double *out,
-                      hipStream_t st = nullptr, int k_begin = 0, int k_end = -1, bool accumulate = false)
+                      hipStream_t st = nullptr)
 {
     if (!st) st = h->stream;
-    if (k_end < 0) k_end = Kd;
-    const bool window = k_begin != 0 || k_end != Kd || accumulate;
-    const size_t lds2 = (size_t)4 * cdiv(k_end - k_begin, 16) * h->NB * 64 * sizeof(double);   // k_mm_rows2: W staged in LDS
-    if (mm_rows2_fits(h, ldx, M, Kd) && k_begin % 2 == 0) {
+    if (mm_rows2_fits(h, ldx, M, Kd)) {
         const int tiles = cdiv(M, 16), tpw = mm_tiles_per_wave(h, tiles);
-        const int kread = (int)((ldx - k_begin) & ~(int64_t)1);
+        const size_t lds2 = (size_t)4 * cdiv(Kd, 16) * h->NB * 64 * sizeof(double);   // W staged in LDS
         NB_DISPATCH(h->NB, {
             (void)WPB_;
-            hipLaunchKernelGGL((k_mm_rows2<NB_, false>), dim3(cdiv(cdiv(tiles, tpw), 4), 1), dim3(256), lds2, st, X + k_begin, ldx, M,
-                               k_end - k_begin, W + (size_t)k_begin * h->KP, h->KP, h->KP, out, (int64_t)h->KP, h->KP, tpw, kread,
-                               accumulate ? 1 : 0);
+            hipLaunchKernelGGL((k_mm_rows2<NB_, false>), dim3(cdiv(cdiv(tiles, tpw), 4), 1), dim3(256), lds2, st, X, ldx, M, Kd, W,
+                               h->KP, h->KP, out, (int64_t)h->KP, h->KP, tpw);
         });
         KCHECK();
         return INSIDER_OK;
     }
-    if (window) return fail(INSIDER_ERR_ARG, "a window of the product needs k_mm_rows2");
     NB_DISPATCH(h->NB, {
         (void)WPB_;
         hipLaunchKernelGGL((k_mm_rows<NB_, false>), dim3(cdiv(cdiv(M, 16), 4), 1), dim3(256), 0, st, X, ldx, M, Kd, W,
@@ -611,22 +585,15 @@ int phase_R(insider_hip_handle *h, bool use_side = false, bool r_is_current = fa
     if (use_side) {
         HIPCHECK(hipEventRecord(h->ev_a_ready, h->stream));
         // Qheld = S^held A, which the factored column statistics read: on the third stream (idle since the row phase's C'C),
-        // beside R'R on the main one instead of behind it, and beside Qfull on the side stream.  (join_lean bit 4 puts Qfull
-        // behind Qheld — alone, Qheld takes 22 instead of 33 us and the statistics start 11 us earlier — but Qfull then runs
-        // beside the statistics kernel and costs it 40 us of LDS and matrix time for its own 21: measured, round 5.)
-        // (launch_q_early: the rows [0, kb) of the stacked factors, final since the second-to-last update of the row phase, are
-        // already in both products — formed beside the last update; only the last block's columns are left)
-        const int kb = h->q_kb;
-        h->q_kb = 0;
+        // beside R'R on the main one instead of behind it, and beside Qfull on the side stream (Qfull behind Qheld: DESIGN §4.5)
         HIPCHECK(hipStreamWaitEvent(h->side, h->ev_a_ready, 0));
         if (want_qheld && h->Qheld && use_col_factored(h)) {
             HIPCHECK(hipStreamWaitEvent(h->side3, h->ev_a_ready, 0));
-            if (int rh = launch_mm_rows_kp(h, h->Sheld, h->SLP, (int)h->p, h->SL, h->Astack, h->Qheld, h->side3, kb, h->SL, kb > 0)) return rh;
+            if (int rh = launch_mm_rows_kp(h, h->Sheld, h->SLP, (int)h->p, h->SL, h->Astack, h->Qheld, h->side3)) return rh;
             HIPCHECK(hipEventRecord(h->ev_qheld, h->side3));
             h->qheld_pending = true;
-            if (h->join_lean & 4) HIPCHECK(hipStreamWaitEvent(h->side, h->ev_qheld, 0));
         }
-        int rq = launch_mm_rows_kp(h, h->S, h->SLP, (int)h->p, h->SL, h->Astack, h->Qfull, h->side, kb, h->SL, kb > 0);
+        int rq = launch_mm_rows_kp(h, h->S, h->SLP, (int)h->p, h->SL, h->Astack, h->Qfull, h->side);
         if (rq) return rq;
         HIPCHECK(hipEventRecord(h->ev_qfull, h->side));
         h->qfull_pending = true;
@@ -637,29 +604,6 @@ int phase_R(insider_hip_handle *h, bool use_side = false, bool r_is_current = fa
     if (rc) return rc;
     if (use_side) return INSIDER_OK;
     return launch_mm_rows_kp(h, h->S, h->SLP, (int)h->p, h->SL, h->Astack, h->Qfull);
-}
-
-// Qfull = S A and Qheld = S^held A by parts (option "q_split"): the product over the rows [0, kb) of the stacked factors —
-// every block of the row phase but its last — is formed on the side streams as soon as those rows are final, beside the last
-// block's update (small dependent kernels that leave the machine idle); phase_R then adds the last block's columns.  At c3
-// (100 + 10 levels) that leaves 10 of 110 columns behind the row phase: 8 instead of 33 us in front of the column statistics.
-// Sums over the stacked levels in two runs [0, kb), [kb, SL) instead of one: agrees with the one-piece product to rounding.
-int q_split_boundary(const insider_hip_handle *h, int masked, bool cont_follow)
-{
-    if (!h->q_split || !masked || !h->Qheld || !use_col_factored(h)) return 0;
-    const int kb = cont_follow ? h->SLcat : (h->c >= 2 ? h->lvl_off[h->c - 1] : 0);
-    if (kb < 16 || kb % 2 != 0 || kb >= h->SL || !mm_rows2_fits(h, h->SLP, (int)h->p, h->SL)) return 0;
-    return kb;
-}
-int launch_q_early(insider_hip_handle *h, int kb)
-{
-    HIPCHECK(hipEventRecord(h->ev_q_early, h->stream));
-    HIPCHECK(hipStreamWaitEvent(h->side3, h->ev_q_early, 0));
-    if (int rh = launch_mm_rows_kp(h, h->Sheld, h->SLP, (int)h->p, h->SL, h->Astack, h->Qheld, h->side3, 0, kb, false)) return rh;
-    HIPCHECK(hipStreamWaitEvent(h->side, h->ev_q_early, 0));
-    if (int rq = launch_mm_rows_kp(h, h->S, h->SLP, (int)h->p, h->SL, h->Astack, h->Qfull, h->side, 0, kb, false)) return rq;
-    h->q_kb = kb;
-    return INSIDER_OK;
 }
 
 struct Timer {   // HIP-event pair around one launch on the library's stream (option "profile")
@@ -689,7 +633,7 @@ struct Timer {   // HIP-event pair around one launch on the library's stream (op
 // is built while the current solve runs — the sweep kernel leaves no room for other waves, so the builder runs in its tail,
 // on SIMDs that have already drained — instead of competing with the row phase.
 // 32 < K <= 48 with an l1 term: the register-resident kernel with its third slot's matrix columns in LDS (insider_cd_reg.hpp)
-static bool reg3_path(int K, double la, int variant) { return K > 32 && K <= 48 && la > 0.0 && variant == 0; }
+static bool reg3_path(int K, double la) { return K > 32 && K <= 48 && la > 0.0; }
 
 // the address of the table of code blocks of k_cd_cols_reg<., KMAX(K), true> on this device (K <= 32): one probe launch per workspace
 int ensure_code_base(insider_hip_handle *h, int K)
@@ -731,18 +675,11 @@ int ensure_order_table(insider_hip_handle *h, uint64_t seed, uint32_t iter, int 
     }
     // rows for K > 32 carry 64 row offsets (row16 kernel) unless the solve takes the register-resident kernel's successor list
     hipLaunchKernelGGL(k_order_table, dim3(cdiv((int64_t)(rows + 1) * 64, 256)), dim3(256), 0, stream, seed, iter, K, rows,
-                       order_mode, K * 8, reg_kmax(K), (K > 32 && !reg3_path(K, la, h->cd_variant)) ? 1 : 0, h->cd_code_base,
+                       order_mode, K * 8, reg_kmax(K), (K > 32 && !(h->cd_variant == 0 && reg3_path(K, la))) ? 1 : 0, h->cd_code_base,
                        h->cd_pairs ? h->cd_pair_base : 0ull, h->order_buf[slot]);
     KCHECK();
     if (!h->order) h->order = h->order_buf[slot];
     return INSIDER_OK;
-}
-
-// most genes a split solve treats as long (whole buckets of the launch order up to this many)
-int long_cap(const insider_hip_handle *h)
-{
-    const double f = h->cd_long_frac < 0.0 ? 0.0 : (h->cd_long_frac > 0.25 ? 0.25 : h->cd_long_frac);
-    return (int)(f * (double)h->p);
 }
 
 // the launch order of the next column solve: genes by decreasing key, a bucket sort on a log scale (insider_kernels.hpp).
@@ -757,10 +694,8 @@ int launch_gene_order(insider_hip_handle *h, const int *sweeps, int reset, int f
                            h->sweep_key, cnt, h->sched_bkt, h->sched_rank);
     KCHECK();
     hipLaunchKernelGGL(k_sched_scatter, dim3(cdiv(h->p, 256)), dim3(256), 0, st, (const int *)cnt, cnt_next,
-                       (const uint16_t *)h->sched_bkt, (const int *)h->sched_rank, (int)h->p, h->gene_perm, long_cap(h),
-                       h->sched_long);
+                       (const uint16_t *)h->sched_bkt, (const int *)h->sched_rank, (int)h->p, h->gene_perm);
     KCHECK();
-    h->sched_long_valid = !float_bits;   // the sum-of-squares order of a first solve predicts no lengths
     return INSIDER_OK;
 }
 
@@ -796,9 +731,10 @@ int col_stats_path(const insider_hip_handle *h)
 }
 bool use_col_factored(const insider_hip_handle *h) { return col_stats_path(h) != 0; }
 
-// the pair-count statistics kernel (insider_col_factored.hpp) on `blocks` blocks of four genes
-int launch_paircnt(insider_hip_handle *h, const ColFacArgs &a, int blocks, hipStream_t st)
+// the pair-count statistics kernel (insider_col_factored.hpp) over every gene, on the main stream
+int launch_paircnt(insider_hip_handle *h, const ColFacArgs &a)
 {
+    const int blocks = cdiv(a.p, 4);
     if (h->col_mfma4 && h->NB <= 2 && !(a.zt && a.nsteps > 4)) {   // (real-valued counts with more than four k-steps: 180 registers, two waves per SIMD)
         // second product on the 4x4x4 matrix instruction, factor rows of every position staged in LDS (k_col_paircnt4);
         size_t quads = 1;
@@ -810,17 +746,16 @@ int launch_paircnt(insider_hip_handle *h, const ColFacArgs &a, int blocks, hipSt
             int nb = std::min(blocks, resident);
             const int npart = nb >= PC4_PARTS ? PC4_PARTS : 1;      // ticket counters in use (k_col_paircnt4)
             nb -= nb % npart;
-            const int nitems = a.list ? 4 * blocks : a.p;           // (a list launch: its bound; the kernel stops at *list_count)
-            const int cap = cdiv(nitems, npart);
-            // the two launch sites may run at the same time: a set of counters each; a launch with ONE counter (few blocks) has
-            // a counter of its own behind the sixteen, so that the counters of a set always stand at the same value
-            const int which = (st == h->lng ? 2 : 0) + (npart == 1 ? 1 : 0);
-            unsigned *tk = h->pc4_ticket + ((size_t)(which >> 1) * (PC4_PARTS + 1) + (npart == 1 ? PC4_PARTS : 0)) * 32;
+            const int cap = cdiv(a.p, npart);
+            // a launch with ONE counter (few blocks) has a counter of its own behind the sixteen, so that the sixteen always
+            // stand at the same value
+            const int which = npart == 1 ? 1 : 0;
+            unsigned *tk = h->pc4_ticket + (size_t)which * PC4_PARTS * 32;
             const unsigned tbase = h->pc4_base[which];
 #define PC4(NBV, MS)                                                                                                         \
     {                                                                                                                        \
-        if (a.zt) hipLaunchKernelGGL((k_col_paircnt4<NBV, 4, MS, true>), dim3(nb), dim3(256), lds, st, a, nitems, tk, tbase, npart, cap); \
-        else hipLaunchKernelGGL((k_col_paircnt4<NBV, 4, MS, false>), dim3(nb), dim3(256), lds, st, a, nitems, tk, tbase, npart, cap); \
+        if (a.zt) hipLaunchKernelGGL((k_col_paircnt4<NBV, 4, MS, true>), dim3(nb), dim3(256), lds, h->stream, a, tk, tbase, npart, cap); \
+        else hipLaunchKernelGGL((k_col_paircnt4<NBV, 4, MS, false>), dim3(nb), dim3(256), lds, h->stream, a, tk, tbase, npart, cap); \
     }
             if (h->NB == 1 && a.nsteps <= 4) PC4(1, 4)
             else if (h->NB == 1) PC4(1, 8)
@@ -836,36 +771,15 @@ int launch_paircnt(insider_hip_handle *h, const ColFacArgs &a, int blocks, hipSt
     NB_DISPATCH(h->NB, {
         (void)WPB_;
         const size_t lds = ((size_t)4 * 16 * 17 + (size_t)Geo<NB_>::KP * Geo<NB_>::KP + (size_t)4 * a.nsteps * Geo<NB_>::KP) * sizeof(double);
-        if (a.zt) hipLaunchKernelGGL((k_col_paircnt<NB_, 4, true>), dim3(blocks), dim3(256), lds, st, a);
-        else hipLaunchKernelGGL((k_col_paircnt<NB_, 4, false>), dim3(blocks), dim3(256), lds, st, a);
+        if (a.zt) hipLaunchKernelGGL((k_col_paircnt<NB_, 4, true>), dim3(blocks), dim3(256), lds, h->stream, a);
+        else hipLaunchKernelGGL((k_col_paircnt<NB_, 4, false>), dim3(blocks), dim3(256), lds, h->stream, a);
     });
     KCHECK();
     return INSIDER_OK;
 }
 
-// Should this outer iteration's column step run split (long genes on their own stream, ahead of the others' statistics)?
-// Steady-state iterations only (the cold ones are throughput-bound and solve in passes), the pair-count statistics, the
-// register-resident sweep kernel, and a launch order made from sweep counts.
-bool use_split(const insider_hip_handle *h, int masked, double alpha, int outer_iter)
-{
-    if (!(h->cd_split && masked && alpha != 0.0 && h->cd_variant == 0 && h->K <= 32 && col_stats_path(h) == 2 &&
-          outer_iter >= std::max(h->cd_cold_iters, (int)insider_hip_handle::EARLY) && h->have_perm && h->sched_long_valid &&
-          long_cap(h) >= 4))
-        return false;
-    // Not on by default.  Measured on a 25000-gene slab of c4 (one rank of the 8-GPU configuration; tools/slab_trace.sh,
-    // tools/tail_probe.py): the launch order predicts the tail well (the 50 longest genes of a solve are all among its first
-    // 3 %, correlation of consecutive sweep counts 0.95), but the tail is BROAD, not a few outliers (median 171, p99 415, max
-    // 612 sweeps; the longest gene outside the first 10 % still needs 425).  So the launch that holds everyone else is barely
-    // shorter than the whole solve (0.69 - 0.72 ms against 0.73, which is what the longest gene takes alone), and the long
-    // genes' sweeps next to the others' MFMA-bound statistics slow those down: 1.26 ms
-    // per steady iteration unsplit, 1.30 / 1.33 / 1.40 ms with 3 / 10 / 25 % of the genes split off.
-    return h->cd_split >= 2;   // forced
-}
-
 // masked Gram/XtY complement statistics of every gene (column side of src/optimize.cpp:216-222)
-// split: the long genes' records first, on the stream `lng` (their solve follows there, launch_col_solve); the launch over
-// all genes on the main stream skips them
-int launch_col_stats(insider_hip_handle *h, bool timed, bool split = false)
+int launch_col_stats(insider_hip_handle *h, bool timed)
 {
     Timer t;
     int rc;
@@ -891,27 +805,7 @@ int launch_col_stats(insider_hip_handle *h, bool timed, bool split = false)
             a.cnt = h->cf_cnt;
             a.hn = h->cf_hn;
             a.zt = h->cf_zt;
-            if (split) {
-                // the long branch starts here: everything the main stream has produced so far (row factors, R'R, Qheld)
-                // plus what the side stream prepares for the solve (launch order, sweep-order table, Qfull)
-                HIPCHECK(hipEventRecord(h->ev_long_go, h->stream));
-                HIPCHECK(hipStreamWaitEvent(h->lng, h->ev_long_go, 0));
-                if (h->side_pending) HIPCHECK(hipStreamWaitEvent(h->lng, h->ev_side_done, 0));
-                if (h->qfull_pending) HIPCHECK(hipStreamWaitEvent(h->lng, h->ev_qfull, 0));
-                ColFacArgs al = a;
-                al.list = h->gene_perm;
-                al.list_count = h->sched_long;
-                rc = launch_paircnt(h, al, cdiv(long_cap(h), 4), h->lng);
-                if (rc) return rc;
-                KCHECK();
-                h->long_pending = true;
-                a.skip_bkt = h->sched_bkt;
-                a.skip_last = h->sched_long + 1;
-                // the all-gene launch below reads sched_long / sched_bkt too, which k_sched_scatter wrote on the side stream:
-                // the main stream must see them as well (it otherwise waits for the side stream only before the solve)
-                if (h->side_pending) HIPCHECK(hipStreamWaitEvent(h->stream, h->ev_side_done, 0));
-            }
-            rc = launch_paircnt(h, a, cdiv(h->p, 4), h->stream);
+            rc = launch_paircnt(h, a);
             if (rc) return rc;
         } else {
             NB_DISPATCH(h->NB, {
@@ -936,9 +830,8 @@ int launch_col_solve(insider_hip_handle *h, int masked, bool solve, double lambd
     const int NBLK = h->NB * (h->NB + 1) / 2, STAT = NBLK * 256;
     // (every stream join is a barrier packet on the main queue, ~5 us of bubble each at c3: ev_qfull is recorded on the side stream
     // AFTER the previous iteration's ev_side_done — phase_R comes after side_close — so it stands for both)
-    if (h->side_pending && !((h->join_lean & 2) && h->qfull_pending)) {   // the gene order / sweep-order table prepared on the side stream
+    if (h->side_pending)   // the gene order / sweep-order table prepared on the side stream
         HIPCHECK(hipStreamWaitEvent(h->stream, h->ev_side_done, 0));
-    }
     h->side_pending = false;
     if (h->qfull_pending) {
         HIPCHECK(hipStreamWaitEvent(h->stream, h->ev_qfull, 0));
@@ -1023,7 +916,6 @@ int launch_col_solve(insider_hip_handle *h, int masked, bool solve, double lambd
         a.hsave = h->cd_hsave;
         a.isave = h->cd_isave;
         a.pass_count = nullptr;
-        a.slot_begin = nullptr;
         a.resume = 0;
         a.pass_slot = nullptr;
         a.bucket_cnt = nullptr;
@@ -1034,7 +926,7 @@ int launch_col_solve(insider_hip_handle *h, int masked, bool solve, double lambd
         const size_t r16_bytes = (size_t)r16_lds_doubles(h->K) * sizeof(double);
         // the register-resident kernel scales its state by 1 / (2 lambda alpha): lambda alpha = 0 (alpha < 0 or lambda = 0: no l1
         // term at all) takes the group kernel below
-        if (h->cd_variant == 0 && (h->K <= 32 || reg3_path(h->K, a.cd.la, 0)) && a.cd.la > 0.0) {
+        if (h->cd_variant == 0 && (h->K <= 32 || reg3_path(h->K, a.cd.la)) && a.cd.la > 0.0) {
             // Cold outer iterations: thousands of sweeps per gene whose counts no history predicts, so a wave's four genes
             // finish far apart (measured at c3: 1.17x / 1.44x / 2.1x the ideal wave time in outer iterations 0 / 1 / 2).
             // The solve then runs in passes over geometrically growing sweep ranges: a limited pass stops at its sweep
@@ -1056,18 +948,6 @@ int launch_col_solve(insider_hip_handle *h, int masked, bool solve, double lambd
                     limits[npass++] = (int)l;   // the last pass runs from the last limit to the end, however far that is
             int start = 0;
             const int *perm_in = a.gene_perm;
-            if (h->long_pending) {
-                // split solve: the long genes (the first n_long slots of the launch order) on their own stream, right after their
-                // statistics; everyone else here, from slot n_long on
-                ColArgs al = a;
-                al.cd.start_sweep = 0;
-                al.cd.sweep_limit = 0;
-                al.pass_count = h->sched_long;
-                REG_DISPATCH(h->K, hipLaunchKernelGGL((k_cd_cols_reg<SL_, KM_, true>), dim3(cdiv(long_cap(h), 4)), dim3(64), 0, h->lng, al));
-                KCHECK();
-                HIPCHECK(hipEventRecord(h->ev_long_done, h->lng));
-                a.slot_begin = h->sched_long;
-            }
             for (int pass = 0;; ++pass) {
                 const int limit = pass < npass ? limits[pass] : 0;
                 a.cd.start_sweep = start;
@@ -1087,10 +967,6 @@ int launch_col_solve(insider_hip_handle *h, int masked, bool solve, double lambd
                 a.pass_count = count_out;
                 a.resume = 1;
                 start = limit;
-            }
-            if (h->long_pending) {   // the column step ends when both parts have
-                HIPCHECK(hipStreamWaitEvent(h->stream, h->ev_long_done, 0));
-                h->long_pending = false;
             }
             eval_after = checkpoint != 0;
             eval_args = a;
@@ -1114,7 +990,6 @@ int launch_col_solve(insider_hip_handle *h, int masked, bool solve, double lambd
     if (eval_after) {   // the per-gene loss statistics of the (updated) columns: the evaluation kernel, all genes (not part of the solve's time)
         eval_args.gene_perm = nullptr;
         eval_args.pass_count = nullptr;
-        eval_args.slot_begin = nullptr;
         eval_args.resume = 0;
         if (h->K <= 32) {
             REG_DISPATCH(h->K, hipLaunchKernelGGL((k_cd_cols_reg<SL_, KM_, false>), dim3(cdiv(h->p, 4)), dim3(64), 0, h->stream, eval_args));
@@ -1215,7 +1090,7 @@ int launch_gene_v(insider_hip_handle *h, int q_begin, int q_end)
 #define GV2_LAUNCH(NT_)                                                                                                       \
     hipLaunchKernelGGL((k_mm_rows2<NT_, true>), dim3(cdiv(cdiv(tiles, tpw), 4), cdiv(N, 16 * NT_)), dim3(256), ldsb * NT_, h->stream, \
                        (const double *)h->C, (int64_t)h->KP, (int)h->p, h->K,                                                \
-                       (const double *)(h->Astack + (size_t)q_begin * h->KP), h->KP, N, h->Vlev + q_begin, (int64_t)h->SLP, N, tpw, h->KP, 0)
+                       (const double *)(h->Astack + (size_t)q_begin * h->KP), h->KP, N, h->Vlev + q_begin, (int64_t)h->SLP, N, tpw)
         if (N <= 16) GV2_LAUNCH(1);
         else if (N <= 32) GV2_LAUNCH(2);
         else GV2_LAUNCH(4);
@@ -1325,9 +1200,6 @@ int launch_wsyrk_side(insider_hip_handle *h)
     for (int i = 0; i < h->c; ++i) {
         const int plen = h->NB * (h->NB + 1) / 2 * 256 + 2 * h->KP + 2;
         if (int rg = launch_level_gram(h, i, h->side2, h->lvl_sum_all + (size_t)h->lvl_off[i] * plen)) return rg;
-        // the level solves need C'C and (S^train C') as well: this stream joins the third one once, in front of its first event,
-        // so that every ev_w stands for ev_prep too and the main chain waits ONCE per covariate
-        if (i == 0 && (h->join_lean & 1)) HIPCHECK(hipStreamWaitEvent(h->side2, h->ev_prep, 0));
         HIPCHECK(hipEventRecord(h->ev_w[i], h->side2));
     }
     for (int k = 0; k < (h->cont_merged ? h->m : 0); ++k) {   // continuous columns: one-level covariates with real-valued weights
@@ -1389,7 +1261,7 @@ int row_update(insider_hip_handle *h, int i, int cont_col, int masked, double la
         if (int rcy = launch_mm_reduce_kp(h, h->U, 2, h->C, (int)h->p, 1, h->sc_part, nullptr, nullptr, &ypart_n)) return rcy;
         if (h->w_ready) {
             HIPCHECK(hipStreamWaitEvent(h->stream, h->ev_w[h->c + cont_col], 0));
-            if (!((h->join_lean & 1) && h->c > 0)) HIPCHECK(hipStreamWaitEvent(h->stream, h->ev_prep, 0));
+            HIPCHECK(hipStreamWaitEvent(h->stream, h->ev_prep, 0));
         }
         NB_DISPATCH(h->NB, {
             (void)WPB_;
@@ -1431,7 +1303,7 @@ int row_update(insider_hip_handle *h, int i, int cont_col, int masked, double la
         if (!h->row_fused) ypart_n = 0;
         if (h->w_ready) {   // wsyrk + level sums came from side2, C'C and (S^train C') from side3
             HIPCHECK(hipStreamWaitEvent(h->stream, h->ev_w[i], 0));
-            if (!(h->join_lean & 1)) HIPCHECK(hipStreamWaitEvent(h->stream, h->ev_prep, 0));
+            HIPCHECK(hipStreamWaitEvent(h->stream, h->ev_prep, 0));
         }
         if (!h->w_ready)
             if (int rg = launch_level_gram(h, i, h->stream, h->lvl_sum)) return rg;
@@ -1673,16 +1545,12 @@ hipError_t make_streams(insider_hip_handle *h)
     MS(hipStreamCreateWithFlags(&h->side, hipStreamNonBlocking));
     MS(hipStreamCreateWithFlags(&h->side2, hipStreamNonBlocking));
     MS(hipStreamCreateWithFlags(&h->side3, hipStreamNonBlocking));
-    MS(hipStreamCreateWithFlags(&h->lng, hipStreamNonBlocking));
-    MS(hipEventCreateWithFlags(&h->ev_long_go, EV_SYNC));
-    MS(hipEventCreateWithFlags(&h->ev_long_done, EV_SYNC));
     MS(hipEventCreateWithFlags(&h->ev_prep, EV_SYNC));
     MS(hipEventCreateWithFlags(&h->ev_c_ready, EV_SYNC));
     MS(hipEventCreateWithFlags(&h->ev_head, EV_SYNC));
     MS(hipEventCreateWithFlags(&h->ev_a_ready, EV_SYNC));
     MS(hipEventCreateWithFlags(&h->ev_qfull, EV_SYNC));
     MS(hipEventCreateWithFlags(&h->ev_qheld, EV_SYNC));
-    MS(hipEventCreateWithFlags(&h->ev_q_early, EV_SYNC));
     h->ev_w.assign((h->c > 0 ? h->c : 1) + h->m, nullptr);
     for (auto &ev : h->ev_w) MS(hipEventCreateWithFlags(&ev, EV_SYNC));
     MS(hipEventCreateWithFlags(&h->ev_cd_done, EV_SYNC));
@@ -1694,9 +1562,9 @@ hipError_t make_streams(insider_hip_handle *h)
 
 void destroy_streams(insider_hip_handle *h)
 {
-    for (hipStream_t *st : {&h->side, &h->side2, &h->side3, &h->lng}) { if (*st) (void)hipStreamDestroy(*st); *st = nullptr; }
-    for (hipEvent_t *ev : {&h->ev_long_go, &h->ev_long_done, &h->ev_prep, &h->ev_c_ready, &h->ev_head, &h->ev_a_ready, &h->ev_qfull, &h->ev_qheld, &h->ev_cd_done,
-                           &h->ev_side_done, &h->ev_tab, &h->ev_q_early}) { if (*ev) (void)hipEventDestroy(*ev); *ev = nullptr; }
+    for (hipStream_t *st : {&h->side, &h->side2, &h->side3}) { if (*st) (void)hipStreamDestroy(*st); *st = nullptr; }
+    for (hipEvent_t *ev : {&h->ev_prep, &h->ev_c_ready, &h->ev_head, &h->ev_a_ready, &h->ev_qfull, &h->ev_qheld, &h->ev_cd_done,
+                           &h->ev_side_done, &h->ev_tab}) { if (*ev) (void)hipEventDestroy(*ev); *ev = nullptr; }
     for (auto ev : h->ev_w) if (ev) (void)hipEventDestroy(ev);
     h->ev_w.clear();
     if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -1740,7 +1608,7 @@ void insider_hip_destroy(insider_hip_handle *h)
     if (!h) return;
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    for (hipStream_t st : {h->side, h->side2, h->side3, h->lng}) if (st) (void)hipStreamSynchronize(st);
+    for (hipStream_t st : {h->side, h->side2, h->side3}) if (st) (void)hipStreamSynchronize(st);
     if (h->comm) { (void)ncclCommDestroy(h->comm); h->comm = nullptr; }
     clear_events(h);
     free_workspace(h);
@@ -1764,14 +1632,12 @@ int insider_hip_clone(insider_hip_handle *src, insider_hip_handle **out)
     insider_hip_handle *h = new insider_hip_handle(*src);   // every data-set field and option; the rest is reset below
     forget_workspace(h);                                    // (the copied pointers are the source's buffers)
     h->post = nullptr;                                      // (likewise the post-hoc workspace)
-    h->stream = h->side = h->side2 = h->side3 = h->lng = nullptr;
-    h->ev_long_go = h->ev_long_done = h->ev_prep = h->ev_c_ready = h->ev_head = h->ev_a_ready = h->ev_qfull = h->ev_qheld = nullptr;
-    h->ev_cd_done = h->ev_side_done = h->ev_tab = h->ev_q_early = nullptr;
-    h->q_kb = 0;
+    h->stream = h->side = h->side2 = h->side3 = nullptr;
+    h->ev_prep = h->ev_c_ready = h->ev_head = h->ev_a_ready = h->ev_qfull = h->ev_qheld = nullptr;
+    h->ev_cd_done = h->ev_side_done = h->ev_tab = nullptr;
     h->ev_w.clear();
     for (auto *v : {&h->ev_col, &h->ev_row, &h->ev_cd, &h->ev_test}) v->clear();
-    h->side_pending = h->w_ready = h->qfull_pending = h->qheld_pending = h->long_pending = false;
-    h->q_kb = 0;
+    h->side_pending = h->w_ready = h->qfull_pending = h->qheld_pending = false;
     h->comm = nullptr;                                      // a sharded clone joins its own communicator (insider_hip_comm_init)
     for (double &v : h->prof) v = 0.0;
     h->steady_cd_ms = h->steady_col_ms = 0.0;
@@ -2328,19 +2194,14 @@ int insider_hip_set_option(insider_hip_handle *h, const char *name, double value
     else if (s == "row_merged") h->row_merged = (int)value;   // 1 = merged masked row update when the time model favours it (default), 2 = always, 0 = per-sample statistics
     else if (s == "row_gemm_waves") { h->wg_waves = std::max(64, (int)value); h->K = 0; }   // (re-plans the workspace)
     else if (s == "row_gemm") h->row_gemm = (int)value;       // 1 (default) = k_wgemm for covariates with >= 49 levels, 0 = k_wsyrk everywhere
-    else if (s == "row_head") h->row_head = (int)value;       // 1 (default) = the main chain's k_gene_u is dispatched behind the level Gram GEMM (launch_wsyrk_side)
     else if (s == "row_fused") h->row_fused = (int)value;     // 1 (default) = k_level_merged (one launch per covariate), 0 = k_level_pack / k_level_reduce / k_level_solve
     else if (s == "cd_cold_iters") h->cd_cold_iters = (int)value;   // outer iterations 0 .. value-1 of a call solve in passes
     else if (s == "cd_pass1") h->cd_pass_first = (int)value;        // sweep index where the first pass stops (0 = single pass)
     else if (s == "cd_pass_ratio") h->cd_pass_ratio = (int)value;   // each further pass stops at ratio x the previous limit
     else if (s == "list_fine") h->list_fine = (int)value;       // 1 (default) = per-entry statistics on v_mfma_f64_4x4x4 for 16 <= K <= 31, 0 = on 16x16x4
-    else if (s == "q_split") h->q_split = (int)value;             // 0 = both products in one piece behind the row phase
-    else if (s == "join_lean") h->join_lean = (int)value;         // experiment of round 5, off: bits 1 | 2 gain 0.6 % at c3 and cost c2 2.5 % (chained joins add their wake-up latencies)
     else if (s == "mm_fast") h->mm_fast = (int)value;             // 0 = k_mm_rows / k_mm_reduce as in round 4
     else if (s == "col_mfma4") h->col_mfma4 = (int)value;         // 1 = k_col_paircnt4 (K <= 31, factor rows fit LDS), 0 = k_col_paircnt
     else if (s == "cd_pairs") h->cd_pairs = (int)value;           // 1 (default) = sweeps routed through the blocks of two coordinate steps (K <= 30; same iterates), 0 = one step per block
-    else if (s == "cd_split") h->cd_split = (int)value;           // 2 = steady-state column steps run split (long genes first, on their own stream); 0 (default) = never (measured: no gain, see use_split)
-    else if (s == "cd_long_frac") h->cd_long_frac = value;        // at most this fraction of the genes counts as long (default 0.03)
     else if (s == "resid_stage_mb") h->resid_stage_mb = value;   // device buffer insider_hip_residual() copies out through (MB; at least 16 genes of the window)
     else if (s == "cd_variant") h->cd_variant = (int)value;   // 0 = register-resident (4 genes per wave; K <= 32, and 32 < K <= 48 with the third slot's columns in LDS), 1 = group kernel, 2 = row16 (LDS, K <= 48)
     else return fail(INSIDER_ERR_ARG, "unknown option " + s);
@@ -2359,7 +2220,6 @@ static int optimize_body(insider_hip_handle *h, double *const *A, double *C, int
     HIPCHECK(hipStreamSynchronize(h->side));
     HIPCHECK(hipStreamSynchronize(h->side2));
     HIPCHECK(hipStreamSynchronize(h->side3));
-    HIPCHECK(hipStreamSynchronize(h->lng));
     if ((rc = ensure_workspace(h, K))) return rc;
     const auto t_begin = std::chrono::steady_clock::now();
     clear_events(h);
@@ -2367,8 +2227,6 @@ static int optimize_body(insider_hip_handle *h, double *const *A, double *C, int
     h->side_pending = false;
     h->qfull_pending = false;
     h->qheld_pending = false;
-    h->q_kb = 0;
-    h->long_pending = false;
     const int masked = tuning == 1;
     if ((rc = upload_factors(h, A, C, K))) return rc;
 
@@ -2411,22 +2269,15 @@ static int optimize_body(insider_hip_handle *h, double *const *A, double *C, int
         if (masked && !use_merged(h, masked)) if ((rc = launch_row_stats(h, true))) return rc;
         // V = C A' of the covariates 1 .. c-1: what covariate 0's update reads.  Covariate 0's own columns are first read by
         // covariate 1's update, after they have been recomputed from the updated factors (below): not formed here
-#ifdef INSIDER_V_ALL   // (A/B builds: every column, as before round 3)
-        if (use_merged(h, masked)) if ((rc = launch_gene_v(h, 0, h->SL))) return rc;
-#else
         // (with continuous covariates on the merged form: their columns of V too — s_r carries A_c' z_r)
         if (use_merged(h, masked)) if ((rc = launch_gene_v(h, h->c > 1 ? h->lvl_off[1] : h->SLcat, h->SL))) return rc;
-#endif
-        if (use_merged(h, masked) && h->row_head) HIPCHECK(hipStreamWaitEvent(h->stream, h->ev_head, 0));   // launch_wsyrk_side
+        if (use_merged(h, masked)) HIPCHECK(hipStreamWaitEvent(h->stream, h->ev_head, 0));   // launch_wsyrk_side
         const bool cont_follow = inc_continuous && h->m > 0;
-        const int q_kb = use_merged(h, masked) ? q_split_boundary(h, masked, cont_follow) : 0;
         for (int i = 0; i < h->c; ++i) {
             const bool need_R = !(use_merged(h, masked) || unmasked_fused(h, masked)) || (i + 1 == h->c && !cont_follow);
             if ((rc = row_update(h, i, -1, masked, lambda1, need_R))) return rc;                // :339
             if (use_merged(h, masked) && (i + 1 < h->c || cont_follow))   // (the continuous columns read every categorical column of V)
                 if ((rc = launch_gene_v(h, h->lvl_off[i], h->lvl_off[i + 1]))) return rc;
-            if (q_kb && i + (cont_follow ? 1 : 2) == h->c)   // every block but the last is final: its part of Qfull / Qheld, beside the last update
-                if ((rc = launch_q_early(h, q_kb))) return rc;
         }
         if (cont_follow)
             for (int j = 0; j < h->m; ++j) {
@@ -2440,7 +2291,7 @@ static int optimize_body(insider_hip_handle *h, double *const *A, double *C, int
         const int checkpoint = iter % 10 == 0;
         if (alpha != 0.0 && iter == 0)   // later iterations: built on the side stream while the previous solve ran
             if ((rc = ensure_order_table(h, seed, iter, K, h->max_sweeps, h->order_mode, lambda2 * alpha, nullptr, 0))) return rc;
-        if (masked) if ((rc = launch_col_stats(h, true, use_split(h, masked, alpha, (int)iter)))) return rc;
+        if (masked) if ((rc = launch_col_stats(h, true))) return rc;
         if (alpha != 0.0) {
             h->order = h->order_buf[iter & 1];
             if (iter < max_iter) {   // the next iteration's table, from here on: beside this iteration's solve
@@ -2541,16 +2392,14 @@ int insider_hip_optimize(insider_hip_handle *h, double *const *A, double *C, int
     const int rc = optimize_body(h, A, C, inc_continuous, K, lambda1, lambda2, alpha, tuning, global_tol, sub_tol, max_iter,
                                  seed, out_train_rmse, out_test_rmse, out_loss, traj, traj_cap, out_traj_rows, out_iters);
     if (rc != INSIDER_OK && h && h->stream) {
-        // an early return leaves enqueued work on all three streams: drain them so that the next call starts clean
+        // an early return leaves enqueued work on every stream: drain them so that the next call starts clean
         const std::string keep = g_err;
         (void)hipSetDevice(h->device);
         (void)hipStreamSynchronize(h->stream);
         (void)hipStreamSynchronize(h->side);
         (void)hipStreamSynchronize(h->side2);
         (void)hipStreamSynchronize(h->side3);
-        (void)hipStreamSynchronize(h->lng);
-        h->side_pending = h->qfull_pending = h->qheld_pending = h->w_ready = h->long_pending = false;
-        h->q_kb = 0;
+        h->side_pending = h->qfull_pending = h->qheld_pending = h->w_ready = false;
         if (h->failflag) (void)hipMemset(h->failflag, 0, 4 * sizeof(int));
         clear_events(h);
         g_err = keep;
@@ -2659,12 +2508,10 @@ static int strong_cd_device(DevBufs &bufs, const double *dG, const double *dq, c
     const int rows = std::min<int64_t>(ms, INSIDER_PERM_PERIOD);   // one period of the order sequence (include/insider_perm.h)
     uint8_t *dord = nullptr;
     if ((rc = bufs.alloc(&dord, (size_t)(rows + 4) * ORDER_ROW))) return rc;   // + the look-ahead row
-    // debugging knob: INSIDER_CD_VARIANT=2 runs the LDS-resident row16 solver instead of the register-resident one, 1 the group kernel
-    const char *var = std::getenv("INSIDER_CD_VARIANT");
-    const int variant = var ? std::atoi(var) : 0;
-    const bool reg3 = reg3_path(K, lambda * alpha, variant);
+    const bool reg = K <= 32 && lambda * alpha > 0.0;   // the register-resident batch kernel
+    const bool reg3 = reg3_path(K, lambda * alpha);
     unsigned long long code_base = 0;
-    if (reg_pairs(reg_kmax(K)) && variant == 0 && lambda * alpha > 0.0) {   // the register-resident batch kernel will run: where are its code blocks?
+    if (reg && reg_pairs(reg_kmax(K))) {   // where are its code blocks?
         unsigned long long *dcb = nullptr;
         if ((rc = bufs.alloc(&dcb, 1))) return rc;
         HIPCHECK(hipMemset(dcb, 0, sizeof(unsigned long long)));
@@ -2693,13 +2540,8 @@ static int strong_cd_device(DevBufs &bufs, const double *dG, const double *dq, c
     HIPCHECK(hipEventCreate(&e1));
     bufs.events.push_back(e1);
     HIPCHECK(hipEventRecord(e0, 0));
-    const bool lds_variant = variant == 2;
     const size_t r16_bytes = (size_t)r16_lds_doubles(K) * sizeof(double);
-    if (K <= 16 && lds_variant)
-        hipLaunchKernelGGL((k_cd_batch_r16<1>), dim3(cdiv(nprob, 4)), dim3(64), r16_bytes, 0, dG, dq, dw, K, nprob, cd, db, ds);
-    else if (K <= 32 && lds_variant)
-        hipLaunchKernelGGL((k_cd_batch_r16<2>), dim3(cdiv(nprob, 4)), dim3(64), r16_bytes, 0, dG, dq, dw, K, nprob, cd, db, ds);
-    else if (K <= 32 && cd.la > 0.0) {   // (the register-resident solver's state is scaled by 1 / (2 lambda alpha))
+    if (reg) {   // (the register-resident solver's state is scaled by 1 / (2 lambda alpha))
         REG_DISPATCH(K, hipLaunchKernelGGL((k_cd_batch_reg<SL_, KM_>), dim3(cdiv(nprob, 4)), dim3(64), 0, 0, dG, dq, dw, K,
                                            nprob, cd, db, ds, (unsigned long long *)nullptr));
     } else if (K <= 16) hipLaunchKernelGGL((k_cd_batch<16, 4>), dim3(cdiv(nprob, 16)), dim3(256), 0, 0, dG, dq, dw, K, nprob, cd, db, ds);
@@ -2708,7 +2550,7 @@ static int strong_cd_device(DevBufs &bufs, const double *dG, const double *dq, c
         REG3_DISPATCH(K, hipLaunchKernelGGL((k_cd_batch_reg<SL_, KM_>), dim3(cdiv(nprob, 4)), dim3(64), 0, 0, dG, dq, dw, K,
                                             nprob, cd, db, ds, (unsigned long long *)nullptr));
     }
-    else if (K <= 48 && variant != 1) {   // lambda alpha = 0 or INSIDER_CD_VARIANT=2: the LDS-resident row16 solver (=1: one problem per wavefront)
+    else if (K <= 48) {   // lambda alpha = 0: the LDS-resident row16 solver
         if (int rl = r16_wide_lds(r16_bytes)) return rl;
         hipLaunchKernelGGL((k_cd_batch_r16<3>), dim3(cdiv(nprob, 4)), dim3(64), r16_bytes, 0, dG, dq, dw, K, nprob, cd, db, ds);
     }

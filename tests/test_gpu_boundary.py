@@ -283,3 +283,14 @@ def test_handle_facts_for_measurement():
     with pytest.raises(_lib.InsiderError):
         ds.info("no_such_key")
     ds.close()
+
+
+def test_removed_options_are_unknown():
+    # options of round-5 experiments that stayed off and were removed: rejected like any other unknown name
+    w = workloads.small(n=40, p=30, K=4)
+    ds = api.InsiderData(w.X, w.levels, w.M_train, w.M_test)
+    for name in ("cd_split", "cd_long_frac", "q_split", "join_lean", "row_head"):
+        with pytest.raises(_lib.InsiderError, match="unknown option") as e:
+            ds.set_option(name, 0)
+        assert e.value.status == _lib.ERR_ARG
+    ds.close()

@@ -331,18 +331,17 @@ def test_optimize_31_iterations(oracle, case, paths):
                                   (dict(n=60, p=16400, level_counts=(50, 4, 3), K=17, f=0.15, with_na=True), 0),
                                   (dict(n=48, p=16390, level_counts=(12, 5), K=6, f=0.2), 2)],
                          ids=["two-cov", "three-cov-K17-gemm", "ctns2"])
-def test_streaming_products_and_ticketed_statistics_at_many_genes(oracle, kw, m):
+def test_streaming_products_and_ticketed_statistics_vs_oracle_and_round4(oracle, kw, m):
     """From 16384 genes on the row phase's products run on k_mm_rows2 / k_mm_reduce2 (option mm_fast) and the pair-count
     statistics' resident blocks (768 at most) each take many genes by ticket — the suite's other oracle comparisons have a few
-    hundred genes and never reach either.  Few samples keep the oracle to seconds.  Against the oracle, against round 4's
-    kernels (mm_fast = 0, col_mfma4 = 0), and with the two experimental arrangements of round 5 (join_lean, q_split), which
-    may only reorder sums."""
+    hundred genes and never reach either.  Few samples keep the oracle to seconds.  Against the oracle and against round 4's
+    kernels (mm_fast = 0, col_mfma4 = 0)."""
     w = workloads.small(seed=77, **kw)
     rng = np.random.default_rng(6)
     Z = np.asfortranarray(rng.standard_normal((w.n, m))) if m else None
     U0 = [np.asfortranarray(rng.normal(0.0, 0.001, size=(m, w.K)))] if m else []
     out = {}
-    for name, opts in (("default", {}), ("round4", dict(mm_fast=0, col_mfma4=0)), ("joins", dict(join_lean=7)), ("qsplit", dict(q_split=1))):
+    for name, opts in (("default", {}), ("round4", dict(mm_fast=0, col_mfma4=0))):
         ds = api.InsiderData(w.X, w.levels, w.M_train, w.M_test, ctns_confounder=Z)
         for k, v in PATHS["pair"].items():
             ds.set_option(k, v)
@@ -360,10 +359,8 @@ def test_streaming_products_and_ticketed_statistics_at_many_genes(oracle, kw, m)
         assert relerr(got["column_factor"], ref["column_factor"]) < 1e-6, name
         for i, a in enumerate(ref["row_matrices"]):
             assert relerr(got["row_matrices"][f"factor{i}"], a) < 1e-6, (name, i)
-    for name in ("round4", "joins", "qsplit"):
-        np.testing.assert_allclose(out[name]["traj"][:, 1:8], out["default"]["traj"][:, 1:8], rtol=1e-10, equal_nan=True, err_msg=name)
-        assert relerr(out[name]["column_factor"], out["default"]["column_factor"]) < 1e-8, name
-    assert np.array_equal(out["joins"]["column_factor"], out["default"]["column_factor"])   # the joins change no arithmetic
+    np.testing.assert_allclose(out["round4"]["traj"][:, 1:8], out["default"]["traj"][:, 1:8], rtol=1e-10, equal_nan=True)
+    assert relerr(out["round4"]["column_factor"], out["default"]["column_factor"]) < 1e-8
 
 
 @pytest.mark.parametrize("opts", [dict(cd_variant=1), dict(cd_variant=2), dict(order_mode=1), dict(max_sweeps=7),
@@ -415,37 +412,6 @@ def test_multipass_column_solve_is_bit_identical(oracle, K, limits):
                           max_iter=4, sub_tol=1e-11, seed=9)
     assert relerr(multi["column_factor"], ref["column_factor"]) < 1e-6
     assert abs(tot_multi - ref["total_sweeps"]) <= max(3, 0.002 * ref["total_sweeps"])
-
-
-@pytest.mark.parametrize("K,frac", [(12, 0.03), (30, 0.1), (20, 0.25), (30, 0.001)])
-def test_split_column_step_is_bit_identical(oracle, K, frac):
-    """Steady-state outer iterations can run the column step split (option cd_split = 2; OFF by default): the genes predicted longest —
-    whole buckets of the launch order, at most cd_long_frac of the genes — get their statistics and their solve on a stream of
-    their own, ahead of the statistics of everyone else.  Every gene's record and solve are the same computations as in the
-    unsplit step, so factors, trajectory and sweep counts must be bit-identical (and agree with the oracle)."""
-    w = workloads.small(K=K, n=150, p=1500, level_counts=(12, 5), f=0.2, seed=40 + K)
-    ds = api.InsiderData(w.X, w.levels, w.M_train, w.M_test)
-    ds.set_option("profile", 1)
-    ds.set_option("col_factored", 3)            # the pair-count statistics (what c3 / c4 take): the split path's kernel
-    assert int(ds.info("col_stats_path")) == 2
-    kw = dict(tuning=1, max_iter=12, seed=9)
-    ds.set_option("cd_split", 0)
-    one = ds.optimize(*_cp(w), w.K, w.lam, w.lam, w.alpha, **kw)
-    sw_one, tot_one = ds.sweeps(), ds.profile()["sweeps"]
-    ds.set_option("cd_split", 2)                # forced (the default engages it by problem size)
-    ds.set_option("cd_long_frac", frac)
-    two = ds.optimize(*_cp(w), w.K, w.lam, w.lam, w.alpha, **kw)
-    sw_two, tot_two = ds.sweeps(), ds.profile()["sweeps"]
-    ds.close()
-    assert np.array_equal(one["column_factor"], two["column_factor"])
-    assert np.array_equal(one["traj"], two["traj"], equal_nan=True)
-    for i in range(len(w.A0)):
-        assert np.array_equal(one["row_matrices"][f"factor{i}"], two["row_matrices"][f"factor{i}"])
-    assert np.array_equal(sw_one, sw_two) and tot_one == tot_two
-    ref = oracle.optimize(w.X, w.levels, w.n_levels, w.A0, w.C0, w.M_train, w.M_test, w.lam, w.lam, w.alpha, tuning=1,
-                          max_iter=12, seed=9)
-    assert relerr(two["column_factor"], ref["column_factor"]) < 1e-6
-    np.testing.assert_allclose(two["traj"][:, 1:8], ref["traj"][:, 1:8], rtol=1e-9, equal_nan=True)
 
 
 @pytest.mark.parametrize("K,levels", [(9, (7, 4)), (30, (12, 5, 3)), (40, (6, 5))])

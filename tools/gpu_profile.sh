@@ -24,9 +24,5 @@ rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write -- python3 $R/b
 echo "profiles done"
 cd $R
 python3 tools/iter_timeline.py $OUT/prof_c3 6 > $OUT/c3_steady_iteration_timeline.txt 2>&1
-for S in 0 2; do
-  python3 tools/slab_c4_probe.py --split $S 8 > $OUT/slab8_split$S.log 2>&1; tail -1 $OUT/slab8_split$S.log
-done
-bash tools/slab_trace.sh 2 > $OUT/slab8_timeline_split2.txt 2>&1; head -1 $OUT/slab8_timeline_split2.txt
-bash tools/slab_trace.sh 0 > $OUT/slab8_timeline_split0.txt 2>&1; head -1 $OUT/slab8_timeline_split0.txt
+python3 tools/slab_c4_probe.py 8 > $OUT/slab8.log 2>&1; tail -1 $OUT/slab8.log
 echo PROFILE_DONE

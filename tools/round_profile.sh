@@ -25,7 +25,6 @@ cd $R
 python3 tools/iter_timeline.py $OUT/prof_c3 6 > $OUT/c3_steady_iteration_timeline.txt 2>&1
 python3 tools/trace_avg.py $OUT/prof_c3 > $OUT/c3_trace_avg.txt 2>&1
 python3 tools/slab_c4_probe.py 8 2>&1 | tail -1 > $OUT/slab8.log; cat $OUT/slab8.log
-bash tools/slab_trace.sh 0 > $OUT/slab8_timeline.txt 2>&1; tail -1 $OUT/slab8_timeline.txt
 bash tools/conc_probe.sh c1 6 2>&1 | tee $OUT/concurrent_grids.log
 bash tools/conc_probe.sh c2 4 2>&1 | tee -a $OUT/concurrent_grids.log
 bash tools/conc_probe.sh c3 2 2>&1 | tee -a $OUT/concurrent_grids.log
