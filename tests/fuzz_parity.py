@@ -24,7 +24,8 @@ def relerr(a, b):
 
 
 def draw_case(rng):
-    """The next case of the stream (None: the draw is not a valid data set — a level that never occurs)."""
+    """The next case of the stream (None: the draw is not a valid data set — a level that never occurs).  A case runs 0, 1, 3,
+    25 or 60 outer iterations; the long ones (>= 25) have at most 60 genes."""
     from insider_amd import workloads
     c = int(rng.integers(1, 5))
     levels = tuple(int(x) for x in rng.integers(1, 13, size=c))
@@ -50,7 +51,9 @@ def draw_case(rng):
                 cd_pass1=int(rng.choice([0, 32, 48, 64])), cd_pass_ratio=int(rng.choice([2, 3, 4])),
                 cd_cold_iters=int(rng.choice([1, 3, 9])))
     sub_tol = float(rng.choice([1e-5, 1e-5, 1e-8, 1e-11]))   # tight tolerances: hundreds of sweeps, so that passes really split solves
-    iters = int(rng.choice([0, 1, 3]))
+    iters = int(rng.choice([0, 1, 3, 25, 60]))   # 25, 60: down the decay ladder, into the steady-state gene schedule
+    if iters >= 25:
+        kw["p"] = min(kw["p"], 60)                # long fits on at most 60 genes: bounds what they add to the sweep
     seed = int(rng.integers(1, 1000))
     m = int(rng.choice([0, 0, 0, 1, 3]))   # continuous covariates (optimize_continuous_v2)
     if m:

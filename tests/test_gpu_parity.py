@@ -530,6 +530,137 @@ def test_global_tol_early_stop(oracle):
     ref = oracle.optimize(w.X, w.levels, w.n_levels, w.A0, w.C0, w.M_train, w.M_test, w.lam, w.lam, w.alpha,
                           max_iter=200, global_tol=1e-3, seed=1)
     assert got["iters"] == ref["iters"] and got["traj"].shape == ref["traj"].shape
+    assert ref["traj"][:, 9].min() <= 1e-3                            # the case reaches the steady-state schedule
+    assert np.array_equal(got["traj"][:, 9], ref["traj"][:, 9])
+    np.testing.assert_allclose(got["traj"][:, 1:8], ref["traj"][:, 1:8], rtol=1e-9, equal_nan=True)
+    for i, a in enumerate(ref["row_matrices"]):
+        assert relerr(got["row_matrices"][f"factor{i}"], a) < 1e-7, i
+    assert relerr(got["column_factor"], ref["column_factor"]) < 1e-7
+    assert got["loss"] == pytest.approx(ref["loss"], rel=1e-9)
+
+
+# ---- fits to convergence: down the decay ladder (src/optimize.cpp:389-403) ------------------------------------------------
+# max_iter = 400, global_tol = 1e-9 (the reference's fit runs with 1e-9): every case but ridge runs all 401 iterations with the
+# inner tolerance sub_tol * decay at 1e-3 .. 1e-5 of its start, where the sweep kernel schedules genes by the previous
+# iteration's sweep counts.  The tolerances rest on the oracle's own two formulations (tests/test_oracle_optimize.py::
+# test_covariance_form_tracks_residual_form_to_convergence): covariance-form vs residual-form CD over these fits differ by
+# 1e-14 (small K) to 3e-10 (K = 40) and follow the same decay ladder at every checkpoint.
+# case -> (workload arguments, the lowest decay the oracle's fit reaches)
+LONG_CASES = {
+    "plain": (CASES["plain"], 1e-4),
+    "unmasked": (CASES["unmasked"], 1e-4),
+    "interaction": (CASES["interaction"], 1e-5),
+    "na": (CASES["na"], 1e-4),
+    "ridge": (CASES["ridge"], 1e-6),               # stops on global_tol at iteration 400
+    "three_cov": (CASES["three_cov"], 1e-4),
+    "lasso": (CASES["lasso"], 1e-4),
+    "k17": (CASES["k17"], 1e-3),
+    "k30": (dict(K=30, n=150, p=40), 1e-3),       # k_cd_cols_reg<2,30>
+    "k40": (dict(K=40, n=150, p=30), 1e-3),       # three slots, the third in LDS
+}
+LONG_FIT = dict(max_iter=400, global_tol=1e-9, seed=1)
+_long_refs = {}
+
+
+def _long_ref(oracle, case):
+    """The oracle's fit of a case, once per module (about 1-2.5 s each on the CPU)."""
+    if case not in _long_refs:
+        w = workloads.small(**LONG_CASES[case][0])
+        _long_refs[case] = oracle.optimize(w.X, w.levels, w.n_levels, w.A0, w.C0, w.M_train, w.M_test, w.lam, w.lam, w.alpha,
+                                           tuning=w.tuning, **LONG_FIT)
+    return _long_refs[case]
+
+
+@pytest.mark.parametrize("case,paths", [(c, pth) for c in list(LONG_CASES)[:8] for pth in PATHS]
+                         + [(c, "default") for c in ("plain", "k30", "k40")])
+def test_fit_to_convergence_vs_oracle(oracle, case, paths):
+    """Every value of a 400-iteration fit against the oracle; "default" leaves the path to the cost model and counts sweeps
+    (profile = 1): at decay 1e-4 the per-gene sweep counts are what the steady-state schedule is built from."""
+    w = workloads.small(**LONG_CASES[case][0])
+    ref = _long_ref(oracle, case)
+    assert ref["traj"][:, 9].min() <= LONG_CASES[case][1]              # the case still reaches the bottom of its ladder
+    ds = api.InsiderData(w.X, w.levels, w.M_train, w.M_test)
+    for k, v in (dict(profile=1) if paths == "default" else PATHS[paths]).items():
+        ds.set_option(k, v)
+    got = ds.optimize(*_cp(w), w.K, w.lam, w.lam, w.alpha, tuning=w.tuning, **LONG_FIT)
+    sweeps = ds.profile()["sweeps"]
+    ds.close()
+    assert got["iters"] == ref["iters"]
+    assert np.array_equal(got["traj"][:, 0], ref["traj"][:, 0])
+    assert np.array_equal(got["traj"][:, 9], ref["traj"][:, 9])       # same decay at every checkpoint
+    np.testing.assert_allclose(got["traj"][:, 1:8], ref["traj"][:, 1:8], rtol=1e-9, equal_nan=True)
+    for i, a in enumerate(ref["row_matrices"]):
+        assert relerr(got["row_matrices"][f"factor{i}"], a) < 1e-7, i
+    assert relerr(got["column_factor"], ref["column_factor"]) < 1e-7
+    assert got["loss"] == pytest.approx(ref["loss"], rel=1e-9)
+    if w.tuning == 0:
+        assert np.isnan(got["test_rmse"])
+    if paths == "default":
+        assert abs(sweeps - ref["total_sweeps"]) <= max(3, 0.002 * ref["total_sweeps"]), (sweeps, ref["total_sweeps"])
+
+
+def test_fit_to_convergence_with_continuous_covariates(oracle):
+    """The m = 2 case of test_optimize_with_continuous_covariates over 200 iterations: the continuous columns' scalar CD
+    (src/optimize.cpp:76-137) at every outer iteration while the ladder goes down to decay 1e-3."""
+    w = workloads.small(with_na=True)
+    rng = np.random.default_rng(8)
+    Z = np.asfortranarray(rng.standard_normal((w.n, 2)))
+    U0 = np.asfortranarray(rng.normal(0.0, 0.001, size=(2, w.K)))
+    ds = api.InsiderData(w.X, w.levels, w.M_train, w.M_test, ctns_confounder=Z)
+    A, C = _cp(w)
+    kw = dict(tuning=w.tuning, max_iter=200, global_tol=1e-9, seed=5)
+    got = ds.optimize(A + [U0.copy(order="F")], C, w.K, w.lam, w.lam, w.alpha, inc_continuous=1, **kw)
+    ds.close()
+    ref = oracle.optimize(w.X, w.levels, w.n_levels, w.A0 + [U0], w.C0, w.M_train, w.M_test, w.lam, w.lam, w.alpha, ctns=Z,
+                          **kw)
+    assert ref["traj"][:, 9].min() <= 1e-3
+    assert got["iters"] == ref["iters"]
+    assert np.array_equal(got["traj"][:, 9], ref["traj"][:, 9])
+    np.testing.assert_allclose(got["traj"][:, 1:8], ref["traj"][:, 1:8], rtol=1e-9, equal_nan=True)
+    for i, a in enumerate(ref["row_matrices"]):
+        assert relerr(got["row_matrices"][f"factor{i}"], a) < 1e-6, i
+    assert relerr(got["column_factor"], ref["column_factor"]) < 1e-6
+
+
+def test_long_fit_is_independent_of_handle_history():
+    """Gene order and schedule (perm_early, gene_perm, sched_cnt: kept on the handle from one optimize() to the next while K
+    stays, as tune() uses it) decide when a gene's solve runs, never what it computes: a 400-iteration fit is bit-identical on
+    (a) a fresh handle, (b) a handle that first ran another 400-iteration fit of the same K, (c) the same with the cold
+    iterations solved in passes, (d) a clone of (b)."""
+    w = workloads.small()
+    kw = dict(tuning=1, **LONG_FIT)
+
+    def fit(ds):
+        return ds.optimize(*_cp(w), w.K, w.lam, w.lam, w.alpha, **kw)
+
+    def prior(ds):   # another fit of the same K: leaves its own order history behind
+        ds.optimize(*_cp(w), w.K, 0.7, 0.7, 0.8, **kw)
+
+    runs = {}
+    ds = api.InsiderData(w.X, w.levels, w.M_train, w.M_test)
+    runs["fresh"] = fit(ds)
+    ds.close()
+    ds = api.InsiderData(w.X, w.levels, w.M_train, w.M_test)
+    prior(ds)
+    cl = ds.clone()
+    runs["after_fit"] = fit(ds)
+    runs["clone"] = fit(cl)
+    cl.close()
+    ds.close()
+    ds = api.InsiderData(w.X, w.levels, w.M_train, w.M_test)
+    ds.set_option("cd_cold_iters", 3)
+    ds.set_option("cd_pass1", 32)
+    prior(ds)
+    runs["after_fit_multipass"] = fit(ds)
+    ds.close()
+    a = runs["fresh"]
+    assert a["traj"][:, 9].min() <= 1e-4
+    for name, r in runs.items():
+        assert r["iters"] == a["iters"], name
+        assert np.array_equal(r["traj"], a["traj"], equal_nan=True), name
+        assert np.array_equal(r["column_factor"], a["column_factor"]), name
+        for i in range(len(w.A0)):
+            assert np.array_equal(r["row_matrices"][f"factor{i}"], a["row_matrices"][f"factor{i}"]), (name, i)
 
 
 def test_bad_arguments_return_status():

@@ -169,3 +169,35 @@ def test_optimize_with_continuous_matches_numpy(oracle, kw):
     for a, b in zip(res_c["row_matrices"], res_n["row_matrices"]):
         np.testing.assert_allclose(a, b, rtol=1e-8, atol=1e-10)
     np.testing.assert_allclose(res_c["column_factor"], res_n["column_factor"], rtol=1e-8, atol=1e-10)
+
+
+def _relerr(a, b):
+    return np.linalg.norm(np.asarray(a) - np.asarray(b)) / max(np.linalg.norm(np.asarray(b)), 1e-300)
+
+
+@pytest.mark.parametrize("kw,lowest", [(dict(), 1e-4), (dict(interaction_idx=(1, 2)), 1e-5), (dict(alpha=0.0), 1e-6)],
+                         ids=["plain", "interaction", "ridge"])
+def test_covariance_form_tracks_residual_form_to_convergence(oracle, kw, lowest):
+    """The library's CD runs in covariance form, the parity oracle in residual form (the reference's).  Over 400-iteration fits
+    down the decay ladder the two formulations stay at rounding level and take the same decay at every checkpoint: what the
+    GPU tolerances of test_gpu_parity.py::test_fit_to_convergence_vs_oracle rest on."""
+    w = W.small(**kw)
+    res = {}
+    for form in (0, 1):
+        oracle.set_cd_form(form)
+        try:
+            res[form] = oracle.optimize(w.X, w.levels, w.n_levels, w.A0, w.C0, w.M_train, w.M_test, w.lam, w.lam, w.alpha,
+                                        tuning=w.tuning, max_iter=400, global_tol=1e-9, seed=1)
+        finally:
+            oracle.set_cd_form(0)
+    r, c = res[0], res[1]
+    assert r["traj"][:, 9].min() <= lowest
+    assert c["iters"] == r["iters"]
+    assert np.array_equal(c["traj"][:, 9], r["traj"][:, 9])
+    assert np.array_equal(c["traj"][:, 0], r["traj"][:, 0])
+    np.testing.assert_allclose(c["traj"][:, 1:8], r["traj"][:, 1:8], rtol=1e-12, atol=0, equal_nan=True)
+    # column 8, the loss decrease between checkpoints, is a difference of two losses: rounding level of the loss itself
+    np.testing.assert_allclose(c["traj"][:, 8], r["traj"][:, 8], rtol=0, atol=1e-12 * np.nanmax(r["traj"][:, 7]), equal_nan=True)
+    assert _relerr(c["column_factor"], r["column_factor"]) < 1e-12
+    for a, b in zip(c["row_matrices"], r["row_matrices"]):
+        assert _relerr(a, b) < 1e-12
