@@ -312,7 +312,10 @@ int insider_hip_get_profile(insider_hip_handle *h, double *out12);
  * "cd_ms_steady" / "col_stats_ms_steady" (option "profile": mean HIP-event time per outer iteration from iteration 5 on of
  * the last optimize(), i.e. without the cold start), "cap_hits" / "max_gene_sweeps" (of the last optimize() / optimize_col():
  * elastic-net solves ended by "max_sweeps" instead of convergence — must be 0 to match the reference, which has no cap — and
- * the longest solve in sweeps), "max_sweeps". */
+ * the longest solve in sweeps), "max_sweeps", "col_solver" / "col_eval" (the kernel the last column solve launched for the solve,
+ * and for the evaluation pass after it; 0 = none: 1 k_ridge_cols_reg, 2 k_ridge_cols, 3 k_cd_cols_reg with one or two slots,
+ * 4 k_cd_cols_reg with three slots, 5 k_cd_cols<16,4>, 6 k_cd_cols<32,2>, 7 k_cd_cols<64,1>, 8 / 9 / 10 k_cd_cols_r16<1 / 2 / 3>),
+ * "col_ridge_fallback" (1: the last ridge solve also launched k_ridge_cols for the genes k_ridge_cols_reg marked). */
 int insider_hip_get_info(insider_hip_handle *h, const char *name, double *out);
 
 /* Diagnostics: copy an internal per-gene array to the host: "cd_pass_slot" (uint32 x p: what the last limited pass of a

@@ -29,6 +29,9 @@ SYMBOLS = (
     "insider_hip_optimize_continuous_v2", "insider_hip_residual", "insider_hip_interaction_glm",
 )
 COMM_ID_BYTES = 128
+# insider_hip_get_info("col_solver" / "col_eval"): the column-solve kernel behind each code (include/insider_hip.h)
+COL_SOLVERS = ("none", "ridge_reg", "ridge", "cd_reg", "cd_reg3", "cd_cols16", "cd_cols32", "cd_cols64", "cd_r16_1", "cd_r16_2",
+               "cd_r16_3")
 
 
 class InsiderError(RuntimeError):

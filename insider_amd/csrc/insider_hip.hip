@@ -238,6 +238,9 @@ struct insider_hip_handle {
     // of the last optimize() / optimize_col(): genes whose elastic-net solve was ended by max_sweeps, not by convergence
     // (the reference has no cap, src/coordinate_descent.cpp:86-114), and the longest solve in sweeps
     int cap_hits = 0, max_gene_sweeps = 0;
+    // of the last column solve: the kernel that ran the solve and the one that ran the evaluation pass after it (ColSolver), and
+    // whether the ridge solve launched the general-route fallback for the genes the register kernel marked
+    int col_solver = 0, col_eval = 0, col_ridge_fallback = 0;
     // post-hoc interaction GLM / residual (insider_hip_residual, insider_hip_interaction_glm): a workspace of its own, so
     // that nothing insider_hip_optimize() reads is touched; allocated on first use, grown on demand, freed with the handle
     PostWs *post = nullptr;
@@ -822,6 +825,13 @@ int launch_col_stats(insider_hip_handle *h, bool timed)
     return t.end(h, h->ev_col);
 }
 
+// the kernels launch_col_solve() can launch, as insider_hip_get_info("col_solver" / "col_eval") reports them
+// (include/insider_hip.h; insider_amd/_lib.py mirrors the names)
+enum ColSolver {
+    CS_NONE = 0, CS_RIDGE_REG = 1, CS_RIDGE = 2, CS_CD_REG = 3, CS_CD_REG3 = 4, CS_CD_COLS16 = 5, CS_CD_COLS32 = 6,
+    CS_CD_COLS64 = 7, CS_CD_R16_1 = 8, CS_CD_R16_2 = 9, CS_CD_R16_3 = 10
+};
+
 // column update from the statistics: elastic-net CD (alpha > 0) or ridge (alpha == 0), or evaluation only
 int launch_col_solve(insider_hip_handle *h, int masked, bool solve, double lambda, double alpha, double tol,
                      int checkpoint, bool timed, int outer_iter = -1, bool side = false)
@@ -842,6 +852,7 @@ int launch_col_solve(insider_hip_handle *h, int masked, bool solve, double lambd
     if (rc) return rc;
     bool eval_after = false, fused_bucket = false;
     ColArgs eval_args;
+    h->col_solver = h->col_eval = h->col_ridge_fallback = CS_NONE;
     if (alpha == 0.0) {
         RidgeArgs a;
         a.stat = masked ? h->stat_col : nullptr;
@@ -871,13 +882,16 @@ int launch_col_solve(insider_hip_handle *h, int masked, bool solve, double lambd
                 HIPCHECK(hipMemsetAsync(h->failflag + 1, 0, sizeof(int), h->stream));
             }
             REG_DISPATCH(h->K, hipLaunchKernelGGL((k_ridge_cols_reg<SL_, KM_>), dim3(cdiv(h->p, 4)), dim3(64), 0, h->stream, a));
+            h->col_solver = CS_RIDGE_REG;
             KCHECK();
             if (solve) {   // genes whose system was not positive definite: solve(..., likely_sympd)'s general route
                 a.only_marked = 1;
                 hipLaunchKernelGGL((k_ridge_cols<1>), dim3((unsigned)h->p), dim3(64), 0, h->stream, a);   // unmarked genes exit at once
+                h->col_ridge_fallback = 1;
             }
         } else {
             hipLaunchKernelGGL((k_ridge_cols<1>), dim3((unsigned)h->p), dim3(64), 0, h->stream, a);
+            h->col_solver = CS_RIDGE;
         }
         KCHECK();
         if (solve) HIPCHECK(hipMemsetAsync(h->sweeps, 0, (size_t)h->p * sizeof(int), h->stream));
@@ -955,7 +969,10 @@ int launch_col_solve(insider_hip_handle *h, int masked, bool solve, double lambd
                 a.pass_slot = npass ? h->cd_pass_slot : nullptr;
                 a.bucket_cnt = limit ? h->cd_pass_cnt : nullptr;
                 if (limit) HIPCHECK(hipMemsetAsync(h->cd_pass_cnt, 0, CD_BUCKETS * sizeof(int), h->stream));
-                if (solve) { REG_ANY_DISPATCH(h->K, hipLaunchKernelGGL((k_cd_cols_reg<SL_, KM_, true>), dim3(cdiv(h->p, 4)), dim3(64), 0, h->stream, a)); }
+                if (solve) {
+                    REG_ANY_DISPATCH(h->K, hipLaunchKernelGGL((k_cd_cols_reg<SL_, KM_, true>), dim3(cdiv(h->p, 4)), dim3(64), 0, h->stream, a);
+                                           h->col_solver = SL_ == 3 ? CS_CD_REG3 : CS_CD_REG);
+                }
                 KCHECK();
                 if (!limit) break;
                 int *count_out = h->cd_pass_cnt + CD_BUCKETS + (pass & 1);
@@ -970,20 +987,29 @@ int launch_col_solve(insider_hip_handle *h, int masked, bool solve, double lambd
             }
             eval_after = checkpoint != 0;
             eval_args = a;
-        } else if (h->cd_variant == 2 && h->K <= 16)
+        } else if (h->cd_variant == 2 && h->K <= 16) {
             hipLaunchKernelGGL((k_cd_cols_r16<1>), dim3(cdiv(h->p, 4)), dim3(64), r16_bytes, h->stream, a);
-        else if (h->cd_variant == 2 && h->K <= 32)
+            h->col_solver = CS_CD_R16_1;
+        } else if (h->cd_variant == 2 && h->K <= 32) {
             hipLaunchKernelGGL((k_cd_cols_r16<2>), dim3(cdiv(h->p, 4)), dim3(64), r16_bytes, h->stream, a);
-        else if (h->K <= 16) hipLaunchKernelGGL((k_cd_cols<16, 4>), dim3(cdiv(h->p, 16)), dim3(256), 0, h->stream, a);
-        else if (h->K <= 32) hipLaunchKernelGGL((k_cd_cols<32, 2>), dim3(cdiv(h->p, 4)), dim3(128), 0, h->stream, a);
-        else if (h->cd_variant != 1 && h->K <= 48) {
+            h->col_solver = CS_CD_R16_2;
+        } else if (h->K <= 16) {
+            hipLaunchKernelGGL((k_cd_cols<16, 4>), dim3(cdiv(h->p, 16)), dim3(256), 0, h->stream, a);
+            h->col_solver = CS_CD_COLS16;
+        } else if (h->K <= 32) {
+            hipLaunchKernelGGL((k_cd_cols<32, 2>), dim3(cdiv(h->p, 4)), dim3(128), 0, h->stream, a);
+            h->col_solver = CS_CD_COLS32;
+        } else if (h->cd_variant != 1 && h->K <= 48) {
             // 32 < K <= 48 when the register-resident kernel's three-slot form does not apply (cd_variant = 2, or no l1 term): four genes
             // per wavefront with the whole Gram matrices in LDS (row16 kernel, three coordinate slots per lane).  Beyond 48 a CU's LDS
             // holds one such wave and the kernel below is faster; it also stays as cd_variant = 1 (cross-check)
             if (int rl = r16_wide_lds(r16_bytes)) return rl;
             hipLaunchKernelGGL((k_cd_cols_r16<3>), dim3(cdiv(h->p, 4)), dim3(64), r16_bytes, h->stream, a);
+            h->col_solver = CS_CD_R16_3;
+        } else {
+            hipLaunchKernelGGL((k_cd_cols<64, 1>), dim3((unsigned)h->p), dim3(64), 0, h->stream, a);
+            h->col_solver = CS_CD_COLS64;
         }
-        else hipLaunchKernelGGL((k_cd_cols<64, 1>), dim3((unsigned)h->p), dim3(64), 0, h->stream, a);
         KCHECK();
     }
     if ((rc = t.end(h, h->ev_cd))) return rc;
@@ -993,11 +1019,13 @@ int launch_col_solve(insider_hip_handle *h, int masked, bool solve, double lambd
         eval_args.resume = 0;
         if (h->K <= 32) {
             REG_DISPATCH(h->K, hipLaunchKernelGGL((k_cd_cols_reg<SL_, KM_, false>), dim3(cdiv(h->p, 4)), dim3(64), 0, h->stream, eval_args));
+            h->col_eval = CS_CD_REG;
         } else {   // three slots: the row16 kernel's evaluation part (the sweep kernel's registers are all taken)
             const size_t eb = (size_t)r16_lds_doubles(h->K) * sizeof(double);
             if (int rl = r16_wide_lds(eb)) return rl;
             eval_args.mode = COL_EVAL;
             hipLaunchKernelGGL((k_cd_cols_r16<3>), dim3(cdiv(h->p, 4)), dim3(64), eb, h->stream, eval_args);
+            h->col_eval = CS_CD_R16_3;
         }
         KCHECK();
     }
@@ -2812,6 +2840,9 @@ int insider_hip_get_info(insider_hip_handle *h, const char *name, double *out)
     else if (s == "cap_hits") *out = h->cap_hits;                   // last optimize() / optimize_col(): solves ended by max_sweeps
     else if (s == "max_gene_sweeps") *out = h->max_gene_sweeps;     // ... and the longest solve, in sweeps
     else if (s == "max_sweeps") *out = h->max_sweeps;
+    else if (s == "col_solver") *out = h->col_solver;               // last column solve: the kernel that ran it (ColSolver) ...
+    else if (s == "col_eval") *out = h->col_eval;                   // ... and the one that ran its evaluation pass (0 = none)
+    else if (s == "col_ridge_fallback") *out = h->col_ridge_fallback;   // ... and whether the ridge solve launched the general route
     else if (s == "cd_ms_steady") *out = h->steady_cd_ms;           // option "profile": mean over outer iterations >= 5 of the last call
     else if (s == "col_stats_ms_steady") *out = h->steady_col_ms;
     else if (s == "col_mfma_per_gene") {
