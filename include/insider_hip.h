@@ -315,7 +315,18 @@ int insider_hip_get_profile(insider_hip_handle *h, double *out12);
  * the longest solve in sweeps), "max_sweeps", "col_solver" / "col_eval" (the kernel the last column solve launched for the solve,
  * and for the evaluation pass after it; 0 = none: 1 k_ridge_cols_reg, 2 k_ridge_cols, 3 k_cd_cols_reg with one or two slots,
  * 4 k_cd_cols_reg with three slots, 5 k_cd_cols<16,4>, 6 k_cd_cols<32,2>, 7 k_cd_cols<64,1>, 8 / 9 / 10 k_cd_cols_r16<1 / 2 / 3>),
- * "col_ridge_fallback" (1: the last ridge solve also launched k_ridge_cols for the genes k_ridge_cols_reg marked). */
+ * "col_ridge_fallback" (1: the last ridge solve also launched k_ridge_cols for the genes k_ridge_cols_reg marked),
+ * "row_kernels" (a bit mask of the row-phase kernel forms the last optimize() / optimize_row() launched, reset at the start of
+ * each; set on the host at each launch site.  Level Gram sums: bit 0 wgemm4, 1 wgemm5, 2 wgemm6, 3 wgemm7 (k_wgemm<LT>),
+ * 4 wgemm_chunks (a k_wgemm launch with more than one level-tile chunk, grid.z > 1), 5 wsyrk (k_wsyrk<NB>; neither wsyrk nor a
+ * wgemm bit: no held-out entry), 6 gram_side (level Gram sums on optimize()'s second side stream).  u: 7 gene_u_cnt
+ * (k_gene_u_cnt), 8 gene_u (k_gene_u), 9 gene_uc (k_gene_uc, a continuous column).  Record tail + equations: 10 merged_solve
+ * (k_level_merged with the ridge solve), 11 merged (k_level_merged without it), 12 merged_zero (k_level_merged on the zero
+ * record of tuning = 0), 13 pack_reduce (k_level_pack + k_level_reduce).  Per-sample path and solves: 14 list_stats4
+ * (k_list_stats4, row side), 15 list_stats (k_list_stats<NB>, row side), 16 level_partial (k_level_partial + k_level_sum +
+ * k_level_reduce), 17 level_solve (k_level_solve), 18 cont_cd (k_cont_cd).  Products of the row update (not the row prep):
+ * V = C A' 19 mm_rows2 (k_mm_rows2), 20 mm_rows (k_mm_rows); Y = U'C 21 mm_reduce2_2 (k_mm_reduce2<NB,2>), 22 mm_reduce2_4
+ * (k_mm_reduce2<NB,4>), 23 mm_reduce (k_mm_reduce)). */
 int insider_hip_get_info(insider_hip_handle *h, const char *name, double *out);
 
 /* Diagnostics: copy an internal per-gene array to the host: "cd_pass_slot" (uint32 x p: what the last limited pass of a

@@ -32,6 +32,12 @@ COMM_ID_BYTES = 128
 # insider_hip_get_info("col_solver" / "col_eval"): the column-solve kernel behind each code (include/insider_hip.h)
 COL_SOLVERS = ("none", "ridge_reg", "ridge", "cd_reg", "cd_reg3", "cd_cols16", "cd_cols32", "cd_cols64", "cd_r16_1", "cd_r16_2",
                "cd_r16_3")
+# insider_hip_get_info("row_kernels"): the row-phase kernel form behind each bit, bit 0 first (include/insider_hip.h)
+ROW_KERNELS = ("wgemm4", "wgemm5", "wgemm6", "wgemm7", "wgemm_chunks", "wsyrk", "gram_side",
+               "gene_u_cnt", "gene_u", "gene_uc",
+               "merged_solve", "merged", "merged_zero", "pack_reduce",
+               "list_stats4", "list_stats", "level_partial", "level_solve", "cont_cd",
+               "mm_rows2", "mm_rows", "mm_reduce2_2", "mm_reduce2_4", "mm_reduce")
 
 
 class InsiderError(RuntimeError):

@@ -241,6 +241,8 @@ struct insider_hip_handle {
     // of the last column solve: the kernel that ran the solve and the one that ran the evaluation pass after it (ColSolver), and
     // whether the ridge solve launched the general-route fallback for the genes the register kernel marked
     int col_solver = 0, col_eval = 0, col_ridge_fallback = 0;
+    // of the last optimize() / optimize_row(): one bit per row-phase kernel form it launched (RowKernel)
+    uint64_t row_kernels = 0;
     // post-hoc interaction GLM / residual (insider_hip_residual, insider_hip_interaction_glm): a workspace of its own, so
     // that nothing insider_hip_optimize() reads is touched; allocated on first use, grown on demand, freed with the handle
     PostWs *post = nullptr;
@@ -291,6 +293,18 @@ void free_workspace(insider_hip_handle *h)
         if (*slot) (void)hipFree(*slot);
     forget_workspace(h);
 }
+
+// the kernel forms the row phase can launch, as insider_hip_get_info("row_kernels") reports them: bit RK_* is set on the host
+// where its form is launched (include/insider_hip.h; insider_amd/_lib.py ROW_KERNELS names them in this order)
+enum RowKernel {
+    RK_WGEMM4 = 0, RK_WGEMM5, RK_WGEMM6, RK_WGEMM7, RK_WGEMM_CHUNKS, RK_WSYRK, RK_GRAM_SIDE,   // level Gram sums
+    RK_GENE_U_CNT, RK_GENE_U, RK_GENE_UC,                                                       // u
+    RK_MERGED_SOLVE, RK_MERGED, RK_MERGED_ZERO, RK_PACK_REDUCE,                                 // record tail + equations (+ solve)
+    RK_LIST_STATS4, RK_LIST_STATS, RK_LEVEL_PARTIAL, RK_LEVEL_SOLVE, RK_CONT_CD,               // per-sample statistics, solves
+    RK_MM_ROWS2, RK_MM_ROWS, RK_MM_REDUCE2_2, RK_MM_REDUCE2_4, RK_MM_REDUCE                     // V = C A', Y = U'C
+};
+inline uint64_t rk_bit(RowKernel k) { return 1ull << (int)k; }
+inline void row_mark(insider_hip_handle *h, RowKernel k) { h->row_kernels |= rk_bit(k); }
 
 // The weighted SYRK of covariate i as a GEMM over genes (k_wgemm, insider_row_merged.hpp)?  Needs the static half-count table
 // of the pair-count statistics; pays when the covariate has at least four tiles of 16 levels and the GEMM needs clearly fewer
@@ -446,8 +460,9 @@ int ensure_workspace(insider_hip_handle *h, int K)
         default: { constexpr int NB_ = 4; constexpr int WPB_ = 1; __VA_ARGS__; } break;  \
     }
 
+// mark: when given, the bit of the form launched (RK_LIST_STATS4 / RK_LIST_STATS) is or'ed into it
 int launch_list_stats(insider_hip_handle *h, bool cols, int nseg, const double *F, double *stat,
-                      const double *base = nullptr)
+                      const double *base = nullptr, uint64_t *mark = nullptr)
 {
     const int units = cols ? (int)h->p : (int)h->n;
     const int64_t f_rows = cols ? h->n : h->p;
@@ -471,11 +486,13 @@ int launch_list_stats(insider_hip_handle *h, bool cols, int nseg, const double *
         }
 #undef LS4
         KCHECK();
+        if (mark) *mark |= rk_bit(RK_LIST_STATS4);
         return INSIDER_OK;
     }
     NB_DISPATCH(h->NB, hipLaunchKernelGGL((k_list_stats<NB_, WPB_>), dim3(cdiv(items, WPB_)), dim3(WPB_ * 64), 0,
                                            h->stream, ptr, lidx, lval, units, nseg, F, f_rows, stat, base, h->K));
     KCHECK();
+    if (mark) *mark |= rk_bit(RK_LIST_STATS);
     return INSIDER_OK;
 }
 
@@ -514,8 +531,9 @@ int launch_mm_rows_kp(insider_hip_handle *h, const double *X, int64_t ldx, int M
 
 // part[slab][L][KP] = sum over slabs of MM_SLAB rows of X[m][l] Y[m][n], then the fixed-order sum over slabs -> out[L][KP]
 // out == nullptr: the partial sums are left in `part` for the consumer to add up (k_level_merged); returns the slab count in *nslab
+// mark: when given, the bit of the form launched (RK_MM_REDUCE2_2 / RK_MM_REDUCE2_4 / RK_MM_REDUCE) is or'ed into it
 int launch_mm_reduce_kp(insider_hip_handle *h, const double *X, int64_t ldx, const double *Y, int M, int L, double *part,
-                        double *out, hipStream_t st = nullptr, int *nslab = nullptr)
+                        double *out, hipStream_t st = nullptr, int *nslab = nullptr, uint64_t *mark = nullptr)
 {
     if (!st) st = h->stream;
     const int slabs = cdiv(M, MM_SLAB);
@@ -527,16 +545,23 @@ int launch_mm_reduce_kp(insider_hip_handle *h, const double *X, int64_t ldx, con
                        MM_SLAB, L, h->KP, part, h->KP)
         NB_DISPATCH(h->NB, {
             (void)WPB_;
-            if (lt <= 2 || h->mm_fast == 2 || NB_ > 2) MR2(NB_, 2);
-            else MR2(NB_, 4);
+            if (lt <= 2 || h->mm_fast == 2 || NB_ > 2) {
+                MR2(NB_, 2);
+                if (mark) *mark |= rk_bit(RK_MM_REDUCE2_2);
+            } else {
+                MR2(NB_, 4);
+                if (mark) *mark |= rk_bit(RK_MM_REDUCE2_4);
+            }
         });
 #undef MR2
-    } else
-    NB_DISPATCH(h->NB, {
-        (void)WPB_;
-        hipLaunchKernelGGL((k_mm_reduce<NB_>), dim3(slabs, cdiv(L, 16)), dim3(64), 0, st, X, ldx, Y, (int64_t)h->KP, M,
-                           MM_SLAB, L, h->KP, part, h->KP);
-    });
+    } else {
+        NB_DISPATCH(h->NB, {
+            (void)WPB_;
+            hipLaunchKernelGGL((k_mm_reduce<NB_>), dim3(slabs, cdiv(L, 16)), dim3(64), 0, st, X, ldx, Y, (int64_t)h->KP, M,
+                               MM_SLAB, L, h->KP, part, h->KP);
+        });
+        if (mark) *mark |= rk_bit(RK_MM_REDUCE);
+    }
     KCHECK();
     if (out)
         hipLaunchKernelGGL(k_sum_partials, dim3(cdiv(L * h->KP, 16)), dim3(256), 0, st, (const double *)part, slabs,
@@ -1124,6 +1149,7 @@ int launch_gene_v(insider_hip_handle *h, int q_begin, int q_end)
         else GV2_LAUNCH(4);
 #undef GV2_LAUNCH
         KCHECK();
+        row_mark(h, RK_MM_ROWS2);
         return INSIDER_OK;
     }
 #define GV_LAUNCH(NT_)                                                                                                        \
@@ -1135,6 +1161,7 @@ int launch_gene_v(insider_hip_handle *h, int q_begin, int q_end)
     else GV_LAUNCH(4);
 #undef GV_LAUNCH
     KCHECK();
+    row_mark(h, RK_MM_ROWS);
     return INSIDER_OK;
 }
 
@@ -1143,7 +1170,7 @@ int launch_row_stats(insider_hip_handle *h, bool timed)
     Timer t;
     int rc = t.begin(h, timed);
     if (rc) return rc;
-    rc = launch_list_stats(h, false, h->nseg, h->C, h->stat);
+    rc = launch_list_stats(h, false, h->nseg, h->C, h->stat, nullptr, &h->row_kernels);
     if (rc) return rc;
     return t.end(h, h->ev_row);
 }
@@ -1181,12 +1208,13 @@ int launch_level_gram(insider_hip_handle *h, int i, hipStream_t st, double *rec,
     hipLaunchKernelGGL((k_wgemm<LT_>), grid, dim3(256), 0, st, hn, h->cf.hn_stride, w.tiles, (const double *)h->C, h->KP,   \
                        (int)h->p, w.slab, w.nslab, (const uint8_t *)h->wg_pair, w.ntile, h->wg_part)
         switch (w.LT) {
-            case 4: WG_LAUNCH(4); break;
-            case 5: WG_LAUNCH(5); break;
-            case 6: WG_LAUNCH(6); break;
-            default: WG_LAUNCH(7); break;
+            case 4: WG_LAUNCH(4); row_mark(h, RK_WGEMM4); break;
+            case 5: WG_LAUNCH(5); row_mark(h, RK_WGEMM5); break;
+            case 6: WG_LAUNCH(6); row_mark(h, RK_WGEMM6); break;
+            default: WG_LAUNCH(7); row_mark(h, RK_WGEMM7); break;
         }
 #undef WG_LAUNCH
+        if (w.zch > 1) row_mark(h, RK_WGEMM_CHUNKS);
         KCHECK();
         hipLaunchKernelGGL(k_wgemm_sum, dim3(cdiv(stat_len, 256), ct.L), dim3(256), 0, st, (const double *)h->wg_part, w.nslab,
                            w.tiles, w.ntile, h->K, stat_len, rec, plen);
@@ -1195,10 +1223,12 @@ int launch_level_gram(insider_hip_handle *h, int i, hipStream_t st, double *rec,
     }
     NB_DISPATCH(h->NB, {
         constexpr int STAT_ = Geo<NB_>::STAT, PLEN = STAT_ + 2 * Geo<NB_>::KP + 2;
-        if (ct.nitems > 0)   // no held-out entry at all: every level sum is zero
+        if (ct.nitems > 0) {   // no held-out entry at all: every level sum is zero
             hipLaunchKernelGGL((k_wsyrk<NB_, WPB_>), dim3(cdiv(ct.nitems, WPB_)), dim3(WPB_ * 64), 0, st,
                                (const uint32_t *)ct.item_begin, (const uint32_t *)ct.item_end, ct.nitems,
                                (const int *)ct.wl_idx, (const double *)ct.wl_w, (const double *)h->C, (int64_t)h->p, h->wpart);
+            row_mark(h, RK_WSYRK);
+        }
         hipLaunchKernelGGL(k_level_sum, dim3(cdiv(STAT_, 16), ct.L), dim3(256), 0, st, (const double *)h->wpart,
                            (const int *)ct.lvl_item_ptr, STAT_, rec, PLEN);
     });
@@ -1225,6 +1255,7 @@ int launch_wsyrk_side(insider_hip_handle *h)
     if (int rp = launch_gram(h, h->C, h->p, h->CCt, h->side3, h->gram_part2)) return rp;
     if (int rp = launch_mm_reduce_kp(h, h->Strain, h->SLP, h->C, (int)h->p, h->SL, h->sc_part2, h->SC, h->side3)) return rp;
     HIPCHECK(hipEventRecord(h->ev_prep, h->side3));
+    row_mark(h, RK_GRAM_SIDE);
     for (int i = 0; i < h->c; ++i) {
         const int plen = h->NB * (h->NB + 1) / 2 * 256 + 2 * h->KP + 2;
         if (int rg = launch_level_gram(h, i, h->side2, h->lvl_sum_all + (size_t)h->lvl_off[i] * plen)) return rg;
@@ -1285,8 +1316,10 @@ int row_update(insider_hip_handle *h, int i, int cont_col, int masked, double la
         hipLaunchKernelGGL((k_gene_uc<4>), dim3(cdiv(h->p, 4)), dim3(256), 0, h->stream, ca, cont_col, (const double *)h->Vlev, h->SLP,
                            h->U);
         KCHECK();
+        row_mark(h, RK_GENE_UC);
         int ypart_n = 0;
-        if (int rcy = launch_mm_reduce_kp(h, h->U, 2, h->C, (int)h->p, 1, h->sc_part, nullptr, nullptr, &ypart_n)) return rcy;
+        if (int rcy = launch_mm_reduce_kp(h, h->U, 2, h->C, (int)h->p, 1, h->sc_part, nullptr, nullptr, &ypart_n, &h->row_kernels))
+            return rcy;
         if (h->w_ready) {
             HIPCHECK(hipStreamWaitEvent(h->stream, h->ev_w[h->c + cont_col], 0));
             HIPCHECK(hipStreamWaitEvent(h->stream, h->ev_prep, 0));
@@ -1302,6 +1335,7 @@ int row_update(insider_hip_handle *h, int i, int cont_col, int masked, double la
                                (const double *)h->CCt, (const double *)(h->SC + (size_t)row0 * KP), 1, h->K, lambda1, 0, h->eq,
                                h->Astack + (size_t)row0 * KP, h->failflag, (const double *)(h->cont_cnt + cont_col));
         });
+        row_mark(h, RK_MERGED);
     } else if (!cont && use_merged(h, masked)) {
         // merged update: one weighted rank-one term per (level, gene) pair, one look-up per held-out entry
         const int L = ct.L, LP = (int)round_up(L, 2), KP = h->KP;
@@ -1312,6 +1346,7 @@ int row_update(insider_hip_handle *h, int i, int cont_col, int masked, double la
             ca.zt = h->m > 0 ? h->cf_zt : nullptr;   // (+ the continuous covariates' term from the real-valued counts)
             hipLaunchKernelGGL((k_gene_u_cnt<4>), dim3(cdiv(h->p, 4)), dim3(256), gu_lds, h->stream, ca, h->cf_pos[i], LP,
                                (const double *)h->Vlev, h->SLP, h->SL, h->U);
+            row_mark(h, RK_GENE_U_CNT);
         } else {
             // (k_gene_u knows nothing of the continuous covariates' term: insider_hip_create_ex leaves cont_merged off when a
             // covariate's k_gene_u_cnt record does not fit, so this branch is never reached with m > 0)
@@ -1320,13 +1355,14 @@ int row_update(insider_hip_handle *h, int i, int cont_col, int masked, double la
                                h->stream, (const uint32_t *)ct.grp, (const uint16_t *)ct.slev,
                                (size_t)h->col_entries + LIST_BLOCK, h->c - 1, L, LP, (const double *)h->Vlev, h->SLP, (int)h->p,
                                h->SLcat, h->U);
+            row_mark(h, RK_GENE_U);
         }
         KCHECK();
         // Y = U'C, the same reduction over genes as (S C'); with the fused level kernel its per-slab partial sums are added up
         // there (k_sum_partials' order), which takes one launch per covariate off the main chain
         int ypart_n = 0;
         if (int rcy = launch_mm_reduce_kp(h, h->U, LP, h->C, (int)h->p, L, h->sc_part, h->row_fused ? nullptr : h->Ylvl, nullptr,
-                                          &ypart_n))
+                                          &ypart_n, &h->row_kernels))
             return rcy;
         if (!h->row_fused) ypart_n = 0;
         if (h->w_ready) {   // wsyrk + level sums came from side2, C'C and (S^train C') from side3
@@ -1340,18 +1376,20 @@ int row_update(insider_hip_handle *h, int i, int cont_col, int masked, double la
             double *rec = h->w_ready ? h->lvl_sum_all + (size_t)h->lvl_off[i] * PLEN : h->lvl_sum;
             // the level records' tail, the level equations and (unless the equations still have to cross ranks) the solves: one launch
             fused_solve = h->world <= 1 && !h->force_allreduce && h->row_fused && NB_ <= 2;
-            if (h->row_fused)
+            if (h->row_fused) {
                 hipLaunchKernelGGL((k_level_merged<NB_>), dim3(L), dim3(256), 0, h->stream, (const double *)rec,
                                    (const double *)(ypart_n ? h->sc_part : h->Ylvl), ypart_n, (const double *)ct.paircnt, h->SL, (const double *)h->Astack,
                                    (const int *)(h->lvl_count_all + h->lvl_off[i]), (const double *)h->CCt,
                                    (const double *)(h->SC + (size_t)row0 * KP), L, h->K, lambda1, fused_solve ? 1 : 0, h->eq,
                                    h->Astack + (size_t)row0 * KP, h->failflag);
-            else {
+                row_mark(h, fused_solve ? RK_MERGED_SOLVE : RK_MERGED);
+            } else {
                 hipLaunchKernelGGL(k_level_pack, dim3(L), dim3(256), 0, h->stream, (const double *)h->Ylvl,
                                    (const double *)ct.paircnt, h->SL, (const double *)h->Astack,
                                    (const int *)(h->lvl_count_all + h->lvl_off[i]), L, h->K, KP, STAT_, rec);
                 ra.part = rec;
                 hipLaunchKernelGGL((k_level_reduce<NB_>), dim3(L), dim3(64), 0, h->stream, ra);
+                row_mark(h, RK_PACK_REDUCE);
             }
         });
     } else if (!cont && unmasked_fused(h, masked)) {
@@ -1365,6 +1403,8 @@ int row_update(insider_hip_handle *h, int i, int cont_col, int masked, double la
                                (const double *)(h->SC + (size_t)row0 * KP), L, h->K, lambda1, fused_solve ? 1 : 0, h->eq,
                                h->Astack + (size_t)row0 * KP, h->failflag);
         });
+        row_mark(h, fused_solve ? RK_MERGED_SOLVE : RK_MERGED);
+        row_mark(h, RK_MERGED_ZERO);
     } else {
         NB_DISPATCH(h->NB, {
             (void)WPB_;
@@ -1374,6 +1414,7 @@ int row_update(insider_hip_handle *h, int i, int cont_col, int masked, double la
                                (const double *)h->lvl_part, (const int *)ct.lvl_chunk_ptr, PLEN, h->lvl_sum, PLEN);
             hipLaunchKernelGGL((k_level_reduce<NB_>), dim3(ct.L), dim3(64), 0, h->stream, ra);
         });
+        row_mark(h, RK_LEVEL_PARTIAL);
     }
     KCHECK();
     if (fused_solve) return rebuild_R ? launch_build_R(h) : INSIDER_OK;
@@ -1385,6 +1426,7 @@ int row_update(insider_hip_handle *h, int i, int cont_col, int masked, double la
             hipLaunchKernelGGL((k_cont_cd<NB_>), dim3(1), dim3(64), 0, h->stream, (const double *)h->eq, h->K, lambda1,
                                h->Astack + (size_t)row0 * h->KP);
         });
+        row_mark(h, RK_CONT_CD);
     } else {
         NB_DISPATCH(h->NB, {
             (void)WPB_;
@@ -1392,6 +1434,7 @@ int row_update(insider_hip_handle *h, int i, int cont_col, int masked, double la
                                (const int *)(cont ? h->one_count : h->lvl_count_all + h->lvl_off[i]), ct.L, h->K, lambda1,
                                h->Astack + (size_t)row0 * h->KP, h->failflag);
         });
+        row_mark(h, RK_LEVEL_SOLVE);
     }
     KCHECK();
     // the next covariate's Gauss-Seidel residual sees this update (:353-355, :347-349): the per-sample path reads it from R;
@@ -2251,6 +2294,7 @@ static int optimize_body(insider_hip_handle *h, double *const *A, double *C, int
     if ((rc = ensure_workspace(h, K))) return rc;
     const auto t_begin = std::chrono::steady_clock::now();
     clear_events(h);
+    h->row_kernels = 0;
     h->w_ready = false;
     h->side_pending = false;
     h->qfull_pending = false;
@@ -2486,6 +2530,7 @@ int insider_hip_optimize_row(insider_hip_handle *h, double *const *A, const doub
     if (!(lambda == lambda)) return fail(INSIDER_ERR_ARG, "lambda is NaN");   // any finite value, like the reference
     HIPCHECK(hipSetDevice(h->device));
     if ((rc = ensure_workspace(h, K))) return rc;
+    h->row_kernels = 0;
     h->w_ready = false;
     if ((rc = upload_factors(h, A, C, K))) return rc;
     if ((rc = launch_row_prep(h, tuning))) return rc;
@@ -2843,6 +2888,7 @@ int insider_hip_get_info(insider_hip_handle *h, const char *name, double *out)
     else if (s == "col_solver") *out = h->col_solver;               // last column solve: the kernel that ran it (ColSolver) ...
     else if (s == "col_eval") *out = h->col_eval;                   // ... and the one that ran its evaluation pass (0 = none)
     else if (s == "col_ridge_fallback") *out = h->col_ridge_fallback;   // ... and whether the ridge solve launched the general route
+    else if (s == "row_kernels") *out = (double)h->row_kernels;     // last optimize() / optimize_row(): row-phase kernel forms (RowKernel bits)
     else if (s == "cd_ms_steady") *out = h->steady_cd_ms;           // option "profile": mean over outer iterations >= 5 of the last call
     else if (s == "col_stats_ms_steady") *out = h->steady_col_ms;
     else if (s == "col_mfma_per_gene") {

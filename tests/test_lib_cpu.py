@@ -28,6 +28,24 @@ def test_exports_every_declared_symbol(lib):
     assert b"gfx950" in lib.insider_hip_version()
 
 
+def test_row_kernel_bits_are_documented_and_distinct():
+    """insider_hip_get_info("row_kernels"): _lib.ROW_KERNELS names bit i, the header describes bit i by that name, and the
+    library's RowKernel enumeration lists the same forms in the same order."""
+    names = _lib.ROW_KERNELS
+    assert len(set(names)) == len(names) and len(names) <= 53      # distinct bits that a double carries exactly
+    bits = [1 << i for i in range(len(names))]
+    assert len(set(bits)) == len(bits) and max(bits) < 2 ** 53
+    hdr = open(os.path.join(ROOT, "include", "insider_hip.h")).read()
+    desc = hdr[hdr.index('"row_kernels"'):]
+    desc = " ".join(desc[:desc.index("*/")].replace("*", " ").split())
+    for i, name in enumerate(names):
+        assert re.search(rf"\b{i} {name}\b", desc), (i, name)
+    src = open(os.path.join(ROOT, "insider_amd", "csrc", "insider_hip.hip")).read()
+    enum = re.search(r"enum RowKernel \{(.*?)\};", src, re.S).group(1)
+    enum = re.sub(r"//[^\n]*", "", enum)
+    assert [e.strip().split("=")[0].strip()[3:].lower() for e in enum.split(",") if e.strip()] == list(names)
+
+
 def test_product_never_imports_oracle():
     # only tests/, smoke() and bench.py's cpu_baseline leg may touch oracle/
     for dirpath, _, files in os.walk(os.path.join(ROOT, "insider_amd")):
