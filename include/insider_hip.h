@@ -144,7 +144,9 @@ int insider_hip_comm_init(insider_hip_handle *h, const void *unique_id, int rank
  * cd_cold_iters outer iterations of a call [default 3]: the register-resident sweep kernel stops at sweep cd_pass1 [64; 0 = one
  * pass], cd_pass1 x ratio [4], ..., re-packing the genes still running by their estimated remaining length between passes;
  * the iterates are bit-identical to the single-pass solve), "resid_stage_mb" (size in MB of the device buffer
- * insider_hip_residual() copies the residual out through, default 256; at least 16 genes of the window). */
+ * insider_hip_residual() copies the residual out through, default 256; at least 16 genes of the window), "vd_stage_kb" (LDS budget in
+ * KiB for the level tables insider_hip_variance_decomposition() stages per block, default 48, at most 60; tables that do not
+ * fit are read from global memory instead, with the same result; 0 = always that form). */
 int insider_hip_set_option(insider_hip_handle *h, const char *name, double value);
 
 /*
@@ -298,6 +300,26 @@ int insider_hip_interaction_glm(insider_hip_handle *h, double *const *A, const d
                                 const int32_t *subtract, const int32_t *group, int G, double *coeff, double *se,
                                 double *dof);
 
+/*
+ * Per-gene variance decomposition of a fitted model on the resident data set.  Covariate blocks are numbered as in
+ * insider_hip_residual(): 0..c-1 the categorical covariates, c the continuous block (inc_continuous = 1); B = c +
+ * inc_continuous.  For sample i and gene j, block b contributes g_b(i,j) = A_b[level_b(i)] . C[:, j] (categorical) or
+ * g_c(i,j) = z_i B_c C[:, j] (continuous: z_i = row i of ctns_confounder, B_c = A[c], m x K).  The fit is f = sum_b g_b
+ * and the residual r = x - f, with x the handle's X as given to insider_hip_create[_ex].
+ * entries chooses the entries S_j of each gene: 0 = every entry, 1 = entries whose train bit is set (the handle's
+ * train_indicator), 2 = entries whose test bit is set (test_indicator).  On a handle built for fit() (train = train + test,
+ * test = NA) 1 is the observed set; on a tuning handle 2 is each gene's held-out set.
+ * out holds p records of 4 + 3 B doubles, record j at out + j (4 + 3 B): n_j = |S_j|, sum x, sum x^2, sum r^2 (formed from
+ * r itself), then for b = 0..B-1 at 4 + 3 b: sum g_b, sum g_b^2, sum r g_b.  All sums run over S_j.
+ * Arguments, status codes and scope as in the post-hoc calls above (K 1..63, the same inc_continuous rules, a sharded
+ * handle returns INSIDER_ERR_UNSUPPORTED); entries outside 0..2 return INSIDER_ERR_ARG.  Works on clones, on the handle's
+ * main stream, in the post-hoc workspace: an optimize() after it is bit-identical to one without.  Every sum runs in a fixed
+ * order without atomics: repeated calls give bit-identical records.  insider_hip_get_info("vd_path") tells which form of
+ * the streaming pass the last call ran (1 = level tables staged in LDS, 2 = read from global memory; option "vd_stage_kb").
+ */
+int insider_hip_variance_decomposition(insider_hip_handle *h, double *const *A, const double *C, int inc_continuous, int K,
+                                       int entries, double *out);
+
 /* Profile of the last insider_hip_optimize() call (option "profile" = 1), HIP-event timed on the library's stream.
  * out[0..11]: {column-side masked-Gram launches, total ms, row-side masked-Gram launches, total ms,
  *  column-solve (CD / ridge) launches, total ms, test-residual launches, total ms,
@@ -316,6 +338,8 @@ int insider_hip_get_profile(insider_hip_handle *h, double *out12);
  * and for the evaluation pass after it; 0 = none: 1 k_ridge_cols_reg, 2 k_ridge_cols, 3 k_cd_cols_reg with one or two slots,
  * 4 k_cd_cols_reg with three slots, 5 k_cd_cols<16,4>, 6 k_cd_cols<32,2>, 7 k_cd_cols<64,1>, 8 / 9 / 10 k_cd_cols_r16<1 / 2 / 3>),
  * "col_ridge_fallback" (1: the last ridge solve also launched k_ridge_cols for the genes k_ridge_cols_reg marked),
+ * "vd_path" (the form of k_vd_stats the last insider_hip_variance_decomposition() ran: 1 = level tables in LDS, 2 = read from
+ * global memory; 0 = none yet),
  * "row_kernels" (a bit mask of the row-phase kernel forms the last optimize() / optimize_row() launched, reset at the start of
  * each; set on the host at each launch site.  Level Gram sums: bit 0 wgemm4, 1 wgemm5, 2 wgemm6, 3 wgemm7 (k_wgemm<LT>),
  * 4 wgemm_chunks (a k_wgemm launch with more than one level-tile chunk, grid.z > 1), 5 wsyrk (k_wsyrk<NB>; neither wsyrk nor a

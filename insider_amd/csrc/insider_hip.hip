@@ -7,6 +7,7 @@
 // checkpoints (every 10th iteration) and around the optional cross-rank all-reduce.
 #include "insider_kernels.hpp"
 #include "insider_posthoc.hpp"
+#include "insider_vardecomp.hpp"
 
 #include <rccl/rccl.h>
 
@@ -247,6 +248,10 @@ struct insider_hip_handle {
     // that nothing insider_hip_optimize() reads is touched; allocated on first use, grown on demand, freed with the handle
     PostWs *post = nullptr;
     double resid_stage_mb = 256.0;   // option "resid_stage_mb": size of the device buffer the residual is copied out through
+    // variance decomposition (insider_hip_variance_decomposition): option "vd_stage_kb" bounds the LDS a block of k_vd_stats
+    // may stage its genes' level tables in (KiB); vd_path = the form the last call ran (1 = tables in LDS, 2 = from global)
+    double vd_stage_kb = 48.0;
+    int vd_path = 0;
 };
 
 namespace {
@@ -2274,6 +2279,7 @@ int insider_hip_set_option(insider_hip_handle *h, const char *name, double value
     else if (s == "col_mfma4") h->col_mfma4 = (int)value;         // 1 = k_col_paircnt4 (K <= 31, factor rows fit LDS), 0 = k_col_paircnt
     else if (s == "cd_pairs") h->cd_pairs = (int)value;           // 1 (default) = sweeps routed through the blocks of two coordinate steps (K <= 30; same iterates), 0 = one step per block
     else if (s == "resid_stage_mb") h->resid_stage_mb = value;   // device buffer insider_hip_residual() copies out through (MB; at least 16 genes of the window)
+    else if (s == "vd_stage_kb") h->vd_stage_kb = value;         // LDS budget (KiB, default 48, at most 60) of the staged level tables of k_vd_stats (0 = always the global form)
     else if (s == "cd_variant") h->cd_variant = (int)value;   // 0 = register-resident (4 genes per wave; K <= 32, and 32 < K <= 48 with the third slot's columns in LDS), 1 = group kernel, 2 = row16 (LDS, K <= 48)
     else return fail(INSIDER_ERR_ARG, "unknown option " + s);
     return INSIDER_OK;
@@ -2891,6 +2897,7 @@ int insider_hip_get_info(insider_hip_handle *h, const char *name, double *out)
     else if (s == "row_kernels") *out = (double)h->row_kernels;     // last optimize() / optimize_row(): row-phase kernel forms (RowKernel bits)
     else if (s == "cd_ms_steady") *out = h->steady_cd_ms;           // option "profile": mean over outer iterations >= 5 of the last call
     else if (s == "col_stats_ms_steady") *out = h->steady_col_ms;
+    else if (s == "vd_path") *out = h->vd_path;                     // last variance decomposition: 1 = level tables in LDS, 2 = read from global
     else if (s == "col_mfma_per_gene") {
         // v_mfma_f64_16x16x4_f64 instructions the column-side statistics kernel issues per gene (2048 flops each; the 4x4x4 form
         // of the per-entry kernel is counted in the same unit: a quarter per instruction)
@@ -2953,13 +2960,17 @@ struct PostWs {
     // gpart / gram: C C'; ints: host-built group tables; cpart / gsum: group sums; L / dinv / info: the factor;
     // outs: coeff, se, dof
     Buf Ast, U, cp, nz, part, stats, stage, gpart, gram, ints, cpart, gsum, L, dinv, info, outs;
+    // variance decomposition: vin = the host factors (A blocks at row offset x K, then C as p rows of K); vtab = the level
+    // table T (p rows of SL); vrec = the p records
+    Buf vin, vtab, vrec;
 };
 
 void free_posthoc(PostWs *w)
 {
     if (!w) return;
     for (PostWs::Buf *b : {&w->Ast, &w->U, &w->cp, &w->nz, &w->part, &w->stats, &w->stage, &w->gpart, &w->gram, &w->ints,
-                           &w->cpart, &w->gsum, &w->L, &w->dinv, &w->info, &w->outs})
+                           &w->cpart, &w->gsum, &w->L, &w->dinv, &w->info, &w->outs,
+                           &w->vin, &w->vtab, &w->vrec})
         if (b->p) (void)hipFree(b->p);
     delete w;
 }
@@ -3220,6 +3231,80 @@ int ph_finish(insider_hip_handle *h, int rc)
 
 #undef PH_DISPATCH
 
+// ---- variance decomposition (kernels: insider_vardecomp.hpp) ------------------------------------------------------------
+int variance_decomposition_body(insider_hip_handle *h, double *const *A, const double *C, int inc_continuous, int K,
+                                int entries, double *out)
+{
+    if (!h) return fail(INSIDER_ERR_ARG, "null handle");
+    const std::vector<int32_t> every((size_t)h->c + 2, 1);   // every block enters the fit
+    int rc = ph_check(h, A, C, inc_continuous, K, every.data());
+    if (rc) return rc;
+    if (entries < 0 || entries > 2) return fail(INSIDER_ERR_ARG, "entries must be 0 (all), 1 (train) or 2 (test)");
+    if (!out) return fail(INSIDER_ERR_ARG, "null output");
+    HIPCHECK(hipSetDevice(h->device));
+    if (!h->post) h->post = new PostWs();
+    PostWs &w = *h->post;
+    hipStream_t st = h->stream;
+    const int nb = h->c + inc_continuous, SL = h->SL, KPW = 16 * ((K + 15) / 16), rec = 4 + 3 * nb;
+    const int64_t n = h->n, p = h->p;
+    double *vin = nullptr, *Ast = nullptr, *T = nullptr, *R = nullptr;
+    if ((rc = ph_grow(w.vin, (size_t)(SL + p) * K, &vin))) return rc;
+    if ((rc = ph_grow(w.Ast, (size_t)SL * KPW, &Ast))) return rc;
+    if ((rc = ph_grow(w.vtab, (size_t)p * SL, &T))) return rc;
+    if ((rc = ph_grow(w.vrec, (size_t)p * rec, &R))) return rc;
+    // [A_stack; B_c] as SL rows of KPW (the layout of ph_prepare), C as p rows of K
+    for (int b = 0; b < nb; ++b) {
+        const int L = b < h->c ? h->n_levels[b] : h->m;
+        const int off = b < h->c ? h->lvl_off[b] : h->SLcat;
+        HIPCHECK(hipMemcpyAsync(vin + (size_t)off * K, A[b], (size_t)L * K * sizeof(double), hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_pack_A, dim3(cdiv((int64_t)L * KPW, 256)), dim3(256), 0, st, (const double *)(vin + (size_t)off * K),
+                           L, K, KPW, Ast + (size_t)off * KPW);
+        KCHECK();
+    }
+    double *Cd = vin + (size_t)SL * K;
+    HIPCHECK(hipMemcpyAsync(Cd, C, (size_t)p * K * sizeof(double), hipMemcpyHostToDevice, st));
+    // T[j][s] = sum_k Ast[s][k] C[k][j]: gene-major, one gene's table contiguous
+#define VT_LAUNCH(NT_)                                                                                                      \
+    hipLaunchKernelGGL((k_mm_rows<NT_, true>), dim3(cdiv(cdiv((int)p, 16), 4), cdiv(SL, 16 * NT_)), dim3(256), 0, st,         \
+                       (const double *)Cd, (int64_t)K, (int)p, K, (const double *)Ast, KPW, SL, T, (int64_t)SL, SL)
+    if (SL <= 16) VT_LAUNCH(1);
+    else if (SL <= 32) VT_LAUNCH(2);
+    else VT_LAUNCH(4);
+#undef VT_LAUNCH
+    KCHECK();
+    // one pass over X per window of BW blocks
+    const int sel = entries == 0 ? 0 : entries == 1 ? CODE_TRAIN : CODE_TEST;
+    const int m = inc_continuous ? h->m : 0;
+    // (at most 60 KiB of dynamic LDS beside the kernel's static reduction buffer: no launch attribute needed)
+    const double budget = std::min(std::max(h->vd_stage_kb, 0.0), 60.0) * 1024.0;
+#define VD_LAUNCH(BW_, GW_)                                                                                                 \
+    do {                                                                                                                     \
+        const bool staged = (double)GW_ * SL * sizeof(double) <= budget;                                                     \
+        h->vd_path = staged ? 1 : 2;                                                                                         \
+        for (int b0 = 0; b0 < nb; b0 += BW_) {                                                                               \
+            if (staged)                                                                                                      \
+                hipLaunchKernelGGL((k_vd_stats<BW_, GW_, true>), dim3(cdiv(p, GW_)), dim3(64 * VD_WAVES),                    \
+                                   (size_t)GW_ * SL * sizeof(double), st, (const double *)h->X, (const uint8_t *)h->codes,   \
+                                   h->ldn, (int)n, p, (const int *)h->lev, (const int *)h->lvl_off_d, h->c,                  \
+                                   (const double *)h->Zc, m, h->SLcat, (const double *)T, SL, sel, nb, b0, R);               \
+            else                                                                                                             \
+                hipLaunchKernelGGL((k_vd_stats<BW_, GW_, false>), dim3(cdiv(p, GW_)), dim3(64 * VD_WAVES), 0, st,            \
+                                   (const double *)h->X, (const uint8_t *)h->codes, h->ldn, (int)n, p, (const int *)h->lev,  \
+                                   (const int *)h->lvl_off_d, h->c, (const double *)h->Zc, m, h->SLcat, (const double *)T,   \
+                                   SL, sel, nb, b0, R);                                                                      \
+            KCHECK();                                                                                                        \
+        }                                                                                                                    \
+    } while (0)
+    // two genes per wave: 126 / 154 / 215 VGPRs for windows of 1 / 2 / 4 blocks (four genes: 227 / 256, fewer waves per SIMD)
+    if (nb == 1) VD_LAUNCH(1, 2);
+    else if (nb == 2) VD_LAUNCH(2, 2);
+    else VD_LAUNCH(4, 2);
+#undef VD_LAUNCH
+    HIPCHECK(hipMemcpyAsync(out, R, (size_t)p * rec * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipStreamSynchronize(st));
+    return INSIDER_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -3235,6 +3320,12 @@ int insider_hip_interaction_glm(insider_hip_handle *h, double *const *A, const d
                                 double *dof)
 {
     return ph_finish(h, interaction_glm_body(h, A, C, inc_continuous, K, subtract, group, G, coeff, se, dof));
+}
+
+int insider_hip_variance_decomposition(insider_hip_handle *h, double *const *A, const double *C, int inc_continuous, int K,
+                                       int entries, double *out)
+{
+    return ph_finish(h, variance_decomposition_body(h, A, C, inc_continuous, K, entries, out));
 }
 
 }  // extern "C"

@@ -5,12 +5,14 @@
         --rank K --lambda 5 --alpha 0.4 [--partition 0|1] [--max-iter N] [--out DIR] [--out-format npy|flat]
     ... --tune --ranks 10 12 14 --lambdas 1 3 5 --alphas 0.2 0.4   # tune()'s rank sweep + lambda x alpha grid
     ... --interaction 1 2 --interaction-glm 1   # then glm_interaction() on the device for covariate column 1 (0-based)
+    ... --variance-decomposition                # then the per-gene variance decomposition on the device
 
 Semantics are those of insider_amd.api (the mirror of R/insider.R): with masks given, `--partition 1` fits on the
 train entries (optimize(tuning = 1)) and reports the test RMSE; without masks (or `--partition 0`) every non-NA entry is
 used (fit()'s default, R/insider.R:190-216; NaN entries of X are the NA set).  Inits are N(0, 0.001^2)
 (R/utils.R:40-43) from --seed.  --interaction-glm COV adds interaction_coeff / interaction_pval (L_COV x K, glm_interaction()
-on the device against the residual of every other block).  Output: A<i> (L_i x K), C (K x p) and result.json {train_rmse, test_rmse, loss,
+on the device against the residual of every other block); --variance-decomposition adds vd_r2 / vd_rmse (p) and
+vd_explained / vd_drop_one (B x p, posthoc.vd_derived) over the entries the fit used.  Output: A<i> (L_i x K), C (K x p) and result.json {train_rmse, test_rmse, loss,
 iters, traj} in --out.  There is no CPU fallback: without a visible MI355X the command fails with the library's status.
 """
 import argparse
@@ -54,6 +56,9 @@ def parse(argv=None):
                     help="after the fit, glm_interaction() on the device for the levels of covariate column COV (0-based, "
                          "after --interaction: its indicator is column 1) against the residual of every other block; "
                          "writes interaction_coeff / interaction_pval (L x K) next to the factors")
+    ap.add_argument("--variance-decomposition", action="store_true",
+                    help="after the fit, the per-gene variance decomposition on the device over the entries the fit used; "
+                         "writes vd_r2, vd_rmse (p) and vd_explained, vd_drop_one (blocks x p) next to the factors")
     a = ap.parse_args(argv)
     if not a.flat and not (a.x and a.levels):
         ap.error("give --flat DIR or --x and --levels")
@@ -135,6 +140,12 @@ def main(argv=None):
                                             subtract=[b != cov for b in range(len(rows))],
                                             inc_continuous=1 if Z is not None else 0, n_groups=int(ds.n_levels[cov]))
         glm = (coeff, t_pvalues(coeff, se, dof))
+    vd = None
+    if a.variance_decomposition:
+        from .posthoc import vd_derived
+        d = vd_derived(ds.variance_decomposition(list(res["row_matrices"].values()), res["column_factor"], entries="train",
+                                                 inc_continuous=1 if Z is not None else 0))
+        vd = {"vd_r2": d["r2"], "vd_rmse": d["rmse"], "vd_explained": d["explained"], "vd_drop_one": d["drop_one"]}
     ds.close()
     summary = dict(train_rmse=res["train_rmse"], test_rmse=None if np.isnan(res["test_rmse"]) else res["test_rmse"],
                    loss=res["loss"], iters=res["iters"], rank=K, **{"lambda": a.lam}, alpha=a.alpha, partition=partition,
@@ -146,6 +157,11 @@ def main(argv=None):
                 np.save(os.path.join(a.out, name + ".npy"), np.asfortranarray(v))
             else:
                 flatio.write_raw(os.path.join(a.out, name + ".f64"), v)
+    for name, v in (vd or {}).items():
+        if fmt == "npy":
+            np.save(os.path.join(a.out, name + ".npy"), np.asfortranarray(v))
+        else:
+            flatio.write_raw(os.path.join(a.out, name + ".f64"), v)
     print(json.dumps({k: summary[k] for k in ("train_rmse", "test_rmse", "loss", "iters")} | {"out": a.out}))
     return 0
 

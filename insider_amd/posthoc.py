@@ -9,6 +9,10 @@ Closed form of that stacked least-squares problem (m samples in the level, p gen
 glm_interaction() below is that closed form in plain numpy on a host residual matrix (the yardstick);
 glm_interaction_resident() runs the same arithmetic on the device from the resident data set of a fitted object
 (InsiderData.interaction_glm: one streaming pass over X, the residual never leaves the GPU).
+
+variance_decomposition() answers a different question per gene: how much of its variance each covariate block carries
+and how well the model fits it (InsiderData.variance_decomposition: the level table [A_stack; B_c] C, then one streaming
+pass over X); variance_decomposition_host() is the same record in plain numpy (the yardstick).
 """
 import numpy as np
 
@@ -70,3 +74,63 @@ def glm_interaction_resident(obj, group_cov, subtract=None):
     coeff, se, dof = ds.interaction_glm(cfd, obj["column_factor"], group, subtract=subtract, inc_continuous=inc,
                                         n_groups=int(ds.n_levels[group_cov]))
     return coeff, t_pvalues(coeff, se, dof)
+
+
+def vd_derived(rec):
+    """The raw per-gene sums of a variance decomposition (InsiderData.variance_decomposition) plus
+        tss = sum x^2 - (sum x)^2 / n,  r2 = 1 - rss / tss,  rmse = sqrt(rss / n),
+        explained[b] = (sum g_b^2 - (sum g_b)^2 / n) / tss   (the share of the gene's variance block b carries),
+        drop_one[b] = (sum g_b^2 + 2 sum r g_b) / tss         (the rise in RSS, over tss, when block b leaves the fit).
+    tss is formed from the raw sums (one pass, no centring): for a gene whose mean is large against its spread it loses
+    digits to cancellation.  The explained shares do not add up to r2: the cross terms between blocks (and between the
+    fit and the residual) are not split among them.  A gene with n = 0 gets NaN in every derived value."""
+    out = {k: np.asarray(v, dtype=np.float64) for k, v in rec.items()}
+    n = out["n"]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        nn = np.where(n > 0, n, np.nan)
+        tss = out["sum_xx"] - out["sum_x"] ** 2 / nn
+        out["tss"] = tss
+        out["r2"] = 1.0 - out["rss"] / tss
+        out["rmse"] = np.sqrt(out["rss"] / nn)
+        out["explained"] = (out["sum_gg"] - out["sum_g"] ** 2 / nn) / tss
+        out["drop_one"] = (out["sum_gg"] + 2.0 * out["sum_rg"]) / tss
+    return out
+
+
+def variance_decomposition_host(X, levels, ctns, mask, A, C):
+    """The variance-decomposition record in plain numpy (the yardstick of the device path).  X: n x p; levels: n x c level
+    ids 1..L_b; ctns: n x m or None; mask: n x p (entries that count) or None (every entry); A: the c categorical row
+    factors (L_b x K), then B_c (m x K) when ctns is given; C: K x p.  -> vd_derived() of the raw sums."""
+    X = np.asarray(X, dtype=np.float64)
+    Cm = np.asarray(C, dtype=np.float64)
+    lev = np.asarray(levels).reshape(X.shape[0], -1)
+    c = lev.shape[1]
+    g = [np.asarray(A[b], dtype=np.float64)[lev[:, b].astype(np.int64) - 1] @ Cm for b in range(c)]
+    if ctns is not None:
+        Z = np.asarray(ctns, dtype=np.float64).reshape(X.shape[0], -1)
+        g.append(Z @ (np.asarray(A[c], dtype=np.float64) @ Cm))
+    f = np.zeros_like(X)
+    for gb in g:
+        f = f + gb
+    w = np.ones(X.shape, dtype=bool) if mask is None else np.asarray(mask).astype(bool)
+    r = np.where(w, X - f, 0.0)
+    xs = np.where(w, X, 0.0)
+    gs = [np.where(w, gb, 0.0) for gb in g]
+    rec = dict(n=w.sum(axis=0).astype(np.float64), sum_x=xs.sum(axis=0), sum_xx=(xs * xs).sum(axis=0),
+               rss=(r * r).sum(axis=0), sum_g=np.array([gb.sum(axis=0) for gb in gs]).reshape(len(g), -1),
+               sum_gg=np.array([(gb * gb).sum(axis=0) for gb in gs]).reshape(len(g), -1),
+               sum_rg=np.array([(r * gb).sum(axis=0) for gb in gs]).reshape(len(g), -1))
+    return vd_derived(rec)
+
+
+def variance_decomposition(obj, which="fit", entries="train"):
+    """Per-gene variance decomposition of a fitted ``Insider`` object (api.insider + api.fit / tune) on the device, over
+    the entries ``entries`` of the resident data set ``which`` ("fit": train = the observed entries, test = NA; "tune": the
+    ratio_splitter split, so entries="test" gives each gene's held-out error).  Blocks: the columns of obj["confounder"],
+    then the continuous block.  -> vd_derived() of the raw sums: n, sum_x, sum_xx, rss (p), sum_g, sum_gg, sum_rg (B x p),
+    tss, r2, rmse (p), explained, drop_one (B x p)."""
+    from . import api
+    ds = api._resident(obj, which)
+    rec = ds.variance_decomposition(list(obj["cfd_matrices"].values()), obj["column_factor"], entries=entries,
+                                    inc_continuous=int(obj["inc_continuous"]))
+    return vd_derived(rec)
