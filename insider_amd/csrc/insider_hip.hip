@@ -18,8 +18,10 @@
 #include <cstdio>
 #include <cstring>
 #include <limits>
+#include <memory>
 #include <atomic>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/insider_hip.h"
@@ -50,190 +52,298 @@ int fail(int code, const std::string &msg)
 inline int64_t round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
 inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
+// One device allocation of count T: freed on destruction and on reassignment, handed to launches as a raw pointer.
 template <typename T>
-int dmalloc(T **p, size_t count)
-{
-    *p = nullptr;
-    if (count == 0) count = 1;
-    HIPCHECK(hipMalloc((void **)p, count * sizeof(T)));
-    return INSIDER_OK;
-}
+class DevBuf {
+public:
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    DevBuf(DevBuf &&o) noexcept : p_(o.p_), count_(o.count_) { o.p_ = nullptr; o.count_ = 0; }
+    DevBuf &operator=(DevBuf &&o) noexcept
+    {
+        if (this != &o) {
+            reset();
+            std::swap(p_, o.p_);
+            std::swap(count_, o.count_);
+        }
+        return *this;
+    }
+    ~DevBuf() { reset(); }
+    void reset()
+    {
+        if (p_) (void)hipFree(p_);
+        p_ = nullptr;
+        count_ = 0;
+    }
+    // a fresh allocation of count elements (at least one); the old one is freed first
+    int alloc(size_t count)
+    {
+        reset();
+        if (count == 0) count = 1;
+        HIPCHECK(hipMalloc((void **)&p_, count * sizeof(T)));
+        count_ = count;
+        return INSIDER_OK;
+    }
+    // at least count elements: a new allocation only when the current one is smaller (contents are not kept)
+    int grow(size_t count) { return std::max<size_t>(count, 1) <= count_ ? INSIDER_OK : alloc(count); }
+    // an allocation of max(v.size(), count) elements that starts with the host vector v
+    int upload(const std::vector<T> &v, size_t count = 0)
+    {
+        if (int rc = alloc(std::max(v.size(), count))) return rc;
+        HIPCHECK(hipMemcpy(p_, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+        return INSIDER_OK;
+    }
+    T *get() const { return p_; }
+    operator T *() const { return p_; }
 
-// device temporaries of the handle-less entry points: freed on every exit path
-struct DevBufs {
-    std::vector<void *> ptrs;
-    std::vector<hipEvent_t> events;
-    ~DevBufs()
-    {
-        for (void *q : ptrs) if (q) (void)hipFree(q);
-        for (hipEvent_t e : events) (void)hipEventDestroy(e);
-    }
-    template <typename T>
-    int alloc(T **p, size_t count)
-    {
-        int rc = dmalloc(p, count);
-        if (rc == INSIDER_OK) ptrs.push_back((void *)*p);
-        return rc;
-    }
+private:
+    T *p_ = nullptr;
+    size_t count_ = 0;
 };
+
+// An owned stream or event, destroyed with its owner.
+template <typename H, hipError_t (*Destroy)(H)>
+class HipObject {
+public:
+    HipObject() = default;
+    HipObject(const HipObject &) = delete;
+    HipObject &operator=(const HipObject &) = delete;
+    HipObject(HipObject &&o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+    HipObject &operator=(HipObject &&o) noexcept
+    {
+        if (this != &o) {
+            reset();
+            std::swap(h_, o.h_);
+        }
+        return *this;
+    }
+    ~HipObject() { reset(); }
+    void reset()
+    {
+        if (h_) (void)Destroy(h_);
+        h_ = nullptr;
+    }
+    H *out() { reset(); return &h_; }   // for the create call
+    operator H() const { return h_; }
+
+private:
+    H h_ = nullptr;
+};
+using Stream = HipObject<hipStream_t, hipStreamDestroy>;
+using Event = HipObject<hipEvent_t, hipEventDestroy>;
 
 struct CovTables {   // per covariate, device
     int L = 0, nchunks = 0;
-    int *chunk_level = nullptr, *chunk_begin = nullptr, *chunk_end = nullptr, *lvl_chunk_ptr = nullptr;
+    DevBuf<int> chunk_level, chunk_begin, chunk_end, lvl_chunk_ptr;
     // merged masked row update (insider_row_merged.hpp), built once per data set
-    uint32_t *grp = nullptr;          // [p][L + 1] positions of the level groups inside each gene's sorted held-out samples
-    uint16_t *slev = nullptr;         // per entry of every gene's level-grouped held-out samples: stacked level of each other covariate
-    uint32_t *item_begin = nullptr, *item_end = nullptr;   // weighted-SYRK work items: ranges of the (gene, count) lists
-    int *lvl_item_ptr = nullptr;      // [L + 1] items of every level
+    DevBuf<uint32_t> grp;             // [p][L + 1] positions of the level groups inside each gene's sorted held-out samples
+    DevBuf<uint16_t> slev;            // per entry of every gene's level-grouped held-out samples: stacked level of each other covariate
+    DevBuf<uint32_t> item_begin, item_end;   // weighted-SYRK work items: ranges of the (gene, count) lists
+    DevBuf<int> lvl_item_ptr;         // [L + 1] items of every level
     int nitems = 0;
     int64_t npairs = 0;               // (level, gene) pairs with held-out samples
-    int *wl_idx = nullptr;            // (gene, count) lists of every level, padded like the held-out lists
-    double *wl_w = nullptr;
-    double *paircnt = nullptr;        // [L][SLcat] samples in (level of this covariate, stacked level of another one)
+    DevBuf<int> wl_idx;               // (gene, count) lists of every level, padded like the held-out lists
+    DevBuf<double> wl_w;
+    DevBuf<double> paircnt;           // [L][SLcat] samples in (level of this covariate, stacked level of another one)
 };
 // continuous columns share one table: a single pseudo-level whose members are all samples, in 16-sample chunks
 
-
-}  // namespace
-
-// device workspace of the post-hoc calls (section "post-hoc interaction GLM")
-struct PostWs;
-void free_posthoc(PostWs *w);
-
-struct insider_hip_handle {
+// The read-only DATA SET: everything insider_hip_create builds (X-derived lists, level sums, pair counts, chunk tables) and
+// the shape facts that describe it.  Shared by the handles of insider_hip_clone — each has its own workspace, streams and
+// options, so that several fits of one data set (tune()'s grid points) run on the GPU at the same time — and freed with the
+// last of them.
+struct DataSet {
     int device = 0;
-    // The read-only DATA SET (X-derived lists, level sums, pair counts, chunk tables: everything insider_hip_create builds)
-    // may be shared by several handles (insider_hip_clone): each has its own factor workspace, streams and options, so that
-    // several fits of one data set — tune()'s grid points — run on the GPU at the same time.  The device arrays are freed
-    // by the last handle that goes.
-    std::atomic<int> *data_refs = nullptr;
-    hipStream_t stream = nullptr;
-    // scheduling work that nothing but the next column solve needs (sweep keys -> gene order, the next iteration's sweep-order
-    // table) runs on a side stream, next to the row update, between two events
-    hipStream_t side = nullptr;
-    hipEvent_t ev_cd_done = nullptr, ev_side_done = nullptr;
-    bool side_pending = false;
-    // the weighted SYRK of the merged row update depends on C only: all covariates' level sums are formed on a second
-    // side stream while the main stream computes V, u and U'C
-    hipStream_t side2 = nullptr;
-    hipStream_t side3 = nullptr;      // C'C and (S^train C') of the merged row update, next to the weighted SYRK
-    hipEvent_t ev_prep = nullptr;
-    hipEvent_t ev_c_ready = nullptr;
-    hipEvent_t ev_head = nullptr;     // recorded on side2 in front of the level Gram GEMM: the main chain's k_gene_u waits for it
-    std::vector<hipEvent_t> ev_w;
-    double *lvl_sum_all = nullptr;    // [SLcat][STAT + 2 KP + 2]: the level records of every covariate
-    bool w_ready = false;
-    double *gram_part2 = nullptr, *sc_part2 = nullptr;   // partial-sum buffers of the side-stream products
-    hipEvent_t ev_a_ready = nullptr, ev_qfull = nullptr, ev_qheld = nullptr;
-    bool qfull_pending = false;
-    bool qheld_pending = false;       // Qheld = S^held A of the factored column statistics is being formed on side3 (phase_R)
+    int n_simd = 1024;                // SIMDs of the device (4 per CU)
     int64_t n = 0, p = 0, ldn = 0, ldp = 0;
-    int c = 0, SL = 0, SLP = 0;   // SL: rows of the stacked row factors = all levels of all covariates + m
-    int m = 0, SLcat = 0;          // continuous covariates (columns of ctns_confounder) and the categorical level total
-    double *Zc = nullptr;          // m x n
-    int *one_count = nullptr;      // a "member count" of 1 for the single pseudo-level of a continuous column
+    int c = 0, SL = 0, SLP = 0;       // SL: rows of the stacked row factors = all levels of all covariates + m
+    int m = 0, SLcat = 0;             // continuous covariates (columns of ctns_confounder) and the categorical level total
     std::vector<int> n_levels, lvl_off;   // lvl_off has c + 1 entries
-    // data-set state (device)
-    double *X = nullptr, *Xt = nullptr;
-    uint8_t *codes = nullptr, *codes_t = nullptr;
-    int *lev = nullptr, *lvl_off_d = nullptr, *members_all = nullptr, *lvl_ptr_all = nullptr, *lvl_count_all = nullptr;
+    DevBuf<double> X;                 // gene-major lines of pitch ldn
+    DevBuf<uint8_t> codes;            // mask codes, same layout
+    DevBuf<int> lev, lvl_off_d, members_all, lvl_ptr_all, lvl_count_all;
     std::vector<CovTables> cov;
-    CovTables cont;                // chunk tables shared by every continuous column
+    CovTables cont;                   // chunk tables shared by every continuous column
+    DevBuf<double> Zc;                // m x n
+    DevBuf<int> one_count;            // a "member count" of 1 for the single pseudo-level of a continuous column
+    DevBuf<int> ident_members;        // 0..n-1
+    int max_chunks = 0, max_L = 0, max_items = 0;
+    DevBuf<double> S, yy_train, yy_all;
+    DevBuf<double> Strain;            // per-level sums of X over TRAIN entries (p x SLP)
+    DevBuf<double> Sheld;             // S - Strain: per-level sums over the held-out entries
+    double cnt_train = 0, cnt_test = 0;
+    bool no_na = false;               // every entry is train or test: held-out == test
+    // held-out lists (element index, value) of every gene (col) and of every sample (row); padded to LIST_ALIGN
+    DevBuf<uint32_t> col_ptr, row_ptr;
+    DevBuf<int> col_idx, row_idx;
+    DevBuf<double> col_val, row_val;
+    DevBuf<uint8_t> col_flag;         // per column-side list entry: 1 = test entry (only kept when the data has NA entries)
+    uint64_t col_entries = 0, row_entries = 0;
+    bool merged = false;              // the merged masked row update is available (categorical covariates only)
+    // factored column statistics (insider_col_factored.hpp)
+    ColFacArgs cf;                    // its static part
+    int cf_pos[CF_MAXC] = {0};        // position of covariate i in cf's order (decreasing level count)
+    bool cf_pair_ok = false;
+    DevBuf<uint8_t> cf_cnt;           // dense pair counts of every gene (pair-count form)
+    DevBuf<float> cf_hn;              // 1/2 held-out count per (gene, level) in the pair-count kernel's order (ColFacArgs::hn)
+    DevBuf<double> cf_zt;             // real-valued counts of the continuous covariates in the same order (ColFacArgs::zt), m <= 4
     // merged row update with continuous covariates (m <= 4, real-valued counts ColFacArgs::zt): column k is a ONE-level
     // covariate whose membership weights are z_rk — its (gene, weight) list carries sum_{r in H(j)} z_rk^2, its pair "counts"
-    // sum_{r in l} z_rk per categorical level and (Z'Z)[k][k'] per other column, its |l| = sum_r z_rk^2
+    // sum_{r in l} z_rk per categorical level and (Z'Z)[k][k'] per other column, its |l| = sum_r z_rk^2.  The columns' lists
+    // are the same (every gene): one copy, contm_lists; contm[k] holds the weights and pair counts of column k
     std::vector<CovTables> contm;
-    double *cont_cnt = nullptr;    // [m] sum_r z_rk^2
+    CovTables contm_lists;
+    DevBuf<double> cont_cnt;          // [m] sum_r z_rk^2
     bool cont_merged = false;
-    int *ident_members = nullptr;  // 0..n-1
-    int max_chunks = 0, max_L = 0;
-    double *S = nullptr, *yy_train = nullptr, *yy_all = nullptr;
-    double cnt_train = 0, cnt_test = 0;
-    bool no_na = false;     // every entry is train or test: held-out == test
-    // held-out lists (element index, value) of every gene (col) and of every sample (row); padded to LIST_ALIGN
-    uint32_t *col_ptr = nullptr, *row_ptr = nullptr;
-    int *col_idx = nullptr, *row_idx = nullptr;
-    double *col_val = nullptr, *row_val = nullptr;
-    uint8_t *col_flag = nullptr;   // per column-side list entry: 1 = test entry (only kept when the data has NA entries)
-    uint64_t col_entries = 0, row_entries = 0;
-    // factor-dependent workspace for the current K
-    int K = 0, NB = 0, KP = 0, nseg = 1, seg_len = 0;
-    double *Astack = nullptr, *R = nullptr, *C = nullptr, *RtR = nullptr, *CCt = nullptr, *Qfull = nullptr, *SC = nullptr;
-    double *stat = nullptr, *stat_col = nullptr, *gram_part = nullptr, *sc_part = nullptr, *lvl_part = nullptr, *eq = nullptr;
-    double *lvl_sum = nullptr;
-    double *fperm = nullptr;      // max(n, p) x KP: the factor rows in k_tile_perm's order (k_list_stats4)
-    double *lvl_zero = nullptr;   // max_L x (STAT + 2 KP + 2) zeros: the (empty) held-out sums of the unmasked row update (unmasked_fused)
-    double *Strain = nullptr;         // per-level sums of X over TRAIN entries (p x SLP), once per data set
-    double *Sheld = nullptr;          // S - Strain: per-level sums over the held-out entries
-    double *Qheld = nullptr;          // p x KP workspace: sum_l A_l' Sheld[j][l]
-    int col_factored = 1;             // option: factored column statistics (insider_col_factored.hpp): 0 list kernel, 1 cost model, 2 look-up form, 3 pair-count form
-    uint8_t *cf_cnt = nullptr;        // dense pair counts of every gene (pair-count form), static per data set
-    float *cf_hn = nullptr;           // 1/2 held-out count per (gene, level) in the pair-count kernel's order (ColFacArgs::hn)
-    double *cf_zt = nullptr;          // real-valued counts of the continuous covariates in the same order (ColFacArgs::zt), m <= 4
-    bool cf_pair_ok = false;
-    int cf_pos[CF_MAXC] = {0};        // position of covariate i in cf's order (decreasing level count)
-    int row_counts = 1;               // option: k_gene_u from the dense pair counts when they exist
-    ColFacArgs cf;                    // its static part (filled at create)
-    size_t cf_lds = 0;
-    double *U = nullptr, *Ylvl = nullptr, *wpart = nullptr, *Vlev = nullptr;   // merged row update workspace
-    int max_items = 0;
-    bool merged = false;              // the merged masked row update is available (categorical covariates only)
-    int row_merged = 1;               // option: use it
-    int row_gemm = 1;                 // option "row_gemm": weighted SYRK of a many-level covariate as one GEMM over genes (k_wgemm)
-    double *wg_part = nullptr;        // its per-slab partial sums
-    int wg_waves = 1024;              // option "row_gemm_waves": waves the GEMM is cut into (sets the number of gene slabs)
-    uint8_t *wg_pair = nullptr;       // packed pair index -> (a, b), a >= b: [2][16 ntile]
-    int row_fused = 1;                // option "row_fused": level records' tail + equations + solve of the merged update in one launch
-    double *sse_train = nullptr, *sse_test = nullptr, *b2 = nullptr, *b1 = nullptr, *loss_buf = nullptr, *stage = nullptr;
-    int *sweeps = nullptr, *failflag = nullptr;
-    int *sweep_key = nullptr;   // smoothed sweep counts: the longest-first scheduling key (k_sched_bucket)
-    unsigned long long *sweep_total = nullptr;
-    unsigned *pc4_ticket = nullptr;     // k_col_paircnt4's gene tickets: counters that only grow
-    unsigned pc4_base[2] = {0, 0};      // ... and the value they stand at when the next launch starts: [one counter ? 1 : 0]
+
+    // the row factors as blocks of the stacked factor: covariate b < c, then (m > 0) the continuous columns
+    struct Block { int rows, off; };
+    int blocks() const { return c + (m > 0 ? 1 : 0); }
+    Block block(int b) const { return b < c ? Block{n_levels[b], lvl_off[b]} : Block{m, SLcat}; }
+
+    DataSet() = default;
+    DataSet(const DataSet &) = delete;
+    DataSet &operator=(const DataSet &) = delete;
+    ~DataSet() { (void)hipSetDevice(device); }   // (runs before the members free their buffers)
+};
+
+// The factor-dependent WORKSPACE of one handle for the current K (ensure_workspace), and the state that starts over with it.
+struct Workspace {
+    static constexpr int EARLY = 3;
+    int K = 0, NB = 0, KP = 0, nseg = 1;
+    int gram_blocks_p = 0, gram_blocks_n = 0, sc_blocks = 0;
+    DevBuf<double> Astack, R, C, RtR, CCt, Qfull, SC, stat, stat_col, gram_part, sc_part, lvl_part, eq, lvl_sum;
+    DevBuf<double> fperm;             // max(n, p) x KP: the factor rows in k_tile_perm's order (k_list_stats4)
+    DevBuf<double> lvl_zero;          // max_L x (STAT + 2 KP + 2) zeros: the (empty) held-out sums of the unmasked row update (unmasked_fused)
+    DevBuf<double> Qheld;             // p x KP: sum_l A_l' Sheld[j][l]
+    DevBuf<double> U, Ylvl, wpart, Vlev;   // merged row update
+    DevBuf<double> lvl_sum_all;       // [SLcat][STAT + 2 KP + 2]: the level records of every covariate
+    DevBuf<double> gram_part2, sc_part2;   // partial-sum buffers of the side-stream products
+    DevBuf<double> wg_part;           // k_wgemm's per-slab partial sums
+    DevBuf<uint8_t> wg_pair;          // packed pair index -> (a, b), a >= b: [2][16 ntile]
+    DevBuf<double> sse_train, sse_test, b2, b1, loss_buf, stage;
+    size_t stage_count = 0;
+    DevBuf<int> sweeps, failflag;
+    DevBuf<int> sweep_key;            // smoothed sweep counts: the longest-first scheduling key (k_sched_bucket)
+    DevBuf<unsigned long long> sweep_total;
+    DevBuf<unsigned> pc4_ticket;      // k_col_paircnt4's gene tickets: counters that only grow
+    unsigned pc4_base[2] = {0, 0};    // ... and the value they stand at when the next launch starts: [one counter ? 1 : 0]
     // where the register-resident sweep kernel of the current K keeps its table of code blocks (K <= 32; 0 = not asked yet): the
     // order table holds absolute block addresses (insider_cd_reg.hpp), published by a probe launch of that kernel
     unsigned long long cd_code_base = 0, cd_pair_base = 0;
-    unsigned long long *code_base_dev = nullptr;   // where the probe launch stores them (workspace)
-    int mm_fast = 1;                   // option "mm_fast": the small dense products on k_mm_rows2 / k_mm_reduce2 (default; 2: two column tiles per wave in the reductions)
-    int col_mfma4 = 1;                 // option "col_mfma4": pair-count statistics with the second product on v_mfma_f64_4x4x4 (k_col_paircnt4; default)
-    int cd_pairs = 1;                  // option "cd_pairs": route the sweeps through the kernel's blocks of two coordinate steps (default)
-    uint8_t *order = nullptr;          // the sweep-order table the next column solve reads: one of order_buf
-    uint8_t *order_buf[2] = {nullptr, nullptr};   // two tables: the next outer iteration's is built while the current solve runs
-    hipEvent_t ev_tab = nullptr;
+    DevBuf<unsigned long long> code_base_dev;   // where the probe launch stores them
+    uint8_t *order = nullptr;         // the sweep-order table the next column solve reads: one of order_buf
+    DevBuf<uint8_t> order_buf[2];     // two tables: the next outer iteration's is built while the current solve runs
     int order_rows = 0;
     // gene scheduling for the CD kernel: genes sorted by the sweep count of their previous solve
-    int *gene_perm = nullptr;
+    DevBuf<int> gene_perm;
     // the bucket sort behind it (k_sched_bucket / k_sched_scatter): two alternating sets of bucket counters, per gene its bucket
     // and its rank in the bucket
-    int *sched_cnt[2] = {nullptr, nullptr}, *sched_rank = nullptr;
-    uint16_t *sched_bkt = nullptr;
+    DevBuf<int> sched_cnt[2], sched_rank;
+    DevBuf<uint16_t> sched_bkt;
     int sched_flip = 0;
-    int n_simd = 1024;                // SIMDs of the device (4 per CU)
     // multi-pass column solves in the cold outer iterations (CdParams::sweep_limit): saved state of the unfinished genes,
     // their estimated remaining lengths (two buffers, alternating between passes) and the order of the next pass
-    double *cd_hsave = nullptr, *cd_isave = nullptr;
-    uint32_t *cd_pass_slot = nullptr;
-    int *cd_pass_perm[2] = {nullptr, nullptr}, *cd_pass_cnt = nullptr;   // cd_pass_cnt: CD_BUCKETS counters + 2 list lengths
-    int list_fine = 1;   // option "list_fine": 1 (default) = k_list_stats4 (4x4x4 matrix instruction) where it applies, 0 = k_list_stats
-    int cd_cold_iters = 3, cd_pass_first = 64, cd_pass_ratio = 4;   // options "cd_cold_iters", "cd_pass1" (0 = single pass), "cd_pass_ratio"
+    DevBuf<double> cd_hsave, cd_isave;
+    DevBuf<uint32_t> cd_pass_slot;
+    DevBuf<int> cd_pass_perm[2], cd_pass_cnt;   // cd_pass_cnt: CD_BUCKETS counters + 2 list lengths
     // longest-first gene orders of outer iterations 0..2 of the previous optimize() on this handle: the early iterations
     // of the next call (tune()'s next grid point) have similar per-gene sweep counts, its later ones do not
-    static constexpr int EARLY = 3;
-    int *perm_early[EARLY] = {nullptr, nullptr, nullptr};
+    DevBuf<int> perm_early[EARLY];
     bool have_early[EARLY] = {false, false, false};
     bool have_perm = false;
-    size_t stage_count = 0;
-    int gram_blocks_p = 0, gram_blocks_n = 0, sc_blocks = 0;
+};
+
+// events that order the handle's own streams against each other on ONE device: no timing, and no system-scope fence — what one
+// stream's kernels wrote must reach the other stream's kernels (device scope: every kernel boundary does that), not the host
+constexpr unsigned EV_SYNC = hipEventDisableTiming | hipEventDisableSystemFence;
+
+// The streams and events of one handle (each handle, clones included, has its own).
+struct Streams {
+    Stream stream;
+    // scheduling work that nothing but the next column solve needs (sweep keys -> gene order, the next iteration's sweep-order
+    // table) runs on a side stream, next to the row update, between two events
+    Stream side;
+    // the weighted SYRK of the merged row update depends on C only: all covariates' level sums are formed on a second
+    // side stream while the main stream computes V, u and U'C
+    Stream side2;
+    Stream side3;                     // C'C and (S^train C') of the merged row update, next to the weighted SYRK
+    Event ev_cd_done, ev_side_done, ev_prep, ev_c_ready;
+    Event ev_head;                    // recorded on side2 in front of the level Gram GEMM: the main chain's k_gene_u waits for it
+    std::vector<Event> ev_w;          // per covariate (and continuous column): its level Gram sums are done
+    Event ev_a_ready, ev_qfull, ev_qheld, ev_tab;
+
+    int create(int n_w)
+    {
+        HIPCHECK(hipStreamCreate(stream.out()));
+        for (Stream *s : {&side, &side2, &side3}) HIPCHECK(hipStreamCreateWithFlags(s->out(), hipStreamNonBlocking));
+        for (Event *e : {&ev_prep, &ev_c_ready, &ev_head, &ev_a_ready, &ev_qfull, &ev_qheld, &ev_cd_done, &ev_side_done, &ev_tab})
+            HIPCHECK(hipEventCreateWithFlags(e->out(), EV_SYNC));
+        ev_w.resize(n_w);
+        for (Event &e : ev_w) HIPCHECK(hipEventCreateWithFlags(e.out(), EV_SYNC));
+        return INSIDER_OK;
+    }
+    void synchronize() const
+    {
+        for (const Stream *s : {&stream, &side, &side2, &side3}) if (*s) (void)hipStreamSynchronize(*s);
+    }
+};
+
+struct Options {
+    int max_sweeps = 1 << 24, order_mode = 0, profile = 0, verbose = 0, cd_variant = 0, force_allreduce = 0;
+    int col_factored = 1;             // factored column statistics (insider_col_factored.hpp): 0 list kernel, 1 cost model, 2 look-up form, 3 pair-count form
+    int row_counts = 1;               // k_gene_u from the dense pair counts when they exist
+    int row_merged = 1;               // use the merged masked row update
+    int row_gemm = 1;                 // "row_gemm": weighted SYRK of a many-level covariate as one GEMM over genes (k_wgemm)
+    int wg_waves = 1024;              // "row_gemm_waves": waves the GEMM is cut into (sets the number of gene slabs)
+    int row_fused = 1;                // "row_fused": level records' tail + equations + solve of the merged update in one launch
+    int mm_fast = 1;                  // "mm_fast": the small dense products on k_mm_rows2 / k_mm_reduce2 (default; 2: two column tiles per wave in the reductions)
+    int col_mfma4 = 1;                // "col_mfma4": pair-count statistics with the second product on v_mfma_f64_4x4x4 (k_col_paircnt4; default)
+    int cd_pairs = 1;                 // "cd_pairs": route the sweeps through the kernel's blocks of two coordinate steps (default)
+    int list_fine = 1;                // "list_fine": 1 (default) = k_list_stats4 (4x4x4 matrix instruction) where it applies, 0 = k_list_stats
+    int cd_cold_iters = 3, cd_pass_first = 64, cd_pass_ratio = 4;   // "cd_cold_iters", "cd_pass1" (0 = single pass), "cd_pass_ratio"
+    double resid_stage_mb = 256.0;    // "resid_stage_mb": size of the device buffer the residual is copied out through
+    // "vd_stage_kb" bounds the LDS a block of k_vd_stats may stage its genes' level tables in (KiB)
+    double vd_stage_kb = 48.0;
+};
+
+// device workspace of the post-hoc calls (section "post-hoc interaction GLM"): grown on demand, freed with the handle
+struct PostWs {
+    // Ast: stacked row factors (SL x KPW, blocks not subtracted zero); U: n x KPW; cp: p x KPW; nz: K flags;
+    // part: slab partials of the per-sample statistics; stats: n x (K + 1); stage: residual copy-out buffer;
+    // gpart / gram: C C'; ints: host-built group tables; cpart / gsum: group sums; L / dinv / info: the factor;
+    // outs: coeff, se, dof
+    DevBuf<double> Ast, U, cp, part, stats, stage, gpart, gram, cpart, gsum, L, dinv, outs;
+    DevBuf<int> nz, ints, info;
+    // variance decomposition: vin = the host factors (A blocks at row offset x K, then C as p rows of K); vtab = the level
+    // table T (p rows of SL); vrec = the p records
+    DevBuf<double> vin, vtab, vrec;
+};
+
+}  // namespace
+
+struct insider_hip_handle {
+    std::shared_ptr<const DataSet> ds;
+    Streams st;
+    Options opt;
+    Workspace ws;
+    // post-hoc interaction GLM / residual / variance decomposition: a workspace of its own, so that nothing
+    // insider_hip_optimize() reads is touched
+    PostWs post;
+    // state of the running optimize()
+    bool side_pending = false;
+    bool w_ready = false;
+    bool qfull_pending = false;
+    bool qheld_pending = false;       // Qheld = S^held A of the factored column statistics is being formed on side3 (phase_R)
     // sharding
     int64_t gene_offset = 0;
     int rank = 0, world = 1;
     insider_allreduce_fn allreduce = nullptr;
     void *allreduce_user = nullptr;
-    ncclComm_t comm = nullptr;     // RCCL communicator over the gene-sharded ranks (insider_hip_comm_init); owned
-    // options
-    int max_sweeps = 1 << 24, order_mode = 0, profile = 0, verbose = 0, cd_variant = 0, force_allreduce = 0;
+    ncclComm_t comm = nullptr;        // RCCL communicator over the gene-sharded ranks (insider_hip_comm_init); owned
     // profile of the last optimize()
-    std::vector<hipEvent_t> ev_col, ev_row, ev_cd, ev_test;
+    std::vector<Event> ev_col, ev_row, ev_cd, ev_test;
     double prof[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     double steady_cd_ms = 0, steady_col_ms = 0;   // means over the outer iterations >= 5 of the last profiled optimize()
     // of the last optimize() / optimize_col(): genes whose elastic-net solve was ended by max_sweeps, not by convergence
@@ -244,60 +354,24 @@ struct insider_hip_handle {
     int col_solver = 0, col_eval = 0, col_ridge_fallback = 0;
     // of the last optimize() / optimize_row(): one bit per row-phase kernel form it launched (RowKernel)
     uint64_t row_kernels = 0;
-    // post-hoc interaction GLM / residual (insider_hip_residual, insider_hip_interaction_glm): a workspace of its own, so
-    // that nothing insider_hip_optimize() reads is touched; allocated on first use, grown on demand, freed with the handle
-    PostWs *post = nullptr;
-    double resid_stage_mb = 256.0;   // option "resid_stage_mb": size of the device buffer the residual is copied out through
-    // variance decomposition (insider_hip_variance_decomposition): option "vd_stage_kb" bounds the LDS a block of k_vd_stats
-    // may stage its genes' level tables in (KiB); vd_path = the form the last call ran (1 = tables in LDS, 2 = from global)
-    double vd_stage_kb = 48.0;
+    // the form the last variance decomposition ran (1 = tables in LDS, 2 = from global)
     int vd_path = 0;
+
+    // work still in flight is drained and the communicator closed before the members free their buffers (the data set with
+    // its last handle)
+    ~insider_hip_handle()
+    {
+        if (ds) (void)hipSetDevice(ds->device);
+        st.synchronize();
+        if (comm) (void)ncclCommDestroy(comm);
+    }
 };
 
 namespace {
 
-// events that order the handle's own streams against each other on ONE device: no timing, and no system-scope fence — what one
-// stream's kernels wrote must reach the other stream's kernels (device scope: every kernel boundary does that), not the host
-constexpr unsigned EV_SYNC = hipEventDisableTiming | hipEventDisableSystemFence;
-
 constexpr int PC4_PARTS = 16;        // ticket counters of k_col_paircnt4
 constexpr int MM_FAST_MIN = 16384;   // rows from which k_mm_rows2 / k_mm_reduce2 run (below: the staging and the longer waves cost more than they save; c1: 5000 genes)
 constexpr int MM_SLAB = 128;  // rows per partial of the reduction products (insider_mm.hpp)
-
-// every K-dependent device buffer of a handle (ensure_workspace), as pointer slots
-std::vector<void **> workspace_slots(insider_hip_handle *h)
-{
-    std::vector<void **> v;
-    auto add = [&v](auto &ptr) { v.push_back(reinterpret_cast<void **>(&ptr)); };
-    add(h->Astack); add(h->R); add(h->C); add(h->RtR); add(h->CCt); add(h->Qfull); add(h->SC); add(h->stat); add(h->stat_col);
-    add(h->gram_part); add(h->sc_part); add(h->gram_part2); add(h->sc_part2); add(h->lvl_part); add(h->lvl_sum); add(h->lvl_zero); add(h->fperm); add(h->lvl_sum_all);
-    add(h->U); add(h->Ylvl); add(h->wpart); add(h->Vlev); add(h->Qheld); add(h->eq); add(h->sse_train); add(h->sse_test); add(h->b2);
-    add(h->b1); add(h->loss_buf); add(h->stage); add(h->wg_part); add(h->wg_pair); add(h->sweeps); add(h->sweep_key); add(h->failflag);
-    add(h->sweep_total); add(h->pc4_ticket); add(h->order_buf[0]); add(h->order_buf[1]); add(h->gene_perm); add(h->sched_cnt[0]); add(h->sched_cnt[1]);
-    add(h->sched_rank); add(h->sched_bkt); add(h->cd_hsave); add(h->cd_isave); add(h->cd_pass_slot);
-    add(h->cd_pass_perm[0]); add(h->cd_pass_perm[1]); add(h->cd_pass_cnt); add(h->code_base_dev);
-    for (int e = 0; e < insider_hip_handle::EARLY; ++e) add(h->perm_early[e]);
-    return v;
-}
-
-// drop the workspace WITHOUT freeing it (a clone starts from a copy of its source's fields: the buffers are the source's)
-void forget_workspace(insider_hip_handle *h)
-{
-    for (void **slot : workspace_slots(h)) *slot = nullptr;
-    h->order = nullptr;
-    h->order_rows = 0;
-    h->cd_code_base = h->cd_pair_base = 0;
-    for (int e = 0; e < insider_hip_handle::EARLY; ++e) h->have_early[e] = false;
-    h->have_perm = false;
-    h->K = 0;
-}
-
-void free_workspace(insider_hip_handle *h)
-{
-    for (void **slot : workspace_slots(h))
-        if (*slot) (void)hipFree(*slot);
-    forget_workspace(h);
-}
 
 // the kernel forms the row phase can launch, as insider_hip_get_info("row_kernels") reports them: bit RK_* is set on the host
 // where its form is launched (include/insider_hip.h; insider_amd/_lib.py ROW_KERNELS names them in this order)
@@ -321,9 +395,9 @@ struct WgPlan {
 WgPlan wgemm_plan(const insider_hip_handle *h, int i, int K, bool whatever_the_option = false)
 {
     WgPlan w;
-    if (!((h->row_gemm || whatever_the_option) && h->cf_pair_ok && h->cf_hn && h->merged && h->c <= CF_MAXC && K >= 1)) return w;
+    if (!((h->opt.row_gemm || whatever_the_option) && h->ds->cf_pair_ok && h->ds->cf_hn && h->ds->merged && h->ds->c <= CF_MAXC && K >= 1)) return w;
     const int NB = (K + 1 + 15) / 16;
-    const int L = h->cov[i].L, NBLK = NB * (NB + 1) / 2;
+    const int L = h->ds->cov[i].L, NBLK = NB * (NB + 1) / 2;
     w.tiles = cdiv(L, 16);
     w.npair = K * (K + 1) / 2;
     w.ntile = cdiv(w.npair, 16);
@@ -334,9 +408,9 @@ WgPlan wgemm_plan(const insider_hip_handle *h, int i, int K, bool whatever_the_o
     // one wave per SIMD: the kernel runs beside the main stream's V -> u -> U'C chain (other waves fill the machine), its
     // operands are prefetched a step ahead, and every slab costs a partial record (levels x pairs doubles) to write and re-read
     // (rounded DOWN: at most wg_waves waves in all — with the default, one per SIMD: a surplus block would run as a second round)
-    const int want = std::max(1, std::min<int>(h->wg_waves / waves_per_slab, (int)cdiv(h->p, 64)));
-    w.slab = (int)round_up(cdiv(h->p, want), 4);
-    w.nslab = (int)cdiv(h->p, w.slab);
+    const int want = std::max(1, std::min<int>(h->opt.wg_waves / waves_per_slab, (int)cdiv(h->ds->p, 64)));
+    w.slab = (int)round_up(cdiv(h->ds->p, want), 4);
+    w.nslab = (int)cdiv(h->ds->p, w.slab);
     w.use = true;
     return w;
 }
@@ -344,54 +418,56 @@ WgPlan wgemm_plan(const insider_hip_handle *h, int i, int K, bool whatever_the_o
 int ensure_workspace(insider_hip_handle *h, int K)
 {
     if (K < 1 || K > INSIDER_MAX_K) return fail(INSIDER_ERR_UNSUPPORTED, "K must be in 1..63");
-    if (h->K == K) return INSIDER_OK;
-    free_workspace(h);
+    if (h->ws.K == K) return INSIDER_OK;
+    h->ws = Workspace();   // the old buffers go first: two workspaces are never held at once
+    const DataSet &d = *h->ds;
+    const hipStream_t st = h->st.stream;
+    Workspace w;
     const int NB = (K + 1 + 15) / 16, KP = 16 * NB, NBLK = NB * (NB + 1) / 2, STAT = NBLK * 256;
-    h->NB = NB;
-    h->KP = KP;
-    // row-side segmentation: enough work items to fill 256 CUs even for few samples
-    // enough work items to fill 256 CUs even for few samples: split long lists into up to 64 segments
-    const int64_t avg_batches = (int64_t)(h->row_entries / (uint64_t)LIST_ALIGN / (uint64_t)std::max<int64_t>(h->n, 1));
-    int nseg = (int)std::min<int64_t>(std::max<int64_t>(1, cdiv(8192, h->n)), std::max<int64_t>(1, avg_batches / 16));
+    w.NB = NB;
+    w.KP = KP;
+    // row-side segmentation: enough work items to fill 256 CUs even for few samples: split long lists into up to 64 segments
+    const int64_t avg_batches = (int64_t)(d.row_entries / (uint64_t)LIST_ALIGN / (uint64_t)std::max<int64_t>(d.n, 1));
+    int nseg = (int)std::min<int64_t>(std::max<int64_t>(1, cdiv(8192, d.n)), std::max<int64_t>(1, avg_batches / 16));
     nseg = std::min(nseg, 64);
-    h->nseg = nseg;
-    h->seg_len = 0;
-    h->gram_blocks_p = cdiv(h->p, MM_SLAB);
-    h->gram_blocks_n = cdiv(h->n, MM_SLAB);
-    h->sc_blocks = cdiv(h->p, MM_SLAB);
+    w.nseg = nseg;
+    w.gram_blocks_p = cdiv(d.p, MM_SLAB);
+    w.gram_blocks_n = cdiv(d.n, MM_SLAB);
+    w.sc_blocks = cdiv(d.p, MM_SLAB);
+    const size_t rec = STAT + 2 * KP + 2, max_L = std::max(d.max_L, 1);
     int rc;
     // 16 rows of zero padding: the pair-count statistics kernel reads whole blocks of 16 levels without clamping
-    if ((rc = dmalloc(&h->Astack, (size_t)(h->SL + 16) * KP))) return rc;
-    HIPCHECK(hipMemset(h->Astack, 0, (size_t)(h->SL + 16) * KP * sizeof(double)));
-    if ((rc = dmalloc(&h->R, (size_t)h->n * KP))) return rc;
-    if ((rc = dmalloc(&h->C, (size_t)(std::max<int64_t>(h->p, h->ldp) + 4) * KP))) return rc;   // + 4 zero rows: k_wgemm reads whole steps of four genes
-    if ((rc = dmalloc(&h->RtR, (size_t)KP * KP))) return rc;
-    if ((rc = dmalloc(&h->CCt, (size_t)KP * KP))) return rc;
-    if ((rc = dmalloc(&h->Qfull, (size_t)h->p * KP))) return rc;
-    if ((rc = dmalloc(&h->SC, (size_t)h->SL * KP))) return rc;
-    if ((rc = dmalloc(&h->stat, (size_t)nseg * h->n * STAT))) return rc;
-    if ((rc = dmalloc(&h->stat_col, (size_t)h->p * STAT))) return rc;
-    if ((rc = dmalloc(&h->gram_part, (size_t)std::max(h->gram_blocks_p, h->gram_blocks_n) * KP * KP))) return rc;
-    if ((rc = dmalloc(&h->sc_part, (size_t)h->sc_blocks * h->SL * KP))) return rc;
-    if ((rc = dmalloc(&h->lvl_part, (size_t)h->max_chunks * (STAT + 2 * KP + 2)))) return rc;
-    if ((rc = dmalloc(&h->lvl_sum, (size_t)std::max(h->max_L, 1) * (STAT + 2 * KP + 2)))) return rc;
+    if ((rc = w.Astack.alloc((size_t)(d.SL + 16) * KP))) return rc;
+    HIPCHECK(hipMemset(w.Astack, 0, (size_t)(d.SL + 16) * KP * sizeof(double)));
+    if ((rc = w.R.alloc((size_t)d.n * KP))) return rc;
+    if ((rc = w.C.alloc((size_t)(std::max<int64_t>(d.p, d.ldp) + 4) * KP))) return rc;   // + 4 zero rows: k_wgemm reads whole steps of four genes
+    if ((rc = w.RtR.alloc((size_t)KP * KP))) return rc;
+    if ((rc = w.CCt.alloc((size_t)KP * KP))) return rc;
+    if ((rc = w.Qfull.alloc((size_t)d.p * KP))) return rc;
+    if ((rc = w.SC.alloc((size_t)d.SL * KP))) return rc;
+    if ((rc = w.stat.alloc((size_t)nseg * d.n * STAT))) return rc;
+    if ((rc = w.stat_col.alloc((size_t)d.p * STAT))) return rc;
+    if ((rc = w.gram_part.alloc((size_t)std::max(w.gram_blocks_p, w.gram_blocks_n) * KP * KP))) return rc;
+    if ((rc = w.sc_part.alloc((size_t)w.sc_blocks * d.SL * KP))) return rc;
+    if ((rc = w.lvl_part.alloc((size_t)d.max_chunks * rec))) return rc;
+    if ((rc = w.lvl_sum.alloc(max_L * rec))) return rc;
     if (NB == 2 && K >= 16)   // (the statistics kernels that read it exist for 16 <= K <= 31)
-        if ((rc = dmalloc(&h->fperm, (size_t)std::max(h->n, h->p) * KP))) return rc;
-    if ((rc = dmalloc(&h->lvl_zero, (size_t)std::max(h->max_L, 1) * (STAT + 2 * KP + 2)))) return rc;
-    HIPCHECK(hipMemsetAsync(h->lvl_zero, 0, (size_t)std::max(h->max_L, 1) * (STAT + 2 * KP + 2) * sizeof(double), h->stream));
-    if (h->merged) {
+        if ((rc = w.fperm.alloc((size_t)std::max(d.n, d.p) * KP))) return rc;
+    if ((rc = w.lvl_zero.alloc(max_L * rec))) return rc;
+    HIPCHECK(hipMemsetAsync(w.lvl_zero, 0, max_L * rec * sizeof(double), st));
+    if (d.merged) {
         // k_wgemm (weighted SYRK as a GEMM over genes): partial sums per gene slab, and the packed pair index -> (a, b) table
         size_t wg_len = 0;
         int wg_ntile = 0;
-        for (int i = 0; i < h->c; ++i) {
-            const WgPlan w = wgemm_plan(h, i, K, true);
-            if (w.use) {
-                wg_len = std::max(wg_len, (size_t)w.nslab * (16 * w.tiles) * (16 * w.ntile));
-                wg_ntile = w.ntile;
+        for (int i = 0; i < d.c; ++i) {
+            const WgPlan g = wgemm_plan(h, i, K, true);
+            if (g.use) {
+                wg_len = std::max(wg_len, (size_t)g.nslab * (16 * g.tiles) * (16 * g.ntile));
+                wg_ntile = g.ntile;
             }
         }
         if (wg_len) {
-            if ((rc = dmalloc(&h->wg_part, wg_len))) return rc;
+            if ((rc = w.wg_part.alloc(wg_len))) return rc;
             std::vector<uint8_t> ab((size_t)2 * 16 * wg_ntile, (uint8_t)(KP - 1));   // padded pairs: column KP - 1 of C, always zero
             int idx = 0;
             for (int a = 0; a < K; ++a)
@@ -399,60 +475,54 @@ int ensure_workspace(insider_hip_handle *h, int K)
                     ab[idx] = (uint8_t)a;
                     ab[(size_t)16 * wg_ntile + idx] = (uint8_t)b;
                 }
-            if ((rc = dmalloc(&h->wg_pair, ab.size()))) return rc;
-            HIPCHECK(hipMemcpy(h->wg_pair, ab.data(), ab.size(), hipMemcpyHostToDevice));
+            if ((rc = w.wg_pair.upload(ab))) return rc;
         }
-        const int LP = (int)round_up(std::max(h->max_L, 1), 2);
-        if ((rc = dmalloc(&h->U, (size_t)h->p * LP))) return rc;
-        if ((rc = dmalloc(&h->Ylvl, (size_t)std::max(h->max_L, 1) * KP))) return rc;
-        if ((rc = dmalloc(&h->wpart, (size_t)std::max(h->max_items, 1) * STAT))) return rc;
-        if ((rc = dmalloc(&h->lvl_sum_all, (size_t)std::max(h->SL, 1) * (STAT + 2 * KP + 2)))) return rc;
-        if ((rc = dmalloc(&h->gram_part2, (size_t)std::max(h->gram_blocks_p, h->gram_blocks_n) * KP * KP))) return rc;
-        if ((rc = dmalloc(&h->sc_part2, (size_t)h->sc_blocks * h->SL * KP))) return rc;
-        if ((rc = dmalloc(&h->Vlev, (size_t)h->p * h->SLP))) return rc;
-        HIPCHECK(hipMemsetAsync(h->Vlev, 0, (size_t)h->p * h->SLP * sizeof(double), h->stream));   // (columns are filled as they are first needed)
-        if ((rc = dmalloc(&h->Qheld, (size_t)h->p * KP))) return rc;
+        if ((rc = w.U.alloc((size_t)d.p * round_up(max_L, 2)))) return rc;
+        if ((rc = w.Ylvl.alloc(max_L * KP))) return rc;
+        if ((rc = w.wpart.alloc((size_t)std::max(d.max_items, 1) * STAT))) return rc;
+        if ((rc = w.lvl_sum_all.alloc((size_t)std::max(d.SL, 1) * rec))) return rc;
+        if ((rc = w.gram_part2.alloc((size_t)std::max(w.gram_blocks_p, w.gram_blocks_n) * KP * KP))) return rc;
+        if ((rc = w.sc_part2.alloc((size_t)w.sc_blocks * d.SL * KP))) return rc;
+        if ((rc = w.Vlev.alloc((size_t)d.p * d.SLP))) return rc;
+        HIPCHECK(hipMemsetAsync(w.Vlev, 0, (size_t)d.p * d.SLP * sizeof(double), st));   // (columns are filled as they are first needed)
+        if ((rc = w.Qheld.alloc((size_t)d.p * KP))) return rc;
     }
-    if ((rc = dmalloc(&h->eq, (size_t)h->max_L * (KP * KP + KP)))) return rc;
-    if ((rc = dmalloc(&h->sse_train, (size_t)h->p))) return rc;
-    if ((rc = dmalloc(&h->sse_test, (size_t)h->p))) return rc;
-    if ((rc = dmalloc(&h->b2, (size_t)h->p))) return rc;
-    if ((rc = dmalloc(&h->b1, (size_t)h->p))) return rc;
-    if ((rc = dmalloc(&h->loss_buf, 8))) return rc;
-    h->stage_count = (size_t)std::max<int64_t>(std::max<int64_t>(h->p, h->n), h->SL) * KP;
-    if ((rc = dmalloc(&h->stage, h->stage_count))) return rc;
-    if ((rc = dmalloc(&h->sweeps, (size_t)h->p))) return rc;
+    if ((rc = w.eq.alloc((size_t)d.max_L * (KP * KP + KP)))) return rc;
+    for (DevBuf<double> *b : {&w.sse_train, &w.sse_test, &w.b2, &w.b1})
+        if ((rc = b->alloc((size_t)d.p))) return rc;
+    if ((rc = w.loss_buf.alloc(8))) return rc;
+    w.stage_count = (size_t)std::max<int64_t>(std::max<int64_t>(d.p, d.n), d.SL) * KP;
+    if ((rc = w.stage.alloc(w.stage_count))) return rc;
+    if ((rc = w.sweeps.alloc((size_t)d.p))) return rc;
     // [0] a system was singular, [1] ridge genes wait for the general route, [2] genes stopped by max_sweeps, [3] longest solve
-    if ((rc = dmalloc(&h->failflag, 4))) return rc;
-    if ((rc = dmalloc(&h->sweep_total, 256))) return rc;
-    if ((rc = dmalloc(&h->pc4_ticket, (size_t)(PC4_PARTS + 1) * 32))) return rc;   // (a 128-byte line per counter)
-    HIPCHECK(hipMemsetAsync(h->pc4_ticket, 0, (size_t)(PC4_PARTS + 1) * 32 * sizeof(unsigned), h->stream));
-    for (unsigned &b : h->pc4_base) b = 0;
-    if ((rc = dmalloc(&h->gene_perm, (size_t)h->p))) return rc;
-    if ((rc = dmalloc(&h->sched_cnt[0], (size_t)SCHED_BUCKETS))) return rc;
-    if ((rc = dmalloc(&h->sched_cnt[1], (size_t)SCHED_BUCKETS))) return rc;
-    if ((rc = dmalloc(&h->sched_rank, (size_t)h->p))) return rc;
-    if ((rc = dmalloc(&h->sched_bkt, (size_t)h->p))) return rc;
-    if ((rc = dmalloc(&h->sweep_key, (size_t)h->p))) return rc;
-    if ((rc = dmalloc(&h->cd_hsave, (size_t)h->p * KP))) return rc;
-    if ((rc = dmalloc(&h->cd_isave, (size_t)h->p * KP))) return rc;
-    if ((rc = dmalloc(&h->cd_pass_slot, (size_t)h->p))) return rc;
-    if ((rc = dmalloc(&h->cd_pass_perm[0], (size_t)h->p))) return rc;
-    if ((rc = dmalloc(&h->cd_pass_perm[1], (size_t)h->p))) return rc;
-    if ((rc = dmalloc(&h->cd_pass_cnt, (size_t)CD_BUCKETS + 2))) return rc;
-    if ((rc = dmalloc(&h->code_base_dev, 2))) return rc;
-    for (int e = 0; e < insider_hip_handle::EARLY; ++e)
-        if ((rc = dmalloc(&h->perm_early[e], (size_t)h->p))) return rc;
-    HIPCHECK(hipMemsetAsync(h->sched_cnt[0], 0, SCHED_BUCKETS * sizeof(int), h->stream));
-    HIPCHECK(hipMemsetAsync(h->sched_cnt[1], 0, SCHED_BUCKETS * sizeof(int), h->stream));
-    h->sched_flip = 0;
-    h->have_perm = false;
+    if ((rc = w.failflag.alloc(4))) return rc;
+    if ((rc = w.sweep_total.alloc(256))) return rc;
+    if ((rc = w.pc4_ticket.alloc((size_t)(PC4_PARTS + 1) * 32))) return rc;   // (a 128-byte line per counter)
+    HIPCHECK(hipMemsetAsync(w.pc4_ticket, 0, (size_t)(PC4_PARTS + 1) * 32 * sizeof(unsigned), st));
+    if ((rc = w.gene_perm.alloc((size_t)d.p))) return rc;
+    if ((rc = w.sched_cnt[0].alloc((size_t)SCHED_BUCKETS))) return rc;
+    if ((rc = w.sched_cnt[1].alloc((size_t)SCHED_BUCKETS))) return rc;
+    if ((rc = w.sched_rank.alloc((size_t)d.p))) return rc;
+    if ((rc = w.sched_bkt.alloc((size_t)d.p))) return rc;
+    if ((rc = w.sweep_key.alloc((size_t)d.p))) return rc;
+    if ((rc = w.cd_hsave.alloc((size_t)d.p * KP))) return rc;
+    if ((rc = w.cd_isave.alloc((size_t)d.p * KP))) return rc;
+    if ((rc = w.cd_pass_slot.alloc((size_t)d.p))) return rc;
+    if ((rc = w.cd_pass_perm[0].alloc((size_t)d.p))) return rc;
+    if ((rc = w.cd_pass_perm[1].alloc((size_t)d.p))) return rc;
+    if ((rc = w.cd_pass_cnt.alloc((size_t)CD_BUCKETS + 2))) return rc;
+    if ((rc = w.code_base_dev.alloc(2))) return rc;
+    for (DevBuf<int> &b : w.perm_early)
+        if ((rc = b.alloc((size_t)d.p))) return rc;
+    HIPCHECK(hipMemsetAsync(w.sched_cnt[0], 0, SCHED_BUCKETS * sizeof(int), st));
+    HIPCHECK(hipMemsetAsync(w.sched_cnt[1], 0, SCHED_BUCKETS * sizeof(int), st));
     // rows of the padded factor buffers beyond K must stay zero: C rows are gathered with pitch KP and the
     // pad genes of the transposed layout index rows p..ldp-1
-    HIPCHECK(hipMemsetAsync(h->C, 0, (size_t)(std::max<int64_t>(h->p, h->ldp) + 4) * KP * sizeof(double), h->stream));
-    HIPCHECK(hipMemsetAsync(h->R, 0, (size_t)h->n * KP * sizeof(double), h->stream));
-    HIPCHECK(hipMemsetAsync(h->failflag, 0, 4 * sizeof(int), h->stream));
-    h->K = K;
+    HIPCHECK(hipMemsetAsync(w.C, 0, (size_t)(std::max<int64_t>(d.p, d.ldp) + 4) * KP * sizeof(double), st));
+    HIPCHECK(hipMemsetAsync(w.R, 0, (size_t)d.n * KP * sizeof(double), st));
+    HIPCHECK(hipMemsetAsync(w.failflag, 0, 4 * sizeof(int), st));
+    w.K = K;
+    h->ws = std::move(w);
     return INSIDER_OK;
 }
 
@@ -469,20 +539,20 @@ int ensure_workspace(insider_hip_handle *h, int K)
 int launch_list_stats(insider_hip_handle *h, bool cols, int nseg, const double *F, double *stat,
                       const double *base = nullptr, uint64_t *mark = nullptr)
 {
-    const int units = cols ? (int)h->p : (int)h->n;
-    const int64_t f_rows = cols ? h->n : h->p;
-    const uint32_t *ptr = cols ? h->col_ptr : h->row_ptr;
-    const int *lidx = cols ? h->col_idx : h->row_idx;
-    const double *lval = cols ? h->col_val : h->row_val;
+    const int units = cols ? (int)h->ds->p : (int)h->ds->n;
+    const int64_t f_rows = cols ? h->ds->n : h->ds->p;
+    const uint32_t *ptr = cols ? h->ds->col_ptr : h->ds->row_ptr;
+    const int *lidx = cols ? h->ds->col_idx : h->ds->row_idx;
+    const double *lval = cols ? h->ds->col_val : h->ds->row_val;
     const int64_t items = (int64_t)units * nseg;
     // 16 <= K <= 31: the 4x4x4 form of the matrix instruction (fewer wasted outputs: 28 tiles instead of 3 blocks at K = 25)
-    const int NT = (h->K + 4) / 4;
-    if (h->list_fine && h->NB == 2 && NT >= 5 && NT <= 8 && h->fperm) {
+    const int NT = (h->ws.K + 4) / 4;
+    if (h->opt.list_fine && h->ws.NB == 2 && NT >= 5 && NT <= 8 && h->ws.fperm) {
         // the rows in the tile-pair order the kernel's 16-byte loads want (a copy: every other consumer keeps F's order)
-        hipLaunchKernelGGL(k_tile_perm, dim3(cdiv(f_rows * h->KP, 256)), dim3(256), 0, h->stream, F, f_rows, h->KP, h->fperm);
+        hipLaunchKernelGGL(k_tile_perm, dim3(cdiv(f_rows * h->ws.KP, 256)), dim3(256), 0, h->st.stream, F, f_rows, h->ws.KP, h->ws.fperm);
 #define LS4(NT_)                                                                                                               \
-    hipLaunchKernelGGL((k_list_stats4<2, NT_, 4>), dim3(cdiv(items, 4)), dim3(256), 0, h->stream, ptr, lidx, lval, units, nseg,   \
-                       (const double *)h->fperm, f_rows, stat, base, h->K)
+    hipLaunchKernelGGL((k_list_stats4<2, NT_, 4>), dim3(cdiv(items, 4)), dim3(256), 0, h->st.stream, ptr, lidx, lval, units, nseg,   \
+                       (const double *)h->ws.fperm, f_rows, stat, base, h->ws.K)
         switch (NT) {
             case 5: LS4(5); break;
             case 6: LS4(6); break;
@@ -494,8 +564,8 @@ int launch_list_stats(insider_hip_handle *h, bool cols, int nseg, const double *
         if (mark) *mark |= rk_bit(RK_LIST_STATS4);
         return INSIDER_OK;
     }
-    NB_DISPATCH(h->NB, hipLaunchKernelGGL((k_list_stats<NB_, WPB_>), dim3(cdiv(items, WPB_)), dim3(WPB_ * 64), 0,
-                                           h->stream, ptr, lidx, lval, units, nseg, F, f_rows, stat, base, h->K));
+    NB_DISPATCH(h->ws.NB, hipLaunchKernelGGL((k_list_stats<NB_, WPB_>), dim3(cdiv(items, WPB_)), dim3(WPB_ * 64), 0,
+                                           h->st.stream, ptr, lidx, lval, units, nseg, F, f_rows, stat, base, h->ws.K));
     KCHECK();
     if (mark) *mark |= rk_bit(RK_LIST_STATS);
     return INSIDER_OK;
@@ -503,32 +573,32 @@ int launch_list_stats(insider_hip_handle *h, bool cols, int nseg, const double *
 
 // ---- the small dense products on MFMA (insider_mm.hpp) -------------------------------------------------------------------
 // k_mm_rows2: tiles of 16 rows one wave takes — one until the grid fills every SIMD twice, then as many as keep it at that
-int mm_tiles_per_wave(const insider_hip_handle *h, int tiles) { return std::max(1, tiles / (2 * h->n_simd)); }
+int mm_tiles_per_wave(const insider_hip_handle *h, int tiles) { return std::max(1, tiles / (2 * h->ds->n_simd)); }
 
 // out[M x KP] = X[M x Kd] W[Kd x KP]   (W row-major with pitch KP)
 bool mm_rows2_fits(const insider_hip_handle *h, int64_t ldx, int M, int Kd)
 {
-    return h->mm_fast && M >= MM_FAST_MIN && ldx % 2 == 0 && (size_t)4 * cdiv(Kd, 16) * h->NB * 64 * sizeof(double) <= 64 * 1024;
+    return h->opt.mm_fast && M >= MM_FAST_MIN && ldx % 2 == 0 && (size_t)4 * cdiv(Kd, 16) * h->ws.NB * 64 * sizeof(double) <= 64 * 1024;
 }
 int launch_mm_rows_kp(insider_hip_handle *h, const double *X, int64_t ldx, int M, int Kd, const double *W, double *out,
                       hipStream_t st = nullptr)
 {
-    if (!st) st = h->stream;
+    if (!st) st = h->st.stream;
     if (mm_rows2_fits(h, ldx, M, Kd)) {
         const int tiles = cdiv(M, 16), tpw = mm_tiles_per_wave(h, tiles);
-        const size_t lds2 = (size_t)4 * cdiv(Kd, 16) * h->NB * 64 * sizeof(double);   // W staged in LDS
-        NB_DISPATCH(h->NB, {
+        const size_t lds2 = (size_t)4 * cdiv(Kd, 16) * h->ws.NB * 64 * sizeof(double);   // W staged in LDS
+        NB_DISPATCH(h->ws.NB, {
             (void)WPB_;
             hipLaunchKernelGGL((k_mm_rows2<NB_, false>), dim3(cdiv(cdiv(tiles, tpw), 4), 1), dim3(256), lds2, st, X, ldx, M, Kd, W,
-                               h->KP, h->KP, out, (int64_t)h->KP, h->KP, tpw);
+                               h->ws.KP, h->ws.KP, out, (int64_t)h->ws.KP, h->ws.KP, tpw);
         });
         KCHECK();
         return INSIDER_OK;
     }
-    NB_DISPATCH(h->NB, {
+    NB_DISPATCH(h->ws.NB, {
         (void)WPB_;
         hipLaunchKernelGGL((k_mm_rows<NB_, false>), dim3(cdiv(cdiv(M, 16), 4), 1), dim3(256), 0, st, X, ldx, M, Kd, W,
-                           h->KP, h->KP, out, (int64_t)h->KP, h->KP);
+                           h->ws.KP, h->ws.KP, out, (int64_t)h->ws.KP, h->ws.KP);
     });
     KCHECK();
     return INSIDER_OK;
@@ -540,17 +610,17 @@ int launch_mm_rows_kp(insider_hip_handle *h, const double *X, int64_t ldx, int M
 int launch_mm_reduce_kp(insider_hip_handle *h, const double *X, int64_t ldx, const double *Y, int M, int L, double *part,
                         double *out, hipStream_t st = nullptr, int *nslab = nullptr, uint64_t *mark = nullptr)
 {
-    if (!st) st = h->stream;
+    if (!st) st = h->st.stream;
     const int slabs = cdiv(M, MM_SLAB);
     if (nslab) *nslab = slabs;
-    if (h->mm_fast && M >= MM_FAST_MIN && L > 16) {   // several column tiles of X per wave, deeper look-ahead; the same partial sums (k_mm_reduce2)
+    if (h->opt.mm_fast && M >= MM_FAST_MIN && L > 16) {   // several column tiles of X per wave, deeper look-ahead; the same partial sums (k_mm_reduce2)
         const int lt = cdiv(L, 16);
 #define MR2(NBV, LTV)                                                                                                         \
-    hipLaunchKernelGGL((k_mm_reduce2<NBV, LTV>), dim3(slabs, cdiv(lt, LTV)), dim3(64), 0, st, X, ldx, Y, (int64_t)h->KP, M,   \
-                       MM_SLAB, L, h->KP, part, h->KP)
-        NB_DISPATCH(h->NB, {
+    hipLaunchKernelGGL((k_mm_reduce2<NBV, LTV>), dim3(slabs, cdiv(lt, LTV)), dim3(64), 0, st, X, ldx, Y, (int64_t)h->ws.KP, M,   \
+                       MM_SLAB, L, h->ws.KP, part, h->ws.KP)
+        NB_DISPATCH(h->ws.NB, {
             (void)WPB_;
-            if (lt <= 2 || h->mm_fast == 2 || NB_ > 2) {
+            if (lt <= 2 || h->opt.mm_fast == 2 || NB_ > 2) {
                 MR2(NB_, 2);
                 if (mark) *mark |= rk_bit(RK_MM_REDUCE2_2);
             } else {
@@ -560,17 +630,17 @@ int launch_mm_reduce_kp(insider_hip_handle *h, const double *X, int64_t ldx, con
         });
 #undef MR2
     } else {
-        NB_DISPATCH(h->NB, {
+        NB_DISPATCH(h->ws.NB, {
             (void)WPB_;
-            hipLaunchKernelGGL((k_mm_reduce<NB_>), dim3(slabs, cdiv(L, 16)), dim3(64), 0, st, X, ldx, Y, (int64_t)h->KP, M,
-                               MM_SLAB, L, h->KP, part, h->KP);
+            hipLaunchKernelGGL((k_mm_reduce<NB_>), dim3(slabs, cdiv(L, 16)), dim3(64), 0, st, X, ldx, Y, (int64_t)h->ws.KP, M,
+                               MM_SLAB, L, h->ws.KP, part, h->ws.KP);
         });
         if (mark) *mark |= rk_bit(RK_MM_REDUCE);
     }
     KCHECK();
     if (out)
-        hipLaunchKernelGGL(k_sum_partials, dim3(cdiv(L * h->KP, 16)), dim3(256), 0, st, (const double *)part, slabs,
-                           L * h->KP, out);
+        hipLaunchKernelGGL(k_sum_partials, dim3(cdiv(L * h->ws.KP, 16)), dim3(256), 0, st, (const double *)part, slabs,
+                           L * h->ws.KP, out);
     KCHECK();
     return INSIDER_OK;
 }
@@ -597,14 +667,14 @@ int r16_wide_lds(size_t bytes)
 int launch_gram(insider_hip_handle *h, const double *F, int64_t rows, double *out, hipStream_t st = nullptr,
                 double *part = nullptr)
 {
-    return launch_mm_reduce_kp(h, F, h->KP, F, (int)rows, h->KP, part ? part : h->gram_part, out, st);
+    return launch_mm_reduce_kp(h, F, h->ws.KP, F, (int)rows, h->ws.KP, part ? part : h->ws.gram_part, out, st);
 }
 
 int launch_build_R(insider_hip_handle *h)
 {
-    hipLaunchKernelGGL(k_build_R, dim3(cdiv(h->n * h->KP, 256)), dim3(256), 0, h->stream, (const int *)h->lev,
-                       (const int *)h->lvl_off_d, h->c, (int)h->n, (const double *)h->Astack, h->KP,
-                       (const double *)h->Zc, h->m, h->SLcat, h->R);
+    hipLaunchKernelGGL(k_build_R, dim3(cdiv(h->ds->n * h->ws.KP, 256)), dim3(256), 0, h->st.stream, (const int *)h->ds->lev,
+                       (const int *)h->ds->lvl_off_d, h->ds->c, (int)h->ds->n, (const double *)h->ws.Astack, h->ws.KP,
+                       (const double *)h->ds->Zc, h->ds->m, h->ds->SLcat, h->ws.R);
     KCHECK();
     return INSIDER_OK;
 }
@@ -616,53 +686,53 @@ bool use_col_factored(const insider_hip_handle *h);
 int phase_R(insider_hip_handle *h, bool use_side = false, bool r_is_current = false, bool want_qheld = false)
 {
     if (use_side) {
-        HIPCHECK(hipEventRecord(h->ev_a_ready, h->stream));
+        HIPCHECK(hipEventRecord(h->st.ev_a_ready, h->st.stream));
         // Qheld = S^held A, which the factored column statistics read: on the third stream (idle since the row phase's C'C),
         // beside R'R on the main one instead of behind it, and beside Qfull on the side stream (Qfull behind Qheld: DESIGN §4.5)
-        HIPCHECK(hipStreamWaitEvent(h->side, h->ev_a_ready, 0));
-        if (want_qheld && h->Qheld && use_col_factored(h)) {
-            HIPCHECK(hipStreamWaitEvent(h->side3, h->ev_a_ready, 0));
-            if (int rh = launch_mm_rows_kp(h, h->Sheld, h->SLP, (int)h->p, h->SL, h->Astack, h->Qheld, h->side3)) return rh;
-            HIPCHECK(hipEventRecord(h->ev_qheld, h->side3));
+        HIPCHECK(hipStreamWaitEvent(h->st.side, h->st.ev_a_ready, 0));
+        if (want_qheld && h->ws.Qheld && use_col_factored(h)) {
+            HIPCHECK(hipStreamWaitEvent(h->st.side3, h->st.ev_a_ready, 0));
+            if (int rh = launch_mm_rows_kp(h, h->ds->Sheld, h->ds->SLP, (int)h->ds->p, h->ds->SL, h->ws.Astack, h->ws.Qheld, h->st.side3)) return rh;
+            HIPCHECK(hipEventRecord(h->st.ev_qheld, h->st.side3));
             h->qheld_pending = true;
         }
-        int rq = launch_mm_rows_kp(h, h->S, h->SLP, (int)h->p, h->SL, h->Astack, h->Qfull, h->side);
+        int rq = launch_mm_rows_kp(h, h->ds->S, h->ds->SLP, (int)h->ds->p, h->ds->SL, h->ws.Astack, h->ws.Qfull, h->st.side);
         if (rq) return rq;
-        HIPCHECK(hipEventRecord(h->ev_qfull, h->side));
+        HIPCHECK(hipEventRecord(h->st.ev_qfull, h->st.side));
         h->qfull_pending = true;
     }
     int rc = r_is_current ? INSIDER_OK : launch_build_R(h);
     if (rc) return rc;
-    rc = launch_gram(h, h->R, h->n, h->RtR);
+    rc = launch_gram(h, h->ws.R, h->ds->n, h->ws.RtR);
     if (rc) return rc;
     if (use_side) return INSIDER_OK;
-    return launch_mm_rows_kp(h, h->S, h->SLP, (int)h->p, h->SL, h->Astack, h->Qfull);
+    return launch_mm_rows_kp(h, h->ds->S, h->ds->SLP, (int)h->ds->p, h->ds->SL, h->ws.Astack, h->ws.Qfull);
 }
 
 struct Timer {   // HIP-event pair around one launch on the library's stream (option "profile")
-    hipEvent_t e0 = nullptr, e1 = nullptr;
+    Event e0, e1;
     int begin(insider_hip_handle *h, bool on)
     {
-        if (!on || !h->profile) return INSIDER_OK;
+        if (!on || !h->opt.profile) return INSIDER_OK;
         // timing only: no system-scope fence (the cache write-back and invalidation it brings cost the FOLLOWING kernel ~20 us behind
         // a statistics launch that has just written 300 MB; nothing reads these events' work from the host)
-        HIPCHECK(hipEventCreateWithFlags(&e0, hipEventDisableSystemFence));
-        HIPCHECK(hipEventCreateWithFlags(&e1, hipEventDisableSystemFence));
-        HIPCHECK(hipEventRecord(e0, h->stream));
+        HIPCHECK(hipEventCreateWithFlags(e0.out(), hipEventDisableSystemFence));
+        HIPCHECK(hipEventCreateWithFlags(e1.out(), hipEventDisableSystemFence));
+        HIPCHECK(hipEventRecord(e0, h->st.stream));
         return INSIDER_OK;
     }
-    int end(insider_hip_handle *h, std::vector<hipEvent_t> &into)
+    int end(insider_hip_handle *h, std::vector<Event> &into)
     {
         if (!e0) return INSIDER_OK;
-        HIPCHECK(hipEventRecord(e1, h->stream));
-        into.push_back(e0);
-        into.push_back(e1);
+        HIPCHECK(hipEventRecord(e1, h->st.stream));
+        into.push_back(std::move(e0));
+        into.push_back(std::move(e1));
         return INSIDER_OK;
     }
 };
 
 // Builds the sweep-order table of outer iteration `iter` into order_buf[slot] (on `stream`); the caller makes it current
-// (h->order) when its solve is launched.  Two buffers: an outer iteration's table depends on (seed, iter) only, so the NEXT one
+// (h->ws.order) when its solve is launched.  Two buffers: an outer iteration's table depends on (seed, iter) only, so the NEXT one
 // is built while the current solve runs — the sweep kernel leaves no room for other waves, so the builder runs in its tail,
 // on SIMDs that have already drained — instead of competing with the row phase.
 // 32 < K <= 48 with an l1 term: the register-resident kernel with its third slot's matrix columns in LDS (insider_cd_reg.hpp)
@@ -671,22 +741,22 @@ static bool reg3_path(int K, double la) { return K > 32 && K <= 48 && la > 0.0; 
 // the address of the table of code blocks of k_cd_cols_reg<., KMAX(K), true> on this device (K <= 32): one probe launch per workspace
 int ensure_code_base(insider_hip_handle *h, int K)
 {
-    if (!reg_pairs(reg_kmax(K)) || h->cd_code_base) return INSIDER_OK;
-    unsigned long long *d = h->code_base_dev;
-    HIPCHECK(hipMemsetAsync(d, 0, 2 * sizeof(unsigned long long), h->stream));
+    if (!reg_pairs(reg_kmax(K)) || h->ws.cd_code_base) return INSIDER_OK;
+    unsigned long long *d = h->ws.code_base_dev;
+    HIPCHECK(hipMemsetAsync(d, 0, 2 * sizeof(unsigned long long), h->st.stream));
     ColArgs a{};
     a.p = 0;
     a.K = K;
-    a.KP = h->KP;
+    a.KP = h->ws.KP;
     a.code_base = d;
-    REG_DISPATCH(K, hipLaunchKernelGGL((k_cd_cols_reg<SL_, KM_, true>), dim3(1), dim3(64), 0, h->stream, a));
+    REG_DISPATCH(K, hipLaunchKernelGGL((k_cd_cols_reg<SL_, KM_, true>), dim3(1), dim3(64), 0, h->st.stream, a));
     KCHECK();
     unsigned long long v[2] = {0, 0};
-    HIPCHECK(hipMemcpyAsync(v, d, sizeof(v), hipMemcpyDeviceToHost, h->stream));
-    HIPCHECK(hipStreamSynchronize(h->stream));
+    HIPCHECK(hipMemcpyAsync(v, d, sizeof(v), hipMemcpyDeviceToHost, h->st.stream));
+    HIPCHECK(hipStreamSynchronize(h->st.stream));
     if (!v[0] || !v[1]) return fail(INSIDER_ERR_HIP, "the sweep kernel did not publish the addresses of its code blocks");
-    h->cd_code_base = v[0];
-    h->cd_pair_base = v[1];
+    h->ws.cd_code_base = v[0];
+    h->ws.cd_pair_base = v[1];
     return INSIDER_OK;
 }
 
@@ -694,24 +764,20 @@ int ensure_order_table(insider_hip_handle *h, uint64_t seed, uint32_t iter, int 
                        hipStream_t stream = nullptr, int slot = 0)
 {
     if (int rb = ensure_code_base(h, K)) return rb;
-    if (!stream) stream = h->stream;
+    if (!stream) stream = h->st.stream;
     // one period of the order sequence at most (include/insider_perm.h): the table does not grow with max_sweeps
     const int rows = std::min<int64_t>(max_sweeps, INSIDER_PERM_PERIOD);
-    if (h->order_rows < rows) {
-        for (auto &b : h->order_buf) {
-            if (b) (void)hipFree(b);
-            b = nullptr;
-            int rc = dmalloc(&b, (size_t)(rows + 4) * ORDER_ROW);   // + the look-ahead row (and the prologue's touch of the one after)
-            if (rc) return rc;
-        }
-        h->order_rows = rows;
+    if (h->ws.order_rows < rows) {
+        for (auto &b : h->ws.order_buf)
+            if (int rc = b.alloc((size_t)(rows + 4) * ORDER_ROW)) return rc;   // + the look-ahead row (and the prologue's touch of the one after)
+        h->ws.order_rows = rows;
     }
     // rows for K > 32 carry 64 row offsets (row16 kernel) unless the solve takes the register-resident kernel's successor list
     hipLaunchKernelGGL(k_order_table, dim3(cdiv((int64_t)(rows + 1) * 64, 256)), dim3(256), 0, stream, seed, iter, K, rows,
-                       order_mode, K * 8, reg_kmax(K), (K > 32 && !(h->cd_variant == 0 && reg3_path(K, la))) ? 1 : 0, h->cd_code_base,
-                       h->cd_pairs ? h->cd_pair_base : 0ull, h->order_buf[slot]);
+                       order_mode, K * 8, reg_kmax(K), (K > 32 && !(h->opt.cd_variant == 0 && reg3_path(K, la))) ? 1 : 0, h->ws.cd_code_base,
+                       h->opt.cd_pairs ? h->ws.cd_pair_base : 0ull, h->ws.order_buf[slot]);
     KCHECK();
-    if (!h->order) h->order = h->order_buf[slot];
+    if (!h->ws.order) h->ws.order = h->ws.order_buf[slot];
     return INSIDER_OK;
 }
 
@@ -720,14 +786,14 @@ int ensure_order_table(insider_hip_handle *h, uint64_t seed, uint32_t iter, int 
 // bucketed: the solve kernel has already done k_sched_bucket's part (ColArgs::sched_key ...), with the same counter set
 int launch_gene_order(insider_hip_handle *h, const int *sweeps, int reset, int float_bits, hipStream_t st, bool bucketed = false)
 {
-    int *cnt = h->sched_cnt[h->sched_flip], *cnt_next = h->sched_cnt[h->sched_flip ^ 1];
-    h->sched_flip ^= 1;
+    int *cnt = h->ws.sched_cnt[h->ws.sched_flip], *cnt_next = h->ws.sched_cnt[h->ws.sched_flip ^ 1];
+    h->ws.sched_flip ^= 1;
     if (!bucketed)
-        hipLaunchKernelGGL(k_sched_bucket, dim3(cdiv(h->p, 256)), dim3(256), 0, st, sweeps, (int)h->p, reset, float_bits,
-                           h->sweep_key, cnt, h->sched_bkt, h->sched_rank);
+        hipLaunchKernelGGL(k_sched_bucket, dim3(cdiv(h->ds->p, 256)), dim3(256), 0, st, sweeps, (int)h->ds->p, reset, float_bits,
+                           h->ws.sweep_key, cnt, h->ws.sched_bkt, h->ws.sched_rank);
     KCHECK();
-    hipLaunchKernelGGL(k_sched_scatter, dim3(cdiv(h->p, 256)), dim3(256), 0, st, (const int *)cnt, cnt_next,
-                       (const uint16_t *)h->sched_bkt, (const int *)h->sched_rank, (int)h->p, h->gene_perm);
+    hipLaunchKernelGGL(k_sched_scatter, dim3(cdiv(h->ds->p, 256)), dim3(256), 0, st, (const int *)cnt, cnt_next,
+                       (const uint16_t *)h->ws.sched_bkt, (const int *)h->ws.sched_rank, (int)h->ds->p, h->ws.gene_perm);
     KCHECK();
     return INSIDER_OK;
 }
@@ -740,26 +806,26 @@ int launch_gene_order(insider_hip_handle *h, const int *sweeps, int reset, int f
 // (model 14.5k vs 48k cycles) and 2.44 vs 0.66 ms (72k vs 24k).
 int col_stats_path(const insider_hip_handle *h)
 {
-    if (!(h->merged && h->col_factored && h->c <= CF_MAXC)) return 0;
-    if (h->m > 0) return (h->cf_pair_ok && h->cf_zt) ? 2 : 0;   // continuous covariates: the pair-count form with real-valued counts, or the lists
+    if (!(h->ds->merged && h->opt.col_factored && h->ds->c <= CF_MAXC)) return 0;
+    if (h->ds->m > 0) return (h->ds->cf_pair_ok && h->ds->cf_zt) ? 2 : 0;   // continuous covariates: the pair-count form with real-valued counts, or the lists
     const bool lookup_fits =
-        ((size_t)(h->cf.tab_rows + 1) * h->KP + 4 * 16 * 17) * sizeof(double) + (size_t)4 * CF_CAP * 2 <= 64 * 1024;
-    if (h->col_factored == 3 && h->cf_pair_ok) return 2;                   // forced
-    if (h->col_factored >= 2) return lookup_fits ? 1 : (h->cf_pair_ok ? 2 : 0);   // forced (3 without a count table: look-up form)
-    const double E = (double)h->col_entries / (double)std::max<int64_t>(h->p, 1);
-    const int NB = h->NB;
+        ((size_t)(h->ds->cf.tab_rows + 1) * h->ws.KP + 4 * 16 * 17) * sizeof(double) + (size_t)4 * CF_CAP * 2 <= 64 * 1024;
+    if (h->opt.col_factored == 3 && h->ds->cf_pair_ok) return 2;                   // forced
+    if (h->opt.col_factored >= 2) return lookup_fits ? 1 : (h->ds->cf_pair_ok ? 2 : 0);   // forced (3 without a count table: look-up form)
+    const double E = (double)h->ds->col_entries / (double)std::max<int64_t>(h->ds->p, 1);
+    const int NB = h->ws.NB;
     const double list = E * (NB * (NB + 1) / 2) * 16.0;
     double fac = 0.0, pair = 0.0;
-    for (int t = 0; t < h->cf.c; ++t) {
-        const double batches = std::ceil(std::max(1.0, E / h->cf.L[t]) / 16.0);
-        fac += std::ceil(h->cf.L[t] / 4.0) * (NB * NB * 64.0 + h->cf.nlater[t] * batches * 16.0 * (2 + NB) * 4.6);
-        pair += std::ceil(h->cf.L[t] / 4.0) * NB * NB * 64.0 +
-                std::ceil(h->cf.L[t] / 16.0) * ((h->cf.nlater[t] > 0 ? h->cf.nsteps * NB * 64.0 : 0.0) + 150.0);
+    for (int t = 0; t < h->ds->cf.c; ++t) {
+        const double batches = std::ceil(std::max(1.0, E / h->ds->cf.L[t]) / 16.0);
+        fac += std::ceil(h->ds->cf.L[t] / 4.0) * (NB * NB * 64.0 + h->ds->cf.nlater[t] * batches * 16.0 * (2 + NB) * 4.6);
+        pair += std::ceil(h->ds->cf.L[t] / 4.0) * NB * NB * 64.0 +
+                std::ceil(h->ds->cf.L[t] / 16.0) * ((h->ds->cf.nlater[t] > 0 ? h->ds->cf.nsteps * NB * 64.0 : 0.0) + 150.0);
     }
     double best = list;
     int path = 0;
     if (lookup_fits && 1.3 * fac < best) { best = 1.3 * fac; path = 1; }
-    if (h->cf_pair_ok && 1.3 * pair < best) { best = 1.3 * pair; path = 2; }
+    if (h->ds->cf_pair_ok && 1.3 * pair < best) { best = 1.3 * pair; path = 2; }
     return path;
 }
 bool use_col_factored(const insider_hip_handle *h) { return col_stats_path(h) != 0; }
@@ -768,14 +834,14 @@ bool use_col_factored(const insider_hip_handle *h) { return col_stats_path(h) !=
 int launch_paircnt(insider_hip_handle *h, const ColFacArgs &a)
 {
     const int blocks = cdiv(a.p, 4);
-    if (h->col_mfma4 && h->NB <= 2 && !(a.zt && a.nsteps > 4)) {   // (real-valued counts with more than four k-steps: 180 registers, two waves per SIMD)
+    if (h->opt.col_mfma4 && h->ws.NB <= 2 && !(a.zt && a.nsteps > 4)) {   // (real-valued counts with more than four k-steps: 180 registers, two waves per SIMD)
         // second product on the 4x4x4 matrix instruction, factor rows of every position staged in LDS (k_col_paircnt4);
         size_t quads = 1;
         for (int t = 0; t < a.c + (a.zt ? 1 : 0); ++t) quads += (size_t)(a.L[t] + 3) / 4;
-        const size_t lds = ((size_t)4 * 16 * 17 + (size_t)h->KP * h->KP + (size_t)4 * a.nsteps * h->KP + 4 * quads * h->KP) * sizeof(double);
+        const size_t lds = ((size_t)4 * 16 * 17 + (size_t)h->ws.KP * h->ws.KP + (size_t)4 * a.nsteps * h->ws.KP + 4 * quads * h->ws.KP) * sizeof(double);
         if (lds <= 64 * 1024) {
             // as many blocks as stay resident (48.6 KB of LDS at c3: three per CU); each walks the groups of four genes with the grid's stride
-            const int resident = std::max(1, std::min((int)(160 * 1024 / lds), (a.zt && a.nsteps > 4) ? 2 : 3)) * std::max(1, h->n_simd / 4);   // registers: 148 - 166 (180 with real-valued counts and more than four k-steps)
+            const int resident = std::max(1, std::min((int)(160 * 1024 / lds), (a.zt && a.nsteps > 4) ? 2 : 3)) * std::max(1, h->ds->n_simd / 4);   // registers: 148 - 166 (180 with real-valued counts and more than four k-steps)
             int nb = std::min(blocks, resident);
             const int npart = nb >= PC4_PARTS ? PC4_PARTS : 1;      // ticket counters in use (k_col_paircnt4)
             nb -= nb % npart;
@@ -783,29 +849,29 @@ int launch_paircnt(insider_hip_handle *h, const ColFacArgs &a)
             // a launch with ONE counter (few blocks) has a counter of its own behind the sixteen, so that the sixteen always
             // stand at the same value
             const int which = npart == 1 ? 1 : 0;
-            unsigned *tk = h->pc4_ticket + (size_t)which * PC4_PARTS * 32;
-            const unsigned tbase = h->pc4_base[which];
+            unsigned *tk = h->ws.pc4_ticket + (size_t)which * PC4_PARTS * 32;
+            const unsigned tbase = h->ws.pc4_base[which];
 #define PC4(NBV, MS)                                                                                                         \
     {                                                                                                                        \
-        if (a.zt) hipLaunchKernelGGL((k_col_paircnt4<NBV, 4, MS, true>), dim3(nb), dim3(256), lds, h->stream, a, tk, tbase, npart, cap); \
-        else hipLaunchKernelGGL((k_col_paircnt4<NBV, 4, MS, false>), dim3(nb), dim3(256), lds, h->stream, a, tk, tbase, npart, cap); \
+        if (a.zt) hipLaunchKernelGGL((k_col_paircnt4<NBV, 4, MS, true>), dim3(nb), dim3(256), lds, h->st.stream, a, tk, tbase, npart, cap); \
+        else hipLaunchKernelGGL((k_col_paircnt4<NBV, 4, MS, false>), dim3(nb), dim3(256), lds, h->st.stream, a, tk, tbase, npart, cap); \
     }
-            if (h->NB == 1 && a.nsteps <= 4) PC4(1, 4)
-            else if (h->NB == 1) PC4(1, 8)
+            if (h->ws.NB == 1 && a.nsteps <= 4) PC4(1, 4)
+            else if (h->ws.NB == 1) PC4(1, 8)
             else if (a.nsteps <= 4) PC4(2, 4)
             else PC4(2, 8)
 #undef PC4
             KCHECK();
             // what the launch takes from each counter in use: its items and one ticket per wave (only once it is known to be enqueued)
-            h->pc4_base[which] += (unsigned)cap + 4u * (unsigned)(nb / npart);
+            h->ws.pc4_base[which] += (unsigned)cap + 4u * (unsigned)(nb / npart);
             return INSIDER_OK;
         }
     }
-    NB_DISPATCH(h->NB, {
+    NB_DISPATCH(h->ws.NB, {
         (void)WPB_;
         const size_t lds = ((size_t)4 * 16 * 17 + (size_t)Geo<NB_>::KP * Geo<NB_>::KP + (size_t)4 * a.nsteps * Geo<NB_>::KP) * sizeof(double);
-        if (a.zt) hipLaunchKernelGGL((k_col_paircnt<NB_, 4, true>), dim3(blocks), dim3(256), lds, h->stream, a);
-        else hipLaunchKernelGGL((k_col_paircnt<NB_, 4, false>), dim3(blocks), dim3(256), lds, h->stream, a);
+        if (a.zt) hipLaunchKernelGGL((k_col_paircnt<NB_, 4, true>), dim3(blocks), dim3(256), lds, h->st.stream, a);
+        else hipLaunchKernelGGL((k_col_paircnt<NB_, 4, false>), dim3(blocks), dim3(256), lds, h->st.stream, a);
     });
     KCHECK();
     return INSIDER_OK;
@@ -817,39 +883,39 @@ int launch_col_stats(insider_hip_handle *h, bool timed)
     Timer t;
     int rc;
     if (use_col_factored(h) && h->qheld_pending) {   // Qheld = S^held A formed on side3 since the row factors were final (phase_R):
-        HIPCHECK(hipStreamWaitEvent(h->stream, h->ev_qheld, 0));   // joined BEFORE the timer, which then holds the statistics kernel alone
+        HIPCHECK(hipStreamWaitEvent(h->st.stream, h->st.ev_qheld, 0));   // joined BEFORE the timer, which then holds the statistics kernel alone
         h->qheld_pending = false;
         if ((rc = t.begin(h, timed))) return rc;
     } else {
         if ((rc = t.begin(h, timed))) return rc;
         if (use_col_factored(h))
-            if ((rc = launch_mm_rows_kp(h, h->Sheld, h->SLP, (int)h->p, h->SL, h->Astack, h->Qheld))) return rc;
+            if ((rc = launch_mm_rows_kp(h, h->ds->Sheld, h->ds->SLP, (int)h->ds->p, h->ds->SL, h->ws.Astack, h->ws.Qheld))) return rc;
     }
     if (use_col_factored(h)) {
-        ColFacArgs a = h->cf;
-        a.K = h->K;
-        a.Astack = h->Astack;
-        a.Qheld = h->Qheld;
-        a.RtR = h->RtR;
-        a.yy_all = h->yy_all;
-        a.yy_train = h->yy_train;
-        a.stat = h->stat_col;
+        ColFacArgs a = h->ds->cf;
+        a.K = h->ws.K;
+        a.Astack = h->ws.Astack;
+        a.Qheld = h->ws.Qheld;
+        a.RtR = h->ws.RtR;
+        a.yy_all = h->ds->yy_all;
+        a.yy_train = h->ds->yy_train;
+        a.stat = h->ws.stat_col;
         if (col_stats_path(h) == 2) {
-            a.cnt = h->cf_cnt;
-            a.hn = h->cf_hn;
-            a.zt = h->cf_zt;
+            a.cnt = h->ds->cf_cnt;
+            a.hn = h->ds->cf_hn;
+            a.zt = h->ds->cf_zt;
             rc = launch_paircnt(h, a);
             if (rc) return rc;
         } else {
-            NB_DISPATCH(h->NB, {
+            NB_DISPATCH(h->ws.NB, {
                 (void)WPB_;
                 const size_t lds = ((size_t)(a.tab_rows + 1) * Geo<NB_>::KP + (size_t)4 * 16 * 17) * sizeof(double) + (size_t)4 * CF_CAP * 2;
-                hipLaunchKernelGGL((k_col_factored<NB_, 4>), dim3(cdiv(h->p, 4)), dim3(256), lds, h->stream, a);
+                hipLaunchKernelGGL((k_col_factored<NB_, 4>), dim3(cdiv(h->ds->p, 4)), dim3(256), lds, h->st.stream, a);
             });
         }
         KCHECK();
     } else {
-        rc = launch_list_stats(h, true, 1, h->R, h->stat_col, h->RtR);   // the record's K x K part = R'R - complement
+        rc = launch_list_stats(h, true, 1, h->ws.R, h->ws.stat_col, h->ws.RtR);   // the record's K x K part = R'R - complement
         if (rc) return rc;
     }
     return t.end(h, h->ev_col);
@@ -866,15 +932,15 @@ enum ColSolver {
 int launch_col_solve(insider_hip_handle *h, int masked, bool solve, double lambda, double alpha, double tol,
                      int checkpoint, bool timed, int outer_iter = -1, bool side = false)
 {
-    const bool early = outer_iter >= 0 && outer_iter < insider_hip_handle::EARLY;
-    const int NBLK = h->NB * (h->NB + 1) / 2, STAT = NBLK * 256;
+    const bool early = outer_iter >= 0 && outer_iter < Workspace::EARLY;
+    const int NBLK = h->ws.NB * (h->ws.NB + 1) / 2, STAT = NBLK * 256;
     // (every stream join is a barrier packet on the main queue, ~5 us of bubble each at c3: ev_qfull is recorded on the side stream
     // AFTER the previous iteration's ev_side_done — phase_R comes after side_close — so it stands for both)
     if (h->side_pending)   // the gene order / sweep-order table prepared on the side stream
-        HIPCHECK(hipStreamWaitEvent(h->stream, h->ev_side_done, 0));
+        HIPCHECK(hipStreamWaitEvent(h->st.stream, h->st.ev_side_done, 0));
     h->side_pending = false;
     if (h->qfull_pending) {
-        HIPCHECK(hipStreamWaitEvent(h->stream, h->ev_qfull, 0));
+        HIPCHECK(hipStreamWaitEvent(h->st.stream, h->st.ev_qfull, 0));
         h->qfull_pending = false;
     }
     Timer t;
@@ -885,57 +951,57 @@ int launch_col_solve(insider_hip_handle *h, int masked, bool solve, double lambd
     h->col_solver = h->col_eval = h->col_ridge_fallback = CS_NONE;
     if (alpha == 0.0) {
         RidgeArgs a;
-        a.stat = masked ? h->stat_col : nullptr;
+        a.stat = masked ? h->ws.stat_col : nullptr;
         a.stat_len = STAT;
-        a.p = (int)h->p;
-        a.K = h->K;
-        a.KP = h->KP;
-        a.RtR = h->RtR;
-        a.Qfull = h->Qfull;
-        a.C = h->C;
-        a.yy = masked ? h->yy_train : h->yy_all;
+        a.p = (int)h->ds->p;
+        a.K = h->ws.K;
+        a.KP = h->ws.KP;
+        a.RtR = h->ws.RtR;
+        a.Qfull = h->ws.Qfull;
+        a.C = h->ws.C;
+        a.yy = masked ? h->ds->yy_train : h->ds->yy_all;
         a.lambda = lambda;
         a.solve = solve ? 1 : 0;
         a.checkpoint = checkpoint;
-        a.sse_train = h->sse_train;
-        a.b2 = h->b2;
-        a.b1 = h->b1;
-        a.sse_test = h->sse_test;
-        a.test_from_stats = masked && h->no_na;
-        a.fail = h->failflag;
-        a.mark = h->sweeps;          // free in the alpha == 0 path: cleared below
-        a.retry = h->failflag + 1;
+        a.sse_train = h->ws.sse_train;
+        a.b2 = h->ws.b2;
+        a.b1 = h->ws.b1;
+        a.sse_test = h->ws.sse_test;
+        a.test_from_stats = masked && h->ds->no_na;
+        a.fail = h->ws.failflag;
+        a.mark = h->ws.sweeps;          // free in the alpha == 0 path: cleared below
+        a.retry = h->ws.failflag + 1;
         a.only_marked = 0;
-        if (h->K <= 32 && h->cd_variant == 0) {
+        if (h->ws.K <= 32 && h->opt.cd_variant == 0) {
             if (solve) {
-                HIPCHECK(hipMemsetAsync(h->sweeps, 0, (size_t)h->p * sizeof(int), h->stream));
-                HIPCHECK(hipMemsetAsync(h->failflag + 1, 0, sizeof(int), h->stream));
+                HIPCHECK(hipMemsetAsync(h->ws.sweeps, 0, (size_t)h->ds->p * sizeof(int), h->st.stream));
+                HIPCHECK(hipMemsetAsync(h->ws.failflag + 1, 0, sizeof(int), h->st.stream));
             }
-            REG_DISPATCH(h->K, hipLaunchKernelGGL((k_ridge_cols_reg<SL_, KM_>), dim3(cdiv(h->p, 4)), dim3(64), 0, h->stream, a));
+            REG_DISPATCH(h->ws.K, hipLaunchKernelGGL((k_ridge_cols_reg<SL_, KM_>), dim3(cdiv(h->ds->p, 4)), dim3(64), 0, h->st.stream, a));
             h->col_solver = CS_RIDGE_REG;
             KCHECK();
             if (solve) {   // genes whose system was not positive definite: solve(..., likely_sympd)'s general route
                 a.only_marked = 1;
-                hipLaunchKernelGGL((k_ridge_cols<1>), dim3((unsigned)h->p), dim3(64), 0, h->stream, a);   // unmarked genes exit at once
+                hipLaunchKernelGGL((k_ridge_cols<1>), dim3((unsigned)h->ds->p), dim3(64), 0, h->st.stream, a);   // unmarked genes exit at once
                 h->col_ridge_fallback = 1;
             }
         } else {
-            hipLaunchKernelGGL((k_ridge_cols<1>), dim3((unsigned)h->p), dim3(64), 0, h->stream, a);
+            hipLaunchKernelGGL((k_ridge_cols<1>), dim3((unsigned)h->ds->p), dim3(64), 0, h->st.stream, a);
             h->col_solver = CS_RIDGE;
         }
         KCHECK();
-        if (solve) HIPCHECK(hipMemsetAsync(h->sweeps, 0, (size_t)h->p * sizeof(int), h->stream));
+        if (solve) HIPCHECK(hipMemsetAsync(h->ws.sweeps, 0, (size_t)h->ds->p * sizeof(int), h->st.stream));
     } else {
         ColArgs a;
-        a.stat = masked ? h->stat_col : nullptr;
+        a.stat = masked ? h->ws.stat_col : nullptr;
         a.stat_len = STAT;
-        a.p = (int)h->p;
-        a.K = h->K;
-        a.KP = h->KP;
-        a.RtR = h->RtR;
-        a.Qfull = h->Qfull;
-        a.C = h->C;
-        a.yy = masked ? h->yy_train : h->yy_all;
+        a.p = (int)h->ds->p;
+        a.K = h->ws.K;
+        a.KP = h->ws.KP;
+        a.RtR = h->ws.RtR;
+        a.Qfull = h->ws.Qfull;
+        a.C = h->ws.C;
+        a.yy = masked ? h->ds->yy_train : h->ds->yy_all;
         a.mode = solve ? COL_CD : COL_EVAL;
         a.checkpoint = checkpoint;
         a.cd.lambda = lambda;
@@ -945,32 +1011,32 @@ int launch_col_solve(insider_hip_handle *h, int masked, bool solve, double lambd
         a.cd.l2 = lambda * (1.0 - alpha);
         a.cd.two_la = 2.0 * a.cd.la;
         a.cd.inv_two_la = a.cd.la > 0.0 ? 0.5 / a.cd.la : 0.0;
-        a.cd.max_sweeps = h->max_sweeps;
-        a.cd.order = h->order;
-        a.sse_train = h->sse_train;
-        a.b2 = h->b2;
-        a.b1 = h->b1;
-        a.sse_test = h->sse_test;
-        a.test_from_stats = masked && h->no_na;
-        a.sweeps = h->sweeps;
-        a.sweep_bins = (timed && solve) ? h->sweep_total : nullptr;
-        a.gene_perm = !solve ? nullptr : (early && h->have_early[outer_iter]) ? h->perm_early[outer_iter]
-                                       : h->have_perm                         ? h->gene_perm
+        a.cd.max_sweeps = h->opt.max_sweeps;
+        a.cd.order = h->ws.order;
+        a.sse_train = h->ws.sse_train;
+        a.b2 = h->ws.b2;
+        a.b1 = h->ws.b1;
+        a.sse_test = h->ws.sse_test;
+        a.test_from_stats = masked && h->ds->no_na;
+        a.sweeps = h->ws.sweeps;
+        a.sweep_bins = (timed && solve) ? h->ws.sweep_total : nullptr;
+        a.gene_perm = !solve ? nullptr : (early && h->ws.have_early[outer_iter]) ? h->ws.perm_early[outer_iter]
+                                       : h->ws.have_perm                         ? h->ws.gene_perm
                                                                               : nullptr;
-        a.hsave = h->cd_hsave;
-        a.isave = h->cd_isave;
+        a.hsave = h->ws.cd_hsave;
+        a.isave = h->ws.cd_isave;
         a.pass_count = nullptr;
         a.resume = 0;
         a.pass_slot = nullptr;
         a.bucket_cnt = nullptr;
-        a.cap_hits = solve ? h->failflag + 2 : nullptr;
+        a.cap_hits = solve ? h->ws.failflag + 2 : nullptr;
         a.sched_key = a.sched_cnt = a.sched_rank = nullptr;
         a.sched_bkt = nullptr;
         a.sched_reset = 0;
-        const size_t r16_bytes = (size_t)r16_lds_doubles(h->K) * sizeof(double);
+        const size_t r16_bytes = (size_t)r16_lds_doubles(h->ws.K) * sizeof(double);
         // the register-resident kernel scales its state by 1 / (2 lambda alpha): lambda alpha = 0 (alpha < 0 or lambda = 0: no l1
         // term at all) takes the group kernel below
-        if (h->cd_variant == 0 && (h->K <= 32 || reg3_path(h->K, a.cd.la)) && a.cd.la > 0.0) {
+        if (h->opt.cd_variant == 0 && (h->ws.K <= 32 || reg3_path(h->ws.K, a.cd.la)) && a.cd.la > 0.0) {
             // Cold outer iterations: thousands of sweeps per gene whose counts no history predicts, so a wave's four genes
             // finish far apart (measured at c3: 1.17x / 1.44x / 2.1x the ideal wave time in outer iterations 0 / 1 / 2).
             // The solve then runs in passes over geometrically growing sweep ranges: a limited pass stops at its sweep
@@ -978,17 +1044,17 @@ int launch_col_solve(insider_hip_handle *h, int masked, bool solve, double lambd
             // of the loss change), k_pass_scatter groups them by that estimate, and the next pass continues them
             // bit-identically in waves of similar length (insider_cd_reg.hpp).  A pass with nothing left exits at once.
             if (solve) {   // every gene's part of the next launch order, when it finishes (launch_gene_order below skips k_sched_bucket)
-                a.sched_key = h->sweep_key;
-                a.sched_cnt = h->sched_cnt[h->sched_flip];
-                a.sched_rank = h->sched_rank;
-                a.sched_bkt = h->sched_bkt;
-                a.sched_reset = (outer_iter < insider_hip_handle::EARLY || !h->have_perm) ? 1 : 0;
+                a.sched_key = h->ws.sweep_key;
+                a.sched_cnt = h->ws.sched_cnt[h->ws.sched_flip];
+                a.sched_rank = h->ws.sched_rank;
+                a.sched_bkt = h->ws.sched_bkt;
+                a.sched_reset = (outer_iter < Workspace::EARLY || !h->ws.have_perm) ? 1 : 0;
                 fused_bucket = true;
             }
             int limits[16], npass = 0;
-            if (solve && outer_iter >= 0 && outer_iter < h->cd_cold_iters && h->cd_pass_first >= 32)
-                for (int64_t l = h->cd_pass_first; l < std::min<int64_t>(h->max_sweeps, 4 * (int64_t)INSIDER_PERM_PERIOD) && npass < 16;
-                     l *= std::max(h->cd_pass_ratio, 2))
+            if (solve && outer_iter >= 0 && outer_iter < h->opt.cd_cold_iters && h->opt.cd_pass_first >= 32)
+                for (int64_t l = h->opt.cd_pass_first; l < std::min<int64_t>(h->opt.max_sweeps, 4 * (int64_t)INSIDER_PERM_PERIOD) && npass < 16;
+                     l *= std::max(h->opt.cd_pass_ratio, 2))
                     limits[npass++] = (int)l;   // the last pass runs from the last limit to the end, however far that is
             int start = 0;
             const int *perm_in = a.gene_perm;
@@ -996,48 +1062,48 @@ int launch_col_solve(insider_hip_handle *h, int masked, bool solve, double lambd
                 const int limit = pass < npass ? limits[pass] : 0;
                 a.cd.start_sweep = start;
                 a.cd.sweep_limit = limit;
-                a.pass_slot = npass ? h->cd_pass_slot : nullptr;
-                a.bucket_cnt = limit ? h->cd_pass_cnt : nullptr;
-                if (limit) HIPCHECK(hipMemsetAsync(h->cd_pass_cnt, 0, CD_BUCKETS * sizeof(int), h->stream));
+                a.pass_slot = npass ? h->ws.cd_pass_slot : nullptr;
+                a.bucket_cnt = limit ? h->ws.cd_pass_cnt : nullptr;
+                if (limit) HIPCHECK(hipMemsetAsync(h->ws.cd_pass_cnt, 0, CD_BUCKETS * sizeof(int), h->st.stream));
                 if (solve) {
-                    REG_ANY_DISPATCH(h->K, hipLaunchKernelGGL((k_cd_cols_reg<SL_, KM_, true>), dim3(cdiv(h->p, 4)), dim3(64), 0, h->stream, a);
+                    REG_ANY_DISPATCH(h->ws.K, hipLaunchKernelGGL((k_cd_cols_reg<SL_, KM_, true>), dim3(cdiv(h->ds->p, 4)), dim3(64), 0, h->st.stream, a);
                                            h->col_solver = SL_ == 3 ? CS_CD_REG3 : CS_CD_REG);
                 }
                 KCHECK();
                 if (!limit) break;
-                int *count_out = h->cd_pass_cnt + CD_BUCKETS + (pass & 1);
-                hipLaunchKernelGGL(k_pass_scatter, dim3(cdiv(h->p, 256)), dim3(256), 0, h->stream,
-                                   (const uint32_t *)h->cd_pass_slot, (const int *)h->cd_pass_cnt, perm_in, a.pass_count, (int)h->p,
-                                   h->cd_pass_perm[pass & 1], count_out);
+                int *count_out = h->ws.cd_pass_cnt + CD_BUCKETS + (pass & 1);
+                hipLaunchKernelGGL(k_pass_scatter, dim3(cdiv(h->ds->p, 256)), dim3(256), 0, h->st.stream,
+                                   (const uint32_t *)h->ws.cd_pass_slot, (const int *)h->ws.cd_pass_cnt, perm_in, a.pass_count, (int)h->ds->p,
+                                   h->ws.cd_pass_perm[pass & 1], count_out);
                 KCHECK();
-                perm_in = a.gene_perm = h->cd_pass_perm[pass & 1];
+                perm_in = a.gene_perm = h->ws.cd_pass_perm[pass & 1];
                 a.pass_count = count_out;
                 a.resume = 1;
                 start = limit;
             }
             eval_after = checkpoint != 0;
             eval_args = a;
-        } else if (h->cd_variant == 2 && h->K <= 16) {
-            hipLaunchKernelGGL((k_cd_cols_r16<1>), dim3(cdiv(h->p, 4)), dim3(64), r16_bytes, h->stream, a);
+        } else if (h->opt.cd_variant == 2 && h->ws.K <= 16) {
+            hipLaunchKernelGGL((k_cd_cols_r16<1>), dim3(cdiv(h->ds->p, 4)), dim3(64), r16_bytes, h->st.stream, a);
             h->col_solver = CS_CD_R16_1;
-        } else if (h->cd_variant == 2 && h->K <= 32) {
-            hipLaunchKernelGGL((k_cd_cols_r16<2>), dim3(cdiv(h->p, 4)), dim3(64), r16_bytes, h->stream, a);
+        } else if (h->opt.cd_variant == 2 && h->ws.K <= 32) {
+            hipLaunchKernelGGL((k_cd_cols_r16<2>), dim3(cdiv(h->ds->p, 4)), dim3(64), r16_bytes, h->st.stream, a);
             h->col_solver = CS_CD_R16_2;
-        } else if (h->K <= 16) {
-            hipLaunchKernelGGL((k_cd_cols<16, 4>), dim3(cdiv(h->p, 16)), dim3(256), 0, h->stream, a);
+        } else if (h->ws.K <= 16) {
+            hipLaunchKernelGGL((k_cd_cols<16, 4>), dim3(cdiv(h->ds->p, 16)), dim3(256), 0, h->st.stream, a);
             h->col_solver = CS_CD_COLS16;
-        } else if (h->K <= 32) {
-            hipLaunchKernelGGL((k_cd_cols<32, 2>), dim3(cdiv(h->p, 4)), dim3(128), 0, h->stream, a);
+        } else if (h->ws.K <= 32) {
+            hipLaunchKernelGGL((k_cd_cols<32, 2>), dim3(cdiv(h->ds->p, 4)), dim3(128), 0, h->st.stream, a);
             h->col_solver = CS_CD_COLS32;
-        } else if (h->cd_variant != 1 && h->K <= 48) {
+        } else if (h->opt.cd_variant != 1 && h->ws.K <= 48) {
             // 32 < K <= 48 when the register-resident kernel's three-slot form does not apply (cd_variant = 2, or no l1 term): four genes
             // per wavefront with the whole Gram matrices in LDS (row16 kernel, three coordinate slots per lane).  Beyond 48 a CU's LDS
             // holds one such wave and the kernel below is faster; it also stays as cd_variant = 1 (cross-check)
             if (int rl = r16_wide_lds(r16_bytes)) return rl;
-            hipLaunchKernelGGL((k_cd_cols_r16<3>), dim3(cdiv(h->p, 4)), dim3(64), r16_bytes, h->stream, a);
+            hipLaunchKernelGGL((k_cd_cols_r16<3>), dim3(cdiv(h->ds->p, 4)), dim3(64), r16_bytes, h->st.stream, a);
             h->col_solver = CS_CD_R16_3;
         } else {
-            hipLaunchKernelGGL((k_cd_cols<64, 1>), dim3((unsigned)h->p), dim3(64), 0, h->stream, a);
+            hipLaunchKernelGGL((k_cd_cols<64, 1>), dim3((unsigned)h->ds->p), dim3(64), 0, h->st.stream, a);
             h->col_solver = CS_CD_COLS64;
         }
         KCHECK();
@@ -1047,14 +1113,14 @@ int launch_col_solve(insider_hip_handle *h, int masked, bool solve, double lambd
         eval_args.gene_perm = nullptr;
         eval_args.pass_count = nullptr;
         eval_args.resume = 0;
-        if (h->K <= 32) {
-            REG_DISPATCH(h->K, hipLaunchKernelGGL((k_cd_cols_reg<SL_, KM_, false>), dim3(cdiv(h->p, 4)), dim3(64), 0, h->stream, eval_args));
+        if (h->ws.K <= 32) {
+            REG_DISPATCH(h->ws.K, hipLaunchKernelGGL((k_cd_cols_reg<SL_, KM_, false>), dim3(cdiv(h->ds->p, 4)), dim3(64), 0, h->st.stream, eval_args));
             h->col_eval = CS_CD_REG;
         } else {   // three slots: the row16 kernel's evaluation part (the sweep kernel's registers are all taken)
-            const size_t eb = (size_t)r16_lds_doubles(h->K) * sizeof(double);
+            const size_t eb = (size_t)r16_lds_doubles(h->ws.K) * sizeof(double);
             if (int rl = r16_wide_lds(eb)) return rl;
             eval_args.mode = COL_EVAL;
-            hipLaunchKernelGGL((k_cd_cols_r16<3>), dim3(cdiv(h->p, 4)), dim3(64), eb, h->stream, eval_args);
+            hipLaunchKernelGGL((k_cd_cols_r16<3>), dim3(cdiv(h->ds->p, 4)), dim3(64), eb, h->st.stream, eval_args);
             h->col_eval = CS_CD_R16_3;
         }
         KCHECK();
@@ -1063,19 +1129,19 @@ int launch_col_solve(insider_hip_handle *h, int masked, bool solve, double lambd
         // schedule the next solve longest-first, genes of similar length sharing a wave.  (The bucket sort's order inside a
         // bucket is the order of the solve kernel's atomics: which genes share a wave — and so the timings — may differ from
         // run to run; no result depends on it.)
-        hipStream_t st = h->stream;
+        hipStream_t st = h->st.stream;
         if (side) {
-            HIPCHECK(hipEventRecord(h->ev_cd_done, h->stream));
-            HIPCHECK(hipStreamWaitEvent(h->side, h->ev_cd_done, 0));
-            st = h->side;
+            HIPCHECK(hipEventRecord(h->st.ev_cd_done, h->st.stream));
+            HIPCHECK(hipStreamWaitEvent(h->st.side, h->st.ev_cd_done, 0));
+            st = h->st.side;
         }
-        if ((rc = launch_gene_order(h, h->sweeps, (outer_iter < insider_hip_handle::EARLY || !h->have_perm) ? 1 : 0, 0, st, fused_bucket)))
+        if ((rc = launch_gene_order(h, h->ws.sweeps, (outer_iter < Workspace::EARLY || !h->ws.have_perm) ? 1 : 0, 0, st, fused_bucket)))
             return rc;
-        h->have_perm = true;
+        h->ws.have_perm = true;
         if (early) {
-            HIPCHECK(hipMemcpyAsync(h->perm_early[outer_iter], h->gene_perm, (size_t)h->p * sizeof(int),
+            HIPCHECK(hipMemcpyAsync(h->ws.perm_early[outer_iter], h->ws.gene_perm, (size_t)h->ds->p * sizeof(int),
                                     hipMemcpyDeviceToDevice, st));
-            h->have_early[outer_iter] = true;
+            h->ws.have_early[outer_iter] = true;
         }
         if (side) {   // the caller may add the next sweep-order table to the side stream, then closes it with side_close()
             h->side_pending = true;
@@ -1086,7 +1152,7 @@ int launch_col_solve(insider_hip_handle *h, int masked, bool solve, double lambd
 
 int side_close(insider_hip_handle *h)
 {
-    if (h->side_pending) HIPCHECK(hipEventRecord(h->ev_side_done, h->side));
+    if (h->side_pending) HIPCHECK(hipEventRecord(h->st.ev_side_done, h->st.side));
     return INSIDER_OK;
 }
 
@@ -1094,16 +1160,16 @@ int side_close(insider_hip_handle *h)
 int launch_test_sse(insider_hip_handle *h, int masked, bool timed)
 {
     if (!masked) {
-        HIPCHECK(hipMemsetAsync(h->sse_test, 0, (size_t)h->p * sizeof(double), h->stream));
+        HIPCHECK(hipMemsetAsync(h->ws.sse_test, 0, (size_t)h->ds->p * sizeof(double), h->st.stream));
         return INSIDER_OK;
     }
-    if (h->no_na) return INSIDER_OK;   // the column kernel derived the test residuals from the statistics
+    if (h->ds->no_na) return INSIDER_OK;   // the column kernel derived the test residuals from the statistics
     Timer t;
     int rc = t.begin(h, timed);
     if (rc) return rc;
-    hipLaunchKernelGGL((k_test_sse_list<4>), dim3(cdiv(h->p, 4)), dim3(256), 0, h->stream, (const uint32_t *)h->col_ptr,
-                       (const int *)h->col_idx, (const double *)h->col_val, (const uint8_t *)h->col_flag, (int)h->p,
-                       (const double *)h->R, (const double *)h->C, h->K, h->KP, h->sse_test);
+    hipLaunchKernelGGL((k_test_sse_list<4>), dim3(cdiv(h->ds->p, 4)), dim3(256), 0, h->st.stream, (const uint32_t *)h->ds->col_ptr,
+                       (const int *)h->ds->col_idx, (const double *)h->ds->col_val, (const uint8_t *)h->ds->col_flag, (int)h->ds->p,
+                       (const double *)h->ws.R, (const double *)h->ws.C, h->ws.K, h->ws.KP, h->ws.sse_test);
     KCHECK();
     return t.end(h, h->ev_test);
 }
@@ -1114,16 +1180,16 @@ int launch_test_sse(insider_hip_handle *h, int masked, bool timed)
 // c3: 0.55 vs 1.4 ms (model 0.45 vs 1.38); at c5 (4 covariates): 1.37 vs 0.85 ms (model 1.24 vs 0.84).
 bool use_merged(const insider_hip_handle *h, int masked)
 {
-    if (!(masked && h->merged && h->row_merged && (h->m == 0 || h->cont_merged))) return false;
-    if (h->row_merged == 2 || h->m > 0) return true;   // forced / continuous covariates: the per-sample pass is the slow alternative
-    const int NB = h->NB ? h->NB : 2;
+    if (!(masked && h->ds->merged && h->opt.row_merged && (h->ds->m == 0 || h->ds->cont_merged))) return false;
+    if (h->opt.row_merged == 2 || h->ds->m > 0) return true;   // forced / continuous covariates: the per-sample pass is the slow alternative
+    const int NB = h->ws.NB ? h->ws.NB : 2;
     const double mf = (NB * (NB + 1) / 2) * 16.0 / (1024.0 * 2100.0);   // us per rank-one group entry on the whole GPU
-    const double E = (double)h->row_entries, pscale = (double)h->p / 5.0e4;
-    const double old_us = E * mf * 1.15 + 50.0 * h->c;
+    const double E = (double)h->ds->row_entries, pscale = (double)h->ds->p / 5.0e4;
+    const double old_us = E * mf * 1.15 + 50.0 * h->ds->c;
     double merged_us = 0.0;
-    for (int i = 0; i < h->c; ++i)
-        merged_us += (double)h->cov[i].npairs * mf * 1.1 + E * (h->c - 1) * 1.3e-6 + 33.0 * pscale * h->SLcat / 110.0 / h->c +
-                     37.0 * pscale * h->cov[i].L / 100.0 + 40.0;
+    for (int i = 0; i < h->ds->c; ++i)
+        merged_us += (double)h->ds->cov[i].npairs * mf * 1.1 + E * (h->ds->c - 1) * 1.3e-6 + 33.0 * pscale * h->ds->SLcat / 110.0 / h->ds->c +
+                     37.0 * pscale * h->ds->cov[i].L / 100.0 + 40.0;
     return 1.1 * merged_us < old_us;
 }
 
@@ -1133,7 +1199,7 @@ bool use_merged(const insider_hip_handle *h, int masked)
 // What it buys is launch latency: on small data a long unmasked fit (the reference's fit() default) is a chain of ~5 us kernels.
 bool unmasked_fused(const insider_hip_handle *h, int masked)
 {
-    return !masked && h->merged && h->row_merged && h->row_fused && h->m == 0 && h->lvl_zero;
+    return !masked && h->ds->merged && h->opt.row_merged && h->opt.row_fused && h->ds->m == 0 && h->ws.lvl_zero;
 }
 
 // V = C A' for the stacked levels [q_begin, q_end) (all of them once per outer iteration, then the updated covariate's)
@@ -1142,13 +1208,13 @@ int launch_gene_v(insider_hip_handle *h, int q_begin, int q_end)
     // V[:, q_begin:q_end) = C A[q_begin:q_end, :]'  (A given "transposed": one row per output column)
     const int N = q_end - q_begin;
     if (N <= 0) return INSIDER_OK;
-    if (h->mm_fast && h->p >= MM_FAST_MIN) {   // A' staged in LDS once per block, C read in 16-byte pieces (k_mm_rows2)
-        const int tiles = cdiv((int)h->p, 16), tpw = mm_tiles_per_wave(h, tiles);
-        const size_t ldsb = (size_t)4 * cdiv(h->K, 16) * 64 * sizeof(double);
+    if (h->opt.mm_fast && h->ds->p >= MM_FAST_MIN) {   // A' staged in LDS once per block, C read in 16-byte pieces (k_mm_rows2)
+        const int tiles = cdiv((int)h->ds->p, 16), tpw = mm_tiles_per_wave(h, tiles);
+        const size_t ldsb = (size_t)4 * cdiv(h->ws.K, 16) * 64 * sizeof(double);
 #define GV2_LAUNCH(NT_)                                                                                                       \
-    hipLaunchKernelGGL((k_mm_rows2<NT_, true>), dim3(cdiv(cdiv(tiles, tpw), 4), cdiv(N, 16 * NT_)), dim3(256), ldsb * NT_, h->stream, \
-                       (const double *)h->C, (int64_t)h->KP, (int)h->p, h->K,                                                \
-                       (const double *)(h->Astack + (size_t)q_begin * h->KP), h->KP, N, h->Vlev + q_begin, (int64_t)h->SLP, N, tpw)
+    hipLaunchKernelGGL((k_mm_rows2<NT_, true>), dim3(cdiv(cdiv(tiles, tpw), 4), cdiv(N, 16 * NT_)), dim3(256), ldsb * NT_, h->st.stream, \
+                       (const double *)h->ws.C, (int64_t)h->ws.KP, (int)h->ds->p, h->ws.K,                                                \
+                       (const double *)(h->ws.Astack + (size_t)q_begin * h->ws.KP), h->ws.KP, N, h->ws.Vlev + q_begin, (int64_t)h->ds->SLP, N, tpw)
         if (N <= 16) GV2_LAUNCH(1);
         else if (N <= 32) GV2_LAUNCH(2);
         else GV2_LAUNCH(4);
@@ -1158,9 +1224,9 @@ int launch_gene_v(insider_hip_handle *h, int q_begin, int q_end)
         return INSIDER_OK;
     }
 #define GV_LAUNCH(NT_)                                                                                                        \
-    hipLaunchKernelGGL((k_mm_rows<NT_, true>), dim3(cdiv(cdiv((int)h->p, 16), 4), cdiv(N, 16 * NT_)), dim3(256), 0, h->stream, \
-                       (const double *)h->C, (int64_t)h->KP, (int)h->p, h->K,                                                \
-                       (const double *)(h->Astack + (size_t)q_begin * h->KP), h->KP, N, h->Vlev + q_begin, (int64_t)h->SLP, N)
+    hipLaunchKernelGGL((k_mm_rows<NT_, true>), dim3(cdiv(cdiv((int)h->ds->p, 16), 4), cdiv(N, 16 * NT_)), dim3(256), 0, h->st.stream, \
+                       (const double *)h->ws.C, (int64_t)h->ws.KP, (int)h->ds->p, h->ws.K,                                                \
+                       (const double *)(h->ws.Astack + (size_t)q_begin * h->ws.KP), h->ws.KP, N, h->ws.Vlev + q_begin, (int64_t)h->ds->SLP, N)
     if (N <= 16) GV_LAUNCH(1);        // (a covariate with few levels: one 16-column tile, not four)
     else if (N <= 32) GV_LAUNCH(2);
     else GV_LAUNCH(4);
@@ -1175,18 +1241,18 @@ int launch_row_stats(insider_hip_handle *h, bool timed)
     Timer t;
     int rc = t.begin(h, timed);
     if (rc) return rc;
-    rc = launch_list_stats(h, false, h->nseg, h->C, h->stat, nullptr, &h->row_kernels);
+    rc = launch_list_stats(h, false, h->ws.nseg, h->ws.C, h->ws.stat, nullptr, &h->row_kernels);
     if (rc) return rc;
     return t.end(h, h->ev_row);
 }
 
 int do_allreduce(insider_hip_handle *h, double *buf, int64_t count)
 {
-    if (h->world <= 1 && !h->force_allreduce) return INSIDER_OK;
+    if (h->world <= 1 && !h->opt.force_allreduce) return INSIDER_OK;
     if (h->comm) {
         // in-library RCCL: the collective is enqueued on the library's own stream, between the kernels that produce
         // and consume `buf`; no host synchronisation, no callback into the host language
-        const ncclResult_t r = ncclAllReduce(buf, buf, (size_t)count, ncclDouble, ncclSum, h->comm, h->stream);
+        const ncclResult_t r = ncclAllReduce(buf, buf, (size_t)count, ncclDouble, ncclSum, h->comm, h->st.stream);
         if (r != ncclSuccess) return fail(INSIDER_ERR_COMM, std::string("ncclAllReduce: ") + ncclGetErrorString(r));
         return INSIDER_OK;
     }
@@ -1194,8 +1260,8 @@ int do_allreduce(insider_hip_handle *h, double *buf, int64_t count)
         if (h->world > 1) return fail(INSIDER_ERR_COMM, "world > 1 needs insider_hip_comm_init() or an all-reduce callback");
         return INSIDER_OK;
     }
-    // stream-ordered: the callback enqueues the collective against h->stream (see include/insider_hip.h)
-    if (h->allreduce(h->allreduce_user, buf, count, (void *)h->stream) != 0)
+    // stream-ordered: the callback enqueues the collective against h->st.stream (see include/insider_hip.h)
+    if (h->allreduce(h->allreduce_user, buf, count, (void *)h->st.stream) != 0)
         return fail(INSIDER_ERR_COMM, "all-reduce callback failed");
     return INSIDER_OK;
 }
@@ -1203,15 +1269,16 @@ int do_allreduce(insider_hip_handle *h, double *buf, int64_t count)
 // level records' Gram part of covariate i: sum_j n_jl c_j c_j' for every level -> rec[l][0 .. STAT)
 int launch_level_gram(insider_hip_handle *h, int i, hipStream_t st, double *rec, const CovTables *cont_ct = nullptr)
 {
-    const CovTables &ct = cont_ct ? *cont_ct : h->cov[i];
-    const WgPlan w = cont_ct ? WgPlan() : wgemm_plan(h, i, h->K);
+    const CovTables &ct = cont_ct ? *cont_ct : h->ds->cov[i];
+    const CovTables &lists = cont_ct ? h->ds->contm_lists : ct;   // (the continuous columns' lists and work items: one copy)
+    const WgPlan w = cont_ct ? WgPlan() : wgemm_plan(h, i, h->ws.K);
     if (w.use) {
-        const int stat_len = h->NB * (h->NB + 1) / 2 * 256, plen = stat_len + 2 * h->KP + 2;
-        const float *hn = h->cf_hn + h->cf.hn_off[h->cf_pos[i]];
+        const int stat_len = h->ws.NB * (h->ws.NB + 1) / 2 * 256, plen = stat_len + 2 * h->ws.KP + 2;
+        const float *hn = h->ds->cf_hn + h->ds->cf.hn_off[h->ds->cf_pos[i]];
         const dim3 grid(cdiv(cdiv(w.ntile, 2) * w.nslab, 4), 1, w.zch);   // (slab, pair-tile pair) items, four waves per block
 #define WG_LAUNCH(LT_)                                                                                                     \
-    hipLaunchKernelGGL((k_wgemm<LT_>), grid, dim3(256), 0, st, hn, h->cf.hn_stride, w.tiles, (const double *)h->C, h->KP,   \
-                       (int)h->p, w.slab, w.nslab, (const uint8_t *)h->wg_pair, w.ntile, h->wg_part)
+    hipLaunchKernelGGL((k_wgemm<LT_>), grid, dim3(256), 0, st, hn, h->ds->cf.hn_stride, w.tiles, (const double *)h->ws.C, h->ws.KP,   \
+                       (int)h->ds->p, w.slab, w.nslab, (const uint8_t *)h->ws.wg_pair, w.ntile, h->ws.wg_part)
         switch (w.LT) {
             case 4: WG_LAUNCH(4); row_mark(h, RK_WGEMM4); break;
             case 5: WG_LAUNCH(5); row_mark(h, RK_WGEMM5); break;
@@ -1221,21 +1288,21 @@ int launch_level_gram(insider_hip_handle *h, int i, hipStream_t st, double *rec,
 #undef WG_LAUNCH
         if (w.zch > 1) row_mark(h, RK_WGEMM_CHUNKS);
         KCHECK();
-        hipLaunchKernelGGL(k_wgemm_sum, dim3(cdiv(stat_len, 256), ct.L), dim3(256), 0, st, (const double *)h->wg_part, w.nslab,
-                           w.tiles, w.ntile, h->K, stat_len, rec, plen);
+        hipLaunchKernelGGL(k_wgemm_sum, dim3(cdiv(stat_len, 256), ct.L), dim3(256), 0, st, (const double *)h->ws.wg_part, w.nslab,
+                           w.tiles, w.ntile, h->ws.K, stat_len, rec, plen);
         KCHECK();
         return INSIDER_OK;
     }
-    NB_DISPATCH(h->NB, {
+    NB_DISPATCH(h->ws.NB, {
         constexpr int STAT_ = Geo<NB_>::STAT, PLEN = STAT_ + 2 * Geo<NB_>::KP + 2;
         if (ct.nitems > 0) {   // no held-out entry at all: every level sum is zero
             hipLaunchKernelGGL((k_wsyrk<NB_, WPB_>), dim3(cdiv(ct.nitems, WPB_)), dim3(WPB_ * 64), 0, st,
-                               (const uint32_t *)ct.item_begin, (const uint32_t *)ct.item_end, ct.nitems,
-                               (const int *)ct.wl_idx, (const double *)ct.wl_w, (const double *)h->C, (int64_t)h->p, h->wpart);
+                               (const uint32_t *)lists.item_begin, (const uint32_t *)lists.item_end, ct.nitems,
+                               (const int *)lists.wl_idx, (const double *)ct.wl_w, (const double *)h->ws.C, (int64_t)h->ds->p, h->ws.wpart);
             row_mark(h, RK_WSYRK);
         }
-        hipLaunchKernelGGL(k_level_sum, dim3(cdiv(STAT_, 16), ct.L), dim3(256), 0, st, (const double *)h->wpart,
-                           (const int *)ct.lvl_item_ptr, STAT_, rec, PLEN);
+        hipLaunchKernelGGL(k_level_sum, dim3(cdiv(STAT_, 16), ct.L), dim3(256), 0, st, (const double *)h->ws.wpart,
+                           (const int *)lists.lvl_item_ptr, STAT_, rec, PLEN);
     });
     KCHECK();
     return INSIDER_OK;
@@ -1245,8 +1312,8 @@ int launch_level_gram(insider_hip_handle *h, int i, hipStream_t st, double *rec,
 // second side stream, from the point where C is final; row_update() waits for its covariate's event
 int launch_wsyrk_side(insider_hip_handle *h)
 {
-    HIPCHECK(hipEventRecord(h->ev_c_ready, h->stream));
-    HIPCHECK(hipStreamWaitEvent(h->side2, h->ev_c_ready, 0));
+    HIPCHECK(hipEventRecord(h->st.ev_c_ready, h->st.stream));
+    HIPCHECK(hipStreamWaitEvent(h->st.side2, h->st.ev_c_ready, 0));
     // The weighted SYRK of the first covariate is the longest kernel of the row phase (MFMA-bound on its (level, gene)
     // pairs) and the first thing the main chain waits for: it starts at once.  C'C and (S^train C') (launch_row_prep) run on
     // a third stream: they are first read by k_level_reduce, which waits for ev_prep.
@@ -1255,21 +1322,21 @@ int launch_wsyrk_side(insider_hip_handle *h)
     // them and it takes 220 us instead of 140 — 590 against 460 us for the phase, the mode chosen by how the queues happen to
     // wake up after the solve.  So k_gene_u waits for this event, recorded on the GEMM's stream directly in front of it: its
     // queue goes on to dispatch the GEMM at once, the main stream's wake-up comes a few microseconds later (and behind V).
-    HIPCHECK(hipEventRecord(h->ev_head, h->side2));
-    HIPCHECK(hipStreamWaitEvent(h->side3, h->ev_c_ready, 0));
-    if (int rp = launch_gram(h, h->C, h->p, h->CCt, h->side3, h->gram_part2)) return rp;
-    if (int rp = launch_mm_reduce_kp(h, h->Strain, h->SLP, h->C, (int)h->p, h->SL, h->sc_part2, h->SC, h->side3)) return rp;
-    HIPCHECK(hipEventRecord(h->ev_prep, h->side3));
+    HIPCHECK(hipEventRecord(h->st.ev_head, h->st.side2));
+    HIPCHECK(hipStreamWaitEvent(h->st.side3, h->st.ev_c_ready, 0));
+    if (int rp = launch_gram(h, h->ws.C, h->ds->p, h->ws.CCt, h->st.side3, h->ws.gram_part2)) return rp;
+    if (int rp = launch_mm_reduce_kp(h, h->ds->Strain, h->ds->SLP, h->ws.C, (int)h->ds->p, h->ds->SL, h->ws.sc_part2, h->ws.SC, h->st.side3)) return rp;
+    HIPCHECK(hipEventRecord(h->st.ev_prep, h->st.side3));
     row_mark(h, RK_GRAM_SIDE);
-    for (int i = 0; i < h->c; ++i) {
-        const int plen = h->NB * (h->NB + 1) / 2 * 256 + 2 * h->KP + 2;
-        if (int rg = launch_level_gram(h, i, h->side2, h->lvl_sum_all + (size_t)h->lvl_off[i] * plen)) return rg;
-        HIPCHECK(hipEventRecord(h->ev_w[i], h->side2));
+    for (int i = 0; i < h->ds->c; ++i) {
+        const int plen = h->ws.NB * (h->ws.NB + 1) / 2 * 256 + 2 * h->ws.KP + 2;
+        if (int rg = launch_level_gram(h, i, h->st.side2, h->ws.lvl_sum_all + (size_t)h->ds->lvl_off[i] * plen)) return rg;
+        HIPCHECK(hipEventRecord(h->st.ev_w[i], h->st.side2));
     }
-    for (int k = 0; k < (h->cont_merged ? h->m : 0); ++k) {   // continuous columns: one-level covariates with real-valued weights
-        const int plen = h->NB * (h->NB + 1) / 2 * 256 + 2 * h->KP + 2;
-        if (int rg = launch_level_gram(h, 0, h->side2, h->lvl_sum_all + (size_t)(h->SLcat + k) * plen, &h->contm[k])) return rg;
-        HIPCHECK(hipEventRecord(h->ev_w[h->c + k], h->side2));
+    for (int k = 0; k < (h->ds->cont_merged ? h->ds->m : 0); ++k) {   // continuous columns: one-level covariates with real-valued weights
+        const int plen = h->ws.NB * (h->ws.NB + 1) / 2 * 256 + 2 * h->ws.KP + 2;
+        if (int rg = launch_level_gram(h, 0, h->st.side2, h->ws.lvl_sum_all + (size_t)(h->ds->SLcat + k) * plen, &h->ds->contm[k])) return rg;
+        HIPCHECK(hipEventRecord(h->st.ev_w[h->ds->c + k], h->st.side2));
     }
     h->w_ready = true;
     return INSIDER_OK;
@@ -1281,163 +1348,163 @@ int row_update(insider_hip_handle *h, int i, int cont_col, int masked, double la
 {
     const bool cont = cont_col >= 0;
     bool fused_solve = false;
-    const CovTables &ct = cont ? h->cont : h->cov[i];
-    const int row0 = cont ? h->SLcat + cont_col : h->lvl_off[i];   // first row of this covariate in Astack / SC
+    const CovTables &ct = cont ? h->ds->cont : h->ds->cov[i];
+    const int row0 = cont ? h->ds->SLcat + cont_col : h->ds->lvl_off[i];   // first row of this covariate in Astack / SC
     LevelArgs la;
-    la.stat = h->stat;
-    la.nseg = h->nseg;
-    la.n = (int)h->n;
-    la.K = h->K;
+    la.stat = h->ws.stat;
+    la.nseg = h->ws.nseg;
+    la.n = (int)h->ds->n;
+    la.K = h->ws.K;
     la.masked = masked;
-    la.R = h->R;
-    la.lev = h->lev;
-    la.lvl_off = h->lvl_off_d;
+    la.R = h->ws.R;
+    la.lev = h->ds->lev;
+    la.lvl_off = h->ds->lvl_off_d;
     la.cov = cont ? -1 : i;
     la.own_row = row0;
-    la.weights = cont ? h->Zc + (size_t)cont_col * h->n : nullptr;
+    la.weights = cont ? h->ds->Zc + (size_t)cont_col * h->ds->n : nullptr;
     la.chunk_begin = ct.chunk_begin;
     la.chunk_end = ct.chunk_end;
-    la.members = cont ? h->ident_members : h->members_all + (size_t)i * h->n;
+    la.members = cont ? h->ds->ident_members : h->ds->members_all + (size_t)i * h->ds->n;
     la.nchunks = ct.nchunks;
-    la.Astack = h->Astack;
-    la.part = h->lvl_part;
+    la.Astack = h->ws.Astack;
+    la.part = h->ws.lvl_part;
     LevelReduceArgs ra;
-    ra.part = h->lvl_sum;
+    ra.part = h->ws.lvl_sum;
     ra.L = ct.L;
-    ra.K = h->K;
-    ra.CCt = h->CCt;
-    ra.SC = h->SC;
+    ra.K = h->ws.K;
+    ra.CCt = h->ws.CCt;
+    ra.SC = h->ws.SC;
     ra.sc_off = row0;
-    ra.eq = h->eq;
+    ra.eq = h->ws.eq;
     if (cont && use_merged(h, masked)) {
         // merged update of continuous column cont_col (optimize_continuous_v2, src/optimize.cpp:76-137): the one-level covariate
         // with real-valued membership weights z_r — u_j from the real-valued count table, Y = U'C, the level record's Gram sum
         // from the (gene, sum z^2) list, sum_r z_r s_r from the real-valued pair counts; then the reference's cyclic scalar
         // passes on (H, b) (k_cont_cd) as on the per-sample path
-        const int KP = h->KP;
-        const CovTables &cm = h->contm[cont_col];
-        ColFacArgs ca = h->cf;
-        ca.zt = h->cf_zt;
-        hipLaunchKernelGGL((k_gene_uc<4>), dim3(cdiv(h->p, 4)), dim3(256), 0, h->stream, ca, cont_col, (const double *)h->Vlev, h->SLP,
-                           h->U);
+        const int KP = h->ws.KP;
+        const CovTables &cm = h->ds->contm[cont_col];
+        ColFacArgs ca = h->ds->cf;
+        ca.zt = h->ds->cf_zt;
+        hipLaunchKernelGGL((k_gene_uc<4>), dim3(cdiv(h->ds->p, 4)), dim3(256), 0, h->st.stream, ca, cont_col, (const double *)h->ws.Vlev, h->ds->SLP,
+                           h->ws.U);
         KCHECK();
         row_mark(h, RK_GENE_UC);
         int ypart_n = 0;
-        if (int rcy = launch_mm_reduce_kp(h, h->U, 2, h->C, (int)h->p, 1, h->sc_part, nullptr, nullptr, &ypart_n, &h->row_kernels))
+        if (int rcy = launch_mm_reduce_kp(h, h->ws.U, 2, h->ws.C, (int)h->ds->p, 1, h->ws.sc_part, nullptr, nullptr, &ypart_n, &h->row_kernels))
             return rcy;
         if (h->w_ready) {
-            HIPCHECK(hipStreamWaitEvent(h->stream, h->ev_w[h->c + cont_col], 0));
-            HIPCHECK(hipStreamWaitEvent(h->stream, h->ev_prep, 0));
+            HIPCHECK(hipStreamWaitEvent(h->st.stream, h->st.ev_w[h->ds->c + cont_col], 0));
+            HIPCHECK(hipStreamWaitEvent(h->st.stream, h->st.ev_prep, 0));
         }
-        NB_DISPATCH(h->NB, {
+        NB_DISPATCH(h->ws.NB, {
             (void)WPB_;
             constexpr int STAT_ = Geo<NB_>::STAT, PLEN = STAT_ + 2 * Geo<NB_>::KP + 2;
-            double *rec = h->w_ready ? h->lvl_sum_all + (size_t)row0 * PLEN : h->lvl_sum;
+            double *rec = h->w_ready ? h->ws.lvl_sum_all + (size_t)row0 * PLEN : h->ws.lvl_sum;
             if (!h->w_ready)
-                if (int rg = launch_level_gram(h, 0, h->stream, rec, &cm)) return rg;
-            hipLaunchKernelGGL((k_level_merged<NB_>), dim3(1), dim3(256), 0, h->stream, (const double *)rec, (const double *)h->sc_part,
-                               ypart_n, (const double *)cm.paircnt, h->SL, (const double *)h->Astack, (const int *)h->one_count,
-                               (const double *)h->CCt, (const double *)(h->SC + (size_t)row0 * KP), 1, h->K, lambda1, 0, h->eq,
-                               h->Astack + (size_t)row0 * KP, h->failflag, (const double *)(h->cont_cnt + cont_col));
+                if (int rg = launch_level_gram(h, 0, h->st.stream, rec, &cm)) return rg;
+            hipLaunchKernelGGL((k_level_merged<NB_>), dim3(1), dim3(256), 0, h->st.stream, (const double *)rec, (const double *)h->ws.sc_part,
+                               ypart_n, (const double *)cm.paircnt, h->ds->SL, (const double *)h->ws.Astack, (const int *)h->ds->one_count,
+                               (const double *)h->ws.CCt, (const double *)(h->ws.SC + (size_t)row0 * KP), 1, h->ws.K, lambda1, 0, h->ws.eq,
+                               h->ws.Astack + (size_t)row0 * KP, h->ws.failflag, (const double *)(h->ds->cont_cnt + cont_col));
         });
         row_mark(h, RK_MERGED);
     } else if (!cont && use_merged(h, masked)) {
         // merged update: one weighted rank-one term per (level, gene) pair, one look-up per held-out entry
-        const int L = ct.L, LP = (int)round_up(L, 2), KP = h->KP;
-        const size_t gu_lds = (size_t)4 * (h->SL + LP + GU_BATCH * WAVE) * sizeof(double);
-        if (h->cf_pair_ok && (h->row_counts || h->m > 0) && h->c <= CF_MAXC && gu_lds <= 64 * 1024) {   // u from the dense pair counts (insider_col_factored.hpp)
-            ColFacArgs ca = h->cf;
-            ca.cnt = h->cf_cnt;
-            ca.zt = h->m > 0 ? h->cf_zt : nullptr;   // (+ the continuous covariates' term from the real-valued counts)
-            hipLaunchKernelGGL((k_gene_u_cnt<4>), dim3(cdiv(h->p, 4)), dim3(256), gu_lds, h->stream, ca, h->cf_pos[i], LP,
-                               (const double *)h->Vlev, h->SLP, h->SL, h->U);
+        const int L = ct.L, LP = (int)round_up(L, 2), KP = h->ws.KP;
+        const size_t gu_lds = (size_t)4 * (h->ds->SL + LP + GU_BATCH * WAVE) * sizeof(double);
+        if (h->ds->cf_pair_ok && (h->opt.row_counts || h->ds->m > 0) && h->ds->c <= CF_MAXC && gu_lds <= 64 * 1024) {   // u from the dense pair counts (insider_col_factored.hpp)
+            ColFacArgs ca = h->ds->cf;
+            ca.cnt = h->ds->cf_cnt;
+            ca.zt = h->ds->m > 0 ? h->ds->cf_zt : nullptr;   // (+ the continuous covariates' term from the real-valued counts)
+            hipLaunchKernelGGL((k_gene_u_cnt<4>), dim3(cdiv(h->ds->p, 4)), dim3(256), gu_lds, h->st.stream, ca, h->ds->cf_pos[i], LP,
+                               (const double *)h->ws.Vlev, h->ds->SLP, h->ds->SL, h->ws.U);
             row_mark(h, RK_GENE_U_CNT);
         } else {
             // (k_gene_u knows nothing of the continuous covariates' term: insider_hip_create_ex leaves cont_merged off when a
             // covariate's k_gene_u_cnt record does not fit, so this branch is never reached with m > 0)
-            if (h->m > 0) return fail(INSIDER_ERR_UNSUPPORTED, "merged row update with continuous covariates needs the pair-count form");
-            hipLaunchKernelGGL((k_gene_u<4>), dim3(cdiv(h->p, 4)), dim3(256), (size_t)4 * (h->SLcat + GU_TILE) * sizeof(double),
-                               h->stream, (const uint32_t *)ct.grp, (const uint16_t *)ct.slev,
-                               (size_t)h->col_entries + LIST_BLOCK, h->c - 1, L, LP, (const double *)h->Vlev, h->SLP, (int)h->p,
-                               h->SLcat, h->U);
+            if (h->ds->m > 0) return fail(INSIDER_ERR_UNSUPPORTED, "merged row update with continuous covariates needs the pair-count form");
+            hipLaunchKernelGGL((k_gene_u<4>), dim3(cdiv(h->ds->p, 4)), dim3(256), (size_t)4 * (h->ds->SLcat + GU_TILE) * sizeof(double),
+                               h->st.stream, (const uint32_t *)ct.grp, (const uint16_t *)ct.slev,
+                               (size_t)h->ds->col_entries + LIST_BLOCK, h->ds->c - 1, L, LP, (const double *)h->ws.Vlev, h->ds->SLP, (int)h->ds->p,
+                               h->ds->SLcat, h->ws.U);
             row_mark(h, RK_GENE_U);
         }
         KCHECK();
         // Y = U'C, the same reduction over genes as (S C'); with the fused level kernel its per-slab partial sums are added up
         // there (k_sum_partials' order), which takes one launch per covariate off the main chain
         int ypart_n = 0;
-        if (int rcy = launch_mm_reduce_kp(h, h->U, LP, h->C, (int)h->p, L, h->sc_part, h->row_fused ? nullptr : h->Ylvl, nullptr,
+        if (int rcy = launch_mm_reduce_kp(h, h->ws.U, LP, h->ws.C, (int)h->ds->p, L, h->ws.sc_part, h->opt.row_fused ? nullptr : h->ws.Ylvl, nullptr,
                                           &ypart_n, &h->row_kernels))
             return rcy;
-        if (!h->row_fused) ypart_n = 0;
+        if (!h->opt.row_fused) ypart_n = 0;
         if (h->w_ready) {   // wsyrk + level sums came from side2, C'C and (S^train C') from side3
-            HIPCHECK(hipStreamWaitEvent(h->stream, h->ev_w[i], 0));
-            HIPCHECK(hipStreamWaitEvent(h->stream, h->ev_prep, 0));
+            HIPCHECK(hipStreamWaitEvent(h->st.stream, h->st.ev_w[i], 0));
+            HIPCHECK(hipStreamWaitEvent(h->st.stream, h->st.ev_prep, 0));
         }
         if (!h->w_ready)
-            if (int rg = launch_level_gram(h, i, h->stream, h->lvl_sum)) return rg;
-        NB_DISPATCH(h->NB, {
+            if (int rg = launch_level_gram(h, i, h->st.stream, h->ws.lvl_sum)) return rg;
+        NB_DISPATCH(h->ws.NB, {
             constexpr int STAT_ = Geo<NB_>::STAT, PLEN = STAT_ + 2 * Geo<NB_>::KP + 2;
-            double *rec = h->w_ready ? h->lvl_sum_all + (size_t)h->lvl_off[i] * PLEN : h->lvl_sum;
+            double *rec = h->w_ready ? h->ws.lvl_sum_all + (size_t)h->ds->lvl_off[i] * PLEN : h->ws.lvl_sum;
             // the level records' tail, the level equations and (unless the equations still have to cross ranks) the solves: one launch
-            fused_solve = h->world <= 1 && !h->force_allreduce && h->row_fused && NB_ <= 2;
-            if (h->row_fused) {
-                hipLaunchKernelGGL((k_level_merged<NB_>), dim3(L), dim3(256), 0, h->stream, (const double *)rec,
-                                   (const double *)(ypart_n ? h->sc_part : h->Ylvl), ypart_n, (const double *)ct.paircnt, h->SL, (const double *)h->Astack,
-                                   (const int *)(h->lvl_count_all + h->lvl_off[i]), (const double *)h->CCt,
-                                   (const double *)(h->SC + (size_t)row0 * KP), L, h->K, lambda1, fused_solve ? 1 : 0, h->eq,
-                                   h->Astack + (size_t)row0 * KP, h->failflag);
+            fused_solve = h->world <= 1 && !h->opt.force_allreduce && h->opt.row_fused && NB_ <= 2;
+            if (h->opt.row_fused) {
+                hipLaunchKernelGGL((k_level_merged<NB_>), dim3(L), dim3(256), 0, h->st.stream, (const double *)rec,
+                                   (const double *)(ypart_n ? h->ws.sc_part : h->ws.Ylvl), ypart_n, (const double *)ct.paircnt, h->ds->SL, (const double *)h->ws.Astack,
+                                   (const int *)(h->ds->lvl_count_all + h->ds->lvl_off[i]), (const double *)h->ws.CCt,
+                                   (const double *)(h->ws.SC + (size_t)row0 * KP), L, h->ws.K, lambda1, fused_solve ? 1 : 0, h->ws.eq,
+                                   h->ws.Astack + (size_t)row0 * KP, h->ws.failflag);
                 row_mark(h, fused_solve ? RK_MERGED_SOLVE : RK_MERGED);
             } else {
-                hipLaunchKernelGGL(k_level_pack, dim3(L), dim3(256), 0, h->stream, (const double *)h->Ylvl,
-                                   (const double *)ct.paircnt, h->SL, (const double *)h->Astack,
-                                   (const int *)(h->lvl_count_all + h->lvl_off[i]), L, h->K, KP, STAT_, rec);
+                hipLaunchKernelGGL(k_level_pack, dim3(L), dim3(256), 0, h->st.stream, (const double *)h->ws.Ylvl,
+                                   (const double *)ct.paircnt, h->ds->SL, (const double *)h->ws.Astack,
+                                   (const int *)(h->ds->lvl_count_all + h->ds->lvl_off[i]), L, h->ws.K, KP, STAT_, rec);
                 ra.part = rec;
-                hipLaunchKernelGGL((k_level_reduce<NB_>), dim3(L), dim3(64), 0, h->stream, ra);
+                hipLaunchKernelGGL((k_level_reduce<NB_>), dim3(L), dim3(64), 0, h->st.stream, ra);
                 row_mark(h, RK_PACK_REDUCE);
             }
         });
     } else if (!cont && unmasked_fused(h, masked)) {
-        const int L = ct.L, KP = h->KP;
-        NB_DISPATCH(h->NB, {
+        const int L = ct.L, KP = h->ws.KP;
+        NB_DISPATCH(h->ws.NB, {
             (void)WPB_;
-            fused_solve = h->world <= 1 && !h->force_allreduce && NB_ <= 2;
-            hipLaunchKernelGGL((k_level_merged<NB_>), dim3(L), dim3(256), 0, h->stream, (const double *)h->lvl_zero,
-                               (const double *)h->lvl_zero, 0, (const double *)ct.paircnt, h->SL, (const double *)h->Astack,
-                               (const int *)(h->lvl_count_all + h->lvl_off[i]), (const double *)h->CCt,
-                               (const double *)(h->SC + (size_t)row0 * KP), L, h->K, lambda1, fused_solve ? 1 : 0, h->eq,
-                               h->Astack + (size_t)row0 * KP, h->failflag);
+            fused_solve = h->world <= 1 && !h->opt.force_allreduce && NB_ <= 2;
+            hipLaunchKernelGGL((k_level_merged<NB_>), dim3(L), dim3(256), 0, h->st.stream, (const double *)h->ws.lvl_zero,
+                               (const double *)h->ws.lvl_zero, 0, (const double *)ct.paircnt, h->ds->SL, (const double *)h->ws.Astack,
+                               (const int *)(h->ds->lvl_count_all + h->ds->lvl_off[i]), (const double *)h->ws.CCt,
+                               (const double *)(h->ws.SC + (size_t)row0 * KP), L, h->ws.K, lambda1, fused_solve ? 1 : 0, h->ws.eq,
+                               h->ws.Astack + (size_t)row0 * KP, h->ws.failflag);
         });
         row_mark(h, fused_solve ? RK_MERGED_SOLVE : RK_MERGED);
         row_mark(h, RK_MERGED_ZERO);
     } else {
-        NB_DISPATCH(h->NB, {
+        NB_DISPATCH(h->ws.NB, {
             (void)WPB_;
             constexpr int PLEN = Geo<NB_>::STAT + 2 * Geo<NB_>::KP + 2;
-            hipLaunchKernelGGL((k_level_partial<NB_>), dim3(ct.nchunks), dim3(64), 0, h->stream, la);
-            hipLaunchKernelGGL(k_level_sum, dim3(cdiv(PLEN, 16), ct.L), dim3(256), 0, h->stream,
-                               (const double *)h->lvl_part, (const int *)ct.lvl_chunk_ptr, PLEN, h->lvl_sum, PLEN);
-            hipLaunchKernelGGL((k_level_reduce<NB_>), dim3(ct.L), dim3(64), 0, h->stream, ra);
+            hipLaunchKernelGGL((k_level_partial<NB_>), dim3(ct.nchunks), dim3(64), 0, h->st.stream, la);
+            hipLaunchKernelGGL(k_level_sum, dim3(cdiv(PLEN, 16), ct.L), dim3(256), 0, h->st.stream,
+                               (const double *)h->ws.lvl_part, (const int *)ct.lvl_chunk_ptr, PLEN, h->ws.lvl_sum, PLEN);
+            hipLaunchKernelGGL((k_level_reduce<NB_>), dim3(ct.L), dim3(64), 0, h->st.stream, ra);
         });
         row_mark(h, RK_LEVEL_PARTIAL);
     }
     KCHECK();
     if (fused_solve) return rebuild_R ? launch_build_R(h) : INSIDER_OK;
-    int rc = do_allreduce(h, h->eq, (int64_t)ct.L * (h->KP * h->KP + h->KP));
+    int rc = do_allreduce(h, h->ws.eq, (int64_t)ct.L * (h->ws.KP * h->ws.KP + h->ws.KP));
     if (rc) return rc;
     if (cont && masked) {
-        NB_DISPATCH(h->NB, {
+        NB_DISPATCH(h->ws.NB, {
             (void)WPB_;
-            hipLaunchKernelGGL((k_cont_cd<NB_>), dim3(1), dim3(64), 0, h->stream, (const double *)h->eq, h->K, lambda1,
-                               h->Astack + (size_t)row0 * h->KP);
+            hipLaunchKernelGGL((k_cont_cd<NB_>), dim3(1), dim3(64), 0, h->st.stream, (const double *)h->ws.eq, h->ws.K, lambda1,
+                               h->ws.Astack + (size_t)row0 * h->ws.KP);
         });
         row_mark(h, RK_CONT_CD);
     } else {
-        NB_DISPATCH(h->NB, {
+        NB_DISPATCH(h->ws.NB, {
             (void)WPB_;
-            hipLaunchKernelGGL((k_level_solve<NB_>), dim3(ct.L), dim3(64), 0, h->stream, (const double *)h->eq,
-                               (const int *)(cont ? h->one_count : h->lvl_count_all + h->lvl_off[i]), ct.L, h->K, lambda1,
-                               h->Astack + (size_t)row0 * h->KP, h->failflag);
+            hipLaunchKernelGGL((k_level_solve<NB_>), dim3(ct.L), dim3(64), 0, h->st.stream, (const double *)h->ws.eq,
+                               (const int *)(cont ? h->ds->one_count : h->ds->lvl_count_all + h->ds->lvl_off[i]), ct.L, h->ws.K, lambda1,
+                               h->ws.Astack + (size_t)row0 * h->ws.KP, h->ws.failflag);
         });
         row_mark(h, RK_LEVEL_SOLVE);
     }
@@ -1454,17 +1521,17 @@ struct LossOut {
 // evaluate() + compute_loss() (src/utils.cpp:56-102) from the per-gene statistics of the last column pass
 int loss_checkpoint(insider_hip_handle *h, int tuning, double lambda1, double lambda2, double alpha, LossOut *o)
 {
-    hipLaunchKernelGGL(k_loss_reduce, dim3(1), dim3(256), 0, h->stream, h->sse_train, h->sse_test, h->b2, h->b1,
-                       (int)h->p, h->Astack, h->SL, h->K, h->KP, h->loss_buf);
+    hipLaunchKernelGGL(k_loss_reduce, dim3(1), dim3(256), 0, h->st.stream, h->ws.sse_train, h->ws.sse_test, h->ws.b2, h->ws.b1,
+                       (int)h->ds->p, h->ws.Astack, h->ds->SL, h->ws.K, h->ws.KP, h->ws.loss_buf);
     KCHECK();
     // layout: [0]=sse_train [1]=sse_test [2]=sum c^2 [3]=sum |c| [4]=cnt_train [5]=cnt_test | [6]=sum a^2 (replicated)
-    double cnt[2] = {tuning == 1 ? h->cnt_train : (double)h->n * (double)h->p, h->cnt_test};
-    HIPCHECK(hipMemcpyAsync(h->loss_buf + 4, cnt, 2 * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    int rc = do_allreduce(h, h->loss_buf, 6);
+    double cnt[2] = {tuning == 1 ? h->ds->cnt_train : (double)h->ds->n * (double)h->ds->p, h->ds->cnt_test};
+    HIPCHECK(hipMemcpyAsync(h->ws.loss_buf + 4, cnt, 2 * sizeof(double), hipMemcpyHostToDevice, h->st.stream));
+    int rc = do_allreduce(h, h->ws.loss_buf, 6);
     if (rc) return rc;
     double v[8];
-    HIPCHECK(hipMemcpyAsync(v, h->loss_buf, 8 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHECK(hipStreamSynchronize(h->stream));
+    HIPCHECK(hipMemcpyAsync(v, h->ws.loss_buf, 8 * sizeof(double), hipMemcpyDeviceToHost, h->st.stream));
+    HIPCHECK(hipStreamSynchronize(h->st.stream));
     o->sum_residual = v[0];
     o->train_rmse = std::sqrt(v[0] / v[4]);                                                   // :63,66
     o->test_rmse = (tuning == 1 && v[5] > 0) ? std::sqrt(v[1] / v[5]) : std::numeric_limits<double>::quiet_NaN();
@@ -1479,10 +1546,10 @@ int loss_checkpoint(insider_hip_handle *h, int tuning, double lambda1, double la
 int check_fail_flag(insider_hip_handle *h)
 {
     int f = 0;
-    HIPCHECK(hipMemcpyAsync(&f, h->failflag, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    HIPCHECK(hipStreamSynchronize(h->stream));
+    HIPCHECK(hipMemcpyAsync(&f, h->ws.failflag, sizeof(int), hipMemcpyDeviceToHost, h->st.stream));
+    HIPCHECK(hipStreamSynchronize(h->st.stream));
     if (f) {
-        HIPCHECK(hipMemsetAsync(h->failflag, 0, sizeof(int), h->stream));
+        HIPCHECK(hipMemsetAsync(h->ws.failflag, 0, sizeof(int), h->st.stream));
         return fail(INSIDER_ERR_SOLVE, "a ridge normal-equation system was not positive definite");
     }
     return INSIDER_OK;
@@ -1492,8 +1559,8 @@ int check_fail_flag(insider_hip_handle *h)
 int read_cap_hits(insider_hip_handle *h)
 {
     int v[2] = {0, 0};
-    HIPCHECK(hipMemcpyAsync(v, h->failflag + 2, sizeof(v), hipMemcpyDeviceToHost, h->stream));
-    HIPCHECK(hipStreamSynchronize(h->stream));
+    HIPCHECK(hipMemcpyAsync(v, h->ws.failflag + 2, sizeof(v), hipMemcpyDeviceToHost, h->st.stream));
+    HIPCHECK(hipStreamSynchronize(h->st.stream));
     h->cap_hits = v[0];
     h->max_gene_sweeps = v[1];
     return INSIDER_OK;
@@ -1501,34 +1568,25 @@ int read_cap_hits(insider_hip_handle *h)
 
 void clear_events(insider_hip_handle *h)
 {
-    for (auto *v : {&h->ev_col, &h->ev_row, &h->ev_cd, &h->ev_test}) {
-        for (auto e : *v) (void)hipEventDestroy(e);
-        v->clear();
-    }
+    for (auto *v : {&h->ev_col, &h->ev_row, &h->ev_cd, &h->ev_test}) v->clear();
 }
 
 // host row/column factors -> padded device layout (the reference aliases R's memory, src/optimize.cpp:283-284)
 int upload_factors(insider_hip_handle *h, double *const *A, const double *C, int K)
 {
-    const int KP = h->KP;
-    for (int i = 0; i < h->c; ++i) {
-        const int L = h->n_levels[i];
-        HIPCHECK(hipMemcpyAsync(h->stage, A[i], (size_t)L * K * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        hipLaunchKernelGGL(k_pack_A, dim3(cdiv(L * KP, 256)), dim3(256), 0, h->stream, (const double *)h->stage, L, K, KP,
-                           h->Astack + (size_t)h->lvl_off[i] * KP);
+    const DataSet &d = *h->ds;
+    const int KP = h->ws.KP;
+    const hipStream_t st = h->st.stream;
+    for (int b = 0; b < d.blocks(); ++b) {
+        const DataSet::Block blk = d.block(b);
+        HIPCHECK(hipMemcpyAsync(h->ws.stage, A[b], (size_t)blk.rows * K * sizeof(double), hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_pack_A, dim3(cdiv(blk.rows * KP, 256)), dim3(256), 0, st, (const double *)h->ws.stage, blk.rows, K, KP,
+                           h->ws.Astack + (size_t)blk.off * KP);
         KCHECK();
-        HIPCHECK(hipStreamSynchronize(h->stream));   // stage is reused
+        HIPCHECK(hipStreamSynchronize(st));   // stage is reused
     }
-    if (h->m > 0) {
-        HIPCHECK(hipMemcpyAsync(h->stage, A[h->c], (size_t)h->m * K * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        hipLaunchKernelGGL(k_pack_A, dim3(cdiv(h->m * KP, 256)), dim3(256), 0, h->stream, (const double *)h->stage, h->m, K,
-                           KP, h->Astack + (size_t)h->SLcat * KP);
-        KCHECK();
-        HIPCHECK(hipStreamSynchronize(h->stream));
-    }
-    HIPCHECK(hipMemcpyAsync(h->stage, C, (size_t)h->p * K * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(k_pack_rows, dim3(cdiv(h->p * KP, 256)), dim3(256), 0, h->stream, (const double *)h->stage, h->p, K,
-                       KP, h->C);
+    HIPCHECK(hipMemcpyAsync(h->ws.stage, C, (size_t)d.p * K * sizeof(double), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_pack_rows, dim3(cdiv(d.p * KP, 256)), dim3(256), 0, st, (const double *)h->ws.stage, d.p, K, KP, h->ws.C);
     KCHECK();
     return INSIDER_OK;
 }
@@ -1536,30 +1594,23 @@ int upload_factors(insider_hip_handle *h, double *const *A, const double *C, int
 // device factors -> the caller's buffers (the reference returns copies AND has mutated its inputs in place, :413-421)
 int download_factors(insider_hip_handle *h, double *const *A, double *C, int K)
 {
-    const int KP = h->KP;
-    if (A) {
-        for (int i = 0; i < h->c; ++i) {
-            const int L = h->n_levels[i];
-            hipLaunchKernelGGL(k_unpack_A, dim3(cdiv(L * K, 256)), dim3(256), 0, h->stream,
-                               (const double *)(h->Astack + (size_t)h->lvl_off[i] * KP), L, K, KP, h->stage);
-            KCHECK();
-            HIPCHECK(hipMemcpyAsync(A[i], h->stage, (size_t)L * K * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-            HIPCHECK(hipStreamSynchronize(h->stream));
-        }
-        if (h->m > 0) {
-            hipLaunchKernelGGL(k_unpack_A, dim3(cdiv(h->m * K, 256)), dim3(256), 0, h->stream,
-                               (const double *)(h->Astack + (size_t)h->SLcat * KP), h->m, K, KP, h->stage);
-            KCHECK();
-            HIPCHECK(hipMemcpyAsync(A[h->c], h->stage, (size_t)h->m * K * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-            HIPCHECK(hipStreamSynchronize(h->stream));
-        }
+    const DataSet &d = *h->ds;
+    const int KP = h->ws.KP;
+    const hipStream_t st = h->st.stream;
+    for (int b = 0; A && b < d.blocks(); ++b) {
+        const DataSet::Block blk = d.block(b);
+        hipLaunchKernelGGL(k_unpack_A, dim3(cdiv(blk.rows * K, 256)), dim3(256), 0, st,
+                           (const double *)(h->ws.Astack + (size_t)blk.off * KP), blk.rows, K, KP, h->ws.stage);
+        KCHECK();
+        HIPCHECK(hipMemcpyAsync(A[b], h->ws.stage, (size_t)blk.rows * K * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIPCHECK(hipStreamSynchronize(st));
     }
     if (C) {
-        hipLaunchKernelGGL(k_unpack_rows, dim3(cdiv(h->p * K, 256)), dim3(256), 0, h->stream, (const double *)h->C, h->p, K,
-                           KP, h->stage);
+        hipLaunchKernelGGL(k_unpack_rows, dim3(cdiv(d.p * K, 256)), dim3(256), 0, st, (const double *)h->ws.C, d.p, K, KP,
+                           h->ws.stage);
         KCHECK();
-        HIPCHECK(hipMemcpyAsync(C, h->stage, (size_t)h->p * K * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        HIPCHECK(hipStreamSynchronize(h->stream));
+        HIPCHECK(hipMemcpyAsync(C, h->ws.stage, (size_t)d.p * K * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIPCHECK(hipStreamSynchronize(st));
     }
     return INSIDER_OK;
 }
@@ -1567,10 +1618,10 @@ int download_factors(insider_hip_handle *h, double *const *A, double *C, int K)
 // C C' and S_i C' for the row step (src/optimize.cpp:332 and the unmasked part of :166,188)
 int launch_row_prep(insider_hip_handle *h, int masked)
 {
-    int rc = launch_gram(h, h->C, h->p, h->CCt);
+    int rc = launch_gram(h, h->ws.C, h->ds->p, h->ws.CCt);
     if (rc) return rc;
     // the merged update wants (S^train C'): the per-level sums of the TRAIN entries, i.e. (S C') minus sum_r bc_r
-    if ((rc = launch_mm_reduce_kp(h, use_merged(h, masked) ? h->Strain : h->S, h->SLP, h->C, (int)h->p, h->SL, h->sc_part, h->SC)))
+    if ((rc = launch_mm_reduce_kp(h, use_merged(h, masked) ? h->ds->Strain : h->ds->S, h->ds->SLP, h->ws.C, (int)h->ds->p, h->ds->SL, h->ws.sc_part, h->ws.SC)))
         return rc;
     return INSIDER_OK;
 }
@@ -1582,11 +1633,11 @@ int check_factor_args(insider_hip_handle *h, double *const *A, const double *C, 
         return fail(INSIDER_ERR_ARG, "Parameter tuning should be either 0 or 1!");
     if (inc_continuous != 0 && inc_continuous != 1)   // src/optimize.cpp:270-272
         return fail(INSIDER_ERR_ARG, "The value of prarameter inc_continuous can only be 0 or 1.");
-    if (inc_continuous == 1 && h->m == 0)
+    if (inc_continuous == 1 && h->ds->m == 0)
         return fail(INSIDER_ERR_ARG, "inc_continuous = 1 needs a handle created with ctns_confounder (insider_hip_create_ex)");
-    if (inc_continuous == 0 && h->m > 0)
+    if (inc_continuous == 0 && h->ds->m > 0)
         return fail(INSIDER_ERR_ARG, "this handle carries continuous covariates: pass inc_continuous = 1");
-    for (int i = 0; i < h->c + (h->m > 0 ? 1 : 0); ++i) if (!A[i]) return fail(INSIDER_ERR_ARG, "null row factor");
+    for (int b = 0; b < h->ds->blocks(); ++b) if (!A[b]) return fail(INSIDER_ERR_ARG, "null row factor");
     return INSIDER_OK;
 }
 
@@ -1611,120 +1662,505 @@ int insider_hip_device_count(void)
     return n;
 }
 
+}  // extern "C"
+
 namespace {
-// streams and events of one handle (each handle, clones included, has its own)
-hipError_t make_streams(insider_hip_handle *h)
+int stream_events(int c, int m) { return (c > 0 ? c : 1) + m; }   // Streams::ev_w: one per covariate and continuous column
+
+// ---- insider_hip_create_ex in stages: each fills its part of the DataSet ---------------------------------------------------
+struct CreateArgs {
+    const double *X;
+    int64_t n, p;
+    const int32_t *levels;
+    int c;
+    const int32_t *n_levels;
+    const double *ctns;
+    int m;
+    const uint8_t *M_train, *M_test;
+};
+
+int check_create_args(const CreateArgs &a, int device)
 {
-    hipError_t e;
-#define MS(call) do { if ((e = (call)) != hipSuccess) return e; } while (0)
-    MS(hipStreamCreate(&h->stream));
-    MS(hipStreamCreateWithFlags(&h->side, hipStreamNonBlocking));
-    MS(hipStreamCreateWithFlags(&h->side2, hipStreamNonBlocking));
-    MS(hipStreamCreateWithFlags(&h->side3, hipStreamNonBlocking));
-    MS(hipEventCreateWithFlags(&h->ev_prep, EV_SYNC));
-    MS(hipEventCreateWithFlags(&h->ev_c_ready, EV_SYNC));
-    MS(hipEventCreateWithFlags(&h->ev_head, EV_SYNC));
-    MS(hipEventCreateWithFlags(&h->ev_a_ready, EV_SYNC));
-    MS(hipEventCreateWithFlags(&h->ev_qfull, EV_SYNC));
-    MS(hipEventCreateWithFlags(&h->ev_qheld, EV_SYNC));
-    h->ev_w.assign((h->c > 0 ? h->c : 1) + h->m, nullptr);
-    for (auto &ev : h->ev_w) MS(hipEventCreateWithFlags(&ev, EV_SYNC));
-    MS(hipEventCreateWithFlags(&h->ev_cd_done, EV_SYNC));
-    MS(hipEventCreateWithFlags(&h->ev_side_done, EV_SYNC));
-    MS(hipEventCreateWithFlags(&h->ev_tab, EV_SYNC));
-#undef MS
-    return hipSuccess;
+    if (!a.X || !a.levels || !a.n_levels || !a.M_train || !a.M_test) return fail(INSIDER_ERR_ARG, "null input");
+    if (a.n < 1 || a.p < 1 || a.c < 1) return fail(INSIDER_ERR_ARG, "n, p, c must be positive");
+    if (a.n > (1 << 30) || a.p > (1 << 30)) return fail(INSIDER_ERR_ARG, "dimension too large");
+    if (a.n >= LIST_PAD || a.p >= LIST_PAD) return fail(INSIDER_ERR_UNSUPPORTED, "n and p must be below 2^23");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
+        return fail(INSIDER_ERR_NO_DEVICE, "no HIP device visible: libinsider_hip has no CPU fallback");
+    if (device < 0 || device >= ndev) return fail(INSIDER_ERR_ARG, "bad device ordinal");
+    // level ids must be exactly 1..L_i (src/optimize.cpp:175,286)
+    for (int i = 0; i < a.c; ++i) {
+        if (a.n_levels[i] < 1) return fail(INSIDER_ERR_ARG, "n_levels must be positive");
+        for (int64_t r = 0; r < a.n; ++r) {
+            const int32_t l = a.levels[r + (size_t)i * a.n];
+            if (l < 1 || l > a.n_levels[i]) return fail(INSIDER_ERR_ARG, "level ids must be within 1..L_i");
+        }
+    }
+    return INSIDER_OK;
 }
 
-void destroy_streams(insider_hip_handle *h)
+// 0-based level of every sample, covariate by covariate (c x n)
+std::vector<int> level_index(const CreateArgs &a)
 {
-    for (hipStream_t *st : {&h->side, &h->side2, &h->side3}) { if (*st) (void)hipStreamDestroy(*st); *st = nullptr; }
-    for (hipEvent_t *ev : {&h->ev_prep, &h->ev_c_ready, &h->ev_head, &h->ev_a_ready, &h->ev_qfull, &h->ev_qheld, &h->ev_cd_done,
-                           &h->ev_side_done, &h->ev_tab}) { if (*ev) (void)hipEventDestroy(*ev); *ev = nullptr; }
-    for (auto ev : h->ev_w) if (ev) (void)hipEventDestroy(ev);
-    h->ev_w.clear();
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-    h->stream = nullptr;
+    std::vector<int> lev0((size_t)a.c * a.n);
+    for (size_t e = 0; e < lev0.size(); ++e) lev0[e] = a.levels[e] - 1;
+    return lev0;
 }
 
-// the device arrays of the data set (everything insider_hip_create_ex builds that does not depend on K or on the factors)
-void free_data_set(insider_hip_handle *h)
+void describe(DataSet &d, const CreateArgs &a, int device)
 {
-    void *ptrs[] = {h->X, h->Xt, h->codes, h->codes_t, h->lev, h->lvl_off_d, h->members_all, h->lvl_ptr_all,
-                    h->lvl_count_all, h->S, h->yy_train, h->yy_all, h->col_ptr, h->row_ptr, h->col_idx, h->row_idx,
-                    h->col_val, h->row_val, h->col_flag, h->Zc, h->one_count, h->ident_members, h->cont.chunk_begin, h->cont.chunk_end,
-                    h->cont.lvl_chunk_ptr};
-    for (void *q : ptrs) if (q) (void)hipFree(q);
-    for (auto &ct : h->cov) {
-        if (ct.chunk_level) (void)hipFree(ct.chunk_level);
-        if (ct.chunk_begin) (void)hipFree(ct.chunk_begin);
-        if (ct.chunk_end) (void)hipFree(ct.chunk_end);
-        if (ct.lvl_chunk_ptr) (void)hipFree(ct.lvl_chunk_ptr);
-        for (void *q : {(void *)ct.grp, (void *)ct.slev, (void *)ct.item_begin, (void *)ct.item_end, (void *)ct.lvl_item_ptr,
-                        (void *)ct.wl_idx, (void *)ct.wl_w, (void *)ct.paircnt})
-            if (q) (void)hipFree(q);
+    d.device = device;
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0) d.n_simd = 4 * cus;
+    d.n = a.n;
+    d.p = a.p;
+    d.c = a.c;
+    d.ldn = round_up(a.n, CHUNK);
+    d.ldp = round_up(a.p, CHUNK);
+    d.n_levels.assign(a.n_levels, a.n_levels + a.c);
+    d.lvl_off.assign(a.c + 1, 0);
+    for (int i = 0; i < a.c; ++i) d.lvl_off[i + 1] = d.lvl_off[i] + a.n_levels[i];
+    d.m = a.m;
+    d.SLcat = d.lvl_off[a.c];
+    d.SL = d.SLcat + a.m;
+    d.SLP = (int)round_up(d.SL, 2);
+}
+
+// X (gene-major lines of pitch ldn) and mask codes
+int stage_matrix(DataSet &d, const CreateArgs &a, hipStream_t st)
+{
+    const int64_t n = a.n, p = a.p;
+    int rc;
+    if ((rc = d.X.alloc((size_t)p * d.ldn)) || (rc = d.codes.alloc((size_t)p * d.ldn))) return rc;
+    HIPCHECK(hipMemsetAsync(d.X, 0, (size_t)p * d.ldn * sizeof(double), st));
+    HIPCHECK(hipMemcpy2DAsync(d.X, d.ldn * sizeof(double), a.X, n * sizeof(double), n * sizeof(double), p, hipMemcpyHostToDevice,
+                              st));
+    DevBuf<uint8_t> mtr, mte;
+    if ((rc = mtr.alloc((size_t)n * p)) || (rc = mte.alloc((size_t)n * p))) return rc;
+    HIPCHECK(hipMemcpyAsync(mtr, a.M_train, (size_t)n * p, hipMemcpyHostToDevice, st));
+    HIPCHECK(hipMemcpyAsync(mte, a.M_test, (size_t)n * p, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_make_codes, dim3(cdiv(p * d.ldn, 256)), dim3(256), 0, st, mtr, mte, n, p, d.ldn, d.codes);
+    KCHECK();
+    HIPCHECK(hipStreamSynchronize(st));
+    return INSIDER_OK;
+}
+
+// level tables: members of every level, and the chunk tables of the two-stage level reduction
+int stage_levels(DataSet &d, const CreateArgs &a)
+{
+    const int64_t n = a.n;
+    const int c = a.c;
+    const std::vector<int> lev0 = level_index(a);
+    std::vector<int> members((size_t)c * n), lvl_ptr((size_t)d.SLcat + c), lvl_count(d.SLcat);
+    d.cov.resize(c);
+    int rc;
+    for (int i = 0; i < c; ++i) {
+        const int L = a.n_levels[i];
+        std::vector<int> cnt(L, 0);
+        for (int64_t r = 0; r < n; ++r) cnt[lev0[(size_t)i * n + r]]++;
+        int *ptr = lvl_ptr.data() + d.lvl_off[i] + i;
+        ptr[0] = 0;
+        for (int l = 0; l < L; ++l) { ptr[l + 1] = ptr[l] + cnt[l]; lvl_count[d.lvl_off[i] + l] = cnt[l]; }
+        std::vector<int> fill(ptr, ptr + L);
+        for (int64_t r = 0; r < n; ++r) members[(size_t)i * n + fill[lev0[(size_t)i * n + r]]++] = (int)r;
+        std::vector<int> ch_level, ch_begin, ch_end, lcp(L + 1, 0);
+        for (int l = 0; l < L; ++l) {
+            lcp[l] = (int)ch_level.size();
+            for (int b = ptr[l]; b < ptr[l + 1]; b += LEVEL_CHUNK) {
+                ch_level.push_back(l);
+                ch_begin.push_back(b);
+                ch_end.push_back(std::min(b + LEVEL_CHUNK, ptr[l + 1]));
+            }
+        }
+        lcp[L] = (int)ch_level.size();
+        CovTables &ct = d.cov[i];
+        ct.L = L;
+        ct.nchunks = (int)ch_level.size();
+        d.max_chunks = std::max(d.max_chunks, ct.nchunks);
+        d.max_L = std::max(d.max_L, L);
+        if ((rc = ct.chunk_level.upload(ch_level)) || (rc = ct.chunk_begin.upload(ch_begin)) || (rc = ct.chunk_end.upload(ch_end)) ||
+            (rc = ct.lvl_chunk_ptr.upload(lcp)))
+            return rc;
     }
-    if (h->Strain) (void)hipFree(h->Strain);
-    if (h->Sheld) (void)hipFree(h->Sheld);
-    if (h->cf_cnt) (void)hipFree(h->cf_cnt);
-    if (h->cf_hn) (void)hipFree(h->cf_hn);
-    if (h->cf_zt) (void)hipFree(h->cf_zt);
-    if (h->cont_cnt) (void)hipFree(h->cont_cnt);
-    for (size_t k = 0; k < h->contm.size(); ++k) {
-        CovTables &ct = h->contm[k];
-        for (void *q : {(void *)(k == 0 ? ct.wl_idx : nullptr), (void *)ct.wl_w, (void *)(k == 0 ? ct.item_begin : nullptr),
-                        (void *)(k == 0 ? ct.item_end : nullptr), (void *)(k == 0 ? ct.lvl_item_ptr : nullptr), (void *)ct.paircnt})
-            if (q) (void)hipFree(q);   // (the index list and the work items are shared by the columns: freed with column 0)
+    if ((rc = d.lev.upload(lev0)) || (rc = d.members_all.upload(members)) || (rc = d.lvl_ptr_all.upload(lvl_ptr)) ||
+        (rc = d.lvl_count_all.upload(lvl_count)) || (rc = d.lvl_off_d.upload(d.lvl_off)))
+        return rc;
+    return INSIDER_OK;
+}
+
+// continuous covariates: one pseudo-level whose members are all samples, weighted by z
+int stage_continuous(DataSet &d, const CreateArgs &a)
+{
+    const int64_t n = a.n;
+    if (a.m == 0) return INSIDER_OK;
+    int rc;
+    if ((rc = d.Zc.alloc((size_t)a.m * n))) return rc;
+    HIPCHECK(hipMemcpy(d.Zc, a.ctns, (size_t)a.m * n * sizeof(double), hipMemcpyHostToDevice));   // n x m column-major == m x n rows
+    std::vector<int> ident(n), cb, ce, lcp(2, 0);
+    for (int64_t r = 0; r < n; ++r) ident[r] = (int)r;
+    for (int64_t b0 = 0; b0 < n; b0 += LEVEL_CHUNK) { cb.push_back((int)b0); ce.push_back((int)std::min<int64_t>(b0 + LEVEL_CHUNK, n)); }
+    lcp[1] = (int)cb.size();
+    d.cont.L = 1;
+    d.cont.nchunks = (int)cb.size();
+    d.max_chunks = std::max(d.max_chunks, d.cont.nchunks);
+    d.max_L = std::max(d.max_L, 1);
+    if ((rc = d.ident_members.upload(ident)) || (rc = d.cont.chunk_begin.upload(cb)) || (rc = d.cont.chunk_end.upload(ce)) ||
+        (rc = d.cont.lvl_chunk_ptr.upload(lcp)) || (rc = d.one_count.upload(std::vector<int>{1})))
+        return rc;
+    return INSIDER_OK;
+}
+
+// factor-independent statistics: per-gene sums of squares, per-level sums of X (all entries and train entries), entry counts
+int stage_sums(DataSet &d, const CreateArgs &a, hipStream_t st)
+{
+    const int64_t n = a.n, p = a.p;
+    const int c = a.c, m = a.m;
+    int rc;
+    if ((rc = d.S.alloc((size_t)p * d.SLP)) || (rc = d.yy_train.alloc((size_t)p)) || (rc = d.yy_all.alloc((size_t)p))) return rc;
+    HIPCHECK(hipMemsetAsync(d.S, 0, (size_t)p * d.SLP * sizeof(double), st));
+    DevBuf<unsigned long long> cnt;
+    if ((rc = cnt.alloc(2))) return rc;
+    HIPCHECK(hipMemsetAsync(cnt, 0, 2 * sizeof(unsigned long long), st));
+    hipLaunchKernelGGL(k_line_sumsq, dim3(cdiv(p, 4)), dim3(256), 0, st, (const double *)d.X, (const uint8_t *)d.codes, d.ldn, (int)n,
+                       (int)p, d.yy_train, d.yy_all, cnt);
+    hipLaunchKernelGGL(k_level_sums, dim3(cdiv(p * d.SLcat, 256)), dim3(256), 0, st, (const double *)d.X, (const uint8_t *)nullptr,
+                       d.ldn, (int)p, (const int *)d.members_all, (const int *)d.lvl_ptr_all, (const int *)d.lvl_off_d, c, (int)n,
+                       d.SLcat, d.SLP, d.S);
+    // train-only sums for the merged masked row update / the factored column statistics (the categorical columns)
+    if ((rc = d.Strain.alloc((size_t)p * d.SLP))) return rc;
+    HIPCHECK(hipMemsetAsync(d.Strain, 0, (size_t)p * d.SLP * sizeof(double), st));
+    hipLaunchKernelGGL(k_level_sums, dim3(cdiv(p * d.SLcat, 256)), dim3(256), 0, st, (const double *)d.X, (const uint8_t *)d.codes,
+                       d.ldn, (int)p, (const int *)d.members_all, (const int *)d.lvl_ptr_all, (const int *)d.lvl_off_d, c, (int)n,
+                       d.SLcat, d.SLP, d.Strain);
+    if (m > 0)
+        hipLaunchKernelGGL(k_cont_sums, dim3(cdiv(p * m, 256)), dim3(256), 0, st, (const double *)d.X, d.ldn, (int)p,
+                           (const double *)d.Zc, m, (int)n, d.SLcat, d.SLP, d.S);
+    KCHECK();
+    unsigned long long hc[2];
+    HIPCHECK(hipMemcpyAsync(hc, cnt, sizeof(hc), hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipStreamSynchronize(st));
+    d.cnt_train = (double)hc[0];
+    d.cnt_test = (double)hc[1];
+    d.no_na = hc[0] + hc[1] == (unsigned long long)n * (unsigned long long)p;
+    return INSIDER_OK;
+}
+
+// held-out lists of both sides (the masks never change: built once).  The row side is read from transposed copies
+// (sample-major lines of pitch ldp) that live only here.
+int stage_lists(DataSet &d, const CreateArgs &a, hipStream_t st)
+{
+    const int64_t n = a.n, p = a.p;
+    int rc;
+    DevBuf<double> Xt;
+    DevBuf<uint8_t> codes_t;
+    if ((rc = Xt.alloc((size_t)n * d.ldp)) || (rc = codes_t.alloc((size_t)n * d.ldp))) return rc;
+    HIPCHECK(hipMemsetAsync(Xt, 0, (size_t)n * d.ldp * sizeof(double), st));
+    HIPCHECK(hipMemsetAsync(codes_t, CODE_TRAIN, (size_t)n * d.ldp, st));
+    const dim3 grid(cdiv(n, 32), cdiv(p, 32));   // input: p lines (rows) x n columns
+    hipLaunchKernelGGL((k_transpose<double>), grid, dim3(256), 0, st, (const double *)d.X, p, n, d.ldn, Xt, d.ldp);
+    hipLaunchKernelGGL((k_transpose<uint8_t>), grid, dim3(256), 0, st, (const uint8_t *)d.codes, p, n, d.ldn, codes_t, d.ldp);
+    KCHECK();
+    for (int side = 0; side < 2; ++side) {
+        const bool cols = side == 0;
+        const int lines = cols ? (int)p : (int)n, len = cols ? (int)n : (int)p;
+        const double *vals = cols ? d.X : Xt;
+        const uint8_t *cds = cols ? d.codes : codes_t;
+        const int64_t pitch = cols ? d.ldn : d.ldp;
+        DevBuf<int> cnt_d;
+        if ((rc = cnt_d.alloc((size_t)lines))) return rc;
+        hipLaunchKernelGGL(k_count_heldout, dim3(cdiv(lines, 4)), dim3(256), 0, st, cds, pitch, len, lines, cnt_d);
+        KCHECK();
+        std::vector<int> cnt(lines);
+        HIPCHECK(hipMemcpyAsync(cnt.data(), cnt_d, (size_t)lines * sizeof(int), hipMemcpyDeviceToHost, st));
+        HIPCHECK(hipStreamSynchronize(st));
+        std::vector<uint32_t> ptr((size_t)lines + 1);
+        uint64_t tot = 0;
+        for (int i = 0; i < lines; ++i) { ptr[i] = (uint32_t)tot; tot += (uint64_t)round_up(cnt[i], LIST_ALIGN); }
+        ptr[lines] = (uint32_t)tot;
+        if (tot >= (1ull << 32)) return fail(INSIDER_ERR_UNSUPPORTED, "more than 2^32 held-out entries");
+        DevBuf<uint32_t> &dptr = cols ? d.col_ptr : d.row_ptr;
+        DevBuf<int> &didx = cols ? d.col_idx : d.row_idx;
+        DevBuf<double> &dval = cols ? d.col_val : d.row_val;
+        (cols ? d.col_entries : d.row_entries) = tot;
+        if ((rc = dptr.upload(ptr)) || (rc = didx.alloc((size_t)tot + LIST_BLOCK)) || (rc = dval.alloc((size_t)tot + LIST_BLOCK)))
+            return rc;
+        uint8_t *dflag = nullptr;
+        if (cols && !d.no_na) {
+            if ((rc = d.col_flag.alloc((size_t)tot + LIST_BLOCK))) return rc;
+            dflag = d.col_flag;
+        }
+        hipLaunchKernelGGL(k_fill_lists, dim3(cdiv(lines, 4)), dim3(256), 0, st, vals, cds, pitch, len, lines, (const uint32_t *)dptr,
+                           didx, dval, dflag);
+        KCHECK();
+        HIPCHECK(hipStreamSynchronize(st));
     }
+    return INSIDER_OK;
+}
+
+constexpr uint32_t SEG = 1024;   // list entries per weighted-SYRK work item (multiple of LIST_ALIGN)
+
+// merged masked row update: per covariate, the genes' held-out samples grouped by level, the (gene, count) lists of every
+// level and the level-pair sample counts (insider_row_merged.hpp).
+// (k_gene_u keeps a gene's SLcat look-up values per wave in LDS: beyond ~1500 stacked levels the per-sample path stays)
+// (with continuous covariates, m <= 4: the same tables serve the pair-count column statistics, ColFacArgs::zt)
+int stage_merged(DataSet &d, const CreateArgs &a, hipStream_t st)
+{
+    const int64_t n = a.n, p = a.p;
+    const int c = a.c, m = a.m;
+    if (!(m <= 4 && (size_t)4 * (d.SLcat + GU_TILE) * sizeof(double) <= 64 * 1024)) return INSIDER_OK;
+    const std::vector<int> lev0 = level_index(a);
+    int rc;
+    for (int i = 0; i < c; ++i) {
+        CovTables &ct = d.cov[i];
+        const int L = ct.L;
+        if ((rc = ct.grp.alloc((size_t)p * (L + 1)))) return rc;
+        const size_t plane = (size_t)d.col_entries + LIST_BLOCK;
+        if (d.SLcat > 65535) return fail(INSIDER_ERR_UNSUPPORTED, "more than 65535 levels in total");
+        if ((rc = ct.slev.alloc(plane * (size_t)std::max(c - 1, 1)))) return rc;
+        const size_t lds = (size_t)4 * L * sizeof(int);
+        if (lds > 60 * 1024) return fail(INSIDER_ERR_UNSUPPORTED, "a covariate has more than 3840 levels");
+        hipLaunchKernelGGL(k_group_count, dim3(cdiv(p, 4)), dim3(256), lds, st, (const uint32_t *)d.col_ptr, (const int *)d.col_idx,
+                           (const int *)(d.lev + (size_t)i * n), L, (int)p, ct.grp);
+        hipLaunchKernelGGL(k_group_fill, dim3(cdiv(p, 4)), dim3(256), lds, st, (const uint32_t *)d.col_ptr, (const int *)d.col_idx,
+                           (const int *)d.lev, (const int *)d.lvl_off_d, c, (int)n, i, L, (int)p, (const uint32_t *)ct.grp, ct.slev,
+                           plane);
+        KCHECK();
+        std::vector<uint32_t> grp((size_t)p * (L + 1));
+        HIPCHECK(hipMemcpyAsync(grp.data(), ct.grp, grp.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIPCHECK(hipStreamSynchronize(st));
+        // (gene, count) list of every level, padded to LIST_ALIGN; work items of at most SEG entries
+        std::vector<int> widx, lip(L + 1, 0);
+        std::vector<double> ww;
+        std::vector<uint32_t> ib, ie;
+        for (int l = 0; l < L; ++l) {
+            lip[l] = (int)ib.size();
+            const size_t start = widx.size();
+            for (int64_t j = 0; j < p; ++j) {
+                const uint32_t cnt = grp[(size_t)j * (L + 1) + l + 1] - grp[(size_t)j * (L + 1) + l];
+                if (cnt) { widx.push_back((int)j); ww.push_back((double)cnt); }
+            }
+            while ((widx.size() - start) % LIST_ALIGN) { widx.push_back(LIST_PAD); ww.push_back(0.0); }
+            for (size_t b = start; b < widx.size(); b += SEG) {
+                ib.push_back((uint32_t)b);
+                ie.push_back((uint32_t)std::min(b + SEG, widx.size()));
+            }
+        }
+        lip[L] = (int)ib.size();
+        if (widx.size() >= (1ull << 32)) return fail(INSIDER_ERR_UNSUPPORTED, "level lists too long");
+        ct.nitems = (int)ib.size();
+        ct.npairs = 0;
+        for (double wv : ww) ct.npairs += wv != 0.0;
+        d.max_items = std::max(d.max_items, ct.nitems);
+        if ((rc = ct.wl_idx.upload(widx, widx.size() + LIST_BLOCK)) || (rc = ct.wl_w.upload(ww, ww.size() + LIST_BLOCK)) ||
+            (rc = ct.item_begin.upload(ib, ib.size() + 1)) || (rc = ct.item_end.upload(ie, ie.size() + 1)) ||
+            (rc = ct.lvl_item_ptr.upload(lip)))
+            return rc;
+        // samples per (level of covariate i, stacked level of another covariate): sum_{r in l} s_r = paircnt A
+        // (+ m columns sum_{r in l} z_rk: a continuous column is a stacked "level" with real-valued counts)
+        std::vector<double> pc((size_t)L * d.SL, 0.0);
+        for (int64_t r = 0; r < n; ++r) {
+            const int l = lev0[(size_t)i * n + r];
+            for (int q = 0; q < c; ++q)
+                if (q != i) pc[(size_t)l * d.SL + d.lvl_off[q] + lev0[(size_t)q * n + r]] += 1.0;
+            for (int k = 0; k < m; ++k) pc[(size_t)l * d.SL + d.SLcat + k] += a.ctns[(size_t)k * n + r];
+        }
+        if ((rc = ct.paircnt.upload(pc))) return rc;
+    }
+    d.merged = true;
+    if ((rc = d.Sheld.alloc((size_t)p * d.SLP))) return rc;
+    hipLaunchKernelGGL(k_sub, dim3(cdiv((int64_t)p * d.SLP, 256)), dim3(256), 0, st, (const double *)d.S, (const double *)d.Strain,
+                       (size_t)p * d.SLP, d.Sheld);
+    KCHECK();
+    return INSIDER_OK;
+}
+
+// factored column statistics: covariates by decreasing level count, the planes of the later ones; the dense pair counts
+// and half counts of the pair-count form when they are small enough
+int stage_factored(DataSet &d, const CreateArgs &a, hipStream_t st)
+{
+    const int64_t n = a.n, p = a.p;
+    const int c = a.c;
+    if (!d.merged || c > CF_MAXC) return INSIDER_OK;
+    std::vector<int> ord(c);
+    for (int i = 0; i < c; ++i) ord[i] = i;
+    std::stable_sort(ord.begin(), ord.end(), [&](int x, int y) { return a.n_levels[x] > a.n_levels[y]; });
+    ColFacArgs &cf = d.cf;
+    cf.p = (int)p;
+    cf.c = c;
+    cf.plane = (size_t)d.col_entries + LIST_BLOCK;
+    for (int t = 0; t < c; ++t) {
+        const int o = ord[t];
+        d.cf_pos[o] = t;
+        cf.grp[t] = d.cov[o].grp;
+        cf.slev[t] = d.cov[o].slev;
+        cf.L[t] = a.n_levels[o];
+        cf.off[t] = d.lvl_off[o];
+        cf.nlater[t] = c - 1 - t;
+        for (int k = t + 1; k < c; ++k) cf.later_plane[t][k - t - 1] = ord[k] < o ? ord[k] : ord[k] - 1;
+    }
+    cf.tab_skip_lo = d.lvl_off[ord[0]];
+    cf.tab_skip_n = a.n_levels[ord[0]];
+    cf.tab_rows = d.SLcat - cf.tab_skip_n;
+    // pair-count form: the dense per-gene count tables (one byte per cell), when they are small enough
+    cf.nsteps = (cf.tab_rows + 3) / 4;
+    bool fits = cf.nsteps <= CP_MAXSTEPS;
+    int off = 0;
+    for (int t = 0; t < c; ++t) {
+        const int cells = ((cf.L[t] + 15) / 16) * 64 * (cf.nsteps <= 4 ? 4 : 8);   // bytes: 4 or 8 per lane and block
+        cf.cnt_off[t] = off;
+        if (cf.nlater[t] > 0) off += cells;
+    }
+    cf.cnt_stride = off;
+    cf.cnt = nullptr;
+    int rc;
+    if (fits && off <= 64 * 1024 && (size_t)p * (size_t)off <= ((size_t)1 << 32)) {   // <= 64 KB of counts per gene
+        if (off > 0) {
+            DevBuf<int> ovf;
+            if ((rc = d.cf_cnt.alloc((size_t)p * off)) || (rc = ovf.alloc(1))) return rc;
+            HIPCHECK(hipMemsetAsync(ovf, 0, sizeof(int), st));
+            hipLaunchKernelGGL((k_pair_count_build<2>), dim3(cdiv(p, 2)), dim3(128), 0, st, cf, d.cf_cnt, ovf);
+            KCHECK();
+            int hv = 0;
+            HIPCHECK(hipMemcpyAsync(&hv, ovf, sizeof(int), hipMemcpyDeviceToHost, st));
+            HIPCHECK(hipStreamSynchronize(st));
+            fits = hv == 0;
+        }
+        if (fits && n < ((int64_t)1 << 24)) {   // (1/2 n as a float is exact)
+            int hoff = 0;
+            for (int t = 0; t < c; ++t) {
+                cf.hn_off[t] = hoff;
+                hoff += ((cf.L[t] + 15) / 16) * 16;
+            }
+            cf.hn_stride = hoff;
+            if ((rc = d.cf_hn.alloc((size_t)(p + 4) * hoff))) return rc;   // + 4 zero rows: k_wgemm reads whole steps of four genes
+            HIPCHECK(hipMemsetAsync(d.cf_hn, 0, (size_t)(p + 4) * hoff * sizeof(float), st));
+            hipLaunchKernelGGL(k_half_counts, dim3((unsigned)cdiv((int64_t)p * hoff, 256)), dim3(256), 0, st, cf, d.cf_hn);
+            KCHECK();
+        } else {
+            fits = false;
+        }
+        d.cf_pair_ok = fits;
+    }
+    cf.zt = nullptr;
+    cf.m = a.m;
+    cf.SLcat = d.SLcat;
+    for (int t = 0; t < c; ++t) cf.pos_cov[t] = ord[t];
+    return INSIDER_OK;
+}
+
+// continuous covariates on the pair-count form: the real-valued count table, and the continuous columns as one-level
+// covariates of the merged row update
+int stage_cont_factored(DataSet &d, const CreateArgs &a, hipStream_t st)
+{
+    const int64_t n = a.n, p = a.p;
+    const int c = a.c, m = a.m;
+    // The merged row update with continuous columns takes u_j from k_gene_u_cnt ALONE (only it adds the term of the
+    // real-valued counts, ColFacArgs::zt; k_gene_u reads the categorical columns of V only): every covariate's launch
+    // of it must fit its per-wave LDS record — V row [SL] | out [LP] | GU_BATCH x 64 partial sums, four waves per block
+    // — or the whole data set stays on the per-sample / per-entry paths (a covariate with ~770 levels or more).
+    bool gu_fits = true;
+    for (int t = 0; t < c; ++t)
+        gu_fits = gu_fits && (size_t)4 * (d.SL + round_up(d.n_levels[t], 2) + GU_BATCH * WAVE) * sizeof(double) <= 64 * 1024;
+    if (!(m > 0 && d.cf_pair_ok && gu_fits)) return INSIDER_OK;
+    // one more position (the m columns as pseudo-levels, no count bytes, 1/2 n = 0: sixteen more zero floats per gene would
+    // do, the block reads what follows its offset -> its own zero region) and the real-valued count table
+    ColFacArgs &cf = d.cf;
+    cf.L[c] = m;
+    cf.off[c] = d.SLcat;
+    cf.nlater[c] = 0;
+    cf.cnt_off[c] = 0;
+    int zoff = 0;
+    for (int t = 0; t < c; ++t) { cf.zt_off[t] = zoff; zoff += ((cf.L[t] + 15) / 16) * 64; }
+    cf.zt_off[c] = zoff;
+    cf.zt_stride = zoff + 64;
+    // 1/2 n of position c: a zero region behind the table (rebuilt with the longer stride)
+    d.cf_hn.reset();
+    cf.hn_off[c] = cf.hn_stride;
+    cf.hn_stride += 16;
+    int rc;
+    if ((rc = d.cf_hn.alloc((size_t)(p + 4) * cf.hn_stride))) return rc;
+    HIPCHECK(hipMemsetAsync(d.cf_hn, 0, (size_t)(p + 4) * cf.hn_stride * sizeof(float), st));
+    hipLaunchKernelGGL(k_half_counts, dim3((unsigned)cdiv((int64_t)p * cf.hn_stride, 256)), dim3(256), 0, st, cf, d.cf_hn);
+    KCHECK();
+    if ((rc = d.cf_zt.alloc((size_t)p * cf.zt_stride))) return rc;
+    HIPCHECK(hipMemsetAsync(d.cf_zt, 0, (size_t)p * cf.zt_stride * sizeof(double), st));
+    // (Sheld's continuous columns: sum over the held-out entries of x z, next to S - S^train of the categorical ones)
+    hipLaunchKernelGGL(k_zt_build, dim3(cdiv(p, 4)), dim3(256), 0, st, cf, (const uint32_t *)d.col_ptr, (const int *)d.col_idx,
+                       (const double *)d.col_val, (const int *)d.lev, (const double *)d.Zc, (int)n, d.cf_zt, d.Sheld, d.SLP,
+                       (const double *)d.S, d.Strain);
+    KCHECK();
+    HIPCHECK(hipStreamSynchronize(st));
+    // ---- the continuous columns as one-level covariates of the merged row update: one (gene) list and work items for all ----
+    const size_t plen_l = (size_t)round_up(p, LIST_ALIGN);
+    std::vector<int> widx(plen_l, LIST_PAD);
+    for (int64_t j = 0; j < p; ++j) widx[j] = (int)j;
+    std::vector<uint32_t> ib, ie;
+    for (size_t b = 0; b < plen_l; b += SEG) { ib.push_back((uint32_t)b); ie.push_back((uint32_t)std::min(b + SEG, plen_l)); }
+    CovTables &lists = d.contm_lists;
+    lists.L = 1;
+    lists.nitems = (int)ib.size();
+    lists.npairs = p;
+    if ((rc = lists.wl_idx.upload(widx, plen_l + LIST_BLOCK)) || (rc = lists.item_begin.upload(ib, ib.size() + 1)) ||
+        (rc = lists.item_end.upload(ie, ie.size() + 1)) || (rc = lists.lvl_item_ptr.upload(std::vector<int>{0, (int)ib.size()})))
+        return rc;
+    d.max_items = std::max(d.max_items, (int)ib.size());
+    std::vector<double> zz((size_t)m * m, 0.0);
+    for (int k = 0; k < m; ++k)
+        for (int k2 = 0; k2 < m; ++k2) {
+            double acc = 0.0;
+            for (int64_t r = 0; r < n; ++r) acc += a.ctns[(size_t)k * n + r] * a.ctns[(size_t)k2 * n + r];
+            zz[(size_t)k * m + k2] = acc;
+        }
+    const std::vector<int> lev0 = level_index(a);
+    std::vector<double> cc(m);
+    d.contm.resize(m);
+    for (int k = 0; k < m; ++k) {
+        CovTables &ct = d.contm[k];
+        ct.L = 1;
+        ct.nitems = lists.nitems;
+        ct.npairs = p;
+        if ((rc = ct.wl_w.alloc(plen_l + LIST_BLOCK))) return rc;
+        HIPCHECK(hipMemsetAsync(ct.wl_w, 0, (plen_l + LIST_BLOCK) * sizeof(double), st));
+        hipLaunchKernelGGL(k_cont_weights, dim3(cdiv(p, 256)), dim3(256), 0, st, (const double *)d.cf_zt, cf.zt_stride, cf.zt_off[c], k,
+                           (int)p, ct.wl_w);
+        KCHECK();
+        std::vector<double> pc((size_t)d.SL, 0.0);
+        for (int64_t r = 0; r < n; ++r)
+            for (int q = 0; q < c; ++q) pc[d.lvl_off[q] + lev0[(size_t)q * n + r]] += a.ctns[(size_t)k * n + r];
+        for (int k2 = 0; k2 < m; ++k2) pc[d.SLcat + k2] = k2 == k ? 0.0 : zz[(size_t)k * m + k2];
+        if ((rc = ct.paircnt.upload(pc))) return rc;
+        cc[k] = zz[(size_t)k * m + k];
+    }
+    if ((rc = d.cont_cnt.upload(cc))) return rc;
+    HIPCHECK(hipStreamSynchronize(st));
+    d.cont_merged = true;
+    return INSIDER_OK;
 }
 }  // namespace
 
-void insider_hip_destroy(insider_hip_handle *h)
-{
-    if (!h) return;
-    (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    for (hipStream_t st : {h->side, h->side2, h->side3}) if (st) (void)hipStreamSynchronize(st);
-    if (h->comm) { (void)ncclCommDestroy(h->comm); h->comm = nullptr; }
-    clear_events(h);
-    free_workspace(h);
-    free_posthoc(h->post);
-    h->post = nullptr;
-    // the data set goes with its last user (insider_hip_clone shares it)
-    if (!h->data_refs || h->data_refs->fetch_sub(1) == 1) {
-        free_data_set(h);
-        delete h->data_refs;
-    }
-    destroy_streams(h);
-    delete h;
-}
+extern "C" {
+
+void insider_hip_destroy(insider_hip_handle *h) { delete h; }
 
 int insider_hip_clone(insider_hip_handle *src, insider_hip_handle **out)
 {
     if (!out) return fail(INSIDER_ERR_ARG, "out is null");
     *out = nullptr;
-    if (!src || !src->data_refs) return fail(INSIDER_ERR_ARG, "null handle");
-    HIPCHECK(hipSetDevice(src->device));
-    insider_hip_handle *h = new insider_hip_handle(*src);   // every data-set field and option; the rest is reset below
-    forget_workspace(h);                                    // (the copied pointers are the source's buffers)
-    h->post = nullptr;                                      // (likewise the post-hoc workspace)
-    h->stream = h->side = h->side2 = h->side3 = nullptr;
-    h->ev_prep = h->ev_c_ready = h->ev_head = h->ev_a_ready = h->ev_qfull = h->ev_qheld = nullptr;
-    h->ev_cd_done = h->ev_side_done = h->ev_tab = nullptr;
-    h->ev_w.clear();
-    for (auto *v : {&h->ev_col, &h->ev_row, &h->ev_cd, &h->ev_test}) v->clear();
-    h->side_pending = h->w_ready = h->qfull_pending = h->qheld_pending = false;
-    h->comm = nullptr;                                      // a sharded clone joins its own communicator (insider_hip_comm_init)
-    for (double &v : h->prof) v = 0.0;
-    h->steady_cd_ms = h->steady_col_ms = 0.0;
-    h->cap_hits = h->max_gene_sweeps = 0;
-    src->data_refs->fetch_add(1);
-    const hipError_t e = make_streams(h);
-    if (e != hipSuccess) {
-        insider_hip_destroy(h);
-        return fail(e == hipErrorOutOfMemory ? INSIDER_ERR_ALLOC : INSIDER_ERR_HIP, std::string("insider_hip_clone: ") + hipGetErrorString(e));
-    }
-    *out = h;
+    if (!src || !src->ds) return fail(INSIDER_ERR_ARG, "null handle");
+    HIPCHECK(hipSetDevice(src->ds->device));
+    // the data set, the options and the shard settings; a workspace, streams, diagnostics of its own (a sharded clone joins
+    // its own communicator: insider_hip_comm_init)
+    auto h = std::make_unique<insider_hip_handle>();
+    h->ds = src->ds;
+    h->opt = src->opt;
+    h->gene_offset = src->gene_offset;
+    h->rank = src->rank;
+    h->world = src->world;
+    h->allreduce = src->allreduce;
+    h->allreduce_user = src->allreduce_user;
+    if (int rc = h->st.create(stream_events(h->ds->c, h->ds->m))) return rc;
+    *out = h.release();
     return INSIDER_OK;
 }
 
@@ -1741,475 +2177,22 @@ int insider_hip_create_ex(const double *X, int64_t n, int64_t p, const int32_t *
     if (m < 0 || (m > 0 && !ctns)) { if (out) *out = nullptr; return fail(INSIDER_ERR_ARG, "bad continuous covariates"); }
     if (!out) return fail(INSIDER_ERR_ARG, "out is null");
     *out = nullptr;
-    if (!X || !levels || !n_levels || !M_train || !M_test) return fail(INSIDER_ERR_ARG, "null input");
-    if (n < 1 || p < 1 || c < 1) return fail(INSIDER_ERR_ARG, "n, p, c must be positive");
-    if (n > (1 << 30) || p > (1 << 30)) return fail(INSIDER_ERR_ARG, "dimension too large");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
-        return fail(INSIDER_ERR_NO_DEVICE, "no HIP device visible: libinsider_hip has no CPU fallback");
-    if (device < 0 || device >= ndev) return fail(INSIDER_ERR_ARG, "bad device ordinal");
-    // level ids must be exactly 1..L_i (src/optimize.cpp:175,286)
-    for (int i = 0; i < c; ++i) {
-        if (n_levels[i] < 1) return fail(INSIDER_ERR_ARG, "n_levels must be positive");
-        for (int64_t r = 0; r < n; ++r) {
-            const int32_t l = levels[r + (size_t)i * n];
-            if (l < 1 || l > n_levels[i]) return fail(INSIDER_ERR_ARG, "level ids must be within 1..L_i");
-        }
-    }
+    const CreateArgs a{X, n, p, levels, c, n_levels, ctns, m, M_train, M_test};
+    int rc = check_create_args(a, device);
+    if (rc) return rc;
     HIPCHECK(hipSetDevice(device));
-    insider_hip_handle *h = new insider_hip_handle();
-    h->device = device;
-    {
-        int cus = 0;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0) h->n_simd = 4 * cus;
-    }
-    h->n = n;
-    h->p = p;
-    h->c = c;
-    h->ldn = round_up(n, CHUNK);
-    h->ldp = round_up(p, CHUNK);
-    h->n_levels.assign(n_levels, n_levels + c);
-    h->lvl_off.assign(c + 1, 0);
-    for (int i = 0; i < c; ++i) h->lvl_off[i + 1] = h->lvl_off[i] + n_levels[i];
-    h->m = m;
-    h->SLcat = h->lvl_off[c];
-    h->SL = h->SLcat + m;
-    h->SLP = (int)round_up(h->SL, 2);
-    int rc = INSIDER_OK;
-#define CR(x) do { rc = (x); if (rc) { insider_hip_destroy(h); return rc; } } while (0)
-#define CH(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { insider_hip_destroy(h); \
-        return fail(e_ == hipErrorOutOfMemory ? INSIDER_ERR_ALLOC : INSIDER_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); } } while (0)
-    h->data_refs = new std::atomic<int>(1);
-    CH(make_streams(h));
-    // ---- X (gene-major lines of pitch ldn) and mask codes -------------------------------------------------
-    CR(dmalloc(&h->X, (size_t)p * h->ldn));
-    CR(dmalloc(&h->codes, (size_t)p * h->ldn));
-    CH(hipMemsetAsync(h->X, 0, (size_t)p * h->ldn * sizeof(double), h->stream));
-    CH(hipMemcpy2DAsync(h->X, h->ldn * sizeof(double), X, n * sizeof(double), n * sizeof(double), p,
-                        hipMemcpyHostToDevice, h->stream));
-    {
-        uint8_t *mtr = nullptr, *mte = nullptr;
-        CR(dmalloc(&mtr, (size_t)n * p));
-        CR(dmalloc(&mte, (size_t)n * p));
-        CH(hipMemcpyAsync(mtr, M_train, (size_t)n * p, hipMemcpyHostToDevice, h->stream));
-        CH(hipMemcpyAsync(mte, M_test, (size_t)n * p, hipMemcpyHostToDevice, h->stream));
-        hipLaunchKernelGGL(k_make_codes, dim3(cdiv(p * h->ldn, 256)), dim3(256), 0, h->stream, mtr, mte, n, p, h->ldn,
-                           h->codes);
-        CH(hipGetLastError());
-        CH(hipStreamSynchronize(h->stream));
-        (void)hipFree(mtr);
-        (void)hipFree(mte);
-    }
-    // ---- transposed copies for the row-side pass (sample-major lines of pitch ldp) --------------------------
-    CR(dmalloc(&h->Xt, (size_t)n * h->ldp));
-    CR(dmalloc(&h->codes_t, (size_t)n * h->ldp));
-    CH(hipMemsetAsync(h->Xt, 0, (size_t)n * h->ldp * sizeof(double), h->stream));
-    CH(hipMemsetAsync(h->codes_t, CODE_TRAIN, (size_t)n * h->ldp, h->stream));
-    {
-        dim3 grid(cdiv(n, 32), cdiv(p, 32));   // input: p lines (rows) x n columns
-        hipLaunchKernelGGL((k_transpose<double>), grid, dim3(256), 0, h->stream, (const double *)h->X, p, n, h->ldn,
-                           h->Xt, h->ldp);
-        hipLaunchKernelGGL((k_transpose<uint8_t>), grid, dim3(256), 0, h->stream, (const uint8_t *)h->codes, p, n,
-                           h->ldn, h->codes_t, h->ldp);
-        CH(hipGetLastError());
-    }
-    // ---- level tables ------------------------------------------------------------------------------------------
-    {
-        std::vector<int> lev0((size_t)c * n), members((size_t)c * n), lvl_ptr((size_t)h->SLcat + c), lvl_count(h->SLcat);
-        h->cov.resize(c);
-        for (int i = 0; i < c; ++i) {
-            const int L = n_levels[i];
-            std::vector<int> cnt(L, 0);
-            for (int64_t r = 0; r < n; ++r) {
-                const int l = levels[r + (size_t)i * n] - 1;
-                lev0[(size_t)i * n + r] = l;
-                cnt[l]++;
-            }
-            int *ptr = lvl_ptr.data() + h->lvl_off[i] + i;
-            ptr[0] = 0;
-            for (int l = 0; l < L; ++l) { ptr[l + 1] = ptr[l] + cnt[l]; lvl_count[h->lvl_off[i] + l] = cnt[l]; }
-            std::vector<int> fill(ptr, ptr + L);
-            for (int64_t r = 0; r < n; ++r) members[(size_t)i * n + fill[lev0[(size_t)i * n + r]]++] = (int)r;
-            // chunk tables for the two-stage level reduction
-            std::vector<int> ch_level, ch_begin, ch_end, lcp(L + 1, 0);
-            for (int l = 0; l < L; ++l) {
-                lcp[l] = (int)ch_level.size();
-                for (int b = ptr[l]; b < ptr[l + 1]; b += LEVEL_CHUNK) {
-                    ch_level.push_back(l);
-                    ch_begin.push_back(b);
-                    ch_end.push_back(std::min(b + LEVEL_CHUNK, ptr[l + 1]));
-                }
-            }
-            lcp[L] = (int)ch_level.size();
-            CovTables &ct = h->cov[i];
-            ct.L = L;
-            ct.nchunks = (int)ch_level.size();
-            h->max_chunks = std::max(h->max_chunks, ct.nchunks);
-            h->max_L = std::max(h->max_L, L);
-            CR(dmalloc(&ct.chunk_level, ch_level.size()));
-            CR(dmalloc(&ct.chunk_begin, ch_begin.size()));
-            CR(dmalloc(&ct.chunk_end, ch_end.size()));
-            CR(dmalloc(&ct.lvl_chunk_ptr, lcp.size()));
-            CH(hipMemcpy(ct.chunk_level, ch_level.data(), ch_level.size() * sizeof(int), hipMemcpyHostToDevice));
-            CH(hipMemcpy(ct.chunk_begin, ch_begin.data(), ch_begin.size() * sizeof(int), hipMemcpyHostToDevice));
-            CH(hipMemcpy(ct.chunk_end, ch_end.data(), ch_end.size() * sizeof(int), hipMemcpyHostToDevice));
-            CH(hipMemcpy(ct.lvl_chunk_ptr, lcp.data(), lcp.size() * sizeof(int), hipMemcpyHostToDevice));
-        }
-        CR(dmalloc(&h->lev, lev0.size()));
-        CR(dmalloc(&h->members_all, members.size()));
-        CR(dmalloc(&h->lvl_ptr_all, lvl_ptr.size()));
-        CR(dmalloc(&h->lvl_count_all, lvl_count.size()));
-        CR(dmalloc(&h->lvl_off_d, h->lvl_off.size()));
-        CH(hipMemcpy(h->lev, lev0.data(), lev0.size() * sizeof(int), hipMemcpyHostToDevice));
-        CH(hipMemcpy(h->members_all, members.data(), members.size() * sizeof(int), hipMemcpyHostToDevice));
-        CH(hipMemcpy(h->lvl_ptr_all, lvl_ptr.data(), lvl_ptr.size() * sizeof(int), hipMemcpyHostToDevice));
-        CH(hipMemcpy(h->lvl_count_all, lvl_count.data(), lvl_count.size() * sizeof(int), hipMemcpyHostToDevice));
-        CH(hipMemcpy(h->lvl_off_d, h->lvl_off.data(), h->lvl_off.size() * sizeof(int), hipMemcpyHostToDevice));
-    }
-    // ---- continuous covariates: one pseudo-level whose members are all samples, weighted by z ----------------------------
-    if (m > 0) {
-        CR(dmalloc(&h->Zc, (size_t)m * n));
-        CH(hipMemcpy(h->Zc, ctns, (size_t)m * n * sizeof(double), hipMemcpyHostToDevice));   // n x m column-major == m x n rows
-        std::vector<int> ident(n), cb, ce, lcp(2, 0);
-        for (int64_t r = 0; r < n; ++r) ident[r] = (int)r;
-        for (int64_t b0 = 0; b0 < n; b0 += LEVEL_CHUNK) { cb.push_back((int)b0); ce.push_back((int)std::min<int64_t>(b0 + LEVEL_CHUNK, n)); }
-        lcp[1] = (int)cb.size();
-        h->cont.L = 1;
-        h->cont.nchunks = (int)cb.size();
-        h->max_chunks = std::max(h->max_chunks, h->cont.nchunks);
-        h->max_L = std::max(h->max_L, 1);
-        CR(dmalloc(&h->ident_members, ident.size()));
-        CR(dmalloc(&h->cont.chunk_begin, cb.size()));
-        CR(dmalloc(&h->cont.chunk_end, ce.size()));
-        CR(dmalloc(&h->cont.lvl_chunk_ptr, lcp.size()));
-        CR(dmalloc(&h->one_count, 1));
-        const int one = 1;
-        CH(hipMemcpy(h->ident_members, ident.data(), ident.size() * sizeof(int), hipMemcpyHostToDevice));
-        CH(hipMemcpy(h->cont.chunk_begin, cb.data(), cb.size() * sizeof(int), hipMemcpyHostToDevice));
-        CH(hipMemcpy(h->cont.chunk_end, ce.data(), ce.size() * sizeof(int), hipMemcpyHostToDevice));
-        CH(hipMemcpy(h->cont.lvl_chunk_ptr, lcp.data(), lcp.size() * sizeof(int), hipMemcpyHostToDevice));
-        CH(hipMemcpy(h->one_count, &one, sizeof(int), hipMemcpyHostToDevice));
-    }
-    // ---- factor-independent statistics -----------------------------------------------------------------------------
-    CR(dmalloc(&h->S, (size_t)p * h->SLP));
-    CR(dmalloc(&h->yy_train, (size_t)p));
-    CR(dmalloc(&h->yy_all, (size_t)p));
-    CH(hipMemsetAsync(h->S, 0, (size_t)p * h->SLP * sizeof(double), h->stream));
-    {
-        unsigned long long *cnt = nullptr;
-        CR(dmalloc(&cnt, 2));
-        CH(hipMemsetAsync(cnt, 0, 2 * sizeof(unsigned long long), h->stream));
-        hipLaunchKernelGGL(k_line_sumsq, dim3(cdiv(p, 4)), dim3(256), 0, h->stream, (const double *)h->X,
-                           (const uint8_t *)h->codes, h->ldn, (int)n, (int)p, h->yy_train, h->yy_all, cnt);
-        hipLaunchKernelGGL(k_level_sums, dim3(cdiv(p * h->SLcat, 256)), dim3(256), 0, h->stream, (const double *)h->X,
-                           (const uint8_t *)nullptr, h->ldn, (int)p, (const int *)h->members_all,
-                           (const int *)h->lvl_ptr_all, (const int *)h->lvl_off_d, c, (int)n, h->SLcat, h->SLP, h->S);
-        {   // train-only sums for the merged masked row update / the factored column statistics (the categorical columns)
-            CR(dmalloc(&h->Strain, (size_t)p * h->SLP));
-            CH(hipMemsetAsync(h->Strain, 0, (size_t)p * h->SLP * sizeof(double), h->stream));
-            hipLaunchKernelGGL(k_level_sums, dim3(cdiv(p * h->SLcat, 256)), dim3(256), 0, h->stream, (const double *)h->X,
-                               (const uint8_t *)h->codes, h->ldn, (int)p, (const int *)h->members_all,
-                               (const int *)h->lvl_ptr_all, (const int *)h->lvl_off_d, c, (int)n, h->SLcat, h->SLP,
-                               h->Strain);
-        }
-        if (m > 0)
-            hipLaunchKernelGGL(k_cont_sums, dim3(cdiv(p * m, 256)), dim3(256), 0, h->stream, (const double *)h->X, h->ldn,
-                               (int)p, (const double *)h->Zc, m, (int)n, h->SLcat, h->SLP, h->S);
-        CH(hipGetLastError());
-        unsigned long long hc[2];
-        CH(hipMemcpyAsync(hc, cnt, sizeof(hc), hipMemcpyDeviceToHost, h->stream));
-        CH(hipStreamSynchronize(h->stream));
-        (void)hipFree(cnt);
-        h->cnt_train = (double)hc[0];
-        h->cnt_test = (double)hc[1];
-        h->no_na = hc[0] + hc[1] == (unsigned long long)n * (unsigned long long)p;
-    }
-    // ---- held-out lists of both sides (the masks never change: built once) -------------------------------------------
-    if (n >= LIST_PAD || p >= LIST_PAD) { insider_hip_destroy(h); return fail(INSIDER_ERR_UNSUPPORTED, "n and p must be below 2^23"); }
-    for (int side = 0; side < 2; ++side) {
-        const bool cols = side == 0;
-        const int lines = cols ? (int)p : (int)n, len = cols ? (int)n : (int)p;
-        const double *vals = cols ? h->X : h->Xt;
-        const uint8_t *cds = cols ? h->codes : h->codes_t;
-        const int64_t pitch = cols ? h->ldn : h->ldp;
-        int *cnt_d = nullptr;
-        CR(dmalloc(&cnt_d, (size_t)lines));
-        hipLaunchKernelGGL(k_count_heldout, dim3(cdiv(lines, 4)), dim3(256), 0, h->stream, cds, pitch, len, lines, cnt_d);
-        CH(hipGetLastError());
-        std::vector<int> cnt(lines);
-        CH(hipMemcpyAsync(cnt.data(), cnt_d, (size_t)lines * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-        CH(hipStreamSynchronize(h->stream));
-        (void)hipFree(cnt_d);
-        std::vector<uint32_t> ptr((size_t)lines + 1);
-        uint64_t tot = 0;
-        for (int i = 0; i < lines; ++i) { ptr[i] = (uint32_t)tot; tot += (uint64_t)round_up(cnt[i], LIST_ALIGN); }
-        ptr[lines] = (uint32_t)tot;
-        if (tot >= (1ull << 32)) { insider_hip_destroy(h); return fail(INSIDER_ERR_UNSUPPORTED, "more than 2^32 held-out entries"); }
-        uint32_t *&dptr = cols ? h->col_ptr : h->row_ptr;
-        int *&didx = cols ? h->col_idx : h->row_idx;
-        double *&dval = cols ? h->col_val : h->row_val;
-        (cols ? h->col_entries : h->row_entries) = tot;
-        CR(dmalloc(&dptr, ptr.size()));
-        CR(dmalloc(&didx, (size_t)tot + LIST_BLOCK));
-        CR(dmalloc(&dval, (size_t)tot + LIST_BLOCK));
-        CH(hipMemcpyAsync(dptr, ptr.data(), ptr.size() * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
-        uint8_t *dflag = nullptr;
-        if (cols && !h->no_na) { CR(dmalloc(&h->col_flag, (size_t)tot + LIST_BLOCK)); dflag = h->col_flag; }
-        hipLaunchKernelGGL(k_fill_lists, dim3(cdiv(lines, 4)), dim3(256), 0, h->stream, vals, cds, pitch, len, lines,
-                           (const uint32_t *)dptr, didx, dval, dflag);
-        CH(hipGetLastError());
-        CH(hipStreamSynchronize(h->stream));
-    }
-    // ---- merged masked row update: per covariate, the genes' held-out samples grouped by level, the (gene, count)
-    // lists of every level and the level-pair sample counts (insider_row_merged.hpp) -------------------------------------
-    // (k_gene_u keeps a gene's SLcat look-up values per wave in LDS: beyond ~1500 stacked levels the per-sample path stays)
-    // (with continuous covariates, m <= 4: the same tables serve the pair-count column statistics, ColFacArgs::zt)
-    if (m <= 4 && (size_t)4 * (h->SLcat + GU_TILE) * sizeof(double) <= 64 * 1024) {
-        constexpr uint32_t SEG = 1024;   // list entries per weighted-SYRK work item (multiple of LIST_ALIGN)
-        std::vector<int> lev0((size_t)c * n);
-        CH(hipMemcpy(lev0.data(), h->lev, lev0.size() * sizeof(int), hipMemcpyDeviceToHost));
-        for (int i = 0; i < c; ++i) {
-            CovTables &ct = h->cov[i];
-            const int L = ct.L;
-            CR(dmalloc(&ct.grp, (size_t)p * (L + 1)));
-            const size_t plane = (size_t)h->col_entries + LIST_BLOCK;
-            if (h->SLcat > 65535) { insider_hip_destroy(h); return fail(INSIDER_ERR_UNSUPPORTED, "more than 65535 levels in total"); }
-            CR(dmalloc(&ct.slev, plane * (size_t)std::max(c - 1, 1)));
-            const size_t lds = (size_t)4 * L * sizeof(int);
-            if (lds > 60 * 1024) { insider_hip_destroy(h); return fail(INSIDER_ERR_UNSUPPORTED, "a covariate has more than 3840 levels"); }
-            hipLaunchKernelGGL(k_group_count, dim3(cdiv(p, 4)), dim3(256), lds, h->stream, (const uint32_t *)h->col_ptr,
-                               (const int *)h->col_idx, (const int *)(h->lev + (size_t)i * n), L, (int)p, ct.grp);
-            hipLaunchKernelGGL(k_group_fill, dim3(cdiv(p, 4)), dim3(256), lds, h->stream, (const uint32_t *)h->col_ptr,
-                               (const int *)h->col_idx, (const int *)h->lev, (const int *)h->lvl_off_d, c, (int)n, i, L,
-                               (int)p, (const uint32_t *)ct.grp, ct.slev, plane);
-            CH(hipGetLastError());
-            std::vector<uint32_t> grp((size_t)p * (L + 1));
-            CH(hipMemcpyAsync(grp.data(), ct.grp, grp.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-            CH(hipStreamSynchronize(h->stream));
-            // (gene, count) list of every level, padded to LIST_ALIGN; work items of at most SEG entries
-            std::vector<int> widx, lip(L + 1, 0);
-            std::vector<double> ww;
-            std::vector<uint32_t> ib, ie;
-            for (int l = 0; l < L; ++l) {
-                lip[l] = (int)ib.size();
-                const size_t start = widx.size();
-                for (int64_t j = 0; j < p; ++j) {
-                    const uint32_t cnt = grp[(size_t)j * (L + 1) + l + 1] - grp[(size_t)j * (L + 1) + l];
-                    if (cnt) { widx.push_back((int)j); ww.push_back((double)cnt); }
-                }
-                while ((widx.size() - start) % LIST_ALIGN) { widx.push_back(LIST_PAD); ww.push_back(0.0); }
-                for (size_t b = start; b < widx.size(); b += SEG) {
-                    ib.push_back((uint32_t)b);
-                    ie.push_back((uint32_t)std::min(b + SEG, widx.size()));
-                }
-            }
-            lip[L] = (int)ib.size();
-            if (widx.size() >= (1ull << 32)) { insider_hip_destroy(h); return fail(INSIDER_ERR_UNSUPPORTED, "level lists too long"); }
-            ct.nitems = (int)ib.size();
-            ct.npairs = 0;
-            for (double wv : ww) ct.npairs += wv != 0.0;
-            h->max_items = std::max(h->max_items, ct.nitems);
-            CR(dmalloc(&ct.wl_idx, widx.size() + LIST_BLOCK));
-            CR(dmalloc(&ct.wl_w, ww.size() + LIST_BLOCK));
-            CR(dmalloc(&ct.item_begin, ib.size() + 1));
-            CR(dmalloc(&ct.item_end, ie.size() + 1));
-            CR(dmalloc(&ct.lvl_item_ptr, lip.size()));
-            CH(hipMemcpy(ct.wl_idx, widx.data(), widx.size() * sizeof(int), hipMemcpyHostToDevice));
-            CH(hipMemcpy(ct.wl_w, ww.data(), ww.size() * sizeof(double), hipMemcpyHostToDevice));
-            CH(hipMemcpy(ct.item_begin, ib.data(), ib.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-            CH(hipMemcpy(ct.item_end, ie.data(), ie.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-            CH(hipMemcpy(ct.lvl_item_ptr, lip.data(), lip.size() * sizeof(int), hipMemcpyHostToDevice));
-            // samples per (level of covariate i, stacked level of another covariate): sum_{r in l} s_r = paircnt A
-            // (+ m columns sum_{r in l} z_rk: a continuous column is a stacked "level" with real-valued counts)
-            std::vector<double> pc((size_t)L * h->SL, 0.0);
-            for (int64_t r = 0; r < n; ++r) {
-                const int l = lev0[(size_t)i * n + r];
-                for (int q = 0; q < c; ++q)
-                    if (q != i) pc[(size_t)l * h->SL + h->lvl_off[q] + lev0[(size_t)q * n + r]] += 1.0;
-                for (int k = 0; k < m; ++k) pc[(size_t)l * h->SL + h->SLcat + k] += ctns[(size_t)k * n + r];
-            }
-            CR(dmalloc(&ct.paircnt, pc.size()));
-            CH(hipMemcpy(ct.paircnt, pc.data(), pc.size() * sizeof(double), hipMemcpyHostToDevice));
-        }
-        h->merged = true;
-        // ---- factored column statistics: covariates by decreasing level count, the planes of the later ones ----------
-        CR(dmalloc(&h->Sheld, (size_t)p * h->SLP));
-        hipLaunchKernelGGL(k_sub, dim3(cdiv((int64_t)p * h->SLP, 256)), dim3(256), 0, h->stream, (const double *)h->S,
-                           (const double *)h->Strain, (size_t)p * h->SLP, h->Sheld);
-        CH(hipGetLastError());
-        if (c <= CF_MAXC) {
-            std::vector<int> ord(c);
-            for (int i = 0; i < c; ++i) ord[i] = i;
-            std::stable_sort(ord.begin(), ord.end(), [&](int x, int y) { return n_levels[x] > n_levels[y]; });
-            ColFacArgs &cf = h->cf;
-            cf.p = (int)p;
-            cf.c = c;
-            cf.plane = (size_t)h->col_entries + LIST_BLOCK;
-            for (int t = 0; t < c; ++t) {
-                const int o = ord[t];
-                h->cf_pos[o] = t;
-                cf.grp[t] = h->cov[o].grp;
-                cf.slev[t] = h->cov[o].slev;
-                cf.L[t] = n_levels[o];
-                cf.off[t] = h->lvl_off[o];
-                cf.nlater[t] = c - 1 - t;
-                for (int k = t + 1; k < c; ++k) cf.later_plane[t][k - t - 1] = ord[k] < o ? ord[k] : ord[k] - 1;
-            }
-            cf.tab_skip_lo = h->lvl_off[ord[0]];
-            cf.tab_skip_n = n_levels[ord[0]];
-            cf.tab_rows = h->SLcat - cf.tab_skip_n;
-            // pair-count form: the dense per-gene count tables (one byte per cell), when they are small enough
-            cf.nsteps = (cf.tab_rows + 3) / 4;
-            bool fits = cf.nsteps <= CP_MAXSTEPS;
-            int off = 0;
-            for (int t = 0; t < c; ++t) {
-                const int cells = ((cf.L[t] + 15) / 16) * 64 * (cf.nsteps <= 4 ? 4 : 8);   // bytes: 4 or 8 per lane and block
-                cf.cnt_off[t] = off;
-                if (cf.nlater[t] > 0) off += cells;
-            }
-            cf.cnt_stride = off;
-            cf.cnt = nullptr;
-            if (fits && off <= 64 * 1024 && (size_t)p * (size_t)off <= ((size_t)1 << 32)) {   // <= 64 KB of counts per gene
-                int *ovf = nullptr;
-                if (off > 0) {
-                    CR(dmalloc(&h->cf_cnt, (size_t)p * off));
-                    CR(dmalloc(&ovf, 1));
-                    CH(hipMemsetAsync(ovf, 0, sizeof(int), h->stream));
-                    hipLaunchKernelGGL((k_pair_count_build<2>), dim3(cdiv(p, 2)), dim3(128), 0, h->stream, cf, h->cf_cnt, ovf);
-                    CH(hipGetLastError());
-                    int hv = 0;
-                    CH(hipMemcpyAsync(&hv, ovf, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-                    CH(hipStreamSynchronize(h->stream));
-                    (void)hipFree(ovf);
-                    fits = hv == 0;
-                }
-                if (fits && n < ((int64_t)1 << 24)) {   // (1/2 n as a float is exact)
-                    int hoff = 0;
-                    for (int t = 0; t < c; ++t) {
-                        cf.hn_off[t] = hoff;
-                        hoff += ((cf.L[t] + 15) / 16) * 16;
-                    }
-                    cf.hn_stride = hoff;
-                    CR(dmalloc(&h->cf_hn, (size_t)(p + 4) * hoff));   // + 4 zero rows: k_wgemm reads whole steps of four genes
-                    CH(hipMemsetAsync(h->cf_hn, 0, (size_t)(p + 4) * hoff * sizeof(float), h->stream));
-                    hipLaunchKernelGGL(k_half_counts, dim3((unsigned)cdiv((int64_t)p * hoff, 256)), dim3(256), 0, h->stream, cf,
-                                       h->cf_hn);
-                    CH(hipGetLastError());
-                } else {
-                    fits = false;
-                }
-                h->cf_pair_ok = fits;
-            }
-            cf.zt = nullptr;
-            cf.m = m;
-            cf.SLcat = h->SLcat;
-            for (int t = 0; t < c; ++t) cf.pos_cov[t] = ord[t];
-            // The merged row update with continuous columns takes u_j from k_gene_u_cnt ALONE (only it adds the term of the
-            // real-valued counts, ColFacArgs::zt; k_gene_u reads the categorical columns of V only): every covariate's launch
-            // of it must fit its per-wave LDS record — V row [SL] | out [LP] | GU_BATCH x 64 partial sums, four waves per block
-            // — or the whole data set stays on the per-sample / per-entry paths (a covariate with ~770 levels or more).
-            bool gu_fits = true;
-            for (int t = 0; t < c; ++t)
-                gu_fits = gu_fits && (size_t)4 * (h->SL + round_up(h->n_levels[t], 2) + GU_BATCH * WAVE) * sizeof(double) <= 64 * 1024;
-            if (m > 0 && h->cf_pair_ok && gu_fits) {
-                // continuous covariates on the pair-count form: one more position (the m columns as pseudo-levels, no count
-                // bytes, 1/2 n = 0: sixteen more zero floats per gene would do, the block reads what follows its offset ->
-                // its own zero region) and the real-valued count table
-                cf.L[c] = m;
-                cf.off[c] = h->SLcat;
-                cf.nlater[c] = 0;
-                cf.cnt_off[c] = 0;
-                int zoff = 0;
-                for (int t = 0; t < c; ++t) { cf.zt_off[t] = zoff; zoff += ((cf.L[t] + 15) / 16) * 64; }
-                cf.zt_off[c] = zoff;
-                cf.zt_stride = zoff + 64;
-                // 1/2 n of position c: a zero region behind the table (rebuilt with the longer stride)
-                (void)hipFree(h->cf_hn);
-                h->cf_hn = nullptr;
-                cf.hn_off[c] = cf.hn_stride;
-                cf.hn_stride += 16;
-                CR(dmalloc(&h->cf_hn, (size_t)(p + 4) * cf.hn_stride));
-                CH(hipMemsetAsync(h->cf_hn, 0, (size_t)(p + 4) * cf.hn_stride * sizeof(float), h->stream));
-                hipLaunchKernelGGL(k_half_counts, dim3((unsigned)cdiv((int64_t)p * cf.hn_stride, 256)), dim3(256), 0, h->stream, cf,
-                                   h->cf_hn);
-                CH(hipGetLastError());
-                CR(dmalloc(&h->cf_zt, (size_t)p * cf.zt_stride));
-                CH(hipMemsetAsync(h->cf_zt, 0, (size_t)p * cf.zt_stride * sizeof(double), h->stream));
-                // (Sheld's continuous columns: sum over the held-out entries of x z, next to S - S^train of the categorical ones)
-                hipLaunchKernelGGL(k_zt_build, dim3(cdiv(p, 4)), dim3(256), 0, h->stream, cf, (const uint32_t *)h->col_ptr,
-                                   (const int *)h->col_idx, (const double *)h->col_val, (const int *)h->lev, (const double *)h->Zc,
-                                   (int)n, h->cf_zt, h->Sheld, h->SLP, (const double *)h->S, h->Strain);
-                CH(hipGetLastError());
-                CH(hipStreamSynchronize(h->stream));
-                // ---- the continuous columns as one-level covariates of the merged row update ----
-                h->contm.assign(m, CovTables());
-                const size_t plen_l = (size_t)round_up(p, LIST_ALIGN);
-                std::vector<int> widx(plen_l, LIST_PAD);
-                for (int64_t j = 0; j < p; ++j) widx[j] = (int)j;
-                std::vector<uint32_t> ib, ie;
-                for (size_t b = 0; b < plen_l; b += SEG) { ib.push_back((uint32_t)b); ie.push_back((uint32_t)std::min(b + SEG, plen_l)); }
-                const int lip[2] = {0, (int)ib.size()};
-                int *d_idx = nullptr, *d_lip = nullptr;
-                uint32_t *d_ib = nullptr, *d_ie = nullptr;
-                // (owned by contm[0] from the moment they exist: free_data_set releases them on every error path below)
-                CR(dmalloc(&d_idx, plen_l + LIST_BLOCK));
-                h->contm[0].wl_idx = d_idx;
-                CR(dmalloc(&d_ib, ib.size() + 1));
-                h->contm[0].item_begin = d_ib;
-                CR(dmalloc(&d_ie, ie.size() + 1));
-                h->contm[0].item_end = d_ie;
-                CR(dmalloc(&d_lip, 2));
-                h->contm[0].lvl_item_ptr = d_lip;
-                CH(hipMemcpy(d_idx, widx.data(), plen_l * sizeof(int), hipMemcpyHostToDevice));
-                CH(hipMemcpy(d_ib, ib.data(), ib.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-                CH(hipMemcpy(d_ie, ie.data(), ie.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-                CH(hipMemcpy(d_lip, lip, sizeof(lip), hipMemcpyHostToDevice));
-                h->max_items = std::max(h->max_items, (int)ib.size());
-                std::vector<double> zz((size_t)m * m, 0.0);
-                for (int k = 0; k < m; ++k)
-                    for (int k2 = 0; k2 < m; ++k2) {
-                        double acc = 0.0;
-                        for (int64_t r = 0; r < n; ++r) acc += ctns[(size_t)k * n + r] * ctns[(size_t)k2 * n + r];
-                        zz[(size_t)k * m + k2] = acc;
-                    }
-                std::vector<double> cc(m);
-                for (int k = 0; k < m; ++k) {
-                    CovTables &ct = h->contm[k];
-                    ct.L = 1;
-                    ct.wl_idx = d_idx;
-                    ct.item_begin = d_ib;
-                    ct.item_end = d_ie;
-                    ct.lvl_item_ptr = d_lip;
-                    ct.nitems = (int)ib.size();
-                    ct.npairs = p;
-                    CR(dmalloc(&ct.wl_w, plen_l + LIST_BLOCK));
-                    CH(hipMemsetAsync(ct.wl_w, 0, (plen_l + LIST_BLOCK) * sizeof(double), h->stream));
-                    hipLaunchKernelGGL(k_cont_weights, dim3(cdiv(p, 256)), dim3(256), 0, h->stream, (const double *)h->cf_zt, cf.zt_stride,
-                                       cf.zt_off[c], k, (int)p, ct.wl_w);
-                    CH(hipGetLastError());
-                    std::vector<double> pc((size_t)h->SL, 0.0);
-                    for (int64_t r = 0; r < n; ++r)
-                        for (int q = 0; q < c; ++q) pc[h->lvl_off[q] + lev0[(size_t)q * n + r]] += ctns[(size_t)k * n + r];
-                    for (int k2 = 0; k2 < m; ++k2) pc[h->SLcat + k2] = k2 == k ? 0.0 : zz[(size_t)k * m + k2];
-                    CR(dmalloc(&ct.paircnt, pc.size()));
-                    CH(hipMemcpy(ct.paircnt, pc.data(), pc.size() * sizeof(double), hipMemcpyHostToDevice));
-                    cc[k] = zz[(size_t)k * m + k];
-                }
-                CR(dmalloc(&h->cont_cnt, (size_t)m));
-                CH(hipMemcpy(h->cont_cnt, cc.data(), (size_t)m * sizeof(double), hipMemcpyHostToDevice));
-                CH(hipStreamSynchronize(h->stream));
-                h->cont_merged = true;
-            }
-        }
-    }
-    // the transposed copies were only needed to build the row-side lists
-    (void)hipFree(h->Xt);
-    (void)hipFree(h->codes_t);
-    h->Xt = nullptr;
-    h->codes_t = nullptr;
-#undef CR
-#undef CH
-    *out = h;
+    // (d before h: on an error the handle drains its streams before the data set's buffers go)
+    auto d = std::make_shared<DataSet>();
+    auto h = std::make_unique<insider_hip_handle>();
+    describe(*d, a, device);
+    if ((rc = h->st.create(stream_events(c, m)))) return rc;
+    const hipStream_t st = h->st.stream;
+    if ((rc = stage_matrix(*d, a, st)) || (rc = stage_levels(*d, a)) || (rc = stage_continuous(*d, a)) ||
+        (rc = stage_sums(*d, a, st)) || (rc = stage_lists(*d, a, st)) || (rc = stage_merged(*d, a, st)) ||
+        (rc = stage_factored(*d, a, st)) || (rc = stage_cont_factored(*d, a, st)))
+        return rc;
+    h->ds = std::move(d);
+    *out = h.release();
     return INSIDER_OK;
 }
 
@@ -2220,7 +2203,7 @@ int insider_hip_set_shard(insider_hip_handle *h, int64_t gene_offset, int rank, 
     // world > 1 without a callback is completed by insider_hip_comm_init(); optimize() refuses to run with neither.
     // Installing a callback drops a communicator of an earlier insider_hip_comm_init(): the callback is then the exchange.
     if (fn && h->comm) {
-        (void)hipSetDevice(h->device);
+        (void)hipSetDevice(h->ds->device);
         (void)ncclCommDestroy(h->comm);
         h->comm = nullptr;
     }
@@ -2247,7 +2230,7 @@ int insider_hip_comm_init(insider_hip_handle *h, const void *unique_id, int rank
 {
     if (!h || !unique_id || world < 1 || rank < 0 || rank >= world) return fail(INSIDER_ERR_ARG, "bad communicator arguments");
     if (h->world != world || h->rank != rank) return fail(INSIDER_ERR_ARG, "rank / world differ from insider_hip_set_shard()");
-    HIPCHECK(hipSetDevice(h->device));
+    HIPCHECK(hipSetDevice(h->ds->device));
     if (h->comm) { (void)ncclCommDestroy(h->comm); h->comm = nullptr; }
     ncclUniqueId id;
     std::memcpy(&id, unique_id, sizeof(id));
@@ -2260,27 +2243,31 @@ int insider_hip_set_option(insider_hip_handle *h, const char *name, double value
 {
     if (!h || !name) return fail(INSIDER_ERR_ARG, "null");
     const std::string s(name);
-    if (s == "max_sweeps") h->max_sweeps = value < 1 ? 1 : (int)value;
-    else if (s == "order_mode") h->order_mode = (int)value;
-    else if (s == "profile") h->profile = (int)value;
-    else if (s == "verbose") h->verbose = (int)value;
-    else if (s == "force_allreduce") h->force_allreduce = (int)value;   // call the all-reduce callback even when world == 1
-    else if (s == "col_factored") h->col_factored = (int)value;   // 1 = cost model picks list / look-up / pair-count form (default), 2 = look-up form, 3 = pair-count form, 0 = k_list_stats
-    else if (s == "row_counts") h->row_counts = (int)value;   // 1 = the merged row update takes u from the dense pair counts when they exist (default), 0 = from the entry lists
-    else if (s == "row_merged") h->row_merged = (int)value;   // 1 = merged masked row update when the time model favours it (default), 2 = always, 0 = per-sample statistics
-    else if (s == "row_gemm_waves") { h->wg_waves = std::max(64, (int)value); h->K = 0; }   // (re-plans the workspace)
-    else if (s == "row_gemm") h->row_gemm = (int)value;       // 1 (default) = k_wgemm for covariates with >= 49 levels, 0 = k_wsyrk everywhere
-    else if (s == "row_fused") h->row_fused = (int)value;     // 1 (default) = k_level_merged (one launch per covariate), 0 = k_level_pack / k_level_reduce / k_level_solve
-    else if (s == "cd_cold_iters") h->cd_cold_iters = (int)value;   // outer iterations 0 .. value-1 of a call solve in passes
-    else if (s == "cd_pass1") h->cd_pass_first = (int)value;        // sweep index where the first pass stops (0 = single pass)
-    else if (s == "cd_pass_ratio") h->cd_pass_ratio = (int)value;   // each further pass stops at ratio x the previous limit
-    else if (s == "list_fine") h->list_fine = (int)value;       // 1 (default) = per-entry statistics on v_mfma_f64_4x4x4 for 16 <= K <= 31, 0 = on 16x16x4
-    else if (s == "mm_fast") h->mm_fast = (int)value;             // 0 = k_mm_rows / k_mm_reduce as in round 4
-    else if (s == "col_mfma4") h->col_mfma4 = (int)value;         // 1 = k_col_paircnt4 (K <= 31, factor rows fit LDS), 0 = k_col_paircnt
-    else if (s == "cd_pairs") h->cd_pairs = (int)value;           // 1 (default) = sweeps routed through the blocks of two coordinate steps (K <= 30; same iterates), 0 = one step per block
-    else if (s == "resid_stage_mb") h->resid_stage_mb = value;   // device buffer insider_hip_residual() copies out through (MB; at least 16 genes of the window)
-    else if (s == "vd_stage_kb") h->vd_stage_kb = value;         // LDS budget (KiB, default 48, at most 60) of the staged level tables of k_vd_stats (0 = always the global form)
-    else if (s == "cd_variant") h->cd_variant = (int)value;   // 0 = register-resident (4 genes per wave; K <= 32, and 32 < K <= 48 with the third slot's columns in LDS), 1 = group kernel, 2 = row16 (LDS, K <= 48)
+    if (s == "max_sweeps") h->opt.max_sweeps = value < 1 ? 1 : (int)value;
+    else if (s == "order_mode") h->opt.order_mode = (int)value;
+    else if (s == "profile") h->opt.profile = (int)value;
+    else if (s == "verbose") h->opt.verbose = (int)value;
+    else if (s == "force_allreduce") h->opt.force_allreduce = (int)value;   // call the all-reduce callback even when world == 1
+    else if (s == "col_factored") h->opt.col_factored = (int)value;   // 1 = cost model picks list / look-up / pair-count form (default), 2 = look-up form, 3 = pair-count form, 0 = k_list_stats
+    else if (s == "row_counts") h->opt.row_counts = (int)value;   // 1 = the merged row update takes u from the dense pair counts when they exist (default), 0 = from the entry lists
+    else if (s == "row_merged") h->opt.row_merged = (int)value;   // 1 = merged masked row update when the time model favours it (default), 2 = always, 0 = per-sample statistics
+    else if (s == "row_gemm_waves") {   // (re-plans the workspace: the next call builds it anew)
+        h->opt.wg_waves = std::max(64, (int)value);
+        HIPCHECK(hipSetDevice(h->ds->device));
+        h->ws = Workspace();
+    }
+    else if (s == "row_gemm") h->opt.row_gemm = (int)value;       // 1 (default) = k_wgemm for covariates with >= 49 levels, 0 = k_wsyrk everywhere
+    else if (s == "row_fused") h->opt.row_fused = (int)value;     // 1 (default) = k_level_merged (one launch per covariate), 0 = k_level_pack / k_level_reduce / k_level_solve
+    else if (s == "cd_cold_iters") h->opt.cd_cold_iters = (int)value;   // outer iterations 0 .. value-1 of a call solve in passes
+    else if (s == "cd_pass1") h->opt.cd_pass_first = (int)value;        // sweep index where the first pass stops (0 = single pass)
+    else if (s == "cd_pass_ratio") h->opt.cd_pass_ratio = (int)value;   // each further pass stops at ratio x the previous limit
+    else if (s == "list_fine") h->opt.list_fine = (int)value;       // 1 (default) = per-entry statistics on v_mfma_f64_4x4x4 for 16 <= K <= 31, 0 = on 16x16x4
+    else if (s == "mm_fast") h->opt.mm_fast = (int)value;             // 0 = k_mm_rows / k_mm_reduce as in round 4
+    else if (s == "col_mfma4") h->opt.col_mfma4 = (int)value;         // 1 = k_col_paircnt4 (K <= 31, factor rows fit LDS), 0 = k_col_paircnt
+    else if (s == "cd_pairs") h->opt.cd_pairs = (int)value;           // 1 (default) = sweeps routed through the blocks of two coordinate steps (K <= 30; same iterates), 0 = one step per block
+    else if (s == "resid_stage_mb") h->opt.resid_stage_mb = value;   // device buffer insider_hip_residual() copies out through (MB; at least 16 genes of the window)
+    else if (s == "vd_stage_kb") h->opt.vd_stage_kb = value;         // LDS budget (KiB, default 48, at most 60) of the staged level tables of k_vd_stats (0 = always the global form)
+    else if (s == "cd_variant") h->opt.cd_variant = (int)value;   // 0 = register-resident (4 genes per wave; K <= 32, and 32 < K <= 48 with the third slot's columns in LDS), 1 = group kernel, 2 = row16 (LDS, K <= 48)
     else return fail(INSIDER_ERR_ARG, "unknown option " + s);
     return INSIDER_OK;
 }
@@ -2292,11 +2279,11 @@ static int optimize_body(insider_hip_handle *h, double *const *A, double *C, int
 {
     int rc = check_factor_args(h, A, C, inc_continuous, tuning);
     if (rc) return rc;
-    HIPCHECK(hipSetDevice(h->device));
+    HIPCHECK(hipSetDevice(h->ds->device));
     // work a failed earlier call may have left on the side streams must not race with this call's
-    HIPCHECK(hipStreamSynchronize(h->side));
-    HIPCHECK(hipStreamSynchronize(h->side2));
-    HIPCHECK(hipStreamSynchronize(h->side3));
+    HIPCHECK(hipStreamSynchronize(h->st.side));
+    HIPCHECK(hipStreamSynchronize(h->st.side2));
+    HIPCHECK(hipStreamSynchronize(h->st.side3));
     if ((rc = ensure_workspace(h, K))) return rc;
     const auto t_begin = std::chrono::steady_clock::now();
     clear_events(h);
@@ -2330,17 +2317,17 @@ static int optimize_body(insider_hip_handle *h, double *const *A, double *C, int
 
     uint32_t iter = 0;
     unsigned long long sweeps_total = 0;
-    HIPCHECK(hipMemsetAsync(h->sweep_total, 0, 256 * sizeof(unsigned long long), h->stream));
-    HIPCHECK(hipMemsetAsync(h->failflag + 2, 0, 2 * sizeof(int), h->stream));
-    if (alpha != 0.0 && !h->have_perm && !h->have_early[0]) {   // no history on this handle: order the genes by sum of squares
-        hipLaunchKernelGGL(k_yy_key, dim3(cdiv(h->p, 256)), dim3(256), 0, h->stream,
-                           (const double *)(masked ? h->yy_train : h->yy_all), (int)h->p, h->sweep_key);
+    HIPCHECK(hipMemsetAsync(h->ws.sweep_total, 0, 256 * sizeof(unsigned long long), h->st.stream));
+    HIPCHECK(hipMemsetAsync(h->ws.failflag + 2, 0, 2 * sizeof(int), h->st.stream));
+    if (alpha != 0.0 && !h->ws.have_perm && !h->ws.have_early[0]) {   // no history on this handle: order the genes by sum of squares
+        hipLaunchKernelGGL(k_yy_key, dim3(cdiv(h->ds->p, 256)), dim3(256), 0, h->st.stream,
+                           (const double *)(masked ? h->ds->yy_train : h->ds->yy_all), (int)h->ds->p, h->ws.sweep_key);
         KCHECK();
-        if ((rc = launch_gene_order(h, nullptr, 0, 1, h->stream))) return rc;
-        h->have_perm = true;
+        if ((rc = launch_gene_order(h, nullptr, 0, 1, h->st.stream))) return rc;
+        h->ws.have_perm = true;
     }
     while (iter <= max_iter) {                                                                  // :325
-        if (h->verbose && iter % 10 == 0) printf("Iteration %u ---------------------------------\n", iter);
+        if (h->opt.verbose && iter % 10 == 0) printf("Iteration %u ---------------------------------\n", iter);
         // ---- row step: all covariates, Gauss-Seidel (:332-362) -------------------------------------------------
         if (use_merged(h, masked)) { if ((rc = launch_wsyrk_side(h))) return rc; }                // incl. the row prep
         else if ((rc = launch_row_prep(h, masked))) return rc;                                  // :332
@@ -2348,34 +2335,34 @@ static int optimize_body(insider_hip_handle *h, double *const *A, double *C, int
         // V = C A' of the covariates 1 .. c-1: what covariate 0's update reads.  Covariate 0's own columns are first read by
         // covariate 1's update, after they have been recomputed from the updated factors (below): not formed here
         // (with continuous covariates on the merged form: their columns of V too — s_r carries A_c' z_r)
-        if (use_merged(h, masked)) if ((rc = launch_gene_v(h, h->c > 1 ? h->lvl_off[1] : h->SLcat, h->SL))) return rc;
-        if (use_merged(h, masked)) HIPCHECK(hipStreamWaitEvent(h->stream, h->ev_head, 0));   // launch_wsyrk_side
-        const bool cont_follow = inc_continuous && h->m > 0;
-        for (int i = 0; i < h->c; ++i) {
-            const bool need_R = !(use_merged(h, masked) || unmasked_fused(h, masked)) || (i + 1 == h->c && !cont_follow);
+        if (use_merged(h, masked)) if ((rc = launch_gene_v(h, h->ds->c > 1 ? h->ds->lvl_off[1] : h->ds->SLcat, h->ds->SL))) return rc;
+        if (use_merged(h, masked)) HIPCHECK(hipStreamWaitEvent(h->st.stream, h->st.ev_head, 0));   // launch_wsyrk_side
+        const bool cont_follow = inc_continuous && h->ds->m > 0;
+        for (int i = 0; i < h->ds->c; ++i) {
+            const bool need_R = !(use_merged(h, masked) || unmasked_fused(h, masked)) || (i + 1 == h->ds->c && !cont_follow);
             if ((rc = row_update(h, i, -1, masked, lambda1, need_R))) return rc;                // :339
-            if (use_merged(h, masked) && (i + 1 < h->c || cont_follow))   // (the continuous columns read every categorical column of V)
-                if ((rc = launch_gene_v(h, h->lvl_off[i], h->lvl_off[i + 1]))) return rc;
+            if (use_merged(h, masked) && (i + 1 < h->ds->c || cont_follow))   // (the continuous columns read every categorical column of V)
+                if ((rc = launch_gene_v(h, h->ds->lvl_off[i], h->ds->lvl_off[i + 1]))) return rc;
         }
         if (cont_follow)
-            for (int j = 0; j < h->m; ++j) {
-                if ((rc = row_update(h, 0, j, masked, lambda1, !use_merged(h, masked) || j + 1 == h->m))) return rc;   // :340-351
-                if (use_merged(h, masked) && j + 1 < h->m)
-                    if ((rc = launch_gene_v(h, h->SLcat + j, h->SLcat + j + 1))) return rc;
+            for (int j = 0; j < h->ds->m; ++j) {
+                if ((rc = row_update(h, 0, j, masked, lambda1, !use_merged(h, masked) || j + 1 == h->ds->m))) return rc;   // :340-351
+                if (use_merged(h, masked) && j + 1 < h->ds->m)
+                    if ((rc = launch_gene_v(h, h->ds->SLcat + j, h->ds->SLcat + j + 1))) return rc;
             }
         h->w_ready = false;
         // ---- column step (:365-378) -------------------------------------------------------------------------------
         if ((rc = phase_R(h, true, true, masked != 0))) return rc;
         const int checkpoint = iter % 10 == 0;
         if (alpha != 0.0 && iter == 0)   // later iterations: built on the side stream while the previous solve ran
-            if ((rc = ensure_order_table(h, seed, iter, K, h->max_sweeps, h->order_mode, lambda2 * alpha, nullptr, 0))) return rc;
+            if ((rc = ensure_order_table(h, seed, iter, K, h->opt.max_sweeps, h->opt.order_mode, lambda2 * alpha, nullptr, 0))) return rc;
         if (masked) if ((rc = launch_col_stats(h, true))) return rc;
         if (alpha != 0.0) {
-            h->order = h->order_buf[iter & 1];
+            h->ws.order = h->ws.order_buf[iter & 1];
             if (iter < max_iter) {   // the next iteration's table, from here on: beside this iteration's solve
-                HIPCHECK(hipEventRecord(h->ev_tab, h->stream));
-                HIPCHECK(hipStreamWaitEvent(h->side, h->ev_tab, 0));
-                if ((rc = ensure_order_table(h, seed, iter + 1, K, h->max_sweeps, h->order_mode, lambda2 * alpha, h->side, (int)((iter + 1) & 1))))
+                HIPCHECK(hipEventRecord(h->st.ev_tab, h->st.stream));
+                HIPCHECK(hipStreamWaitEvent(h->st.side, h->st.ev_tab, 0));
+                if ((rc = ensure_order_table(h, seed, iter + 1, K, h->opt.max_sweeps, h->opt.order_mode, lambda2 * alpha, h->st.side, (int)((iter + 1) & 1))))
                     return rc;
             }
         }
@@ -2399,7 +2386,7 @@ static int optimize_body(insider_hip_handle *h, double *const *A, double *C, int
             else if (delta_loss / 1000 <= 1e-1) decay = 1e-1;
             else decay = 1.0;
             put_traj(iter, delta_loss, decay);
-            if (h->verbose) {
+            if (h->opt.verbose) {
                 printf("insider iter %u: train rmse = %.12g\n", iter, train_rmse);
                 if (tuning == 1) printf("insider iter %u: test rmse = %.12g\n", iter, test_rmse);
                 printf("total_residual\t%.12g;\nrow_reg_loss:\t%.12g;\ncol_reg_loss:\t%.12g;\nl1_reg_loss:\t%.12g.\n",
@@ -2413,15 +2400,15 @@ static int optimize_body(insider_hip_handle *h, double *const *A, double *C, int
     if ((rc = download_factors(h, A, C, K))) return rc;
     if ((rc = check_fail_flag(h))) return rc;
     if ((rc = read_cap_hits(h))) return rc;
-    HIPCHECK(hipStreamSynchronize(h->side2));
-    HIPCHECK(hipStreamSynchronize(h->side3));
-    HIPCHECK(hipStreamSynchronize(h->side));   // the gene orders kept for the next call
+    HIPCHECK(hipStreamSynchronize(h->st.side2));
+    HIPCHECK(hipStreamSynchronize(h->st.side3));
+    HIPCHECK(hipStreamSynchronize(h->st.side));   // the gene orders kept for the next call
     h->side_pending = false;
     {
         unsigned long long bins[256];
         // (on the handle's own stream: a null-stream copy would wait for every other handle's work, insider_hip_clone)
-        HIPCHECK(hipMemcpyAsync(bins, h->sweep_total, sizeof(bins), hipMemcpyDeviceToHost, h->stream));
-        HIPCHECK(hipStreamSynchronize(h->stream));
+        HIPCHECK(hipMemcpyAsync(bins, h->ws.sweep_total, sizeof(bins), hipMemcpyDeviceToHost, h->st.stream));
+        HIPCHECK(hipStreamSynchronize(h->st.stream));
         for (unsigned long long v : bins) sweeps_total += v;
     }
     if (out_train_rmse) *out_train_rmse = train_rmse;
@@ -2432,7 +2419,7 @@ static int optimize_body(insider_hip_handle *h, double *const *A, double *C, int
     // ---- profile -------------------------------------------------------------------------------------------------------
     const auto t_end = std::chrono::steady_clock::now();
     for (double &v : h->prof) v = 0;
-    auto sum_events = [&](std::vector<hipEvent_t> &ev, double *launches, double *ms) {
+    auto sum_events = [&](std::vector<Event> &ev, double *launches, double *ms) {
         for (size_t i = 0; i + 1 < ev.size(); i += 2) {
             float t = 0;
             if (hipEventElapsedTime(&t, ev[i], ev[i + 1]) == hipSuccess) { *ms += t; *launches += 1; }
@@ -2442,7 +2429,7 @@ static int optimize_body(insider_hip_handle *h, double *const *A, double *C, int
     sum_events(h->ev_row, &h->prof[2], &h->prof[3]);
     sum_events(h->ev_cd, &h->prof[4], &h->prof[5]);
     sum_events(h->ev_test, &h->prof[6], &h->prof[7]);
-    auto tail_mean = [&](std::vector<hipEvent_t> &ev) {   // one event pair per outer iteration: the mean from iteration 5 on
+    auto tail_mean = [&](std::vector<Event> &ev) {   // one event pair per outer iteration: the mean from iteration 5 on
         double ms = 0.0;
         int cnt = 0;
         for (size_t i = 10; i + 1 < ev.size(); i += 2) {
@@ -2469,16 +2456,16 @@ int insider_hip_optimize(insider_hip_handle *h, double *const *A, double *C, int
 {
     const int rc = optimize_body(h, A, C, inc_continuous, K, lambda1, lambda2, alpha, tuning, global_tol, sub_tol, max_iter,
                                  seed, out_train_rmse, out_test_rmse, out_loss, traj, traj_cap, out_traj_rows, out_iters);
-    if (rc != INSIDER_OK && h && h->stream) {
+    if (rc != INSIDER_OK && h && h->st.stream) {
         // an early return leaves enqueued work on every stream: drain them so that the next call starts clean
         const std::string keep = g_err;
-        (void)hipSetDevice(h->device);
-        (void)hipStreamSynchronize(h->stream);
-        (void)hipStreamSynchronize(h->side);
-        (void)hipStreamSynchronize(h->side2);
-        (void)hipStreamSynchronize(h->side3);
+        (void)hipSetDevice(h->ds->device);
+        (void)hipStreamSynchronize(h->st.stream);
+        (void)hipStreamSynchronize(h->st.side);
+        (void)hipStreamSynchronize(h->st.side2);
+        (void)hipStreamSynchronize(h->st.side3);
         h->side_pending = h->qfull_pending = h->qheld_pending = h->w_ready = false;
-        if (h->failflag) (void)hipMemset(h->failflag, 0, 4 * sizeof(int));
+        if (h->ws.failflag) (void)hipMemset(h->ws.failflag, 0, 4 * sizeof(int));
         clear_events(h);
         g_err = keep;
     }
@@ -2532,9 +2519,9 @@ int insider_hip_optimize_row(insider_hip_handle *h, double *const *A, const doub
 {
     int rc = check_factor_args(h, A, C, inc_continuous, tuning);
     if (rc) return rc;
-    if (cov < 0 || cov >= h->c + (inc_continuous ? h->m : 0)) return fail(INSIDER_ERR_ARG, "covariate index out of range");
+    if (cov < 0 || cov >= h->ds->c + (inc_continuous ? h->ds->m : 0)) return fail(INSIDER_ERR_ARG, "covariate index out of range");
     if (!(lambda == lambda)) return fail(INSIDER_ERR_ARG, "lambda is NaN");   // any finite value, like the reference
-    HIPCHECK(hipSetDevice(h->device));
+    HIPCHECK(hipSetDevice(h->ds->device));
     if ((rc = ensure_workspace(h, K))) return rc;
     h->row_kernels = 0;
     h->w_ready = false;
@@ -2542,9 +2529,9 @@ int insider_hip_optimize_row(insider_hip_handle *h, double *const *A, const doub
     if ((rc = launch_row_prep(h, tuning))) return rc;
     if (tuning == 1 && !use_merged(h, tuning)) if ((rc = launch_row_stats(h, false))) return rc;
     if ((rc = launch_build_R(h))) return rc;
-    if (use_merged(h, tuning)) if ((rc = launch_gene_v(h, 0, h->SL))) return rc;
-    if (cov < h->c) rc = row_update(h, cov, -1, tuning, lambda);
-    else rc = row_update(h, 0, cov - h->c, tuning, lambda);
+    if (use_merged(h, tuning)) if ((rc = launch_gene_v(h, 0, h->ds->SL))) return rc;
+    if (cov < h->ds->c) rc = row_update(h, cov, -1, tuning, lambda);
+    else rc = row_update(h, 0, cov - h->ds->c, tuning, lambda);
     if (rc) return rc;
     if ((rc = download_factors(h, A, nullptr, K))) return rc;
     return check_fail_flag(h);
@@ -2558,16 +2545,16 @@ int insider_hip_optimize_col(insider_hip_handle *h, double *const *A, double *C,
 {
     int rc = check_factor_args(h, A, C, inc_continuous, tuning);
     if (rc) return rc;
-    HIPCHECK(hipSetDevice(h->device));
+    HIPCHECK(hipSetDevice(h->ds->device));
     if ((rc = ensure_workspace(h, K))) return rc;
     if ((rc = upload_factors(h, A, C, K))) return rc;
     if ((rc = phase_R(h))) return rc;
     if (alpha != 0.0) {
-        if ((rc = ensure_order_table(h, seed, iter, K, h->max_sweeps, h->order_mode, lambda * alpha, nullptr, 0))) return rc;
-        h->order = h->order_buf[0];
+        if ((rc = ensure_order_table(h, seed, iter, K, h->opt.max_sweeps, h->opt.order_mode, lambda * alpha, nullptr, 0))) return rc;
+        h->ws.order = h->ws.order_buf[0];
     }
     if (tuning == 1) if ((rc = launch_col_stats(h, false))) return rc;
-    HIPCHECK(hipMemsetAsync(h->failflag + 2, 0, 2 * sizeof(int), h->stream));
+    HIPCHECK(hipMemsetAsync(h->ws.failflag + 2, 0, 2 * sizeof(int), h->st.stream));
     if ((rc = launch_col_solve(h, tuning, true, lambda, alpha, tol, 0, false))) return rc;
     if ((rc = download_factors(h, nullptr, C, K))) return rc;
     if ((rc = read_cap_hits(h))) return rc;
@@ -2575,24 +2562,24 @@ int insider_hip_optimize_col(insider_hip_handle *h, double *const *A, double *C,
 }
 
 // device part shared by the two strong_coordinate_descent entries: dG / dq / dw hold nprob problems on `device`
-static int strong_cd_device(DevBufs &bufs, const double *dG, const double *dq, const double *dw, int K, int64_t nprob,
+static int strong_cd_device(const double *dG, const double *dq, const double *dw, int K, int64_t nprob,
                             double lambda, double alpha, double tol, uint64_t seed, uint32_t iter, int order_mode,
                             int max_sweeps, double *beta_out, int32_t *sweeps_out)
 {
-    double *db = nullptr;
-    int *ds = nullptr;
+    DevBuf<double> db;
+    DevBuf<int> ds;
     int rc;
-    if ((rc = bufs.alloc(&db, (size_t)nprob * K)) || (rc = bufs.alloc(&ds, (size_t)nprob))) return rc;
+    if ((rc = db.alloc((size_t)nprob * K)) || (rc = ds.alloc((size_t)nprob))) return rc;
     const int ms = max_sweeps < 1 ? 1 : max_sweeps;
     const int rows = std::min<int64_t>(ms, INSIDER_PERM_PERIOD);   // one period of the order sequence (include/insider_perm.h)
-    uint8_t *dord = nullptr;
-    if ((rc = bufs.alloc(&dord, (size_t)(rows + 4) * ORDER_ROW))) return rc;   // + the look-ahead row
+    DevBuf<uint8_t> dord;
+    if ((rc = dord.alloc((size_t)(rows + 4) * ORDER_ROW))) return rc;   // + the look-ahead row
     const bool reg = K <= 32 && lambda * alpha > 0.0;   // the register-resident batch kernel
     const bool reg3 = reg3_path(K, lambda * alpha);
     unsigned long long code_base = 0;
     if (reg && reg_pairs(reg_kmax(K))) {   // where are its code blocks?
-        unsigned long long *dcb = nullptr;
-        if ((rc = bufs.alloc(&dcb, 1))) return rc;
+        DevBuf<unsigned long long> dcb;
+        if ((rc = dcb.alloc(1))) return rc;
         HIPCHECK(hipMemset(dcb, 0, sizeof(unsigned long long)));
         CdParams none{};
         REG_DISPATCH(K, hipLaunchKernelGGL((k_cd_batch_reg<SL_, KM_>), dim3(1), dim3(64), 0, 0, dG, dq, dw, K, (int64_t)0, none, db, ds, dcb));
@@ -2613,11 +2600,9 @@ static int strong_cd_device(DevBufs &bufs, const double *dG, const double *dq, c
     cd.inv_two_la = cd.la > 0.0 ? 0.5 / cd.la : 0.0;
     cd.max_sweeps = ms;
     cd.order = dord;
-    hipEvent_t e0, e1;
-    HIPCHECK(hipEventCreate(&e0));
-    bufs.events.push_back(e0);
-    HIPCHECK(hipEventCreate(&e1));
-    bufs.events.push_back(e1);
+    Event e0, e1;
+    HIPCHECK(hipEventCreate(e0.out()));
+    HIPCHECK(hipEventCreate(e1.out()));
     HIPCHECK(hipEventRecord(e0, 0));
     const size_t r16_bytes = (size_t)r16_lds_doubles(K) * sizeof(double);
     if (reg) {   // (the register-resident solver's state is scaled by 1 / (2 lambda alpha))
@@ -2664,15 +2649,12 @@ int insider_hip_strong_cd(const double *XtX, const double *Xty, const double *ws
     if (rc) return rc;
     if (nprob == 0) return INSIDER_OK;
     HIPCHECK(hipSetDevice(device));
-    DevBufs bufs;
-    double *dG = nullptr, *dq = nullptr, *dw = nullptr;
-    if ((rc = bufs.alloc(&dG, (size_t)nprob * K * K)) || (rc = bufs.alloc(&dq, (size_t)nprob * K)) ||
-        (rc = bufs.alloc(&dw, (size_t)nprob * K)))
-        return rc;
+    DevBuf<double> dG, dq, dw;
+    if ((rc = dG.alloc((size_t)nprob * K * K)) || (rc = dq.alloc((size_t)nprob * K)) || (rc = dw.alloc((size_t)nprob * K))) return rc;
     HIPCHECK(hipMemcpy(dG, XtX, (size_t)nprob * K * K * sizeof(double), hipMemcpyHostToDevice));
     HIPCHECK(hipMemcpy(dq, Xty, (size_t)nprob * K * sizeof(double), hipMemcpyHostToDevice));
     HIPCHECK(hipMemcpy(dw, wstart, (size_t)nprob * K * sizeof(double), hipMemcpyHostToDevice));
-    return strong_cd_device(bufs, dG, dq, dw, K, nprob, lambda, alpha, tol, seed, iter, order_mode, max_sweeps, beta_out,
+    return strong_cd_device(dG, dq, dw, K, nprob, lambda, alpha, tol, seed, iter, order_mode, max_sweeps, beta_out,
                             sweeps_out);
 }
 
@@ -2686,13 +2668,11 @@ int insider_hip_strong_cd_xy(const double *X, const double *y, int64_t m, int K,
     int rc = cd_common_checks(K, 1, device);
     if (rc) return rc;
     HIPCHECK(hipSetDevice(device));
-    DevBufs bufs;
-    double *dG = nullptr, *dq = nullptr, *dw = nullptr;
-    if ((rc = bufs.alloc(&dG, (size_t)K * K)) || (rc = bufs.alloc(&dq, (size_t)K)) || (rc = bufs.alloc(&dw, (size_t)K)))
-        return rc;
+    DevBuf<double> dG, dq, dw;
+    if ((rc = dG.alloc((size_t)K * K)) || (rc = dq.alloc((size_t)K)) || (rc = dw.alloc((size_t)K))) return rc;
     if (!XtX || !Xty) {   // X'X and X'y on the device from the design matrix and outcome (src/optimize.cpp:219-222,234-235)
-        double *dX = nullptr, *dy = nullptr;
-        if ((rc = bufs.alloc(&dX, (size_t)m * K)) || (rc = bufs.alloc(&dy, (size_t)m))) return rc;
+        DevBuf<double> dX, dy;
+        if ((rc = dX.alloc((size_t)m * K)) || (rc = dy.alloc((size_t)m))) return rc;
         HIPCHECK(hipMemcpy(dX, X, (size_t)m * K * sizeof(double), hipMemcpyHostToDevice));
         HIPCHECK(hipMemcpy(dy, y, (size_t)m * sizeof(double), hipMemcpyHostToDevice));
         hipLaunchKernelGGL(k_xtx_xty, dim3(K, K + 1), dim3(64), 0, 0, (const double *)dX, (const double *)dy, m, K, dG, dq);
@@ -2701,7 +2681,7 @@ int insider_hip_strong_cd_xy(const double *X, const double *y, int64_t m, int K,
     if (XtX) HIPCHECK(hipMemcpy(dG, XtX, (size_t)K * K * sizeof(double), hipMemcpyHostToDevice));
     if (Xty) HIPCHECK(hipMemcpy(dq, Xty, (size_t)K * sizeof(double), hipMemcpyHostToDevice));
     HIPCHECK(hipMemcpy(dw, wstart, (size_t)K * sizeof(double), hipMemcpyHostToDevice));
-    return strong_cd_device(bufs, dG, dq, dw, K, 1, lambda, alpha, tol, seed, iter, order_mode, max_sweeps, beta_out,
+    return strong_cd_device(dG, dq, dw, K, 1, lambda, alpha, tol, seed, iter, order_mode, max_sweeps, beta_out,
                             sweeps_out);
 }
 
@@ -2712,11 +2692,10 @@ int insider_hip_solve_sympd(const double *A, const double *b, int K, int64_t nsy
     if (rc) return rc;
     if (nsys == 0) return INSIDER_OK;
     HIPCHECK(hipSetDevice(device));
-    DevBufs bufs;
-    double *dA = nullptr, *db = nullptr, *dx = nullptr;
-    int *dr = nullptr;
-    if ((rc = bufs.alloc(&dA, (size_t)nsys * K * K)) || (rc = bufs.alloc(&db, (size_t)nsys * K)) ||
-        (rc = bufs.alloc(&dx, (size_t)nsys * K)) || (rc = bufs.alloc(&dr, (size_t)nsys)))
+    DevBuf<double> dA, db, dx;
+    DevBuf<int> dr;
+    if ((rc = dA.alloc((size_t)nsys * K * K)) || (rc = db.alloc((size_t)nsys * K)) || (rc = dx.alloc((size_t)nsys * K)) ||
+        (rc = dr.alloc((size_t)nsys)))
         return rc;
     HIPCHECK(hipMemcpy(dA, A, (size_t)nsys * K * K * sizeof(double), hipMemcpyHostToDevice));
     HIPCHECK(hipMemcpy(db, b, (size_t)nsys * K * sizeof(double), hipMemcpyHostToDevice));
@@ -2757,14 +2736,11 @@ int insider_hip_optimize_continuous_v2(const double *data, int64_t n, int64_t p,
     const int NB = (K + 1 + 15) / 16, KP = 16 * NB, len = KP * KP + KP;
     const int nslab = cdiv(p, CV2_SLAB);
     const size_t np = (size_t)n * (size_t)p;
-    DevBufs bufs;
-    double *dD = nullptr, *dC = nullptr, *dz = nullptr, *dw = nullptr, *dt = nullptr, *dpart = nullptr, *deq = nullptr, *du = nullptr,
-           *dg = nullptr, *dzz = nullptr;
-    uint8_t *dM = nullptr;
-    int *dflag = nullptr;   // [0] the solve's fail flag, [1] a level count of 1 for k_level_solve
-    if ((rc = bufs.alloc(&dD, np)) || (rc = bufs.alloc(&dC, (size_t)K * p)) || (rc = bufs.alloc(&dz, (size_t)n)) ||
-        (rc = bufs.alloc(&dt, (size_t)p)) || (rc = bufs.alloc(&dpart, (size_t)nslab * len)) || (rc = bufs.alloc(&deq, (size_t)len)) ||
-        (rc = bufs.alloc(&du, (size_t)KP)) || (rc = bufs.alloc(&dflag, 2)))
+    DevBuf<double> dD, dC, dz, dw, dt, dpart, deq, du, dg, dzz;
+    DevBuf<uint8_t> dM;
+    DevBuf<int> dflag;   // [0] the solve's fail flag, [1] a level count of 1 for k_level_solve
+    if ((rc = dD.alloc(np)) || (rc = dC.alloc((size_t)K * p)) || (rc = dz.alloc((size_t)n)) || (rc = dt.alloc((size_t)p)) ||
+        (rc = dpart.alloc((size_t)nslab * len)) || (rc = deq.alloc((size_t)len)) || (rc = du.alloc((size_t)KP)) || (rc = dflag.alloc(2)))
         return rc;
     HIPCHECK(hipMemcpy(dD, data, np * sizeof(double), hipMemcpyHostToDevice));
     HIPCHECK(hipMemcpy(dC, c_factor, (size_t)K * p * sizeof(double), hipMemcpyHostToDevice));
@@ -2774,12 +2750,12 @@ int insider_hip_optimize_continuous_v2(const double *data, int64_t n, int64_t p,
     const int flag0[2] = {0, 1};
     HIPCHECK(hipMemcpy(dflag, flag0, sizeof(flag0), hipMemcpyHostToDevice));
     if (tuning == 1) {
-        if ((rc = bufs.alloc(&dM, np)) || (rc = bufs.alloc(&dw, (size_t)p))) return rc;
+        if ((rc = dM.alloc(np)) || (rc = dw.alloc((size_t)p))) return rc;
         HIPCHECK(hipMemcpy(dM, indicator, np, hipMemcpyHostToDevice));
         hipLaunchKernelGGL((k_cv2_gene<true>), dim3(cdiv(p, 4)), dim3(256), 0, 0, (const double *)dD, (const uint8_t *)dM,
                            (const double *)dz, n, p, dw, dt);
     } else {
-        if ((rc = bufs.alloc(&dg, (size_t)K * K)) || (rc = bufs.alloc(&dzz, 1))) return rc;
+        if ((rc = dg.alloc((size_t)K * K)) || (rc = dzz.alloc(1))) return rc;
         HIPCHECK(hipMemcpy(dg, gram, (size_t)K * K * sizeof(double), hipMemcpyHostToDevice));
         hipLaunchKernelGGL(k_cv2_zz, dim3(1), dim3(64), 0, 0, (const double *)dz, n, dzz);
         hipLaunchKernelGGL((k_cv2_gene<false>), dim3(cdiv(p, 4)), dim3(256), 0, 0, (const double *)dD, (const uint8_t *)nullptr,
@@ -2812,41 +2788,40 @@ int insider_hip_optimize_continuous_v2(const double *data, int64_t n, int64_t p,
 static int masked_gram_common(insider_hip_handle *h, bool cols, const double *Fhost, int K, double *G_out, double *q_out)
 {
     if (!h || !Fhost || !G_out || !q_out) return fail(INSIDER_ERR_ARG, "null argument");
-    HIPCHECK(hipSetDevice(h->device));
+    HIPCHECK(hipSetDevice(h->ds->device));
     int rc = ensure_workspace(h, K);
     if (rc) return rc;
-    const int KP = h->KP;
-    const int64_t units = cols ? h->p : h->n, flen = cols ? h->n : h->p;
-    double *F = cols ? h->R : h->C, *full = cols ? h->RtR : h->CCt;
+    const int KP = h->ws.KP;
+    const int64_t units = cols ? h->ds->p : h->ds->n, flen = cols ? h->ds->n : h->ds->p;
+    double *F = cols ? h->ws.R : h->ws.C, *full = cols ? h->ws.RtR : h->ws.CCt;
     // host factor: cols -> R is n x K column-major; rows -> C is K x p column-major (= p rows of K)
-    HIPCHECK(hipMemcpy(h->stage, Fhost, (size_t)flen * K * sizeof(double), hipMemcpyHostToDevice));
-    if (cols) hipLaunchKernelGGL(k_pack_A, dim3(cdiv(flen * KP, 256)), dim3(256), 0, h->stream, (const double *)h->stage,
+    HIPCHECK(hipMemcpy(h->ws.stage, Fhost, (size_t)flen * K * sizeof(double), hipMemcpyHostToDevice));
+    if (cols) hipLaunchKernelGGL(k_pack_A, dim3(cdiv(flen * KP, 256)), dim3(256), 0, h->st.stream, (const double *)h->ws.stage,
                                  (int)flen, K, KP, F);
-    else hipLaunchKernelGGL(k_pack_rows, dim3(cdiv(flen * KP, 256)), dim3(256), 0, h->stream, (const double *)h->stage,
+    else hipLaunchKernelGGL(k_pack_rows, dim3(cdiv(flen * KP, 256)), dim3(256), 0, h->st.stream, (const double *)h->ws.stage,
                             flen, K, KP, F);
     KCHECK();
     if ((rc = launch_gram(h, F, flen, full))) return rc;
-    double *stat = nullptr, *qf = nullptr, *Gd = nullptr, *qd = nullptr;
-    const int NBLK = h->NB * (h->NB + 1) / 2, STAT = NBLK * 256;
-    const int nseg = cols ? 1 : h->nseg;
-    DevBufs bufs;
-    if ((rc = bufs.alloc(&stat, (size_t)nseg * units * STAT)) || (rc = bufs.alloc(&qf, (size_t)units * KP)) ||
-        (rc = bufs.alloc(&Gd, (size_t)units * K * K)) || (rc = bufs.alloc(&qd, (size_t)units * K)))
+    const int NBLK = h->ws.NB * (h->ws.NB + 1) / 2, STAT = NBLK * 256;
+    const int nseg = cols ? 1 : h->ws.nseg;
+    DevBuf<double> stat, qf, Gd, qd;
+    if ((rc = stat.alloc((size_t)nseg * units * STAT)) || (rc = qf.alloc((size_t)units * KP)) || (rc = Gd.alloc((size_t)units * K * K)) ||
+        (rc = qd.alloc((size_t)units * K)))
         return rc;
     if ((rc = launch_list_stats(h, cols, nseg, F, stat))) return rc;
     // dense X'F over all entries from the gene-major copy (rows: strided reads; stand-alone API only)
-    if (cols) hipLaunchKernelGGL(k_line_dense_xty, dim3((unsigned)units), dim3(64), 0, h->stream, (const double *)h->X,
-                                 h->ldn, (int)flen, (const double *)F, K, KP, qf);
-    else hipLaunchKernelGGL(k_row_dense_xty, dim3((unsigned)units), dim3(64), 0, h->stream, (const double *)h->X, h->ldn,
+    if (cols) hipLaunchKernelGGL(k_line_dense_xty, dim3((unsigned)units), dim3(64), 0, h->st.stream, (const double *)h->ds->X,
+                                 h->ds->ldn, (int)flen, (const double *)F, K, KP, qf);
+    else hipLaunchKernelGGL(k_row_dense_xty, dim3((unsigned)units), dim3(64), 0, h->st.stream, (const double *)h->ds->X, h->ds->ldn,
                             (int)flen, (const double *)F, K, KP, qf);
     KCHECK();
-    NB_DISPATCH(h->NB, {
+    NB_DISPATCH(h->ws.NB, {
         (void)WPB_;
-        hipLaunchKernelGGL((k_stats_to_dense<NB_>), dim3((unsigned)units), dim3(64), 0, h->stream, (const double *)stat,
+        hipLaunchKernelGGL((k_stats_to_dense<NB_>), dim3((unsigned)units), dim3(64), 0, h->st.stream, (const double *)stat,
                            nseg, (int)units, K, (const double *)full, (const double *)qf, Gd, qd);
     });
     KCHECK();
-    HIPCHECK(hipStreamSynchronize(h->stream));
+    HIPCHECK(hipStreamSynchronize(h->st.stream));
     HIPCHECK(hipMemcpy(G_out, Gd, (size_t)units * K * K * sizeof(double), hipMemcpyDeviceToHost));
     HIPCHECK(hipMemcpy(q_out, qd, (size_t)units * K * sizeof(double), hipMemcpyDeviceToHost));
     // the pad rows of C (genes p..ldp-1) were not touched; R/C now hold the caller's factor
@@ -2868,10 +2843,10 @@ double insider_hip_last_cd_ms(void) { return g_last_cd_ms; }
 int insider_hip_get_sweeps(insider_hip_handle *h, int32_t *out)
 {
     if (!h || !out) return fail(INSIDER_ERR_ARG, "null");
-    if (!h->sweeps) return fail(INSIDER_ERR_ARG, "no column update has run yet");
-    HIPCHECK(hipSetDevice(h->device));
-    HIPCHECK(hipStreamSynchronize(h->stream));
-    HIPCHECK(hipMemcpy(out, h->sweeps, (size_t)h->p * sizeof(int), hipMemcpyDeviceToHost));
+    if (!h->ws.sweeps) return fail(INSIDER_ERR_ARG, "no column update has run yet");
+    HIPCHECK(hipSetDevice(h->ds->device));
+    HIPCHECK(hipStreamSynchronize(h->st.stream));
+    HIPCHECK(hipMemcpy(out, h->ws.sweeps, (size_t)h->ds->p * sizeof(int), hipMemcpyDeviceToHost));
     return INSIDER_OK;
 }
 
@@ -2879,18 +2854,18 @@ int insider_hip_get_info(insider_hip_handle *h, const char *name, double *out)
 {
     if (!h || !name || !out) return fail(INSIDER_ERR_ARG, "null");
     const std::string s(name);
-    const int NB = h->NB;
+    const int NB = h->ws.NB;
     if (s == "col_stats_path") *out = col_stats_path(h);
     else if (s == "row_merged") *out = use_merged(h, 1) ? 1.0 : 0.0;
-    else if (s == "col_entries") *out = (double)h->col_entries;      // padded held-out list entries, column side
-    else if (s == "row_entries") *out = (double)h->row_entries;
+    else if (s == "col_entries") *out = (double)h->ds->col_entries;      // padded held-out list entries, column side
+    else if (s == "row_entries") *out = (double)h->ds->row_entries;
     else if (s == "stat_doubles") *out = NB ? NB * (NB + 1) / 2 * 256.0 : 0.0;
-    else if (s == "kp") *out = h->KP;
-    else if (s == "pair_count_bytes_per_gene") *out = h->cf_pair_ok ? h->cf.cnt_stride : 0.0;
-    else if (s == "lists_bytes") *out = 12.0 * ((double)h->col_entries + (double)h->row_entries);
+    else if (s == "kp") *out = h->ws.KP;
+    else if (s == "pair_count_bytes_per_gene") *out = h->ds->cf_pair_ok ? h->ds->cf.cnt_stride : 0.0;
+    else if (s == "lists_bytes") *out = 12.0 * ((double)h->ds->col_entries + (double)h->ds->row_entries);
     else if (s == "cap_hits") *out = h->cap_hits;                   // last optimize() / optimize_col(): solves ended by max_sweeps
     else if (s == "max_gene_sweeps") *out = h->max_gene_sweeps;     // ... and the longest solve, in sweeps
-    else if (s == "max_sweeps") *out = h->max_sweeps;
+    else if (s == "max_sweeps") *out = h->opt.max_sweeps;
     else if (s == "col_solver") *out = h->col_solver;               // last column solve: the kernel that ran it (ColSolver) ...
     else if (s == "col_eval") *out = h->col_eval;                   // ... and the one that ran its evaluation pass (0 = none)
     else if (s == "col_ridge_fallback") *out = h->col_ridge_fallback;   // ... and whether the ridge solve launched the general route
@@ -2905,18 +2880,18 @@ int insider_hip_get_info(insider_hip_handle *h, const char *name, double *out)
         const int path = col_stats_path(h);
         double v = 0.0;
         if (path == 0) {
-            const int NT = (h->K + 4) / 4;
-            if (h->list_fine && NB == 2 && NT >= 5 && NT <= 8 && h->fperm)   // k_list_stats4: NT (NT + 1) / 2 instructions of 512 flops per 16 entries
-                v = (double)h->col_entries / (double)std::max<int64_t>(h->p, 1) / 16.0 * (NT * (NT + 1) / 2) / 4.0;
+            const int NT = (h->ws.K + 4) / 4;
+            if (h->opt.list_fine && NB == 2 && NT >= 5 && NT <= 8 && h->ws.fperm)   // k_list_stats4: NT (NT + 1) / 2 instructions of 512 flops per 16 entries
+                v = (double)h->ds->col_entries / (double)std::max<int64_t>(h->ds->p, 1) / 16.0 * (NT * (NT + 1) / 2) / 4.0;
             else
-                v = (double)h->col_entries / (double)std::max<int64_t>(h->p, 1) / 4.0 * (NB * (NB + 1) / 2);
+                v = (double)h->ds->col_entries / (double)std::max<int64_t>(h->ds->p, 1) / 4.0 * (NB * (NB + 1) / 2);
         } else
-            for (int t = 0; t < h->cf.c; ++t) {
-                v += std::ceil(h->cf.L[t] / 4.0) * NB * NB;                                           // M += A' P
-                if (path == 2 && h->cf.nlater[t] > 0) v += std::ceil(h->cf.L[t] / 16.0) * h->cf.nsteps * NB;   // P = N_j Tab
-                if (path == 2 && h->m > 0) v += std::ceil(h->cf.L[t] / 16.0) * NB;                            // + real-valued counts
+            for (int t = 0; t < h->ds->cf.c; ++t) {
+                v += std::ceil(h->ds->cf.L[t] / 4.0) * NB * NB;                                           // M += A' P
+                if (path == 2 && h->ds->cf.nlater[t] > 0) v += std::ceil(h->ds->cf.L[t] / 16.0) * h->ds->cf.nsteps * NB;   // P = N_j Tab
+                if (path == 2 && h->ds->m > 0) v += std::ceil(h->ds->cf.L[t] / 16.0) * NB;                            // + real-valued counts
             }
-        if (path == 2 && h->m > 0) v += std::ceil(h->m / 4.0) * NB * NB + NB;                                 // the continuous position
+        if (path == 2 && h->ds->m > 0) v += std::ceil(h->ds->m / 4.0) * NB * NB + NB;                                 // the continuous position
         *out = v;
     } else return fail(INSIDER_ERR_ARG, "unknown info key " + s);
     return INSIDER_OK;
@@ -2928,13 +2903,13 @@ int insider_hip_get_array(insider_hip_handle *h, const char *name, void *out, in
     const std::string s(name);
     const void *src = nullptr;
     int64_t have = 0;
-    if (s == "cd_pass_slot") { src = h->cd_pass_slot; have = h->p * (int64_t)sizeof(int); }
-    else if (s == "gene_perm") { src = h->gene_perm; have = h->p * (int64_t)sizeof(int); }
-    else if (s == "order_table") { src = h->order; have = (int64_t)(h->order_rows + 1) * ORDER_ROW; }   // rows of ORDER_ROW bytes: the last solve's
+    if (s == "cd_pass_slot") { src = h->ws.cd_pass_slot; have = h->ds->p * (int64_t)sizeof(int); }
+    else if (s == "gene_perm") { src = h->ws.gene_perm; have = h->ds->p * (int64_t)sizeof(int); }
+    else if (s == "order_table") { src = h->ws.order; have = (int64_t)(h->ws.order_rows + 1) * ORDER_ROW; }   // rows of ORDER_ROW bytes: the last solve's
     else return fail(INSIDER_ERR_ARG, "unknown array " + s);
     if (!src || bytes > have) return fail(INSIDER_ERR_ARG, "array not available or too short");
-    HIPCHECK(hipSetDevice(h->device));
-    HIPCHECK(hipStreamSynchronize(h->stream));
+    HIPCHECK(hipSetDevice(h->ds->device));
+    HIPCHECK(hipStreamSynchronize(h->st.stream));
     HIPCHECK(hipMemcpy(out, src, (size_t)bytes, hipMemcpyDeviceToHost));
     return INSIDER_OK;
 }
@@ -2953,44 +2928,7 @@ int insider_hip_get_profile(insider_hip_handle *h, double *out12)
 // subtracted covariate blocks and the per-group regression on the column factor (kernels: insider_posthoc.hpp).  Own
 // workspace and the handle's main stream only: nothing insider_hip_optimize() reads is written.
 // =================================================================================================================
-struct PostWs {
-    struct Buf { void *p = nullptr; size_t bytes = 0; };
-    // Ast: stacked row factors (SL x KPW, blocks not subtracted zero); U: n x KPW; cp: p x KPW; nz: K flags;
-    // part: slab partials of the per-sample statistics; stats: n x (K + 1); stage: residual copy-out buffer;
-    // gpart / gram: C C'; ints: host-built group tables; cpart / gsum: group sums; L / dinv / info: the factor;
-    // outs: coeff, se, dof
-    Buf Ast, U, cp, nz, part, stats, stage, gpart, gram, ints, cpart, gsum, L, dinv, info, outs;
-    // variance decomposition: vin = the host factors (A blocks at row offset x K, then C as p rows of K); vtab = the level
-    // table T (p rows of SL); vrec = the p records
-    Buf vin, vtab, vrec;
-};
-
-void free_posthoc(PostWs *w)
-{
-    if (!w) return;
-    for (PostWs::Buf *b : {&w->Ast, &w->U, &w->cp, &w->nz, &w->part, &w->stats, &w->stage, &w->gpart, &w->gram, &w->ints,
-                           &w->cpart, &w->gsum, &w->L, &w->dinv, &w->info, &w->outs,
-                           &w->vin, &w->vtab, &w->vrec})
-        if (b->p) (void)hipFree(b->p);
-    delete w;
-}
-
 namespace {
-
-template <typename T>
-int ph_grow(PostWs::Buf &b, size_t count, T **out)
-{
-    const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
-    if (b.bytes < bytes) {
-        if (b.p) (void)hipFree(b.p);
-        b.p = nullptr;
-        b.bytes = 0;
-        HIPCHECK(hipMalloc(&b.p, bytes));
-        b.bytes = bytes;
-    }
-    *out = static_cast<T *>(b.p);
-    return INSIDER_OK;
-}
 
 int ph_check(insider_hip_handle *h, double *const *A, const double *C, int inc_continuous, int K, const int32_t *subtract)
 {
@@ -2999,14 +2937,14 @@ int ph_check(insider_hip_handle *h, double *const *A, const double *C, int inc_c
     if (K < 1 || K > INSIDER_MAX_K) return fail(INSIDER_ERR_UNSUPPORTED, "K must be in 1..63");
     if (inc_continuous != 0 && inc_continuous != 1)
         return fail(INSIDER_ERR_ARG, "The value of prarameter inc_continuous can only be 0 or 1.");
-    if (inc_continuous == 1 && h->m == 0)
+    if (inc_continuous == 1 && h->ds->m == 0)
         return fail(INSIDER_ERR_ARG, "inc_continuous = 1 needs a handle created with ctns_confounder (insider_hip_create_ex)");
-    if (inc_continuous == 0 && h->m > 0)
+    if (inc_continuous == 0 && h->ds->m > 0)
         return fail(INSIDER_ERR_ARG, "this handle carries continuous covariates: pass inc_continuous = 1");
     if (h->world > 1)
         return fail(INSIDER_ERR_UNSUPPORTED, "the post-hoc calls need the whole matrix: not available on a sharded handle "
                                              "(world > 1)");
-    for (int b = 0; b < h->c + inc_continuous; ++b)
+    for (int b = 0; b < h->ds->c + inc_continuous; ++b)
         if (subtract[b] && !A[b]) return fail(INSIDER_ERR_ARG, "null row factor of a subtracted block");
     return INSIDER_OK;
 }
@@ -3014,36 +2952,35 @@ int ph_check(insider_hip_handle *h, double *const *A, const double *C, int inc_c
 // U (n x KPW) = the sum of the subtracted blocks' contributions, and C in the kernels' layout (cp, nz)
 int ph_prepare(insider_hip_handle *h, double *const *A, const double *C, int K, const int32_t *subtract, int KPW)
 {
-    if (!h->post) h->post = new PostWs();
-    PostWs &w = *h->post;
-    hipStream_t st = h->stream;
-    double *Ast = nullptr, *U = nullptr, *cp = nullptr, *tmp = nullptr;
-    int *nz = nullptr;
+    const DataSet &d = *h->ds;
+    PostWs &w = h->post;
+    hipStream_t st = h->st.stream;
     int rc;
-    if ((rc = ph_grow(w.Ast, (size_t)h->SL * KPW, &Ast))) return rc;
-    if ((rc = ph_grow(w.U, (size_t)h->n * KPW, &U))) return rc;
-    if ((rc = ph_grow(w.cp, (size_t)h->p * KPW, &cp))) return rc;
-    if ((rc = ph_grow(w.nz, 64, &nz))) return rc;
+    if ((rc = w.Ast.grow((size_t)d.SL * KPW)) || (rc = w.U.grow((size_t)d.n * KPW)) || (rc = w.cp.grow((size_t)d.p * KPW)) ||
+        (rc = w.nz.grow(64)))
+        return rc;
+    double *Ast = w.Ast, *U = w.U, *cp = w.cp;
+    int *nz = w.nz;
     // the host factors go through the residual stage buffer (at least p K doubles)
-    if ((rc = ph_grow(w.stage, std::max<size_t>((size_t)h->p * K, (size_t)std::max(h->max_L, h->m) * K), &tmp))) return rc;
-    HIPCHECK(hipMemsetAsync(Ast, 0, (size_t)h->SL * KPW * sizeof(double), st));
-    for (int b = 0; b < h->c + (h->m > 0 ? 1 : 0); ++b) {
+    if ((rc = w.stage.grow(std::max<size_t>((size_t)d.p * K, (size_t)std::max(d.max_L, d.m) * K)))) return rc;
+    double *tmp = w.stage;
+    HIPCHECK(hipMemsetAsync(Ast, 0, (size_t)d.SL * KPW * sizeof(double), st));
+    for (int b = 0; b < d.blocks(); ++b) {
         if (!subtract[b]) continue;
-        const int L = b < h->c ? h->n_levels[b] : h->m;
-        const int off = b < h->c ? h->lvl_off[b] : h->SLcat;
-        HIPCHECK(hipMemcpyAsync(tmp, A[b], (size_t)L * K * sizeof(double), hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_pack_A, dim3(cdiv((int64_t)L * KPW, 256)), dim3(256), 0, st, (const double *)tmp, L, K, KPW,
-                           Ast + (size_t)off * KPW);
+        const DataSet::Block blk = d.block(b);
+        HIPCHECK(hipMemcpyAsync(tmp, A[b], (size_t)blk.rows * K * sizeof(double), hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_pack_A, dim3(cdiv((int64_t)blk.rows * KPW, 256)), dim3(256), 0, st, (const double *)tmp, blk.rows, K, KPW,
+                           Ast + (size_t)blk.off * KPW);
         KCHECK();
         HIPCHECK(hipStreamSynchronize(st));   // tmp is reused
     }
-    hipLaunchKernelGGL(k_build_R, dim3(cdiv(h->n * KPW, 256)), dim3(256), 0, st, (const int *)h->lev,
-                       (const int *)h->lvl_off_d, h->c, (int)h->n, (const double *)Ast, KPW, (const double *)h->Zc, h->m,
-                       h->SLcat, U);
+    hipLaunchKernelGGL(k_build_R, dim3(cdiv(h->ds->n * KPW, 256)), dim3(256), 0, st, (const int *)h->ds->lev,
+                       (const int *)h->ds->lvl_off_d, h->ds->c, (int)h->ds->n, (const double *)Ast, KPW, (const double *)h->ds->Zc, h->ds->m,
+                       h->ds->SLcat, U);
     KCHECK();
-    HIPCHECK(hipMemcpyAsync(tmp, C, (size_t)h->p * K * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHECK(hipMemcpyAsync(tmp, C, (size_t)h->ds->p * K * sizeof(double), hipMemcpyHostToDevice, st));
     HIPCHECK(hipMemsetAsync(nz, 0, 64 * sizeof(int), st));
-    hipLaunchKernelGGL(k_ph_pack_c, dim3(cdiv(h->p * KPW, 256)), dim3(256), 0, st, (const double *)tmp, h->p, K, KPW, cp, nz);
+    hipLaunchKernelGGL(k_ph_pack_c, dim3(cdiv(h->ds->p * KPW, 256)), dim3(256), 0, st, (const double *)tmp, h->ds->p, K, KPW, cp, nz);
     KCHECK();
     HIPCHECK(hipStreamSynchronize(st));   // the stage buffer is free again
     return INSIDER_OK;
@@ -3062,33 +2999,33 @@ int residual_body(insider_hip_handle *h, double *const *A, const double *C, int 
 {
     int rc = ph_check(h, A, C, inc_continuous, K, subtract);
     if (rc) return rc;
-    if (row_begin < 0 || row_end > h->n || row_begin > row_end)
+    if (row_begin < 0 || row_end > h->ds->n || row_begin > row_end)
         return fail(INSIDER_ERR_ARG, "rows must satisfy 0 <= row_begin <= row_end <= n");
     const int64_t nrows = row_end - row_begin;
     if (nrows == 0) return INSIDER_OK;
     if (!out) return fail(INSIDER_ERR_ARG, "null output");
-    HIPCHECK(hipSetDevice(h->device));
+    HIPCHECK(hipSetDevice(h->ds->device));
     const int NB = (K + 15) / 16, KPW = 16 * NB;
     if ((rc = ph_prepare(h, A, C, K, subtract, KPW))) return rc;
     // gene slabs of the window that fit the stage buffer (multiples of 16 genes, at least one tile)
-    const double cap = std::max(h->resid_stage_mb, 0.0) * 1048576.0;
+    const double cap = std::max(h->opt.resid_stage_mb, 0.0) * 1048576.0;
     int64_t gw = (int64_t)(cap / (8.0 * (double)nrows)) / 16 * 16;
-    gw = std::max<int64_t>(16, std::min<int64_t>(gw, round_up(h->p, 16)));
-    double *stage = nullptr;
-    if ((rc = ph_grow(h->post->stage, (size_t)nrows * gw, &stage))) return rc;
-    const double *U = static_cast<const double *>(h->post->U.p), *cp = static_cast<const double *>(h->post->cp.p);
+    gw = std::max<int64_t>(16, std::min<int64_t>(gw, round_up(h->ds->p, 16)));
+    if ((rc = h->post.stage.grow((size_t)nrows * gw))) return rc;
+    double *stage = h->post.stage;
+    const double *U = h->post.U, *cp = h->post.cp;
     const int row_blocks = cdiv(cdiv(nrows, 16), PH_WPB);
-    for (int64_t jb = 0; jb < h->p; jb += gw) {
-        const int64_t je = std::min<int64_t>(jb + gw, h->p);
+    for (int64_t jb = 0; jb < h->ds->p; jb += gw) {
+        const int64_t je = std::min<int64_t>(jb + gw, h->ds->p);
         PH_DISPATCH(NB, {
             const size_t lds = (size_t)GT_ * 4 * NB_ * 64 * sizeof(double);
             hipLaunchKernelGGL((k_resid_write<NB_, GT_>), dim3(row_blocks, cdiv(je - jb, 16 * GT_)), dim3(64 * PH_WPB), lds,
-                               h->stream, (const double *)h->X, h->ldn, row_begin, row_end, U, cp, K, jb, je, stage, nrows);
+                               h->st.stream, (const double *)h->ds->X, h->ds->ldn, row_begin, row_end, U, cp, K, jb, je, stage, nrows);
         });
         KCHECK();
         HIPCHECK(hipMemcpyAsync(out + jb * nrows, stage, (size_t)nrows * (je - jb) * sizeof(double), hipMemcpyDeviceToHost,
-                                h->stream));
-        HIPCHECK(hipStreamSynchronize(h->stream));
+                                h->st.stream));
+        HIPCHECK(hipStreamSynchronize(h->st.stream));
     }
     return INSIDER_OK;
 }
@@ -3100,7 +3037,7 @@ int interaction_glm_body(insider_hip_handle *h, double *const *A, const double *
     if (rc) return rc;
     if (!group || !coeff || !se || !dof) return fail(INSIDER_ERR_ARG, "null argument");
     if (G < 1) return fail(INSIDER_ERR_ARG, "G must be positive");
-    const int64_t n = h->n, p = h->p;
+    const int64_t n = h->ds->n, p = h->ds->p;
     // group tables on the host: members by group (sample order inside a group), chunks of <= PH_CHUNK members
     std::vector<int> cnt((size_t)G + 1, 0);
     for (int64_t i = 0; i < n; ++i) {
@@ -3124,38 +3061,37 @@ int interaction_glm_body(insider_hip_handle *h, double *const *A, const double *
     }
     grp_chunk[G] = (int)ch_begin.size();
     const int nchunks = grp_chunk[G];
-    HIPCHECK(hipSetDevice(h->device));
+    HIPCHECK(hipSetDevice(h->ds->device));
     const int NB = (K + 15) / 16, KPW = 16 * NB, ldw = K + 1;
     if ((rc = ph_prepare(h, A, C, K, subtract, KPW))) return rc;
-    PostWs &w = *h->post;
-    hipStream_t st = h->stream;
+    PostWs &w = h->post;
+    hipStream_t st = h->st.stream;
     // ---- one pass over X: per-sample w = C r and ss = ||r||^2, gene slabs summed in slab order ----------------------
     const int ntiles = cdiv(n, 16), row_blocks = cdiv(ntiles, PH_WPB);
     int64_t slab_len = 0;
     int slabs = 1;
-    double *part = nullptr, *stats = nullptr;
     PH_DISPATCH(NB, {
         // enough blocks for every SIMD of the device several times over, slabs of whole staging rounds
-        const int want = std::max(1, std::min(64, cdiv(4 * h->n_simd, (int64_t)row_blocks * PH_WPB)));
+        const int want = std::max(1, std::min(64, cdiv(4 * h->ds->n_simd, (int64_t)row_blocks * PH_WPB)));
         slab_len = round_up(cdiv(p, want), 16 * GT_);
         slabs = cdiv(p, slab_len);
     });
-    if ((rc = ph_grow(w.part, (size_t)slabs * n * ldw, &part))) return rc;
-    if ((rc = ph_grow(w.stats, (size_t)n * ldw, &stats))) return rc;
-    const double *U = static_cast<const double *>(w.U.p), *cp = static_cast<const double *>(w.cp.p);
+    if ((rc = w.part.grow((size_t)slabs * n * ldw)) || (rc = w.stats.grow((size_t)n * ldw))) return rc;
+    double *part = w.part, *stats = w.stats;
+    const double *U = w.U, *cp = w.cp;
     PH_DISPATCH(NB, {
         const size_t lds = (size_t)2 * GT_ * 4 * NB_ * 64 * sizeof(double);
         hipLaunchKernelGGL((k_resid_stats<NB_, GT_>), dim3(row_blocks, slabs), dim3(64 * PH_WPB), lds, st,
-                           (const double *)h->X, h->ldn, (int)n, p, U, cp, K, slab_len, part);
+                           (const double *)h->ds->X, h->ds->ldn, (int)n, p, U, cp, K, slab_len, part);
     });
     KCHECK();
     hipLaunchKernelGGL(k_sum_partials, dim3(cdiv(n * ldw, 16)), dim3(256), 0, st, (const double *)part, slabs,
                        (int)(n * ldw), stats);
     KCHECK();
     // ---- per-group sums -----------------------------------------------------------------------------------------------
-    int *ints = nullptr;
     const size_t n_ints = (size_t)(G + 1) + members.size() + 2 * std::max(nchunks, 1) + (size_t)(G + 1);
-    if ((rc = ph_grow(w.ints, n_ints, &ints))) return rc;
+    if ((rc = w.ints.grow(n_ints))) return rc;
+    int *ints = w.ints;
     int *d_gptr = ints, *d_mem = d_gptr + (G + 1), *d_cb = d_mem + members.size(), *d_ce = d_cb + std::max(nchunks, 1),
         *d_gc = d_ce + std::max(nchunks, 1);
     std::vector<int> packed;
@@ -3168,9 +3104,8 @@ int interaction_glm_body(insider_hip_handle *h, double *const *A, const double *
     packed.insert(packed.end(), ch_end.begin(), ch_end.end());
     packed.insert(packed.end(), grp_chunk.begin(), grp_chunk.end());
     HIPCHECK(hipMemcpyAsync(ints, packed.data(), packed.size() * sizeof(int), hipMemcpyHostToDevice, st));
-    double *cpart = nullptr, *gsum = nullptr;
-    if ((rc = ph_grow(w.cpart, (size_t)std::max(nchunks, 1) * ldw, &cpart))) return rc;
-    if ((rc = ph_grow(w.gsum, (size_t)G * ldw, &gsum))) return rc;
+    if ((rc = w.cpart.grow((size_t)std::max(nchunks, 1) * ldw)) || (rc = w.gsum.grow((size_t)G * ldw))) return rc;
+    double *cpart = w.cpart, *gsum = w.gsum;
     if (nchunks > 0) {
         hipLaunchKernelGGL(k_ph_chunk_sums, dim3(cdiv(nchunks, 4)), dim3(256), 0, st, (const double *)stats, ldw,
                            (const int *)d_mem, (const int *)d_cb, (const int *)d_ce, nchunks, cpart);
@@ -3180,14 +3115,11 @@ int interaction_glm_body(insider_hip_handle *h, double *const *A, const double *
     KCHECK();
     // ---- G = C C', its reduced Cholesky factor, and every group's coefficients ------------------------------------------
     const int gslabs = cdiv(p, MM_SLAB);
-    double *gpart = nullptr, *gram = nullptr, *L = nullptr, *dinv = nullptr, *outs = nullptr;
-    int *info = nullptr;
-    if ((rc = ph_grow(w.gpart, (size_t)gslabs * K * K, &gpart))) return rc;
-    if ((rc = ph_grow(w.gram, (size_t)K * K, &gram))) return rc;
-    if ((rc = ph_grow(w.L, (size_t)64 * 64, &L))) return rc;
-    if ((rc = ph_grow(w.dinv, 64, &dinv))) return rc;
-    if ((rc = ph_grow(w.info, 2 + 64, &info))) return rc;
-    if ((rc = ph_grow(w.outs, (size_t)2 * G * K + G, &outs))) return rc;
+    if ((rc = w.gpart.grow((size_t)gslabs * K * K)) || (rc = w.gram.grow((size_t)K * K)) || (rc = w.L.grow((size_t)64 * 64)) ||
+        (rc = w.dinv.grow(64)) || (rc = w.info.grow(2 + 64)) || (rc = w.outs.grow((size_t)2 * G * K + G)))
+        return rc;
+    double *gpart = w.gpart, *gram = w.gram, *L = w.L, *dinv = w.dinv, *outs = w.outs;
+    int *info = w.info;
     PH_DISPATCH(NB, {
         (void)GT_;
         hipLaunchKernelGGL((k_mm_reduce<NB_>), dim3(gslabs, cdiv(K, 16)), dim3(64), 0, st, cp, (int64_t)KPW, cp,
@@ -3196,11 +3128,11 @@ int interaction_glm_body(insider_hip_handle *h, double *const *A, const double *
     KCHECK();
     hipLaunchKernelGGL(k_sum_partials, dim3(cdiv(K * K, 16)), dim3(256), 0, st, (const double *)gpart, gslabs, K * K, gram);
     KCHECK();
-    hipLaunchKernelGGL(k_glm_factor, dim3(1), dim3(64), 0, st, (const double *)gram, (const int *)w.nz.p, K, L, dinv, info);
+    hipLaunchKernelGGL(k_glm_factor, dim3(1), dim3(64), 0, st, (const double *)gram, (const int *)w.nz, K, L, dinv, info);
     KCHECK();
     double *d_coeff = outs, *d_se = outs + (size_t)G * K, *d_dof = outs + (size_t)2 * G * K;
     hipLaunchKernelGGL(k_glm_groups, dim3(G), dim3(64), 0, st, (const double *)gsum, ldw, (const int *)d_gptr, K, p,
-                       (const int *)w.nz.p, (const double *)L, (const double *)dinv, (const int *)info, G, d_coeff, d_se,
+                       (const int *)w.nz, (const double *)L, (const double *)dinv, (const int *)info, G, d_coeff, d_se,
                        d_dof);
     KCHECK();
     int hinfo[2] = {0, 0};
@@ -3220,10 +3152,10 @@ int interaction_glm_body(insider_hip_handle *h, double *const *A, const double *
 // a failed call may leave work enqueued: drain the stream so that the next call starts clean
 int ph_finish(insider_hip_handle *h, int rc)
 {
-    if (rc != INSIDER_OK && h && h->stream) {
+    if (rc != INSIDER_OK && h && h->st.stream) {
         const std::string keep = g_err;
-        (void)hipSetDevice(h->device);
-        (void)hipStreamSynchronize(h->stream);
+        (void)hipSetDevice(h->ds->device);
+        (void)hipStreamSynchronize(h->st.stream);
         g_err = keep;
     }
     return rc;
@@ -3236,29 +3168,26 @@ int variance_decomposition_body(insider_hip_handle *h, double *const *A, const d
                                 int entries, double *out)
 {
     if (!h) return fail(INSIDER_ERR_ARG, "null handle");
-    const std::vector<int32_t> every((size_t)h->c + 2, 1);   // every block enters the fit
+    const std::vector<int32_t> every((size_t)h->ds->c + 2, 1);   // every block enters the fit
     int rc = ph_check(h, A, C, inc_continuous, K, every.data());
     if (rc) return rc;
     if (entries < 0 || entries > 2) return fail(INSIDER_ERR_ARG, "entries must be 0 (all), 1 (train) or 2 (test)");
     if (!out) return fail(INSIDER_ERR_ARG, "null output");
-    HIPCHECK(hipSetDevice(h->device));
-    if (!h->post) h->post = new PostWs();
-    PostWs &w = *h->post;
-    hipStream_t st = h->stream;
-    const int nb = h->c + inc_continuous, SL = h->SL, KPW = 16 * ((K + 15) / 16), rec = 4 + 3 * nb;
-    const int64_t n = h->n, p = h->p;
-    double *vin = nullptr, *Ast = nullptr, *T = nullptr, *R = nullptr;
-    if ((rc = ph_grow(w.vin, (size_t)(SL + p) * K, &vin))) return rc;
-    if ((rc = ph_grow(w.Ast, (size_t)SL * KPW, &Ast))) return rc;
-    if ((rc = ph_grow(w.vtab, (size_t)p * SL, &T))) return rc;
-    if ((rc = ph_grow(w.vrec, (size_t)p * rec, &R))) return rc;
+    HIPCHECK(hipSetDevice(h->ds->device));
+    PostWs &w = h->post;
+    hipStream_t st = h->st.stream;
+    const int nb = h->ds->c + inc_continuous, SL = h->ds->SL, KPW = 16 * ((K + 15) / 16), rec = 4 + 3 * nb;
+    const int64_t n = h->ds->n, p = h->ds->p;
+    if ((rc = w.vin.grow((size_t)(SL + p) * K)) || (rc = w.Ast.grow((size_t)SL * KPW)) || (rc = w.vtab.grow((size_t)p * SL)) ||
+        (rc = w.vrec.grow((size_t)p * rec)))
+        return rc;
+    double *vin = w.vin, *Ast = w.Ast, *T = w.vtab, *R = w.vrec;
     // [A_stack; B_c] as SL rows of KPW (the layout of ph_prepare), C as p rows of K
     for (int b = 0; b < nb; ++b) {
-        const int L = b < h->c ? h->n_levels[b] : h->m;
-        const int off = b < h->c ? h->lvl_off[b] : h->SLcat;
-        HIPCHECK(hipMemcpyAsync(vin + (size_t)off * K, A[b], (size_t)L * K * sizeof(double), hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_pack_A, dim3(cdiv((int64_t)L * KPW, 256)), dim3(256), 0, st, (const double *)(vin + (size_t)off * K),
-                           L, K, KPW, Ast + (size_t)off * KPW);
+        const DataSet::Block blk = h->ds->block(b);
+        HIPCHECK(hipMemcpyAsync(vin + (size_t)blk.off * K, A[b], (size_t)blk.rows * K * sizeof(double), hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_pack_A, dim3(cdiv((int64_t)blk.rows * KPW, 256)), dim3(256), 0, st,
+                           (const double *)(vin + (size_t)blk.off * K), blk.rows, K, KPW, Ast + (size_t)blk.off * KPW);
         KCHECK();
     }
     double *Cd = vin + (size_t)SL * K;
@@ -3274,9 +3203,9 @@ int variance_decomposition_body(insider_hip_handle *h, double *const *A, const d
     KCHECK();
     // one pass over X per window of BW blocks
     const int sel = entries == 0 ? 0 : entries == 1 ? CODE_TRAIN : CODE_TEST;
-    const int m = inc_continuous ? h->m : 0;
+    const int m = inc_continuous ? h->ds->m : 0;
     // (at most 60 KiB of dynamic LDS beside the kernel's static reduction buffer: no launch attribute needed)
-    const double budget = std::min(std::max(h->vd_stage_kb, 0.0), 60.0) * 1024.0;
+    const double budget = std::min(std::max(h->opt.vd_stage_kb, 0.0), 60.0) * 1024.0;
 #define VD_LAUNCH(BW_, GW_)                                                                                                 \
     do {                                                                                                                     \
         const bool staged = (double)GW_ * SL * sizeof(double) <= budget;                                                     \
@@ -3284,13 +3213,13 @@ int variance_decomposition_body(insider_hip_handle *h, double *const *A, const d
         for (int b0 = 0; b0 < nb; b0 += BW_) {                                                                               \
             if (staged)                                                                                                      \
                 hipLaunchKernelGGL((k_vd_stats<BW_, GW_, true>), dim3(cdiv(p, GW_)), dim3(64 * VD_WAVES),                    \
-                                   (size_t)GW_ * SL * sizeof(double), st, (const double *)h->X, (const uint8_t *)h->codes,   \
-                                   h->ldn, (int)n, p, (const int *)h->lev, (const int *)h->lvl_off_d, h->c,                  \
-                                   (const double *)h->Zc, m, h->SLcat, (const double *)T, SL, sel, nb, b0, R);               \
+                                   (size_t)GW_ * SL * sizeof(double), st, (const double *)h->ds->X, (const uint8_t *)h->ds->codes,   \
+                                   h->ds->ldn, (int)n, p, (const int *)h->ds->lev, (const int *)h->ds->lvl_off_d, h->ds->c,                  \
+                                   (const double *)h->ds->Zc, m, h->ds->SLcat, (const double *)T, SL, sel, nb, b0, R);               \
             else                                                                                                             \
                 hipLaunchKernelGGL((k_vd_stats<BW_, GW_, false>), dim3(cdiv(p, GW_)), dim3(64 * VD_WAVES), 0, st,            \
-                                   (const double *)h->X, (const uint8_t *)h->codes, h->ldn, (int)n, p, (const int *)h->lev,  \
-                                   (const int *)h->lvl_off_d, h->c, (const double *)h->Zc, m, h->SLcat, (const double *)T,   \
+                                   (const double *)h->ds->X, (const uint8_t *)h->ds->codes, h->ds->ldn, (int)n, p, (const int *)h->ds->lev,  \
+                                   (const int *)h->ds->lvl_off_d, h->ds->c, (const double *)h->ds->Zc, m, h->ds->SLcat, (const double *)T,   \
                                    SL, sel, nb, b0, R);                                                                      \
             KCHECK();                                                                                                        \
         }                                                                                                                    \

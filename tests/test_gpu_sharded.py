@@ -384,3 +384,55 @@ def test_clones_share_the_data_set_and_outlive_their_source():
     assert np.array_equal(again["column_factor"], alone[0]["column_factor"])
     for hd in handles[1:]:
         hd.close()
+
+
+def test_clones_leak_no_device_memory_and_start_without_diagnostics():
+    """Handles of one data set own their memory by type: four rounds of create, two clones, fits at K = 8 and K = 20 on
+    every handle (the workspace is rebuilt), residual, interaction GLM and variance decomposition on a clone, then the
+    source destroyed first and the clones after it.  The data set is n = 2000 x p = 6000 (X alone is 96 MB on the device,
+    the workspace at K = 20 over 40 MB): free device memory (hipMemGetInfo) after the last round must be within 32 MB of
+    the figure after the first round, where one leaked data set or workspace per round would have cost 120 MB or more by then.  A new
+    clone reports zero for the diagnostics of the last call ("col_solver", "col_eval", "col_ridge_fallback", "row_kernels",
+    "vd_path") while its source reports its own."""
+    import ctypes
+    from insider_amd import api
+    hip = ctypes.CDLL("libamdhip64.so")
+
+    def free_bytes():
+        f, t = ctypes.c_size_t(0), ctypes.c_size_t(0)
+        assert hip.hipMemGetInfo(ctypes.byref(f), ctypes.byref(t)) == 0
+        return f.value
+
+    w = workloads.small(n=2000, p=6000, level_counts=(12, 5), K=8, f=0.1, seed=31, with_na=True)
+    keys = ("col_solver", "col_eval", "col_ridge_fallback", "row_kernels", "vd_path")
+    rng = np.random.default_rng(5)
+    inits = {K: ([np.asfortranarray(rng.standard_normal((int(L), K)) * 1e-2) for L in w.n_levels],
+                 np.asfortranarray(rng.standard_normal((K, w.p)) * 1e-2)) for K in (8, 20)}
+
+    def fit(hd, K):
+        A, C = inits[K]
+        return hd.optimize([a.copy(order="F") for a in A], C.copy(order="F"), K, 2.0, 2.0, 0.4, tuning=1, max_iter=3,
+                           global_tol=-1.0, seed=3)
+
+    free = []
+    for _ in range(4):
+        ds = api.InsiderData(w.X, w.levels, w.M_train, w.M_test)
+        fit(ds, 8)
+        ds.variance_decomposition(list(fit(ds, 20)["row_matrices"].values()), inits[20][1])
+        assert ds.info("col_solver") != 0 and ds.info("row_kernels") != 0 and ds.info("vd_path") != 0
+        clones = [ds.clone(), ds.clone()]
+        for cl in clones:
+            assert [cl.info(k) for k in keys] == [0.0] * len(keys)
+        for hd in [ds] + clones:
+            fit(hd, 8)
+            r = fit(hd, 20)
+        A = list(r["row_matrices"].values())
+        cl = clones[0]
+        assert cl.residual(A, r["column_factor"]).shape == (w.n, w.p)
+        cl.interaction_glm(A, r["column_factor"], w.levels[:, 1], subtract=[1, 0])
+        cl.variance_decomposition(A, r["column_factor"])
+        ds.close()
+        for cl in clones:
+            cl.close()
+        free.append(free_bytes())
+    assert abs(free[-1] - free[0]) < (32 << 20), free
