@@ -271,6 +271,20 @@ int insider_hip_masked_gram_cols(insider_hip_handle *h, const double *R, int K, 
 int insider_hip_masked_gram_rows(insider_hip_handle *h, const double *C, int K, double *H_out, double *b_out);
 
 /*
+ * The column-side statistics the column solve of insider_hip_optimize_col() (tuning = 1) reads, from the row factors A
+ * alone (as in insider_hip_optimize(); no column factor): R = sum_i Z_i A_i (+ Z_c A_c, inc_continuous = 1), R'R, X'R, then
+ * the statistics kernel the handle's options pick (insider_hip_get_info "col_stats_kernel") and its record densified.  For
+ * every gene j with training entries T(j):
+ *   G_out  p blocks of K x K column-major: sum_{i in T(j)} r_i r_i';
+ *   q_out  p blocks of K: sum_{i in T(j)} x_ij r_i;
+ *   ss_out p doubles: sum_{i not in T(j)} x_ij^2 (held-out and NA entries; what the test SSE starts from).
+ * Writes the workspace buffers insider_hip_optimize_col() overwrites and nothing else an optimize() reads.  A sharded handle
+ * (world > 1) returns INSIDER_ERR_UNSUPPORTED.
+ */
+int insider_hip_col_stats(insider_hip_handle *h, double *const *A, int inc_continuous, int K, double *G_out, double *q_out,
+                          double *ss_out);
+
+/*
  * glm_interaction() (R/glm_interaction.R:2-30) on the resident data set: per-level coefficients and standard errors of
  * interaction effects on the metagenes, without the residual matrix ever leaving the device.
  *   Covariate blocks are numbered 0..c-1 (the categorical covariates) and, with inc_continuous = 1, c (the continuous
@@ -338,6 +352,12 @@ int insider_hip_get_profile(insider_hip_handle *h, double *out12);
  * and for the evaluation pass after it; 0 = none: 1 k_ridge_cols_reg, 2 k_ridge_cols, 3 k_cd_cols_reg with one or two slots,
  * 4 k_cd_cols_reg with three slots, 5 k_cd_cols<16,4>, 6 k_cd_cols<32,2>, 7 k_cd_cols<64,1>, 8 / 9 / 10 k_cd_cols_r16<1 / 2 / 3>),
  * "col_ridge_fallback" (1: the last ridge solve also launched k_ridge_cols for the genes k_ridge_cols_reg marked),
+ * "col_stats_kernel" (the kernel the last column-side statistics launch ran, in optimize(), optimize_col() or col_stats(): 0 =
+ * none yet, 1 k_list_stats<NB>, 2 k_list_stats4, 3 k_col_factored, 4 k_col_paircnt, 5 k_col_paircnt with real-valued counts
+ * (continuous covariates), 6 / 7 k_col_paircnt4 with MAXS = 4 / 8 k-steps, 8 k_col_paircnt4 with MAXS = 4 and real-valued
+ * counts; MAXS = 8 with real-valued counts is never launched), "col_stats_tickets" (the ticket counters k_col_paircnt4 drew
+ * genes from: 1 or 16; 0 for the other kernels), "col_stats_blocks" (k_col_paircnt4's grid size, 0 for the other kernels: its
+ * blocks walk the genes in groups of four when 4 x blocks < p),
  * "vd_path" (the form of k_vd_stats the last insider_hip_variance_decomposition() ran: 1 = level tables in LDS, 2 = read from
  * global memory; 0 = none yet),
  * "row_kernels" (a bit mask of the row-phase kernel forms the last optimize() / optimize_row() launched, reset at the start of

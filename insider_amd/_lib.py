@@ -27,12 +27,15 @@ SYMBOLS = (
     "insider_hip_optimize_oneshot_ex", "insider_hip_strong_cd_xy", "insider_hip_solve_sympd", "insider_hip_get_info",
     "insider_hip_comm_unique_id", "insider_hip_comm_init", "insider_hip_get_array", "insider_hip_clone",
     "insider_hip_optimize_continuous_v2", "insider_hip_residual", "insider_hip_interaction_glm",
-    "insider_hip_variance_decomposition",
+    "insider_hip_variance_decomposition", "insider_hip_col_stats",
 )
 COMM_ID_BYTES = 128
 # insider_hip_get_info("col_solver" / "col_eval"): the column-solve kernel behind each code (include/insider_hip.h)
 COL_SOLVERS = ("none", "ridge_reg", "ridge", "cd_reg", "cd_reg3", "cd_cols16", "cd_cols32", "cd_cols64", "cd_r16_1", "cd_r16_2",
                "cd_r16_3")
+# insider_hip_get_info("col_stats_kernel"): the column-side statistics kernel behind each code (include/insider_hip.h)
+COL_STATS_KERNELS = ("none", "list", "list4", "factored", "paircnt", "paircnt_zt", "paircnt4_ms4", "paircnt4_ms8",
+                     "paircnt4_ms4_zt")
 # insider_hip_get_info("row_kernels"): the row-phase kernel form behind each bit, bit 0 first (include/insider_hip.h)
 ROW_KERNELS = ("wgemm4", "wgemm5", "wgemm6", "wgemm7", "wgemm_chunks", "wsyrk", "gram_side",
                "gene_u_cnt", "gene_u", "gene_uc",
@@ -113,6 +116,7 @@ def load():
                                           C.c_uint64, C.c_uint32, C.c_int, C.c_int, C.c_int, dp, i32p]
     lib.insider_hip_masked_gram_cols.argtypes = [C.c_void_p, dp, C.c_int, dp, dp]
     lib.insider_hip_masked_gram_rows.argtypes = [C.c_void_p, dp, C.c_int, dp, dp]
+    lib.insider_hip_col_stats.argtypes = [C.c_void_p, C.POINTER(dp), C.c_int, C.c_int, dp, dp, dp]
     lib.insider_hip_residual.argtypes = [C.c_void_p, C.POINTER(dp), dp, C.c_int, C.c_int, i32p, C.c_int64, C.c_int64, dp]
     lib.insider_hip_interaction_glm.argtypes = [C.c_void_p, C.POINTER(dp), dp, C.c_int, C.c_int, i32p, i32p, C.c_int, dp,
                                                 dp, dp]

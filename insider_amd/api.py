@@ -249,6 +249,20 @@ class InsiderData:
         _lib.check(_lib.load().insider_hip_masked_gram_cols(self._h, _lib.ptr(R), K, _lib.ptr(G), _lib.ptr(q)))
         return G, q
 
+    def col_stats(self, cfd_factors, inc_continuous=0):
+        """The column-side statistics the column solve reads (insider_hip_col_stats), from the row factors alone: per gene j
+        the training Gram G[j] = R_t'R_t, q[j] = R_t'x_t over its training entries t, and ss[j], the sum of x^2 over the
+        others (held out and NA).  R = sum_i Z_i A_i (+ Z_c A_c with inc_continuous); the statistics kernel is the one the
+        handle's options pick for a fit (info "col_stats_kernel")."""
+        K = int(np.asarray(cfd_factors[0]).shape[1])
+        A, _, Aptrs = self._marshal(cfd_factors, np.zeros((K, self.p), order="F"), K, inc_continuous)
+        G = np.zeros((self.p, K, K))
+        q = np.zeros((self.p, K))
+        ss = np.zeros(self.p)
+        _lib.check(_lib.load().insider_hip_col_stats(self._h, Aptrs, int(inc_continuous), K, _lib.ptr(G), _lib.ptr(q),
+                                                     _lib.ptr(ss)))
+        return G, q, ss
+
     def masked_gram_rows(self, Cmat):
         Cmat = _lib.f64(Cmat)
         K = Cmat.shape[0]

@@ -352,6 +352,9 @@ struct insider_hip_handle {
     // of the last column solve: the kernel that ran the solve and the one that ran the evaluation pass after it (ColSolver), and
     // whether the ridge solve launched the general-route fallback for the genes the register kernel marked
     int col_solver = 0, col_eval = 0, col_ridge_fallback = 0;
+    // of the last column-side statistics launch (launch_col_stats): the kernel that formed them (ColStatsKernel), and for
+    // k_col_paircnt4 the ticket counters it drew from and its grid size (0 for the other kernels)
+    int col_stats_kernel = 0, col_stats_tickets = 0, col_stats_blocks = 0;
     // of the last optimize() / optimize_row(): one bit per row-phase kernel form it launched (RowKernel)
     uint64_t row_kernels = 0;
     // the form the last variance decomposition ran (1 = tables in LDS, 2 = from global)
@@ -830,6 +833,14 @@ int col_stats_path(const insider_hip_handle *h)
 }
 bool use_col_factored(const insider_hip_handle *h) { return col_stats_path(h) != 0; }
 
+// the kernels launch_col_stats() can launch, as insider_hip_get_info("col_stats_kernel") reports them
+// (include/insider_hip.h; insider_amd/_lib.py COL_STATS_KERNELS mirrors the names).  k_col_paircnt4<., ., 8, true> is compiled
+// (the PC4 macro instantiates it) but never launched: real-valued counts with more than four k-steps take k_col_paircnt.
+enum ColStatsKernel {
+    CSK_NONE = 0, CSK_LIST = 1, CSK_LIST4 = 2, CSK_FACTORED = 3, CSK_PAIRCNT = 4, CSK_PAIRCNT_ZT = 5, CSK_PAIRCNT4_MS4 = 6,
+    CSK_PAIRCNT4_MS8 = 7, CSK_PAIRCNT4_MS4_ZT = 8
+};
+
 // the pair-count statistics kernel (insider_col_factored.hpp) over every gene, on the main stream
 int launch_paircnt(insider_hip_handle *h, const ColFacArgs &a)
 {
@@ -864,6 +875,9 @@ int launch_paircnt(insider_hip_handle *h, const ColFacArgs &a)
             KCHECK();
             // what the launch takes from each counter in use: its items and one ticket per wave (only once it is known to be enqueued)
             h->ws.pc4_base[which] += (unsigned)cap + 4u * (unsigned)(nb / npart);
+            h->col_stats_kernel = a.zt ? CSK_PAIRCNT4_MS4_ZT : a.nsteps <= 4 ? CSK_PAIRCNT4_MS4 : CSK_PAIRCNT4_MS8;
+            h->col_stats_tickets = npart;
+            h->col_stats_blocks = nb;
             return INSIDER_OK;
         }
     }
@@ -874,6 +888,8 @@ int launch_paircnt(insider_hip_handle *h, const ColFacArgs &a)
         else hipLaunchKernelGGL((k_col_paircnt<NB_, 4, false>), dim3(blocks), dim3(256), lds, h->st.stream, a);
     });
     KCHECK();
+    h->col_stats_kernel = a.zt ? CSK_PAIRCNT_ZT : CSK_PAIRCNT;
+    h->col_stats_tickets = h->col_stats_blocks = 0;
     return INSIDER_OK;
 }
 
@@ -912,11 +928,16 @@ int launch_col_stats(insider_hip_handle *h, bool timed)
                 const size_t lds = ((size_t)(a.tab_rows + 1) * Geo<NB_>::KP + (size_t)4 * 16 * 17) * sizeof(double) + (size_t)4 * CF_CAP * 2;
                 hipLaunchKernelGGL((k_col_factored<NB_, 4>), dim3(cdiv(h->ds->p, 4)), dim3(256), lds, h->st.stream, a);
             });
+            h->col_stats_kernel = CSK_FACTORED;
+            h->col_stats_tickets = h->col_stats_blocks = 0;
         }
         KCHECK();
     } else {
-        rc = launch_list_stats(h, true, 1, h->ws.R, h->ws.stat_col, h->ws.RtR);   // the record's K x K part = R'R - complement
+        uint64_t mark = 0;
+        rc = launch_list_stats(h, true, 1, h->ws.R, h->ws.stat_col, h->ws.RtR, &mark);   // the record's K x K part = R'R - complement
         if (rc) return rc;
+        h->col_stats_kernel = (mark & rk_bit(RK_LIST_STATS4)) ? CSK_LIST4 : CSK_LIST;
+        h->col_stats_tickets = h->col_stats_blocks = 0;
     }
     return t.end(h, h->ev_col);
 }
@@ -1585,6 +1606,7 @@ int upload_factors(insider_hip_handle *h, double *const *A, const double *C, int
         KCHECK();
         HIPCHECK(hipStreamSynchronize(st));   // stage is reused
     }
+    if (!C) return INSIDER_OK;   // (the row factors alone: insider_hip_col_stats)
     HIPCHECK(hipMemcpyAsync(h->ws.stage, C, (size_t)d.p * K * sizeof(double), hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_pack_rows, dim3(cdiv(d.p * KP, 256)), dim3(256), 0, st, (const double *)h->ws.stage, d.p, K, KP, h->ws.C);
     KCHECK();
@@ -2818,7 +2840,7 @@ static int masked_gram_common(insider_hip_handle *h, bool cols, const double *Fh
     NB_DISPATCH(h->ws.NB, {
         (void)WPB_;
         hipLaunchKernelGGL((k_stats_to_dense<NB_>), dim3((unsigned)units), dim3(64), 0, h->st.stream, (const double *)stat,
-                           nseg, (int)units, K, (const double *)full, (const double *)qf, Gd, qd);
+                           nseg, (int)units, K, (const double *)full, (const double *)qf, Gd, qd, (double *)nullptr);
     });
     KCHECK();
     HIPCHECK(hipStreamSynchronize(h->st.stream));
@@ -2836,6 +2858,36 @@ int insider_hip_masked_gram_cols(insider_hip_handle *h, const double *R, int K, 
 int insider_hip_masked_gram_rows(insider_hip_handle *h, const double *C, int K, double *H_out, double *b_out)
 {
     return masked_gram_common(h, false, C, K, H_out, b_out);
+}
+
+// The column-side statistics the column solve reads, densified: the first half of insider_hip_optimize_col() with tuning = 1
+// (R, R'R, Qfull; the statistics kernel the handle's options pick), then the record of every gene as G, q and its corner.
+int insider_hip_col_stats(insider_hip_handle *h, double *const *A, int inc_continuous, int K, double *G_out, double *q_out,
+                          double *ss_out)
+{
+    if (!h || !G_out || !q_out || !ss_out) return fail(INSIDER_ERR_ARG, "null argument");
+    int rc = check_factor_args(h, A, G_out, inc_continuous, 1);   // (G_out stands in for the column factor this entry does not take)
+    if (rc) return rc;
+    if (h->world > 1) return fail(INSIDER_ERR_UNSUPPORTED, "insider_hip_col_stats on a sharded handle");
+    HIPCHECK(hipSetDevice(h->ds->device));
+    if ((rc = ensure_workspace(h, K))) return rc;
+    if ((rc = upload_factors(h, A, nullptr, K))) return rc;
+    if ((rc = phase_R(h))) return rc;
+    if ((rc = launch_col_stats(h, false))) return rc;
+    const int64_t p = h->ds->p;
+    DevBuf<double> Gd, qd, sd;
+    if ((rc = Gd.alloc((size_t)p * K * K)) || (rc = qd.alloc((size_t)p * K)) || (rc = sd.alloc((size_t)p))) return rc;
+    NB_DISPATCH(h->ws.NB, {
+        (void)WPB_;   // full = null: the record's K x K part already holds XtX_j (R'R - complement)
+        hipLaunchKernelGGL((k_stats_to_dense<NB_>), dim3((unsigned)p), dim3(64), 0, h->st.stream, (const double *)h->ws.stat_col, 1,
+                           (int)p, K, (const double *)nullptr, (const double *)h->ws.Qfull, Gd, qd, sd);
+    });
+    KCHECK();
+    HIPCHECK(hipStreamSynchronize(h->st.stream));
+    HIPCHECK(hipMemcpy(G_out, Gd, (size_t)p * K * K * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHECK(hipMemcpy(q_out, qd, (size_t)p * K * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHECK(hipMemcpy(ss_out, sd, (size_t)p * sizeof(double), hipMemcpyDeviceToHost));
+    return INSIDER_OK;
 }
 
 double insider_hip_last_cd_ms(void) { return g_last_cd_ms; }
@@ -2869,6 +2921,9 @@ int insider_hip_get_info(insider_hip_handle *h, const char *name, double *out)
     else if (s == "col_solver") *out = h->col_solver;               // last column solve: the kernel that ran it (ColSolver) ...
     else if (s == "col_eval") *out = h->col_eval;                   // ... and the one that ran its evaluation pass (0 = none)
     else if (s == "col_ridge_fallback") *out = h->col_ridge_fallback;   // ... and whether the ridge solve launched the general route
+    else if (s == "col_stats_kernel") *out = h->col_stats_kernel;   // last column-side statistics: the kernel (ColStatsKernel) ...
+    else if (s == "col_stats_tickets") *out = h->col_stats_tickets; // ... k_col_paircnt4's ticket counters (1 or 16; 0: another kernel)
+    else if (s == "col_stats_blocks") *out = h->col_stats_blocks;   // ... and its grid size (0: another kernel)
     else if (s == "row_kernels") *out = (double)h->row_kernels;     // last optimize() / optimize_row(): row-phase kernel forms (RowKernel bits)
     else if (s == "cd_ms_steady") *out = h->steady_cd_ms;           // option "profile": mean over outer iterations >= 5 of the last call
     else if (s == "col_stats_ms_steady") *out = h->steady_col_ms;

@@ -1779,11 +1779,14 @@ __global__ void __launch_bounds__(64) k_row_dense_xty(const double *__restrict__
 }
 
 // blocks of sum f~ f~' (stat layout) -> dense K x K column-major XtX = full - complement and Xty = qfull - row K
+// full == null: the record's K x K part is XtX itself (a column record written with base = R'R); ss_out (optional): the
+// record's corner, the sum of x^2 over the complement entries
 template <int NB>
 __global__ void __launch_bounds__(64) k_stats_to_dense(const double *__restrict__ stat, int nseg, int units, int K,
-                                                       const double *__restrict__ full /*KP x KP*/,
+                                                       const double *__restrict__ full /*KP x KP or null*/,
                                                        const double *__restrict__ qfull /*units x KP*/,
-                                                       double *__restrict__ G_out, double *__restrict__ q_out)
+                                                       double *__restrict__ G_out, double *__restrict__ q_out,
+                                                       double *__restrict__ ss_out)
 {
     constexpr int KP = Geo<NB>::KP, NBLK = Geo<NB>::NBLK, STAT = Geo<NB>::STAT;
     __shared__ double s_H[KP * KP];
@@ -1799,13 +1802,30 @@ __global__ void __launch_bounds__(64) k_stats_to_dense(const double *__restrict_
 #pragma unroll
             for (int q = 0; q < 4; ++q) h[b][q] += src[b * 256 + (sub + 4 * q) * 16 + c16];
     }
-    acc_to_lds<NB>(h, s_H, lane);
+    // the lower triangle of the record and its mirror image (not acc_to_lds: the diagonal blocks of a factored record are not
+    // symmetric — row KP - 1 holds the complement X'r, column KP - 1 zeros — and their two halves would race for one cell)
+    {
+        int blk = 0;
+#pragma unroll
+        for (int bi = 0; bi < NB; ++bi)
+#pragma unroll
+            for (int bj = 0; bj <= bi; ++bj, ++blk)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int a = 16 * bi + sub + 4 * r, b = 16 * bj + c16;
+                    if (a >= b) {
+                        s_H[a * KP + b] = h[blk][r];
+                        s_H[b * KP + a] = h[blk][r];
+                    }
+                }
+    }
     wave_sync();
     for (int i = lane; i < K * K; i += WAVE) {
         const int x = i % K, y = i / K;
-        G_out[(size_t)u * K * K + i] = full[x * KP + y] - s_H[x * KP + y];
+        G_out[(size_t)u * K * K + i] = full ? full[x * KP + y] - s_H[x * KP + y] : s_H[x * KP + y];
     }
     if (lane < K) q_out[(size_t)u * K + lane] = qfull[(size_t)u * KP + lane] - s_H[(KP - 1) * KP + lane];
+    if (ss_out && lane == 0) ss_out[u] = s_H[(KP - 1) * KP + KP - 1];
 }
 
 }  // namespace insider

@@ -46,6 +46,20 @@ def test_row_kernel_bits_are_documented_and_distinct():
     assert [e.strip().split("=")[0].strip()[3:].lower() for e in enum.split(",") if e.strip()] == list(names)
 
 
+def test_col_stats_kernel_codes_match_the_library():
+    """insider_hip_get_info("col_stats_kernel"): _lib.COL_STATS_KERNELS names code i as the library's ColStatsKernel
+    enumeration does, and the header documents the key."""
+    names = _lib.COL_STATS_KERNELS
+    assert len(set(names)) == len(names) and names[0] == "none"
+    src = open(os.path.join(ROOT, "insider_amd", "csrc", "insider_hip.hip")).read()
+    enum = re.search(r"enum ColStatsKernel \{(.*?)\};", src, re.S).group(1)
+    items = [e.split("=") for e in re.sub(r"//[^\n]*", "", enum).split(",") if e.strip()]
+    assert [(k.strip()[4:].lower(), int(v)) for k, v in items] == [(name, i) for i, name in enumerate(names)]
+    hdr = open(os.path.join(ROOT, "include", "insider_hip.h")).read()
+    for key in ("col_stats_kernel", "col_stats_tickets", "col_stats_blocks"):
+        assert f'"{key}"' in hdr, key
+
+
 def test_product_never_imports_oracle():
     # only tests/, smoke() and bench.py's cpu_baseline leg may touch oracle/
     for dirpath, _, files in os.walk(os.path.join(ROOT, "insider_amd")):
