@@ -214,10 +214,12 @@ int insider_hip_optimize_col(insider_hip_handle *h, double *const *A, double *C,
 /*
  * strong_coordinate_descent (src/coordinate_descent.cpp:56-127; .Call symbol
  * _insider_strong_coordinate_descent, src/RcppExports.cpp:35-50), batched: nprob independent K-variable
- * elastic-net subproblems, one wavefront each, solved in covariance form from (XtX, Xty) — the design
- * matrix X and outcome y of the reference signature enter only through XtX = X'X and Xty = X'y, which the
- * reference's callers always pass alongside (src/optimize.cpp:228,246), so they are not taken here.
- *   XtX    nprob blocks of K x K (column-major; symmetric), Xty / wstart / beta_out nprob blocks of K
+ * elastic-net subproblems solved in covariance form from (XtX, Xty), by the kernels of the column update
+ * (insider_hip_last_cd_solver() says which) — the design matrix X and outcome y of the reference signature
+ * enter only through XtX = X'X and Xty = X'y, which the reference's callers always pass alongside
+ * (src/optimize.cpp:228,246), so they are not taken here.
+ *   XtX    nprob blocks of K x K (column-major; symmetric: only the upper triangle is read), Xty / wstart /
+ *          beta_out nprob blocks of K
  *   seed, iter  key the per-sweep coordinate order (include/insider_perm.h; the same for every subproblem)
  *   sweeps_out  optional, nprob ints
  */
@@ -379,10 +381,12 @@ int insider_hip_get_info(insider_hip_handle *h, const char *name, double *out);
  * period; bytes 0..K-1 of row s = the coordinates of sweep s in visiting order, include/insider_perm.h). */
 int insider_hip_get_array(insider_hip_handle *h, const char *name, void *out, int64_t bytes);
 
-/* Diagnostics: per-gene sweep counts of the last column update (p ints), and the HIP-event time in ms of the
- * kernel launched by the calling THREAD's last insider_hip_strong_cd() / _xy(). */
+/* Diagnostics: per-gene sweep counts of the last column update (p ints); of the calling THREAD's last
+ * insider_hip_strong_cd() / _xy(), the HIP-event time in ms of its solve launches (summed over the chunks of a large
+ * batch) and the kernel that ran them, coded as insider_hip_get_info("col_solver") codes it. */
 int insider_hip_get_sweeps(insider_hip_handle *h, int32_t *out);
 double insider_hip_last_cd_ms(void);
+int insider_hip_last_cd_solver(void);
 
 #ifdef __cplusplus
 }

@@ -27,10 +27,11 @@ SYMBOLS = (
     "insider_hip_optimize_oneshot_ex", "insider_hip_strong_cd_xy", "insider_hip_solve_sympd", "insider_hip_get_info",
     "insider_hip_comm_unique_id", "insider_hip_comm_init", "insider_hip_get_array", "insider_hip_clone",
     "insider_hip_optimize_continuous_v2", "insider_hip_residual", "insider_hip_interaction_glm",
-    "insider_hip_variance_decomposition", "insider_hip_col_stats",
+    "insider_hip_variance_decomposition", "insider_hip_col_stats", "insider_hip_last_cd_solver",
 )
 COMM_ID_BYTES = 128
-# insider_hip_get_info("col_solver" / "col_eval"): the column-solve kernel behind each code (include/insider_hip.h)
+# insider_hip_get_info("col_solver" / "col_eval") and insider_hip_last_cd_solver(): the column-solve kernel behind each code
+# (include/insider_hip.h)
 COL_SOLVERS = ("none", "ridge_reg", "ridge", "cd_reg", "cd_reg3", "cd_cols16", "cd_cols32", "cd_cols64", "cd_r16_1", "cd_r16_2",
                "cd_r16_3")
 # insider_hip_get_info("col_stats_kernel"): the column-side statistics kernel behind each code (include/insider_hip.h)
@@ -124,6 +125,7 @@ def load():
     lib.insider_hip_get_profile.argtypes = [C.c_void_p, dp]
     lib.insider_hip_get_sweeps.argtypes = [C.c_void_p, i32p]
     lib.insider_hip_last_cd_ms.restype = C.c_double
+    lib.insider_hip_last_cd_solver.restype = C.c_int
     _lib = lib
     return lib
 

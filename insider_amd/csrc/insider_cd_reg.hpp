@@ -180,7 +180,7 @@ struct RegState {
     REG_LDS REG_CAT(REG_LOADS_, REG_KM)(REG_AD)                       \
     "s_branch Lgo%=\n"                                                \
     ".p2align 8\n"                                                    \
-    "insider_cdtab_" REG_STR(REG_KM) "_%c[who]:\n"                     \
+    "insider_cdtab_" REG_STR(REG_KM) ":\n"                            \
     "Lc%=:\n"
 #define REG_DPP4(D0, D1, S0, S1, CTRL)                                                          \
     "v_mov_b32_dpp " D0 ", " S0 " " CTRL " row_mask:0xf bank_mask:0xf bound_ctrl:1\n"           \
@@ -308,44 +308,33 @@ struct RegState {
 // of the genes still running; lds: LDS byte address of this lane's first stash cell; accw: running sum of |loss change| (the
 // windows of a limited pass: the caller resets and files it); dl: the last sweep's loss change (row sum); cand: lanes of running
 // genes whose |loss change| <= tol in the last sweep (0: the statement left because sw == stop).
-// WHO: which kernel the loop is inlined into (0 = the column update k_cd_cols_reg, 1 = the stand-alone batch k_cd_batch_reg): part
-// of the NAMED label of the table of blocks, whose address reg_code_base() takes from another asm statement of the same kernel;
-// the column-update kernel also carries the blocks of two steps.
+// The table of blocks carries a NAMED label (one per KMAX: k_cd_cols_reg is the one kernel that inlines the loop), whose address
+// reg_code_base() takes from another asm statement of the same kernel.
 #define REG_LOOP_OUTS2                                                                                                     \
     [h0] "+v"(S.y[0]), [h1] "+v"(S.y[1]), [b0] "+v"(S.beta[0]), [b1] "+v"(S.beta[1]), [aw] "+v"(accw), [dl] "=&{v[2:3]}"(dl), \
         [rb] "=&{v[4:5]}"(rb), [dn] "=&v"(dn), [t0] "=&v"(t0), [t1] "=&v"(t1), [t2] "=&v"(t2), [t3] "=&v"(t3), [t4] "=&v"(t4),      \
         [t5] "=&v"(t5), [sw] "+s"(sw), [off] "+s"(off), [cand] "=&s"(cand)
 #define REG_LOOP_INS_TAIL                                                                                                  \
-    [tb0] "s"(tb0), [lm] "s"(lm), [run] "s"(run), [las] "s"(la), [tol] "s"(tol), [stop] "s"(stop), [la] "v"(lds), [who] "i"(WHO)
+    [tb0] "s"(tb0), [lm] "s"(lm), [run] "s"(run), [las] "s"(la), [tol] "s"(tol), [stop] "s"(stop), [la] "v"(lds)
 #define REG_LOOP_CLOBBERS "vcc", REG_CLOBBERS
 #if defined(__HIP_DEVICE_COMPILE__)   // gfx950 assembly: hipcc's host pass must not parse it
 #define REG_DEFINE_SWEEP2(KMAX)                                                                                          \
-    template <int WHO>                                                                                                   \
     __device__ __forceinline__ void reg_sweeps(RegState<2> &S, const double (&G)[2][KMAX], const uint32_t *tb0, int &off, \
                                                int &sw, int stop, uint64_t run, double la, double tol, uint32_t lds,     \
                                                double &accw, double &dl, uint64_t &cand)                                 \
     {                                                                                                                    \
         double dn, rb, t0, t1, t2, t3, t4, t5;                                                                           \
         const uint64_t lm = 0x0001000100010001ull;                                                                       \
-        if constexpr (WHO == 0)                                                                                          \
-            asm volatile(REG_LOOP_ENTRY REG_LIST_LO(REG_BLOCK2_LO) REG_HB_##KMAX(REG_HI16) REG_ORG(KMAX) REG_TAIL2            \
-                             REG_PAIRS_OPEN REG_LIST_LO(REGP_ROW_LO) REG_HB_##KMAX(REGP_ROW_HI) REG_PAIRS_CLOSE               \
-                         : REG_LOOP_OUTS2                                                                                \
-                         : REG_LIST_LO(REG_GA) REG_HI_##KMAX(REG_GA) REG_LIST_LO(REG_GB) REG_HI_##KMAX(REG_GB)[i0] "v"(  \
-                               S.tau[0]),                                                                                \
-                           [i1] "v"(S.tau[1]), REG_LOOP_INS_TAIL                                                         \
-                         : REG_LOOP_CLOBBERS);                                                                           \
-        else                                                                                                             \
-            asm volatile(REG_LOOP_ENTRY REG_LIST_LO(REG_BLOCK2_LO) REG_HB_##KMAX(REG_HI16) REG_ORG(KMAX) REG_TAIL2            \
-                         : REG_LOOP_OUTS2                                                                                \
-                         : REG_LIST_LO(REG_GA) REG_HI_##KMAX(REG_GA) REG_LIST_LO(REG_GB) REG_HI_##KMAX(REG_GB)[i0] "v"(  \
-                               S.tau[0]),                                                                                \
-                           [i1] "v"(S.tau[1]), REG_LOOP_INS_TAIL                                                         \
-                         : REG_LOOP_CLOBBERS);                                                                           \
+        asm volatile(REG_LOOP_ENTRY REG_LIST_LO(REG_BLOCK2_LO) REG_HB_##KMAX(REG_HI16) REG_ORG(KMAX) REG_TAIL2                \
+                         REG_PAIRS_OPEN REG_LIST_LO(REGP_ROW_LO) REG_HB_##KMAX(REGP_ROW_HI) REG_PAIRS_CLOSE                   \
+                     : REG_LOOP_OUTS2                                                                                    \
+                     : REG_LIST_LO(REG_GA) REG_HI_##KMAX(REG_GA) REG_LIST_LO(REG_GB) REG_HI_##KMAX(REG_GB)[i0] "v"(      \
+                           S.tau[0]),                                                                                    \
+                       [i1] "v"(S.tau[1]), REG_LOOP_INS_TAIL                                                             \
+                     : REG_LOOP_CLOBBERS);                                                                               \
     }
 #else
 #define REG_DEFINE_SWEEP2(KMAX)                                                                                          \
-    template <int WHO>                                                                                                   \
     __device__ __forceinline__ void reg_sweeps(RegState<2> &, const double (&)[2][KMAX], const uint32_t *, int &, int &, int, \
                                                uint64_t, double, double, uint32_t, double &, double &, uint64_t &) {}
 #endif
@@ -419,7 +408,6 @@ REG_DEFINE_SWEEP2(30)
     "s_setpc_b64 vcc\n.p2align 12\n"              \
     "Lc%=:\n"
 #if defined(__HIP_DEVICE_COMPILE__)
-template <int WHO>
 __device__ __forceinline__ void reg_sweep(RegState<2> &S, const double (&G)[2][32], const uint32_t *tb)
 {
     double dn;
@@ -433,7 +421,6 @@ __device__ __forceinline__ void reg_sweep(RegState<2> &S, const double (&G)[2][3
                  : "vcc", "scc", "memory", REG_S64_97, "s98", "s99");
 }
 #else
-template <int WHO>
 __device__ __forceinline__ void reg_sweep(RegState<2> &, const double (&)[2][32], const uint32_t *) {}
 #endif
 
@@ -444,29 +431,22 @@ __device__ __forceinline__ void reg_sweep(RegState<2> &, const double (&)[2][32]
 #define REG_LOOP_OUTS1                                                                                                      \
     [h0] "+v"(S.y[0]), [b0] "+v"(S.beta[0]), [aw] "+v"(accw), [dl] "=&{v[2:3]}"(dl), [rb] "=&{v[4:5]}"(rb), [dn] "=&v"(dn),  \
         [t0] "=&v"(t0), [t2] "=&v"(t2), [t4] "=&v"(t4), [sw] "+s"(sw), [off] "+s"(off), [cand] "=&s"(cand)
-template <int WHO>
 __device__ __forceinline__ void reg_sweeps(RegState<1> &S, const double (&G)[1][16], const uint32_t *tb0, int &off, int &sw, int stop,
                                            uint64_t run, double la, double tol, uint32_t lds, double &accw, double &dl, uint64_t &cand)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
     double dn, rb, t0, t2, t4;
     const uint64_t lm = 0x0001000100010001ull;
-    if constexpr (WHO == 0)
-        asm volatile(REG_LOOP_ENTRY REG_LIST_LO(REG_BLOCK1) REG_ORG(16) REG_TAIL1 REG_PAIRS_OPEN REG_LIST_LO(REGP1_ROW_LO) REG_PAIRS_CLOSE
-                     : REG_LOOP_OUTS1
-                     : REG_LIST_LO(REG_GA)[i0] "v"(S.tau[0]), REG_LOOP_INS_TAIL
-                     : REG_LOOP_CLOBBERS);
-    else
-        asm volatile(REG_LOOP_ENTRY REG_LIST_LO(REG_BLOCK1) REG_ORG(16) REG_TAIL1
-                     : REG_LOOP_OUTS1
-                     : REG_LIST_LO(REG_GA)[i0] "v"(S.tau[0]), REG_LOOP_INS_TAIL
-                     : REG_LOOP_CLOBBERS);
+    asm volatile(REG_LOOP_ENTRY REG_LIST_LO(REG_BLOCK1) REG_ORG(16) REG_TAIL1 REG_PAIRS_OPEN REG_LIST_LO(REGP1_ROW_LO) REG_PAIRS_CLOSE
+                 : REG_LOOP_OUTS1
+                 : REG_LIST_LO(REG_GA)[i0] "v"(S.tau[0]), REG_LOOP_INS_TAIL
+                 : REG_LOOP_CLOBBERS);
 #endif
 }
 #undef REG_KM
 #undef REG_PBN
 
-// Address of the pair blocks of the KMAX instantiation of the column-update kernel (their own section: a pc-relative relocation)
+// Address of the pair blocks of the KMAX instantiation (their own section: a pc-relative relocation)
 template <int KMAX>
 __device__ __forceinline__ uint64_t reg_pair_base()
 {
@@ -486,19 +466,19 @@ __device__ __forceinline__ uint64_t reg_pair_base()
 
 // Address of the table of code blocks of THIS kernel's sweep (the named label of REG_PROLOGUE): k_order_table adds the block
 // offsets to it, so the kernel that will run the sweeps is launched once with a null gene set to publish it (ColArgs::code_base)
-template <int KMAX, int WHO>
+template <int KMAX>
 __device__ __forceinline__ uint64_t reg_code_base()
 {
     uint32_t lo = 0, hi = 0;
 #if defined(__HIP_DEVICE_COMPILE__)
     asm volatile("s_getpc_b64 s[98:99]\n"
                  "Lq%=:\n"
-                 "s_add_u32 s98, s98, insider_cdtab_%c[km]_%c[who]-Lq%=\n"
+                 "s_add_u32 s98, s98, insider_cdtab_%c[km]-Lq%=\n"
                  "s_addc_u32 s99, s99, 0\n"
                  "s_mov_b32 %[lo], s98\n"
                  "s_mov_b32 %[hi], s99\n"
                  : [lo] "=s"(lo), [hi] "=s"(hi)
-                 : [km] "i"(KMAX), [who] "i"(WHO)
+                 : [km] "i"(KMAX)
                  : "s98", "s99", "scc");
 #endif
     return ((uint64_t)hi << 32) | lo;
@@ -564,7 +544,6 @@ constexpr int reg3_ps(int KMAX) { return 4 * reg3_w(KMAX) + 1; }            // p
 // la: LDS byte address of this lane's cell in row 0 of the panel
 #if defined(__HIP_DEVICE_COMPILE__)
 #define REG_DEFINE_SWEEP3(KMAX)                                                                                          \
-    template <int WHO>                                                                                                   \
     __device__ __forceinline__ void reg_sweep(RegState<3> &S, const double (&G)[2][KMAX], const uint32_t *tb, uint32_t la) \
     {                                                                                                                    \
         double dn, gc;                                                                                                   \
@@ -582,7 +561,6 @@ constexpr int reg3_ps(int KMAX) { return 4 * reg3_w(KMAX) + 1; }            // p
     }
 #else
 #define REG_DEFINE_SWEEP3(KMAX) \
-    template <int WHO>          \
     __device__ __forceinline__ void reg_sweep(RegState<3> &, const double (&)[2][KMAX], const uint32_t *, uint32_t) {}
 #endif
 #define REG3_PS_STR "136"
@@ -740,7 +718,7 @@ __device__ __forceinline__ RegState<SLOTS> cd_reg_begin(int K, const double (&q)
 }
 
 // S: the start values of cd_reg_begin; beta / hs / is are outputs here
-template <int SLOTS, int KMAX, int WHO>
+template <int SLOTS, int KMAX>
 __device__ __forceinline__ int cd_reg(RegState<SLOTS> S, const double (&G)[reg_rs(SLOTS)][KMAX], int K, double (&beta)[SLOTS],
                                       bool gene_ok, const CdParams &P, int lane, double *stash, bool resume,
                                       double (&hs)[SLOTS], double (&is)[SLOTS], bool &unfinished, int &key, bool &capped,
@@ -839,7 +817,7 @@ __device__ __forceinline__ int cd_reg(RegState<SLOTS> S, const double (&G)[reg_r
             int bound = stop;
             if (sweep < win) bound = win < stop ? win : stop;
             else if (sweep < win + W) bound = win + W;
-            reg_sweeps<WHO>(S, G, tb0, off, sweep, bound, runm, la, tol, lds, accw, dloss, cand);
+            reg_sweeps(S, G, tb0, off, sweep, bound, runm, la, tol, lds, accw, dloss, cand);
             if (sweep == win) accw = 0.0;                          // window 0: sweeps win + 1 ... win + W
             else if (sweep == win + W) { s_acc[0] = accw; accw = 0.0; }   // window 1: the rest of the pass
             if (cand != 0) candidates(cand);
@@ -849,8 +827,8 @@ __device__ __forceinline__ int cd_reg(RegState<SLOTS> S, const double (&G)[reg_r
         const uint32_t *tb = tb0 + (size_t)(sweep & (int)(INSIDER_PERM_PERIOD - 1)) * (ORDER_ROW / 4);
         while (runm != 0 && sweep < stop) {   // the sweep cap / pass limit is the loop bound: genes still running then are handled below
             // ---- the sweep (:91-110) -----------------------------------------------------------------------------------
-            if constexpr (SLOTS == 3) reg_sweep<WHO>(S, G, tb, pla);
-            else if constexpr (!reg_pairs(KMAX)) reg_sweep<WHO>(S, G, tb);
+            if constexpr (SLOTS == 3) reg_sweep(S, G, tb, pla);
+            else if constexpr (!reg_pairs(KMAX)) reg_sweep(S, G, tb);
             ++sweep;
             tb = (sweep & (int)(INSIDER_PERM_PERIOD - 1)) ? tb + ORDER_ROW / 4 : tb0;
             // ---- loss change of the sweep (:112-114), per gene ------------------------------------------------------------
@@ -961,7 +939,7 @@ __global__ void __launch_bounds__(64, reg_waves(KMAX)) k_cd_cols_reg(ColArgs a)
     if constexpr (SOLVE && reg_pairs(KMAX)) {
         if (a.code_base) {   // probe launch (wave-uniform): where this kernel's table of code blocks lies, for k_order_table
             if (blockIdx.x == 0 && lane == 0) {
-                a.code_base[0] = reg_code_base<KMAX, 0>();
+                a.code_base[0] = reg_code_base<KMAX>();
                 a.code_base[1] = reg_pair_base<KMAX>();
             }
             return;
@@ -1027,7 +1005,7 @@ __global__ void __launch_bounds__(64, reg_waves(KMAX)) k_cd_cols_reg(ColArgs a)
         }
         if constexpr (SLOTS == 3) wave_sync();
         if constexpr (SOLVE)                                                              // :228,246
-            sweeps = cd_reg<SLOTS, KMAX, 0>(S, G, K, beta, w.gene, a.cd, lane, stash, resume, hs, is, unfinished, key, capped, panel);
+            sweeps = cd_reg<SLOTS, KMAX>(S, G, K, beta, w.gene, a.cd, lane, stash, resume, hs, is, unfinished, key, capped, panel);
     }
     // ---- results: everything that addresses the gene is formed again, from a laundered lane id ------------------------
     int lane_c = lane;
@@ -1108,87 +1086,6 @@ __global__ void __launch_bounds__(64, reg_waves(KMAX)) k_cd_cols_reg(ColArgs a)
         a.b1[w.j] = sb1;
         if (a.test_from_stats) a.sse_test[w.j] = w.st ? w.st[stat_index(KP - 1, KP - 1)] + te : 0.0;
     }
-}
-
-// stand-alone batch form (insider_hip_strong_cd) on dense (XtX, Xty)
-// (two waves per SIMD from KMAX = 30 on: the dense problems' per-element addresses need registers the column-update kernel
-// does not, and the stand-alone solver is not on the fit's path; no instantiation spills)
-template <int SLOTS, int KMAX>
-__global__ void __launch_bounds__(64, KMAX >= 30 ? 2 : reg_waves(KMAX))
-k_cd_batch_reg(const double *__restrict__ XtX, const double *__restrict__ Xty, const double *__restrict__ wstart, int K,
-               int64_t nprob, CdParams cd, double *__restrict__ beta_out, int *__restrict__ sweeps_out,
-               unsigned long long *__restrict__ code_base = nullptr)
-{
-    const int lane = threadIdx.x;
-    if constexpr (reg_pairs(KMAX)) {
-        if (code_base) {   // probe launch: see k_cd_cols_reg
-            if (blockIdx.x == 0 && lane == 0) *code_base = reg_code_base<KMAX, 1>();
-            return;
-        }
-    }
-    __shared__ double stash[reg_stash(SLOTS)];
-    double *const panel = RegPanel<SLOTS, KMAX>::get();
-    double G[reg_rs(SLOTS)][KMAX], beta[SLOTS];
-    int sw;
-    {
-        const int row = lane >> 4, i = lane & 15;
-        const int64_t b = (int64_t)blockIdx.x * 4 + row;
-        const bool prob = b < nprob;
-        const double *Gb = XtX + (size_t)(prob ? b : 0) * K * K;     // absent problems read problem 0: every load unconditional
-        const double *qb = Xty + (size_t)(prob ? b : 0) * K, *wb = wstart + (size_t)(prob ? b : 0) * K;
-        double hs[SLOTS], is[SLOTS];
-        RegState<SLOTS> S;
-        {
-            double q[SLOTS], Gll[SLOTS];
-#pragma unroll
-            for (int u = 0; u < SLOTS; ++u) {
-                const int c = 16 * u + i;
-                const bool ok = prob && c < K;
-                const int cc = c < K ? c : 0;
-                const double dv = Gb[(size_t)cc * K + cc], qv = qb[cc], wv = wb[cc];
-                Gll[u] = ok ? dv : 1.0;
-                q[u] = ok ? qv : 0.0;
-                beta[u] = ok ? wv : 0.0;
-                hs[u] = is[u] = 0.0;
-            }
-            S = cd_reg_begin<SLOTS>(K, q, Gll, beta, prob, cd, lane, stash, false, hs, is);
-        }
-#if defined(__HIP_DEVICE_COMPILE__)
-        asm volatile("" ::: "memory");   // the matrix loads stay below the start values
-#endif
-#pragma unroll
-        for (int u = 0; u < SLOTS; ++u) {
-            const int c = 16 * u + i;
-            const bool ok = prob && c < K;
-            const int cc = c < K ? c : 0;
-#pragma unroll
-            for (int k = 0; k < KMAX; ++k) {
-                const double v = Gb[(size_t)(k < K ? k : 0) * K + cc];
-                const double gv = (ok && k < K && k != c) ? v * cd.inv_two_la : 0.0;   // the sweeps work on XtX / (2 la): RegState
-                if constexpr (SLOTS == 3) {
-                    if (u < 2) G[u < 2 ? u : 0][k] = gv;
-                    else if (k < K) panel[k * reg3_ps(KMAX) + reg3_cell<KMAX>(lane)] = gv;
-                } else {
-                    G[u][k] = gv;
-                }
-            }
-        }
-        if constexpr (SLOTS == 3) wave_sync();
-        bool unfinished, capped;
-        int key;
-        sw = cd_reg<SLOTS, KMAX, 1>(S, G, K, beta, prob, cd, lane, stash, false, hs, is, unfinished, key, capped, panel);
-    }
-    int lane_c = lane;
-#if defined(__HIP_DEVICE_COMPILE__)
-    asm volatile("" : "+v"(lane_c));
-#endif
-    const int row = lane_c >> 4, i = lane_c & 15;
-    const int64_t b = (int64_t)blockIdx.x * 4 + row;
-    const bool prob = b < nprob;
-#pragma unroll
-    for (int u = 0; u < SLOTS; ++u)
-        if (prob && 16 * u + i < K) beta_out[(size_t)b * K + 16 * u + i] = beta[u];
-    if (prob && i == 0 && sweeps_out) sweeps_out[b] = sw;
 }
 
 // host-side dispatch over the instantiated (SLOTS, KMAX) pairs: F is a generic lambda taking two integral constants

@@ -379,38 +379,4 @@ __global__ void __launch_bounds__(64) k_cd_cols_r16(ColArgs a)
     }
 }
 
-// stand-alone batch form (insider_hip_strong_cd) on dense (XtX, Xty)
-template <int SLOTS>
-__global__ void __launch_bounds__(64)
-k_cd_batch_r16(const double *__restrict__ XtX, const double *__restrict__ Xty, const double *__restrict__ wstart, int K,
-               int64_t nprob, CdParams cd, double *__restrict__ beta_out, int *__restrict__ sweeps_out)
-{
-    extern __shared__ double r16_lds[];
-    const int lane = threadIdx.x;
-    const int row = lane >> 4, i = lane & 15;
-    const int64_t b = (int64_t)blockIdx.x * 4 + row;
-    const bool prob = b < nprob;
-    double *Gg = r16_lds + row * r16_gstride(K);
-    double q[SLOTS], Gll[SLOTS], beta[SLOTS];
-#pragma unroll
-    for (int u = 0; u < SLOTS; ++u) {
-        const int c = 16 * u + i;
-        const bool ok = prob && c < K;
-        Gll[u] = 1.0;
-        for (int k = 0; k < K; ++k) {
-            double v = ok ? XtX[(size_t)b * K * K + (size_t)k * K + c] : 0.0;
-            if (k == c) { Gll[u] = ok ? v : 1.0; v = 0.0; }
-            if (c < K) Gg[k * K + c] = v;
-        }
-        q[u] = ok ? Xty[(size_t)b * K + c] : 0.0;
-        beta[u] = ok ? wstart[(size_t)b * K + c] : 0.0;
-    }
-    wave_sync();
-    const int sw = cd_row16<SLOTS>(r16_lds, K, q, Gll, beta, prob, cd, lane);
-#pragma unroll
-    for (int u = 0; u < SLOTS; ++u)
-        if (prob && 16 * u + i < K) beta_out[(size_t)b * K + 16 * u + i] = beta[u];
-    if (prob && i == 0 && sweeps_out) sweeps_out[b] = sw < 0 ? -sw : sw;
-}
-
 }  // namespace insider

@@ -32,6 +32,7 @@ namespace {
 
 thread_local std::string g_err;
 thread_local double g_last_cd_ms = 0.0;   // per calling thread: the ABI is re-entrant per handle / per thread
+thread_local int g_last_cd_solver = 0;     // (ColSolver)
 
 int fail(int code, const std::string &msg)
 {
@@ -661,7 +662,6 @@ int r16_wide_lds(size_t bytes)
     if (dev >= 64 || !(done.load() & bit)) {
         const int lim = 160 * 1024;
         HIPCHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_cd_cols_r16<3>), hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-        HIPCHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_cd_batch_r16<3>), hipFuncAttributeMaxDynamicSharedMemorySize, lim));
         done.fetch_or(bit);
     }
     return INSIDER_OK;
@@ -734,35 +734,102 @@ struct Timer {   // HIP-event pair around one launch on the library's stream (op
     }
 };
 
-// Builds the sweep-order table of outer iteration `iter` into order_buf[slot] (on `stream`); the caller makes it current
-// (h->ws.order) when its solve is launched.  Two buffers: an outer iteration's table depends on (seed, iter) only, so the NEXT one
-// is built while the current solve runs — the sweep kernel leaves no room for other waves, so the builder runs in its tail,
-// on SIMDs that have already drained — instead of competing with the row phase.
 // 32 < K <= 48 with an l1 term: the register-resident kernel with its third slot's matrix columns in LDS (insider_cd_reg.hpp)
 static bool reg3_path(int K, double la) { return K > 32 && K <= 48 && la > 0.0; }
 
-// the address of the table of code blocks of k_cd_cols_reg<., KMAX(K), true> on this device (K <= 32): one probe launch per workspace
+// the kernels launch_col_solve() can launch, as insider_hip_get_info("col_solver" / "col_eval") reports them, and the one the
+// batch entry launched (insider_hip_last_cd_solver; include/insider_hip.h; insider_amd/_lib.py COL_SOLVERS mirrors the names)
+enum ColSolver {
+    CS_NONE = 0, CS_RIDGE_REG = 1, CS_RIDGE = 2, CS_CD_REG = 3, CS_CD_REG3 = 4, CS_CD_COLS16 = 5, CS_CD_COLS32 = 6,
+    CS_CD_COLS64 = 7, CS_CD_R16_1 = 8, CS_CD_R16_2 = 9, CS_CD_R16_3 = 10
+};
+
+// The elastic-net solve kernel for K, lambda alpha and the option cd_variant: the column update's and the batch entry's.
+static ColSolver cd_solver(int K, double la, int cd_variant)
+{
+    // the register-resident kernel scales its state by 1 / (2 lambda alpha): lambda alpha = 0 (alpha < 0 or lambda = 0: no l1
+    // term at all) takes the group kernel below
+    if (cd_variant == 0 && (K <= 32 || reg3_path(K, la)) && la > 0.0) return K <= 32 ? CS_CD_REG : CS_CD_REG3;
+    if (cd_variant == 2 && K <= 16) return CS_CD_R16_1;
+    if (cd_variant == 2 && K <= 32) return CS_CD_R16_2;
+    if (K <= 16) return CS_CD_COLS16;
+    if (K <= 32) return CS_CD_COLS32;
+    // 32 < K <= 48 when the register-resident kernel's three-slot form does not apply (cd_variant = 2, or no l1 term): four genes
+    // per wavefront with the whole Gram matrices in LDS (row16 kernel, three coordinate slots per lane).  Beyond 48 a CU's LDS
+    // holds one such wave and the group kernel is faster; it also stays as cd_variant = 1 (cross-check)
+    if (cd_variant != 1 && K <= 48) return CS_CD_R16_3;
+    return CS_CD_COLS64;
+}
+
+// one launch of the elastic-net kernel s over the a.p genes of `a` (a.mode: the solve or, outside the register-resident
+// kernel, the evaluation only)
+static int launch_cd(ColSolver s, const ColArgs &a, hipStream_t st)
+{
+    const size_t r16_bytes = (size_t)r16_lds_doubles(a.K) * sizeof(double);
+    switch (s) {
+        case CS_CD_REG:
+        case CS_CD_REG3:
+            REG_ANY_DISPATCH(a.K, hipLaunchKernelGGL((k_cd_cols_reg<SL_, KM_, true>), dim3(cdiv(a.p, 4)), dim3(64), 0, st, a));
+            break;
+        case CS_CD_R16_1: hipLaunchKernelGGL((k_cd_cols_r16<1>), dim3(cdiv(a.p, 4)), dim3(64), r16_bytes, st, a); break;
+        case CS_CD_R16_2: hipLaunchKernelGGL((k_cd_cols_r16<2>), dim3(cdiv(a.p, 4)), dim3(64), r16_bytes, st, a); break;
+        case CS_CD_R16_3:
+            if (int rl = r16_wide_lds(r16_bytes)) return rl;
+            hipLaunchKernelGGL((k_cd_cols_r16<3>), dim3(cdiv(a.p, 4)), dim3(64), r16_bytes, st, a);
+            break;
+        case CS_CD_COLS16: hipLaunchKernelGGL((k_cd_cols<16, 4>), dim3(cdiv(a.p, 16)), dim3(256), 0, st, a); break;
+        case CS_CD_COLS32: hipLaunchKernelGGL((k_cd_cols<32, 2>), dim3(cdiv(a.p, 4)), dim3(128), 0, st, a); break;
+        case CS_CD_COLS64: hipLaunchKernelGGL((k_cd_cols<64, 1>), dim3((unsigned)a.p), dim3(64), 0, st, a); break;
+        default: return fail(INSIDER_ERR_ARG, "not an elastic-net solve kernel");
+    }
+    KCHECK();
+    return INSIDER_OK;
+}
+
+// The addresses of the table of code blocks [0] and of the blocks of two steps [1] of k_cd_cols_reg<., KMAX(K), true> on the
+// current device (reg_pairs(KMAX) only): a probe launch with a null gene set, through the two device words d.
+static int probe_code_base(int K, unsigned long long *d, hipStream_t st, unsigned long long (&v)[2])
+{
+    HIPCHECK(hipMemsetAsync(d, 0, 2 * sizeof(unsigned long long), st));
+    ColArgs a{};
+    a.K = K;
+    a.code_base = d;
+    REG_DISPATCH(K, hipLaunchKernelGGL((k_cd_cols_reg<SL_, KM_, true>), dim3(1), dim3(64), 0, st, a));
+    KCHECK();
+    v[0] = v[1] = 0;
+    HIPCHECK(hipMemcpyAsync(v, d, sizeof(v), hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipStreamSynchronize(st));
+    if (!v[0] || !v[1]) return fail(INSIDER_ERR_HIP, "the sweep kernel did not publish the addresses of its code blocks");
+    return INSIDER_OK;
+}
+
+// The sweep-order table (one period of rows at most, + the look-ahead row) for solves with the kernel s: rows for K > 32 carry
+// 64 row offsets (row16 kernel) unless s takes the register-resident kernel's successor list.  code_base / pair_base:
+// probe_code_base's addresses (pair_base 0: one step per block).
+static int launch_order_table(uint64_t seed, uint32_t iter, int K, int rows, int order_mode, ColSolver s,
+                              unsigned long long code_base, unsigned long long pair_base, uint8_t *out, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_order_table, dim3(cdiv((int64_t)(rows + 1) * 64, 256)), dim3(256), 0, st, seed, iter, K, rows, order_mode,
+                       K * 8, reg_kmax(K), (K > 32 && s != CS_CD_REG3) ? 1 : 0, code_base, pair_base, out);
+    KCHECK();
+    return INSIDER_OK;
+}
+
+// the code addresses of the register-resident kernel for K (K <= 30) on this device: one probe launch per workspace
 int ensure_code_base(insider_hip_handle *h, int K)
 {
     if (!reg_pairs(reg_kmax(K)) || h->ws.cd_code_base) return INSIDER_OK;
-    unsigned long long *d = h->ws.code_base_dev;
-    HIPCHECK(hipMemsetAsync(d, 0, 2 * sizeof(unsigned long long), h->st.stream));
-    ColArgs a{};
-    a.p = 0;
-    a.K = K;
-    a.KP = h->ws.KP;
-    a.code_base = d;
-    REG_DISPATCH(K, hipLaunchKernelGGL((k_cd_cols_reg<SL_, KM_, true>), dim3(1), dim3(64), 0, h->st.stream, a));
-    KCHECK();
-    unsigned long long v[2] = {0, 0};
-    HIPCHECK(hipMemcpyAsync(v, d, sizeof(v), hipMemcpyDeviceToHost, h->st.stream));
-    HIPCHECK(hipStreamSynchronize(h->st.stream));
-    if (!v[0] || !v[1]) return fail(INSIDER_ERR_HIP, "the sweep kernel did not publish the addresses of its code blocks");
+    unsigned long long v[2];
+    if (int rc = probe_code_base(K, h->ws.code_base_dev, h->st.stream, v)) return rc;
     h->ws.cd_code_base = v[0];
     h->ws.cd_pair_base = v[1];
     return INSIDER_OK;
 }
 
+// Builds the sweep-order table of outer iteration `iter` into order_buf[slot] (on `stream`); the caller makes it current
+// (h->ws.order) when its solve is launched.  Two buffers: an outer iteration's table depends on (seed, iter) only, so the NEXT one
+// is built while the current solve runs — the sweep kernel leaves no room for other waves, so the builder runs in its tail,
+// on SIMDs that have already drained — instead of competing with the row phase.
 int ensure_order_table(insider_hip_handle *h, uint64_t seed, uint32_t iter, int K, int max_sweeps, int order_mode, double la,
                        hipStream_t stream = nullptr, int slot = 0)
 {
@@ -775,11 +842,9 @@ int ensure_order_table(insider_hip_handle *h, uint64_t seed, uint32_t iter, int 
             if (int rc = b.alloc((size_t)(rows + 4) * ORDER_ROW)) return rc;   // + the look-ahead row (and the prologue's touch of the one after)
         h->ws.order_rows = rows;
     }
-    // rows for K > 32 carry 64 row offsets (row16 kernel) unless the solve takes the register-resident kernel's successor list
-    hipLaunchKernelGGL(k_order_table, dim3(cdiv((int64_t)(rows + 1) * 64, 256)), dim3(256), 0, stream, seed, iter, K, rows,
-                       order_mode, K * 8, reg_kmax(K), (K > 32 && !(h->opt.cd_variant == 0 && reg3_path(K, la))) ? 1 : 0, h->ws.cd_code_base,
-                       h->opt.cd_pairs ? h->ws.cd_pair_base : 0ull, h->ws.order_buf[slot]);
-    KCHECK();
+    if (int rc = launch_order_table(seed, iter, K, rows, order_mode, cd_solver(K, la, h->opt.cd_variant), h->ws.cd_code_base,
+                                    h->opt.cd_pairs ? h->ws.cd_pair_base : 0ull, h->ws.order_buf[slot], stream))
+        return rc;
     if (!h->ws.order) h->ws.order = h->ws.order_buf[slot];
     return INSIDER_OK;
 }
@@ -942,13 +1007,6 @@ int launch_col_stats(insider_hip_handle *h, bool timed)
     return t.end(h, h->ev_col);
 }
 
-// the kernels launch_col_solve() can launch, as insider_hip_get_info("col_solver" / "col_eval") reports them
-// (include/insider_hip.h; insider_amd/_lib.py mirrors the names)
-enum ColSolver {
-    CS_NONE = 0, CS_RIDGE_REG = 1, CS_RIDGE = 2, CS_CD_REG = 3, CS_CD_REG3 = 4, CS_CD_COLS16 = 5, CS_CD_COLS32 = 6,
-    CS_CD_COLS64 = 7, CS_CD_R16_1 = 8, CS_CD_R16_2 = 9, CS_CD_R16_3 = 10
-};
-
 // column update from the statistics: elastic-net CD (alpha > 0) or ridge (alpha == 0), or evaluation only
 int launch_col_solve(insider_hip_handle *h, int masked, bool solve, double lambda, double alpha, double tol,
                      int checkpoint, bool timed, int outer_iter = -1, bool side = false)
@@ -1054,10 +1112,8 @@ int launch_col_solve(insider_hip_handle *h, int masked, bool solve, double lambd
         a.sched_key = a.sched_cnt = a.sched_rank = nullptr;
         a.sched_bkt = nullptr;
         a.sched_reset = 0;
-        const size_t r16_bytes = (size_t)r16_lds_doubles(h->ws.K) * sizeof(double);
-        // the register-resident kernel scales its state by 1 / (2 lambda alpha): lambda alpha = 0 (alpha < 0 or lambda = 0: no l1
-        // term at all) takes the group kernel below
-        if (h->opt.cd_variant == 0 && (h->ws.K <= 32 || reg3_path(h->ws.K, a.cd.la)) && a.cd.la > 0.0) {
+        const ColSolver cs = cd_solver(h->ws.K, a.cd.la, h->opt.cd_variant);
+        if (cs == CS_CD_REG || cs == CS_CD_REG3) {
             // Cold outer iterations: thousands of sweeps per gene whose counts no history predicts, so a wave's four genes
             // finish far apart (measured at c3: 1.17x / 1.44x / 2.1x the ideal wave time in outer iterations 0 / 1 / 2).
             // The solve then runs in passes over geometrically growing sweep ranges: a limited pass stops at its sweep
@@ -1087,10 +1143,9 @@ int launch_col_solve(insider_hip_handle *h, int masked, bool solve, double lambd
                 a.bucket_cnt = limit ? h->ws.cd_pass_cnt : nullptr;
                 if (limit) HIPCHECK(hipMemsetAsync(h->ws.cd_pass_cnt, 0, CD_BUCKETS * sizeof(int), h->st.stream));
                 if (solve) {
-                    REG_ANY_DISPATCH(h->ws.K, hipLaunchKernelGGL((k_cd_cols_reg<SL_, KM_, true>), dim3(cdiv(h->ds->p, 4)), dim3(64), 0, h->st.stream, a);
-                                           h->col_solver = SL_ == 3 ? CS_CD_REG3 : CS_CD_REG);
+                    if ((rc = launch_cd(cs, a, h->st.stream))) return rc;
+                    h->col_solver = cs;
                 }
-                KCHECK();
                 if (!limit) break;
                 int *count_out = h->ws.cd_pass_cnt + CD_BUCKETS + (pass & 1);
                 hipLaunchKernelGGL(k_pass_scatter, dim3(cdiv(h->ds->p, 256)), dim3(256), 0, h->st.stream,
@@ -1104,30 +1159,10 @@ int launch_col_solve(insider_hip_handle *h, int masked, bool solve, double lambd
             }
             eval_after = checkpoint != 0;
             eval_args = a;
-        } else if (h->opt.cd_variant == 2 && h->ws.K <= 16) {
-            hipLaunchKernelGGL((k_cd_cols_r16<1>), dim3(cdiv(h->ds->p, 4)), dim3(64), r16_bytes, h->st.stream, a);
-            h->col_solver = CS_CD_R16_1;
-        } else if (h->opt.cd_variant == 2 && h->ws.K <= 32) {
-            hipLaunchKernelGGL((k_cd_cols_r16<2>), dim3(cdiv(h->ds->p, 4)), dim3(64), r16_bytes, h->st.stream, a);
-            h->col_solver = CS_CD_R16_2;
-        } else if (h->ws.K <= 16) {
-            hipLaunchKernelGGL((k_cd_cols<16, 4>), dim3(cdiv(h->ds->p, 16)), dim3(256), 0, h->st.stream, a);
-            h->col_solver = CS_CD_COLS16;
-        } else if (h->ws.K <= 32) {
-            hipLaunchKernelGGL((k_cd_cols<32, 2>), dim3(cdiv(h->ds->p, 4)), dim3(128), 0, h->st.stream, a);
-            h->col_solver = CS_CD_COLS32;
-        } else if (h->opt.cd_variant != 1 && h->ws.K <= 48) {
-            // 32 < K <= 48 when the register-resident kernel's three-slot form does not apply (cd_variant = 2, or no l1 term): four genes
-            // per wavefront with the whole Gram matrices in LDS (row16 kernel, three coordinate slots per lane).  Beyond 48 a CU's LDS
-            // holds one such wave and the kernel below is faster; it also stays as cd_variant = 1 (cross-check)
-            if (int rl = r16_wide_lds(r16_bytes)) return rl;
-            hipLaunchKernelGGL((k_cd_cols_r16<3>), dim3(cdiv(h->ds->p, 4)), dim3(64), r16_bytes, h->st.stream, a);
-            h->col_solver = CS_CD_R16_3;
         } else {
-            hipLaunchKernelGGL((k_cd_cols<64, 1>), dim3((unsigned)h->ds->p), dim3(64), 0, h->st.stream, a);
-            h->col_solver = CS_CD_COLS64;
+            if ((rc = launch_cd(cs, a, h->st.stream))) return rc;
+            h->col_solver = cs;
         }
-        KCHECK();
     }
     if ((rc = t.end(h, h->ev_cd))) return rc;
     if (eval_after) {   // the per-gene loss statistics of the (updated) columns: the evaluation kernel, all genes (not part of the solve's time)
@@ -2583,72 +2618,79 @@ int insider_hip_optimize_col(insider_hip_handle *h, double *const *A, double *C,
     return check_fail_flag(h);
 }
 
-// device part shared by the two strong_coordinate_descent entries: dG / dq / dw hold nprob problems on `device`
+// Device part shared by the two strong_coordinate_descent entries: dG / dq / dw hold nprob problems on the current device.
+// They run on the column update's kernels (cd_solver, launch_cd; default options): k_pack_cols writes a chunk of problems in
+// the layout of the column statistics, one record per problem, and one solve launch per chunk — a single pass, no launch order,
+// no evaluation — leaves the solutions in rows of pitch KP.  A record is much larger than K x K at small K (256 doubles at
+// K = 1), so a chunk holds CD_BATCH_DOUBLES of records at most; the problems are independent and the order table does not
+// depend on the problem index, so the chunking changes no result.
+constexpr int64_t CD_BATCH_DOUBLES = int64_t(1) << 26;
 static int strong_cd_device(const double *dG, const double *dq, const double *dw, int K, int64_t nprob,
                             double lambda, double alpha, double tol, uint64_t seed, uint32_t iter, int order_mode,
                             int max_sweeps, double *beta_out, int32_t *sweeps_out)
 {
-    DevBuf<double> db;
-    DevBuf<int> ds;
-    int rc;
-    if ((rc = db.alloc((size_t)nprob * K)) || (rc = ds.alloc((size_t)nprob))) return rc;
+    const int KP = 16 * ((K + 16) / 16), NB = KP / 16, stat_len = NB * (NB + 1) / 2 * 256;
+    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(nprob, CD_BATCH_DOUBLES / stat_len));
+    const ColSolver cs = cd_solver(K, lambda * alpha, 0);
     const int ms = max_sweeps < 1 ? 1 : max_sweeps;
     const int rows = std::min<int64_t>(ms, INSIDER_PERM_PERIOD);   // one period of the order sequence (include/insider_perm.h)
-    DevBuf<uint8_t> dord;
-    if ((rc = dord.alloc((size_t)(rows + 4) * ORDER_ROW))) return rc;   // + the look-ahead row
-    const bool reg = K <= 32 && lambda * alpha > 0.0;   // the register-resident batch kernel
-    const bool reg3 = reg3_path(K, lambda * alpha);
-    unsigned long long code_base = 0;
-    if (reg && reg_pairs(reg_kmax(K))) {   // where are its code blocks?
-        DevBuf<unsigned long long> dcb;
-        if ((rc = dcb.alloc(1))) return rc;
-        HIPCHECK(hipMemset(dcb, 0, sizeof(unsigned long long)));
-        CdParams none{};
-        REG_DISPATCH(K, hipLaunchKernelGGL((k_cd_batch_reg<SL_, KM_>), dim3(1), dim3(64), 0, 0, dG, dq, dw, K, (int64_t)0, none, db, ds, dcb));
-        KCHECK();
-        HIPCHECK(hipMemcpy(&code_base, dcb, sizeof(code_base), hipMemcpyDeviceToHost));
-        if (!code_base) return fail(INSIDER_ERR_HIP, "the sweep kernel did not publish the address of its code blocks");
-    }
-    hipLaunchKernelGGL(k_order_table, dim3(cdiv((int64_t)(rows + 1) * 64, 256)), dim3(256), 0, 0, seed, iter, K, rows, order_mode, K * 8,
-                       reg_kmax(K), (K > 32 && !reg3) ? 1 : 0, code_base, 0ull, dord);
-    KCHECK();
-    CdParams cd;
-    cd.lambda = lambda;
-    cd.alpha = alpha;
-    cd.tol = tol;
-    cd.la = lambda * alpha;
-    cd.l2 = lambda * (1.0 - alpha);
-    cd.two_la = 2.0 * cd.la;
-    cd.inv_two_la = cd.la > 0.0 ? 0.5 / cd.la : 0.0;
-    cd.max_sweeps = ms;
-    cd.order = dord;
+    DevBuf<double> stat, Qfull, C, RtR;
+    DevBuf<int> sw;
+    DevBuf<uint8_t> order;
+    DevBuf<unsigned long long> cb;
+    int rc;
+    if ((rc = stat.alloc((size_t)chunk * stat_len)) || (rc = Qfull.alloc((size_t)chunk * KP)) || (rc = C.alloc((size_t)chunk * KP)) ||
+        (rc = RtR.alloc((size_t)KP * KP)) || (rc = sw.alloc((size_t)chunk)) || (rc = cb.alloc(2)) ||
+        (rc = order.alloc((size_t)(rows + 4) * ORDER_ROW)))   // + the look-ahead row
+        return rc;
+    HIPCHECK(hipMemset(RtR, 0, (size_t)KP * KP * sizeof(double)));   // (every problem has its record: R'R is not read, but valid)
+    unsigned long long code[2] = {0, 0};
+    if (cs == CS_CD_REG && reg_pairs(reg_kmax(K)))
+        if ((rc = probe_code_base(K, cb, nullptr, code))) return rc;
+    if ((rc = launch_order_table(seed, iter, K, rows, order_mode, cs, code[0], code[1], order, nullptr))) return rc;
+    ColArgs a{};
+    a.stat = stat;
+    a.stat_len = stat_len;
+    a.K = K;
+    a.KP = KP;
+    a.RtR = RtR;
+    a.Qfull = Qfull;
+    a.C = C;
+    a.mode = COL_CD;
+    a.cd.lambda = lambda;
+    a.cd.alpha = alpha;
+    a.cd.tol = tol;
+    a.cd.la = lambda * alpha;
+    a.cd.l2 = lambda * (1.0 - alpha);
+    a.cd.two_la = 2.0 * a.cd.la;
+    a.cd.inv_two_la = a.cd.la > 0.0 ? 0.5 / a.cd.la : 0.0;
+    a.cd.max_sweeps = ms;
+    a.cd.order = order;
+    a.sweeps = sw;
+    a.hsave = a.isave = C;   // read by a resumed pass only (none here)
     Event e0, e1;
     HIPCHECK(hipEventCreate(e0.out()));
     HIPCHECK(hipEventCreate(e1.out()));
-    HIPCHECK(hipEventRecord(e0, 0));
-    const size_t r16_bytes = (size_t)r16_lds_doubles(K) * sizeof(double);
-    if (reg) {   // (the register-resident solver's state is scaled by 1 / (2 lambda alpha))
-        REG_DISPATCH(K, hipLaunchKernelGGL((k_cd_batch_reg<SL_, KM_>), dim3(cdiv(nprob, 4)), dim3(64), 0, 0, dG, dq, dw, K,
-                                           nprob, cd, db, ds, (unsigned long long *)nullptr));
-    } else if (K <= 16) hipLaunchKernelGGL((k_cd_batch<16, 4>), dim3(cdiv(nprob, 16)), dim3(256), 0, 0, dG, dq, dw, K, nprob, cd, db, ds);
-    else if (K <= 32) hipLaunchKernelGGL((k_cd_batch<32, 2>), dim3(cdiv(nprob, 4)), dim3(128), 0, 0, dG, dq, dw, K, nprob, cd, db, ds);
-    else if (reg3) {   // 32 < K <= 48: register-resident with the third slot's matrix columns in LDS
-        REG3_DISPATCH(K, hipLaunchKernelGGL((k_cd_batch_reg<SL_, KM_>), dim3(cdiv(nprob, 4)), dim3(64), 0, 0, dG, dq, dw, K,
-                                            nprob, cd, db, ds, (unsigned long long *)nullptr));
+    float total = 0.0f;
+    for (int64_t b0 = 0; b0 < nprob; b0 += chunk) {
+        const int n = (int)std::min<int64_t>(chunk, nprob - b0);
+        hipLaunchKernelGGL(k_pack_cols, dim3(cdiv((int64_t)n * stat_len, 256)), dim3(256), 0, 0, dG + (size_t)b0 * K * K,
+                           dq + (size_t)b0 * K, dw + (size_t)b0 * K, K, KP, n, stat_len, stat, Qfull, C);
+        KCHECK();
+        a.p = n;
+        HIPCHECK(hipEventRecord(e0, 0));
+        if ((rc = launch_cd(cs, a, 0))) return rc;
+        HIPCHECK(hipEventRecord(e1, 0));
+        HIPCHECK(hipEventSynchronize(e1));
+        float msf = 0.0f;
+        (void)hipEventElapsedTime(&msf, e0, e1);
+        total += msf;
+        HIPCHECK(hipMemcpy2D(beta_out + (size_t)b0 * K, (size_t)K * sizeof(double), C, (size_t)KP * sizeof(double),
+                             (size_t)K * sizeof(double), (size_t)n, hipMemcpyDeviceToHost));
+        if (sweeps_out) HIPCHECK(hipMemcpy(sweeps_out + b0, sw, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
     }
-    else if (K <= 48) {   // lambda alpha = 0: the LDS-resident row16 solver
-        if (int rl = r16_wide_lds(r16_bytes)) return rl;
-        hipLaunchKernelGGL((k_cd_batch_r16<3>), dim3(cdiv(nprob, 4)), dim3(64), r16_bytes, 0, dG, dq, dw, K, nprob, cd, db, ds);
-    }
-    else hipLaunchKernelGGL((k_cd_batch<64, 1>), dim3((unsigned)nprob), dim3(64), 0, 0, dG, dq, dw, K, nprob, cd, db, ds);
-    KCHECK();
-    HIPCHECK(hipEventRecord(e1, 0));
-    HIPCHECK(hipDeviceSynchronize());
-    float msf = 0;
-    (void)hipEventElapsedTime(&msf, e0, e1);
-    g_last_cd_ms = msf;
-    HIPCHECK(hipMemcpy(beta_out, db, (size_t)nprob * K * sizeof(double), hipMemcpyDeviceToHost));
-    if (sweeps_out) HIPCHECK(hipMemcpy(sweeps_out, ds, (size_t)nprob * sizeof(int), hipMemcpyDeviceToHost));
+    g_last_cd_ms = total;
+    g_last_cd_solver = cs;
     return INSIDER_OK;
 }
 
@@ -2891,6 +2933,7 @@ int insider_hip_col_stats(insider_hip_handle *h, double *const *A, int inc_conti
 }
 
 double insider_hip_last_cd_ms(void) { return g_last_cd_ms; }
+int insider_hip_last_cd_solver(void) { return g_last_cd_solver; }
 
 int insider_hip_get_sweeps(insider_hip_handle *h, int32_t *out)
 {

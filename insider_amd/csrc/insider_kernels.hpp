@@ -1144,33 +1144,28 @@ k_test_sse_list(const uint32_t *__restrict__ ptr, const int *__restrict__ lidx, 
 }
 
 // ---------------------------------------------------------------------------------------------
-// Kernel: batched stand-alone CD from dense (XtX, Xty) in global memory (insider_hip_strong_cd)
+// Kernel: the batch entry's dense problems (insider_hip_strong_cd) in the column solvers' layout
 // ---------------------------------------------------------------------------------------------
-template <int W, int WPB>
-__global__ void __launch_bounds__(WPB * 64)
-k_cd_batch(const double *__restrict__ XtX, const double *__restrict__ Xty, const double *__restrict__ wstart, int K,
-           int64_t nprob, CdParams cd, double *__restrict__ beta_out, int *__restrict__ sweeps_out)
+// Record j of `stat` (stat_len doubles) holds problem j's XtX where a statistics record holds XtX_j: cell (r, c) of the
+// lower-block-stored form (stat_index) = XtX[r * K + c] with r >= c — ONE triangle of the symmetric input, mirrored into
+// the upper half of the diagonal blocks, which the register-resident kernel also reads — and 0 outside K x K, row KP - 1
+// included, so that the solvers' q = Qfull - 0 = Xty.  Rows j of Qfull and C (pitch KP): Xty and the warm start, 0 beyond K.
+__global__ void __launch_bounds__(256) k_pack_cols(const double *__restrict__ XtX, const double *__restrict__ Xty,
+                                                   const double *__restrict__ wstart, int K, int KP, int n, int stat_len,
+                                                   double *__restrict__ stat, double *__restrict__ Qfull, double *__restrict__ C)
 {
-    constexpr int GPW = 64 / W;
-    __shared__ double s_G[WPB][GPW][W * W];
-    __shared__ int s_ord[WPB][80];
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int grp = lane / W, l = lane & (W - 1);
-    const int64_t b = ((int64_t)blockIdx.x * WPB + w) * GPW + grp;
-    const bool prob = b < nprob, valid = prob && l < K;
-    double *Goff = s_G[w][grp];
-    double Gll = 1.0;
-    for (int k = 0; k < K; ++k) {
-        double v = valid ? XtX[(size_t)b * K * K + (size_t)k * K + l] : 0.0;
-        if (k == l) { Gll = valid ? v : 1.0; v = 0.0; }
-        Goff[k * W + l] = v;
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= (int64_t)n * stat_len) return;
+    const int j = (int)(t / stat_len), e = (int)(t % stat_len), blk = e >> 8;
+    int bi = 0;   // block (bi, bj) of the lower block triangle: blk = bi (bi + 1) / 2 + bj
+    while ((bi + 1) * (bi + 2) / 2 <= blk) ++bi;
+    const int r0 = 16 * bi + ((e >> 4) & 15), c0 = 16 * (blk - bi * (bi + 1) / 2) + (e & 15);
+    const int r = r0 > c0 ? r0 : c0, c = r0 > c0 ? c0 : r0;
+    stat[t] = (r < K && c < K) ? XtX[(size_t)j * K * K + (size_t)r * K + c] : 0.0;
+    if (e < KP) {   // (stat_len >= 256 > KP)
+        Qfull[(size_t)j * KP + e] = e < K ? Xty[(size_t)j * K + e] : 0.0;
+        C[(size_t)j * KP + e] = e < K ? wstart[(size_t)j * K + e] : 0.0;
     }
-    wave_sync();
-    const double q = valid ? Xty[(size_t)b * K + l] : 0.0;
-    double beta = valid ? wstart[(size_t)b * K + l] : 0.0, g;
-    const int sw = cd_sweeps<W>(Goff, s_ord[w], K, Gll, q, beta, g, valid, cd, lane);
-    if (valid) beta_out[(size_t)b * K + l] = beta;
-    if (prob && l == 0 && sweeps_out) sweeps_out[b] = sw < 0 ? -sw : sw;
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -33,7 +33,7 @@ for K in (5, 30):
     differs = any(c_oracle.sweep_order(K, 3, 1, s) != c_oracle.sweep_order(K, 3, 1, s + 1) for s in range(PERIOD - 1))
     report(f"oracle order period K={K}", same and differs, f"period {PERIOD}")
 
-# (1) the stand-alone batch solver: nearly collinear designs (CD needs thousands of sweeps), tol < 0 = every solve runs exactly to
+# (1) the batch entry (the column update's kernels on packed dense problems): nearly collinear designs (CD needs thousands of sweeps), tol < 0 = every solve runs exactly to
 #     the cap, far from converged — so the iterate at the cap depends on every sweep's order: an order-perturbed oracle run
 #     (another outer-iteration stream) lands somewhere else, the library (same stream, wrapped 5 times) on the oracle's iterate
 rng = np.random.default_rng(5)

@@ -1,5 +1,8 @@
 """Every column-solver kernel that launch_col_solve() and the batch entry can launch, against the CPU oracle.
 
+The batch entry (insider_hip_strong_cd) runs the column update's elastic-net kernels with the default cd_variant, and
+insider_hip_last_cd_solver() reports which one; its tests assert it as well.
+
 launch_col_solve() (insider_amd/csrc/insider_hip.hip) picks one of ten kernels from the K band, from whether lambda alpha > 0,
 alpha > 0 or alpha == 0, and from the option cd_variant; insider_hip_get_info("col_solver" / "col_eval") reports which one
 ran.  SOLVER below is that choice written out by hand: each test asserts the kernel it reached, so that a dispatch edit that
@@ -313,6 +316,8 @@ def test_strong_cd_batch_every_solver(oracle, regime, K):
         for cap in (3, UNCAPPED):
             beta, sw = api.strong_coordinate_descent(None, None, ws, lam, alpha, Gs, qs, tol=TOL, seed=5, it=3,
                                                      order_mode=mode, max_sweeps=cap, return_sweeps=True)
+            assert _lib.COL_SOLVERS[_lib.load().insider_hip_last_cd_solver()] == \
+                expected("enet" if regime == "enet" else "nol1", 0, K), (mode, cap)
             for b in range(B):
                 ob, osw = oracle.strong_cd(Xs[b], ys[b], ws[b], lam, alpha, Gs[b], qs[b], tol=TOL, seed=5, unit=b, it=3,
                                            order_mode=mode, max_sweeps=cap)

@@ -181,6 +181,7 @@ def test_strong_cd_every_register_kernel_instantiation(oracle, K):
     lam = 0.35 * float(np.max(np.abs(qs)))       # the strong rule screens out part of the coordinates
     beta, sw = api.strong_coordinate_descent(None, None, ws, lam, 0.6, Gs, qs, tol=1e-10, seed=5, it=3,
                                              return_sweeps=True)
+    assert _lib.COL_SOLVERS[_lib.load().insider_hip_last_cd_solver()] == ("cd_reg" if K <= 32 else "cd_reg3")
     for b in range(B):
         ob, osw = oracle.strong_cd(Xs[b], ys[b], ws[b], lam, 0.6, Gs[b], qs[b], tol=1e-10, seed=5, unit=b, it=3)
         assert abs(osw - sw[b]) <= 1, (K, b, osw, sw[b])

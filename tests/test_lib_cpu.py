@@ -146,7 +146,7 @@ def test_workload_configs():
     assert np.array_equal(slab.X, full.X[:, 1000:2100]) and np.array_equal(slab.M_train, full.M_train[:, 1000:2100])
 
 
-def test_sweep_kernels_do_not_spill(tmp_path, lib):
+def test_column_sweep_kernels_do_not_spill(tmp_path, lib):
     """The register-resident sweep kernels (insider_cd_reg.hpp) must not spill.
 
     Twice (KMAX = 22 in round 2, KMAX = 20 in round 3) a 128-VGPR build of the column-update kernel wrote its results to
@@ -154,9 +154,10 @@ def test_sweep_kernels_do_not_spill(tmp_path, lib):
     region, the reload ran under the full mask, and the lanes that had been masked off used stale scratch.  The kernels are
     now written so that nothing needs spilling; this test disassembles the shipped code object and checks that
       * every instantiation up to KMAX = 30 (K <= 30 covers the BASELINE configurations) contains NO scratch instruction at
-        all, the solve kernels (with their sweep loop), the evaluation kernels and the stand-alone batch solver alike;
+        all, the solve kernels (with their sweep loop) and the evaluation kernels alike;
       * KMAX = 32 (168 VGPRs for 128 matrix registers) keeps its sweep loop free of scratch traffic;
-      * no kernel of the whole library stores a spill under a narrowed exec mask (tools/spill_scan.py)."""
+      * no kernel of the whole library stores a spill under a narrowed exec mask (tools/spill_scan.py);
+      * the batch entry (insider_hip_strong_cd) has no kernels of its own: it runs these same ones."""
     import re as _re
     import shutil
     import subprocess
@@ -180,7 +181,7 @@ def test_sweep_kernels_do_not_spill(tmp_path, lib):
     loops = kernels = 0
     for fn in funcs:
         head = fn.split("\n", 1)[0]
-        if "k_cd_cols_reg" not in head and "k_cd_batch_reg" not in head:
+        if "k_cd_cols_reg" not in head:
             continue
         kernels += 1
         kmax = int(_re.search(r"ILi[123]ELi(\d+)E", head).group(1))
@@ -198,7 +199,7 @@ def test_sweep_kernels_do_not_spill(tmp_path, lib):
         pb = 96 - 2 * kmax
         first = f"s_load_dwordx16 s[{pb}:{pb + 15}]" if kmax <= 30 else ("s_load_dwordx16 s[48:63]" if kmax > 32 else "s_load_dwordx16 s[64:79]")
         sites = [i for i, (_, t, _r) in enumerate(ins) if t.startswith(first)]
-        if "k_cd_cols_reg" in head and "ELb0E" in head:
+        if "ELb0E" in head:
             assert not sites and not any(t.startswith("s_setpc_b64") for _a, t, _r in ins), head   # the evaluation kernels have no sweep loop
             continue
         if kmax <= 30:
@@ -206,9 +207,9 @@ def test_sweep_kernels_do_not_spill(tmp_path, lib):
             # one computed jump per code block and one into the first block, each on its own register pair; no address add
             jumps = [t for _a, t, _r in ins if t.startswith("s_setpc_b64 s[")]
             assert len(set(jumps)) == kmax + 1, (head, len(set(jumps)))
-            # the column-update kernel also carries its blocks of two steps (a section of their own behind insider_cdpair_<KMAX>;
-            # the disassembly lists them under the kernel in front of that label): one jump per block, 16 x 16 + W x W of them
-            npair = 256 + (kmax - 16) ** 2 if "k_cd_cols_reg" in head else 0
+            # the kernel also carries its blocks of two steps (a section of their own behind insider_cdpair_<KMAX>; the
+            # disassembly lists them under the kernel in front of that label): one jump per block, 16 x 16 + W x W of them
+            npair = 256 + (kmax - 16) ** 2
             assert len(jumps) in (kmax + 1, kmax + 1 + npair), (head, len(jumps))
             assert not any(t.startswith("s_add_u32 vcc_lo") for _a, t, _r in ins), head
             # the loop body = from the table of blocks to the jump back into the first block (label Lgo): no scratch traffic, no
@@ -248,12 +249,13 @@ def test_sweep_kernels_do_not_spill(tmp_path, lib):
         assert len(body) > 100, (head, len(body))                     # the whole sweep (code blocks + loss bookkeeping) is in it
         spills = [t for t in body if t.startswith(("scratch_", "buffer_load", "buffer_store"))]
         assert not spills, (head, spills[:4])
-        if "k_cd_cols_reg" in head:   # ... nor parks values in accumulation registers (the three-slot kernels use up to 251 VGPRs)
-            parked = [t for t in body if t.startswith("v_accvgpr")]
-            assert not parked, (head, parked[:4])
+        parked = [t for t in body if t.startswith("v_accvgpr")]   # ... nor parks values in accumulation registers (the three-slot
+        assert not parked, (head, parked[:4])                      # kernels use up to 251 VGPRs)
         loops += 1
-    # 9 register budgets x {solve, evaluate, stand-alone batch solver} + 4 three-slot budgets (32 < K <= 47) x {solve, batch solver}
-    assert loops == 26 and kernels == 35, (loops, kernels)
+    # 9 register budgets x {solve, evaluate} + 4 three-slot budgets (32 < K <= 47), solve only: the batch entry runs these kernels
+    # too, and no second copy of the sweep loop is built for it
+    assert loops == 13 and kernels == 22, (loops, kernels)
+    assert "k_cd_batch" not in dis
 
 
 def test_bench_gpus_n_starts_its_own_ranks(monkeypatch):

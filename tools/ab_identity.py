@@ -2,7 +2,9 @@
     INSIDER_HIP_LIB=<build> python tools/ab_identity.py run <tag>     factors, sweep counts, trajectory -> gpurun_out/ab/<tag>.npz
     python tools/ab_identity.py cmp <tagA> <tagB>                     every array equal, bit for bit?
 Cases: c2 in full (K = 20: the four-wave kernel), a 10000 x 8192 slab of c3 (K = 30), a K = 16 and a K = 32 fit, 31 outer
-iterations each from the N(0, 1e-6) inits (cold multi-pass iterations included), and one deep fit (sub_tol 1e-7, 61 iterations)."""
+iterations each from the N(0, 1e-6) inits (cold multi-pass iterations included), and one deep fit (sub_tol 1e-7, 61 iterations);
+then the batch entry (insider_hip_strong_cd: solutions and sweep counts) in every K band up to K = 64, with an l1 term (enet),
+lambda = 0 and alpha = 0, on exactly symmetric XtX (the entry reads one triangle)."""
 import os, sys
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -31,6 +33,22 @@ def run(tag):
         print(f"{tag} case {ci} {name} {kw}: K={w.K} iters={res['iters']} last-iteration sweeps mean {np.mean(sw):.1f} max {np.max(sw)}",
               flush=True)
         ds.close()
+    for K in (1, 7, 16, 17, 24, 30, 31, 32, 33, 40, 47, 48, 49, 63, 64):
+        rng = np.random.default_rng(700 + K)
+        B, m = 33, 3 * K + 20                                # a partial last wave at 4 and at 16 problems per wave
+        Xs = rng.standard_normal((B, m, K))
+        ys = np.einsum("bmk,bk->bm", Xs, rng.standard_normal((B, K)) * (rng.random((B, K)) < 0.5)) + 0.3 * rng.standard_normal((B, m))
+        Gs = np.einsum("bmk,bml->bkl", Xs, Xs)
+        Gs = 0.5 * (Gs + Gs.transpose(0, 2, 1))
+        qs = np.einsum("bmk,bm->bk", Xs, ys)
+        ws = 0.1 * rng.standard_normal((B, K))
+        for regime, (lam, alpha) in (("enet", (0.35 * float(np.max(np.abs(qs))), 0.6)), ("lambda0", (0.0, 0.5)), ("alpha0", (3.0, 0.0))):
+            for mode, cap in ((0, 1 << 24), (1, 1 << 24), (0, 3)):
+                beta, sw = api.strong_coordinate_descent(None, None, ws, lam, alpha, Gs, qs, tol=1e-10, seed=5, it=3, order_mode=mode,
+                                                         max_sweeps=cap, return_sweeps=True)
+                out[f"cd_K{K}_{regime}_m{mode}_c{cap}_beta"] = beta
+                out[f"cd_K{K}_{regime}_m{mode}_c{cap}_sweeps"] = sw
+        print(f"{tag} strong_cd K={K}: 3 regimes x 3 runs, last sweeps mean {np.mean(sw):.1f}", flush=True)
     np.savez(os.path.join(OUT, tag + ".npz"), **out)
 
 
