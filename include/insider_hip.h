@@ -94,6 +94,25 @@ void insider_hip_destroy(insider_hip_handle *h);
  * not depend on which handle ran it or on what ran beside it. */
 int insider_hip_clone(insider_hip_handle *src, insider_hip_handle **out);
 
+/* A handle on a NEW data set over the SAME resident X: the mask-independent device arrays of src's data set (X, the level
+ * and chunk tables, the all-entry sums, the pair counts) are shared — not copied, not uploaded again; the codes, held-out
+ * lists, train sums, group tables and per-gene counts are built for the new masks (n x p uint8 column-major, as for
+ * insider_hip_create) by the stages insider_hip_create_ex runs.  Workspace, streams and options as insider_hip_clone (options
+ * copied as they stand).  src may be a clone or itself a re-masked handle; either may be destroyed first; the shared arrays
+ * go with the last handle that uses them.  A fit on the new handle is bit-identical to one on a handle that
+ * insider_hip_create_ex made from the same inputs.  A sharded src (world > 1): INSIDER_ERR_UNSUPPORTED.
+ * insider_hip_get_info "data_bytes_shared" / "data_bytes_own": device bytes of the handle's data set that it holds jointly
+ * with its source / that it allocated itself (the first is 0 for a handle of insider_hip_create_ex). */
+int insider_hip_remask(insider_hip_handle *src, const uint8_t *M_train, const uint8_t *M_test, insider_hip_handle **out);
+
+/* Fold ids of the resident matrix: n x p uint8 column-major, 0 = NA, 1..F = the fold the entry is held out in (F <= 255).
+ * Stored once on the device in the layout of X, with the shared part of the data set (clones of h see them).  Values above
+ * F: INSIDER_ERR_ARG.  Calling it again replaces the ids for handles derived afterwards. */
+int insider_hip_set_folds(insider_hip_handle *h, const uint8_t *fold_id, int F);
+/* Re-mask by fold, nothing uploaded: test = entries whose id == fold, train = entries with any other id >= 1, NA = id 0.
+ * Otherwise as insider_hip_remask (the new handle carries the ids too).  fold outside 1..F or no ids set: INSIDER_ERR_ARG. */
+int insider_hip_remask_fold(insider_hip_handle *src, int fold, insider_hip_handle **out);
+
 /* Gene-axis sharding: this handle holds genes [gene_offset, gene_offset + p) of the global
  * matrix.  gene_offset keys the per-gene sweep order so results do not depend on the sharding.  `fn` (may be
  * NULL when world == 1, or when insider_hip_comm_init() supplies the exchange) is called once per covariate per outer
@@ -346,7 +365,7 @@ int insider_hip_get_profile(insider_hip_handle *h, double *out12);
 /* Facts about the handle that measurement code needs (bench.py's roofline): "col_stats_path" (0 = per-entry lists, 1 =
  * look-up form, 2 = pair-count form, as the cost model / options chose for the current K), "col_mfma_per_gene"
  * (v_mfma_f64_16x16x4 instructions the column-side statistics kernel issues per gene), "row_merged", "col_entries",
- * "row_entries" (padded held-out list lengths), "lists_bytes", "pair_count_bytes_per_gene", "stat_doubles", "kp",
+ * "row_entries" (padded held-out list lengths), "data_bytes_shared" / "data_bytes_own" (insider_hip_remask), "lists_bytes", "pair_count_bytes_per_gene", "stat_doubles", "kp",
  * "cd_ms_steady" / "col_stats_ms_steady" (option "profile": mean HIP-event time per outer iteration from iteration 5 on of
  * the last optimize(), i.e. without the cold start), "cap_hits" / "max_gene_sweeps" (of the last optimize() / optimize_col():
  * elastic-net solves ended by "max_sweeps" instead of convergence — must be 0 to match the reference, which has no cap — and

@@ -28,6 +28,7 @@ SYMBOLS = (
     "insider_hip_comm_unique_id", "insider_hip_comm_init", "insider_hip_get_array", "insider_hip_clone",
     "insider_hip_optimize_continuous_v2", "insider_hip_residual", "insider_hip_interaction_glm",
     "insider_hip_variance_decomposition", "insider_hip_col_stats", "insider_hip_last_cd_solver",
+    "insider_hip_remask", "insider_hip_set_folds", "insider_hip_remask_fold",
 )
 COMM_ID_BYTES = 128
 # insider_hip_get_info("col_solver" / "col_eval") and insider_hip_last_cd_solver(): the column-solve kernel behind each code
@@ -87,6 +88,9 @@ def load():
     lib.insider_hip_create_ex.argtypes = [dp, C.c_int64, C.c_int64, i32p, C.c_int, i32p, dp, C.c_int, u8p, u8p, C.c_int,
                                           C.POINTER(C.c_void_p)]
     lib.insider_hip_clone.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+    lib.insider_hip_remask.argtypes = [C.c_void_p, u8p, u8p, C.POINTER(C.c_void_p)]
+    lib.insider_hip_set_folds.argtypes = [C.c_void_p, u8p, C.c_int]
+    lib.insider_hip_remask_fold.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
     lib.insider_hip_destroy.argtypes = [C.c_void_p]
     lib.insider_hip_destroy.restype = None
     lib.insider_hip_set_shard.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_int, ALLREDUCE_FN, C.c_void_p]

@@ -69,8 +69,63 @@ class InsiderData:
         other._h = C.c_void_p()
         other._cb = None
         other._options = dict(getattr(self, "_options", {}))       # the library copies the options as they stand
+        other._folds = self._fold_state()                          # one data set: the clone sees the same fold ids
         _lib.check(_lib.load().insider_hip_clone(self._h, C.byref(other._h)))
         return other
+
+    def _fold_state(self):
+        """{"F": number of folds} once set_folds() has run on a handle of this data set; shared by its clones."""
+        return self.__dict__.setdefault("_folds", {})
+
+    def _derived(self, call):
+        """A handle on a new data set over this one's resident X (insider_hip_remask / insider_hip_remask_fold)."""
+        other = object.__new__(InsiderData)
+        other.n, other.p, other.c, other.m, other.n_levels = self.n, self.p, self.c, self.m, self.n_levels
+        other._h = C.c_void_p()
+        other._cb = None
+        other._options = dict(getattr(self, "_options", {}))
+        other._folds = dict(self._fold_state())                    # the new data set carries the ids it was derived under
+        _lib.check(call(C.byref(other._h)))
+        return other
+
+    def remask(self, train_indicator, test_indicator):
+        """A handle on a NEW data set over the SAME resident X with other masks (insider_hip_remask): X, the level and chunk
+        tables, the all-entry sums and the pair counts are shared with this handle's data set (no second upload, no second
+        device copy); the codes, lists and per-gene counts are built for the new masks.  Everything a created data set does
+        works on it, with bit-identical results; either handle may be closed first."""
+        Mtr = np.asfortranarray(train_indicator, dtype=np.uint8)
+        Mte = np.asfortranarray(test_indicator, dtype=np.uint8)
+        if Mtr.shape != (self.n, self.p) or Mte.shape != (self.n, self.p):
+            raise InsiderError(_lib.ERR_ARG, "indicator shape must match data")
+        lib = _lib.load()
+        return self._derived(lambda out: lib.insider_hip_remask(self._h, _lib.ptr(Mtr, C.c_uint8), _lib.ptr(Mte, C.c_uint8), out))
+
+    def set_folds(self, fold_id, n_folds=None):
+        """Store the fold ids of the resident matrix on the device (insider_hip_set_folds): n x p, 0 = NA, 1..F = the fold
+        the entry is held out in (``n_folds`` = F, default the largest id).  fold(f) then re-masks without any upload."""
+        ids = np.asarray(fold_id)
+        if ids.shape != (self.n, self.p):
+            raise InsiderError(_lib.ERR_ARG, "fold_id shape must match data")
+        lo, hi = (int(ids.min()), int(ids.max())) if ids.size else (0, 0)
+        F = hi if n_folds is None else int(n_folds)
+        if not 1 <= F <= 255:
+            raise InsiderError(_lib.ERR_ARG, "the number of folds must be in 1..255")
+        if lo < 0 or hi > F or not np.array_equal(ids, np.round(ids)):
+            raise InsiderError(_lib.ERR_ARG, f"fold ids must be integers within 0..{F}")
+        ids = np.asfortranarray(ids, dtype=np.uint8)
+        _lib.check(_lib.load().insider_hip_set_folds(self._h, _lib.ptr(ids, C.c_uint8), F))
+        self._fold_state()["F"] = F
+
+    def fold(self, f):
+        """The data set of fold f (1-based; insider_hip_remask_fold): test = the entries whose fold id is f, train = the
+        entries of every other fold, NA = id 0.  As remask(), with the codes formed on the device from the resident ids."""
+        F = self._fold_state().get("F")
+        if F is None:
+            raise InsiderError(_lib.ERR_ARG, "no fold ids set: call set_folds() first")
+        if int(f) != f or not 1 <= int(f) <= F:
+            raise InsiderError(_lib.ERR_ARG, f"fold must be in 1..{F}")
+        lib = _lib.load()
+        return self._derived(lambda out: lib.insider_hip_remask_fold(self._h, int(f), out))
 
     def set_option(self, name, value):
         _lib.check(_lib.load().insider_hip_set_option(self._h, name.encode(), float(value)))
@@ -510,13 +565,47 @@ def ratio_splitter(data, ratio=0.1, rm_na_col=True, seed=123):
                 test_indicator=test[:, keep], na_indicator=na[:, keep], kept_columns=keep)
 
 
+def fold_splitter(data, folds=5, rm_na_col=True, seed=123):
+    """k-fold counterpart of ratio_splitter(): NA -> 0 and fold id 0; the non-NA entries are permuted (numpy PCG64, like
+    ratio_splitter) and dealt round-robin to the folds 1..F, so fold sizes differ by at most one and every non-NA entry is
+    held out in exactly one fold.  A column is kept when its non-zero entries lie in at least two folds: R/utils.R:102-109
+    drops a column whose train set is all zero, and the train set of fold f is every other fold, so the rule holds for every
+    fold at once exactly then.  Returns fold_id (uint8), na_indicator and data over the kept columns, and kept_columns."""
+    F = int(folds)
+    if not 2 <= F <= 255:
+        raise ValueError("fold_splitter(): folds must be in 2..255")
+    data = np.array(data, dtype=np.float64, order="F")
+    na = np.isnan(data)
+    data[na] = 0.0
+    rng = np.random.Generator(np.random.PCG64(seed))
+    existing = np.flatnonzero((~na).ravel(order="F"))
+    ids = np.zeros(data.size, dtype=np.uint8)
+    ids[rng.permutation(existing)] = (np.arange(existing.size) % F + 1).astype(np.uint8)
+    ids = ids.reshape(data.shape, order="F")
+    nz = data != 0
+    folds_with_nz = sum(((ids == f) & nz).any(axis=0).astype(np.int64) for f in range(1, F + 1))
+    keep = folds_with_nz >= 2 if rm_na_col else np.ones(data.shape[1], dtype=bool)
+    print(f"number of columns removed by the fold rule: {int((~keep).sum())}")
+    return dict(fold_id=np.asfortranarray(ids[:, keep]), na_indicator=na[:, keep], kept_columns=keep,
+                data=np.asfortranarray(data[:, keep]))
+
+
+def pooled_rmse(fold_rmse, fold_counts):
+    """Cross-validated RMSE of fold RMSEs rmse_f over n_f held-out entries each: sqrt(sum_f n_f rmse_f^2 / sum_f n_f) — every
+    held-out entry counted once.  ``fold_rmse``: (..., F); ``fold_counts``: (F,)."""
+    r = np.asarray(fold_rmse, dtype=np.float64)
+    w = np.asarray(fold_counts, dtype=np.float64)
+    return np.sqrt((r * r * w).sum(axis=-1) / w.sum())
+
+
 class Insider(dict):
     """The reference's S3 object of class "insider" (a list, R/insider.R:24)."""
 
 
 def insider(data, confounder, ctns_confounder=None, interaction_idx=None, split_ratio=0.1, global_tol=1e-9,
-            sub_tol=1e-5, tuning_iter=30, max_iter=50000, device=0, seed=DEFAULT_SEED):
-    """insider() of R/insider.R:18-67."""
+            sub_tol=1e-5, tuning_iter=30, max_iter=50000, device=0, seed=DEFAULT_SEED, folds=None):
+    """insider() of R/insider.R:18-67.  ``folds`` = k (not in the reference): the object also carries ``fold_id``
+    (fold_splitter) for tune(folds=True), over the columns both splitters keep."""
     data = np.asarray(data, dtype=np.float64)
     confounder = np.asarray(confounder)
     if confounder.ndim == 1:
@@ -524,6 +613,14 @@ def insider(data, confounder, ctns_confounder=None, interaction_idx=None, split_
     dataset = ratio_splitter(data, ratio=split_ratio)
     obj = Insider()
     keep = dataset["kept_columns"]
+    fold_id = None
+    if folds is not None:
+        fs = fold_splitter(data, folds=folds)
+        both = keep & fs["kept_columns"]
+        fold_id = fs["fold_id"][:, both[fs["kept_columns"]]]
+        for name in ("train_indicator", "test_indicator", "na_indicator"):
+            dataset[name] = dataset[name][:, both[keep]]
+        keep = both
     d = np.array(data[:, keep], dtype=np.float64, order="F")
     d[np.isnan(d)] = 0.0                                      # R/insider.R:26 (intent: NA -> 0)
     obj["data"] = d
@@ -546,6 +643,8 @@ def insider(data, confounder, ctns_confounder=None, interaction_idx=None, split_
     obj["train_indicator"] = np.asfortranarray(dataset["train_indicator"], dtype=np.uint8)   # :57-59
     obj["test_indicator"] = np.asfortranarray(dataset["test_indicator"], dtype=np.uint8)
     obj["na_indicator"] = np.asfortranarray(dataset["na_indicator"], dtype=np.uint8)
+    if fold_id is not None:
+        obj["fold_id"] = np.asfortranarray(fold_id, dtype=np.uint8)
     obj["params"] = dict(global_tol=global_tol, sub_tol=sub_tol, tuning_iter=tuning_iter, max_iter=max_iter)
     obj["device"] = device
     obj["seed"] = seed
@@ -560,8 +659,13 @@ def _resident(obj, which):
             tr, te = obj["train_indicator"], obj["test_indicator"]
         else:  # R/insider.R:207-208: indicator = train + test, "test" = NA mask
             tr, te = obj["train_indicator"] + obj["test_indicator"], obj["na_indicator"]
-        obj[key] = InsiderData(obj["data"], obj["confounder"], tr, te, device=obj.get("device", 0),
-                               ctns_confounder=obj["ctns_confounder"] if obj["inc_continuous"] == 1 else None)
+        other = obj.get("_resident_" + ("fit" if which == "tune" else "tune"))
+        if other is not None and getattr(other, "_h", None):
+            # the same X under other masks: share the resident matrix instead of a second upload and device copy
+            obj[key] = other.remask(tr, te)
+        else:
+            obj[key] = InsiderData(obj["data"], obj["confounder"], tr, te, device=obj.get("device", 0),
+                                   ctns_confounder=obj["ctns_confounder"] if obj["inc_continuous"] == 1 else None)
     return obj[key]
 
 
@@ -620,8 +724,141 @@ def _tune_handles(obj, ds, k):
     return [ds] + clones[: k - 1]
 
 
+def _fold_handles(obj, ds):
+    """The fold data sets ds.fold(1..F) of the resident tune data set, derived once and kept on the object."""
+    hs = obj.get("_fold_handles", [])
+    if not hs or any(not getattr(hd, "_h", None) or getattr(hd, "_src", None) is not ds for hd in hs):
+        fold_id = np.asarray(obj["fold_id"])
+        ds.set_folds(fold_id, int(fold_id.max()))
+        hs = []
+        for f in range(1, int(fold_id.max()) + 1):
+            hd = ds.fold(f)
+            hd._src = ds
+            hs.append(hd)
+        obj["_fold_handles"] = hs
+        obj["_fold_clones"] = {}
+    return hs
+
+
+def _tune_folds(obj, lat, lam, alp, out_dir, rng, rank, world, timings, concurrent):
+    """tune(folds=True): every point of the rank sweep and of the (lambda, alpha) grid is fitted once per fold."""
+    import queue
+    import threading
+    import time as _time
+    prm = obj["params"]
+    seed = obj.get("seed", DEFAULT_SEED)
+    ds = _resident(obj, "tune")
+    handles = _fold_handles(obj, ds)
+    F = len(handles)
+    fold_id = np.asarray(obj["fold_id"])
+    n_f = np.array([(fold_id == f).sum() for f in range(1, F + 1)], dtype=np.float64)
+    k = max(1, int(concurrent))
+
+    def _handle(worker, f):
+        """Worker 0 fits on the fold handles themselves, worker w > 0 on clones of them (made on first use, kept)."""
+        if worker == 0:
+            return handles[f]
+        clones = obj.setdefault("_fold_clones", {})
+        hd = clones.get((worker, f))
+        if hd is None or not getattr(hd, "_h", None):
+            hd = clones[(worker, f)] = handles[f].clone()
+        return hd
+
+    def _run(points, label):
+        """points: (K, lambda, alpha) in the reference's order.  Returns the per-fold train and test RMSE (points x F)."""
+        tr = np.zeros((len(points), F))
+        te = np.zeros((len(points), F))
+        tasks = queue.Queue(maxsize=2 * k * F)
+        lock = threading.Lock()
+        errors = []
+
+        def _producer():
+            try:
+                for g, (K_, l_, a_) in enumerate(points):
+                    if errors:
+                        break
+                    t_0 = _time.perf_counter()
+                    cfd, col = _fresh_inits(obj, K_, rng)       # ONE draw per point, whatever the number of folds
+                    t_draw = _time.perf_counter() - t_0
+                    if g % world != rank:
+                        continue
+                    with lock:
+                        print(label(K_, l_, a_))
+                    for f in range(F):                          # every fold starts from copies of the point's inits
+                        tasks.put((g, f, [a.copy(order="F") for a in cfd], col.copy(order="F"), t_draw))
+            except BaseException as e:
+                errors.append(e)
+            finally:
+                for _ in range(k):
+                    tasks.put(None)
+
+        def _worker(w):
+            while True:
+                item = tasks.get()
+                if item is None:
+                    return
+                if errors:
+                    continue
+                g, f, cfd, col, t_draw = item
+                K_, l_, a_ = points[g]
+                t_1 = _time.perf_counter()
+                try:
+                    hd = _handle(w, f)
+                    fitted = hd.optimize(cfd, col, K_, l_, l_, a_, 1, prm["global_tol"], prm["sub_tol"], prm["tuning_iter"],
+                                         seed=seed, inc_continuous=obj["inc_continuous"], copy=False)
+                except Exception as e:
+                    errors.append(e)
+                    continue
+                with lock:
+                    tr[g, f], te[g, f] = fitted["train_rmse"], fitted["test_rmse"]
+                    if timings is not None:
+                        timings.append(dict(latent_rank=K_, lambda_=l_, alpha=a_, fold=f + 1, init_s=t_draw, init_wait_s=0.0,
+                                            warm_from=None, optimize_s=_time.perf_counter() - t_1,
+                                            library_ms=hd.profile()["wall_ms"]))
+
+        threads = [threading.Thread(target=_producer)] + [threading.Thread(target=_worker, args=(w,)) for w in range(k)]
+        for t in threads:
+            t.start()
+        for t in threads:
+            t.join()
+        if errors:
+            raise errors[0]
+        return _grid_sum(tr, world), _grid_sum(te, world)
+
+    def _save(name, table):
+        if out_dir is not None and rank == 0:
+            np.savetxt(os.path.join(out_dir, name), table, delimiter=",")
+
+    def _sd(te):
+        return te.std(axis=1, ddof=1) if F > 1 else np.zeros(len(te))
+
+    out = dict(rank_tuning=None, reg_tuning=None, rank_tuning_folds=None, reg_tuning_folds=None, rank_tuning_test_sd=None,
+               reg_tuning_test_sd=None, fold_counts=n_f)
+    if lat.size > 1:
+        l_, a_ = (float(lam[0]), float(alp[0])) if lam.size == 1 and alp.size == 1 else (0.1, 0.0)
+        tr, te = _run([(int(K_), l_, a_) for K_ in lat], lambda K_, l, a: f"Latent rank:  {K_} ---------------------------------")
+        out["rank_tuning"] = np.column_stack([lat.astype(np.float64), tr.mean(axis=1), pooled_rmse(te, n_f)])
+        out["rank_tuning_folds"], out["rank_tuning_test_sd"] = te, _sd(te)
+        _save("insider_rank_tuning_result.csv", out["rank_tuning"])
+        _save("insider_rank_tuning_result_folds.csv", np.column_stack([lat.astype(np.float64), te]))
+        latent_rank = int(lat[int(np.argmin(out["rank_tuning"][:, 2]))])
+    else:
+        latent_rank = int(lat[0])
+    out["latent_rank"] = latent_rank
+    if lam.size > 1 or alp.size > 1:
+        grid = [(round(float(l_), 2), round(float(a_), 2)) for a_ in alp for l_ in lam]   # expand.grid: lambda fastest
+        tr, te = _run([(latent_rank, l_, a_) for l_, a_ in grid],
+                      lambda K_, l, a: f"parameter grid: {l},{a} ---------------------------------")
+        g2 = np.array(grid, dtype=np.float64).reshape(-1, 2)
+        out["reg_tuning"] = np.column_stack([g2, tr.mean(axis=1), pooled_rmse(te, n_f)])
+        out["reg_tuning_folds"], out["reg_tuning_test_sd"] = te, _sd(te)
+        _save(f"insider_R{latent_rank}_reg_tuning_result.csv", out["reg_tuning"])
+        _save(f"insider_R{latent_rank}_reg_tuning_result_folds.csv", np.column_stack([g2, te]))
+    return out
+
+
 def tune(obj, latent_dimension=None, lambda_=0.1, alpha=0.0, out_dir=None, rng=None, rank=0, world=1, timings=None,
-         warm_start=False, concurrent=1):
+         warm_start=False, concurrent=1, folds=None):
     """tune() of R/insider.R:81-176.  ``out_dir``: where to write the reference's CSVs (None = do not write).
 
     ``warm_start`` (opt-in, NOT the reference's behaviour, which draws fresh N(0, 0.001^2) inits for every grid point,
@@ -647,7 +884,26 @@ def tune(obj, latent_dimension=None, lambda_=0.1, alpha=0.0, out_dir=None, rng=N
     column step is bound by its longest gene's sequential sweep chain, which a second fit overlaps.  The inits are still
     drawn by ONE generator in the reference's order, and every point's result is bit-identical to the serial grid's
     (tests/test_gpu_parity.py::test_concurrent_tune_is_bit_identical).  Not combinable with ``warm_start`` (whose
-    starting points depend on the order in which fits finish)."""
+    starting points depend on the order in which fits finish).
+
+    ``folds`` (default None: the single hold-out above, unchanged): with ``folds=True`` every point of the rank sweep and of
+    the grid is fitted once per fold of ``obj["fold_id"]`` (insider(folds=k)), on the data sets ``ds.fold(1..F)`` derived
+    once from the resident tune data set (InsiderData.fold: X is not uploaded or copied again) and kept on the object.  The
+    fresh inits of a point are drawn ONCE, in the reference's order from the one generator, and every fold of the point starts
+    from copies of them: the generator state after tune() does not depend on ``folds``.  ``rank_tuning`` / ``reg_tuning``
+    keep their columns, with train RMSE = the mean over the folds and test RMSE = the pooled (cross-validated) value
+    sqrt(sum_f n_f rmse_f^2 / sum_f n_f), n_f = held-out entries of fold f; ``rank_tuning_folds`` / ``reg_tuning_folds``
+    hold the per-fold test RMSE (points x F), ``*_test_sd`` their sample standard deviation.  ``concurrent`` = k runs up
+    to k (point, fold) fits at once on the fold handles and clones of them; results are bit-identical to the serial order.
+    The CSVs keep their columns; a second file ``..._folds.csv`` holds the point's parameters and its per-fold test RMSE.
+    Not combinable with ``warm_start`` (ValueError)."""
+    if folds is not None and folds is not False:
+        if warm_start:
+            raise ValueError("tune(): folds and warm_start exclude each other")
+        if folds is not True:
+            raise ValueError("tune(): folds must be None or True (the folds are those of obj['fold_id'], insider(folds=k))")
+        if "fold_id" not in obj:
+            raise ValueError("tune(folds=True): the object carries no fold ids: build it with insider(..., folds=k)")
     if concurrent > 1 and warm_start:
         raise ValueError("tune(): concurrent > 1 and warm_start exclude each other")
     import time as _time
@@ -662,6 +918,8 @@ def tune(obj, latent_dimension=None, lambda_=0.1, alpha=0.0, out_dir=None, rng=N
                          "than 1.")                                                                      # :87-89
     prm = obj["params"]
     rng = rng if rng is not None else np.random.default_rng(obj.get("seed", DEFAULT_SEED))
+    if folds:
+        return _tune_folds(obj, lat, lam, alp, out_dir, rng, rank, world, timings, concurrent)
     ds = _resident(obj, "tune")
     rank_tuning, reg_tuning = None, None
     if lat.size > 1:                                                                                     # :98-132

@@ -19,6 +19,7 @@
 #include <cstring>
 #include <limits>
 #include <memory>
+#include <mutex>
 #include <atomic>
 #include <string>
 #include <utility>
@@ -53,37 +54,61 @@ int fail(int code, const std::string &msg)
 inline int64_t round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
 inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
-// One device allocation of count T: freed on destruction and on reassignment, handed to launches as a raw pointer.
+// Device bytes allocated (and not freed again) by the calling thread while a Tally is open: what a data set's set-up
+// allocated for itself (DataSet::bytes_own), temporaries of the stages excluded.
+struct Tally {
+    int64_t bytes = 0;
+    Tally *prev;
+    static Tally *&open() { static thread_local Tally *t = nullptr; return t; }
+    Tally() : prev(open()) { open() = this; }
+    ~Tally() { open() = prev; }
+    Tally(const Tally &) = delete;
+    Tally &operator=(const Tally &) = delete;
+    static void add(int64_t b) { if (open()) open()->bytes += b; }
+};
+
+// One device allocation of count T, handed to launches as a raw pointer.  The allocation is freed when the last DevBuf that
+// holds it is destroyed or reassigned: alloc() makes a fresh one, share() joins another buffer's (a re-masked data set
+// holds the mask-independent arrays of its source this way: nothing is copied, and either side may go first).
 template <typename T>
 class DevBuf {
 public:
     DevBuf() = default;
     DevBuf(const DevBuf &) = delete;
     DevBuf &operator=(const DevBuf &) = delete;
-    DevBuf(DevBuf &&o) noexcept : p_(o.p_), count_(o.count_) { o.p_ = nullptr; o.count_ = 0; }
+    DevBuf(DevBuf &&o) noexcept : blk_(std::move(o.blk_)), p_(o.p_), count_(o.count_), own_(o.own_) { o.p_ = nullptr; o.count_ = 0; o.own_ = false; }
     DevBuf &operator=(DevBuf &&o) noexcept
     {
         if (this != &o) {
             reset();
+            blk_ = std::move(o.blk_);
             std::swap(p_, o.p_);
             std::swap(count_, o.count_);
+            std::swap(own_, o.own_);
         }
         return *this;
     }
     ~DevBuf() { reset(); }
     void reset()
     {
-        if (p_) (void)hipFree(p_);
+        if (p_ && own_) Tally::add(-(int64_t)bytes());
+        blk_.reset();
         p_ = nullptr;
         count_ = 0;
+        own_ = false;
     }
-    // a fresh allocation of count elements (at least one); the old one is freed first
+    // a fresh allocation of count elements (at least one); the old one is let go first
     int alloc(size_t count)
     {
         reset();
         if (count == 0) count = 1;
-        HIPCHECK(hipMalloc((void **)&p_, count * sizeof(T)));
+        T *p = nullptr;
+        HIPCHECK(hipMalloc((void **)&p, count * sizeof(T)));
+        blk_ = std::make_shared<Block>(p);
+        p_ = p;
         count_ = count;
+        own_ = true;
+        Tally::add((int64_t)bytes());
         return INSIDER_OK;
     }
     // at least count elements: a new allocation only when the current one is smaller (contents are not kept)
@@ -95,12 +120,31 @@ public:
         HIPCHECK(hipMemcpy(p_, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
         return INSIDER_OK;
     }
+    // the allocation of o, held jointly (nothing when o holds none); returns the bytes now shared
+    size_t share(const DevBuf &o)
+    {
+        reset();
+        blk_ = o.blk_;
+        p_ = o.p_;
+        count_ = o.count_;
+        return bytes();
+    }
+    size_t bytes() const { return p_ ? count_ * sizeof(T) : 0; }
     T *get() const { return p_; }
     operator T *() const { return p_; }
 
 private:
+    struct Block {
+        void *p;
+        explicit Block(void *q) : p(q) {}
+        Block(const Block &) = delete;
+        Block &operator=(const Block &) = delete;
+        ~Block() { if (p) (void)hipFree(p); }
+    };
+    std::shared_ptr<Block> blk_;
     T *p_ = nullptr;
     size_t count_ = 0;
+    bool own_ = false;                // allocated here (alloc), not joined (share)
 };
 
 // An owned stream or event, destroyed with its owner.
@@ -150,10 +194,29 @@ struct CovTables {   // per covariate, device
 };
 // continuous columns share one table: a single pseudo-level whose members are all samples, in 16-sample chunks
 
+// Host copies of the small inputs the mask-dependent stages read (stage_merged, stage_cont_factored): kept with the
+// mask-independent part, so that a re-mask runs the same stages without the caller's arrays.
+struct HostTables {
+    std::vector<int> lev0;            // c x n: 0-based level of every sample, covariate by covariate
+    std::vector<double> ctns;         // n x m column-major: the continuous covariates
+};
+
+// Fold ids of the resident matrix (insider_hip_set_folds): 0 = NA, 1..F = the fold an entry is held out in
+struct FoldIds {
+    DevBuf<uint8_t> id;               // layout of X: gene-major lines of pitch ldn, pad elements 0
+    int F = 0;
+};
+
 // The read-only DATA SET: everything insider_hip_create builds (X-derived lists, level sums, pair counts, chunk tables) and
 // the shape facts that describe it.  Shared by the handles of insider_hip_clone — each has its own workspace, streams and
 // options, so that several fits of one data set (tune()'s grid points) run on the GPU at the same time — and freed with the
 // last of them.
+// It has two parts.  The MASK-INDEPENDENT part depends on X and the covariates only: X, lev, members_all, lvl_ptr_all,
+// lvl_count_all, lvl_off_d, the chunk tables and paircnt of every CovTables, cont, Zc, ident_members, one_count, cont_pair,
+// cont_cnt, S, yy_all, host, the fold ids and the shape facts.  The MASK-DEPENDENT part is everything else.  A re-masked data set
+// (insider_hip_remask, insider_hip_remask_fold) holds the allocations of its source's mask-independent part jointly
+// (share_resident: DevBuf::share, nothing copied) and builds the mask-dependent part for its own masks with the stages
+// insider_hip_create_ex runs (build_masked).
 struct DataSet {
     int device = 0;
     int n_simd = 1024;                // SIMDs of the device (4 per CU)
@@ -197,6 +260,16 @@ struct DataSet {
     CovTables contm_lists;
     DevBuf<double> cont_cnt;          // [m] sum_r z_rk^2
     bool cont_merged = false;
+    // mask-independent: the pair "counts" of continuous column k (contm[k].paircnt holds the same allocation)
+    std::vector<DevBuf<double>> cont_pair;
+    std::shared_ptr<const HostTables> host;
+    // fold ids: set after creation (insider_hip_set_folds), read when a handle is derived; a derived data set keeps the ids
+    // it was derived under
+    mutable std::mutex fold_mu;
+    mutable std::shared_ptr<const FoldIds> folds;
+    std::shared_ptr<const FoldIds> get_folds() const { std::lock_guard<std::mutex> g(fold_mu); return folds; }
+    // device bytes of the DevBufs above: held jointly with the source data set / allocated by this one
+    size_t bytes_shared = 0, bytes_own = 0;
 
     // the row factors as blocks of the stacked factor: covariate b < c, then (m > 0) the continuous columns
     struct Block { int rows, off; };
@@ -1757,12 +1830,14 @@ int check_create_args(const CreateArgs &a, int device)
     return INSIDER_OK;
 }
 
-// 0-based level of every sample, covariate by covariate (c x n)
-std::vector<int> level_index(const CreateArgs &a)
+// the host copies the later stages read instead of the caller's arrays
+std::shared_ptr<const HostTables> host_tables(const CreateArgs &a)
 {
-    std::vector<int> lev0((size_t)a.c * a.n);
-    for (size_t e = 0; e < lev0.size(); ++e) lev0[e] = a.levels[e] - 1;
-    return lev0;
+    auto t = std::make_shared<HostTables>();
+    t->lev0.resize((size_t)a.c * a.n);
+    for (size_t e = 0; e < t->lev0.size(); ++e) t->lev0[e] = a.levels[e] - 1;
+    if (a.m > 0) t->ctns.assign(a.ctns, a.ctns + (size_t)a.m * a.n);
+    return t;
 }
 
 void describe(DataSet &d, const CreateArgs &a, int device)
@@ -1782,22 +1857,47 @@ void describe(DataSet &d, const CreateArgs &a, int device)
     d.SLcat = d.lvl_off[a.c];
     d.SL = d.SLcat + a.m;
     d.SLP = (int)round_up(d.SL, 2);
+    d.host = host_tables(a);
 }
 
-// X (gene-major lines of pitch ldn) and mask codes
+// ---- the mask-independent part -----------------------------------------------------------------------------------------------
+// X (gene-major lines of pitch ldn)
 int stage_matrix(DataSet &d, const CreateArgs &a, hipStream_t st)
 {
     const int64_t n = a.n, p = a.p;
     int rc;
-    if ((rc = d.X.alloc((size_t)p * d.ldn)) || (rc = d.codes.alloc((size_t)p * d.ldn))) return rc;
+    if ((rc = d.X.alloc((size_t)p * d.ldn))) return rc;
     HIPCHECK(hipMemsetAsync(d.X, 0, (size_t)p * d.ldn * sizeof(double), st));
     HIPCHECK(hipMemcpy2DAsync(d.X, d.ldn * sizeof(double), a.X, n * sizeof(double), n * sizeof(double), p, hipMemcpyHostToDevice,
                               st));
+    HIPCHECK(hipStreamSynchronize(st));
+    return INSIDER_OK;
+}
+
+// mask codes (layout of X) from the caller's two masks
+int codes_from_masks(DataSet &d, const uint8_t *M_train, const uint8_t *M_test, hipStream_t st)
+{
+    const int64_t n = d.n, p = d.p;
+    int rc;
+    if ((rc = d.codes.alloc((size_t)p * d.ldn))) return rc;
     DevBuf<uint8_t> mtr, mte;
     if ((rc = mtr.alloc((size_t)n * p)) || (rc = mte.alloc((size_t)n * p))) return rc;
-    HIPCHECK(hipMemcpyAsync(mtr, a.M_train, (size_t)n * p, hipMemcpyHostToDevice, st));
-    HIPCHECK(hipMemcpyAsync(mte, a.M_test, (size_t)n * p, hipMemcpyHostToDevice, st));
+    HIPCHECK(hipMemcpyAsync(mtr, M_train, (size_t)n * p, hipMemcpyHostToDevice, st));
+    HIPCHECK(hipMemcpyAsync(mte, M_test, (size_t)n * p, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_make_codes, dim3(cdiv(p * d.ldn, 256)), dim3(256), 0, st, mtr, mte, n, p, d.ldn, d.codes);
+    KCHECK();
+    HIPCHECK(hipStreamSynchronize(st));
+    return INSIDER_OK;
+}
+
+// mask codes of one fold from the resident fold ids: nothing is uploaded
+int codes_from_fold(DataSet &d, const FoldIds &f, int fold, hipStream_t st)
+{
+    int rc;
+    if ((rc = d.codes.alloc((size_t)d.p * d.ldn))) return rc;
+    const int blocks = (int)std::min<int64_t>(cdiv(d.p, 4), 8 * (int64_t)d.n_simd);
+    hipLaunchKernelGGL(k_fold_codes, dim3(blocks), dim3(256), 0, st, (const uint8_t *)f.id, (int)d.n, (int)d.p, (int)d.ldn, fold,
+                       d.codes);
     KCHECK();
     HIPCHECK(hipStreamSynchronize(st));
     return INSIDER_OK;
@@ -1808,7 +1908,7 @@ int stage_levels(DataSet &d, const CreateArgs &a)
 {
     const int64_t n = a.n;
     const int c = a.c;
-    const std::vector<int> lev0 = level_index(a);
+    const std::vector<int> &lev0 = d.host->lev0;
     std::vector<int> members((size_t)c * n), lvl_ptr((size_t)d.SLcat + c), lvl_count(d.SLcat);
     d.cov.resize(c);
     int rc;
@@ -1868,31 +1968,92 @@ int stage_continuous(DataSet &d, const CreateArgs &a)
     return INSIDER_OK;
 }
 
-// factor-independent statistics: per-gene sums of squares, per-level sums of X (all entries and train entries), entry counts
-int stage_sums(DataSet &d, const CreateArgs &a, hipStream_t st)
+// per-level sums of X over all entries
+int stage_all_sums(DataSet &d, hipStream_t st)
 {
-    const int64_t n = a.n, p = a.p;
-    const int c = a.c, m = a.m;
+    const int64_t n = d.n, p = d.p;
+    const int c = d.c, m = d.m;
     int rc;
-    if ((rc = d.S.alloc((size_t)p * d.SLP)) || (rc = d.yy_train.alloc((size_t)p)) || (rc = d.yy_all.alloc((size_t)p))) return rc;
+    if ((rc = d.S.alloc((size_t)p * d.SLP))) return rc;
     HIPCHECK(hipMemsetAsync(d.S, 0, (size_t)p * d.SLP * sizeof(double), st));
+    hipLaunchKernelGGL(k_level_sums, dim3(cdiv(p * d.SLcat, 256)), dim3(256), 0, st, (const double *)d.X, (const uint8_t *)nullptr,
+                       d.ldn, (int)p, (const int *)d.members_all, (const int *)d.lvl_ptr_all, (const int *)d.lvl_off_d, c, (int)n,
+                       d.SLcat, d.SLP, d.S);
+    if (m > 0)
+        hipLaunchKernelGGL(k_cont_sums, dim3(cdiv(p * m, 256)), dim3(256), 0, st, (const double *)d.X, d.ldn, (int)p,
+                           (const double *)d.Zc, m, (int)n, d.SLcat, d.SLP, d.S);
+    KCHECK();
+    return INSIDER_OK;
+}
+
+// the merged row update's tables exist for data sets of this shape (stage_merged)
+bool merged_shape(const DataSet &d) { return d.m <= 4 && (size_t)4 * (d.SLcat + GU_TILE) * sizeof(double) <= 64 * 1024; }
+
+// level-pair sample counts of the merged row update (insider_row_merged.hpp): they count samples, not entries
+int stage_pair_tables(DataSet &d)
+{
+    const int64_t n = d.n;
+    const int c = d.c, m = d.m;
+    if (!merged_shape(d)) return INSIDER_OK;
+    const std::vector<int> &lev0 = d.host->lev0;
+    const double *ctns = d.host->ctns.data();
+    int rc;
+    for (int i = 0; i < c; ++i) {
+        // samples per (level of covariate i, stacked level of another covariate): sum_{r in l} s_r = paircnt A
+        // (+ m columns sum_{r in l} z_rk: a continuous column is a stacked "level" with real-valued counts)
+        std::vector<double> pc((size_t)d.cov[i].L * d.SL, 0.0);
+        for (int64_t r = 0; r < n; ++r) {
+            const int l = lev0[(size_t)i * n + r];
+            for (int q = 0; q < c; ++q)
+                if (q != i) pc[(size_t)l * d.SL + d.lvl_off[q] + lev0[(size_t)q * n + r]] += 1.0;
+            for (int k = 0; k < m; ++k) pc[(size_t)l * d.SL + d.SLcat + k] += ctns[(size_t)k * n + r];
+        }
+        if ((rc = d.cov[i].paircnt.upload(pc))) return rc;
+    }
+    if (m == 0 || c > CF_MAXC) return INSIDER_OK;
+    // the continuous columns as one-level covariates (stage_cont_factored): their pair "counts" and |l| = sum_r z_rk^2
+    std::vector<double> zz((size_t)m * m, 0.0);
+    for (int k = 0; k < m; ++k)
+        for (int k2 = 0; k2 < m; ++k2) {
+            double acc = 0.0;
+            for (int64_t r = 0; r < n; ++r) acc += ctns[(size_t)k * n + r] * ctns[(size_t)k2 * n + r];
+            zz[(size_t)k * m + k2] = acc;
+        }
+    std::vector<double> cc(m);
+    d.cont_pair.resize(m);
+    for (int k = 0; k < m; ++k) {
+        std::vector<double> pc((size_t)d.SL, 0.0);
+        for (int64_t r = 0; r < n; ++r)
+            for (int q = 0; q < c; ++q) pc[d.lvl_off[q] + lev0[(size_t)q * n + r]] += ctns[(size_t)k * n + r];
+        for (int k2 = 0; k2 < m; ++k2) pc[d.SLcat + k2] = k2 == k ? 0.0 : zz[(size_t)k * m + k2];
+        if ((rc = d.cont_pair[k].upload(pc))) return rc;
+        cc[k] = zz[(size_t)k * m + k];
+    }
+    return d.cont_cnt.upload(cc);
+}
+
+// ---- the mask-dependent part: run from the device codes and the data set's own copies alone ------------------------------------
+// factor-independent statistics of the masks: per-gene sums of squares, per-level sums of X over the train entries, entry counts
+int stage_sums(DataSet &d, hipStream_t st)
+{
+    const int64_t n = d.n, p = d.p;
+    const int c = d.c;
+    int rc;
+    // (the kernel forms both sums of squares; a data set that holds its source's yy_all writes the second one to a scratch line)
+    DevBuf<double> yy_scratch;
+    const bool own_all = !d.yy_all;
+    if ((rc = d.yy_train.alloc((size_t)p)) || (rc = (own_all ? d.yy_all : yy_scratch).alloc((size_t)p))) return rc;
     DevBuf<unsigned long long> cnt;
     if ((rc = cnt.alloc(2))) return rc;
     HIPCHECK(hipMemsetAsync(cnt, 0, 2 * sizeof(unsigned long long), st));
     hipLaunchKernelGGL(k_line_sumsq, dim3(cdiv(p, 4)), dim3(256), 0, st, (const double *)d.X, (const uint8_t *)d.codes, d.ldn, (int)n,
-                       (int)p, d.yy_train, d.yy_all, cnt);
-    hipLaunchKernelGGL(k_level_sums, dim3(cdiv(p * d.SLcat, 256)), dim3(256), 0, st, (const double *)d.X, (const uint8_t *)nullptr,
-                       d.ldn, (int)p, (const int *)d.members_all, (const int *)d.lvl_ptr_all, (const int *)d.lvl_off_d, c, (int)n,
-                       d.SLcat, d.SLP, d.S);
+                       (int)p, d.yy_train, own_all ? d.yy_all.get() : yy_scratch.get(), cnt);
     // train-only sums for the merged masked row update / the factored column statistics (the categorical columns)
     if ((rc = d.Strain.alloc((size_t)p * d.SLP))) return rc;
     HIPCHECK(hipMemsetAsync(d.Strain, 0, (size_t)p * d.SLP * sizeof(double), st));
     hipLaunchKernelGGL(k_level_sums, dim3(cdiv(p * d.SLcat, 256)), dim3(256), 0, st, (const double *)d.X, (const uint8_t *)d.codes,
                        d.ldn, (int)p, (const int *)d.members_all, (const int *)d.lvl_ptr_all, (const int *)d.lvl_off_d, c, (int)n,
                        d.SLcat, d.SLP, d.Strain);
-    if (m > 0)
-        hipLaunchKernelGGL(k_cont_sums, dim3(cdiv(p * m, 256)), dim3(256), 0, st, (const double *)d.X, d.ldn, (int)p,
-                           (const double *)d.Zc, m, (int)n, d.SLcat, d.SLP, d.S);
     KCHECK();
     unsigned long long hc[2];
     HIPCHECK(hipMemcpyAsync(hc, cnt, sizeof(hc), hipMemcpyDeviceToHost, st));
@@ -1905,9 +2066,9 @@ int stage_sums(DataSet &d, const CreateArgs &a, hipStream_t st)
 
 // held-out lists of both sides (the masks never change: built once).  The row side is read from transposed copies
 // (sample-major lines of pitch ldp) that live only here.
-int stage_lists(DataSet &d, const CreateArgs &a, hipStream_t st)
+int stage_lists(DataSet &d, hipStream_t st)
 {
-    const int64_t n = a.n, p = a.p;
+    const int64_t n = d.n, p = d.p;
     int rc;
     DevBuf<double> Xt;
     DevBuf<uint8_t> codes_t;
@@ -1961,12 +2122,12 @@ constexpr uint32_t SEG = 1024;   // list entries per weighted-SYRK work item (mu
 // level and the level-pair sample counts (insider_row_merged.hpp).
 // (k_gene_u keeps a gene's SLcat look-up values per wave in LDS: beyond ~1500 stacked levels the per-sample path stays)
 // (with continuous covariates, m <= 4: the same tables serve the pair-count column statistics, ColFacArgs::zt)
-int stage_merged(DataSet &d, const CreateArgs &a, hipStream_t st)
+// (the level-pair sample counts do not depend on the masks: stage_pair_tables)
+int stage_merged(DataSet &d, hipStream_t st)
 {
-    const int64_t n = a.n, p = a.p;
-    const int c = a.c, m = a.m;
-    if (!(m <= 4 && (size_t)4 * (d.SLcat + GU_TILE) * sizeof(double) <= 64 * 1024)) return INSIDER_OK;
-    const std::vector<int> lev0 = level_index(a);
+    const int64_t n = d.n, p = d.p;
+    const int c = d.c;
+    if (!merged_shape(d)) return INSIDER_OK;
     int rc;
     for (int i = 0; i < c; ++i) {
         CovTables &ct = d.cov[i];
@@ -2013,16 +2174,6 @@ int stage_merged(DataSet &d, const CreateArgs &a, hipStream_t st)
             (rc = ct.item_begin.upload(ib, ib.size() + 1)) || (rc = ct.item_end.upload(ie, ie.size() + 1)) ||
             (rc = ct.lvl_item_ptr.upload(lip)))
             return rc;
-        // samples per (level of covariate i, stacked level of another covariate): sum_{r in l} s_r = paircnt A
-        // (+ m columns sum_{r in l} z_rk: a continuous column is a stacked "level" with real-valued counts)
-        std::vector<double> pc((size_t)L * d.SL, 0.0);
-        for (int64_t r = 0; r < n; ++r) {
-            const int l = lev0[(size_t)i * n + r];
-            for (int q = 0; q < c; ++q)
-                if (q != i) pc[(size_t)l * d.SL + d.lvl_off[q] + lev0[(size_t)q * n + r]] += 1.0;
-            for (int k = 0; k < m; ++k) pc[(size_t)l * d.SL + d.SLcat + k] += a.ctns[(size_t)k * n + r];
-        }
-        if ((rc = ct.paircnt.upload(pc))) return rc;
     }
     d.merged = true;
     if ((rc = d.Sheld.alloc((size_t)p * d.SLP))) return rc;
@@ -2034,14 +2185,14 @@ int stage_merged(DataSet &d, const CreateArgs &a, hipStream_t st)
 
 // factored column statistics: covariates by decreasing level count, the planes of the later ones; the dense pair counts
 // and half counts of the pair-count form when they are small enough
-int stage_factored(DataSet &d, const CreateArgs &a, hipStream_t st)
+int stage_factored(DataSet &d, hipStream_t st)
 {
-    const int64_t n = a.n, p = a.p;
-    const int c = a.c;
+    const int64_t n = d.n, p = d.p;
+    const int c = d.c;
     if (!d.merged || c > CF_MAXC) return INSIDER_OK;
     std::vector<int> ord(c);
     for (int i = 0; i < c; ++i) ord[i] = i;
-    std::stable_sort(ord.begin(), ord.end(), [&](int x, int y) { return a.n_levels[x] > a.n_levels[y]; });
+    std::stable_sort(ord.begin(), ord.end(), [&](int x, int y) { return d.n_levels[x] > d.n_levels[y]; });
     ColFacArgs &cf = d.cf;
     cf.p = (int)p;
     cf.c = c;
@@ -2051,13 +2202,13 @@ int stage_factored(DataSet &d, const CreateArgs &a, hipStream_t st)
         d.cf_pos[o] = t;
         cf.grp[t] = d.cov[o].grp;
         cf.slev[t] = d.cov[o].slev;
-        cf.L[t] = a.n_levels[o];
+        cf.L[t] = d.n_levels[o];
         cf.off[t] = d.lvl_off[o];
         cf.nlater[t] = c - 1 - t;
         for (int k = t + 1; k < c; ++k) cf.later_plane[t][k - t - 1] = ord[k] < o ? ord[k] : ord[k] - 1;
     }
     cf.tab_skip_lo = d.lvl_off[ord[0]];
-    cf.tab_skip_n = a.n_levels[ord[0]];
+    cf.tab_skip_n = d.n_levels[ord[0]];
     cf.tab_rows = d.SLcat - cf.tab_skip_n;
     // pair-count form: the dense per-gene count tables (one byte per cell), when they are small enough
     cf.nsteps = (cf.tab_rows + 3) / 4;
@@ -2100,7 +2251,7 @@ int stage_factored(DataSet &d, const CreateArgs &a, hipStream_t st)
         d.cf_pair_ok = fits;
     }
     cf.zt = nullptr;
-    cf.m = a.m;
+    cf.m = d.m;
     cf.SLcat = d.SLcat;
     for (int t = 0; t < c; ++t) cf.pos_cov[t] = ord[t];
     return INSIDER_OK;
@@ -2108,10 +2259,10 @@ int stage_factored(DataSet &d, const CreateArgs &a, hipStream_t st)
 
 // continuous covariates on the pair-count form: the real-valued count table, and the continuous columns as one-level
 // covariates of the merged row update
-int stage_cont_factored(DataSet &d, const CreateArgs &a, hipStream_t st)
+int stage_cont_factored(DataSet &d, hipStream_t st)
 {
-    const int64_t n = a.n, p = a.p;
-    const int c = a.c, m = a.m;
+    const int64_t n = d.n, p = d.p;
+    const int c = d.c, m = d.m;
     // The merged row update with continuous columns takes u_j from k_gene_u_cnt ALONE (only it adds the term of the
     // real-valued counts, ColFacArgs::zt; k_gene_u reads the categorical columns of V only): every covariate's launch
     // of it must fit its per-wave LDS record — V row [SL] | out [LP] | GU_BATCH x 64 partial sums, four waves per block
@@ -2162,15 +2313,6 @@ int stage_cont_factored(DataSet &d, const CreateArgs &a, hipStream_t st)
         (rc = lists.item_end.upload(ie, ie.size() + 1)) || (rc = lists.lvl_item_ptr.upload(std::vector<int>{0, (int)ib.size()})))
         return rc;
     d.max_items = std::max(d.max_items, (int)ib.size());
-    std::vector<double> zz((size_t)m * m, 0.0);
-    for (int k = 0; k < m; ++k)
-        for (int k2 = 0; k2 < m; ++k2) {
-            double acc = 0.0;
-            for (int64_t r = 0; r < n; ++r) acc += a.ctns[(size_t)k * n + r] * a.ctns[(size_t)k2 * n + r];
-            zz[(size_t)k * m + k2] = acc;
-        }
-    const std::vector<int> lev0 = level_index(a);
-    std::vector<double> cc(m);
     d.contm.resize(m);
     for (int k = 0; k < m; ++k) {
         CovTables &ct = d.contm[k];
@@ -2182,16 +2324,85 @@ int stage_cont_factored(DataSet &d, const CreateArgs &a, hipStream_t st)
         hipLaunchKernelGGL(k_cont_weights, dim3(cdiv(p, 256)), dim3(256), 0, st, (const double *)d.cf_zt, cf.zt_stride, cf.zt_off[c], k,
                            (int)p, ct.wl_w);
         KCHECK();
-        std::vector<double> pc((size_t)d.SL, 0.0);
-        for (int64_t r = 0; r < n; ++r)
-            for (int q = 0; q < c; ++q) pc[d.lvl_off[q] + lev0[(size_t)q * n + r]] += a.ctns[(size_t)k * n + r];
-        for (int k2 = 0; k2 < m; ++k2) pc[d.SLcat + k2] = k2 == k ? 0.0 : zz[(size_t)k * m + k2];
-        if ((rc = ct.paircnt.upload(pc))) return rc;
-        cc[k] = zz[(size_t)k * m + k];
+        ct.paircnt.share(d.cont_pair[k]);   // (mask-independent: stage_pair_tables)
     }
-    if ((rc = d.cont_cnt.upload(cc))) return rc;
     HIPCHECK(hipStreamSynchronize(st));
     d.cont_merged = true;
+    return INSIDER_OK;
+}
+
+// everything that depends on the masks, from the codes on the device: insider_hip_create_ex and the re-masks run this
+int build_masked(DataSet &d, hipStream_t st)
+{
+    int rc;
+    if ((rc = stage_sums(d, st)) || (rc = stage_lists(d, st)) || (rc = stage_merged(d, st)) || (rc = stage_factored(d, st)) ||
+        (rc = stage_cont_factored(d, st)))
+        return rc;
+    return INSIDER_OK;
+}
+
+// d holds the mask-independent part of src jointly: the shape facts are copied, every device array is shared
+void share_resident(DataSet &d, const DataSet &s)
+{
+    d.device = s.device; d.n_simd = s.n_simd;
+    d.n = s.n; d.p = s.p; d.ldn = s.ldn; d.ldp = s.ldp;
+    d.c = s.c; d.SL = s.SL; d.SLP = s.SLP; d.m = s.m; d.SLcat = s.SLcat;
+    d.n_levels = s.n_levels; d.lvl_off = s.lvl_off;
+    d.max_chunks = s.max_chunks; d.max_L = s.max_L;
+    d.host = s.host;
+    d.folds = s.get_folds();
+    size_t b = 0;
+    b += d.X.share(s.X) + d.lev.share(s.lev) + d.lvl_off_d.share(s.lvl_off_d) + d.members_all.share(s.members_all) +
+         d.lvl_ptr_all.share(s.lvl_ptr_all) + d.lvl_count_all.share(s.lvl_count_all) + d.Zc.share(s.Zc) +
+         d.one_count.share(s.one_count) + d.ident_members.share(s.ident_members) + d.S.share(s.S) + d.yy_all.share(s.yy_all) +
+         d.cont_cnt.share(s.cont_cnt);
+    auto chunks = [&b](CovTables &o, const CovTables &i) {
+        o.L = i.L;
+        o.nchunks = i.nchunks;
+        b += o.chunk_level.share(i.chunk_level) + o.chunk_begin.share(i.chunk_begin) + o.chunk_end.share(i.chunk_end) +
+             o.lvl_chunk_ptr.share(i.lvl_chunk_ptr) + o.paircnt.share(i.paircnt);
+    };
+    d.cov.resize(s.cov.size());
+    for (size_t i = 0; i < s.cov.size(); ++i) chunks(d.cov[i], s.cov[i]);
+    chunks(d.cont, s.cont);
+    d.cont_pair.resize(s.cont_pair.size());
+    for (size_t k = 0; k < s.cont_pair.size(); ++k) b += d.cont_pair[k].share(s.cont_pair[k]);
+    if (d.folds) b += d.folds->id.bytes();
+    d.bytes_shared = b;
+}
+
+// A handle with src's options and shard settings and a workspace, streams and diagnostics of its own (insider_hip_clone)
+int handle_like(const insider_hip_handle *src, std::unique_ptr<insider_hip_handle> &h)
+{
+    h = std::make_unique<insider_hip_handle>();
+    h->opt = src->opt;
+    h->gene_offset = src->gene_offset;
+    h->rank = src->rank;
+    h->world = src->world;
+    h->allreduce = src->allreduce;
+    h->allreduce_user = src->allreduce_user;
+    return h->st.create(stream_events(src->ds->c, src->ds->m));
+}
+
+// A handle on a new data set over src's resident X whose codes `make_codes` writes
+template <typename F>
+int derive(insider_hip_handle *src, insider_hip_handle **out, F make_codes)
+{
+    if (src->world > 1) return fail(INSIDER_ERR_UNSUPPORTED, "a gene-sharded handle cannot be re-masked");
+    HIPCHECK(hipSetDevice(src->ds->device));
+    // (d before h: on an error the handle drains its streams before the data set's buffers go)
+    auto d = std::make_shared<DataSet>();
+    std::unique_ptr<insider_hip_handle> h;
+    int rc;
+    if ((rc = handle_like(src, h))) return rc;
+    share_resident(*d, *src->ds);
+    {
+        Tally own;
+        if ((rc = make_codes(*d, (hipStream_t)h->st.stream)) || (rc = build_masked(*d, h->st.stream))) return rc;
+        d->bytes_own = (size_t)own.bytes;
+    }
+    h->ds = std::move(d);
+    *out = h.release();
     return INSIDER_OK;
 }
 }  // namespace
@@ -2208,17 +2419,51 @@ int insider_hip_clone(insider_hip_handle *src, insider_hip_handle **out)
     HIPCHECK(hipSetDevice(src->ds->device));
     // the data set, the options and the shard settings; a workspace, streams, diagnostics of its own (a sharded clone joins
     // its own communicator: insider_hip_comm_init)
-    auto h = std::make_unique<insider_hip_handle>();
+    std::unique_ptr<insider_hip_handle> h;
+    if (int rc = handle_like(src, h)) return rc;
     h->ds = src->ds;
-    h->opt = src->opt;
-    h->gene_offset = src->gene_offset;
-    h->rank = src->rank;
-    h->world = src->world;
-    h->allreduce = src->allreduce;
-    h->allreduce_user = src->allreduce_user;
-    if (int rc = h->st.create(stream_events(h->ds->c, h->ds->m))) return rc;
     *out = h.release();
     return INSIDER_OK;
+}
+
+int insider_hip_remask(insider_hip_handle *src, const uint8_t *M_train, const uint8_t *M_test, insider_hip_handle **out)
+{
+    if (!out) return fail(INSIDER_ERR_ARG, "out is null");
+    *out = nullptr;
+    if (!src || !src->ds) return fail(INSIDER_ERR_ARG, "null handle");
+    if (!M_train || !M_test) return fail(INSIDER_ERR_ARG, "null mask");
+    return derive(src, out, [&](DataSet &d, hipStream_t st) { return codes_from_masks(d, M_train, M_test, st); });
+}
+
+int insider_hip_set_folds(insider_hip_handle *h, const uint8_t *fold_id, int F)
+{
+    if (!h || !h->ds || !fold_id) return fail(INSIDER_ERR_ARG, "null");
+    if (F < 1 || F > 255) return fail(INSIDER_ERR_ARG, "F must be in 1..255");
+    const DataSet &d = *h->ds;
+    const size_t np = (size_t)d.n * (size_t)d.p;
+    for (size_t e = 0; e < np; ++e)
+        if (fold_id[e] > F) return fail(INSIDER_ERR_ARG, "fold ids must be within 0..F");
+    HIPCHECK(hipSetDevice(d.device));
+    auto f = std::make_shared<FoldIds>();
+    f->F = F;
+    if (int rc = f->id.alloc((size_t)d.p * d.ldn)) return rc;
+    HIPCHECK(hipMemset(f->id, 0, (size_t)d.p * d.ldn));
+    HIPCHECK(hipMemcpy2D(f->id, (size_t)d.ldn, fold_id, (size_t)d.n, (size_t)d.n, (size_t)d.p, hipMemcpyHostToDevice));
+    std::lock_guard<std::mutex> g(d.fold_mu);
+    d.folds = std::move(f);
+    return INSIDER_OK;
+}
+
+int insider_hip_remask_fold(insider_hip_handle *src, int fold, insider_hip_handle **out)
+{
+    if (!out) return fail(INSIDER_ERR_ARG, "out is null");
+    *out = nullptr;
+    if (!src || !src->ds) return fail(INSIDER_ERR_ARG, "null handle");
+    if (src->world > 1) return fail(INSIDER_ERR_UNSUPPORTED, "a gene-sharded handle cannot be re-masked");
+    const std::shared_ptr<const FoldIds> f = src->ds->get_folds();
+    if (!f) return fail(INSIDER_ERR_ARG, "no fold ids set: insider_hip_set_folds");
+    if (fold < 1 || fold > f->F) return fail(INSIDER_ERR_ARG, "fold must be in 1..F");
+    return derive(src, out, [&](DataSet &d, hipStream_t st) { return codes_from_fold(d, *f, fold, st); });
 }
 
 int insider_hip_create(const double *X, int64_t n, int64_t p, const int32_t *levels, int c, const int32_t *n_levels,
@@ -2244,10 +2489,14 @@ int insider_hip_create_ex(const double *X, int64_t n, int64_t p, const int32_t *
     describe(*d, a, device);
     if ((rc = h->st.create(stream_events(c, m)))) return rc;
     const hipStream_t st = h->st.stream;
-    if ((rc = stage_matrix(*d, a, st)) || (rc = stage_levels(*d, a)) || (rc = stage_continuous(*d, a)) ||
-        (rc = stage_sums(*d, a, st)) || (rc = stage_lists(*d, a, st)) || (rc = stage_merged(*d, a, st)) ||
-        (rc = stage_factored(*d, a, st)) || (rc = stage_cont_factored(*d, a, st)))
-        return rc;
+    {
+        Tally own;
+        if ((rc = stage_matrix(*d, a, st)) || (rc = stage_levels(*d, a)) || (rc = stage_continuous(*d, a)) ||
+            (rc = stage_all_sums(*d, st)) || (rc = stage_pair_tables(*d)) || (rc = codes_from_masks(*d, M_train, M_test, st)) ||
+            (rc = build_masked(*d, st)))
+            return rc;
+        d->bytes_own = (size_t)own.bytes;
+    }
     h->ds = std::move(d);
     *out = h.release();
     return INSIDER_OK;
@@ -2954,6 +3203,8 @@ int insider_hip_get_info(insider_hip_handle *h, const char *name, double *out)
     else if (s == "row_merged") *out = use_merged(h, 1) ? 1.0 : 0.0;
     else if (s == "col_entries") *out = (double)h->ds->col_entries;      // padded held-out list entries, column side
     else if (s == "row_entries") *out = (double)h->ds->row_entries;
+    else if (s == "data_bytes_shared") *out = (double)h->ds->bytes_shared;   // device bytes of the data set held jointly with its source (0: a created one) ...
+    else if (s == "data_bytes_own") *out = (double)h->ds->bytes_own;         // ... and allocated by the data set itself
     else if (s == "stat_doubles") *out = NB ? NB * (NB + 1) / 2 * 256.0 : 0.0;
     else if (s == "kp") *out = h->ws.KP;
     else if (s == "pair_count_bytes_per_gene") *out = h->ds->cf_pair_ok ? h->ds->cf.cnt_stride : 0.0;

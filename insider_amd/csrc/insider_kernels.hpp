@@ -1613,6 +1613,43 @@ __global__ void k_make_codes(const uint8_t *__restrict__ mtr, const uint8_t *__r
     codes[t] = cd;
 }
 
+// Mask codes of one fold from the resident fold ids (same layout as the codes: lines of pitch `pitch`, a multiple of CHUNK;
+// id 0 = NA, 1..F = the fold the entry is held out in): id == fold -> CODE_TEST, another id >= 1 -> CODE_TRAIN, 0 -> NA; pad
+// elements CODE_TRAIN as in k_make_codes.  A byte stream: one wave per line, 16 bytes per lane and access, the line's base
+// addresses formed once and 32-bit offsets inside it; the four ids of a word are classified at once.
+__global__ void __launch_bounds__(256) k_fold_codes(const uint8_t *__restrict__ ids, int n, int p, int pitch, int fold,
+                                                    uint8_t *__restrict__ codes)
+{
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const uint32_t fw = (uint32_t)fold * 0x01010101u;
+    const int groups = pitch >> 4;
+    for (int j = blockIdx.x * 4 + w; j < p; j += gridDim.x * 4) {
+        const uint4 *src = reinterpret_cast<const uint4 *>(ids + (size_t)j * pitch);
+        uint4 *dst = reinterpret_cast<uint4 *>(codes + (size_t)j * pitch);
+        for (int g = lane; g < groups; g += WAVE) {
+            const uint4 v = src[g];
+            uint32_t in[4] = {v.x, v.y, v.z, v.w}, o[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                // per byte: 1 where the byte of x is non-zero
+                const uint32_t x = in[q], y = in[q] ^ fw;
+                const uint32_t nz = ((((x & 0x7f7f7f7fu) + 0x7f7f7f7fu) | x) >> 7) & 0x01010101u;
+                const uint32_t ne = ((((y & 0x7f7f7f7fu) + 0x7f7f7f7fu) | y) >> 7) & 0x01010101u;
+                const uint32_t eq = ne ^ 0x01010101u;          // id == fold (fold >= 1: never an NA byte)
+                o[q] = (nz & ne) * CODE_TRAIN | eq * CODE_TEST;
+                // pad elements (index >= n) of the line's last groups
+                const int i0 = g * 16 + q * 4;
+                if (i0 + 4 > n) {
+                    const int keep = i0 < n ? n - i0 : 0;      // bytes of this word inside the line
+                    const uint32_t m = keep ? (0xffffffffu >> (8 * (4 - keep))) : 0u;
+                    o[q] = (o[q] & m) | ((CODE_TRAIN * 0x01010101u) & ~m);
+                }
+            }
+            dst[g] = make_uint4(o[0], o[1], o[2], o[3]);
+        }
+    }
+}
+
 // out[c][r] = in[r][c] for an (rows x cols) line-major matrix with pitches; pads keep `padval`
 template <typename T>
 __global__ void __launch_bounds__(256) k_transpose(const T *__restrict__ in, int64_t rows, int64_t cols, int64_t ipitch,

@@ -4,6 +4,7 @@
     python -m insider_amd.fit --x X.npy --levels L.npy [--train-mask M.npy --test-mask T.npy] [--ctns Z.npy]
         --rank K --lambda 5 --alpha 0.4 [--partition 0|1] [--max-iter N] [--out DIR] [--out-format npy|flat]
     ... --tune --ranks 10 12 14 --lambdas 1 3 5 --alphas 0.2 0.4   # tune()'s rank sweep + lambda x alpha grid
+    ... --tune --folds 5 ...                    # k-fold cross-validated tune(): mean / pooled / per-fold RMSE per grid point
     ... --interaction 1 2 --interaction-glm 1   # then glm_interaction() on the device for covariate column 1 (0-based)
     ... --variance-decomposition                # then the per-gene variance decomposition on the device
 
@@ -49,6 +50,9 @@ def parse(argv=None):
     ap.add_argument("--warm-start", action="store_true",
                     help="--tune: start every (lambda, alpha) grid point from its nearest finished neighbour's factors "
                          "(opt-in; the reference draws fresh inits per point, R/insider.R:152-161)")
+    ap.add_argument("--folds", type=int, default=None, metavar="K",
+                    help="--tune: K-fold cross-validation (every grid point fitted once per fold on re-masks of the one "
+                         "resident matrix); tune.json gains the per-fold tables, tune_folds.csv holds them")
     ap.add_argument("--split-ratio", type=float, default=0.1)
     ap.add_argument("--out", default="insider_fit_out")
     ap.add_argument("--out-format", choices=("npy", "flat"), default=None)
@@ -64,6 +68,10 @@ def parse(argv=None):
         ap.error("give --flat DIR or --x and --levels")
     if not a.tune and (a.rank is None or a.lam is None or a.alpha is None):
         ap.error("a fit needs --rank, --lambda and --alpha (or use --tune)")
+    if a.folds is not None and not a.tune:
+        ap.error("--folds goes with --tune")
+    if a.folds is not None and a.warm_start:
+        ap.error("--folds and --warm-start exclude each other")
     return a
 
 
@@ -96,15 +104,27 @@ def main(argv=None):
     if a.tune:
         # the caller-level path: insider() draws its own hold-out (R/utils.R:78-117) unless masks were given
         obj = api.insider(np.where(na, np.nan, X), lev, ctns_confounder=Z, split_ratio=a.split_ratio, global_tol=a.global_tol,
-                          sub_tol=a.sub_tol, tuning_iter=a.tuning_iter, max_iter=a.max_iter, device=a.device, seed=a.seed)
-        if tr is not None and te is not None:
+                          sub_tol=a.sub_tol, tuning_iter=a.tuning_iter, max_iter=a.max_iter, device=a.device, seed=a.seed,
+                          folds=a.folds)
+        if tr is not None and te is not None and a.folds is None:
             obj["train_indicator"] = np.asfortranarray(np.asarray(tr) != 0, dtype=np.uint8)
             obj["test_indicator"] = np.asfortranarray(np.asarray(te) != 0, dtype=np.uint8)
         res = api.tune(obj, latent_dimension=np.array(a.ranks if a.ranks else [a.rank]),
                        lambda_=a.lambdas if a.lambdas else (a.lam if a.lam is not None else 0.1),
                        alpha=a.alphas if a.alphas else (a.alpha if a.alpha is not None else 0.0), out_dir=None,
-                       rng=np.random.default_rng(a.seed), warm_start=a.warm_start)
+                       rng=np.random.default_rng(a.seed), warm_start=a.warm_start, folds=True if a.folds else None)
         os.makedirs(a.out, exist_ok=True)
+        if a.folds:
+            # the per-fold table next to tune.json: one row per fitted point (the rank sweep first) — latent rank, lambda,
+            # alpha (NaN in the rank sweep's rows: tune() fixes them there), then the F per-fold test RMSEs
+            blocks = []
+            if res["rank_tuning"] is not None:
+                k_col = res["rank_tuning"][:, :1]
+                blocks.append(np.column_stack([k_col, np.full((len(k_col), 2), np.nan), res["rank_tuning_folds"]]))
+            if res["reg_tuning"] is not None:
+                g2 = res["reg_tuning"][:, :2]
+                blocks.append(np.column_stack([np.full(len(g2), float(res["latent_rank"])), g2, res["reg_tuning_folds"]]))
+            np.savetxt(os.path.join(a.out, "tune_folds.csv"), np.vstack(blocks), delimiter=",")
         out = {k: (v.tolist() if isinstance(v, np.ndarray) else v) for k, v in res.items()}
         with open(os.path.join(a.out, "tune.json"), "w") as f:
             json.dump(out, f, indent=1)
