@@ -157,7 +157,9 @@ int insider_hip_comm_init(insider_hip_handle *h, const void *unique_id, int rank
  * in four rotations from LDS, resident blocks whose waves draw genes by ticket; 0 = the 16x16x4 form; same sums to rounding),
  * "mm_fast" (1, default = the streaming products of the row phase [V = C A', S A, U'C, S'C: from 16384 rows on] stage their small
  * operand in LDS once per block and read the tall one in 16-byte pieces / several column tiles per wave; 0 = round 4's kernels;
- * same sums, the row products in another order), "cd_pairs" (1, default = the register-resident sweep kernel [K <= 30] is routed through its blocks of TWO
+ * same sums, the row products in another order), "mm_tiles" (0, default = a wave of k_mm_rows2 takes one tile of 16 rows until
+ * the grid holds two waves per SIMD, then as many as keep it there; t >= 1 = t tiles per wave, in S A and in V = C A'; a tile's sums
+ * do not depend on the wave that takes it: same bits), "cd_pairs" (1, default = the register-resident sweep kernel [K <= 30] is routed through its blocks of TWO
  * coordinate steps wherever two consecutive coordinates of a sweep's order share a coordinate slot: a third fewer computed jumps,
  * the same steps in the same order — bit-identical iterates; 0 = one step per block), "cd_pass1" / "cd_pass_ratio" / "cd_cold_iters" (multi-pass column solves in the first
  * cd_cold_iters outer iterations of a call [default 3]: the register-resident sweep kernel stops at sweep cd_pass1 [64; 0 = one
@@ -379,6 +381,9 @@ int insider_hip_get_profile(insider_hip_handle *h, double *out12);
  * counts; MAXS = 8 with real-valued counts is never launched), "col_stats_tickets" (the ticket counters k_col_paircnt4 drew
  * genes from: 1 or 16; 0 for the other kernels), "col_stats_blocks" (k_col_paircnt4's grid size, 0 for the other kernels: its
  * blocks walk the genes in groups of four when 4 x blocks < p),
+ * "col_q_kernel" (the kernel the last Q = S A or S^held A product ran: 0 = none yet, 1 k_mm_rows<NB>, 2 k_mm_rows2<NB>),
+ * "mm_rows2_tiles" (the tiles of 16 rows per wave of the last k_mm_rows2 launch, for S A or for V = C A'; 0 = none yet),
+ * "n_simd" (SIMDs of the handle's device, 4 per compute unit),
  * "vd_path" (the form of k_vd_stats the last insider_hip_variance_decomposition() ran: 1 = level tables in LDS, 2 = read from
  * global memory; 0 = none yet),
  * "row_kernels" (a bit mask of the row-phase kernel forms the last optimize() / optimize_row() launched, reset at the start of

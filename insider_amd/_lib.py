@@ -38,6 +38,8 @@ COL_SOLVERS = ("none", "ridge_reg", "ridge", "cd_reg", "cd_reg3", "cd_cols16", "
 # insider_hip_get_info("col_stats_kernel"): the column-side statistics kernel behind each code (include/insider_hip.h)
 COL_STATS_KERNELS = ("none", "list", "list4", "factored", "paircnt", "paircnt_zt", "paircnt4_ms4", "paircnt4_ms8",
                      "paircnt4_ms4_zt")
+# insider_hip_get_info("col_q_kernel"): the kernel of the last Q = S A product behind each code (include/insider_hip.h)
+COL_Q_KERNELS = ("none", "mm_rows", "mm_rows2")
 # insider_hip_get_info("row_kernels"): the row-phase kernel form behind each bit, bit 0 first (include/insider_hip.h)
 ROW_KERNELS = ("wgemm4", "wgemm5", "wgemm6", "wgemm7", "wgemm_chunks", "wsyrk", "gram_side",
                "gene_u_cnt", "gene_u", "gene_uc",

@@ -373,6 +373,7 @@ struct Options {
     int wg_waves = 1024;              // "row_gemm_waves": waves the GEMM is cut into (sets the number of gene slabs)
     int row_fused = 1;                // "row_fused": level records' tail + equations + solve of the merged update in one launch
     int mm_fast = 1;                  // "mm_fast": the small dense products on k_mm_rows2 / k_mm_reduce2 (default; 2: two column tiles per wave in the reductions)
+    int mm_tiles = 0;                 // "mm_tiles": tiles of 16 rows a wave of k_mm_rows2 takes (0, default = mm_tiles_per_wave()'s rule)
     int col_mfma4 = 1;                // "col_mfma4": pair-count statistics with the second product on v_mfma_f64_4x4x4 (k_col_paircnt4; default)
     int cd_pairs = 1;                 // "cd_pairs": route the sweeps through the kernel's blocks of two coordinate steps (default)
     int list_fine = 1;                // "list_fine": 1 (default) = k_list_stats4 (4x4x4 matrix instruction) where it applies, 0 = k_list_stats
@@ -429,6 +430,9 @@ struct insider_hip_handle {
     // of the last column-side statistics launch (launch_col_stats): the kernel that formed them (ColStatsKernel), and for
     // k_col_paircnt4 the ticket counters it drew from and its grid size (0 for the other kernels)
     int col_stats_kernel = 0, col_stats_tickets = 0, col_stats_blocks = 0;
+    // of the last Q = S A / Qheld = S^held A product (launch_mm_rows_kp): 1 = k_mm_rows, 2 = k_mm_rows2; and tiles_per_wave of the
+    // last k_mm_rows2 launch from either site (launch_mm_rows_kp, launch_gene_v)
+    int col_q_kernel = 0, mm_rows2_tiles = 0;
     // of the last optimize() / optimize_row(): one bit per row-phase kernel form it launched (RowKernel)
     uint64_t row_kernels = 0;
     // the form the last variance decomposition ran (1 = tables in LDS, 2 = from global)
@@ -650,7 +654,12 @@ int launch_list_stats(insider_hip_handle *h, bool cols, int nseg, const double *
 
 // ---- the small dense products on MFMA (insider_mm.hpp) -------------------------------------------------------------------
 // k_mm_rows2: tiles of 16 rows one wave takes — one until the grid fills every SIMD twice, then as many as keep it at that
-int mm_tiles_per_wave(const insider_hip_handle *h, int tiles) { return std::max(1, tiles / (2 * h->ds->n_simd)); }
+// (option "mm_tiles" >= 1: that many)
+int mm_tiles_per_wave(const insider_hip_handle *h, int tiles)
+{
+    if (h->opt.mm_tiles >= 1) return h->opt.mm_tiles;
+    return std::max(1, tiles / (2 * h->ds->n_simd));
+}
 
 // out[M x KP] = X[M x Kd] W[Kd x KP]   (W row-major with pitch KP)
 bool mm_rows2_fits(const insider_hip_handle *h, int64_t ldx, int M, int Kd)
@@ -670,6 +679,8 @@ int launch_mm_rows_kp(insider_hip_handle *h, const double *X, int64_t ldx, int M
                                h->ws.KP, h->ws.KP, out, (int64_t)h->ws.KP, h->ws.KP, tpw);
         });
         KCHECK();
+        h->col_q_kernel = 2;
+        h->mm_rows2_tiles = tpw;
         return INSIDER_OK;
     }
     NB_DISPATCH(h->ws.NB, {
@@ -678,6 +689,7 @@ int launch_mm_rows_kp(insider_hip_handle *h, const double *X, int64_t ldx, int M
                            h->ws.KP, h->ws.KP, out, (int64_t)h->ws.KP, h->ws.KP);
     });
     KCHECK();
+    h->col_q_kernel = 1;
     return INSIDER_OK;
 }
 
@@ -1350,6 +1362,7 @@ int launch_gene_v(insider_hip_handle *h, int q_begin, int q_end)
 #undef GV2_LAUNCH
         KCHECK();
         row_mark(h, RK_MM_ROWS2);
+        h->mm_rows2_tiles = tpw;
         return INSIDER_OK;
     }
 #define GV_LAUNCH(NT_)                                                                                                        \
@@ -2569,6 +2582,7 @@ int insider_hip_set_option(insider_hip_handle *h, const char *name, double value
     else if (s == "cd_pass_ratio") h->opt.cd_pass_ratio = (int)value;   // each further pass stops at ratio x the previous limit
     else if (s == "list_fine") h->opt.list_fine = (int)value;       // 1 (default) = per-entry statistics on v_mfma_f64_4x4x4 for 16 <= K <= 31, 0 = on 16x16x4
     else if (s == "mm_fast") h->opt.mm_fast = (int)value;             // 0 = k_mm_rows / k_mm_reduce as in round 4
+    else if (s == "mm_tiles") h->opt.mm_tiles = value < 1 ? 0 : (int)value;   // tiles of 16 rows per wave of k_mm_rows2 (0, default = as many as keep the grid at two waves per SIMD)
     else if (s == "col_mfma4") h->opt.col_mfma4 = (int)value;         // 1 = k_col_paircnt4 (K <= 31, factor rows fit LDS), 0 = k_col_paircnt
     else if (s == "cd_pairs") h->opt.cd_pairs = (int)value;           // 1 (default) = sweeps routed through the blocks of two coordinate steps (K <= 30; same iterates), 0 = one step per block
     else if (s == "resid_stage_mb") h->opt.resid_stage_mb = value;   // device buffer insider_hip_residual() copies out through (MB; at least 16 genes of the window)
@@ -3218,6 +3232,9 @@ int insider_hip_get_info(insider_hip_handle *h, const char *name, double *out)
     else if (s == "col_stats_kernel") *out = h->col_stats_kernel;   // last column-side statistics: the kernel (ColStatsKernel) ...
     else if (s == "col_stats_tickets") *out = h->col_stats_tickets; // ... k_col_paircnt4's ticket counters (1 or 16; 0: another kernel)
     else if (s == "col_stats_blocks") *out = h->col_stats_blocks;   // ... and its grid size (0: another kernel)
+    else if (s == "col_q_kernel") *out = h->col_q_kernel;           // last Q = S A product: 0 = none yet, 1 = k_mm_rows, 2 = k_mm_rows2
+    else if (s == "mm_rows2_tiles") *out = h->mm_rows2_tiles;       // tiles per wave of the last k_mm_rows2 launch (Q or V), 0 = none yet
+    else if (s == "n_simd") *out = h->ds->n_simd;
     else if (s == "row_kernels") *out = (double)h->row_kernels;     // last optimize() / optimize_row(): row-phase kernel forms (RowKernel bits)
     else if (s == "cd_ms_steady") *out = h->steady_cd_ms;           // option "profile": mean over outer iterations >= 5 of the last call
     else if (s == "col_stats_ms_steady") *out = h->steady_col_ms;

@@ -331,6 +331,70 @@ def test_strong_cd_batch_every_solver(oracle, regime, K):
 
 
 # ----------------------------------------------------------------------------------------------------------------------
+# e. the batch entry past one chunk: strong_cd_device() solves CD_BATCH_DOUBLES / stat_len problems per launch
+# ----------------------------------------------------------------------------------------------------------------------
+CD_BATCH_DOUBLES = 1 << 26
+GEN_BLOCK = 4096                       # problems generated at a time (their design matrices are not kept)
+CHUNKED = [(1, "enet"), (17, "enet"), (17, "lambda0"), (49, "enet")]
+
+
+def _batch_chunk(K):
+    """chunk = 2^26 / stat_len, stat_len = NB (NB + 1) / 2 * 256 doubles per record: 262144, 87381 and 26214 problems."""
+    NB = (K + 16) // 16
+    return CD_BATCH_DOUBLES // (NB * (NB + 1) // 2 * 256)
+
+
+def _batch_block(K, b, count):
+    """Problems b * GEN_BLOCK ... of the batch, built as in test_strong_cd_batch_every_solver from a stream keyed by the block."""
+    rng = np.random.default_rng([300 + K, b])
+    m = 3 * K + 20
+    Xs = rng.standard_normal((count, m, K), dtype=np.float32).astype(np.float64)     # (single-precision draws: half the time)
+    bt = rng.standard_normal((count, K)) * (rng.random((count, K)) < 0.5)
+    ys = np.matmul(Xs, bt[:, :, None])[:, :, 0] + 0.3 * rng.standard_normal((count, m))
+    ws = 0.1 * rng.standard_normal((count, K))
+    return Xs, ys, ws
+
+
+@pytest.mark.parametrize("K,regime", CHUNKED, ids=[f"{r}-K{K}" for K, r in CHUNKED])
+def test_strong_cd_batch_past_one_chunk(oracle, K, regime):
+    chunk = _batch_chunk(K)
+    assert chunk == {1: 262144, 17: 87381, 49: 26214}[K]
+    nprob = chunk + 3
+    Gs, qs, ws = np.empty((nprob, K, K)), np.empty((nprob, K)), np.empty((nprob, K))
+    for b in range(-(-nprob // GEN_BLOCK)):
+        lo, hi = b * GEN_BLOCK, min((b + 1) * GEN_BLOCK, nprob)
+        Xs, ys, ws[lo:hi] = _batch_block(K, b, hi - lo)
+        np.matmul(Xs.transpose(0, 2, 1), Xs, out=Gs[lo:hi])
+        qs[lo:hi] = np.matmul(Xs.transpose(0, 2, 1), ys[:, :, None])[:, :, 0]
+    lam, alpha = {"lambda0": (0.0, 0.5), "enet": (0.35 * float(np.max(np.abs(qs[:9]))), 0.6)}[regime]
+    probe = [0, 1, chunk - 2, chunk - 1, chunk, chunk + 1, chunk + 2]
+    alone = np.r_[chunk - 64:chunk + 3]           # the last 64 problems of the first chunk and the 3 of the second
+    for cap in (3, UNCAPPED):
+        beta, sw = api.strong_coordinate_descent(None, None, ws, lam, alpha, Gs, qs, tol=TOL, seed=5, it=3, max_sweeps=cap,
+                                                 return_sweeps=True)
+        assert _lib.COL_SOLVERS[_lib.load().insider_hip_last_cd_solver()] == \
+            expected("enet" if regime == "enet" else "nol1", 0, K), cap
+        # against the oracle: what a wrong offset of a chunk's Gram matrices, solutions or sweep counts would fail
+        for j in probe:
+            Xs, ys, _ = _batch_block(K, j // GEN_BLOCK, min(GEN_BLOCK, nprob - j // GEN_BLOCK * GEN_BLOCK))
+            i = j % GEN_BLOCK
+            ob, osw = oracle.strong_cd(Xs[i], ys[i], ws[j], lam, alpha, Gs[j], qs[j], tol=TOL, seed=5, unit=j, it=3,
+                                       max_sweeps=cap)
+            if cap == 3:
+                assert sw[j] == osw, (j, sw[j], osw)
+                assert np.max(np.abs(ob - beta[j])) < 1e-10 * max(1.0, np.max(np.abs(ob))), j
+            else:
+                assert abs(osw - sw[j]) <= 1, (j, osw, sw[j])
+                assert np.max(np.abs(ob - beta[j])) < (1e-9 if osw == sw[j] else 50 * np.sqrt(TOL)), j
+                assert np.array_equal(ob == 0, beta[j] == 0)
+        # across the chunks: the chunking changes no result, so the same problems solved in a call of their own give the same bits
+        beta1, sw1 = api.strong_coordinate_descent(None, None, ws[alone], lam, alpha, Gs[alone], qs[alone], tol=TOL, seed=5,
+                                                   it=3, max_sweeps=cap, return_sweeps=True)
+        assert np.array_equal(sw1, sw[alone]), (cap, np.nonzero(sw1 != sw[alone]))
+        assert np.array_equal(beta1, beta[alone]), (cap, np.nonzero((beta1 != beta[alone]).any(1)))
+
+
+# ----------------------------------------------------------------------------------------------------------------------
 # the upper edge of the band
 # ----------------------------------------------------------------------------------------------------------------------
 def test_k64_is_unsupported_and_leaves_the_factors_untouched():

@@ -168,15 +168,16 @@ def factors(c, rng):
     return A
 
 
-def reference(c, A):
-    """G, q, ss of every gene in float64, and the scales of the bounds: ||R'R||, ||X'R|| per gene, sum x^2 per gene."""
+def reference(c, A, genes=None):
+    """G, q, ss of every gene in float64, and the scales of the bounds: ||R'R||, ||X'R|| per gene, sum x^2 per gene.  genes: the
+    genes G is formed for (a large p: K^2 doubles per gene); q, ss and the scales are always those of every gene."""
     lev, X, Mtr, Mte, Z = data(c)
     ncov = len(c["levels"])
     R = sum(A[t][lev[:, t] - 1] for t in range(ncov))
     if c["m"]:
         R = R + Z @ A[ncov]
     T = Mtr.astype(np.float64)
-    G = np.einsum("ij,ik,il->jkl", T, R, R)
+    G = np.einsum("ij,ik,il->jkl", T if genes is None else T[:, genes], R, R)
     q = np.einsum("ij,ik->jk", T * X, R)
     ss = ((1.0 - T) * X * X).sum(0)
     return G, q, ss, np.linalg.norm(R.T @ R), np.linalg.norm(X.T @ R, axis=1), (X * X).sum(0)
@@ -190,9 +191,12 @@ def handle(c):
     return ds
 
 
-def check_values(c, got, A, tag=""):
+def check_values(c, got, A, tag="", genes=None, ref=None):
+    """genes: compare G on these genes only (reference(c, A, genes)); ref: that reference, when the caller has it already."""
     G, q, ss = got
-    Gr, qr, ssr, sG, sq, sx = reference(c, A)
+    Gr, qr, ssr, sG, sq, sx = ref if ref is not None else reference(c, A, genes)
+    if genes is not None:
+        G = G[genes]
     # every form but the lists builds train = full - complement: the bounds scale with the full products
     eG = np.linalg.norm(G - Gr, axis=(1, 2))
     assert np.all(eG <= 1e-12 * sG), (tag, int(np.argmax(eG / sG)), float(np.max(eG / sG)))

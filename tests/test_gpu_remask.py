@@ -143,17 +143,25 @@ def _fold_masks(ids, f):
     return (np.asfortranarray((ids != f) & (ids != 0), dtype=np.uint8), np.asfortranarray(ids == f, dtype=np.uint8))
 
 
-@pytest.mark.parametrize("F", [3, 5])
-@pytest.mark.parametrize("kw,m", [(dict(n=70, p=90, level_counts=(5, 4)), 0),
-                                  (dict(n=131, p=77, level_counts=(6, 3), with_na=True), 0),     # n not a multiple of CHUNK, NA
-                                  (dict(n=128, p=50, level_counts=(4, 4)), 1),                   # n a multiple: no pad elements
-                                  (dict(n=300, p=40, level_counts=(5, 2), with_na=True), 0)])    # more than one 16-byte step per lane
+FOLD_DATA = [(dict(n=70, p=90, level_counts=(5, 4)), 0),
+             (dict(n=131, p=77, level_counts=(6, 3), with_na=True), 0),     # n not a multiple of CHUNK, NA
+             (dict(n=128, p=50, level_counts=(4, 4)), 1),                   # n a multiple: no pad elements
+             (dict(n=300, p=40, level_counts=(5, 2), with_na=True), 0)]     # more than one 16-byte step per lane
+P_PAST_GRID = 32805    # k_fold_codes runs min(ceil(p / 4), 8 n_simd) blocks of four genes: past 32 n_simd genes the blocks stride
+                       # (32 * 1024 + 37 on 256 compute units)
+FOLD_CASES = [pytest.param(kw, m, F, id=f"kw{i}-{m}-{F}") for F in (3, 5) for i, (kw, m) in enumerate(FOLD_DATA)] + \
+             [pytest.param(dict(n=21, p=P_PAST_GRID, level_counts=(4, 3)), 0, 3, id="kw4-0-3")]
+
+
+@pytest.mark.parametrize("kw,m,F", FOLD_CASES)
 def test_fold_equals_create_by_bits(kw, m, F):
     K = 9
     w = workloads.small(K=K, **kw)
     Z = np.asfortranarray(np.random.default_rng(8).standard_normal((w.n, m))) if m else None
     ids = _fold_ids(w, F)
     a = api.InsiderData(w.X, w.levels, w.M_train, w.M_test, ctns_confounder=Z)
+    if w.p == P_PAST_GRID:
+        assert 4 * 8 * a.info("n_simd") < w.p
     a.set_folds(ids, F)
     try:
         for f in range(1, F + 1):

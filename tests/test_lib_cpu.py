@@ -60,6 +60,19 @@ def test_col_stats_kernel_codes_match_the_library():
         assert f'"{key}"' in hdr, key
 
 
+def test_streaming_product_facts_are_documented():
+    """insider_hip_get_info("col_q_kernel" / "mm_rows2_tiles" / "n_simd") and the option "mm_tiles": the header documents
+    them, the library knows them, and _lib.COL_Q_KERNELS names the codes the header gives."""
+    assert _lib.COL_Q_KERNELS == ("none", "mm_rows", "mm_rows2")
+    hdr = open(os.path.join(ROOT, "include", "insider_hip.h")).read()
+    src = open(os.path.join(ROOT, "insider_amd", "csrc", "insider_hip.hip")).read()
+    for key in ("col_q_kernel", "mm_rows2_tiles", "n_simd", "mm_tiles"):
+        assert f'"{key}"' in hdr, key
+        assert f's == "{key}"' in src, key
+    desc = " ".join(hdr[hdr.index('"col_q_kernel"'):hdr.index('"mm_rows2_tiles"')].replace("*", " ").split())
+    assert "1 k_mm_rows<NB>" in desc and "2 k_mm_rows2<NB>" in desc
+
+
 def test_product_never_imports_oracle():
     # only tests/, smoke() and bench.py's cpu_baseline leg may touch oracle/
     for dirpath, _, files in os.walk(os.path.join(ROOT, "insider_amd")):
