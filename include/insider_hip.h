@@ -167,7 +167,10 @@ int insider_hip_comm_init(insider_hip_handle *h, const void *unique_id, int rank
  * the iterates are bit-identical to the single-pass solve), "resid_stage_mb" (size in MB of the device buffer
  * insider_hip_residual() copies the residual out through, default 256; at least 16 genes of the window), "vd_stage_kb" (LDS budget in
  * KiB for the level tables insider_hip_variance_decomposition() stages per block, default 48, at most 60; tables that do not
- * fit are read from global memory instead, with the same result; 0 = always that form). */
+ * fit are read from global memory instead, with the same result; 0 = always that form; insider_hip_sample_decomposition()
+ * stages its groups of genes' tables under the same budget), "sd_slabs" (gene slabs the streaming pass of
+ * insider_hip_sample_decomposition() is cut into, summed in slab order; 0, default = from n, p and the device's compute units;
+ * at most 256 and at most p; another count gives the same sums in another order). */
 int insider_hip_set_option(insider_hip_handle *h, const char *name, double value);
 
 /*
@@ -357,6 +360,25 @@ int insider_hip_interaction_glm(insider_hip_handle *h, double *const *A, const d
 int insider_hip_variance_decomposition(insider_hip_handle *h, double *const *A, const double *C, int inc_continuous, int K,
                                        int entries, double *out);
 
+/*
+ * Per-sample fit diagnostics of a fitted model on the resident data set: the record of insider_hip_variance_decomposition()
+ * along the other axis.  Blocks, g_b(i,j), f, r, x and the meaning of entries are those of that call; S_i is the set of genes j
+ * whose entry (i, j) is selected.
+ * out holds n records of 4 + 3 B doubles, record i at out + i (4 + 3 B): n_i = |S_i|, sum x, sum x^2, sum r^2 (formed from r
+ * itself), then for b = 0..B-1 at 4 + 3 b: sum g_b, sum g_b^2, sum r g_b.  All sums run over S_i.  Summed over the samples, a
+ * slot equals the same slot of the per-gene records summed over the genes (to rounding).
+ * Arguments, status codes and scope as in insider_hip_variance_decomposition() (K 1..63, the same inc_continuous rules, entries
+ * outside 0..2 and a null out return INSIDER_ERR_ARG, a sharded handle returns INSIDER_ERR_UNSUPPORTED).  Works on clones and
+ * re-masked handles, on the handle's main stream, in the post-hoc workspace: an optimize() after it is bit-identical to one
+ * without.  The pass is one stream over X and the mask codes on a grid of sample tiles x gene slabs; the slabs' partial records
+ * are summed in slab order, without atomics: repeated calls with the same options on the same device give bit-identical
+ * records.  The slab count follows from n, p, the device's compute units and option "sd_slabs" alone;
+ * insider_hip_get_info("sd_slabs") tells the count of the last call and "sd_path" the form of its pass (1 = level tables
+ * staged in LDS in groups of genes, 2 = read from global memory; option "vd_stage_kb"; both forms give the same bits).
+ */
+int insider_hip_sample_decomposition(insider_hip_handle *h, double *const *A, const double *C, int inc_continuous, int K,
+                                     int entries, double *out);
+
 /* Profile of the last insider_hip_optimize() call (option "profile" = 1), HIP-event timed on the library's stream.
  * out[0..11]: {column-side masked-Gram launches, total ms, row-side masked-Gram launches, total ms,
  *  column-solve (CD / ridge) launches, total ms, test-residual launches, total ms,
@@ -386,6 +408,8 @@ int insider_hip_get_profile(insider_hip_handle *h, double *out12);
  * "n_simd" (SIMDs of the handle's device, 4 per compute unit),
  * "vd_path" (the form of k_vd_stats the last insider_hip_variance_decomposition() ran: 1 = level tables in LDS, 2 = read from
  * global memory; 0 = none yet),
+ * "sd_path" / "sd_slabs" (of the last insider_hip_sample_decomposition(): the form of k_sd_stats, 1 = level tables in LDS, 2 =
+ * read from global memory, 0 = none yet; and the gene slabs its grid had),
  * "row_kernels" (a bit mask of the row-phase kernel forms the last optimize() / optimize_row() launched, reset at the start of
  * each; set on the host at each launch site.  Level Gram sums: bit 0 wgemm4, 1 wgemm5, 2 wgemm6, 3 wgemm7 (k_wgemm<LT>),
  * 4 wgemm_chunks (a k_wgemm launch with more than one level-tile chunk, grid.z > 1), 5 wsyrk (k_wsyrk<NB>; neither wsyrk nor a

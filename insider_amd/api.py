@@ -296,6 +296,25 @@ class InsiderData:
         return dict(n=out[:, 0].copy(), sum_x=out[:, 1].copy(), sum_xx=out[:, 2].copy(), rss=out[:, 3].copy(),
                     sum_g=blk[:, :, 0].T.copy(), sum_gg=blk[:, :, 1].T.copy(), sum_rg=blk[:, :, 2].T.copy())
 
+    def sample_decomposition(self, cfd_factors, column_factor, entries="train", inc_continuous=0):
+        """Per-sample sums of the fit diagnostics (insider_hip_sample_decomposition): variance_decomposition() along the
+        other axis, over the selected entries of every sample: a dict of ``n``, ``sum_x``, ``sum_xx``, ``rss`` (length n) and
+        ``sum_g``, ``sum_gg``, ``sum_rg`` (B x n).  posthoc.vd_derived() turns them into r2 / rmse / explained / drop_one,
+        posthoc.level_decomposition() sums them per level of a covariate first."""
+        if entries not in self.VD_ENTRIES:
+            raise InsiderError(_lib.ERR_ARG, f"entries must be one of {sorted(self.VD_ENTRIES)}, got {entries!r}")
+        if inc_continuous not in (0, 1):
+            raise InsiderError(_lib.ERR_ARG, "The value of prarameter inc_continuous can only be 0 or 1.")
+        K = int(np.asarray(column_factor).shape[0])
+        A, Cw, Aptrs = self._marshal(cfd_factors, column_factor, K, inc_continuous)
+        nb = self.c + int(inc_continuous)
+        out = np.empty((self.n, 4 + 3 * nb), dtype=np.float64)
+        _lib.check(_lib.load().insider_hip_sample_decomposition(self._h, Aptrs, _lib.ptr(Cw), int(inc_continuous), K,
+                                                                self.VD_ENTRIES[entries], _lib.ptr(out)))
+        blk = out[:, 4:].reshape(self.n, nb, 3)
+        return dict(n=out[:, 0].copy(), sum_x=out[:, 1].copy(), sum_xx=out[:, 2].copy(), rss=out[:, 3].copy(),
+                    sum_g=blk[:, :, 0].T.copy(), sum_gg=blk[:, :, 1].T.copy(), sum_rg=blk[:, :, 2].T.copy())
+
     def masked_gram_cols(self, R):
         R = _lib.f64(R)
         K = R.shape[1]

@@ -8,6 +8,7 @@
 #include "insider_kernels.hpp"
 #include "insider_posthoc.hpp"
 #include "insider_vardecomp.hpp"
+#include "insider_sampdecomp.hpp"
 
 #include <rccl/rccl.h>
 
@@ -381,6 +382,7 @@ struct Options {
     double resid_stage_mb = 256.0;    // "resid_stage_mb": size of the device buffer the residual is copied out through
     // "vd_stage_kb" bounds the LDS a block of k_vd_stats may stage its genes' level tables in (KiB)
     double vd_stage_kb = 48.0;
+    int sd_slabs = 0;                 // "sd_slabs": gene slabs of k_sd_stats (0 = automatic; at most 256)
 };
 
 // device workspace of the post-hoc calls (section "post-hoc interaction GLM"): grown on demand, freed with the handle
@@ -394,6 +396,8 @@ struct PostWs {
     // variance decomposition: vin = the host factors (A blocks at row offset x K, then C as p rows of K); vtab = the level
     // table T (p rows of SL); vrec = the p records
     DevBuf<double> vin, vtab, vrec;
+    // sample decomposition: spart = the slabs' partial records (slabs x n x (4 + 3 BW)); srec = the n records
+    DevBuf<double> spart, srec;
 };
 
 }  // namespace
@@ -403,7 +407,7 @@ struct insider_hip_handle {
     Streams st;
     Options opt;
     Workspace ws;
-    // post-hoc interaction GLM / residual / variance decomposition: a workspace of its own, so that nothing
+    // post-hoc interaction GLM / residual / variance and sample decomposition: a workspace of its own, so that nothing
     // insider_hip_optimize() reads is touched
     PostWs post;
     // state of the running optimize()
@@ -437,6 +441,8 @@ struct insider_hip_handle {
     uint64_t row_kernels = 0;
     // the form the last variance decomposition ran (1 = tables in LDS, 2 = from global)
     int vd_path = 0;
+    // the form the last sample decomposition ran (1 = tables in LDS, 2 = from global) and its gene slabs
+    int sd_path = 0, sd_slabs = 0;
 
     // work still in flight is drained and the communicator closed before the members free their buffers (the data set with
     // its last handle)
@@ -2587,6 +2593,7 @@ int insider_hip_set_option(insider_hip_handle *h, const char *name, double value
     else if (s == "cd_pairs") h->opt.cd_pairs = (int)value;           // 1 (default) = sweeps routed through the blocks of two coordinate steps (K <= 30; same iterates), 0 = one step per block
     else if (s == "resid_stage_mb") h->opt.resid_stage_mb = value;   // device buffer insider_hip_residual() copies out through (MB; at least 16 genes of the window)
     else if (s == "vd_stage_kb") h->opt.vd_stage_kb = value;         // LDS budget (KiB, default 48, at most 60) of the staged level tables of k_vd_stats (0 = always the global form)
+    else if (s == "sd_slabs") h->opt.sd_slabs = value < 1 ? 0 : (int)std::min(value, 256.0);   // gene slabs of k_sd_stats (0 = from n, p and the compute units; at most 256)
     else if (s == "cd_variant") h->opt.cd_variant = (int)value;   // 0 = register-resident (4 genes per wave; K <= 32, and 32 < K <= 48 with the third slot's columns in LDS), 1 = group kernel, 2 = row16 (LDS, K <= 48)
     else return fail(INSIDER_ERR_ARG, "unknown option " + s);
     return INSIDER_OK;
@@ -3239,6 +3246,8 @@ int insider_hip_get_info(insider_hip_handle *h, const char *name, double *out)
     else if (s == "cd_ms_steady") *out = h->steady_cd_ms;           // option "profile": mean over outer iterations >= 5 of the last call
     else if (s == "col_stats_ms_steady") *out = h->steady_col_ms;
     else if (s == "vd_path") *out = h->vd_path;                     // last variance decomposition: 1 = level tables in LDS, 2 = read from global
+    else if (s == "sd_path") *out = h->sd_path;                     // last sample decomposition: 1 = level tables in LDS, 2 = read from global
+    else if (s == "sd_slabs") *out = h->sd_slabs;                   // ... and its gene slabs
     else if (s == "col_mfma_per_gene") {
         // v_mfma_f64_16x16x4_f64 instructions the column-side statistics kernel issues per gene (2048 flops each; the 4x4x4 form
         // of the per-entry kernel is counted in the same unit: a quarter per instruction)
@@ -3529,9 +3538,10 @@ int ph_finish(insider_hip_handle *h, int rc)
 
 #undef PH_DISPATCH
 
-// ---- variance decomposition (kernels: insider_vardecomp.hpp) ------------------------------------------------------------
-int variance_decomposition_body(insider_hip_handle *h, double *const *A, const double *C, int inc_continuous, int K,
-                                int entries, double *out)
+// ---- variance / sample decomposition (kernels: insider_vardecomp.hpp, insider_sampdecomp.hpp) -------------------------
+// the argument checks both decompositions share
+int vd_check(insider_hip_handle *h, double *const *A, const double *C, int inc_continuous, int K, int entries,
+             const double *out)
 {
     if (!h) return fail(INSIDER_ERR_ARG, "null handle");
     const std::vector<int32_t> every((size_t)h->ds->c + 2, 1);   // every block enters the fit
@@ -3539,15 +3549,21 @@ int variance_decomposition_body(insider_hip_handle *h, double *const *A, const d
     if (rc) return rc;
     if (entries < 0 || entries > 2) return fail(INSIDER_ERR_ARG, "entries must be 0 (all), 1 (train) or 2 (test)");
     if (!out) return fail(INSIDER_ERR_ARG, "null output");
-    HIPCHECK(hipSetDevice(h->ds->device));
+    return INSIDER_OK;
+}
+
+// the level table T = [A_stack; B_c] C of the nb blocks, gene-major (T[j][0..SL)), enqueued on the main stream into
+// PostWs::vtab
+int vd_build_table(insider_hip_handle *h, double *const *A, const double *C, int K, int nb)
+{
     PostWs &w = h->post;
     hipStream_t st = h->st.stream;
-    const int nb = h->ds->c + inc_continuous, SL = h->ds->SL, KPW = 16 * ((K + 15) / 16), rec = 4 + 3 * nb;
-    const int64_t n = h->ds->n, p = h->ds->p;
-    if ((rc = w.vin.grow((size_t)(SL + p) * K)) || (rc = w.Ast.grow((size_t)SL * KPW)) || (rc = w.vtab.grow((size_t)p * SL)) ||
-        (rc = w.vrec.grow((size_t)p * rec)))
+    const int SL = h->ds->SL, KPW = 16 * ((K + 15) / 16);
+    const int64_t p = h->ds->p;
+    int rc;
+    if ((rc = w.vin.grow((size_t)(SL + p) * K)) || (rc = w.Ast.grow((size_t)SL * KPW)) || (rc = w.vtab.grow((size_t)p * SL)))
         return rc;
-    double *vin = w.vin, *Ast = w.Ast, *T = w.vtab, *R = w.vrec;
+    double *vin = w.vin, *Ast = w.Ast, *T = w.vtab;
     // [A_stack; B_c] as SL rows of KPW (the layout of ph_prepare), C as p rows of K
     for (int b = 0; b < nb; ++b) {
         const DataSet::Block blk = h->ds->block(b);
@@ -3567,6 +3583,21 @@ int variance_decomposition_body(insider_hip_handle *h, double *const *A, const d
     else VT_LAUNCH(4);
 #undef VT_LAUNCH
     KCHECK();
+    return INSIDER_OK;
+}
+
+int variance_decomposition_body(insider_hip_handle *h, double *const *A, const double *C, int inc_continuous, int K,
+                                int entries, double *out)
+{
+    int rc = vd_check(h, A, C, inc_continuous, K, entries, out);
+    if (rc) return rc;
+    HIPCHECK(hipSetDevice(h->ds->device));
+    PostWs &w = h->post;
+    hipStream_t st = h->st.stream;
+    const int nb = h->ds->c + inc_continuous, SL = h->ds->SL, rec = 4 + 3 * nb;
+    const int64_t n = h->ds->n, p = h->ds->p;
+    if ((rc = vd_build_table(h, A, C, K, nb)) || (rc = w.vrec.grow((size_t)p * rec))) return rc;
+    double *T = w.vtab, *R = w.vrec;
     // one pass over X per window of BW blocks
     const int sel = entries == 0 ? 0 : entries == 1 ? CODE_TRAIN : CODE_TEST;
     const int m = inc_continuous ? h->ds->m : 0;
@@ -3600,6 +3631,65 @@ int variance_decomposition_body(insider_hip_handle *h, double *const *A, const d
     return INSIDER_OK;
 }
 
+// the same record per sample: the level table, then per window of BW blocks one streaming pass over X and the codes whose
+// grid is sample tiles x gene slabs (k_sd_stats) and the sum of the slabs' partial records in slab order (k_sd_reduce)
+int sample_decomposition_body(insider_hip_handle *h, double *const *A, const double *C, int inc_continuous, int K,
+                              int entries, double *out)
+{
+    int rc = vd_check(h, A, C, inc_continuous, K, entries, out);
+    if (rc) return rc;
+    HIPCHECK(hipSetDevice(h->ds->device));
+    PostWs &w = h->post;
+    hipStream_t st = h->st.stream;
+    const int nb = h->ds->c + inc_continuous, SL = h->ds->SL, rec = 4 + 3 * nb;
+    const int64_t n = h->ds->n, p = h->ds->p;
+    // gene slabs: from n, p, the device's compute units and option "sd_slabs" alone.  Automatic: eight blocks per compute
+    // unit (a block is SD_WAVES waves; three are resident per unit at 130 - 170 registers), at most 256 slabs
+    const int tiles = cdiv(n, SD_TILE);
+    const int want = h->opt.sd_slabs > 0 ? h->opt.sd_slabs : cdiv(2 * h->ds->n_simd, tiles);
+    const int64_t slab_len = cdiv(p, (int64_t)std::max(1, std::min(want, 256)));
+    const int slabs = (int)cdiv(p, slab_len);
+    const int BW = nb == 1 ? 1 : nb == 2 ? 2 : 4, RW = 4 + 3 * BW;
+    if ((rc = vd_build_table(h, A, C, K, nb)) || (rc = w.spart.grow((size_t)slabs * n * RW)) ||
+        (rc = w.srec.grow((size_t)n * rec)))
+        return rc;
+    double *T = w.vtab, *part = w.spart, *R = w.srec;
+    const int sel = entries == 0 ? 0 : entries == 1 ? CODE_TRAIN : CODE_TEST;
+    const int m = inc_continuous ? h->ds->m : 0;
+    // tables staged in groups of whole load steps of SD_GU genes, as many as the budget of "vd_stage_kb" holds (at most 60 KiB
+    // of dynamic LDS and no static LDS: no launch attribute needed); when not even one step's tables fit: the global form
+    const double budget = std::min(std::max(h->opt.vd_stage_kb, 0.0), 60.0) * 1024.0;
+    const int fit = (int)std::min<double>(budget / ((double)SL * sizeof(double)), SD_GROUP_MAX) / SD_GU * SD_GU;
+    const bool staged = fit >= SD_GU;
+    const int gg = staged ? fit : (int)std::min<int64_t>(slab_len, INT32_MAX);
+    h->sd_path = staged ? 1 : 2;
+    h->sd_slabs = slabs;
+#define SD_LAUNCH(BW_)                                                                                                      \
+    for (int b0 = 0; b0 < nb; b0 += BW_) {                                                                                   \
+        if (staged)                                                                                                          \
+            hipLaunchKernelGGL((k_sd_stats<BW_, true>), dim3(tiles, slabs), dim3(64 * SD_WAVES),                             \
+                               (size_t)gg * SL * sizeof(double), st, (const double *)h->ds->X, (const uint8_t *)h->ds->codes, \
+                               h->ds->ldn, (int)n, p, (const int *)h->ds->lev, (const int *)h->ds->lvl_off_d, h->ds->c,      \
+                               (const double *)h->ds->Zc, m, h->ds->SLcat, (const double *)T, SL, sel, b0, slab_len, gg, part); \
+        else                                                                                                                 \
+            hipLaunchKernelGGL((k_sd_stats<BW_, false>), dim3(tiles, slabs), dim3(64 * SD_WAVES), 0, st,                     \
+                               (const double *)h->ds->X, (const uint8_t *)h->ds->codes, h->ds->ldn, (int)n, p,               \
+                               (const int *)h->ds->lev, (const int *)h->ds->lvl_off_d, h->ds->c, (const double *)h->ds->Zc, m, \
+                               h->ds->SLcat, (const double *)T, SL, sel, b0, slab_len, gg, part);                            \
+        KCHECK();                                                                                                            \
+        hipLaunchKernelGGL(k_sd_reduce, dim3(cdiv(n * RW, 256)), dim3(256), 0, st, (const double *)part, slabs, n, RW, nb,   \
+                           b0, R);                                                                                           \
+        KCHECK();                                                                                                            \
+    }
+    if (BW == 1) SD_LAUNCH(1)
+    else if (BW == 2) SD_LAUNCH(2)
+    else SD_LAUNCH(4)
+#undef SD_LAUNCH
+    HIPCHECK(hipMemcpyAsync(out, R, (size_t)n * rec * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipStreamSynchronize(st));
+    return INSIDER_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -3621,6 +3711,12 @@ int insider_hip_variance_decomposition(insider_hip_handle *h, double *const *A, 
                                        int entries, double *out)
 {
     return ph_finish(h, variance_decomposition_body(h, A, C, inc_continuous, K, entries, out));
+}
+
+int insider_hip_sample_decomposition(insider_hip_handle *h, double *const *A, const double *C, int inc_continuous, int K,
+                                     int entries, double *out)
+{
+    return ph_finish(h, sample_decomposition_body(h, A, C, inc_continuous, K, entries, out));
 }
 
 }  // extern "C"

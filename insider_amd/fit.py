@@ -7,13 +7,16 @@
     ... --tune --folds 5 ...                    # k-fold cross-validated tune(): mean / pooled / per-fold RMSE per grid point
     ... --interaction 1 2 --interaction-glm 1   # then glm_interaction() on the device for covariate column 1 (0-based)
     ... --variance-decomposition                # then the per-gene variance decomposition on the device
+    ... --sample-decomposition                  # then the per-sample and per-level fit diagnostics on the device
 
 Semantics are those of insider_amd.api (the mirror of R/insider.R): with masks given, `--partition 1` fits on the
 train entries (optimize(tuning = 1)) and reports the test RMSE; without masks (or `--partition 0`) every non-NA entry is
 used (fit()'s default, R/insider.R:190-216; NaN entries of X are the NA set).  Inits are N(0, 0.001^2)
 (R/utils.R:40-43) from --seed.  --interaction-glm COV adds interaction_coeff / interaction_pval (L_COV x K, glm_interaction()
 on the device against the residual of every other block); --variance-decomposition adds vd_r2 / vd_rmse (p) and
-vd_explained / vd_drop_one (B x p, posthoc.vd_derived) over the entries the fit used.  Output: A<i> (L_i x K), C (K x p) and result.json {train_rmse, test_rmse, loss,
+vd_explained / vd_drop_one (B x p, posthoc.vd_derived) over the entries the fit used; --sample-decomposition adds the same per
+sample, sd_r2 / sd_rmse (n) and sd_explained / sd_drop_one (B x n), and per level of every categorical covariate b,
+sd_level<b>_r2 / sd_level<b>_rmse (L_b, posthoc.level_decomposition).  Output: A<i> (L_i x K), C (K x p) and result.json {train_rmse, test_rmse, loss,
 iters, traj} in --out.  There is no CPU fallback: without a visible MI355X the command fails with the library's status.
 """
 import argparse
@@ -63,6 +66,10 @@ def parse(argv=None):
     ap.add_argument("--variance-decomposition", action="store_true",
                     help="after the fit, the per-gene variance decomposition on the device over the entries the fit used; "
                          "writes vd_r2, vd_rmse (p) and vd_explained, vd_drop_one (blocks x p) next to the factors")
+    ap.add_argument("--sample-decomposition", action="store_true",
+                    help="after the fit, the per-sample fit diagnostics on the device over the entries the fit used; writes "
+                         "sd_r2, sd_rmse (n), sd_explained, sd_drop_one (blocks x n) and, per categorical covariate b, "
+                         "sd_level<b>_r2, sd_level<b>_rmse (its levels) next to the factors")
     a = ap.parse_args(argv)
     if not a.flat and not (a.x and a.levels):
         ap.error("give --flat DIR or --x and --levels")
@@ -166,6 +173,15 @@ def main(argv=None):
         d = vd_derived(ds.variance_decomposition(list(res["row_matrices"].values()), res["column_factor"], entries="train",
                                                  inc_continuous=1 if Z is not None else 0))
         vd = {"vd_r2": d["r2"], "vd_rmse": d["rmse"], "vd_explained": d["explained"], "vd_drop_one": d["drop_one"]}
+    if a.sample_decomposition:
+        from .posthoc import level_decomposition, vd_derived
+        rec = ds.sample_decomposition(list(res["row_matrices"].values()), res["column_factor"], entries="train",
+                                      inc_continuous=1 if Z is not None else 0)
+        d = vd_derived(rec)
+        vd = dict(vd or {}, sd_r2=d["r2"], sd_rmse=d["rmse"], sd_explained=d["explained"], sd_drop_one=d["drop_one"])
+        for b in range(ds.c):
+            lv = level_decomposition(rec, ds_levels[:, b], int(ds.n_levels[b]))
+            vd[f"sd_level{b}_r2"], vd[f"sd_level{b}_rmse"] = lv["r2"], lv["rmse"]
     ds.close()
     summary = dict(train_rmse=res["train_rmse"], test_rmse=None if np.isnan(res["test_rmse"]) else res["test_rmse"],
                    loss=res["loss"], iters=res["iters"], rank=K, **{"lambda": a.lam}, alpha=a.alpha, partition=partition,

@@ -13,6 +13,11 @@ glm_interaction_resident() runs the same arithmetic on the device from the resid
 variance_decomposition() answers a different question per gene: how much of its variance each covariate block carries
 and how well the model fits it (InsiderData.variance_decomposition: the level table [A_stack; B_c] C, then one streaming
 pass over X); variance_decomposition_host() is the same record in plain numpy (the yardstick).
+
+sample_decomposition() is the same record per sample instead of per gene (InsiderData.sample_decomposition: how well the
+model fits each sample, which samples are outliers, what each block carries of a sample's variance), with
+sample_decomposition_host() as its yardstick; level_decomposition() pools the samples of each level of a covariate
+(per donor, per tissue).
 """
 import numpy as np
 
@@ -97,10 +102,8 @@ def vd_derived(rec):
     return out
 
 
-def variance_decomposition_host(X, levels, ctns, mask, A, C):
-    """The variance-decomposition record in plain numpy (the yardstick of the device path).  X: n x p; levels: n x c level
-    ids 1..L_b; ctns: n x m or None; mask: n x p (entries that count) or None (every entry); A: the c categorical row
-    factors (L_b x K), then B_c (m x K) when ctns is given; C: K x p.  -> vd_derived() of the raw sums."""
+def _decomposition_host(X, levels, ctns, mask, A, C, axis):
+    """The raw sums of the decomposition record over ``axis`` of the n x p terms (0: per gene, 1: per sample)."""
     X = np.asarray(X, dtype=np.float64)
     Cm = np.asarray(C, dtype=np.float64)
     lev = np.asarray(levels).reshape(X.shape[0], -1)
@@ -116,11 +119,17 @@ def variance_decomposition_host(X, levels, ctns, mask, A, C):
     r = np.where(w, X - f, 0.0)
     xs = np.where(w, X, 0.0)
     gs = [np.where(w, gb, 0.0) for gb in g]
-    rec = dict(n=w.sum(axis=0).astype(np.float64), sum_x=xs.sum(axis=0), sum_xx=(xs * xs).sum(axis=0),
-               rss=(r * r).sum(axis=0), sum_g=np.array([gb.sum(axis=0) for gb in gs]).reshape(len(g), -1),
-               sum_gg=np.array([(gb * gb).sum(axis=0) for gb in gs]).reshape(len(g), -1),
-               sum_rg=np.array([(r * gb).sum(axis=0) for gb in gs]).reshape(len(g), -1))
-    return vd_derived(rec)
+    return dict(n=w.sum(axis=axis).astype(np.float64), sum_x=xs.sum(axis=axis), sum_xx=(xs * xs).sum(axis=axis),
+                rss=(r * r).sum(axis=axis), sum_g=np.array([gb.sum(axis=axis) for gb in gs]).reshape(len(g), -1),
+                sum_gg=np.array([(gb * gb).sum(axis=axis) for gb in gs]).reshape(len(g), -1),
+                sum_rg=np.array([(r * gb).sum(axis=axis) for gb in gs]).reshape(len(g), -1))
+
+
+def variance_decomposition_host(X, levels, ctns, mask, A, C):
+    """The variance-decomposition record in plain numpy (the yardstick of the device path).  X: n x p; levels: n x c level
+    ids 1..L_b; ctns: n x m or None; mask: n x p (entries that count) or None (every entry); A: the c categorical row
+    factors (L_b x K), then B_c (m x K) when ctns is given; C: K x p.  -> vd_derived() of the raw sums."""
+    return vd_derived(_decomposition_host(X, levels, ctns, mask, A, C, 0))
 
 
 def variance_decomposition(obj, which="fit", entries="train"):
@@ -134,3 +143,44 @@ def variance_decomposition(obj, which="fit", entries="train"):
     rec = ds.variance_decomposition(list(obj["cfd_matrices"].values()), obj["column_factor"], entries=entries,
                                     inc_continuous=int(obj["inc_continuous"]))
     return vd_derived(rec)
+
+
+def sample_decomposition_host(X, levels, ctns, mask, A, C):
+    """The per-sample record in plain numpy (the yardstick of InsiderData.sample_decomposition): the terms of
+    variance_decomposition_host(), summed over the genes of every sample.  -> vd_derived() of the raw sums, each of length
+    n (B x n per block)."""
+    return vd_derived(_decomposition_host(X, levels, ctns, mask, A, C, 1))
+
+
+def sample_decomposition(obj, which="fit", entries="train"):
+    """Per-sample fit diagnostics of a fitted ``Insider`` object on the device: variance_decomposition() along the other
+    axis, with the same ``which`` / ``entries``.  -> vd_derived() of the raw sums: n, sum_x, sum_xx, rss, tss, r2, rmse (n),
+    sum_g, sum_gg, sum_rg, explained, drop_one (B x n).  A sample's tss is its spread across genes."""
+    from . import api
+    ds = api._resident(obj, which)
+    rec = ds.sample_decomposition(list(obj["cfd_matrices"].values()), obj["column_factor"], entries=entries,
+                                  inc_continuous=int(obj["inc_continuous"]))
+    return vd_derived(rec)
+
+
+RAW_SUMS = ("n", "sum_x", "sum_xx", "rss", "sum_g", "sum_gg", "sum_rg")
+
+
+def level_decomposition(rec, level_ids, n_levels):
+    """The per-sample records pooled per level of a covariate: the raw sums of ``rec`` (sample_decomposition() or
+    InsiderData.sample_decomposition()) of the samples with level id l (1-based ``level_ids``, length n) are added up, row
+    l - 1 of the result for level l, then vd_derived() gives per level n, r2, rmse, explained, drop_one (L and B x L).  A
+    level without selected entries gets NaN in every derived value."""
+    ids = np.asarray(level_ids).ravel().astype(np.int64) - 1
+    L = int(n_levels)
+    if ids.size and (ids.min() < 0 or ids.max() >= L):
+        raise ValueError(f"level ids must be within 1..{L}")
+    pooled = {}
+    for k in RAW_SUMS:
+        v = np.asarray(rec[k], dtype=np.float64)
+        if v.shape[-1] != ids.size:
+            raise ValueError(f"rec[{k!r}] holds {v.shape[-1]} samples, level_ids {ids.size}")
+        out = np.zeros(v.shape[:-1] + (L,))
+        np.add.at(out.reshape(-1, L).T, ids, v.reshape(-1, ids.size).T)
+        pooled[k] = out
+    return vd_derived(pooled)
