@@ -379,6 +379,30 @@ int insider_hip_variance_decomposition(insider_hip_handle *h, double *const *A, 
 int insider_hip_sample_decomposition(insider_hip_handle *h, double *const *A, const double *C, int inc_continuous, int K,
                                      int entries, double *out);
 
+/*
+ * Per-factor decomposition of a fitted model on the resident data set: the record of
+ * insider_hip_variance_decomposition() split along the K latent factors.  Blocks b = 0..B-1 (B = c + inc_continuous) have the
+ * per-sample embeddings u_b(i) in R^K (A_b[level_b(i)] for a categorical block, z_i B_c for the continuous one); one more
+ * block b = B, the total, has u_B(i) = sum_b u_b(i), row i of the row factor.  Factor k contributes
+ * h_{b,k}(i, j) = u_b(i)[k] C[k][j] through block b; the fit is f = sum_k h_{B,k} and r = x - f.  S_j, A, C, entries as in
+ * insider_hip_variance_decomposition().
+ * out: p records of 4 + 3 (B + 1) K doubles, record j at out + j (4 + 3 (B + 1) K): n_j = |S_j|, sum x, sum x^2, sum r^2
+ * (formed from r itself), then for b = 0..B, k = 0..K-1 at 4 + 3 (b K + k): sum h_{b,k}, sum h_{b,k}^2, sum r h_{b,k}.  All
+ * sums run over S_j.  The total's sum h and sum r h are the sums of the blocks' slots in block order; its sum h^2 is formed
+ * from u_B itself (it carries the cross terms between blocks).  A factor whose row of C is zero has slots that are 0.
+ * Arguments, status codes and scope as in the post-hoc calls above (K 1..63, the same inc_continuous rules; entries outside
+ * 0..2 and a null out return INSIDER_ERR_ARG, a sharded handle returns INSIDER_ERR_UNSUPPORTED).  Works on clones and
+ * re-masked handles, on the handle's main stream, in the post-hoc workspace: an optimize() after it is bit-identical to one
+ * without.  Per gene the device forms (M_j .* r_j)' W, M_j' W and M_j' (W .* W) against W = [U_0 | ... | U_B] on the f64
+ * matrix instruction: a heavy pass over X and the mask codes (the fit of a tile from the same instruction) and a light pass
+ * over the codes alone, each in windows of at most 128 columns of W.  Every sum runs in a fixed order without atomics:
+ * repeated calls on the same device give bit-identical records.  insider_hip_get_info("fd_path") tells the form of the heavy
+ * pass of the last call: 1 = the B K columns fit one window (X is read once), 2 = several windows (X is read once per window
+ * of 128 columns).
+ */
+int insider_hip_factor_decomposition(insider_hip_handle *h, double *const *A, const double *C, int inc_continuous, int K,
+                                     int entries, double *out);
+
 /* Profile of the last insider_hip_optimize() call (option "profile" = 1), HIP-event timed on the library's stream.
  * out[0..11]: {column-side masked-Gram launches, total ms, row-side masked-Gram launches, total ms,
  *  column-solve (CD / ridge) launches, total ms, test-residual launches, total ms,
@@ -410,6 +434,8 @@ int insider_hip_get_profile(insider_hip_handle *h, double *out12);
  * global memory; 0 = none yet),
  * "sd_path" / "sd_slabs" (of the last insider_hip_sample_decomposition(): the form of k_sd_stats, 1 = level tables in LDS, 2 =
  * read from global memory, 0 = none yet; and the gene slabs its grid had),
+ * "fd_path" (the form of the heavy pass of the last insider_hip_factor_decomposition(): 1 = one column window, X read once;
+ * 2 = several windows of 128 columns of W, X read once per window; 0 = none yet),
  * "row_kernels" (a bit mask of the row-phase kernel forms the last optimize() / optimize_row() launched, reset at the start of
  * each; set on the host at each launch site.  Level Gram sums: bit 0 wgemm4, 1 wgemm5, 2 wgemm6, 3 wgemm7 (k_wgemm<LT>),
  * 4 wgemm_chunks (a k_wgemm launch with more than one level-tile chunk, grid.z > 1), 5 wsyrk (k_wsyrk<NB>; neither wsyrk nor a

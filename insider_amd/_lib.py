@@ -28,7 +28,7 @@ SYMBOLS = (
     "insider_hip_comm_unique_id", "insider_hip_comm_init", "insider_hip_get_array", "insider_hip_clone",
     "insider_hip_optimize_continuous_v2", "insider_hip_residual", "insider_hip_interaction_glm",
     "insider_hip_variance_decomposition", "insider_hip_sample_decomposition", "insider_hip_col_stats", "insider_hip_last_cd_solver",
-    "insider_hip_remask", "insider_hip_set_folds", "insider_hip_remask_fold",
+    "insider_hip_remask", "insider_hip_set_folds", "insider_hip_remask_fold", "insider_hip_factor_decomposition",
 )
 COMM_ID_BYTES = 128
 # insider_hip_get_info("col_solver" / "col_eval") and insider_hip_last_cd_solver(): the column-solve kernel behind each code
@@ -129,6 +129,7 @@ def load():
                                                 dp, dp]
     lib.insider_hip_variance_decomposition.argtypes = [C.c_void_p, C.POINTER(dp), dp, C.c_int, C.c_int, C.c_int, dp]
     lib.insider_hip_sample_decomposition.argtypes = [C.c_void_p, C.POINTER(dp), dp, C.c_int, C.c_int, C.c_int, dp]
+    lib.insider_hip_factor_decomposition.argtypes = [C.c_void_p, C.POINTER(dp), dp, C.c_int, C.c_int, C.c_int, dp]
     lib.insider_hip_get_profile.argtypes = [C.c_void_p, dp]
     lib.insider_hip_get_sweeps.argtypes = [C.c_void_p, i32p]
     lib.insider_hip_last_cd_ms.restype = C.c_double

@@ -315,6 +315,27 @@ class InsiderData:
         return dict(n=out[:, 0].copy(), sum_x=out[:, 1].copy(), sum_xx=out[:, 2].copy(), rss=out[:, 3].copy(),
                     sum_g=blk[:, :, 0].T.copy(), sum_gg=blk[:, :, 1].T.copy(), sum_rg=blk[:, :, 2].T.copy())
 
+    def factor_decomposition(self, cfd_factors, column_factor, entries="train", inc_continuous=0):
+        """Per-gene sums of the per-factor decomposition (insider_hip_factor_decomposition) over the entries ``entries`` of
+        every gene: variance_decomposition() split along the K latent factors.  A dict of ``n``, ``sum_x``, ``sum_xx``,
+        ``rss`` (length p) and ``sum_h``, ``sum_hh``, ``sum_rh`` ((B + 1) x K x p: block b = covariate b, then the continuous
+        block, then the total, whose embedding is the row factor).  posthoc.fd_derived() turns them into r2 / rmse /
+        explained / drop_one per (block, factor, gene), posthoc.factor_summary() pools the genes."""
+        if entries not in self.VD_ENTRIES:
+            raise InsiderError(_lib.ERR_ARG, f"entries must be one of {sorted(self.VD_ENTRIES)}, got {entries!r}")
+        if inc_continuous not in (0, 1):
+            raise InsiderError(_lib.ERR_ARG, "The value of prarameter inc_continuous can only be 0 or 1.")
+        K = int(np.asarray(column_factor).shape[0])
+        A, Cw, Aptrs = self._marshal(cfd_factors, column_factor, K, inc_continuous)
+        nb = self.c + int(inc_continuous)
+        out = np.empty((self.p, 4 + 3 * (nb + 1) * K), dtype=np.float64)
+        _lib.check(_lib.load().insider_hip_factor_decomposition(self._h, Aptrs, _lib.ptr(Cw), int(inc_continuous), K,
+                                                                self.VD_ENTRIES[entries], _lib.ptr(out)))
+        blk = out[:, 4:].reshape(self.p, nb + 1, K, 3)
+        return dict(n=out[:, 0].copy(), sum_x=out[:, 1].copy(), sum_xx=out[:, 2].copy(), rss=out[:, 3].copy(),
+                    sum_h=blk[..., 0].transpose(1, 2, 0).copy(), sum_hh=blk[..., 1].transpose(1, 2, 0).copy(),
+                    sum_rh=blk[..., 2].transpose(1, 2, 0).copy())
+
     def masked_gram_cols(self, R):
         R = _lib.f64(R)
         K = R.shape[1]

@@ -9,6 +9,7 @@
 #include "insider_posthoc.hpp"
 #include "insider_vardecomp.hpp"
 #include "insider_sampdecomp.hpp"
+#include "insider_factdecomp.hpp"
 
 #include <rccl/rccl.h>
 
@@ -398,6 +399,9 @@ struct PostWs {
     DevBuf<double> vin, vtab, vrec;
     // sample decomposition: spart = the slabs' partial records (slabs x n x (4 + 3 BW)); srec = the n records
     DevBuf<double> spart, srec;
+    // factor decomposition: fwall = [W | W .* W] (padded rows x 2 ldq); fprod = the p rows [P1 | P2 | P3]; fbase = the p base
+    // slots; frec = the p records
+    DevBuf<double> fwall, fprod, fbase, frec;
 };
 
 }  // namespace
@@ -443,6 +447,7 @@ struct insider_hip_handle {
     int vd_path = 0;
     // the form the last sample decomposition ran (1 = tables in LDS, 2 = from global) and its gene slabs
     int sd_path = 0, sd_slabs = 0;
+    int fd_path = 0;
 
     // work still in flight is drained and the communicator closed before the members free their buffers (the data set with
     // its last handle)
@@ -3248,6 +3253,7 @@ int insider_hip_get_info(insider_hip_handle *h, const char *name, double *out)
     else if (s == "vd_path") *out = h->vd_path;                     // last variance decomposition: 1 = level tables in LDS, 2 = read from global
     else if (s == "sd_path") *out = h->sd_path;                     // last sample decomposition: 1 = level tables in LDS, 2 = read from global
     else if (s == "sd_slabs") *out = h->sd_slabs;                   // ... and its gene slabs
+    else if (s == "fd_path") *out = h->fd_path;                     // last factor decomposition: 1 = one column window (X read once), 2 = several
     else if (s == "col_mfma_per_gene") {
         // v_mfma_f64_16x16x4_f64 instructions the column-side statistics kernel issues per gene (2048 flops each; the 4x4x4 form
         // of the per-entry kernel is counted in the same unit: a quarter per instruction)
@@ -3690,6 +3696,88 @@ int sample_decomposition_body(insider_hip_handle *h, double *const *A, const dou
     return INSIDER_OK;
 }
 
+// ---- factor decomposition (kernels: insider_factdecomp.hpp) ----------------------------------------------------------
+// Wall = [W | W .* W] from the packed row factors, then the heavy pass over X and the codes (P1 and the base slots, the
+// B K columns of the covariate blocks in windows of FD_QT tiles of 16), the light pass over the codes (P2, P3, every
+// column) and k_fd_finish
+constexpr int FD_QT = 8;   // tiles of 16 columns per window at most (64 accumulator registers)
+
+int factor_decomposition_body(insider_hip_handle *h, double *const *A, const double *C, int inc_continuous, int K,
+                              int entries, double *out)
+{
+    int rc = vd_check(h, A, C, inc_continuous, K, entries, out);
+    if (rc) return rc;
+    HIPCHECK(hipSetDevice(h->ds->device));
+    PostWs &w = h->post;
+    hipStream_t st = h->st.stream;
+    const DataSet &d = *h->ds;
+    const int nb = d.c + inc_continuous, SL = d.SL, KPW = 16 * ((K + 15) / 16), KS = KPW / 16;
+    const int rec = 4 + 3 * (nb + 1) * K;
+    const int64_t n = d.n, p = d.p;
+    const int ldq = (int)round_up((int64_t)(nb + 1) * K, 16), ldw = 2 * ldq, ldp = 3 * ldq;
+    const int64_t rows = round_up(n, FD_CHUNK);
+    if ((rc = w.vin.grow((size_t)(SL + p) * K)) || (rc = w.Ast.grow((size_t)SL * KPW)) ||
+        (rc = w.fwall.grow((size_t)rows * ldw)) || (rc = w.fprod.grow((size_t)p * ldp)) || (rc = w.fbase.grow((size_t)p * 4)) ||
+        (rc = w.frec.grow((size_t)p * rec)))
+        return rc;
+    double *vin = w.vin, *Ast = w.Ast, *Wall = w.fwall, *P = w.fprod, *base = w.fbase, *R = w.frec;
+    // [A_stack; B_c] as SL rows of KPW, C as p rows of K (the layout of vd_build_table)
+    for (int b = 0; b < nb; ++b) {
+        const DataSet::Block blk = d.block(b);
+        HIPCHECK(hipMemcpyAsync(vin + (size_t)blk.off * K, A[b], (size_t)blk.rows * K * sizeof(double), hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_pack_A, dim3(cdiv((int64_t)blk.rows * KPW, 256)), dim3(256), 0, st,
+                           (const double *)(vin + (size_t)blk.off * K), blk.rows, K, KPW, Ast + (size_t)blk.off * KPW);
+        KCHECK();
+    }
+    double *Cd = vin + (size_t)SL * K;
+    HIPCHECK(hipMemcpyAsync(Cd, C, (size_t)p * K * sizeof(double), hipMemcpyHostToDevice, st));
+    const int m = inc_continuous ? d.m : 0;
+    HIPCHECK(hipMemsetAsync(Wall, 0, (size_t)rows * ldw * sizeof(double), st));
+    hipLaunchKernelGGL(k_fd_build_w, dim3(cdiv(n * K, 256)), dim3(256), 0, st, (const int *)d.lev, (const int *)d.lvl_off_d, d.c,
+                       (int)n, (const double *)Ast, KPW, (const double *)d.Zc, m, d.SLcat, K, ldq, Wall);
+    KCHECK();
+    const int sel = entries == 0 ? 0 : entries == 1 ? CODE_TRAIN : CODE_TEST;
+    const int heavy_tiles = cdiv(nb * K, 16), light_tiles = ldw / 16;
+    h->fd_path = heavy_tiles <= FD_QT ? 1 : 2;
+    const dim3 grid((unsigned)cdiv(p, (int64_t)FD_GENES)), block(64 * FD_WAVES);
+#define FD_LAUNCH(QT_, KS_)                                                                                                 \
+    do {                                                                                                                     \
+        const size_t lw = (size_t)FD_CHUNK * (16 * QT_ + 4) * sizeof(double);                                                \
+        const size_t lr = (size_t)FD_CHUNK * (16 * KS_ + 2) * sizeof(double);                                                \
+        for (int t0 = 0; t0 < heavy_tiles; t0 += QT_) {                                                                      \
+            hipLaunchKernelGGL((k_fd_prod<QT_, KS_, true>), grid, block, lw + lr, st, (const double *)d.X,                   \
+                               (const uint8_t *)d.codes, d.ldn, (int)n, p, (const double *)Wall, ldw, 16 * t0,               \
+                               std::min(QT_, heavy_tiles - t0), nb * K, (const double *)Cd, K, sel, P, ldp, 16 * t0, base);  \
+            KCHECK();                                                                                                        \
+        }                                                                                                                    \
+        for (int t0 = 0; t0 < light_tiles; t0 += QT_) {                                                                      \
+            hipLaunchKernelGGL((k_fd_prod<QT_, 1, false>), grid, block, lw, st, (const double *)d.X,                         \
+                               (const uint8_t *)d.codes, d.ldn, (int)n, p, (const double *)Wall, ldw, 16 * t0,               \
+                               std::min(QT_, light_tiles - t0), 0, (const double *)Cd, K, sel, P, ldp, ldq + 16 * t0,        \
+                               (double *)nullptr);                                                                           \
+            KCHECK();                                                                                                        \
+        }                                                                                                                    \
+    } while (0)
+#define FD_LAUNCH_KS(QT_)                                                                                                   \
+    switch (KS) {                                                                                                            \
+        case 1: FD_LAUNCH(QT_, 1); break;                                                                                    \
+        case 2: FD_LAUNCH(QT_, 2); break;                                                                                    \
+        case 3: FD_LAUNCH(QT_, 3); break;                                                                                    \
+        default: FD_LAUNCH(QT_, 4); break;                                                                                   \
+    }
+    // one window width for every shape: the form with 8 tiles needs 132 - 157 registers (three blocks per compute unit); tiles
+    // beyond the live ones of a window are skipped by a uniform branch
+    FD_LAUNCH_KS(FD_QT)
+#undef FD_LAUNCH_KS
+#undef FD_LAUNCH
+    hipLaunchKernelGGL(k_fd_finish, dim3(cdiv(p * K, 256)), dim3(256), 0, st, (const double *)P, ldq, (const double *)base,
+                       (const double *)Cd, p, K, nb, R);
+    KCHECK();
+    HIPCHECK(hipMemcpyAsync(out, R, (size_t)p * rec * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipStreamSynchronize(st));
+    return INSIDER_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -3717,6 +3805,12 @@ int insider_hip_sample_decomposition(insider_hip_handle *h, double *const *A, co
                                      int entries, double *out)
 {
     return ph_finish(h, sample_decomposition_body(h, A, C, inc_continuous, K, entries, out));
+}
+
+int insider_hip_factor_decomposition(insider_hip_handle *h, double *const *A, const double *C, int inc_continuous, int K,
+                                     int entries, double *out)
+{
+    return ph_finish(h, factor_decomposition_body(h, A, C, inc_continuous, K, entries, out));
 }
 
 }  // extern "C"

@@ -8,6 +8,7 @@
     ... --interaction 1 2 --interaction-glm 1   # then glm_interaction() on the device for covariate column 1 (0-based)
     ... --variance-decomposition                # then the per-gene variance decomposition on the device
     ... --sample-decomposition                  # then the per-sample and per-level fit diagnostics on the device
+    ... --factor-decomposition                  # then the per-factor decomposition (which factor, through which covariate)
 
 Semantics are those of insider_amd.api (the mirror of R/insider.R): with masks given, `--partition 1` fits on the
 train entries (optimize(tuning = 1)) and reports the test RMSE; without masks (or `--partition 0`) every non-NA entry is
@@ -16,7 +17,10 @@ used (fit()'s default, R/insider.R:190-216; NaN entries of X are the NA set).  I
 on the device against the residual of every other block); --variance-decomposition adds vd_r2 / vd_rmse (p) and
 vd_explained / vd_drop_one (B x p, posthoc.vd_derived) over the entries the fit used; --sample-decomposition adds the same per
 sample, sd_r2 / sd_rmse (n) and sd_explained / sd_drop_one (B x n), and per level of every categorical covariate b,
-sd_level<b>_r2 / sd_level<b>_rmse (L_b, posthoc.level_decomposition).  Output: A<i> (L_i x K), C (K x p) and result.json {train_rmse, test_rmse, loss,
+sd_level<b>_r2 / sd_level<b>_rmse (L_b, posthoc.level_decomposition); --factor-decomposition adds the tables pooled over genes
+fd_summary_explained / fd_summary_drop_one ((B + 1) x K, the last block the total; posthoc.factor_summary), fd_order (the
+factors by descending pooled drop_one of the total) and per gene fd_explained / fd_drop_one (p x (B + 1) K, block-major
+columns).  Output: A<i> (L_i x K), C (K x p) and result.json {train_rmse, test_rmse, loss,
 iters, traj} in --out.  There is no CPU fallback: without a visible MI355X the command fails with the library's status.
 """
 import argparse
@@ -70,6 +74,10 @@ def parse(argv=None):
                     help="after the fit, the per-sample fit diagnostics on the device over the entries the fit used; writes "
                          "sd_r2, sd_rmse (n), sd_explained, sd_drop_one (blocks x n) and, per categorical covariate b, "
                          "sd_level<b>_r2, sd_level<b>_rmse (its levels) next to the factors")
+    ap.add_argument("--factor-decomposition", action="store_true",
+                    help="after the fit, the per-factor decomposition on the device over the entries the fit used; writes "
+                         "fd_summary_explained, fd_summary_drop_one ((blocks + 1) x K), fd_order (K) and fd_explained, "
+                         "fd_drop_one (p x (blocks + 1) K, block-major columns) next to the factors")
     a = ap.parse_args(argv)
     if not a.flat and not (a.x and a.levels):
         ap.error("give --flat DIR or --x and --levels")
@@ -182,6 +190,14 @@ def main(argv=None):
         for b in range(ds.c):
             lv = level_decomposition(rec, ds_levels[:, b], int(ds.n_levels[b]))
             vd[f"sd_level{b}_r2"], vd[f"sd_level{b}_rmse"] = lv["r2"], lv["rmse"]
+    if a.factor_decomposition:
+        from .posthoc import factor_summary, fd_derived
+        rec = ds.factor_decomposition(list(res["row_matrices"].values()), res["column_factor"], entries="train",
+                                      inc_continuous=1 if Z is not None else 0)
+        d, fs = fd_derived(rec), factor_summary(rec)
+        vd = dict(vd or {}, fd_summary_explained=fs["explained"], fd_summary_drop_one=fs["drop_one"],
+                  fd_order=fs["order"].astype(np.float64), fd_explained=d["explained"].reshape(-1, p).T,
+                  fd_drop_one=d["drop_one"].reshape(-1, p).T)
     ds.close()
     summary = dict(train_rmse=res["train_rmse"], test_rmse=None if np.isnan(res["test_rmse"]) else res["test_rmse"],
                    loss=res["loss"], iters=res["iters"], rank=K, **{"lambda": a.lam}, alpha=a.alpha, partition=partition,

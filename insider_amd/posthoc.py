@@ -18,6 +18,10 @@ sample_decomposition() is the same record per sample instead of per gene (Inside
 model fits each sample, which samples are outliers, what each block carries of a sample's variance), with
 sample_decomposition_host() as its yardstick; level_decomposition() pools the samples of each level of a covariate
 (per donor, per tissue).
+
+factor_decomposition() splits the per-gene record along the K latent factors (InsiderData.factor_decomposition: which
+factors matter, which covariate drives factor k, in which genes it acts), with factor_decomposition_host() as its
+yardstick, fd_derived() for the per-gene shares and factor_summary() for the (B + 1) x K tables pooled over genes.
 """
 import numpy as np
 
@@ -184,3 +188,79 @@ def level_decomposition(rec, level_ids, n_levels):
         np.add.at(out.reshape(-1, L).T, ids, v.reshape(-1, ids.size).T)
         pooled[k] = out
     return vd_derived(pooled)
+
+
+def factor_decomposition_host(X, levels, ctns, mask, A, C):
+    """The per-factor record in plain numpy (the yardstick of InsiderData.factor_decomposition); arguments as in
+    variance_decomposition_host().  Blocks: the categorical covariates, the continuous block when ctns is given, then the
+    total (the sum of the blocks' embeddings: the row factor).  Loops over the blocks and k: no n x p x K array is formed.
+    -> fd_derived() of the raw sums n, sum_x, sum_xx, rss (p) and sum_h, sum_hh, sum_rh ((B + 1) x K x p)."""
+    X = np.asarray(X, dtype=np.float64)
+    Cm = np.asarray(C, dtype=np.float64)
+    lev = np.asarray(levels).reshape(X.shape[0], -1)
+    c = lev.shape[1]
+    U = [np.asarray(A[b], dtype=np.float64)[lev[:, b].astype(np.int64) - 1] for b in range(c)]
+    if ctns is not None:
+        U.append(np.asarray(ctns, dtype=np.float64).reshape(X.shape[0], -1) @ np.asarray(A[c], dtype=np.float64))
+    tot = np.zeros_like(U[0])
+    for u in U:
+        tot = tot + u
+    U.append(tot)
+    K, p = Cm.shape
+    w = np.ones(X.shape, dtype=bool) if mask is None else np.asarray(mask).astype(bool)
+    r = np.where(w, X - tot @ Cm, 0.0)
+    xs = np.where(w, X, 0.0)
+    sum_h, sum_hh, sum_rh = (np.zeros((len(U), K, p)) for _ in range(3))
+    for b, u in enumerate(U):
+        for k in range(K):
+            h = np.where(w, np.outer(u[:, k], Cm[k]), 0.0)
+            sum_h[b, k], sum_hh[b, k], sum_rh[b, k] = h.sum(axis=0), (h * h).sum(axis=0), (r * h).sum(axis=0)
+    return fd_derived(dict(n=w.sum(axis=0).astype(np.float64), sum_x=xs.sum(axis=0), sum_xx=(xs * xs).sum(axis=0),
+                           rss=(r * r).sum(axis=0), sum_h=sum_h, sum_hh=sum_hh, sum_rh=sum_rh))
+
+
+def fd_derived(rec):
+    """The raw per-gene sums of a factor decomposition plus tss, r2, rmse as in vd_derived() and, per (block, factor, gene),
+        explained[b, k] = (sum h^2 - (sum h)^2 / n) / tss   (the share of the gene's variance factor k carries through b),
+        drop_one[b, k] = (sum h^2 + 2 sum r h) / tss         (the rise in RSS, over tss, when that term leaves the fit).
+    A gene with n = 0 gets NaN in every derived value."""
+    out = {k: np.asarray(v, dtype=np.float64) for k, v in rec.items()}
+    n = out["n"]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        nn = np.where(n > 0, n, np.nan)
+        tss = out["sum_xx"] - out["sum_x"] ** 2 / nn
+        out["tss"] = tss
+        out["r2"] = 1.0 - out["rss"] / tss
+        out["rmse"] = np.sqrt(out["rss"] / nn)
+        out["explained"] = (out["sum_hh"] - out["sum_h"] ** 2 / nn) / tss
+        out["drop_one"] = (out["sum_hh"] + 2.0 * out["sum_rh"]) / tss
+    return out
+
+
+def factor_summary(rec, column_factor=None):
+    """The (B + 1) x K tables of a factor decomposition pooled over genes: the numerators of fd_derived()'s explained and
+    drop_one summed over the genes with n > 0, over the sum of their tss.  -> dict of ``explained``, ``drop_one``
+    ((B + 1) x K), ``tss`` (the denominator), ``order`` (the factors by descending pooled drop_one of the total block) and,
+    with ``column_factor`` (K x p) given, ``loading_nnz`` (the non-zero loadings of every factor)."""
+    d = fd_derived({k: rec[k] for k in ("n", "sum_x", "sum_xx", "rss", "sum_h", "sum_hh", "sum_rh")})
+    live = d["n"] > 0
+    nn = d["n"][live]
+    tss = float(d["tss"][live].sum())
+    sh, shh, srh = (d[k][:, :, live] for k in ("sum_h", "sum_hh", "sum_rh"))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        out = dict(explained=(shh - sh ** 2 / nn).sum(axis=2) / tss, drop_one=(shh + 2.0 * srh).sum(axis=2) / tss, tss=tss)
+    out["order"] = np.argsort(-out["drop_one"][-1], kind="stable")
+    if column_factor is not None:
+        out["loading_nnz"] = np.count_nonzero(np.asarray(column_factor), axis=1)
+    return out
+
+
+def factor_decomposition(obj, which="fit", entries="train"):
+    """Per-factor decomposition of a fitted ``Insider`` object on the device, with the ``which`` / ``entries`` of
+    variance_decomposition().  -> fd_derived() of the raw sums: n, sum_x, sum_xx, rss, tss, r2, rmse (p), sum_h, sum_hh,
+    sum_rh, explained, drop_one ((B + 1) x K x p; the last block is the total)."""
+    from . import api
+    ds = api._resident(obj, which)
+    rec = ds.factor_decomposition(list(obj["cfd_matrices"].values()), obj["column_factor"], entries=entries,
+                                  inc_continuous=int(obj["inc_continuous"]))
+    return fd_derived(rec)
