@@ -403,6 +403,39 @@ int insider_hip_sample_decomposition(insider_hip_handle *h, double *const *A, co
 int insider_hip_factor_decomposition(insider_hip_handle *h, double *const *A, const double *C, int inc_continuous, int K,
                                      int entries, double *out);
 
+/*
+ * Aberrant entries of a fitted model on the resident data set: the (sample, gene) entries whose standardised residual the
+ * model cannot explain.  Blocks, g_b(i,j), f = sum_b g_b (in block order), r = x - f, x, the meaning of entries (0 all / 1 train
+ * bit / 2 test bit) and S_j are exactly those of insider_hip_variance_decomposition().
+ * Standardised residual: z_ij = (r_ij - center_j) / scale_j.  center holds p doubles (NULL = 0), scale holds p doubles and is
+ * required; a gene whose scale is not finite or not > 0 yields no call (not an error).  posthoc.residual_center_scale() derives
+ * both from a variance-decomposition record.
+ * Call: an entry in S_j with |z_ij| >= threshold; it is low when z < 0 and high when z > 0.  threshold must be finite and > 0.
+ * Counts: *total = the number of calls (always written on success); gene_counts = p pairs {low, high}, sample_counts = n pairs
+ * {low, high}; either may be NULL, and when present both are complete whatever cap is.
+ * List: rows[t], cols[t] (0-based sample and gene) and z[t] hold the calls in ascending gene, then ascending sample.  Only the
+ * first min(total, cap) calls are written and nothing beyond them.  cap = 0 with NULL list pointers is the counts-only form;
+ * cap < 0, and cap > 0 with any NULL list pointer, return INSIDER_ERR_ARG.  total > cap is not an error: the caller compares
+ * the two (and may call again with cap = total).
+ * Arguments, status codes and scope as in the post-hoc calls above: K 1..63 (K > 63 returns INSIDER_ERR_UNSUPPORTED), the same
+ * inc_continuous rules; entries outside 0..2, a NULL scale or a NULL total return INSIDER_ERR_ARG; a sharded handle returns
+ * INSIDER_ERR_UNSUPPORTED.  No output is written when a status other than INSIDER_OK is returned for an argument.  Works on
+ * clones and re-masked handles, on the handle's main stream, in the post-hoc workspace: an optimize() after it is bit-identical
+ * to one without.
+ * The device builds the level table, then makes one streaming pass over X and the mask codes that forms z per entry and writes
+ * a bitmap of the calls (one bit per entry, n p / 8 bytes) and the per-gene counts; an exclusive scan of the genes' totals gives
+ * 64-bit list offsets; a second pass reads the bitmap, not X, and for set bits only forms z again through the same device
+ * function and stores the call at its offset + rank.  Membership is decided once, in the first pass, so the list of a gene is
+ * exactly as long as its count.  The per-sample counts are integer atomics; everything else runs in a fixed order: repeated
+ * calls on one device return identical bits for the list, the z values and the counts.  insider_hip_get_info("ol_path") tells
+ * which form of the first pass the last call ran (1 = level tables staged in LDS, 2 = read from global memory; option
+ * "vd_stage_kb", as for "vd_path").
+ */
+int insider_hip_outliers(insider_hip_handle *h, double *const *A, const double *C, int inc_continuous, int K,
+                         int entries, const double *center, const double *scale, double threshold,
+                         int64_t cap, int32_t *rows, int32_t *cols, double *z, int64_t *total,
+                         int32_t *gene_counts, int32_t *sample_counts);
+
 /* Profile of the last insider_hip_optimize() call (option "profile" = 1), HIP-event timed on the library's stream.
  * out[0..11]: {column-side masked-Gram launches, total ms, row-side masked-Gram launches, total ms,
  *  column-solve (CD / ridge) launches, total ms, test-residual launches, total ms,
@@ -436,6 +469,8 @@ int insider_hip_get_profile(insider_hip_handle *h, double *out12);
  * read from global memory, 0 = none yet; and the gene slabs its grid had),
  * "fd_path" (the form of the heavy pass of the last insider_hip_factor_decomposition(): 1 = one column window, X read once;
  * 2 = several windows of 128 columns of W, X read once per window; 0 = none yet),
+ * "ol_path" (the form of k_ol_flag the last insider_hip_outliers() ran: 1 = level tables in LDS, 2 = read from global memory;
+ * 0 = none yet),
  * "row_kernels" (a bit mask of the row-phase kernel forms the last optimize() / optimize_row() launched, reset at the start of
  * each; set on the host at each launch site.  Level Gram sums: bit 0 wgemm4, 1 wgemm5, 2 wgemm6, 3 wgemm7 (k_wgemm<LT>),
  * 4 wgemm_chunks (a k_wgemm launch with more than one level-tile chunk, grid.z > 1), 5 wsyrk (k_wsyrk<NB>; neither wsyrk nor a

@@ -29,8 +29,13 @@ SYMBOLS = (
     "insider_hip_optimize_continuous_v2", "insider_hip_residual", "insider_hip_interaction_glm",
     "insider_hip_variance_decomposition", "insider_hip_sample_decomposition", "insider_hip_col_stats", "insider_hip_last_cd_solver",
     "insider_hip_remask", "insider_hip_set_folds", "insider_hip_remask_fold", "insider_hip_factor_decomposition",
+    "insider_hip_outliers",
 )
 COMM_ID_BYTES = 128
+# insider_hip_outliers (insider_amd/csrc/insider_outliers.hpp): the samples a block of k_ol_flag covers per trip (OL_TRIP) and the
+# genes k_ol_scan takes per step (OL_SCAN_CHUNK): the sizes at which the kernels change path
+OL_TRIP = 1024
+OL_SCAN_CHUNK = 1024
 # insider_hip_get_info("col_solver" / "col_eval") and insider_hip_last_cd_solver(): the column-solve kernel behind each code
 # (include/insider_hip.h)
 COL_SOLVERS = ("none", "ridge_reg", "ridge", "cd_reg", "cd_reg3", "cd_cols16", "cd_cols32", "cd_cols64", "cd_r16_1", "cd_r16_2",
@@ -130,6 +135,8 @@ def load():
     lib.insider_hip_variance_decomposition.argtypes = [C.c_void_p, C.POINTER(dp), dp, C.c_int, C.c_int, C.c_int, dp]
     lib.insider_hip_sample_decomposition.argtypes = [C.c_void_p, C.POINTER(dp), dp, C.c_int, C.c_int, C.c_int, dp]
     lib.insider_hip_factor_decomposition.argtypes = [C.c_void_p, C.POINTER(dp), dp, C.c_int, C.c_int, C.c_int, dp]
+    lib.insider_hip_outliers.argtypes = [C.c_void_p, C.POINTER(dp), dp, C.c_int, C.c_int, C.c_int, dp, dp, C.c_double, C.c_int64,
+                                         i32p, i32p, dp, C.POINTER(C.c_int64), i32p, i32p]
     lib.insider_hip_get_profile.argtypes = [C.c_void_p, dp]
     lib.insider_hip_get_sweeps.argtypes = [C.c_void_p, i32p]
     lib.insider_hip_last_cd_ms.restype = C.c_double

@@ -336,6 +336,55 @@ class InsiderData:
                     sum_h=blk[..., 0].transpose(1, 2, 0).copy(), sum_hh=blk[..., 1].transpose(1, 2, 0).copy(),
                     sum_rh=blk[..., 2].transpose(1, 2, 0).copy())
 
+    def outliers(self, cfd_factors, column_factor, scale, center=None, threshold=3.0, entries="train", inc_continuous=0,
+                 cap=None):
+        """The aberrant entries of a fitted model (insider_hip_outliers): the entries ``entries`` whose standardised residual
+        z = (x - f - center[j]) / scale[j] has |z| >= ``threshold`` (``scale``, ``center``: length p, center None = 0; a gene
+        whose scale is not finite or not > 0 gives no call).  A dict of ``rows``, ``cols`` (0-based sample and gene, int32),
+        ``z`` (the calls in ascending gene, then ascending sample), ``total`` (the number of calls) and the complete counts
+        ``gene_low``, ``gene_high`` (p), ``sample_low``, ``sample_high`` (n).  ``cap`` bounds the list: None = one call with a
+        capacity of max(2^20, n p / 64) and, when ``total`` exceeds it, a second one with cap = total (the whole list); an
+        integer = the first ``cap`` calls (compare ``total`` with it); 0 = counts only.
+        posthoc.residual_center_scale() derives center and scale from a variance-decomposition record."""
+        if entries not in self.VD_ENTRIES:
+            raise InsiderError(_lib.ERR_ARG, f"entries must be one of {sorted(self.VD_ENTRIES)}, got {entries!r}")
+        if inc_continuous not in (0, 1):
+            raise InsiderError(_lib.ERR_ARG, "The value of prarameter inc_continuous can only be 0 or 1.")
+        if scale is None:
+            raise InsiderError(_lib.ERR_ARG, "scale is required")
+        if cap is not None and (int(cap) != cap or cap < 0):
+            raise InsiderError(_lib.ERR_ARG, "cap must be None or an integer >= 0")
+        K = int(np.asarray(column_factor).shape[0])
+        A, Cw, Aptrs = self._marshal(cfd_factors, column_factor, K, inc_continuous)
+        sc = np.ascontiguousarray(np.asarray(scale, dtype=np.float64).ravel())
+        ce = None if center is None else np.ascontiguousarray(np.asarray(center, dtype=np.float64).ravel())
+        if sc.shape != (self.p,) or (ce is not None and ce.shape != (self.p,)):
+            raise InsiderError(_lib.ERR_ARG, f"scale and center must hold p = {self.p} values")
+        gene = np.empty((self.p, 2), dtype=np.int32)
+        samp = np.empty((self.n, 2), dtype=np.int32)
+        total = C.c_int64()
+        lib = _lib.load()
+
+        def call(capacity):
+            rows, cols = np.empty(capacity, dtype=np.int32), np.empty(capacity, dtype=np.int32)
+            z = np.empty(capacity, dtype=np.float64)
+            lists = (_lib.ptr(rows, C.c_int32), _lib.ptr(cols, C.c_int32), _lib.ptr(z)) if capacity else (None, None, None)
+            _lib.check(lib.insider_hip_outliers(self._h, Aptrs, _lib.ptr(Cw), int(inc_continuous), K,
+                                                self.VD_ENTRIES[entries], None if ce is None else _lib.ptr(ce), _lib.ptr(sc),
+                                                float(threshold), capacity, *lists, C.byref(total),
+                                                _lib.ptr(gene, C.c_int32), _lib.ptr(samp, C.c_int32)))
+            return rows, cols, z
+
+        capacity = max(1 << 20, self.n * self.p // 64) if cap is None else int(cap)
+        rows, cols, z = call(capacity)
+        if cap is None and total.value > capacity:
+            capacity = int(total.value)
+            rows, cols, z = call(capacity)
+        k = min(int(total.value), capacity)
+        return dict(rows=rows[:k].copy(), cols=cols[:k].copy(), z=z[:k].copy(), total=int(total.value),
+                    gene_low=gene[:, 0].copy(), gene_high=gene[:, 1].copy(), sample_low=samp[:, 0].copy(),
+                    sample_high=samp[:, 1].copy())
+
     def masked_gram_cols(self, R):
         R = _lib.f64(R)
         K = R.shape[1]

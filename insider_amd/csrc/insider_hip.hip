@@ -10,6 +10,7 @@
 #include "insider_vardecomp.hpp"
 #include "insider_sampdecomp.hpp"
 #include "insider_factdecomp.hpp"
+#include "insider_outliers.hpp"
 
 #include <rccl/rccl.h>
 
@@ -402,6 +403,12 @@ struct PostWs {
     // factor decomposition: fwall = [W | W .* W] (padded rows x 2 ldq); fprod = the p rows [P1 | P2 | P3]; fbase = the p base
     // slots; frec = the p records
     DevBuf<double> fwall, fprod, fbase, frec;
+    // outlier calls: ocs = center (p; unused without one) then scale (p); obits = the bitmap of flagged entries (p x ldn / 32
+    // words); ogcnt / oscnt = the p / n pairs {low, high}; ooffs = the p + 1 list offsets; orows / ocols / oz = the list
+    DevBuf<double> ocs, oz;
+    DevBuf<uint32_t> obits;
+    DevBuf<int> ogcnt, oscnt, orows, ocols;
+    DevBuf<long long> ooffs;
 };
 
 }  // namespace
@@ -448,6 +455,8 @@ struct insider_hip_handle {
     // the form the last sample decomposition ran (1 = tables in LDS, 2 = from global) and its gene slabs
     int sd_path = 0, sd_slabs = 0;
     int fd_path = 0;
+    // the form the flag pass of the last outlier call ran (1 = tables in LDS, 2 = from global)
+    int ol_path = 0;
 
     // work still in flight is drained and the communicator closed before the members free their buffers (the data set with
     // its last handle)
@@ -3250,6 +3259,7 @@ int insider_hip_get_info(insider_hip_handle *h, const char *name, double *out)
     else if (s == "row_kernels") *out = (double)h->row_kernels;     // last optimize() / optimize_row(): row-phase kernel forms (RowKernel bits)
     else if (s == "cd_ms_steady") *out = h->steady_cd_ms;           // option "profile": mean over outer iterations >= 5 of the last call
     else if (s == "col_stats_ms_steady") *out = h->steady_col_ms;
+    else if (s == "ol_path") *out = h->ol_path;                     // last outlier call: 1 = level tables in LDS, 2 = read from global
     else if (s == "vd_path") *out = h->vd_path;                     // last variance decomposition: 1 = level tables in LDS, 2 = read from global
     else if (s == "sd_path") *out = h->sd_path;                     // last sample decomposition: 1 = level tables in LDS, 2 = read from global
     else if (s == "sd_slabs") *out = h->sd_slabs;                   // ... and its gene slabs
@@ -3778,6 +3788,82 @@ int factor_decomposition_body(insider_hip_handle *h, double *const *A, const dou
     return INSIDER_OK;
 }
 
+// ---- outlier calls (kernels: insider_outliers.hpp) -------------------------------------------------------------------
+// the level table, the flag pass over X and the codes (bitmap + per-gene counts), the scan of the genes' totals, and the fill
+// pass over the bitmap (the list + per-sample counts).  Nothing is written to the caller's arrays before every check passed.
+int outliers_body(insider_hip_handle *h, double *const *A, const double *C, int inc_continuous, int K, int entries,
+                  const double *center, const double *scale, double threshold, int64_t cap, int32_t *rows, int32_t *cols,
+                  double *z, int64_t *total, int32_t *gene_counts, int32_t *sample_counts)
+{
+    if (!h) return fail(INSIDER_ERR_ARG, "null handle");
+    const std::vector<int32_t> every((size_t)h->ds->c + 2, 1);   // every block enters the fit
+    int rc = ph_check(h, A, C, inc_continuous, K, every.data());
+    if (rc) return rc;
+    if (entries < 0 || entries > 2) return fail(INSIDER_ERR_ARG, "entries must be 0 (all), 1 (train) or 2 (test)");
+    if (!scale) return fail(INSIDER_ERR_ARG, "null scale");
+    if (!total) return fail(INSIDER_ERR_ARG, "null total");
+    if (!(threshold > 0.0) || !std::isfinite(threshold)) return fail(INSIDER_ERR_ARG, "threshold must be finite and > 0");
+    if (cap < 0) return fail(INSIDER_ERR_ARG, "cap must not be negative");
+    if (cap > 0 && (!rows || !cols || !z)) return fail(INSIDER_ERR_ARG, "cap > 0 needs rows, cols and z");
+    HIPCHECK(hipSetDevice(h->ds->device));
+    PostWs &w = h->post;
+    hipStream_t st = h->st.stream;
+    const DataSet &d = *h->ds;
+    const int nb = d.c + inc_continuous, SL = d.SL;
+    const int64_t n = d.n, p = d.p, wpl = d.ldn / 32;
+    if ((rc = vd_build_table(h, A, C, K, nb)) || (rc = w.ocs.grow((size_t)2 * p)) || (rc = w.obits.grow((size_t)p * wpl)) ||
+        (rc = w.ogcnt.grow((size_t)2 * p)) || (rc = w.oscnt.grow((size_t)2 * n)) || (rc = w.ooffs.grow((size_t)p + 1)))
+        return rc;
+    const double *T = w.vtab;
+    double *d_scale = w.ocs.get() + p, *d_center = center ? w.ocs.get() : nullptr;
+    if (center) HIPCHECK(hipMemcpyAsync(d_center, center, (size_t)p * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHECK(hipMemcpyAsync(d_scale, scale, (size_t)p * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHECK(hipMemsetAsync(w.oscnt, 0, (size_t)2 * n * sizeof(int), st));
+    const int sel = entries == 0 ? 0 : entries == 1 ? CODE_TRAIN : CODE_TEST;
+    const int m = inc_continuous ? d.m : 0;
+    // (at most 60 KiB of dynamic LDS beside the kernel's static count buffer: no launch attribute needed)
+    const double budget = std::min(std::max(h->opt.vd_stage_kb, 0.0), 60.0) * 1024.0;
+    const bool staged = (double)OL_GW * SL * sizeof(double) <= budget;
+    h->ol_path = staged ? 1 : 2;
+    // four genes per block: 132 VGPRs staged, 113 from global (tools/kernel_regs.sh), no scratch: three / four waves per SIMD
+    if (staged)
+        hipLaunchKernelGGL((k_ol_flag<OL_GW, true>), dim3(cdiv(p, OL_GW)), dim3(64 * OL_WAVES), (size_t)OL_GW * SL * sizeof(double),
+                           st, (const double *)d.X, (const uint8_t *)d.codes, d.ldn, (int)n, p, (const int *)d.lev,
+                           (const int *)d.lvl_off_d, d.c, (const double *)d.Zc, m, d.SLcat, T, SL, sel, (const double *)d_center,
+                           (const double *)d_scale, threshold, w.obits.get(), w.ogcnt.get());
+    else
+        hipLaunchKernelGGL((k_ol_flag<OL_GW, false>), dim3(cdiv(p, OL_GW)), dim3(64 * OL_WAVES), 0, st, (const double *)d.X,
+                           (const uint8_t *)d.codes, d.ldn, (int)n, p, (const int *)d.lev, (const int *)d.lvl_off_d, d.c,
+                           (const double *)d.Zc, m, d.SLcat, T, SL, sel, (const double *)d_center, (const double *)d_scale,
+                           threshold, w.obits.get(), w.ogcnt.get());
+    KCHECK();
+    hipLaunchKernelGGL(k_ol_scan, dim3(1), dim3(OL_SCAN_THREADS), 0, st, (const int *)w.ogcnt, p, w.ooffs.get());
+    KCHECK();
+    long long tot = 0;
+    HIPCHECK(hipMemcpyAsync(&tot, w.ooffs.get() + p, sizeof(long long), hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipStreamSynchronize(st));
+    // the list holds the first min(total, cap) calls; the fill pass also runs without a list, for the per-sample counts
+    const long long keep = std::min<long long>(tot, cap);
+    if ((rc = w.orows.grow((size_t)keep)) || (rc = w.ocols.grow((size_t)keep)) || (rc = w.oz.grow((size_t)keep))) return rc;
+    if (tot > 0 && (keep > 0 || sample_counts)) {
+        hipLaunchKernelGGL(k_ol_fill, dim3(cdiv(p, OL_WAVES)), dim3(64 * OL_WAVES), 0, st, (const double *)d.X, d.ldn, (int)n, p,
+                           (const int *)d.lev, (const int *)d.lvl_off_d, d.c, (const double *)d.Zc, m, d.SLcat, T, SL,
+                           (const double *)d_center, (const double *)d_scale, (const uint32_t *)w.obits,
+                           (const long long *)w.ooffs, keep, w.orows.get(), w.ocols.get(), w.oz.get(), w.oscnt.get());
+        KCHECK();
+    }
+    if (keep > 0) {
+        HIPCHECK(hipMemcpyAsync(rows, w.orows, (size_t)keep * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        HIPCHECK(hipMemcpyAsync(cols, w.ocols, (size_t)keep * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        HIPCHECK(hipMemcpyAsync(z, w.oz, (size_t)keep * sizeof(double), hipMemcpyDeviceToHost, st));
+    }
+    if (gene_counts) HIPCHECK(hipMemcpyAsync(gene_counts, w.ogcnt, (size_t)2 * p * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    if (sample_counts) HIPCHECK(hipMemcpyAsync(sample_counts, w.oscnt, (size_t)2 * n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipStreamSynchronize(st));
+    *total = (int64_t)tot;
+    return INSIDER_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -3811,6 +3897,15 @@ int insider_hip_factor_decomposition(insider_hip_handle *h, double *const *A, co
                                      int entries, double *out)
 {
     return ph_finish(h, factor_decomposition_body(h, A, C, inc_continuous, K, entries, out));
+}
+
+int insider_hip_outliers(insider_hip_handle *h, double *const *A, const double *C, int inc_continuous, int K,
+                         int entries, const double *center, const double *scale, double threshold, int64_t cap,
+                         int32_t *rows, int32_t *cols, double *z, int64_t *total, int32_t *gene_counts,
+                         int32_t *sample_counts)
+{
+    return ph_finish(h, outliers_body(h, A, C, inc_continuous, K, entries, center, scale, threshold, cap, rows, cols, z, total,
+                                      gene_counts, sample_counts));
 }
 
 }  // extern "C"

@@ -9,6 +9,7 @@
     ... --variance-decomposition                # then the per-gene variance decomposition on the device
     ... --sample-decomposition                  # then the per-sample and per-level fit diagnostics on the device
     ... --factor-decomposition                  # then the per-factor decomposition (which factor, through which covariate)
+    ... --outliers 3 [--outlier-entries train]  # then the entries whose standardised residual has |z| >= 3, on the device
 
 Semantics are those of insider_amd.api (the mirror of R/insider.R): with masks given, `--partition 1` fits on the
 train entries (optimize(tuning = 1)) and reports the test RMSE; without masks (or `--partition 0`) every non-NA entry is
@@ -20,7 +21,9 @@ sample, sd_r2 / sd_rmse (n) and sd_explained / sd_drop_one (B x n), and per leve
 sd_level<b>_r2 / sd_level<b>_rmse (L_b, posthoc.level_decomposition); --factor-decomposition adds the tables pooled over genes
 fd_summary_explained / fd_summary_drop_one ((B + 1) x K, the last block the total; posthoc.factor_summary), fd_order (the
 factors by descending pooled drop_one of the total) and per gene fd_explained / fd_drop_one (p x (B + 1) K, block-major
-columns).  Output: A<i> (L_i x K), C (K x p) and result.json {train_rmse, test_rmse, loss,
+columns); --outliers T adds the calls |z| >= T among the --outlier-entries (z standardised by each gene's residual mean and
+standard deviation over those entries, posthoc.residual_center_scale): ol_rows, ol_cols (0-based sample and gene), ol_z (in
+ascending gene, then sample), ol_gene_counts (p x 2) and ol_sample_counts (n x 2), columns {low, high}.  Output: A<i> (L_i x K), C (K x p) and result.json {train_rmse, test_rmse, loss,
 iters, traj} in --out.  There is no CPU fallback: without a visible MI355X the command fails with the library's status.
 """
 import argparse
@@ -78,6 +81,12 @@ def parse(argv=None):
                     help="after the fit, the per-factor decomposition on the device over the entries the fit used; writes "
                          "fd_summary_explained, fd_summary_drop_one ((blocks + 1) x K), fd_order (K) and fd_explained, "
                          "fd_drop_one (p x (blocks + 1) K, block-major columns) next to the factors")
+    ap.add_argument("--outliers", type=float, default=None, metavar="T",
+                    help="after the fit, the entries whose standardised residual has |z| >= T, on the device; writes ol_rows, "
+                         "ol_cols, ol_z (ascending gene, then sample), ol_gene_counts (p x 2) and ol_sample_counts (n x 2; "
+                         "columns low, high) next to the factors")
+    ap.add_argument("--outlier-entries", choices=("all", "train", "test"), default="train",
+                    help="--outliers: the entries that can be called (default: train, the entries the fit used)")
     a = ap.parse_args(argv)
     if not a.flat and not (a.x and a.levels):
         ap.error("give --flat DIR or --x and --levels")
@@ -198,6 +207,16 @@ def main(argv=None):
         vd = dict(vd or {}, fd_summary_explained=fs["explained"], fd_summary_drop_one=fs["drop_one"],
                   fd_order=fs["order"].astype(np.float64), fd_explained=d["explained"].reshape(-1, p).T,
                   fd_drop_one=d["drop_one"].reshape(-1, p).T)
+    if a.outliers is not None:
+        from .posthoc import residual_center_scale
+        rows_, inc = list(res["row_matrices"].values()), 1 if Z is not None else 0
+        ce, sc = residual_center_scale(ds.variance_decomposition(rows_, res["column_factor"], entries=a.outlier_entries,
+                                                                 inc_continuous=inc))
+        ol = ds.outliers(rows_, res["column_factor"], sc, center=ce, threshold=a.outliers, entries=a.outlier_entries,
+                         inc_continuous=inc)
+        vd = dict(vd or {}, ol_rows=ol["rows"], ol_cols=ol["cols"], ol_z=ol["z"],
+                  ol_gene_counts=np.column_stack([ol["gene_low"], ol["gene_high"]]),
+                  ol_sample_counts=np.column_stack([ol["sample_low"], ol["sample_high"]]))
     ds.close()
     summary = dict(train_rmse=res["train_rmse"], test_rmse=None if np.isnan(res["test_rmse"]) else res["test_rmse"],
                    loss=res["loss"], iters=res["iters"], rank=K, **{"lambda": a.lam}, alpha=a.alpha, partition=partition,

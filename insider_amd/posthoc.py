@@ -22,6 +22,10 @@ sample_decomposition_host() as its yardstick; level_decomposition() pools the sa
 factor_decomposition() splits the per-gene record along the K latent factors (InsiderData.factor_decomposition: which
 factors matter, which covariate drives factor k, in which genes it acts), with factor_decomposition_host() as its
 yardstick, fd_derived() for the per-gene shares and factor_summary() for the (B + 1) x K tables pooled over genes.
+
+outliers() lists the entries themselves: the (sample, gene) entries whose standardised residual the model cannot explain
+(InsiderData.outliers: a flag pass over X into a bitmap, a scan, a fill pass over the bitmap), with outliers_host() as its
+yardstick and residual_center_scale() for the per-gene center and scale from a variance-decomposition record.
 """
 import numpy as np
 
@@ -264,3 +268,67 @@ def factor_decomposition(obj, which="fit", entries="train"):
     rec = ds.factor_decomposition(list(obj["cfd_matrices"].values()), obj["column_factor"], entries=entries,
                                   inc_continuous=int(obj["inc_continuous"]))
     return fd_derived(rec)
+
+
+def residual_center_scale(rec):
+    """Per-gene mean and standard deviation of the residual r = x - f over S_j, from the raw sums of a variance
+    decomposition (InsiderData.variance_decomposition / variance_decomposition_host):
+        center = (sum_x - sum_b sum_g_b) / n,   scale = sqrt((rss - n center^2) / (n - 1)).
+    A gene with n < 2 gets a NaN scale (and with n = 0 a NaN center): outliers() gives it no call.  -> (center, scale)."""
+    n = np.asarray(rec["n"], dtype=np.float64)
+    sum_r = np.asarray(rec["sum_x"], dtype=np.float64) - np.asarray(rec["sum_g"], dtype=np.float64).sum(axis=0)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        center = sum_r / np.where(n > 0, n, np.nan)
+        var = (np.asarray(rec["rss"], dtype=np.float64) - n * center * center) / np.where(n > 1, n - 1.0, np.nan)
+        scale = np.sqrt(np.maximum(var, 0.0))
+    return center, scale
+
+
+def outliers_host(X, levels, ctns, mask, A, C, center, scale, threshold):
+    """The outlier calls in plain numpy (the yardstick of InsiderData.outliers); X, levels, ctns, mask, A, C as in
+    variance_decomposition_host(), ``center`` (None = 0) and ``scale`` of length p.  An entry that counts is a call when
+    |z| >= threshold, z = (x - f - center[j]) / scale[j], f the sum of the blocks in block order; a gene whose scale is not
+    finite or not > 0 has none.  -> dict of rows, cols (int32), z in ascending gene, then ascending sample, total, and the
+    counts gene_low, gene_high (p), sample_low, sample_high (n) (low: z < 0, high: z > 0)."""
+    X = np.asarray(X, dtype=np.float64)
+    n, p = X.shape
+    Cm = np.asarray(C, dtype=np.float64)
+    lev = np.asarray(levels).reshape(n, -1)
+    c = lev.shape[1]
+    f = np.zeros_like(X)
+    for b in range(c):
+        f = f + np.asarray(A[b], dtype=np.float64)[lev[:, b].astype(np.int64) - 1] @ Cm
+    if ctns is not None:
+        f = f + np.asarray(ctns, dtype=np.float64).reshape(n, -1) @ (np.asarray(A[c], dtype=np.float64) @ Cm)
+    sc = np.asarray(scale, dtype=np.float64).ravel()
+    ce = np.zeros(p) if center is None else np.asarray(center, dtype=np.float64).ravel()
+    usable = np.isfinite(sc) & (sc > 0)
+    w = np.ones(X.shape, dtype=bool) if mask is None else np.asarray(mask).astype(bool)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        z = ((X - f) - ce) / sc
+        call = w & usable[None, :] & (np.abs(z) >= threshold)
+    cols, rows = np.nonzero(call.T)                       # gene-major: ascending gene, then ascending sample
+    low, high = call & (z < 0), call & (z > 0)
+    return dict(rows=rows.astype(np.int32), cols=cols.astype(np.int32), z=z[rows, cols], total=int(call.sum()),
+                gene_low=low.sum(axis=0).astype(np.int32), gene_high=high.sum(axis=0).astype(np.int32),
+                sample_low=low.sum(axis=1).astype(np.int32), sample_high=high.sum(axis=1).astype(np.int32))
+
+
+def outliers(obj, which="fit", entries="train", threshold=3.0, center=None, scale=None, cap=None):
+    """The aberrant entries of a fitted ``Insider`` object on the device, with the ``which`` / ``entries`` of
+    variance_decomposition().  ``center`` / ``scale`` (length p) not given: variance_decomposition() runs on the same entries
+    first and residual_center_scale() supplies each gene's residual mean and standard deviation.  -> the dict of
+    InsiderData.outliers() (rows, cols, z, total, gene_low, gene_high, sample_low, sample_high) plus the ``center`` and
+    ``scale`` that were used."""
+    from . import api
+    ds = api._resident(obj, which)
+    cfd, inc = list(obj["cfd_matrices"].values()), int(obj["inc_continuous"])
+    if center is None or scale is None:
+        ce, sc = residual_center_scale(ds.variance_decomposition(cfd, obj["column_factor"], entries=entries,
+                                                                 inc_continuous=inc))
+        center = ce if center is None else center
+        scale = sc if scale is None else scale
+    out = ds.outliers(cfd, obj["column_factor"], scale, center=center, threshold=threshold, entries=entries,
+                      inc_continuous=inc, cap=cap)
+    out["center"], out["scale"] = np.asarray(center, dtype=np.float64), np.asarray(scale, dtype=np.float64)
+    return out
