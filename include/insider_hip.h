@@ -436,6 +436,25 @@ int insider_hip_outliers(insider_hip_handle *h, double *const *A, const double *
                          int64_t cap, int32_t *rows, int32_t *cols, double *z, int64_t *total,
                          int32_t *gene_counts, int32_t *sample_counts);
 
+/* Top-k nearest neighbours of embeddings (insider_amd/csrc/insider_neighbors.hpp).  Handle-free, one device.
+ *   Q (K x nq) and B (K x nb) are column-major: one embedding is K contiguous doubles, the layout of column_factor.  For every
+ *   query the k base columns with the largest score, metric 0 = cosine (q.b / (|q| |b|)), 1 = dot (q.b).  idx_out / score_out
+ *   are nq x k, query-major: row i lists the neighbours of query i in descending score, equal scores (-0.0 == 0.0) by ascending
+ *   base index, so the answer is a pure function of the inputs.  self_offset = s >= 0: Q is the window B[:, s : s + nq] and
+ *   query i never returns base index s + i (pass Q = B + s K and the matrix is uploaded once); -1: no exclusion.  A query with
+ *   fewer than k eligible candidates ends its row with index -1 / score NaN.  Under cosine a zero-norm base column (its sum of
+ *   squares is 0 in fp64) is nobody's neighbour and a zero-norm query gets a row of open slots; under dot zero columns are
+ *   ordinary candidates of score 0.  Raw Euclidean distance is not offered: on unit-normalised columns it orders as cosine.
+ *   The score of a pair is the same instruction sequence wherever the pair falls: repeated calls return identical bits, and a
+ *   call on a window of the queries returns exactly the rows of the full call.  Device memory is O((nq + nb) K + nq k).
+ *   INSIDER_ERR_ARG: a NULL pointer, K outside 1..63, k outside 1..64, nq < 0, nb < 1 or nb > INT32_MAX, an unknown metric,
+ *   self_offset < -1 or self_offset + nq > nb, a non-finite value in Q or B (checked on the host); nothing is written then.
+ *   nq = 0 returns INSIDER_OK and writes nothing.  insider_hip_last_neighbors_ms: of the calling THREAD's last call, the
+ *   HIP-event time in ms of its kernels (transfers excluded). */
+int insider_hip_neighbors(const double *Q, int64_t nq, const double *B, int64_t nb, int K, int metric, int k,
+                          int64_t self_offset, int device, int32_t *idx_out, double *score_out);
+double insider_hip_last_neighbors_ms(void);
+
 /* Profile of the last insider_hip_optimize() call (option "profile" = 1), HIP-event timed on the library's stream.
  * out[0..11]: {column-side masked-Gram launches, total ms, row-side masked-Gram launches, total ms,
  *  column-solve (CD / ridge) launches, total ms, test-residual launches, total ms,

@@ -29,7 +29,7 @@ SYMBOLS = (
     "insider_hip_optimize_continuous_v2", "insider_hip_residual", "insider_hip_interaction_glm",
     "insider_hip_variance_decomposition", "insider_hip_sample_decomposition", "insider_hip_col_stats", "insider_hip_last_cd_solver",
     "insider_hip_remask", "insider_hip_set_folds", "insider_hip_remask_fold", "insider_hip_factor_decomposition",
-    "insider_hip_outliers",
+    "insider_hip_outliers", "insider_hip_neighbors", "insider_hip_last_neighbors_ms",
 )
 COMM_ID_BYTES = 128
 # insider_hip_outliers (insider_amd/csrc/insider_outliers.hpp): the samples a block of k_ol_flag covers per trip (OL_TRIP) and the
@@ -137,6 +137,8 @@ def load():
     lib.insider_hip_factor_decomposition.argtypes = [C.c_void_p, C.POINTER(dp), dp, C.c_int, C.c_int, C.c_int, dp]
     lib.insider_hip_outliers.argtypes = [C.c_void_p, C.POINTER(dp), dp, C.c_int, C.c_int, C.c_int, dp, dp, C.c_double, C.c_int64,
                                          i32p, i32p, dp, C.POINTER(C.c_int64), i32p, i32p]
+    lib.insider_hip_neighbors.argtypes = [dp, C.c_int64, dp, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, i32p, dp]
+    lib.insider_hip_last_neighbors_ms.restype = C.c_double
     lib.insider_hip_get_profile.argtypes = [C.c_void_p, dp]
     lib.insider_hip_get_sweeps.argtypes = [C.c_void_p, i32p]
     lib.insider_hip_last_cd_ms.restype = C.c_double

@@ -621,6 +621,67 @@ def solve_sympd(A, b, device=0, return_route=False):
     return (x, route) if return_route else x
 
 
+NEIGHBOR_METRICS = {"cosine": 0, "dot": 1}
+NEIGHBOR_MAX_K = 64
+
+
+def neighbor_args(query, base, k, metric, exclude_self):
+    """The checked arguments of neighbors() / posthoc.neighbors_host(): (Q, B, k, metric code, self_offset), Q and B
+    column-major float64 (B is Q itself when ``base`` is None).  Shape, metric, k and window errors raise
+    InsiderError(ERR_ARG)."""
+    Q = _lib.f64(query)
+    if Q.ndim != 2:
+        raise InsiderError(_lib.ERR_ARG, "query must be a K x nq array")
+    if base is None:
+        B = Q
+        if exclude_self is None:
+            exclude_self = 0
+    else:
+        B = _lib.f64(base)
+        if B.ndim != 2 or B.shape[0] != Q.shape[0]:
+            raise InsiderError(_lib.ERR_ARG, "base must be a K x nb array with the K of query")
+    if not 1 <= Q.shape[0] <= _lib.MAX_K:
+        raise InsiderError(_lib.ERR_ARG, f"K must be in 1..{_lib.MAX_K}")
+    if B.shape[1] < 1:
+        raise InsiderError(_lib.ERR_ARG, "base must hold at least one column")
+    if metric not in NEIGHBOR_METRICS:
+        raise InsiderError(_lib.ERR_ARG, f"metric must be one of {sorted(NEIGHBOR_METRICS)}")
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= NEIGHBOR_MAX_K:
+        raise InsiderError(_lib.ERR_ARG, f"k must be an integer in 1..{NEIGHBOR_MAX_K}")
+    if exclude_self is None or exclude_self is False:
+        off = -1
+    elif isinstance(exclude_self, (bool, float)) or not isinstance(exclude_self, (int, np.integer)):
+        raise InsiderError(_lib.ERR_ARG, "exclude_self must be None, False or a window start (an integer >= 0)")
+    else:
+        off = int(exclude_self)
+        if off < 0 or off + Q.shape[1] > B.shape[1]:
+            raise InsiderError(_lib.ERR_ARG, "exclude_self: the window start + nq must lie within the base")
+    return Q, B, int(k), NEIGHBOR_METRICS[metric], off
+
+
+def neighbors(query, base=None, k=10, metric="cosine", exclude_self=None, device=0):
+    """The k nearest base columns of every query column on the device (insider_hip_neighbors).  ``query`` (K x nq) and
+    ``base`` (K x nb) hold one embedding per column, as column_factor does; base=None: the base is the queries and a query
+    never returns itself.  metric "cosine" or "dot" (raw Euclidean distance is not offered: on unit-normalised columns it
+    orders as cosine).  exclude_self: None / False = no exclusion, s >= 0 = the queries are base[:, s : s + nq] and query i
+    never returns base column s + i.  -> dict(index=(nq, k) int32, score=(nq, k) float64): descending score, equal scores by
+    ascending base index; a row with fewer than k eligible candidates ends in -1 / NaN (under cosine a zero column is
+    nobody's neighbour and has none)."""
+    Q, B, k, code, off = neighbor_args(query, base, k, metric, exclude_self)
+    K, nq = Q.shape
+    index = np.full((nq, k), -1, dtype=np.int32)
+    score = np.full((nq, k), np.nan)
+    if nq:
+        if off >= 0 and (B is Q or np.array_equal(B[:, off:off + nq], Q)):
+            # the self call: hand the library the window of B itself, so the matrix is checked and uploaded once
+            qp = C.cast(B.ctypes.data + off * K * 8, C.POINTER(C.c_double))
+        else:
+            qp = _lib.ptr(Q)
+        _lib.check(_lib.load().insider_hip_neighbors(qp, nq, _lib.ptr(B), B.shape[1], K, code, k, off, int(device),
+                                                     _lib.ptr(index, C.c_int32), _lib.ptr(score)))
+    return dict(index=index, score=score)
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # caller level — R/insider.R, R/utils.R
 # ---------------------------------------------------------------------------------------------------------------

@@ -11,6 +11,7 @@
 #include "insider_sampdecomp.hpp"
 #include "insider_factdecomp.hpp"
 #include "insider_outliers.hpp"
+#include "insider_neighbors.hpp"
 
 #include <rccl/rccl.h>
 
@@ -37,6 +38,7 @@ namespace {
 thread_local std::string g_err;
 thread_local double g_last_cd_ms = 0.0;   // per calling thread: the ABI is re-entrant per handle / per thread
 thread_local int g_last_cd_solver = 0;     // (ColSolver)
+thread_local double g_last_neighbors_ms = 0.0;
 
 int fail(int code, const std::string &msg)
 {
@@ -3062,6 +3064,85 @@ int insider_hip_solve_sympd(const double *A, const double *b, int K, int64_t nsy
     if (singular) return fail(INSIDER_ERR_SOLVE, "a system is singular to working precision");
     return INSIDER_OK;
 }
+
+// ---- neighbours (insider_neighbors.hpp) ------------------------------------------------------------------------------------
+static bool all_finite(const double *v, size_t count)
+{
+    for (size_t e = 0; e < count; ++e)
+        if (!std::isfinite(v[e])) return false;
+    return true;
+}
+
+int insider_hip_neighbors(const double *Q, int64_t nq, const double *B, int64_t nb, int K, int metric, int k,
+                          int64_t self_offset, int device, int32_t *idx_out, double *score_out)
+{
+    if (!Q || !B || !idx_out || !score_out) return fail(INSIDER_ERR_ARG, "null argument");
+    if (K < 1 || K > INSIDER_MAX_K) return fail(INSIDER_ERR_ARG, "K must be in 1..63");
+    if (k < 1 || k > NN_MAX_TOPK) return fail(INSIDER_ERR_ARG, "k must be in 1..64");
+    if (nq < 0) return fail(INSIDER_ERR_ARG, "nq must be >= 0");
+    if (nb < 1 || nb > (int64_t)std::numeric_limits<int32_t>::max()) return fail(INSIDER_ERR_ARG, "nb must be in 1..2^31-1");
+    if (metric != 0 && metric != 1) return fail(INSIDER_ERR_ARG, "metric must be 0 (cosine) or 1 (dot)");
+    if (self_offset < -1) return fail(INSIDER_ERR_ARG, "self_offset must be >= -1");
+    if (self_offset >= 0 && (nq > nb || self_offset > nb - nq))
+        return fail(INSIDER_ERR_ARG, "self_offset + nq must be <= nb");
+    if (nq > (int64_t)std::numeric_limits<int32_t>::max()) return fail(INSIDER_ERR_UNSUPPORTED, "nq must be < 2^31");
+    // the queries are a window of the base (the self call): one check, one upload
+    const bool window = self_offset >= 0 && Q == B + (size_t)self_offset * K;
+    if (!all_finite(B, (size_t)nb * K) || (!window && !all_finite(Q, (size_t)nq * K)))
+        return fail(INSIDER_ERR_ARG, "Q and B must be finite");
+    int rc = cd_common_checks(K, nq, device);
+    if (rc) return rc;
+    if (nq == 0) return INSIDER_OK;
+    HIPCHECK(hipSetDevice(device));
+    const int K4 = (K + 3) & ~3, KS = (K4 + 15) / 16;
+    const int NT = K4 <= 32 ? 4 : 2;
+    const int64_t nbpad = round_up(nb, 64), nqpad = round_up(nq, 16);
+    auto lds = [&](int nw) { return (size_t)(NT * 16 * K4 + nw * 16 * (k + NN_CAP)) * 8 + (size_t)(NT * 16 + nw * 16 * (k + NN_CAP)) * 4; };
+    const int NW = lds(4) <= 64 * 1024 ? 4 : 2;
+    DevBuf<double> dB, dQ, dBp, dQp, dscore;
+    DevBuf<int> dba, dqa;
+    DevBuf<int32_t> didx;
+    if ((rc = dB.alloc((size_t)nb * K)) || (rc = dBp.alloc((size_t)nbpad * K4)) || (rc = dQp.alloc((size_t)nqpad * K4)) ||
+        (rc = dba.alloc((size_t)nbpad)) || (rc = dqa.alloc((size_t)nqpad)) || (rc = dscore.alloc((size_t)nq * k)) ||
+        (rc = didx.alloc((size_t)nq * k)))
+        return rc;
+    HIPCHECK(hipMemcpy(dB, B, (size_t)nb * K * sizeof(double), hipMemcpyHostToDevice));
+    const double *qsrc = dB.get() + (size_t)(window ? self_offset : 0) * K;
+    if (!window) {
+        if ((rc = dQ.alloc((size_t)nq * K))) return rc;
+        HIPCHECK(hipMemcpy(dQ, Q, (size_t)nq * K * sizeof(double), hipMemcpyHostToDevice));
+        qsrc = dQ;
+    }
+    Event e0, e1;
+    HIPCHECK(hipEventCreate(e0.out()));
+    HIPCHECK(hipEventCreate(e1.out()));
+    HIPCHECK(hipEventRecord(e0, 0));
+    hipLaunchKernelGGL(k_nn_prep, dim3(cdiv(nbpad, 256)), dim3(256), 0, 0, (const double *)dB, nb, nbpad, K, K4, metric, dBp.get(),
+                       dba.get());
+    KCHECK();
+    hipLaunchKernelGGL(k_nn_prep, dim3(cdiv(nqpad, 256)), dim3(256), 0, 0, qsrc, nq, nqpad, K, K4, metric, dQp.get(), dqa.get());
+    KCHECK();
+    const dim3 grid(cdiv(nq, 16 * NW)), block(64 * NW);
+#define NN_LAUNCH(KS_)                                                                                                       \
+    hipLaunchKernelGGL((k_nn_topk<KS_>), grid, block, lds(NW), 0, (const double *)dQp, (const int *)dqa, nq, (const double *)dBp,  \
+                       (const int *)dba, nbpad, K4, NT, k, self_offset, didx.get(), dscore.get())
+    if (KS == 1) NN_LAUNCH(1);
+    else if (KS == 2) NN_LAUNCH(2);
+    else if (KS == 3) NN_LAUNCH(3);
+    else NN_LAUNCH(4);
+#undef NN_LAUNCH
+    KCHECK();
+    HIPCHECK(hipEventRecord(e1, 0));
+    HIPCHECK(hipEventSynchronize(e1));
+    float ms = 0.0f;
+    (void)hipEventElapsedTime(&ms, e0, e1);
+    g_last_neighbors_ms = ms;
+    HIPCHECK(hipMemcpy(idx_out, didx, (size_t)nq * k * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIPCHECK(hipMemcpy(score_out, dscore, (size_t)nq * k * sizeof(double), hipMemcpyDeviceToHost));
+    return INSIDER_OK;
+}
+
+double insider_hip_last_neighbors_ms(void) { return g_last_neighbors_ms; }
 
 // optimize_continuous_v2 (src/optimize.cpp:76-137) with the reference's eight arguments, on an arbitrary `data` matrix
 // (insider_cont_v2.hpp): one streaming pass over (data, indicator) for the per-gene sums, the K x K weighted Gram, then the

@@ -10,6 +10,7 @@
     ... --sample-decomposition                  # then the per-sample and per-level fit diagnostics on the device
     ... --factor-decomposition                  # then the per-factor decomposition (which factor, through which covariate)
     ... --outliers 3 [--outlier-entries train]  # then the entries whose standardised residual has |z| >= 3, on the device
+    ... --gene-neighbors 10 --sample-neighbors 10 [--neighbor-metric cosine]   # then each gene's / sample's nearest in latent space
 
 Semantics are those of insider_amd.api (the mirror of R/insider.R): with masks given, `--partition 1` fits on the
 train entries (optimize(tuning = 1)) and reports the test RMSE; without masks (or `--partition 0`) every non-NA entry is
@@ -23,7 +24,11 @@ fd_summary_explained / fd_summary_drop_one ((B + 1) x K, the last block the tota
 factors by descending pooled drop_one of the total) and per gene fd_explained / fd_drop_one (p x (B + 1) K, block-major
 columns); --outliers T adds the calls |z| >= T among the --outlier-entries (z standardised by each gene's residual mean and
 standard deviation over those entries, posthoc.residual_center_scale): ol_rows, ol_cols (0-based sample and gene), ol_z (in
-ascending gene, then sample), ol_gene_counts (p x 2) and ol_sample_counts (n x 2), columns {low, high}.  Output: A<i> (L_i x K), C (K x p) and result.json {train_rmse, test_rmse, loss,
+ascending gene, then sample), ol_gene_counts (p x 2) and ol_sample_counts (n x 2), columns {low, high};
+--gene-neighbors N / --sample-neighbors N add each gene's N nearest genes by its column of C and each sample's N nearest
+samples by its row embedding (posthoc.gene_neighbors / sample_neighbors, --neighbor-metric cosine or dot): nn_gene_index /
+nn_gene_score (p x N) and nn_sample_index / nn_sample_score (n x N), 0-based, descending score, ties by ascending index, open
+slots -1 / NaN.  Output: A<i> (L_i x K), C (K x p) and result.json {train_rmse, test_rmse, loss,
 iters, traj} in --out.  There is no CPU fallback: without a visible MI355X the command fails with the library's status.
 """
 import argparse
@@ -87,7 +92,19 @@ def parse(argv=None):
                          "columns low, high) next to the factors")
     ap.add_argument("--outlier-entries", choices=("all", "train", "test"), default="train",
                     help="--outliers: the entries that can be called (default: train, the entries the fit used)")
+    ap.add_argument("--gene-neighbors", type=int, default=None, metavar="N",
+                    help="after the fit, every gene's N nearest genes in the latent space (columns of C), on the device; "
+                         "writes nn_gene_index, nn_gene_score (p x N; 0-based, open slots -1 / NaN) next to the factors")
+    ap.add_argument("--sample-neighbors", type=int, default=None, metavar="N",
+                    help="after the fit, every sample's N nearest samples by its row embedding (the sum of its levels' rows), "
+                         "on the device; writes nn_sample_index, nn_sample_score (n x N) next to the factors")
+    ap.add_argument("--neighbor-metric", choices=("cosine", "dot"), default="cosine",
+                    help="--gene-neighbors / --sample-neighbors: the score (default: cosine)")
     a = ap.parse_args(argv)
+    for name in ("gene_neighbors", "sample_neighbors"):
+        v = getattr(a, name)
+        if v is not None and not 1 <= v <= 64:
+            ap.error(f"--{name.replace('_', '-')} must be in 1..64")
     if not a.flat and not (a.x and a.levels):
         ap.error("give --flat DIR or --x and --levels")
     if not a.tune and (a.rank is None or a.lam is None or a.alpha is None):
@@ -217,6 +234,15 @@ def main(argv=None):
         vd = dict(vd or {}, ol_rows=ol["rows"], ol_cols=ol["cols"], ol_z=ol["z"],
                   ol_gene_counts=np.column_stack([ol["gene_low"], ol["gene_high"]]),
                   ol_sample_counts=np.column_stack([ol["sample_low"], ol["sample_high"]]))
+    if a.gene_neighbors is not None:
+        from .posthoc import gene_neighbors
+        nn = gene_neighbors(res["column_factor"], k=a.gene_neighbors, metric=a.neighbor_metric, device=a.device)
+        vd = dict(vd or {}, nn_gene_index=nn["index"], nn_gene_score=nn["score"])
+    if a.sample_neighbors is not None:
+        from .posthoc import sample_neighbors
+        nn = sample_neighbors(list(res["row_matrices"].values()), ds_levels, Z, k=a.sample_neighbors, metric=a.neighbor_metric,
+                              device=a.device)
+        vd = dict(vd or {}, nn_sample_index=nn["index"], nn_sample_score=nn["score"])
     ds.close()
     summary = dict(train_rmse=res["train_rmse"], test_rmse=None if np.isnan(res["test_rmse"]) else res["test_rmse"],
                    loss=res["loss"], iters=res["iters"], rank=K, **{"lambda": a.lam}, alpha=a.alpha, partition=partition,
@@ -228,11 +254,7 @@ def main(argv=None):
                 np.save(os.path.join(a.out, name + ".npy"), np.asfortranarray(v))
             else:
                 flatio.write_raw(os.path.join(a.out, name + ".f64"), v)
-    for name, v in (vd or {}).items():
-        if fmt == "npy":
-            np.save(os.path.join(a.out, name + ".npy"), np.asfortranarray(v))
-        else:
-            flatio.write_raw(os.path.join(a.out, name + ".f64"), v)
+    flatio.write_records(a.out, fmt, vd or {})
     print(json.dumps({k: summary[k] for k in ("train_rmse", "test_rmse", "loss", "iters")} | {"out": a.out}))
     return 0
 

@@ -89,3 +89,13 @@ def write_result(outdir, fmt, row_matrices, column_factor, summary):
         write_raw(os.path.join(outdir, "C.f64"), column_factor)
     with open(os.path.join(outdir, "result.json"), "w") as f:
         json.dump(summary, f, indent=1)
+
+
+def write_records(outdir, fmt, records):
+    """The post-hoc records of the driver next to the factors, one file per name: "npy" keeps each array's own element type,
+    "flat" writes every record as <name>.f64 (column-major; index records as doubles, 0-based, an open slot as -1 / NaN)."""
+    for name, v in records.items():
+        if fmt == "npy":
+            np.save(os.path.join(outdir, name + ".npy"), np.asfortranarray(v))
+        else:
+            write_raw(os.path.join(outdir, name + ".f64"), v)

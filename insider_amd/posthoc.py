@@ -26,6 +26,10 @@ yardstick, fd_derived() for the per-gene shares and factor_summary() for the (B 
 outliers() lists the entries themselves: the (sample, gene) entries whose standardised residual the model cannot explain
 (InsiderData.outliers: a flag pass over X into a bitmap, a scan, a fill pass over the bitmap), with outliers_host() as its
 yardstick and residual_center_scale() for the per-gene center and scale from a variance-decomposition record.
+
+gene_neighbors() / sample_neighbors() ask the latent representations themselves which genes lie next to a gene and which
+samples next to a sample (api.neighbors: a K-deep product on the device with the top-k selection fused behind it, the
+similarity matrix never exists), on column_factor and on sample_embeddings(); neighbors_host() is the yardstick.
 """
 import numpy as np
 
@@ -332,3 +336,75 @@ def outliers(obj, which="fit", entries="train", threshold=3.0, center=None, scal
                       inc_continuous=inc, cap=cap)
     out["center"], out["scale"] = np.asarray(center, dtype=np.float64), np.asarray(scale, dtype=np.float64)
     return out
+
+
+def neighbors_host(query, base=None, k=10, metric="cosine", exclude_self=None, device=0, chunk=512):
+    """api.neighbors() in plain numpy (the yardstick of the device path): the same arguments, checks and result.  Scores are
+    float64, q.b or q.b / (|q| |b|); per query the eligible base columns are ordered by np.lexsort on (index, -score):
+    descending score, equal scores (-0.0 == 0.0) by ascending index.  Not eligible: the query's own column under
+    exclude_self and, under cosine, zero-norm base columns; a zero-norm query has no candidate at all.  Rows with fewer than
+    k candidates end in -1 / NaN.  Queries are taken ``chunk`` at a time: no nq x nb array is formed (``device`` is accepted
+    for the common signature and not used)."""
+    from . import api
+    Q, B, k, code, off = api.neighbor_args(query, base, k, metric, exclude_self)
+    nq, nb = Q.shape[1], B.shape[1]
+    index = np.full((nq, k), -1, dtype=np.int32)
+    score = np.full((nq, k), np.nan)
+    ids = np.arange(nb)
+    nrm_b = np.sqrt((B * B).sum(axis=0))
+    for c0 in range(0, nq, chunk):
+        Qc = Q[:, c0:c0 + chunk]
+        S = Qc.T @ B
+        ok = np.ones(S.shape, dtype=bool)
+        if code == 0:
+            nrm_q = np.sqrt((Qc * Qc).sum(axis=0))
+            with np.errstate(divide="ignore", invalid="ignore"):
+                S = S / (nrm_q[:, None] * nrm_b[None, :])
+            ok &= (nrm_q > 0)[:, None] & (nrm_b > 0)[None, :]
+        if off >= 0:
+            own = off + c0 + np.arange(Qc.shape[1])
+            ok[np.arange(Qc.shape[1]), own] = False
+        for i in range(Qc.shape[1]):
+            cand = ids[ok[i]]
+            sc = S[i, cand] + 0.0                                   # (-0.0 + 0.0 = 0.0: one zero for the sort key)
+            order = np.lexsort((cand, -sc))[:k]
+            index[c0 + i, :order.size] = cand[order]
+            score[c0 + i, :order.size] = sc[order]
+    return dict(index=index, score=score)
+
+
+def gene_neighbors(column_factor, k=10, metric="cosine", device=0):
+    """The k nearest genes of every gene in the latent space: one api.neighbors() call on C (K x p) against itself, a gene
+    never its own neighbour.  -> dict(index=(p, k) int32 0-based genes, score=(p, k)); open slots -1 / NaN (under cosine
+    an all-zero column of C, which elastic-net fits do produce, has no neighbours and is nobody's)."""
+    from . import api
+    return api.neighbors(column_factor, None, k=k, metric=metric, device=device)
+
+
+def sample_embeddings(cfd_factors, levels, ctns_confounder=None):
+    """The K x n per-sample row embedding of a fit: column i is the sum over the covariates b of row levels[i, b] (1-based)
+    of cfd_factors[b], plus ctns_confounder[i] @ cfd_factors[c] when the continuous block is given: the total block of
+    factor_decomposition_host(), summed in block order."""
+    lev = np.asarray(levels)
+    lev = lev.reshape(lev.shape[0], -1)
+    A = [np.asarray(a, dtype=np.float64) for a in cfd_factors]
+    c = lev.shape[1]
+    if len(A) != c + (0 if ctns_confounder is None else 1):
+        raise ValueError(f"{len(A)} factor matrices for {c} covariates" + ("" if ctns_confounder is None else " + the continuous block"))
+    tot = np.zeros((lev.shape[0], A[0].shape[1]))
+    for b in range(c):
+        ids = lev[:, b].astype(np.int64) - 1
+        if ids.size and (ids.min() < 0 or ids.max() >= A[b].shape[0]):
+            raise ValueError(f"level ids of covariate {b} must be within 1..{A[b].shape[0]}")
+        tot = tot + A[b][ids]
+    if ctns_confounder is not None:
+        tot = tot + np.asarray(ctns_confounder, dtype=np.float64).reshape(lev.shape[0], -1) @ A[c]
+    return np.asfortranarray(tot.T)
+
+
+def sample_neighbors(cfd_factors, levels, ctns_confounder=None, k=10, metric="cosine", device=0):
+    """The k nearest samples of every sample: api.neighbors() on sample_embeddings() against itself.  Samples that share
+    every level have equal embeddings: they tie, and ties list by ascending sample.  -> dict(index=(n, k) int32 0-based
+    samples, score=(n, k)); open slots -1 / NaN."""
+    from . import api
+    return api.neighbors(sample_embeddings(cfd_factors, levels, ctns_confounder), None, k=k, metric=metric, device=device)

@@ -1,0 +1,351 @@
+"""insider_hip_neighbors on the device against the numpy yardstick posthoc.neighbors_host().
+
+Every call goes through ctypes with outputs prefilled with sentinels and NGUARD guard elements past nq * k; the guards must
+be unchanged after every call, and after a refused call the whole output is.
+
+Where the arithmetic is exact (integer entries: every score is exact in fp64 whatever the summation order) indices and
+scores must EQUAL the yardstick's.  With real-valued inputs the bound is derived, not fitted: with u = 2^-53 a K-term fp64
+dot in any order errs by at most K u |q| |b| to first order and the normalisation adds a few u, so
+tol = 4 (K + 4) 2^-52 |q| |b| for dot and the same with |q| |b| = 1 for cosine covers the device's and the yardstick's
+error together."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import __graft_entry__ as ge
+from insider_amd import _lib, api, posthoc
+
+pytestmark = pytest.mark.gpu
+
+NGUARD = 7
+IDX_SENTINEL = -77
+SCORE_SENTINEL = 12345.678
+COS, DOT = 0, 1
+METRIC = {COS: "cosine", DOT: "dot"}
+
+
+@pytest.fixture(scope="module")
+def lib():
+    ge.build()
+    return _lib.load()
+
+
+def call(lib, Q, B, k, metric, off, nq=None, nb=None, K=None, qptr=None, expect=_lib.OK, null=()):
+    """One guarded call.  Q / B: column-major K x n arrays; qptr: a raw address for the queries (a window of B)."""
+    Kq, nq_ = Q.shape
+    nq = nq_ if nq is None else nq
+    nb = B.shape[1] if nb is None else nb
+    K = Kq if K is None else K
+    rows = max(nq_, 0)
+    idx = np.full(rows * max(k, 1) + NGUARD, IDX_SENTINEL, dtype=np.int32)
+    sc = np.full(rows * max(k, 1) + NGUARD, SCORE_SENTINEL)
+    dp = C.POINTER(C.c_double)
+    qp = C.cast(qptr, dp) if qptr is not None else _lib.ptr(Q)
+    args = [qp, nq, _lib.ptr(B), nb, K, metric, k, off, 0, _lib.ptr(idx, C.c_int32), _lib.ptr(sc)]
+    for pos in null:
+        args[pos] = None
+    status = lib.insider_hip_neighbors(*args)
+    assert status == expect, (status, lib.insider_hip_last_error().decode(errors="replace"))
+    used = rows * k if status == _lib.OK else 0
+    assert np.all(idx[used:] == IDX_SENTINEL) and np.all(sc[used:] == SCORE_SENTINEL)
+    if status != _lib.OK:
+        return None
+    return dict(index=idx[:used].reshape(rows, k), score=sc[:used].reshape(rows, k))
+
+
+def window(B, s):
+    """The address of column s of the column-major B."""
+    assert B.flags.f_contiguous
+    return B.ctypes.data + s * B.shape[0] * 8
+
+
+def equal(got, ref):
+    assert np.array_equal(got["index"], ref["index"])
+    assert np.array_equal(got["score"], ref["score"], equal_nan=True)
+
+
+def bits(r):
+    return r["index"].tobytes() + r["score"].tobytes()
+
+
+# ---- 1. exact arithmetic, dot metric --------------------------------------------------------------------------------------
+@pytest.mark.parametrize("K", [1, 3, 4, 5, 15, 16, 17, 31, 32, 33, 63])
+def test_exact_integers_equal_the_yardstick(lib, K):
+    """Entries in -2..2: ties everywhere, so this is the test of the tie rule.  (250, 250) is the self call."""
+    rng = np.random.default_rng(100 + K)
+    for nq, nb in ((1, 1), (1, 17), (15, 16), (17, 33), (33, 250), (250, 250)):
+        B = np.asfortranarray(rng.integers(-2, 3, (K, nb)).astype(np.float64))
+        self_call = nq == nb == 250
+        Q = B if self_call else np.asfortranarray(rng.integers(-2, 3, (K, nq)).astype(np.float64))
+        for k in (1, 2, 10, 64):
+            if self_call:
+                got = call(lib, Q, B, k, DOT, 0, qptr=window(B, 0))
+                ref = posthoc.neighbors_host(B, None, k=k, metric="dot")
+            else:
+                got = call(lib, Q, B, k, DOT, -1)
+                ref = posthoc.neighbors_host(Q, B, k=k, metric="dot")
+            equal(got, ref)
+
+
+# ---- 2. adversarial order ---------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("k", [1, 10, 64])
+def test_adversarial_orders_are_exact(lib, k):
+    """Q = e_1 for 40 queries against nb = 5000 columns (j + 1) e_1: every candidate beats the threshold, so each query's
+    buffer of 32 slots fills after two base tiles of 16 and is merged about 150 times (three merges need nb >= 100); the
+    reversed base: none does after the first k; all columns equal: the tie rule alone decides, the answer is 0..k-1."""
+    K, nq, nb = 5, 40, 5000
+    Q = np.zeros((K, nq), order="F")
+    Q[0] = 1.0
+    up = np.zeros((K, nb), order="F")
+    up[0] = np.arange(1, nb + 1)
+    down = np.asfortranarray(up[:, ::-1])
+    flat = np.zeros((K, nb), order="F")
+    flat[0] = 3.0
+    for B in (up, down, flat):
+        got = call(lib, Q, B, k, DOT, -1)
+        equal(got, posthoc.neighbors_host(Q, B, k=k, metric="dot"))
+    assert np.array_equal(got["index"], np.tile(np.arange(k, dtype=np.int32), (nq, 1)))
+    got = call(lib, Q, up, k, DOT, -1)
+    assert np.array_equal(got["index"][0], np.arange(nb - 1, nb - 1 - k, -1))
+
+
+# ---- 3. real-valued inputs ------------------------------------------------------------------------------------------------
+def real_inputs(K, nq, nb, seed, self_start=None):
+    rng = np.random.default_rng(seed)
+    B = rng.standard_normal((K, nb))
+    B[:, rng.random(nb) < 0.1] *= 1e-3
+    B[:, rng.random(nb) < 0.1] *= 1e3
+    B = np.asfortranarray(B)
+    if self_start is not None:
+        return np.asfortranarray(B[:, self_start:self_start + nq]), B
+    Q = rng.standard_normal((K, nq))
+    Q[:, rng.random(nq) < 0.1] *= 1e-3
+    Q[:, rng.random(nq) < 0.1] *= 1e3
+    return np.asfortranarray(Q), B
+
+
+def reference_scores(Q, B, metric):
+    """The float64 score of every pair and its tolerance (nq x nb each)."""
+    K = Q.shape[0]
+    nrm = np.sqrt((Q * Q).sum(axis=0))[:, None] * np.sqrt((B * B).sum(axis=0))[None, :]
+    S = Q.T @ B
+    eps = 4.0 * (K + 4) * 2.0 ** -52
+    if metric == COS:
+        return S / nrm, np.full(S.shape, eps)
+    return S, eps * nrm
+
+
+def eligible(Q, B, metric, off):
+    """Who may be whose neighbour (nq x nb)."""
+    nq, nb = Q.shape[1], B.shape[1]
+    elig = np.ones((nq, nb), dtype=bool)
+    if metric == COS:
+        elig &= ((Q * Q).sum(axis=0) > 0)[:, None] & ((B * B).sum(axis=0) > 0)[None, :]
+    if off >= 0:
+        elig[np.arange(nq), off + np.arange(nq)] = False
+    return elig
+
+
+def check_rule3(got, S, T, k, elig):
+    """(a) - (d) of the bound.  A row with fewer than k eligible candidates returns all of them and ends in -1 / NaN."""
+    idx, sc = got["index"].astype(np.int64), got["score"]
+    nq, nb = S.shape
+    fill = np.minimum(elig.sum(axis=1), k)
+    slot = np.arange(k)[None, :] < fill[:, None]
+    assert np.array_equal(idx >= 0, slot) and np.all(idx[~slot] == -1) and np.all(np.isnan(sc[~slot]))
+    assert np.all(np.isfinite(sc[slot])) and idx.max() < nb
+    rows = np.arange(nq)[:, None]
+    safe = np.where(slot, idx, 0)
+    assert np.all(elig[rows, safe][slot])
+    assert all(len(set(r[r >= 0])) == f for r, f in zip(idx, fill))
+    # (a) every reported score is the pair's reference score within tol
+    err = np.where(slot, np.abs(sc - S[rows, safe]), 0.0)
+    print("rule 3: max (a) error / tol", float(np.max(err / T[rows, safe])))
+    assert np.all(err <= T[rows, safe])
+    # (b) non-increasing; exactly equal scores in ascending index
+    both = slot[:, 1:]
+    d = np.diff(sc, axis=1)
+    assert np.all(d[both] <= 0) and np.all(np.diff(idx, axis=1)[both & (d == 0)] > 0)
+    full = fill == k
+    if not full.any():
+        return
+    idx, sc, S, T, elig = idx[full], sc[full], S[full], T[full], elig[full]
+    rows = np.arange(idx.shape[0])[:, None]
+    # (c) nothing left out beats the reported k-th score by more than the two tolerances
+    out = elig.copy()
+    out[rows, idx] = False
+    kth, kth_tol = sc[:, -1:], T[rows, idx][:, -1:]
+    assert np.all(np.where(out, S - (kth + T + kth_tol), -np.inf) <= 0)
+    # (d) nothing returned lies below the reference's k-th score by more than the two tolerances
+    Se = np.where(elig, S, -np.inf)
+    ref_pos = np.argpartition(-Se, k - 1, axis=1)[:, k - 1:k]
+    ref_kth, ref_tol = Se[rows, ref_pos], T[rows, ref_pos]
+    assert np.all(S[rows, idx] >= ref_kth - (T[rows, idx] + ref_tol))
+
+
+@pytest.mark.parametrize("K", [7, 30, 48])
+@pytest.mark.parametrize("shape", [(700, 5000), (33, 250)])
+def test_real_inputs_within_the_derived_bound(lib, K, shape):
+    """(700, 5000): separate queries; (33, 250): the queries are the window of the base that starts at 100."""
+    nq, nb = shape
+    start = 100 if shape == (33, 250) else None
+    Q, B = real_inputs(K, nq, nb, 7 * K + nq, self_start=start)
+    off = -1 if start is None else start
+    for metric in (COS, DOT):
+        S, T = reference_scores(Q, B, metric)
+        for k in (1, 10, 64):
+            got = call(lib, Q, B, k, metric, off, qptr=None if start is None else window(B, start))
+            check_rule3(got, S, T, k, eligible(Q, B, metric, off))
+
+
+# ---- 4. open slots ----------------------------------------------------------------------------------------------------------
+def test_open_slots(lib):
+    rng = np.random.default_rng(4)
+    K = 6
+    # nb - 1 < k under self exclusion: the head is right, the tail open
+    B = np.asfortranarray(rng.integers(-2, 3, (K, 9)).astype(np.float64))
+    got = call(lib, B, B, 12, DOT, 0, qptr=window(B, 0))
+    equal(got, posthoc.neighbors_host(B, None, k=12, metric="dot"))
+    assert np.all(got["index"][:, :8] >= 0) and np.all(got["index"][:, 8:] == -1) and np.all(np.isnan(got["score"][:, 8:]))
+    # a base in which fewer than k columns are non-zero
+    nb, live = 40, (3, 17, 18, 39)
+    B = np.zeros((K, nb), order="F")
+    for j in live:
+        B[:, j] = rng.integers(1, 3, K)
+    Q = np.asfortranarray(rng.integers(-2, 3, (K, 21)).astype(np.float64))
+    Q[:, 0] = 1.0
+    Q[:, [5, 20]] = 0.0                                                   # zero-norm queries
+    k = 10
+    got = call(lib, Q, B, k, COS, -1)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        S, T = reference_scores(Q, B, COS)
+    check_rule3(got, S, T, k, eligible(Q, B, COS, -1))
+    assert np.all(got["index"][[5, 20]] == -1) and np.all(np.isnan(got["score"][[5, 20]]))
+    other = [i for i in range(21) if i not in (5, 20)]
+    assert np.all(np.sort(got["index"][other, :4], axis=1) == np.array(live)) and np.all(got["index"][other, 4:] == -1)
+    # under dot the zero columns are ordinary candidates of score 0, in ascending index
+    got = call(lib, Q, B, k, DOT, -1)
+    equal(got, posthoc.neighbors_host(Q, B, k=k, metric="dot"))
+    zeros = [j for j in range(nb) if j not in live]
+    assert list(got["index"][5]) == list(range(k)) and np.all(got["score"][5] == 0.0)
+    assert list(got["index"][0][:4]) == sorted(live, key=lambda j: (-B[:, j].sum(), j))
+    assert list(got["index"][0][4:]) == zeros[:k - 4] and np.all(got["score"][0][4:] == 0.0)
+    # the self call under cosine on a matrix with zero columns (elastic-net fits produce them)
+    Cm = np.asfortranarray(rng.standard_normal((K, 50)))
+    Cm[:, [0, 7, 31, 49]] = 0.0
+    got = call(lib, Cm, Cm, 5, COS, 0, qptr=window(Cm, 0))
+    assert np.all(got["index"][[0, 7, 31, 49]] == -1) and not np.isin(got["index"], (0, 7, 31, 49)).any()
+    with np.errstate(invalid="ignore", divide="ignore"):
+        S, T = reference_scores(Cm, Cm, COS)
+    check_rule3(got, S, T, 5, eligible(Cm, Cm, COS, 0))
+
+
+# ---- 5. window invariance and repeatability -------------------------------------------------------------------------------------
+@pytest.mark.parametrize("metric", [COS, DOT])
+def test_windows_and_repeats_are_bit_identical(lib, metric):
+    K, nb, k = 30, 250, 10
+    _, B = real_inputs(K, 1, nb, 55)
+    full = call(lib, B, B, k, metric, 0, qptr=window(B, 0))
+    again = call(lib, B, B, k, metric, 0, qptr=window(B, 0))
+    assert bits(full) == bits(again)
+    for s, m in ((0, 1), (1, 16), (7, 33), (233, 17)):
+        Q = np.asfortranarray(B[:, s:s + m])
+        part = call(lib, Q, B, k, metric, s, qptr=window(B, s))
+        assert bits(part) == bits(dict(index=full["index"][s:s + m], score=full["score"][s:s + m])), (s, m)
+        copy = call(lib, Q, B, k, metric, s)                                 # the same window from a buffer of its own
+        assert bits(copy) == bits(part)
+
+
+# ---- 6. C-ABI errors ------------------------------------------------------------------------------------------------------------
+def test_bad_arguments_are_refused_and_write_nothing(lib):
+    rng = np.random.default_rng(6)
+    K = 5
+    B = np.asfortranarray(rng.standard_normal((K, 20)))
+    Q = np.asfortranarray(rng.standard_normal((K, 4)))
+    bad = _lib.ERR_ARG
+    for pos in (0, 2, 9, 10):                                                # Q, B, idx_out, score_out
+        call(lib, Q, B, 3, COS, -1, expect=bad, null=(pos,))
+    big = np.zeros((64, 4), order="F")
+    call(lib, big, np.zeros((64, 20), order="F"), 3, DOT, -1, expect=bad)   # K = 64
+    call(lib, Q, B, 3, COS, -1, K=0, expect=bad)
+    call(lib, Q, B, 3, COS, -1, K=-1, expect=bad)
+    call(lib, Q, B, 0, COS, -1, expect=bad)
+    call(lib, Q, B, 65, COS, -1, expect=bad)
+    call(lib, Q, B, 3, COS, -1, nq=-1, expect=bad)
+    call(lib, Q, B, 3, COS, -1, nb=0, expect=bad)
+    call(lib, Q, B, 3, COS, -1, nb=-5, expect=bad)
+    call(lib, Q, B, 3, COS, -1, nb=2 ** 31, expect=bad)                      # (refused before B is read)
+    call(lib, Q, B, 3, 2, -1, expect=bad)
+    call(lib, Q, B, 3, -1, -1, expect=bad)
+    call(lib, Q, B, 3, COS, -2, expect=bad)
+    call(lib, Q, B, 3, COS, 17, expect=bad)                                  # 17 + 4 > 20
+    for val in (np.nan, np.inf, -np.inf):
+        Qn, Bn = Q.copy(order="F"), B.copy(order="F")
+        Qn[2, 3] = val
+        Bn[4, 19] = val
+        call(lib, Qn, B, 3, DOT, -1, expect=bad)
+        call(lib, Q, Bn, 3, DOT, -1, expect=bad)
+        call(lib, Bn, Bn, 3, COS, 0, qptr=window(Bn, 0), expect=bad)
+    assert b"finite" in lib.insider_hip_last_error()
+    # what is allowed: the last window; no queries (OK, nothing written)
+    assert call(lib, Q, B, 3, COS, 16)["index"].shape == (4, 3)
+    got = call(lib, Q, B, 3, COS, -1, nq=0)
+    assert np.all(got["index"] == IDX_SENTINEL) and np.all(got["score"] == SCORE_SENTINEL)
+    # the wrapper reports the library's refusal
+    Qn = Q.copy(order="F")
+    Qn[0, 0] = np.nan
+    with pytest.raises(_lib.InsiderError) as e:
+        api.neighbors(Qn, B, k=3)
+    assert e.value.status == _lib.ERR_ARG
+    assert lib.insider_hip_last_neighbors_ms() >= 0.0
+
+
+# ---- 7. through the layers ------------------------------------------------------------------------------------------------------
+def layer_check(got, E, k, metric):
+    with np.errstate(invalid="ignore", divide="ignore"):
+        S, T = reference_scores(E, E, metric)
+    check_rule3(got, S, T, k, eligible(E, E, metric, 0))
+
+
+def test_gene_and_sample_neighbors_on_random_factors(lib):
+    rng = np.random.default_rng(8)
+    K, p, n, counts, m = 9, 300, 90, (40, 25), 2
+    Cm = np.asfortranarray(rng.standard_normal((K, p)))
+    lev = np.column_stack([rng.integers(1, L + 1, n) for L in counts]).astype(np.int32)
+    A = [rng.standard_normal((L, K)) for L in counts] + [rng.standard_normal((m, K))]
+    Z = rng.standard_normal((n, m))
+    for metric in ("cosine", "dot"):
+        code = api.NEIGHBOR_METRICS[metric]
+        got = posthoc.gene_neighbors(Cm, k=8, metric=metric)
+        assert got["index"].shape == (p, 8) and got["index"].dtype == np.int32
+        layer_check(got, Cm, 8, code)
+        got = posthoc.sample_neighbors(A, lev, Z, k=6, metric=metric)
+        assert got["index"].shape == (n, 6)
+        layer_check(got, posthoc.sample_embeddings(A, lev, Z), 6, code)
+    # without the continuous block samples that share their levels tie exactly: ascending sample, as the yardstick
+    lev2 = np.column_stack([rng.integers(1, 4, n), rng.integers(1, 3, n)]).astype(np.int32)
+    A2 = [np.round(rng.standard_normal((3, K)) * 4), np.round(rng.standard_normal((2, K)) * 4)]   # (exact arithmetic)
+    got = posthoc.sample_neighbors(A2, lev2, k=10, metric="dot")
+    equal(got, posthoc.neighbors_host(posthoc.sample_embeddings(A2, lev2), None, k=10, metric="dot"))
+
+
+def test_cli_writes_the_neighbor_records(tmp_path):
+    from insider_amd import fit as fit_cli
+    rng = np.random.default_rng(9)
+    n, p, K = 60, 45, 4
+    conf = np.column_stack([rng.integers(1, 4, n), rng.integers(1, 3, n)]).astype(np.int32)
+    np.save(tmp_path / "X.npy", rng.standard_normal((n, p)))
+    np.save(tmp_path / "L.npy", conf)
+    out = tmp_path / "out"
+    assert fit_cli.main(["--x", str(tmp_path / "X.npy"), "--levels", str(tmp_path / "L.npy"), "--rank", str(K), "--lambda", "1",
+                         "--alpha", "0.2", "--max-iter", "3", "--gene-neighbors", "5", "--sample-neighbors", "5",
+                         "--out", str(out)]) == 0
+    gi, gs = np.load(out / "nn_gene_index.npy"), np.load(out / "nn_gene_score.npy")
+    si, ss = np.load(out / "nn_sample_index.npy"), np.load(out / "nn_sample_score.npy")
+    assert gi.shape == gs.shape == (p, 5) and si.shape == ss.shape == (n, 5)
+    assert gi.dtype == si.dtype == np.int32 and gs.dtype == ss.dtype == np.float64
+    Cm = np.load(out / "C.npy")
+    A = [np.load(out / f"A{i}.npy") for i in range(2)]
+    layer_check(dict(index=gi, score=gs), np.asfortranarray(Cm), 5, COS)
+    layer_check(dict(index=si, score=ss), posthoc.sample_embeddings(A, conf), 5, COS)
