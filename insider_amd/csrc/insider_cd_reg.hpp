@@ -11,7 +11,8 @@
 // one per coordinate, whose byte offsets the order table holds as a successor list (34 dwords loaded into SGPRs at
 // the start of a sweep; block k reads its successor from its own register).  Inside block k everything is static — the Gram operand is the register holding G[u][k], the lane that
 // owns k is k % 16, and its (negated) increment reaches the row as the DPP row_newbcast:k%16 source operand of a
-// 64-bit v_fmac_f64 (gfx90a+ "DP ALU DPP").  Per step and wave (4 genes): 6 vector + 4 scalar instructions (round 3: the
+// 64-bit v_fmac_f64 (gfx90a+ "DP ALU DPP").  Per step and wave (4 genes): 5 vector + 3 scalar instructions + one s_nop for K <= 30 (the coefficient update waits for the exit
+// block, REG_STEP_HEAD below; K = 31 ... 48 keep it in the step: 6 vector instructions) (round 3: the
 // soft threshold is the hardware's output clamp on a scaled gradient, RegState below), no memory or LDS access; the sweep is one inline-asm block (the compiler turns a C++ switch into a compare tree with
 // register copies at the merge).  Without LDS the occupancy is set by registers alone (REG_WAVES(KMAX) waves per
 // SIMD), where the LDS-resident variant (insider_cd_row16.hpp) held 5 waves per CU at K = 30.
@@ -34,7 +35,8 @@ constexpr int REG_BLOCK = INSIDER_REG_BLOCK;   // bytes between the code blocks 
 // and the Gram registers hold G / (2 la).  Then  soft(h, la) = h - clamp(h, -la, la) = 2 la (y - clamp01(y)), and the
 // hardware's output clamp to [0, 1] does the soft threshold in ONE instruction where min + max took two:
 //   c = clamp01(y);  e = y - c;  dn = beta - e tau  (minus the increment);  beta -= dn;  y_u += bcast(dn) Ghat_u[k]
-// — 4 + 2 vector instructions per step instead of 5 + 2, and a dependent chain of 3 before the DPP fmacs instead of 4.
+// — 4 + 2 vector instructions per step instead of 5 + 2, and a dependent chain of 3 before the DPP fmacs instead of 4
+// (K <= 30: `beta -= dn` once per sweep, in the exit block: 3 + 2, REG_STEP_HEAD).
 // Exact zeros survive: |h| <= la  <=>  0 <= y <= 1  =>  c = y, e = 0, dn = beta, beta - dn = 0 exactly.  The offset costs
 // no accuracy that matters: y is rounded at 1.1e-16 absolute, i.e. h at 2.2e-16 la.
 template <int SLOTS>
@@ -52,24 +54,36 @@ struct RegState {
 // straddle a 4 GiB boundary and the high word of every block address is the same (vcc_hi, set once).  Block k forms its
 // successor's address from its own table register s[65 + k] in vcc_lo while the vector chain runs, and jumps: no
 // position counter, M0 untouched.  Critical chain per step: clamp, sub, fma (dn), DPP fmac.  Hazards respected by
-// construction: >= 2 instructions between the write of dn and its DPP read; exec is written by SALU only; nothing in a
+// construction: >= 2 instructions between the write of dn and its DPP read (s_nop 0 and the exec restore); exec is written by SALU only; nothing in a
 // block writes vcc_hi.
-// The four scalar-like instructions of a step do useful work on the owner lane of each row only: they run under a four-lane
-// exec mask (the DPP fmacs that follow need every lane).  Same instruction count as narrowing the mask around the beta
-// update alone, but the part sustains a higher clock (round 3, tools/ab_variants.sh: +4 % sweep rate, bit-identical).
+// The scalar-like instructions of a step (three for K <= 30, four with the beta update for K > 30) do useful work on the owner
+// lane of each row only: they run under a four-lane exec mask (the DPP fmacs that follow need every lane).  Same instruction
+// count as narrowing the mask around the beta update alone (round 3, when the update was in every step), but the part sustains a higher clock (round 3, tools/ab_variants.sh: +4 % sweep rate, bit-identical).
 // The address add sits between the clamp and the subtraction that depends on it (round 4: in the shadow of the clamp's
 // result latency instead of in front of the chain, sweep kernel 2.08 -> 2.00 ms per launch at c3, tools/exp_probe.sh).
 // Measured and NOT adopted in round 4 (same tool): the head on all lanes with the beta update as a bank-masked
 // DPP fmac on a lane indicator (no exec writes: slower, 2.17-2.24 ms — four more full-width fp64 instructions per step
 // cost more clock than the two exec writes cost issue slots); wave priorities by hardware wave id (slower); the exec
 // narrowing after the clamp (slower); other positions of the add (equal).
-#define REG_BLOCK_HEAD(KK, HS, BS, IS, IT) REG_ORG(KK) REG_STEP_HEAD(HS, BS, IS, IT)
-#define REG_STEP_HEAD(HS, BS, IS, IT)                            \
+// The coefficient itself is NOT updated in the step (K <= 30): a sweep visits every coordinate exactly once (the order is a sort
+// of all K keys, include/insider_perm.h; screened-out coordinates are visited with tau = beta = 0) and the only reader of a
+// coordinate's beta inside the sweep is that coordinate's own head, so the owner lanes keep their (negated) increments — one
+// register per coordinate slot, dn0 / dn1: lane i owns coordinates i and 16 + i, a shared register would lose the first when the
+// second is stepped — and the exit block applies them in two full-width instructions, beta_s = fma(-1.0, dn_s, beta_s): the same
+// instruction on the same operands per lane as the per-step update it replaces, so every iterate is bit-identical.  A step is
+// 5 vector instructions instead of 6 (a sweep of K = 30 issues 28 fewer); `s_nop 0` keeps the DPP hazard distance the update used
+// to provide.  Lanes whose coordinate is never visited (coordinates >= K, slot 1 of lanes >= KMAX - 16) must hold an exact zero in
+// dn_s at every sweep.  The two registers cost nothing: dn0 / dn1 ARE the pinned pairs v[2:3] / v[4:5] of the exit block's row
+// reduction, which are idle while a sweep runs; the exit block consumes them in its first two vector instructions, then uses
+// them as its temporaries as before, and Lgo — which the statement's entry and every further sweep pass through — zeroes them
+// again in front of the jump into the sweep's first block.
+#define REG_BLOCK_HEAD(KK, HS, BS, IS, IT, DN) REG_ORG(KK) REG_STEP_HEAD(HS, BS, IS, IT, DN)
+#define REG_STEP_HEAD(HS, BS, IS, IT, DN)                        \
     "s_lshl_b64 exec, %[lm], " #IT "\n"                          \
-    "v_max_f64 %[dn], %[" HS "], %[" HS "] clamp\n"              \
-    "v_add_f64 %[dn], %[" HS "], -%[dn]\n"                       \
-    "v_fma_f64 %[dn], -%[dn], %[" IS "], %[" BS "]\n"            \
-    "v_fmac_f64 %[" BS "], -1.0, %[dn]\n"                        \
+    "v_max_f64 %[" DN "], %[" HS "], %[" HS "] clamp\n"          \
+    "v_add_f64 %[" DN "], %[" HS "], -%[" DN "]\n"               \
+    "v_fma_f64 %[" DN "], -%[" DN "], %[" IS "], %[" BS "]\n"    \
+    "s_nop 0\n"                                                  \
     "s_mov_b64 exec, -1\n"
 // Round 5: the successor list holds ABSOLUTE code addresses as (lo, hi) dword pairs — entry e (0 = the sweep's first block,
 // 1 + k = the block visited after coordinate k) sits in the aligned scalar pair s[REG_PB + 2 e : REG_PB + 2 e + 1], REG_PB =
@@ -79,12 +93,13 @@ struct RegState {
 #define REG_PB REG_STR(REG_PBN)
 #define REG_JUMP(KK) "s_setpc_b64 s[" REG_PB "+2+2*" #KK ":" REG_PB "+3+2*" #KK "]\n"
 #define REG_ORG(KK) ".org Lc%= + " REG_STR(INSIDER_REG_BLOCK) "*" #KK "\n"
-#define REG_FMAC(H, GK, IT) "v_fmac_f64_dpp %[" H "], %[dn], %[" GK "] row_newbcast:" #IT " row_mask:0xf bank_mask:0xf\n"
+#define REG_FMAC_DN(H, GK, IT, DN) "v_fmac_f64_dpp %[" H "], %[" DN "], %[" GK "] row_newbcast:" #IT " row_mask:0xf bank_mask:0xf\n"
+#define REG_FMAC(H, GK, IT) REG_FMAC_DN(H, GK, IT, "dn")   /* K > 30: one increment register, beta updated in the step */
 #define REG_BLOCK2_LO(KK) \
-    REG_BLOCK_HEAD(KK, "h0", "b0", "i0", KK) REG_FMAC("h0", "ga" #KK, KK) REG_FMAC("h1", "gb" #KK, KK) REG_JUMP(KK)
+    REG_BLOCK_HEAD(KK, "h0", "b0", "i0", KK, "dn0") REG_FMAC_DN("h0", "ga" #KK, KK, "dn0") REG_FMAC_DN("h1", "gb" #KK, KK, "dn0") REG_JUMP(KK)
 #define REG_BLOCK2_HI(KK, IT) \
-    REG_BLOCK_HEAD(KK, "h1", "b1", "i1", IT) REG_FMAC("h0", "ga" #KK, IT) REG_FMAC("h1", "gb" #KK, IT) REG_JUMP(KK)
-#define REG_BLOCK1(KK) REG_BLOCK_HEAD(KK, "h0", "b0", "i0", KK) REG_FMAC("h0", "ga" #KK, KK) REG_JUMP(KK)
+    REG_BLOCK_HEAD(KK, "h1", "b1", "i1", IT, "dn1") REG_FMAC_DN("h0", "ga" #KK, IT, "dn1") REG_FMAC_DN("h1", "gb" #KK, IT, "dn1") REG_JUMP(KK)
+#define REG_BLOCK1(KK) REG_BLOCK_HEAD(KK, "h0", "b0", "i0", KK, "dn0") REG_FMAC_DN("h0", "ga" #KK, KK, "dn0") REG_JUMP(KK)
 // ---- blocks of TWO coordinate steps (round 5) -----------------------------------------------------------------------------
 // A launch whose waves are mostly alone on their SIMDs (few genes, or the tail of the longest genes) is bound by ONE wave's
 // step: its instructions at one per ~6 cycles plus the ~28 cycles an instruction buffer takes to refill behind the computed
@@ -99,14 +114,14 @@ struct RegState {
 // (One LINE per step: the compiler's branch relaxation prices an asm statement at 20 bytes per line, and 452 blocks of 18 lines
 // would make it turn the sweep loop's back edge into a four-instruction long branch.  The step is therefore an ASSEMBLER macro,
 // defined inside the statement that uses it (every inline-asm statement is assembled by a parser of its own) and purged at its
-// end — the same eight instructions as REG_STEP_HEAD + two REG_FMAC; a one-slot step has no second fmac.)
+// end — the same instructions as REG_STEP_HEAD + two REG_FMAC_DN; a one-slot step has no second fmac.)
 #define REG_STEP_MACROS                                                \
     ".macro INSIDER_CD_STEP2 it, h, b, i, lm, dn, h0, h1, g0, g1\n"    \
     "s_lshl_b64 exec, \\lm, \\it\n"                                    \
     "v_max_f64 \\dn, \\h, \\h clamp\n"                                \
     "v_add_f64 \\dn, \\h, -\\dn\n"                                    \
     "v_fma_f64 \\dn, -\\dn, \\i, \\b\n"                              \
-    "v_fmac_f64 \\b, -1.0, \\dn\n"                                    \
+    "s_nop 0\n"                                                       \
     "s_mov_b64 exec, -1\n"                                             \
     "v_fmac_f64_dpp \\h0, \\dn, \\g0 row_newbcast:\\it row_mask:0xf bank_mask:0xf\n" \
     "v_fmac_f64_dpp \\h1, \\dn, \\g1 row_newbcast:\\it row_mask:0xf bank_mask:0xf\n" \
@@ -116,13 +131,13 @@ struct RegState {
     "v_max_f64 \\dn, \\h, \\h clamp\n"                                \
     "v_add_f64 \\dn, \\h, -\\dn\n"                                    \
     "v_fma_f64 \\dn, -\\dn, \\i, \\b\n"                              \
-    "v_fmac_f64 \\b, -1.0, \\dn\n"                                    \
+    "s_nop 0\n"                                                       \
     "s_mov_b64 exec, -1\n"                                             \
     "v_fmac_f64_dpp \\h, \\dn, \\g0 row_newbcast:\\it row_mask:0xf bank_mask:0xf\n" \
     ".endm\n"
-#define REG_STEP_LO(KK) "INSIDER_CD_STEP2 " #KK ", %[h0], %[b0], %[i0], %[lm], %[dn], %[h0], %[h1], %[ga" #KK "], %[gb" #KK "]\n"
-#define REG_STEP_HI(KK, IT) "INSIDER_CD_STEP2 " #IT ", %[h1], %[b1], %[i1], %[lm], %[dn], %[h0], %[h1], %[ga" #KK "], %[gb" #KK "]\n"
-#define REG_STEP1_LO(KK) "INSIDER_CD_STEP1 " #KK ", %[h0], %[b0], %[i0], %[lm], %[dn], %[ga" #KK "]\n"
+#define REG_STEP_LO(KK) "INSIDER_CD_STEP2 " #KK ", %[h0], %[b0], %[i0], %[lm], %[dn0], %[h0], %[h1], %[ga" #KK "], %[gb" #KK "]\n"
+#define REG_STEP_HI(KK, IT) "INSIDER_CD_STEP2 " #IT ", %[h1], %[b1], %[i1], %[lm], %[dn1], %[h0], %[h1], %[ga" #KK "], %[gb" #KK "]\n"
+#define REG_STEP1_LO(KK) "INSIDER_CD_STEP1 " #KK ", %[h0], %[b0], %[i0], %[lm], %[dn0], %[ga" #KK "]\n"
 #define REGP_LO(A, B) ".p2align 7\n" REG_STEP_LO(A) REG_STEP_LO(B) REG_JUMP(B)
 #define REGP_HI(A, IA, B, IB) ".p2align 7\n" REG_STEP_HI(A, IA) REG_STEP_HI(B, IB) REG_JUMP(B)
 #define REGP1_LO(A, B) ".p2align 7\n" REG_STEP1_LO(A) REG_STEP1_LO(B) REG_JUMP(B)
@@ -186,8 +201,8 @@ struct RegState {
     "v_mov_b32_dpp " D0 ", " S0 " " CTRL " row_mask:0xf bank_mask:0xf bound_ctrl:1\n"           \
     "v_mov_b32_dpp " D1 ", " S1 " " CTRL " row_mask:0xf bank_mask:0xf bound_ctrl:1\n"
 // sum over each 16-lane row of la * t (t in v[2:3]) -> v[2:3]: row16_sum(la * t) as the compiler contracted it.  (The tails keep
-// three of their values in the pinned pairs and in dn, which is free between sweeps: the loop needs no more registers than the C++
-// bookkeeping took.)
+// their values in the pinned pairs, which carry the sweep's increments into the exit block as dn0 / dn1 and are zeroed again
+// at Lgo.)
 #define REG_ROWSUM                                                    \
     "v_mul_f64 v[4:5], %[las], v[2:3]\n"                              \
     "s_nop 1\n"                                                       \
@@ -218,12 +233,16 @@ struct RegState {
     "s_cmp_lt_i32 %[sw], %[stop]\n"                                   \
     "s_cbranch_scc0 Lout%=\n"                                         \
     "Lgo%=:\n"                                                        \
+    REG_DN_ZERO                                                       \
     "s_waitcnt lgkmcnt(0)\n"                                          \
     "s_setpc_b64 s[" REG_PB ":" REG_PB "+1]\n"                        \
     "Lout%=:\n"                                                       \
     "s_waitcnt lgkmcnt(0)\n"
 // (the stash values a tail needs — D, the sweep-start beta and what — are requested at the END of the previous tail, behind its
 // writes, into registers the blocks do not touch: a tail starts computing at once)
+// (the increment registers of the coming sweep: an exact zero in every lane, REG_STEP_HEAD)
+#define REG_DN_ZERO2 "v_mov_b64 %[dn0], 0\n v_mov_b64 %[dn1], 0\n"
+#define REG_DN_ZERO1 "v_mov_b64 %[dn0], 0\n"
 #define REG_LDS2                                                      \
     "ds_read_b64 %[t0], %[la]\n"                                      \
     "ds_read_b64 %[t1], %[la] offset:512\n"                           \
@@ -235,20 +254,24 @@ struct RegState {
     "ds_read_b64 %[t0], %[la]\n"                                      \
     "ds_read_b64 %[t2], %[la] offset:1024\n"                          \
     "ds_read_b64 %[t4], %[la] offset:2048\n"
+// (the increments of the sweep first — dn0 = v[2:3], dn1 = v[4:5] — : everything below reads the updated beta, and the two
+// pairs are the tail's temporaries from there on)
 #define REG_TAIL2                                                     \
     REG_NEXT_LIST                                                     \
+    "v_fmac_f64 %[b0], -1.0, %[dn0]\n"                                \
+    "v_fmac_f64 %[b1], -1.0, %[dn1]\n"                                \
     "v_fma_f64 %[t0], %[b0], %[t0], -%[h0]\n"                         \
     "v_fma_f64 %[t1], %[b1], %[t1], -%[h1]\n"                         \
     "v_add_f64 %[t4], %[t0], %[t4]\n"                                 \
-    "v_add_f64 %[dn], %[b0], -%[t2]\n"                                \
+    "v_add_f64 v[4:5], %[b0], -%[t2]\n"                               \
     "v_add_f64 %[t4], %[t4], 1.0\n"                                   \
     "v_add_f64 %[t5], %[t1], %[t5]\n"                                 \
     "v_add_f64 %[t2], |%[b0]|, -|%[t2]|\n"                            \
-    "v_fma_f64 %[t4], %[dn], %[t4], 0\n"                              \
-    "v_add_f64 %[dn], %[b1], -%[t3]\n"                                \
+    "v_fma_f64 %[t4], v[4:5], %[t4], 0\n"                             \
+    "v_add_f64 v[4:5], %[b1], -%[t3]\n"                               \
     "v_add_f64 %[t5], %[t5], 1.0\n"                                   \
     "v_add_f64 %[t3], |%[b1]|, -|%[t3]|\n"                            \
-    "v_fmac_f64 %[t4], %[dn], %[t5]\n"                                \
+    "v_fmac_f64 %[t4], v[4:5], %[t5]\n"                               \
     "v_add_f64 %[t2], %[t2], %[t3]\n"                                 \
     "ds_write_b64 %[la], %[b0] offset:1024\n"                         \
     "ds_write_b64 %[la], %[b1] offset:1536\n"                         \
@@ -258,14 +281,15 @@ struct RegState {
     REG_LDS2 REG_ROWSUM REG_LOOP_END
 #define REG_TAIL1                                                     \
     REG_NEXT_LIST                                                     \
+    "v_fmac_f64 %[b0], -1.0, %[dn0]\n"                                \
     "v_fma_f64 %[t0], %[b0], %[t0], -%[h0]\n"                         \
     "v_add_f64 %[t4], %[t0], %[t4]\n"                                 \
-    "v_add_f64 %[dn], %[b0], -%[t2]\n"                                \
+    "v_add_f64 v[4:5], %[b0], -%[t2]\n"                               \
     "ds_write_b64 %[la], %[b0] offset:1024\n"                         \
     "ds_write_b64 %[la], %[t0] offset:2048\n"                         \
     "v_add_f64 %[t4], %[t4], 1.0\n"                                   \
     "v_add_f64 %[t2], |%[b0]|, -|%[t2]|\n"                            \
-    "v_fma_f64 %[t4], %[dn], %[t4], 0\n"                              \
+    "v_fma_f64 %[t4], v[4:5], %[t4], 0\n"                             \
     "v_add_f64 v[2:3], %[t2], %[t4]\n"                                \
     REG_LDS1 REG_ROWSUM REG_LOOP_END
 #define REG_EPILOGUE(NBLK) REG_ORG(NBLK) " s_waitcnt lgkmcnt(0)\n"   /* exit block */
@@ -311,8 +335,8 @@ struct RegState {
 // The table of blocks carries a NAMED label (one per KMAX: k_cd_cols_reg is the one kernel that inlines the loop), whose address
 // reg_code_base() takes from another asm statement of the same kernel.
 #define REG_LOOP_OUTS2                                                                                                     \
-    [h0] "+v"(S.y[0]), [h1] "+v"(S.y[1]), [b0] "+v"(S.beta[0]), [b1] "+v"(S.beta[1]), [aw] "+v"(accw), [dl] "=&{v[2:3]}"(dl), \
-        [rb] "=&{v[4:5]}"(rb), [dn] "=&v"(dn), [t0] "=&v"(t0), [t1] "=&v"(t1), [t2] "=&v"(t2), [t3] "=&v"(t3), [t4] "=&v"(t4),      \
+    [h0] "+v"(S.y[0]), [h1] "+v"(S.y[1]), [b0] "+v"(S.beta[0]), [b1] "+v"(S.beta[1]), [aw] "+v"(accw),                         \
+        [dn0] "=&{v[2:3]}"(dl), [dn1] "=&{v[4:5]}"(rb), [t0] "=&v"(t0), [t1] "=&v"(t1), [t2] "=&v"(t2), [t3] "=&v"(t3), [t4] "=&v"(t4),      \
         [t5] "=&v"(t5), [sw] "+s"(sw), [off] "+s"(off), [cand] "=&s"(cand)
 #define REG_LOOP_INS_TAIL                                                                                                  \
     [tb0] "s"(tb0), [lm] "s"(lm), [run] "s"(run), [las] "s"(la), [tol] "s"(tol), [stop] "s"(stop), [la] "v"(lds)
@@ -323,7 +347,7 @@ struct RegState {
                                                int &sw, int stop, uint64_t run, double la, double tol, uint32_t lds,     \
                                                double &accw, double &dl, uint64_t &cand)                                 \
     {                                                                                                                    \
-        double dn, rb, t0, t1, t2, t3, t4, t5;                                                                           \
+        double rb, t0, t1, t2, t3, t4, t5;                                                                                  \
         const uint64_t lm = 0x0001000100010001ull;                                                                       \
         asm volatile(REG_LOOP_ENTRY REG_LIST_LO(REG_BLOCK2_LO) REG_HB_##KMAX(REG_HI16) REG_ORG(KMAX) REG_TAIL2                \
                          REG_PAIRS_OPEN REG_LIST_LO(REGP_ROW_LO) REG_HB_##KMAX(REGP_ROW_HI) REG_PAIRS_CLOSE                   \
@@ -339,6 +363,7 @@ struct RegState {
                                                uint64_t, double, double, uint32_t, double &, double &, uint64_t &) {}
 #endif
 #define REG_LDS REG_LDS2
+#define REG_DN_ZERO REG_DN_ZERO2
 #define REG_KM 18
 #define REG_PBN 60
 REG_DEFINE_SWEEP2(18)
@@ -425,17 +450,19 @@ __device__ __forceinline__ void reg_sweep(RegState<2> &, const double (&)[2][32]
 #endif
 
 #undef REG_LDS
+#undef REG_DN_ZERO
 #define REG_LDS REG_LDS1
+#define REG_DN_ZERO REG_DN_ZERO1
 #define REG_KM 16
 #define REG_PBN 64
 #define REG_LOOP_OUTS1                                                                                                      \
-    [h0] "+v"(S.y[0]), [b0] "+v"(S.beta[0]), [aw] "+v"(accw), [dl] "=&{v[2:3]}"(dl), [rb] "=&{v[4:5]}"(rb), [dn] "=&v"(dn),  \
+    [h0] "+v"(S.y[0]), [b0] "+v"(S.beta[0]), [aw] "+v"(accw), [dn0] "=&{v[2:3]}"(dl), [rb] "=&{v[4:5]}"(rb),                 \
         [t0] "=&v"(t0), [t2] "=&v"(t2), [t4] "=&v"(t4), [sw] "+s"(sw), [off] "+s"(off), [cand] "=&s"(cand)
 __device__ __forceinline__ void reg_sweeps(RegState<1> &S, const double (&G)[1][16], const uint32_t *tb0, int &off, int &sw, int stop,
                                            uint64_t run, double la, double tol, uint32_t lds, double &accw, double &dl, uint64_t &cand)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
-    double dn, rb, t0, t2, t4;
+    double rb, t0, t2, t4;
     const uint64_t lm = 0x0001000100010001ull;
     asm volatile(REG_LOOP_ENTRY REG_LIST_LO(REG_BLOCK1) REG_ORG(16) REG_TAIL1 REG_PAIRS_OPEN REG_LIST_LO(REGP1_ROW_LO) REG_PAIRS_CLOSE
                  : REG_LOOP_OUTS1

@@ -2,7 +2,8 @@
 // N identical 128-byte blocks (6 independent v_fma_f64 + the scalar work that picks the next block) visited in a pseudo-random
 // cyclic order (a full-period LCG on the block index, every wave from its own start), 3 waves per SIMD on every CU: time per jump
 // against the table's footprint N x 128 B.  Behind DESIGN.md 9 (blocks of two coordinate steps: 62 KB of blocks did not pay).
-//   hipcc --offload-arch=gfx950 -O3 tools/ubench8.hip -o tools/ubench8 && tools/ubench8
+// Second part (step6 / step5 below): the sweep kernel's step in its two shapes, 6 vector instructions against 5 + s_nop.
+//   hipcc --offload-arch=gfx950 -O3 tools/ubench8.hip -o tools/ubench8 && tools/ubench8      (tools/ubench8 steps: the step shapes only)
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #define STR_(x) #x
@@ -110,6 +111,98 @@ LKERNEL(128)
 LKERNEL(256)
 LKERNEL(512)
 
+// ---- blocks of the sweep kernel's own step (insider_cd_reg.hpp), in its two shapes: what is one VALU instruction of the step worth? --
+// 31 step blocks, 128 bytes apart, each ending in s_setpc_b64 on its own successor pair held in SGPRs (absolute addresses, as the
+// kernel's round-5 list), and a 32nd control block (count down, leave or jump on): one cycle = one "sweep" of 31 steps in the order
+// k -> 5 k + 1 mod 32.  Steps 0..15 work on slot 0 (h0, b0, i0), 16..30 on slot 1, owner lane k % 16, as in the kernel.
+//   SHAPE 6: exec narrow | clamp, sub, fma (dn), beta -= dn | exec full | two DPP fmacs          (the step as it is)
+//   SHAPE 5: exec narrow | clamp, sub, fma (dn_s)           | s_nop 0, exec full | two DPP fmacs  (beta updated once behind the sweep)
+#define SWEEPS 4000
+#define S_LO "0,1,2,3,4,5,6,7,8,9,10,11,12,13,14,15"
+#define S_HI "0,1,2,3,4,5,6,7,8,9,10,11,12,13,14"   /* slot 1: coordinate 16 + k, owner lane k */
+#define S_FMACS(DN, PB)                                                                                     \
+    "v_fmac_f64_dpp %[h0], " DN ", %[g0] row_newbcast:\\k row_mask:0xf bank_mask:0xf\n"                     \
+    "v_fmac_f64_dpp %[h1], " DN ", %[g1] row_newbcast:\\k row_mask:0xf bank_mask:0xf\n"                     \
+    "s_setpc_b64 s[" PB "+2*\\k:" PB "+1+2*\\k]\n"
+#define S_STEP6(H, B, I, PB)                                                                                   \
+    ".p2align 7\n"                                                                                          \
+    "s_lshl_b64 exec, %[lm], \\k\n"                                                                          \
+    "v_max_f64 %[dn0], " H ", " H " clamp\n"                                                                \
+    "v_add_f64 %[dn0], " H ", -%[dn0]\n"                                                                    \
+    "v_fma_f64 %[dn0], -%[dn0], " I ", " B "\n"                                                             \
+    "v_fmac_f64 " B ", -1.0, %[dn0]\n"                                                                      \
+    "s_mov_b64 exec, -1\n" S_FMACS("%[dn0]", PB)
+#define S_STEP5(H, B, I, DN, PB)                                                                               \
+    ".p2align 7\n"                                                                                          \
+    "s_lshl_b64 exec, %[lm], \\k\n"                                                                          \
+    "v_max_f64 " DN ", " H ", " H " clamp\n"                                                                \
+    "v_add_f64 " DN ", " H ", -" DN "\n"                                                                    \
+    "v_fma_f64 " DN ", -" DN ", " I ", " B "\n"                                                             \
+    "s_nop 0\n"                                                                                             \
+    "s_mov_b64 exec, -1\n" S_FMACS(DN, PB)
+#define SBODY(LO, HI, TAIL)                                                                                 \
+    "s_getpc_b64 s[98:99]\n"                                                                                \
+    "Lh%=:\n"                                                                                               \
+    "s_add_u32 s98, s98, Lt%=-Lh%=\n"                                                                       \
+    "s_addc_u32 s99, s99, 0\n"                                                                              \
+    ".irp k,0,1,2,3,4,5,6,7,8,9,10,11,12,13,14,15,16,17,18,19,20,21,22,23,24,25,26,27,28,29,30,31\n"                                                                      \
+    "s_add_u32 s[34+2*\\k], s98, ((5*\\k+1)&31)*128\n"                                                      \
+    "s_addc_u32 s[35+2*\\k], s99, 0\n"                                                                      \
+    ".endr\n"                                                                                               \
+    "s_mov_b32 s33, " STR(SWEEPS) "\n"                                                                      \
+    "s_setpc_b64 s[98:99]\n"                                                                                \
+    ".p2align 8\n"                                                                                          \
+    "Lt%=:\n"                                                                                               \
+    ".irp k," S_LO "\n" LO ".endr\n"                                                                        \
+    ".irp k," S_HI "\n" HI ".endr\n"                                                                        \
+    ".p2align 7\n" TAIL                                                                                     \
+    "s_sub_u32 s33, s33, 1\n"                                                                               \
+    "s_cmp_eq_u32 s33, 0\n"                                                                                 \
+    "s_cbranch_scc1 Le%=\n"                                                                                 \
+    "s_setpc_b64 s[96:97]\n"                                                                                \
+    "Le%=:\n"
+#define S_CLOB "s33", "s34", "s35", "s36", "s37", "s38", "s39", "s40", "s41", "s42", "s43", "s44", "s45", "s46", "s47", "s48", "s49", "s50", \
+    "s51", "s52", "s53", "s54", "s55", "s56", "s57", "s58", "s59", "s60", "s61", "s62", "s63", "s64", "s65", "s66", "s67", "s68", "s69", "s70", \
+    "s71", "s72", "s73", "s74", "s75", "s76", "s77", "s78", "s79", "s80", "s81", "s82", "s83", "s84", "s85", "s86", "s87", "s88", "s89", "s90", \
+    "s91", "s92", "s93", "s94", "s95", "s96", "s97", "s98", "s99", "scc"
+#define SKERNEL(NAME, LO, HI, TAIL)                                                                         \
+    __global__ void __launch_bounds__(256) NAME(double seed, double *out)                                   \
+    {                                                                                                       \
+        double h0 = 0.25 + 1e-3 * threadIdx.x, h1 = 1.5 - h0, b0 = 0.1 * seed, b1 = -b0, i0 = 1e-3, i1 = 2e-3, g0 = 1e-3, g1 = -1e-3; \
+        double dn0 = 0.0, dn1 = 0.0;                                                                        \
+        const unsigned long long lm = 0x0001000100010001ull;                                               \
+        asm volatile(SBODY(LO, HI, TAIL)                                                                    \
+                     : [h0] "+v"(h0), [h1] "+v"(h1), [b0] "+v"(b0), [b1] "+v"(b1), [dn0] "+v"(dn0), [dn1] "+v"(dn1) \
+                     : [i0] "v"(i0), [i1] "v"(i1), [g0] "v"(g0), [g1] "v"(g1), [lm] "s"(lm)                  \
+                     : S_CLOB);                                                                             \
+        if (h0 + h1 + b0 + b1 == 12345.678) out[0] = 1;                                                     \
+    }
+SKERNEL(step6, S_STEP6("%[h0]", "%[b0]", "%[i0]", "34"), S_STEP6("%[h1]", "%[b1]", "%[i1]", "66"), "")
+SKERNEL(step5, S_STEP5("%[h0]", "%[b0]", "%[i0]", "%[dn0]", "34"), S_STEP5("%[h1]", "%[b1]", "%[i1]", "%[dn1]", "66"),
+        "v_fmac_f64 %[b0], -1.0, %[dn0]\n v_fmac_f64 %[b1], -1.0, %[dn1]\n")
+
+template <typename F>
+void run_steps(F kern, const char *name, double *d)
+{
+    for (int wps : {1, 3, 4}) {
+        float best = 1e30f;
+        for (int rep = 0; rep < 3; ++rep) {
+            hipEvent_t e0, e1;
+            (void)hipEventCreate(&e0);
+            (void)hipEventCreate(&e1);
+            (void)hipEventRecord(e0);
+            hipLaunchKernelGGL(kern, dim3(256 * wps), dim3(256), 0, 0, 1.5, d);
+            (void)hipEventRecord(e1);
+            (void)hipDeviceSynchronize();
+            float ms;
+            (void)hipEventElapsedTime(&ms, e0, e1);
+            if (rep > 0 && ms < best) best = ms;   // (the first launch warms up)
+        }
+        printf("%s  waves/SIMD %d: %.3f ms  %.2f ns per block per wave  %.2f ns per block per SIMD\n", name, wps, best,
+               best * 1e6 / SWEEPS / 32, best * 1e6 / SWEEPS / 32 / wps);
+    }
+}
+
 template <typename F>
 void run(F kern, int n, double *d)
 {
@@ -129,10 +222,16 @@ void run(F kern, int n, double *d)
     }
 }
 
-int main()
+int main(int argc, char **)
 {
     double *d;
     (void)hipMalloc(&d, 1 << 16);
+    printf("blocks of the sweep kernel's step, 31 steps + 1 control block per cycle:\n");
+    run_steps(step6, "6 VALU (beta updated in the step)  ", d);
+    run_steps(step5, "5 VALU + s_nop (beta updated once) ", d);
+    run_steps(step6, "6 VALU (again)                     ", d);
+    run_steps(step5, "5 VALU + s_nop (again)             ", d);
+    if (argc > 1) return 0;   // any argument: the step shapes only
     printf("lean blocks (2 VALU + 8 scalar instructions):\n");
     run(l16, 16, d);
     run(l32, 32, d);
