@@ -855,29 +855,44 @@ def _nearest_finished(done, g, n_lambda):
     return best
 
 
+def _usable_clone(hd, base):
+    """The rule of tune()'s handle pools (_tune_clones, _fold_handles, _fold_clones): a handle made from `base` (``_src``) is
+    usable only while it is open and `base` is still the handle it came from (bench.py closes clones between grids; a
+    re-created resident data set is another `base`)."""
+    return bool(getattr(hd, "_h", None)) and getattr(hd, "_src", None) is base
+
+
+def _bring_options(hd, base):
+    """A handle made from `base` copied its options as they stood then: bring the ones set on `base` since across."""
+    for name, value in getattr(base, "_options", {}).items():
+        if getattr(hd, "_options", {}).get(name) != value:
+            hd.set_option(name, value)
+
+
+def _clone(base):
+    hd = base.clone()
+    hd._src = base
+    return hd
+
+
 def _tune_handles(obj, ds, k):
     """k handles on the resident tune() data set: the data set's own plus k - 1 clones (insider_hip_clone: shared device
     arrays, private workspaces), kept on the object for the next call."""
-    # clones whose handle has been closed since (bench.py closes them between grids) are dropped; the others are dropped too
-    # when they belong to another data set handle than `ds` (a re-created resident data set)
-    clones = [hd for hd in obj.get("_tune_clones", []) if getattr(hd, "_h", None) and getattr(hd, "_src", None) is ds]
+    clones = [hd for hd in obj.get("_tune_clones", []) if _usable_clone(hd, ds)]
     while len(clones) < k - 1:
-        hd = ds.clone()
-        hd._src = ds
-        clones.append(hd)
+        clones.append(_clone(ds))
     obj["_tune_clones"] = clones
-    # a clone copies its source's options as they stood at clone time: bring the ones set on `ds` since then across
     for hd in clones[: k - 1]:
-        for name, value in getattr(ds, "_options", {}).items():
-            if getattr(hd, "_options", {}).get(name) != value:
-                hd.set_option(name, value)
+        _bring_options(hd, ds)
     return [ds] + clones[: k - 1]
 
 
 def _fold_handles(obj, ds):
-    """The fold data sets ds.fold(1..F) of the resident tune data set, derived once and kept on the object."""
+    """The fold data sets ds.fold(1..F) of the resident tune data set, derived once and kept on the object, and
+    ``obj["_fold_clones"]``: {(worker, fold index): clone of that fold's handle}, the usable ones of earlier calls.  All of
+    them carry the options of `ds` as they stand now."""
     hs = obj.get("_fold_handles", [])
-    if not hs or any(not getattr(hd, "_h", None) or getattr(hd, "_src", None) is not ds for hd in hs):
+    if not hs or not all(_usable_clone(hd, ds) for hd in hs):
         fold_id = np.asarray(obj["fold_id"])
         ds.set_folds(fold_id, int(fold_id.max()))
         hs = []
@@ -887,124 +902,117 @@ def _fold_handles(obj, ds):
             hs.append(hd)
         obj["_fold_handles"] = hs
         obj["_fold_clones"] = {}
+    obj["_fold_clones"] = {(w, f): hd for (w, f), hd in obj.get("_fold_clones", {}).items() if _usable_clone(hd, hs[f])}
+    for hd in hs:
+        _bring_options(hd, ds)
+    for (w, f), hd in obj["_fold_clones"].items():
+        _bring_options(hd, hs[f])
     return hs
 
 
-def _tune_folds(obj, lat, lam, alp, out_dir, rng, rank, world, timings, concurrent):
-    """tune(folds=True): every point of the rank sweep and of the (lambda, alpha) grid is fitted once per fold."""
+def _fold_clone(obj, base, worker, f):
+    """Worker `worker` > 0's clone of the fold handle `base` of fold index f: made on first use, kept on the object."""
+    clones = obj["_fold_clones"]
+    if (worker, f) not in clones:
+        clones[(worker, f)] = _clone(base)
+    return clones[(worker, f)]
+
+
+def _fit_points(obj, points, label, handle, F, k, rng, rank, world, timings, warm_cols=0, done=None):
+    """tune()'s one scheduler: fit ``points`` — (K, lambda, alpha) in the reference's order — once per fold (``F`` folds,
+    1 = the single hold-out), ``k`` fits in flight, and return the train and test RMSE tables (points x F) summed over the
+    ranks.
+
+    One producer thread walks all points: it draws every point's fresh inits from ``rng`` on every rank (the generator state
+    depends on neither ``world`` nor the mode), and for the points of this rank (g % world == rank) queues one task per fold,
+    at most 2 k F ahead of the fits: the arrays themselves when F == 1, F-ordered copies per fold otherwise (a fit updates its
+    arguments in place).  Worker w takes tasks until its sentinel arrives and fits them on ``handle(w, fold)``.  With k == 1
+    the one worker is the calling thread; with k > 1 every worker is a thread and the caller waits (two fits in flight are
+    slower when the caller's thread drives one of them: profiles/tune_scheduler/README.md).  Once any draw or fit has failed
+    the producer stops drawing and the workers discard what is queued, so nobody blocks on the queue; all threads are joined
+    and the first error is raised.
+
+    ``label(K, lambda, alpha)`` is printed when the first task of a point is taken.  ``warm_cols`` = n_lambda > 0 (k == 1 and
+    F == 1 only): point g starts from copies of the fitted factors of _nearest_finished() instead of from its draw.  ``done(g,
+    train, test)`` is called after the last fold of point g (k == 1 only: the points finish in order)."""
     import queue
     import threading
     import time as _time
-    prm = obj["params"]
-    seed = obj.get("seed", DEFAULT_SEED)
-    ds = _resident(obj, "tune")
-    handles = _fold_handles(obj, ds)
-    F = len(handles)
-    fold_id = np.asarray(obj["fold_id"])
-    n_f = np.array([(fold_id == f).sum() for f in range(1, F + 1)], dtype=np.float64)
-    k = max(1, int(concurrent))
+    prm, seed = obj["params"], obj.get("seed", DEFAULT_SEED)
+    train, test = np.zeros((len(points), F)), np.zeros((len(points), F))
+    tasks = queue.Queue(maxsize=2 * k * F)
+    lock = threading.Lock()
+    errors, labelled = [], set()
+    finished = {}           # warm start: point -> (row factors, column factor) of the points this rank has fitted
 
-    def _handle(worker, f):
-        """Worker 0 fits on the fold handles themselves, worker w > 0 on clones of them (made on first use, kept)."""
-        if worker == 0:
-            return handles[f]
-        clones = obj.setdefault("_fold_clones", {})
-        hd = clones.get((worker, f))
-        if hd is None or not getattr(hd, "_h", None):
-            hd = clones[(worker, f)] = handles[f].clone()
-        return hd
+    def _producer():
+        try:
+            for g, (K, _, _) in enumerate(points):
+                if errors:
+                    break
+                t_0 = _time.perf_counter()
+                cfd, col = _fresh_inits(obj, K, rng)            # ONE draw per point, whatever the number of folds
+                t_draw = _time.perf_counter() - t_0
+                if g % world != rank:
+                    continue
+                for f in range(F):
+                    tasks.put((g, f, cfd, col, t_draw) if F == 1 else
+                              (g, f, [a.copy(order="F") for a in cfd], col.copy(order="F"), t_draw))
+        except BaseException as e:      # a failed draw (MemoryError, ...) must not leave the workers waiting for ever
+            errors.append(e)
+        finally:
+            for _ in range(k):          # one sentinel per worker, whatever happened above
+                tasks.put(None)
 
-    def _run(points, label):
-        """points: (K, lambda, alpha) in the reference's order.  Returns the per-fold train and test RMSE (points x F)."""
-        tr = np.zeros((len(points), F))
-        te = np.zeros((len(points), F))
-        tasks = queue.Queue(maxsize=2 * k * F)
-        lock = threading.Lock()
-        errors = []
+    def _fit(w, t_wait, g, f, cfd, col, t_draw):
+        K, l, a = points[g]
+        t_1 = _time.perf_counter()
+        with lock:
+            if g not in labelled:
+                labelled.add(g)
+                print(label(K, l, a))
+        src = _nearest_finished(finished, g, warm_cols) if warm_cols else None
+        if src is not None:
+            cfd, col = [x.copy(order="F") for x in finished[src][0]], finished[src][1].copy(order="F")
+        hd = handle(w, f)
+        fitted = hd.optimize(cfd, col, K, l, l, a, 1, prm["global_tol"], prm["sub_tol"], prm["tuning_iter"], seed=seed,
+                             inc_continuous=obj["inc_continuous"], copy=False)
+        if warm_cols:
+            finished[g] = (list(fitted["row_matrices"].values()), fitted["column_factor"])
+            for old_g in [h for h in finished if h < g - warm_cols * world - world]:     # keep about one alpha row back
+                del finished[old_g]
+        with lock:
+            train[g, f], test[g, f] = fitted["train_rmse"], fitted["test_rmse"]
+            if timings is not None:
+                timings.append(dict(latent_rank=K, lambda_=l, alpha=a, init_s=t_draw, init_wait_s=t_wait if k == 1 else 0.0,
+                                    warm_from=src, optimize_s=_time.perf_counter() - t_1, library_ms=hd.profile()["wall_ms"]))
+                if F > 1:
+                    timings[-1]["fold"] = f + 1
+        if done is not None and f == F - 1:
+            done(g, train, test)
 
-        def _producer():
-            try:
-                for g, (K_, l_, a_) in enumerate(points):
-                    if errors:
-                        break
-                    t_0 = _time.perf_counter()
-                    cfd, col = _fresh_inits(obj, K_, rng)       # ONE draw per point, whatever the number of folds
-                    t_draw = _time.perf_counter() - t_0
-                    if g % world != rank:
-                        continue
-                    with lock:
-                        print(label(K_, l_, a_))
-                    for f in range(F):                          # every fold starts from copies of the point's inits
-                        tasks.put((g, f, [a.copy(order="F") for a in cfd], col.copy(order="F"), t_draw))
-            except BaseException as e:
-                errors.append(e)
-            finally:
-                for _ in range(k):
-                    tasks.put(None)
-
-        def _worker(w):
-            while True:
+    def _worker(w):
+        while True:
+            try:                        # BaseException: a lone worker is the caller's thread: a KeyboardInterrupt arrives here
+                t_w = _time.perf_counter()
                 item = tasks.get()
                 if item is None:
                     return
-                if errors:
-                    continue
-                g, f, cfd, col, t_draw = item
-                K_, l_, a_ = points[g]
-                t_1 = _time.perf_counter()
-                try:
-                    hd = _handle(w, f)
-                    fitted = hd.optimize(cfd, col, K_, l_, l_, a_, 1, prm["global_tol"], prm["sub_tol"], prm["tuning_iter"],
-                                         seed=seed, inc_continuous=obj["inc_continuous"], copy=False)
-                except Exception as e:
-                    errors.append(e)
-                    continue
-                with lock:
-                    tr[g, f], te[g, f] = fitted["train_rmse"], fitted["test_rmse"]
-                    if timings is not None:
-                        timings.append(dict(latent_rank=K_, lambda_=l_, alpha=a_, fold=f + 1, init_s=t_draw, init_wait_s=0.0,
-                                            warm_from=None, optimize_s=_time.perf_counter() - t_1,
-                                            library_ms=hd.profile()["wall_ms"]))
+                if not errors:
+                    _fit(w, _time.perf_counter() - t_w, *item)
+            except BaseException as e:
+                errors.append(e)
 
-        threads = [threading.Thread(target=_producer)] + [threading.Thread(target=_worker, args=(w,)) for w in range(k)]
-        for t in threads:
-            t.start()
-        for t in threads:
-            t.join()
-        if errors:
-            raise errors[0]
-        return _grid_sum(tr, world), _grid_sum(te, world)
-
-    def _save(name, table):
-        if out_dir is not None and rank == 0:
-            np.savetxt(os.path.join(out_dir, name), table, delimiter=",")
-
-    def _sd(te):
-        return te.std(axis=1, ddof=1) if F > 1 else np.zeros(len(te))
-
-    out = dict(rank_tuning=None, reg_tuning=None, rank_tuning_folds=None, reg_tuning_folds=None, rank_tuning_test_sd=None,
-               reg_tuning_test_sd=None, fold_counts=n_f)
-    if lat.size > 1:
-        l_, a_ = (float(lam[0]), float(alp[0])) if lam.size == 1 and alp.size == 1 else (0.1, 0.0)
-        tr, te = _run([(int(K_), l_, a_) for K_ in lat], lambda K_, l, a: f"Latent rank:  {K_} ---------------------------------")
-        out["rank_tuning"] = np.column_stack([lat.astype(np.float64), tr.mean(axis=1), pooled_rmse(te, n_f)])
-        out["rank_tuning_folds"], out["rank_tuning_test_sd"] = te, _sd(te)
-        _save("insider_rank_tuning_result.csv", out["rank_tuning"])
-        _save("insider_rank_tuning_result_folds.csv", np.column_stack([lat.astype(np.float64), te]))
-        latent_rank = int(lat[int(np.argmin(out["rank_tuning"][:, 2]))])
-    else:
-        latent_rank = int(lat[0])
-    out["latent_rank"] = latent_rank
-    if lam.size > 1 or alp.size > 1:
-        grid = [(round(float(l_), 2), round(float(a_), 2)) for a_ in alp for l_ in lam]   # expand.grid: lambda fastest
-        tr, te = _run([(latent_rank, l_, a_) for l_, a_ in grid],
-                      lambda K_, l, a: f"parameter grid: {l},{a} ---------------------------------")
-        g2 = np.array(grid, dtype=np.float64).reshape(-1, 2)
-        out["reg_tuning"] = np.column_stack([g2, tr.mean(axis=1), pooled_rmse(te, n_f)])
-        out["reg_tuning_folds"], out["reg_tuning_test_sd"] = te, _sd(te)
-        _save(f"insider_R{latent_rank}_reg_tuning_result.csv", out["reg_tuning"])
-        _save(f"insider_R{latent_rank}_reg_tuning_result_folds.csv", np.column_stack([g2, te]))
-    return out
+    threads = [threading.Thread(target=_producer)] + [threading.Thread(target=_worker, args=(w,)) for w in range(k) if k > 1]
+    for t in threads:
+        t.start()
+    if k == 1:
+        _worker(0)
+    for t in threads:
+        t.join()
+    if errors:
+        raise errors[0]
+    return _grid_sum(train, world), _grid_sum(test, world)
 
 
 def tune(obj, latent_dimension=None, lambda_=0.1, alpha=0.0, out_dir=None, rng=None, rank=0, world=1, timings=None,
@@ -1025,16 +1033,23 @@ def tune(obj, latent_dimension=None, lambda_=0.1, alpha=0.0, out_dir=None, rng=N
     ``rank`` / ``world``: grid-parallel tuning across the GPUs of a node: every rank keeps the
     whole data set resident, grid point g is fitted by rank g % world and the result tables are summed over
     torch.distributed.  The fresh inits of ALL grid points are drawn on every rank, in the reference's order, so
-    the tables do not depend on ``world``.  ``timings``: a list that receives one dict per fitted point
-    (init_s = drawing the fresh inits, optimize_s = the optimize() call, library_ms = time inside the library).
+    the tables do not depend on ``world``.  ``timings``: a list that receives one dict per fit, of the rank sweep and of the
+    grid, one per fold with ``folds`` (latent_rank, lambda_, alpha, with folds ``fold``; init_s = drawing the fresh inits,
+    init_wait_s = what the one worker waited for them, 0.0 with several; warm_from; optimize_s = the optimize() call,
+    library_ms = time inside the library).
 
-    ``concurrent`` = k > 1: k grid points of this rank are fitted AT THE SAME TIME on the one GPU, each on its own handle of
-    the shared resident data set (InsiderData.clone) from its own host thread.  The grid points are independent fits
-    (R/insider.R:145-164), and a data set of the size real INSIDER inputs have does not fill an MI355X with one fit: its
-    column step is bound by its longest gene's sequential sweep chain, which a second fit overlaps.  The inits are still
-    drawn by ONE generator in the reference's order, and every point's result is bit-identical to the serial grid's
-    (tests/test_gpu_parity.py::test_concurrent_tune_is_bit_identical).  Not combinable with ``warm_start`` (whose
-    starting points depend on the order in which fits finish).
+    Every mode runs on one scheduler (_fit_points), once for the rank sweep and once for the grid: a producer thread draws the
+    inits ahead of the fits (numpy's generator and the ctypes call both release the GIL), ``concurrent`` workers fit them,
+    a single one on the calling thread.  The CSVs are rewritten after every point when one worker fits a hold-out
+    sweep of a one-rank job, and written once at the end (by rank 0) otherwise.
+
+    ``concurrent`` = k > 1: k points of this rank are fitted AT THE SAME TIME on the one GPU, each on its own handle of
+    the shared resident data set (InsiderData.clone, kept on the object as ``_tune_clones``) from its own host thread.  The
+    points are independent fits (R/insider.R:145-164), and a data set of the size real INSIDER inputs have does not fill an
+    MI355X with one fit: its column step is bound by its longest gene's sequential sweep chain, which a second fit overlaps.
+    The inits are still drawn by ONE generator in the reference's order, and every point's result is bit-identical to the
+    serial sweep's (tests/test_gpu_sharded.py::test_concurrent_tune_is_bit_identical).  Not combinable with ``warm_start``
+    (whose starting points depend on the order in which fits finish).
 
     ``folds`` (default None: the single hold-out above, unchanged): with ``folds=True`` every point of the rank sweep and of
     the grid is fitted once per fold of ``obj["fold_id"]`` (insider(folds=k)), on the data sets ``ds.fold(1..F)`` derived
@@ -1045,6 +1060,7 @@ def tune(obj, latent_dimension=None, lambda_=0.1, alpha=0.0, out_dir=None, rng=N
     sqrt(sum_f n_f rmse_f^2 / sum_f n_f), n_f = held-out entries of fold f; ``rank_tuning_folds`` / ``reg_tuning_folds``
     hold the per-fold test RMSE (points x F), ``*_test_sd`` their sample standard deviation.  ``concurrent`` = k runs up
     to k (point, fold) fits at once on the fold handles and clones of them; results are bit-identical to the serial order.
+    Options set on the resident data set reach the fold handles and their clones at the next call.
     The CSVs keep their columns; a second file ``..._folds.csv`` holds the point's parameters and its per-fold test RMSE.
     Not combinable with ``warm_start`` (ValueError)."""
     if folds is not None and folds is not False:
@@ -1056,7 +1072,6 @@ def tune(obj, latent_dimension=None, lambda_=0.1, alpha=0.0, out_dir=None, rng=N
             raise ValueError("tune(folds=True): the object carries no fold ids: build it with insider(..., folds=k)")
     if concurrent > 1 and warm_start:
         raise ValueError("tune(): concurrent > 1 and warm_start exclude each other")
-    import time as _time
     lat = np.atleast_1d(latent_dimension) if latent_dimension is not None else np.array([])
     lam = np.atleast_1d(np.asarray(lambda_, dtype=float))
     alp = np.atleast_1d(np.asarray(alpha, dtype=float))
@@ -1066,137 +1081,64 @@ def tune(obj, latent_dimension=None, lambda_=0.1, alpha=0.0, out_dir=None, rng=N
     if lat.size <= 1 and lam.size <= 1 and alp.size <= 1:
         raise ValueError("TUNNING: The length of either latent_dimension or lambda and alpha should be greater "
                          "than 1.")                                                                      # :87-89
-    prm = obj["params"]
     rng = rng if rng is not None else np.random.default_rng(obj.get("seed", DEFAULT_SEED))
-    if folds:
-        return _tune_folds(obj, lat, lam, alp, out_dir, rng, rank, world, timings, concurrent)
     ds = _resident(obj, "tune")
-    rank_tuning, reg_tuning = None, None
+    k = max(1, int(concurrent))
+    if folds:
+        fold_handles = _fold_handles(obj, ds)
+        F = len(fold_handles)
+        n_f = np.array([(np.asarray(obj["fold_id"]) == f).sum() for f in range(1, F + 1)], dtype=np.float64)
+
+        def handle(w, f):       # worker 0 fits on the fold handles themselves, worker w > 0 on its clones of them
+            return fold_handles[f] if w == 0 else _fold_clone(obj, fold_handles[f], w, f)
+
+        out = dict(rank_tuning=None, reg_tuning=None, rank_tuning_folds=None, reg_tuning_folds=None, rank_tuning_test_sd=None,
+                   reg_tuning_test_sd=None, fold_counts=n_f)
+    else:
+        F = 1
+        handles = _tune_handles(obj, ds, k) if k > 1 else [ds]
+
+        def handle(w, f):
+            return handles[w]
+
+        out = dict(rank_tuning=None, latent_rank=None, reg_tuning=None)
+    stepwise = not folds and world == 1 and k == 1      # the table is rewritten after every point, as the reference does
+
+    def _table(head, train, test):
+        """The reference's columns: the point's parameters, train RMSE (mean over the folds), test RMSE (pooled over them)."""
+        return np.column_stack([head, train.mean(axis=1), pooled_rmse(test, n_f) if folds else test[:, 0]])
+
+    def _save(name, table):
+        if out_dir is not None and rank == 0:
+            np.savetxt(os.path.join(out_dir, name), table, delimiter=",")
+
+    def _sweep(which, csv, points, head, label, warm_cols=0):
+        """Fit `points`, fill out[which] (with folds: its per-fold table and spread too) and write the CSVs."""
+        head = np.array(head, dtype=np.float64).reshape(len(points), -1)
+        done = (lambda g, tr, te: _save(csv + ".csv", _table(head[: g + 1], tr[: g + 1], te[: g + 1]))) if stepwise else None
+        train, test = _fit_points(obj, points, label, handle, F, k, rng, rank, world, timings, warm_cols, done)
+        out[which] = _table(head, train, test)
+        if not stepwise:
+            _save(csv + ".csv", out[which])
+        if folds:
+            out[which + "_folds"] = test
+            out[which + "_test_sd"] = test.std(axis=1, ddof=1) if F > 1 else np.zeros(len(test))
+            _save(csv + "_folds.csv", np.column_stack([head, test]))
+
     if lat.size > 1:                                                                                     # :98-132
-        rows = np.zeros((lat.size, 3))
-        for g, latent_rank in enumerate(lat):
-            cfd, col = _fresh_inits(obj, int(latent_rank), rng)
-            if g % world != rank:
-                continue
-            print(f"Latent rank:  {int(latent_rank)} ---------------------------------")
-            if lam.size == 1 and alp.size == 1:
-                l_, a_ = float(lam[0]), float(alp[0])
-            else:
-                l_, a_ = 0.1, 0.0                                                                        # :120-121
-            fitted = ds.optimize(cfd, col, int(latent_rank), l_, l_, a_, 1, prm["global_tol"], prm["sub_tol"],
-                                 prm["tuning_iter"], seed=obj.get("seed", DEFAULT_SEED),
-                                 inc_continuous=obj["inc_continuous"])
-            rows[g] = (int(latent_rank), fitted["train_rmse"], fitted["test_rmse"])
-            if out_dir is not None and world == 1:
-                np.savetxt(os.path.join(out_dir, "insider_rank_tuning_result.csv"), rows[: g + 1], delimiter=",")
-        rank_tuning = _grid_sum(rows, world)
-        if out_dir is not None and world > 1 and rank == 0:
-            np.savetxt(os.path.join(out_dir, "insider_rank_tuning_result.csv"), rank_tuning, delimiter=",")
-        latent_rank = int(lat[int(np.argmin(rank_tuning[:, 2]))])                                        # :136
+        l_, a_ = (float(lam[0]), float(alp[0])) if lam.size == 1 and alp.size == 1 else (0.1, 0.0)      # :120-121
+        _sweep("rank_tuning", "insider_rank_tuning_result", [(int(K), l_, a_) for K in lat], [int(K) for K in lat],
+               lambda K, l, a: f"Latent rank:  {K} ---------------------------------")
+        latent_rank = int(lat[int(np.argmin(out["rank_tuning"][:, 2]))])                                 # :136
     else:
         latent_rank = int(lat[0])
+    out["latent_rank"] = latent_rank
     if lam.size > 1 or alp.size > 1:                                                                     # :142-174
         grid = [(round(float(l_), 2), round(float(a_), 2)) for a_ in alp for l_ in lam]   # expand.grid: lambda fastest
-        rows = np.zeros((len(grid), 4))
-        csv = os.path.join(out_dir, f"insider_R{latent_rank}_reg_tuning_result.csv") if out_dir is not None else None
-        # the fresh inits of grid point g + 1 are drawn (same generator, same order: R/insider.R:152-161) on a helper
-        # thread while the GPU fits point g: numpy's generator and the ctypes call both release the GIL
-        from concurrent.futures import ThreadPoolExecutor
-
-        def _draw():
-            t_0 = _time.perf_counter()
-            v = _fresh_inits(obj, latent_rank, rng)
-            return v, _time.perf_counter() - t_0
-
-        if concurrent > 1:
-            import queue
-            import threading
-            handles = _tune_handles(obj, ds, int(concurrent))
-            ready = queue.Queue(maxsize=2 * len(handles))      # inits drawn ahead of the fits, in the reference's order
-            lock = threading.Lock()
-            errors = []
-
-            def _producer():
-                try:
-                    for g in range(len(grid)):
-                        if errors:
-                            break
-                        v, t_draw = _draw()
-                        if g % world == rank:
-                            ready.put((g, v, t_draw))
-                except BaseException as e:      # a failed draw (MemoryError, ...) must not leave the workers waiting for ever
-                    errors.append(e)
-                finally:
-                    for _ in handles:           # one sentinel per worker, whatever happened above
-                        ready.put(None)
-
-            def _worker(hd):
-                while True:
-                    item = ready.get()
-                    if item is None or errors:
-                        if item is not None:
-                            continue        # drain after a failure elsewhere
-                        return
-                    g, (cfd, col), t_draw = item
-                    l_r, a_r = grid[g]
-                    t_1 = _time.perf_counter()
-                    try:
-                        fitted = hd.optimize(cfd, col, latent_rank, l_r, l_r, a_r, 1, prm["global_tol"], prm["sub_tol"],
-                                             prm["tuning_iter"], seed=obj.get("seed", DEFAULT_SEED),
-                                             inc_continuous=obj["inc_continuous"])
-                    except Exception as e:      # reported by the caller's thread
-                        errors.append(e)
-                        continue
-                    with lock:
-                        print(f"parameter grid: {l_r},{a_r} ---------------------------------")
-                        rows[g] = (l_r, a_r, fitted["train_rmse"], fitted["test_rmse"])
-                        if timings is not None:
-                            timings.append(dict(lambda_=l_r, alpha=a_r, init_s=t_draw, init_wait_s=0.0, warm_from=None,
-                                                optimize_s=_time.perf_counter() - t_1, library_ms=hd.profile()["wall_ms"]))
-
-            threads = [threading.Thread(target=_producer)] + [threading.Thread(target=_worker, args=(hd,)) for hd in handles]
-            for t in threads:
-                t.start()
-            for t in threads:
-                t.join()
-            if errors:
-                raise errors[0]
-            if csv and world == 1:
-                np.savetxt(csv, rows, delimiter=",")
-        finished = {}       # warm_start: grid index -> (row factors, column factor) of the points this rank has fitted
-        with ThreadPoolExecutor(max_workers=1) as pool:
-            nxt = pool.submit(_draw) if concurrent <= 1 else None
-            for g, (l_r, a_r) in enumerate(grid if concurrent <= 1 else []):                             # :147-150
-                t_w = _time.perf_counter()
-                (cfd, col), t_draw = nxt.result()
-                t_wait = _time.perf_counter() - t_w
-                if g + 1 < len(grid):
-                    nxt = pool.submit(_draw)
-                if g % world != rank:
-                    continue
-                t_1 = _time.perf_counter()
-                print(f"parameter grid: {l_r},{a_r} ---------------------------------")
-                src = _nearest_finished(finished, g, lam.size) if warm_start else None
-                if src is not None:
-                    cfd = [a.copy(order="F") for a in finished[src][0]]
-                    col = finished[src][1].copy(order="F")
-                fitted = ds.optimize(cfd, col, latent_rank, l_r, l_r, a_r, 1, prm["global_tol"], prm["sub_tol"],
-                                     prm["tuning_iter"], seed=obj.get("seed", DEFAULT_SEED),
-                                     inc_continuous=obj["inc_continuous"])
-                if warm_start:
-                    finished[g] = (list(fitted["row_matrices"].values()), fitted["column_factor"])
-                    for old_g in [h for h in finished if h < g - lam.size * world - world]:   # keep about one alpha row back
-                        del finished[old_g]
-                if timings is not None:
-                    timings.append(dict(lambda_=l_r, alpha=a_r, init_s=t_draw, init_wait_s=t_wait, warm_from=src,
-                                        optimize_s=_time.perf_counter() - t_1, library_ms=ds.profile()["wall_ms"]))
-                rows[g] = (l_r, a_r, fitted["train_rmse"], fitted["test_rmse"])
-                if csv and world == 1:
-                    np.savetxt(csv, rows[: g + 1], delimiter=",")
-        reg_tuning = _grid_sum(rows, world)
-        if csv and world > 1 and rank == 0:
-            np.savetxt(csv, reg_tuning, delimiter=",")
-    return dict(rank_tuning=rank_tuning, latent_rank=latent_rank, reg_tuning=reg_tuning)
+        _sweep("reg_tuning", f"insider_R{latent_rank}_reg_tuning_result", [(latent_rank, l_, a_) for l_, a_ in grid], grid,
+               lambda K, l, a: f"parameter grid: {l},{a} ---------------------------------",
+               warm_cols=lam.size if warm_start else 0)
+    return out
 
 
 def fit(obj, latent_dimension=None, lambda_=None, alpha=None, partition=0, rng=None):

@@ -128,7 +128,7 @@ def test_two_rank_row_update_and_loss_match_unsharded(oracle):
 class _FakeData:
     """Stands in for the HBM-resident data set: a deterministic function of the inits and hyper-parameters."""
 
-    def optimize(self, cfd, col, K, l1, l2, a, tuning, gtol, stol, iters, seed=0, inc_continuous=0):
+    def optimize(self, cfd, col, K, l1, l2, a, tuning, gtol, stol, iters, seed=0, inc_continuous=0, copy=True):
         s = float(sum(np.sum(m) for m in cfd) + np.sum(col))
         return dict(train_rmse=1e3 * s + l1, test_rmse=1e3 * s + 10 * a + K)
 
