@@ -170,7 +170,11 @@ int insider_hip_comm_init(insider_hip_handle *h, const void *unique_id, int rank
  * fit are read from global memory instead, with the same result; 0 = always that form; insider_hip_sample_decomposition()
  * stages its groups of genes' tables under the same budget), "sd_slabs" (gene slabs the streaming pass of
  * insider_hip_sample_decomposition() is cut into, summed in slab order; 0, default = from n, p and the device's compute units;
- * at most 256 and at most p; another count gives the same sums in another order). */
+ * at most 256 and at most p; another count gives the same sums in another order), "ls_slabs" / "ls_part_mb" (gene slabs the
+ * streaming pass of insider_hip_level_scores() is cut into, summed in slab order; 0, default = the rule of "sd_slabs" on that
+ * pass's sample tiles, lowered until the slabs' partial scores [slabs x n x the levels padded to 16, doubles] stay within
+ * ls_part_mb MB, default 256: a memory budget, not a tuned value; a count given explicitly is used as it is, at most 256 and at
+ * most p; another count gives the same sums in another order). */
 int insider_hip_set_option(insider_hip_handle *h, const char *name, double value);
 
 /*
@@ -380,6 +384,41 @@ int insider_hip_sample_decomposition(insider_hip_handle *h, double *const *A, co
                                      int entries, double *out);
 
 /*
+ * Every sample scored against every level of one categorical covariate, on the resident data set: how well is the row of
+ * sample i explained when its embedding for covariate cov is replaced by each candidate embedding in turn?  Blocks, u_b(i), x,
+ * entries (0 all / 1 train bit / 2 test bit) and S_i, the set of selected genes of sample i, are those of
+ * insider_hip_sample_decomposition().
+ *   cov    a CATEGORICAL block, 0 <= cov < c.
+ *   cand   the candidates e_1 .. e_L in R^K: NULL (with n_cand = 0) = the rows of A[cov], L = n_levels[cov]; else the rows of
+ *          cand (n_cand x K, column-major like a factor), L = n_cand >= 1: any embeddings in the model's latent space.
+ * With d_ij = x_ij - sum_{b != cov} u_b(i) . C[:, j] (the continuous block included when inc_continuous = 1):
+ *   sse[i][l] = sum_{j in S_i} (d_ij - e_l . C[:, j])^2      n x L, column-major (leading dimension n)
+ *   cnt[i]    = |S_i|                                        n doubles
+ * A sample with S_i empty gets a row of zeros and cnt = 0.  The device sums the expanded form (below), whose three terms
+ * cancel when a candidate fits a sample almost exactly: a sum that comes out negative is returned as 0, so sse >= 0 always, and
+ * a value that small carries the absolute error of the tolerance (about 1e-16 of sum (|x| + |fit| + |e_l . C|)^2), not its own
+ * digits.  The column of a sample's assigned level is the rss of
+ * insider_hip_sample_decomposition() (to rounding).  A sample's own level was fitted WITH that sample: on the entries the fit
+ * used the assigned level is favoured, most for levels with few samples (a level with one sample fits itself); on a tuning
+ * handle entries = 2 scores on entries no embedding has seen.  The call reports this nowhere and corrects nothing.
+ * Status codes: the checks of the post-hoc calls above (K 1..63: K > 63 returns INSIDER_ERR_UNSUPPORTED; the same
+ * inc_continuous rules; entries outside 0..2 returns INSIDER_ERR_ARG; a sharded handle returns INSIDER_ERR_UNSUPPORTED); cov
+ * outside 0..c-1 (the continuous block included), cand != NULL with n_cand < 1, cand == NULL with n_cand != 0 and a NULL sse or
+ * cnt return INSIDER_ERR_ARG.  Nothing is written to the caller's arrays unless the status is INSIDER_OK.  Works on clones and
+ * re-masked handles, on the handle's main stream, in the post-hoc workspace: an optimize() after it is bit-identical to one
+ * without.
+ * The device forms the candidate table Tc = cand C and, in one streaming pass over X and the mask codes per window of 128
+ * levels, sse = sum M d^2 - 2 (M .* d) Tc + M (Tc .* Tc) (M the 0/1 selection) as two masked products over the genes on the
+ * f64 matrix instruction, the fit of a tile from the same instruction, on a grid of sample tiles x gene slabs x windows; the
+ * slabs' partial scores are summed in slab order.  Every sum runs in a fixed order without atomics: repeated calls with the same
+ * options on the same device return identical bits, and cand equal to A[cov] returns the same bits as cand == NULL.
+ * insider_hip_get_info("ls_path") tells the form of the last call (1 = one level window, X read once; 2 = several, X read once
+ * per window of 128 levels) and "ls_slabs" its gene slabs (options "ls_slabs", "ls_part_mb").
+ */
+int insider_hip_level_scores(insider_hip_handle *h, double *const *A, const double *C, int inc_continuous, int K,
+                             int entries, int cov, const double *cand, int n_cand, double *sse, double *cnt);
+
+/*
  * Per-factor decomposition of a fitted model on the resident data set: the record of
  * insider_hip_variance_decomposition() split along the K latent factors.  Blocks b = 0..B-1 (B = c + inc_continuous) have the
  * per-sample embeddings u_b(i) in R^K (A_b[level_b(i)] for a categorical block, z_i B_c for the continuous one); one more
@@ -486,6 +525,8 @@ int insider_hip_get_profile(insider_hip_handle *h, double *out12);
  * global memory; 0 = none yet),
  * "sd_path" / "sd_slabs" (of the last insider_hip_sample_decomposition(): the form of k_sd_stats, 1 = level tables in LDS, 2 =
  * read from global memory, 0 = none yet; and the gene slabs its grid had),
+ * "ls_path" / "ls_slabs" (of the last insider_hip_level_scores(): 1 = one level window, X read once, 2 = several windows of 128
+ * levels, X read once per window, 0 = none yet; and the gene slabs its grid had),
  * "fd_path" (the form of the heavy pass of the last insider_hip_factor_decomposition(): 1 = one column window, X read once;
  * 2 = several windows of 128 columns of W, X read once per window; 0 = none yet),
  * "ol_path" (the form of k_ol_flag the last insider_hip_outliers() ran: 1 = level tables in LDS, 2 = read from global memory;

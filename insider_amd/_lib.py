@@ -29,7 +29,7 @@ SYMBOLS = (
     "insider_hip_optimize_continuous_v2", "insider_hip_residual", "insider_hip_interaction_glm",
     "insider_hip_variance_decomposition", "insider_hip_sample_decomposition", "insider_hip_col_stats", "insider_hip_last_cd_solver",
     "insider_hip_remask", "insider_hip_set_folds", "insider_hip_remask_fold", "insider_hip_factor_decomposition",
-    "insider_hip_outliers", "insider_hip_neighbors", "insider_hip_last_neighbors_ms",
+    "insider_hip_outliers", "insider_hip_neighbors", "insider_hip_last_neighbors_ms", "insider_hip_level_scores",
 )
 COMM_ID_BYTES = 128
 # insider_hip_outliers (insider_amd/csrc/insider_outliers.hpp): the samples a block of k_ol_flag covers per trip (OL_TRIP) and the
@@ -134,6 +134,8 @@ def load():
                                                 dp, dp]
     lib.insider_hip_variance_decomposition.argtypes = [C.c_void_p, C.POINTER(dp), dp, C.c_int, C.c_int, C.c_int, dp]
     lib.insider_hip_sample_decomposition.argtypes = [C.c_void_p, C.POINTER(dp), dp, C.c_int, C.c_int, C.c_int, dp]
+    lib.insider_hip_level_scores.argtypes = [C.c_void_p, C.POINTER(dp), dp, C.c_int, C.c_int, C.c_int, C.c_int, dp, C.c_int, dp,
+                                             dp]
     lib.insider_hip_factor_decomposition.argtypes = [C.c_void_p, C.POINTER(dp), dp, C.c_int, C.c_int, C.c_int, dp]
     lib.insider_hip_outliers.argtypes = [C.c_void_p, C.POINTER(dp), dp, C.c_int, C.c_int, C.c_int, dp, dp, C.c_double, C.c_int64,
                                          i32p, i32p, dp, C.POINTER(C.c_int64), i32p, i32p]

@@ -315,6 +315,42 @@ class InsiderData:
         return dict(n=out[:, 0].copy(), sum_x=out[:, 1].copy(), sum_xx=out[:, 2].copy(), rss=out[:, 3].copy(),
                     sum_g=blk[:, :, 0].T.copy(), sum_gg=blk[:, :, 1].T.copy(), sum_rg=blk[:, :, 2].T.copy())
 
+    def level_scores(self, cfd_factors, column_factor, cov, entries="train", candidates=None, inc_continuous=0):
+        """Every sample scored against every level of the categorical covariate ``cov`` (0-based; insider_hip_level_scores):
+        ``sse[i, l]`` is the residual sum of squares of sample i over its selected entries when its embedding for ``cov`` is
+        replaced by candidate l — the rows of ``cfd_factors[cov]`` (``candidates`` None, L = its levels) or of ``candidates``
+        (L x K: any embeddings in the latent space, e.g. for samples that carry a placeholder level).  A dict of ``sse``
+        (n x L) and ``n`` (length n, the selected entries of every sample; a sample without any has a row of zeros).
+        posthoc.ls_derived() turns them into best / second / margin / flagged / confusion.  The device sums the expanded
+        form sum d^2 - 2 sum d g + sum g^2: sse is never negative (a sum that cancels below 0 is returned as 0), but a value
+        far below its row's other entries holds the rounding of those three sums, not digits of its own.
+        A sample's own level was fitted WITH that sample: on ``entries="train"`` the assigned level is favoured, most for
+        levels with few samples (a level with one sample fits itself); on a tuning handle ``entries="test"`` scores on
+        entries no embedding has seen.  The call reports and corrects nothing."""
+        if entries not in self.VD_ENTRIES:
+            raise InsiderError(_lib.ERR_ARG, f"entries must be one of {sorted(self.VD_ENTRIES)}, got {entries!r}")
+        if inc_continuous not in (0, 1):
+            raise InsiderError(_lib.ERR_ARG, "The value of prarameter inc_continuous can only be 0 or 1.")
+        if not isinstance(cov, (int, np.integer)) or isinstance(cov, bool) or not 0 <= cov < self.c:
+            raise InsiderError(_lib.ERR_ARG, f"cov must be a categorical covariate in 0..{self.c - 1}, got {cov!r}")
+        K = int(np.asarray(column_factor).shape[0])
+        A, Cw, Aptrs = self._marshal(cfd_factors, column_factor, K, inc_continuous)
+        if candidates is None:
+            cand, L = None, int(self.n_levels[int(cov)])
+        else:
+            cand = np.asarray(candidates)
+            if cand.ndim != 2 or cand.shape[0] < 1 or cand.shape[1] != K:
+                raise InsiderError(_lib.ERR_ARG, f"candidates must be L x {K} with L >= 1")
+            cand = _lib.f64(cand)
+            L = cand.shape[0]
+        sse = np.empty((self.n, L), dtype=np.float64, order="F")
+        cnt = np.empty(self.n, dtype=np.float64)
+        _lib.check(_lib.load().insider_hip_level_scores(self._h, Aptrs, _lib.ptr(Cw), int(inc_continuous), K,
+                                                        self.VD_ENTRIES[entries], int(cov),
+                                                        None if cand is None else _lib.ptr(cand), 0 if cand is None else L,
+                                                        _lib.ptr(sse), _lib.ptr(cnt)))
+        return dict(sse=sse, n=cnt)
+
     def factor_decomposition(self, cfd_factors, column_factor, entries="train", inc_continuous=0):
         """Per-gene sums of the per-factor decomposition (insider_hip_factor_decomposition) over the entries ``entries`` of
         every gene: variance_decomposition() split along the K latent factors.  A dict of ``n``, ``sum_x``, ``sum_xx``,

@@ -9,6 +9,7 @@
 #include "insider_posthoc.hpp"
 #include "insider_vardecomp.hpp"
 #include "insider_sampdecomp.hpp"
+#include "insider_levelscores.hpp"
 #include "insider_factdecomp.hpp"
 #include "insider_outliers.hpp"
 #include "insider_neighbors.hpp"
@@ -387,6 +388,8 @@ struct Options {
     // "vd_stage_kb" bounds the LDS a block of k_vd_stats may stage its genes' level tables in (KiB)
     double vd_stage_kb = 48.0;
     int sd_slabs = 0;                 // "sd_slabs": gene slabs of k_sd_stats (0 = automatic; at most 256)
+    int ls_slabs = 0;                 // "ls_slabs": gene slabs of k_ls_prod (0 = automatic; at most 256)
+    double ls_part_mb = 256.0;        // "ls_part_mb": bound (MB) on the slabs' partial scores of the automatic slab count
 };
 
 // device workspace of the post-hoc calls (section "post-hoc interaction GLM"): grown on demand, freed with the handle
@@ -402,6 +405,9 @@ struct PostWs {
     DevBuf<double> vin, vtab, vrec;
     // sample decomposition: spart = the slabs' partial records (slabs x n x (4 + 3 BW)); srec = the n records
     DevBuf<double> spart, srec;
+    // level scores: lcand = the candidates (L x KPW); ltab = the candidate table Tc (p rows of ldt); lpart / lcnt = the slabs'
+    // partial scores (slabs x n x ldt) and counts (slabs x n); lout = sse (n x L column-major), then cnt (n)
+    DevBuf<double> lcand, ltab, lpart, lcnt, lout;
     // factor decomposition: fwall = [W | W .* W] (padded rows x 2 ldq); fprod = the p rows [P1 | P2 | P3]; fbase = the p base
     // slots; frec = the p records
     DevBuf<double> fwall, fprod, fbase, frec;
@@ -456,6 +462,8 @@ struct insider_hip_handle {
     int vd_path = 0;
     // the form the last sample decomposition ran (1 = tables in LDS, 2 = from global) and its gene slabs
     int sd_path = 0, sd_slabs = 0;
+    // the form the last level scores ran (1 = one level window, 2 = several) and its gene slabs
+    int ls_path = 0, ls_slabs = 0;
     int fd_path = 0;
     // the form the flag pass of the last outlier call ran (1 = tables in LDS, 2 = from global)
     int ol_path = 0;
@@ -2609,6 +2617,8 @@ int insider_hip_set_option(insider_hip_handle *h, const char *name, double value
     else if (s == "cd_pairs") h->opt.cd_pairs = (int)value;           // 1 (default) = sweeps routed through the blocks of two coordinate steps (K <= 30; same iterates), 0 = one step per block
     else if (s == "resid_stage_mb") h->opt.resid_stage_mb = value;   // device buffer insider_hip_residual() copies out through (MB; at least 16 genes of the window)
     else if (s == "vd_stage_kb") h->opt.vd_stage_kb = value;         // LDS budget (KiB, default 48, at most 60) of the staged level tables of k_vd_stats (0 = always the global form)
+    else if (s == "ls_slabs") h->opt.ls_slabs = value < 1 ? 0 : (int)std::min(value, 256.0);   // gene slabs of k_ls_prod (0 = from n, p, the compute units and "ls_part_mb"; at most 256)
+    else if (s == "ls_part_mb") h->opt.ls_part_mb = value;          // bound (MB, default 256) on the partial scores of the automatic slab count of k_ls_prod
     else if (s == "sd_slabs") h->opt.sd_slabs = value < 1 ? 0 : (int)std::min(value, 256.0);   // gene slabs of k_sd_stats (0 = from n, p and the compute units; at most 256)
     else if (s == "cd_variant") h->opt.cd_variant = (int)value;   // 0 = register-resident (4 genes per wave; K <= 32, and 32 < K <= 48 with the third slot's columns in LDS), 1 = group kernel, 2 = row16 (LDS, K <= 48)
     else return fail(INSIDER_ERR_ARG, "unknown option " + s);
@@ -3343,6 +3353,8 @@ int insider_hip_get_info(insider_hip_handle *h, const char *name, double *out)
     else if (s == "ol_path") *out = h->ol_path;                     // last outlier call: 1 = level tables in LDS, 2 = read from global
     else if (s == "vd_path") *out = h->vd_path;                     // last variance decomposition: 1 = level tables in LDS, 2 = read from global
     else if (s == "sd_path") *out = h->sd_path;                     // last sample decomposition: 1 = level tables in LDS, 2 = read from global
+    else if (s == "ls_path") *out = h->ls_path;                     // last level scores: 1 = one level window (X read once), 2 = several
+    else if (s == "ls_slabs") *out = h->ls_slabs;                   // ... and its gene slabs
     else if (s == "sd_slabs") *out = h->sd_slabs;                   // ... and its gene slabs
     else if (s == "fd_path") *out = h->fd_path;                     // last factor decomposition: 1 = one column window (X read once), 2 = several
     else if (s == "col_mfma_per_gene") {
@@ -3787,6 +3799,92 @@ int sample_decomposition_body(insider_hip_handle *h, double *const *A, const dou
     return INSIDER_OK;
 }
 
+// ---- level scores (kernels: insider_levelscores.hpp) -------------------------------------------------------------------
+// U_{-cov} and C in the kernels' layout (ph_prepare with every block but cov), the candidate table Tc = cand C (k_pack_A +
+// k_mm_rows, as vd_build_table builds T), then one streaming pass over X and the codes per window of LS_QT level tiles on a
+// grid of sample tiles x gene slabs x windows (k_ls_prod) and the sum of the slabs' partial scores in slab order
+// (k_ls_reduce).  cand == NULL scores the rows of A[cov] through the very same path: the same bits as passing them.
+int level_scores_body(insider_hip_handle *h, double *const *A, const double *C, int inc_continuous, int K, int entries,
+                      int cov, const double *cand, int n_cand, double *sse, double *cnt)
+{
+    int rc = vd_check(h, A, C, inc_continuous, K, entries, sse);
+    if (rc) return rc;
+    if (!cnt) return fail(INSIDER_ERR_ARG, "null output");
+    const DataSet &d = *h->ds;
+    if (cov < 0 || cov >= d.c) return fail(INSIDER_ERR_ARG, "cov must be a categorical covariate block in 0..c-1");
+    if (cand && n_cand < 1) return fail(INSIDER_ERR_ARG, "n_cand must be positive when candidates are given");
+    if (!cand && n_cand != 0) return fail(INSIDER_ERR_ARG, "n_cand must be 0 without candidates");
+    HIPCHECK(hipSetDevice(d.device));
+    PostWs &w = h->post;
+    hipStream_t st = h->st.stream;
+    const int KS = (K + 15) / 16, KPW = 16 * KS;
+    const int L = cand ? n_cand : d.block(cov).rows;
+    const double *E = cand ? cand : A[cov];
+    const int64_t n = d.n, p = d.p;
+    std::vector<int32_t> sub((size_t)d.c + 2, 1);   // every block but cov enters d
+    sub[cov] = 0;
+    if ((rc = ph_prepare(h, A, C, K, sub.data(), KPW))) return rc;
+    const int ldt = (int)round_up(L, 16), ltiles = ldt / 16, nwin = cdiv(ltiles, LS_QT);
+    // gene slabs: the rule of "sd_slabs" (eight blocks per compute unit, at most 256), and, when automatic, no more than keep
+    // the partial scores within "ls_part_mb"
+    const int tiles = cdiv(n, LS_TILE);
+    int want = h->opt.ls_slabs;
+    if (want <= 0) {
+        const double cap = std::max(h->opt.ls_part_mb, 0.0) * 1048576.0 / ((double)n * ldt * sizeof(double));
+        want = (int)std::min<double>(cdiv(2 * h->ds->n_simd, tiles), std::max(cap, 1.0));
+    }
+    const int64_t slab_len = cdiv(p, (int64_t)std::max(1, std::min(want, 256)));
+    const int slabs = (int)cdiv(p, slab_len);
+    if ((rc = w.stage.grow((size_t)L * K)) || (rc = w.lcand.grow((size_t)L * KPW)) || (rc = w.ltab.grow((size_t)p * ldt)) ||
+        (rc = w.lpart.grow((size_t)slabs * n * ldt)) || (rc = w.lcnt.grow((size_t)slabs * n)) ||
+        (rc = w.lout.grow((size_t)n * L + n)))
+        return rc;
+    double *tmp = w.stage, *Ec = w.lcand, *Tc = w.ltab, *part = w.lpart, *cpart = w.lcnt, *out = w.lout;
+    const double *U = w.U, *cp = w.cp;
+    HIPCHECK(hipMemcpyAsync(tmp, E, (size_t)L * K * sizeof(double), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_pack_A, dim3(cdiv((int64_t)L * KPW, 256)), dim3(256), 0, st, (const double *)tmp, L, K, KPW, Ec);
+    KCHECK();
+    // Tc[j][l] = sum_k C[k][j] cand[l][k]: gene-major, zero beyond L
+#define LT_LAUNCH(NT_)                                                                                                      \
+    hipLaunchKernelGGL((k_mm_rows<NT_, true>), dim3(cdiv(cdiv((int)p, 16), 4), cdiv(ldt, 16 * NT_)), dim3(256), 0, st, cp,    \
+                       (int64_t)KPW, (int)p, K, (const double *)Ec, KPW, L, Tc, (int64_t)ldt, ldt)
+    if (ltiles <= 1) LT_LAUNCH(1);
+    else if (ltiles <= 2) LT_LAUNCH(2);
+    else LT_LAUNCH(4);
+#undef LT_LAUNCH
+    KCHECK();
+    const int sel = entries == 0 ? 0 : entries == 1 ? CODE_TRAIN : CODE_TEST;
+    h->ls_path = nwin == 1 ? 1 : 2;
+    h->ls_slabs = slabs;
+#define LS_LAUNCH(QT_, KS_)                                                                                                 \
+    hipLaunchKernelGGL((k_ls_prod<QT_, KS_>), dim3(tiles, slabs, cdiv(ltiles, QT_)), dim3(64 * LS_WAVES),                    \
+                       ls_lds_bytes(QT_, KS_), st, (const double *)d.X, (const uint8_t *)d.codes, d.ldn, (int)n, p, U, cp, K, \
+                       (const double *)Tc, ldt, sel, slab_len, part, cpart)
+#define LS_LAUNCH_KS(QT_)                                                                                                   \
+    switch (KS) {                                                                                                            \
+        case 1: LS_LAUNCH(QT_, 1); break;                                                                                    \
+        case 2: LS_LAUNCH(QT_, 2); break;                                                                                    \
+        case 3: LS_LAUNCH(QT_, 3); break;                                                                                    \
+        default: LS_LAUNCH(QT_, 4); break;                                                                                   \
+    }
+    // one level tile: 84 - 102 registers; else the window form of LS_QT tiles: 196 - 215 (tools/kernel_regs.sh), no scratch, two
+    // waves per SIMD; tiles beyond the live ones of a window are skipped by a uniform branch.  (Forms of 2 and 4 tiles were
+    // dropped: the 4-tile one compiled to 446 - 468 registers, one wave per SIMD.)
+    if (ltiles <= 1) { LS_LAUNCH_KS(1) }
+    else { LS_LAUNCH_KS(LS_QT) }
+#undef LS_LAUNCH_KS
+#undef LS_LAUNCH
+    KCHECK();
+    hipLaunchKernelGGL(k_ls_reduce, dim3(cdiv(n * ldt, 256)), dim3(256), 0, st, (const double *)part, (const double *)cpart,
+                       slabs, n, ldt, L, out, out + (size_t)n * L);
+    KCHECK();
+    HIPCHECK(hipStreamSynchronize(st));   // the caller's arrays are written only after the kernels ran
+    HIPCHECK(hipMemcpyAsync(sse, out, (size_t)n * L * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipMemcpyAsync(cnt, out + (size_t)n * L, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipStreamSynchronize(st));
+    return INSIDER_OK;
+}
+
 // ---- factor decomposition (kernels: insider_factdecomp.hpp) ----------------------------------------------------------
 // Wall = [W | W .* W] from the packed row factors, then the heavy pass over X and the codes (P1 and the base slots, the
 // B K columns of the covariate blocks in windows of FD_QT tiles of 16), the light pass over the codes (P2, P3, every
@@ -3972,6 +4070,12 @@ int insider_hip_sample_decomposition(insider_hip_handle *h, double *const *A, co
                                      int entries, double *out)
 {
     return ph_finish(h, sample_decomposition_body(h, A, C, inc_continuous, K, entries, out));
+}
+
+int insider_hip_level_scores(insider_hip_handle *h, double *const *A, const double *C, int inc_continuous, int K,
+                             int entries, int cov, const double *cand, int n_cand, double *sse, double *cnt)
+{
+    return ph_finish(h, level_scores_body(h, A, C, inc_continuous, K, entries, cov, cand, n_cand, sse, cnt));
 }
 
 int insider_hip_factor_decomposition(insider_hip_handle *h, double *const *A, const double *C, int inc_continuous, int K,

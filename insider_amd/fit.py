@@ -11,6 +11,7 @@
     ... --factor-decomposition                  # then the per-factor decomposition (which factor, through which covariate)
     ... --outliers 3 [--outlier-entries train]  # then the entries whose standardised residual has |z| >= 3, on the device
     ... --gene-neighbors 10 --sample-neighbors 10 [--neighbor-metric cosine]   # then each gene's / sample's nearest in latent space
+    ... --level-scores 1 [--level-score-entries train]   # then every sample against every level of covariate column 1 (1-based)
 
 Semantics are those of insider_amd.api (the mirror of R/insider.R): with masks given, `--partition 1` fits on the
 train entries (optimize(tuning = 1)) and reports the test RMSE; without masks (or `--partition 0`) every non-NA entry is
@@ -28,7 +29,10 @@ ascending gene, then sample), ol_gene_counts (p x 2) and ol_sample_counts (n x 2
 --gene-neighbors N / --sample-neighbors N add each gene's N nearest genes by its column of C and each sample's N nearest
 samples by its row embedding (posthoc.gene_neighbors / sample_neighbors, --neighbor-metric cosine or dot): nn_gene_index /
 nn_gene_score (p x N) and nn_sample_index / nn_sample_score (n x N), 0-based, descending score, ties by ascending index, open
-slots -1 / NaN.  Output: A<i> (L_i x K), C (K x p) and result.json {train_rmse, test_rmse, loss,
+slots -1 / NaN; --level-scores COV adds, for covariate column COV (1-based), ls_sse (n x L: the residual sum of squares of every
+sample over the --level-score-entries with its embedding for COV replaced by each level's), ls_n, ls_best (1-based, 0 = no
+entry), ls_margin (n) and ls_confusion (L x L, assigned x best; posthoc.ls_derived) — a sample's own level was fitted with that
+sample, so on the entries the fit used the assigned level is favoured, most for levels with few samples.  Output: A<i> (L_i x K), C (K x p) and result.json {train_rmse, test_rmse, loss,
 iters, traj} in --out.  There is no CPU fallback: without a visible MI355X the command fails with the library's status.
 """
 import argparse
@@ -92,6 +96,13 @@ def parse(argv=None):
                          "columns low, high) next to the factors")
     ap.add_argument("--outlier-entries", choices=("all", "train", "test"), default="train",
                     help="--outliers: the entries that can be called (default: train, the entries the fit used)")
+    ap.add_argument("--level-scores", type=int, default=None, metavar="COV",
+                    help="after the fit, every sample scored against every level of covariate column COV (1-based like "
+                         "--interaction, counted after it), on the device; writes ls_sse (n x L), ls_n, ls_best, ls_margin (n) "
+                         "and ls_confusion (L x L, assigned x best) next to the factors.  A sample's own level was fitted with "
+                         "that sample: on the entries the fit used the assigned level is favoured")
+    ap.add_argument("--level-score-entries", choices=("all", "train", "test"), default="train",
+                    help="--level-scores: the entries that are scored (default: train, the entries the fit used)")
     ap.add_argument("--gene-neighbors", type=int, default=None, metavar="N",
                     help="after the fit, every gene's N nearest genes in the latent space (columns of C), on the device; "
                          "writes nn_gene_index, nn_gene_score (p x N; 0-based, open slots -1 / NaN) next to the factors")
@@ -105,10 +116,14 @@ def parse(argv=None):
         v = getattr(a, name)
         if v is not None and not 1 <= v <= 64:
             ap.error(f"--{name.replace('_', '-')} must be in 1..64")
+    if a.level_scores is not None and a.level_scores < 1:
+        ap.error("--level-scores: COV is 1-based")
     if not a.flat and not (a.x and a.levels):
         ap.error("give --flat DIR or --x and --levels")
     if not a.tune and (a.rank is None or a.lam is None or a.alpha is None):
         ap.error("a fit needs --rank, --lambda and --alpha (or use --tune)")
+    if a.tune and a.level_scores is not None:
+        ap.error("--level-scores scores a fit: it does not go with --tune")
     if a.folds is not None and not a.tune:
         ap.error("--folds goes with --tune")
     if a.folds is not None and a.warm_start:
@@ -141,6 +156,8 @@ def main(argv=None):
         from .workloads import interaction_indicator
         lev = interaction_indicator(np.asarray(lev, dtype=np.int32), tuple(a.interaction))
     n, p = X.shape
+    if a.level_scores is not None and not 1 <= a.level_scores <= np.asarray(lev).reshape(n, -1).shape[1]:
+        raise SystemExit(f"--level-scores: COV must be in 1..{np.asarray(lev).reshape(n, -1).shape[1]}")
     fmt = a.out_format or ("flat" if a.flat else "npy")
     if a.tune:
         # the caller-level path: insider() draws its own hold-out (R/utils.R:78-117) unless masks were given
@@ -234,6 +251,14 @@ def main(argv=None):
         vd = dict(vd or {}, ol_rows=ol["rows"], ol_cols=ol["cols"], ol_z=ol["z"],
                   ol_gene_counts=np.column_stack([ol["gene_low"], ol["gene_high"]]),
                   ol_sample_counts=np.column_stack([ol["sample_low"], ol["sample_high"]]))
+    if a.level_scores is not None:
+        from .posthoc import ls_derived
+        cov = a.level_scores - 1
+        ls = ls_derived(ds.level_scores(list(res["row_matrices"].values()), res["column_factor"], cov,
+                                        entries=a.level_score_entries, inc_continuous=1 if Z is not None else 0),
+                        ds_levels[:, cov])
+        vd = dict(vd or {}, ls_sse=ls["sse"], ls_n=ls["n"], ls_best=ls["best"].astype(np.float64), ls_margin=ls["margin"],
+                  ls_confusion=ls["confusion"].astype(np.float64))
     if a.gene_neighbors is not None:
         from .posthoc import gene_neighbors
         nn = gene_neighbors(res["column_factor"], k=a.gene_neighbors, metric=a.neighbor_metric, device=a.device)

@@ -27,6 +27,10 @@ outliers() lists the entries themselves: the (sample, gene) entries whose standa
 (InsiderData.outliers: a flag pass over X into a bitmap, a scan, a fill pass over the bitmap), with outliers_host() as its
 yardstick and residual_center_scale() for the per-gene center and scale from a variance-decomposition record.
 
+level_scores() asks whether each sample's label of a covariate is right: every sample scored against every level's embedding
+(InsiderData.level_scores: the candidate table cand C, then one streaming pass over X as two masked products over the genes),
+with level_scores_host() as its yardstick and ls_derived() for best / second / margin / flagged / confusion.
+
 gene_neighbors() / sample_neighbors() ask the latent representations themselves which genes lie next to a gene and which
 samples next to a sample (api.neighbors: a K-deep product on the device with the top-k selection fused behind it, the
 similarity matrix never exists), on column_factor and on sample_embeddings(); neighbors_host() is the yardstick.
@@ -272,6 +276,90 @@ def factor_decomposition(obj, which="fit", entries="train"):
     rec = ds.factor_decomposition(list(obj["cfd_matrices"].values()), obj["column_factor"], entries=entries,
                                   inc_continuous=int(obj["inc_continuous"]))
     return fd_derived(rec)
+
+
+def level_scores_host(X, levels, ctns, mask, A, C, cov, candidates=None):
+    """The level scores in plain numpy (the yardstick of InsiderData.level_scores); X, levels, ctns, mask, A, C as in
+    variance_decomposition_host(), ``cov`` the 0-based categorical covariate, ``candidates`` (L x K) or None = A[cov].  The
+    direct form: d = x - (every block but cov), sse[i, l] = sum over the entries of sample i that count of
+    (d - candidates[l] . C)^2.  -> dict(sse=(n, L), n=(n,))."""
+    X = np.asarray(X, dtype=np.float64)
+    n = X.shape[0]
+    Cm = np.asarray(C, dtype=np.float64)
+    lev = np.asarray(levels).reshape(n, -1)
+    c = lev.shape[1]
+    if not 0 <= cov < c:
+        raise ValueError(f"cov must be a categorical covariate in 0..{c - 1}")
+    d = X.copy()
+    for b in range(c):
+        if b != cov:
+            d = d - np.asarray(A[b], dtype=np.float64)[lev[:, b].astype(np.int64) - 1] @ Cm
+    if ctns is not None:
+        d = d - np.asarray(ctns, dtype=np.float64).reshape(n, -1) @ (np.asarray(A[c], dtype=np.float64) @ Cm)
+    E = np.asarray(A[cov] if candidates is None else candidates, dtype=np.float64).reshape(-1, Cm.shape[0])
+    w = np.ones(X.shape, dtype=bool) if mask is None else np.asarray(mask).astype(bool)
+    sse = np.empty((n, E.shape[0]))
+    for l in range(E.shape[0]):
+        r = np.where(w, d - E[l] @ Cm, 0.0)
+        sse[:, l] = (r * r).sum(axis=1)
+    return dict(sse=sse, n=w.sum(axis=1).astype(np.float64))
+
+
+def ls_derived(rec, assigned=None):
+    """The scores of level_scores() / InsiderData.level_scores() (``sse`` n x L, ``n``) plus, per sample,
+        mse = sse / n                                  (NaN where n = 0),
+        best, second                                   the 1-based levels of the smallest and second smallest sse, ties to
+                                                       the lowest id; 0 where n = 0 (second also 0 when L = 1),
+        margin = (sse[assigned] - sse[best]) / sse[assigned]   (0 when the assigned level is best or ties with the best —
+                                                       also when both are 0 — NaN where n = 0 or without ``assigned``),
+        flagged = best != assigned                     (False where n = 0 or without ``assigned``),
+        confusion                                      L x L counts, assigned x best, over the samples with n > 0 (None
+                                                       without ``assigned``).
+    ``assigned`` holds the 1-based ids of the scored covariate's column (length n), or None when the candidates are foreign
+    embeddings.  A sample's own level was fitted WITH that sample, so on the entries the fit used the assigned level is
+    favoured (a level with one sample fits itself); nothing here corrects for that."""
+    sse = np.asarray(rec["sse"], dtype=np.float64)
+    cnt = np.asarray(rec["n"], dtype=np.float64)
+    n, L = sse.shape
+    live = cnt > 0
+    with np.errstate(divide="ignore", invalid="ignore"):
+        mse = sse / np.where(live, cnt, np.nan)[:, None]
+    order = np.argsort(sse, axis=1, kind="stable")          # stable: ties to the lowest id
+    best = np.where(live, order[:, 0] + 1, 0).astype(np.int64)
+    second = np.where(live, order[:, 1] + 1, 0).astype(np.int64) if L > 1 else np.zeros(n, dtype=np.int64)
+    out = dict(sse=sse, n=cnt, mse=mse, best=best, second=second)
+    if assigned is None:
+        out.update(margin=np.full(n, np.nan), flagged=np.zeros(n, dtype=bool), confusion=None)
+        return out
+    ids = np.asarray(assigned).ravel().astype(np.int64)
+    if ids.shape != (n,) or (n and (ids.min() < 1 or ids.max() > L)):
+        raise ValueError(f"assigned must hold n = {n} level ids within 1..{L}")
+    rows = np.arange(n)
+    own, low = sse[rows, ids - 1], sse[rows, np.maximum(best, 1) - 1]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        margin = np.where((best == ids) | (own <= low), 0.0, (own - low) / np.where(own > low, own, 1.0))
+    out["margin"] = np.where(live, margin, np.nan)
+    out["flagged"] = live & (best != ids)
+    conf = np.zeros((L, L), dtype=np.int64)
+    np.add.at(conf, (ids[live] - 1, best[live] - 1), 1)
+    out["confusion"] = conf
+    return out
+
+
+def level_scores(obj, cov, which="fit", entries="train", candidates=None):
+    """Every sample of a fitted ``Insider`` object scored against every level of covariate column ``cov`` (0-based column of
+    obj["confounder"]) on the device, with the ``which`` / ``entries`` of variance_decomposition(): is each sample's label
+    right, and what should a sample with a placeholder label be called?  ``candidates`` (L x K): score against those
+    embeddings instead of the covariate's own.  -> ls_derived() of the scores against the column's ids (against None with
+    ``candidates``): sse, mse (n x L), n, best, second, margin, flagged (n), confusion (L x L).
+    A sample's own level was fitted WITH that sample: on which="fit" / entries="train" the assigned level is favoured, most
+    for levels with few samples (a level with one sample fits itself); which="tune", entries="test" scores on held-out
+    entries no embedding has seen.  Nothing is reported or corrected for it."""
+    from . import api
+    ds = api._resident(obj, which)
+    rec = ds.level_scores(list(obj["cfd_matrices"].values()), obj["column_factor"], int(cov), entries=entries,
+                          candidates=candidates, inc_continuous=int(obj["inc_continuous"]))
+    return ls_derived(rec, None if candidates is not None else np.asarray(obj["confounder"])[:, int(cov)])
 
 
 def residual_center_scale(rec):
