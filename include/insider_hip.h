@@ -494,6 +494,45 @@ int insider_hip_neighbors(const double *Q, int64_t nq, const double *B, int64_t 
                           int64_t self_offset, int device, int32_t *idx_out, double *score_out);
 double insider_hip_last_neighbors_ms(void);
 
+/* Preranked gene-set enrichment with a permutation null (insider_amd/csrc/insider_enrich.hpp).  Handle-free, one device.
+ *   Inputs.  scores is R x p, row-major: profile r is p contiguous doubles.  set_ptr (int64, S + 1) and set_genes (int32) hold S
+ *   sets in CSR form: set s is set_genes[set_ptr[s] .. set_ptr[s + 1]), 0-based gene indices, distinct within a set.
+ *   Ranking.  Within a profile the genes are ordered by descending score, equal scores (-0.0 == 0.0) by ascending gene index;
+ *   position 0 is the top.  The ranking runs on the host inside the library (a stable sort); everything behind it on the device.
+ *   Weights.  weight = 0: w(t) = 1; weight = 1: w(t) = |score of the gene at position t|.
+ *   Enrichment score of a position set T = {t_1 < ... < t_m}, 1 <= m < p:  P_i = w(t_1) + ... + w(t_i), N = P_m (N == 0: w = 1
+ *   for this set, the classic statistic, so nothing divides by zero), miss_i = t_i - (i - 1),
+ *       hi = max_i (P_i / N - miss_i / (p - m)),    lo = min_i (P_{i-1} / N - miss_i / (p - m)),    P_0 = 0,
+ *   ES = hi if hi >= -lo, else lo; peak = the smallest t_i at which the chosen extreme is attained.  Each deviation is evaluated
+ *   exactly as written (an fp64 division, another, one subtraction; no reciprocals): with integer-valued weights the result is
+ *   a pure function of integers, identical on host and device.  This equals the running sum over all p positions.
+ *   Observed score of (profile, set): T = the rank positions of the set's genes.
+ *   Null draw b (0 <= b < nperm) of size m: T = { phi(j) : j = 0 .. m - 1 }, phi the keyed bijection of [0, p) of
+ *   include/insider_sample.h: bits = the smallest even number >= 2 with 2^bits >= p, half = bits / 2, mask = 2^half - 1,
+ *   key = h32(h32(lo32(seed) ^ 0x9E3779B9) ^ hi32(seed) ^ 0x85EBCA6B * b); x = j, then until x < p (cycle walking):
+ *   L = x >> half, Rr = x & mask; for i = 1..8: t = L ^ (h32(Rr ^ key ^ 0xC2B2AE35 * i) & mask), L = Rr, Rr = t;
+ *   x = L << half | Rr.  h32 = insider_h32 (include/insider_perm.h), uint32 arithmetic that wraps.  A draw depends on
+ *   (seed, b, p, m) only, not on the profile or the set, and the sizes are nested.
+ *   Counts per (profile, set), over the nperm draws of the set's size scored on the profile: the side of a score is positive
+ *   when ES >= 0; n_same = the draws on the observed side, n_ge = those of them with |ES_b| >= |ES|, sum_same = the sum of
+ *   their ES_b (added in draw order), hits_nonzero = the set's genes whose score is not 0.  The caller derives
+ *   p = (n_ge + 1) / (n_same + 1) and NES = ES / (sum_same / n_same).
+ *   Outputs are R x S, profile-major.  No atomics: repeated calls return identical bits, a call on some of the profiles returns
+ *   exactly those rows and a call on some of the sets exactly those columns.  Device memory is O(R p + nnz + R S).
+ *   INSIDER_ERR_ARG, nothing written: a NULL pointer, R < 0, S < 0, p < 2 or p > INT32_MAX, weight outside {0, 1}, nperm outside
+ *   1..65536, a set with m < 1, m >= p or m > 4096, a gene index out of range or repeated within a set, a set_ptr that
+ *   decreases or starts below 0, a non-finite score (all checked on the host, before a device is opened).  R == 0 or S == 0
+ *   returns INSIDER_OK and writes nothing.
+ *   insider_hip_last_enrichment_ms: of the calling THREAD's last call, the HIP-event time in ms of its kernels (ranking and
+ *   transfers excluded).
+ *   insider_hip_enrichment_sample: host only, opens no device: out[j] = phi(j), j < m, of draw `perm` under `seed` on [0, p)
+ *   (0 <= m <= p, p as above; otherwise INSIDER_ERR_ARG). */
+int insider_hip_enrichment(const double *scores, int64_t R, int64_t p, const int64_t *set_ptr, const int32_t *set_genes,
+                           int64_t S, int weight, int nperm, uint64_t seed, int device, double *es, int32_t *peak,
+                           int32_t *n_ge, int32_t *n_same, double *sum_same, int32_t *hits_nonzero);
+double insider_hip_last_enrichment_ms(void);
+int insider_hip_enrichment_sample(uint64_t seed, uint32_t perm, int64_t m, int64_t p, int32_t *out);
+
 /* Profile of the last insider_hip_optimize() call (option "profile" = 1), HIP-event timed on the library's stream.
  * out[0..11]: {column-side masked-Gram launches, total ms, row-side masked-Gram launches, total ms,
  *  column-solve (CD / ridge) launches, total ms, test-residual launches, total ms,

@@ -718,6 +718,53 @@ def neighbors(query, base=None, k=10, metric="cosine", exclude_self=None, device
     return dict(index=index, score=score)
 
 
+ENRICH_MAX_SET = 4096
+ENRICH_MAX_PERMS = 65536
+
+
+def enrichment_args(scores, set_ptr, set_genes, nperm, weight, seed):
+    """The arguments of enrichment() / posthoc.enrichment_host() in the library's types: (scores R x p row-major float64 (a
+    vector is one profile), set_ptr int64 (S + 1), set_genes int32, nperm, weight, seed).  Shape errors raise
+    InsiderError(ERR_ARG); the values are the library's to check."""
+    sc = np.ascontiguousarray(np.atleast_2d(np.asarray(scores, dtype=np.float64)))
+    ptr = np.ascontiguousarray(set_ptr, dtype=np.int64)
+    genes = np.ascontiguousarray(set_genes, dtype=np.int32)
+    if sc.ndim != 2 or ptr.ndim != 1 or genes.ndim != 1 or ptr.size < 1:
+        raise InsiderError(_lib.ERR_ARG, "scores must be R x p, set_ptr (S + 1) and set_genes vectors")
+    if ptr[-1] > genes.size:
+        raise InsiderError(_lib.ERR_ARG, "set_ptr ends beyond set_genes")
+    for name, v in (("nperm", nperm), ("weight", weight), ("seed", seed)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise InsiderError(_lib.ERR_ARG, f"{name} must be an integer")
+    if not 0 <= seed < 2 ** 64:
+        raise InsiderError(_lib.ERR_ARG, "seed must fit 64 bits")
+    return sc, ptr, genes, int(nperm), int(weight), int(seed)
+
+
+def enrichment(scores, set_ptr, set_genes, nperm=1000, weight=1, seed=DEFAULT_SEED, device=0):
+    """Preranked gene-set enrichment of every profile (row of ``scores``, R x p) against every set (CSR: set_ptr, set_genes,
+    0-based genes) with a permutation null of ``nperm`` random gene sets of equal size (insider_hip_enrichment; the
+    definitions are in include/insider_hip.h).  weight 1 weights a gene by |score|, 0 is the classic statistic.  -> the raw
+    record: es, sum_same (R x S float64), peak, n_ge, n_same, hits_nonzero (R x S int32), size (S), nonzero (R: the
+    profile's non-zero scores), nperm, weight, seed and the inputs (scores, set_ptr, set_genes); posthoc.gs_derived() turns it
+    into p, NES, FDR and the hypergeometric p, posthoc.leading_edge() lists a set's leading genes."""
+    sc, ptr, genes, nperm, weight, seed = enrichment_args(scores, set_ptr, set_genes, nperm, weight, seed)
+    R, p = sc.shape
+    S = ptr.size - 1
+    rec = dict(es=np.full((R, S), np.nan), sum_same=np.full((R, S), np.nan))
+    for name in ("peak", "n_ge", "n_same", "hits_nonzero"):
+        rec[name] = np.full((R, S), -1, dtype=np.int32)
+    gp = genes if genes.size else np.zeros(1, dtype=np.int32)
+    i32 = C.c_int32
+    _lib.check(_lib.load().insider_hip_enrichment(_lib.ptr(sc), R, p, _lib.ptr(ptr, C.c_int64), _lib.ptr(gp, i32), S, weight,
+                                                  nperm, seed, int(device), _lib.ptr(rec["es"]), _lib.ptr(rec["peak"], i32),
+                                                  _lib.ptr(rec["n_ge"], i32), _lib.ptr(rec["n_same"], i32),
+                                                  _lib.ptr(rec["sum_same"]), _lib.ptr(rec["hits_nonzero"], i32)))
+    rec.update(size=np.diff(ptr).astype(np.int32), nonzero=np.count_nonzero(sc, axis=1).astype(np.int64), nperm=nperm,
+               weight=weight, seed=seed, scores=sc, set_ptr=ptr, set_genes=genes)
+    return rec
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # caller level — R/insider.R, R/utils.R
 # ---------------------------------------------------------------------------------------------------------------

@@ -13,6 +13,7 @@
 #include "insider_factdecomp.hpp"
 #include "insider_outliers.hpp"
 #include "insider_neighbors.hpp"
+#include "insider_enrich.hpp"
 
 #include <rccl/rccl.h>
 
@@ -40,6 +41,7 @@ thread_local std::string g_err;
 thread_local double g_last_cd_ms = 0.0;   // per calling thread: the ABI is re-entrant per handle / per thread
 thread_local int g_last_cd_solver = 0;     // (ColSolver)
 thread_local double g_last_neighbors_ms = 0.0;
+thread_local double g_last_enrichment_ms = 0.0;
 
 int fail(int code, const std::string &msg)
 {
@@ -3153,6 +3155,128 @@ int insider_hip_neighbors(const double *Q, int64_t nq, const double *B, int64_t 
 }
 
 double insider_hip_last_neighbors_ms(void) { return g_last_neighbors_ms; }
+
+// ---- enrichment (insider_enrich.hpp) -----------------------------------------------------------------------------------------
+int insider_hip_enrichment_sample(uint64_t seed, uint32_t perm, int64_t m, int64_t p, int32_t *out)
+{
+    if (!out) return fail(INSIDER_ERR_ARG, "null argument");
+    if (p < 2 || p > (int64_t)std::numeric_limits<int32_t>::max()) return fail(INSIDER_ERR_ARG, "p must be in 2..2^31-1");
+    if (m < 0 || m > p) return fail(INSIDER_ERR_ARG, "m must be in 0..p");
+    const uint32_t key = insider_sample_key(seed, perm), half = insider_sample_half((uint32_t)p);
+    for (int64_t j = 0; j < m; ++j) out[j] = (int32_t)insider_sample_phi(key, half, (uint32_t)p, (uint32_t)j);
+    return INSIDER_OK;
+}
+
+int insider_hip_enrichment(const double *scores, int64_t R, int64_t p, const int64_t *set_ptr, const int32_t *set_genes,
+                           int64_t S, int weight, int nperm, uint64_t seed, int device, double *es, int32_t *peak,
+                           int32_t *n_ge, int32_t *n_same, double *sum_same, int32_t *hits_nonzero)
+{
+    if (!scores || !set_ptr || !set_genes || !es || !peak || !n_ge || !n_same || !sum_same || !hits_nonzero)
+        return fail(INSIDER_ERR_ARG, "null argument");
+    if (R < 0 || S < 0) return fail(INSIDER_ERR_ARG, "R and S must be >= 0");
+    if (p < 2 || p > (int64_t)std::numeric_limits<int32_t>::max()) return fail(INSIDER_ERR_ARG, "p must be in 2..2^31-1");
+    if (weight != 0 && weight != 1) return fail(INSIDER_ERR_ARG, "weight must be 0 or 1");
+    if (nperm < 1 || nperm > 65536) return fail(INSIDER_ERR_ARG, "nperm must be in 1..65536");
+    if (S > (int64_t)std::numeric_limits<int32_t>::max()) return fail(INSIDER_ERR_UNSUPPORTED, "S must be < 2^31");
+    if (set_ptr[0] < 0) return fail(INSIDER_ERR_ARG, "set_ptr must not be negative");
+    if (S > 0) {
+        std::vector<int32_t> seen((size_t)p, -1);   // the last set each gene was met in
+        for (int64_t s = 0; s < S; ++s) {
+            const int64_t m = set_ptr[s + 1] - set_ptr[s];
+            if (m < 0) return fail(INSIDER_ERR_ARG, "set_ptr must not decrease");
+            if (m < 1 || m >= p || m > GS_MAX_SET) return fail(INSIDER_ERR_ARG, "a set must hold 1..min(p - 1, 4096) genes");
+            for (int64_t e = set_ptr[s]; e < set_ptr[s + 1]; ++e) {
+                const int32_t g = set_genes[e];
+                if (g < 0 || g >= p) return fail(INSIDER_ERR_ARG, "gene index out of range");
+                if (seen[g] == (int32_t)s) return fail(INSIDER_ERR_ARG, "a gene is repeated within a set");
+                seen[g] = (int32_t)s;
+            }
+        }
+    }
+    if (!all_finite(scores, (size_t)R * p)) return fail(INSIDER_ERR_ARG, "scores must be finite");
+    if (R == 0 || S == 0) return INSIDER_OK;
+    int rc = cd_common_checks(1, R, device);
+    if (rc) return rc;
+    HIPCHECK(hipSetDevice(device));
+    // the ranking: descending score, ties by ascending gene (a stable sort of 0..p-1)
+    std::vector<int32_t> rank((size_t)R * p), order((size_t)p);
+    std::vector<double> aw((size_t)R * p);
+    for (int64_t r = 0; r < R; ++r) {
+        const double *sc = scores + (size_t)r * p;
+        for (int64_t g = 0; g < p; ++g) order[g] = (int32_t)g;
+        std::stable_sort(order.begin(), order.end(), [sc](int32_t a, int32_t b) { return sc[a] > sc[b]; });
+        for (int64_t t = 0; t < p; ++t) {
+            rank[(size_t)r * p + order[t]] = (int32_t)t;
+            aw[(size_t)r * p + t] = std::fabs(sc[order[t]]);
+        }
+    }
+    // the sets by size: size_sets lists the set ids in ascending (size, id), sizes / size_ptr its runs of one size
+    std::vector<int32_t> size_sets((size_t)S), sizes, size_ptr;
+    for (int64_t s = 0; s < S; ++s) size_sets[s] = (int32_t)s;
+    auto msize = [set_ptr](int32_t s) { return (int32_t)(set_ptr[s + 1] - set_ptr[s]); };
+    std::stable_sort(size_sets.begin(), size_sets.end(), [&](int32_t a, int32_t b) { return msize(a) < msize(b); });
+    for (int64_t q = 0; q < S; ++q)
+        if (q == 0 || msize(size_sets[q]) != sizes.back()) {
+            sizes.push_back(msize(size_sets[q]));
+            size_ptr.push_back((int32_t)q);
+        }
+    size_ptr.push_back((int32_t)S);
+    const int64_t nnz = set_ptr[S];
+    DevBuf<int32_t> drank, dgenes, dsets, dsizes, dszptr, dpeak, dnge, dnsame, dhits;
+    DevBuf<double> daw, des, dsum;
+    DevBuf<int64_t> dptr;
+    if ((rc = drank.upload(rank)) || (rc = daw.upload(aw)) || (rc = dsets.upload(size_sets)) || (rc = dsizes.upload(sizes)) ||
+        (rc = dszptr.upload(size_ptr)) || (rc = dgenes.alloc((size_t)nnz)) || (rc = dptr.alloc((size_t)S + 1)) ||
+        (rc = des.alloc((size_t)R * S)) || (rc = dsum.alloc((size_t)R * S)) || (rc = dpeak.alloc((size_t)R * S)) ||
+        (rc = dnge.alloc((size_t)R * S)) || (rc = dnsame.alloc((size_t)R * S)) || (rc = dhits.alloc((size_t)R * S)))
+        return rc;
+    HIPCHECK(hipMemcpy(dgenes, set_genes, (size_t)nnz * sizeof(int32_t), hipMemcpyHostToDevice));
+    HIPCHECK(hipMemcpy(dptr, set_ptr, ((size_t)S + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
+    const uint32_t half = insider_sample_half((uint32_t)p);
+    Event e0, e1;
+    HIPCHECK(hipEventCreate(e0.out()));
+    HIPCHECK(hipEventCreate(e1.out()));
+    HIPCHECK(hipEventRecord(e0, 0));
+    // one pair of launches per class of sizes that sort at the same padded length M2
+    const int nsz_all = (int)sizes.size();
+    for (int z0 = 0; z0 < nsz_all;) {
+        int M2 = 64;
+        while (M2 < sizes[z0]) M2 <<= 1;
+        int z1 = z0;
+        while (z1 < nsz_all && sizes[z1] <= M2) ++z1;
+        const int q0 = size_ptr[z0], nsets = size_ptr[z1] - q0, nsz = z1 - z0;
+        const int64_t ntask_o = R * nsets, ntask_n = R * nsz;
+        const int64_t cap = (int64_t)1 << 20;
+        hipLaunchKernelGGL(k_gs_observed, dim3((unsigned)std::min(ntask_o, cap)), dim3(64), (size_t)M2 * sizeof(int), 0,
+                           (const int32_t *)drank, (const double *)daw, p, (const int64_t *)dptr, (const int32_t *)dgenes,
+                           (const int32_t *)dsets.get() + q0, nsets, ntask_o, M2, weight, S, des.get(), dpeak.get(), dhits.get());
+        KCHECK();
+#define GS_NULL(NW_)                                                                                                         \
+    hipLaunchKernelGGL((k_gs_null<NW_>), dim3((unsigned)std::min(ntask_n, cap)), dim3(64 * NW_),                             \
+                       (size_t)NW_ * M2 * sizeof(int) + GS_CHUNK * sizeof(double), 0, (const double *)daw, p, half, seed,    \
+                       nperm, (const int32_t *)dsizes.get() + z0, (const int32_t *)dszptr.get() + z0, (const int32_t *)dsets, \
+                       nsz, ntask_n, M2, weight, S, (const double *)des, dnge.get(), dnsame.get(), dsum.get())
+        if (M2 <= 2048) GS_NULL(4);
+        else GS_NULL(2);
+#undef GS_NULL
+        KCHECK();
+        z0 = z1;
+    }
+    HIPCHECK(hipEventRecord(e1, 0));
+    HIPCHECK(hipEventSynchronize(e1));
+    float ms = 0.0f;
+    (void)hipEventElapsedTime(&ms, e0, e1);
+    g_last_enrichment_ms = ms;
+    HIPCHECK(hipMemcpy(es, des, (size_t)R * S * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHECK(hipMemcpy(sum_same, dsum, (size_t)R * S * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHECK(hipMemcpy(peak, dpeak, (size_t)R * S * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIPCHECK(hipMemcpy(n_ge, dnge, (size_t)R * S * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIPCHECK(hipMemcpy(n_same, dnsame, (size_t)R * S * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIPCHECK(hipMemcpy(hits_nonzero, dhits, (size_t)R * S * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return INSIDER_OK;
+}
+
+double insider_hip_last_enrichment_ms(void) { return g_last_enrichment_ms; }
 
 // optimize_continuous_v2 (src/optimize.cpp:76-137) with the reference's eight arguments, on an arbitrary `data` matrix
 // (insider_cont_v2.hpp): one streaming pass over (data, indicator) for the per-gene sums, the K x K weighted Gram, then the

@@ -12,6 +12,7 @@
     ... --outliers 3 [--outlier-entries train]  # then the entries whose standardised residual has |z| >= 3, on the device
     ... --gene-neighbors 10 --sample-neighbors 10 [--neighbor-metric cosine]   # then each gene's / sample's nearest in latent space
     ... --level-scores 1 [--level-score-entries train]   # then every sample against every level of covariate column 1 (1-based)
+    ... --gene-sets SETS.gmt [--gene-names NAMES.txt] [--enrich-perms 1000] [--enrich-levels 1]   # then what each factor means
 
 Semantics are those of insider_amd.api (the mirror of R/insider.R): with masks given, `--partition 1` fits on the
 train entries (optimize(tuning = 1)) and reports the test RMSE; without masks (or `--partition 0`) every non-NA entry is
@@ -32,7 +33,12 @@ nn_gene_score (p x N) and nn_sample_index / nn_sample_score (n x N), 0-based, de
 slots -1 / NaN; --level-scores COV adds, for covariate column COV (1-based), ls_sse (n x L: the residual sum of squares of every
 sample over the --level-score-entries with its embedding for COV replaced by each level's), ls_n, ls_best (1-based, 0 = no
 entry), ls_margin (n) and ls_confusion (L x L, assigned x best; posthoc.ls_derived) — a sample's own level was fitted with that
-sample, so on the entries the fit used the assigned level is favoured, most for levels with few samples.  Output: A<i> (L_i x K), C (K x p) and result.json {train_rmse, test_rmse, loss,
+sample, so on the entries the fit used the assigned level is favoured, most for levels with few samples; --gene-sets FILE (GMT;
+tokens are the lines of --gene-names, else 0-based gene columns; sets outside --enrich-min-size..--enrich-max-size are dropped)
+adds the preranked gene-set enrichment of every factor's |loadings| against every set with --enrich-perms random sets of equal
+size as the null (posthoc.factor_enrichment): gs_factor_es / gs_factor_nes / gs_factor_pval / gs_factor_fdr / gs_factor_peak
+(K x S), gs_size (S) and gs_set_names.txt, and with --enrich-levels B the same for the signed per-gene effect of every level of
+covariate column B (1-based), gs_level<B>_es / _nes / _pval / _fdr / _peak (L_B x S; posthoc.level_enrichment).  Output: A<i> (L_i x K), C (K x p) and result.json {train_rmse, test_rmse, loss,
 iters, traj} in --out.  There is no CPU fallback: without a visible MI355X the command fails with the library's status.
 """
 import argparse
@@ -111,7 +117,33 @@ def parse(argv=None):
                          "on the device; writes nn_sample_index, nn_sample_score (n x N) next to the factors")
     ap.add_argument("--neighbor-metric", choices=("cosine", "dot"), default="cosine",
                     help="--gene-neighbors / --sample-neighbors: the score (default: cosine)")
+    ap.add_argument("--gene-sets", default=None, metavar="FILE",
+                    help="after the fit, the gene-set enrichment of every factor's |loadings| on the device against the sets of "
+                         "this GMT file (name, description, genes; tab-separated); writes gs_factor_es, gs_factor_nes, "
+                         "gs_factor_pval, gs_factor_fdr, gs_factor_peak (K x S), gs_size (S) and gs_set_names.txt next to the "
+                         "factors")
+    ap.add_argument("--gene-names", default=None, metavar="FILE",
+                    help="--gene-sets: one gene name per line, in the order of the columns of X (default: the GMT tokens are "
+                         "0-based column indices)")
+    ap.add_argument("--enrich-perms", type=int, default=1000, metavar="N",
+                    help="--gene-sets: random gene sets of equal size per (factor, set size) (default 1000, at most 65536)")
+    ap.add_argument("--enrich-min-size", type=int, default=15, help="--gene-sets: smallest set kept (default 15)")
+    ap.add_argument("--enrich-max-size", type=int, default=500, help="--gene-sets: largest set kept (default 500, at most 4096)")
+    ap.add_argument("--enrich-levels", type=int, default=None, metavar="B",
+                    help="--gene-sets: also the enrichment of every level's signed per-gene effect of covariate column B "
+                         "(1-based like --level-scores); writes gs_level<B>_es / _nes / _pval / _fdr / _peak (L x S)")
     a = ap.parse_args(argv)
+    if a.gene_sets is None and (a.gene_names is not None or a.enrich_levels is not None):
+        ap.error("--gene-names and --enrich-levels go with --gene-sets")
+    if a.gene_sets is not None:
+        if a.tune:
+            ap.error("--gene-sets interprets a fit: it does not go with --tune")
+        if not 1 <= a.enrich_perms <= 65536:
+            ap.error("--enrich-perms must be in 1..65536")
+        if not 1 <= a.enrich_min_size <= a.enrich_max_size <= 4096:
+            ap.error("--enrich-min-size / --enrich-max-size must satisfy 1 <= min <= max <= 4096")
+        if a.enrich_levels is not None and a.enrich_levels < 1:
+            ap.error("--enrich-levels: B is 1-based")
     for name in ("gene_neighbors", "sample_neighbors"):
         v = getattr(a, name)
         if v is not None and not 1 <= v <= 64:
@@ -158,6 +190,8 @@ def main(argv=None):
     n, p = X.shape
     if a.level_scores is not None and not 1 <= a.level_scores <= np.asarray(lev).reshape(n, -1).shape[1]:
         raise SystemExit(f"--level-scores: COV must be in 1..{np.asarray(lev).reshape(n, -1).shape[1]}")
+    if a.enrich_levels is not None and not 1 <= a.enrich_levels <= np.asarray(lev).reshape(n, -1).shape[1]:
+        raise SystemExit(f"--enrich-levels: B must be in 1..{np.asarray(lev).reshape(n, -1).shape[1]}")
     fmt = a.out_format or ("flat" if a.flat else "npy")
     if a.tune:
         # the caller-level path: insider() draws its own hold-out (R/utils.R:78-117) unless masks were given
@@ -268,6 +302,26 @@ def main(argv=None):
         nn = sample_neighbors(list(res["row_matrices"].values()), ds_levels, Z, k=a.sample_neighbors, metric=a.neighbor_metric,
                               device=a.device)
         vd = dict(vd or {}, nn_sample_index=nn["index"], nn_sample_score=nn["score"])
+    gs_names = None
+    if a.gene_sets is not None:
+        from .posthoc import factor_enrichment, level_enrichment
+        gene_names = None
+        if a.gene_names is not None:
+            with open(a.gene_names) as f:
+                gene_names = [ln.strip() for ln in f if ln.strip()]
+            if len(gene_names) != p:
+                raise SystemExit(f"--gene-names: {len(gene_names)} names for {p} genes")
+        sets = flatio.read_gmt(a.gene_sets, gene_names, min_size=a.enrich_min_size, max_size=min(a.enrich_max_size, p - 1))
+        if not sets[0]:
+            raise SystemExit("--gene-sets: no set is left within the size window")
+        gs_names = sets[0]
+        keys = ("es", "nes", "pval", "fdr", "peak")
+        gs = factor_enrichment(res["column_factor"], sets, nperm=a.enrich_perms, seed=a.seed, device=a.device)
+        vd = dict(vd or {}, gs_size=gs["size"], **{f"gs_factor_{k}": gs[k] for k in keys})
+        if a.enrich_levels is not None:
+            gs = level_enrichment(list(res["row_matrices"].values())[a.enrich_levels - 1], res["column_factor"], sets,
+                                  nperm=a.enrich_perms, seed=a.seed, device=a.device)
+            vd.update({f"gs_level{a.enrich_levels}_{k}": gs[k] for k in keys})
     ds.close()
     summary = dict(train_rmse=res["train_rmse"], test_rmse=None if np.isnan(res["test_rmse"]) else res["test_rmse"],
                    loss=res["loss"], iters=res["iters"], rank=K, **{"lambda": a.lam}, alpha=a.alpha, partition=partition,
@@ -280,6 +334,9 @@ def main(argv=None):
             else:
                 flatio.write_raw(os.path.join(a.out, name + ".f64"), v)
     flatio.write_records(a.out, fmt, vd or {})
+    if gs_names is not None:
+        with open(os.path.join(a.out, "gs_set_names.txt"), "w") as f:
+            f.write("".join(name + "\n" for name in gs_names))
     print(json.dumps({k: summary[k] for k in ("train_rmse", "test_rmse", "loss", "iters")} | {"out": a.out}))
     return 0
 

@@ -99,3 +99,32 @@ def write_records(outdir, fmt, records):
             np.save(os.path.join(outdir, name + ".npy"), np.asfortranarray(v))
         else:
             write_raw(os.path.join(outdir, name + ".f64"), v)
+
+
+def read_gmt(path, gene_names=None, min_size=15, max_size=500):
+    """Gene sets from a GMT file (one set per line: name<TAB>description<TAB>gene...).  Tokens are looked up in
+    ``gene_names`` (the name of every column of X, in order); without it they are 0-based column indices.  Unknown tokens are
+    dropped, duplicates removed (the first occurrence stays), and a set whose remaining size is outside
+    min_size..max_size is dropped.  -> (names, set_ptr int64 (S + 1), set_genes int32): the CSR form of api.enrichment()."""
+    index = None if gene_names is None else {str(g): i for i, g in reversed(list(enumerate(gene_names)))}
+    names, ptr, genes = [], [0], []
+    with open(path) as f:
+        for line in f:
+            tok = line.rstrip("\r\n").split("\t")
+            if len(tok) < 2 or not tok[0]:
+                continue
+            ids = []
+            for t in tok[2:]:
+                t = t.strip()
+                if index is not None:
+                    g = index.get(t)
+                else:
+                    g = int(t) if t.isdigit() else None
+                if g is not None:
+                    ids.append(g)
+            ids = list(dict.fromkeys(ids))
+            if min_size <= len(ids) <= max_size:
+                names.append(tok[0])
+                genes.extend(ids)
+                ptr.append(len(genes))
+    return names, np.asarray(ptr, dtype=np.int64), np.asarray(genes, dtype=np.int32)

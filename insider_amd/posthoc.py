@@ -34,6 +34,11 @@ with level_scores_host() as its yardstick and ls_derived() for best / second / m
 gene_neighbors() / sample_neighbors() ask the latent representations themselves which genes lie next to a gene and which
 samples next to a sample (api.neighbors: a K-deep product on the device with the top-k selection fused behind it, the
 similarity matrix never exists), on column_factor and on sample_embeddings(); neighbors_host() is the yardstick.
+
+factor_enrichment() / level_enrichment() ask what a factor or a level effect means: a preranked gene-set enrichment of the
+rows of column_factor, or of A_b @ column_factor, with a permutation null of random gene sets of equal size
+(api.enrichment: per (profile, set) a sort and a scan on the device, the null table never exists); enrichment_host() is the
+yardstick, gs_derived() gives p, NES, FDR and the hypergeometric p, leading_edge() a set's leading genes.
 """
 import numpy as np
 
@@ -496,3 +501,186 @@ def sample_neighbors(cfd_factors, levels, ctns_confounder=None, k=10, metric="co
     samples, score=(n, k)); open slots -1 / NaN."""
     from . import api
     return api.neighbors(sample_embeddings(cfd_factors, levels, ctns_confounder), None, k=k, metric=metric, device=device)
+
+
+# ---- gene-set enrichment (include/insider_hip.h states the definitions) ----------------------------------------------------
+def _h32(x):
+    """insider_h32 (include/insider_perm.h) on a uint32 array."""
+    x = x ^ (x >> np.uint32(16))
+    x = x * np.uint32(0x7FEB352D)
+    x = x ^ (x >> np.uint32(15))
+    x = x * np.uint32(0x846CA68B)
+    return x ^ (x >> np.uint32(16))
+
+
+def gs_sample_host(seed, perm, m, p):
+    """Null draw ``perm`` under ``seed``: phi(0 .. m - 1) on [0, p), the numpy mirror of include/insider_sample.h (uint32
+    arithmetic that wraps; the Feistel network is walked until every value is below p).  -> int64 (m)."""
+    half = 1
+    while half < 16 and (1 << (2 * half)) < p:
+        half += 1
+    h, mask = np.uint32(half), np.uint32((1 << half) - 1)
+    with np.errstate(over="ignore"):
+        key = _h32(np.array([(seed & 0xFFFFFFFF) ^ 0x9E3779B9], dtype=np.uint32))
+        key = _h32(key ^ np.uint32((seed >> 32) & 0xFFFFFFFF) ^ np.uint32((0x85EBCA6B * perm) & 0xFFFFFFFF))
+        x = np.arange(m, dtype=np.uint32)
+        todo = np.ones(m, dtype=bool)
+        while todo.any():
+            L, Rr = x[todo] >> h, x[todo] & mask
+            for i in range(1, 9):
+                t = L ^ (_h32(Rr ^ key ^ np.uint32((0xC2B2AE35 * i) & 0xFFFFFFFF)) & mask)
+                L, Rr = Rr, t
+            x[todo] = (L << h) | Rr
+            todo = x >= p
+    return x.astype(np.int64)
+
+
+def gs_deviations(aw, T, weight):
+    """The deviations of the position sets T (ascending; (m) for all profiles or (R, m) per profile) on the profiles whose
+    |score| by rank position is aw (R x p): (P_i / N - miss_i / (p - m), P_{i-1} / N - miss_i / (p - m)), each R x m, every
+    term in exactly that form; rows with N == 0 use w = 1."""
+    R, p = aw.shape
+    T = np.broadcast_to(T, (R, np.shape(T)[-1]))
+    m = T.shape[1]
+    i = np.arange(m)
+    miss = (T - i).astype(np.float64) / float(p - m)
+    if weight:
+        P = np.cumsum(np.take_along_axis(aw, T, axis=1), axis=1)
+        N = P[:, -1:].copy()
+        zero = N[:, 0] == 0.0
+        P[zero] = i + 1.0
+        N[zero] = float(m)
+    else:
+        P = np.broadcast_to(i + 1.0, (R, m))
+        N = float(m)
+    Pprev = np.concatenate([np.zeros((R, 1)), P[:, :-1]], axis=1)
+    return P / N - miss, Pprev / N - miss
+
+
+def gs_pick(dh, dl, T):
+    """(ES, peak) per row from the deviations: ES = hi if hi >= -lo else lo, peak the smallest position at the extreme."""
+    T = np.broadcast_to(T, dh.shape)
+    ihi, ilo = dh.argmax(axis=1), dl.argmin(axis=1)
+    rows = np.arange(dh.shape[0])
+    hi, lo = dh[rows, ihi], dl[rows, ilo]
+    up = hi >= -lo
+    return np.where(up, hi, lo), T[rows, np.where(up, ihi, ilo)].astype(np.int32)
+
+
+def enrichment_host(scores, set_ptr, set_genes, nperm=1000, weight=1, seed=0x1D5EED, device=0, return_null=False):
+    """api.enrichment() in plain numpy (the yardstick of the device path): the same arguments and record, vectorised over
+    the profiles.  return_null: the record also holds ``null`` (R x distinct sizes x nperm, the score of every draw) and
+    ``null_sizes`` (``device`` is accepted for the common signature and not used; the arguments are assumed valid)."""
+    from . import api
+    sc, ptr, genes, nperm, weight, seed = api.enrichment_args(scores, set_ptr, set_genes, nperm, weight, seed)
+    R, p = sc.shape
+    S = ptr.size - 1
+    order = np.argsort(-sc, axis=1, kind="stable")                 # descending score, ties by ascending gene
+    rank = np.empty_like(order)
+    np.put_along_axis(rank, order, np.broadcast_to(np.arange(p), (R, p)), axis=1)
+    aw = np.abs(np.take_along_axis(sc, order, axis=1))
+    size = np.diff(ptr).astype(np.int32)
+    rec = dict(es=np.zeros((R, S)), sum_same=np.zeros((R, S)))
+    for name in ("peak", "n_ge", "n_same", "hits_nonzero"):
+        rec[name] = np.zeros((R, S), dtype=np.int32)
+    for s in range(S):
+        g = genes[ptr[s]:ptr[s + 1]]
+        T = np.sort(rank[:, g], axis=1)
+        rec["es"][:, s], rec["peak"][:, s] = gs_pick(*gs_deviations(aw, T, weight), T)
+        rec["hits_nonzero"][:, s] = np.count_nonzero(sc[:, g], axis=1)
+    usizes = np.unique(size)
+    null = np.zeros((R, usizes.size, nperm))
+    for b in range(nperm if S and R else 0):
+        pos = gs_sample_host(seed, b, int(usizes[-1]), p)
+        for z, m in enumerate(usizes):
+            T = np.sort(pos[:m])
+            null[:, z, b] = gs_pick(*gs_deviations(aw, T, weight), T)[0]
+    for s in range(S):
+        nb = null[:, np.searchsorted(usizes, size[s]), :]
+        obs = rec["es"][:, s:s + 1]
+        same = (nb >= 0.0) == (obs >= 0.0)
+        rec["n_same"][:, s] = same.sum(axis=1)
+        rec["n_ge"][:, s] = (same & (np.abs(nb) >= np.abs(obs))).sum(axis=1)
+        total, comp = np.zeros(R), np.zeros(R)                     # a compensated (Neumaier) sum in draw order
+        for b in range(nperm):
+            e = np.where(same[:, b], nb[:, b], 0.0)
+            t = total + e
+            comp += np.where(np.abs(total) >= np.abs(e), (total - t) + e, (e - t) + total)
+            total = t
+        rec["sum_same"][:, s] = total + comp
+    rec.update(size=size, nonzero=np.count_nonzero(sc, axis=1).astype(np.int64), nperm=nperm, weight=weight, seed=seed,
+               scores=sc, set_ptr=ptr, set_genes=genes)
+    if return_null:
+        rec.update(null=null, null_sizes=usizes)
+    return rec
+
+
+def _hyper_tail(k, M, n, N):
+    """P(X >= k), X hypergeometric: N draws without replacement from M genes of which n are marked (math.lgamma)."""
+    import math
+    lo, hi = max(k, 0, N - (M - n)), min(n, N)
+    if lo > hi:
+        return 0.0
+    lc = lambda a, b: math.lgamma(a + 1) - math.lgamma(b + 1) - math.lgamma(a - b + 1)
+    den = lc(M, N)
+    return min(1.0, math.fsum(math.exp(lc(n, x) + lc(M - n, N - x) - den) for x in range(lo, hi + 1)))
+
+
+def gs_derived(rec):
+    """From an enrichment record: pval = (n_ge + 1) / (n_same + 1); nes = ES / (sum_same / n_same), NaN where no draw fell
+    on the observed side; fdr = Benjamini-Hochberg over the sets of each profile; hyper_p = the hypergeometric upper tail of
+    hits_nonzero among the set's genes against the profile's non-zero count (the over-representation test of a sparse
+    factor's support).  All R x S."""
+    es, n_same = rec["es"], rec["n_same"].astype(np.float64)
+    R, S = es.shape
+    pval = (rec["n_ge"] + 1.0) / (n_same + 1.0)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        nes = np.where(n_same > 0, es / (rec["sum_same"] / n_same), np.nan)
+    fdr = np.ones((R, S))
+    if S:
+        o = np.argsort(pval, axis=1, kind="stable")
+        q = np.take_along_axis(pval, o, axis=1) * S / np.arange(1, S + 1)
+        q = np.minimum(np.minimum.accumulate(q[:, ::-1], axis=1)[:, ::-1], 1.0)
+        np.put_along_axis(fdr, o, q, axis=1)
+    p = rec["scores"].shape[1]
+    hyper = np.array([[_hyper_tail(int(rec["hits_nonzero"][r, s]), p, int(rec["nonzero"][r]), int(rec["size"][s]))
+                       for s in range(S)] for r in range(R)], dtype=np.float64).reshape(R, S)
+    return dict(pval=pval, nes=nes, fdr=fdr, hyper_p=hyper)
+
+
+def leading_edge(rec, r, s):
+    """The genes of set s that make the score of profile r: those ranked at or before the peak when ES >= 0, at or after it
+    otherwise, in rank order (int64 gene indices, 0-based)."""
+    sc = rec["scores"][r]
+    g = rec["set_genes"][rec["set_ptr"][s]:rec["set_ptr"][s + 1]].astype(np.int64)
+    rank = np.empty(sc.size, dtype=np.int64)
+    rank[np.argsort(-sc, kind="stable")] = np.arange(sc.size)
+    t = rank[g]
+    keep = t <= rec["peak"][r, s] if rec["es"][r, s] >= 0.0 else t >= rec["peak"][r, s]
+    return g[keep][np.argsort(t[keep])]
+
+
+def _enrich(profiles, sets, nperm, weight, seed, device):
+    from . import api
+    ptr, genes = sets[-2], sets[-1]                               # (set_ptr, set_genes) or flatio.read_gmt()'s triple
+    rec = api.enrichment(profiles, ptr, genes, nperm=nperm, weight=weight, seed=seed, device=device)
+    rec.update(gs_derived(rec))
+    if len(sets) == 3:
+        rec["names"] = list(sets[0])
+    return rec
+
+
+def factor_enrichment(column_factor, sets, abs=True, nperm=1000, weight=1, seed=0x1D5EED, device=0):
+    """Gene-set enrichment of every factor's loadings: the profiles are the rows of column_factor (K x p).  abs=True ranks by
+    |loading|: a factor's sign is arbitrary and, after the elastic net, most loadings are 0.  ``sets`` is
+    (set_ptr, set_genes) or what flatio.read_gmt() returns.  -> the api.enrichment() record with gs_derived() merged in
+    (K x S)."""
+    Cm = np.asarray(column_factor, dtype=np.float64)
+    return _enrich(np.abs(Cm) if abs else Cm, sets, nperm, weight, seed, device)
+
+
+def level_enrichment(cfd_factor, column_factor, sets, nperm=1000, weight=1, seed=0x1D5EED, device=0):
+    """Gene-set enrichment of every level's per-gene effect A_b[l] . C of one covariate: the profiles are the rows of
+    cfd_factor (L x K) @ column_factor (K x p), signed.  -> as factor_enrichment(), L x S."""
+    return _enrich(np.asarray(cfd_factor, dtype=np.float64) @ np.asarray(column_factor, dtype=np.float64), sets, nperm,
+                   weight, seed, device)
