@@ -174,7 +174,10 @@ int insider_hip_comm_init(insider_hip_handle *h, const void *unique_id, int rank
  * streaming pass of insider_hip_level_scores() is cut into, summed in slab order; 0, default = the rule of "sd_slabs" on that
  * pass's sample tiles, lowered until the slabs' partial scores [slabs x n x the levels padded to 16, doubles] stay within
  * ls_part_mb MB, default 256: a memory budget, not a tuned value; a count given explicitly is used as it is, at most 256 and at
- * most p; another count gives the same sums in another order). */
+ * most p; another count gives the same sums in another order), "glm_slabs" (gene slabs the streaming pass of
+ * insider_hip_interaction_glm() is cut into, summed in slab order; 0, default = from n and the device's compute units, at most
+ * 64; s >= 1 [at most 64] = slabs of cdiv(p, s) genes rounded up to whole staging rounds of k_resid_stats; another count gives
+ * the same sums in another order). */
 int insider_hip_set_option(insider_hip_handle *h, const char *name, double value);
 
 /*
@@ -328,11 +331,14 @@ int insider_hip_col_stats(insider_hip_handle *h, double *const *A, int inc_conti
  * insider_hip_interaction_glm — group is an int32 vector of n ids in 0..G (0 = the sample is in no group; anything else:
  *   INSIDER_ERR_ARG).  For every group g with m_g samples: G = C C', beta_g = G^-1 C mean_{i in g}(r_i),
  *   RSS_g = sum_{i in g} ||r_i - C' beta_g||^2, dof_g = m_g p - rank, se_g = sqrt(RSS_g / dof_g diag(G^-1) / m_g).
+ *   RSS_g is formed as sum ||r_i||^2 - m_g beta_g' C mean(r_i); where the group's residual rows lie in the row space of C
+ *   that difference cancels to rounding noise of either sign, and a negative one is returned as 0 (se = 0, never NaN).
  *   coeff and se are G x K column-major (row g-1 for id g, like the factors), dof has G entries.  A group without samples
  *   gives zero rows and dof 0.  A latent dimension whose row of C is exactly zero is dropped from G (rank counts the
  *   others) and its coefficient and standard error are NaN (R's glm reports NA); any other pivot of the Cholesky
  *   factorisation of the reduced G that is not larger than rank x machine epsilon times its diagonal entry returns
- *   INSIDER_ERR_SOLVE.  p-values are left to the caller: 2 P(T_dof > |coeff / se|).
+ *   INSIDER_ERR_SOLVE, and so does a C with more non-zero rows than genes (the reduced G is then rank-deficient whatever
+ *   rounding leaves in its last pivots).  p-values are left to the caller: 2 P(T_dof > |coeff / se|).
  * Both work on any handle (clones included), on the handle's main stream, with a workspace of their own (allocated on first
  * use, freed by insider_hip_destroy): nothing insider_hip_optimize() reads is touched, and an optimize() after them is
  * bit-identical to one without.  K is bounded as in insider_hip_optimize() (1..63).  A sharded handle (world > 1) returns
@@ -566,6 +572,9 @@ int insider_hip_get_profile(insider_hip_handle *h, double *out12);
  * read from global memory, 0 = none yet; and the gene slabs its grid had),
  * "ls_path" / "ls_slabs" (of the last insider_hip_level_scores(): 1 = one level window, X read once, 2 = several windows of 128
  * levels, X read once per window, 0 = none yet; and the gene slabs its grid had),
+ * "glm_slabs" / "glm_form" (of the last insider_hip_interaction_glm(): the gene slabs the grid of k_resid_stats had, and its
+ * form 10 NB + GT, NB = ceil(K / 16) blocks of 16 latent dimensions and GT gene tiles per staging round: 18, 24, 32, 42; 0 =
+ * none yet),
  * "fd_path" (the form of the heavy pass of the last insider_hip_factor_decomposition(): 1 = one column window, X read once;
  * 2 = several windows of 128 columns of W, X read once per window; 0 = none yet),
  * "ol_path" (the form of k_ol_flag the last insider_hip_outliers() ran: 1 = level tables in LDS, 2 = read from global memory;

@@ -392,6 +392,7 @@ struct Options {
     int sd_slabs = 0;                 // "sd_slabs": gene slabs of k_sd_stats (0 = automatic; at most 256)
     int ls_slabs = 0;                 // "ls_slabs": gene slabs of k_ls_prod (0 = automatic; at most 256)
     double ls_part_mb = 256.0;        // "ls_part_mb": bound (MB) on the slabs' partial scores of the automatic slab count
+    int glm_slabs = 0;                // "glm_slabs": gene slabs of k_resid_stats (0 = automatic; at most 64)
 };
 
 // device workspace of the post-hoc calls (section "post-hoc interaction GLM"): grown on demand, freed with the handle
@@ -466,6 +467,8 @@ struct insider_hip_handle {
     int sd_path = 0, sd_slabs = 0;
     // the form the last level scores ran (1 = one level window, 2 = several) and its gene slabs
     int ls_path = 0, ls_slabs = 0;
+    // of the last interaction GLM: the gene slabs of k_resid_stats and its form, 10 NB + GT
+    int glm_slabs = 0, glm_form = 0;
     int fd_path = 0;
     // the form the flag pass of the last outlier call ran (1 = tables in LDS, 2 = from global)
     int ol_path = 0;
@@ -2621,6 +2624,7 @@ int insider_hip_set_option(insider_hip_handle *h, const char *name, double value
     else if (s == "vd_stage_kb") h->opt.vd_stage_kb = value;         // LDS budget (KiB, default 48, at most 60) of the staged level tables of k_vd_stats (0 = always the global form)
     else if (s == "ls_slabs") h->opt.ls_slabs = value < 1 ? 0 : (int)std::min(value, 256.0);   // gene slabs of k_ls_prod (0 = from n, p, the compute units and "ls_part_mb"; at most 256)
     else if (s == "ls_part_mb") h->opt.ls_part_mb = value;          // bound (MB, default 256) on the partial scores of the automatic slab count of k_ls_prod
+    else if (s == "glm_slabs") h->opt.glm_slabs = value < 1 ? 0 : (int)std::min(value, 64.0);   // gene slabs of k_resid_stats (0 = from n and the compute units; at most 64)
     else if (s == "sd_slabs") h->opt.sd_slabs = value < 1 ? 0 : (int)std::min(value, 256.0);   // gene slabs of k_sd_stats (0 = from n, p and the compute units; at most 256)
     else if (s == "cd_variant") h->opt.cd_variant = (int)value;   // 0 = register-resident (4 genes per wave; K <= 32, and 32 < K <= 48 with the third slot's columns in LDS), 1 = group kernel, 2 = row16 (LDS, K <= 48)
     else return fail(INSIDER_ERR_ARG, "unknown option " + s);
@@ -3480,6 +3484,8 @@ int insider_hip_get_info(insider_hip_handle *h, const char *name, double *out)
     else if (s == "ls_path") *out = h->ls_path;                     // last level scores: 1 = one level window (X read once), 2 = several
     else if (s == "ls_slabs") *out = h->ls_slabs;                   // ... and its gene slabs
     else if (s == "sd_slabs") *out = h->sd_slabs;                   // ... and its gene slabs
+    else if (s == "glm_slabs") *out = h->glm_slabs;                 // gene slabs of the last interaction GLM's k_resid_stats
+    else if (s == "glm_form") *out = h->glm_form;                   // ... and its form, 10 NB + GT (18, 24, 32, 42)
     else if (s == "fd_path") *out = h->fd_path;                     // last factor decomposition: 1 = one column window (X read once), 2 = several
     else if (s == "col_mfma_per_gene") {
         // v_mfma_f64_16x16x4_f64 instructions the column-side statistics kernel issues per gene (2048 flops each; the 4x4x4 form
@@ -3679,11 +3685,16 @@ int interaction_glm_body(insider_hip_handle *h, double *const *A, const double *
     int64_t slab_len = 0;
     int slabs = 1;
     PH_DISPATCH(NB, {
-        // enough blocks for every SIMD of the device several times over, slabs of whole staging rounds
-        const int want = std::max(1, std::min(64, cdiv(4 * h->ds->n_simd, (int64_t)row_blocks * PH_WPB)));
+        // enough blocks for every SIMD of the device several times over (or option "glm_slabs"), slabs of whole staging
+        // rounds
+        const int want = h->opt.glm_slabs > 0
+                             ? h->opt.glm_slabs
+                             : std::max(1, std::min(64, cdiv(4 * h->ds->n_simd, (int64_t)row_blocks * PH_WPB)));
         slab_len = round_up(cdiv(p, want), 16 * GT_);
         slabs = cdiv(p, slab_len);
+        h->glm_form = 10 * NB_ + GT_;
     });
+    h->glm_slabs = slabs;
     if ((rc = w.part.grow((size_t)slabs * n * ldw)) || (rc = w.stats.grow((size_t)n * ldw))) return rc;
     double *part = w.part, *stats = w.stats;
     const double *U = w.U, *cp = w.cp;
@@ -3746,6 +3757,10 @@ int interaction_glm_body(insider_hip_handle *h, double *const *A, const double *
     int hinfo[2] = {0, 0};
     HIPCHECK(hipMemcpyAsync(hinfo, info, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
     HIPCHECK(hipStreamSynchronize(st));
+    // more non-zero rows than genes: C C' is rank-deficient whatever rounding leaves in its last pivots
+    if (!hinfo[0] && hinfo[1] > p)
+        return fail(INSIDER_ERR_SOLVE, "insider_hip_interaction_glm: the column factor has " + std::to_string(hinfo[1]) +
+                                       " non-zero rows over " + std::to_string(p) + " genes: C C' is rank-deficient");
     if (hinfo[0])
         return fail(INSIDER_ERR_SOLVE, "insider_hip_interaction_glm: C C' restricted to the non-zero rows of C is singular to "
                                        "working precision (pivot " + std::to_string(hinfo[0]) + " of " +

@@ -288,8 +288,10 @@ __global__ void __launch_bounds__(64) k_glm_factor(const double *__restrict__ Gm
 }
 
 // One wave per group: beta = G_r^-1 mean(w) (forward and back substitution with L, lane q = reduced dimension q),
-// RSS = ss - m beta'mean(w) (= ss - m beta' G beta), dof = m p - r, se = sqrt(RSS / dof diag(G_r^-1) / m).  Outputs
-// G x K column-major (row grp); aliased dimensions NaN; an empty group gives zeros and dof 0.
+// RSS = max(ss - m beta'mean(w), 0) (= ss - m beta' G beta; for residual rows in the row space of C the difference cancels
+// to rounding noise of either sign, and a negative one is returned as 0: se = 0, not NaN), dof = m p - r,
+// se = sqrt(RSS / dof diag(G_r^-1) / m).  Outputs G x K column-major (row grp); aliased dimensions NaN; an empty group
+// gives zeros and dof 0.
 __global__ void __launch_bounds__(64) k_glm_groups(const double *__restrict__ gsum, int ldw, const int *__restrict__ gptr,
                                                    int K, int64_t p, const int *__restrict__ nz, const double *__restrict__ L,
                                                    const double *__restrict__ dinv, const int *__restrict__ info, int G,
@@ -323,7 +325,8 @@ __global__ void __launch_bounds__(64) k_glm_groups(const double *__restrict__ gs
     double dot = lane < r ? b * wbar : 0.0;
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) dot += __shfl_xor(dot, o);
-    const double rss = gsum[(size_t)grp * ldw + K] - m * dot;
+    const double diff = gsum[(size_t)grp * ldw + K] - m * dot;
+    const double rss = diff < 0.0 ? 0.0 : diff;   // (the expanded form may cancel to a tiny negative sum: a sum of squares is not)
     const double dofv = (double)m * (double)p - r;
     if (lane < r) {
         coeff[grp + (size_t)kq * G] = b;

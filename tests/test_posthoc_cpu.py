@@ -90,3 +90,52 @@ def test_cli_accepts_interaction_glm():
     assert a.interaction_glm == 1
     assert fit.parse(["--x", "X.npy", "--levels", "L.npy", "--rank", "3", "--lambda", "1", "--alpha", "0.1"]).interaction_glm \
         is None
+
+
+def test_longdouble_reference_agrees_with_glm_interaction():
+    """tests/glm_reference.py (the yardstick of tests/test_gpu_glm_forms.py) against the host closed form at K = 7, p = 301:
+    coefficients to 1e-12 of each level's largest, p-values through t_pvalues() to 1e-9."""
+    from tests import glm_reference as gr
+    rng = np.random.default_rng(11)
+    n, p, K, G = 90, 301, 7, 6
+    R = rng.standard_normal((n, p))
+    Cm = rng.standard_normal((K, p))
+    group = rng.permutation(np.concatenate([np.arange(1, G + 1), rng.integers(1, G + 1, size=n - G)]))
+    ref_c, ref_p = posthoc.glm_interaction(R, None, group, Cm)
+    got = gr.glm_reference(R, group, G, Cm)
+    assert got["coeff"].dtype == np.longdouble
+    assert gr.EXTENDED == (np.finfo(np.longdouble).eps < np.finfo(np.float64).eps)
+    coeff = got["coeff"].astype(np.float64)
+    assert np.all(np.abs(coeff - ref_c) <= 1e-12 * np.abs(ref_c).max(axis=1, keepdims=True))
+    counts = np.bincount(group, minlength=G + 1)[1:]
+    np.testing.assert_array_equal(got["m"], counts)
+    np.testing.assert_array_equal(got["dof"].astype(np.float64), counts * p - K)
+    pv = posthoc.t_pvalues(coeff, got["se"].astype(np.float64), got["dof"].astype(np.float64))
+    np.testing.assert_allclose(pv, ref_p, rtol=1e-9, atol=0)
+    # the direct RSS and the expanded form the device uses agree; ss and cond are what they say
+    np.testing.assert_allclose(got["ss"].astype(np.float64), [np.sum(R[group == g] ** 2) for g in range(1, G + 1)], rtol=1e-13)
+    assert abs(got["cond"] - np.linalg.cond(Cm @ Cm.T)) <= 1e-9 * got["cond"]
+    np.testing.assert_allclose(got["dinv"].astype(np.float64), np.diag(np.linalg.inv(Cm @ Cm.T)), rtol=1e-12)
+    # a zero row of C is dropped: NaN columns, rank K - 1, an empty group gives zero rows
+    Cz = Cm.copy()
+    Cz[2] = 0.0
+    gz = np.where(group == 3, 0, group)
+    got = gr.glm_reference(R, gz, G, Cz)
+    keep = [0, 1, 3, 4, 5, 6]
+    assert list(got["keep"]) == keep
+    assert np.all(np.isnan(got["coeff"][[0, 1, 3, 4, 5], 2])) and np.isnan(got["dinv"][2])
+    assert np.all(got["coeff"][2] == 0) and np.all(got["se"][2] == 0) and got["dof"][2] == 0 and got["m"][2] == 0
+    live = [0, 1, 3, 4, 5]
+    ref_c, _ = posthoc.glm_interaction(R[gz > 0], None, np.searchsorted(np.unique(gz[gz > 0]), gz[gz > 0]) + 1, Cz[keep])
+    c = got["coeff"].astype(np.float64)[np.ix_(live, keep)]
+    assert np.all(np.abs(c - ref_c) <= 1e-12 * np.abs(ref_c).max(axis=1, keepdims=True))
+
+
+def test_glm_option_and_info_keys_are_declared():
+    import os
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    hdr = open(os.path.join(root, "include", "insider_hip.h")).read()
+    src = open(os.path.join(root, "insider_amd", "csrc", "insider_hip.hip")).read()
+    for key in ("glm_slabs", "glm_form"):
+        assert f'"{key}"' in hdr and f's == "{key}"' in src, key
+    assert src.count('s == "glm_slabs"') == 2                 # an option and an info key
