@@ -539,6 +539,50 @@ int insider_hip_enrichment(const double *scores, int64_t R, int64_t p, const int
 double insider_hip_last_enrichment_ms(void);
 int insider_hip_enrichment_sample(uint64_t seed, uint32_t perm, int64_t m, int64_t p, int32_t *out);
 
+/* K-means (Lloyd) clustering of embeddings (insider_amd/csrc/insider_kmeans.hpp).  Handle-free, one device.
+ *   Layout.  P is D x N, column-major: one point is D contiguous doubles, the layout of column_factor.  init is D x k or NULL,
+ *   centers D x k; label, dist, second, dist2 have length N, sizes length k, traj max_iter + 1 entries; final_inertia, iters and
+ *   converged have length `restarts`; best is one int.
+ *   Working points.  metric 0 = cosine (spherical k-means): x_i = p_i / |p_i|, |p_i| the square root of the sum of squares taken
+ *   in index order (as insider_hip_neighbors normalises); a point whose sum of squares is 0 is DEAD: label = second = -1,
+ *   dist = dist2 = NaN, it is in no cluster, no sum, no size, and never an initial centre.  metric 1 = Euclidean: x_i = p_i and
+ *   every point is alive.  Na = the number of alive points.
+ *   Score of (point i, centre j).  Cosine: s = x_i . c_j (centres have unit norm).  Euclidean: s = x_i . c_j - h_j,
+ *   h_j = 0.5 * (the sum of squares of c_j in index order).  The centre of a point (label) is the one with the largest s, equal
+ *   scores (-0.0 == 0.0) to the lowest centre index; second is the next centre in that order (-1 / NaN when k = 1).
+ *   Distances.  Cosine: dist = 1 - s.  Euclidean: dist = max(0, |x_i|^2 - 2 s), |x_i|^2 summed in index order.  dist2 is the same
+ *   of the second centre.
+ *   Update.  Cluster j = the alive points with label j, n_j its size.  Euclidean: c_j = (sum of the members) / n_j, one division
+ *   per coordinate, no reciprocal.  Cosine: c_j = (sum of the members) / |sum| (index order).  A cluster with n_j = 0 keeps its
+ *   centre and reports size 0; so does a cluster under cosine whose sum has norm 0.
+ *   Loop of one restart.  Assign to the initial centres: L_0 and J_0, J = the sum of dist over the alive points (the inertia).
+ *   For t = 0, 1, ...: if t == max_iter stop, unconverged; else update the centres from L_t and assign again: L_{t+1}, J_{t+1};
+ *   if L_{t+1} == L_t stop, converged.  iters = the number of updates; traj = J_0 .. J_iters, NaN beyond; label, second, dist,
+ *   dist2 and sizes always come from the last assignment, which was made against the returned centres.  max_iter = 0 with
+ *   init given is therefore "assign these points to these centres".
+ *   Initial centres.  init given: restarts must be 1; under cosine its columns are normalised (a zero-norm column is an
+ *   argument error).  init NULL (Forgy): with a_0 < a_1 < ... the Na alive point indices, restart r starts from x at
+ *   a_{phi(j)}, j < k, phi = insider_sample_phi on [0, Na) under insider_sample_key(seed, r) (include/insider_sample.h;
+ *   insider_hip_enrichment_sample(seed, r, k, Na, out) names the draw).  Duplicate points may give duplicate centres: the tie
+ *   rule then leaves the higher-indexed one empty.
+ *   Restarts are independent; best = the restart with the lowest final_inertia (= its last J), ties to the lowest r; centers,
+ *   label, dist, second, dist2, sizes and traj belong to best.
+ *   Purity.  Centre sums use no floating-point atomics (a stable counting sort by label, then sums in member order; the counts
+ *   are integer atomics): the result is a pure function of the arguments and repeated calls return identical bits.  The score of
+ *   a pair is the same instruction sequence wherever the pair falls: with max_iter = 0 a call on a window of the points returns
+ *   exactly those rows of the full call.
+ *   Device memory is O((N + k) D + N) (the counting sort adds at most 4 N + k integers).  Between the upload and the final
+ *   download the only thing that crosses the bus is one record per iteration: the inertia and the count of changed labels.
+ *   INSIDER_ERR_ARG, nothing written: a NULL pointer (init may be NULL), D outside 1..63, k outside 1..4096, N < 1 or
+ *   N > INT32_MAX, an unknown metric, restarts outside 1..256, restarts != 1 with init given, max_iter outside 0..10000, a
+ *   non-finite value in P or init, k > Na, init NULL with Na < 2 (all checked on the host, before a device is opened).
+ *   insider_hip_last_kmeans_ms: of the calling THREAD's last call, the HIP-event time in ms from its first kernel to its last
+ *   (the per-iteration records included, the upload and the download excluded). */
+int insider_hip_kmeans(const double *P, int64_t N, int D, int k, int metric, const double *init, int restarts, int max_iter,
+                       uint64_t seed, int device, double *centers, int32_t *label, double *dist, int32_t *second, double *dist2,
+                       int32_t *sizes, double *traj, double *final_inertia, int32_t *iters, int32_t *converged, int32_t *best);
+double insider_hip_last_kmeans_ms(void);
+
 /* Profile of the last insider_hip_optimize() call (option "profile" = 1), HIP-event timed on the library's stream.
  * out[0..11]: {column-side masked-Gram launches, total ms, row-side masked-Gram launches, total ms,
  *  column-solve (CD / ridge) launches, total ms, test-residual launches, total ms,

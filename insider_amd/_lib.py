@@ -31,6 +31,7 @@ SYMBOLS = (
     "insider_hip_remask", "insider_hip_set_folds", "insider_hip_remask_fold", "insider_hip_factor_decomposition",
     "insider_hip_outliers", "insider_hip_neighbors", "insider_hip_last_neighbors_ms", "insider_hip_level_scores",
     "insider_hip_enrichment", "insider_hip_last_enrichment_ms", "insider_hip_enrichment_sample",
+    "insider_hip_kmeans", "insider_hip_last_kmeans_ms",
 )
 COMM_ID_BYTES = 128
 # insider_hip_outliers (insider_amd/csrc/insider_outliers.hpp): the samples a block of k_ol_flag covers per trip (OL_TRIP) and the
@@ -146,6 +147,9 @@ def load():
                                            C.c_uint64, C.c_int, dp, i32p, i32p, i32p, dp, i32p]
     lib.insider_hip_last_enrichment_ms.restype = C.c_double
     lib.insider_hip_enrichment_sample.argtypes = [C.c_uint64, C.c_uint32, C.c_int64, C.c_int64, i32p]
+    lib.insider_hip_kmeans.argtypes = [dp, C.c_int64, C.c_int, C.c_int, C.c_int, dp, C.c_int, C.c_int, C.c_uint64, C.c_int, dp, i32p,
+                                       dp, i32p, dp, i32p, dp, dp, i32p, i32p, i32p]
+    lib.insider_hip_last_kmeans_ms.restype = C.c_double
     lib.insider_hip_get_profile.argtypes = [C.c_void_p, dp]
     lib.insider_hip_get_sweeps.argtypes = [C.c_void_p, i32p]
     lib.insider_hip_last_cd_ms.restype = C.c_double

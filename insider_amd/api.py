@@ -765,6 +765,79 @@ def enrichment(scores, set_ptr, set_genes, nperm=1000, weight=1, seed=DEFAULT_SE
     return rec
 
 
+KMEANS_METRICS = {"cosine": 0, "euclidean": 1}
+KMEANS_MAX_K = 4096
+KMEANS_MAX_RESTARTS = 256
+KMEANS_MAX_ITER = 10000
+
+
+def kmeans_args(points, k, metric, init, restarts, max_iter, seed):
+    """The checked arguments of kmeans() / posthoc.kmeans_host(): (P column-major float64 D x N, k, metric code, init
+    column-major D x k or None, restarts, max_iter, seed).  Every argument error of insider_hip_kmeans (include/insider_hip.h)
+    raises InsiderError(ERR_ARG) here, before the library is reached."""
+    def bad(msg):
+        return InsiderError(_lib.ERR_ARG, msg)
+    P = _lib.f64(points)
+    if P.ndim != 2:
+        raise bad("points must be a D x N array")
+    D, N = P.shape
+    if not 1 <= D <= _lib.MAX_K:
+        raise bad(f"D must be in 1..{_lib.MAX_K}")
+    if not 1 <= N < 2 ** 31:
+        raise bad("points must hold 1..2^31-1 columns")
+    if metric not in KMEANS_METRICS:
+        raise bad(f"metric must be one of {sorted(KMEANS_METRICS)}")
+    for name, v, lo, hi in (("k", k, 1, KMEANS_MAX_K), ("restarts", restarts, 1, KMEANS_MAX_RESTARTS),
+                            ("max_iter", max_iter, 0, KMEANS_MAX_ITER), ("seed", seed, 0, 2 ** 64 - 1)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
+            raise bad(f"{name} must be an integer in {lo}..{hi}")
+    if not np.isfinite(P).all():
+        raise bad("points must be finite")
+    code = KMEANS_METRICS[metric]
+    n_alive = int(np.count_nonzero((P * P).sum(axis=0) > 0)) if code == 0 else N
+    if init is not None:
+        init = _lib.f64(init)
+        if init.ndim != 2 or init.shape != (D, k):
+            raise bad("init must be a D x k array")
+        if restarts != 1:
+            raise bad("restarts must be 1 when init is given")
+        if not np.isfinite(init).all():
+            raise bad("init must be finite")
+        if code == 0 and not ((init * init).sum(axis=0) > 0).all():
+            raise bad("an init column has norm 0")
+    elif n_alive < 2:
+        raise bad("a drawn start needs at least 2 alive points")
+    if k > n_alive:
+        raise bad("k must not exceed the number of alive points")
+    return P, int(k), code, init, int(restarts), int(max_iter), int(seed)
+
+
+def kmeans(points, k, metric="cosine", init=None, restarts=8, max_iter=100, seed=DEFAULT_SEED, device=0):
+    """K-means (Lloyd) of the columns of ``points`` (D x N, one point per column, as column_factor) on the device
+    (insider_hip_kmeans; include/insider_hip.h states the definitions).  metric "cosine" is spherical k-means on the normalised
+    columns (an all-zero column is dead: label -1, in no cluster), "euclidean" the plain one.  init: D x k starting centres
+    (restarts must then be 1; max_iter = 0 assigns the points to them), None: ``restarts`` Forgy starts drawn from ``seed``, the
+    one with the lowest final inertia is returned.  -> dict(centers (D x k), label, second (N int32, 0-based, -1 = none), dist,
+    dist2 (N), sizes (k int32), traj (max_iter + 1: the inertia before every update, NaN beyond iters), final_inertia, iters,
+    converged (restarts), best, ms (the HIP-event time of the call's kernels))."""
+    P, k, code, init, restarts, max_iter, seed = kmeans_args(points, k, metric, init, restarts, max_iter, seed)
+    D, N = P.shape
+    i32 = C.c_int32
+    rec = dict(centers=np.full((D, k), np.nan, order="F"), label=np.full(N, -1, dtype=np.int32), dist=np.full(N, np.nan),
+               second=np.full(N, -1, dtype=np.int32), dist2=np.full(N, np.nan), sizes=np.zeros(k, dtype=np.int32),
+               traj=np.full(max_iter + 1, np.nan), final_inertia=np.full(restarts, np.nan),
+               iters=np.zeros(restarts, dtype=np.int32), converged=np.zeros(restarts, dtype=np.int32))
+    best = np.zeros(1, dtype=np.int32)
+    lib = _lib.load()
+    _lib.check(lib.insider_hip_kmeans(_lib.ptr(P), N, D, k, code, None if init is None else _lib.ptr(init), restarts, max_iter,
+                                      seed, int(device), _lib.ptr(rec["centers"]), _lib.ptr(rec["label"], i32),
+                                      _lib.ptr(rec["dist"]), _lib.ptr(rec["second"], i32), _lib.ptr(rec["dist2"]),
+                                      _lib.ptr(rec["sizes"], i32), _lib.ptr(rec["traj"]), _lib.ptr(rec["final_inertia"]),
+                                      _lib.ptr(rec["iters"], i32), _lib.ptr(rec["converged"], i32), _lib.ptr(best, i32)))
+    rec.update(best=int(best[0]), ms=float(lib.insider_hip_last_kmeans_ms()))
+    return rec
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # caller level — R/insider.R, R/utils.R
 # ---------------------------------------------------------------------------------------------------------------

@@ -14,6 +14,7 @@
 #include "insider_outliers.hpp"
 #include "insider_neighbors.hpp"
 #include "insider_enrich.hpp"
+#include "insider_kmeans.hpp"
 
 #include <rccl/rccl.h>
 
@@ -42,6 +43,7 @@ thread_local double g_last_cd_ms = 0.0;   // per calling thread: the ABI is re-e
 thread_local int g_last_cd_solver = 0;     // (ColSolver)
 thread_local double g_last_neighbors_ms = 0.0;
 thread_local double g_last_enrichment_ms = 0.0;
+thread_local double g_last_kmeans_ms = 0.0;
 
 int fail(int code, const std::string &msg)
 {
@@ -3159,6 +3161,205 @@ int insider_hip_neighbors(const double *Q, int64_t nq, const double *B, int64_t 
 }
 
 double insider_hip_last_neighbors_ms(void) { return g_last_neighbors_ms; }
+
+// ---- k-means (insider_kmeans.hpp) -----------------------------------------------------------------------------------------
+int insider_hip_kmeans(const double *P, int64_t N, int D, int k, int metric, const double *init, int restarts, int max_iter,
+                       uint64_t seed, int device, double *centers, int32_t *label, double *dist, int32_t *second, double *dist2,
+                       int32_t *sizes, double *traj, double *final_inertia, int32_t *iters, int32_t *converged, int32_t *best)
+{
+    if (!P || !centers || !label || !dist || !second || !dist2 || !sizes || !traj || !final_inertia || !iters || !converged ||
+        !best)
+        return fail(INSIDER_ERR_ARG, "null argument");
+    if (D < 1 || D > INSIDER_MAX_K) return fail(INSIDER_ERR_ARG, "D must be in 1..63");
+    if (k < 1 || k > KM_MAX_K) return fail(INSIDER_ERR_ARG, "k must be in 1..4096");
+    if (N < 1 || N > (int64_t)std::numeric_limits<int32_t>::max()) return fail(INSIDER_ERR_ARG, "N must be in 1..2^31-1");
+    if (metric != 0 && metric != 1) return fail(INSIDER_ERR_ARG, "metric must be 0 (cosine) or 1 (Euclidean)");
+    if (restarts < 1 || restarts > 256) return fail(INSIDER_ERR_ARG, "restarts must be in 1..256");
+    if (init && restarts != 1) return fail(INSIDER_ERR_ARG, "restarts must be 1 when init is given");
+    if (max_iter < 0 || max_iter > 10000) return fail(INSIDER_ERR_ARG, "max_iter must be in 0..10000");
+    if (!all_finite(P, (size_t)N * D) || (init && !all_finite(init, (size_t)k * D)))
+        return fail(INSIDER_ERR_ARG, "P and init must be finite");
+    // the alive points, by k_nn_prep's rule: the sum of squares in index order is not 0
+    auto zero_norm = [D](const double *c) {
+        double ss = 0.0;
+        for (int d = 0; d < D; ++d) ss = std::fma(c[d], c[d], ss);
+        return !(std::sqrt(ss) > 0.0);
+    };
+    std::vector<int32_t> alive_idx;
+    int64_t Na = N;
+    if (metric == 0) {
+        Na = 0;
+        if (!init) alive_idx.reserve((size_t)N);
+        for (int64_t i = 0; i < N; ++i) {
+            if (zero_norm(P + (size_t)i * D)) continue;
+            ++Na;
+            if (!init) alive_idx.push_back((int32_t)i);
+        }
+    }
+    if (k > Na) return fail(INSIDER_ERR_ARG, "k must not exceed the number of alive points");
+    if (!init && Na < 2) return fail(INSIDER_ERR_ARG, "a drawn start needs at least 2 alive points");
+    if (init && metric == 0)
+        for (int j = 0; j < k; ++j)
+            if (zero_norm(init + (size_t)j * D)) return fail(INSIDER_ERR_ARG, "an init column has norm 0");
+    std::vector<int32_t> pick;   // restart r starts from the points pick[r k ..]
+    if (!init) {
+        pick.resize((size_t)restarts * k);
+        const uint32_t half = insider_sample_half((uint32_t)Na);
+        for (int r = 0; r < restarts; ++r) {
+            const uint32_t key = insider_sample_key(seed, (uint32_t)r);
+            for (int j = 0; j < k; ++j) {
+                const uint32_t a = insider_sample_phi(key, half, (uint32_t)Na, (uint32_t)j);
+                pick[(size_t)r * k + j] = metric == 0 ? alive_idx[a] : (int32_t)a;
+            }
+        }
+        std::vector<int32_t>().swap(alive_idx);
+    }
+    int rc = cd_common_checks(D, N, device);
+    if (rc) return rc;
+    HIPCHECK(hipSetDevice(device));
+    const int K4 = (D + 3) & ~3, KS = (K4 + 15) / 16;
+    const int NT = std::min(K4 <= 32 ? 4 : 2, (k + 15) / 16);
+    const int kpad = (int)round_up(k, 16 * NT);
+    const int64_t npad = round_up(N, 16);
+    const int nblk = cdiv(N, 16 * KM_NW);
+    const int B = (int)std::min<int64_t>(KM_MAX_CHUNKS, (N + 1023) / 1024);   // B k <= 4 N + k
+    const int64_t chunk = (N + B - 1) / B;
+    const size_t lds = (size_t)(NT * 16 * K4 + NT * 16) * sizeof(double);
+    const bool keep = restarts > 1;
+    DevBuf<double> dX, dXp, dxx, dC, dCp, dh, ddist, ddist2, dpin, drec, bC, bdist, bdist2;
+    DevBuf<int> dalive, dpch, dtable, dfirst;
+    DevBuf<int32_t> dlabel, dsecond, dsize, dmember, dpick, blabel, bsecond, bsize;
+    if ((rc = dX.alloc((size_t)N * D)) || (rc = dXp.alloc((size_t)npad * K4)) || (rc = dalive.alloc((size_t)npad)) ||
+        (rc = dxx.alloc((size_t)std::max<int64_t>(N, k))) || (rc = dC.alloc((size_t)k * D)) || (rc = dCp.alloc((size_t)kpad * K4)) ||
+        (rc = dh.alloc((size_t)kpad)) || (rc = ddist.alloc((size_t)N)) || (rc = ddist2.alloc((size_t)N)) ||
+        (rc = dlabel.alloc((size_t)N)) || (rc = dsecond.alloc((size_t)N)) || (rc = dpin.alloc((size_t)nblk)) ||
+        (rc = dpch.alloc((size_t)nblk)) || (rc = drec.alloc(2)) || (rc = dtable.alloc((size_t)B * k)) ||
+        (rc = dfirst.alloc((size_t)k)) || (rc = dsize.alloc((size_t)k)) || (rc = dmember.alloc((size_t)N)))
+        return rc;
+    if (keep && ((rc = bC.alloc((size_t)k * D)) || (rc = bdist.alloc((size_t)N)) || (rc = bdist2.alloc((size_t)N)) ||
+                 (rc = blabel.alloc((size_t)N)) || (rc = bsecond.alloc((size_t)N)) || (rc = bsize.alloc((size_t)k))))
+        return rc;
+    HIPCHECK(hipMemcpy(dX, P, (size_t)N * D * sizeof(double), hipMemcpyHostToDevice));
+    if (!init && (rc = dpick.upload(pick))) return rc;
+    Event e0, e1;
+    HIPCHECK(hipEventCreate(e0.out()));
+    HIPCHECK(hipEventCreate(e1.out()));
+    HIPCHECK(hipEventRecord(e0, 0));
+    hipLaunchKernelGGL(k_nn_prep, dim3(cdiv(npad, 256)), dim3(256), 0, 0, (const double *)dX, N, npad, D, K4, metric, dXp.get(),
+                       dalive.get());
+    KCHECK();
+    hipLaunchKernelGGL(k_km_points, dim3(cdiv(N, 256)), dim3(256), 0, 0, dX.get(), N, D, metric, dxx.get());
+    KCHECK();
+    // one assignment against dC, its record and the clusters' sizes
+    auto assign = [&]() -> int {
+        hipLaunchKernelGGL(k_km_cprep, dim3(cdiv(kpad, 256)), dim3(256), 0, 0, (const double *)dC, k, kpad, D, K4, metric,
+                           dCp.get(), dh.get());
+        KCHECK();
+#define KM_LAUNCH(KS_)                                                                                                          \
+    hipLaunchKernelGGL((k_km_assign<KS_>), dim3(nblk), dim3(64 * KM_NW), lds, 0, (const double *)dXp, (const int *)dalive, N,    \
+                       (const double *)dCp, (const double *)dh, k, kpad, K4, NT, metric, (const double *)dxx, dlabel.get(),      \
+                       dsecond.get(), ddist.get(), ddist2.get(), dpin.get(), dpch.get())
+        if (KS == 1) KM_LAUNCH(1);
+        else if (KS == 2) KM_LAUNCH(2);
+        else if (KS == 3) KM_LAUNCH(3);
+        else KM_LAUNCH(4);
+#undef KM_LAUNCH
+        KCHECK();
+        hipLaunchKernelGGL(k_km_reduce, dim3(1), dim3(256), 0, 0, (const double *)dpin, (const int *)dpch, nblk, drec.get());
+        KCHECK();
+        hipLaunchKernelGGL(k_km_hist, dim3(B), dim3(64), (size_t)k * sizeof(int), 0, (const int32_t *)dlabel, N, chunk, k,
+                           dtable.get());
+        KCHECK();
+        hipLaunchKernelGGL(k_km_colscan, dim3(cdiv(k, 256)), dim3(256), 0, 0, dtable.get(), B, k, dsize.get());
+        KCHECK();
+        return INSIDER_OK;
+    };
+    std::vector<double> tr((size_t)max_iter + 1), best_tr;
+    std::vector<double> fin((size_t)restarts);
+    std::vector<int32_t> its((size_t)restarts), conv((size_t)restarts);
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    int best_r = 0;
+    for (int r = 0; r < restarts; ++r) {
+        if (init) {
+            HIPCHECK(hipMemcpy(dC, init, (size_t)k * D * sizeof(double), hipMemcpyHostToDevice));
+            if (metric == 0) {   // the columns normalised as the points are (|c|^2 goes to a corner nobody reads again)
+                hipLaunchKernelGGL(k_km_points, dim3(cdiv(k, 256)), dim3(256), 0, 0, dC.get(), (int64_t)k, D, metric, dh.get());
+                KCHECK();
+            }
+        } else {
+            hipLaunchKernelGGL(k_km_gather, dim3(cdiv((int64_t)k * D, 256)), dim3(256), 0, 0, (const double *)dX,
+                               (const int32_t *)dpick.get() + (size_t)r * k, k, D, dC.get());
+            KCHECK();
+        }
+        HIPCHECK(hipMemsetAsync(dlabel, 0xFF, (size_t)N * sizeof(int32_t), 0));
+        std::fill(tr.begin(), tr.end(), nan);
+        double rec[2];
+        if ((rc = assign())) return rc;
+        HIPCHECK(hipMemcpy(rec, drec, sizeof(rec), hipMemcpyDeviceToHost));
+        tr[0] = rec[0];
+        int t = 0, cv = 0;
+        while (t < max_iter) {
+            hipLaunchKernelGGL(k_km_scan, dim3(1), dim3(256), 0, 0, (const int32_t *)dsize, k, dfirst.get());
+            KCHECK();
+            hipLaunchKernelGGL(k_km_scatter, dim3(B), dim3(64), (size_t)k * sizeof(int), 0, (const int32_t *)dlabel, N, chunk, k,
+                               (const int *)dtable, (const int *)dfirst, dmember.get());
+            KCHECK();
+            hipLaunchKernelGGL(k_km_sum, dim3(k), dim3(256), 0, 0, (const double *)dX, (const int32_t *)dmember,
+                               (const int *)dfirst, (const int32_t *)dsize, D, metric, dC.get());
+            KCHECK();
+            if ((rc = assign())) return rc;
+            HIPCHECK(hipMemcpy(rec, drec, sizeof(rec), hipMemcpyDeviceToHost));   // the iteration's record: all the host reads
+            tr[++t] = rec[0];
+            if (rec[1] == 0.0) {
+                cv = 1;
+                break;
+            }
+        }
+        fin[r] = tr[t];
+        its[r] = t;
+        conv[r] = cv;
+        if (r == 0 || fin[r] < fin[best_r]) {
+            best_r = r;
+            best_tr = tr;
+            if (keep) {
+                HIPCHECK(hipMemcpyAsync(bC, dC, (size_t)k * D * sizeof(double), hipMemcpyDeviceToDevice, 0));
+                HIPCHECK(hipMemcpyAsync(bdist, ddist, (size_t)N * sizeof(double), hipMemcpyDeviceToDevice, 0));
+                HIPCHECK(hipMemcpyAsync(bdist2, ddist2, (size_t)N * sizeof(double), hipMemcpyDeviceToDevice, 0));
+                HIPCHECK(hipMemcpyAsync(blabel, dlabel, (size_t)N * sizeof(int32_t), hipMemcpyDeviceToDevice, 0));
+                HIPCHECK(hipMemcpyAsync(bsecond, dsecond, (size_t)N * sizeof(int32_t), hipMemcpyDeviceToDevice, 0));
+                HIPCHECK(hipMemcpyAsync(bsize, dsize, (size_t)k * sizeof(int32_t), hipMemcpyDeviceToDevice, 0));
+            }
+        }
+    }
+    HIPCHECK(hipEventRecord(e1, 0));
+    HIPCHECK(hipEventSynchronize(e1));
+    float ms = 0.0f;
+    (void)hipEventElapsedTime(&ms, e0, e1);
+    g_last_kmeans_ms = ms;
+    // every result is staged on the host first: a failed download leaves the caller's arrays as they were
+    std::vector<double> hC((size_t)k * D), hdist((size_t)N), hdist2((size_t)N);
+    std::vector<int32_t> hlabel((size_t)N), hsecond((size_t)N), hsize((size_t)k);
+    HIPCHECK(hipMemcpy(hC.data(), keep ? bC : dC, hC.size() * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHECK(hipMemcpy(hdist.data(), keep ? bdist : ddist, hdist.size() * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHECK(hipMemcpy(hdist2.data(), keep ? bdist2 : ddist2, hdist2.size() * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHECK(hipMemcpy(hlabel.data(), keep ? blabel : dlabel, hlabel.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIPCHECK(hipMemcpy(hsecond.data(), keep ? bsecond : dsecond, hsecond.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIPCHECK(hipMemcpy(hsize.data(), keep ? bsize : dsize, hsize.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    std::copy(hC.begin(), hC.end(), centers);
+    std::copy(hdist.begin(), hdist.end(), dist);
+    std::copy(hdist2.begin(), hdist2.end(), dist2);
+    std::copy(hlabel.begin(), hlabel.end(), label);
+    std::copy(hsecond.begin(), hsecond.end(), second);
+    std::copy(hsize.begin(), hsize.end(), sizes);
+    std::copy(best_tr.begin(), best_tr.end(), traj);
+    std::copy(fin.begin(), fin.end(), final_inertia);
+    std::copy(its.begin(), its.end(), iters);
+    std::copy(conv.begin(), conv.end(), converged);
+    *best = best_r;
+    return INSIDER_OK;
+}
+
+double insider_hip_last_kmeans_ms(void) { return g_last_kmeans_ms; }
 
 // ---- enrichment (insider_enrich.hpp) -----------------------------------------------------------------------------------------
 int insider_hip_enrichment_sample(uint64_t seed, uint32_t perm, int64_t m, int64_t p, int32_t *out)

@@ -11,6 +11,7 @@
     ... --factor-decomposition                  # then the per-factor decomposition (which factor, through which covariate)
     ... --outliers 3 [--outlier-entries train]  # then the entries whose standardised residual has |z| >= 3, on the device
     ... --gene-neighbors 10 --sample-neighbors 10 [--neighbor-metric cosine]   # then each gene's / sample's nearest in latent space
+    ... --gene-modules 20 --sample-clusters 6 [--cluster-metric cosine]        # then k-means of the genes / samples in latent space
     ... --level-scores 1 [--level-score-entries train]   # then every sample against every level of covariate column 1 (1-based)
     ... --gene-sets SETS.gmt [--gene-names NAMES.txt] [--enrich-perms 1000] [--enrich-levels 1]   # then what each factor means
 
@@ -30,7 +31,13 @@ ascending gene, then sample), ol_gene_counts (p x 2) and ol_sample_counts (n x 2
 --gene-neighbors N / --sample-neighbors N add each gene's N nearest genes by its column of C and each sample's N nearest
 samples by its row embedding (posthoc.gene_neighbors / sample_neighbors, --neighbor-metric cosine or dot): nn_gene_index /
 nn_gene_score (p x N) and nn_sample_index / nn_sample_score (n x N), 0-based, descending score, ties by ascending index, open
-slots -1 / NaN; --level-scores COV adds, for covariate column COV (1-based), ls_sse (n x L: the residual sum of squares of every
+slots -1 / NaN; --gene-modules K / --sample-clusters K add the k-means partition of the genes by their columns of C and of the
+samples by their row embeddings (posthoc.gene_modules / sample_clusters; --cluster-metric cosine or euclidean, the best of
+--cluster-restarts drawn starts from --cluster-seed, at most --cluster-iters updates each): km_gene_label / km_gene_second (p,
+0-based, -1 = an all-zero column under cosine, or no second centre), km_gene_dist / km_gene_dist2 (p), km_gene_center (K x k),
+km_gene_size (k), km_gene_traj (the inertia before every update, NaN beyond the last) and the same under km_sample_*; with
+--gene-sets also km_gene_overlap / km_gene_hyper_p / km_gene_hyper_fdr (k x S, posthoc.module_overrepresentation);
+--level-scores COV adds, for covariate column COV (1-based), ls_sse (n x L: the residual sum of squares of every
 sample over the --level-score-entries with its embedding for COV replaced by each level's), ls_n, ls_best (1-based, 0 = no
 entry), ls_margin (n) and ls_confusion (L x L, assigned x best; posthoc.ls_derived) — a sample's own level was fitted with that
 sample, so on the entries the fit used the assigned level is favoured, most for levels with few samples; --gene-sets FILE (GMT;
@@ -117,6 +124,23 @@ def parse(argv=None):
                          "on the device; writes nn_sample_index, nn_sample_score (n x N) next to the factors")
     ap.add_argument("--neighbor-metric", choices=("cosine", "dot"), default="cosine",
                     help="--gene-neighbors / --sample-neighbors: the score (default: cosine)")
+    ap.add_argument("--gene-modules", type=int, default=None, metavar="K",
+                    help="after the fit, the k-means partition of the genes into K modules by their columns of C, on the device; "
+                         "writes km_gene_label, km_gene_dist, km_gene_second, km_gene_dist2 (p), km_gene_center (rank x K), "
+                         "km_gene_size (K) and km_gene_traj next to the factors; with --gene-sets also km_gene_overlap, "
+                         "km_gene_hyper_p, km_gene_hyper_fdr (K x S)")
+    ap.add_argument("--sample-clusters", type=int, default=None, metavar="K",
+                    help="after the fit, the k-means partition of the samples into K clusters by their row embeddings, on the "
+                         "device; writes the km_sample_* records (samples that share every level are equal points)")
+    ap.add_argument("--cluster-metric", choices=("cosine", "euclidean"), default="cosine",
+                    help="--gene-modules / --sample-clusters: spherical (cosine, the default: all-zero columns of C form no "
+                         "module) or Euclidean k-means")
+    ap.add_argument("--cluster-restarts", type=int, default=8, metavar="R",
+                    help="--gene-modules / --sample-clusters: drawn starts, the lowest final inertia is kept (default 8)")
+    ap.add_argument("--cluster-iters", type=int, default=100, metavar="I",
+                    help="--gene-modules / --sample-clusters: updates per start at most (default 100)")
+    ap.add_argument("--cluster-seed", type=int, default=0x1D5EED, metavar="S",
+                    help="--gene-modules / --sample-clusters: the seed of the drawn starts")
     ap.add_argument("--gene-sets", default=None, metavar="FILE",
                     help="after the fit, the gene-set enrichment of every factor's |loadings| on the device against the sets of "
                          "this GMT file (name, description, genes; tab-separated); writes gs_factor_es, gs_factor_nes, "
@@ -148,6 +172,18 @@ def parse(argv=None):
         v = getattr(a, name)
         if v is not None and not 1 <= v <= 64:
             ap.error(f"--{name.replace('_', '-')} must be in 1..64")
+    for name in ("gene_modules", "sample_clusters"):
+        v = getattr(a, name)
+        if v is not None and not 1 <= v <= 4096:
+            ap.error(f"--{name.replace('_', '-')} must be in 1..4096")
+        if v is not None and a.tune:
+            ap.error(f"--{name.replace('_', '-')} partitions a fit: it does not go with --tune")
+    if not 1 <= a.cluster_restarts <= 256:
+        ap.error("--cluster-restarts must be in 1..256")
+    if not 0 <= a.cluster_iters <= 10000:
+        ap.error("--cluster-iters must be in 0..10000")
+    if not 0 <= a.cluster_seed < 2 ** 64:
+        ap.error("--cluster-seed must fit 64 bits")
     if a.level_scores is not None and a.level_scores < 1:
         ap.error("--level-scores: COV is 1-based")
     if not a.flat and not (a.x and a.levels):
@@ -175,6 +211,12 @@ def load_inputs(a):
         te = flatio.load_matrix(a.test_mask) if a.test_mask else None
         Z = flatio.load_matrix(a.ctns, np.float64) if a.ctns else None
     return X, lev, tr, te, Z
+
+
+def km_records(prefix, rec):
+    """The records of one api.kmeans() result under <prefix>_label, _dist, _second, _dist2, _center, _size and _traj."""
+    names = dict(label="label", dist="dist", second="second", dist2="dist2", center="centers", size="sizes", traj="traj")
+    return {f"{prefix}_{out}": rec[key] for out, key in names.items()}
 
 
 def main(argv=None):
@@ -302,6 +344,16 @@ def main(argv=None):
         nn = sample_neighbors(list(res["row_matrices"].values()), ds_levels, Z, k=a.sample_neighbors, metric=a.neighbor_metric,
                               device=a.device)
         vd = dict(vd or {}, nn_sample_index=nn["index"], nn_sample_score=nn["score"])
+    km_gene = None
+    km = dict(metric=a.cluster_metric, restarts=a.cluster_restarts, max_iter=a.cluster_iters, seed=a.cluster_seed, device=a.device)
+    if a.gene_modules is not None:
+        from .posthoc import gene_modules
+        km_gene = gene_modules(res["column_factor"], a.gene_modules, **km)
+        vd = dict(vd or {}, **km_records("km_gene", km_gene))
+    if a.sample_clusters is not None:
+        from .posthoc import sample_clusters
+        vd = dict(vd or {}, **km_records("km_sample", sample_clusters(list(res["row_matrices"].values()), ds_levels, Z,
+                                                                      k=a.sample_clusters, **km)))
     gs_names = None
     if a.gene_sets is not None:
         from .posthoc import factor_enrichment, level_enrichment
@@ -322,6 +374,10 @@ def main(argv=None):
             gs = level_enrichment(list(res["row_matrices"].values())[a.enrich_levels - 1], res["column_factor"], sets,
                                   nperm=a.enrich_perms, seed=a.seed, device=a.device)
             vd.update({f"gs_level{a.enrich_levels}_{k}": gs[k] for k in keys})
+        if km_gene is not None:
+            from .posthoc import module_overrepresentation
+            ora = module_overrepresentation(km_gene["label"], sets, k=a.gene_modules)
+            vd.update(km_gene_overlap=ora["overlap"], km_gene_hyper_p=ora["hyper_p"], km_gene_hyper_fdr=ora["hyper_fdr"])
     ds.close()
     summary = dict(train_rmse=res["train_rmse"], test_rmse=None if np.isnan(res["test_rmse"]) else res["test_rmse"],
                    loss=res["loss"], iters=res["iters"], rank=K, **{"lambda": a.lam}, alpha=a.alpha, partition=partition,

@@ -34,6 +34,8 @@ with level_scores_host() as its yardstick and ls_derived() for best / second / m
 gene_neighbors() / sample_neighbors() ask the latent representations themselves which genes lie next to a gene and which
 samples next to a sample (api.neighbors: a K-deep product on the device with the top-k selection fused behind it, the
 similarity matrix never exists), on column_factor and on sample_embeddings(); neighbors_host() is the yardstick.
+gene_modules() / sample_clusters() partition the same two embeddings (api.kmeans: the whole Lloyd loop on the device, cosine or
+Euclidean, restarts); kmeans_host() is the yardstick, module_overrepresentation() / module_summary() read the modules.
 
 factor_enrichment() / level_enrichment() ask what a factor or a level effect means: a preranked gene-set enrichment of the
 rows of column_factor, or of A_b @ column_factor, with a permutation null of random gene sets of equal size
@@ -684,3 +686,190 @@ def level_enrichment(cfd_factor, column_factor, sets, nperm=1000, weight=1, seed
     cfd_factor (L x K) @ column_factor (K x p), signed.  -> as factor_enrichment(), L x S."""
     return _enrich(np.asarray(cfd_factor, dtype=np.float64) @ np.asarray(column_factor, dtype=np.float64), sets, nperm,
                    weight, seed, device)
+
+
+# ---- k-means (include/insider_hip.h states the definitions) ------------------------------------------------------------------
+def _sumsq(M):
+    """The sum of squares of every column, taken in index order."""
+    ss = np.zeros(M.shape[1])
+    for d in range(M.shape[0]):
+        ss = ss + M[d] * M[d]
+    return ss
+
+
+def kmeans_host(points, k, metric="cosine", init=None, restarts=8, max_iter=100, seed=0x1D5EED, device=0, chunk=4096,
+                blas=False):
+    """api.kmeans() in plain numpy float64 (the yardstick of the device path): the same arguments, checks and record, following
+    the definitions of include/insider_hip.h line by line.  The record also holds ``score`` / ``score2`` (N: the best and the
+    runner-up score of the last assignment, NaN for a dead point and for k = 1) and ``min_gap``: over every assignment of the
+    returned restart, the smallest (best - runner-up) score of an alive point divided by the largest |best score| of that
+    assignment (inf when k = 1): how far the run is from a tie that rounding could decide.  Points are scored ``chunk`` at a
+    time; a score adds its D products in index order, so equal points and equal centres tie exactly and the tie rule decides
+    (blas=True takes the matrix product instead: faster, and equal columns may then differ in the last bit).  A cluster's sum
+    runs over its members in ascending index (``device`` is accepted for the common signature and not used; ``ms`` is the wall
+    time)."""
+    import time
+    from . import api
+    t_start = time.perf_counter()
+    P, k, code, init, restarts, max_iter, seed = api.kmeans_args(points, k, metric, init, restarts, max_iter, seed)
+    D, N = P.shape
+    if code == 0:                                                   # working points: x = p / |p|, a zero column is dead
+        nrm = np.sqrt(_sumsq(P))
+        alive = nrm > 0
+        X = np.where(alive, P / np.where(alive, nrm, 1.0), 0.0)
+    else:
+        X, alive = P, np.ones(N, dtype=bool)
+    xx = _sumsq(X)
+    ids = np.flatnonzero(alive)
+
+    def assign(Cm):
+        h = 0.5 * _sumsq(Cm) if code == 1 else np.zeros(k)
+        label, second = np.full(N, -1, dtype=np.int32), np.full(N, -1, dtype=np.int32)
+        s1, s2 = np.full(N, np.nan), np.full(N, np.nan)
+        for c0 in range(0, N, chunk):
+            Xc = X[:, c0:c0 + chunk]
+            if blas:
+                S = Xc.T @ Cm
+            else:
+                S = np.zeros((Xc.shape[1], k))
+                for d in range(D):
+                    S = S + Xc[d][:, None] * Cm[d][None, :]
+            S = (S - h) + 0.0                                       # (-0.0 + 0.0 = 0.0: one zero)
+            rows = np.arange(S.shape[0])
+            l1 = S.argmax(axis=1)                                   # the first of equal scores: the lowest centre index
+            label[c0:c0 + chunk], s1[c0:c0 + chunk] = l1, S[rows, l1]
+            if k > 1:
+                S[rows, l1] = -np.inf
+                l2 = S.argmax(axis=1)
+                second[c0:c0 + chunk], s2[c0:c0 + chunk] = l2, S[rows, l2]
+        if code == 0:
+            d1, d2 = 1.0 - s1, 1.0 - s2
+        else:
+            d1, d2 = np.maximum(0.0, xx - 2.0 * s1), np.where(np.isnan(s2), np.nan, np.maximum(0.0, xx - 2.0 * s2))
+        label[~alive], second[~alive] = -1, -1
+        d1[~alive], d2[~alive] = np.nan, np.nan
+        gap = np.inf
+        if k > 1 and ids.size:
+            top = float(np.abs(s1[ids]).max())
+            gap = float((s1[ids] - s2[ids]).min()) / top if top > 0 else 0.0
+        s1[~alive], s2[~alive] = np.nan, np.nan
+        return label, second, d1, d2, float(d1[ids].sum()), gap, s1, s2
+
+    def update(Cm, label):
+        Cm = Cm.copy(order="F")
+        for j in range(k):
+            members = X[:, label == j]                              # (dead points carry -1)
+            if members.shape[1] == 0:
+                continue                                            # an empty cluster keeps its centre
+            tot = np.cumsum(members, axis=1)[:, -1]                 # (one after the other, in member order)
+            den = float(members.shape[1]) if code == 1 else float(np.sqrt(_sumsq(tot[:, None]))[0])
+            if den > 0.0:                                           # (cosine: a sum of norm 0 keeps the centre too)
+                Cm[:, j] = tot / den
+        return Cm
+
+    runs = []
+    for r in range(restarts):
+        if init is not None:
+            Cm = np.asfortranarray(init / np.sqrt(_sumsq(init)) if code == 0 else init.copy())
+        else:
+            Cm = np.asfortranarray(X[:, ids[gs_sample_host(seed, r, k, ids.size)]])
+        traj = np.full(max_iter + 1, np.nan)
+        label, second, d1, d2, traj[0], gap, s1, s2 = assign(Cm)
+        t, conv = 0, 0
+        while t < max_iter:
+            Cm = update(Cm, label)
+            new, second, d1, d2, J, g, s1, s2 = assign(Cm)
+            t += 1
+            traj[t], gap = J, min(gap, g)
+            same = np.array_equal(new, label)
+            label = new
+            if same:
+                conv = 1
+                break
+        runs.append(dict(centers=Cm, label=label, dist=d1, second=second, dist2=d2,
+                         sizes=np.bincount(label[label >= 0], minlength=k).astype(np.int32), traj=traj, iters=t, converged=conv,
+                         final=traj[t], min_gap=gap, score=s1, score2=s2))
+    final = np.array([q["final"] for q in runs])
+    best = int(np.argmin(final))                                    # (the first of equal minima: the lowest r)
+    rec = {name: runs[best][name] for name in ("centers", "label", "dist", "second", "dist2", "sizes", "traj", "min_gap", "score",
+                                               "score2")}
+    rec.update(final_inertia=final, iters=np.array([q["iters"] for q in runs], dtype=np.int32),
+               converged=np.array([q["converged"] for q in runs], dtype=np.int32), best=best,
+               ms=(time.perf_counter() - t_start) * 1e3)
+    return rec
+
+
+def gene_modules(column_factor, k, metric="cosine", init=None, restarts=8, max_iter=100, seed=0x1D5EED, device=0):
+    """Gene modules: api.kmeans() on the columns of C (K x p), genes with the same loading pattern share a module.  Under
+    cosine (the default) an all-zero column of C, which elastic-net fits do produce, is dead: label -1, in no module.  -> the
+    api.kmeans() record (label: p, 0-based modules)."""
+    from . import api
+    return api.kmeans(column_factor, k, metric=metric, init=init, restarts=restarts, max_iter=max_iter, seed=seed, device=device)
+
+
+def sample_clusters(cfd_factors, levels, ctns_confounder=None, k=8, metric="cosine", init=None, restarts=8, max_iter=100,
+                    seed=0x1D5EED, device=0):
+    """Sample clusters: api.kmeans() on sample_embeddings().  Samples that share every level (and, with a continuous block,
+    its values) are EQUAL points: they always fall into one cluster, and when two of them are drawn as starting centres the
+    tie rule leaves the higher-indexed centre empty (size 0).  -> the api.kmeans() record (label: n)."""
+    from . import api
+    return api.kmeans(sample_embeddings(cfd_factors, levels, ctns_confounder), k, metric=metric, init=init, restarts=restarts,
+                      max_iter=max_iter, seed=seed, device=device)
+
+
+def assign_to_centers(points, centers, metric="cosine", device=0):
+    """The points (D x N) assigned to given centres (D x k): the max_iter = 0 call of api.kmeans() (label, second, dist, dist2
+    and sizes against ``centers``, normalised under cosine)."""
+    from . import api
+    Cm = np.asarray(centers, dtype=np.float64)
+    if Cm.ndim != 2:
+        raise api.InsiderError(api._lib.ERR_ARG, "centers must be a D x k array")
+    return api.kmeans(points, int(Cm.shape[1]), metric=metric, init=Cm, restarts=1, max_iter=0, device=device)
+
+
+def module_overrepresentation(label, sets, k=None):
+    """Over-representation of gene sets in gene modules, on the host.  ``label``: a module per gene, -1 = dead (the record of
+    gene_modules()); ``sets``: (set_ptr, set_genes) or what flatio.read_gmt() returns.  The universe is the alive genes
+    (label >= 0), M of them; set s marks its alive genes (size[s]); module j draws its n_j genes.  -> dict(overlap (k x S
+    int32: the genes of set s in module j), hyper_p (k x S: the hypergeometric upper tail P(X >= overlap)), hyper_fdr
+    (Benjamini-Hochberg over the sets of each module), size (S), module_size (k), and names when the sets carry them)."""
+    lab = np.asarray(label).astype(np.int64).ravel()
+    ptr, genes = np.asarray(sets[-2], dtype=np.int64), np.asarray(sets[-1], dtype=np.int64)
+    S = ptr.size - 1
+    k = int(lab.max()) + 1 if k is None else int(k)
+    alive = lab >= 0
+    M = int(alive.sum())
+    module_size = np.bincount(lab[alive], minlength=k).astype(np.int32)
+    overlap, size = np.zeros((k, S), dtype=np.int32), np.zeros(S, dtype=np.int32)
+    for s in range(S):
+        g = lab[genes[ptr[s]:ptr[s + 1]]]
+        g = g[g >= 0]
+        size[s] = g.size
+        overlap[:, s] = np.bincount(g, minlength=k)
+    hyper = np.array([[_hyper_tail(int(overlap[j, s]), M, int(size[s]), int(module_size[j])) for s in range(S)]
+                      for j in range(k)], dtype=np.float64).reshape(k, S)
+    fdr = np.ones((k, S))
+    if S:
+        o = np.argsort(hyper, axis=1, kind="stable")
+        q = np.take_along_axis(hyper, o, axis=1) * S / np.arange(1, S + 1)
+        q = np.minimum(np.minimum.accumulate(q[:, ::-1], axis=1)[:, ::-1], 1.0)
+        np.put_along_axis(fdr, o, q, axis=1)
+    rec = dict(overlap=overlap, hyper_p=hyper, hyper_fdr=fdr, size=size, module_size=module_size)
+    if len(sets) == 3:
+        rec["names"] = list(sets[0])
+    return rec
+
+
+def module_summary(rec, column_factor):
+    """What the modules of a gene_modules() record look like: mean_abs_loading (k x K: per module the mean |loading| of its
+    genes on every factor, NaN for an empty module) and members (k arrays of 0-based genes by ascending dist, equal distances by
+    ascending gene: the most typical gene first)."""
+    Cm = np.abs(np.asarray(column_factor, dtype=np.float64))
+    lab, k = np.asarray(rec["label"]), int(np.asarray(rec["sizes"]).size)
+    mean_abs, members = np.full((k, Cm.shape[0]), np.nan), []
+    for j in range(k):
+        g = np.flatnonzero(lab == j)
+        members.append(g[np.argsort(np.asarray(rec["dist"])[g], kind="stable")])
+        if g.size:
+            mean_abs[j] = Cm[:, g].mean(axis=1)
+    return dict(mean_abs_loading=mean_abs, members=members)
