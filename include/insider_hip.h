@@ -174,6 +174,9 @@ int insider_hip_comm_init(insider_hip_handle *h, const void *unique_id, int rank
  * streaming pass of insider_hip_level_scores() is cut into, summed in slab order; 0, default = the rule of "sd_slabs" on that
  * pass's sample tiles, lowered until the slabs' partial scores [slabs x n x the levels padded to 16, doubles] stay within
  * ls_part_mb MB, default 256: a memory budget, not a tuned value; a count given explicitly is used as it is, at most 256 and at
+ * most p; another count gives the same sums in another order), "rc_slabs" (gene slabs the forward pass of
+ * insider_hip_residual_products() is cut into, summed in slab order; 0, default = the rule of "ls_slabs" with the partial Y
+ * [slabs x n x q padded to 16, doubles] kept within ls_part_mb MB; a count given explicitly is used as it is, at most 256 and at
  * most p; another count gives the same sums in another order), "glm_slabs" (gene slabs the streaming pass of
  * insider_hip_interaction_glm() is cut into, summed in slab order; 0, default = from n and the device's compute units, at most
  * 64; s >= 1 [at most 64] = slabs of cdiv(p, s) genes rounded up to whole staging rounds of k_resid_stats; another count gives
@@ -449,6 +452,36 @@ int insider_hip_factor_decomposition(insider_hip_handle *h, double *const *A, co
                                      int entries, double *out);
 
 /*
+ * The masked, standardised residual of a fitted model as an operator on a block of vectors: the two thin products of one step
+ * of a subspace iteration for the leading singular directions of R (structure shared across samples and genes that the model
+ * has left behind: an unmodelled batch, a hidden gradient, a missing interaction).  Blocks, u_b(i), f = sum_b g_b (in block
+ * order), x and the meaning of entries (0 all / 1 train bit / 2 test bit) are exactly those of
+ * insider_hip_variance_decomposition().  The working residual is
+ *   r_ij = (x_ij - f_ij - center_j) / scale_j on the selected entries, 0 elsewhere.
+ * center holds p doubles (NULL = 0), scale holds p doubles (NULL = 1); a gene whose scale is not finite or not > 0 is an
+ * all-zero column of R (not an error, as in insider_hip_outliers()).  The device multiplies by 1 / scale_j.
+ *   Q    n x q, column-major (leading dimension n), 1 <= q <= 64, every value finite.
+ *   Z    = R' Q,       p x q, column-major (leading dimension p).
+ *   Y    = R Z = R (R' Q), n x q, column-major (leading dimension n); may be NULL: the forward pass is then skipped and Z has
+ *        the same bits as with it.
+ *   rss  rss_j = sum_i r_ij^2, p doubles; may be NULL.
+ * Status codes: the checks of the post-hoc calls above (K 1..63: K > 63 returns INSIDER_ERR_UNSUPPORTED; the same
+ * inc_continuous rules; a sharded handle returns INSIDER_ERR_UNSUPPORTED); entries outside 0..2, a NULL Q or Z, q outside 1..64
+ * and a value of Q that is not finite return INSIDER_ERR_ARG.  Nothing is written to the caller's arrays unless the status is
+ * INSIDER_OK.  Works on clones and re-masked handles, on the handle's main stream, in the post-hoc workspace: an optimize()
+ * after it is bit-identical to one without.
+ * R is never stored.  Each product is one streaming pass over X and the mask codes on the f64 matrix instruction, the fit of a
+ * 16 x 16 tile from the same instruction (K deep: the cost does not depend on the number of blocks or levels).  Z: a block owns
+ * 64 genes and walks the samples in order, so a gene's sums have no partials.  Y: a grid of sample tiles x gene slabs, the
+ * slabs' partial Y summed in slab order.  Every sum runs in a fixed order without atomics: repeated calls with the same options
+ * on the same device return identical bits.  insider_hip_get_info("rc_slabs") tells the gene slabs of the last call's forward
+ * pass (0 = skipped; option "rc_slabs") and "rc_ms" the HIP-event time of its kernels in milliseconds.
+ */
+int insider_hip_residual_products(insider_hip_handle *h, double *const *A, const double *C, int inc_continuous, int K,
+                                  int entries, const double *center, const double *scale, const double *Q, int q,
+                                  double *Z, double *Y, double *rss);
+
+/*
  * Aberrant entries of a fitted model on the resident data set: the (sample, gene) entries whose standardised residual the
  * model cannot explain.  Blocks, g_b(i,j), f = sum_b g_b (in block order), r = x - f, x, the meaning of entries (0 all / 1 train
  * bit / 2 test bit) and S_j are exactly those of insider_hip_variance_decomposition().
@@ -621,6 +654,8 @@ int insider_hip_get_profile(insider_hip_handle *h, double *out12);
  * none yet),
  * "fd_path" (the form of the heavy pass of the last insider_hip_factor_decomposition(): 1 = one column window, X read once;
  * 2 = several windows of 128 columns of W, X read once per window; 0 = none yet),
+ * "rc_slabs" / "rc_ms" (of the last insider_hip_residual_products(): the gene slabs the grid of k_rc_fwd had, 0 = no forward
+ * pass or none yet; and the HIP-event time in milliseconds of k_rc_back, k_rc_fwd and k_rc_reduce),
  * "ol_path" (the form of k_ol_flag the last insider_hip_outliers() ran: 1 = level tables in LDS, 2 = read from global memory;
  * 0 = none yet),
  * "row_kernels" (a bit mask of the row-phase kernel forms the last optimize() / optimize_row() launched, reset at the start of

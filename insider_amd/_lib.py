@@ -31,7 +31,7 @@ SYMBOLS = (
     "insider_hip_remask", "insider_hip_set_folds", "insider_hip_remask_fold", "insider_hip_factor_decomposition",
     "insider_hip_outliers", "insider_hip_neighbors", "insider_hip_last_neighbors_ms", "insider_hip_level_scores",
     "insider_hip_enrichment", "insider_hip_last_enrichment_ms", "insider_hip_enrichment_sample",
-    "insider_hip_kmeans", "insider_hip_last_kmeans_ms",
+    "insider_hip_kmeans", "insider_hip_last_kmeans_ms", "insider_hip_residual_products",
 )
 COMM_ID_BYTES = 128
 # insider_hip_outliers (insider_amd/csrc/insider_outliers.hpp): the samples a block of k_ol_flag covers per trip (OL_TRIP) and the
@@ -139,6 +139,8 @@ def load():
     lib.insider_hip_level_scores.argtypes = [C.c_void_p, C.POINTER(dp), dp, C.c_int, C.c_int, C.c_int, C.c_int, dp, C.c_int, dp,
                                              dp]
     lib.insider_hip_factor_decomposition.argtypes = [C.c_void_p, C.POINTER(dp), dp, C.c_int, C.c_int, C.c_int, dp]
+    lib.insider_hip_residual_products.argtypes = [C.c_void_p, C.POINTER(dp), dp, C.c_int, C.c_int, C.c_int, dp, dp, dp, C.c_int, dp,
+                                                  dp, dp]
     lib.insider_hip_outliers.argtypes = [C.c_void_p, C.POINTER(dp), dp, C.c_int, C.c_int, C.c_int, dp, dp, C.c_double, C.c_int64,
                                          i32p, i32p, dp, C.POINTER(C.c_int64), i32p, i32p]
     lib.insider_hip_neighbors.argtypes = [dp, C.c_int64, dp, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, i32p, dp]

@@ -372,6 +372,44 @@ class InsiderData:
                     sum_h=blk[..., 0].transpose(1, 2, 0).copy(), sum_hh=blk[..., 1].transpose(1, 2, 0).copy(),
                     sum_rh=blk[..., 2].transpose(1, 2, 0).copy())
 
+    def residual_products(self, cfd_factors, column_factor, Q, entries="train", center=None, scale=None, inc_continuous=0,
+                          want_y=True):
+        """The masked, standardised residual of a fitted model applied to a block of vectors
+        (insider_hip_residual_products): with r = (x - f - center[j]) / scale[j] on the entries ``entries`` and 0 elsewhere
+        (``center`` None = 0, ``scale`` None = 1, each of length p; a gene whose scale is not finite or not > 0 is an all-zero
+        column) and ``Q`` n x q (q in 1..64, finite), a dict of ``Z`` = R'Q (p x q), ``Y`` = R Z (n x q; None with
+        ``want_y`` False: the forward pass is skipped) and ``rss`` (p, each gene's sum of r^2).  R never exists: each product is
+        one streaming pass over the resident X.  posthoc.residual_components() iterates it to the leading singular directions
+        of R."""
+        if entries not in self.VD_ENTRIES:
+            raise InsiderError(_lib.ERR_ARG, f"entries must be one of {sorted(self.VD_ENTRIES)}, got {entries!r}")
+        if inc_continuous not in (0, 1):
+            raise InsiderError(_lib.ERR_ARG, "The value of prarameter inc_continuous can only be 0 or 1.")
+        Qm = np.asarray(Q, dtype=np.float64)
+        if Qm.ndim == 1:
+            Qm = Qm.reshape(-1, 1)
+        if Qm.ndim != 2 or Qm.shape[0] != self.n or not 1 <= Qm.shape[1] <= 64:
+            raise InsiderError(_lib.ERR_ARG, f"Q must be n x q with n = {self.n} and q in 1..64")
+        if not np.all(np.isfinite(Qm)):
+            raise InsiderError(_lib.ERR_ARG, "Q holds a value that is not finite")
+        Qm = _lib.f64(Qm)
+        q = Qm.shape[1]
+        K = int(np.asarray(column_factor).shape[0])
+        A, Cw, Aptrs = self._marshal(cfd_factors, column_factor, K, inc_continuous)
+        ce = None if center is None else np.ascontiguousarray(np.asarray(center, dtype=np.float64).ravel())
+        sc = None if scale is None else np.ascontiguousarray(np.asarray(scale, dtype=np.float64).ravel())
+        if (ce is not None and ce.shape != (self.p,)) or (sc is not None and sc.shape != (self.p,)):
+            raise InsiderError(_lib.ERR_ARG, f"center and scale must hold p = {self.p} values")
+        Z = np.empty((self.p, q), dtype=np.float64, order="F")
+        Y = np.empty((self.n, q), dtype=np.float64, order="F") if want_y else None
+        rss = np.empty(self.p, dtype=np.float64)
+        _lib.check(_lib.load().insider_hip_residual_products(self._h, Aptrs, _lib.ptr(Cw), int(inc_continuous), K,
+                                                             self.VD_ENTRIES[entries],
+                                                             None if ce is None else _lib.ptr(ce),
+                                                             None if sc is None else _lib.ptr(sc), _lib.ptr(Qm), q,
+                                                             _lib.ptr(Z), None if Y is None else _lib.ptr(Y), _lib.ptr(rss)))
+        return dict(Z=Z, Y=Y, rss=rss)
+
     def outliers(self, cfd_factors, column_factor, scale, center=None, threshold=3.0, entries="train", inc_continuous=0,
                  cap=None):
         """The aberrant entries of a fitted model (insider_hip_outliers): the entries ``entries`` whose standardised residual

@@ -11,6 +11,7 @@
 #include "insider_sampdecomp.hpp"
 #include "insider_levelscores.hpp"
 #include "insider_factdecomp.hpp"
+#include "insider_rescomp.hpp"
 #include "insider_outliers.hpp"
 #include "insider_neighbors.hpp"
 #include "insider_enrich.hpp"
@@ -395,6 +396,7 @@ struct Options {
     int ls_slabs = 0;                 // "ls_slabs": gene slabs of k_ls_prod (0 = automatic; at most 256)
     double ls_part_mb = 256.0;        // "ls_part_mb": bound (MB) on the slabs' partial scores of the automatic slab count
     int glm_slabs = 0;                // "glm_slabs": gene slabs of k_resid_stats (0 = automatic; at most 64)
+    int rc_slabs = 0;                 // "rc_slabs": gene slabs of k_rc_fwd (0 = automatic; at most 256)
 };
 
 // device workspace of the post-hoc calls (section "post-hoc interaction GLM"): grown on demand, freed with the handle
@@ -416,6 +418,10 @@ struct PostWs {
     // factor decomposition: fwall = [W | W .* W] (padded rows x 2 ldq); fprod = the p rows [P1 | P2 | P3]; fbase = the p base
     // slots; frec = the p records
     DevBuf<double> fwall, fprod, fbase, frec;
+    // residual products: rq = Q (n rows of ldq); rcs = the p pairs (centre, inverse scale); rz = Z (p rows of ldq); rpart = the
+    // slabs' partial Y (slabs x n x ldq); rin = the caller's Q, centre and scale as they came; rout = Z (p x q column-major),
+    // Y (n x q column-major), rss (p)
+    DevBuf<double> rq, rcs, rz, rpart, rin, rout;
     // outlier calls: ocs = center (p; unused without one) then scale (p); obits = the bitmap of flagged entries (p x ldn / 32
     // words); ogcnt / oscnt = the p / n pairs {low, high}; ooffs = the p + 1 list offsets; orows / ocols / oz = the list
     DevBuf<double> ocs, oz;
@@ -472,6 +478,9 @@ struct insider_hip_handle {
     // of the last interaction GLM: the gene slabs of k_resid_stats and its form, 10 NB + GT
     int glm_slabs = 0, glm_form = 0;
     int fd_path = 0;
+    // of the last residual products: the gene slabs of k_rc_fwd (0: no forward pass) and the HIP-event time of its kernels
+    int rc_slabs = 0;
+    double rc_ms = 0.0;
     // the form the flag pass of the last outlier call ran (1 = tables in LDS, 2 = from global)
     int ol_path = 0;
 
@@ -2625,6 +2634,7 @@ int insider_hip_set_option(insider_hip_handle *h, const char *name, double value
     else if (s == "resid_stage_mb") h->opt.resid_stage_mb = value;   // device buffer insider_hip_residual() copies out through (MB; at least 16 genes of the window)
     else if (s == "vd_stage_kb") h->opt.vd_stage_kb = value;         // LDS budget (KiB, default 48, at most 60) of the staged level tables of k_vd_stats (0 = always the global form)
     else if (s == "ls_slabs") h->opt.ls_slabs = value < 1 ? 0 : (int)std::min(value, 256.0);   // gene slabs of k_ls_prod (0 = from n, p, the compute units and "ls_part_mb"; at most 256)
+    else if (s == "rc_slabs") h->opt.rc_slabs = value < 1 ? 0 : (int)std::min(value, 256.0);   // gene slabs of k_rc_fwd (0 = from n, p, the compute units and "ls_part_mb"; at most 256)
     else if (s == "ls_part_mb") h->opt.ls_part_mb = value;          // bound (MB, default 256) on the partial scores of the automatic slab count of k_ls_prod
     else if (s == "glm_slabs") h->opt.glm_slabs = value < 1 ? 0 : (int)std::min(value, 64.0);   // gene slabs of k_resid_stats (0 = from n and the compute units; at most 64)
     else if (s == "sd_slabs") h->opt.sd_slabs = value < 1 ? 0 : (int)std::min(value, 256.0);   // gene slabs of k_sd_stats (0 = from n, p and the compute units; at most 256)
@@ -3687,6 +3697,8 @@ int insider_hip_get_info(insider_hip_handle *h, const char *name, double *out)
     else if (s == "sd_slabs") *out = h->sd_slabs;                   // ... and its gene slabs
     else if (s == "glm_slabs") *out = h->glm_slabs;                 // gene slabs of the last interaction GLM's k_resid_stats
     else if (s == "glm_form") *out = h->glm_form;                   // ... and its form, 10 NB + GT (18, 24, 32, 42)
+    else if (s == "rc_slabs") *out = h->rc_slabs;                   // last residual products: the gene slabs of k_rc_fwd (0 = no forward pass)
+    else if (s == "rc_ms") *out = h->rc_ms;                         // ... and the HIP-event time of its kernels (k_rc_back, k_rc_fwd, k_rc_reduce)
     else if (s == "fd_path") *out = h->fd_path;                     // last factor decomposition: 1 = one column window (X read once), 2 = several
     else if (s == "col_mfma_per_gene") {
         // v_mfma_f64_16x16x4_f64 instructions the column-side statistics kernel issues per gene (2048 flops each; the 4x4x4 form
@@ -4307,6 +4319,112 @@ int factor_decomposition_body(insider_hip_handle *h, double *const *A, const dou
     return INSIDER_OK;
 }
 
+// ---- residual products (kernels: insider_rescomp.hpp) ----------------------------------------------------------------
+// U and C in the kernels' layout (ph_prepare with every block), Q packed to rows of ldq, the pairs (centre, inverse scale),
+// then k_rc_back (Z = R' Q and rss: one streaming pass over X and the codes, a block per 64 genes) and, when Y is wanted,
+// k_rc_fwd on a grid of sample tiles x gene slabs and k_rc_reduce (the slabs' partial Y summed in slab order).  Nothing is
+// written to the caller's arrays before every check passed and the kernels ran.
+int residual_products_body(insider_hip_handle *h, double *const *A, const double *C, int inc_continuous, int K, int entries,
+                           const double *center, const double *scale, const double *Q, int q, double *Z, double *Y,
+                           double *rss)
+{
+    if (!h) return fail(INSIDER_ERR_ARG, "null handle");
+    const std::vector<int32_t> every((size_t)h->ds->c + 2, 1);   // every block enters the fit
+    int rc = ph_check(h, A, C, inc_continuous, K, every.data());
+    if (rc) return rc;
+    if (entries < 0 || entries > 2) return fail(INSIDER_ERR_ARG, "entries must be 0 (all), 1 (train) or 2 (test)");
+    if (!Q || !Z) return fail(INSIDER_ERR_ARG, "null Q or Z");
+    if (q < 1 || q > 64) return fail(INSIDER_ERR_ARG, "q must be in 1..64");
+    const DataSet &d = *h->ds;
+    const int64_t n = d.n, p = d.p;
+    for (int64_t e = 0; e < n * q; ++e)
+        if (!std::isfinite(Q[e])) return fail(INSIDER_ERR_ARG, "Q holds a value that is not finite");
+    HIPCHECK(hipSetDevice(d.device));
+    PostWs &w = h->post;
+    hipStream_t st = h->st.stream;
+    const int KS = (K + 15) / 16, KPW = 16 * KS;
+    if ((rc = ph_prepare(h, A, C, K, every.data(), KPW))) return rc;
+    const int QT = (q + 15) / 16, ldq = 16 * QT;
+    // gene slabs of the forward pass: the rule of "ls_slabs" (eight blocks per compute unit, at most 256) and, when automatic, no
+    // more than keep the partial Y within "ls_part_mb"
+    const int tiles = cdiv(n, RC_TILE);
+    int want = h->opt.rc_slabs;
+    if (want <= 0) {
+        const double cap = std::max(h->opt.ls_part_mb, 0.0) * 1048576.0 / ((double)n * ldq * sizeof(double));
+        want = (int)std::min<double>(cdiv(2 * d.n_simd, tiles), std::max(cap, 1.0));
+    }
+    const int64_t slab_len = cdiv(p, (int64_t)std::max(1, std::min(want, 256)));
+    const int slabs = Y ? (int)cdiv(p, slab_len) : 0;
+    const size_t n_in = (size_t)n * q + 2 * (size_t)p, n_out = (size_t)p * q + (size_t)n * q + (size_t)p;
+    if ((rc = w.rin.grow(n_in)) || (rc = w.rq.grow((size_t)n * ldq)) || (rc = w.rcs.grow((size_t)2 * p)) ||
+        (rc = w.rz.grow((size_t)p * ldq)) || (rc = w.rpart.grow((size_t)std::max(slabs, 1) * n * ldq)) ||
+        (rc = w.rout.grow(n_out)))
+        return rc;
+    double *q_in = w.rin, *c_in = q_in + (size_t)n * q, *s_in = c_in + p;
+    double *Qd = w.rq, *cs = w.rcs, *Zd = w.rz, *part = w.rpart;
+    double *z_out = w.rout, *y_out = z_out + (size_t)p * q, *r_out = y_out + (size_t)n * q;
+    const double *U = w.U, *cp = w.cp;
+    HIPCHECK(hipMemcpyAsync(q_in, Q, (size_t)n * q * sizeof(double), hipMemcpyHostToDevice, st));
+    if (center) HIPCHECK(hipMemcpyAsync(c_in, center, (size_t)p * sizeof(double), hipMemcpyHostToDevice, st));
+    if (scale) HIPCHECK(hipMemcpyAsync(s_in, scale, (size_t)p * sizeof(double), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_rc_pack_q, dim3(cdiv(n * ldq, 256)), dim3(256), 0, st, (const double *)q_in, n, q, ldq, Qd);
+    KCHECK();
+    hipLaunchKernelGGL(k_rc_center_scale, dim3(cdiv(p, 256)), dim3(256), 0, st, (const double *)(center ? c_in : nullptr),
+                       (const double *)(scale ? s_in : nullptr), p, cs);
+    KCHECK();
+    const int sel = entries == 0 ? 0 : entries == 1 ? CODE_TRAIN : CODE_TEST;
+    Event e0, e1;
+    HIPCHECK(hipEventCreate(e0.out()));
+    HIPCHECK(hipEventCreate(e1.out()));
+    HIPCHECK(hipEventRecord(e0, st));
+#define RC_LAUNCH(QT_, KS_)                                                                                                 \
+    do {                                                                                                                     \
+        hipLaunchKernelGGL((k_rc_back<QT_, KS_>), dim3((unsigned)cdiv(p, (int64_t)RC_GENES)), dim3(64 * RC_WAVES),           \
+                           rc_back_lds(QT_, KS_), st, (const double *)d.X, (const uint8_t *)d.codes, d.ldn, (int)n, p, U, cp, \
+                           K, (const double *)Qd, (const double *)cs, sel, Zd, r_out);                                       \
+        KCHECK();                                                                                                            \
+        if (Y) {                                                                                                             \
+            hipLaunchKernelGGL((k_rc_fwd<QT_, KS_>), dim3(tiles, slabs), dim3(64 * RC_WAVES), rc_fwd_lds(QT_, KS_), st,      \
+                               (const double *)d.X, (const uint8_t *)d.codes, d.ldn, (int)n, p, U, cp, K, (const double *)Zd, \
+                               (const double *)cs, sel, slab_len, part);                                                     \
+            KCHECK();                                                                                                        \
+        }                                                                                                                    \
+    } while (0)
+#define RC_LAUNCH_KS(QT_)                                                                                                   \
+    switch (KS) {                                                                                                            \
+        case 1: RC_LAUNCH(QT_, 1); break;                                                                                    \
+        case 2: RC_LAUNCH(QT_, 2); break;                                                                                    \
+        case 3: RC_LAUNCH(QT_, 3); break;                                                                                    \
+        default: RC_LAUNCH(QT_, 4); break;                                                                                   \
+    }
+    // one form per number of column tiles of Q and of K: registers per form in DESIGN (tools/kernel_regs.sh), no scratch
+    switch (QT) {
+        case 1: RC_LAUNCH_KS(1) break;
+        case 2: RC_LAUNCH_KS(2) break;
+        case 3: RC_LAUNCH_KS(3) break;
+        default: RC_LAUNCH_KS(4) break;
+    }
+#undef RC_LAUNCH_KS
+#undef RC_LAUNCH
+    if (Y) {
+        hipLaunchKernelGGL(k_rc_reduce, dim3(cdiv(n * ldq, 256)), dim3(256), 0, st, (const double *)part, slabs, n, ldq, q, y_out);
+        KCHECK();
+    }
+    HIPCHECK(hipEventRecord(e1, st));
+    hipLaunchKernelGGL(k_rc_unpack, dim3(cdiv(p * q, 256)), dim3(256), 0, st, (const double *)Zd, p, q, ldq, z_out);
+    KCHECK();
+    HIPCHECK(hipStreamSynchronize(st));   // the caller's arrays are written only after the kernels ran
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, e0, e1);
+    h->rc_ms = ms;
+    h->rc_slabs = slabs;
+    HIPCHECK(hipMemcpyAsync(Z, z_out, (size_t)p * q * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (Y) HIPCHECK(hipMemcpyAsync(Y, y_out, (size_t)n * q * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (rss) HIPCHECK(hipMemcpyAsync(rss, r_out, (size_t)p * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipStreamSynchronize(st));
+    return INSIDER_OK;
+}
+
 // ---- outlier calls (kernels: insider_outliers.hpp) -------------------------------------------------------------------
 // the level table, the flag pass over X and the codes (bitmap + per-gene counts), the scan of the genes' totals, and the fill
 // pass over the bitmap (the list + per-sample counts).  Nothing is written to the caller's arrays before every check passed.
@@ -4422,6 +4540,13 @@ int insider_hip_factor_decomposition(insider_hip_handle *h, double *const *A, co
                                      int entries, double *out)
 {
     return ph_finish(h, factor_decomposition_body(h, A, C, inc_continuous, K, entries, out));
+}
+
+int insider_hip_residual_products(insider_hip_handle *h, double *const *A, const double *C, int inc_continuous, int K,
+                                  int entries, const double *center, const double *scale, const double *Q, int q, double *Z,
+                                  double *Y, double *rss)
+{
+    return ph_finish(h, residual_products_body(h, A, C, inc_continuous, K, entries, center, scale, Q, q, Z, Y, rss));
 }
 
 int insider_hip_outliers(insider_hip_handle *h, double *const *A, const double *C, int inc_continuous, int K,

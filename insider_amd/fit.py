@@ -13,6 +13,7 @@
     ... --gene-neighbors 10 --sample-neighbors 10 [--neighbor-metric cosine]   # then each gene's / sample's nearest in latent space
     ... --gene-modules 20 --sample-clusters 6 [--cluster-metric cosine]        # then k-means of the genes / samples in latent space
     ... --level-scores 1 [--level-score-entries train]   # then every sample against every level of covariate column 1 (1-based)
+    ... --residual-components 5 [--rc-standardize] [--rc-entries train]   # then the hidden factors: what the model left behind
     ... --gene-sets SETS.gmt [--gene-names NAMES.txt] [--enrich-perms 1000] [--enrich-levels 1]   # then what each factor means
 
 Semantics are those of insider_amd.api (the mirror of R/insider.R): with masks given, `--partition 1` fits on the
@@ -40,7 +41,12 @@ km_gene_size (k), km_gene_traj (the inertia before every update, NaN beyond the 
 --level-scores COV adds, for covariate column COV (1-based), ls_sse (n x L: the residual sum of squares of every
 sample over the --level-score-entries with its embedding for COV replaced by each level's), ls_n, ls_best (1-based, 0 = no
 entry), ls_margin (n) and ls_confusion (L x L, assigned x best; posthoc.ls_derived) — a sample's own level was fitted with that
-sample, so on the entries the fit used the assigned level is favoured, most for levels with few samples; --gene-sets FILE (GMT;
+sample, so on the entries the fit used the assigned level is favoured, most for levels with few samples;
+--residual-components R adds the R leading singular directions of the masked residual over the --rc-entries
+(posthoc.residual_components: a subspace iteration whose products stream over the resident X; --rc-standardize centres and
+scales every gene's residual first): rc_sv, rc_share (R), rc_sample_scores (n x R), rc_gene_loadings (p x R) and rc_assoc
+(blocks x R: eta-squared of every component on every categorical covariate, R-squared on the continuous block;
+posthoc.component_associations); --gene-sets FILE (GMT;
 tokens are the lines of --gene-names, else 0-based gene columns; sets outside --enrich-min-size..--enrich-max-size are dropped)
 adds the preranked gene-set enrichment of every factor's |loadings| against every set with --enrich-perms random sets of equal
 size as the null (posthoc.factor_enrichment): gs_factor_es / gs_factor_nes / gs_factor_pval / gs_factor_fdr / gs_factor_peak
@@ -116,6 +122,15 @@ def parse(argv=None):
                          "that sample: on the entries the fit used the assigned level is favoured")
     ap.add_argument("--level-score-entries", choices=("all", "train", "test"), default="train",
                     help="--level-scores: the entries that are scored (default: train, the entries the fit used)")
+    ap.add_argument("--residual-components", type=int, default=None, metavar="R",
+                    help="after the fit, the R leading singular directions of the masked residual (hidden factors: an "
+                         "unmodelled batch, a missing interaction), on the device; writes rc_sv, rc_share (R), rc_sample_scores "
+                         "(n x R), rc_gene_loadings (p x R) and rc_assoc (blocks x R: how much of each component every known "
+                         "covariate explains) next to the factors")
+    ap.add_argument("--rc-standardize", action="store_true",
+                    help="--residual-components: centre and scale every gene's residual first")
+    ap.add_argument("--rc-entries", choices=("all", "train", "test"), default="train",
+                    help="--residual-components: the entries of the residual (default: train, the entries the fit used)")
     ap.add_argument("--gene-neighbors", type=int, default=None, metavar="N",
                     help="after the fit, every gene's N nearest genes in the latent space (columns of C), on the device; "
                          "writes nn_gene_index, nn_gene_score (p x N; 0-based, open slots -1 / NaN) next to the factors")
@@ -192,6 +207,13 @@ def parse(argv=None):
         ap.error("a fit needs --rank, --lambda and --alpha (or use --tune)")
     if a.tune and a.level_scores is not None:
         ap.error("--level-scores scores a fit: it does not go with --tune")
+    if a.residual_components is None and a.rc_standardize:
+        ap.error("--rc-standardize goes with --residual-components")
+    if a.residual_components is not None:
+        if a.tune:
+            ap.error("--residual-components reads a fit: it does not go with --tune")
+        if not 1 <= a.residual_components <= 64:
+            ap.error("--residual-components must be in 1..64")
     if a.folds is not None and not a.tune:
         ap.error("--folds goes with --tune")
     if a.folds is not None and a.warm_start:
@@ -335,6 +357,13 @@ def main(argv=None):
                         ds_levels[:, cov])
         vd = dict(vd or {}, ls_sse=ls["sse"], ls_n=ls["n"], ls_best=ls["best"].astype(np.float64), ls_margin=ls["margin"],
                   ls_confusion=ls["confusion"].astype(np.float64))
+    if a.residual_components is not None:
+        from .posthoc import component_associations, residual_components_resident
+        rcs = residual_components_resident(ds, list(res["row_matrices"].values()), res["column_factor"],
+                                           1 if Z is not None else 0, r=a.residual_components, entries=a.rc_entries,
+                                           standardize=a.rc_standardize, seed=a.seed)
+        vd = dict(vd or {}, rc_sv=rcs["sv"], rc_share=rcs["share"], rc_sample_scores=rcs["sample_scores"],
+                  rc_gene_loadings=rcs["gene_loadings"], rc_assoc=component_associations(rcs["sample_scores"], ds_levels, Z))
     if a.gene_neighbors is not None:
         from .posthoc import gene_neighbors
         nn = gene_neighbors(res["column_factor"], k=a.gene_neighbors, metric=a.neighbor_metric, device=a.device)

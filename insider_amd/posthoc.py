@@ -31,6 +31,12 @@ level_scores() asks whether each sample's label of a covariate is right: every s
 (InsiderData.level_scores: the candidate table cand C, then one streaming pass over X as two masked products over the genes),
 with level_scores_host() as its yardstick and ls_derived() for best / second / margin / flagged / confusion.
 
+residual_components() asks what the model has left behind across samples and genes at once: the leading singular directions
+of the masked (optionally standardised) residual, by a block subspace iteration whose two thin products per step run on the
+device (InsiderData.residual_products: R never exists), with residual_products_host() / residual_components_host() as the
+yardsticks (the same driver on the numpy operator) and component_associations() to tell a component tied to a known
+covariate (misfit, a missing interaction) from one tied to none (an unknown factor).
+
 gene_neighbors() / sample_neighbors() ask the latent representations themselves which genes lie next to a gene and which
 samples next to a sample (api.neighbors: a K-deep product on the device with the top-k selection fused behind it, the
 similarity matrix never exists), on column_factor and on sample_embeddings(); neighbors_host() is the yardstick.
@@ -431,6 +437,193 @@ def outliers(obj, which="fit", entries="train", threshold=3.0, center=None, scal
                       inc_continuous=inc, cap=cap)
     out["center"], out["scale"] = np.asarray(center, dtype=np.float64), np.asarray(scale, dtype=np.float64)
     return out
+
+
+# ---- hidden factors: the leading components of the masked residual ------------------------------------------------------------
+def residual_products_host(X, levels, ctns, mask, A, C, Q, center=None, scale=None):
+    """The residual products in plain numpy (the yardstick of InsiderData.residual_products); X, levels, ctns, mask, A, C as
+    in variance_decomposition_host(), ``Q`` n x q, ``center`` (None = 0) and ``scale`` (None = 1) of length p.  The direct
+    form: r = ((x - f) - center[j]) / scale[j] on the entries that count and 0 elsewhere, f the sum of the blocks in block
+    order; a gene whose scale is not finite or not > 0 is an all-zero column.  -> dict(Z = r'Q (p x q), Y = r Z (n x q),
+    rss (p))."""
+    X = np.asarray(X, dtype=np.float64)
+    if X.ndim != 2:
+        raise ValueError("X must be an n x p matrix")
+    n, p = X.shape
+    Qm = np.asarray(Q, dtype=np.float64)
+    if Qm.ndim == 1:
+        Qm = Qm.reshape(-1, 1)
+    if Qm.ndim != 2 or Qm.shape[0] != n or not 1 <= Qm.shape[1] <= 64:
+        raise ValueError(f"Q must be n x q with n = {n} and q in 1..64")
+    if not np.all(np.isfinite(Qm)):
+        raise ValueError("Q holds a value that is not finite")
+    sc = np.ones(p) if scale is None else np.asarray(scale, dtype=np.float64).ravel()
+    ce = np.zeros(p) if center is None else np.asarray(center, dtype=np.float64).ravel()
+    if sc.shape != (p,) or ce.shape != (p,):
+        raise ValueError(f"center and scale must hold p = {p} values")
+    Cm = np.asarray(C, dtype=np.float64)
+    lev = np.asarray(levels).reshape(n, -1)
+    c = lev.shape[1]
+    f = np.zeros_like(X)
+    for b in range(c):
+        f = f + np.asarray(A[b], dtype=np.float64)[lev[:, b].astype(np.int64) - 1] @ Cm
+    if ctns is not None:
+        f = f + np.asarray(ctns, dtype=np.float64).reshape(n, -1) @ (np.asarray(A[c], dtype=np.float64) @ Cm)
+    usable = np.isfinite(sc) & (sc > 0)
+    w = np.ones(X.shape, dtype=bool) if mask is None else np.asarray(mask).astype(bool)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        r = np.where(w & usable[None, :], ((X - f) - ce) / sc, 0.0)
+    Z = r.T @ Qm
+    return dict(Z=Z, Y=r @ Z, rss=(r * r).sum(axis=0))
+
+
+def _rc_check(r, oversample, max_iter, tol, seed):
+    for name, v, low in (("r", r, 1), ("oversample", oversample, 0), ("max_iter", max_iter, 1)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < low:
+            raise ValueError(f"{name} must be an integer >= {low}, got {v!r}")
+    if r > 64:
+        raise ValueError("r must be at most 64 (the block of one operator application)")
+    if not (isinstance(tol, (int, float, np.floating)) and np.isfinite(tol) and tol > 0):
+        raise ValueError(f"tol must be finite and > 0, got {tol!r}")
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or seed < 0:
+        raise ValueError(f"seed must be a non-negative integer, got {seed!r}")
+
+
+def component_signs(U):
+    """The sign convention of the components: +1 / -1 per column of U so that, multiplied by it, the column's entry of largest
+    magnitude is positive (equal magnitudes: the entry of lowest index decides)."""
+    U = np.asarray(U, dtype=np.float64)
+    lead = np.argmax(np.abs(U), axis=0)                               # (the first of equal magnitudes: the lowest index)
+    return np.where(U[lead, np.arange(U.shape[1])] < 0, -1.0, 1.0)
+
+
+def residual_components_driver(apply, n, r=5, oversample=8, max_iter=30, tol=1e-10, seed=0x1D5EED):
+    """The block subspace iteration behind residual_components() and residual_components_host(), written once against the
+    operator ``apply(Q) -> dict(Z = R'Q, Y = R Z, rss)``.  Block size q = min(r + oversample, 64, n) (r itself is clamped to
+    q); Q0 = qr(gaussian(n, q)) from numpy.random.default_rng(seed); each pass applies the operator, takes svd(Z') = W S V'
+    — with Q orthonormal, R ~ Q Q'R = (Q W) S V' — and sets U = Q W, sv, V, then Q <- qr(Y).  It stops when the largest
+    relative change of the top-r singular values between two passes is below ``tol`` (converged), or after ``max_iter``
+    passes.  Sign: each component's entry of U with the largest magnitude is positive (ties: the lowest index).
+    -> dict(sv (r), sample_scores = U sv (n x r), gene_loadings = V (p x r), share = sv^2 / sum(rss), iters, converged,
+    last_change (inf after a single pass))."""
+    _rc_check(r, oversample, max_iter, tol, seed)
+    n = int(n)
+    q = max(1, min(int(r) + int(oversample), 64, n))
+    r = min(int(r), q)
+    rng = np.random.default_rng(seed)
+    Q = np.linalg.qr(rng.standard_normal((n, q)))[0]
+    prev, change, converged, iters = None, np.inf, False, 0
+    while iters < max_iter:
+        out = apply(np.asfortranarray(Q))
+        iters += 1
+        Z = np.asarray(out["Z"], dtype=np.float64)
+        W, sv, Vt = np.linalg.svd(Z.T, full_matrices=False)
+        if prev is not None:
+            top = sv[:r]
+            with np.errstate(divide="ignore", invalid="ignore"):
+                rel = np.where(top > 0, np.abs(top - prev[:r]) / top, np.where(prev[:r] > 0, np.inf, 0.0))
+            change = float(rel.max())
+            if change < tol:
+                converged = True
+                break
+        prev = sv
+        if iters < max_iter:
+            Q = np.linalg.qr(np.asarray(out["Y"], dtype=np.float64))[0]
+    U, V = (Q @ W)[:, :r], Vt[:r].T
+    sign = component_signs(U)
+    U, V = U * sign, V * sign
+    total = float(np.sum(out["rss"]))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        share = sv[:r] ** 2 / total
+    return dict(sv=sv[:r].copy(), sample_scores=U * sv[:r], gene_loadings=V, share=share, iters=iters, converged=converged,
+                last_change=change)
+
+
+def residual_components_host(X, levels, ctns, mask, A, C, r=5, standardize=False, oversample=8, max_iter=30, tol=1e-10,
+                             seed=0x1D5EED):
+    """residual_components() in plain numpy (the yardstick of the device path): residual_components_driver() on
+    residual_products_host(); X, levels, ctns, mask, A, C as in variance_decomposition_host().  standardize=True takes each
+    gene's centre and scale from residual_center_scale() of the host variance decomposition under the same mask."""
+    _rc_check(r, oversample, max_iter, tol, seed)
+    X = np.asarray(X, dtype=np.float64)
+    if X.ndim != 2:
+        raise ValueError("X must be an n x p matrix")
+    center = scale = None
+    if standardize:
+        center, scale = residual_center_scale(_decomposition_host(X, levels, ctns, mask, A, C, 0))
+    return residual_components_driver(lambda Q: residual_products_host(X, levels, ctns, mask, A, C, Q, center, scale),
+                                      X.shape[0], r, oversample, max_iter, tol, seed)
+
+
+def residual_components_resident(ds, cfd_factors, column_factor, inc_continuous=0, r=5, entries="train", standardize=False,
+                                 oversample=8, max_iter=30, tol=1e-10, seed=0x1D5EED):
+    """residual_components() on a resident data set and explicit factors (the command line's entry):
+    residual_components_driver() on InsiderData.residual_products."""
+    _rc_check(r, oversample, max_iter, tol, seed)
+    if entries not in ds.VD_ENTRIES:
+        raise ValueError(f"entries must be one of {sorted(ds.VD_ENTRIES)}, got {entries!r}")
+    center = scale = None
+    if standardize:
+        center, scale = residual_center_scale(ds.variance_decomposition(cfd_factors, column_factor, entries=entries,
+                                                                        inc_continuous=inc_continuous))
+    return residual_components_driver(
+        lambda Q: ds.residual_products(cfd_factors, column_factor, Q, entries=entries, center=center, scale=scale,
+                                       inc_continuous=inc_continuous), ds.n, r, oversample, max_iter, tol, seed)
+
+
+def residual_components(obj, r=5, which="fit", entries="train", standardize=False, oversample=8, max_iter=30, tol=1e-10,
+                        seed=0x1D5EED):
+    """The hidden factors of a fitted ``Insider`` object: the r leading singular directions of its masked residual
+    R = M .* (X - fit) on the device, with the ``which`` / ``entries`` of variance_decomposition().  standardize=True centres
+    and scales every gene's residual first (residual_center_scale() of a variance decomposition on the same entries), so
+    that a few high-variance genes do not own the leading components.  A block subspace iteration
+    (residual_components_driver) whose two thin products per step, R'Q and R Z, are streaming passes over the resident X:
+    the residual never exists, on the device or the host.  -> dict(sv, sample_scores (n x r), gene_loadings (p x r), share
+    (of the residual sum of squares), iters, converged, last_change); component_associations() relates the scores to the
+    known covariates."""
+    _rc_check(r, oversample, max_iter, tol, seed)
+    if entries not in ("all", "train", "test"):
+        raise ValueError(f"entries must be one of ['all', 'test', 'train'], got {entries!r}")
+    from . import api
+    ds = api._resident(obj, which)
+    return residual_components_resident(ds, list(obj["cfd_matrices"].values()), obj["column_factor"],
+                                        int(obj["inc_continuous"]), r, entries, standardize, oversample, max_iter, tol, seed)
+
+
+def component_associations(sample_scores, levels, ctns=None):
+    """How much of every component the known covariates explain, on the host: row b < c holds eta-squared of the r columns of
+    ``sample_scores`` (n x r) on categorical covariate b (between-level over total sum of squares about the mean), and with
+    ``ctns`` (n x m) a last row holds R-squared of the least-squares fit on [1, ctns].  A component tied to a known
+    covariate points at misfit or a missing interaction, one tied to none at an unknown factor.  A constant component
+    gives NaN.  -> (B x r)."""
+    S = np.asarray(sample_scores, dtype=np.float64)
+    if S.ndim == 1:
+        S = S.reshape(-1, 1)
+    if S.ndim != 2:
+        raise ValueError("sample_scores must be n x r")
+    n = S.shape[0]
+    lev = np.asarray(levels)
+    if lev.ndim < 1 or lev.ndim > 2 or lev.shape[0] != n or lev.size == 0:
+        raise ValueError(f"levels must hold n = {n} rows")
+    lev = lev.reshape(n, -1)
+    dev = S - S.mean(axis=0)
+    tss = (dev * dev).sum(axis=0)
+    rows = []
+    for b in range(lev.shape[1]):
+        ids = np.unique(lev[:, b], return_inverse=True)[1].ravel()
+        cnt = np.bincount(ids).astype(np.float64)
+        sums = np.zeros((cnt.size, S.shape[1]))
+        np.add.at(sums, ids, dev)
+        rows.append((sums * sums / cnt[:, None]).sum(axis=0))
+    if ctns is not None:
+        Zc = np.asarray(ctns, dtype=np.float64)
+        if Zc.shape[0] != n:
+            raise ValueError(f"ctns must hold n = {n} rows")
+        D = np.column_stack([np.ones(n), Zc.reshape(n, -1)])
+        res = dev - D @ np.linalg.lstsq(D, dev, rcond=None)[0]
+        rows.append(tss - (res * res).sum(axis=0))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.array(rows).reshape(len(rows), S.shape[1]) / np.where(tss > 0, tss, np.nan)
 
 
 def neighbors_host(query, base=None, k=10, metric="cosine", exclude_self=None, device=0, chunk=512):
