@@ -272,9 +272,23 @@ int insider_hip_strong_cd_xy(const double *X, const double *y, int64_t m, int K,
  * src/fit_interaction.cpp:54), batched: nsys systems of K x K (column-major) with one right-hand side each.  The
  * positive-definite route (Cholesky) first; when a pivot is not positive, the general route (Gaussian elimination with
  * partial pivoting) — Armadillo's documented behaviour.  route (optional, nsys ints): 0 = Cholesky, 1 = general, -1 =
- * singular (status INSIDER_ERR_SOLVE).  Stand-alone for parity tests of the fallback; the updates call the same
- * device code. */
+ * singular (status INSIDER_ERR_SOLVE; route and the other systems' x are filled in all the same).  K <= 64.  This is
+ * insider_hip_solve_sympd_form(..., lambda = 0, form = 0): the stand-alone kernel k_solve_batch, which runs the LDS
+ * Cholesky and the pivoted elimination at row pitch K.  The updates of the fit reach the same two routines at pitch KP,
+ * and a register Gauss-Jordan for K <= 31, through k_level_solve: form = 1 below. */
 int insider_hip_solve_sympd(const double *A, const double *b, int K, int64_t nsys, int device, double *x, int32_t *route);
+
+/* The same solve of (A + lambda I) x = b with the kernel chosen by the caller; lambda is added on the device.
+ *   form = 0  k_solve_batch, K <= 64; A may be non-symmetric (the general route then solves A x = b).
+ *   form = 1  the fit's own level solve, K <= 63: every system is packed as the level equation record of the row update
+ *             (KP = 16 ceil((K + 1) / 16); KP KP + KP doubles, zeros outside K; a level count of 1) and k_level_solve<NB>
+ *             is launched as the row update launches it: the register Gauss-Jordan for K <= 31, the LDS Cholesky at pitch
+ *             KP for K >= 32, the pivoted elimination at pitch KP on a reloaded system after a non-positive pivot.
+ *             SYMMETRIC INPUT ONLY: the register route reads the record by columns, the LDS routes by rows.  The x of a
+ *             singular system is returned as zeros.
+ * route and the status are those of insider_hip_solve_sympd.  Input must be finite. */
+int insider_hip_solve_sympd_form(const double *A, const double *b, int K, int64_t nsys, double lambda, int form, int device,
+                                 double *x, int32_t *route);
 
 /* optimize_continuous_v2 with the reference's eight arguments (src/optimize.cpp:76-137; .Call symbol
  * `_insider_optimize_continuous_v2`, src/RcppExports.cpp:69-85, R/RcppExports.R:16-18): the update of ONE continuous

@@ -31,7 +31,7 @@ SYMBOLS = (
     "insider_hip_remask", "insider_hip_set_folds", "insider_hip_remask_fold", "insider_hip_factor_decomposition",
     "insider_hip_outliers", "insider_hip_neighbors", "insider_hip_last_neighbors_ms", "insider_hip_level_scores",
     "insider_hip_enrichment", "insider_hip_last_enrichment_ms", "insider_hip_enrichment_sample",
-    "insider_hip_kmeans", "insider_hip_last_kmeans_ms", "insider_hip_residual_products",
+    "insider_hip_kmeans", "insider_hip_last_kmeans_ms", "insider_hip_residual_products", "insider_hip_solve_sympd_form",
 )
 COMM_ID_BYTES = 128
 # insider_hip_outliers (insider_amd/csrc/insider_outliers.hpp): the samples a block of k_ol_flag covers per trip (OL_TRIP) and the
@@ -117,6 +117,7 @@ def load():
     lib.insider_hip_strong_cd_xy.argtypes = [dp, dp, C.c_int64, C.c_int, dp, C.c_double, C.c_double, dp, dp, C.c_double,
                                              C.c_uint64, C.c_uint32, C.c_int, C.c_int, C.c_int, dp, i32p]
     lib.insider_hip_solve_sympd.argtypes = [dp, dp, C.c_int, C.c_int64, C.c_int, dp, i32p]
+    lib.insider_hip_solve_sympd_form.argtypes = [dp, dp, C.c_int, C.c_int64, C.c_double, C.c_int, C.c_int, dp, i32p]
     lib.insider_hip_optimize_continuous_v2.argtypes = [dp, C.c_int64, C.c_int64, u8p, dp, dp, C.c_int, dp, dp, C.c_double,
                                                        C.c_int, C.c_int]
     lib.insider_hip_get_info.argtypes = [C.c_void_p, C.c_char_p, dp]

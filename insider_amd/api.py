@@ -673,9 +673,17 @@ def optimize_continuous_v2(data, indicator, updating_factor, c_factor, updating_
     return u
 
 
-def solve_sympd(A, b, device=0, return_route=False):
-    """solve(A, b, solve_opts::likely_sympd) (src/optimize.cpp:175,190,226,240), batched: A (B, K, K) or (K, K), b (B, K)
-    or (K,).  Cholesky first, Gaussian elimination with partial pivoting when A is not positive definite."""
+SOLVE_FORMS = {"batch": 0, "level": 1}
+
+
+def solve_sympd(A, b, device=0, return_route=False, lambda_=0.0, form="batch"):
+    """solve(A + lambda I, b, solve_opts::likely_sympd) (src/optimize.cpp:175,190,226,240), batched: A (B, K, K) or (K, K),
+    b (B, K) or (K,).  Cholesky first, Gaussian elimination with partial pivoting when the matrix is not positive definite;
+    ``lambda_`` is added to the diagonal on the device.  ``form``: "batch" = the stand-alone kernel (K <= 64), "level" = the
+    fit's own level solve on every system packed as a level equation record (K <= 63, symmetric A only).  A singular system
+    raises InsiderError(ERR_SOLVE); the error carries ``x`` and ``route`` of the whole batch as attributes."""
+    if form not in SOLVE_FORMS:
+        raise InsiderError(_lib.ERR_ARG, f"form must be one of {sorted(SOLVE_FORMS)}")
     Am = np.asarray(A, dtype=np.float64)
     bm = np.asarray(b, dtype=np.float64)
     single = Am.ndim == 2
@@ -688,8 +696,14 @@ def solve_sympd(A, b, device=0, return_route=False):
     bf = np.ascontiguousarray(bm)
     x = np.zeros((B, K))
     route = np.zeros(B, dtype=np.int32)
-    _lib.check(_lib.load().insider_hip_solve_sympd(_lib.ptr(Af), _lib.ptr(bf), K, B, int(device), _lib.ptr(x),
-                                                   _lib.ptr(route, C.c_int32)))
+    try:
+        _lib.check(_lib.load().insider_hip_solve_sympd_form(_lib.ptr(Af), _lib.ptr(bf), K, B, float(lambda_),
+                                                            SOLVE_FORMS[form], int(device), _lib.ptr(x),
+                                                            _lib.ptr(route, C.c_int32)))
+    except InsiderError as e:
+        if e.status == _lib.ERR_SOLVE:
+            e.x, e.route = x, route
+        raise
     if single:
         x, route = x[0], int(route[0])
     return (x, route) if return_route else x

@@ -3063,26 +3063,67 @@ int insider_hip_strong_cd_xy(const double *X, const double *y, int64_t m, int K,
                             sweeps_out);
 }
 
-int insider_hip_solve_sympd(const double *A, const double *b, int K, int64_t nsys, int device, double *x, int32_t *route)
+// solve(A, b, likely_sympd) on a caller's systems, by the stand-alone kernel (form 0: k_solve_batch, pitch K) or by the fit's own
+// level solve (form 1: every system packed as the level equation record [KP x KP | KP] with a count of 1, k_level_solve<NB>
+// launched as row_update() launches it).  lambda is added to the diagonal on the device in both forms.
+int insider_hip_solve_sympd_form(const double *A, const double *b, int K, int64_t nsys, double lambda, int form, int device,
+                                 double *x, int32_t *route)
 {
     if (!A || !b || !x) return fail(INSIDER_ERR_ARG, "null argument");
+    if (form != 0 && form != 1) return fail(INSIDER_ERR_ARG, "form must be 0 (batch) or 1 (level)");
+    if (!(lambda == lambda)) return fail(INSIDER_ERR_ARG, "lambda is NaN");
     int rc = cd_common_checks(K, nsys, device);
     if (rc) return rc;
+    if (form == 1 && K > INSIDER_MAX_K) return fail(INSIDER_ERR_UNSUPPORTED, "form 1 (the level solve) needs K in 1..63");
     if (nsys == 0) return INSIDER_OK;
     HIPCHECK(hipSetDevice(device));
     DevBuf<double> dA, db, dx;
     DevBuf<int> dr;
-    if ((rc = dA.alloc((size_t)nsys * K * K)) || (rc = db.alloc((size_t)nsys * K)) || (rc = dx.alloc((size_t)nsys * K)) ||
-        (rc = dr.alloc((size_t)nsys)))
-        return rc;
-    HIPCHECK(hipMemcpy(dA, A, (size_t)nsys * K * K * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHECK(hipMemcpy(db, b, (size_t)nsys * K * sizeof(double), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_solve_batch, dim3((unsigned)nsys), dim3(64), 0, 0, (const double *)dA, (const double *)db, K, nsys, dx,
-                       dr);
-    KCHECK();
-    HIPCHECK(hipDeviceSynchronize());
-    HIPCHECK(hipMemcpy(x, dx, (size_t)nsys * K * sizeof(double), hipMemcpyDeviceToHost));
     std::vector<int> hr(nsys);
+    if (form == 0) {
+        if ((rc = dA.alloc((size_t)nsys * K * K)) || (rc = db.alloc((size_t)nsys * K)) || (rc = dx.alloc((size_t)nsys * K)) ||
+            (rc = dr.alloc((size_t)nsys)))
+            return rc;
+        HIPCHECK(hipMemcpy(dA, A, (size_t)nsys * K * K * sizeof(double), hipMemcpyHostToDevice));
+        HIPCHECK(hipMemcpy(db, b, (size_t)nsys * K * sizeof(double), hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(k_solve_batch, dim3((unsigned)nsys), dim3(64), 0, 0, (const double *)dA, (const double *)db, K, nsys,
+                           lambda, dx, dr);
+        KCHECK();
+        HIPCHECK(hipDeviceSynchronize());
+        HIPCHECK(hipMemcpy(x, dx, (size_t)nsys * K * sizeof(double), hipMemcpyDeviceToHost));
+    } else {
+        const int NB = (K + 1 + 15) / 16, KP = 16 * NB;
+        const size_t len = (size_t)KP * KP + KP;
+        std::vector<double> rec((size_t)nsys * len, 0.0);   // element (r, c) at r * KP + c, b behind it; zeros outside K
+        for (int64_t s = 0; s < nsys; ++s) {
+            double *q = rec.data() + (size_t)s * len;
+            const double *As = A + (size_t)s * K * K;
+            for (int r = 0; r < K; ++r) {
+                for (int c = 0; c < K; ++c) q[(size_t)r * KP + c] = As[r + (size_t)c * K];
+                q[(size_t)KP * KP + r] = b[(size_t)s * K + r];
+            }
+        }
+        DevBuf<int> dcnt, dfail;
+        if ((rc = dA.alloc((size_t)nsys * len)) || (rc = dx.alloc((size_t)nsys * KP)) || (rc = dr.alloc((size_t)nsys)) ||
+            (rc = dcnt.alloc((size_t)nsys)) || (rc = dfail.alloc(1)))
+            return rc;
+        const std::vector<int> ones(nsys, 1);
+        HIPCHECK(hipMemcpy(dA, rec.data(), (size_t)nsys * len * sizeof(double), hipMemcpyHostToDevice));
+        HIPCHECK(hipMemcpy(dcnt, ones.data(), (size_t)nsys * sizeof(int), hipMemcpyHostToDevice));
+        HIPCHECK(hipMemset(dx, 0, (size_t)nsys * KP * sizeof(double)));
+        HIPCHECK(hipMemset(dfail, 0, sizeof(int)));
+        NB_DISPATCH(NB, {
+            (void)WPB_;
+            hipLaunchKernelGGL((k_level_solve<NB_>), dim3((unsigned)nsys), dim3(64), 0, 0, (const double *)dA, (const int *)dcnt,
+                               (int)nsys, K, lambda, dx, dfail, dr);
+        });
+        KCHECK();
+        HIPCHECK(hipDeviceSynchronize());
+        std::vector<double> hx((size_t)nsys * KP);
+        HIPCHECK(hipMemcpy(hx.data(), dx, hx.size() * sizeof(double), hipMemcpyDeviceToHost));
+        for (int64_t s = 0; s < nsys; ++s)
+            for (int r = 0; r < K; ++r) x[(size_t)s * K + r] = hx[(size_t)s * KP + r];
+    }
     HIPCHECK(hipMemcpy(hr.data(), dr, (size_t)nsys * sizeof(int), hipMemcpyDeviceToHost));
     bool singular = false;
     for (int64_t i = 0; i < nsys; ++i) {
@@ -3091,6 +3132,11 @@ int insider_hip_solve_sympd(const double *A, const double *b, int K, int64_t nsy
     }
     if (singular) return fail(INSIDER_ERR_SOLVE, "a system is singular to working precision");
     return INSIDER_OK;
+}
+
+int insider_hip_solve_sympd(const double *A, const double *b, int K, int64_t nsys, int device, double *x, int32_t *route)
+{
+    return insider_hip_solve_sympd_form(A, b, K, nsys, 0.0, 0, device, x, route);
 }
 
 // ---- neighbours (insider_neighbors.hpp) ------------------------------------------------------------------------------------

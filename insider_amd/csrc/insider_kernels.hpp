@@ -535,7 +535,12 @@ __device__ __forceinline__ bool lu_solve_lds(double *A, int KP, int K, double &b
         const int pr = bi;
         const double f = (lane == pr || !valid) ? 0.0 : A[lane * KP + j] / A[pr * KP + j];
         // the pivot row has zeros in the earlier pivot columns, and it is not written in this step (f = 0 for its lane)
-        for (int c = j + 1; c < K; ++c) A[lane * KP + c] -= f * A[pr * KP + c];
+        // Lanes K .. 63 own no row and touch nothing.  Unguarded, they read and rewrote (f = 0: the same value)
+        // A[lane * KP + c]: for lane >= KP, at a pitch KP < 64 (k_level_solve<1>, <2>, <3> and the fallback of
+        // k_level_merged), that lies behind the KP x KP matrix, in whatever LDS follows it (in k_level_merged the other
+        // shared arrays of the kernel, dead by then).
+        if (valid)
+            for (int c = j + 1; c < K; ++c) A[lane * KP + c] -= f * A[pr * KP + c];
         b -= f * __shfl(b, pr, 64);
         if (lane == pr) { used = true; mycol = j; }
         wave_sync();
@@ -1514,10 +1519,11 @@ __global__ void __launch_bounds__(64) k_cont_cd(const double *__restrict__ eq, i
 // Stage 3 (one wave per level, after the cross-rank sum): add the ridge term and solve; write A_i[l].
 // solve(..., likely_sympd): the positive-definite route first (register Gauss-Jordan / LDS Cholesky); on a non-positive
 // pivot the general route (lu_solve_lds) on a fresh copy of the system; `fail` only when that is singular too.
+// route (optional, L ints; the fit passes none): 0 = positive-definite route, 1 = general, -1 = singular, per visited level.
 template <int NB>
 __global__ void __launch_bounds__(64) k_level_solve(const double *__restrict__ eq, const int *__restrict__ lvl_count,
                                                     int L, int K, double lambda, double *__restrict__ Arows /*L x KP*/,
-                                                    int *__restrict__ fail)
+                                                    int *__restrict__ fail, int *__restrict__ route = nullptr)
 {
     constexpr int KP = Geo<NB>::KP;
     __shared__ double s_A[KP * KP];
@@ -1549,9 +1555,13 @@ __global__ void __launch_bounds__(64) k_level_solve(const double *__restrict__ e
         if (lane < K) s_A[lane * KP + lane] += lambda;
         b = lane < KP ? src[KP * KP + lane] : 0.0;
         wave_sync();
-        if (!lu_solve_lds(s_A, KP, K, b, lane)) { if (lane == 0) *fail = 1; return; }
+        if (!lu_solve_lds(s_A, KP, K, b, lane)) {
+            if (lane == 0) { *fail = 1; if (route) route[l] = -1; }
+            return;
+        }
     }
     if (lane < K) Arows[(size_t)l * KP + lane] = b;
+    if (lane == 0 && route) route[l] = ok ? 0 : 1;   // insider_hip_solve_sympd_form only: the fit passes none
 }
 
 // X'X (K x K, column-major) and X'y of an m x K column-major design matrix and outcome: what the reference's callers
@@ -1574,8 +1584,10 @@ __global__ void __launch_bounds__(64) k_xtx_xty(const double *__restrict__ X, co
 // solve(A, b, likely_sympd) on its own, batched: one wave per K x K system (column-major = row-major of A', and the
 // positive-definite route needs A symmetric; the general route solves A' x = b for the transposed read, so the matrix
 // is loaded transposed to keep A x = b for non-symmetric input).  route[s]: 0 = Cholesky, 1 = general, -1 = singular.
+// lambda != 0 is added to the diagonal after the load (lambda == 0 leaves every bit of the system, a -0.0 included).
 __global__ void __launch_bounds__(64) k_solve_batch(const double *__restrict__ A, const double *__restrict__ bvec, int K,
-                                                    int64_t nsys, double *__restrict__ x, int *__restrict__ route)
+                                                    int64_t nsys, double lambda, double *__restrict__ x,
+                                                    int *__restrict__ route)
 {
     __shared__ double s_A[64 * 64];
     const int64_t sidx = blockIdx.x;
@@ -1585,6 +1597,10 @@ __global__ void __launch_bounds__(64) k_solve_batch(const double *__restrict__ A
     auto load = [&]() {
         for (int i = lane; i < K * K; i += WAVE) s_A[(i % K) * K + (i / K)] = src[i];   // element (r, c) at r * K + c
         wave_sync();
+        if (lambda != 0.0) {                                                            // wave-uniform
+            if (lane < K) s_A[lane * K + lane] += lambda;
+            wave_sync();
+        }
     };
     load();
     double b = lane < K ? bvec[(size_t)sidx * K + lane] : 0.0;
