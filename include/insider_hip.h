@@ -630,6 +630,50 @@ int insider_hip_kmeans(const double *P, int64_t N, int D, int k, int metric, con
                        int32_t *sizes, double *traj, double *final_inertia, int32_t *iters, int32_t *converged, int32_t *best);
 double insider_hip_last_kmeans_ms(void);
 
+/* Exact t-SNE map of a neighbour graph (insider_amd/csrc/insider_tsne.hpp).  Handle-free, one device.
+ *   Input: a graph, not points.  nbr_idx is N x k int32, point-major (row i = the k slots of point i), 0-based, -1 = an open
+ *   slot; nbr_d2 is N x k double, the squared distance >= 0 of every filled slot (open slots are not read; NaN by convention).
+ *   This is what insider_hip_neighbors returns under cosine with d2 = max(0, 2 - 2 score).  A row's filled slots come first; no
+ *   row names itself or one index twice.  m_i = the filled slots of row i.  A point with m_i = 0 that is in nobody's row is DEAD:
+ *   its coordinates (and beta, grad) are NaN, its p_cond row 0, and it takes part in no sum.  Na = the number of alive points.
+ *   Calibration of row i.  d_s = d2_s - (the smallest d2 of the row).  perplexity >= m_i: p_s|i = 1 / m_i, beta = 1.  Otherwise
+ *   exactly 100 steps from beta = 1, lo = 0, hi = inf on H(beta) = log S + beta T / S, S = sum_s exp(-beta d_s),
+ *   T = sum_s d_s exp(-beta d_s) (sums in slot order): H > log(perplexity): lo = beta, then beta = 2 beta while hi is inf, else
+ *   (beta + hi) / 2; otherwise hi = beta, then beta = (lo + beta) / 2.  p_s|i = exp(-beta d_s) / S with the last beta.  A row of
+ *   equal distances has no root: it ends uniform at beta = 2^100.  Nothing here yields NaN or Inf.
+ *   Joint.  P_ij = (p_j|i + p_i|j) / (2 Na), a direction that is in no row counting 0.
+ *   At a map Y (2 x N: y_i = Y[2 i], Y[2 i + 1]).  w_ij = 1 / (1 + |y_i - y_j|^2), the differences taken coordinate-wise before
+ *   squaring; Z = sum over alive i != j of w_ij; g_i = 4 (a sum_j P_ij w_ij (y_i - y_j) - (1 / Z) sum_j w_ij^2 (y_i - y_j)), a
+ *   the exaggeration in force; KL = sum over P_ij > 0 of P_ij log(P_ij Z / w_ij), always with the un-exaggerated P.
+ *   Iteration t = 0 .. max_iter - 1, from gain = 1, v = 0: a = exaggeration and mu = 0.5 while t < exag_iters, else a = 1 and
+ *   mu = 0.8; step = eta if eta > 0, else max(Na / (4 exaggeration), 50).  Per coordinate: gain = gain + 0.2 if
+ *   (g > 0) != (v > 0), else gain * 0.8; gain = max(gain, 0.01); v = mu v - (step gain) g; y = y + v (each product and sum
+ *   rounded as written).  Then the mean of the alive points, summed in a fixed order, is subtracted.  There is no early stop.
+ *   Records.  kl_traj has max_iter / kl_every + 1 entries: entry j is KL at Y_t, t = j kl_every (Y_max_iter = the returned map);
+ *   final_kl is KL at the returned map.  grad (2 x N) and Z are the gradient under a = 1 and Z at the returned map; beta (N) and
+ *   p_cond (N x k, open slots exactly 0) the calibration.  beta, p_cond, grad and Z may each be NULL.
+ *   Start.  init (2 x N) given: Y_0 = init (the values of dead points are checked but not used); max_iter = 0 then means
+ *   "calibrate, and evaluate KL, Z and the gradient at this Y".  init NULL: y_{i,d} = insider_tsne_draw(insider_sample_key(seed,
+ *   0), 2 i + d) (include/insider_sample.h): u = h32(key ^ 0x27D4EB2F (2 i + d + 1)), y = ((u + 0.5) 2^-32 - 0.5) 1e-4, uniform
+ *   in +-0.5e-4, drawn on the host.
+ *   Device.  The alive points are compacted on the host and the pattern of the reverse edges (a stable counting sort of the edges
+ *   by target) is built there before the upload; the all-pairs repulsion runs on a grid of row tiles x `slabs` slabs of the
+ *   points, whose partial sums are added in slab order (slabs = 0: the library chooses, from Na alone; 1..64: forced).  No
+ *   floating-point atomics: the result is a pure function of the arguments and repeated calls return identical bits.  The bits may
+ *   depend on `slabs` (it sets where the sums are cut).  Between the upload and the final download nothing crosses the bus.
+ *   Device memory is O(N k + slabs N).
+ *   INSIDER_ERR_ARG, nothing written: a NULL nbr_idx, nbr_d2, Y, kl_traj or final_kl; N outside 1..2^20; k outside 1..64; a
+ *   perplexity that is not finite or < 1; max_iter or exag_iters outside 0..10000; kl_every < 1; an exaggeration that is not finite
+ *   or < 1; an eta that is not finite or < 0; slabs outside 0..64; max_iter = 0 without init; an index outside -1..N-1, a row that
+ *   names itself or an index twice, a filled slot after an open one; a negative or non-finite d2 in a filled slot; a non-finite
+ *   init; Na < 2 (all checked on the host, before a device is opened).
+ *   insider_hip_last_tsne_ms: of the calling THREAD's last call, the HIP-event time in ms from its first kernel to its last (the
+ *   upload and the download excluded). */
+int insider_hip_tsne(const int32_t *nbr_idx, const double *nbr_d2, int64_t N, int k, double perplexity, const double *init,
+                     int max_iter, int exag_iters, int kl_every, double exaggeration, double eta, uint64_t seed, int slabs,
+                     int device, double *Y, double *kl_traj, double *final_kl, double *beta, double *p_cond, double *grad, double *Z);
+double insider_hip_last_tsne_ms(void);
+
 /* Profile of the last insider_hip_optimize() call (option "profile" = 1), HIP-event timed on the library's stream.
  * out[0..11]: {column-side masked-Gram launches, total ms, row-side masked-Gram launches, total ms,
  *  column-solve (CD / ridge) launches, total ms, test-residual launches, total ms,

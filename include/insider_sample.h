@@ -54,4 +54,13 @@ INSIDER_HD uint32_t insider_sample_phi(uint32_t key, uint32_t half, uint32_t p, 
     return x;
 }
 
+/* Start coordinate e = 2 i + d of insider_hip_tsne's drawn map (point i, coordinate d), key = insider_sample_key(seed, 0):
+ * u = h32(key ^ 0x27D4EB2F * (e + 1)), y = ((u + 0.5) 2^-32 - 0.5) * 1e-4.  Everything before the last product is exact in
+ * fp64, so the value is the same bits wherever it is computed; it lies strictly within +-0.5e-4. */
+INSIDER_HD double insider_tsne_draw(uint32_t key, uint32_t e)
+{
+    const uint32_t u = insider_h32(key ^ (0x27D4EB2FU * (e + 1U)));
+    return (((double)u + 0.5) * (1.0 / 4294967296.0) - 0.5) * 1e-4;
+}
+
 #endif /* INSIDER_SAMPLE_H */

@@ -32,6 +32,7 @@ SYMBOLS = (
     "insider_hip_outliers", "insider_hip_neighbors", "insider_hip_last_neighbors_ms", "insider_hip_level_scores",
     "insider_hip_enrichment", "insider_hip_last_enrichment_ms", "insider_hip_enrichment_sample",
     "insider_hip_kmeans", "insider_hip_last_kmeans_ms", "insider_hip_residual_products", "insider_hip_solve_sympd_form",
+    "insider_hip_tsne", "insider_hip_last_tsne_ms",
 )
 COMM_ID_BYTES = 128
 # insider_hip_outliers (insider_amd/csrc/insider_outliers.hpp): the samples a block of k_ol_flag covers per trip (OL_TRIP) and the
@@ -153,6 +154,9 @@ def load():
     lib.insider_hip_kmeans.argtypes = [dp, C.c_int64, C.c_int, C.c_int, C.c_int, dp, C.c_int, C.c_int, C.c_uint64, C.c_int, dp, i32p,
                                        dp, i32p, dp, i32p, dp, dp, i32p, i32p, i32p]
     lib.insider_hip_last_kmeans_ms.restype = C.c_double
+    lib.insider_hip_tsne.argtypes = [i32p, dp, C.c_int64, C.c_int, C.c_double, dp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double,
+                                     C.c_uint64, C.c_int, C.c_int, dp, dp, dp, dp, dp, dp, dp]
+    lib.insider_hip_last_tsne_ms.restype = C.c_double
     lib.insider_hip_get_profile.argtypes = [C.c_void_p, dp]
     lib.insider_hip_get_sweeps.argtypes = [C.c_void_p, i32p]
     lib.insider_hip_last_cd_ms.restype = C.c_double

@@ -890,6 +890,92 @@ def kmeans(points, k, metric="cosine", init=None, restarts=8, max_iter=100, seed
     return rec
 
 
+TSNE_MAX_N = 2 ** 20
+TSNE_MAX_K = NEIGHBOR_MAX_K
+TSNE_MAX_ITER = 10000
+TSNE_MAX_SLABS = 64
+
+
+def tsne_args(nbr_idx, nbr_d2, perplexity, init=None, max_iter=1000, exag_iters=250, kl_every=50, exaggeration=12.0, eta=0.0,
+              seed=DEFAULT_SEED, slabs=0):
+    """The checked arguments of tsne() / posthoc.tsne_host(): (nbr_idx int32 N x k and nbr_d2 float64 N x k, both row-major,
+    perplexity, init row-major N x 2 or None, max_iter, exag_iters, kl_every, exaggeration, eta, seed, slabs, alive (N bool)).
+    Every argument error of insider_hip_tsne (include/insider_hip.h) raises InsiderError(ERR_ARG) here, before the library is
+    reached."""
+    def bad(msg):
+        return InsiderError(_lib.ERR_ARG, msg)
+    if nbr_idx is None or nbr_d2 is None:
+        raise bad("nbr_idx and nbr_d2 are required")
+    raw = np.asarray(nbr_idx)
+    if raw.ndim != 2 or raw.dtype.kind not in "iu":
+        raise bad("nbr_idx must be an N x k integer array")
+    N, k = raw.shape
+    if not 1 <= N <= TSNE_MAX_N:
+        raise bad("N must be in 1..2^20")
+    if not 1 <= k <= TSNE_MAX_K:
+        raise bad(f"k must be in 1..{TSNE_MAX_K}")
+    if raw.min() < -1 or raw.max() >= N:
+        raise bad("neighbour index out of range")
+    idx = np.ascontiguousarray(raw, dtype=np.int32)
+    d2 = np.ascontiguousarray(nbr_d2, dtype=np.float64)
+    if d2.shape != idx.shape:
+        raise bad("nbr_d2 must have the shape of nbr_idx")
+    for name, v, lo, hi in (("max_iter", max_iter, 0, TSNE_MAX_ITER), ("exag_iters", exag_iters, 0, TSNE_MAX_ITER),
+                            ("kl_every", kl_every, 1, 2 ** 31 - 1), ("seed", seed, 0, 2 ** 64 - 1), ("slabs", slabs, 0, TSNE_MAX_SLABS)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
+            raise bad(f"{name} must be an integer in {lo}..{hi}")
+    for name, v, lo in (("perplexity", perplexity, 1.0), ("exaggeration", exaggeration, 1.0), ("eta", eta, 0.0)):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v) or v < lo:
+            raise bad(f"{name} must be finite and >= {lo:g}")
+    if max_iter == 0 and init is None:
+        raise bad("max_iter = 0 needs init")
+    filled = idx >= 0
+    if (filled[:, 1:] & ~filled[:, :-1]).any():
+        raise bad("a filled slot follows an open one")
+    if (idx == np.arange(N, dtype=np.int32)[:, None]).any():
+        raise bad("a row names itself")
+    srt = np.sort(idx, axis=1)
+    if ((srt[:, 1:] == srt[:, :-1]) & (srt[:, 1:] >= 0)).any():
+        raise bad("an index is repeated within a row")
+    dv = d2[filled]
+    if not (np.isfinite(dv) & (dv >= 0.0)).all():
+        raise bad("d2 must be finite and >= 0 in a filled slot")
+    if init is not None:
+        init = np.ascontiguousarray(init, dtype=np.float64)
+        if init.shape != (N, 2):
+            raise bad("init must be an N x 2 array")
+        if not np.isfinite(init).all():
+            raise bad("init must be finite")
+    alive = filled[:, 0] | (np.bincount(idx[filled], minlength=N) > 0)
+    if int(alive.sum()) < 2:
+        raise bad("fewer than 2 alive points")
+    return (idx, d2, float(perplexity), init, int(max_iter), int(exag_iters), int(kl_every), float(exaggeration), float(eta),
+            int(seed), int(slabs), alive)
+
+
+def tsne(nbr_idx, nbr_d2, perplexity=20.0, init=None, max_iter=1000, exag_iters=250, kl_every=50, exaggeration=12.0, eta=0.0,
+         seed=DEFAULT_SEED, slabs=0, device=0):
+    """The exact t-SNE map of a neighbour graph on the device (insider_hip_tsne; include/insider_hip.h states the definitions).
+    nbr_idx (N x k, 0-based, -1 = open slot) and nbr_d2 (N x k squared distances) are a row per point, as
+    posthoc.embedding_graph() returns them.  init: N x 2 start (max_iter = 0 evaluates KL, Z and the gradient there), None: drawn
+    from ``seed``.  eta = 0: max(Na / (4 exaggeration), 50).  slabs = 0: the library cuts the all-pairs sum.  -> dict(y (N x 2,
+    NaN for a dead point), kl_traj (max_iter // kl_every + 1: KL at Y_t, t = 0, kl_every, ...), final_kl, beta (N), p_cond (N x k),
+    grad (N x 2, at y under exaggeration 1), z, alive (N bool), ms (the HIP-event time of the call's kernels))."""
+    idx, d2, perplexity, init, max_iter, exag_iters, kl_every, exaggeration, eta, seed, slabs, alive = tsne_args(
+        nbr_idx, nbr_d2, perplexity, init, max_iter, exag_iters, kl_every, exaggeration, eta, seed, slabs)
+    N, k = idx.shape
+    rec = dict(y=np.full((N, 2), np.nan), kl_traj=np.full(max_iter // kl_every + 1, np.nan), beta=np.full(N, np.nan),
+               p_cond=np.full((N, k), np.nan), grad=np.full((N, 2), np.nan))
+    fin, z = np.full(1, np.nan), np.full(1, np.nan)
+    lib = _lib.load()
+    _lib.check(lib.insider_hip_tsne(_lib.ptr(idx, C.c_int32), _lib.ptr(d2), N, k, perplexity,
+                                    None if init is None else _lib.ptr(init), max_iter, exag_iters, kl_every, exaggeration, eta,
+                                    seed, slabs, int(device), _lib.ptr(rec["y"]), _lib.ptr(rec["kl_traj"]), _lib.ptr(fin),
+                                    _lib.ptr(rec["beta"]), _lib.ptr(rec["p_cond"]), _lib.ptr(rec["grad"]), _lib.ptr(z)))
+    rec.update(final_kl=float(fin[0]), z=float(z[0]), alive=alive, ms=float(lib.insider_hip_last_tsne_ms()))
+    return rec
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # caller level — R/insider.R, R/utils.R
 # ---------------------------------------------------------------------------------------------------------------

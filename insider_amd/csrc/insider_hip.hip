@@ -16,6 +16,7 @@
 #include "insider_neighbors.hpp"
 #include "insider_enrich.hpp"
 #include "insider_kmeans.hpp"
+#include "insider_tsne.hpp"
 
 #include <rccl/rccl.h>
 
@@ -45,6 +46,7 @@ thread_local int g_last_cd_solver = 0;     // (ColSolver)
 thread_local double g_last_neighbors_ms = 0.0;
 thread_local double g_last_enrichment_ms = 0.0;
 thread_local double g_last_kmeans_ms = 0.0;
+thread_local double g_last_tsne_ms = 0.0;
 
 int fail(int code, const std::string &msg)
 {
@@ -3416,6 +3418,226 @@ int insider_hip_kmeans(const double *P, int64_t N, int D, int k, int metric, con
 }
 
 double insider_hip_last_kmeans_ms(void) { return g_last_kmeans_ms; }
+
+// ---- t-SNE (insider_tsne.hpp) ---------------------------------------------------------------------------------------------
+int insider_hip_tsne(const int32_t *nbr_idx, const double *nbr_d2, int64_t N, int k, double perplexity, const double *init,
+                     int max_iter, int exag_iters, int kl_every, double exaggeration, double eta, uint64_t seed, int slabs,
+                     int device, double *Y, double *kl_traj, double *final_kl, double *beta, double *p_cond, double *grad, double *Z)
+{
+    if (!nbr_idx || !nbr_d2 || !Y || !kl_traj || !final_kl) return fail(INSIDER_ERR_ARG, "null argument");
+    if (N < 1 || N > ((int64_t)1 << 20)) return fail(INSIDER_ERR_ARG, "N must be in 1..2^20");
+    if (k < 1 || k > TS_MAX_K) return fail(INSIDER_ERR_ARG, "k must be in 1..64");
+    if (!std::isfinite(perplexity) || perplexity < 1.0) return fail(INSIDER_ERR_ARG, "perplexity must be finite and >= 1");
+    if (max_iter < 0 || max_iter > 10000) return fail(INSIDER_ERR_ARG, "max_iter must be in 0..10000");
+    if (exag_iters < 0 || exag_iters > 10000) return fail(INSIDER_ERR_ARG, "exag_iters must be in 0..10000");
+    if (kl_every < 1) return fail(INSIDER_ERR_ARG, "kl_every must be >= 1");
+    if (!std::isfinite(exaggeration) || exaggeration < 1.0) return fail(INSIDER_ERR_ARG, "exaggeration must be finite and >= 1");
+    if (!std::isfinite(eta) || eta < 0.0) return fail(INSIDER_ERR_ARG, "eta must be finite and >= 0");
+    if (slabs < 0 || slabs > TS_MAX_SLABS) return fail(INSIDER_ERR_ARG, "slabs must be in 0..64");
+    if (max_iter == 0 && !init) return fail(INSIDER_ERR_ARG, "max_iter = 0 needs init");
+    // the graph: filled slots first, in range, no self edge, no repeat within a row, d2 finite and >= 0; the in-degrees
+    std::vector<int32_t> rev_ptr((size_t)N + 1, 0);
+    {
+        std::vector<int32_t> seen((size_t)N, -1);   // the last row each target was met in
+        for (int64_t i = 0; i < N; ++i) {
+            bool open = false;
+            for (int s = 0; s < k; ++s) {
+                const int32_t j = nbr_idx[(size_t)i * k + s];
+                if (j < 0) {
+                    if (j != -1) return fail(INSIDER_ERR_ARG, "neighbour index out of range");
+                    open = true;
+                    continue;
+                }
+                if (open) return fail(INSIDER_ERR_ARG, "a filled slot follows an open one");
+                if (j >= N) return fail(INSIDER_ERR_ARG, "neighbour index out of range");
+                if (j == i) return fail(INSIDER_ERR_ARG, "a row names itself");
+                if (seen[j] == (int32_t)i) return fail(INSIDER_ERR_ARG, "an index is repeated within a row");
+                seen[j] = (int32_t)i;
+                const double d = nbr_d2[(size_t)i * k + s];
+                if (!std::isfinite(d) || d < 0.0) return fail(INSIDER_ERR_ARG, "d2 must be finite and >= 0 in a filled slot");
+                ++rev_ptr[(size_t)j + 1];
+            }
+        }
+    }
+    if (init && !all_finite(init, (size_t)2 * N)) return fail(INSIDER_ERR_ARG, "init must be finite");
+    // alive = a filled slot of its own or a place in somebody's row; cmp = the compact number of an alive point
+    std::vector<int32_t> cmp((size_t)N, -1), alive;
+    alive.reserve((size_t)N);
+    for (int64_t i = 0; i < N; ++i)
+        if (nbr_idx[(size_t)i * k] >= 0 || rev_ptr[(size_t)i + 1] > 0) {
+            cmp[i] = (int32_t)alive.size();
+            alive.push_back((int32_t)i);
+        }
+    const int n = (int)alive.size();
+    if (n < 2) return fail(INSIDER_ERR_ARG, "fewer than 2 alive points");
+    const size_t nk = (size_t)n * k;
+    // the compacted graph and its transpose: a stable counting sort of the edges by target (sources ascend, then slots)
+    std::vector<int32_t> cidx(nk, -1), mate(nk, -1), ro_ptr((size_t)n + 1, 0), ro_src, ro_flat;
+    std::vector<double> cd2(nk, 0.0);
+    {
+        std::vector<int32_t> rptr((size_t)n + 1, 0);
+        for (int c = 0; c < n; ++c) rptr[(size_t)c + 1] = rptr[c] + rev_ptr[(size_t)alive[c] + 1];
+        std::vector<int32_t>().swap(rev_ptr);
+        const size_t ne = (size_t)rptr[n];
+        std::vector<int32_t> rev_src(ne), rev_slot(ne), next(rptr.begin(), rptr.end() - 1);
+        for (int c = 0; c < n; ++c) {
+            const size_t src = (size_t)alive[c] * k;
+            for (int s = 0; s < k && nbr_idx[src + s] >= 0; ++s) {
+                const int32_t t = cmp[nbr_idx[src + s]];
+                cidx[(size_t)c * k + s] = t;
+                cd2[(size_t)c * k + s] = nbr_d2[src + s];
+                rev_src[next[t]] = c;
+                rev_slot[next[t]] = s;
+                ++next[t];
+            }
+        }
+        // a reverse edge whose source is in the row merges into that forward slot (mate); the others form the reverse-only list
+        std::vector<int32_t> where((size_t)n, -1);   // the slot of target t in the current row
+        ro_src.reserve(ne);
+        ro_flat.reserve(ne);
+        for (int c = 0; c < n; ++c) {
+            for (int s = 0; s < k && cidx[(size_t)c * k + s] >= 0; ++s) where[cidx[(size_t)c * k + s]] = s;
+            for (int32_t e = rptr[c]; e < rptr[(size_t)c + 1]; ++e) {
+                const int32_t j = rev_src[e], flat = j * k + rev_slot[e];
+                if (where[j] >= 0) mate[(size_t)c * k + where[j]] = flat;
+                else {
+                    ro_src.push_back(j);
+                    ro_flat.push_back(flat);
+                }
+            }
+            for (int s = 0; s < k && cidx[(size_t)c * k + s] >= 0; ++s) where[cidx[(size_t)c * k + s]] = -1;
+            ro_ptr[(size_t)c + 1] = (int32_t)ro_src.size();
+        }
+    }
+    const size_t nro = ro_src.size();
+    if (nro == 0) {   // (an upload is never empty)
+        ro_src.push_back(0);
+        ro_flat.push_back(0);
+    }
+    // the start, compacted: the caller's, or the draw of include/insider_hip.h
+    std::vector<double> y0((size_t)2 * n);
+    {
+        const uint32_t key = insider_sample_key(seed, 0U);
+        for (int c = 0; c < n; ++c)
+            for (int d = 0; d < 2; ++d) {
+                const size_t e = (size_t)2 * alive[c] + d;
+                y0[(size_t)2 * c + d] = init ? init[e] : insider_tsne_draw(key, (uint32_t)e);
+            }
+    }
+    int rc = cd_common_checks(1, N, device);
+    if (rc) return rc;
+    HIPCHECK(hipSetDevice(device));
+    const int tiles = cdiv(n, TS_TILE);
+    if (slabs == 0) slabs = std::max(1, std::min({TS_MAX_SLABS, cdiv(TS_BLOCKS, tiles), n / TS_MIN_SLAB}));
+    const int slab_len = cdiv(n, slabs);
+    const int nb = cdiv(n, 256), nsb = cdiv(n, TS_ROWS);
+    const int nrec = max_iter / kl_every + 1;
+    const double eta_used = eta > 0.0 ? eta : std::max((double)n / (4.0 * exaggeration), 50.0);
+    DevBuf<int32_t> didx, dmate, dro_ptr, dro_src, dro_flat;
+    DevBuf<double> dd2, dbeta, dpc, dPF, dPR, dYa, dYb, dV, dG, dgrad, dpart, drep, dzpart, dspart, dscal, dkl;
+    if ((rc = didx.upload(cidx)) || (rc = dmate.upload(mate)) || (rc = dro_ptr.upload(ro_ptr)) || (rc = dro_src.upload(ro_src)) ||
+        (rc = dro_flat.upload(ro_flat)) || (rc = dd2.upload(cd2)) || (rc = dYa.upload(y0)) || (rc = dbeta.alloc((size_t)n)) ||
+        (rc = dpc.alloc(nk)) || (rc = dPF.alloc(nk)) || (rc = dPR.alloc(nro)) || (rc = dYb.alloc((size_t)2 * n)) ||
+        (rc = dV.alloc((size_t)2 * n)) || (rc = dG.alloc((size_t)2 * n)) || (rc = dgrad.alloc((size_t)2 * n)) ||
+        (rc = dpart.alloc((size_t)slabs * n * 3)) || (rc = drep.alloc((size_t)n * 3)) || (rc = dzpart.alloc((size_t)nb)) ||
+        (rc = dspart.alloc((size_t)nsb * 3)) || (rc = dscal.alloc(8)) || (rc = dkl.alloc((size_t)nrec)))
+        return rc;
+    {
+        const std::vector<double> ones((size_t)2 * n, 1.0);
+        HIPCHECK(hipMemcpy(dG, ones.data(), ones.size() * sizeof(double), hipMemcpyHostToDevice));
+        HIPCHECK(hipMemset(dV, 0, (size_t)2 * n * sizeof(double)));
+    }
+    Event e0, e1;
+    HIPCHECK(hipEventCreate(e0.out()));
+    HIPCHECK(hipEventCreate(e1.out()));
+    HIPCHECK(hipEventRecord(e0, 0));
+    hipLaunchKernelGGL(k_ts_calibrate, dim3(nb), dim3(256), 0, 0, (const int32_t *)didx, (const double *)dd2, n, k, perplexity,
+                       dbeta.get(), dpc.get());
+    KCHECK();
+    hipLaunchKernelGGL(k_ts_joint, dim3(cdiv((int64_t)std::max(nk, nro), 256)), dim3(256), 0, 0, (const double *)dpc,
+                       (const int32_t *)dmate, (int64_t)nk, (const int32_t *)dro_flat, (int64_t)nro, 2.0 * (double)n, dPF.get(),
+                       dPR.get());
+    KCHECK();
+    double2 *ycur = (double2 *)dYa.get(), *ynew = (double2 *)dYb.get();
+    double *zsum = dscal.get(), *ssum = dscal.get() + 1, *zout = dscal.get() + 4;
+    // Z and the rows' repulsive sums at ycur
+    auto repulse = [&]() -> int {
+        hipLaunchKernelGGL(k_ts_repulse, dim3(tiles, slabs), dim3(256), 0, 0, (const double2 *)ycur, n, slab_len, dpart.get());
+        KCHECK();
+        hipLaunchKernelGGL(k_ts_reduce, dim3(nb), dim3(256), 0, 0, (const double *)dpart, slabs, n, drep.get(), dzpart.get());
+        KCHECK();
+        hipLaunchKernelGGL(k_ts_fold, dim3(1), dim3(256), 0, 0, (const double *)dzpart, nb, 1, zsum);
+        KCHECK();
+        return INSIDER_OK;
+    };
+    auto step = [&](double a, double mu, int update, int record) -> int {
+        hipLaunchKernelGGL(k_ts_step, dim3(nsb), dim3(256), 0, 0, (const int32_t *)didx, (const double *)dPF,
+                           (const int32_t *)dro_ptr, (const int32_t *)dro_src, (const double *)dPR, (const double *)drep,
+                           (const double *)zsum, n, k, a, mu, eta_used, update, record, (const double2 *)ycur, ynew,
+                           (double2 *)dV.get(), (double2 *)dG.get(), (double2 *)dgrad.get(), dspart.get(), update ? nullptr : zout);
+        KCHECK();
+        hipLaunchKernelGGL(k_ts_fold, dim3(1), dim3(256), 0, 0, (const double *)dspart, nsb, 3, ssum);
+        KCHECK();
+        return INSIDER_OK;
+    };
+    for (int t = 0; t < max_iter; ++t) {
+        const bool early = t < exag_iters, record = t % kl_every == 0;
+        if ((rc = repulse()) || (rc = step(early ? exaggeration : 1.0, early ? 0.5 : 0.8, 1, record))) return rc;
+        hipLaunchKernelGGL(k_ts_centre, dim3(nb), dim3(256), 0, 0, (const double *)ssum, n, ynew,
+                           record ? dkl.get() + t / kl_every : nullptr);
+        KCHECK();
+        std::swap(ycur, ynew);
+    }
+    // the final Y: Z, KL and the gradient under exaggeration 1; nothing moves
+    if ((rc = repulse()) || (rc = step(1.0, 0.0, 0, 1))) return rc;
+    HIPCHECK(hipEventRecord(e1, 0));
+    HIPCHECK(hipEventSynchronize(e1));
+    float ms = 0.0f;
+    (void)hipEventElapsedTime(&ms, e0, e1);
+    g_last_tsne_ms = ms;
+    // every result is staged on the host first: a failed download leaves the caller's arrays as they were
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    std::vector<double> hY((size_t)2 * n), hkl((size_t)nrec, nan), hbeta, hpc, hgrad;
+    double scal[8];
+    HIPCHECK(hipMemcpy(hY.data(), ycur, hY.size() * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHECK(hipMemcpy(scal, dscal, sizeof(scal), hipMemcpyDeviceToHost));
+    const int nloop = (max_iter + kl_every - 1) / kl_every;   // the records of the loop: t = 0, kl_every, ... < max_iter
+    if (nloop) HIPCHECK(hipMemcpy(hkl.data(), dkl, (size_t)nloop * sizeof(double), hipMemcpyDeviceToHost));
+    if (max_iter % kl_every == 0) hkl[(size_t)max_iter / kl_every] = scal[3];
+    if (beta) {
+        hbeta.resize((size_t)n);
+        HIPCHECK(hipMemcpy(hbeta.data(), dbeta, hbeta.size() * sizeof(double), hipMemcpyDeviceToHost));
+    }
+    if (p_cond) {
+        hpc.resize(nk);
+        HIPCHECK(hipMemcpy(hpc.data(), dpc, hpc.size() * sizeof(double), hipMemcpyDeviceToHost));
+    }
+    if (grad) {
+        hgrad.resize((size_t)2 * n);
+        HIPCHECK(hipMemcpy(hgrad.data(), dgrad, hgrad.size() * sizeof(double), hipMemcpyDeviceToHost));
+    }
+    std::fill(Y, Y + (size_t)2 * N, nan);
+    if (beta) std::fill(beta, beta + (size_t)N, nan);
+    if (p_cond) std::fill(p_cond, p_cond + (size_t)N * k, 0.0);
+    if (grad) std::fill(grad, grad + (size_t)2 * N, nan);
+    for (int c = 0; c < n; ++c) {
+        const size_t i = (size_t)alive[c];
+        Y[2 * i] = hY[(size_t)2 * c];
+        Y[2 * i + 1] = hY[(size_t)2 * c + 1];
+        if (beta) beta[i] = hbeta[c];
+        if (p_cond) std::copy(hpc.begin() + (size_t)c * k, hpc.begin() + (size_t)(c + 1) * k, p_cond + i * k);
+        if (grad) {
+            grad[2 * i] = hgrad[(size_t)2 * c];
+            grad[2 * i + 1] = hgrad[(size_t)2 * c + 1];
+        }
+    }
+    std::copy(hkl.begin(), hkl.end(), kl_traj);
+    *final_kl = scal[3];
+    if (Z) *Z = scal[4];
+    return INSIDER_OK;
+}
+
+double insider_hip_last_tsne_ms(void) { return g_last_tsne_ms; }
 
 // ---- enrichment (insider_enrich.hpp) -----------------------------------------------------------------------------------------
 int insider_hip_enrichment_sample(uint64_t seed, uint32_t perm, int64_t m, int64_t p, int32_t *out)

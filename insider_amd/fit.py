@@ -12,6 +12,7 @@
     ... --outliers 3 [--outlier-entries train]  # then the entries whose standardised residual has |z| >= 3, on the device
     ... --gene-neighbors 10 --sample-neighbors 10 [--neighbor-metric cosine]   # then each gene's / sample's nearest in latent space
     ... --gene-modules 20 --sample-clusters 6 [--cluster-metric cosine]        # then k-means of the genes / samples in latent space
+    ... --gene-map --sample-map [--map-perplexity 20] [--map-neighbors 60]     # then the t-SNE map of the genes / samples
     ... --level-scores 1 [--level-score-entries train]   # then every sample against every level of covariate column 1 (1-based)
     ... --residual-components 5 [--rc-standardize] [--rc-entries train]   # then the hidden factors: what the model left behind
     ... --gene-sets SETS.gmt [--gene-names NAMES.txt] [--enrich-perms 1000] [--enrich-levels 1]   # then what each factor means
@@ -38,6 +39,10 @@ samples by their row embeddings (posthoc.gene_modules / sample_clusters; --clust
 0-based, -1 = an all-zero column under cosine, or no second centre), km_gene_dist / km_gene_dist2 (p), km_gene_center (K x k),
 km_gene_size (k), km_gene_traj (the inertia before every update, NaN beyond the last) and the same under km_sample_*; with
 --gene-sets also km_gene_overlap / km_gene_hyper_p / km_gene_hyper_fdr (k x S, posthoc.module_overrepresentation);
+--gene-map / --sample-map add the exact t-SNE map of the genes by their columns of C and of the samples by their row embeddings
+(posthoc.gene_map / sample_map: the cosine neighbour graph of --map-neighbors neighbours, --map-perplexity, --map-iters
+iterations from the start drawn from --map-seed; the defaults follow posthoc.tsne_defaults): ts_gene_y (p x 2, NaN for an
+all-zero column), ts_gene_kl (KL every 50 iterations and at the end), ts_gene_beta (p) and the same under ts_sample_*;
 --level-scores COV adds, for covariate column COV (1-based), ls_sse (n x L: the residual sum of squares of every
 sample over the --level-score-entries with its embedding for COV replaced by each level's), ls_n, ls_best (1-based, 0 = no
 entry), ls_margin (n) and ls_confusion (L x L, assigned x best; posthoc.ls_derived) — a sample's own level was fitted with that
@@ -156,6 +161,19 @@ def parse(argv=None):
                     help="--gene-modules / --sample-clusters: updates per start at most (default 100)")
     ap.add_argument("--cluster-seed", type=int, default=0x1D5EED, metavar="S",
                     help="--gene-modules / --sample-clusters: the seed of the drawn starts")
+    ap.add_argument("--gene-map", action="store_true",
+                    help="after the fit, the exact t-SNE map of the genes by their columns of C, on the device; writes ts_gene_y "
+                         "(p x 2; NaN for an all-zero column), ts_gene_kl and ts_gene_beta (p) next to the factors")
+    ap.add_argument("--sample-map", action="store_true",
+                    help="after the fit, the exact t-SNE map of the samples by their row embeddings, on the device; writes the "
+                         "ts_sample_* records")
+    ap.add_argument("--map-perplexity", type=float, default=None, metavar="P",
+                    help="--gene-map / --sample-map: the perplexity (default min(20, (points - 1) / 3))")
+    ap.add_argument("--map-neighbors", type=int, default=None, metavar="N",
+                    help="--gene-map / --sample-map: neighbours per point of the graph, 1..64 (default ceil(3 perplexity))")
+    ap.add_argument("--map-iters", type=int, default=1000, metavar="I",
+                    help="--gene-map / --sample-map: iterations (default 1000, the first 250 exaggerated)")
+    ap.add_argument("--map-seed", type=int, default=0x1D5EED, metavar="S", help="--gene-map / --sample-map: the seed of the start")
     ap.add_argument("--gene-sets", default=None, metavar="FILE",
                     help="after the fit, the gene-set enrichment of every factor's |loadings| on the device against the sets of "
                          "this GMT file (name, description, genes; tab-separated); writes gs_factor_es, gs_factor_nes, "
@@ -193,6 +211,19 @@ def parse(argv=None):
             ap.error(f"--{name.replace('_', '-')} must be in 1..4096")
         if v is not None and a.tune:
             ap.error(f"--{name.replace('_', '-')} partitions a fit: it does not go with --tune")
+    if a.gene_map or a.sample_map:
+        if a.tune:
+            ap.error("--gene-map / --sample-map draw a fit: they do not go with --tune")
+    elif a.map_perplexity is not None or a.map_neighbors is not None:
+        ap.error("--map-perplexity and --map-neighbors go with --gene-map or --sample-map")
+    if a.map_perplexity is not None and not (np.isfinite(a.map_perplexity) and a.map_perplexity >= 1.0):
+        ap.error("--map-perplexity must be finite and >= 1")
+    if a.map_neighbors is not None and not 1 <= a.map_neighbors <= 64:
+        ap.error("--map-neighbors must be in 1..64")
+    if not 1 <= a.map_iters <= 10000:
+        ap.error("--map-iters must be in 1..10000")
+    if not 0 <= a.map_seed < 2 ** 64:
+        ap.error("--map-seed must fit 64 bits")
     if not 1 <= a.cluster_restarts <= 256:
         ap.error("--cluster-restarts must be in 1..256")
     if not 0 <= a.cluster_iters <= 10000:
@@ -239,6 +270,11 @@ def km_records(prefix, rec):
     """The records of one api.kmeans() result under <prefix>_label, _dist, _second, _dist2, _center, _size and _traj."""
     names = dict(label="label", dist="dist", second="second", dist2="dist2", center="centers", size="sizes", traj="traj")
     return {f"{prefix}_{out}": rec[key] for out, key in names.items()}
+
+
+def ts_records(prefix, rec):
+    """The records of one api.tsne() result under <prefix>_y, _kl (the recorded KL, then the final one) and _beta."""
+    return {f"{prefix}_y": rec["y"], f"{prefix}_kl": np.append(rec["kl_traj"], rec["final_kl"]), f"{prefix}_beta": rec["beta"]}
 
 
 def main(argv=None):
@@ -383,6 +419,13 @@ def main(argv=None):
         from .posthoc import sample_clusters
         vd = dict(vd or {}, **km_records("km_sample", sample_clusters(list(res["row_matrices"].values()), ds_levels, Z,
                                                                       k=a.sample_clusters, **km)))
+    ts = dict(perplexity=a.map_perplexity, k=a.map_neighbors, max_iter=a.map_iters, seed=a.map_seed, device=a.device)
+    if a.gene_map:
+        from .posthoc import gene_map
+        vd = dict(vd or {}, **ts_records("ts_gene", gene_map(res["column_factor"], **ts)))
+    if a.sample_map:
+        from .posthoc import sample_map
+        vd = dict(vd or {}, **ts_records("ts_sample", sample_map(list(res["row_matrices"].values()), ds_levels, Z, **ts)))
     gs_names = None
     if a.gene_sets is not None:
         from .posthoc import factor_enrichment, level_enrichment

@@ -42,6 +42,9 @@ samples next to a sample (api.neighbors: a K-deep product on the device with the
 similarity matrix never exists), on column_factor and on sample_embeddings(); neighbors_host() is the yardstick.
 gene_modules() / sample_clusters() partition the same two embeddings (api.kmeans: the whole Lloyd loop on the device, cosine or
 Euclidean, restarts); kmeans_host() is the yardstick, module_overrepresentation() / module_summary() read the modules.
+gene_map() / sample_map() draw them: the exact t-SNE map of the embeddings' cosine neighbour graph (embedding_graph(), api.tsne:
+the whole optimisation on the device, the all-pairs repulsion summed in fp64, the same map to the bit from run to run);
+tsne_host() is the yardstick.
 
 factor_enrichment() / level_enrichment() ask what a factor or a level effect means: a preranked gene-set enrichment of the
 rows of column_factor, or of A_b @ column_factor, with a permutation null of random gene sets of equal size
@@ -1018,6 +1021,213 @@ def assign_to_centers(points, centers, metric="cosine", device=0):
     if Cm.ndim != 2:
         raise api.InsiderError(api._lib.ERR_ARG, "centers must be a D x k array")
     return api.kmeans(points, int(Cm.shape[1]), metric=metric, init=Cm, restarts=1, max_iter=0, device=device)
+
+
+# ---- t-SNE (include/insider_hip.h states the definitions) --------------------------------------------------------------------
+TSNE_U = 2.0 ** -52
+
+
+def tsne_draw_host(seed, N):
+    """The drawn start of insider_hip_tsne (insider_tsne_draw, include/insider_sample.h) -> (N, 2) float64, to the bit."""
+    with np.errstate(over="ignore"):
+        key = _h32(np.array([(seed & 0xFFFFFFFF) ^ 0x9E3779B9], dtype=np.uint32))
+        key = _h32(key ^ np.uint32((seed >> 32) & 0xFFFFFFFF))      # insider_sample_key(seed, 0)
+        e = np.arange(2 * N, dtype=np.uint32)
+        u = _h32(key ^ (np.uint32(0x27D4EB2F) * (e + np.uint32(1))))
+    return ((((u.astype(np.float64) + 0.5) * (1.0 / 4294967296.0)) - 0.5) * 1e-4).reshape(N, 2)
+
+
+def tsne_calibrate_host(idx, d2, perplexity):
+    """The calibration of every row: (beta (N), p_cond (N x k)); the 100 fixed steps, all rows at once, sums in slot order."""
+    N, k = idx.shape
+    filled = idx >= 0
+    m = filled.sum(axis=1)
+    d = np.where(filled, d2, np.inf)
+    d = np.where(filled, d - np.where(m > 0, d.min(axis=1), 0.0)[:, None], 0.0)
+    search = (m > 0) & (perplexity < m)
+    target = np.log(perplexity)
+    b, lo, hi = np.ones(N), np.zeros(N), np.full(N, np.inf)
+
+    def sums(b):
+        S, T = np.zeros(N), np.zeros(N)
+        for s in range(k):
+            e = np.where(filled[:, s], np.exp(-b * d[:, s]), 0.0)
+            S, T = S + e, T + d[:, s] * e
+        return S, T
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        for _ in range(100):
+            S, T = sums(b)
+            up = np.log(S) + b * T / S > target
+            lo, hi = np.where(up, b, lo), np.where(up, hi, b)
+            b = np.where(up, np.where(np.isinf(hi), b * 2.0, (b + hi) * 0.5), (lo + b) * 0.5)
+        b = np.where(search, b, 1.0)
+        S, _ = sums(b)
+        pc = np.where(filled, np.exp(-b[:, None] * d) / S[:, None], 0.0)
+        pc = np.where(search[:, None], pc, np.where(filled, 1.0 / np.maximum(m, 1)[:, None], 0.0))
+    return np.where(m > 0, b, 1.0), pc
+
+
+def tsne_joint_host(idx, pc, n_alive):
+    """The joint P as ordered pairs: (ii, jj, PP), every pair (i, j) with an edge in either direction once, and its mirror."""
+    N = idx.shape[0]
+    src, slot = np.nonzero(idx >= 0)
+    dst = idx[src, slot].astype(np.int64)
+    keys = np.concatenate([src * N + dst, dst * N + src])
+    uniq, inv = np.unique(keys, return_inverse=True)
+    PP = np.bincount(inv.ravel(), weights=np.concatenate([pc[src, slot]] * 2), minlength=uniq.size) / (2.0 * n_alive)
+    return uniq // N, uniq % N, PP
+
+
+def tsne_eval_host(Y, ii, jj, PP, alive, a=1.0, chunk=1024):
+    """Z, KL, the gradient (N x 2, under exaggeration a) and the sums the error bound of the gradient is made of at the map Y
+    (N x 2): dense O(N^2) repulsion, ``chunk`` rows at a time.  -> dict(z, kl, grad, attr_abs, rep_abs, rep, terms)."""
+    N = Y.shape[0]
+    ids = np.flatnonzero(alive)
+    Ya = Y[ids]
+    sw, rep, rep_abs = np.zeros(ids.size), np.zeros((ids.size, 2)), np.zeros((ids.size, 2))
+    for c0 in range(0, ids.size, chunk):
+        dx = Ya[c0:c0 + chunk, 0][:, None] - Ya[None, :, 0]
+        dy = Ya[c0:c0 + chunk, 1][:, None] - Ya[None, :, 1]
+        w = 1.0 / (1.0 + dx * dx + dy * dy)
+        r = np.arange(dx.shape[0])
+        w[r, c0 + r] = 0.0                                          # the self pair
+        sw[c0:c0 + chunk] = w.sum(axis=1)
+        w2 = w * w
+        rep[c0:c0 + chunk, 0], rep[c0:c0 + chunk, 1] = (w2 * dx).sum(axis=1), (w2 * dy).sum(axis=1)
+        rep_abs[c0:c0 + chunk, 0], rep_abs[c0:c0 + chunk, 1] = (w2 * np.abs(dx)).sum(axis=1), (w2 * np.abs(dy)).sum(axis=1)
+    z = float(sw.sum())
+    dlt = Y[ii] - Y[jj]
+    d = 1.0 + dlt[:, 0] * dlt[:, 0] + dlt[:, 1] * dlt[:, 1]
+    t = (PP / d)[:, None] * dlt
+    attr = np.column_stack([np.bincount(ii, weights=t[:, c], minlength=N) for c in range(2)])
+    attr_abs = np.column_stack([np.bincount(ii, weights=np.abs(t[:, c]), minlength=N) for c in range(2)])
+    pos = PP > 0
+    kl = float((PP[pos] * np.log(PP[pos] * z * d[pos])).sum())
+    full = np.zeros((N, 2))
+    full_abs = np.zeros((N, 2))
+    full[ids], full_abs[ids] = rep, rep_abs
+    grad = 4.0 * (a * attr - full / z)
+    grad[~alive] = np.nan
+    return dict(z=z, kl=kl, grad=grad, attr_abs=a * attr_abs, rep_abs=full_abs, rep=full,
+                terms=np.bincount(ii, minlength=N).astype(np.float64))
+
+
+def tsne_grad_bound(ev, n_alive, slabs):
+    """The derived bound on the error of a gradient component of the device (or of the yardstick) against the exact value, from
+    tsne_eval_host()'s sums: a sum of m terms in any order errs by at most (m - 1) u sum |terms| to first order, u = 2^-53; the
+    constant 8 covers the terms' own roundings (the differences, d, a reciprocal good to 2 ulp, the products) at 2^-52:
+        4 [ (m + 8) 2^-52 sum |attractive terms| + (Na + slabs + 8) 2^-52 sum_j |w^2 delta| / Z + |repulsive part| rz ],
+    rz = (Na + slabs + 8) 2^-52 the bound on the relative error of Z.  -> (N x 2)."""
+    rz = (n_alive + slabs + 8) * TSNE_U
+    return 4.0 * ((ev["terms"][:, None] + 8) * TSNE_U * ev["attr_abs"] + rz * ev["rep_abs"] / ev["z"]
+                  + np.abs(ev["rep"]) / ev["z"] * rz)
+
+
+def tsne_host(nbr_idx, nbr_d2, perplexity=20.0, init=None, max_iter=1000, exag_iters=250, kl_every=50, exaggeration=12.0, eta=0.0,
+              seed=0x1D5EED, slabs=0, device=0, chunk=1024, perturb_seed=None):
+    """api.tsne() in plain numpy float64 (the yardstick of the device path): the same arguments, checks, draw, schedule and
+    record over the same sparse definitions, with a dense O(N^2) repulsion ``chunk`` rows at a time.  The record also holds, over
+    the run's sign decisions of alive points, ``min_abs_g`` / ``min_abs_v`` (the smallest |g| and the smallest |v| from iteration
+    1 on: v is exactly 0 at iteration 0 on every side) and ``min_g_margin`` / ``min_v_margin``: the smallest |g| / bound and
+    |v| / (step gain bound), bound = tsne_grad_bound() with max(slabs, 1): a run whose margins exceed 1 takes the same decisions
+    under any evaluation that meets the bound.  perturb_seed: every gradient component is moved by + or - its bound (random
+    signs from that seed) before it is used: how far rounding-sized errors move the map.  (``device`` is accepted for the
+    common signature and not used; ``ms`` is the wall time.)"""
+    import time
+    from . import api
+    t_start = time.perf_counter()
+    idx, d2, perplexity, init, max_iter, exag_iters, kl_every, exaggeration, eta, seed, slabs, alive = api.tsne_args(
+        nbr_idx, nbr_d2, perplexity, init, max_iter, exag_iters, kl_every, exaggeration, eta, seed, slabs)
+    N, k = idx.shape
+    na = int(alive.sum())
+    beta, pc = tsne_calibrate_host(idx, d2, perplexity)
+    ii, jj, PP = tsne_joint_host(idx, pc, na)
+    Y = (tsne_draw_host(seed, N) if init is None else init.copy())
+    step = eta if eta > 0 else max(na / (4.0 * exaggeration), 50.0)
+    gain, v = np.ones((N, 2)), np.zeros((N, 2))
+    traj = np.full(max_iter // kl_every + 1, np.nan)
+    rng = None if perturb_seed is None else np.random.default_rng(perturb_seed)
+    mins = dict(min_abs_g=np.inf, min_abs_v=np.inf, min_g_margin=np.inf, min_v_margin=np.inf)
+    for t in range(max_iter):
+        a, mu = (exaggeration, 0.5) if t < exag_iters else (1.0, 0.8)
+        ev = tsne_eval_host(Y, ii, jj, PP, alive, a, chunk)
+        if t % kl_every == 0:
+            traj[t // kl_every] = ev["kl"]
+        g, bound = ev["grad"], tsne_grad_bound(ev, na, max(slabs, 1))
+        if rng is not None:
+            g = g + np.where(rng.random((N, 2)) < 0.5, -1.0, 1.0) * bound
+        ga, ba = np.abs(g[alive]), bound[alive]
+        mins["min_abs_g"] = min(mins["min_abs_g"], float(ga.min()))
+        with np.errstate(divide="ignore", invalid="ignore"):
+            mins["min_g_margin"] = min(mins["min_g_margin"], float(np.min(np.where(ba > 0, ga / ba, np.inf))))
+            if t > 0:
+                va = np.abs(v[alive])
+                mins["min_abs_v"] = min(mins["min_abs_v"], float(va.min()))
+                vb = step * gain[alive] * ba
+                mins["min_v_margin"] = min(mins["min_v_margin"], float(np.min(np.where(vb > 0, va / vb, np.inf))))
+        g = np.where(alive[:, None], g, 0.0)
+        gain = np.maximum(np.where((g > 0) != (v > 0), gain + 0.2, gain * 0.8), 0.01)
+        v = mu * v - (step * gain) * g
+        Y = Y + v
+        Y = Y - Y[alive].sum(axis=0) / float(na)
+    ev = tsne_eval_host(Y, ii, jj, PP, alive, 1.0, chunk)
+    if max_iter % kl_every == 0:
+        traj[max_iter // kl_every] = ev["kl"]
+    Y = np.where(alive[:, None], Y, np.nan)
+    rec = dict(y=Y, kl_traj=traj, final_kl=ev["kl"], beta=np.where(alive, beta, np.nan), p_cond=pc, grad=ev["grad"], z=ev["z"],
+               alive=alive, grad_bound=tsne_grad_bound(ev, na, max(slabs, 1)), ms=(time.perf_counter() - t_start) * 1e3)
+    rec.update(mins)
+    return rec
+
+
+def embedding_graph(points, k, metric="cosine", device=0):
+    """The neighbour graph of the columns of ``points`` (D x N) for tsne(): api.neighbors() of the points against themselves
+    -> (nbr_idx (N x k int32, -1 = open slot), nbr_d2 (N x k): d2 = max(0, 2 - 2 score), the squared distance of the unit
+    vectors, NaN at open slots).  Only the cosine score is a distance this way; api.tsne() itself takes any graph."""
+    from . import api
+    if metric != "cosine":
+        raise api.InsiderError(api._lib.ERR_ARG, "embedding_graph offers the cosine metric only")
+    nn = api.neighbors(points, None, k=k, metric=metric, device=device)
+    idx, sc = nn["index"], nn["score"]
+    with np.errstate(invalid="ignore"):
+        return idx, np.where(idx >= 0, np.maximum(0.0, 2.0 - 2.0 * sc), np.nan)
+
+
+def tsne_defaults(n_alive, n_points, perplexity=None, k=None):
+    """The maps' defaults: perplexity = min(20, (Na - 1) / 3) (at least 1), k = min(64, N - 1, ceil(3 perplexity))."""
+    if perplexity is None:
+        perplexity = max(1.0, min(20.0, (n_alive - 1) / 3.0))
+    if k is None:
+        k = int(max(1, min(64, n_points - 1, np.ceil(3.0 * perplexity))))
+    return float(perplexity), int(k)
+
+
+def embedding_map(points, perplexity=None, k=None, metric="cosine", max_iter=1000, seed=0x1D5EED, device=0, **kw):
+    """The t-SNE map of the columns of ``points`` (D x N): embedding_graph() and api.tsne() with tsne_defaults() (Na counted as
+    the columns that are not all zero).  -> the api.tsne() record plus nbr_idx, nbr_d2, perplexity and k."""
+    from . import api
+    P = np.asarray(points, dtype=np.float64)
+    if P.ndim != 2 or P.shape[1] < 2:
+        raise api.InsiderError(api._lib.ERR_ARG, "points must be a D x N array of at least 2 columns")
+    perplexity, k = tsne_defaults(int(np.count_nonzero((P * P).sum(axis=0) > 0)), P.shape[1], perplexity, k)
+    idx, d2 = embedding_graph(P, k, metric=metric, device=device)
+    rec = api.tsne(idx, d2, perplexity=perplexity, max_iter=max_iter, seed=seed, device=device, **kw)
+    rec.update(nbr_idx=idx, nbr_d2=d2, perplexity=perplexity, k=k)
+    return rec
+
+
+def gene_map(column_factor, perplexity=None, k=None, metric="cosine", max_iter=1000, seed=0x1D5EED, device=0, **kw):
+    """The two-dimensional map of the genes: embedding_map() of the columns of C (K x p).  An all-zero column, which elastic-net
+    fits do produce, has no neighbours under cosine and is nobody's: it is dead (y = NaN).  -> the api.tsne() record (y: p x 2)."""
+    return embedding_map(column_factor, perplexity, k, metric, max_iter, seed, device, **kw)
+
+
+def sample_map(cfd_factors, levels, ctns_confounder=None, perplexity=None, k=None, metric="cosine", max_iter=1000, seed=0x1D5EED,
+               device=0, **kw):
+    """The two-dimensional map of the samples: embedding_map() of sample_embeddings().  Samples that share every level are equal
+    points at distance 0: they stay neighbours of each other.  -> the api.tsne() record (y: n x 2)."""
+    return embedding_map(sample_embeddings(cfd_factors, levels, ctns_confounder), perplexity, k, metric, max_iter, seed, device,
+                         **kw)
 
 
 def module_overrepresentation(label, sets, k=None):
