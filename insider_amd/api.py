@@ -277,43 +277,58 @@ class InsiderData:
 
     VD_ENTRIES = {"all": 0, "train": 1, "test": 2}
 
+    def _entries_code(self, entries, inc_continuous):
+        """The C ABI's code of ``entries``; ERR_ARG for a bad ``entries``, then for a bad ``inc_continuous``."""
+        if entries not in self.VD_ENTRIES:
+            raise InsiderError(_lib.ERR_ARG, f"entries must be one of {sorted(self.VD_ENTRIES)}, got {entries!r}")
+        if inc_continuous not in (0, 1):
+            raise InsiderError(_lib.ERR_ARG, "The value of prarameter inc_continuous can only be 0 or 1.")
+        return self.VD_ENTRIES[entries]
+
+    def _fit_args(self, cfd_factors, column_factor, entries, inc_continuous):
+        """What every call on a whole fit takes: K, the marshalled factors and their pointers, the entries code and the
+        number of covariate blocks (ERR_ARG for ``entries``, then ``inc_continuous``, then the factors' shapes)."""
+        code = self._entries_code(entries, inc_continuous)
+        K = int(np.asarray(column_factor).shape[0])
+        A, Cw, Aptrs = self._marshal(cfd_factors, column_factor, K, inc_continuous)
+        return K, A, Cw, Aptrs, code, self.c + int(inc_continuous)
+
+    @staticmethod
+    def _sums_record(out, nb):
+        """The raw sums of a decomposition from its records ``out`` (one row of 4 + 3 nb per gene or sample)."""
+        blk = out[:, 4:].reshape(out.shape[0], nb, 3)
+        return dict(n=out[:, 0].copy(), sum_x=out[:, 1].copy(), sum_xx=out[:, 2].copy(), rss=out[:, 3].copy(),
+                    sum_g=blk[:, :, 0].T.copy(), sum_gg=blk[:, :, 1].T.copy(), sum_rg=blk[:, :, 2].T.copy())
+
+    def _center_scale(self, center, scale, names):
+        """``center`` and ``scale`` as contiguous float64 vectors of length p (None stays None); ``names`` words the error."""
+        ce = None if center is None else np.ascontiguousarray(np.asarray(center, dtype=np.float64).ravel())
+        sc = None if scale is None else np.ascontiguousarray(np.asarray(scale, dtype=np.float64).ravel())
+        if (ce is not None and ce.shape != (self.p,)) or (sc is not None and sc.shape != (self.p,)):
+            raise InsiderError(_lib.ERR_ARG, f"{names} must hold p = {self.p} values")
+        return ce, sc
+
     def variance_decomposition(self, cfd_factors, column_factor, entries="train", inc_continuous=0):
         """Per-gene sums of the variance decomposition (insider_hip_variance_decomposition) over the entries ``entries``
         ("all", "train": the handle's train bit, "test": its test bit) of every gene: a dict of ``n``, ``sum_x``,
         ``sum_xx``, ``rss`` (length p) and ``sum_g``, ``sum_gg``, ``sum_rg`` (B x p, block b = covariate b, then the
         continuous block).  posthoc.vd_derived() turns them into r2 / rmse / explained / drop_one."""
-        if entries not in self.VD_ENTRIES:
-            raise InsiderError(_lib.ERR_ARG, f"entries must be one of {sorted(self.VD_ENTRIES)}, got {entries!r}")
-        if inc_continuous not in (0, 1):
-            raise InsiderError(_lib.ERR_ARG, "The value of prarameter inc_continuous can only be 0 or 1.")
-        K = int(np.asarray(column_factor).shape[0])
-        A, Cw, Aptrs = self._marshal(cfd_factors, column_factor, K, inc_continuous)
-        nb = self.c + int(inc_continuous)
+        K, A, Cw, Aptrs, code, nb = self._fit_args(cfd_factors, column_factor, entries, inc_continuous)
         out = np.empty((self.p, 4 + 3 * nb), dtype=np.float64)
         _lib.check(_lib.load().insider_hip_variance_decomposition(self._h, Aptrs, _lib.ptr(Cw), int(inc_continuous), K,
-                                                                  self.VD_ENTRIES[entries], _lib.ptr(out)))
-        blk = out[:, 4:].reshape(self.p, nb, 3)
-        return dict(n=out[:, 0].copy(), sum_x=out[:, 1].copy(), sum_xx=out[:, 2].copy(), rss=out[:, 3].copy(),
-                    sum_g=blk[:, :, 0].T.copy(), sum_gg=blk[:, :, 1].T.copy(), sum_rg=blk[:, :, 2].T.copy())
+                                                                  code, _lib.ptr(out)))
+        return self._sums_record(out, nb)
 
     def sample_decomposition(self, cfd_factors, column_factor, entries="train", inc_continuous=0):
         """Per-sample sums of the fit diagnostics (insider_hip_sample_decomposition): variance_decomposition() along the
         other axis, over the selected entries of every sample: a dict of ``n``, ``sum_x``, ``sum_xx``, ``rss`` (length n) and
         ``sum_g``, ``sum_gg``, ``sum_rg`` (B x n).  posthoc.vd_derived() turns them into r2 / rmse / explained / drop_one,
         posthoc.level_decomposition() sums them per level of a covariate first."""
-        if entries not in self.VD_ENTRIES:
-            raise InsiderError(_lib.ERR_ARG, f"entries must be one of {sorted(self.VD_ENTRIES)}, got {entries!r}")
-        if inc_continuous not in (0, 1):
-            raise InsiderError(_lib.ERR_ARG, "The value of prarameter inc_continuous can only be 0 or 1.")
-        K = int(np.asarray(column_factor).shape[0])
-        A, Cw, Aptrs = self._marshal(cfd_factors, column_factor, K, inc_continuous)
-        nb = self.c + int(inc_continuous)
+        K, A, Cw, Aptrs, code, nb = self._fit_args(cfd_factors, column_factor, entries, inc_continuous)
         out = np.empty((self.n, 4 + 3 * nb), dtype=np.float64)
         _lib.check(_lib.load().insider_hip_sample_decomposition(self._h, Aptrs, _lib.ptr(Cw), int(inc_continuous), K,
-                                                                self.VD_ENTRIES[entries], _lib.ptr(out)))
-        blk = out[:, 4:].reshape(self.n, nb, 3)
-        return dict(n=out[:, 0].copy(), sum_x=out[:, 1].copy(), sum_xx=out[:, 2].copy(), rss=out[:, 3].copy(),
-                    sum_g=blk[:, :, 0].T.copy(), sum_gg=blk[:, :, 1].T.copy(), sum_rg=blk[:, :, 2].T.copy())
+                                                                code, _lib.ptr(out)))
+        return self._sums_record(out, nb)
 
     def level_scores(self, cfd_factors, column_factor, cov, entries="train", candidates=None, inc_continuous=0):
         """Every sample scored against every level of the categorical covariate ``cov`` (0-based; insider_hip_level_scores):
@@ -327,14 +342,10 @@ class InsiderData:
         A sample's own level was fitted WITH that sample: on ``entries="train"`` the assigned level is favoured, most for
         levels with few samples (a level with one sample fits itself); on a tuning handle ``entries="test"`` scores on
         entries no embedding has seen.  The call reports and corrects nothing."""
-        if entries not in self.VD_ENTRIES:
-            raise InsiderError(_lib.ERR_ARG, f"entries must be one of {sorted(self.VD_ENTRIES)}, got {entries!r}")
-        if inc_continuous not in (0, 1):
-            raise InsiderError(_lib.ERR_ARG, "The value of prarameter inc_continuous can only be 0 or 1.")
+        self._entries_code(entries, inc_continuous)   # (reported before cov; the factors' shapes after it, as ever)
         if not isinstance(cov, (int, np.integer)) or isinstance(cov, bool) or not 0 <= cov < self.c:
             raise InsiderError(_lib.ERR_ARG, f"cov must be a categorical covariate in 0..{self.c - 1}, got {cov!r}")
-        K = int(np.asarray(column_factor).shape[0])
-        A, Cw, Aptrs = self._marshal(cfd_factors, column_factor, K, inc_continuous)
+        K, A, Cw, Aptrs, code, nb = self._fit_args(cfd_factors, column_factor, entries, inc_continuous)
         if candidates is None:
             cand, L = None, int(self.n_levels[int(cov)])
         else:
@@ -346,7 +357,7 @@ class InsiderData:
         sse = np.empty((self.n, L), dtype=np.float64, order="F")
         cnt = np.empty(self.n, dtype=np.float64)
         _lib.check(_lib.load().insider_hip_level_scores(self._h, Aptrs, _lib.ptr(Cw), int(inc_continuous), K,
-                                                        self.VD_ENTRIES[entries], int(cov),
+                                                        code, int(cov),
                                                         None if cand is None else _lib.ptr(cand), 0 if cand is None else L,
                                                         _lib.ptr(sse), _lib.ptr(cnt)))
         return dict(sse=sse, n=cnt)
@@ -357,16 +368,10 @@ class InsiderData:
         ``rss`` (length p) and ``sum_h``, ``sum_hh``, ``sum_rh`` ((B + 1) x K x p: block b = covariate b, then the continuous
         block, then the total, whose embedding is the row factor).  posthoc.fd_derived() turns them into r2 / rmse /
         explained / drop_one per (block, factor, gene), posthoc.factor_summary() pools the genes."""
-        if entries not in self.VD_ENTRIES:
-            raise InsiderError(_lib.ERR_ARG, f"entries must be one of {sorted(self.VD_ENTRIES)}, got {entries!r}")
-        if inc_continuous not in (0, 1):
-            raise InsiderError(_lib.ERR_ARG, "The value of prarameter inc_continuous can only be 0 or 1.")
-        K = int(np.asarray(column_factor).shape[0])
-        A, Cw, Aptrs = self._marshal(cfd_factors, column_factor, K, inc_continuous)
-        nb = self.c + int(inc_continuous)
+        K, A, Cw, Aptrs, code, nb = self._fit_args(cfd_factors, column_factor, entries, inc_continuous)
         out = np.empty((self.p, 4 + 3 * (nb + 1) * K), dtype=np.float64)
         _lib.check(_lib.load().insider_hip_factor_decomposition(self._h, Aptrs, _lib.ptr(Cw), int(inc_continuous), K,
-                                                                self.VD_ENTRIES[entries], _lib.ptr(out)))
+                                                                code, _lib.ptr(out)))
         blk = out[:, 4:].reshape(self.p, nb + 1, K, 3)
         return dict(n=out[:, 0].copy(), sum_x=out[:, 1].copy(), sum_xx=out[:, 2].copy(), rss=out[:, 3].copy(),
                     sum_h=blk[..., 0].transpose(1, 2, 0).copy(), sum_hh=blk[..., 1].transpose(1, 2, 0).copy(),
@@ -381,10 +386,7 @@ class InsiderData:
         ``want_y`` False: the forward pass is skipped) and ``rss`` (p, each gene's sum of r^2).  R never exists: each product is
         one streaming pass over the resident X.  posthoc.residual_components() iterates it to the leading singular directions
         of R."""
-        if entries not in self.VD_ENTRIES:
-            raise InsiderError(_lib.ERR_ARG, f"entries must be one of {sorted(self.VD_ENTRIES)}, got {entries!r}")
-        if inc_continuous not in (0, 1):
-            raise InsiderError(_lib.ERR_ARG, "The value of prarameter inc_continuous can only be 0 or 1.")
+        self._entries_code(entries, inc_continuous)   # (reported before Q; the factors' shapes after it, as ever)
         Qm = np.asarray(Q, dtype=np.float64)
         if Qm.ndim == 1:
             Qm = Qm.reshape(-1, 1)
@@ -394,17 +396,13 @@ class InsiderData:
             raise InsiderError(_lib.ERR_ARG, "Q holds a value that is not finite")
         Qm = _lib.f64(Qm)
         q = Qm.shape[1]
-        K = int(np.asarray(column_factor).shape[0])
-        A, Cw, Aptrs = self._marshal(cfd_factors, column_factor, K, inc_continuous)
-        ce = None if center is None else np.ascontiguousarray(np.asarray(center, dtype=np.float64).ravel())
-        sc = None if scale is None else np.ascontiguousarray(np.asarray(scale, dtype=np.float64).ravel())
-        if (ce is not None and ce.shape != (self.p,)) or (sc is not None and sc.shape != (self.p,)):
-            raise InsiderError(_lib.ERR_ARG, f"center and scale must hold p = {self.p} values")
+        K, A, Cw, Aptrs, code, nb = self._fit_args(cfd_factors, column_factor, entries, inc_continuous)
+        ce, sc = self._center_scale(center, scale, "center and scale")
         Z = np.empty((self.p, q), dtype=np.float64, order="F")
         Y = np.empty((self.n, q), dtype=np.float64, order="F") if want_y else None
         rss = np.empty(self.p, dtype=np.float64)
         _lib.check(_lib.load().insider_hip_residual_products(self._h, Aptrs, _lib.ptr(Cw), int(inc_continuous), K,
-                                                             self.VD_ENTRIES[entries],
+                                                             code,
                                                              None if ce is None else _lib.ptr(ce),
                                                              None if sc is None else _lib.ptr(sc), _lib.ptr(Qm), q,
                                                              _lib.ptr(Z), None if Y is None else _lib.ptr(Y), _lib.ptr(rss)))
@@ -420,20 +418,13 @@ class InsiderData:
         capacity of max(2^20, n p / 64) and, when ``total`` exceeds it, a second one with cap = total (the whole list); an
         integer = the first ``cap`` calls (compare ``total`` with it); 0 = counts only.
         posthoc.residual_center_scale() derives center and scale from a variance-decomposition record."""
-        if entries not in self.VD_ENTRIES:
-            raise InsiderError(_lib.ERR_ARG, f"entries must be one of {sorted(self.VD_ENTRIES)}, got {entries!r}")
-        if inc_continuous not in (0, 1):
-            raise InsiderError(_lib.ERR_ARG, "The value of prarameter inc_continuous can only be 0 or 1.")
+        self._entries_code(entries, inc_continuous)   # (reported before scale and cap; the factors' shapes after them)
         if scale is None:
             raise InsiderError(_lib.ERR_ARG, "scale is required")
         if cap is not None and (int(cap) != cap or cap < 0):
             raise InsiderError(_lib.ERR_ARG, "cap must be None or an integer >= 0")
-        K = int(np.asarray(column_factor).shape[0])
-        A, Cw, Aptrs = self._marshal(cfd_factors, column_factor, K, inc_continuous)
-        sc = np.ascontiguousarray(np.asarray(scale, dtype=np.float64).ravel())
-        ce = None if center is None else np.ascontiguousarray(np.asarray(center, dtype=np.float64).ravel())
-        if sc.shape != (self.p,) or (ce is not None and ce.shape != (self.p,)):
-            raise InsiderError(_lib.ERR_ARG, f"scale and center must hold p = {self.p} values")
+        K, A, Cw, Aptrs, code, nb = self._fit_args(cfd_factors, column_factor, entries, inc_continuous)
+        ce, sc = self._center_scale(center, scale, "scale and center")
         gene = np.empty((self.p, 2), dtype=np.int32)
         samp = np.empty((self.n, 2), dtype=np.int32)
         total = C.c_int64()
@@ -444,7 +435,7 @@ class InsiderData:
             z = np.empty(capacity, dtype=np.float64)
             lists = (_lib.ptr(rows, C.c_int32), _lib.ptr(cols, C.c_int32), _lib.ptr(z)) if capacity else (None, None, None)
             _lib.check(lib.insider_hip_outliers(self._h, Aptrs, _lib.ptr(Cw), int(inc_continuous), K,
-                                                self.VD_ENTRIES[entries], None if ce is None else _lib.ptr(ce), _lib.ptr(sc),
+                                                code, None if ce is None else _lib.ptr(ce), _lib.ptr(sc),
                                                 float(threshold), capacity, *lists, C.byref(total),
                                                 _lib.ptr(gene, C.c_int32), _lib.ptr(samp, C.c_int32)))
             return rows, cols, z
@@ -669,7 +660,7 @@ def optimize_continuous_v2(data, indicator, updating_factor, c_factor, updating_
         _lib.ptr(D), n, p, _lib.ptr(M, C.c_uint8) if M is not None else None, _lib.ptr(u), _lib.ptr(Cm), K, _lib.ptr(z),
         _lib.ptr(g) if g is not None else None, float(lambda_), int(tuning), int(device)))
     if isinstance(updating_factor, np.ndarray) and updating_factor.dtype == np.float64:
-        updating_factor.reshape(-1)[...] = u
+        np.copyto(updating_factor, u.reshape(updating_factor.shape))   # (also through a non-contiguous view)
     return u
 
 

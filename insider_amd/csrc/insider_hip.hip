@@ -409,8 +409,8 @@ struct PostWs {
     // outs: coeff, se, dof
     DevBuf<double> Ast, U, cp, part, stats, stage, gpart, gram, cpart, gsum, L, dinv, outs;
     DevBuf<int> nz, ints, info;
-    // variance decomposition: vin = the host factors (A blocks at row offset x K, then C as p rows of K); vtab = the level
-    // table T (p rows of SL); vrec = the p records
+    // vin = the host factors as upload_factors leaves them (A blocks at row offset x K, then C as p rows of K).  Variance
+    // decomposition: vtab = the level table T (p rows of SL); vrec = the p records
     DevBuf<double> vin, vtab, vrec;
     // sample decomposition: spart = the slabs' partial records (slabs x n x (4 + 3 BW)); srec = the n records
     DevBuf<double> spart, srec;
@@ -664,6 +664,15 @@ int ensure_workspace(insider_hip_handle *h, int K)
         default: { constexpr int NB_ = 4; constexpr int WPB_ = 1; __VA_ARGS__; } break;  \
     }
 
+// the post-hoc and embedding kernels' forms per number of 16-column tiles of K (1..4): the body sees it as KT_
+#define KT_DISPATCH(KTV, ...)                                   \
+    switch (KTV) {                                              \
+        case 1: { constexpr int KT_ = 1; __VA_ARGS__; } break;  \
+        case 2: { constexpr int KT_ = 2; __VA_ARGS__; } break;  \
+        case 3: { constexpr int KT_ = 3; __VA_ARGS__; } break;  \
+        default: { constexpr int KT_ = 4; __VA_ARGS__; } break; \
+    }
+
 // mark: when given, the bit of the form launched (RK_LIST_STATS4 / RK_LIST_STATS) is or'ed into it
 int launch_list_stats(insider_hip_handle *h, bool cols, int nseg, const double *F, double *stat,
                       const double *base = nullptr, uint64_t *mark = nullptr)
@@ -863,6 +872,39 @@ struct Timer {   // HIP-event pair around one launch on the library's stream (op
         HIPCHECK(hipEventRecord(e1, h->st.stream));
         into.push_back(std::move(e0));
         into.push_back(std::move(e1));
+        return INSIDER_OK;
+    }
+};
+
+// the kernel time a call reports (insider_hip_last_*_ms, "rc_ms"): a pair of default-flag HIP events on the call's stream
+struct Stopwatch {
+    Event e0, e1;
+    bool marked = false;
+    int start(hipStream_t st)   // (a second start reuses the pair: the batch CD entry times every chunk)
+    {
+        if (!e0) {
+            HIPCHECK(hipEventCreate(e0.out()));
+            HIPCHECK(hipEventCreate(e1.out()));
+        }
+        marked = false;
+        HIPCHECK(hipEventRecord(e0, st));
+        return INSIDER_OK;
+    }
+    // the end of the timed stretch alone, for a call that enqueues more work before the host may wait
+    int mark(hipStream_t st)
+    {
+        HIPCHECK(hipEventRecord(e1, st));
+        marked = true;
+        return INSIDER_OK;
+    }
+    // marks the end unless mark() did, waits for it and reads the time (0 when the runtime cannot give one)
+    int stop_ms(hipStream_t st, float *ms)
+    {
+        if (!marked)
+            if (int rc = mark(st)) return rc;
+        HIPCHECK(hipEventSynchronize(e1));
+        *ms = 0.0f;
+        (void)hipEventElapsedTime(ms, e0, e1);
         return INSIDER_OK;
     }
 };
@@ -2984,9 +3026,7 @@ static int strong_cd_device(const double *dG, const double *dq, const double *dw
     a.cd.order = order;
     a.sweeps = sw;
     a.hsave = a.isave = C;   // read by a resumed pass only (none here)
-    Event e0, e1;
-    HIPCHECK(hipEventCreate(e0.out()));
-    HIPCHECK(hipEventCreate(e1.out()));
+    Stopwatch watch;
     float total = 0.0f;
     for (int64_t b0 = 0; b0 < nprob; b0 += chunk) {
         const int n = (int)std::min<int64_t>(chunk, nprob - b0);
@@ -2994,12 +3034,8 @@ static int strong_cd_device(const double *dG, const double *dq, const double *dw
                            dq + (size_t)b0 * K, dw + (size_t)b0 * K, K, KP, n, stat_len, stat, Qfull, C);
         KCHECK();
         a.p = n;
-        HIPCHECK(hipEventRecord(e0, 0));
-        if ((rc = launch_cd(cs, a, 0))) return rc;
-        HIPCHECK(hipEventRecord(e1, 0));
-        HIPCHECK(hipEventSynchronize(e1));
         float msf = 0.0f;
-        (void)hipEventElapsedTime(&msf, e0, e1);
+        if ((rc = watch.start(0)) || (rc = launch_cd(cs, a, 0)) || (rc = watch.stop_ms(0, &msf))) return rc;
         total += msf;
         HIPCHECK(hipMemcpy2D(beta_out + (size_t)b0 * K, (size_t)K * sizeof(double), C, (size_t)KP * sizeof(double),
                              (size_t)K * sizeof(double), (size_t)n, hipMemcpyDeviceToHost));
@@ -3189,29 +3225,20 @@ int insider_hip_neighbors(const double *Q, int64_t nq, const double *B, int64_t 
         HIPCHECK(hipMemcpy(dQ, Q, (size_t)nq * K * sizeof(double), hipMemcpyHostToDevice));
         qsrc = dQ;
     }
-    Event e0, e1;
-    HIPCHECK(hipEventCreate(e0.out()));
-    HIPCHECK(hipEventCreate(e1.out()));
-    HIPCHECK(hipEventRecord(e0, 0));
+    Stopwatch watch;
+    if ((rc = watch.start(0))) return rc;
     hipLaunchKernelGGL(k_nn_prep, dim3(cdiv(nbpad, 256)), dim3(256), 0, 0, (const double *)dB, nb, nbpad, K, K4, metric, dBp.get(),
                        dba.get());
     KCHECK();
     hipLaunchKernelGGL(k_nn_prep, dim3(cdiv(nqpad, 256)), dim3(256), 0, 0, qsrc, nq, nqpad, K, K4, metric, dQp.get(), dqa.get());
     KCHECK();
     const dim3 grid(cdiv(nq, 16 * NW)), block(64 * NW);
-#define NN_LAUNCH(KS_)                                                                                                       \
-    hipLaunchKernelGGL((k_nn_topk<KS_>), grid, block, lds(NW), 0, (const double *)dQp, (const int *)dqa, nq, (const double *)dBp,  \
-                       (const int *)dba, nbpad, K4, NT, k, self_offset, didx.get(), dscore.get())
-    if (KS == 1) NN_LAUNCH(1);
-    else if (KS == 2) NN_LAUNCH(2);
-    else if (KS == 3) NN_LAUNCH(3);
-    else NN_LAUNCH(4);
-#undef NN_LAUNCH
+    KT_DISPATCH(KS, hipLaunchKernelGGL((k_nn_topk<KT_>), grid, block, lds(NW), 0, (const double *)dQp, (const int *)dqa, nq,
+                                       (const double *)dBp, (const int *)dba, nbpad, K4, NT, k, self_offset, didx.get(),
+                                       dscore.get()));
     KCHECK();
-    HIPCHECK(hipEventRecord(e1, 0));
-    HIPCHECK(hipEventSynchronize(e1));
     float ms = 0.0f;
-    (void)hipEventElapsedTime(&ms, e0, e1);
+    if ((rc = watch.stop_ms(0, &ms))) return rc;
     g_last_neighbors_ms = ms;
     HIPCHECK(hipMemcpy(idx_out, didx, (size_t)nq * k * sizeof(int32_t), hipMemcpyDeviceToHost));
     HIPCHECK(hipMemcpy(score_out, dscore, (size_t)nq * k * sizeof(double), hipMemcpyDeviceToHost));
@@ -3299,10 +3326,8 @@ int insider_hip_kmeans(const double *P, int64_t N, int D, int k, int metric, con
         return rc;
     HIPCHECK(hipMemcpy(dX, P, (size_t)N * D * sizeof(double), hipMemcpyHostToDevice));
     if (!init && (rc = dpick.upload(pick))) return rc;
-    Event e0, e1;
-    HIPCHECK(hipEventCreate(e0.out()));
-    HIPCHECK(hipEventCreate(e1.out()));
-    HIPCHECK(hipEventRecord(e0, 0));
+    Stopwatch watch;
+    if ((rc = watch.start(0))) return rc;
     hipLaunchKernelGGL(k_nn_prep, dim3(cdiv(npad, 256)), dim3(256), 0, 0, (const double *)dX, N, npad, D, K4, metric, dXp.get(),
                        dalive.get());
     KCHECK();
@@ -3313,15 +3338,10 @@ int insider_hip_kmeans(const double *P, int64_t N, int D, int k, int metric, con
         hipLaunchKernelGGL(k_km_cprep, dim3(cdiv(kpad, 256)), dim3(256), 0, 0, (const double *)dC, k, kpad, D, K4, metric,
                            dCp.get(), dh.get());
         KCHECK();
-#define KM_LAUNCH(KS_)                                                                                                          \
-    hipLaunchKernelGGL((k_km_assign<KS_>), dim3(nblk), dim3(64 * KM_NW), lds, 0, (const double *)dXp, (const int *)dalive, N,    \
-                       (const double *)dCp, (const double *)dh, k, kpad, K4, NT, metric, (const double *)dxx, dlabel.get(),      \
-                       dsecond.get(), ddist.get(), ddist2.get(), dpin.get(), dpch.get())
-        if (KS == 1) KM_LAUNCH(1);
-        else if (KS == 2) KM_LAUNCH(2);
-        else if (KS == 3) KM_LAUNCH(3);
-        else KM_LAUNCH(4);
-#undef KM_LAUNCH
+        KT_DISPATCH(KS, hipLaunchKernelGGL((k_km_assign<KT_>), dim3(nblk), dim3(64 * KM_NW), lds, 0, (const double *)dXp,
+                                           (const int *)dalive, N, (const double *)dCp, (const double *)dh, k, kpad, K4, NT, metric,
+                                           (const double *)dxx, dlabel.get(), dsecond.get(), ddist.get(), ddist2.get(),
+                                           dpin.get(), dpch.get()));
         KCHECK();
         hipLaunchKernelGGL(k_km_reduce, dim3(1), dim3(256), 0, 0, (const double *)dpin, (const int *)dpch, nblk, drec.get());
         KCHECK();
@@ -3389,10 +3409,8 @@ int insider_hip_kmeans(const double *P, int64_t N, int D, int k, int metric, con
             }
         }
     }
-    HIPCHECK(hipEventRecord(e1, 0));
-    HIPCHECK(hipEventSynchronize(e1));
     float ms = 0.0f;
-    (void)hipEventElapsedTime(&ms, e0, e1);
+    if ((rc = watch.stop_ms(0, &ms))) return rc;
     g_last_kmeans_ms = ms;
     // every result is staged on the host first: a failed download leaves the caller's arrays as they were
     std::vector<double> hC((size_t)k * D), hdist((size_t)N), hdist2((size_t)N);
@@ -3547,10 +3565,8 @@ int insider_hip_tsne(const int32_t *nbr_idx, const double *nbr_d2, int64_t N, in
         HIPCHECK(hipMemcpy(dG, ones.data(), ones.size() * sizeof(double), hipMemcpyHostToDevice));
         HIPCHECK(hipMemset(dV, 0, (size_t)2 * n * sizeof(double)));
     }
-    Event e0, e1;
-    HIPCHECK(hipEventCreate(e0.out()));
-    HIPCHECK(hipEventCreate(e1.out()));
-    HIPCHECK(hipEventRecord(e0, 0));
+    Stopwatch watch;
+    if ((rc = watch.start(0))) return rc;
     hipLaunchKernelGGL(k_ts_calibrate, dim3(nb), dim3(256), 0, 0, (const int32_t *)didx, (const double *)dd2, n, k, perplexity,
                        dbeta.get(), dpc.get());
     KCHECK();
@@ -3590,10 +3606,8 @@ int insider_hip_tsne(const int32_t *nbr_idx, const double *nbr_d2, int64_t N, in
     }
     // the final Y: Z, KL and the gradient under exaggeration 1; nothing moves
     if ((rc = repulse()) || (rc = step(1.0, 0.0, 0, 1))) return rc;
-    HIPCHECK(hipEventRecord(e1, 0));
-    HIPCHECK(hipEventSynchronize(e1));
     float ms = 0.0f;
-    (void)hipEventElapsedTime(&ms, e0, e1);
+    if ((rc = watch.stop_ms(0, &ms))) return rc;
     g_last_tsne_ms = ms;
     // every result is staged on the host first: a failed download leaves the caller's arrays as they were
     const double nan = std::numeric_limits<double>::quiet_NaN();
@@ -3716,10 +3730,8 @@ int insider_hip_enrichment(const double *scores, int64_t R, int64_t p, const int
     HIPCHECK(hipMemcpy(dgenes, set_genes, (size_t)nnz * sizeof(int32_t), hipMemcpyHostToDevice));
     HIPCHECK(hipMemcpy(dptr, set_ptr, ((size_t)S + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
     const uint32_t half = insider_sample_half((uint32_t)p);
-    Event e0, e1;
-    HIPCHECK(hipEventCreate(e0.out()));
-    HIPCHECK(hipEventCreate(e1.out()));
-    HIPCHECK(hipEventRecord(e0, 0));
+    Stopwatch watch;
+    if ((rc = watch.start(0))) return rc;
     // one pair of launches per class of sizes that sort at the same padded length M2
     const int nsz_all = (int)sizes.size();
     for (int z0 = 0; z0 < nsz_all;) {
@@ -3745,10 +3757,8 @@ int insider_hip_enrichment(const double *scores, int64_t R, int64_t p, const int
         KCHECK();
         z0 = z1;
     }
-    HIPCHECK(hipEventRecord(e1, 0));
-    HIPCHECK(hipEventSynchronize(e1));
     float ms = 0.0f;
-    (void)hipEventElapsedTime(&ms, e0, e1);
+    if ((rc = watch.stop_ms(0, &ms))) return rc;
     g_last_enrichment_ms = ms;
     HIPCHECK(hipMemcpy(es, des, (size_t)R * S * sizeof(double), hipMemcpyDeviceToHost));
     HIPCHECK(hipMemcpy(sum_same, dsum, (size_t)R * S * sizeof(double), hipMemcpyDeviceToHost));
@@ -4044,50 +4054,95 @@ int ph_check(insider_hip_handle *h, double *const *A, const double *C, int inc_c
     return INSIDER_OK;
 }
 
-// U (n x KPW) = the sum of the subtracted blocks' contributions, and C in the kernels' layout (cp, nz)
-int ph_prepare(insider_hip_handle *h, double *const *A, const double *C, int K, const int32_t *subtract, int KPW)
+// the checks of a call on the whole fit (every block enters it) over the entries selected by `entries`
+int fit_check(insider_hip_handle *h, double *const *A, const double *C, int inc_continuous, int K, int entries)
+{
+    if (!h) return fail(INSIDER_ERR_ARG, "null handle");
+    const std::vector<int32_t> every((size_t)h->ds->c + 2, 1);
+    int rc = ph_check(h, A, C, inc_continuous, K, every.data());
+    if (rc) return rc;
+    if (entries < 0 || entries > 2) return fail(INSIDER_ERR_ARG, "entries must be 0 (all), 1 (train) or 2 (test)");
+    return INSIDER_OK;
+}
+
+// the kernels' entry selector: 0 takes every observed entry, else the mask code an entry must carry
+int entry_code(int entries) { return entries == 0 ? 0 : entries == 1 ? CODE_TRAIN : CODE_TEST; }
+
+// the continuous columns that enter the fit
+int ctns_cols(const DataSet &d, int inc_continuous) { return inc_continuous ? d.m : 0; }
+
+// bytes of dynamic LDS a kernel may stage level tables in: option "vd_stage_kb", at most 60 KiB (beside a kernel's static
+// buffers: no launch attribute needed)
+double table_lds_budget(const insider_hip_handle *h) { return std::min(std::max(h->opt.vd_stage_kb, 0.0), 60.0) * 1024.0; }
+
+// gene slabs of a streaming pass whose grid is `tiles` sample tiles x slabs: `option` slabs when positive, else eight blocks
+// per compute unit (2 n_simd / tiles) and, where one slab's partials take part_bytes > 0, no more than option "ls_part_mb"
+// holds; at most 256.  Returns the slabs that hold genes and writes the genes per slab.
+int gene_slabs(const insider_hip_handle *h, int option, int tiles, double part_bytes, int64_t *slab_len)
+{
+    int want = option;
+    if (want <= 0) {
+        want = cdiv(2 * h->ds->n_simd, tiles);
+        if (part_bytes > 0.0) {
+            const double cap = std::max(h->opt.ls_part_mb, 0.0) * 1048576.0 / part_bytes;
+            want = (int)std::min<double>(want, std::max(cap, 1.0));
+        }
+    }
+    *slab_len = cdiv(h->ds->p, (int64_t)std::max(1, std::min(want, 256)));
+    return (int)cdiv(h->ds->p, *slab_len);
+}
+
+// the host factors on the device, enqueued on the main stream: the row factors' blocks stacked in PostWs::Ast as SL rows of
+// KPW (the rows of a block whose flag in `use` is 0 are zero; use == NULL takes every block) and C as p rows of K in
+// PostWs::vin behind the SL rows of K the blocks came through.  Returns C's place through Cd.
+int upload_factors(insider_hip_handle *h, double *const *A, const double *C, int K, int KPW, const int32_t *use,
+                   const double **Cd)
 {
     const DataSet &d = *h->ds;
     PostWs &w = h->post;
     hipStream_t st = h->st.stream;
     int rc;
-    if ((rc = w.Ast.grow((size_t)d.SL * KPW)) || (rc = w.U.grow((size_t)d.n * KPW)) || (rc = w.cp.grow((size_t)d.p * KPW)) ||
-        (rc = w.nz.grow(64)))
-        return rc;
-    double *Ast = w.Ast, *U = w.U, *cp = w.cp;
-    int *nz = w.nz;
-    // the host factors go through the residual stage buffer (at least p K doubles)
-    if ((rc = w.stage.grow(std::max<size_t>((size_t)d.p * K, (size_t)std::max(d.max_L, d.m) * K)))) return rc;
-    double *tmp = w.stage;
-    HIPCHECK(hipMemsetAsync(Ast, 0, (size_t)d.SL * KPW * sizeof(double), st));
+    if ((rc = w.vin.grow((size_t)(d.SL + d.p) * K)) || (rc = w.Ast.grow((size_t)d.SL * KPW))) return rc;
+    double *vin = w.vin, *Ast = w.Ast;
+    if (use) HIPCHECK(hipMemsetAsync(Ast, 0, (size_t)d.SL * KPW * sizeof(double), st));
     for (int b = 0; b < d.blocks(); ++b) {
-        if (!subtract[b]) continue;
+        if (use && !use[b]) continue;
         const DataSet::Block blk = d.block(b);
-        HIPCHECK(hipMemcpyAsync(tmp, A[b], (size_t)blk.rows * K * sizeof(double), hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_pack_A, dim3(cdiv((int64_t)blk.rows * KPW, 256)), dim3(256), 0, st, (const double *)tmp, blk.rows, K, KPW,
-                           Ast + (size_t)blk.off * KPW);
+        HIPCHECK(hipMemcpyAsync(vin + (size_t)blk.off * K, A[b], (size_t)blk.rows * K * sizeof(double), hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_pack_A, dim3(cdiv((int64_t)blk.rows * KPW, 256)), dim3(256), 0, st,
+                           (const double *)(vin + (size_t)blk.off * K), blk.rows, K, KPW, Ast + (size_t)blk.off * KPW);
         KCHECK();
-        HIPCHECK(hipStreamSynchronize(st));   // tmp is reused
     }
-    hipLaunchKernelGGL(k_build_R, dim3(cdiv(h->ds->n * KPW, 256)), dim3(256), 0, st, (const int *)h->ds->lev,
-                       (const int *)h->ds->lvl_off_d, h->ds->c, (int)h->ds->n, (const double *)Ast, KPW, (const double *)h->ds->Zc, h->ds->m,
-                       h->ds->SLcat, U);
-    KCHECK();
-    HIPCHECK(hipMemcpyAsync(tmp, C, (size_t)h->ds->p * K * sizeof(double), hipMemcpyHostToDevice, st));
-    HIPCHECK(hipMemsetAsync(nz, 0, 64 * sizeof(int), st));
-    hipLaunchKernelGGL(k_ph_pack_c, dim3(cdiv(h->ds->p * KPW, 256)), dim3(256), 0, st, (const double *)tmp, h->ds->p, K, KPW, cp, nz);
-    KCHECK();
-    HIPCHECK(hipStreamSynchronize(st));   // the stage buffer is free again
+    HIPCHECK(hipMemcpyAsync(vin + (size_t)d.SL * K, C, (size_t)d.p * K * sizeof(double), hipMemcpyHostToDevice, st));
+    *Cd = vin + (size_t)d.SL * K;
     return INSIDER_OK;
 }
 
-#define PH_DISPATCH(NBV, ...)                                                            \
-    switch (NBV) {                                                                       \
-        case 1: { constexpr int NB_ = 1; constexpr int GT_ = 8; __VA_ARGS__; } break;    \
-        case 2: { constexpr int NB_ = 2; constexpr int GT_ = 4; __VA_ARGS__; } break;    \
-        case 3: { constexpr int NB_ = 3; constexpr int GT_ = 2; __VA_ARGS__; } break;    \
-        default: { constexpr int NB_ = 4; constexpr int GT_ = 2; __VA_ARGS__; } break;   \
-    }
+// U (n x KPW) = the sum of the subtracted blocks' contributions, and C in the kernels' layout (cp, nz), enqueued on the main
+// stream
+int ph_prepare(insider_hip_handle *h, double *const *A, const double *C, int K, const int32_t *subtract, int KPW)
+{
+    const DataSet &d = *h->ds;
+    PostWs &w = h->post;
+    hipStream_t st = h->st.stream;
+    const double *Cd = nullptr;
+    int rc;
+    if ((rc = upload_factors(h, A, C, K, KPW, subtract, &Cd)) || (rc = w.U.grow((size_t)d.n * KPW)) ||
+        (rc = w.cp.grow((size_t)d.p * KPW)) || (rc = w.nz.grow(64)))
+        return rc;
+    double *U = w.U, *cp = w.cp;
+    int *nz = w.nz;
+    hipLaunchKernelGGL(k_build_R, dim3(cdiv(d.n * KPW, 256)), dim3(256), 0, st, (const int *)d.lev, (const int *)d.lvl_off_d, d.c,
+                       (int)d.n, (const double *)w.Ast, KPW, (const double *)d.Zc, d.m, d.SLcat, U);
+    KCHECK();
+    HIPCHECK(hipMemsetAsync(nz, 0, 64 * sizeof(int), st));
+    hipLaunchKernelGGL(k_ph_pack_c, dim3(cdiv(d.p * KPW, 256)), dim3(256), 0, st, Cd, d.p, K, KPW, cp, nz);
+    KCHECK();
+    return INSIDER_OK;
+}
+
+// the residual and GLM kernels' second constant: genes staged per round, by the number of K tiles
+constexpr int ph_gene_tiles(int kt) { return kt == 1 ? 8 : kt == 2 ? 4 : 2; }
 
 int residual_body(insider_hip_handle *h, double *const *A, const double *C, int inc_continuous, int K,
                   const int32_t *subtract, int64_t row_begin, int64_t row_end, double *out)
@@ -4112,9 +4167,10 @@ int residual_body(insider_hip_handle *h, double *const *A, const double *C, int 
     const int row_blocks = cdiv(cdiv(nrows, 16), PH_WPB);
     for (int64_t jb = 0; jb < h->ds->p; jb += gw) {
         const int64_t je = std::min<int64_t>(jb + gw, h->ds->p);
-        PH_DISPATCH(NB, {
-            const size_t lds = (size_t)GT_ * 4 * NB_ * 64 * sizeof(double);
-            hipLaunchKernelGGL((k_resid_write<NB_, GT_>), dim3(row_blocks, cdiv(je - jb, 16 * GT_)), dim3(64 * PH_WPB), lds,
+        KT_DISPATCH(NB, {
+            constexpr int GT_ = ph_gene_tiles(KT_);
+            const size_t lds = (size_t)GT_ * 4 * KT_ * 64 * sizeof(double);
+            hipLaunchKernelGGL((k_resid_write<KT_, GT_>), dim3(row_blocks, cdiv(je - jb, 16 * GT_)), dim3(64 * PH_WPB), lds,
                                h->st.stream, (const double *)h->ds->X, h->ds->ldn, row_begin, row_end, U, cp, K, jb, je, stage, nrows);
         });
         KCHECK();
@@ -4165,7 +4221,8 @@ int interaction_glm_body(insider_hip_handle *h, double *const *A, const double *
     const int ntiles = cdiv(n, 16), row_blocks = cdiv(ntiles, PH_WPB);
     int64_t slab_len = 0;
     int slabs = 1;
-    PH_DISPATCH(NB, {
+    KT_DISPATCH(NB, {
+        constexpr int GT_ = ph_gene_tiles(KT_);
         // enough blocks for every SIMD of the device several times over (or option "glm_slabs"), slabs of whole staging
         // rounds
         const int want = h->opt.glm_slabs > 0
@@ -4173,15 +4230,16 @@ int interaction_glm_body(insider_hip_handle *h, double *const *A, const double *
                              : std::max(1, std::min(64, cdiv(4 * h->ds->n_simd, (int64_t)row_blocks * PH_WPB)));
         slab_len = round_up(cdiv(p, want), 16 * GT_);
         slabs = cdiv(p, slab_len);
-        h->glm_form = 10 * NB_ + GT_;
+        h->glm_form = 10 * KT_ + GT_;
     });
     h->glm_slabs = slabs;
     if ((rc = w.part.grow((size_t)slabs * n * ldw)) || (rc = w.stats.grow((size_t)n * ldw))) return rc;
     double *part = w.part, *stats = w.stats;
     const double *U = w.U, *cp = w.cp;
-    PH_DISPATCH(NB, {
-        const size_t lds = (size_t)2 * GT_ * 4 * NB_ * 64 * sizeof(double);
-        hipLaunchKernelGGL((k_resid_stats<NB_, GT_>), dim3(row_blocks, slabs), dim3(64 * PH_WPB), lds, st,
+    KT_DISPATCH(NB, {
+        constexpr int GT_ = ph_gene_tiles(KT_);
+        const size_t lds = (size_t)2 * GT_ * 4 * KT_ * 64 * sizeof(double);
+        hipLaunchKernelGGL((k_resid_stats<KT_, GT_>), dim3(row_blocks, slabs), dim3(64 * PH_WPB), lds, st,
                            (const double *)h->ds->X, h->ds->ldn, (int)n, p, U, cp, K, slab_len, part);
     });
     KCHECK();
@@ -4220,11 +4278,8 @@ int interaction_glm_body(insider_hip_handle *h, double *const *A, const double *
         return rc;
     double *gpart = w.gpart, *gram = w.gram, *L = w.L, *dinv = w.dinv, *outs = w.outs;
     int *info = w.info;
-    PH_DISPATCH(NB, {
-        (void)GT_;
-        hipLaunchKernelGGL((k_mm_reduce<NB_>), dim3(gslabs, cdiv(K, 16)), dim3(64), 0, st, cp, (int64_t)KPW, cp,
-                           (int64_t)KPW, (int)p, MM_SLAB, K, K, gpart, K);
-    });
+    KT_DISPATCH(NB, hipLaunchKernelGGL((k_mm_reduce<KT_>), dim3(gslabs, cdiv(K, 16)), dim3(64), 0, st, cp, (int64_t)KPW, cp,
+                                       (int64_t)KPW, (int)p, MM_SLAB, K, K, gpart, K));
     KCHECK();
     hipLaunchKernelGGL(k_sum_partials, dim3(cdiv(K * K, 16)), dim3(256), 0, st, (const double *)gpart, gslabs, K * K, gram);
     KCHECK();
@@ -4265,48 +4320,24 @@ int ph_finish(insider_hip_handle *h, int rc)
     return rc;
 }
 
-#undef PH_DISPATCH
-
 // ---- variance / sample decomposition (kernels: insider_vardecomp.hpp, insider_sampdecomp.hpp) -------------------------
-// the argument checks both decompositions share
-int vd_check(insider_hip_handle *h, double *const *A, const double *C, int inc_continuous, int K, int entries,
-             const double *out)
-{
-    if (!h) return fail(INSIDER_ERR_ARG, "null handle");
-    const std::vector<int32_t> every((size_t)h->ds->c + 2, 1);   // every block enters the fit
-    int rc = ph_check(h, A, C, inc_continuous, K, every.data());
-    if (rc) return rc;
-    if (entries < 0 || entries > 2) return fail(INSIDER_ERR_ARG, "entries must be 0 (all), 1 (train) or 2 (test)");
-    if (!out) return fail(INSIDER_ERR_ARG, "null output");
-    return INSIDER_OK;
-}
-
-// the level table T = [A_stack; B_c] C of the nb blocks, gene-major (T[j][0..SL)), enqueued on the main stream into
+// the level table T = [A_stack; B_c] C of every block, gene-major (T[j][0..SL)), enqueued on the main stream into
 // PostWs::vtab
-int vd_build_table(insider_hip_handle *h, double *const *A, const double *C, int K, int nb)
+int vd_build_table(insider_hip_handle *h, double *const *A, const double *C, int K)
 {
     PostWs &w = h->post;
     hipStream_t st = h->st.stream;
     const int SL = h->ds->SL, KPW = 16 * ((K + 15) / 16);
     const int64_t p = h->ds->p;
+    const double *Cd = nullptr;
     int rc;
-    if ((rc = w.vin.grow((size_t)(SL + p) * K)) || (rc = w.Ast.grow((size_t)SL * KPW)) || (rc = w.vtab.grow((size_t)p * SL)))
-        return rc;
-    double *vin = w.vin, *Ast = w.Ast, *T = w.vtab;
-    // [A_stack; B_c] as SL rows of KPW (the layout of ph_prepare), C as p rows of K
-    for (int b = 0; b < nb; ++b) {
-        const DataSet::Block blk = h->ds->block(b);
-        HIPCHECK(hipMemcpyAsync(vin + (size_t)blk.off * K, A[b], (size_t)blk.rows * K * sizeof(double), hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_pack_A, dim3(cdiv((int64_t)blk.rows * KPW, 256)), dim3(256), 0, st,
-                           (const double *)(vin + (size_t)blk.off * K), blk.rows, K, KPW, Ast + (size_t)blk.off * KPW);
-        KCHECK();
-    }
-    double *Cd = vin + (size_t)SL * K;
-    HIPCHECK(hipMemcpyAsync(Cd, C, (size_t)p * K * sizeof(double), hipMemcpyHostToDevice, st));
+    if ((rc = upload_factors(h, A, C, K, KPW, nullptr, &Cd)) || (rc = w.vtab.grow((size_t)p * SL))) return rc;
+    const double *Ast = w.Ast;
+    double *T = w.vtab;
     // T[j][s] = sum_k Ast[s][k] C[k][j]: gene-major, one gene's table contiguous
 #define VT_LAUNCH(NT_)                                                                                                      \
     hipLaunchKernelGGL((k_mm_rows<NT_, true>), dim3(cdiv(cdiv((int)p, 16), 4), cdiv(SL, 16 * NT_)), dim3(256), 0, st,         \
-                       (const double *)Cd, (int64_t)K, (int)p, K, (const double *)Ast, KPW, SL, T, (int64_t)SL, SL)
+                       Cd, (int64_t)K, (int)p, K, Ast, KPW, SL, T, (int64_t)SL, SL)
     if (SL <= 16) VT_LAUNCH(1);
     else if (SL <= 32) VT_LAUNCH(2);
     else VT_LAUNCH(4);
@@ -4318,20 +4349,19 @@ int vd_build_table(insider_hip_handle *h, double *const *A, const double *C, int
 int variance_decomposition_body(insider_hip_handle *h, double *const *A, const double *C, int inc_continuous, int K,
                                 int entries, double *out)
 {
-    int rc = vd_check(h, A, C, inc_continuous, K, entries, out);
+    int rc = fit_check(h, A, C, inc_continuous, K, entries);
     if (rc) return rc;
+    if (!out) return fail(INSIDER_ERR_ARG, "null output");
     HIPCHECK(hipSetDevice(h->ds->device));
     PostWs &w = h->post;
     hipStream_t st = h->st.stream;
     const int nb = h->ds->c + inc_continuous, SL = h->ds->SL, rec = 4 + 3 * nb;
     const int64_t n = h->ds->n, p = h->ds->p;
-    if ((rc = vd_build_table(h, A, C, K, nb)) || (rc = w.vrec.grow((size_t)p * rec))) return rc;
+    if ((rc = vd_build_table(h, A, C, K)) || (rc = w.vrec.grow((size_t)p * rec))) return rc;
     double *T = w.vtab, *R = w.vrec;
     // one pass over X per window of BW blocks
-    const int sel = entries == 0 ? 0 : entries == 1 ? CODE_TRAIN : CODE_TEST;
-    const int m = inc_continuous ? h->ds->m : 0;
-    // (at most 60 KiB of dynamic LDS beside the kernel's static reduction buffer: no launch attribute needed)
-    const double budget = std::min(std::max(h->opt.vd_stage_kb, 0.0), 60.0) * 1024.0;
+    const int sel = entry_code(entries), m = ctns_cols(*h->ds, inc_continuous);
+    const double budget = table_lds_budget(h);
 #define VD_LAUNCH(BW_, GW_)                                                                                                 \
     do {                                                                                                                     \
         const bool staged = (double)GW_ * SL * sizeof(double) <= budget;                                                     \
@@ -4365,29 +4395,28 @@ int variance_decomposition_body(insider_hip_handle *h, double *const *A, const d
 int sample_decomposition_body(insider_hip_handle *h, double *const *A, const double *C, int inc_continuous, int K,
                               int entries, double *out)
 {
-    int rc = vd_check(h, A, C, inc_continuous, K, entries, out);
+    int rc = fit_check(h, A, C, inc_continuous, K, entries);
     if (rc) return rc;
+    if (!out) return fail(INSIDER_ERR_ARG, "null output");
     HIPCHECK(hipSetDevice(h->ds->device));
     PostWs &w = h->post;
     hipStream_t st = h->st.stream;
     const int nb = h->ds->c + inc_continuous, SL = h->ds->SL, rec = 4 + 3 * nb;
     const int64_t n = h->ds->n, p = h->ds->p;
-    // gene slabs: from n, p, the device's compute units and option "sd_slabs" alone.  Automatic: eight blocks per compute
-    // unit (a block is SD_WAVES waves; three are resident per unit at 130 - 170 registers), at most 256 slabs
+    // gene slabs: from n, p, the device's compute units and option "sd_slabs" alone (gene_slabs; a block is SD_WAVES waves,
+    // three are resident per unit at 130 - 170 registers)
     const int tiles = cdiv(n, SD_TILE);
-    const int want = h->opt.sd_slabs > 0 ? h->opt.sd_slabs : cdiv(2 * h->ds->n_simd, tiles);
-    const int64_t slab_len = cdiv(p, (int64_t)std::max(1, std::min(want, 256)));
-    const int slabs = (int)cdiv(p, slab_len);
+    int64_t slab_len = 0;
+    const int slabs = gene_slabs(h, h->opt.sd_slabs, tiles, 0.0, &slab_len);
     const int BW = nb == 1 ? 1 : nb == 2 ? 2 : 4, RW = 4 + 3 * BW;
-    if ((rc = vd_build_table(h, A, C, K, nb)) || (rc = w.spart.grow((size_t)slabs * n * RW)) ||
+    if ((rc = vd_build_table(h, A, C, K)) || (rc = w.spart.grow((size_t)slabs * n * RW)) ||
         (rc = w.srec.grow((size_t)n * rec)))
         return rc;
     double *T = w.vtab, *part = w.spart, *R = w.srec;
-    const int sel = entries == 0 ? 0 : entries == 1 ? CODE_TRAIN : CODE_TEST;
-    const int m = inc_continuous ? h->ds->m : 0;
-    // tables staged in groups of whole load steps of SD_GU genes, as many as the budget of "vd_stage_kb" holds (at most 60 KiB
-    // of dynamic LDS and no static LDS: no launch attribute needed); when not even one step's tables fit: the global form
-    const double budget = std::min(std::max(h->opt.vd_stage_kb, 0.0), 60.0) * 1024.0;
+    const int sel = entry_code(entries), m = ctns_cols(*h->ds, inc_continuous);
+    // tables staged in groups of whole load steps of SD_GU genes, as many as table_lds_budget holds; when not even one step's
+    // tables fit: the global form
+    const double budget = table_lds_budget(h);
     const int fit = (int)std::min<double>(budget / ((double)SL * sizeof(double)), SD_GROUP_MAX) / SD_GU * SD_GU;
     const bool staged = fit >= SD_GU;
     const int gg = staged ? fit : (int)std::min<int64_t>(slab_len, INT32_MAX);
@@ -4427,9 +4456,9 @@ int sample_decomposition_body(insider_hip_handle *h, double *const *A, const dou
 int level_scores_body(insider_hip_handle *h, double *const *A, const double *C, int inc_continuous, int K, int entries,
                       int cov, const double *cand, int n_cand, double *sse, double *cnt)
 {
-    int rc = vd_check(h, A, C, inc_continuous, K, entries, sse);
+    int rc = fit_check(h, A, C, inc_continuous, K, entries);
     if (rc) return rc;
-    if (!cnt) return fail(INSIDER_ERR_ARG, "null output");
+    if (!sse || !cnt) return fail(INSIDER_ERR_ARG, "null output");
     const DataSet &d = *h->ds;
     if (cov < 0 || cov >= d.c) return fail(INSIDER_ERR_ARG, "cov must be a categorical covariate block in 0..c-1");
     if (cand && n_cand < 1) return fail(INSIDER_ERR_ARG, "n_cand must be positive when candidates are given");
@@ -4445,16 +4474,10 @@ int level_scores_body(insider_hip_handle *h, double *const *A, const double *C, 
     sub[cov] = 0;
     if ((rc = ph_prepare(h, A, C, K, sub.data(), KPW))) return rc;
     const int ldt = (int)round_up(L, 16), ltiles = ldt / 16, nwin = cdiv(ltiles, LS_QT);
-    // gene slabs: the rule of "sd_slabs" (eight blocks per compute unit, at most 256), and, when automatic, no more than keep
-    // the partial scores within "ls_part_mb"
+    // gene slabs (gene_slabs, option "ls_slabs"): when automatic, no more than keep the partial scores within "ls_part_mb"
     const int tiles = cdiv(n, LS_TILE);
-    int want = h->opt.ls_slabs;
-    if (want <= 0) {
-        const double cap = std::max(h->opt.ls_part_mb, 0.0) * 1048576.0 / ((double)n * ldt * sizeof(double));
-        want = (int)std::min<double>(cdiv(2 * h->ds->n_simd, tiles), std::max(cap, 1.0));
-    }
-    const int64_t slab_len = cdiv(p, (int64_t)std::max(1, std::min(want, 256)));
-    const int slabs = (int)cdiv(p, slab_len);
+    int64_t slab_len = 0;
+    const int slabs = gene_slabs(h, h->opt.ls_slabs, tiles, (double)n * ldt * sizeof(double), &slab_len);
     if ((rc = w.stage.grow((size_t)L * K)) || (rc = w.lcand.grow((size_t)L * KPW)) || (rc = w.ltab.grow((size_t)p * ldt)) ||
         (rc = w.lpart.grow((size_t)slabs * n * ldt)) || (rc = w.lcnt.grow((size_t)slabs * n)) ||
         (rc = w.lout.grow((size_t)n * L + n)))
@@ -4473,26 +4496,18 @@ int level_scores_body(insider_hip_handle *h, double *const *A, const double *C, 
     else LT_LAUNCH(4);
 #undef LT_LAUNCH
     KCHECK();
-    const int sel = entries == 0 ? 0 : entries == 1 ? CODE_TRAIN : CODE_TEST;
+    const int sel = entry_code(entries);
     h->ls_path = nwin == 1 ? 1 : 2;
     h->ls_slabs = slabs;
-#define LS_LAUNCH(QT_, KS_)                                                                                                 \
-    hipLaunchKernelGGL((k_ls_prod<QT_, KS_>), dim3(tiles, slabs, cdiv(ltiles, QT_)), dim3(64 * LS_WAVES),                    \
-                       ls_lds_bytes(QT_, KS_), st, (const double *)d.X, (const uint8_t *)d.codes, d.ldn, (int)n, p, U, cp, K, \
-                       (const double *)Tc, ldt, sel, slab_len, part, cpart)
-#define LS_LAUNCH_KS(QT_)                                                                                                   \
-    switch (KS) {                                                                                                            \
-        case 1: LS_LAUNCH(QT_, 1); break;                                                                                    \
-        case 2: LS_LAUNCH(QT_, 2); break;                                                                                    \
-        case 3: LS_LAUNCH(QT_, 3); break;                                                                                    \
-        default: LS_LAUNCH(QT_, 4); break;                                                                                   \
-    }
+#define LS_LAUNCH(QT_)                                                                                                      \
+    KT_DISPATCH(KS, hipLaunchKernelGGL((k_ls_prod<QT_, KT_>), dim3(tiles, slabs, cdiv(ltiles, QT_)), dim3(64 * LS_WAVES),     \
+                                       ls_lds_bytes(QT_, KT_), st, (const double *)d.X, (const uint8_t *)d.codes, d.ldn,     \
+                                       (int)n, p, U, cp, K, (const double *)Tc, ldt, sel, slab_len, part, cpart))
     // one level tile: 84 - 102 registers; else the window form of LS_QT tiles: 196 - 215 (tools/kernel_regs.sh), no scratch, two
     // waves per SIMD; tiles beyond the live ones of a window are skipped by a uniform branch.  (Forms of 2 and 4 tiles were
     // dropped: the 4-tile one compiled to 446 - 468 registers, one wave per SIMD.)
-    if (ltiles <= 1) { LS_LAUNCH_KS(1) }
-    else { LS_LAUNCH_KS(LS_QT) }
-#undef LS_LAUNCH_KS
+    if (ltiles <= 1) { LS_LAUNCH(1) }
+    else { LS_LAUNCH(LS_QT) }
 #undef LS_LAUNCH
     KCHECK();
     hipLaunchKernelGGL(k_ls_reduce, dim3(cdiv(n * ldt, 256)), dim3(256), 0, st, (const double *)part, (const double *)cpart,
@@ -4514,38 +4529,30 @@ constexpr int FD_QT = 8;   // tiles of 16 columns per window at most (64 accumul
 int factor_decomposition_body(insider_hip_handle *h, double *const *A, const double *C, int inc_continuous, int K,
                               int entries, double *out)
 {
-    int rc = vd_check(h, A, C, inc_continuous, K, entries, out);
+    int rc = fit_check(h, A, C, inc_continuous, K, entries);
     if (rc) return rc;
+    if (!out) return fail(INSIDER_ERR_ARG, "null output");
     HIPCHECK(hipSetDevice(h->ds->device));
     PostWs &w = h->post;
     hipStream_t st = h->st.stream;
     const DataSet &d = *h->ds;
-    const int nb = d.c + inc_continuous, SL = d.SL, KPW = 16 * ((K + 15) / 16), KS = KPW / 16;
+    const int nb = d.c + inc_continuous, KPW = 16 * ((K + 15) / 16), KS = KPW / 16;
     const int rec = 4 + 3 * (nb + 1) * K;
     const int64_t n = d.n, p = d.p;
     const int ldq = (int)round_up((int64_t)(nb + 1) * K, 16), ldw = 2 * ldq, ldp = 3 * ldq;
     const int64_t rows = round_up(n, FD_CHUNK);
-    if ((rc = w.vin.grow((size_t)(SL + p) * K)) || (rc = w.Ast.grow((size_t)SL * KPW)) ||
-        (rc = w.fwall.grow((size_t)rows * ldw)) || (rc = w.fprod.grow((size_t)p * ldp)) || (rc = w.fbase.grow((size_t)p * 4)) ||
-        (rc = w.frec.grow((size_t)p * rec)))
+    const double *Cd = nullptr;
+    if ((rc = upload_factors(h, A, C, K, KPW, nullptr, &Cd)) || (rc = w.fwall.grow((size_t)rows * ldw)) ||
+        (rc = w.fprod.grow((size_t)p * ldp)) || (rc = w.fbase.grow((size_t)p * 4)) || (rc = w.frec.grow((size_t)p * rec)))
         return rc;
-    double *vin = w.vin, *Ast = w.Ast, *Wall = w.fwall, *P = w.fprod, *base = w.fbase, *R = w.frec;
-    // [A_stack; B_c] as SL rows of KPW, C as p rows of K (the layout of vd_build_table)
-    for (int b = 0; b < nb; ++b) {
-        const DataSet::Block blk = d.block(b);
-        HIPCHECK(hipMemcpyAsync(vin + (size_t)blk.off * K, A[b], (size_t)blk.rows * K * sizeof(double), hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_pack_A, dim3(cdiv((int64_t)blk.rows * KPW, 256)), dim3(256), 0, st,
-                           (const double *)(vin + (size_t)blk.off * K), blk.rows, K, KPW, Ast + (size_t)blk.off * KPW);
-        KCHECK();
-    }
-    double *Cd = vin + (size_t)SL * K;
-    HIPCHECK(hipMemcpyAsync(Cd, C, (size_t)p * K * sizeof(double), hipMemcpyHostToDevice, st));
-    const int m = inc_continuous ? d.m : 0;
+    const double *Ast = w.Ast;
+    double *Wall = w.fwall, *P = w.fprod, *base = w.fbase, *R = w.frec;
+    const int m = ctns_cols(d, inc_continuous);
     HIPCHECK(hipMemsetAsync(Wall, 0, (size_t)rows * ldw * sizeof(double), st));
     hipLaunchKernelGGL(k_fd_build_w, dim3(cdiv(n * K, 256)), dim3(256), 0, st, (const int *)d.lev, (const int *)d.lvl_off_d, d.c,
-                       (int)n, (const double *)Ast, KPW, (const double *)d.Zc, m, d.SLcat, K, ldq, Wall);
+                       (int)n, Ast, KPW, (const double *)d.Zc, m, d.SLcat, K, ldq, Wall);
     KCHECK();
-    const int sel = entries == 0 ? 0 : entries == 1 ? CODE_TRAIN : CODE_TEST;
+    const int sel = entry_code(entries);
     const int heavy_tiles = cdiv(nb * K, 16), light_tiles = ldw / 16;
     h->fd_path = heavy_tiles <= FD_QT ? 1 : 2;
     const dim3 grid((unsigned)cdiv(p, (int64_t)FD_GENES)), block(64 * FD_WAVES);
@@ -4556,31 +4563,23 @@ int factor_decomposition_body(insider_hip_handle *h, double *const *A, const dou
         for (int t0 = 0; t0 < heavy_tiles; t0 += QT_) {                                                                      \
             hipLaunchKernelGGL((k_fd_prod<QT_, KS_, true>), grid, block, lw + lr, st, (const double *)d.X,                   \
                                (const uint8_t *)d.codes, d.ldn, (int)n, p, (const double *)Wall, ldw, 16 * t0,               \
-                               std::min(QT_, heavy_tiles - t0), nb * K, (const double *)Cd, K, sel, P, ldp, 16 * t0, base);  \
+                               std::min(QT_, heavy_tiles - t0), nb * K, Cd, K, sel, P, ldp, 16 * t0, base);                  \
             KCHECK();                                                                                                        \
         }                                                                                                                    \
         for (int t0 = 0; t0 < light_tiles; t0 += QT_) {                                                                      \
             hipLaunchKernelGGL((k_fd_prod<QT_, 1, false>), grid, block, lw, st, (const double *)d.X,                         \
                                (const uint8_t *)d.codes, d.ldn, (int)n, p, (const double *)Wall, ldw, 16 * t0,               \
-                               std::min(QT_, light_tiles - t0), 0, (const double *)Cd, K, sel, P, ldp, ldq + 16 * t0,        \
+                               std::min(QT_, light_tiles - t0), 0, Cd, K, sel, P, ldp, ldq + 16 * t0,                        \
                                (double *)nullptr);                                                                           \
             KCHECK();                                                                                                        \
         }                                                                                                                    \
     } while (0)
-#define FD_LAUNCH_KS(QT_)                                                                                                   \
-    switch (KS) {                                                                                                            \
-        case 1: FD_LAUNCH(QT_, 1); break;                                                                                    \
-        case 2: FD_LAUNCH(QT_, 2); break;                                                                                    \
-        case 3: FD_LAUNCH(QT_, 3); break;                                                                                    \
-        default: FD_LAUNCH(QT_, 4); break;                                                                                   \
-    }
     // one window width for every shape: the form with 8 tiles needs 132 - 157 registers (three blocks per compute unit); tiles
     // beyond the live ones of a window are skipped by a uniform branch
-    FD_LAUNCH_KS(FD_QT)
-#undef FD_LAUNCH_KS
+    KT_DISPATCH(KS, FD_LAUNCH(FD_QT, KT_));
 #undef FD_LAUNCH
     hipLaunchKernelGGL(k_fd_finish, dim3(cdiv(p * K, 256)), dim3(256), 0, st, (const double *)P, ldq, (const double *)base,
-                       (const double *)Cd, p, K, nb, R);
+                       Cd, p, K, nb, R);
     KCHECK();
     HIPCHECK(hipMemcpyAsync(out, R, (size_t)p * rec * sizeof(double), hipMemcpyDeviceToHost, st));
     HIPCHECK(hipStreamSynchronize(st));
@@ -4596,11 +4595,8 @@ int residual_products_body(insider_hip_handle *h, double *const *A, const double
                            const double *center, const double *scale, const double *Q, int q, double *Z, double *Y,
                            double *rss)
 {
-    if (!h) return fail(INSIDER_ERR_ARG, "null handle");
-    const std::vector<int32_t> every((size_t)h->ds->c + 2, 1);   // every block enters the fit
-    int rc = ph_check(h, A, C, inc_continuous, K, every.data());
+    int rc = fit_check(h, A, C, inc_continuous, K, entries);
     if (rc) return rc;
-    if (entries < 0 || entries > 2) return fail(INSIDER_ERR_ARG, "entries must be 0 (all), 1 (train) or 2 (test)");
     if (!Q || !Z) return fail(INSIDER_ERR_ARG, "null Q or Z");
     if (q < 1 || q > 64) return fail(INSIDER_ERR_ARG, "q must be in 1..64");
     const DataSet &d = *h->ds;
@@ -4611,18 +4607,14 @@ int residual_products_body(insider_hip_handle *h, double *const *A, const double
     PostWs &w = h->post;
     hipStream_t st = h->st.stream;
     const int KS = (K + 15) / 16, KPW = 16 * KS;
+    const std::vector<int32_t> every((size_t)d.c + 2, 1);   // every block enters the fit
     if ((rc = ph_prepare(h, A, C, K, every.data(), KPW))) return rc;
     const int QT = (q + 15) / 16, ldq = 16 * QT;
-    // gene slabs of the forward pass: the rule of "ls_slabs" (eight blocks per compute unit, at most 256) and, when automatic, no
-    // more than keep the partial Y within "ls_part_mb"
+    // gene slabs of the forward pass (gene_slabs, option "rc_slabs"): when automatic, no more than keep the partial Y within
+    // "ls_part_mb"
     const int tiles = cdiv(n, RC_TILE);
-    int want = h->opt.rc_slabs;
-    if (want <= 0) {
-        const double cap = std::max(h->opt.ls_part_mb, 0.0) * 1048576.0 / ((double)n * ldq * sizeof(double));
-        want = (int)std::min<double>(cdiv(2 * d.n_simd, tiles), std::max(cap, 1.0));
-    }
-    const int64_t slab_len = cdiv(p, (int64_t)std::max(1, std::min(want, 256)));
-    const int slabs = Y ? (int)cdiv(p, slab_len) : 0;
+    int64_t slab_len = 0;
+    const int slabs = Y ? gene_slabs(h, h->opt.rc_slabs, tiles, (double)n * ldq * sizeof(double), &slab_len) : 0;
     const size_t n_in = (size_t)n * q + 2 * (size_t)p, n_out = (size_t)p * q + (size_t)n * q + (size_t)p;
     if ((rc = w.rin.grow(n_in)) || (rc = w.rq.grow((size_t)n * ldq)) || (rc = w.rcs.grow((size_t)2 * p)) ||
         (rc = w.rz.grow((size_t)p * ldq)) || (rc = w.rpart.grow((size_t)std::max(slabs, 1) * n * ldq)) ||
@@ -4640,11 +4632,9 @@ int residual_products_body(insider_hip_handle *h, double *const *A, const double
     hipLaunchKernelGGL(k_rc_center_scale, dim3(cdiv(p, 256)), dim3(256), 0, st, (const double *)(center ? c_in : nullptr),
                        (const double *)(scale ? s_in : nullptr), p, cs);
     KCHECK();
-    const int sel = entries == 0 ? 0 : entries == 1 ? CODE_TRAIN : CODE_TEST;
-    Event e0, e1;
-    HIPCHECK(hipEventCreate(e0.out()));
-    HIPCHECK(hipEventCreate(e1.out()));
-    HIPCHECK(hipEventRecord(e0, st));
+    const int sel = entry_code(entries);
+    Stopwatch watch;
+    if ((rc = watch.start(st))) return rc;
 #define RC_LAUNCH(QT_, KS_)                                                                                                 \
     do {                                                                                                                     \
         hipLaunchKernelGGL((k_rc_back<QT_, KS_>), dim3((unsigned)cdiv(p, (int64_t)RC_GENES)), dim3(64 * RC_WAVES),           \
@@ -4658,32 +4648,24 @@ int residual_products_body(insider_hip_handle *h, double *const *A, const double
             KCHECK();                                                                                                        \
         }                                                                                                                    \
     } while (0)
-#define RC_LAUNCH_KS(QT_)                                                                                                   \
-    switch (KS) {                                                                                                            \
-        case 1: RC_LAUNCH(QT_, 1); break;                                                                                    \
-        case 2: RC_LAUNCH(QT_, 2); break;                                                                                    \
-        case 3: RC_LAUNCH(QT_, 3); break;                                                                                    \
-        default: RC_LAUNCH(QT_, 4); break;                                                                                   \
-    }
     // one form per number of column tiles of Q and of K: registers per form in DESIGN (tools/kernel_regs.sh), no scratch
     switch (QT) {
-        case 1: RC_LAUNCH_KS(1) break;
-        case 2: RC_LAUNCH_KS(2) break;
-        case 3: RC_LAUNCH_KS(3) break;
-        default: RC_LAUNCH_KS(4) break;
+        case 1: KT_DISPATCH(KS, RC_LAUNCH(1, KT_)) break;
+        case 2: KT_DISPATCH(KS, RC_LAUNCH(2, KT_)) break;
+        case 3: KT_DISPATCH(KS, RC_LAUNCH(3, KT_)) break;
+        default: KT_DISPATCH(KS, RC_LAUNCH(4, KT_)) break;
     }
-#undef RC_LAUNCH_KS
 #undef RC_LAUNCH
     if (Y) {
         hipLaunchKernelGGL(k_rc_reduce, dim3(cdiv(n * ldq, 256)), dim3(256), 0, st, (const double *)part, slabs, n, ldq, q, y_out);
         KCHECK();
     }
-    HIPCHECK(hipEventRecord(e1, st));
+    if ((rc = watch.mark(st))) return rc;
     hipLaunchKernelGGL(k_rc_unpack, dim3(cdiv(p * q, 256)), dim3(256), 0, st, (const double *)Zd, p, q, ldq, z_out);
     KCHECK();
     HIPCHECK(hipStreamSynchronize(st));   // the caller's arrays are written only after the kernels ran
     float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, e0, e1);
+    if ((rc = watch.stop_ms(st, &ms))) return rc;
     h->rc_ms = ms;
     h->rc_slabs = slabs;
     HIPCHECK(hipMemcpyAsync(Z, z_out, (size_t)p * q * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -4700,11 +4682,8 @@ int outliers_body(insider_hip_handle *h, double *const *A, const double *C, int 
                   const double *center, const double *scale, double threshold, int64_t cap, int32_t *rows, int32_t *cols,
                   double *z, int64_t *total, int32_t *gene_counts, int32_t *sample_counts)
 {
-    if (!h) return fail(INSIDER_ERR_ARG, "null handle");
-    const std::vector<int32_t> every((size_t)h->ds->c + 2, 1);   // every block enters the fit
-    int rc = ph_check(h, A, C, inc_continuous, K, every.data());
+    int rc = fit_check(h, A, C, inc_continuous, K, entries);
     if (rc) return rc;
-    if (entries < 0 || entries > 2) return fail(INSIDER_ERR_ARG, "entries must be 0 (all), 1 (train) or 2 (test)");
     if (!scale) return fail(INSIDER_ERR_ARG, "null scale");
     if (!total) return fail(INSIDER_ERR_ARG, "null total");
     if (!(threshold > 0.0) || !std::isfinite(threshold)) return fail(INSIDER_ERR_ARG, "threshold must be finite and > 0");
@@ -4714,9 +4693,9 @@ int outliers_body(insider_hip_handle *h, double *const *A, const double *C, int 
     PostWs &w = h->post;
     hipStream_t st = h->st.stream;
     const DataSet &d = *h->ds;
-    const int nb = d.c + inc_continuous, SL = d.SL;
+    const int SL = d.SL;
     const int64_t n = d.n, p = d.p, wpl = d.ldn / 32;
-    if ((rc = vd_build_table(h, A, C, K, nb)) || (rc = w.ocs.grow((size_t)2 * p)) || (rc = w.obits.grow((size_t)p * wpl)) ||
+    if ((rc = vd_build_table(h, A, C, K)) || (rc = w.ocs.grow((size_t)2 * p)) || (rc = w.obits.grow((size_t)p * wpl)) ||
         (rc = w.ogcnt.grow((size_t)2 * p)) || (rc = w.oscnt.grow((size_t)2 * n)) || (rc = w.ooffs.grow((size_t)p + 1)))
         return rc;
     const double *T = w.vtab;
@@ -4724,11 +4703,8 @@ int outliers_body(insider_hip_handle *h, double *const *A, const double *C, int 
     if (center) HIPCHECK(hipMemcpyAsync(d_center, center, (size_t)p * sizeof(double), hipMemcpyHostToDevice, st));
     HIPCHECK(hipMemcpyAsync(d_scale, scale, (size_t)p * sizeof(double), hipMemcpyHostToDevice, st));
     HIPCHECK(hipMemsetAsync(w.oscnt, 0, (size_t)2 * n * sizeof(int), st));
-    const int sel = entries == 0 ? 0 : entries == 1 ? CODE_TRAIN : CODE_TEST;
-    const int m = inc_continuous ? d.m : 0;
-    // (at most 60 KiB of dynamic LDS beside the kernel's static count buffer: no launch attribute needed)
-    const double budget = std::min(std::max(h->opt.vd_stage_kb, 0.0), 60.0) * 1024.0;
-    const bool staged = (double)OL_GW * SL * sizeof(double) <= budget;
+    const int sel = entry_code(entries), m = ctns_cols(d, inc_continuous);
+    const bool staged = (double)OL_GW * SL * sizeof(double) <= table_lds_budget(h);
     h->ol_path = staged ? 1 : 2;
     // four genes per block: 132 VGPRs staged, 113 from global (tools/kernel_regs.sh), no scratch: three / four waves per SIMD
     if (staged)

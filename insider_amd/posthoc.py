@@ -92,6 +92,13 @@ def t_pvalues(coeff, se, dof):
     return pval
 
 
+def _fitted(obj, which):
+    """What every call on a fitted ``Insider`` object starts from: its resident data set ``which`` ("fit" or "tune"), the
+    list of its row factors, its column factor and its inc_continuous flag."""
+    from . import api
+    return api._resident(obj, which), list(obj["cfd_matrices"].values()), obj["column_factor"], int(obj["inc_continuous"])
+
+
 def glm_interaction_resident(obj, group_cov, subtract=None):
     """glm_interaction() of a fitted ``Insider`` object (api.insider + api.fit) on the device: the interaction levels are
     column ``group_cov`` (0-based) of obj["confounder"] (insider(interaction_idx=...) puts its indicator in column 1), the
@@ -170,10 +177,8 @@ def variance_decomposition(obj, which="fit", entries="train"):
     ratio_splitter split, so entries="test" gives each gene's held-out error).  Blocks: the columns of obj["confounder"],
     then the continuous block.  -> vd_derived() of the raw sums: n, sum_x, sum_xx, rss (p), sum_g, sum_gg, sum_rg (B x p),
     tss, r2, rmse (p), explained, drop_one (B x p)."""
-    from . import api
-    ds = api._resident(obj, which)
-    rec = ds.variance_decomposition(list(obj["cfd_matrices"].values()), obj["column_factor"], entries=entries,
-                                    inc_continuous=int(obj["inc_continuous"]))
+    ds, cfd, col, inc = _fitted(obj, which)
+    rec = ds.variance_decomposition(cfd, col, entries=entries, inc_continuous=inc)
     return vd_derived(rec)
 
 
@@ -188,10 +193,8 @@ def sample_decomposition(obj, which="fit", entries="train"):
     """Per-sample fit diagnostics of a fitted ``Insider`` object on the device: variance_decomposition() along the other
     axis, with the same ``which`` / ``entries``.  -> vd_derived() of the raw sums: n, sum_x, sum_xx, rss, tss, r2, rmse (n),
     sum_g, sum_gg, sum_rg, explained, drop_one (B x n).  A sample's tss is its spread across genes."""
-    from . import api
-    ds = api._resident(obj, which)
-    rec = ds.sample_decomposition(list(obj["cfd_matrices"].values()), obj["column_factor"], entries=entries,
-                                  inc_continuous=int(obj["inc_continuous"]))
+    ds, cfd, col, inc = _fitted(obj, which)
+    rec = ds.sample_decomposition(cfd, col, entries=entries, inc_continuous=inc)
     return vd_derived(rec)
 
 
@@ -287,10 +290,8 @@ def factor_decomposition(obj, which="fit", entries="train"):
     """Per-factor decomposition of a fitted ``Insider`` object on the device, with the ``which`` / ``entries`` of
     variance_decomposition().  -> fd_derived() of the raw sums: n, sum_x, sum_xx, rss, tss, r2, rmse (p), sum_h, sum_hh,
     sum_rh, explained, drop_one ((B + 1) x K x p; the last block is the total)."""
-    from . import api
-    ds = api._resident(obj, which)
-    rec = ds.factor_decomposition(list(obj["cfd_matrices"].values()), obj["column_factor"], entries=entries,
-                                  inc_continuous=int(obj["inc_continuous"]))
+    ds, cfd, col, inc = _fitted(obj, which)
+    rec = ds.factor_decomposition(cfd, col, entries=entries, inc_continuous=inc)
     return fd_derived(rec)
 
 
@@ -371,10 +372,8 @@ def level_scores(obj, cov, which="fit", entries="train", candidates=None):
     A sample's own level was fitted WITH that sample: on which="fit" / entries="train" the assigned level is favoured, most
     for levels with few samples (a level with one sample fits itself); which="tune", entries="test" scores on held-out
     entries no embedding has seen.  Nothing is reported or corrected for it."""
-    from . import api
-    ds = api._resident(obj, which)
-    rec = ds.level_scores(list(obj["cfd_matrices"].values()), obj["column_factor"], int(cov), entries=entries,
-                          candidates=candidates, inc_continuous=int(obj["inc_continuous"]))
+    ds, cfd, col, inc = _fitted(obj, which)
+    rec = ds.level_scores(cfd, col, int(cov), entries=entries, candidates=candidates, inc_continuous=inc)
     return ls_derived(rec, None if candidates is not None else np.asarray(obj["confounder"])[:, int(cov)])
 
 
@@ -428,16 +427,12 @@ def outliers(obj, which="fit", entries="train", threshold=3.0, center=None, scal
     first and residual_center_scale() supplies each gene's residual mean and standard deviation.  -> the dict of
     InsiderData.outliers() (rows, cols, z, total, gene_low, gene_high, sample_low, sample_high) plus the ``center`` and
     ``scale`` that were used."""
-    from . import api
-    ds = api._resident(obj, which)
-    cfd, inc = list(obj["cfd_matrices"].values()), int(obj["inc_continuous"])
+    ds, cfd, col, inc = _fitted(obj, which)
     if center is None or scale is None:
-        ce, sc = residual_center_scale(ds.variance_decomposition(cfd, obj["column_factor"], entries=entries,
-                                                                 inc_continuous=inc))
+        ce, sc = residual_center_scale(ds.variance_decomposition(cfd, col, entries=entries, inc_continuous=inc))
         center = ce if center is None else center
         scale = sc if scale is None else scale
-    out = ds.outliers(cfd, obj["column_factor"], scale, center=center, threshold=threshold, entries=entries,
-                      inc_continuous=inc, cap=cap)
+    out = ds.outliers(cfd, col, scale, center=center, threshold=threshold, entries=entries, inc_continuous=inc, cap=cap)
     out["center"], out["scale"] = np.asarray(center, dtype=np.float64), np.asarray(scale, dtype=np.float64)
     return out
 
@@ -587,10 +582,8 @@ def residual_components(obj, r=5, which="fit", entries="train", standardize=Fals
     _rc_check(r, oversample, max_iter, tol, seed)
     if entries not in ("all", "train", "test"):
         raise ValueError(f"entries must be one of ['all', 'test', 'train'], got {entries!r}")
-    from . import api
-    ds = api._resident(obj, which)
-    return residual_components_resident(ds, list(obj["cfd_matrices"].values()), obj["column_factor"],
-                                        int(obj["inc_continuous"]), r, entries, standardize, oversample, max_iter, tol, seed)
+    ds, cfd, col, inc = _fitted(obj, which)
+    return residual_components_resident(ds, cfd, col, inc, r, entries, standardize, oversample, max_iter, tol, seed)
 
 
 def component_associations(sample_scores, levels, ctns=None):

@@ -21,7 +21,7 @@ pytestmark = pytest.mark.gpu
 
 LD = np.longdouble
 COUNTS = (5, 3)
-GT_OF_NB = {1: 8, 2: 4, 3: 2, 4: 2}          # PH_DISPATCH in insider_hip.hip
+GT_OF_NB = {1: 8, 2: 4, 3: 2, 4: 2}          # ph_gene_tiles in insider_hip.hip
 WORST = {}                                   # test label -> (coeff ratio, se^2 ratio), the largest seen
 
 

@@ -139,3 +139,60 @@ def test_glm_option_and_info_keys_are_declared():
     for key in ("glm_slabs", "glm_form"):
         assert f'"{key}"' in hdr and f's == "{key}"' in src, key
     assert src.count('s == "glm_slabs"') == 2                 # an option and an info key
+
+
+_FIT_CALLS = {
+    "variance_decomposition": lambda ds, A, Cm, kw: ds.variance_decomposition(A, Cm, **kw),
+    "sample_decomposition": lambda ds, A, Cm, kw: ds.sample_decomposition(A, Cm, **kw),
+    "level_scores": lambda ds, A, Cm, kw: ds.level_scores(A, Cm, 99, **kw),                          # (cov is bad as well)
+    "factor_decomposition": lambda ds, A, Cm, kw: ds.factor_decomposition(A, Cm, **kw),
+    "residual_products": lambda ds, A, Cm, kw: ds.residual_products(A, Cm, np.ones((19, 2)), **kw),  # (so is Q)
+    "outliers": lambda ds, A, Cm, kw: ds.outliers(A, Cm, None, cap=-1, **kw),                        # (so are scale and cap)
+}
+
+
+@pytest.mark.parametrize("name", sorted(_FIT_CALLS))
+def test_calls_on_a_fit_report_entries_first_then_inc_continuous(name, monkeypatch):
+    """The order of the shared checks: a bad ``entries`` wins over a bad ``inc_continuous``, which wins over the call's own
+    arguments and over factors of the wrong shape; nothing reaches the library."""
+    def no_library():
+        raise AssertionError("the library was touched")
+
+    monkeypatch.setattr(_lib, "load", no_library)
+    ds = _fake()
+    K = 4
+    A = [np.zeros((3, K), order="F"), np.zeros((2, K + 1), order="F")]   # (the second block's K is wrong)
+    Cm = np.ones((K, 12), order="F")
+    call = _FIT_CALLS[name]
+    with pytest.raises(_lib.InsiderError) as e:
+        call(ds, A, Cm, dict(entries="held-out", inc_continuous=2))
+    assert e.value.status == _lib.ERR_ARG and "entries must be one of ['all', 'test', 'train'], got 'held-out'" in str(e.value)
+    with pytest.raises(_lib.InsiderError) as e:
+        call(ds, A, Cm, dict(entries="test", inc_continuous=2))
+    assert e.value.status == _lib.ERR_ARG and "inc_continuous can only be 0 or 1" in str(e.value)
+    with pytest.raises(_lib.InsiderError) as e:
+        call(ds, A, Cm, dict(entries="test", inc_continuous=0))
+    own = {"level_scores": "cov must be", "residual_products": "Q must be n x q", "outliers": "scale is required"}
+    assert e.value.status == _lib.ERR_ARG and own.get(name, "cfd_factors[1] must be 2 x 4") in str(e.value)
+
+
+def test_optimize_continuous_v2_updates_a_non_contiguous_view_in_place(monkeypatch):
+    """``updating_factor`` is the reference's ``rowvec&``: a row of a column-major matrix (a strided float64 view) is written
+    through, not a temporary copy of it.  The library is a stand-in that doubles the vector it is handed."""
+    K, n, p = 3, 4, 5
+
+    class Stub:
+        @staticmethod
+        def insider_hip_optimize_continuous_v2(D, n_, p_, M, u, Cm, K_, z, g, lam, tuning, device):
+            for k in range(K_):
+                u[k] = 2.0 * u[k]
+            return _lib.OK
+
+    monkeypatch.setattr(_lib, "load", lambda: Stub)
+    W = np.asfortranarray(np.arange(2.0 * K).reshape(2, K) + 1.0)
+    row = W[1]
+    assert not row.flags.c_contiguous and not row.flags.f_contiguous
+    before = W.copy()
+    got = api.optimize_continuous_v2(np.zeros((n, p)), None, row, np.ones((K, p)), np.ones(n), np.eye(K), 1.0, 0)
+    assert np.array_equal(got, 2.0 * before[1])
+    assert np.array_equal(W[1], 2.0 * before[1]) and np.array_equal(W[0], before[0])
