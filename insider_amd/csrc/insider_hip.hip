@@ -38,6 +38,8 @@
 
 using namespace insider;
 
+#include "insider_plan.hpp"   // (after the kernel headers and the using-directive: it reads their constants)
+
 namespace {
 
 thread_local std::string g_err;
@@ -64,8 +66,6 @@ int fail(int code, const std::string &msg)
 
 #define KCHECK() HIPCHECK(hipGetLastError())
 
-inline int64_t round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
-inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
 // Device bytes allocated (and not freed again) by the calling thread while a Tally is open: what a data set's set-up
 // allocated for itself (DataSet::bytes_own), temporaries of the stages excluded.
@@ -346,6 +346,20 @@ struct Workspace {
 // stream's kernels wrote must reach the other stream's kernels (device scope: every kernel boundary does that), not the host
 constexpr unsigned EV_SYNC = hipEventDisableTiming | hipEventDisableSystemFence;
 
+// A stream join that one function opens and another closes: the event and whether a wait for it is still owed.
+struct Join {
+    Event ev;
+    bool pending = false;
+    int record(hipStream_t s) { HIPCHECK(hipEventRecord(ev, s)); pending = true; return INSIDER_OK; }
+    int wait(hipStream_t s)           // enqueued only when a record is outstanding
+    {
+        if (pending) HIPCHECK(hipStreamWaitEvent(s, ev, 0));
+        pending = false;
+        return INSIDER_OK;
+    }
+    void drop() { pending = false; }
+};
+
 // The streams and events of one handle (each handle, clones included, has its own).
 struct Streams {
     Stream stream;
@@ -356,19 +370,28 @@ struct Streams {
     // side stream while the main stream computes V, u and U'C
     Stream side2;
     Stream side3;                     // C'C and (S^train C') of the merged row update, next to the weighted SYRK
-    Event ev_cd_done, ev_side_done, ev_prep, ev_c_ready;
+    Event ev_cd_done, ev_prep, ev_c_ready;
     Event ev_head;                    // recorded on side2 in front of the level Gram GEMM: the main chain's k_gene_u waits for it
     std::vector<Event> ev_w;          // per covariate (and continuous column): its level Gram sums are done
-    Event ev_a_ready, ev_qfull, ev_qheld, ev_tab;
+    Event ev_a_ready, ev_tab;
+    // the joins of the running optimize() that cross functions: Qfull = S A on the side stream and Qheld = S^held A of the
+    // factored column statistics on side3 (phase_R -> launch_col_solve / launch_col_stats); the gene order and sweep-order table
+    // on the side stream (launch_col_solve marks it pending, side_close records it, the next launch_col_solve waits)
+    Join qfull, qheld, side_done;
 
     int create(int n_w)
     {
         HIPCHECK(hipStreamCreate(stream.out()));
         for (Stream *s : {&side, &side2, &side3}) HIPCHECK(hipStreamCreateWithFlags(s->out(), hipStreamNonBlocking));
-        for (Event *e : {&ev_prep, &ev_c_ready, &ev_head, &ev_a_ready, &ev_qfull, &ev_qheld, &ev_cd_done, &ev_side_done, &ev_tab})
+        for (Event *e : {&ev_prep, &ev_c_ready, &ev_head, &ev_a_ready, &qfull.ev, &qheld.ev, &ev_cd_done, &side_done.ev, &ev_tab})
             HIPCHECK(hipEventCreateWithFlags(e->out(), EV_SYNC));
         ev_w.resize(n_w);
         for (Event &e : ev_w) HIPCHECK(hipEventCreateWithFlags(e.out(), EV_SYNC));
+        return INSIDER_OK;
+    }
+    int synchronize_sides() const
+    {
+        for (const Stream *s : {&side, &side2, &side3}) HIPCHECK(hipStreamSynchronize(*s));
         return INSIDER_OK;
     }
     void synchronize() const
@@ -442,11 +465,9 @@ struct insider_hip_handle {
     // post-hoc interaction GLM / residual / variance and sample decomposition: a workspace of its own, so that nothing
     // insider_hip_optimize() reads is touched
     PostWs post;
-    // state of the running optimize()
-    bool side_pending = false;
+    // state of the running optimize() (its pending stream joins: Streams)
+    FitPlan plan;                     // the kernel path of the call that is running, or ran last (plan_call)
     bool w_ready = false;
-    bool qfull_pending = false;
-    bool qheld_pending = false;       // Qheld = S^held A of the factored column statistics is being formed on side3 (phase_R)
     // sharding
     int64_t gene_offset = 0;
     int rank = 0, world = 1;
@@ -499,7 +520,6 @@ struct insider_hip_handle {
 namespace {
 
 constexpr int PC4_PARTS = 16;        // ticket counters of k_col_paircnt4
-constexpr int MM_FAST_MIN = 16384;   // rows from which k_mm_rows2 / k_mm_reduce2 run (below: the staging and the longer waves cost more than they save; c1: 5000 genes)
 constexpr int MM_SLAB = 128;  // rows per partial of the reduction products (insider_mm.hpp)
 
 // the kernel forms the row phase can launch, as insider_hip_get_info("row_kernels") reports them: bit RK_* is set on the host
@@ -514,34 +534,22 @@ enum RowKernel {
 inline uint64_t rk_bit(RowKernel k) { return 1ull << (int)k; }
 inline void row_mark(insider_hip_handle *h, RowKernel k) { h->row_kernels |= rk_bit(k); }
 
-// The weighted SYRK of covariate i as a GEMM over genes (k_wgemm, insider_row_merged.hpp)?  Needs the static half-count table
-// of the pair-count statistics; pays when the covariate has at least four tiles of 16 levels and the GEMM needs clearly fewer
-// MFMAs than the per-(level, gene) form.
-struct WgPlan {
-    bool use = false;
-    int tiles = 0, LT = 0, zch = 0, ntile = 0, npair = 0, slab = 0, nslab = 0;
-};
-WgPlan wgemm_plan(const insider_hip_handle *h, int i, int K, bool whatever_the_option = false)
+// the facts of handle h for a call with K factors (the workspace's geometry as it stands: none before the first call)
+PlanFacts plan_facts(const insider_hip_handle *h, int K)
 {
-    WgPlan w;
-    if (!((h->opt.row_gemm || whatever_the_option) && h->ds->cf_pair_ok && h->ds->cf_hn && h->ds->merged && h->ds->c <= CF_MAXC && K >= 1)) return w;
-    const int NB = (K + 1 + 15) / 16;
-    const int L = h->ds->cov[i].L, NBLK = NB * (NB + 1) / 2;
-    w.tiles = cdiv(L, 16);
-    w.npair = K * (K + 1) / 2;
-    w.ntile = cdiv(w.npair, 16);
-    if (w.tiles < 4 || (double)w.tiles * w.ntile >= 0.9 * (double)L * NBLK) return w;
-    w.zch = cdiv(w.tiles, 7);
-    w.LT = cdiv(w.tiles, w.zch);
-    const int waves_per_slab = cdiv(w.ntile, 2) * w.zch;
-    // one wave per SIMD: the kernel runs beside the main stream's V -> u -> U'C chain (other waves fill the machine), its
-    // operands are prefetched a step ahead, and every slab costs a partial record (levels x pairs doubles) to write and re-read
-    // (rounded DOWN: at most wg_waves waves in all — with the default, one per SIMD: a surplus block would run as a second round)
-    const int want = std::max(1, std::min<int>(h->opt.wg_waves / waves_per_slab, (int)cdiv(h->ds->p, 64)));
-    w.slab = (int)round_up(cdiv(h->ds->p, want), 4);
-    w.nslab = (int)cdiv(h->ds->p, w.slab);
-    w.use = true;
-    return w;
+    const DataSet &d = *h->ds;
+    PlanFacts f;
+    const Options &o = h->opt;
+    f.opt = {o.row_merged, o.col_factored, o.row_fused, o.row_gemm, o.row_counts, o.mm_fast, o.force_allreduce, o.wg_waves};
+    f.world = h->world;
+    f.K = K; f.NB = h->ws.NB; f.KP = h->ws.KP; f.lvl_zero = (bool)h->ws.lvl_zero;
+    f.merged = d.merged; f.cont_merged = d.cont_merged; f.cf_pair_ok = d.cf_pair_ok; f.cf_hn = (bool)d.cf_hn; f.cf_zt = (bool)d.cf_zt;
+    f.c = d.c; f.m = d.m; f.SL = d.SL; f.SLcat = d.SLcat; f.p = d.p; f.col_entries = d.col_entries; f.row_entries = d.row_entries;
+    for (const CovTables &ct : d.cov) { f.L.push_back(ct.L); f.npairs.push_back(ct.npairs); }
+    f.cf_c = d.cf.c; f.cf_tab_rows = d.cf.tab_rows; f.cf_nsteps = d.cf.nsteps;
+    std::copy(d.cf.L, d.cf.L + CF_MAXC + 1, f.cf_L);
+    std::copy(d.cf.nlater, d.cf.nlater + CF_MAXC + 1, f.cf_nlater);
+    return f;
 }
 
 int ensure_workspace(insider_hip_handle *h, int K)
@@ -588,8 +596,9 @@ int ensure_workspace(insider_hip_handle *h, int K)
         // k_wgemm (weighted SYRK as a GEMM over genes): partial sums per gene slab, and the packed pair index -> (a, b) table
         size_t wg_len = 0;
         int wg_ntile = 0;
+        const PlanFacts facts = plan_facts(h, K);
         for (int i = 0; i < d.c; ++i) {
-            const WgPlan g = wgemm_plan(h, i, K, true);
+            const WgPlan g = wgemm_plan(facts, i, true);
             if (g.use) {
                 wg_len = std::max(wg_len, (size_t)g.nslab * (16 * g.tiles) * (16 * g.ntile));
                 wg_ntile = g.ntile;
@@ -827,7 +836,6 @@ int launch_build_R(insider_hip_handle *h)
 // R, R'R and Qfull from the current row factors (src/optimize.cpp:365-369 and the Xty of :222,235 via level sums)
 // use_side: Qfull, which only the column solve reads, is formed on the side stream next to R'R and the column statistics
 // r_is_current: the row updates have just rebuilt R (every row_update() ends with k_build_R): do not build it again
-bool use_col_factored(const insider_hip_handle *h);
 int phase_R(insider_hip_handle *h, bool use_side = false, bool r_is_current = false, bool want_qheld = false)
 {
     if (use_side) {
@@ -835,16 +843,14 @@ int phase_R(insider_hip_handle *h, bool use_side = false, bool r_is_current = fa
         // Qheld = S^held A, which the factored column statistics read: on the third stream (idle since the row phase's C'C),
         // beside R'R on the main one instead of behind it, and beside Qfull on the side stream (Qfull behind Qheld: DESIGN §4.5)
         HIPCHECK(hipStreamWaitEvent(h->st.side, h->st.ev_a_ready, 0));
-        if (want_qheld && h->ws.Qheld && use_col_factored(h)) {
+        if (want_qheld && h->ws.Qheld && h->plan.col_path != 0) {
             HIPCHECK(hipStreamWaitEvent(h->st.side3, h->st.ev_a_ready, 0));
             if (int rh = launch_mm_rows_kp(h, h->ds->Sheld, h->ds->SLP, (int)h->ds->p, h->ds->SL, h->ws.Astack, h->ws.Qheld, h->st.side3)) return rh;
-            HIPCHECK(hipEventRecord(h->st.ev_qheld, h->st.side3));
-            h->qheld_pending = true;
+            if (int rh = h->st.qheld.record(h->st.side3)) return rh;
         }
         int rq = launch_mm_rows_kp(h, h->ds->S, h->ds->SLP, (int)h->ds->p, h->ds->SL, h->ws.Astack, h->ws.Qfull, h->st.side);
         if (rq) return rq;
-        HIPCHECK(hipEventRecord(h->st.ev_qfull, h->st.side));
-        h->qfull_pending = true;
+        if ((rq = h->st.qfull.record(h->st.side))) return rq;
     }
     int rc = r_is_current ? INSIDER_OK : launch_build_R(h);
     if (rc) return rc;
@@ -1041,38 +1047,6 @@ int launch_gene_order(insider_hip_handle *h, const int *sweeps, int reset, int f
     return INSIDER_OK;
 }
 
-// Which kernel forms the column-side statistics: 0 = k_list_stats (one rank-one MFMA group per held-out entry), 1 =
-// k_col_factored (look-up form), 2 = k_col_paircnt (pair-count form).  Issue-cycle models per gene with E held-out
-// entries: the list kernel spends NBLK MFMAs (64 cycles) per 4 entries; the look-up form NB^2 MFMAs per 4 levels plus, per
-// later covariate and 16-entry batch of a level group, 16 x (2 + NB) vector instructions (4.6 cycles); the pair-count form
-// NB^2 MFMAs per 4 levels plus ceil(rows / 4) x NB MFMAs per 16 levels.  Measured at c3 / c5: look-up 0.51 vs list 1.30 ms
-// (model 14.5k vs 48k cycles) and 2.44 vs 0.66 ms (72k vs 24k).
-int col_stats_path(const insider_hip_handle *h)
-{
-    if (!(h->ds->merged && h->opt.col_factored && h->ds->c <= CF_MAXC)) return 0;
-    if (h->ds->m > 0) return (h->ds->cf_pair_ok && h->ds->cf_zt) ? 2 : 0;   // continuous covariates: the pair-count form with real-valued counts, or the lists
-    const bool lookup_fits =
-        ((size_t)(h->ds->cf.tab_rows + 1) * h->ws.KP + 4 * 16 * 17) * sizeof(double) + (size_t)4 * CF_CAP * 2 <= 64 * 1024;
-    if (h->opt.col_factored == 3 && h->ds->cf_pair_ok) return 2;                   // forced
-    if (h->opt.col_factored >= 2) return lookup_fits ? 1 : (h->ds->cf_pair_ok ? 2 : 0);   // forced (3 without a count table: look-up form)
-    const double E = (double)h->ds->col_entries / (double)std::max<int64_t>(h->ds->p, 1);
-    const int NB = h->ws.NB;
-    const double list = E * (NB * (NB + 1) / 2) * 16.0;
-    double fac = 0.0, pair = 0.0;
-    for (int t = 0; t < h->ds->cf.c; ++t) {
-        const double batches = std::ceil(std::max(1.0, E / h->ds->cf.L[t]) / 16.0);
-        fac += std::ceil(h->ds->cf.L[t] / 4.0) * (NB * NB * 64.0 + h->ds->cf.nlater[t] * batches * 16.0 * (2 + NB) * 4.6);
-        pair += std::ceil(h->ds->cf.L[t] / 4.0) * NB * NB * 64.0 +
-                std::ceil(h->ds->cf.L[t] / 16.0) * ((h->ds->cf.nlater[t] > 0 ? h->ds->cf.nsteps * NB * 64.0 : 0.0) + 150.0);
-    }
-    double best = list;
-    int path = 0;
-    if (lookup_fits && 1.3 * fac < best) { best = 1.3 * fac; path = 1; }
-    if (h->ds->cf_pair_ok && 1.3 * pair < best) { best = 1.3 * pair; path = 2; }
-    return path;
-}
-bool use_col_factored(const insider_hip_handle *h) { return col_stats_path(h) != 0; }
-
 // the kernels launch_col_stats() can launch, as insider_hip_get_info("col_stats_kernel") reports them
 // (include/insider_hip.h; insider_amd/_lib.py COL_STATS_KERNELS mirrors the names).  k_col_paircnt4<., ., 8, true> is compiled
 // (the PC4 macro instantiates it) but never launched: real-valued counts with more than four k-steps take k_col_paircnt.
@@ -1138,16 +1112,16 @@ int launch_col_stats(insider_hip_handle *h, bool timed)
 {
     Timer t;
     int rc;
-    if (use_col_factored(h) && h->qheld_pending) {   // Qheld = S^held A formed on side3 since the row factors were final (phase_R):
-        HIPCHECK(hipStreamWaitEvent(h->st.stream, h->st.ev_qheld, 0));   // joined BEFORE the timer, which then holds the statistics kernel alone
-        h->qheld_pending = false;
+    const bool factored = h->plan.col_path != 0;
+    if (factored && h->st.qheld.pending) {   // Qheld = S^held A formed on side3 since the row factors were final (phase_R):
+        if ((rc = h->st.qheld.wait(h->st.stream))) return rc;   // joined BEFORE the timer, which then holds the statistics kernel alone
         if ((rc = t.begin(h, timed))) return rc;
     } else {
         if ((rc = t.begin(h, timed))) return rc;
-        if (use_col_factored(h))
+        if (factored)
             if ((rc = launch_mm_rows_kp(h, h->ds->Sheld, h->ds->SLP, (int)h->ds->p, h->ds->SL, h->ws.Astack, h->ws.Qheld))) return rc;
     }
-    if (use_col_factored(h)) {
+    if (factored) {
         ColFacArgs a = h->ds->cf;
         a.K = h->ws.K;
         a.Astack = h->ws.Astack;
@@ -1156,7 +1130,7 @@ int launch_col_stats(insider_hip_handle *h, bool timed)
         a.yy_all = h->ds->yy_all;
         a.yy_train = h->ds->yy_train;
         a.stat = h->ws.stat_col;
-        if (col_stats_path(h) == 2) {
+        if (h->plan.col_path == 2) {
             a.cnt = h->ds->cf_cnt;
             a.hn = h->ds->cf_hn;
             a.zt = h->ds->cf_zt;
@@ -1182,46 +1156,47 @@ int launch_col_stats(insider_hip_handle *h, bool timed)
     return t.end(h, h->ev_col);
 }
 
+// what ColArgs and RidgeArgs share: the statistics, the factors and where the per-gene loss terms go
+template <typename Args>
+void col_args_head(const insider_hip_handle *h, int masked, int checkpoint, Args &a)
+{
+    a.stat = masked ? h->ws.stat_col : nullptr;
+    a.stat_len = h->plan.stat_len;
+    a.p = (int)h->ds->p;
+    a.K = h->ws.K;
+    a.KP = h->ws.KP;
+    a.RtR = h->ws.RtR;
+    a.Qfull = h->ws.Qfull;
+    a.C = h->ws.C;
+    a.yy = masked ? h->ds->yy_train : h->ds->yy_all;
+    a.checkpoint = checkpoint;
+    a.sse_train = h->ws.sse_train;
+    a.b2 = h->ws.b2;
+    a.b1 = h->ws.b1;
+    a.sse_test = h->ws.sse_test;
+    a.test_from_stats = masked && h->ds->no_na;
+}
+
 // column update from the statistics: elastic-net CD (alpha > 0) or ridge (alpha == 0), or evaluation only
 int launch_col_solve(insider_hip_handle *h, int masked, bool solve, double lambda, double alpha, double tol,
                      int checkpoint, bool timed, int outer_iter = -1, bool side = false)
 {
     const bool early = outer_iter >= 0 && outer_iter < Workspace::EARLY;
-    const int NBLK = h->ws.NB * (h->ws.NB + 1) / 2, STAT = NBLK * 256;
-    // (every stream join is a barrier packet on the main queue, ~5 us of bubble each at c3: ev_qfull is recorded on the side stream
-    // AFTER the previous iteration's ev_side_done — phase_R comes after side_close — so it stands for both)
-    if (h->side_pending)   // the gene order / sweep-order table prepared on the side stream
-        HIPCHECK(hipStreamWaitEvent(h->st.stream, h->st.ev_side_done, 0));
-    h->side_pending = false;
-    if (h->qfull_pending) {
-        HIPCHECK(hipStreamWaitEvent(h->st.stream, h->st.ev_qfull, 0));
-        h->qfull_pending = false;
-    }
+    int rc;
+    // (every stream join is a barrier packet on the main queue, ~5 us of bubble each at c3: qfull's event is recorded on the side stream
+    // AFTER the previous iteration's side_done — phase_R comes after side_close — so it stands for both)
+    if ((rc = h->st.side_done.wait(h->st.stream))) return rc;   // the gene order / sweep-order table prepared on the side stream
+    if ((rc = h->st.qfull.wait(h->st.stream))) return rc;
     Timer t;
-    int rc = t.begin(h, timed);
-    if (rc) return rc;
+    if ((rc = t.begin(h, timed))) return rc;
     bool eval_after = false, fused_bucket = false;
     ColArgs eval_args;
     h->col_solver = h->col_eval = h->col_ridge_fallback = CS_NONE;
     if (alpha == 0.0) {
         RidgeArgs a;
-        a.stat = masked ? h->ws.stat_col : nullptr;
-        a.stat_len = STAT;
-        a.p = (int)h->ds->p;
-        a.K = h->ws.K;
-        a.KP = h->ws.KP;
-        a.RtR = h->ws.RtR;
-        a.Qfull = h->ws.Qfull;
-        a.C = h->ws.C;
-        a.yy = masked ? h->ds->yy_train : h->ds->yy_all;
+        col_args_head(h, masked, checkpoint, a);
         a.lambda = lambda;
         a.solve = solve ? 1 : 0;
-        a.checkpoint = checkpoint;
-        a.sse_train = h->ws.sse_train;
-        a.b2 = h->ws.b2;
-        a.b1 = h->ws.b1;
-        a.sse_test = h->ws.sse_test;
-        a.test_from_stats = masked && h->ds->no_na;
         a.fail = h->ws.failflag;
         a.mark = h->ws.sweeps;          // free in the alpha == 0 path: cleared below
         a.retry = h->ws.failflag + 1;
@@ -1247,17 +1222,8 @@ int launch_col_solve(insider_hip_handle *h, int masked, bool solve, double lambd
         if (solve) HIPCHECK(hipMemsetAsync(h->ws.sweeps, 0, (size_t)h->ds->p * sizeof(int), h->st.stream));
     } else {
         ColArgs a;
-        a.stat = masked ? h->ws.stat_col : nullptr;
-        a.stat_len = STAT;
-        a.p = (int)h->ds->p;
-        a.K = h->ws.K;
-        a.KP = h->ws.KP;
-        a.RtR = h->ws.RtR;
-        a.Qfull = h->ws.Qfull;
-        a.C = h->ws.C;
-        a.yy = masked ? h->ds->yy_train : h->ds->yy_all;
+        col_args_head(h, masked, checkpoint, a);
         a.mode = solve ? COL_CD : COL_EVAL;
-        a.checkpoint = checkpoint;
         a.cd.lambda = lambda;
         a.cd.alpha = alpha;
         a.cd.tol = tol;
@@ -1267,11 +1233,6 @@ int launch_col_solve(insider_hip_handle *h, int masked, bool solve, double lambd
         a.cd.inv_two_la = a.cd.la > 0.0 ? 0.5 / a.cd.la : 0.0;
         a.cd.max_sweeps = h->opt.max_sweeps;
         a.cd.order = h->ws.order;
-        a.sse_train = h->ws.sse_train;
-        a.b2 = h->ws.b2;
-        a.b1 = h->ws.b1;
-        a.sse_test = h->ws.sse_test;
-        a.test_from_stats = masked && h->ds->no_na;
         a.sweeps = h->ws.sweeps;
         a.sweep_bins = (timed && solve) ? h->ws.sweep_total : nullptr;
         a.gene_perm = !solve ? nullptr : (early && h->ws.have_early[outer_iter]) ? h->ws.perm_early[outer_iter]
@@ -1374,17 +1335,15 @@ int launch_col_solve(insider_hip_handle *h, int masked, bool solve, double lambd
                                     hipMemcpyDeviceToDevice, st));
             h->ws.have_early[outer_iter] = true;
         }
-        if (side) {   // the caller may add the next sweep-order table to the side stream, then closes it with side_close()
-            h->side_pending = true;
-        }
+        // the caller may add the next sweep-order table to the side stream, then closes it with side_close()
+        if (side) h->st.side_done.pending = true;
     }
     return INSIDER_OK;
 }
 
 int side_close(insider_hip_handle *h)
 {
-    if (h->side_pending) HIPCHECK(hipEventRecord(h->st.ev_side_done, h->st.side));
-    return INSIDER_OK;
+    return h->st.side_done.pending ? h->st.side_done.record(h->st.side) : INSIDER_OK;
 }
 
 // sum over test entries of the squared residual per gene (evaluate(), src/utils.cpp:67); checkpoints only
@@ -1405,33 +1364,7 @@ int launch_test_sse(insider_hip_handle *h, int masked, bool timed)
     return t.end(h, h->ev_test);
 }
 
-// masked update without per-sample statistics (insider_row_merged.hpp)?  Time model (us at c3 / c5 rates): per-sample
-// path = one rank-one MFMA group per held-out entry + the level kernels; merged path per covariate = one weighted group per
-// (level, gene) pair + one look-up per entry and other covariate + the small products over its levels.  Measured at
-// c3: 0.55 vs 1.4 ms (model 0.45 vs 1.38); at c5 (4 covariates): 1.37 vs 0.85 ms (model 1.24 vs 0.84).
-bool use_merged(const insider_hip_handle *h, int masked)
-{
-    if (!(masked && h->ds->merged && h->opt.row_merged && (h->ds->m == 0 || h->ds->cont_merged))) return false;
-    if (h->opt.row_merged == 2 || h->ds->m > 0) return true;   // forced / continuous covariates: the per-sample pass is the slow alternative
-    const int NB = h->ws.NB ? h->ws.NB : 2;
-    const double mf = (NB * (NB + 1) / 2) * 16.0 / (1024.0 * 2100.0);   // us per rank-one group entry on the whole GPU
-    const double E = (double)h->ds->row_entries, pscale = (double)h->ds->p / 5.0e4;
-    const double old_us = E * mf * 1.15 + 50.0 * h->ds->c;
-    double merged_us = 0.0;
-    for (int i = 0; i < h->ds->c; ++i)
-        merged_us += (double)h->ds->cov[i].npairs * mf * 1.1 + E * (h->ds->c - 1) * 1.3e-6 + 33.0 * pscale * h->ds->SLcat / 110.0 / h->ds->c +
-                     37.0 * pscale * h->ds->cov[i].L / 100.0 + 40.0;
-    return 1.1 * merged_us < old_us;
-}
-
-// tuning = 0 (src/optimize.cpp:178-191): XtX_l = |l| CC' + lambda I and Xty_l = (S C')[l] - CC' sum_{r in l} s_r are the merged
-// update's equations with EMPTY held-out sums, and sum_{r in l} s_r comes from the level-pair sample counts: one launch per
-// covariate (k_level_merged on an all-zero record) instead of five over the samples, and R is rebuilt once per outer iteration.
-// What it buys is launch latency: on small data a long unmasked fit (the reference's fit() default) is a chain of ~5 us kernels.
-bool unmasked_fused(const insider_hip_handle *h, int masked)
-{
-    return !masked && h->ds->merged && h->opt.row_merged && h->opt.row_fused && h->ds->m == 0 && h->ws.lvl_zero;
-}
+void plan_call(insider_hip_handle *h, int masked) { h->plan = build_plan(plan_facts(h, h->ws.K), masked); }
 
 // V = C A' for the stacked levels [q_begin, q_end) (all of them once per outer iteration, then the updated covariate's)
 int launch_gene_v(insider_hip_handle *h, int q_begin, int q_end)
@@ -1439,7 +1372,7 @@ int launch_gene_v(insider_hip_handle *h, int q_begin, int q_end)
     // V[:, q_begin:q_end) = C A[q_begin:q_end, :]'  (A given "transposed": one row per output column)
     const int N = q_end - q_begin;
     if (N <= 0) return INSIDER_OK;
-    if (h->opt.mm_fast && h->ds->p >= MM_FAST_MIN) {   // A' staged in LDS once per block, C read in 16-byte pieces (k_mm_rows2)
+    if (h->plan.mm_fast) {   // A' staged in LDS once per block, C read in 16-byte pieces (k_mm_rows2)
         const int tiles = cdiv((int)h->ds->p, 16), tpw = mm_tiles_per_wave(h, tiles);
         const size_t ldsb = (size_t)4 * cdiv(h->ws.K, 16) * 64 * sizeof(double);
 #define GV2_LAUNCH(NT_)                                                                                                       \
@@ -1503,9 +1436,9 @@ int launch_level_gram(insider_hip_handle *h, int i, hipStream_t st, double *rec,
 {
     const CovTables &ct = cont_ct ? *cont_ct : h->ds->cov[i];
     const CovTables &lists = cont_ct ? h->ds->contm_lists : ct;   // (the continuous columns' lists and work items: one copy)
-    const WgPlan w = cont_ct ? WgPlan() : wgemm_plan(h, i, h->ws.K);
+    const WgPlan w = cont_ct ? WgPlan() : h->plan.wg[i];
+    const int stat_len = h->plan.stat_len, plen = h->plan.plen;
     if (w.use) {
-        const int stat_len = h->ws.NB * (h->ws.NB + 1) / 2 * 256, plen = stat_len + 2 * h->ws.KP + 2;
         const float *hn = h->ds->cf_hn + h->ds->cf.hn_off[h->ds->cf_pos[i]];
         const dim3 grid(cdiv(cdiv(w.ntile, 2) * w.nslab, 4), 1, w.zch);   // (slab, pair-tile pair) items, four waves per block
 #define WG_LAUNCH(LT_)                                                                                                     \
@@ -1526,15 +1459,14 @@ int launch_level_gram(insider_hip_handle *h, int i, hipStream_t st, double *rec,
         return INSIDER_OK;
     }
     NB_DISPATCH(h->ws.NB, {
-        constexpr int STAT_ = Geo<NB_>::STAT, PLEN = STAT_ + 2 * Geo<NB_>::KP + 2;
         if (ct.nitems > 0) {   // no held-out entry at all: every level sum is zero
             hipLaunchKernelGGL((k_wsyrk<NB_, WPB_>), dim3(cdiv(ct.nitems, WPB_)), dim3(WPB_ * 64), 0, st,
                                (const uint32_t *)lists.item_begin, (const uint32_t *)lists.item_end, ct.nitems,
                                (const int *)lists.wl_idx, (const double *)ct.wl_w, (const double *)h->ws.C, (int64_t)h->ds->p, h->ws.wpart);
             row_mark(h, RK_WSYRK);
         }
-        hipLaunchKernelGGL(k_level_sum, dim3(cdiv(STAT_, 16), ct.L), dim3(256), 0, st, (const double *)h->ws.wpart,
-                           (const int *)lists.lvl_item_ptr, STAT_, rec, PLEN);
+        hipLaunchKernelGGL(k_level_sum, dim3(cdiv(stat_len, 16), ct.L), dim3(256), 0, st, (const double *)h->ws.wpart,
+                           (const int *)lists.lvl_item_ptr, stat_len, rec, plen);
     });
     KCHECK();
     return INSIDER_OK;
@@ -1560,13 +1492,12 @@ int launch_wsyrk_side(insider_hip_handle *h)
     if (int rp = launch_mm_reduce_kp(h, h->ds->Strain, h->ds->SLP, h->ws.C, (int)h->ds->p, h->ds->SL, h->ws.sc_part2, h->ws.SC, h->st.side3)) return rp;
     HIPCHECK(hipEventRecord(h->st.ev_prep, h->st.side3));
     row_mark(h, RK_GRAM_SIDE);
+    const size_t plen = h->plan.plen;
     for (int i = 0; i < h->ds->c; ++i) {
-        const int plen = h->ws.NB * (h->ws.NB + 1) / 2 * 256 + 2 * h->ws.KP + 2;
         if (int rg = launch_level_gram(h, i, h->st.side2, h->ws.lvl_sum_all + (size_t)h->ds->lvl_off[i] * plen)) return rg;
         HIPCHECK(hipEventRecord(h->st.ev_w[i], h->st.side2));
     }
     for (int k = 0; k < (h->ds->cont_merged ? h->ds->m : 0); ++k) {   // continuous columns: one-level covariates with real-valued weights
-        const int plen = h->ws.NB * (h->ws.NB + 1) / 2 * 256 + 2 * h->ws.KP + 2;
         if (int rg = launch_level_gram(h, 0, h->st.side2, h->ws.lvl_sum_all + (size_t)(h->ds->SLcat + k) * plen, &h->ds->contm[k])) return rg;
         HIPCHECK(hipEventRecord(h->st.ev_w[h->ds->c + k], h->st.side2));
     }
@@ -1579,7 +1510,8 @@ int launch_wsyrk_side(insider_hip_handle *h)
 int row_update(insider_hip_handle *h, int i, int cont_col, int masked, double lambda1, bool rebuild_R = true)
 {
     const bool cont = cont_col >= 0;
-    bool fused_solve = false;
+    const FitPlan &plan = h->plan;
+    const bool fused_solve = !cont && plan.fused_solve;   // (a continuous column's solve is k_cont_cd's cyclic passes)
     const CovTables &ct = cont ? h->ds->cont : h->ds->cov[i];
     const int row0 = cont ? h->ds->SLcat + cont_col : h->ds->lvl_off[i];   // first row of this covariate in Astack / SC
     LevelArgs la;
@@ -1608,7 +1540,7 @@ int row_update(insider_hip_handle *h, int i, int cont_col, int masked, double la
     ra.SC = h->ws.SC;
     ra.sc_off = row0;
     ra.eq = h->ws.eq;
-    if (cont && use_merged(h, masked)) {
+    if (cont && plan.merged) {
         // merged update of continuous column cont_col (optimize_continuous_v2, src/optimize.cpp:76-137): the one-level covariate
         // with real-valued membership weights z_r — u_j from the real-valued count table, Y = U'C, the level record's Gram sum
         // from the (gene, sum z^2) list, sum_r z_r s_r from the real-valued pair counts; then the reference's cyclic scalar
@@ -1628,23 +1560,22 @@ int row_update(insider_hip_handle *h, int i, int cont_col, int masked, double la
             HIPCHECK(hipStreamWaitEvent(h->st.stream, h->st.ev_w[h->ds->c + cont_col], 0));
             HIPCHECK(hipStreamWaitEvent(h->st.stream, h->st.ev_prep, 0));
         }
+        double *rec = h->w_ready ? h->ws.lvl_sum_all + (size_t)row0 * plan.plen : h->ws.lvl_sum;
+        if (!h->w_ready)
+            if (int rg = launch_level_gram(h, 0, h->st.stream, rec, &cm)) return rg;
         NB_DISPATCH(h->ws.NB, {
             (void)WPB_;
-            constexpr int STAT_ = Geo<NB_>::STAT, PLEN = STAT_ + 2 * Geo<NB_>::KP + 2;
-            double *rec = h->w_ready ? h->ws.lvl_sum_all + (size_t)row0 * PLEN : h->ws.lvl_sum;
-            if (!h->w_ready)
-                if (int rg = launch_level_gram(h, 0, h->st.stream, rec, &cm)) return rg;
             hipLaunchKernelGGL((k_level_merged<NB_>), dim3(1), dim3(256), 0, h->st.stream, (const double *)rec, (const double *)h->ws.sc_part,
                                ypart_n, (const double *)cm.paircnt, h->ds->SL, (const double *)h->ws.Astack, (const int *)h->ds->one_count,
                                (const double *)h->ws.CCt, (const double *)(h->ws.SC + (size_t)row0 * KP), 1, h->ws.K, lambda1, 0, h->ws.eq,
                                h->ws.Astack + (size_t)row0 * KP, h->ws.failflag, (const double *)(h->ds->cont_cnt + cont_col));
         });
         row_mark(h, RK_MERGED);
-    } else if (!cont && use_merged(h, masked)) {
+    } else if (!cont && plan.merged) {
         // merged update: one weighted rank-one term per (level, gene) pair, one look-up per held-out entry
         const int L = ct.L, LP = (int)round_up(L, 2), KP = h->ws.KP;
-        const size_t gu_lds = (size_t)4 * (h->ds->SL + LP + GU_BATCH * WAVE) * sizeof(double);
-        if (h->ds->cf_pair_ok && (h->opt.row_counts || h->ds->m > 0) && h->ds->c <= CF_MAXC && gu_lds <= 64 * 1024) {   // u from the dense pair counts (insider_col_factored.hpp)
+        if (plan.u_cnt[i]) {   // u from the dense pair counts (insider_col_factored.hpp)
+            const size_t gu_lds = (size_t)4 * (h->ds->SL + LP + GU_BATCH * WAVE) * sizeof(double);
             ColFacArgs ca = h->ds->cf;
             ca.cnt = h->ds->cf_cnt;
             ca.zt = h->ds->m > 0 ? h->ds->cf_zt : nullptr;   // (+ the continuous covariates' term from the real-valued counts)
@@ -1675,12 +1606,10 @@ int row_update(insider_hip_handle *h, int i, int cont_col, int masked, double la
         }
         if (!h->w_ready)
             if (int rg = launch_level_gram(h, i, h->st.stream, h->ws.lvl_sum)) return rg;
+        double *rec = h->w_ready ? h->ws.lvl_sum_all + (size_t)row0 * plan.plen : h->ws.lvl_sum;
         NB_DISPATCH(h->ws.NB, {
-            constexpr int STAT_ = Geo<NB_>::STAT, PLEN = STAT_ + 2 * Geo<NB_>::KP + 2;
-            double *rec = h->w_ready ? h->ws.lvl_sum_all + (size_t)h->ds->lvl_off[i] * PLEN : h->ws.lvl_sum;
-            // the level records' tail, the level equations and (unless the equations still have to cross ranks) the solves: one launch
-            fused_solve = h->world <= 1 && !h->opt.force_allreduce && h->opt.row_fused && NB_ <= 2;
-            if (h->opt.row_fused) {
+            (void)WPB_;
+            if (h->opt.row_fused) {   // the level records' tail, the level equations and (fused_solve) the solves: one launch
                 hipLaunchKernelGGL((k_level_merged<NB_>), dim3(L), dim3(256), 0, h->st.stream, (const double *)rec,
                                    (const double *)(ypart_n ? h->ws.sc_part : h->ws.Ylvl), ypart_n, (const double *)ct.paircnt, h->ds->SL, (const double *)h->ws.Astack,
                                    (const int *)(h->ds->lvl_count_all + h->ds->lvl_off[i]), (const double *)h->ws.CCt,
@@ -1690,17 +1619,16 @@ int row_update(insider_hip_handle *h, int i, int cont_col, int masked, double la
             } else {
                 hipLaunchKernelGGL(k_level_pack, dim3(L), dim3(256), 0, h->st.stream, (const double *)h->ws.Ylvl,
                                    (const double *)ct.paircnt, h->ds->SL, (const double *)h->ws.Astack,
-                                   (const int *)(h->ds->lvl_count_all + h->ds->lvl_off[i]), L, h->ws.K, KP, STAT_, rec);
+                                   (const int *)(h->ds->lvl_count_all + h->ds->lvl_off[i]), L, h->ws.K, KP, plan.stat_len, rec);
                 ra.part = rec;
                 hipLaunchKernelGGL((k_level_reduce<NB_>), dim3(L), dim3(64), 0, h->st.stream, ra);
                 row_mark(h, RK_PACK_REDUCE);
             }
         });
-    } else if (!cont && unmasked_fused(h, masked)) {
+    } else if (!cont && plan.unmasked_fused) {
         const int L = ct.L, KP = h->ws.KP;
         NB_DISPATCH(h->ws.NB, {
             (void)WPB_;
-            fused_solve = h->world <= 1 && !h->opt.force_allreduce && NB_ <= 2;
             hipLaunchKernelGGL((k_level_merged<NB_>), dim3(L), dim3(256), 0, h->st.stream, (const double *)h->ws.lvl_zero,
                                (const double *)h->ws.lvl_zero, 0, (const double *)ct.paircnt, h->ds->SL, (const double *)h->ws.Astack,
                                (const int *)(h->ds->lvl_count_all + h->ds->lvl_off[i]), (const double *)h->ws.CCt,
@@ -1712,10 +1640,9 @@ int row_update(insider_hip_handle *h, int i, int cont_col, int masked, double la
     } else {
         NB_DISPATCH(h->ws.NB, {
             (void)WPB_;
-            constexpr int PLEN = Geo<NB_>::STAT + 2 * Geo<NB_>::KP + 2;
             hipLaunchKernelGGL((k_level_partial<NB_>), dim3(ct.nchunks), dim3(64), 0, h->st.stream, la);
-            hipLaunchKernelGGL(k_level_sum, dim3(cdiv(PLEN, 16), ct.L), dim3(256), 0, h->st.stream,
-                               (const double *)h->ws.lvl_part, (const int *)ct.lvl_chunk_ptr, PLEN, h->ws.lvl_sum, PLEN);
+            hipLaunchKernelGGL(k_level_sum, dim3(cdiv(plan.plen, 16), ct.L), dim3(256), 0, h->st.stream,
+                               (const double *)h->ws.lvl_part, (const int *)ct.lvl_chunk_ptr, plan.plen, h->ws.lvl_sum, plan.plen);
             hipLaunchKernelGGL((k_level_reduce<NB_>), dim3(ct.L), dim3(64), 0, h->st.stream, ra);
         });
         row_mark(h, RK_LEVEL_PARTIAL);
@@ -1849,14 +1776,12 @@ int download_factors(insider_hip_handle *h, double *const *A, double *C, int K)
 }
 
 // C C' and S_i C' for the row step (src/optimize.cpp:332 and the unmasked part of :166,188)
-int launch_row_prep(insider_hip_handle *h, int masked)
+int launch_row_prep(insider_hip_handle *h)
 {
     int rc = launch_gram(h, h->ws.C, h->ds->p, h->ws.CCt);
     if (rc) return rc;
     // the merged update wants (S^train C'): the per-level sums of the TRAIN entries, i.e. (S C') minus sum_r bc_r
-    if ((rc = launch_mm_reduce_kp(h, use_merged(h, masked) ? h->ds->Strain : h->ds->S, h->ds->SLP, h->ws.C, (int)h->ds->p, h->ds->SL, h->ws.sc_part, h->ws.SC)))
-        return rc;
-    return INSIDER_OK;
+    return launch_mm_reduce_kp(h, h->plan.merged ? h->ds->Strain : h->ds->S, h->ds->SLP, h->ws.C, (int)h->ds->p, h->ds->SL, h->ws.sc_part, h->ws.SC);
 }
 
 int check_factor_args(insider_hip_handle *h, double *const *A, const double *C, int inc_continuous, int tuning)
@@ -2687,6 +2612,55 @@ int insider_hip_set_option(insider_hip_handle *h, const char *name, double value
     return INSIDER_OK;
 }
 
+// Nothing of an earlier call is owed any more: its joins, its level Gram sums, its timer events.  drain: an early return
+// leaves enqueued work on every stream, so they are drained first and the next call starts clean
+static void reset_call_state(insider_hip_handle *h, bool drain)
+{
+    if (drain) (void)hipSetDevice(h->ds->device);
+    if (drain) h->st.synchronize();
+    h->w_ready = false;
+    for (Join *j : {&h->st.qfull, &h->st.qheld, &h->st.side_done}) j->drop();
+    clear_events(h);
+}
+
+// the sub-problem tolerance's factor from the last checkpoint's loss decrease (src/optimize.cpp:389-403)
+static double decay_for(double delta_loss)
+{
+    for (double d : {1e-6, 1e-5, 1e-4, 1e-3, 1e-2, 1e-1})
+        if (delta_loss / 1000 <= d) return d;
+    return 1.0;
+}
+
+// profile of the call that has just ended (insider_hip_profile): launches and HIP-event time per timed kernel, the steady-state
+// means, and which statistics paths its plan ran
+static void profile_summary(insider_hip_handle *h, double wall_ms, double iterations, double sweeps_total)
+{
+    for (double &v : h->prof) v = 0;
+    auto sum_events = [](std::vector<Event> &ev, size_t first, double *launches, double *ms) {
+        for (size_t i = first; i + 1 < ev.size(); i += 2) {
+            float t = 0;
+            if (hipEventElapsedTime(&t, ev[i], ev[i + 1]) == hipSuccess) { *ms += t; *launches += 1; }
+        }
+    };
+    sum_events(h->ev_col, 0, &h->prof[0], &h->prof[1]);
+    sum_events(h->ev_row, 0, &h->prof[2], &h->prof[3]);
+    sum_events(h->ev_cd, 0, &h->prof[4], &h->prof[5]);
+    sum_events(h->ev_test, 0, &h->prof[6], &h->prof[7]);
+    auto tail_mean = [&](std::vector<Event> &ev) {   // one event pair per outer iteration: the mean from iteration 5 on
+        double ms = 0.0, cnt = 0.0;
+        sum_events(ev, 10, &cnt, &ms);
+        return cnt ? ms / cnt : 0.0;
+    };
+    h->steady_cd_ms = tail_mean(h->ev_cd);
+    h->steady_col_ms = tail_mean(h->ev_col);
+    h->prof[8] = wall_ms;
+    h->prof[9] = iterations;
+    h->prof[10] = sweeps_total;
+    const FitPlan &p = h->plan;
+    h->prof[11] = (p.masked && p.col_path != 0 ? 1.0 : 0.0) + (p.merged ? 2.0 : 0.0) + (p.masked && p.col_path == 2 ? 4.0 : 0.0);
+    clear_events(h);
+}
+
 static int optimize_body(insider_hip_handle *h, double *const *A, double *C, int inc_continuous, int K, double lambda1,
                          double lambda2, double alpha, int tuning, double global_tol, double sub_tol, uint32_t max_iter,
                          uint64_t seed, double *out_train_rmse, double *out_test_rmse, double *out_loss, double *traj,
@@ -2696,18 +2670,14 @@ static int optimize_body(insider_hip_handle *h, double *const *A, double *C, int
     if (rc) return rc;
     HIPCHECK(hipSetDevice(h->ds->device));
     // work a failed earlier call may have left on the side streams must not race with this call's
-    HIPCHECK(hipStreamSynchronize(h->st.side));
-    HIPCHECK(hipStreamSynchronize(h->st.side2));
-    HIPCHECK(hipStreamSynchronize(h->st.side3));
+    if ((rc = h->st.synchronize_sides())) return rc;
     if ((rc = ensure_workspace(h, K))) return rc;
     const auto t_begin = std::chrono::steady_clock::now();
-    clear_events(h);
+    reset_call_state(h, false);
     h->row_kernels = 0;
-    h->w_ready = false;
-    h->side_pending = false;
-    h->qfull_pending = false;
-    h->qheld_pending = false;
     const int masked = tuning == 1;
+    plan_call(h, masked);
+    const FitPlan &plan = h->plan;
     if ((rc = upload_factors(h, A, C, K))) return rc;
 
     // ---- fit of the initial values (src/optimize.cpp:320-323) ----------------------------------------------------
@@ -2744,25 +2714,28 @@ static int optimize_body(insider_hip_handle *h, double *const *A, double *C, int
     while (iter <= max_iter) {                                                                  // :325
         if (h->opt.verbose && iter % 10 == 0) printf("Iteration %u ---------------------------------\n", iter);
         // ---- row step: all covariates, Gauss-Seidel (:332-362) -------------------------------------------------
-        if (use_merged(h, masked)) { if ((rc = launch_wsyrk_side(h))) return rc; }                // incl. the row prep
-        else if ((rc = launch_row_prep(h, masked))) return rc;                                  // :332
-        if (masked && !use_merged(h, masked)) if ((rc = launch_row_stats(h, true))) return rc;
-        // V = C A' of the covariates 1 .. c-1: what covariate 0's update reads.  Covariate 0's own columns are first read by
-        // covariate 1's update, after they have been recomputed from the updated factors (below): not formed here
-        // (with continuous covariates on the merged form: their columns of V too — s_r carries A_c' z_r)
-        if (use_merged(h, masked)) if ((rc = launch_gene_v(h, h->ds->c > 1 ? h->ds->lvl_off[1] : h->ds->SLcat, h->ds->SL))) return rc;
-        if (use_merged(h, masked)) HIPCHECK(hipStreamWaitEvent(h->st.stream, h->st.ev_head, 0));   // launch_wsyrk_side
+        if (plan.merged) {
+            if ((rc = launch_wsyrk_side(h))) return rc;                                         // incl. the row prep
+            // V = C A' of the covariates 1 .. c-1: what covariate 0's update reads.  Covariate 0's own columns are first read by
+            // covariate 1's update, after they have been recomputed from the updated factors (below): not formed here
+            // (with continuous covariates on the merged form: their columns of V too — s_r carries A_c' z_r)
+            if ((rc = launch_gene_v(h, h->ds->c > 1 ? h->ds->lvl_off[1] : h->ds->SLcat, h->ds->SL))) return rc;
+            HIPCHECK(hipStreamWaitEvent(h->st.stream, h->st.ev_head, 0));                         // launch_wsyrk_side
+        } else {
+            if ((rc = launch_row_prep(h))) return rc;                                           // :332
+            if (masked) if ((rc = launch_row_stats(h, true))) return rc;
+        }
         const bool cont_follow = inc_continuous && h->ds->m > 0;
         for (int i = 0; i < h->ds->c; ++i) {
-            const bool need_R = !(use_merged(h, masked) || unmasked_fused(h, masked)) || (i + 1 == h->ds->c && !cont_follow);
+            const bool need_R = !(plan.merged || plan.unmasked_fused) || (i + 1 == h->ds->c && !cont_follow);
             if ((rc = row_update(h, i, -1, masked, lambda1, need_R))) return rc;                // :339
-            if (use_merged(h, masked) && (i + 1 < h->ds->c || cont_follow))   // (the continuous columns read every categorical column of V)
+            if (plan.merged && (i + 1 < h->ds->c || cont_follow))   // (the continuous columns read every categorical column of V)
                 if ((rc = launch_gene_v(h, h->ds->lvl_off[i], h->ds->lvl_off[i + 1]))) return rc;
         }
         if (cont_follow)
             for (int j = 0; j < h->ds->m; ++j) {
-                if ((rc = row_update(h, 0, j, masked, lambda1, !use_merged(h, masked) || j + 1 == h->ds->m))) return rc;   // :340-351
-                if (use_merged(h, masked) && j + 1 < h->ds->m)
+                if ((rc = row_update(h, 0, j, masked, lambda1, !plan.merged || j + 1 == h->ds->m))) return rc;   // :340-351
+                if (plan.merged && j + 1 < h->ds->m)
                     if ((rc = launch_gene_v(h, h->ds->SLcat + j, h->ds->SLcat + j + 1))) return rc;
             }
         h->w_ready = false;
@@ -2793,13 +2766,7 @@ static int optimize_body(insider_hip_handle *h, double *const *A, double *C, int
             train_rmse = lo.train_rmse;
             test_rmse = lo.test_rmse;
             const double delta_loss = pre_loss - loss;
-            if (delta_loss / 1000 <= 1e-6) decay = 1e-6;                                        // :389-403
-            else if (delta_loss / 1000 <= 1e-5) decay = 1e-5;
-            else if (delta_loss / 1000 <= 1e-4) decay = 1e-4;
-            else if (delta_loss / 1000 <= 1e-3) decay = 1e-3;
-            else if (delta_loss / 1000 <= 1e-2) decay = 1e-2;
-            else if (delta_loss / 1000 <= 1e-1) decay = 1e-1;
-            else decay = 1.0;
+            decay = decay_for(delta_loss);                                                      // :389-403
             put_traj(iter, delta_loss, decay);
             if (h->opt.verbose) {
                 printf("insider iter %u: train rmse = %.12g\n", iter, train_rmse);
@@ -2815,10 +2782,8 @@ static int optimize_body(insider_hip_handle *h, double *const *A, double *C, int
     if ((rc = download_factors(h, A, C, K))) return rc;
     if ((rc = check_fail_flag(h))) return rc;
     if ((rc = read_cap_hits(h))) return rc;
-    HIPCHECK(hipStreamSynchronize(h->st.side2));
-    HIPCHECK(hipStreamSynchronize(h->st.side3));
-    HIPCHECK(hipStreamSynchronize(h->st.side));   // the gene orders kept for the next call
-    h->side_pending = false;
+    if ((rc = h->st.synchronize_sides())) return rc;   // (the side stream: the gene orders kept for the next call)
+    h->st.side_done.drop();
     {
         unsigned long long bins[256];
         // (on the handle's own stream: a null-stream copy would wait for every other handle's work, insider_hip_clone)
@@ -2831,36 +2796,8 @@ static int optimize_body(insider_hip_handle *h, double *const *A, double *C, int
     if (out_loss) *out_loss = loss;
     if (out_traj_rows) *out_traj_rows = trows;
     if (out_iters) *out_iters = (int)iter;
-    // ---- profile -------------------------------------------------------------------------------------------------------
-    const auto t_end = std::chrono::steady_clock::now();
-    for (double &v : h->prof) v = 0;
-    auto sum_events = [&](std::vector<Event> &ev, double *launches, double *ms) {
-        for (size_t i = 0; i + 1 < ev.size(); i += 2) {
-            float t = 0;
-            if (hipEventElapsedTime(&t, ev[i], ev[i + 1]) == hipSuccess) { *ms += t; *launches += 1; }
-        }
-    };
-    sum_events(h->ev_col, &h->prof[0], &h->prof[1]);
-    sum_events(h->ev_row, &h->prof[2], &h->prof[3]);
-    sum_events(h->ev_cd, &h->prof[4], &h->prof[5]);
-    sum_events(h->ev_test, &h->prof[6], &h->prof[7]);
-    auto tail_mean = [&](std::vector<Event> &ev) {   // one event pair per outer iteration: the mean from iteration 5 on
-        double ms = 0.0;
-        int cnt = 0;
-        for (size_t i = 10; i + 1 < ev.size(); i += 2) {
-            float t = 0;
-            if (hipEventElapsedTime(&t, ev[i], ev[i + 1]) == hipSuccess) { ms += t; ++cnt; }
-        }
-        return cnt ? ms / cnt : 0.0;
-    };
-    h->steady_cd_ms = tail_mean(h->ev_cd);
-    h->steady_col_ms = tail_mean(h->ev_col);
-    h->prof[8] = std::chrono::duration<double, std::milli>(t_end - t_begin).count();
-    h->prof[9] = (double)std::min<uint64_t>((uint64_t)iter + 1, (uint64_t)max_iter + 1);
-    h->prof[10] = (double)sweeps_total;
-    h->prof[11] = (masked && use_col_factored(h) ? 1.0 : 0.0) + (use_merged(h, masked) ? 2.0 : 0.0) +
-                  (masked && col_stats_path(h) == 2 ? 4.0 : 0.0);   // which statistics paths ran
-    clear_events(h);
+    profile_summary(h, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count(),
+                    (double)std::min<uint64_t>((uint64_t)iter + 1, (uint64_t)max_iter + 1), (double)sweeps_total);
     return INSIDER_OK;
 }
 
@@ -2872,16 +2809,9 @@ int insider_hip_optimize(insider_hip_handle *h, double *const *A, double *C, int
     const int rc = optimize_body(h, A, C, inc_continuous, K, lambda1, lambda2, alpha, tuning, global_tol, sub_tol, max_iter,
                                  seed, out_train_rmse, out_test_rmse, out_loss, traj, traj_cap, out_traj_rows, out_iters);
     if (rc != INSIDER_OK && h && h->st.stream) {
-        // an early return leaves enqueued work on every stream: drain them so that the next call starts clean
         const std::string keep = g_err;
-        (void)hipSetDevice(h->ds->device);
-        (void)hipStreamSynchronize(h->st.stream);
-        (void)hipStreamSynchronize(h->st.side);
-        (void)hipStreamSynchronize(h->st.side2);
-        (void)hipStreamSynchronize(h->st.side3);
-        h->side_pending = h->qfull_pending = h->qheld_pending = h->w_ready = false;
+        reset_call_state(h, true);
         if (h->ws.failflag) (void)hipMemset(h->ws.failflag, 0, 4 * sizeof(int));
-        clear_events(h);
         g_err = keep;
     }
     return rc;
@@ -2940,11 +2870,12 @@ int insider_hip_optimize_row(insider_hip_handle *h, double *const *A, const doub
     if ((rc = ensure_workspace(h, K))) return rc;
     h->row_kernels = 0;
     h->w_ready = false;
+    plan_call(h, tuning);
     if ((rc = upload_factors(h, A, C, K))) return rc;
-    if ((rc = launch_row_prep(h, tuning))) return rc;
-    if (tuning == 1 && !use_merged(h, tuning)) if ((rc = launch_row_stats(h, false))) return rc;
+    if ((rc = launch_row_prep(h))) return rc;
+    if (tuning == 1 && !h->plan.merged) if ((rc = launch_row_stats(h, false))) return rc;
     if ((rc = launch_build_R(h))) return rc;
-    if (use_merged(h, tuning)) if ((rc = launch_gene_v(h, 0, h->ds->SL))) return rc;
+    if (h->plan.merged) if ((rc = launch_gene_v(h, 0, h->ds->SL))) return rc;
     if (cov < h->ds->c) rc = row_update(h, cov, -1, tuning, lambda);
     else rc = row_update(h, 0, cov - h->ds->c, tuning, lambda);
     if (rc) return rc;
@@ -2962,6 +2893,7 @@ int insider_hip_optimize_col(insider_hip_handle *h, double *const *A, double *C,
     if (rc) return rc;
     HIPCHECK(hipSetDevice(h->ds->device));
     if ((rc = ensure_workspace(h, K))) return rc;
+    plan_call(h, tuning);
     if ((rc = upload_factors(h, A, C, K))) return rc;
     if ((rc = phase_R(h))) return rc;
     if (alpha != 0.0) {
@@ -3847,7 +3779,8 @@ static int masked_gram_common(insider_hip_handle *h, bool cols, const double *Fh
     HIPCHECK(hipSetDevice(h->ds->device));
     int rc = ensure_workspace(h, K);
     if (rc) return rc;
-    const int KP = h->ws.KP;
+    plan_call(h, 1);
+    const int KP = h->ws.KP, STAT = h->plan.stat_len;
     const int64_t units = cols ? h->ds->p : h->ds->n, flen = cols ? h->ds->n : h->ds->p;
     double *F = cols ? h->ws.R : h->ws.C, *full = cols ? h->ws.RtR : h->ws.CCt;
     // host factor: cols -> R is n x K column-major; rows -> C is K x p column-major (= p rows of K)
@@ -3858,7 +3791,6 @@ static int masked_gram_common(insider_hip_handle *h, bool cols, const double *Fh
                             flen, K, KP, F);
     KCHECK();
     if ((rc = launch_gram(h, F, flen, full))) return rc;
-    const int NBLK = h->ws.NB * (h->ws.NB + 1) / 2, STAT = NBLK * 256;
     const int nseg = cols ? 1 : h->ws.nseg;
     DevBuf<double> stat, qf, Gd, qd;
     if ((rc = stat.alloc((size_t)nseg * units * STAT)) || (rc = qf.alloc((size_t)units * KP)) || (rc = Gd.alloc((size_t)units * K * K)) ||
@@ -3905,6 +3837,7 @@ int insider_hip_col_stats(insider_hip_handle *h, double *const *A, int inc_conti
     if (h->world > 1) return fail(INSIDER_ERR_UNSUPPORTED, "insider_hip_col_stats on a sharded handle");
     HIPCHECK(hipSetDevice(h->ds->device));
     if ((rc = ensure_workspace(h, K))) return rc;
+    plan_call(h, 1);
     if ((rc = upload_factors(h, A, nullptr, K))) return rc;
     if ((rc = phase_R(h))) return rc;
     if ((rc = launch_col_stats(h, false))) return rc;
@@ -3942,8 +3875,9 @@ int insider_hip_get_info(insider_hip_handle *h, const char *name, double *out)
     if (!h || !name || !out) return fail(INSIDER_ERR_ARG, "null");
     const std::string s(name);
     const int NB = h->ws.NB;
-    if (s == "col_stats_path") *out = col_stats_path(h);
-    else if (s == "row_merged") *out = use_merged(h, 1) ? 1.0 : 0.0;
+    // (the path keys answer for the options as they stand now: a fresh plan, not the last call's)
+    if (s == "col_stats_path") *out = build_plan(plan_facts(h, h->ws.K), 1).col_path;
+    else if (s == "row_merged") *out = build_plan(plan_facts(h, h->ws.K), 1).merged ? 1.0 : 0.0;
     else if (s == "col_entries") *out = (double)h->ds->col_entries;      // padded held-out list entries, column side
     else if (s == "row_entries") *out = (double)h->ds->row_entries;
     else if (s == "data_bytes_shared") *out = (double)h->ds->bytes_shared;   // device bytes of the data set held jointly with its source (0: a created one) ...
@@ -3982,7 +3916,7 @@ int insider_hip_get_info(insider_hip_handle *h, const char *name, double *out)
         // v_mfma_f64_16x16x4_f64 instructions the column-side statistics kernel issues per gene (2048 flops each; the 4x4x4 form
         // of the per-entry kernel is counted in the same unit: a quarter per instruction)
         if (!NB) return fail(INSIDER_ERR_ARG, "no workspace yet: run an update first");
-        const int path = col_stats_path(h);
+        const int path = build_plan(plan_facts(h, h->ws.K), 1).col_path;
         double v = 0.0;
         if (path == 0) {
             const int NT = (h->ws.K + 4) / 4;

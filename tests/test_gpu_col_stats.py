@@ -7,7 +7,7 @@ the continuous covariates) or k_col_paircnt4 (the same with its second product o
 8 k-steps, genes dealt by ticket from one or sixteen counters).  insider_hip_col_stats() (InsiderData.col_stats) runs the
 first half of a column update and returns the record densified; insider_hip_get_info("col_stats_kernel" /
 "col_stats_tickets" / "col_stats_blocks") reports what ran.  expected() below is the dispatch written out by hand from
-col_stats_path(), launch_paircnt(), launch_list_stats() and stage_factored(): every case asserts the kernel it reached
+FitPlan::col_path (col_stats_path() in insider_plan.hpp), launch_paircnt(), launch_list_stats() and stage_factored(): every case asserts the kernel it reached
 before it compares values, so that a dispatch edit cannot quietly move a case onto another kernel.
 
 Covered: every code at the K band edges, the covariate structures (c = 1, 8, 9, tied level counts, the largest covariate

@@ -5,7 +5,8 @@ nothing), its u (k_gene_u_cnt, k_gene_u, k_gene_uc), its record tail / equations
 solve, k_level_pack + k_level_reduce, k_level_solve, k_cont_cd), the per-sample chain instead (k_list_stats4 / k_list_stats,
 k_level_partial ...) and the forms of its products V = C A' and Y = U'C.  insider_hip_get_info("row_kernels") reports the
 forms the last optimize() / optimize_row() launched, one bit each (_lib.ROW_KERNELS).  expected() below is that dispatch
-written out by hand from the predicates (wgemm_plan(), use_merged(), unmasked_fused(), row_update(), launch_mm_reduce_kp()):
+written out by hand from the call's FitPlan (build_plan() in insider_plan.hpp: wgemm_plan(), use_merged(), unmasked_fused,
+fused_solve, u_cnt) and from what row_update() and launch_mm_reduce_kp() launch for it:
 every case asserts the exact set it reached before it compares values, so that a dispatch edit that moves a band to another
 kernel fails the case written for the old one instead of quietly testing another kernel.
 """
