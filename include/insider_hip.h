@@ -192,7 +192,11 @@ int insider_hip_set_option(insider_hip_handle *h, const char *name, double value
  *   lambda1/lambda2/alpha/tuning/global_tol/sub_tol/max_iter as src/optimize.cpp:256-257
  *                (max_iter + 1 outer iterations are run: `iter <= max_iter`, :325)
  *   seed         replaces Rcpp::RNGScope / R's global RNG (src/RcppExports.cpp:90)
- *   out_*        train_rmse, test_rmse (NaN when tuning = 0: uninitialised in the reference, :264), loss
+ *   out_*        train_rmse, test_rmse (NaN when tuning = 0: uninitialised in the reference, :264), loss.  The sums of
+ *                squared residuals behind them are formed from statistics as differences of sums of squares: their error
+ *                is absolute, of the order 2^-52 * sum x^2 (an RMSE far below sqrt(2^-52 * sum x^2 / count) is noise), and a
+ *                per-gene sum that comes out negative counts as 0, so no RMSE is NaN for it; only the test sum of data with
+ *                NA entries is formed from explicit residuals and is accurate relative to itself
  *   traj         optional, traj_cap rows of INSIDER_TRAJ_STRIDE doubles; out_traj_rows rows written
  *   out_iters    value of `iter` when the loop ended
  * inc_continuous must be 1 exactly when the handle was created with continuous covariates

@@ -1774,6 +1774,11 @@ __global__ void k_unpack_A(const double *__restrict__ src_rows, int L, int K, in
     dst[t] = src_rows[(size_t)l * KP + k];
 }
 
+// A per-gene sum of squares from the statistics is a difference of sums of squares (yy - b'(q + g)): on a fit that is exact to
+// rounding it may come out negative, and is then taken as 0 (so that no RMSE is the square root of a negative sum; the rule of
+// the interaction GLM's RSS).  Written as a comparison, not fmax: a NaN of a failed solve stays a NaN.
+__device__ __forceinline__ double sumsq_or_zero(double v) { return v < 0.0 ? 0.0 : v; }
+
 // out[0..3] = {sum sse_train, sum sse_test, sum c^2, sum |c|}, out[6] = sum of a^2 over all row factors; one
 // block, fixed order.  out[4..5] (entry counts) are filled by the host.
 __global__ void __launch_bounds__(256) k_loss_reduce(const double *__restrict__ sse_train,
@@ -1784,7 +1789,12 @@ __global__ void __launch_bounds__(256) k_loss_reduce(const double *__restrict__ 
 {
     __shared__ double red[5][256];
     double s[5] = {0, 0, 0, 0, 0};
-    for (int j = threadIdx.x; j < p; j += 256) { s[0] += sse_train[j]; s[1] += sse_test[j]; s[2] += b2[j]; s[3] += b1[j]; }
+    for (int j = threadIdx.x; j < p; j += 256) {
+        s[0] += sumsq_or_zero(sse_train[j]);
+        s[1] += sumsq_or_zero(sse_test[j]);
+        s[2] += b2[j];
+        s[3] += b1[j];
+    }
     for (int i = threadIdx.x; i < SL * KP; i += 256) if (i % KP < K) s[4] += Astack[i] * Astack[i];
     for (int q = 0; q < 5; ++q) red[q][threadIdx.x] = s[q];
     __syncthreads();
