@@ -13,14 +13,12 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
+from tests.support import relerr  # noqa: E402
+
 # the alternative kernel forms a case is re-run under (tools/fuzz_repro.sh; test_fuzz_outliers_*): per-entry list statistics
 # on both sides, the group and the LDS-resident CD kernels, single-pass solves, the look-up form of the column statistics
 FORMS = ({}, {"col_factored": 0, "row_merged": 0}, {"cd_variant": 1}, {"cd_variant": 2}, {"cd_pass1": 0},
          {"row_counts": 0, "col_factored": 2})
-
-
-def relerr(a, b):
-    return np.linalg.norm(np.asarray(a) - np.asarray(b)) / max(np.linalg.norm(np.asarray(b)), 1e-300)
 
 
 def draw_case(rng):

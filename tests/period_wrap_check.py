@@ -12,13 +12,10 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 assert os.environ.get("INSIDER_HIP_LIB") and os.environ.get("INSIDER_ORACLE_LIB"), "variant builds required"
 from insider_amd import api, workloads  # noqa: E402
 from oracle import c_oracle  # noqa: E402  (test infrastructure: the checker)
+from tests.support import relerr  # noqa: E402
 
 PERIOD = 64
 bad = 0
-
-
-def relerr(a, b):
-    return np.linalg.norm(np.asarray(a) - np.asarray(b)) / max(np.linalg.norm(np.asarray(b)), 1e-300)
 
 
 def report(name, ok, detail):

@@ -1,45 +1,18 @@
-"""Host-side checks of the gene-set enrichment (insider_hip_enrichment): the symbols are declared, listed and exported; the
-sampler of include/insider_sample.h (through insider_hip_enrichment_sample, which opens no device) equals its numpy mirror
-posthoc.gs_sample_host(), is a bijection and includes every position equally often; the yardstick posthoc.enrichment_host()
-equals a brute-force running sum over all p positions; p, NES, Benjamini-Hochberg, the hypergeometric tail and the leading
-edge on a case computed by hand; flatio.read_gmt(); every argument the library refuses is refused on the host with the
-outputs untouched."""
+"""Host-side checks of the gene-set enrichment (insider_hip_enrichment): the sampler of include/insider_sample.h (through
+insider_hip_enrichment_sample, which opens no device) equals its numpy mirror posthoc.gs_sample_host(), is a bijection and
+includes every position equally often; the yardstick posthoc.enrichment_host() equals a brute-force running sum over all p
+positions; p, NES, Benjamini-Hochberg, the hypergeometric tail and the leading edge on a case computed by hand;
+flatio.read_gmt(); every argument the library refuses is refused on the host with the outputs untouched."""
 import ctypes as C
 import math
-import os
-import re
 
 import numpy as np
 import pytest
 
-import __graft_entry__ as ge
 from insider_amd import _lib, api, fit, flatio, posthoc
+from tests.support import lib  # noqa: F401  (fixture)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 I32 = C.c_int32
-
-
-@pytest.fixture(scope="module")
-def lib():
-    ge.build()
-    return _lib.load()
-
-
-def test_symbols_are_declared_listed_and_exported(lib):
-    hdr = open(os.path.join(ROOT, "include", "insider_hip.h")).read()
-    assert re.search(r"\bint insider_hip_enrichment\s*\(", hdr)
-    assert re.search(r"\bdouble insider_hip_last_enrichment_ms\s*\(\s*void\s*\)", hdr)
-    assert re.search(r"\bint insider_hip_enrichment_sample\s*\(", hdr)
-    for name in ("insider_hip_enrichment", "insider_hip_last_enrichment_ms", "insider_hip_enrichment_sample"):
-        assert name in _lib.SYMBOLS
-        assert getattr(lib, name) is not None
-    assert len(lib.insider_hip_enrichment.argtypes) == 16
-    assert lib.insider_hip_last_enrichment_ms.restype is C.c_double
-    from insider_amd import _build
-    files = [os.path.basename(f) for f in _build.source_files()]
-    assert "insider_enrich.hpp" in files and "insider_sample.h" in files       # both feed the library's source hash
-    src = open(os.path.join(ROOT, "insider_amd", "csrc", "insider_enrich.hpp")).read()
-    assert re.search(r"GS_MAX_SET = 4096;", src) and api.ENRICH_MAX_SET == 4096
 
 
 # ---- the sampler ------------------------------------------------------------------------------------------------------------

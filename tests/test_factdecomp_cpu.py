@@ -1,43 +1,19 @@
-"""Host-side checks of the per-factor decomposition (insider_hip_factor_decomposition): the symbol is declared, listed and
-exported, the numpy yardstick posthoc.factor_decomposition_host() agrees with a naive triple loop and, summed over the
-factors, with the per-gene yardstick, fd_derived() marks empty genes, factor_summary() pools the genes, and the command line
-accepts --factor-decomposition."""
-import os
-import re
+"""Host-side checks of the per-factor decomposition (insider_hip_factor_decomposition): the numpy yardstick
+posthoc.factor_decomposition_host() agrees with a naive triple loop and, summed over the factors, with the per-gene
+yardstick, fd_derived() marks empty genes, factor_summary() pools the genes, and the command line accepts
+--factor-decomposition."""
+import functools
 
 import numpy as np
 import pytest
 
-import __graft_entry__ as ge
-from insider_amd import _lib, fit, posthoc
+from insider_amd import fit, posthoc
+from tests.support import problem
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 RAW = ("n", "sum_x", "sum_xx", "rss", "sum_h", "sum_hh", "sum_rh")
 
 
-@pytest.fixture(scope="module")
-def lib():
-    ge.build()
-    return _lib.load()
-
-
-def test_symbol_is_declared_listed_and_exported(lib):
-    hdr = open(os.path.join(ROOT, "include", "insider_hip.h")).read()
-    assert re.search(r"\bint insider_hip_factor_decomposition\s*\(", hdr)
-    assert '"fd_path"' in hdr
-    assert "insider_hip_factor_decomposition" in _lib.SYMBOLS
-    assert lib.insider_hip_factor_decomposition is not None
-
-
-def _problem(seed, n=7, p=5, counts=(3, 2), m=1, K=3):
-    rng = np.random.default_rng(seed)
-    X = rng.standard_normal((n, p)) + 0.5
-    lev = np.column_stack([rng.integers(1, L + 1, n) for L in counts]).astype(np.int32)
-    Z = rng.standard_normal((n, m)) if m else None
-    A = [rng.standard_normal((L, K)) for L in counts] + ([rng.standard_normal((m, K))] if m else [])
-    Cm = rng.standard_normal((K, p))
-    mask = rng.random((n, p)) < 0.7
-    return X, lev, Z, mask, A, Cm
+_problem = functools.partial(problem, n=7, p=5, counts=(3, 2), m=1, K=3)
 
 
 def test_host_record_matches_a_naive_triple_loop():

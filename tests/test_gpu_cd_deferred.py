@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 from insider_amd import _lib, api, workloads
+from tests.support import need_gpu, relerr  # noqa: F401  (need_gpu: autouse fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -20,16 +21,6 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 _spec = importlib.util.spec_from_file_location("cd_deferred_golden", os.path.join(os.path.dirname(HERE), "tools", "cd_deferred_golden.py"))
 gen = importlib.util.module_from_spec(_spec)
 _spec.loader.exec_module(gen)
-
-
-def relerr(a, b):
-    return np.linalg.norm(np.asarray(a) - np.asarray(b)) / max(np.linalg.norm(np.asarray(b)), 1e-300)
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _need_gpu():
-    if _lib.device_count() < 1:
-        pytest.fail("no HIP device visible: -m gpu tests need the MI355X box")
 
 
 @pytest.fixture(scope="module")

@@ -15,20 +15,11 @@ import numpy as np
 import pytest
 
 from insider_amd import _lib, api, workloads
+from tests.support import need_gpu, relerr  # noqa: F401  (need_gpu: autouse fixture)
 
 pytestmark = pytest.mark.gpu
 
 UNCAPPED = 1 << 24
-
-
-def relerr(a, b):
-    return np.linalg.norm(np.asarray(a) - np.asarray(b)) / max(np.linalg.norm(np.asarray(b)), 1e-300)
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _need_gpu():
-    if _lib.device_count() < 1:
-        pytest.fail("no HIP device visible: -m gpu tests need the MI355X box")
 
 
 @pytest.fixture(scope="module", autouse=True)

@@ -17,7 +17,8 @@ import os
 import numpy as np
 import pytest
 
-from insider_amd import _lib, api, workloads
+from insider_amd import api, workloads
+from tests.support import need_gpu, relerr  # noqa: F401  (need_gpu: autouse fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -25,16 +26,6 @@ PATHS = {"fast": dict(row_merged=2, col_factored=2, row_counts=0), "pair": dict(
          "lists": dict(row_merged=0, col_factored=0), "default": dict()}
 SLAB_GENES = 192
 SWEEP_CAP = 300
-
-
-def relerr(a, b):
-    return np.linalg.norm(np.asarray(a) - np.asarray(b)) / max(np.linalg.norm(np.asarray(b)), 1e-300)
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _need_gpu():
-    if _lib.device_count() < 1:
-        pytest.fail("no HIP device visible: -m gpu tests need the MI355X box")
 
 
 def _slab(name):

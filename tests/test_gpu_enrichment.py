@@ -21,8 +21,8 @@ import functools
 import numpy as np
 import pytest
 
-import __graft_entry__ as ge
 from insider_amd import _lib, api, posthoc
+from tests.support import bits, lib  # noqa: F401  (lib: fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -32,12 +32,6 @@ OUTS = (("es", np.float64, 12345.678), ("peak", np.int32, -77), ("n_ge", np.int3
 EXACT = ("es", "peak", "n_ge", "n_same", "hits_nonzero")
 M_LIST = (1, 2, 15, 63, 64, 65, 127, 128, 129, 300)
 U = 2.0 ** -52
-
-
-@pytest.fixture(scope="module")
-def lib():
-    ge.build()
-    return _lib.load()
 
 
 def call(lib, sc, ptr, genes, weight, nperm, seed=api.DEFAULT_SEED):
@@ -73,10 +67,6 @@ def make_sets(p, rng):
     rest = np.setdiff1d(np.arange(p), base)
     sets += [base, base.copy()[::-1], np.concatenate([base[:m // 2], rng.choice(rest, m - m // 2, replace=False)])]
     return sets
-
-
-def bits(r):
-    return b"".join(r[name].tobytes() for name, _, _ in OUTS)
 
 
 # ---- 1. exact arithmetic ----------------------------------------------------------------------------------------------------
@@ -228,7 +218,8 @@ def test_subsets_repeats_and_seeds(lib):
     sets = make_sets(p, rng)
     ptr, genes = csr(sets)
     full = call(lib, sc, ptr, genes, 1, nperm, seed=3)
-    assert bits(call(lib, sc, ptr, genes, 1, nperm, seed=3)) == bits(full)                  # repeated calls: identical bytes
+    names = [name for name, _, _ in OUTS]
+    assert bits(call(lib, sc, ptr, genes, 1, nperm, seed=3), names) == bits(full, names)    # repeated calls: identical bytes
     rows = [3, 1]
     part = call(lib, sc[rows], ptr, genes, 1, nperm, seed=3)                                # some of the profiles
     for name, _, _ in OUTS:

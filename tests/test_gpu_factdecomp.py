@@ -10,10 +10,13 @@ them, the fit is a K-term dot product per block (error < (B K + m) 2^-53 of the 
 in some order on either side (< n 2^-53 of the sum of absolute terms), the products with C[k][j] and the fma add a few more
 units: fewer than (n + B K + m + 8) 2^-53 enter a slot, which is below 1e-12 for n + B K + m < 9000; every shape here has
 n + B K + m < 9000 (the largest: n = 3001, B K = 16)."""
+import functools
+
 import numpy as np
 import pytest
 
 from insider_amd import _lib, api, posthoc, workloads
+from tests.support import GENES_3_5_7, close_resident, factors, planted, resident, same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -23,38 +26,11 @@ SUMS = ("n", "sum_x", "sum_xx", "rss", "sum_h", "sum_hh", "sum_rh")
 EMPTY = {"all": (), "train": (5, 7), "test": (3, 7)}
 
 
-def _levels(rng, n, counts):
-    lev = np.empty((n, len(counts)), dtype=np.int32)
-    for i, L in enumerate(counts):
-        v = np.concatenate([np.arange(1, L + 1), rng.integers(1, L + 1, size=n - L)])
-        lev[:, i] = rng.permutation(v)
-    return np.asfortranarray(lev)
-
-
 def _data(n, p, counts, m=0, seed=0):
     """A data set with train, test and NA entries; gene 3 has no test entry, gene 5 no train entry, gene 7 is all NA (as far
     as p reaches)."""
-    rng = np.random.default_rng(seed)
-    X = np.asfortranarray(rng.standard_normal((n, p)) + 0.3)
-    lev = _levels(rng, n, counts)
-    u = rng.random((n, p))
-    tr = u < 0.6
-    te = (u >= 0.6) & (u < 0.85)
-    if p > 7:
-        te[:, 3] = False
-        tr[:, 5] = False
-        tr[:, 7] = te[:, 7] = False
-    Z = np.asfortranarray(rng.standard_normal((n, m))) if m else None
-    ds = api.InsiderData(X, lev, np.asfortranarray(tr, dtype=np.uint8), np.asfortranarray(te, dtype=np.uint8),
-                         ctns_confounder=Z)
-    return ds, X, lev, Z, {"all": None, "train": tr, "test": te}
-
-
-def _factors(rng, counts, m, K, p):
-    A = [np.asfortranarray(rng.standard_normal((L, K))) for L in counts]
-    if m:
-        A.append(np.asfortranarray(rng.standard_normal((m, K))))
-    return A, np.asfortranarray(rng.standard_normal((K, p)))
+    d = planted(n, p, counts, m, seed, empty=GENES_3_5_7)
+    return (resident(*d),) + d
 
 
 def _scales(X, lev, Z, mask, A, Cm):
@@ -89,9 +65,7 @@ def _check(got, X, lev, Z, mask, A, Cm):
     return ref
 
 
-def _same_bits(a, b):
-    for k in SUMS:
-        assert np.array_equal(a[k], b[k]), k
+_same_bits = functools.partial(same_bits, keys=SUMS)
 
 
 @pytest.fixture(scope="module")
@@ -104,7 +78,7 @@ def two():
 @pytest.mark.parametrize("K", [1, 16, 17, 63])
 def test_records_match_host(two, K):
     ds, X, lev, Z, masks = two
-    A, Cm = _factors(np.random.default_rng(K), (5, 3), 0, K, X.shape[1])
+    A, Cm = factors(np.random.default_rng(K), (5, 3), 0, K, X.shape[1])
     for e in ENTRIES:
         got = ds.factor_decomposition(A, Cm, entries=e)
         assert ds.info("fd_path") == 1       # 2 K <= 126 columns: one window
@@ -120,7 +94,7 @@ def test_records_match_host(two, K):
 def test_two_continuous_columns(K):
     ds, X, lev, Z, masks = _data(203, 157, (5, 3), m=2, seed=2)
     try:
-        A, Cm = _factors(np.random.default_rng(K), (5, 3), 2, K, X.shape[1])
+        A, Cm = factors(np.random.default_rng(K), (5, 3), 2, K, X.shape[1])
         for e in ENTRIES:
             got = ds.factor_decomposition(A, Cm, entries=e, inc_continuous=1)
             assert got["sum_h"].shape == (4, K, 157)
@@ -136,7 +110,7 @@ def test_edges(n, p, counts, K):
     past anything a block could stage (the kernel stages rows of the per-sample embeddings, never level tables)."""
     ds, X, lev, Z, masks = _data(n, p, counts, seed=n + p)
     try:
-        A, Cm = _factors(np.random.default_rng(n), counts, 0, K, p)
+        A, Cm = factors(np.random.default_rng(n), counts, 0, K, p)
         for e in ENTRIES:
             got = ds.factor_decomposition(A, Cm, entries=e)
             assert ds.info("fd_path") == 1
@@ -150,7 +124,7 @@ def test_five_blocks_at_k63_run_every_column_window():
     counts = (2, 3, 4, 5, 6)
     ds, X, lev, Z, masks = _data(131, 97, counts, seed=50)
     try:
-        A, Cm = _factors(np.random.default_rng(63), counts, 0, 63, X.shape[1])
+        A, Cm = factors(np.random.default_rng(63), counts, 0, 63, X.shape[1])
         for e in ENTRIES:
             got = ds.factor_decomposition(A, Cm, entries=e)
             assert ds.info("fd_path") == 2
@@ -162,7 +136,7 @@ def test_five_blocks_at_k63_run_every_column_window():
 
 def test_zero_row_of_c_gives_zero_slots(two):
     ds, X, lev, Z, masks = two
-    A, Cm = _factors(np.random.default_rng(33), (5, 3), 0, 7, X.shape[1])
+    A, Cm = factors(np.random.default_rng(33), (5, 3), 0, 7, X.shape[1])
     Cm[2] = 0.0
     Cm[6] = 0.0
     for e in ENTRIES:
@@ -174,7 +148,7 @@ def test_zero_row_of_c_gives_zero_slots(two):
 
 def test_repeat_clone_and_remask_return_the_same_bits(two):
     ds, X, lev, Z, masks = two
-    A, Cm = _factors(np.random.default_rng(21), (5, 3), 0, 30, X.shape[1])
+    A, Cm = factors(np.random.default_rng(21), (5, 3), 0, 30, X.shape[1])
     cl = ds.clone()
     rm = ds.remask(masks["train"], masks["test"])
     try:
@@ -188,30 +162,6 @@ def test_repeat_clone_and_remask_return_the_same_bits(two):
         rm.close()
 
 
-def test_leaves_optimize_bit_identical():
-    w = workloads.small()
-
-    def run(with_fd):
-        ds = api.InsiderData(w.X, w.levels, w.M_train, w.M_test)
-        try:
-            A = [a.copy(order="F") for a in w.A0]
-            Cm = w.C0.copy(order="F")
-            if with_fd:
-                for e in ENTRIES:
-                    ds.factor_decomposition(A, Cm, entries=e)
-                with pytest.raises(_lib.InsiderError):
-                    ds.factor_decomposition(A, Cm, inc_continuous=1)
-            return ds.optimize(A, Cm, w.K, w.lam, w.lam, w.alpha, tuning=1, max_iter=5, seed=3)
-        finally:
-            ds.close()
-
-    ref, got = run(False), run(True)
-    for a, b in zip(ref["row_matrices"].values(), got["row_matrices"].values()):
-        assert np.array_equal(a, b)
-    assert np.array_equal(ref["column_factor"], got["column_factor"])
-    assert np.array_equal(ref["traj"], got["traj"], equal_nan=True)
-
-
 @pytest.mark.parametrize("K", [1, 11])
 def test_sums_over_factors_match_the_variance_decomposition(two, K):
     """sum_k sum_h[b, k] = sum_g[b], sum_k sum_rh[b, k] = sum_rg[b], equal base slots and, with K = 1, sum_hh[b, 0] =
@@ -219,7 +169,7 @@ def test_sums_over_factors_match_the_variance_decomposition(two, K):
     scale is the sum over k of this one's, taken over the selected entries, so it is no larger) and the host sum over k
     adds fewer than K 2^-53 of the scale: (2e-12 + K 2^-53) x the sum over k of the scales."""
     ds, X, lev, Z, masks = two
-    A, Cm = _factors(np.random.default_rng(12 + K), (5, 3), 0, K, X.shape[1])
+    A, Cm = factors(np.random.default_rng(12 + K), (5, 3), 0, K, X.shape[1])
     for e in ENTRIES:
         f = ds.factor_decomposition(A, Cm, entries=e)
         g = ds.variance_decomposition(A, Cm, entries=e)
@@ -235,12 +185,6 @@ def test_sums_over_factors_match_the_variance_decomposition(two, K):
         for fk in ("sum_h", "sum_rh"):
             err = np.abs(f[fk][2] - f[fk][:2].sum(axis=0))
             assert np.all(err <= tol * sc[fk][2]), (e, fk)
-
-
-def _close_resident(obj):
-    for v in obj.values():
-        if isinstance(v, api.InsiderData):
-            v.close()
 
 
 def test_after_fit_and_summary():
@@ -270,12 +214,12 @@ def test_after_fit_and_summary():
         assert np.all(np.diff(got["drop_one"][-1][got["order"]]) <= 0)
         assert np.array_equal(got["loading_nnz"], np.count_nonzero(Cm, axis=1))
     finally:
-        _close_resident(obj)
+        close_resident(obj)
 
 
 def test_argument_errors(two):
     ds, X, lev, Z, masks = two
-    A, Cm = _factors(np.random.default_rng(17), (5, 3), 0, 4, X.shape[1])
+    A, Cm = factors(np.random.default_rng(17), (5, 3), 0, 4, X.shape[1])
 
     def status(fn):
         with pytest.raises(_lib.InsiderError) as e:
@@ -285,7 +229,7 @@ def test_argument_errors(two):
     assert status(lambda: ds.factor_decomposition(A, Cm, entries="held-out")) == _lib.ERR_ARG
     assert status(lambda: ds.factor_decomposition(A, Cm, inc_continuous=1)) == _lib.ERR_ARG
     assert status(lambda: ds.factor_decomposition(A, Cm, inc_continuous=2)) == _lib.ERR_ARG
-    A64, C64 = _factors(np.random.default_rng(1), (5, 3), 0, 64, X.shape[1])
+    A64, C64 = factors(np.random.default_rng(1), (5, 3), 0, 64, X.shape[1])
     assert status(lambda: ds.factor_decomposition(A64, C64)) == _lib.ERR_UNSUPPORTED
     # the same checks inside the library (the C ABI called directly)
     lib = _lib.load()
@@ -300,18 +244,6 @@ def test_argument_errors(two):
                                                 _lib.ptr(out)) == _lib.ERR_UNSUPPORTED
     assert lib.insider_hip_factor_decomposition(ds._h, Aptrs, _lib.ptr(Cw), 0, 4, 1, None) == _lib.ERR_ARG
     assert np.all(out == 0)
-
-
-def test_refuses_a_sharded_handle():
-    w = workloads.small(n=48, p=64, K=3)
-    ds = api.InsiderData(w.X, w.levels, w.M_train, w.M_test)
-    try:
-        ds.set_shard(0, 0, 2, allreduce=lambda ptr, count, stream: None)
-        with pytest.raises(_lib.InsiderError) as e:
-            ds.factor_decomposition(w.A0, w.C0)
-        assert e.value.status == _lib.ERR_UNSUPPORTED
-    finally:
-        ds.close()
 
 
 def test_cli_writes_the_decomposition(tmp_path):

@@ -14,8 +14,9 @@ Every shape keeps p >= 2 K (cond2 at most about 40).  Each check prints its larg
 import numpy as np
 import pytest
 
-from insider_amd import _lib, api
+from insider_amd import _lib
 from tests import glm_reference as gr
+from tests.support import SPLIT_80_20, factors, levels, masks, resident
 
 pytestmark = pytest.mark.gpu
 
@@ -29,23 +30,15 @@ def _cdiv(a, b):
     return -(-a // b)
 
 
-def _levels(rng, n, counts):
-    lev = np.empty((n, len(counts)), dtype=np.int32)
-    for i, L in enumerate(counts):
-        v = np.concatenate([np.arange(1, L + 1), rng.integers(1, L + 1, size=n - L)])
-        lev[:, i] = rng.permutation(v)
-    return np.asfortranarray(lev)
-
-
 class _Data:
     def __init__(self, n, p, m=0, seed=0, X=None):
         rng = np.random.default_rng(seed)
         self.X = np.asfortranarray(rng.standard_normal((n, p)) if X is None else X)
-        self.lev = _levels(rng, n, COUNTS)
-        tr = np.asfortranarray(rng.random((n, p)) < 0.8, dtype=np.uint8)
+        self.lev = levels(rng, n, COUNTS)
+        tr, te = masks(rng, n, p, empty=SPLIT_80_20)
         self.Z = np.asfortranarray(rng.standard_normal((n, m))) if m else None
         self.m = m
-        self.ds = api.InsiderData(self.X, self.lev, tr, np.asfortranarray(1 - tr, dtype=np.uint8), ctns_confounder=self.Z)
+        self.ds = resident(self.X, self.lev, self.Z, {"train": tr, "test": te})
 
     def close(self):
         self.ds.close()
@@ -67,10 +60,7 @@ def data():
 
 
 def _factors(rng, K, p, m=0):
-    A = [np.asfortranarray(rng.standard_normal((L, K))) for L in COUNTS]
-    if m:
-        A.append(np.asfortranarray(rng.standard_normal((m, K))))
-    return A, np.asfortranarray(rng.standard_normal((K, p)))
+    return factors(rng, COUNTS, m, K, p)
 
 
 def _resid(d, A, Cm, sub):

@@ -17,8 +17,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
-import __graft_entry__ as ge
 from insider_amd import _lib, api, posthoc
+from tests.support import bits, lib  # noqa: F401  (lib: fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -30,12 +30,7 @@ METRIC = {COS: "cosine", EUC: "euclidean"}
 U52 = 2.0 ** -52
 NAMES_D = ("centers", "dist", "dist2", "traj", "final_inertia")
 NAMES_I = ("label", "second", "sizes", "iters", "converged", "best")
-
-
-@pytest.fixture(scope="module")
-def lib():
-    ge.build()
-    return _lib.load()
+NAMES = NAMES_D + NAMES_I
 
 
 def call(lib, P, k, metric, init=None, restarts=1, max_iter=0, seed=0x1D5EED, N=None, D=None, expect=_lib.OK, null=(),
@@ -88,10 +83,6 @@ def rows_equal(got, ref):
         assert np.array_equal(got[n], ref[n]), n
     for n in ("dist", "dist2"):
         assert np.array_equal(got[n], ref[n], equal_nan=True), n
-
-
-def bits(r, names=NAMES_D + NAMES_I):
-    return b"".join(np.asarray(r[n]).tobytes() for n in names)
 
 
 # ---- 1. exact arithmetic (Euclidean) -------------------------------------------------------------------------------------------
@@ -305,9 +296,9 @@ def test_windows_and_repeats_are_bit_identical(lib, metric):
         part = call(lib, Q, k, metric, init=init, pptr=window(P, s))
         assert bits(part, rows) == bits({n: full[n][s:s + m] for n in rows}, rows), (s, m)
         copy = call(lib, Q, k, metric, init=init)                               # the same window from a buffer of its own
-        assert bits(copy) == bits(part)
+        assert bits(copy, NAMES) == bits(part, NAMES)
     runs3 = [call(lib, P, k, metric, restarts=3, max_iter=50, seed=5) for _ in range(3)]
-    assert bits(runs3[0]) == bits(runs3[1]) == bits(runs3[2])
+    assert bits(runs3[0], NAMES) == bits(runs3[1], NAMES) == bits(runs3[2], NAMES)
     assert lib.insider_hip_last_kmeans_ms() > 0.0
 
 

@@ -9,11 +9,13 @@ tests/test_gpu_sampdecomp.py.  The device forms the expanded sum s0 - 2 P1 + P2,
 embeddings and a sum adds fewer than p terms on either side: fewer than (p + K + 8) 2^-53 of the scale, below 1e-12 for
 p + K < 9000 (every shape here).  The counts are compared exactly."""
 import ctypes as C
+import functools
 
 import numpy as np
 import pytest
 
-from insider_amd import _lib, api, posthoc, workloads
+from insider_amd import _lib, api, posthoc
+from tests.support import SAMPLES_3_5_7, close_resident, factors, levels, masks, planted, resident, same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -21,41 +23,13 @@ ENTRIES = ("all", "train", "test")
 EMPTY = {"all": (), "train": (5, 7), "test": (3, 7)}
 
 
-def _levels(rng, n, counts):
-    lev = np.empty((n, len(counts)), dtype=np.int32)
-    for i, L in enumerate(counts):
-        v = np.concatenate([np.arange(1, L + 1), rng.integers(1, L + 1, size=n - L)])
-        lev[:, i] = rng.permutation(v)
-    return np.asfortranarray(lev)
-
-
-def _masks(rng, n, p):
-    """Train, test and NA entries; sample 3 has no test entry, sample 5 no train entry, sample 7 is all NA."""
-    u = rng.random((n, p))
-    tr = u < 0.6
-    te = (u >= 0.6) & (u < 0.85)
-    te[3] = False
-    tr[5] = False
-    tr[7] = te[7] = False
-    return tr, te
+# train, test and NA entries; sample 3 has no test entry, sample 5 no train entry, sample 7 is all NA
+_masks = functools.partial(masks, empty=SAMPLES_3_5_7)
 
 
 def _data(n, p, counts, m=0, seed=0):
-    rng = np.random.default_rng(seed)
-    X = np.asfortranarray(rng.standard_normal((n, p)) + 0.3)
-    lev = _levels(rng, n, counts)
-    tr, te = _masks(rng, n, p)
-    Z = np.asfortranarray(rng.standard_normal((n, m))) if m else None
-    ds = api.InsiderData(X, lev, np.asfortranarray(tr, dtype=np.uint8), np.asfortranarray(te, dtype=np.uint8),
-                         ctns_confounder=Z)
-    return ds, X, lev, Z, {"all": None, "train": tr, "test": te}
-
-
-def _factors(rng, counts, m, K, p):
-    A = [np.asfortranarray(rng.standard_normal((L, K))) for L in counts]
-    if m:
-        A.append(np.asfortranarray(rng.standard_normal((m, K))))
-    return A, np.asfortranarray(rng.standard_normal((K, p)))
+    d = planted(n, p, counts, m, seed, empty=SAMPLES_3_5_7)
+    return (resident(*d),) + d
 
 
 def _scale(X, lev, Z, mask, A, Cm, cov, cand=None):
@@ -85,8 +59,7 @@ def _check(got, X, lev, Z, mask, A, Cm, cov, cand=None):
     return ref, sc
 
 
-def _same_bits(a, b):
-    assert np.array_equal(a["sse"], b["sse"]) and np.array_equal(a["n"], b["n"])
+_same_bits = functools.partial(same_bits, keys=("sse", "n"))
 
 
 @pytest.fixture(scope="module")
@@ -99,7 +72,7 @@ def two():
 @pytest.mark.parametrize("K", [1, 16, 17, 63])
 def test_records_match_host(two, K):
     ds, X, lev, Z, masks = two
-    A, Cm = _factors(np.random.default_rng(K), (5, 3), 0, K, X.shape[1])
+    A, Cm = factors(np.random.default_rng(K), (5, 3), 0, K, X.shape[1])
     for cov in (0, 1):
         for e in ENTRIES:
             got = ds.level_scores(A, Cm, cov, entries=e)
@@ -119,7 +92,7 @@ def test_level_tiles_and_windows(L):
     beyond: a last tile of 1, 15 and 16 live columns, a second window of one tile."""
     ds, X, lev, Z, masks = _data(203, 37, (L, 3), seed=L)
     try:
-        A, Cm = _factors(np.random.default_rng(L + 1), (L, 3), 0, 5, X.shape[1])
+        A, Cm = factors(np.random.default_rng(L + 1), (L, 3), 0, 5, X.shape[1])
         for e in ("all", "train"):
             got = ds.level_scores(A, Cm, 0, entries=e)
             assert ds.info("ls_path") == (1 if L <= 128 else 2)
@@ -133,7 +106,7 @@ def test_slabs(two, slabs):
     """157 genes in 1, 2, 3, 7 slabs (no even split, no multiple of the 16 genes of a staging step) and the automatic count:
     the same sums within the bound, the same bits for the same setting; a tiny partial budget lowers the automatic count."""
     ds, X, lev, Z, masks = two
-    A, Cm = _factors(np.random.default_rng(40), (5, 3), 0, 9, X.shape[1])
+    A, Cm = factors(np.random.default_rng(40), (5, 3), 0, 9, X.shape[1])
     ds.set_option("ls_slabs", slabs)
     try:
         a = ds.level_scores(A, Cm, 0, entries="train")
@@ -165,7 +138,7 @@ def test_partial_sample_tiles(n):
     sample; 257: a fifth block of one sample."""
     ds, X, lev, Z, masks = _data(n, 37, (4, 3), seed=n)
     try:
-        A, Cm = _factors(np.random.default_rng(n), (4, 3), 0, 7, X.shape[1])
+        A, Cm = factors(np.random.default_rng(n), (4, 3), 0, 7, X.shape[1])
         for slabs in (0, 2):
             ds.set_option("ls_slabs", slabs)
             for e in ENTRIES:
@@ -181,7 +154,7 @@ def test_other_blocks(counts, m, cov):
     ds, X, lev, Z, masks = _data(131, 97, counts, m=m, seed=len(counts) + 10 * m)
     try:
         for K in (5, 33):
-            A, Cm = _factors(np.random.default_rng(K + m), counts, m, K, X.shape[1])
+            A, Cm = factors(np.random.default_rng(K + m), counts, m, K, X.shape[1])
             for e in ENTRIES:
                 got = ds.level_scores(A, Cm, cov, entries=e, inc_continuous=1 if m else 0)
                 _check(got, X, lev, Z, masks[e], A, Cm, cov)
@@ -192,7 +165,7 @@ def test_other_blocks(counts, m, cov):
 def test_candidates(two):
     ds, X, lev, Z, masks = two
     rng = np.random.default_rng(61)
-    A, Cm = _factors(rng, (5, 3), 0, 12, X.shape[1])
+    A, Cm = factors(rng, (5, 3), 0, 12, X.shape[1])
     for cov in (0, 1):
         own = ds.level_scores(A, Cm, cov, entries="train")
         _same_bits(own, ds.level_scores(A, Cm, cov, entries="train", candidates=A[cov]))
@@ -211,7 +184,7 @@ def test_assigned_column_is_the_sample_decomposition_rss(two):
     """sse[i, assigned_i - 1] is sample_decomposition()'s rss[i] within the sum of the two calls' bounds (both 1e-12 of the same
     scale: with the assigned level's G the scale above is that call's sum (|x| + F)^2), and n agrees exactly."""
     ds, X, lev, Z, masks = two
-    A, Cm = _factors(np.random.default_rng(12), (5, 3), 0, 11, X.shape[1])
+    A, Cm = factors(np.random.default_rng(12), (5, 3), 0, 11, X.shape[1])
     rows = np.arange(203)
     for cov in (0, 1):
         for e in ENTRIES:
@@ -231,8 +204,8 @@ def test_planted_swaps_are_found(cov):
     least 15 entries: the relative gap between best and second is far above any rounding (above 8 in the host form)."""
     rng = np.random.default_rng(100 + cov)
     n, p, K, counts = 203, 157, 6, (5, 3)
-    truth = _levels(rng, n, counts)
-    A, Cm = _factors(rng, counts, 0, K, p)
+    truth = levels(rng, n, counts)
+    A, Cm = factors(rng, counts, 0, K, p)
     X = np.asfortranarray(sum(A[b][truth[:, b] - 1] for b in range(2)) @ Cm + 0.5 * rng.standard_normal((n, p)))
     tr, te = _masks(rng, n, p)
     swapped = rng.choice(np.setdiff1d(np.arange(n), (3, 5, 7)), size=10, replace=False)
@@ -257,7 +230,7 @@ def test_planted_swaps_are_found(cov):
 def test_argument_errors_leave_the_outputs_untouched(two):
     ds, X, lev, Z, masks = two
     n = X.shape[0]
-    A, Cm = _factors(np.random.default_rng(17), (5, 3), 0, 4, X.shape[1])
+    A, Cm = factors(np.random.default_rng(17), (5, 3), 0, 4, X.shape[1])
 
     def status(fn):
         with pytest.raises(_lib.InsiderError) as e:
@@ -273,7 +246,7 @@ def test_argument_errors_leave_the_outputs_untouched(two):
     assert status(lambda: ds.level_scores(A, Cm, 0, inc_continuous=2)) == _lib.ERR_ARG
     assert status(lambda: ds.level_scores(A, Cm, 0, candidates=np.zeros((0, 4)))) == _lib.ERR_ARG
     assert status(lambda: ds.level_scores(A, Cm, 0, candidates=np.zeros((3, 5)))) == _lib.ERR_ARG
-    A64, C64 = _factors(np.random.default_rng(1), (5, 3), 0, 64, X.shape[1])
+    A64, C64 = factors(np.random.default_rng(1), (5, 3), 0, 64, X.shape[1])
     assert status(lambda: ds.level_scores(A64, C64, 0)) == _lib.ERR_UNSUPPORTED
     # the same checks inside the library (the C ABI called directly): sentinel-filled outputs stay as they are
     lib = _lib.load()
@@ -299,7 +272,7 @@ def test_argument_errors_leave_the_outputs_untouched(two):
 def test_continuous_block_is_not_a_candidate_covariate():
     ds, X, lev, Z, masks = _data(40, 21, (3, 2), m=2, seed=9)
     try:
-        A, Cm = _factors(np.random.default_rng(2), (3, 2), 2, 3, X.shape[1])
+        A, Cm = factors(np.random.default_rng(2), (3, 2), 2, 3, X.shape[1])
         _, Cw, Aptrs = ds._marshal(A, Cm, 3, 1)
         sse, cnt = np.full((40, 3), -7.0, order="F"), np.full(40, -7.0)
         assert _lib.load().insider_hip_level_scores(ds._h, Aptrs, _lib.ptr(Cw), 1, 3, 1, 2, None, 0, _lib.ptr(sse),
@@ -312,26 +285,9 @@ def test_continuous_block_is_not_a_candidate_covariate():
         ds.close()
 
 
-def test_refuses_a_sharded_handle():
-    w = workloads.small(n=48, p=64, K=3)
-    ds = api.InsiderData(w.X, w.levels, w.M_train, w.M_test)
-    try:
-        ds.set_shard(0, 0, 2, allreduce=lambda ptr, count, stream: None)
-        with pytest.raises(_lib.InsiderError) as e:
-            ds.level_scores(w.A0, w.C0, 0)
-        assert e.value.status == _lib.ERR_UNSUPPORTED
-        _, Cw, Aptrs = ds._marshal(w.A0, w.C0, 3, 0)
-        sse, cnt = np.full((48, int(ds.n_levels[0])), -7.0, order="F"), np.full(48, -7.0)
-        assert _lib.load().insider_hip_level_scores(ds._h, Aptrs, _lib.ptr(Cw), 0, 3, 1, 0, None, 0, _lib.ptr(sse),
-                                                    _lib.ptr(cnt)) == _lib.ERR_UNSUPPORTED
-        assert np.all(sse == -7.0) and np.all(cnt == -7.0)
-    finally:
-        ds.close()
-
-
 def test_clone_and_remask_score_their_own_masks(two):
     ds, X, lev, Z, masks = two
-    A, Cm = _factors(np.random.default_rng(21), (5, 3), 0, 30, X.shape[1])
+    A, Cm = factors(np.random.default_rng(21), (5, 3), 0, 30, X.shape[1])
     tr2, te2 = _masks(np.random.default_rng(77), *X.shape)
     cl = ds.clone()
     rm = ds.remask(np.asfortranarray(tr2, dtype=np.uint8), np.asfortranarray(te2, dtype=np.uint8))
@@ -345,40 +301,6 @@ def test_clone_and_remask_score_their_own_masks(two):
     finally:
         cl.close()
         rm.close()
-
-
-def test_leaves_optimize_bit_identical():
-    w = workloads.small(n=90, p=140, K=6)
-
-    def run(with_ls):
-        ds = api.InsiderData(w.X, w.levels, w.M_train, w.M_test)
-        try:
-            A = [a.copy(order="F") for a in w.A0]
-            Cm = w.C0.copy(order="F")
-            r1 = ds.optimize(A, Cm, w.K, w.lam, w.lam, w.alpha, tuning=1, max_iter=12, seed=3)
-            A1 = [a.copy(order="F") for a in r1["row_matrices"].values()]
-            C1 = r1["column_factor"].copy(order="F")
-            if with_ls:
-                for e in ENTRIES:
-                    for cov in range(ds.c):
-                        ds.level_scores(A1, C1, cov, entries=e)
-                with pytest.raises(_lib.InsiderError):
-                    ds.level_scores(A1, C1, ds.c)
-            return ds.optimize(A1, C1, w.K, w.lam, w.lam, w.alpha, tuning=1, max_iter=12, seed=3)
-        finally:
-            ds.close()
-
-    ref, got = run(False), run(True)
-    for a, b in zip(ref["row_matrices"].values(), got["row_matrices"].values()):
-        assert np.array_equal(a, b)
-    assert np.array_equal(ref["column_factor"], got["column_factor"])
-    assert np.array_equal(ref["traj"], got["traj"], equal_nan=True)
-
-
-def _close_resident(obj):
-    for v in obj.values():
-        if isinstance(v, api.InsiderData):
-            v.close()
 
 
 def test_fitted_object_and_command_line(tmp_path):
@@ -398,7 +320,7 @@ def test_fitted_object_and_command_line(tmp_path):
         _check(d, obj["data"], obj["confounder"], None, mask, A, Cm, 1)
         assert d["best"].shape == (n,) and d["confusion"].shape == (2, 2) and d["confusion"].sum() == n
     finally:
-        _close_resident(obj)
+        close_resident(obj)
     from insider_amd import fit as fit_cli
     np.save(tmp_path / "X.npy", data)
     np.save(tmp_path / "L.npy", conf)

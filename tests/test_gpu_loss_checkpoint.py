@@ -31,6 +31,7 @@ import pytest
 
 from insider_amd import _lib, api
 from tests import loss_reference as lr
+from tests.support import need_gpu  # noqa: F401  (need_gpu: autouse fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -41,12 +42,6 @@ REACHED = []   # (col_solver, col_eval) of every call of test a
 TIMES = {"create": 0.0, "optimize": 0.0, "reference (CPU seconds, on threads)": 0.0}
 POOL = ThreadPoolExecutor(8)
 LOCK = threading.Lock()
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _need_gpu():
-    if _lib.device_count() < 1:
-        pytest.fail("no HIP device visible: -m gpu tests need the MI355X box")
 
 
 def names(ds):

@@ -13,8 +13,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
-import __graft_entry__ as ge
 from insider_amd import _lib, api, posthoc
+from tests.support import bits, lib  # noqa: F401  (lib: fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -23,12 +23,6 @@ IDX_SENTINEL = -77
 SCORE_SENTINEL = 12345.678
 COS, DOT = 0, 1
 METRIC = {COS: "cosine", DOT: "dot"}
-
-
-@pytest.fixture(scope="module")
-def lib():
-    ge.build()
-    return _lib.load()
 
 
 def call(lib, Q, B, k, metric, off, nq=None, nb=None, K=None, qptr=None, expect=_lib.OK, null=()):
@@ -65,8 +59,7 @@ def equal(got, ref):
     assert np.array_equal(got["score"], ref["score"], equal_nan=True)
 
 
-def bits(r):
-    return r["index"].tobytes() + r["score"].tobytes()
+OUT = ("index", "score")
 
 
 # ---- 1. exact arithmetic, dot metric --------------------------------------------------------------------------------------
@@ -248,13 +241,13 @@ def test_windows_and_repeats_are_bit_identical(lib, metric):
     _, B = real_inputs(K, 1, nb, 55)
     full = call(lib, B, B, k, metric, 0, qptr=window(B, 0))
     again = call(lib, B, B, k, metric, 0, qptr=window(B, 0))
-    assert bits(full) == bits(again)
+    assert bits(full, OUT) == bits(again, OUT)
     for s, m in ((0, 1), (1, 16), (7, 33), (233, 17)):
         Q = np.asfortranarray(B[:, s:s + m])
         part = call(lib, Q, B, k, metric, s, qptr=window(B, s))
-        assert bits(part) == bits(dict(index=full["index"][s:s + m], score=full["score"][s:s + m])), (s, m)
+        assert bits(part, OUT) == bits(dict(index=full["index"][s:s + m], score=full["score"][s:s + m]), OUT), (s, m)
         copy = call(lib, Q, B, k, metric, s)                                 # the same window from a buffer of its own
-        assert bits(copy) == bits(part)
+        assert bits(copy, OUT) == bits(part, OUT)
 
 
 # ---- 6. C-ABI errors ------------------------------------------------------------------------------------------------------------

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from insider_amd import _lib, api, posthoc, workloads
+from tests.support import GENES_3_5, close_resident, factors, planted, resident
 
 pytestmark = pytest.mark.gpu
 
@@ -21,35 +22,10 @@ LISTS = ("rows", "cols", "z")
 SENT_I, SENT_Z = -7, -123.25
 
 
-def _levels(rng, n, counts):
-    lev = np.empty((n, len(counts)), dtype=np.int32)
-    for i, L in enumerate(counts):
-        v = np.concatenate([np.arange(1, L + 1), rng.integers(1, L + 1, size=n - L)])
-        lev[:, i] = rng.permutation(v)
-    return np.asfortranarray(lev)
-
-
 def _data(n, p, counts, m=0, seed=0):
     """A data set with train, test and NA entries; gene 3 has no test entry, gene 5 no train entry."""
-    rng = np.random.default_rng(seed)
-    X = np.asfortranarray(rng.standard_normal((n, p)) + 0.3)
-    lev = _levels(rng, n, counts)
-    u = rng.random((n, p))
-    tr = u < 0.6
-    te = (u >= 0.6) & (u < 0.85)
-    te[:, 3] = False
-    tr[:, 5] = False
-    Z = np.asfortranarray(rng.standard_normal((n, m))) if m else None
-    ds = api.InsiderData(X, lev, np.asfortranarray(tr, dtype=np.uint8), np.asfortranarray(te, dtype=np.uint8),
-                         ctns_confounder=Z)
-    return ds, X, lev, Z, {"all": None, "train": tr, "test": te}
-
-
-def _factors(rng, counts, m, K, p):
-    A = [np.asfortranarray(rng.standard_normal((L, K))) for L in counts]
-    if m:
-        A.append(np.asfortranarray(rng.standard_normal((m, K))))
-    return A, np.asfortranarray(rng.standard_normal((K, p)))
+    d = planted(n, p, counts, m, seed, empty=GENES_3_5)
+    return (resident(*d),) + d
 
 
 def _center_scale(X, lev, Z, mask, A, Cm):
@@ -152,7 +128,7 @@ def two():
 def two_ref(two):
     """One set of factors, center / scale and a gap threshold per entries choice on the shared data set, with its reference."""
     ds, X, lev, Z, masks = two
-    A, Cm = _factors(np.random.default_rng(30), (5, 3), 0, 30, X.shape[1])
+    A, Cm = factors(np.random.default_rng(30), (5, 3), 0, 30, X.shape[1])
     center, scale = _center_scale(X, lev, Z, None, A, Cm)
     z, _ = _zref(X, lev, Z, A, Cm, center, scale)
     out = dict(A=A, Cm=Cm, center=center, scale=scale, z=z)
@@ -166,7 +142,7 @@ def two_ref(two):
 def test_calls_match_host(two, K):
     """n = 203: the sample trip is only partly filled; p = 157: the last block of the flag pass holds one gene."""
     ds, X, lev, Z, masks = two
-    A, Cm = _factors(np.random.default_rng(K), (5, 3), 0, K, X.shape[1])
+    A, Cm = factors(np.random.default_rng(K), (5, 3), 0, K, X.shape[1])
     _run_all_entries(ds, X, lev, Z, masks, A, Cm)
     assert ds.info("ol_path") == 1
 
@@ -178,7 +154,7 @@ def test_trip_boundaries(n):
     counts = (2,) if n == 3 else (3, 2)
     ds, X, lev, Z, masks = _data(n, 11, counts, seed=n)
     try:
-        A, Cm = _factors(np.random.default_rng(n + 1), counts, 0, 7, 11)
+        A, Cm = factors(np.random.default_rng(n + 1), counts, 0, 7, 11)
         _run_all_entries(ds, X, lev, Z, masks, A, Cm, center_mask="all")
     finally:
         ds.close()
@@ -189,7 +165,7 @@ def test_blocks_and_continuous_covariates(counts, m):
     ds, X, lev, Z, masks = _data(131, 97, counts, m=m, seed=len(counts) + 10 * m)
     try:
         for K in (5, 33):
-            A, Cm = _factors(np.random.default_rng(K + m), counts, m, K, X.shape[1])
+            A, Cm = factors(np.random.default_rng(K + m), counts, m, K, X.shape[1])
             _run_all_entries(ds, X, lev, Z, masks, A, Cm, inc=1 if m else 0)
     finally:
         ds.close()
@@ -201,7 +177,7 @@ def test_scan_boundaries():
     assert p >= 2051
     ds, X, lev, Z, masks = _data(9, p, (3, 2), seed=12)
     try:
-        A, Cm = _factors(np.random.default_rng(13), (3, 2), 0, 4, p)
+        A, Cm = factors(np.random.default_rng(13), (3, 2), 0, 4, p)
         _run_all_entries(ds, X, lev, Z, masks, A, Cm, center_mask="all")
     finally:
         ds.close()
@@ -283,7 +259,7 @@ def test_global_table_form():
     memory; forcing that form on a small data set gives the same bits as the staged one."""
     ds, X, lev, Z, masks = _data(3701, 45, (3500, 3), seed=4)
     try:
-        A, Cm = _factors(np.random.default_rng(9), (3500, 3), 0, 17, X.shape[1])
+        A, Cm = factors(np.random.default_rng(9), (3500, 3), 0, 17, X.shape[1])
         center, scale = _center_scale(X, lev, Z, masks["train"], A, Cm)
         z, _ = _zref(X, lev, Z, A, Cm, center, scale)
         t = _gap_threshold(_selected_absz(z, masks["train"], scale))
@@ -294,7 +270,7 @@ def test_global_table_form():
         ds.close()
     ds, X, lev, Z, masks = _data(150, 77, (4, 6), m=2, seed=5)
     try:
-        A, Cm = _factors(np.random.default_rng(2), (4, 6), 2, 31, X.shape[1])
+        A, Cm = factors(np.random.default_rng(2), (4, 6), 2, 31, X.shape[1])
         center, scale = _center_scale(X, lev, Z, masks["train"], A, Cm)
         z, _ = _zref(X, lev, Z, A, Cm, center, scale)
         t = _gap_threshold(_selected_absz(z, masks["train"], scale))
@@ -333,51 +309,11 @@ def test_repeatable_bits_clone_and_remask(two, two_ref):
             assert np.array_equal(a[k], other[k]), k
 
 
-def test_leaves_optimize_bit_identical():
-    w = workloads.small(n=90, p=140, K=6)
-
-    def run(with_ol):
-        ds = api.InsiderData(w.X, w.levels, w.M_train, w.M_test)
-        try:
-            A = [a.copy(order="F") for a in w.A0]
-            Cm = w.C0.copy(order="F")
-            r1 = ds.optimize(A, Cm, w.K, w.lam, w.lam, w.alpha, tuning=1, max_iter=12, seed=3)
-            A1 = [a.copy(order="F") for a in r1["row_matrices"].values()]
-            C1 = r1["column_factor"].copy(order="F")
-            if with_ol:
-                for e in ENTRIES:
-                    got = ds.outliers(A1, C1, np.ones(140), threshold=0.5, entries=e)
-                    assert got["total"] > 0
-                with pytest.raises(_lib.InsiderError):
-                    ds.outliers(A1, C1, np.ones(140), inc_continuous=1)
-            return ds.optimize(A1, C1, w.K, w.lam, w.lam, w.alpha, tuning=1, max_iter=12, seed=3)
-        finally:
-            ds.close()
-
-    ref, got = run(False), run(True)
-    for a, b in zip(ref["row_matrices"].values(), got["row_matrices"].values()):
-        assert np.array_equal(a, b)
-    assert np.array_equal(ref["column_factor"], got["column_factor"])
-    assert np.array_equal(ref["traj"], got["traj"], equal_nan=True)
-
-
-def test_refuses_a_sharded_handle():
-    w = workloads.small(n=48, p=64, K=3)
-    ds = api.InsiderData(w.X, w.levels, w.M_train, w.M_test)
-    try:
-        ds.set_shard(0, 0, 2, allreduce=lambda ptr, count, stream: None)
-        with pytest.raises(_lib.InsiderError) as e:
-            ds.outliers(w.A0, w.C0, np.ones(64))
-        assert e.value.status == _lib.ERR_UNSUPPORTED
-    finally:
-        ds.close()
-
-
 def test_argument_errors(two):
     ds, X, lev, Z, masks = two
     n, p = X.shape
-    A, Cm = _factors(np.random.default_rng(17), (5, 3), 0, 4, p)
-    A64, C64 = _factors(np.random.default_rng(1), (5, 3), 0, 64, p)
+    A, Cm = factors(np.random.default_rng(17), (5, 3), 0, 4, p)
+    A64, C64 = factors(np.random.default_rng(1), (5, 3), 0, 64, p)
     scale = np.ones(p)
 
     def status(fn):
@@ -449,9 +385,7 @@ def test_end_to_end_finds_planted_spikes():
         for k in LISTS + COUNTS:
             assert np.array_equal(got[k], again[k]), k
     finally:
-        for v in obj.values():
-            if isinstance(v, api.InsiderData):
-                v.close()
+        close_resident(obj)
 
 
 def test_cli_writes_the_calls(tmp_path):
@@ -523,6 +457,4 @@ def test_c2_after_fit():
         assert np.array_equal(np.bincount(got["cols"], minlength=p), got["gene_low"] + got["gene_high"])
         assert np.array_equal(np.bincount(got["rows"], minlength=n), got["sample_low"] + got["sample_high"])
     finally:
-        for v in obj.values():
-            if isinstance(v, api.InsiderData):
-                v.close()
+        close_resident(obj)

@@ -8,12 +8,9 @@ import numpy as np
 import pytest
 
 from insider_amd import _lib, api, workloads
+from tests.support import need_gpu, relerr  # noqa: F401  (need_gpu: autouse fixture)
 
 pytestmark = pytest.mark.gpu
-
-
-def relerr(a, b):
-    return np.linalg.norm(np.asarray(a) - np.asarray(b)) / max(np.linalg.norm(np.asarray(b)), 1e-300)
 
 
 def _rand_factors(w, seed, scale=0.5):
@@ -30,12 +27,6 @@ def _cp(w):
 
 def _R(w, A):
     return sum(A[i][w.levels[:, i] - 1, :] for i in range(w.levels.shape[1]))
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _need_gpu():
-    if _lib.device_count() < 1:
-        pytest.fail("no HIP device visible: -m gpu tests need the MI355X box")
 
 
 # the masked statistics have several implementations each (per-entry lists / factored per level, the column side also

@@ -6,35 +6,14 @@ import numpy as np
 import pytest
 
 from insider_amd import _lib, api, posthoc, workloads
+from tests.support import SPLIT_80_20, close_resident, factors, planted, resident
 
 pytestmark = pytest.mark.gpu
 
 
-def _levels(rng, n, counts):
-    lev = np.empty((n, len(counts)), dtype=np.int32)
-    for i, L in enumerate(counts):
-        v = np.concatenate([np.arange(1, L + 1), rng.integers(1, L + 1, size=n - L)])
-        lev[:, i] = rng.permutation(v)
-    return np.asfortranarray(lev)
-
-
 def _data(n, p, counts, m=0, seed=0):
-    rng = np.random.default_rng(seed)
-    X = np.asfortranarray(rng.standard_normal((n, p)))
-    lev = _levels(rng, n, counts)
-    tr = np.asfortranarray(rng.random((n, p)) < 0.8, dtype=np.uint8)
-    te = np.asfortranarray(1 - tr, dtype=np.uint8)
-    Z = np.asfortranarray(rng.standard_normal((n, m))) if m else None
-    ds = api.InsiderData(X, lev, tr, te, ctns_confounder=Z)
-    return ds, X, lev, Z
-
-
-def _factors(rng, counts, m, K, p):
-    A = [np.asfortranarray(rng.standard_normal((L, K))) for L in counts]
-    if m:
-        A.append(np.asfortranarray(rng.standard_normal((m, K))))
-    Cm = np.asfortranarray(rng.standard_normal((K, p)))
-    return A, Cm
+    d = planted(n, p, counts, m, seed, offset=0.0, empty=SPLIT_80_20)
+    return (resident(*d),) + d[:3]
 
 
 def _np_resid(X, lev, Z, A, Cm, sub):
@@ -62,7 +41,7 @@ def cat():
 def test_residual_matches_numpy(cat, K):
     ds, X, lev, Z = cat
     rng = np.random.default_rng(K)
-    A, Cm = _factors(rng, (5, 3), 0, K, X.shape[1])
+    A, Cm = factors(rng, (5, 3), 0, K, X.shape[1])
     for sub in ([1, 1], [1, 0], [0, 1], [0, 0]):
         ref = _np_resid(X, lev, Z, A, Cm, sub)
         for rows in ((0, 133), (5, 37), (17, 18), (120, 133), (3, 131)):
@@ -77,7 +56,7 @@ def test_residual_with_continuous_covariates():
     try:
         rng = np.random.default_rng(3)
         for K in (5, 33):
-            A, Cm = _factors(rng, (4, 6), 2, K, X.shape[1])
+            A, Cm = factors(rng, (4, 6), 2, K, X.shape[1])
             for sub in ([1, 1, 1], [1, 0, 1], [0, 0, 1], [1, 1, 0]):
                 ref = _np_resid(X, lev, Z, A, Cm, sub)
                 got = ds.residual(A, Cm, subtract=sub, rows=(9, 141), inc_continuous=1)
@@ -89,7 +68,7 @@ def test_residual_with_continuous_covariates():
 def test_residual_streams_through_several_staging_slabs(cat):
     ds, X, lev, Z = cat
     rng = np.random.default_rng(9)
-    A, Cm = _factors(rng, (5, 3), 0, 12, X.shape[1])
+    A, Cm = factors(rng, (5, 3), 0, 12, X.shape[1])
     ref = _np_resid(X, lev, Z, A, Cm, [1, 1])
     try:
         for mb in (0.0, 0.05):        # 16 genes per slab; 48 genes per slab
@@ -118,7 +97,7 @@ def test_interaction_glm_matches_glm_interaction(big, G):
     ds, X, lev, Z = big
     rng = np.random.default_rng(G)
     K = 7
-    A, Cm = _factors(rng, (7, 130), 0, K, X.shape[1])
+    A, Cm = factors(rng, (7, 130), 0, K, X.shape[1])
     group = rng.permutation(np.concatenate([np.arange(1, G + 1), rng.integers(1, G + 1, size=X.shape[0] - G)]))
     group = group.astype(np.int32)
     sub = [1, 0]
@@ -135,7 +114,7 @@ def test_interaction_glm_group_ids_with_gaps_and_zero(big):
     ds, X, lev, Z = big
     rng = np.random.default_rng(21)
     K = 9
-    A, Cm = _factors(rng, (7, 130), 0, K, X.shape[1])
+    A, Cm = factors(rng, (7, 130), 0, K, X.shape[1])
     G = 10
     group = rng.choice(np.array([0, 1, 3, 4, 7, 10], dtype=np.int32), size=X.shape[0])
     R = _np_resid(X, lev, Z, A, Cm, [1, 1])
@@ -155,7 +134,7 @@ def test_interaction_glm_aliased_dimensions(big):
     ds, X, lev, Z = big
     rng = np.random.default_rng(5)
     K = 8
-    A, Cm = _factors(rng, (7, 130), 0, K, X.shape[1])
+    A, Cm = factors(rng, (7, 130), 0, K, X.shape[1])
     group = lev[:, 0]
     for zero in ([3], [0, 6]):
         Cz = Cm.copy(order="F")
@@ -217,9 +196,7 @@ def test_glm_interaction_resident_end_to_end(tmp_path):
     assert coeff.shape == (lev[:, 1].max(), 5)
     np.testing.assert_allclose(coeff[:, keep], ref_c, rtol=1e-9, atol=0)
     np.testing.assert_allclose(pval[:, keep], ref_p, rtol=1e-7, atol=1e-300)
-    for d in obj.values():
-        if isinstance(d, api.InsiderData):
-            d.close()
+    close_resident(obj)
     # the command line: --interaction-glm writes the two matrices next to the factors
     from insider_amd import fit as fit_cli
     np.save(tmp_path / "X.npy", data)
@@ -276,7 +253,7 @@ def test_posthoc_calls_leave_optimize_bit_identical():
 def test_posthoc_on_a_clone(cat):
     ds, X, lev, Z = cat
     rng = np.random.default_rng(13)
-    A, Cm = _factors(rng, (5, 3), 0, 4, X.shape[1])
+    A, Cm = factors(rng, (5, 3), 0, 4, X.shape[1])
     cl = ds.clone()
     try:
         assert np.array_equal(cl.residual(A, Cm), ds.residual(A, Cm))
@@ -291,7 +268,7 @@ def test_posthoc_on_a_clone(cat):
 def test_posthoc_argument_errors(cat):
     ds, X, lev, Z = cat
     rng = np.random.default_rng(17)
-    A, Cm = _factors(rng, (5, 3), 0, 4, X.shape[1])
+    A, Cm = factors(rng, (5, 3), 0, 4, X.shape[1])
     group = lev[:, 0]
 
     def status(fn):

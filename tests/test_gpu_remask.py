@@ -13,20 +13,11 @@ import pytest
 
 from insider_amd import _lib, api, workloads
 from insider_amd._lib import InsiderError
+from tests.support import need_gpu, relerr  # noqa: F401  (need_gpu: autouse fixture)
 
 pytestmark = pytest.mark.gpu
 
 CHUNK = 128          # line pitch of the resident matrix: ldn = n rounded up to it (insider_kernels.hpp)
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _need_gpu():
-    if _lib.device_count() < 1:
-        pytest.fail("no HIP device visible: -m gpu tests need the MI355X box")
-
-
-def relerr(a, b):
-    return np.linalg.norm(np.asarray(a) - np.asarray(b)) / max(np.linalg.norm(np.asarray(b)), 1e-300)
 
 
 # the data sets of check 1: two covariates; NA entries; continuous covariates (m = 1, m = 2); one many-level covariate

@@ -18,10 +18,13 @@ The driver, on the planted case of tests/test_rescomp_cpu.py with the same seed:
 arithmetic orders of one iteration, so they stop at the same pass and agree far inside the iteration's own error.  Bounds:
 sv to 1e-10 relative, scores (relative to the component's largest score) and loadings to 1e-7.  Observed on the MI355X:
 see test_driver_matches_host_and_svd's docstring."""
+import functools
+
 import numpy as np
 import pytest
 
-from insider_amd import _lib, api, posthoc, workloads
+from insider_amd import _lib, api, posthoc
+from tests.support import SAMPLES_3_5_7_GENES_1_3, close_resident, factors, masks, planted, resident, same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -29,44 +32,14 @@ ENTRIES = ("all", "train", "test")
 TOL = 1e-9
 
 
-def _levels(rng, n, counts):
-    lev = np.empty((n, len(counts)), dtype=np.int32)
-    for i, L in enumerate(counts):
-        v = np.concatenate([np.arange(1, L + 1), rng.integers(1, L + 1, size=n - L)])
-        lev[:, i] = rng.permutation(v)
-    return np.asfortranarray(lev)
-
-
-def _masks(rng, n, p):
-    """Train, test and NA entries; sample 3 has no test entry, sample 5 no train entry, sample 7 is all NA; gene 1 has no
-    train entry, gene 3 no test entry."""
-    u = rng.random((n, p))
-    tr = u < 0.6
-    te = (u >= 0.6) & (u < 0.85)
-    te[3] = False
-    tr[5] = False
-    tr[7] = te[7] = False
-    tr[:, 1] = False
-    te[:, 3] = False
-    return tr, te
+# train, test and NA entries; sample 3 has no test entry, sample 5 no train entry, sample 7 is all NA; gene 1 has no train
+# entry, gene 3 no test entry
+_masks = functools.partial(masks, empty=SAMPLES_3_5_7_GENES_1_3)
 
 
 def _data(n, p, counts, m=0, seed=0):
-    rng = np.random.default_rng(seed)
-    X = np.asfortranarray(rng.standard_normal((n, p)) + 0.3)
-    lev = _levels(rng, n, counts)
-    tr, te = _masks(rng, n, p)
-    Z = np.asfortranarray(rng.standard_normal((n, m))) if m else None
-    ds = api.InsiderData(X, lev, np.asfortranarray(tr, dtype=np.uint8), np.asfortranarray(te, dtype=np.uint8),
-                         ctns_confounder=Z)
-    return ds, X, lev, Z, {"all": None, "train": tr, "test": te}
-
-
-def _factors(rng, counts, m, K, p):
-    A = [np.asfortranarray(rng.standard_normal((L, K))) for L in counts]
-    if m:
-        A.append(np.asfortranarray(rng.standard_normal((m, K))))
-    return A, np.asfortranarray(rng.standard_normal((K, p)))
+    d = planted(n, p, counts, m, seed, empty=SAMPLES_3_5_7_GENES_1_3)
+    return (resident(*d),) + d
 
 
 def _center_scale(rng, p):
@@ -115,9 +88,7 @@ def _check(got, X, lev, Z, mask, A, Cm, Q, center=None, scale=None, want_y=True)
     return ref
 
 
-def _same_bits(a, b):
-    for k in ("Z", "Y", "rss"):
-        assert (a[k] is None and b[k] is None) or np.array_equal(a[k], b[k]), k
+_same_bits = functools.partial(same_bits, keys=("Z", "Y", "rss"))
 
 
 # n: below one wave tile, no multiple of 16 or 64, three sample tiles of k_rc_fwd (and 5 chunks of k_rc_back, the last of 2 samples);
@@ -157,7 +128,7 @@ def test_products_match_host(n, p, q, K, m, entries, cs, slabs):
     ds, X, lev, Z, masks = _data(n, p, counts, m=m, seed=n + p + q + K)
     try:
         rng = np.random.default_rng(7 * n + p + q)
-        A, Cm = _factors(rng, counts, m, K, p)
+        A, Cm = factors(rng, counts, m, K, p)
         Q = rng.standard_normal((n, q))
         ce, sc = _center_scale(rng, p) if cs else (None, None)
         ds.set_option("rc_slabs", slabs)
@@ -194,7 +165,7 @@ def test_repeated_calls_and_the_z_only_form(two):
     bits of the full call."""
     ds, X, lev, Z, masks = two
     rng = np.random.default_rng(2)
-    A, Cm = _factors(rng, (5, 3), 0, 9, 150)
+    A, Cm = factors(rng, (5, 3), 0, 9, 150)
     Q = rng.standard_normal((130, 20))
     ce, sc = _center_scale(rng, 150)
     for slabs in (0, 3):
@@ -217,7 +188,7 @@ def test_repeated_calls_and_the_z_only_form(two):
 def test_clone_and_remask_use_their_own_masks(two):
     ds, X, lev, Z, masks = two
     rng = np.random.default_rng(21)
-    A, Cm = _factors(rng, (5, 3), 0, 30, 150)
+    A, Cm = factors(rng, (5, 3), 0, 30, 150)
     Q = rng.standard_normal((130, 13))
     tr2, te2 = _masks(np.random.default_rng(77), 130, 150)
     cl = ds.clone()
@@ -233,38 +204,10 @@ def test_clone_and_remask_use_their_own_masks(two):
         rm.close()
 
 
-def test_leaves_optimize_bit_identical():
-    w = workloads.small(n=90, p=140, K=6)
-
-    def run(with_rc):
-        ds = api.InsiderData(w.X, w.levels, w.M_train, w.M_test)
-        try:
-            A = [a.copy(order="F") for a in w.A0]
-            Cm = w.C0.copy(order="F")
-            r1 = ds.optimize(A, Cm, w.K, w.lam, w.lam, w.alpha, tuning=1, max_iter=12, seed=3)
-            A1 = [a.copy(order="F") for a in r1["row_matrices"].values()]
-            C1 = r1["column_factor"].copy(order="F")
-            if with_rc:
-                Q = np.random.default_rng(0).standard_normal((90, 10))
-                for e in ENTRIES:
-                    ds.residual_products(A1, C1, Q, entries=e)
-                with pytest.raises(_lib.InsiderError):
-                    ds.residual_products(A1, C1, Q[:-1])
-            return ds.optimize(A1, C1, w.K, w.lam, w.lam, w.alpha, tuning=1, max_iter=12, seed=3)
-        finally:
-            ds.close()
-
-    ref, got = run(False), run(True)
-    for a, b in zip(ref["row_matrices"].values(), got["row_matrices"].values()):
-        assert np.array_equal(a, b)
-    assert np.array_equal(ref["column_factor"], got["column_factor"])
-    assert np.array_equal(ref["traj"], got["traj"], equal_nan=True)
-
-
 def test_argument_errors_leave_the_outputs_untouched(two):
     ds, X, lev, Z, masks = two
     n, p = X.shape
-    A, Cm = _factors(np.random.default_rng(17), (5, 3), 0, 4, p)
+    A, Cm = factors(np.random.default_rng(17), (5, 3), 0, 4, p)
     Q = np.asfortranarray(np.random.default_rng(18).standard_normal((n, 3)))
 
     def status(fn):
@@ -281,7 +224,7 @@ def test_argument_errors_leave_the_outputs_untouched(two):
     assert status(lambda: ds.residual_products(A, Cm, np.full((n, 2), np.nan))) == _lib.ERR_ARG
     assert status(lambda: ds.residual_products(A, Cm, Q, scale=np.ones(p - 1))) == _lib.ERR_ARG
     assert status(lambda: ds.residual_products(A, Cm, Q, center=np.ones(p + 1))) == _lib.ERR_ARG
-    A64, C64 = _factors(np.random.default_rng(1), (5, 3), 0, 64, p)
+    A64, C64 = factors(np.random.default_rng(1), (5, 3), 0, 64, p)
     assert status(lambda: ds.residual_products(A64, C64, Q)) == _lib.ERR_UNSUPPORTED
     # the same checks inside the library (the C ABI called directly): sentinel-filled outputs stay as they are
     lib = _lib.load()
@@ -306,24 +249,6 @@ def test_argument_errors_leave_the_outputs_untouched(two):
     assert call() == _lib.OK                                  # and the valid call fills exactly p x 3, n x 3 and p
     assert np.all(Zo[:, :3] != -7.0) and np.all(Zo[:, 3] == -7.0) and np.all(Yo[:, 3] == -7.0) and np.all(ro >= 0)
     assert call(y=None, r=None) == _lib.OK                    # Y and rss are optional
-
-
-def test_refuses_a_sharded_handle():
-    w = workloads.small(n=48, p=64, K=3)
-    ds = api.InsiderData(w.X, w.levels, w.M_train, w.M_test)
-    try:
-        ds.set_shard(0, 0, 2, allreduce=lambda ptr, count, stream: None)
-        Q = np.asfortranarray(np.ones((48, 2)))
-        with pytest.raises(_lib.InsiderError) as e:
-            ds.residual_products(w.A0, w.C0, Q)
-        assert e.value.status == _lib.ERR_UNSUPPORTED
-        _, Cw, Aptrs = ds._marshal(w.A0, w.C0, 3, 0)
-        Zo, Yo, ro = np.full((64, 2), -7.0, order="F"), np.full((48, 2), -7.0, order="F"), np.full(64, -7.0)
-        assert _lib.load().insider_hip_residual_products(ds._h, Aptrs, _lib.ptr(Cw), 0, 3, 1, None, None, _lib.ptr(Q), 2,
-                                                         _lib.ptr(Zo), _lib.ptr(Yo), _lib.ptr(ro)) == _lib.ERR_UNSUPPORTED
-        assert np.all(Zo == -7.0) and np.all(Yo == -7.0) and np.all(ro == -7.0)
-    finally:
-        ds.close()
 
 
 def _planted(seed=11):
@@ -379,12 +304,6 @@ def test_driver_matches_host_and_svd():
     assert np.max(np.abs(std["sv"] - hstd["sv"]) / hstd["sv"]) <= 1e-10
 
 
-def _close_resident(obj):
-    for v in obj.values():
-        if isinstance(v, api.InsiderData):
-            v.close()
-
-
 def test_fitted_object_and_command_line(tmp_path):
     """posthoc.residual_components() on the resident handle of a fitted object against the host driver on its factors, and
     --residual-components of the command line: the five rc_* records with their shapes."""
@@ -405,7 +324,7 @@ def test_fitted_object_and_command_line(tmp_path):
         assert np.max(np.abs(d["sv"] - h["sv"]) / h["sv"]) <= 1e-10
         assert d["sample_scores"].shape == (n, 2) and d["gene_loadings"].shape == (p, 2)
     finally:
-        _close_resident(obj)
+        close_resident(obj)
     from insider_amd import fit as fit_cli
     np.save(tmp_path / "X.npy", data)
     np.save(tmp_path / "L.npy", conf)

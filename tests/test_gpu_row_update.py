@@ -14,26 +14,17 @@ import numpy as np
 import pytest
 
 from insider_amd import _lib, api, workloads
+from tests.support import need_gpu, relerr  # noqa: F401  (need_gpu: autouse fixture)
 
 pytestmark = pytest.mark.gpu
 
 BIT = {name: 1 << i for i, name in enumerate(_lib.ROW_KERNELS)}
 
 
-def relerr(a, b):
-    return np.linalg.norm(np.asarray(a) - np.asarray(b)) / max(np.linalg.norm(np.asarray(b)), 1e-300)
-
-
 def launched(ds):
     mask = int(ds.info("row_kernels"))
     assert mask & ~sum(BIT.values()) == 0, hex(mask)
     return {name for name, b in BIT.items() if mask & b}
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _need_gpu():
-    if _lib.device_count() < 1:
-        pytest.fail("no HIP device visible: -m gpu tests need the MI355X box")
 
 
 @pytest.fixture(scope="module", autouse=True)

@@ -8,11 +8,13 @@ slot adds fewer than p terms in some order on either side (< p 2^-53 of the sum 
 add a few more units: fewer than (p + K + 8) 2^-53 in all, below 1e-12 for p + K < 9000, which every shape here but c2
 satisfies (c2 states its own factor)."""
 import ctypes as C
+import functools
 
 import numpy as np
 import pytest
 
 from insider_amd import _lib, api, posthoc, workloads
+from tests.support import SAMPLES_3_5_7, close_resident, factors, planted, resident, same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -20,36 +22,10 @@ ENTRIES = ("all", "train", "test")
 SUMS = ("n", "sum_x", "sum_xx", "rss", "sum_g", "sum_gg", "sum_rg")
 
 
-def _levels(rng, n, counts):
-    lev = np.empty((n, len(counts)), dtype=np.int32)
-    for i, L in enumerate(counts):
-        v = np.concatenate([np.arange(1, L + 1), rng.integers(1, L + 1, size=n - L)])
-        lev[:, i] = rng.permutation(v)
-    return np.asfortranarray(lev)
-
-
 def _data(n, p, counts, m=0, seed=0):
     """A data set with train, test and NA entries; sample 3 has no test entry, sample 5 no train entry, sample 7 is all NA."""
-    rng = np.random.default_rng(seed)
-    X = np.asfortranarray(rng.standard_normal((n, p)) + 0.3)
-    lev = _levels(rng, n, counts)
-    u = rng.random((n, p))
-    tr = u < 0.6
-    te = (u >= 0.6) & (u < 0.85)
-    te[3] = False
-    tr[5] = False
-    tr[7] = te[7] = False
-    Z = np.asfortranarray(rng.standard_normal((n, m))) if m else None
-    ds = api.InsiderData(X, lev, np.asfortranarray(tr, dtype=np.uint8), np.asfortranarray(te, dtype=np.uint8),
-                         ctns_confounder=Z)
-    return ds, X, lev, Z, {"all": None, "train": tr, "test": te}
-
-
-def _factors(rng, counts, m, K, p):
-    A = [np.asfortranarray(rng.standard_normal((L, K))) for L in counts]
-    if m:
-        A.append(np.asfortranarray(rng.standard_normal((m, K))))
-    return A, np.asfortranarray(rng.standard_normal((K, p)))
+    d = planted(n, p, counts, m, seed, empty=SAMPLES_3_5_7)
+    return (resident(*d),) + d
 
 
 def _scale_terms(X, lev, Z, mask, A, Cm):
@@ -86,9 +62,7 @@ def _check(got, X, lev, Z, mask, A, Cm, rows=None, factor=1e-12):
     return ref
 
 
-def _same_bits(a, b):
-    for k in SUMS:
-        assert np.array_equal(a[k], b[k]), k
+_same_bits = functools.partial(same_bits, keys=SUMS)
 
 
 @pytest.fixture(scope="module")
@@ -101,7 +75,7 @@ def two():
 @pytest.mark.parametrize("K", [1, 16, 17, 63])
 def test_records_match_host(two, K):
     ds, X, lev, Z, masks = two
-    A, Cm = _factors(np.random.default_rng(K), (5, 3), 0, K, X.shape[1])
+    A, Cm = factors(np.random.default_rng(K), (5, 3), 0, K, X.shape[1])
     for e in ENTRIES:
         got = ds.sample_decomposition(A, Cm, entries=e)
         assert ds.info("sd_path") == 1
@@ -118,7 +92,7 @@ def test_slabs(two, slabs):
     """157 genes in 1, 2, 3, 7 slabs (no even split) and the automatic count: the same sums within the bound, the same
     bits for the same setting."""
     ds, X, lev, Z, masks = two
-    A, Cm = _factors(np.random.default_rng(40), (5, 3), 0, 9, X.shape[1])
+    A, Cm = factors(np.random.default_rng(40), (5, 3), 0, 9, X.shape[1])
     ds.set_option("sd_slabs", slabs)
     try:
         a = ds.sample_decomposition(A, Cm, entries="train")
@@ -142,7 +116,7 @@ def test_partial_waves_and_tiles(n):
     three samples."""
     ds, X, lev, Z, masks = _data(n, 61, (4, 3), m=1, seed=n)
     try:
-        A, Cm = _factors(np.random.default_rng(n), (4, 3), 1, 7, X.shape[1])
+        A, Cm = factors(np.random.default_rng(n), (4, 3), 1, 7, X.shape[1])
         for slabs in (0, 3):
             ds.set_option("sd_slabs", slabs)
             for e in ENTRIES:
@@ -158,7 +132,7 @@ def test_blocks_and_continuous_covariates(counts, m):
     ds, X, lev, Z, masks = _data(131, 97, counts, m=m, seed=len(counts) + 10 * m)
     try:
         for K in (5, 33):
-            A, Cm = _factors(np.random.default_rng(K + m), counts, m, K, X.shape[1])
+            A, Cm = factors(np.random.default_rng(K + m), counts, m, K, X.shape[1])
             for e in ENTRIES:
                 got = ds.sample_decomposition(A, Cm, entries=e, inc_continuous=1 if m else 0)
                 assert got["sum_g"].shape == (len(counts) + (1 if m else 0), X.shape[0])
@@ -172,7 +146,7 @@ def test_more_blocks_than_registers_hold():
     counts = (2, 3, 2, 4, 2, 3, 2, 2, 3, 2)
     ds, X, lev, Z, masks = _data(90, 41, counts, m=6, seed=77)
     try:
-        A, Cm = _factors(np.random.default_rng(5), counts, 6, 4, X.shape[1])
+        A, Cm = factors(np.random.default_rng(5), counts, 6, 4, X.shape[1])
         got = ds.sample_decomposition(A, Cm, entries="train", inc_continuous=1)
         _check(got, X, lev, Z, masks["train"], A, Cm)
     finally:
@@ -184,7 +158,7 @@ def test_global_table_form():
     are read from global memory; forcing that form on a small data set gives the same bits as the staged one."""
     ds, X, lev, Z, masks = _data(3701, 45, (3500, 3), seed=4)
     try:
-        A, Cm = _factors(np.random.default_rng(9), (3500, 3), 0, 17, X.shape[1])
+        A, Cm = factors(np.random.default_rng(9), (3500, 3), 0, 17, X.shape[1])
         for e in ENTRIES:
             got = ds.sample_decomposition(A, Cm, entries=e)
             assert ds.info("sd_path") == 2
@@ -193,7 +167,7 @@ def test_global_table_form():
         ds.close()
     ds, X, lev, Z, masks = _data(150, 77, (4, 6), m=2, seed=5)
     try:
-        A, Cm = _factors(np.random.default_rng(2), (4, 6), 2, 31, X.shape[1])
+        A, Cm = factors(np.random.default_rng(2), (4, 6), 2, 31, X.shape[1])
         staged = ds.sample_decomposition(A, Cm, entries="train", inc_continuous=1)
         assert ds.info("sd_path") == 1
         ds.set_option("vd_stage_kb", 0)
@@ -210,7 +184,7 @@ def test_totals_match_the_per_gene_call(two):
     bound applied to the grand totals: each side is off by fewer than (p + K + 8 + n) 2^-53 of the grand scale (its records'
     error plus the host sum of n or p records), 1e-13 for both sides together at this shape."""
     ds, X, lev, Z, masks = two
-    A, Cm = _factors(np.random.default_rng(12), (5, 3), 0, 11, X.shape[1])
+    A, Cm = factors(np.random.default_rng(12), (5, 3), 0, 11, X.shape[1])
     for e in ENTRIES:
         s = ds.sample_decomposition(A, Cm, entries=e)
         g = ds.variance_decomposition(A, Cm, entries=e)
@@ -223,7 +197,7 @@ def test_totals_match_the_per_gene_call(two):
 
 def test_clone_and_remask_return_the_same_bits(two):
     ds, X, lev, Z, masks = two
-    A, Cm = _factors(np.random.default_rng(21), (5, 3), 0, 30, X.shape[1])
+    A, Cm = factors(np.random.default_rng(21), (5, 3), 0, 30, X.shape[1])
     cl = ds.clone()
     rm = ds.remask(masks["train"], masks["test"])
     try:
@@ -234,39 +208,6 @@ def test_clone_and_remask_return_the_same_bits(two):
     finally:
         cl.close()
         rm.close()
-
-
-def test_leaves_optimize_bit_identical():
-    w = workloads.small(n=90, p=140, K=6)
-
-    def run(with_sd):
-        ds = api.InsiderData(w.X, w.levels, w.M_train, w.M_test)
-        try:
-            A = [a.copy(order="F") for a in w.A0]
-            Cm = w.C0.copy(order="F")
-            r1 = ds.optimize(A, Cm, w.K, w.lam, w.lam, w.alpha, tuning=1, max_iter=12, seed=3)
-            A1 = [a.copy(order="F") for a in r1["row_matrices"].values()]
-            C1 = r1["column_factor"].copy(order="F")
-            if with_sd:
-                for e in ENTRIES:
-                    ds.sample_decomposition(A1, C1, entries=e)
-                with pytest.raises(_lib.InsiderError):
-                    ds.sample_decomposition(A1, C1, inc_continuous=1)
-            return ds.optimize(A1, C1, w.K, w.lam, w.lam, w.alpha, tuning=1, max_iter=12, seed=3)
-        finally:
-            ds.close()
-
-    ref, got = run(False), run(True)
-    for a, b in zip(ref["row_matrices"].values(), got["row_matrices"].values()):
-        assert np.array_equal(a, b)
-    assert np.array_equal(ref["column_factor"], got["column_factor"])
-    assert np.array_equal(ref["traj"], got["traj"], equal_nan=True)
-
-
-def _close_resident(obj):
-    for v in obj.values():
-        if isinstance(v, api.InsiderData):
-            v.close()
 
 
 def test_interaction_column_fit_and_tune_handles():
@@ -306,7 +247,7 @@ def test_interaction_column_fit_and_tune_handles():
                     r = (X - sum(A[b][lev[:, b] - 1] @ Cm for b in range(3)))[(lev[:, 0] == l)[:, None] & mask]
                     np.testing.assert_allclose(got["rmse"][l - 1], np.sqrt(np.mean(r * r)), rtol=1e-9)
     finally:
-        _close_resident(obj)
+        close_resident(obj)
 
 
 def test_c2_after_fit():
@@ -326,12 +267,12 @@ def test_c2_after_fit():
         np.testing.assert_allclose(d["rmse"][rows], ref["rmse"], rtol=1e-9, atol=1e-12)
         assert d["r2"].shape == (n,) and d["explained"].shape == (2, n) and d["sum_rg"].shape == (2, n)
     finally:
-        _close_resident(obj)
+        close_resident(obj)
 
 
 def test_argument_errors(two):
     ds, X, lev, Z, masks = two
-    A, Cm = _factors(np.random.default_rng(17), (5, 3), 0, 4, X.shape[1])
+    A, Cm = factors(np.random.default_rng(17), (5, 3), 0, 4, X.shape[1])
 
     def status(fn):
         with pytest.raises(_lib.InsiderError) as e:
@@ -341,7 +282,7 @@ def test_argument_errors(two):
     assert status(lambda: ds.sample_decomposition(A, Cm, entries="held-out")) == _lib.ERR_ARG
     assert status(lambda: ds.sample_decomposition(A, Cm, inc_continuous=1)) == _lib.ERR_ARG
     assert status(lambda: ds.sample_decomposition(A, Cm, inc_continuous=2)) == _lib.ERR_ARG
-    A64, C64 = _factors(np.random.default_rng(1), (5, 3), 0, 64, X.shape[1])
+    A64, C64 = factors(np.random.default_rng(1), (5, 3), 0, 64, X.shape[1])
     assert status(lambda: ds.sample_decomposition(A64, C64)) == _lib.ERR_UNSUPPORTED
     # the same checks inside the library (the C ABI called directly)
     lib = _lib.load()
@@ -356,18 +297,6 @@ def test_argument_errors(two):
                                                 _lib.ptr(out)) == _lib.ERR_UNSUPPORTED
     assert lib.insider_hip_sample_decomposition(ds._h, Aptrs, _lib.ptr(Cw), 0, 4, 1, None) == _lib.ERR_ARG
     assert np.all(out == 0)
-
-
-def test_refuses_a_sharded_handle():
-    w = workloads.small(n=48, p=64, K=3)
-    ds = api.InsiderData(w.X, w.levels, w.M_train, w.M_test)
-    try:
-        ds.set_shard(0, 0, 2, allreduce=lambda ptr, count, stream: None)
-        with pytest.raises(_lib.InsiderError) as e:
-            ds.sample_decomposition(w.A0, w.C0)
-        assert e.value.status == _lib.ERR_UNSUPPORTED
-    finally:
-        ds.close()
 
 
 def test_cli_writes_the_decomposition(tmp_path):

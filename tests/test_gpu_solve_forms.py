@@ -38,6 +38,7 @@ import pytest
 
 from insider_amd import _lib, api
 from tests import solve_reference as sr
+from tests.support import need_gpu  # noqa: F401  (need_gpu: autouse fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -46,12 +47,6 @@ CHOL_DIAG_TOL = 5 * 2.0 ** -53 * (1 + 2.0 ** -50)            # a diagonal system
 EDGES = [1, 2, 15, 16, 17, 31, 32, 33, 47, 48, 49, 63]      # the register blocks and the pitches KP = 16, 32, 48, 64
 FWD_COND = 1e8 * (1 + 1e-6)                                  # the forward check runs up to cond 1e8 (module docstring)
 WORST = {}                                                   # (section, family, form) -> largest error / bound seen
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _need_gpu():
-    if _lib.device_count() < 1:
-        pytest.fail("no HIP device visible: -m gpu tests need the MI355X box")
 
 
 def _yardstick_name(form, K, route):

@@ -19,24 +19,15 @@ import math
 import numpy as np
 import pytest
 
-from insider_amd import _lib, api, workloads
+from insider_amd import api, workloads
 from tests import test_gpu_col_stats as cs
 from tests import test_gpu_row_update as ru
+from tests.support import need_gpu, relerr  # noqa: F401  (need_gpu: autouse fixture)
 
 pytestmark = pytest.mark.gpu
 
 MM_FAST_MIN = 16384
 MM_SLAB = 128
-
-
-def relerr(a, b):
-    return np.linalg.norm(np.asarray(a) - np.asarray(b)) / max(np.linalg.norm(np.asarray(b)), 1e-300)
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _need_gpu():
-    if _lib.device_count() < 1:
-        pytest.fail("no HIP device visible: -m gpu tests need the MI355X box")
 
 
 @pytest.fixture(scope="module", autouse=True)

@@ -35,9 +35,9 @@ import ctypes as C
 import numpy as np
 import pytest
 
-import __graft_entry__ as ge
 from insider_amd import _lib, api, posthoc
 from tests import tsne_reference as ref
+from tests.support import bits, lib  # noqa: F401  (lib: fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -45,12 +45,6 @@ NGUARD = 7
 SENTINEL = 12345.678
 U = 2.0 ** -52
 NAMES = ("Y", "kl_traj", "final_kl", "beta", "p_cond", "grad", "Z")
-
-
-@pytest.fixture(scope="module")
-def lib():
-    ge.build()
-    return _lib.load()
 
 
 def call(lib, idx, d2, perplexity=2.0, init=None, max_iter=0, exag_iters=250, kl_every=50, exaggeration=12.0, eta=0.0, seed=7,
@@ -82,10 +76,6 @@ def call(lib, idx, d2, perplexity=2.0, init=None, max_iter=0, exag_iters=250, kl
     rec["p_cond"] = rec["p_cond"].reshape(Np, kp)
     rec["final_kl"], rec["Z"] = float(rec["final_kl"][0]), float(rec["Z"][0])
     return rec
-
-
-def bits(r):
-    return b"".join(np.asarray(r[n]).tobytes() for n in NAMES)
 
 
 def random_graph(N, k, seed, dead=(), open_rows=(), equal_rows=(), far_rows=()):
@@ -280,10 +270,10 @@ def test_repeats_are_bit_identical_and_the_draw_is_the_hosts(lib):
     kw = dict(perplexity=3.0, max_iter=30, exag_iters=10, kl_every=7, seed=0xFEEDFACE12345)
     for slabs in (0, 3):
         runs = [call(lib, idx, d2, slabs=slabs, **kw) for _ in range(3)]
-        assert bits(runs[0]) == bits(runs[1]) == bits(runs[2])
+        assert bits(runs[0], NAMES) == bits(runs[1], NAMES) == bits(runs[2], NAMES)
         assert np.all(np.isfinite(runs[0]["kl_traj"])) and runs[0]["kl_traj"].shape == (5,)
     given = call(lib, idx, d2, init=posthoc.tsne_draw_host(kw["seed"], N), **kw)
-    assert bits(given) == bits(call(lib, idx, d2, **kw))
+    assert bits(given, NAMES) == bits(call(lib, idx, d2, **kw), NAMES)
     assert lib.insider_hip_last_tsne_ms() > 0.0
     # optional outputs may be absent; what is present does not change
     some = call(lib, idx, d2, null=(17, 18, 19, 20), **kw)

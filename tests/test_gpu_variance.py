@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from insider_amd import _lib, api, posthoc, workloads
+from tests.support import GENES_3_5, close_resident, factors, planted, resident
 
 pytestmark = pytest.mark.gpu
 
@@ -13,35 +14,10 @@ ENTRIES = ("all", "train", "test")
 SUMS = ("n", "sum_x", "sum_xx", "rss", "sum_g", "sum_gg", "sum_rg")
 
 
-def _levels(rng, n, counts):
-    lev = np.empty((n, len(counts)), dtype=np.int32)
-    for i, L in enumerate(counts):
-        v = np.concatenate([np.arange(1, L + 1), rng.integers(1, L + 1, size=n - L)])
-        lev[:, i] = rng.permutation(v)
-    return np.asfortranarray(lev)
-
-
 def _data(n, p, counts, m=0, seed=0):
     """A data set with train, test and NA entries; gene 3 has no test entry, gene 5 no train entry."""
-    rng = np.random.default_rng(seed)
-    X = np.asfortranarray(rng.standard_normal((n, p)) + 0.3)
-    lev = _levels(rng, n, counts)
-    u = rng.random((n, p))
-    tr = u < 0.6
-    te = (u >= 0.6) & (u < 0.85)
-    te[:, 3] = False
-    tr[:, 5] = False
-    Z = np.asfortranarray(rng.standard_normal((n, m))) if m else None
-    ds = api.InsiderData(X, lev, np.asfortranarray(tr, dtype=np.uint8), np.asfortranarray(te, dtype=np.uint8),
-                         ctns_confounder=Z)
-    return ds, X, lev, Z, {"all": None, "train": tr, "test": te}
-
-
-def _factors(rng, counts, m, K, p):
-    A = [np.asfortranarray(rng.standard_normal((L, K))) for L in counts]
-    if m:
-        A.append(np.asfortranarray(rng.standard_normal((m, K))))
-    return A, np.asfortranarray(rng.standard_normal((K, p)))
+    d = planted(n, p, counts, m, seed, empty=GENES_3_5)
+    return (resident(*d),) + d
 
 
 def _scales(X, lev, Z, mask, A, Cm):
@@ -84,7 +60,7 @@ def two():
 def test_records_match_host(two, K):
     ds, X, lev, Z, masks = two
     rng = np.random.default_rng(K)
-    A, Cm = _factors(rng, (5, 3), 0, K, X.shape[1])
+    A, Cm = factors(rng, (5, 3), 0, K, X.shape[1])
     for e in ENTRIES:
         got = ds.variance_decomposition(A, Cm, entries=e)
         assert ds.info("vd_path") == 1
@@ -102,7 +78,7 @@ def test_blocks_and_continuous_covariates(counts, m):
     ds, X, lev, Z, masks = _data(131, 97, counts, m=m, seed=len(counts) + 10 * m)
     try:
         for K in (5, 33):
-            A, Cm = _factors(np.random.default_rng(K + m), counts, m, K, X.shape[1])
+            A, Cm = factors(np.random.default_rng(K + m), counts, m, K, X.shape[1])
             for e in ENTRIES:
                 got = ds.variance_decomposition(A, Cm, entries=e, inc_continuous=1 if m else 0)
                 assert got["sum_g"].shape == (len(counts) + (1 if m else 0), X.shape[1])
@@ -116,7 +92,7 @@ def test_global_table_form():
     global memory; forcing that form on a small data set gives the same bits as the staged one."""
     ds, X, lev, Z, masks = _data(3701, 45, (3500, 3), seed=4)
     try:
-        A, Cm = _factors(np.random.default_rng(9), (3500, 3), 0, 17, X.shape[1])
+        A, Cm = factors(np.random.default_rng(9), (3500, 3), 0, 17, X.shape[1])
         for e in ENTRIES:
             got = ds.variance_decomposition(A, Cm, entries=e)
             assert ds.info("vd_path") == 2
@@ -125,7 +101,7 @@ def test_global_table_form():
         ds.close()
     ds, X, lev, Z, masks = _data(150, 77, (4, 6), m=2, seed=5)
     try:
-        A, Cm = _factors(np.random.default_rng(2), (4, 6), 2, 31, X.shape[1])
+        A, Cm = factors(np.random.default_rng(2), (4, 6), 2, 31, X.shape[1])
         staged = ds.variance_decomposition(A, Cm, entries="train", inc_continuous=1)
         assert ds.info("vd_path") == 1
         ds.set_option("vd_stage_kb", 0)
@@ -163,9 +139,7 @@ def test_interaction_column_fit_and_tune_handles():
             for k in ("tss", "r2", "rmse", "explained", "drop_one"):
                 np.testing.assert_allclose(d[k][..., live], ref[k][..., live], rtol=1e-9, atol=1e-12)
     finally:
-        for v in obj.values():
-            if isinstance(v, api.InsiderData):
-                v.close()
+        close_resident(obj)
 
 
 def test_c2_after_fit():
@@ -182,14 +156,12 @@ def test_c2_after_fit():
         np.testing.assert_allclose(d["r2"][genes], ref["r2"], rtol=1e-9, atol=1e-12)
         assert d["r2"].shape == (obj["data"].shape[1],) and d["explained"].shape == (2, obj["data"].shape[1])
     finally:
-        for v in obj.values():
-            if isinstance(v, api.InsiderData):
-                v.close()
+        close_resident(obj)
 
 
 def test_repeatable_bits_and_clone(two):
     ds, X, lev, Z, masks = two
-    A, Cm = _factors(np.random.default_rng(21), (5, 3), 0, 30, X.shape[1])
+    A, Cm = factors(np.random.default_rng(21), (5, 3), 0, 30, X.shape[1])
     a = ds.variance_decomposition(A, Cm, entries="test")
     b = ds.variance_decomposition(A, Cm, entries="test")
     cl = ds.clone()
@@ -201,36 +173,9 @@ def test_repeatable_bits_and_clone(two):
         assert np.array_equal(a[k], b[k]) and np.array_equal(a[k], c[k]), k
 
 
-def test_leaves_optimize_bit_identical():
-    w = workloads.small(n=90, p=140, K=6)
-
-    def run(with_vd):
-        ds = api.InsiderData(w.X, w.levels, w.M_train, w.M_test)
-        try:
-            A = [a.copy(order="F") for a in w.A0]
-            Cm = w.C0.copy(order="F")
-            r1 = ds.optimize(A, Cm, w.K, w.lam, w.lam, w.alpha, tuning=1, max_iter=12, seed=3)
-            A1 = [a.copy(order="F") for a in r1["row_matrices"].values()]
-            C1 = r1["column_factor"].copy(order="F")
-            if with_vd:
-                for e in ENTRIES:
-                    ds.variance_decomposition(A1, C1, entries=e)
-                with pytest.raises(_lib.InsiderError):
-                    ds.variance_decomposition(A1, C1, inc_continuous=1)
-            return ds.optimize(A1, C1, w.K, w.lam, w.lam, w.alpha, tuning=1, max_iter=12, seed=3)
-        finally:
-            ds.close()
-
-    ref, got = run(False), run(True)
-    for a, b in zip(ref["row_matrices"].values(), got["row_matrices"].values()):
-        assert np.array_equal(a, b)
-    assert np.array_equal(ref["column_factor"], got["column_factor"])
-    assert np.array_equal(ref["traj"], got["traj"], equal_nan=True)
-
-
 def test_argument_errors(two):
     ds, X, lev, Z, masks = two
-    A, Cm = _factors(np.random.default_rng(17), (5, 3), 0, 4, X.shape[1])
+    A, Cm = factors(np.random.default_rng(17), (5, 3), 0, 4, X.shape[1])
 
     def status(fn):
         with pytest.raises(_lib.InsiderError) as e:
@@ -240,7 +185,7 @@ def test_argument_errors(two):
     assert status(lambda: ds.variance_decomposition(A, Cm, entries="held-out")) == _lib.ERR_ARG
     assert status(lambda: ds.variance_decomposition(A, Cm, inc_continuous=1)) == _lib.ERR_ARG
     assert status(lambda: ds.variance_decomposition(A, Cm, inc_continuous=2)) == _lib.ERR_ARG
-    A64, C64 = _factors(np.random.default_rng(1), (5, 3), 0, 64, X.shape[1])
+    A64, C64 = factors(np.random.default_rng(1), (5, 3), 0, 64, X.shape[1])
     assert status(lambda: ds.variance_decomposition(A64, C64)) == _lib.ERR_UNSUPPORTED
     # the same checks inside the library (the C ABI called directly)
     lib = _lib.load()
@@ -255,18 +200,6 @@ def test_argument_errors(two):
                                                   _lib.ptr(out)) == _lib.ERR_UNSUPPORTED
     assert lib.insider_hip_variance_decomposition(ds._h, Aptrs, _lib.ptr(Cw), 0, 4, 1, None) == _lib.ERR_ARG
     assert np.all(out == 0)
-
-
-def test_refuses_a_sharded_handle():
-    w = workloads.small(n=48, p=64, K=3)
-    ds = api.InsiderData(w.X, w.levels, w.M_train, w.M_test)
-    try:
-        ds.set_shard(0, 0, 2, allreduce=lambda ptr, count, stream: None)
-        with pytest.raises(_lib.InsiderError) as e:
-            ds.variance_decomposition(w.A0, w.C0)
-        assert e.value.status == _lib.ERR_UNSUPPORTED
-    finally:
-        ds.close()
 
 
 def test_cli_writes_the_decomposition(tmp_path):

@@ -1,41 +1,16 @@
-"""Host-side checks of the k-means call (insider_hip_kmeans): both symbols are declared, listed and exported, the numpy
-yardstick posthoc.kmeans_host() agrees with a brute force built from Python loops and ``sorted`` with the key (-score, index),
-the Forgy start is the draw insider_hip_enrichment_sample names, api.kmeans() refuses every bad argument before it reaches
-the library, module_overrepresentation() counts what a hand count gives, and the driver's flags parse and its records
-round-trip through flatio."""
+"""Host-side checks of the k-means call (insider_hip_kmeans): the numpy yardstick posthoc.kmeans_host() agrees with a brute
+force built from Python loops and ``sorted`` with the key (-score, index), the Forgy start is the draw
+insider_hip_enrichment_sample names, api.kmeans() refuses every bad argument before it reaches the library,
+module_overrepresentation() counts what a hand count gives, and the driver's flags parse and its records round-trip through
+flatio."""
 import ctypes as C
 import math
-import os
-import re
 
 import numpy as np
 import pytest
 
-import __graft_entry__ as ge
 from insider_amd import _lib, api, fit, flatio, posthoc
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def lib():
-    ge.build()
-    return _lib.load()
-
-
-def test_symbols_are_declared_listed_and_exported(lib):
-    hdr = open(os.path.join(ROOT, "include", "insider_hip.h")).read()
-    assert re.search(r"\bint insider_hip_kmeans\s*\(", hdr)
-    assert re.search(r"\bdouble insider_hip_last_kmeans_ms\s*\(\s*void\s*\)", hdr)
-    for name in ("insider_hip_kmeans", "insider_hip_last_kmeans_ms"):
-        assert name in _lib.SYMBOLS
-        assert getattr(lib, name) is not None
-    assert len(lib.insider_hip_kmeans.argtypes) == 21
-    assert lib.insider_hip_last_kmeans_ms.restype is C.c_double
-    from insider_amd import _build
-    assert any(f.endswith("insider_kmeans.hpp") for f in _build.source_files())
-    src = open(os.path.join(ROOT, "insider_amd", "csrc", "insider_kmeans.hpp")).read()
-    assert re.search(r"KM_MAX_K = 4096;", src) and api.KMEANS_MAX_K == 4096
+from tests.support import lib  # noqa: F401  (fixture)
 
 
 # ---- the yardstick against a brute force -------------------------------------------------------------------------------------

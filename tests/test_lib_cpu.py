@@ -9,14 +9,9 @@ import pytest
 
 import __graft_entry__ as ge
 from insider_amd import _lib, api, workloads
+from tests.support import lib  # noqa: F401  (fixture)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def lib():
-    ge.build()
-    return _lib.load()
 
 
 def test_exports_every_declared_symbol(lib):

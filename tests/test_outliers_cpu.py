@@ -1,47 +1,18 @@
-"""Host-side checks of the outlier calls (insider_hip_outliers): the symbol is declared, listed and exported, the numpy
-yardstick posthoc.outliers_host() agrees with a naive double loop, posthoc.residual_center_scale() gives the mean and the
-standard deviation of the masked residual, genes without a usable scale get no call, and the command line accepts
---outliers / --outlier-entries."""
-import os
-import re
+"""Host-side checks of the outlier calls (insider_hip_outliers): the numpy yardstick posthoc.outliers_host() agrees with a
+naive double loop, posthoc.residual_center_scale() gives the mean and the standard deviation of the masked residual, genes
+without a usable scale get no call, and the command line accepts --outliers / --outlier-entries."""
+import functools
 
 import numpy as np
 import pytest
 
-import __graft_entry__ as ge
-from insider_amd import _lib, fit, posthoc
+from insider_amd import fit, posthoc
+from tests.support import problem
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 COUNTS = ("gene_low", "gene_high", "sample_low", "sample_high")
 
 
-@pytest.fixture(scope="module")
-def lib():
-    ge.build()
-    return _lib.load()
-
-
-def test_symbol_is_declared_listed_and_exported(lib):
-    hdr = open(os.path.join(ROOT, "include", "insider_hip.h")).read()
-    assert re.search(r"\bint insider_hip_outliers\s*\(", hdr)
-    assert '"ol_path"' in hdr
-    assert "insider_hip_outliers" in _lib.SYMBOLS
-    assert lib.insider_hip_outliers is not None
-    src = open(os.path.join(ROOT, "insider_amd", "csrc", "insider_outliers.hpp")).read()
-    # the sizes the GPU tests take from _lib are the kernels' own
-    assert re.search(r"OL_WAVES = 4;", src) and re.search(r"OL_SPL = 4;", src) and _lib.OL_TRIP == 64 * 4 * 4
-    assert re.search(r"OL_SCAN_THREADS = 256, OL_SCAN_ITEMS = 4;", src) and _lib.OL_SCAN_CHUNK == 256 * 4
-
-
-def _problem(seed, n=7, p=5, counts=(3, 2), m=1, K=3):
-    rng = np.random.default_rng(seed)
-    X = rng.standard_normal((n, p)) + 0.5
-    lev = np.column_stack([rng.integers(1, L + 1, n) for L in counts]).astype(np.int32)
-    Z = rng.standard_normal((n, m)) if m else None
-    A = [0.3 * rng.standard_normal((L, K)) for L in counts] + ([0.3 * rng.standard_normal((m, K))] if m else [])
-    Cm = rng.standard_normal((K, p))
-    mask = rng.random((n, p)) < 0.7
-    return X, lev, Z, mask, A, Cm
+_problem = functools.partial(problem, n=7, p=5, counts=(3, 2), m=1, K=3, scale=0.3)
 
 
 def _residual(X, lev, Z, A, Cm):

@@ -5,14 +5,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
-import __graft_entry__ as ge
 from insider_amd import _lib, api, fit, posthoc
-
-
-@pytest.fixture(scope="module")
-def lib():
-    ge.build()
-    return _lib.load()
+from tests.support import lib  # noqa: F401  (fixture)
 
 
 def _fake(n=20, p=12, n_levels=(3, 2), m=0):

@@ -1,56 +1,25 @@
-"""Host-side checks of the per-sample fit diagnostics (insider_hip_sample_decomposition): the symbol is declared, listed and
-exported, the numpy yardstick posthoc.sample_decomposition_host() agrees with direct per-sample loops and with the per-gene
-yardstick's totals, posthoc.level_decomposition() pools the samples of a level, and the command line accepts
---sample-decomposition."""
-import os
-import re
+"""Host-side checks of the per-sample fit diagnostics (insider_hip_sample_decomposition): the numpy yardstick
+posthoc.sample_decomposition_host() agrees with direct per-sample loops and with the per-gene yardstick's totals,
+posthoc.level_decomposition() pools the samples of a level, and the command line accepts --sample-decomposition."""
+import functools
 
 import numpy as np
 import pytest
 
-import __graft_entry__ as ge
-from insider_amd import _lib, fit, posthoc
+from insider_amd import fit, posthoc
+from tests.support import blocks, problem
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SUMS = ("n", "sum_x", "sum_xx", "rss", "sum_g", "sum_gg", "sum_rg")
 
 
-@pytest.fixture(scope="module")
-def lib():
-    ge.build()
-    return _lib.load()
-
-
-def test_symbol_is_declared_listed_and_exported(lib):
-    hdr = open(os.path.join(ROOT, "include", "insider_hip.h")).read()
-    assert re.search(r"\bint insider_hip_sample_decomposition\s*\(", hdr)
-    assert "insider_hip_sample_decomposition" in _lib.SYMBOLS
-    assert lib.insider_hip_sample_decomposition is not None
-
-
-def _problem(seed, n=23, p=17, counts=(4, 3), m=2, K=5):
-    rng = np.random.default_rng(seed)
-    X = rng.standard_normal((n, p)) + 0.5
-    lev = np.column_stack([rng.integers(1, L + 1, n) for L in counts]).astype(np.int32)
-    Z = rng.standard_normal((n, m)) if m else None
-    A = [rng.standard_normal((L, K)) for L in counts] + ([rng.standard_normal((m, K))] if m else [])
-    Cm = rng.standard_normal((K, p))
-    mask = rng.random((n, p)) < 0.7
-    return X, lev, Z, mask, A, Cm
-
-
-def _blocks(lev, Z, A, Cm):
-    g = [A[b][lev[:, b] - 1] @ Cm for b in range(lev.shape[1])]
-    if Z is not None:
-        g.append(Z @ A[lev.shape[1]] @ Cm)
-    return g
+_problem = functools.partial(problem, n=23, p=17, counts=(4, 3), m=2, K=5)
 
 
 def test_host_record_matches_per_sample_loops():
     """23 x 17 with a continuous block and a mask: every slot and every derived value of every sample."""
     X, lev, Z, mask, A, Cm = _problem(1)
     d = posthoc.sample_decomposition_host(X, lev, Z, mask, A, Cm)
-    g = _blocks(lev, Z, A, Cm)
+    g = blocks(lev, Z, A, Cm)
     R = X - sum(g)
     B, n = len(g), X.shape[0]
     assert B == 3 and d["sum_g"].shape == (B, n) and d["drop_one"].shape == (B, n) and d["r2"].shape == (n,)
@@ -99,7 +68,7 @@ def test_level_decomposition_matches_direct_and_marks_empty_levels():
     mask[ids == 3] = False                 # level 3 has samples, none with a selected entry
     rec = posthoc.sample_decomposition_host(X, lev, Z, mask, A, Cm)
     d = posthoc.level_decomposition(rec, ids, 5)
-    g = _blocks(lev, Z, A, Cm)
+    g = blocks(lev, Z, A, Cm)
     R = X - sum(g)
     assert d["r2"].shape == (5,) and d["explained"].shape == (3, 5)
     for l in (1, 4):

@@ -1,54 +1,23 @@
-"""Host-side checks of the per-gene variance decomposition (insider_hip_variance_decomposition): the symbol is declared,
-listed and exported, the numpy yardstick posthoc.variance_decomposition_host() agrees with the direct formulas, and the
-command line accepts --variance-decomposition."""
-import os
-import re
+"""Host-side checks of the per-gene variance decomposition (insider_hip_variance_decomposition): the numpy yardstick
+posthoc.variance_decomposition_host() agrees with the direct formulas, and the command line accepts
+--variance-decomposition."""
+import functools
 
 import numpy as np
 import pytest
 
-import __graft_entry__ as ge
-from insider_amd import _lib, fit, posthoc
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from insider_amd import fit, posthoc
+from tests.support import blocks, problem
 
 
-@pytest.fixture(scope="module")
-def lib():
-    ge.build()
-    return _lib.load()
-
-
-def test_symbol_is_declared_listed_and_exported(lib):
-    hdr = open(os.path.join(ROOT, "include", "insider_hip.h")).read()
-    assert re.search(r"\bint insider_hip_variance_decomposition\s*\(", hdr)
-    assert "insider_hip_variance_decomposition" in _lib.SYMBOLS
-    assert lib.insider_hip_variance_decomposition is not None
-
-
-def _problem(seed, n=37, p=23, counts=(4, 3), m=2, K=5):
-    rng = np.random.default_rng(seed)
-    X = rng.standard_normal((n, p)) + 0.5
-    lev = np.column_stack([rng.integers(1, L + 1, n) for L in counts]).astype(np.int32)
-    Z = rng.standard_normal((n, m)) if m else None
-    A = [rng.standard_normal((L, K)) for L in counts] + ([rng.standard_normal((m, K))] if m else [])
-    Cm = rng.standard_normal((K, p))
-    mask = rng.random((n, p)) < 0.7
-    return X, lev, Z, mask, A, Cm
-
-
-def _blocks(lev, Z, A, Cm):
-    g = [A[b][lev[:, b] - 1] @ Cm for b in range(lev.shape[1])]
-    if Z is not None:
-        g.append(Z @ A[lev.shape[1]] @ Cm)
-    return g
+_problem = functools.partial(problem, n=37, p=23, counts=(4, 3), m=2, K=5)
 
 
 @pytest.mark.parametrize("seed,m", [(0, 0), (1, 2), (2, 1)])
 def test_host_record_matches_direct_formulas(seed, m):
     X, lev, Z, mask, A, Cm = _problem(seed, m=m)
     d = posthoc.variance_decomposition_host(X, lev, Z, mask, A, Cm)
-    g = _blocks(lev, Z, A, Cm)
+    g = blocks(lev, Z, A, Cm)
     R = X - sum(g)
     B = len(g)
     assert d["sum_g"].shape == (B, X.shape[1]) and d["drop_one"].shape == (B, X.shape[1])
