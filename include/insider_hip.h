@@ -500,6 +500,42 @@ int insider_hip_residual_products(insider_hip_handle *h, double *const *A, const
                                   double *Z, double *Y, double *rss);
 
 /*
+ * Residual co-expression: the top-k correlated partners of every gene (axis 0) or of every sample (axis 1) in what a fitted
+ * model has left behind (insider_amd/csrc/insider_coexpr.hpp).  The working residual is exactly that of
+ * insider_hip_residual_products(): r_ij = (x_ij - f_ij - center_j) / scale_j on the selected entries, 0 elsewhere, the same
+ * blocks in the same order, the same meaning of entries (0 all / 1 train bit / 2 test bit), center NULL = 0, scale NULL = 1, a
+ * gene whose scale is not finite or not > 0 an all-zero column (its entries stay selected entries of value 0).
+ *   axis 0  genes:   N = p vectors, the contraction runs over the samples;
+ *   axis 1  samples: N = n vectors, the contraction runs over the genes.
+ * Standardisation.  With m the number of selected entries of a vector: mean = (sum of r over the selected entries, in index
+ * order) / m; the selected entries are centred by it, the unselected ones stay 0; the vector is divided by the root of its
+ * centred sum of squares (index order).  A vector with m < 2 or a sum of squares that is not > 0 is DEAD: nobody's partner,
+ * its own row all open slots.
+ * Score.  The plain sum over the whole depth of the products of the standardised values; an entry missing in either vector
+ * contributes 0.  With a full selection this is Pearson's r.  With missing entries it is the ZERO-FILLED correlation: |score|
+ * <= 1 and it shrinks with missingness.  It is NOT the pairwise-complete correlation (which would need six products where this
+ * needs one).  Scores are not clipped: a correlation may exceed 1 by rounding.
+ *   idx_out / score_out  N x k, vector-major: row i lists the partners of vector i (never i itself) in descending score, equal
+ *   scores (-0.0 == 0.0) by ascending index; a row with fewer than k eligible partners ends in -1 / NaN: the rules of
+ *   insider_hip_neighbors().  1 <= k <= 64.
+ * Status codes: the checks of the post-hoc calls above (K 1..63: K > 63 returns INSIDER_ERR_UNSUPPORTED; the same
+ * inc_continuous rules; a sharded handle returns INSIDER_ERR_UNSUPPORTED); entries outside 0..2, axis outside 0..1, k outside
+ * 1..64 and a NULL output return INSIDER_ERR_ARG.  Nothing is written to the caller's arrays unless the status is INSIDER_OK.
+ * Works on clones and re-masked handles, on the handle's main stream: an optimize() after it is bit-identical to one without.
+ * The standardised residual is staged once on the device in operand order: N and the depth rounded up to 64 and 32, 8 bytes
+ * each (4 GB at n = 10000, p = 50000), allocated for the call and freed before it returns, outside the post-hoc workspace;
+ * INSIDER_ERR_ALLOC when it cannot be allocated.  One streaming pass over X and the mask codes writes it (the fit of a 16 x 16
+ * tile on the f64 matrix instruction), one pass over the staged buffer standardises it, and one product kernel forms every
+ * score, K-independent, with the selection fused behind it: the N x N matrix never exists.  The score of a pair is one
+ * accumulator chain over the depth in ascending order; no floating-point atomics: repeated calls return identical bits.
+ * insider_hip_get_info: "cx_stage_mb" the staged bytes of the last call in MB, "cx_stage_ms" the HIP-event time of its staging
+ * kernels and "cx_ms" that of its product kernel, in milliseconds.
+ */
+int insider_hip_coexpression(insider_hip_handle *h, double *const *A, const double *C, int inc_continuous, int K,
+                             int entries, const double *center, const double *scale, int axis, int k, int32_t *idx_out,
+                             double *score_out);
+
+/*
  * Aberrant entries of a fitted model on the resident data set: the (sample, gene) entries whose standardised residual the
  * model cannot explain.  Blocks, g_b(i,j), f = sum_b g_b (in block order), r = x - f, x, the meaning of entries (0 all / 1 train
  * bit / 2 test bit) and S_j are exactly those of insider_hip_variance_decomposition().
@@ -550,6 +586,28 @@ int insider_hip_outliers(insider_hip_handle *h, double *const *A, const double *
 int insider_hip_neighbors(const double *Q, int64_t nq, const double *B, int64_t nb, int K, int metric, int k,
                           int64_t self_offset, int device, int32_t *idx_out, double *score_out);
 double insider_hip_last_neighbors_ms(void);
+
+/* Top-k partners among N deep vectors: the Gram matrix V' V of the standardised vectors with the selection fused behind the
+ * product (insider_amd/csrc/insider_coexpr.hpp).  Handle-free, one device.
+ *   V holds N vectors of `depth` contiguous doubles (column-major, depth x N: the layout insider_hip_neighbors uses for its
+ *   K x n matrices, but the depth is not limited).  For every vector of the window [first, first + count) its k partners among
+ *   all N vectors; a vector is never its own partner.  idx_out / score_out are count x k, query-major, in descending score,
+ *   equal scores (-0.0 == 0.0) by ascending index; a row with fewer than k eligible partners ends in -1 / NaN.
+ *   metric 0 = correlation: each vector is centred by its own mean (sum / depth) and divided by the root of its centred sum of
+ *   squares; 1 = cosine: divided by the root of its sum of squares, no centring; 2 = dot: a plain copy.  Every sum runs in index
+ *   order.  Under metrics 0 and 1 a vector whose (centred) sum of squares is not > 0 is DEAD: nobody's partner, its own row all
+ *   open slots; under metric 2 nothing is dead.  Scores are not clipped: a correlation may exceed 1 by rounding.
+ *   The score of a pair is one accumulator chain over the depth in ascending order, wherever the pair falls in tiles, windows
+ *   or the launch grid: repeated calls return identical bits, and a call on a window returns exactly those rows of the full
+ *   call.  Device memory is O(N depth + count k).
+ *   INSIDER_ERR_ARG, nothing written: a NULL pointer, depth < 1, N < 1 or N > INT32_MAX, k outside 1..64, an unknown metric,
+ *   first < 0, count < 0 or first + count > N, a non-finite value in V (checked on the host).  count = 0 returns INSIDER_OK
+ *   and writes nothing; a failed device allocation returns INSIDER_ERR_ALLOC and writes nothing.
+ *   insider_hip_last_gram_topk_ms: of the calling THREAD's last call, the HIP-event time in ms of its kernels (transfers
+ *   excluded). */
+int insider_hip_gram_topk(const double *V, int64_t depth, int64_t N, int metric, int k, int64_t first, int64_t count,
+                          int device, int32_t *idx_out, double *score_out);
+double insider_hip_last_gram_topk_ms(void);
 
 /* Preranked gene-set enrichment with a permutation null (insider_amd/csrc/insider_enrich.hpp).  Handle-free, one device.
  *   Inputs.  scores is R x p, row-major: profile r is p contiguous doubles.  set_ptr (int64, S + 1) and set_genes (int32) hold S
@@ -718,6 +776,8 @@ int insider_hip_get_profile(insider_hip_handle *h, double *out12);
  * 2 = several windows of 128 columns of W, X read once per window; 0 = none yet),
  * "rc_slabs" / "rc_ms" (of the last insider_hip_residual_products(): the gene slabs the grid of k_rc_fwd had, 0 = no forward
  * pass or none yet; and the HIP-event time in milliseconds of k_rc_back, k_rc_fwd and k_rc_reduce),
+ * "cx_stage_mb" / "cx_stage_ms" / "cx_ms" (of the last insider_hip_coexpression(): the megabytes of the staged standardised
+ * residual, the HIP-event time in milliseconds of k_cx_stage and k_cx_norm, and that of k_cx_topk; 0 = none yet),
  * "ol_path" (the form of k_ol_flag the last insider_hip_outliers() ran: 1 = level tables in LDS, 2 = read from global memory;
  * 0 = none yet),
  * "row_kernels" (a bit mask of the row-phase kernel forms the last optimize() / optimize_row() launched, reset at the start of

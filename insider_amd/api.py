@@ -408,6 +408,37 @@ class InsiderData:
                                                              _lib.ptr(Z), None if Y is None else _lib.ptr(Y), _lib.ptr(rss)))
         return dict(Z=Z, Y=Y, rss=rss)
 
+    COEXPR_AXES = {"genes": 0, "samples": 1}
+
+    def coexpression(self, cfd_factors, column_factor, axis="genes", k=10, entries="train", center=None, scale=None,
+                     inc_continuous=0):
+        """Residual co-expression (insider_hip_coexpression): the ``k`` most correlated partners of every gene
+        (``axis="genes"``: N = p vectors, correlated over the samples) or of every sample (``axis="samples"``: N = n, over the
+        genes) in the working residual of residual_products(): r = (x - f - center[j]) / scale[j] on the entries ``entries``
+        and 0 elsewhere (``center`` None = 0, ``scale`` None = 1; a gene with a bad scale is an all-zero column).  A vector is
+        centred by its mean over its selected entries (the unselected ones stay 0) and divided by the root of its centred sum
+        of squares; one with fewer than two selected entries or no variance is dead: nobody's partner, a row of open slots.
+        The score is the plain sum of products over the whole depth.  With a full selection this is Pearson's r; with missing
+        entries it is the ZERO-FILLED correlation (|score| <= 1, shrinking with missingness), NOT the pairwise-complete one.
+        -> dict(index=(N, k) int32, score=(N, k) float64): descending score, equal scores by ascending index, never the
+        vector itself, -1 / NaN in open slots.  The standardised residual is staged once on the device (about 8 n p bytes,
+        freed before the call returns); the N x N matrix never exists."""
+        self._entries_code(entries, inc_continuous)   # (reported before axis and k; the factors' shapes after them, as ever)
+        if axis not in self.COEXPR_AXES:
+            raise InsiderError(_lib.ERR_ARG, f"axis must be one of {sorted(self.COEXPR_AXES)}, got {axis!r}")
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= NEIGHBOR_MAX_K:
+            raise InsiderError(_lib.ERR_ARG, f"k must be an integer in 1..{NEIGHBOR_MAX_K}")
+        K, A, Cw, Aptrs, code, nb = self._fit_args(cfd_factors, column_factor, entries, inc_continuous)
+        ce, sc = self._center_scale(center, scale, "center and scale")
+        N = self.p if axis == "genes" else self.n
+        index = np.full((N, int(k)), -1, dtype=np.int32)
+        score = np.full((N, int(k)), np.nan)
+        _lib.check(_lib.load().insider_hip_coexpression(self._h, Aptrs, _lib.ptr(Cw), int(inc_continuous), K, code,
+                                                        None if ce is None else _lib.ptr(ce),
+                                                        None if sc is None else _lib.ptr(sc), self.COEXPR_AXES[axis], int(k),
+                                                        _lib.ptr(index, C.c_int32), _lib.ptr(score)))
+        return dict(index=index, score=score)
+
     def outliers(self, cfd_factors, column_factor, scale, center=None, threshold=3.0, entries="train", inc_continuous=0,
                  cap=None):
         """The aberrant entries of a fitted model (insider_hip_outliers): the entries ``entries`` whose standardised residual
@@ -757,6 +788,57 @@ def neighbors(query, base=None, k=10, metric="cosine", exclude_self=None, device
         else:
             qp = _lib.ptr(Q)
         _lib.check(_lib.load().insider_hip_neighbors(qp, nq, _lib.ptr(B), B.shape[1], K, code, k, off, int(device),
+                                                     _lib.ptr(index, C.c_int32), _lib.ptr(score)))
+    return dict(index=index, score=score)
+
+
+GRAM_METRICS = {"correlation": 0, "cosine": 1, "dot": 2}
+# insider_amd/csrc/insider_coexpr.hpp: the queries a block of k_cx_topk owns (CX_QB), the base vectors it takes per step (CX_BG)
+# and the depth chunk it stages (CX_DC): the sizes at which the kernel changes path
+CX_QB = 64
+CX_BG = 64
+CX_DC = 32
+
+
+def gram_topk_args(V, k, metric, first, count):
+    """The checked arguments of gram_topk() / posthoc.gram_topk_host(): (V, k, metric code, first, count), V column-major
+    float64 (depth x N).  Shape, metric, k, window and non-finite errors raise InsiderError(ERR_ARG)."""
+    V = _lib.f64(V)
+    if V.ndim != 2 or V.shape[0] < 1 or V.shape[1] < 1:
+        raise InsiderError(_lib.ERR_ARG, "V must be a depth x N array with depth >= 1 and N >= 1")
+    N = V.shape[1]
+    if N > 2 ** 31 - 1:
+        raise InsiderError(_lib.ERR_ARG, "N must be < 2^31")
+    if metric not in GRAM_METRICS:
+        raise InsiderError(_lib.ERR_ARG, f"metric must be one of {sorted(GRAM_METRICS)}")
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= NEIGHBOR_MAX_K:
+        raise InsiderError(_lib.ERR_ARG, f"k must be an integer in 1..{NEIGHBOR_MAX_K}")
+    if count is None:
+        count = N - first if isinstance(first, (int, np.integer)) and not isinstance(first, bool) else count
+    for name, v in (("first", first), ("count", count)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 0:
+            raise InsiderError(_lib.ERR_ARG, f"{name} must be an integer >= 0")
+    if first + count > N:
+        raise InsiderError(_lib.ERR_ARG, "the window first + count must lie within the N vectors")
+    if not np.all(np.isfinite(V)):
+        raise InsiderError(_lib.ERR_ARG, "V holds a value that is not finite")
+    return V, int(k), GRAM_METRICS[metric], int(first), int(count)
+
+
+def gram_topk(V, k=10, metric="correlation", first=0, count=None, device=0):
+    """The k best partners of deep vectors on the device (insider_hip_gram_topk).  ``V`` (depth x N) holds one vector per
+    column; the depth is not limited (neighbors() keeps K <= 63 in registers, this streams it).  metric "correlation" (each
+    vector centred by its mean and divided by the root of its centred sum of squares), "cosine" (divided by the root of its
+    sum of squares) or "dot" (as given); under the first two a vector without variance / norm is dead: nobody's partner, a row
+    of open slots.  ``first`` / ``count``: the window of vectors to answer for (count None = to the end); the partners come
+    from all N, never the vector itself.  -> dict(index=(count, k) int32, score=(count, k) float64): descending score, equal
+    scores by ascending index, -1 / NaN in open slots.  Scores are not clipped."""
+    V, k, code, first, count = gram_topk_args(V, k, metric, first, count)
+    depth, N = V.shape
+    index = np.full((count, k), -1, dtype=np.int32)
+    score = np.full((count, k), np.nan)
+    if count:
+        _lib.check(_lib.load().insider_hip_gram_topk(_lib.ptr(V), depth, N, code, k, first, count, int(device),
                                                      _lib.ptr(index, C.c_int32), _lib.ptr(score)))
     return dict(index=index, score=score)
 

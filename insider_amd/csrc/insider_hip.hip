@@ -14,6 +14,7 @@
 #include "insider_rescomp.hpp"
 #include "insider_outliers.hpp"
 #include "insider_neighbors.hpp"
+#include "insider_coexpr.hpp"
 #include "insider_enrich.hpp"
 #include "insider_kmeans.hpp"
 #include "insider_tsne.hpp"
@@ -46,6 +47,7 @@ thread_local std::string g_err;
 thread_local double g_last_cd_ms = 0.0;   // per calling thread: the ABI is re-entrant per handle / per thread
 thread_local int g_last_cd_solver = 0;     // (ColSolver)
 thread_local double g_last_neighbors_ms = 0.0;
+thread_local double g_last_gram_topk_ms = 0.0;
 thread_local double g_last_enrichment_ms = 0.0;
 thread_local double g_last_kmeans_ms = 0.0;
 thread_local double g_last_tsne_ms = 0.0;
@@ -504,6 +506,9 @@ struct insider_hip_handle {
     // of the last residual products: the gene slabs of k_rc_fwd (0: no forward pass) and the HIP-event time of its kernels
     int rc_slabs = 0;
     double rc_ms = 0.0;
+    // of the last co-expression call: the staged megabytes and the HIP-event times of the staging kernels (k_cx_stage,
+    // k_cx_norm) and of the product kernel (k_cx_topk)
+    double cx_stage_mb = 0.0, cx_stage_ms = 0.0, cx_ms = 0.0;
     // the form the flag pass of the last outlier call ran (1 = tables in LDS, 2 = from global)
     int ol_path = 0;
 
@@ -3179,6 +3184,63 @@ int insider_hip_neighbors(const double *Q, int64_t nq, const double *B, int64_t 
 
 double insider_hip_last_neighbors_ms(void) { return g_last_neighbors_ms; }
 
+// ---- co-expression: the deep product with fused top-k (insider_coexpr.hpp) -------------------------------------------------
+// the launch of k_cx_topk over the query groups that meet the window, on stream st
+static int launch_cx_topk(const double *P, const int *alive, int64_t npad, int64_t Dpad, int k, int64_t first, int64_t count,
+                          int32_t *idx, double *score, hipStream_t st)
+{
+    const size_t lds = cx_topk_lds(k);
+    // above 64 KB of dynamic LDS (k > 10 or so) the launch needs the function attribute
+    HIPCHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_cx_topk), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const int64_t groups = (first + count - 1) / CX_QB - first / CX_QB + 1;
+    hipLaunchKernelGGL(k_cx_topk, dim3((unsigned)groups), dim3(64 * CX_WAVES), lds, st, P, alive, npad, Dpad, k, first, count, idx,
+                       score);
+    KCHECK();
+    return INSIDER_OK;
+}
+
+int insider_hip_gram_topk(const double *V, int64_t depth, int64_t N, int metric, int k, int64_t first, int64_t count,
+                          int device, int32_t *idx_out, double *score_out)
+{
+    if (!V || !idx_out || !score_out) return fail(INSIDER_ERR_ARG, "null argument");
+    if (depth < 1) return fail(INSIDER_ERR_ARG, "depth must be >= 1");
+    if (N < 1 || N > (int64_t)std::numeric_limits<int32_t>::max()) return fail(INSIDER_ERR_ARG, "N must be in 1..2^31-1");
+    if (k < 1 || k > NN_MAX_TOPK) return fail(INSIDER_ERR_ARG, "k must be in 1..64");
+    if (metric < 0 || metric > 2) return fail(INSIDER_ERR_ARG, "metric must be 0 (correlation), 1 (cosine) or 2 (dot)");
+    if (first < 0 || count < 0 || first > N || count > N - first)
+        return fail(INSIDER_ERR_ARG, "the window must satisfy 0 <= first, 0 <= count, first + count <= N");
+    if (depth > (int64_t)(std::numeric_limits<size_t>::max() / sizeof(double)) / N)
+        return fail(INSIDER_ERR_ARG, "depth x N does not fit the address space");
+    if (!all_finite(V, (size_t)N * depth)) return fail(INSIDER_ERR_ARG, "V must be finite");
+    int rc = cd_common_checks(1, count, device);
+    if (rc) return rc;
+    if (count == 0) return INSIDER_OK;
+    HIPCHECK(hipSetDevice(device));
+    const int64_t npad = round_up(N, CX_PAD), Dpad = round_up(depth, CX_DC);
+    DevBuf<double> dV, dP, dscore;
+    DevBuf<int> dalive;
+    DevBuf<int32_t> didx;
+    if ((rc = dV.alloc((size_t)N * depth)) || (rc = dP.alloc((size_t)npad * Dpad)) || (rc = dalive.alloc((size_t)npad)) ||
+        (rc = dscore.alloc((size_t)count * k)) || (rc = didx.alloc((size_t)count * k)))
+        return rc;
+    HIPCHECK(hipMemcpy(dV, V, (size_t)N * depth * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHECK(hipMemset(dP, 0, (size_t)npad * Dpad * sizeof(double)));
+    Stopwatch watch;
+    if ((rc = watch.start(0))) return rc;
+    hipLaunchKernelGGL(k_cx_prep, dim3(cdiv(npad, 64)), dim3(64), 0, 0, (const double *)dV, depth, N, npad, Dpad, metric, dP.get(),
+                       dalive.get());
+    KCHECK();
+    if ((rc = launch_cx_topk(dP, dalive, npad, Dpad, k, first, count, didx, dscore, 0))) return rc;
+    float ms = 0.0f;
+    if ((rc = watch.stop_ms(0, &ms))) return rc;
+    g_last_gram_topk_ms = ms;
+    HIPCHECK(hipMemcpy(idx_out, didx, (size_t)count * k * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIPCHECK(hipMemcpy(score_out, dscore, (size_t)count * k * sizeof(double), hipMemcpyDeviceToHost));
+    return INSIDER_OK;
+}
+
+double insider_hip_last_gram_topk_ms(void) { return g_last_gram_topk_ms; }
+
 // ---- k-means (insider_kmeans.hpp) -----------------------------------------------------------------------------------------
 int insider_hip_kmeans(const double *P, int64_t N, int D, int k, int metric, const double *init, int restarts, int max_iter,
                        uint64_t seed, int device, double *centers, int32_t *label, double *dist, int32_t *second, double *dist2,
@@ -3910,6 +3972,9 @@ int insider_hip_get_info(insider_hip_handle *h, const char *name, double *out)
     else if (s == "glm_slabs") *out = h->glm_slabs;                 // gene slabs of the last interaction GLM's k_resid_stats
     else if (s == "glm_form") *out = h->glm_form;                   // ... and its form, 10 NB + GT (18, 24, 32, 42)
     else if (s == "rc_slabs") *out = h->rc_slabs;                   // last residual products: the gene slabs of k_rc_fwd (0 = no forward pass)
+    else if (s == "cx_stage_mb") *out = h->cx_stage_mb;             // last co-expression call: the staged megabytes,
+    else if (s == "cx_stage_ms") *out = h->cx_stage_ms;             // ... the HIP-event time of its staging kernels (k_cx_stage, k_cx_norm)
+    else if (s == "cx_ms") *out = h->cx_ms;                         // ... and of its product kernel (k_cx_topk)
     else if (s == "rc_ms") *out = h->rc_ms;                         // ... and the HIP-event time of its kernels (k_rc_back, k_rc_fwd, k_rc_reduce)
     else if (s == "fd_path") *out = h->fd_path;                     // last factor decomposition: 1 = one column window (X read once), 2 = several
     else if (s == "col_mfma_per_gene") {
@@ -4609,6 +4674,73 @@ int residual_products_body(insider_hip_handle *h, double *const *A, const double
     return INSIDER_OK;
 }
 
+// ---- co-expression (kernels: insider_coexpr.hpp) -----------------------------------------------------------------------
+// U and C in the kernels' layout (ph_prepare with every block) and the pairs (centre, inverse scale) of the residual products;
+// the standardised residual staged once in operand order for the axis (k_cx_stage: one pass over X and the codes; k_cx_norm:
+// one over the staged buffer), in a buffer of this call alone; then the deep product with the fused selection.  Nothing is
+// written to the caller's arrays before every check passed and the kernels ran.
+int coexpression_body(insider_hip_handle *h, double *const *A, const double *C, int inc_continuous, int K, int entries,
+                      const double *center, const double *scale, int axis, int k, int32_t *idx_out, double *score_out)
+{
+    int rc = fit_check(h, A, C, inc_continuous, K, entries);
+    if (rc) return rc;
+    if (axis != 0 && axis != 1) return fail(INSIDER_ERR_ARG, "axis must be 0 (genes) or 1 (samples)");
+    if (k < 1 || k > NN_MAX_TOPK) return fail(INSIDER_ERR_ARG, "k must be in 1..64");
+    if (!idx_out || !score_out) return fail(INSIDER_ERR_ARG, "null output");
+    const DataSet &d = *h->ds;
+    const int64_t n = d.n, p = d.p;
+    const int64_t N = axis == 0 ? p : n, depth = axis == 0 ? n : p;
+    HIPCHECK(hipSetDevice(d.device));
+    PostWs &w = h->post;
+    hipStream_t st = h->st.stream;
+    const int KS = (K + 15) / 16, KPW = 16 * KS;
+    const std::vector<int32_t> every((size_t)d.c + 2, 1);   // every block enters the fit
+    if ((rc = ph_prepare(h, A, C, K, every.data(), KPW))) return rc;
+    const int64_t npad = round_up(N, CX_PAD), Dpad = round_up(depth, CX_DC);
+    DevBuf<double> stage, dscore;
+    DevBuf<int> dalive;
+    DevBuf<int32_t> didx;
+    if ((rc = w.rin.grow(2 * (size_t)p)) || (rc = w.rcs.grow((size_t)2 * p)) || (rc = stage.alloc((size_t)npad * Dpad)) ||
+        (rc = dalive.alloc((size_t)npad)) || (rc = dscore.alloc((size_t)N * k)) || (rc = didx.alloc((size_t)N * k)))
+        return rc;
+    double *c_in = w.rin, *s_in = c_in + p, *cs = w.rcs;
+    const double *U = w.U, *cp = w.cp;
+    if (center) HIPCHECK(hipMemcpyAsync(c_in, center, (size_t)p * sizeof(double), hipMemcpyHostToDevice, st));
+    if (scale) HIPCHECK(hipMemcpyAsync(s_in, scale, (size_t)p * sizeof(double), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_rc_center_scale, dim3(cdiv(p, 256)), dim3(256), 0, st, (const double *)(center ? c_in : nullptr),
+                       (const double *)(scale ? s_in : nullptr), p, cs);
+    KCHECK();
+    HIPCHECK(hipMemsetAsync(stage, 0, (size_t)npad * Dpad * sizeof(double), st));
+    // sample tiles x gene slabs of whole fit tiles, eight blocks per compute unit
+    const int tiles = cdiv(n, RC_TILE);
+    int64_t slab_len = 0;
+    (void)gene_slabs(h, 0, tiles, 0.0, &slab_len);
+    slab_len = round_up(slab_len, 16);
+    const int slabs = cdiv(p, slab_len);
+    const int sel = entry_code(entries);
+    Stopwatch stage_watch, watch;
+    if ((rc = stage_watch.start(st))) return rc;
+    KT_DISPATCH(KS, hipLaunchKernelGGL((k_cx_stage<KT_>), dim3(tiles, slabs), dim3(64 * RC_WAVES), (size_t)4 * KT_ * 64 * sizeof(double),
+                                       st, (const double *)d.X, (const uint8_t *)d.codes, d.ldn, (int)n, p, U, cp, K,
+                                       (const double *)cs, sel, slab_len, axis, Dpad, stage.get()));
+    KCHECK();
+    hipLaunchKernelGGL(k_cx_norm, dim3(cdiv(npad, 64)), dim3(64), 0, st, stage.get(), depth, N, npad, Dpad, dalive.get());
+    KCHECK();
+    if ((rc = stage_watch.mark(st)) || (rc = watch.start(st))) return rc;
+    if ((rc = launch_cx_topk(stage, dalive, npad, Dpad, k, 0, N, didx, dscore, st))) return rc;
+    if ((rc = watch.mark(st))) return rc;
+    HIPCHECK(hipStreamSynchronize(st));   // the caller's arrays are written only after the kernels ran
+    float ms_stage = 0.f, ms = 0.f;
+    if ((rc = stage_watch.stop_ms(st, &ms_stage)) || (rc = watch.stop_ms(st, &ms))) return rc;
+    h->cx_stage_mb = (double)npad * (double)Dpad * sizeof(double) / 1048576.0;
+    h->cx_stage_ms = ms_stage;
+    h->cx_ms = ms;
+    HIPCHECK(hipMemcpyAsync(idx_out, didx, (size_t)N * k * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipMemcpyAsync(score_out, dscore, (size_t)N * k * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipStreamSynchronize(st));
+    return INSIDER_OK;
+}
+
 // ---- outlier calls (kernels: insider_outliers.hpp) -------------------------------------------------------------------
 // the level table, the flag pass over X and the codes (bitmap + per-gene counts), the scan of the genes' totals, and the fill
 // pass over the bitmap (the list + per-sample counts).  Nothing is written to the caller's arrays before every check passed.
@@ -4725,6 +4857,13 @@ int insider_hip_residual_products(insider_hip_handle *h, double *const *A, const
                                   double *Y, double *rss)
 {
     return ph_finish(h, residual_products_body(h, A, C, inc_continuous, K, entries, center, scale, Q, q, Z, Y, rss));
+}
+
+int insider_hip_coexpression(insider_hip_handle *h, double *const *A, const double *C, int inc_continuous, int K,
+                             int entries, const double *center, const double *scale, int axis, int k, int32_t *idx_out,
+                             double *score_out)
+{
+    return ph_finish(h, coexpression_body(h, A, C, inc_continuous, K, entries, center, scale, axis, k, idx_out, score_out));
 }
 
 int insider_hip_outliers(insider_hip_handle *h, double *const *A, const double *C, int inc_continuous, int K,

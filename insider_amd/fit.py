@@ -11,6 +11,7 @@
     ... --factor-decomposition                  # then the per-factor decomposition (which factor, through which covariate)
     ... --outliers 3 [--outlier-entries train]  # then the entries whose standardised residual has |z| >= 3, on the device
     ... --gene-neighbors 10 --sample-neighbors 10 [--neighbor-metric cosine]   # then each gene's / sample's nearest in latent space
+    ... --gene-coexpression 10 --sample-coexpression 10   # then each gene's / sample's most correlated partners in the residual
     ... --gene-modules 20 --sample-clusters 6 [--cluster-metric cosine]        # then k-means of the genes / samples in latent space
     ... --gene-map --sample-map [--map-perplexity 20] [--map-neighbors 60]     # then the t-SNE map of the genes / samples
     ... --level-scores 1 [--level-score-entries train]   # then every sample against every level of covariate column 1 (1-based)
@@ -33,7 +34,12 @@ ascending gene, then sample), ol_gene_counts (p x 2) and ol_sample_counts (n x 2
 --gene-neighbors N / --sample-neighbors N add each gene's N nearest genes by its column of C and each sample's N nearest
 samples by its row embedding (posthoc.gene_neighbors / sample_neighbors, --neighbor-metric cosine or dot): nn_gene_index /
 nn_gene_score (p x N) and nn_sample_index / nn_sample_score (n x N), 0-based, descending score, ties by ascending index, open
-slots -1 / NaN; --gene-modules K / --sample-clusters K add the k-means partition of the genes by their columns of C and of the
+slots -1 / NaN; --gene-coexpression N / --sample-coexpression N add each gene's N most correlated genes and each sample's N most
+correlated samples in the residual of the fit over the entries it used (posthoc.gene_coexpression / sample_coexpression; the
+samples after every gene's residual is centred and scaled, posthoc.residual_center_scale; the zero-filled correlation, not the
+pairwise-complete one, where entries are missing): cx_gene_index / cx_gene_score (p x N) and cx_sample_index / cx_sample_score
+(n x N), indices int32 and 0-based, descending score, ties by ascending index, open slots -1 / NaN;
+--gene-modules K / --sample-clusters K add the k-means partition of the genes by their columns of C and of the
 samples by their row embeddings (posthoc.gene_modules / sample_clusters; --cluster-metric cosine or euclidean, the best of
 --cluster-restarts drawn starts from --cluster-seed, at most --cluster-iters updates each): km_gene_label / km_gene_second (p,
 0-based, -1 = an all-zero column under cosine, or no second centre), km_gene_dist / km_gene_dist2 (p), km_gene_center (K x k),
@@ -144,6 +150,13 @@ def parse(argv=None):
                          "on the device; writes nn_sample_index, nn_sample_score (n x N) next to the factors")
     ap.add_argument("--neighbor-metric", choices=("cosine", "dot"), default="cosine",
                     help="--gene-neighbors / --sample-neighbors: the score (default: cosine)")
+    ap.add_argument("--gene-coexpression", type=int, default=None, metavar="N",
+                    help="after the fit, every gene's N most correlated genes in the residual over the entries the fit used, on "
+                         "the device; writes cx_gene_index (int32, 0-based, open slots -1), cx_gene_score (p x N, open slots NaN) "
+                         "next to the factors")
+    ap.add_argument("--sample-coexpression", type=int, default=None, metavar="N",
+                    help="after the fit, every sample's N most correlated samples in the residual (every gene's residual centred "
+                         "and scaled first), on the device; writes cx_sample_index, cx_sample_score (n x N) next to the factors")
     ap.add_argument("--gene-modules", type=int, default=None, metavar="K",
                     help="after the fit, the k-means partition of the genes into K modules by their columns of C, on the device; "
                          "writes km_gene_label, km_gene_dist, km_gene_second, km_gene_dist2 (p), km_gene_center (rank x K), "
@@ -201,10 +214,12 @@ def parse(argv=None):
             ap.error("--enrich-min-size / --enrich-max-size must satisfy 1 <= min <= max <= 4096")
         if a.enrich_levels is not None and a.enrich_levels < 1:
             ap.error("--enrich-levels: B is 1-based")
-    for name in ("gene_neighbors", "sample_neighbors"):
+    for name in ("gene_neighbors", "sample_neighbors", "gene_coexpression", "sample_coexpression"):
         v = getattr(a, name)
         if v is not None and not 1 <= v <= 64:
             ap.error(f"--{name.replace('_', '-')} must be in 1..64")
+        if v is not None and a.tune and name.endswith("coexpression"):
+            ap.error(f"--{name.replace('_', '-')} reads a fit: it does not go with --tune")
     for name in ("gene_modules", "sample_clusters"):
         v = getattr(a, name)
         if v is not None and not 1 <= v <= 4096:
@@ -409,6 +424,17 @@ def main(argv=None):
         nn = sample_neighbors(list(res["row_matrices"].values()), ds_levels, Z, k=a.sample_neighbors, metric=a.neighbor_metric,
                               device=a.device)
         vd = dict(vd or {}, nn_sample_index=nn["index"], nn_sample_score=nn["score"])
+    if a.gene_coexpression is not None:
+        cx = ds.coexpression(list(res["row_matrices"].values()), res["column_factor"], axis="genes", k=a.gene_coexpression,
+                             entries="train", inc_continuous=1 if Z is not None else 0)
+        vd = dict(vd or {}, cx_gene_index=cx["index"], cx_gene_score=cx["score"])
+    if a.sample_coexpression is not None:
+        from .posthoc import residual_center_scale
+        rows_, inc = list(res["row_matrices"].values()), 1 if Z is not None else 0
+        ce, sc = residual_center_scale(ds.variance_decomposition(rows_, res["column_factor"], entries="train", inc_continuous=inc))
+        cx = ds.coexpression(rows_, res["column_factor"], axis="samples", k=a.sample_coexpression, entries="train", center=ce,
+                             scale=sc, inc_continuous=inc)
+        vd = dict(vd or {}, cx_sample_index=cx["index"], cx_sample_score=cx["score"])
     km_gene = None
     km = dict(metric=a.cluster_metric, restarts=a.cluster_restarts, max_iter=a.cluster_iters, seed=a.cluster_seed, device=a.device)
     if a.gene_modules is not None:

@@ -37,6 +37,11 @@ device (InsiderData.residual_products: R never exists), with residual_products_h
 yardsticks (the same driver on the numpy operator) and component_associations() to tell a component tied to a known
 covariate (misfit, a missing interaction) from one tied to none (an unknown factor).
 
+gene_coexpression() / sample_coexpression() ask the pairwise question about the same residual: which genes still move
+together, which samples' residuals correlate (InsiderData.coexpression: the standardised residual staged once on the device,
+then an n- or p-deep product with the top-k selection fused behind it; the zero-filled correlation, not the pairwise-complete
+one, where entries are missing); coexpression_host() is the yardstick, gram_topk_host() that of the handle-free api.gram_topk().
+
 gene_neighbors() / sample_neighbors() ask the latent representations themselves which genes lie next to a gene and which
 samples next to a sample (api.neighbors: a K-deep product on the device with the top-k selection fused behind it, the
 similarity matrix never exists), on column_factor and on sample_embeddings(); neighbors_host() is the yardstick.
@@ -655,6 +660,134 @@ def neighbors_host(query, base=None, k=10, metric="cosine", exclude_self=None, d
             index[c0 + i, :order.size] = cand[order]
             score[c0 + i, :order.size] = sc[order]
     return dict(index=index, score=score)
+
+
+# ---- residual co-expression: the top-k correlated partners of deep vectors -----------------------------------------------------
+def _gram_standardise(R, sel, code):
+    """The device's standardisation of the columns of ``R`` (depth x N) in numpy, every sum in index order (np.cumsum runs
+    sequentially, np.sum would not): ``code`` 0 centres the selected entries (``sel``: a boolean depth x N array, None = all) by
+    their mean and divides by the root of the centred sum of squares, 1 divides by the root of the sum of squares, 2 copies.
+    Unselected entries are 0.  -> (the standardised matrix, alive (N,) bool): a column with fewer than two selected entries
+    (code 0) or a sum of squares that is not > 0 is dead and all zero."""
+    R = np.asarray(R, dtype=np.float64)
+    depth, N = R.shape
+    sel = np.ones(R.shape, dtype=bool) if sel is None else np.asarray(sel, dtype=bool)
+    if code == 2:
+        return np.where(sel, R, 0.0), np.ones(N, dtype=bool)
+    Rz = np.where(sel, R, 0.0)
+    m = sel.sum(axis=0).astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        mean = np.cumsum(Rz, axis=0)[-1] / m if code == 0 else np.zeros(N)
+        cen = np.where(sel, Rz - mean[None, :], 0.0)
+        ss = np.cumsum(cen * cen, axis=0)[-1]
+        alive = (ss > 0) & ((m >= 2) if code == 0 else True)
+        out = np.where(alive[None, :], cen / np.sqrt(ss)[None, :], 0.0)
+    return out, alive
+
+
+def _gram_select(W, alive, k, first, count, chunk):
+    """The selection of neighbors_host() on the scores W' W of the standardised columns ``W``: per query of the window the
+    alive columns other than itself by descending score, equal scores (-0.0 == 0.0) by ascending index; a dead query has none."""
+    N = W.shape[1]
+    index = np.full((count, k), -1, dtype=np.int32)
+    score = np.full((count, k), np.nan)
+    ids = np.arange(N)
+    for c0 in range(first, first + count, chunk):
+        c1 = min(c0 + chunk, first + count)
+        S = W[:, c0:c1].T @ W
+        for i in range(c1 - c0):
+            if not alive[c0 + i]:
+                continue
+            ok = alive.copy()
+            ok[c0 + i] = False
+            cand = ids[ok]
+            sc = S[i, cand] + 0.0                                   # (-0.0 + 0.0 = 0.0: one zero for the sort key)
+            order = np.lexsort((cand, -sc))[:k]
+            index[c0 + i - first, :order.size] = cand[order]
+            score[c0 + i - first, :order.size] = sc[order]
+    return dict(index=index, score=score)
+
+
+def gram_topk_host(V, k=10, metric="correlation", first=0, count=None, chunk=512):
+    """api.gram_topk() in plain numpy (the yardstick of the device path): the same arguments, checks and result.  float64, the
+    device's standardisation with its sums in index order (_gram_standardise), scores W' W of the standardised vectors taken
+    ``chunk`` queries at a time (no N x N array is formed) and the selection of neighbors_host()."""
+    from . import api
+    V, k, code, first, count = api.gram_topk_args(V, k, metric, first, count)
+    W, alive = _gram_standardise(V, None, code)
+    return _gram_select(W, alive, k, first, count, chunk)
+
+
+def coexpression_residual_host(X, levels, ctns, mask, A, C, center=None, scale=None):
+    """The working residual of coexpression_host() and the entries that count: r = ((x - f) - center[j]) / scale[j], f the
+    sum of the blocks in block order (residual_products_host()'s definition); a gene whose scale is not finite or not > 0 is
+    an all-zero column whose entries still count.  -> (r (n x p, 0 where the mask is off), selected (n x p bool))."""
+    X = np.asarray(X, dtype=np.float64)
+    if X.ndim != 2:
+        raise ValueError("X must be an n x p matrix")
+    n, p = X.shape
+    sc = np.ones(p) if scale is None else np.asarray(scale, dtype=np.float64).ravel()
+    ce = np.zeros(p) if center is None else np.asarray(center, dtype=np.float64).ravel()
+    if sc.shape != (p,) or ce.shape != (p,):
+        raise ValueError(f"center and scale must hold p = {p} values")
+    Cm = np.asarray(C, dtype=np.float64)
+    lev = np.asarray(levels).reshape(n, -1)
+    c = lev.shape[1]
+    f = np.zeros_like(X)
+    for b in range(c):
+        f = f + np.asarray(A[b], dtype=np.float64)[lev[:, b].astype(np.int64) - 1] @ Cm
+    if ctns is not None:
+        f = f + np.asarray(ctns, dtype=np.float64).reshape(n, -1) @ (np.asarray(A[c], dtype=np.float64) @ Cm)
+    usable = np.isfinite(sc) & (sc > 0)
+    w = np.ones(X.shape, dtype=bool) if mask is None else np.asarray(mask).astype(bool)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        r = np.where(w & usable[None, :], ((X - f) - ce) / sc, 0.0)
+    return r, w
+
+
+def coexpression_host(X, levels, ctns, mask, A, C, axis, k, center=None, scale=None, chunk=512):
+    """InsiderData.coexpression() in plain numpy (the yardstick of the device path); X, levels, ctns, mask, A, C, center and
+    scale as in residual_products_host(), ``axis`` "genes" (the p columns of the residual, correlated over the samples) or
+    "samples" (its n rows, over the genes).  Every vector is centred by its mean over its selected entries (unselected stay
+    0) and divided by the root of its centred sum of squares; fewer than two selected entries or no variance: dead.  The
+    score is the plain sum of products over the whole depth: Pearson's r under a full selection, the zero-filled correlation
+    (NOT the pairwise-complete one) under a mask.  -> dict(index=(N, k) int32, score=(N, k)), the order and open slots of
+    neighbors_host()."""
+    if axis not in ("genes", "samples"):
+        raise ValueError(f"axis must be 'genes' or 'samples', got {axis!r}")
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= 64:
+        raise ValueError("k must be an integer in 1..64")
+    r, w = coexpression_residual_host(X, levels, ctns, mask, A, C, center, scale)
+    if axis == "samples":
+        r, w = r.T, w.T
+    W, alive = _gram_standardise(r, w, 0)
+    return _gram_select(W, alive, int(k), 0, W.shape[1], chunk)
+
+
+def gene_coexpression(obj, k=10, which="fit", entries="train"):
+    """The k most correlated genes of every gene in the residual of a fitted ``Insider`` object (InsiderData.coexpression,
+    axis "genes"), with the ``which`` / ``entries`` of variance_decomposition(): the co-expression network on corrected
+    expression.  The correlation of two genes does not depend on their scales, so no centre or scale is passed.  Missing
+    entries make it the zero-filled correlation, not the pairwise-complete one.  -> dict(index=(p, k) int32 0-based genes,
+    score=(p, k)); open slots -1 / NaN."""
+    ds, cfd, col, inc = _fitted(obj, which)
+    return ds.coexpression(cfd, col, axis="genes", k=k, entries=entries, inc_continuous=inc)
+
+
+def sample_coexpression(obj, k=10, which="fit", entries="train", standardize=True):
+    """The k most correlated samples of every sample in the residual of a fitted ``Insider`` object (InsiderData.coexpression,
+    axis "samples"): duplicated libraries, cross-contamination, relatedness.  standardize=True centres and scales every
+    gene's residual first (residual_center_scale() of a variance decomposition on the same entries), so that a few
+    high-variance genes do not own the sample correlation.  Zero-filled correlation under missing entries, as
+    gene_coexpression().  -> dict(index=(n, k) int32 0-based samples, score=(n, k)) plus the ``center`` and ``scale`` used
+    (None without standardize)."""
+    ds, cfd, col, inc = _fitted(obj, which)
+    center = scale = None
+    if standardize:
+        center, scale = residual_center_scale(ds.variance_decomposition(cfd, col, entries=entries, inc_continuous=inc))
+    out = ds.coexpression(cfd, col, axis="samples", k=k, entries=entries, center=center, scale=scale, inc_continuous=inc)
+    out["center"], out["scale"] = center, scale
+    return out
 
 
 def gene_neighbors(column_factor, k=10, metric="cosine", device=0):
