@@ -778,6 +778,12 @@ int insider_hip_get_profile(insider_hip_handle *h, double *out12);
  * pass or none yet; and the HIP-event time in milliseconds of k_rc_back, k_rc_fwd and k_rc_reduce),
  * "cx_stage_mb" / "cx_stage_ms" / "cx_ms" (of the last insider_hip_coexpression(): the megabytes of the staged standardised
  * residual, the HIP-event time in milliseconds of k_cx_stage and k_cx_norm, and that of k_cx_topk; 0 = none yet),
+ * "ls_form" / "fd_form" / "rc_form" / "cx_form" (the template instantiation of the heavy launch of the last
+ * insider_hip_level_scores(), _factor_decomposition(), _residual_products() and _coexpression(), set on the host at the launch
+ * site; 0 = none yet.  The first three are 10 QT + KS, KS = ceil(K / 16) blocks of 16 latent dimensions and QT tiles of 16
+ * columns: k_ls_prod<QT,KS> with QT 1 (at most 16 levels) or 8 (the window form): 11..14, 81..84; k_fd_prod<8,KS,true>: 81..84;
+ * k_rc_back<QT,KS> and k_rc_fwd<QT,KS> with QT = ceil(q / 16): 11..14, 21..24, 31..34, 41..44.  "cx_form" is the KS of
+ * k_cx_stage<KS>: 1..4),
  * "ol_path" (the form of k_ol_flag the last insider_hip_outliers() ran: 1 = level tables in LDS, 2 = read from global memory;
  * 0 = none yet),
  * "row_kernels" (a bit mask of the row-phase kernel forms the last optimize() / optimize_row() launched, reset at the start of

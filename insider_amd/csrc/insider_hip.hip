@@ -503,6 +503,9 @@ struct insider_hip_handle {
     // of the last interaction GLM: the gene slabs of k_resid_stats and its form, 10 NB + GT
     int glm_slabs = 0, glm_form = 0;
     int fd_path = 0;
+    // the (QT, KS) instantiation of the heavy launch of the last level scores (k_ls_prod), factor decomposition (k_fd_prod with
+    // the residual), residual products (k_rc_back / k_rc_fwd), as 10 QT + KS, and of the last co-expression (k_cx_stage), KS
+    int ls_form = 0, fd_form = 0, rc_form = 0, cx_form = 0;
     // of the last residual products: the gene slabs of k_rc_fwd (0: no forward pass) and the HIP-event time of its kernels
     int rc_slabs = 0;
     double rc_ms = 0.0;
@@ -3971,6 +3974,10 @@ int insider_hip_get_info(insider_hip_handle *h, const char *name, double *out)
     else if (s == "sd_slabs") *out = h->sd_slabs;                   // ... and its gene slabs
     else if (s == "glm_slabs") *out = h->glm_slabs;                 // gene slabs of the last interaction GLM's k_resid_stats
     else if (s == "glm_form") *out = h->glm_form;                   // ... and its form, 10 NB + GT (18, 24, 32, 42)
+    else if (s == "ls_form") *out = h->ls_form;                     // last level scores: k_ls_prod<QT,KS> as 10 QT + KS (QT 1 or 8)
+    else if (s == "fd_form") *out = h->fd_form;                     // last factor decomposition: k_fd_prod<QT,KS,true> as 10 QT + KS (QT 8)
+    else if (s == "rc_form") *out = h->rc_form;                     // last residual products: k_rc_back / k_rc_fwd<QT,KS> as 10 QT + KS
+    else if (s == "cx_form") *out = h->cx_form;                     // last co-expression call: k_cx_stage<KS> as KS
     else if (s == "rc_slabs") *out = h->rc_slabs;                   // last residual products: the gene slabs of k_rc_fwd (0 = no forward pass)
     else if (s == "cx_stage_mb") *out = h->cx_stage_mb;             // last co-expression call: the staged megabytes,
     else if (s == "cx_stage_ms") *out = h->cx_stage_ms;             // ... the HIP-event time of its staging kernels (k_cx_stage, k_cx_norm)
@@ -4499,9 +4506,12 @@ int level_scores_body(insider_hip_handle *h, double *const *A, const double *C, 
     h->ls_path = nwin == 1 ? 1 : 2;
     h->ls_slabs = slabs;
 #define LS_LAUNCH(QT_)                                                                                                      \
-    KT_DISPATCH(KS, hipLaunchKernelGGL((k_ls_prod<QT_, KT_>), dim3(tiles, slabs, cdiv(ltiles, QT_)), dim3(64 * LS_WAVES),     \
-                                       ls_lds_bytes(QT_, KT_), st, (const double *)d.X, (const uint8_t *)d.codes, d.ldn,     \
-                                       (int)n, p, U, cp, K, (const double *)Tc, ldt, sel, slab_len, part, cpart))
+    KT_DISPATCH(KS, {                                                                                                        \
+        h->ls_form = 10 * QT_ + KT_;                                                                                         \
+        hipLaunchKernelGGL((k_ls_prod<QT_, KT_>), dim3(tiles, slabs, cdiv(ltiles, QT_)), dim3(64 * LS_WAVES),                \
+                           ls_lds_bytes(QT_, KT_), st, (const double *)d.X, (const uint8_t *)d.codes, d.ldn,                 \
+                           (int)n, p, U, cp, K, (const double *)Tc, ldt, sel, slab_len, part, cpart);                        \
+    })
     // one level tile: 84 - 102 registers; else the window form of LS_QT tiles: 196 - 215 (tools/kernel_regs.sh), no scratch, two
     // waves per SIMD; tiles beyond the live ones of a window are skipped by a uniform branch.  (Forms of 2 and 4 tiles were
     // dropped: the 4-tile one compiled to 446 - 468 registers, one wave per SIMD.)
@@ -4557,6 +4567,7 @@ int factor_decomposition_body(insider_hip_handle *h, double *const *A, const dou
     const dim3 grid((unsigned)cdiv(p, (int64_t)FD_GENES)), block(64 * FD_WAVES);
 #define FD_LAUNCH(QT_, KS_)                                                                                                 \
     do {                                                                                                                     \
+        h->fd_form = 10 * QT_ + KS_;                                                                                         \
         const size_t lw = (size_t)FD_CHUNK * (16 * QT_ + 4) * sizeof(double);                                                \
         const size_t lr = (size_t)FD_CHUNK * (16 * KS_ + 2) * sizeof(double);                                                \
         for (int t0 = 0; t0 < heavy_tiles; t0 += QT_) {                                                                      \
@@ -4636,6 +4647,7 @@ int residual_products_body(insider_hip_handle *h, double *const *A, const double
     if ((rc = watch.start(st))) return rc;
 #define RC_LAUNCH(QT_, KS_)                                                                                                 \
     do {                                                                                                                     \
+        h->rc_form = 10 * QT_ + KS_;                                                                                         \
         hipLaunchKernelGGL((k_rc_back<QT_, KS_>), dim3((unsigned)cdiv(p, (int64_t)RC_GENES)), dim3(64 * RC_WAVES),           \
                            rc_back_lds(QT_, KS_), st, (const double *)d.X, (const uint8_t *)d.codes, d.ldn, (int)n, p, U, cp, \
                            K, (const double *)Qd, (const double *)cs, sel, Zd, r_out);                                       \
@@ -4720,9 +4732,12 @@ int coexpression_body(insider_hip_handle *h, double *const *A, const double *C, 
     const int sel = entry_code(entries);
     Stopwatch stage_watch, watch;
     if ((rc = stage_watch.start(st))) return rc;
-    KT_DISPATCH(KS, hipLaunchKernelGGL((k_cx_stage<KT_>), dim3(tiles, slabs), dim3(64 * RC_WAVES), (size_t)4 * KT_ * 64 * sizeof(double),
-                                       st, (const double *)d.X, (const uint8_t *)d.codes, d.ldn, (int)n, p, U, cp, K,
-                                       (const double *)cs, sel, slab_len, axis, Dpad, stage.get()));
+    KT_DISPATCH(KS, {
+        h->cx_form = KT_;
+        hipLaunchKernelGGL((k_cx_stage<KT_>), dim3(tiles, slabs), dim3(64 * RC_WAVES), (size_t)4 * KT_ * 64 * sizeof(double),
+                           st, (const double *)d.X, (const uint8_t *)d.codes, d.ldn, (int)n, p, U, cp, K,
+                           (const double *)cs, sel, slab_len, axis, Dpad, stage.get());
+    });
     KCHECK();
     hipLaunchKernelGGL(k_cx_norm, dim3(cdiv(npad, 64)), dim3(64), 0, st, stage.get(), depth, N, npad, Dpad, dalive.get());
     KCHECK();

@@ -133,6 +133,8 @@ def test_glm_option_and_info_keys_are_declared():
     for key in ("glm_slabs", "glm_form"):
         assert f'"{key}"' in hdr and f's == "{key}"' in src, key
     assert src.count('s == "glm_slabs"') == 2                 # an option and an info key
+    for key in ("ls_form", "fd_form", "rc_form", "cx_form"):  # the forms tests/test_gpu_posthoc_forms.py asserts
+        assert f'"{key}"' in hdr and src.count(f's == "{key}"') == 1 and f"h->{key} = " in src, key
 
 
 _FIT_CALLS = {
