@@ -604,15 +604,12 @@ REG_DEFINE_SWEEP3(48)
 #undef REG3_PS_STR
 static_assert(reg3_ps(36) * 8 == 136 && reg3_ps(40) * 8 == 264 && reg3_ps(44) * 8 == 392 && reg3_ps(48) * 8 == 520, "REG3_PS_STR");
 
-// does the instantiation take its successor list as absolute address pairs (else: 32-bit offsets)?
-__host__ __device__ constexpr bool reg_pairs(int KMAX) { return KMAX <= 30; }
+// (reg_pairs(KMAX), absolute address pairs or 32-bit offsets in the successor list, and reg_kmax(K): insider_shapes.hpp)
 // waves per SIMD the register budget of an instantiation is sized for (512 VGPRs per SIMD lane)
 #ifndef INSIDER_REG_4WAVE_MAX
 #define INSIDER_REG_4WAVE_MAX 20   // largest KMAX built for 4 waves per SIMD (128 VGPRs)
 #endif
 __host__ __device__ constexpr int reg_waves(int KMAX) { return KMAX <= INSIDER_REG_4WAVE_MAX ? 4 : (KMAX <= 32 ? 3 : 2); }
-// smallest instantiated KMAX >= K
-__host__ __device__ constexpr int reg_kmax(int K) { return K <= 16 ? 16 : (K <= 32 ? (K + 1) & ~1 : (K + 3) & ~3); }
 // register slots of an instantiation (the third slot's Gram columns live in LDS)
 __host__ __device__ constexpr int reg_rs(int SLOTS) { return SLOTS < 3 ? SLOTS : 2; }
 // the wave's panel of third-slot Gram columns (SLOTS == 3), else nothing

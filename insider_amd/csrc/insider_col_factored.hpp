@@ -17,8 +17,7 @@
 
 namespace insider {
 
-constexpr int CF_MAXC = 8;        // covariates
-constexpr int CF_CAP = 2048;      // uint16 look-up indices staged per wave (entries x later covariates)
+// (CF_MAXC covariates; CF_CAP look-up indices staged per wave: insider_shapes.hpp)
 constexpr int CP_MAXSTEPS = 8;    // pair-count form: table rows / 4 (k-steps of the count product)
 constexpr int CP_MAXCELLS = 4096; // pair-count form: count bytes one pass of the builder histograms in LDS
 
@@ -706,7 +705,7 @@ __global__ void __launch_bounds__(WPB * 64) k_pair_count_build(ColFacArgs a, uin
 //        + sum_{t' < t} sum_{l'} n^{t'}_j(l', column of (t, l)) V_j[level l' of t']  (the tables of the covariates before it,
 //                                                                                     read transposed).
 // One wave per gene, ~20 instructions per block of 16 levels instead of one look-up per held-out entry and other covariate.
-constexpr int GU_BATCH = 8;   // blocks of 16 levels whose partial sums share one trip through LDS (k_gene_u_cnt)
+// (GU_BATCH blocks of 16 levels share one trip of their partial sums through LDS: insider_shapes.hpp)
 template <int WPB>
 __global__ void __launch_bounds__(WPB * 64) k_gene_u_cnt(ColFacArgs a, int t, int LP, const double *__restrict__ V, int SLP,
                                                          int SL, double *__restrict__ U)

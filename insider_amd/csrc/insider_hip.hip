@@ -39,7 +39,7 @@
 
 using namespace insider;
 
-#include "insider_plan.hpp"   // (after the kernel headers and the using-directive: it reads their constants)
+#include "insider_plan.hpp"
 
 namespace {
 
@@ -411,7 +411,7 @@ struct Options {
     int wg_waves = 1024;              // "row_gemm_waves": waves the GEMM is cut into (sets the number of gene slabs)
     int row_fused = 1;                // "row_fused": level records' tail + equations + solve of the merged update in one launch
     int mm_fast = 1;                  // "mm_fast": the small dense products on k_mm_rows2 / k_mm_reduce2 (default; 2: two column tiles per wave in the reductions)
-    int mm_tiles = 0;                 // "mm_tiles": tiles of 16 rows a wave of k_mm_rows2 takes (0, default = mm_tiles_per_wave()'s rule)
+    int mm_tiles = 0;                 // "mm_tiles": tiles of 16 rows a wave of k_mm_rows2 takes (0, default = mm_tiles_per_wave()'s rule, insider_plan.hpp)
     int col_mfma4 = 1;                // "col_mfma4": pair-count statistics with the second product on v_mfma_f64_4x4x4 (k_col_paircnt4; default)
     int cd_pairs = 1;                 // "cd_pairs": route the sweeps through the kernel's blocks of two coordinate steps (default)
     int list_fine = 1;                // "list_fine": 1 (default) = k_list_stats4 (4x4x4 matrix instruction) where it applies, 0 = k_list_stats
@@ -489,8 +489,8 @@ struct insider_hip_handle {
     // of the last column-side statistics launch (launch_col_stats): the kernel that formed them (ColStatsKernel), and for
     // k_col_paircnt4 the ticket counters it drew from and its grid size (0 for the other kernels)
     int col_stats_kernel = 0, col_stats_tickets = 0, col_stats_blocks = 0;
-    // of the last Q = S A / Qheld = S^held A product (launch_mm_rows_kp): 1 = k_mm_rows, 2 = k_mm_rows2; and tiles_per_wave of the
-    // last k_mm_rows2 launch from either site (launch_mm_rows_kp, launch_gene_v)
+    // of the last Q = S A / Qheld = S^held A product (launch_q): 1 = k_mm_rows, 2 = k_mm_rows2; and tiles_per_wave of the
+    // last k_mm_rows2 launch from either site (launch_q, launch_gene_v)
     int col_q_kernel = 0, mm_rows2_tiles = 0;
     // of the last optimize() / optimize_row(): one bit per row-phase kernel form it launched (RowKernel)
     uint64_t row_kernels = 0;
@@ -527,9 +527,6 @@ struct insider_hip_handle {
 
 namespace {
 
-constexpr int PC4_PARTS = 16;        // ticket counters of k_col_paircnt4
-constexpr int MM_SLAB = 128;  // rows per partial of the reduction products (insider_mm.hpp)
-
 // the kernel forms the row phase can launch, as insider_hip_get_info("row_kernels") reports them: bit RK_* is set on the host
 // where its form is launched (include/insider_hip.h; insider_amd/_lib.py ROW_KERNELS names them in this order)
 enum RowKernel {
@@ -548,11 +545,12 @@ PlanFacts plan_facts(const insider_hip_handle *h, int K)
     const DataSet &d = *h->ds;
     PlanFacts f;
     const Options &o = h->opt;
-    f.opt = {o.row_merged, o.col_factored, o.row_fused, o.row_gemm, o.row_counts, o.mm_fast, o.force_allreduce, o.wg_waves};
-    f.world = h->world;
-    f.K = K; f.NB = h->ws.NB; f.KP = h->ws.KP; f.lvl_zero = (bool)h->ws.lvl_zero;
+    f.opt = {o.row_merged, o.col_factored, o.row_fused, o.row_gemm, o.row_counts, o.mm_fast, o.force_allreduce, o.wg_waves,
+             o.list_fine, o.mm_tiles, o.col_mfma4, o.cd_variant, o.cd_pairs, o.cd_cold_iters, o.cd_pass_first, o.cd_pass_ratio, o.max_sweeps};
+    f.world = h->world; f.n_simd = d.n_simd;
+    f.K = K; f.NB = h->ws.NB; f.KP = h->ws.KP; f.lvl_zero = (bool)h->ws.lvl_zero; f.fperm = (bool)h->ws.fperm;
     f.merged = d.merged; f.cont_merged = d.cont_merged; f.cf_pair_ok = d.cf_pair_ok; f.cf_hn = (bool)d.cf_hn; f.cf_zt = (bool)d.cf_zt;
-    f.c = d.c; f.m = d.m; f.SL = d.SL; f.SLcat = d.SLcat; f.p = d.p; f.col_entries = d.col_entries; f.row_entries = d.row_entries;
+    f.c = d.c; f.m = d.m; f.SL = d.SL; f.SLP = d.SLP; f.SLcat = d.SLcat; f.n = d.n; f.p = d.p; f.col_entries = d.col_entries; f.row_entries = d.row_entries;
     for (const CovTables &ct : d.cov) { f.L.push_back(ct.L); f.npairs.push_back(ct.npairs); }
     f.cf_c = d.cf.c; f.cf_tab_rows = d.cf.tab_rows; f.cf_nsteps = d.cf.nsteps;
     std::copy(d.cf.L, d.cf.L + CF_MAXC + 1, f.cf_L);
@@ -700,9 +698,8 @@ int launch_list_stats(insider_hip_handle *h, bool cols, int nseg, const double *
     const int *lidx = cols ? h->ds->col_idx : h->ds->row_idx;
     const double *lval = cols ? h->ds->col_val : h->ds->row_val;
     const int64_t items = (int64_t)units * nseg;
-    // 16 <= K <= 31: the 4x4x4 form of the matrix instruction (fewer wasted outputs: 28 tiles instead of 3 blocks at K = 25)
-    const int NT = (h->ws.K + 4) / 4;
-    if (h->opt.list_fine && h->ws.NB == 2 && NT >= 5 && NT <= 8 && h->ws.fperm) {
+    if (h->plan.list4) {
+        const int NT = (h->ws.K + 4) / 4;
         // the rows in the tile-pair order the kernel's 16-byte loads want (a copy: every other consumer keeps F's order)
         hipLaunchKernelGGL(k_tile_perm, dim3(cdiv(f_rows * h->ws.KP, 256)), dim3(256), 0, h->st.stream, F, f_rows, h->ws.KP, h->ws.fperm);
 #define LS4(NT_)                                                                                                               \
@@ -727,25 +724,15 @@ int launch_list_stats(insider_hip_handle *h, bool cols, int nseg, const double *
 }
 
 // ---- the small dense products on MFMA (insider_mm.hpp) -------------------------------------------------------------------
-// k_mm_rows2: tiles of 16 rows one wave takes — one until the grid fills every SIMD twice, then as many as keep it at that
-// (option "mm_tiles" >= 1: that many)
-int mm_tiles_per_wave(const insider_hip_handle *h, int tiles)
-{
-    if (h->opt.mm_tiles >= 1) return h->opt.mm_tiles;
-    return std::max(1, tiles / (2 * h->ds->n_simd));
-}
-
-// out[M x KP] = X[M x Kd] W[Kd x KP]   (W row-major with pitch KP)
-bool mm_rows2_fits(const insider_hip_handle *h, int64_t ldx, int M, int Kd)
-{
-    return h->opt.mm_fast && M >= MM_FAST_MIN && ldx % 2 == 0 && (size_t)4 * cdiv(Kd, 16) * h->ws.NB * 64 * sizeof(double) <= 64 * 1024;
-}
-int launch_mm_rows_kp(insider_hip_handle *h, const double *X, int64_t ldx, int M, int Kd, const double *W, double *out,
-                      hipStream_t st = nullptr)
+// out[p x KP] = Sx[p x SL] Astack[SL x KP] for Sx = S (Q) or S^held (Qheld): p rows of pitch SLP   (Astack row-major with pitch KP)
+int launch_q(insider_hip_handle *h, const double *X, double *out, hipStream_t st = nullptr)
 {
     if (!st) st = h->st.stream;
-    if (mm_rows2_fits(h, ldx, M, Kd)) {
-        const int tiles = cdiv(M, 16), tpw = mm_tiles_per_wave(h, tiles);
+    const int64_t ldx = h->ds->SLP;
+    const int M = (int)h->ds->p, Kd = h->ds->SL;
+    const double *W = h->ws.Astack;
+    if (h->plan.q_rows2) {
+        const int tiles = cdiv(M, 16), tpw = h->plan.mm_tpw;
         const size_t lds2 = (size_t)4 * cdiv(Kd, 16) * h->ws.NB * 64 * sizeof(double);   // W staged in LDS
         NB_DISPATCH(h->ws.NB, {
             (void)WPB_;
@@ -776,14 +763,15 @@ int launch_mm_reduce_kp(insider_hip_handle *h, const double *X, int64_t ldx, con
     if (!st) st = h->st.stream;
     const int slabs = cdiv(M, MM_SLAB);
     if (nslab) *nslab = slabs;
-    if (h->opt.mm_fast && M >= MM_FAST_MIN && L > 16) {   // several column tiles of X per wave, deeper look-ahead; the same partial sums (k_mm_reduce2)
+    const ReduceForm form = reduce_form(h->plan, M, L);
+    if (form != MR_REDUCE) {
         const int lt = cdiv(L, 16);
 #define MR2(NBV, LTV)                                                                                                         \
     hipLaunchKernelGGL((k_mm_reduce2<NBV, LTV>), dim3(slabs, cdiv(lt, LTV)), dim3(64), 0, st, X, ldx, Y, (int64_t)h->ws.KP, M,   \
                        MM_SLAB, L, h->ws.KP, part, h->ws.KP)
         NB_DISPATCH(h->ws.NB, {
             (void)WPB_;
-            if (lt <= 2 || h->opt.mm_fast == 2 || NB_ > 2) {
+            if (form == MR_REDUCE2_2) {
                 MR2(NB_, 2);
                 if (mark) *mark |= rk_bit(RK_MM_REDUCE2_2);
             } else {
@@ -853,10 +841,10 @@ int phase_R(insider_hip_handle *h, bool use_side = false, bool r_is_current = fa
         HIPCHECK(hipStreamWaitEvent(h->st.side, h->st.ev_a_ready, 0));
         if (want_qheld && h->ws.Qheld && h->plan.col_path != 0) {
             HIPCHECK(hipStreamWaitEvent(h->st.side3, h->st.ev_a_ready, 0));
-            if (int rh = launch_mm_rows_kp(h, h->ds->Sheld, h->ds->SLP, (int)h->ds->p, h->ds->SL, h->ws.Astack, h->ws.Qheld, h->st.side3)) return rh;
+            if (int rh = launch_q(h, h->ds->Sheld, h->ws.Qheld, h->st.side3)) return rh;
             if (int rh = h->st.qheld.record(h->st.side3)) return rh;
         }
-        int rq = launch_mm_rows_kp(h, h->ds->S, h->ds->SLP, (int)h->ds->p, h->ds->SL, h->ws.Astack, h->ws.Qfull, h->st.side);
+        int rq = launch_q(h, h->ds->S, h->ws.Qfull, h->st.side);
         if (rq) return rq;
         if ((rq = h->st.qfull.record(h->st.side))) return rq;
     }
@@ -865,7 +853,7 @@ int phase_R(insider_hip_handle *h, bool use_side = false, bool r_is_current = fa
     rc = launch_gram(h, h->ws.R, h->ds->n, h->ws.RtR);
     if (rc) return rc;
     if (use_side) return INSIDER_OK;
-    return launch_mm_rows_kp(h, h->ds->S, h->ds->SLP, (int)h->ds->p, h->ds->SL, h->ws.Astack, h->ws.Qfull);
+    return launch_q(h, h->ds->S, h->ws.Qfull);
 }
 
 struct Timer {   // HIP-event pair around one launch on the library's stream (option "profile")
@@ -923,31 +911,20 @@ struct Stopwatch {
     }
 };
 
-// 32 < K <= 48 with an l1 term: the register-resident kernel with its third slot's matrix columns in LDS (insider_cd_reg.hpp)
-static bool reg3_path(int K, double la) { return K > 32 && K <= 48 && la > 0.0; }
-
-// the kernels launch_col_solve() can launch, as insider_hip_get_info("col_solver" / "col_eval") reports them, and the one the
-// batch entry launched (insider_hip_last_cd_solver; include/insider_hip.h; insider_amd/_lib.py COL_SOLVERS mirrors the names)
-enum ColSolver {
-    CS_NONE = 0, CS_RIDGE_REG = 1, CS_RIDGE = 2, CS_CD_REG = 3, CS_CD_REG3 = 4, CS_CD_COLS16 = 5, CS_CD_COLS32 = 6,
-    CS_CD_COLS64 = 7, CS_CD_R16_1 = 8, CS_CD_R16_2 = 9, CS_CD_R16_3 = 10
-};
-
-// The elastic-net solve kernel for K, lambda alpha and the option cd_variant: the column update's and the batch entry's.
-static ColSolver cd_solver(int K, double la, int cd_variant)
+// the elastic-net parameters as the kernels take them: the column update's and the batch entry's
+static CdParams cd_params(double lambda, double alpha, double tol, int max_sweeps, const uint8_t *order)
 {
-    // the register-resident kernel scales its state by 1 / (2 lambda alpha): lambda alpha = 0 (alpha < 0 or lambda = 0: no l1
-    // term at all) takes the group kernel below
-    if (cd_variant == 0 && (K <= 32 || reg3_path(K, la)) && la > 0.0) return K <= 32 ? CS_CD_REG : CS_CD_REG3;
-    if (cd_variant == 2 && K <= 16) return CS_CD_R16_1;
-    if (cd_variant == 2 && K <= 32) return CS_CD_R16_2;
-    if (K <= 16) return CS_CD_COLS16;
-    if (K <= 32) return CS_CD_COLS32;
-    // 32 < K <= 48 when the register-resident kernel's three-slot form does not apply (cd_variant = 2, or no l1 term): four genes
-    // per wavefront with the whole Gram matrices in LDS (row16 kernel, three coordinate slots per lane).  Beyond 48 a CU's LDS
-    // holds one such wave and the group kernel is faster; it also stays as cd_variant = 1 (cross-check)
-    if (cd_variant != 1 && K <= 48) return CS_CD_R16_3;
-    return CS_CD_COLS64;
+    CdParams c;
+    c.lambda = lambda;
+    c.alpha = alpha;
+    c.tol = tol;
+    c.la = lambda * alpha;
+    c.l2 = lambda * (1.0 - alpha);
+    c.two_la = 2.0 * c.la;
+    c.inv_two_la = c.la > 0.0 ? 0.5 / c.la : 0.0;
+    c.max_sweeps = max_sweeps;
+    c.order = order;
+    return c;
 }
 
 // one launch of the elastic-net kernel s over the a.p genes of `a` (a.mode: the solve or, outside the register-resident
@@ -992,14 +969,13 @@ static int probe_code_base(int K, unsigned long long *d, hipStream_t st, unsigne
     return INSIDER_OK;
 }
 
-// The sweep-order table (one period of rows at most, + the look-ahead row) for solves with the kernel s: rows for K > 32 carry
-// 64 row offsets (row16 kernel) unless s takes the register-resident kernel's successor list.  code_base / pair_base:
-// probe_code_base's addresses (pair_base 0: one step per block).
-static int launch_order_table(uint64_t seed, uint32_t iter, int K, int rows, int order_mode, ColSolver s,
+// The sweep-order table (one period of rows at most, + the look-ahead row).  wide: its rows carry 64 row offsets
+// (order_wide_rows, insider_plan.hpp).  code_base / pair_base: probe_code_base's addresses (pair_base 0: one step per block).
+static int launch_order_table(uint64_t seed, uint32_t iter, int K, int rows, int order_mode, bool wide,
                               unsigned long long code_base, unsigned long long pair_base, uint8_t *out, hipStream_t st)
 {
     hipLaunchKernelGGL(k_order_table, dim3(cdiv((int64_t)(rows + 1) * 64, 256)), dim3(256), 0, st, seed, iter, K, rows, order_mode,
-                       K * 8, reg_kmax(K), (K > 32 && s != CS_CD_REG3) ? 1 : 0, code_base, pair_base, out);
+                       K * 8, reg_kmax(K), wide ? 1 : 0, code_base, pair_base, out);
     KCHECK();
     return INSIDER_OK;
 }
@@ -1019,7 +995,7 @@ int ensure_code_base(insider_hip_handle *h, int K)
 // (h->ws.order) when its solve is launched.  Two buffers: an outer iteration's table depends on (seed, iter) only, so the NEXT one
 // is built while the current solve runs — the sweep kernel leaves no room for other waves, so the builder runs in its tail,
 // on SIMDs that have already drained — instead of competing with the row phase.
-int ensure_order_table(insider_hip_handle *h, uint64_t seed, uint32_t iter, int K, int max_sweeps, int order_mode, double la,
+int ensure_order_table(insider_hip_handle *h, uint64_t seed, uint32_t iter, int K, int max_sweeps, int order_mode,
                        hipStream_t stream = nullptr, int slot = 0)
 {
     if (int rb = ensure_code_base(h, K)) return rb;
@@ -1031,8 +1007,8 @@ int ensure_order_table(insider_hip_handle *h, uint64_t seed, uint32_t iter, int 
             if (int rc = b.alloc((size_t)(rows + 4) * ORDER_ROW)) return rc;   // + the look-ahead row (and the prologue's touch of the one after)
         h->ws.order_rows = rows;
     }
-    if (int rc = launch_order_table(seed, iter, K, rows, order_mode, cd_solver(K, la, h->opt.cd_variant), h->ws.cd_code_base,
-                                    h->opt.cd_pairs ? h->ws.cd_pair_base : 0ull, h->ws.order_buf[slot], stream))
+    if (int rc = launch_order_table(seed, iter, K, rows, order_mode, h->plan.order_wide, h->ws.cd_code_base,
+                                    h->plan.order_pairs ? h->ws.cd_pair_base : 0ull, h->ws.order_buf[slot], stream))
         return rc;
     if (!h->ws.order) h->ws.order = h->ws.order_buf[slot];
     return INSIDER_OK;
@@ -1055,30 +1031,16 @@ int launch_gene_order(insider_hip_handle *h, const int *sweeps, int reset, int f
     return INSIDER_OK;
 }
 
-// the kernels launch_col_stats() can launch, as insider_hip_get_info("col_stats_kernel") reports them
-// (include/insider_hip.h; insider_amd/_lib.py COL_STATS_KERNELS mirrors the names).  k_col_paircnt4<., ., 8, true> is compiled
-// (the PC4 macro instantiates it) but never launched: real-valued counts with more than four k-steps take k_col_paircnt.
-enum ColStatsKernel {
-    CSK_NONE = 0, CSK_LIST = 1, CSK_LIST4 = 2, CSK_FACTORED = 3, CSK_PAIRCNT = 4, CSK_PAIRCNT_ZT = 5, CSK_PAIRCNT4_MS4 = 6,
-    CSK_PAIRCNT4_MS8 = 7, CSK_PAIRCNT4_MS4_ZT = 8
-};
-
 // the pair-count statistics kernel (insider_col_factored.hpp) over every gene, on the main stream
 int launch_paircnt(insider_hip_handle *h, const ColFacArgs &a)
 {
-    const int blocks = cdiv(a.p, 4);
-    if (h->opt.col_mfma4 && h->ws.NB <= 2 && !(a.zt && a.nsteps > 4)) {   // (real-valued counts with more than four k-steps: 180 registers, two waves per SIMD)
-        // second product on the 4x4x4 matrix instruction, factor rows of every position staged in LDS (k_col_paircnt4);
-        size_t quads = 1;
-        for (int t = 0; t < a.c + (a.zt ? 1 : 0); ++t) quads += (size_t)(a.L[t] + 3) / 4;
-        const size_t lds = ((size_t)4 * 16 * 17 + (size_t)h->ws.KP * h->ws.KP + (size_t)4 * a.nsteps * h->ws.KP + 4 * quads * h->ws.KP) * sizeof(double);
-        if (lds <= 64 * 1024) {
-            // as many blocks as stay resident (48.6 KB of LDS at c3: three per CU); each walks the groups of four genes with the grid's stride
-            const int resident = std::max(1, std::min((int)(160 * 1024 / lds), (a.zt && a.nsteps > 4) ? 2 : 3)) * std::max(1, h->ds->n_simd / 4);   // registers: 148 - 166 (180 with real-valued counts and more than four k-steps)
-            int nb = std::min(blocks, resident);
-            const int npart = nb >= PC4_PARTS ? PC4_PARTS : 1;      // ticket counters in use (k_col_paircnt4)
-            nb -= nb % npart;
-            const int cap = cdiv(a.p, npart);
+    const FitPlan &plan = h->plan;
+    const size_t lds = plan.pc_lds;
+    switch (plan.pc_kernel) {
+        case CSK_PAIRCNT4_MS4:
+        case CSK_PAIRCNT4_MS8:
+        case CSK_PAIRCNT4_MS4_ZT: {
+            const int nb = plan.pc_blocks, npart = plan.pc_parts, cap = cdiv(a.p, npart);
             // a launch with ONE counter (few blocks) has a counter of its own behind the sixteen, so that the sixteen always
             // stand at the same value
             const int which = npart == 1 ? 1 : 0;
@@ -1089,30 +1051,33 @@ int launch_paircnt(insider_hip_handle *h, const ColFacArgs &a)
         if (a.zt) hipLaunchKernelGGL((k_col_paircnt4<NBV, 4, MS, true>), dim3(nb), dim3(256), lds, h->st.stream, a, tk, tbase, npart, cap); \
         else hipLaunchKernelGGL((k_col_paircnt4<NBV, 4, MS, false>), dim3(nb), dim3(256), lds, h->st.stream, a, tk, tbase, npart, cap); \
     }
-            if (h->ws.NB == 1 && a.nsteps <= 4) PC4(1, 4)
+            const bool ms4 = plan.pc_kernel != CSK_PAIRCNT4_MS8;
+            if (h->ws.NB == 1 && ms4) PC4(1, 4)
             else if (h->ws.NB == 1) PC4(1, 8)
-            else if (a.nsteps <= 4) PC4(2, 4)
+            else if (ms4) PC4(2, 4)
             else PC4(2, 8)
 #undef PC4
             KCHECK();
             // what the launch takes from each counter in use: its items and one ticket per wave (only once it is known to be enqueued)
             h->ws.pc4_base[which] += (unsigned)cap + 4u * (unsigned)(nb / npart);
-            h->col_stats_kernel = a.zt ? CSK_PAIRCNT4_MS4_ZT : a.nsteps <= 4 ? CSK_PAIRCNT4_MS4 : CSK_PAIRCNT4_MS8;
+            h->col_stats_kernel = a.zt ? CSK_PAIRCNT4_MS4_ZT : ms4 ? CSK_PAIRCNT4_MS4 : CSK_PAIRCNT4_MS8;
             h->col_stats_tickets = npart;
             h->col_stats_blocks = nb;
             return INSIDER_OK;
         }
+        case CSK_PAIRCNT:
+        case CSK_PAIRCNT_ZT:
+            NB_DISPATCH(h->ws.NB, {
+                (void)WPB_;
+                if (a.zt) hipLaunchKernelGGL((k_col_paircnt<NB_, 4, true>), dim3(cdiv(a.p, 4)), dim3(256), lds, h->st.stream, a);
+                else hipLaunchKernelGGL((k_col_paircnt<NB_, 4, false>), dim3(cdiv(a.p, 4)), dim3(256), lds, h->st.stream, a);
+            });
+            KCHECK();
+            h->col_stats_kernel = a.zt ? CSK_PAIRCNT_ZT : CSK_PAIRCNT;
+            h->col_stats_tickets = h->col_stats_blocks = 0;
+            return INSIDER_OK;
+        default: return fail(INSIDER_ERR_ARG, "the call's plan names no pair-count statistics kernel");
     }
-    NB_DISPATCH(h->ws.NB, {
-        (void)WPB_;
-        const size_t lds = ((size_t)4 * 16 * 17 + (size_t)Geo<NB_>::KP * Geo<NB_>::KP + (size_t)4 * a.nsteps * Geo<NB_>::KP) * sizeof(double);
-        if (a.zt) hipLaunchKernelGGL((k_col_paircnt<NB_, 4, true>), dim3(blocks), dim3(256), lds, h->st.stream, a);
-        else hipLaunchKernelGGL((k_col_paircnt<NB_, 4, false>), dim3(blocks), dim3(256), lds, h->st.stream, a);
-    });
-    KCHECK();
-    h->col_stats_kernel = a.zt ? CSK_PAIRCNT_ZT : CSK_PAIRCNT;
-    h->col_stats_tickets = h->col_stats_blocks = 0;
-    return INSIDER_OK;
 }
 
 // masked Gram/XtY complement statistics of every gene (column side of src/optimize.cpp:216-222)
@@ -1127,7 +1092,7 @@ int launch_col_stats(insider_hip_handle *h, bool timed)
     } else {
         if ((rc = t.begin(h, timed))) return rc;
         if (factored)
-            if ((rc = launch_mm_rows_kp(h, h->ds->Sheld, h->ds->SLP, (int)h->ds->p, h->ds->SL, h->ws.Astack, h->ws.Qheld))) return rc;
+            if ((rc = launch_q(h, h->ds->Sheld, h->ws.Qheld))) return rc;
     }
     if (factored) {
         ColFacArgs a = h->ds->cf;
@@ -1197,6 +1162,10 @@ int launch_col_solve(insider_hip_handle *h, int masked, bool solve, double lambd
     if ((rc = h->st.qfull.wait(h->st.stream))) return rc;
     Timer t;
     if ((rc = t.begin(h, timed))) return rc;
+    const FitPlan &plan = h->plan;
+    const ColSolver cs = plan.col_solver;
+    if (cs == CS_NONE || (alpha == 0.0) != (cs == CS_RIDGE_REG || cs == CS_RIDGE))
+        return fail(INSIDER_ERR_ARG, "the call's plan names no kernel for this column solve");
     bool eval_after = false, fused_bucket = false;
     ColArgs eval_args;
     h->col_solver = h->col_eval = h->col_ridge_fallback = CS_NONE;
@@ -1209,7 +1178,7 @@ int launch_col_solve(insider_hip_handle *h, int masked, bool solve, double lambd
         a.mark = h->ws.sweeps;          // free in the alpha == 0 path: cleared below
         a.retry = h->ws.failflag + 1;
         a.only_marked = 0;
-        if (h->ws.K <= 32 && h->opt.cd_variant == 0) {
+        if (cs == CS_RIDGE_REG) {
             if (solve) {
                 HIPCHECK(hipMemsetAsync(h->ws.sweeps, 0, (size_t)h->ds->p * sizeof(int), h->st.stream));
                 HIPCHECK(hipMemsetAsync(h->ws.failflag + 1, 0, sizeof(int), h->st.stream));
@@ -1217,7 +1186,7 @@ int launch_col_solve(insider_hip_handle *h, int masked, bool solve, double lambd
             REG_DISPATCH(h->ws.K, hipLaunchKernelGGL((k_ridge_cols_reg<SL_, KM_>), dim3(cdiv(h->ds->p, 4)), dim3(64), 0, h->st.stream, a));
             h->col_solver = CS_RIDGE_REG;
             KCHECK();
-            if (solve) {   // genes whose system was not positive definite: solve(..., likely_sympd)'s general route
+            if (solve && plan.ridge_fallback) {   // genes whose system was not positive definite: solve(..., likely_sympd)'s general route
                 a.only_marked = 1;
                 hipLaunchKernelGGL((k_ridge_cols<1>), dim3((unsigned)h->ds->p), dim3(64), 0, h->st.stream, a);   // unmarked genes exit at once
                 h->col_ridge_fallback = 1;
@@ -1232,15 +1201,7 @@ int launch_col_solve(insider_hip_handle *h, int masked, bool solve, double lambd
         ColArgs a;
         col_args_head(h, masked, checkpoint, a);
         a.mode = solve ? COL_CD : COL_EVAL;
-        a.cd.lambda = lambda;
-        a.cd.alpha = alpha;
-        a.cd.tol = tol;
-        a.cd.la = lambda * alpha;
-        a.cd.l2 = lambda * (1.0 - alpha);
-        a.cd.two_la = 2.0 * a.cd.la;
-        a.cd.inv_two_la = a.cd.la > 0.0 ? 0.5 / a.cd.la : 0.0;
-        a.cd.max_sweeps = h->opt.max_sweeps;
-        a.cd.order = h->ws.order;
+        a.cd = cd_params(lambda, alpha, tol, h->opt.max_sweeps, h->ws.order);
         a.sweeps = h->ws.sweeps;
         a.sweep_bins = (timed && solve) ? h->ws.sweep_total : nullptr;
         a.gene_perm = !solve ? nullptr : (early && h->ws.have_early[outer_iter]) ? h->ws.perm_early[outer_iter]
@@ -1256,7 +1217,6 @@ int launch_col_solve(insider_hip_handle *h, int masked, bool solve, double lambd
         a.sched_key = a.sched_cnt = a.sched_rank = nullptr;
         a.sched_bkt = nullptr;
         a.sched_reset = 0;
-        const ColSolver cs = cd_solver(h->ws.K, a.cd.la, h->opt.cd_variant);
         if (cs == CS_CD_REG || cs == CS_CD_REG3) {
             // Cold outer iterations: thousands of sweeps per gene whose counts no history predicts, so a wave's four genes
             // finish far apart (measured at c3: 1.17x / 1.44x / 2.1x the ideal wave time in outer iterations 0 / 1 / 2).
@@ -1272,15 +1232,11 @@ int launch_col_solve(insider_hip_handle *h, int masked, bool solve, double lambd
                 a.sched_reset = (outer_iter < Workspace::EARLY || !h->ws.have_perm) ? 1 : 0;
                 fused_bucket = true;
             }
-            int limits[16], npass = 0;
-            if (solve && outer_iter >= 0 && outer_iter < h->opt.cd_cold_iters && h->opt.cd_pass_first >= 32)
-                for (int64_t l = h->opt.cd_pass_first; l < std::min<int64_t>(h->opt.max_sweeps, 4 * (int64_t)INSIDER_PERM_PERIOD) && npass < 16;
-                     l *= std::max(h->opt.cd_pass_ratio, 2))
-                    limits[npass++] = (int)l;   // the last pass runs from the last limit to the end, however far that is
+            const int npass = (solve && outer_iter >= 0 && outer_iter < plan.cold_iters) ? plan.npass : 0;
             int start = 0;
             const int *perm_in = a.gene_perm;
             for (int pass = 0;; ++pass) {
-                const int limit = pass < npass ? limits[pass] : 0;
+                const int limit = pass < npass ? plan.pass_limit[pass] : 0;
                 a.cd.start_sweep = start;
                 a.cd.sweep_limit = limit;
                 a.pass_slot = npass ? h->ws.cd_pass_slot : nullptr;
@@ -1313,7 +1269,7 @@ int launch_col_solve(insider_hip_handle *h, int masked, bool solve, double lambd
         eval_args.gene_perm = nullptr;
         eval_args.pass_count = nullptr;
         eval_args.resume = 0;
-        if (h->ws.K <= 32) {
+        if (plan.col_eval == CS_CD_REG) {
             REG_DISPATCH(h->ws.K, hipLaunchKernelGGL((k_cd_cols_reg<SL_, KM_, false>), dim3(cdiv(h->ds->p, 4)), dim3(64), 0, h->st.stream, eval_args));
             h->col_eval = CS_CD_REG;
         } else {   // three slots: the row16 kernel's evaluation part (the sweep kernel's registers are all taken)
@@ -1372,7 +1328,8 @@ int launch_test_sse(insider_hip_handle *h, int masked, bool timed)
     return t.end(h, h->ev_test);
 }
 
-void plan_call(insider_hip_handle *h, int masked) { h->plan = build_plan(plan_facts(h, h->ws.K), masked); }
+// col: the call's column solve (none: a call that runs no column solve)
+void plan_call(insider_hip_handle *h, int masked, const ColCall *col = nullptr) { h->plan = build_plan(plan_facts(h, h->ws.K), masked, col); }
 
 // V = C A' for the stacked levels [q_begin, q_end) (all of them once per outer iteration, then the updated covariate's)
 int launch_gene_v(insider_hip_handle *h, int q_begin, int q_end)
@@ -1380,16 +1337,18 @@ int launch_gene_v(insider_hip_handle *h, int q_begin, int q_end)
     // V[:, q_begin:q_end) = C A[q_begin:q_end, :]'  (A given "transposed": one row per output column)
     const int N = q_end - q_begin;
     if (N <= 0) return INSIDER_OK;
-    if (h->plan.mm_fast) {   // A' staged in LDS once per block, C read in 16-byte pieces (k_mm_rows2)
-        const int tiles = cdiv((int)h->ds->p, 16), tpw = mm_tiles_per_wave(h, tiles);
+    if (h->plan.v_rows2) {   // A' staged in LDS once per block, C read in 16-byte pieces (k_mm_rows2)
+        const int tiles = cdiv((int)h->ds->p, 16), tpw = h->plan.mm_tpw;
         const size_t ldsb = (size_t)4 * cdiv(h->ws.K, 16) * 64 * sizeof(double);
 #define GV2_LAUNCH(NT_)                                                                                                       \
     hipLaunchKernelGGL((k_mm_rows2<NT_, true>), dim3(cdiv(cdiv(tiles, tpw), 4), cdiv(N, 16 * NT_)), dim3(256), ldsb * NT_, h->st.stream, \
                        (const double *)h->ws.C, (int64_t)h->ws.KP, (int)h->ds->p, h->ws.K,                                                \
                        (const double *)(h->ws.Astack + (size_t)q_begin * h->ws.KP), h->ws.KP, N, h->ws.Vlev + q_begin, (int64_t)h->ds->SLP, N, tpw)
-        if (N <= 16) GV2_LAUNCH(1);
-        else if (N <= 32) GV2_LAUNCH(2);
-        else GV2_LAUNCH(4);
+        switch (mm_rows_nt(N)) {
+            case 1: GV2_LAUNCH(1); break;
+            case 2: GV2_LAUNCH(2); break;
+            default: GV2_LAUNCH(4); break;
+        }
 #undef GV2_LAUNCH
         KCHECK();
         row_mark(h, RK_MM_ROWS2);
@@ -1400,9 +1359,11 @@ int launch_gene_v(insider_hip_handle *h, int q_begin, int q_end)
     hipLaunchKernelGGL((k_mm_rows<NT_, true>), dim3(cdiv(cdiv((int)h->ds->p, 16), 4), cdiv(N, 16 * NT_)), dim3(256), 0, h->st.stream, \
                        (const double *)h->ws.C, (int64_t)h->ws.KP, (int)h->ds->p, h->ws.K,                                                \
                        (const double *)(h->ws.Astack + (size_t)q_begin * h->ws.KP), h->ws.KP, N, h->ws.Vlev + q_begin, (int64_t)h->ds->SLP, N)
-    if (N <= 16) GV_LAUNCH(1);        // (a covariate with few levels: one 16-column tile, not four)
-    else if (N <= 32) GV_LAUNCH(2);
-    else GV_LAUNCH(4);
+    switch (mm_rows_nt(N)) {
+        case 1: GV_LAUNCH(1); break;
+        case 2: GV_LAUNCH(2); break;
+        default: GV_LAUNCH(4); break;
+    }
 #undef GV_LAUNCH
     KCHECK();
     row_mark(h, RK_MM_ROWS);
@@ -1421,7 +1382,7 @@ int launch_row_stats(insider_hip_handle *h, bool timed)
 
 int do_allreduce(insider_hip_handle *h, double *buf, int64_t count)
 {
-    if (h->world <= 1 && !h->opt.force_allreduce) return INSIDER_OK;
+    if (!h->plan.allreduce) return INSIDER_OK;
     if (h->comm) {
         // in-library RCCL: the collective is enqueued on the library's own stream, between the kernels that produce
         // and consume `buf`; no host synchronisation, no callback into the host language
@@ -1604,10 +1565,10 @@ int row_update(insider_hip_handle *h, int i, int cont_col, int masked, double la
         // Y = U'C, the same reduction over genes as (S C'); with the fused level kernel its per-slab partial sums are added up
         // there (k_sum_partials' order), which takes one launch per covariate off the main chain
         int ypart_n = 0;
-        if (int rcy = launch_mm_reduce_kp(h, h->ws.U, LP, h->ws.C, (int)h->ds->p, L, h->ws.sc_part, h->opt.row_fused ? nullptr : h->ws.Ylvl, nullptr,
+        if (int rcy = launch_mm_reduce_kp(h, h->ws.U, LP, h->ws.C, (int)h->ds->p, L, h->ws.sc_part, plan.row_fused ? nullptr : h->ws.Ylvl, nullptr,
                                           &ypart_n, &h->row_kernels))
             return rcy;
-        if (!h->opt.row_fused) ypart_n = 0;
+        if (!plan.row_fused) ypart_n = 0;
         if (h->w_ready) {   // wsyrk + level sums came from side2, C'C and (S^train C') from side3
             HIPCHECK(hipStreamWaitEvent(h->st.stream, h->st.ev_w[i], 0));
             HIPCHECK(hipStreamWaitEvent(h->st.stream, h->st.ev_prep, 0));
@@ -1617,7 +1578,7 @@ int row_update(insider_hip_handle *h, int i, int cont_col, int masked, double la
         double *rec = h->w_ready ? h->ws.lvl_sum_all + (size_t)row0 * plan.plen : h->ws.lvl_sum;
         NB_DISPATCH(h->ws.NB, {
             (void)WPB_;
-            if (h->opt.row_fused) {   // the level records' tail, the level equations and (fused_solve) the solves: one launch
+            if (plan.row_fused) {   // the level records' tail, the level equations and (fused_solve) the solves: one launch
                 hipLaunchKernelGGL((k_level_merged<NB_>), dim3(L), dim3(256), 0, h->st.stream, (const double *)rec,
                                    (const double *)(ypart_n ? h->ws.sc_part : h->ws.Ylvl), ypart_n, (const double *)ct.paircnt, h->ds->SL, (const double *)h->ws.Astack,
                                    (const int *)(h->ds->lvl_count_all + h->ds->lvl_off[i]), (const double *)h->ws.CCt,
@@ -2684,7 +2645,8 @@ static int optimize_body(insider_hip_handle *h, double *const *A, double *C, int
     reset_call_state(h, false);
     h->row_kernels = 0;
     const int masked = tuning == 1;
-    plan_call(h, masked);
+    const ColCall col{alpha, lambda2 * alpha};
+    plan_call(h, masked, &col);
     const FitPlan &plan = h->plan;
     if ((rc = upload_factors(h, A, C, K))) return rc;
 
@@ -2751,14 +2713,14 @@ static int optimize_body(insider_hip_handle *h, double *const *A, double *C, int
         if ((rc = phase_R(h, true, true, masked != 0))) return rc;
         const int checkpoint = iter % 10 == 0;
         if (alpha != 0.0 && iter == 0)   // later iterations: built on the side stream while the previous solve ran
-            if ((rc = ensure_order_table(h, seed, iter, K, h->opt.max_sweeps, h->opt.order_mode, lambda2 * alpha, nullptr, 0))) return rc;
+            if ((rc = ensure_order_table(h, seed, iter, K, h->opt.max_sweeps, h->opt.order_mode, nullptr, 0))) return rc;
         if (masked) if ((rc = launch_col_stats(h, true))) return rc;
         if (alpha != 0.0) {
             h->ws.order = h->ws.order_buf[iter & 1];
             if (iter < max_iter) {   // the next iteration's table, from here on: beside this iteration's solve
                 HIPCHECK(hipEventRecord(h->st.ev_tab, h->st.stream));
                 HIPCHECK(hipStreamWaitEvent(h->st.side, h->st.ev_tab, 0));
-                if ((rc = ensure_order_table(h, seed, iter + 1, K, h->opt.max_sweeps, h->opt.order_mode, lambda2 * alpha, h->st.side, (int)((iter + 1) & 1))))
+                if ((rc = ensure_order_table(h, seed, iter + 1, K, h->opt.max_sweeps, h->opt.order_mode, h->st.side, (int)((iter + 1) & 1))))
                     return rc;
             }
         }
@@ -2901,11 +2863,12 @@ int insider_hip_optimize_col(insider_hip_handle *h, double *const *A, double *C,
     if (rc) return rc;
     HIPCHECK(hipSetDevice(h->ds->device));
     if ((rc = ensure_workspace(h, K))) return rc;
-    plan_call(h, tuning);
+    const ColCall col{alpha, lambda * alpha};
+    plan_call(h, tuning, &col);
     if ((rc = upload_factors(h, A, C, K))) return rc;
     if ((rc = phase_R(h))) return rc;
     if (alpha != 0.0) {
-        if ((rc = ensure_order_table(h, seed, iter, K, h->opt.max_sweeps, h->opt.order_mode, lambda * alpha, nullptr, 0))) return rc;
+        if ((rc = ensure_order_table(h, seed, iter, K, h->opt.max_sweeps, h->opt.order_mode, nullptr, 0))) return rc;
         h->ws.order = h->ws.order_buf[0];
     }
     if (tuning == 1) if ((rc = launch_col_stats(h, false))) return rc;
@@ -2945,7 +2908,7 @@ static int strong_cd_device(const double *dG, const double *dq, const double *dw
     unsigned long long code[2] = {0, 0};
     if (cs == CS_CD_REG && reg_pairs(reg_kmax(K)))
         if ((rc = probe_code_base(K, cb, nullptr, code))) return rc;
-    if ((rc = launch_order_table(seed, iter, K, rows, order_mode, cs, code[0], code[1], order, nullptr))) return rc;
+    if ((rc = launch_order_table(seed, iter, K, rows, order_mode, order_wide_rows(K, cs), code[0], code[1], order, nullptr))) return rc;
     ColArgs a{};
     a.stat = stat;
     a.stat_len = stat_len;
@@ -2955,15 +2918,7 @@ static int strong_cd_device(const double *dG, const double *dq, const double *dw
     a.Qfull = Qfull;
     a.C = C;
     a.mode = COL_CD;
-    a.cd.lambda = lambda;
-    a.cd.alpha = alpha;
-    a.cd.tol = tol;
-    a.cd.la = lambda * alpha;
-    a.cd.l2 = lambda * (1.0 - alpha);
-    a.cd.two_la = 2.0 * a.cd.la;
-    a.cd.inv_two_la = a.cd.la > 0.0 ? 0.5 / a.cd.la : 0.0;
-    a.cd.max_sweeps = ms;
-    a.cd.order = order;
+    a.cd = cd_params(lambda, alpha, tol, ms, order);
     a.sweeps = sw;
     a.hsave = a.isave = C;   // read by a resumed pass only (none here)
     Stopwatch watch;
@@ -3988,11 +3943,12 @@ int insider_hip_get_info(insider_hip_handle *h, const char *name, double *out)
         // v_mfma_f64_16x16x4_f64 instructions the column-side statistics kernel issues per gene (2048 flops each; the 4x4x4 form
         // of the per-entry kernel is counted in the same unit: a quarter per instruction)
         if (!NB) return fail(INSIDER_ERR_ARG, "no workspace yet: run an update first");
-        const int path = build_plan(plan_facts(h, h->ws.K), 1).col_path;
+        const FitPlan fresh = build_plan(plan_facts(h, h->ws.K), 1);
+        const int path = fresh.col_path;
         double v = 0.0;
         if (path == 0) {
             const int NT = (h->ws.K + 4) / 4;
-            if (h->opt.list_fine && NB == 2 && NT >= 5 && NT <= 8 && h->ws.fperm)   // k_list_stats4: NT (NT + 1) / 2 instructions of 512 flops per 16 entries
+            if (fresh.list4)   // k_list_stats4: NT (NT + 1) / 2 instructions of 512 flops per 16 entries
                 v = (double)h->ds->col_entries / (double)std::max<int64_t>(h->ds->p, 1) / 16.0 * (NT * (NT + 1) / 2) / 4.0;
             else
                 v = (double)h->ds->col_entries / (double)std::max<int64_t>(h->ds->p, 1) / 4.0 * (NB * (NB + 1) / 2);

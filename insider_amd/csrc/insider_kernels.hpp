@@ -21,13 +21,13 @@
 #include <stdint.h>
 
 #include "../../include/insider_perm.h"
+#include "insider_shapes.hpp"
 
 namespace insider {
 
 typedef double d4 __attribute__((ext_vector_type(4)));
 typedef double d2 __attribute__((ext_vector_type(2)));
 
-constexpr int WAVE = 64;
 constexpr int CHUNK = 128;      // elements per streaming step (2 per lane); line pitches are multiples of it
 
 constexpr int LEVEL_CHUNK = 4;   // member samples per wave of k_level_partial (row update, stage 1)

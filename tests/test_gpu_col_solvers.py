@@ -1,12 +1,13 @@
-"""Every column-solver kernel that launch_col_solve() and the batch entry can launch, against the CPU oracle.
+"""Every column-solver kernel that the column update and the batch entry can launch, against the CPU oracle.
 
 The batch entry (insider_hip_strong_cd) runs the column update's elastic-net kernels with the default cd_variant, and
 insider_hip_last_cd_solver() reports which one; its tests assert it as well.
 
-launch_col_solve() (insider_amd/csrc/insider_hip.hip) picks one of ten kernels from the K band, from whether lambda alpha > 0,
-alpha > 0 or alpha == 0, and from the option cd_variant; insider_hip_get_info("col_solver" / "col_eval") reports which one
-ran.  SOLVER below is that choice written out by hand: each test asserts the kernel it reached, so that a dispatch edit that
-moves a band to another kernel fails the test written for the old one instead of quietly testing another kernel.
+The call's plan (build_plan() in insider_amd/csrc/insider_plan.hpp) picks one of ten kernels from the K band, from whether
+lambda alpha > 0, alpha > 0 or alpha == 0, and from the option cd_variant; insider_hip_get_info("col_solver" / "col_eval")
+reports which one ran.  SOLVER (tests/dispatch_rules.py) is that choice written out by hand: each test asserts the kernel it
+reached, so that a dispatch edit that moves a band to another kernel fails the test written for the old one instead of
+quietly testing another kernel.
 
 The operator-level checks cap the solve at three sweeps: every kernel converges to the same minimiser at a tight tol, whatever
 its coordinate order, so only a capped solve shows that a kernel reads its row of the sweep-order table correctly.
@@ -15,6 +16,8 @@ import numpy as np
 import pytest
 
 from insider_amd import _lib, api, workloads
+from tests.dispatch_rules import EVAL, SOLVER, col_solver as expected
+from tests.dispatch_rules import REGIMES as ALL_REGIMES
 from tests.support import need_gpu, relerr  # noqa: F401  (need_gpu: autouse fixture)
 
 pytestmark = pytest.mark.gpu
@@ -34,33 +37,13 @@ def solver(ds, key="col_solver"):
     return _lib.COL_SOLVERS[int(ds.info(key))]
 
 
-# (lambda, alpha) of the column update in each regime
-REGIMES = {"enet": (30.0, 0.4),     # lambda alpha > 0 and an l2 term
-           "lasso": (30.0, 1.0),    # l2 = 0: XtX_kk + l2 = 0 in a zero latent dimension
-           "nol1": (0.0, 0.5),      # lambda = 0: alpha > 0 but no l1 term, so not the register-resident kernel
-           "ridge": (30.0, 0.0)}
-
-# the kernel launch_col_solve() launches, per (regime, cd_variant), for K in 1..16 | 17..32 | 33..48 | 49..63
-SOLVER = {
-    ("enet", 0): ("cd_reg", "cd_reg", "cd_reg3", "cd_cols64"),
-    ("lasso", 0): ("cd_reg", "cd_reg", "cd_reg3", "cd_cols64"),
-    ("nol1", 0): ("cd_cols16", "cd_cols32", "cd_r16_3", "cd_cols64"),
-    ("ridge", 0): ("ridge_reg", "ridge_reg", "ridge", "ridge"),
-    ("enet", 1): ("cd_cols16", "cd_cols32", "cd_cols64", "cd_cols64"),
-    ("lasso", 1): ("cd_cols16", "cd_cols32", "cd_cols64", "cd_cols64"),
-    ("ridge", 1): ("ridge", "ridge", "ridge", "ridge"),
-    ("enet", 2): ("cd_r16_1", "cd_r16_2", "cd_r16_3", "cd_cols64"),
-    ("lasso", 2): ("cd_r16_1", "cd_r16_2", "cd_r16_3", "cd_cols64"),
-}
-
-
-def expected(regime, variant, K):
-    return SOLVER[(regime, variant)][(K - 1) // 16]
-
+# (lambda, alpha) of the column update in each regime of this file
+REGIMES = {r: ALL_REGIMES[r] for r in ("enet", "lasso", "nol1", "ridge")}
 
 # the edges of every band and an odd K inside each
 KS = [1, 2, 9, 15, 16, 17, 18, 25, 31, 32, 33, 34, 41, 47, 48, 49, 50, 55, 62, 63]
-CELLS = [(r, v, K) for (r, v) in SOLVER for K in KS if not (r == "ridge" and v == 1 and K > 32)]   # (same kernel as cd_variant 0)
+CELLS = [(r, v, K) for (r, v) in SOLVER if r in REGIMES for K in KS
+         if not (r == "ridge" and v == 1 and K > 32)]   # (same kernel as cd_variant 0)
 
 # ----------------------------------------------------------------------------------------------------------------------
 # a. operator level: optimize_col() against oracle.optimize_col()
@@ -183,8 +166,7 @@ FIT_CELLS = [("cd_reg", 0, 0.4, 1), ("cd_reg", 0, 0.4, 32), ("cd_reg3", 0, 0.4, 
              ("cd_r16_1", 2, 0.4, 1), ("cd_r16_1", 2, 0.4, 16), ("cd_r16_2", 2, 0.4, 17), ("cd_r16_2", 2, 0.4, 32),
              ("cd_r16_3", 2, 0.4, 33), ("cd_r16_3", 2, 0.4, 48), ("ridge_reg", 0, 0.0, 1), ("ridge_reg", 0, 0.0, 32),
              ("ridge", 0, 0.0, 33), ("ridge", 0, 0.0, 63), ("ridge", 1, 0.0, 1), ("ridge", 2, 0.0, 32)]
-# the evaluation pass after the register-resident solve (the three-slot kernel hands it to the row16 kernel)
-EVAL = {"cd_reg": "cd_reg", "cd_reg3": "cd_r16_3"}
+# (EVAL: the evaluation pass after the register-resident solve; the three-slot kernel hands it to the row16 kernel)
 
 
 @pytest.mark.parametrize("kernel,variant,alpha,K", FIT_CELLS, ids=[f"{k}-v{v}-K{K}" for k, v, _, K in FIT_CELLS])

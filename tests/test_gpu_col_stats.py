@@ -6,9 +6,10 @@ over the entries that are not training entries.  launch_col_stats() forms it wit
 the continuous covariates) or k_col_paircnt4 (the same with its second product on the 4x4x4 matrix instruction, MAXS = 4 or
 8 k-steps, genes dealt by ticket from one or sixteen counters).  insider_hip_col_stats() (InsiderData.col_stats) runs the
 first half of a column update and returns the record densified; insider_hip_get_info("col_stats_kernel" /
-"col_stats_tickets" / "col_stats_blocks") reports what ran.  expected() below is the dispatch written out by hand from
-FitPlan::col_path (col_stats_path() in insider_plan.hpp), launch_paircnt(), launch_list_stats() and stage_factored(): every case asserts the kernel it reached
-before it compares values, so that a dispatch edit cannot quietly move a case onto another kernel.
+"col_stats_tickets" / "col_stats_blocks") reports what ran.  expected() is the dispatch written out by hand
+(tests/dispatch_rules.py: col_structure(), col_stats_kernel(), check_pc4_blocks()) from the call's plan (col_stats_path(),
+paircnt_plan(), list_stats4() in insider_plan.hpp) and stage_factored(): every case asserts the kernel it reached before it
+compares values, so that a dispatch edit cannot quietly move a case onto another kernel.
 
 Covered: every code at the K band edges, the covariate structures (c = 1, 8, 9, tied level counts, the largest covariate
 first / in the middle / last), both sides of every fit boundary (look-up table, k-steps, k_col_paircnt4's LDS, the one-byte
@@ -16,12 +17,12 @@ count cell, k_col_factored's staged indices), continuous covariates, the ticket 
 that walk the genes, p >= 16384), stale records across launches on one workspace and on a clone, and one fit per form that
 the parity tests do not reach.
 """
-import math
-
 import numpy as np
 import pytest
 
 from insider_amd import _lib, api
+from tests import dispatch_rules as dr
+from tests.dispatch_rules import COL_OPTS as OPTS
 from tests.support import need_gpu, relerr  # noqa: F401  (need_gpu: autouse fixture)
 
 pytestmark = pytest.mark.gpu
@@ -31,66 +32,16 @@ NAME = dict(enumerate(_lib.COL_STATS_KERNELS))
 
 
 # ----------------------------------------------------------------------------------------------------------------------
-# the dispatch, by hand
+# the dispatch, by hand (tests/dispatch_rules.py) on this file's data
 # ----------------------------------------------------------------------------------------------------------------------
-OPTS = dict(col_factored=1, col_mfma4=1, list_fine=1)
-CF_MAXC = 8
-GU_TILE = 512
-
-
-def lookup_fits(tab_rows, KP):
-    """k_col_factored's LDS: (tab_rows + 1) KP doubles of table + 4 x 16 x 17 transpose scratch + 4 x CF_CAP uint16 <= 64 KB,
-    i.e. (tab_rows + 1) KP <= 5056: tab_rows <= 315 / 157 / 104 / 78 at KP = 16 / 32 / 48 / 64."""
-    return (tab_rows + 1) * KP <= 5056
-
-
-def pc4_fits(KP, nsteps, quads):
-    """k_col_paircnt4's LDS: 1088 + KP^2 + 4 nsteps KP + 4 quads KP <= 8192 doubles (nsteps + quads <= 47 at KP = 32)."""
-    return 1088 + KP * KP + 4 * nsteps * KP + 4 * quads * KP <= 8192
-
-
 def structure(c):
     """What stage_merged() / stage_factored() / stage_cont_factored() decide for a case's data set."""
-    levels, m = c["levels"], c["m"]
-    ncov, SLcat = len(levels), sum(levels)
-    merged = m <= 4 and SLcat + GU_TILE <= 2048
-    tab_rows = SLcat - max(levels)                 # every covariate but the largest (position 0) is in the table
-    nsteps = (tab_rows + 3) // 4
-    pair_ok = merged and ncov <= CF_MAXC and nsteps <= 8 and max_cell(c) <= 255
-    zt = m > 0 and pair_ok and all(SLcat + m + L + L % 2 <= 1536 for L in levels)
-    return merged, tab_rows, nsteps, pair_ok, zt
+    return dr.col_structure(c, max_cell(c))
 
 
 def expected(c):
     """(col_stats_kernel, col_stats_tickets) of one col_stats() call on the case's handle."""
-    o = {**OPTS, **c["opts"]}
-    K, levels, m, p = c["K"], c["levels"], c["m"], c["p"]
-    NB = (K + 16) // 16
-    KP = 16 * NB
-    merged, tab_rows, nsteps, pair_ok, zt = structure(c)
-    # col_stats_path()
-    if not (merged and o["col_factored"] and len(levels) <= CF_MAXC):
-        path = "list"
-    elif m > 0:
-        path = "pair" if pair_ok and zt else "list"
-    elif o["col_factored"] == 3 and pair_ok:
-        path = "pair"
-    elif o["col_factored"] >= 2:
-        # (a table too large for the look-up form has more than 78 rows: never a pair-count table, whose limit is 32)
-        path = "lookup" if lookup_fits(tab_rows, KP) else ("pair" if pair_ok else "list")
-    else:
-        path = c["cost"]          # the cost model: pinned by hand per case (COST below)
-        assert path in ("list", "lookup", "pair"), c["id"]
-    if path == "list":   # launch_list_stats(): k_list_stats4 for 16 <= K <= 31 (NB = 2, NT = 5..8)
-        return ("list4" if o["list_fine"] and 16 <= K <= 31 else "list"), 0
-    if path == "lookup":
-        return "factored", 0
-    # launch_paircnt()
-    quads = 1 + sum(math.ceil(L / 4) for L in levels) + (1 if zt else 0)
-    if o["col_mfma4"] and NB <= 2 and not (zt and nsteps > 4) and pc4_fits(KP, nsteps, quads):
-        name = "paircnt4_ms4" if nsteps <= 4 else "paircnt4_ms8"
-        return name + ("_zt" if zt else ""), 16 if math.ceil(p / 4) >= 16 else 1
-    return ("paircnt_zt" if zt else "paircnt"), 0
+    return dr.col_stats_kernel(c, structure(c))
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -206,15 +157,7 @@ def check_launch(c, ds):
     want_k, want_t = expected(c)
     assert kernel == want_k, (c["id"], kernel, want_k)
     assert tickets == want_t, (c["id"], tickets, want_t)
-    if kernel.startswith("paircnt4"):
-        nb = math.ceil(c["p"] / 4)
-        assert blocks % tickets == 0 and blocks >= tickets, blocks
-        if c["walk"]:                       # fewer resident blocks than groups of four genes: the blocks walk
-            assert 4 * blocks < c["p"], (blocks, c["p"])
-        else:
-            assert blocks == nb - nb % tickets, (blocks, nb)
-    else:
-        assert blocks == 0
+    dr.check_pc4_blocks(c, kernel, tickets, blocks)
 
 
 # ----------------------------------------------------------------------------------------------------------------------

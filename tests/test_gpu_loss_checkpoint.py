@@ -8,9 +8,9 @@ identity is written out in k_cd_cols<W, WPB>, k_ridge_cols, k_cd_cols_reg (nine 
 k_ridge_cols_reg (nine instantiations); which copy runs follows the K band, lambda alpha and cd_variant.
 
 Driver: optimize(max_iter = 0) from planted factors.  Trajectory row 0 (iter -1) is the evaluation of exactly the caller's
-(A, C) (launch_col_solve(solve = false)), compared with evaluate() of the inputs; row 1 (iter 0) is the checkpoint taken by
+(A, C) (a column solve that only evaluates), compared with evaluate() of the inputs; row 1 (iter 0) is the checkpoint taken by
 or after the first solve, compared with evaluate() of the returned factors.  The kernels are asserted by name from the
-table below, written out by hand.
+tables of tests/dispatch_rules.py, written out by hand.
 
 Contract checked on both rows (u = 2^-53; loss_reference.bounds() derives the bounds):
     every value finite where the contract says a number, NaN exactly where it says NaN (test_rmse: tuning = 0, no test entry)
@@ -30,7 +30,10 @@ import numpy as np
 import pytest
 
 from insider_amd import _lib, api
+from tests import dispatch_rules as dr
 from tests import loss_reference as lr
+from tests.dispatch_rules import REGIMES, SOLVER
+from tests.dispatch_rules import loss_stats_kernel as stats_kernel
 from tests.support import need_gpu  # noqa: F401  (need_gpu: autouse fixture)
 
 pytestmark = pytest.mark.gpu
@@ -48,51 +51,22 @@ def names(ds):
     return _lib.COL_SOLVERS[int(ds.info("col_solver"))], _lib.COL_SOLVERS[int(ds.info("col_eval"))]
 
 
-# (lambda, alpha) of the column update; the two last leave row 1 a near-exact fit on the cd_reg and ridge_reg evaluators
-REGIMES = {"enet": (30.0, 0.4), "lasso": (30.0, 1.0), "nol1": (0.0, 0.5), "ridge": (30.0, 0.0),
-           "enet_tiny": (1e-12, 0.4), "ridge_tiny": (1e-12, 0.0)}
+# (REGIMES: (lambda, alpha) of the column update; the two last leave row 1 a near-exact fit on the cd_reg and ridge_reg evaluators)
 # lambda1 of the row update: the column update's lambda, and 30 where that is 0
 LAM1 = {"enet": 30.0, "lasso": 30.0, "nol1": 30.0, "ridge": 30.0, "enet_tiny": 1e-12, "ridge_tiny": 1e-12}
 # a gene held out entirely has the system 0 b = 0: solvable only under a penalty that is not vanishing
 HELD_GENE = {"enet": True, "lasso": True, "nol1": False, "ridge": True, "enet_tiny": False, "ridge_tiny": False}
 
-# the kernel launch_col_solve() launches, per (regime, cd_variant), for K in 1..16 | 17..32 | 33..48 | 49..63
-SOLVER = {
-    ("enet", 0): ("cd_reg", "cd_reg", "cd_reg3", "cd_cols64"),
-    ("lasso", 0): ("cd_reg", "cd_reg", "cd_reg3", "cd_cols64"),
-    ("nol1", 0): ("cd_cols16", "cd_cols32", "cd_r16_3", "cd_cols64"),
-    ("ridge", 0): ("ridge_reg", "ridge_reg", "ridge", "ridge"),
-    ("enet", 1): ("cd_cols16", "cd_cols32", "cd_cols64", "cd_cols64"),
-    ("lasso", 1): ("cd_cols16", "cd_cols32", "cd_cols64", "cd_cols64"),
-    ("ridge", 1): ("ridge", "ridge", "ridge", "ridge"),
-    ("enet", 2): ("cd_r16_1", "cd_r16_2", "cd_r16_3", "cd_cols64"),
-    ("lasso", 2): ("cd_r16_1", "cd_r16_2", "cd_r16_3", "cd_cols64"),
-    ("enet_tiny", 0): ("cd_reg", "cd_reg", "cd_reg3", "cd_cols64"),
-    ("ridge_tiny", 0): ("ridge_reg", "ridge_reg", "ridge", "ridge"),
-}
-# the evaluation launch after the register-resident solves (the three-slot kernel hands it to the row16 kernel)
-EVAL = {"cd_reg": "cd_reg", "cd_reg3": "cd_r16_3"}
-
 
 def expected(regime, variant, K):
-    s = SOLVER[(regime, variant)][(K - 1) // 16]
-    return s, EVAL.get(s, "none")
+    """(col_solver, col_eval) of the call."""
+    s = dr.col_solver(regime, variant, K)
+    return s, dr.col_eval(s)
 
 
 # the statistics paths (the PATHS options of test_gpu_col_solvers.py; every option set in every call: a handle serves several)
 PATHS = {"fast": dict(row_merged=2, col_factored=2, row_counts=0), "pair": dict(row_merged=2, col_factored=3, row_counts=1),
          "lists": dict(row_merged=0, col_factored=0, row_counts=1)}
-
-
-def stats_kernel(paths, K, m=0):
-    """The column-statistics kernel of a masked call under PATHS[paths] on the data of this file (info "col_stats_kernel"),
-    by hand: seven table rows (the smaller covariate) fit the look-up form and two k-steps of the pair-count form; the pair
-    counts run on the 4x4x4 instruction up to K = 31; continuous columns take the pair-count form with real-valued counts."""
-    if paths == "lists":
-        return "list4" if 16 <= K <= 31 else "list"
-    if paths == "fast" and m == 0:
-        return "factored"
-    return ("paircnt4_ms4" if K <= 31 else "paircnt") + ("_zt" if m else "")
 
 
 # ----------------------------------------------------------------------------------------------------------------------

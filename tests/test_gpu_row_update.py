@@ -4,16 +4,17 @@ For each covariate the row update picks its level Gram sums (k_wgemm<4..7> in on
 nothing), its u (k_gene_u_cnt, k_gene_u, k_gene_uc), its record tail / equations / solve (k_level_merged with or without the
 solve, k_level_pack + k_level_reduce, k_level_solve, k_cont_cd), the per-sample chain instead (k_list_stats4 / k_list_stats,
 k_level_partial ...) and the forms of its products V = C A' and Y = U'C.  insider_hip_get_info("row_kernels") reports the
-forms the last optimize() / optimize_row() launched, one bit each (_lib.ROW_KERNELS).  expected() below is that dispatch
-written out by hand from the call's FitPlan (build_plan() in insider_plan.hpp: wgemm_plan(), use_merged(), unmasked_fused,
-fused_solve, u_cnt) and from what row_update() and launch_mm_reduce_kp() launch for it:
-every case asserts the exact set it reached before it compares values, so that a dispatch edit that moves a band to another
-kernel fails the case written for the old one instead of quietly testing another kernel.
+forms the last optimize() / optimize_row() launched, one bit each (_lib.ROW_KERNELS).  expected() (row_kernels() in
+tests/dispatch_rules.py) is that dispatch written out by hand from the call's FitPlan (build_plan() in insider_plan.hpp:
+wgemm_plan(), use_merged(), unmasked_fused, fused_solve, row_fused, u_cnt, list4, v_rows2, reduce_form()): every case asserts
+the exact set it reached before it compares values, so that a dispatch edit that moves a band to another kernel fails the
+case written for the old one instead of quietly testing another kernel.
 """
 import numpy as np
 import pytest
 
 from insider_amd import _lib, api, workloads
+from tests.dispatch_rules import GEMM_WIDE, row_kernels as expected
 from tests.support import need_gpu, relerr  # noqa: F401  (need_gpu: autouse fixture)
 
 pytestmark = pytest.mark.gpu
@@ -33,84 +34,6 @@ def _oracle_chunk(oracle):
     oracle.set_col_chunk(1)
     yield
     oracle.set_col_chunk(100)
-
-
-# ----------------------------------------------------------------------------------------------------------------------
-# the dispatch, by hand
-# ----------------------------------------------------------------------------------------------------------------------
-# Level Gram sums of a covariate with L levels on the k_wgemm route (row_gemm = 1, dense pair counts, c <= 8): tiles =
-# ceil(L / 16) >= 4, split into ceil(tiles / 7) chunks of LT = ceil(tiles / chunks) tiles.  For K <= 31 the cost test
-# tiles * ceil(K (K + 1) / 32) < 0.9 L NB (NB + 1) / 2 holds at every L >= 49.
-GEMM_BANDS = [((1, 48), {"wsyrk"}),
-              ((49, 64), {"wgemm4"}), ((65, 80), {"wgemm5"}), ((81, 96), {"wgemm6"}), ((97, 112), {"wgemm7"}),
-              ((113, 128), {"wgemm4", "wgemm_chunks"}), ((129, 160), {"wgemm5", "wgemm_chunks"}),
-              ((161, 192), {"wgemm6", "wgemm_chunks"}), ((193, 224), {"wgemm7", "wgemm_chunks"}),
-              ((225, 240), {"wgemm5", "wgemm_chunks"}), ((993, 1008), {"wgemm7", "wgemm_chunks"})]
-# K >= 32: the cost test decides (written out: tiles * ntile against 0.9 L NBLK)
-GEMM_WIDE = {(47, 52): {"wsyrk"},     # 4 * 71 = 284 >= 280.8
-             (47, 53): {"wgemm4"},    # 284 < 286.2
-             (47, 65): {"wsyrk"},     # 5 * 71 = 355 >= 351
-             (63, 55): {"wsyrk"},     # 4 * 126 = 504 >= 495
-             (63, 58): {"wgemm4"},    # 504 < 522
-             (63, 65): {"wsyrk"}}     # 630 >= 585
-# the K sweep's many-level covariate: 60 levels pass the test at every K (K = 47: 284 < 324; K = 63: 504 < 540)
-GEMM_WIDE.update({(K, 60): {"wgemm4"} for K in range(32, 64)})
-
-
-def gemm_forms(K, L):
-    if K >= 32 and L >= 49:
-        return GEMM_WIDE[(K, L)]
-    for (lo, hi), forms in GEMM_BANDS:
-        if lo <= L <= hi:
-            return forms
-    raise KeyError((K, L))
-
-
-OPTS = dict(row_merged=1, row_gemm=1, row_counts=1, row_fused=1, list_fine=1, force_allreduce=0, mm_fast=1)
-MM_FAST_MIN = 16384
-
-
-def expected(case, cov):
-    """The forms one optimize_row() of covariate `cov` launches (cov >= c: continuous column cov - c)."""
-    o = {**OPTS, **case["opts"]}
-    K, levels, m, p, tuning = case["K"], case["levels"], case["m"], case["p"], case["tuning"]
-    c, SLcat = len(levels), sum(levels)
-    NB = (K + 16) // 16
-    cont = cov >= c
-    # insider_hip_create_ex: the merged tables exist for m <= 4 and SLcat + 512 <= 2048 (k_gene_u's LDS record); the dense
-    # pair counts for c <= 8, at most 32 table rows (levels of all covariates but the largest) and no cell over 255
-    tables = m <= 4 and SLcat <= 1536
-    pair = tables and c <= 8 and SLcat - max(levels) <= 32 and not case["overflow"]
-    cont_merged = m > 0 and pair and all(SLcat + m + L + L % 2 <= 1536 for L in levels)
-    merged = tables and o["row_merged"] != 0 and (m == 0 or cont_merged)
-    if o["row_merged"] == 1 and m == 0 and tuning == 1:
-        merged = merged and case["cost_merged"]     # use_merged()'s cost model, evaluated by hand for the case
-    solve = {"merged_solve"} if NB <= 2 and not o["force_allreduce"] else {"merged", "level_solve"}
-    s = set()
-    if tuning == 1 and merged:
-        s.add("mm_rows2" if o["mm_fast"] and p >= MM_FAST_MIN else "mm_rows")
-        if cont:
-            return s | {"gene_uc", "mm_reduce", "wsyrk", "merged", "cont_cd"}
-        L = levels[cov]
-        s.add("gene_u_cnt" if pair and (o["row_counts"] or m > 0) and SLcat + m + L + L % 2 <= 1536 else "gene_u")
-        if o["mm_fast"] and p >= MM_FAST_MIN and L > 16:
-            s.add("mm_reduce2_2" if (L + 15) // 16 <= 2 or o["mm_fast"] == 2 or NB > 2 else "mm_reduce2_4")
-        else:
-            s.add("mm_reduce")
-        gram = gemm_forms(K, L) if o["row_gemm"] and pair else {"wsyrk"}
-        if case["no_heldout"]:
-            assert gram == {"wsyrk"}
-            gram = set()
-        s |= gram
-        s |= solve if o["row_fused"] else {"pack_reduce", "level_solve"}
-    elif tuning == 1:
-        s.add("list_stats4" if o["list_fine"] and 16 <= K <= 31 else "list_stats")
-        s |= {"level_partial", "cont_cd" if cont else "level_solve"}
-    elif tables and o["row_merged"] and o["row_fused"] and m == 0:
-        s |= {"merged_zero"} | solve
-    else:
-        s |= {"level_partial", "level_solve"}
-    return s
 
 
 # ----------------------------------------------------------------------------------------------------------------------

@@ -1,6 +1,6 @@
 """The streaming products (k_mm_rows2, k_mm_reduce2: from 16384 genes on) at the size edges only a large extent switches on.
 
-a. Q = S A and Qheld = S^held A (launch_mm_rows_kp, k_mm_rows2<NB, false>) through insider_hip_col_stats(), against the
+a. Q = S A and Qheld = S^held A (launch_q, k_mm_rows2<NB, false>) through insider_hip_col_stats(), against the
    float64 reference and the bounds of test_gpu_col_stats.py: the partial last tile of 16 genes, both sides of MM_FAST_MIN,
    one / two / eight / nine / seventeen chunks of 16 stacked levels (the second trip of the S0 loop starts at the ninth), both
    sides of the LDS fit of the staged factors for every NB (past it: k_mm_rows at streaming size), NB = 3 and 4, and more than
@@ -10,24 +10,21 @@ b. V = C A' (launch_gene_v, k_mm_rows2<NT, true>) and U'C (launch_mm_reduce_kp, 
    reads, more than one column block (grid.y > 1), every length of k_mm_reduce2's last slab, tiles per wave.
 c. One fit with "mm_tiles" = 3: the side-stream launches of optimize() carry the option.
 
-q_kernel() / tiles() / v_nt() / reduce2_form() below are the dispatch written out by hand from mm_rows2_fits(),
-mm_tiles_per_wave(), launch_gene_v() and launch_mm_reduce_kp(); every case asserts insider_hip_get_info("col_q_kernel" /
-"mm_rows2_tiles" / "row_kernels") before it compares values, so a dispatch edit fails the case written for the old kernel.
+q_kernel() / tiles() / v_nt() / reduce2_form() (tests/dispatch_rules.py) are the dispatch written out by hand from the plan's
+rules (mm_rows2_fits(), mm_tiles_per_wave(), reduce_form() in insider_plan.hpp) and launch_gene_v(); every case asserts
+insider_hip_get_info("col_q_kernel" / "mm_rows2_tiles" / "row_kernels") before it compares values, so a dispatch edit fails
+the case written for the old kernel.
 """
-import math
-
 import numpy as np
 import pytest
 
 from insider_amd import api, workloads
 from tests import test_gpu_col_stats as cs
 from tests import test_gpu_row_update as ru
+from tests.dispatch_rules import MM_FAST_MIN, MM_SLAB, nb_of, q_kernel, reduce2_form, tiles, v_nt
 from tests.support import need_gpu, relerr  # noqa: F401  (need_gpu: autouse fixture)
 
 pytestmark = pytest.mark.gpu
-
-MM_FAST_MIN = 16384
-MM_SLAB = 128
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -46,37 +43,6 @@ def n_simd():
         return int(ds.info("n_simd"))
     finally:
         ds.close()
-
-
-# ----------------------------------------------------------------------------------------------------------------------
-# the dispatch, by hand
-# ----------------------------------------------------------------------------------------------------------------------
-def nb_of(K):
-    return (K + 16) // 16
-
-
-def q_kernel(K, SL, p, mm_fast=1):
-    """mm_rows2_fits(): the staged factors, 4 ceil(SL / 16) NB 64 doubles, within 64 KB: ceil(SL / 16) NB <= 32 (SLP is even)."""
-    return 2 if mm_fast and p >= MM_FAST_MIN and math.ceil(SL / 16) * nb_of(K) <= 32 else 1
-
-
-def tiles(p, n_simd, mm_tiles=0):
-    """mm_tiles_per_wave()."""
-    return mm_tiles if mm_tiles >= 1 else max(1, math.ceil(p / 16) // (2 * n_simd))
-
-
-def v_nt(N):
-    """launch_gene_v(): (NT, grid.y) of V = C A' for N stacked levels."""
-    NT = 1 if N <= 16 else 2 if N <= 32 else 4
-    return NT, math.ceil(N / (16 * NT))
-
-
-def reduce2_form(K, L, p, mm_fast=1):
-    """launch_mm_reduce_kp(): (NB, LT) of k_mm_reduce2, or None (k_mm_reduce)."""
-    if not (mm_fast and p >= MM_FAST_MIN and L > 16):
-        return None
-    NB = nb_of(K)
-    return NB, (2 if math.ceil(L / 16) <= 2 or mm_fast == 2 or NB > 2 else 4)
 
 
 # ----------------------------------------------------------------------------------------------------------------------

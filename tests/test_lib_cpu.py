@@ -46,7 +46,7 @@ def test_col_stats_kernel_codes_match_the_library():
     enumeration does, and the header documents the key."""
     names = _lib.COL_STATS_KERNELS
     assert len(set(names)) == len(names) and names[0] == "none"
-    src = open(os.path.join(ROOT, "insider_amd", "csrc", "insider_hip.hip")).read()
+    src = open(os.path.join(ROOT, "insider_amd", "csrc", "insider_plan.hpp")).read()   # (the plan decides the kernel: its header names them)
     enum = re.search(r"enum ColStatsKernel \{(.*?)\};", src, re.S).group(1)
     items = [e.split("=") for e in re.sub(r"//[^\n]*", "", enum).split(",") if e.strip()]
     assert [(k.strip()[4:].lower(), int(v)) for k, v in items] == [(name, i) for i, name in enumerate(names)]
