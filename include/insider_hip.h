@@ -155,6 +155,12 @@ int insider_hip_comm_init(insider_hip_handle *h, const void *unique_id, int rank
  * same sums in another order, results agree to rounding), "col_mfma4" (1, default = the pair-count column statistics [K <= 31, the
  * factor rows of all covariates within 64 KB of LDS] form sum_l a_l p_l' on the 4x4x4 form of the f64 matrix instruction, rows read
  * in four rotations from LDS, resident blocks whose waves draw genes by ticket; 0 = the 16x16x4 form; same sums to rounding),
+ * "stats_own_q" (1, default = that kernel [categorical covariates, one rank, K not 15 or 31, at most four k-steps] forms each
+ * gene's rows of S A and S^held A itself, in two free columns of its second product, in the calls that run a column solve, so
+ * the two products over the genes and their stream joins are not launched; 2 = in insider_hip_col_stats too — with 1 that entry
+ * keeps the products for no other reason than that insider_hip_get_info's facts about the last product over the genes go on
+ * reporting a launch after it, which the suite's cases of the streaming products read; 0 = the products; same sums in another
+ * order),
  * "mm_fast" (1, default = the streaming products of the row phase [V = C A', S A, U'C, S'C: from 16384 rows on] stage their small
  * operand in LDS once per block and read the tall one in 16-byte pieces / several column tiles per wave; 0 = round 4's kernels;
  * same sums, the row products in another order), "mm_tiles" (0, default = a wave of k_mm_rows2 takes one tile of 16 rows until
@@ -759,7 +765,8 @@ int insider_hip_get_profile(insider_hip_handle *h, double *out12);
  * (continuous covariates), 6 / 7 k_col_paircnt4 with MAXS = 4 / 8 k-steps, 8 k_col_paircnt4 with MAXS = 4 and real-valued
  * counts; MAXS = 8 with real-valued counts is never launched), "col_stats_tickets" (the ticket counters k_col_paircnt4 drew
  * genes from: 1 or 16; 0 for the other kernels), "col_stats_blocks" (k_col_paircnt4's grid size, 0 for the other kernels: its
- * blocks walk the genes in groups of four when 4 x blocks < p),
+ * blocks walk the genes in groups of four when 4 x blocks < p), "col_stats_own_q" (1: that launch formed the genes' rows of S A
+ * and S^held A itself, option "stats_own_q", and no product over the genes ran for it; 0: it read the products),
  * "col_q_kernel" (the kernel the last Q = S A or S^held A product ran: 0 = none yet, 1 k_mm_rows<NB>, 2 k_mm_rows2<NB>),
  * "mm_rows2_tiles" (the tiles of 16 rows per wave of the last k_mm_rows2 launch, for S A or for V = C A'; 0 = none yet),
  * "n_simd" (SIMDs of the handle's device, 4 per compute unit),

@@ -58,6 +58,13 @@ struct ColFacArgs {
     int zt_stride, zt_off[CF_MAXC + 1];         // doubles per gene, offset of position t
     int m, SLcat;                               // continuous columns; their factor rows are Astack[SLcat .. SLcat + m)
     int pos_cov[CF_MAXC];                       // covariate (column of the level table) at position t
+    // k_col_paircnt4<.., OWNQ = true>: the kernel forms each gene's rows of Q = S A (-> Qfull_out, p x KP) and Qheld = S^held A
+    // itself (no product over the genes beforehand, Qheld is not read).  sq: the level sums S and S^held of every gene in the
+    // order the kernel's lanes want them, CF_SQ_BLOCK doubles per gene and block of 16 levels (the blocks of ColFacArgs::hn):
+    // [S | S^held][l % 4][(l % 16) / 4], zero beyond the last level, then four zeros; static per data set (k_own_q_table)
+    const double *sq;
+    int sq_stride;                              // doubles per gene
+    double *Qfull_out;
 };
 
 // Gc = M + M' for the lower blocks, XtX_j = R'R - Gc; qc and the sum of squares go into row KP - 1 of the record
@@ -359,10 +366,21 @@ __global__ void __launch_bounds__(WPB * 64) k_col_paircnt(ColFacArgs a)
 //    the port the f64 matrix instructions hold.)
 // acc[bi][bj][x] of lane (g4, b, j) = M[16 bi + 4 ((b + x) & 3) + g4][16 bj + 4 b + j].
 // LDS: per wave two 16 x 17 tiles | R'R | table rows | factor rows [position][level / 4][bi][level % 4][16]
-template <int NB, int WPB, int MAXS, bool ZC = false>
+//
+// OWNQ (K <= KP - 2): the gene's rows of Q = S A (ColFacArgs::Qfull_out) and Qheld = S^held A (the record's row KP - 1) come out
+// of the matrix instructions the kernel issues anyway.  Columns KP - 2 and KP - 1 of P are free (the factor rows are zero
+// beyond K): a block of 16 levels starts its P with the level sums S[j][l] in column KP - 2 and S^held[j][l] in column KP - 1,
+// so the second product M += a_l p_l' leaves sum_l a_l S[j][l] in column KP - 2 of M and sum_l a_l S^held[j][l] in column
+// KP - 1, and the epilogue's M + M' carries them in rows KP - 2 and KP - 1 (the other halves are products with the zero
+// components of a_l).  No instruction more in the loop but two 16-byte loads per block of 16 levels (ColFacArgs::sq: lanes of
+// the other columns read its four zeros), a fixed summation order (the quads of levels in order), and no product over the
+// genes in front of the statistics: the kernel depends on the factors and R'R alone.  It rests on columns KP - 2 and KP - 1 of
+// Astack (the staged factor rows and table rows) and of the LDS copy of R'R being exactly zero, which K <= KP - 2 gives.
+template <int NB, int WPB, int MAXS, bool ZC = false, bool OWNQ = false>
 __global__ void __launch_bounds__(WPB * 64) k_col_paircnt4(ColFacArgs a, unsigned *__restrict__ ticket, unsigned ticket_base, int npart, int cap)
 {
     static_assert(NB <= 2, "accumulators of the 4x4x4 form");
+    static_assert(!(ZC && OWNQ), "continuous covariates keep the products over the genes");
     constexpr int KP = Geo<NB>::KP;
     extern __shared__ double s_c4[];
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -410,7 +428,10 @@ __global__ void __launch_bounds__(WPB * 64) k_col_paircnt4(ColFacArgs a, unsigne
         uint32_t cw[2];
         float4 hn;
         double z;
+        double2 sq[2];   // OWNQ: the level sums of levels l0 + 4 s + g4, s = 0 .. 3 (S in the lanes of column KP - 2, S^held in those of KP - 1, else 0)
     };
+    // OWNQ: this lane's place in a block's record of level sums
+    const unsigned off_q = c16 == 14 ? g4 * 4u : c16 == 15 ? 16u + g4 * 4u : 32u;
     // A block keeps its staged rows for every gene its waves take (grid = the blocks that can be resident: the staging is paid
     // once).  Genes are dealt by TICKET: a static split would hand a block that starts late (another kernel holding its CU —
     // Qfull's product, a second fit on the same device) a full share to work off alone (measured: 0.28 -> 0.40 ms with a 20 us
@@ -433,7 +454,7 @@ __global__ void __launch_bounds__(WPB * 64) k_col_paircnt4(ColFacArgs a, unsigne
     if (j >= a.p) continue;
     double qh[NB];
 #pragma unroll
-    for (int bb = 0; bb < NB; ++bb) qh[bb] = a.Qheld[(size_t)j * KP + 16 * bb + c16];
+    for (int bb = 0; bb < NB; ++bb) qh[bb] = OWNQ ? 0.0 : a.Qheld[(size_t)j * KP + 16 * bb + c16];
     const double ss = a.yy_all[j] - a.yy_train[j];
     double acc[NB][NB][4];
 #pragma unroll
@@ -445,6 +466,7 @@ __global__ void __launch_bounds__(WPB * 64) k_col_paircnt4(ColFacArgs a, unsigne
     const uint8_t *cj = a.cnt + (size_t)j * a.cnt_stride;
     const float *hj = a.hn + (size_t)j * a.hn_stride;
     const double *zj = ZC ? a.zt + (size_t)j * a.zt_stride : nullptr;
+    const double *qj = OWNQ ? a.sq + (size_t)j * a.sq_stride + off_q : nullptr;
     int pb4 = 0;
     for (int t = 0; t < npos; ++t) {
         const int Lo = a.L[t];
@@ -452,6 +474,7 @@ __global__ void __launch_bounds__(WPB * 64) k_col_paircnt4(ColFacArgs a, unsigne
         const uint8_t *ct = cj + a.cnt_off[t];
         const float *ht = hj + a.hn_off[t];
         const double *zt = ZC ? zj + a.zt_off[t] : nullptr;
+        const double *qt = OWNQ ? qj + (size_t)(a.hn_off[t] >> 4) * CF_SQ_BLOCK : nullptr;
         auto fetch = [&](int l0, Blk &b) {
             if constexpr (ZC) b.z = zt[(size_t)(l0 >> 4) * 64 + lane];
             b.cw[0] = b.cw[1] = 0;
@@ -461,6 +484,11 @@ __global__ void __launch_bounds__(WPB * 64) k_col_paircnt4(ColFacArgs a, unsigne
                 if (bpl == 8) b.cw[1] = src[1];
             }
             b.hn = *reinterpret_cast<const float4 *>(ht + l0 + off_h);
+            if constexpr (OWNQ) {
+                const double2 *src = reinterpret_cast<const double2 *>(qt + (size_t)(l0 >> 4) * CF_SQ_BLOCK);
+                b.sq[0] = src[0];
+                b.sq[1] = src[1];
+            }
         };
         // the four rotations of the factor rows of quad s (0 .. 4: 4 = the next block's first) of the block of 16 levels at rp:
         // constant offsets from four addresses that move once per block
@@ -490,6 +518,7 @@ __global__ void __launch_bounds__(WPB * 64) k_col_paircnt4(ColFacArgs a, unsigne
             d4 P[NB];
 #pragma unroll
             for (int bb = 0; bb < NB; ++bb) P[bb] = d4{0.0, 0.0, 0.0, 0.0};
+            if constexpr (OWNQ) P[NB - 1] = d4{cur.sq[0].x, cur.sq[0].y, cur.sq[1].x, cur.sq[1].y};
             if (cross) {
 #pragma unroll
                 for (int s = 0; s < MAXS; ++s)
@@ -563,15 +592,43 @@ __global__ void __launch_bounds__(WPB * 64) k_col_paircnt4(ColFacArgs a, unsigne
                     res[r] = rtr[ra * KP + cb] - (res[r] + tr[c16 * 17 + g4 + 4 * r]);
                 }
                 wave_sync();
-                if (bi == NB - 1 && g4 == 3) {
+                if constexpr (OWNQ) {
+                    // columns KP - 2 and KP - 1 of the last diagonal block carry -Q[row] and -Qheld[row] (the transposed halves): the
+                    // record is zero outside its K x K part but for row KP - 1, as the other kernels leave it
+                    if (bi == NB - 1 && bj == NB - 1 && c16 >= 14) res = d4{0.0, 0.0, 0.0, 0.0};
+                }
+                if (bi == NB - 1 && g4 == 3) {   // (OWNQ: res[3] = 0 - (0 + Qheld[col]))
                     const int col = 16 * bj + c16;
-                    res[3] = col < a.K ? qh[bj] : (col == KP - 1 ? ss : 0.0);
+                    res[3] = col < a.K ? (OWNQ ? -res[3] : qh[bj]) : (col == KP - 1 ? ss : 0.0);
+                }
+                if constexpr (OWNQ) {
+                    if (bi == NB - 1 && g4 == 2) {   // row KP - 2 = register 3 of lanes 32..47: 0 - (0 + Q[col]); the record keeps its zero there
+                        const int col = 16 * bj + c16;
+                        a.Qfull_out[(size_t)j * KP + col] = col < a.K ? -res[3] : 0.0;
+                        res[3] = 0.0;
+                    }
                 }
 #pragma unroll
                 for (int r = 0; r < 4; ++r) out[blk * 256 + (g4 + 4 * r) * 16 + c16] = res[r];
             }
     }
     }
+}
+
+// The level sums in k_col_paircnt4's order (ColFacArgs::sq); once per data set.  One thread per double of the table.
+__global__ void __launch_bounds__(256) k_own_q_table(ColFacArgs a, const double *__restrict__ S, const double *__restrict__ Sheld,
+                                                     int SLP, double *__restrict__ out)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)a.p * a.sq_stride) return;
+    const int j = (int)(i / a.sq_stride), r = (int)(i % a.sq_stride);
+    const int blk = r / CF_SQ_BLOCK, x = r % CF_SQ_BLOCK;
+    int t = 0;
+    while (t + 1 < a.c && 16 * blk >= a.hn_off[t + 1]) ++t;
+    const int l = 16 * blk - a.hn_off[t] + 4 * (x & 3) + ((x >> 2) & 3);
+    double v = 0.0;
+    if (x < 32 && l < a.L[t]) v = (x < 16 ? S : Sheld)[(size_t)j * SLP + a.off[t] + l];
+    out[i] = v;
 }
 
 // The real-valued count table of the continuous covariates (ColFacArgs::zt) and the held-out sums sum_{i in H(j)} x_ij z_ik,

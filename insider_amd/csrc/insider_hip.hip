@@ -266,6 +266,7 @@ struct DataSet {
     bool cf_pair_ok = false;
     DevBuf<uint8_t> cf_cnt;           // dense pair counts of every gene (pair-count form)
     DevBuf<float> cf_hn;              // 1/2 held-out count per (gene, level) in the pair-count kernel's order (ColFacArgs::hn)
+    DevBuf<double> cf_sq;             // S and S^held per (gene, level) in k_col_paircnt4's order (ColFacArgs::sq; categorical covariates only)
     DevBuf<double> cf_zt;             // real-valued counts of the continuous covariates in the same order (ColFacArgs::zt), m <= 4
     // merged row update with continuous covariates (m <= 4, real-valued counts ColFacArgs::zt): column k is a ONE-level
     // covariate whose membership weights are z_rk — its (gene, weight) list carries sum_{r in H(j)} z_rk^2, its pair "counts"
@@ -413,6 +414,7 @@ struct Options {
     int mm_fast = 1;                  // "mm_fast": the small dense products on k_mm_rows2 / k_mm_reduce2 (default; 2: two column tiles per wave in the reductions)
     int mm_tiles = 0;                 // "mm_tiles": tiles of 16 rows a wave of k_mm_rows2 takes (0, default = mm_tiles_per_wave()'s rule, insider_plan.hpp)
     int col_mfma4 = 1;                // "col_mfma4": pair-count statistics with the second product on v_mfma_f64_4x4x4 (k_col_paircnt4; default)
+    int stats_own_q = 1;              // "stats_own_q": k_col_paircnt4 forms Q = S A and Qheld = S^held A itself (stats_own_q, insider_plan.hpp): 1 (default) where a column solve follows, 2 in insider_hip_col_stats too, 0 = the two products over the genes
     int cd_pairs = 1;                 // "cd_pairs": route the sweeps through the kernel's blocks of two coordinate steps (default)
     int list_fine = 1;                // "list_fine": 1 (default) = k_list_stats4 (4x4x4 matrix instruction) where it applies, 0 = k_list_stats
     int cd_cold_iters = 3, cd_pass_first = 64, cd_pass_ratio = 4;   // "cd_cold_iters", "cd_pass1" (0 = single pass), "cd_pass_ratio"
@@ -489,6 +491,7 @@ struct insider_hip_handle {
     // of the last column-side statistics launch (launch_col_stats): the kernel that formed them (ColStatsKernel), and for
     // k_col_paircnt4 the ticket counters it drew from and its grid size (0 for the other kernels)
     int col_stats_kernel = 0, col_stats_tickets = 0, col_stats_blocks = 0;
+    int col_stats_own_q = 0;          // ... and whether it formed Q = S A and Qheld = S^held A itself (FitPlan::stats_own_q)
     // of the last Q = S A / Qheld = S^held A product (launch_q): 1 = k_mm_rows, 2 = k_mm_rows2; and tiles_per_wave of the
     // last k_mm_rows2 launch from either site (launch_q, launch_gene_v)
     int col_q_kernel = 0, mm_rows2_tiles = 0;
@@ -546,10 +549,11 @@ PlanFacts plan_facts(const insider_hip_handle *h, int K)
     PlanFacts f;
     const Options &o = h->opt;
     f.opt = {o.row_merged, o.col_factored, o.row_fused, o.row_gemm, o.row_counts, o.mm_fast, o.force_allreduce, o.wg_waves,
-             o.list_fine, o.mm_tiles, o.col_mfma4, o.cd_variant, o.cd_pairs, o.cd_cold_iters, o.cd_pass_first, o.cd_pass_ratio, o.max_sweeps};
+             o.list_fine, o.mm_tiles, o.col_mfma4, o.cd_variant, o.cd_pairs, o.cd_cold_iters, o.cd_pass_first, o.cd_pass_ratio, o.max_sweeps,
+             o.stats_own_q};
     f.world = h->world; f.n_simd = d.n_simd;
     f.K = K; f.NB = h->ws.NB; f.KP = h->ws.KP; f.lvl_zero = (bool)h->ws.lvl_zero; f.fperm = (bool)h->ws.fperm;
-    f.merged = d.merged; f.cont_merged = d.cont_merged; f.cf_pair_ok = d.cf_pair_ok; f.cf_hn = (bool)d.cf_hn; f.cf_zt = (bool)d.cf_zt;
+    f.merged = d.merged; f.cont_merged = d.cont_merged; f.cf_pair_ok = d.cf_pair_ok; f.cf_hn = (bool)d.cf_hn; f.cf_zt = (bool)d.cf_zt; f.cf_sq = (bool)d.cf_sq;
     f.c = d.c; f.m = d.m; f.SL = d.SL; f.SLP = d.SLP; f.SLcat = d.SLcat; f.n = d.n; f.p = d.p; f.col_entries = d.col_entries; f.row_entries = d.row_entries;
     for (const CovTables &ct : d.cov) { f.L.push_back(ct.L); f.npairs.push_back(ct.npairs); }
     f.cf_c = d.cf.c; f.cf_tab_rows = d.cf.tab_rows; f.cf_nsteps = d.cf.nsteps;
@@ -834,7 +838,10 @@ int launch_build_R(insider_hip_handle *h)
 // r_is_current: the row updates have just rebuilt R (every row_update() ends with k_build_R): do not build it again
 int phase_R(insider_hip_handle *h, bool use_side = false, bool r_is_current = false, bool want_qheld = false)
 {
-    if (use_side) {
+    // the statistics kernel forms Q and Qheld itself (FitPlan::stats_own_q; every masked call launches it behind this): no
+    // product over the genes, no side stream, no join
+    const bool own_q = h->plan.stats_own_q;
+    if (use_side && !own_q) {
         HIPCHECK(hipEventRecord(h->st.ev_a_ready, h->st.stream));
         // Qheld = S^held A, which the factored column statistics read: on the third stream (idle since the row phase's C'C),
         // beside R'R on the main one instead of behind it, and beside Qfull on the side stream (Qfull behind Qheld: DESIGN §4.5)
@@ -852,7 +859,7 @@ int phase_R(insider_hip_handle *h, bool use_side = false, bool r_is_current = fa
     if (rc) return rc;
     rc = launch_gram(h, h->ws.R, h->ds->n, h->ws.RtR);
     if (rc) return rc;
-    if (use_side) return INSIDER_OK;
+    if (use_side || own_q) return INSIDER_OK;
     return launch_q(h, h->ds->S, h->ws.Qfull);
 }
 
@@ -1048,7 +1055,8 @@ int launch_paircnt(insider_hip_handle *h, const ColFacArgs &a)
             const unsigned tbase = h->ws.pc4_base[which];
 #define PC4(NBV, MS)                                                                                                         \
     {                                                                                                                        \
-        if (a.zt) hipLaunchKernelGGL((k_col_paircnt4<NBV, 4, MS, true>), dim3(nb), dim3(256), lds, h->st.stream, a, tk, tbase, npart, cap); \
+        if (plan.stats_own_q) hipLaunchKernelGGL((k_col_paircnt4<NBV, 4, 4, false, true>), dim3(nb), dim3(256), lds, h->st.stream, a, tk, tbase, npart, cap); /* (MS = 4 only: stats_own_q) */ \
+        else if (a.zt) hipLaunchKernelGGL((k_col_paircnt4<NBV, 4, MS, true>), dim3(nb), dim3(256), lds, h->st.stream, a, tk, tbase, npart, cap); \
         else hipLaunchKernelGGL((k_col_paircnt4<NBV, 4, MS, false>), dim3(nb), dim3(256), lds, h->st.stream, a, tk, tbase, npart, cap); \
     }
             const bool ms4 = plan.pc_kernel != CSK_PAIRCNT4_MS8;
@@ -1085,8 +1093,10 @@ int launch_col_stats(insider_hip_handle *h, bool timed)
 {
     Timer t;
     int rc;
-    const bool factored = h->plan.col_path != 0;
-    if (factored && h->st.qheld.pending) {   // Qheld = S^held A formed on side3 since the row factors were final (phase_R):
+    const bool factored = h->plan.col_path != 0, own_q = h->plan.stats_own_q;
+    if (own_q) {
+        if ((rc = t.begin(h, timed))) return rc;
+    } else if (factored && h->st.qheld.pending) {   // Qheld = S^held A formed on side3 since the row factors were final (phase_R):
         if ((rc = h->st.qheld.wait(h->st.stream))) return rc;   // joined BEFORE the timer, which then holds the statistics kernel alone
         if ((rc = t.begin(h, timed))) return rc;
     } else {
@@ -1099,6 +1109,8 @@ int launch_col_stats(insider_hip_handle *h, bool timed)
         a.K = h->ws.K;
         a.Astack = h->ws.Astack;
         a.Qheld = h->ws.Qheld;
+        a.sq = own_q ? (const double *)h->ds->cf_sq : nullptr;
+        a.Qfull_out = own_q ? (double *)h->ws.Qfull : nullptr;
         a.RtR = h->ws.RtR;
         a.yy_all = h->ds->yy_all;
         a.yy_train = h->ds->yy_train;
@@ -1126,6 +1138,7 @@ int launch_col_stats(insider_hip_handle *h, bool timed)
         h->col_stats_kernel = (mark & rk_bit(RK_LIST_STATS4)) ? CSK_LIST4 : CSK_LIST;
         h->col_stats_tickets = h->col_stats_blocks = 0;
     }
+    h->col_stats_own_q = own_q ? 1 : 0;
     return t.end(h, h->ev_col);
 }
 
@@ -2242,6 +2255,15 @@ int stage_factored(DataSet &d, hipStream_t st)
             HIPCHECK(hipMemsetAsync(d.cf_hn, 0, (size_t)(p + 4) * hoff * sizeof(float), st));
             hipLaunchKernelGGL(k_half_counts, dim3((unsigned)cdiv((int64_t)p * hoff, 256)), dim3(256), 0, st, cf, d.cf_hn);
             KCHECK();
+            // the level sums in k_col_paircnt4's order, for the launches that form Q themselves (stats_own_q, insider_plan.hpp)
+            cf.sq_stride = hoff / 16 * CF_SQ_BLOCK;
+            if (d.m == 0 && (int64_t)p * cf.sq_stride / 256 < ((int64_t)1 << 31)) {
+                // (no room for the table: the data set stands without it and stats_own_q() keeps the products)
+                if (d.cf_sq.alloc((size_t)p * cf.sq_stride)) { (void)hipGetLastError(); d.cf_sq.reset(); }
+                else hipLaunchKernelGGL(k_own_q_table, dim3((unsigned)cdiv((int64_t)p * cf.sq_stride, 256)), dim3(256), 0, st, cf,
+                                   (const double *)d.S, (const double *)d.Sheld, (int)d.SLP, (double *)d.cf_sq);
+                KCHECK();
+            }
         } else {
             fits = false;
         }
@@ -2567,6 +2589,7 @@ int insider_hip_set_option(insider_hip_handle *h, const char *name, double value
     else if (s == "list_fine") h->opt.list_fine = (int)value;       // 1 (default) = per-entry statistics on v_mfma_f64_4x4x4 for 16 <= K <= 31, 0 = on 16x16x4
     else if (s == "mm_fast") h->opt.mm_fast = (int)value;             // 0 = k_mm_rows / k_mm_reduce as in round 4
     else if (s == "mm_tiles") h->opt.mm_tiles = value < 1 ? 0 : (int)value;   // tiles of 16 rows per wave of k_mm_rows2 (0, default = as many as keep the grid at two waves per SIMD)
+    else if (s == "stats_own_q") h->opt.stats_own_q = (int)value;     // 1 = k_col_paircnt4 forms Q and Qheld itself where a column solve follows, 2 = in insider_hip_col_stats too, 0 = never
     else if (s == "col_mfma4") h->opt.col_mfma4 = (int)value;         // 1 = k_col_paircnt4 (K <= 31, factor rows fit LDS), 0 = k_col_paircnt
     else if (s == "cd_pairs") h->opt.cd_pairs = (int)value;           // 1 (default) = sweeps routed through the blocks of two coordinate steps (K <= 30; same iterates), 0 = one step per block
     else if (s == "resid_stage_mb") h->opt.resid_stage_mb = value;   // device buffer insider_hip_residual() copies out through (MB; at least 16 genes of the window)
@@ -3915,6 +3938,7 @@ int insider_hip_get_info(insider_hip_handle *h, const char *name, double *out)
     else if (s == "col_stats_kernel") *out = h->col_stats_kernel;   // last column-side statistics: the kernel (ColStatsKernel) ...
     else if (s == "col_stats_tickets") *out = h->col_stats_tickets; // ... k_col_paircnt4's ticket counters (1 or 16; 0: another kernel)
     else if (s == "col_stats_blocks") *out = h->col_stats_blocks;   // ... and its grid size (0: another kernel)
+    else if (s == "col_stats_own_q") *out = h->col_stats_own_q;     // ... and whether it formed Q = S A and Qheld = S^held A itself (option "stats_own_q")
     else if (s == "col_q_kernel") *out = h->col_q_kernel;           // last Q = S A product: 0 = none yet, 1 = k_mm_rows, 2 = k_mm_rows2
     else if (s == "mm_rows2_tiles") *out = h->mm_rows2_tiles;       // tiles per wave of the last k_mm_rows2 launch (Q or V), 0 = none yet
     else if (s == "n_simd") *out = h->ds->n_simd;

@@ -49,12 +49,13 @@ struct PlanFacts {
     struct {                          // the options that decide a path (Options, by name)
         int row_merged, col_factored, row_fused, row_gemm, row_counts, mm_fast, force_allreduce, wg_waves;
         int list_fine, mm_tiles, col_mfma4, cd_variant, cd_pairs, cd_cold_iters, cd_pass_first, cd_pass_ratio, max_sweeps;
+        int stats_own_q;
     } opt{};
     int world = 1, n_simd = 1024;
     int K = 0, NB = 0, KP = 0;        // NB = KP = 0: no workspace yet (insider_hip_get_info before the first call)
     bool lvl_zero = false;            // the workspace holds its all-zero level records
     bool fperm = false;               // ... and the buffer of k_tile_perm's row order (k_list_stats4)
-    bool merged = false, cont_merged = false, cf_pair_ok = false, cf_hn = false, cf_zt = false;
+    bool merged = false, cont_merged = false, cf_pair_ok = false, cf_hn = false, cf_zt = false, cf_sq = false;
     int c = 0, m = 0, SL = 0, SLP = 0, SLcat = 0;
     int64_t n = 0, p = 0;
     uint64_t col_entries = 0, row_entries = 0;
@@ -92,6 +93,9 @@ struct FitPlan {
     ColStatsKernel pc_kernel = CSK_NONE;
     size_t pc_lds = 0;
     int pc_blocks = 0, pc_parts = 0;
+    // ... and whether k_col_paircnt4 forms Q = S A and Qheld = S^held A of its genes itself (stats_own_q): the two products over
+    // the genes and their stream joins are then not launched
+    bool stats_own_q = false;
     // the column solve (CS_NONE: the call runs none), the kernel of the evaluation pass behind a register-resident solve
     // (CS_NONE: the solve kernel evaluates), and whether a ridge solve is followed by the general route for the genes it marked
     ColSolver col_solver = CS_NONE, col_eval = CS_NONE;
@@ -161,6 +165,18 @@ inline void paircnt_plan(const PlanFacts &f, FitPlan &p)
     }
     p.pc_lds = ((size_t)4 * 16 * 17 + (size_t)KP * KP + (size_t)4 * nsteps * KP) * sizeof(double);
     p.pc_kernel = zt ? CSK_PAIRCNT_ZT : CSK_PAIRCNT;
+}
+
+// k_col_paircnt4 forms each gene's rows of Q = S A and Qheld = S^held A itself, in two free columns of its second product (option
+// "stats_own_q"; insider_col_factored.hpp)?  Needs K <= KP - 2, the level sums in the kernel's order (categorical covariates
+// only) and one rank (a shard keeps the products).  Option 1: calls that run a column solve (the fit, the column update); 2: the
+// densifying entry insider_hip_col_stats too.
+inline bool stats_own_q(const PlanFacts &f, const FitPlan &p, bool col_call)
+{
+    if (!(f.opt.stats_own_q >= 2 || (f.opt.stats_own_q == 1 && col_call))) return false;
+    // (k_col_paircnt4 with eight k-steps would go past 168 registers and lose its third wave per SIMD: it keeps the products)
+    if (!(p.masked && p.col_path == 2 && p.pc_kernel == CSK_PAIRCNT4_MS4)) return false;
+    return f.cf_sq && f.m == 0 && !f.cf_zt && f.world <= 1 && f.K <= f.KP - 2;
 }
 
 // 32 < K <= 48 with an l1 term: the register-resident kernel with its third slot's matrix columns in LDS (insider_cd_reg.hpp)
@@ -305,6 +321,7 @@ FitPlan build_plan(const PlanFacts &f, int masked, const ColCall *col = nullptr)
     p.mm_tpw = mm_tiles_per_wave(f, cdiv(f.p, 16));
     p.col_path = col_stats_path(f);
     if (p.col_path == 2) paircnt_plan(f, p);
+    p.stats_own_q = stats_own_q(f, p, col != nullptr);
     if (col) col_solve_plan(f, *col, p);
     p.order_pairs = f.opt.cd_pairs && reg_pairs(reg_kmax(f.K));
     p.NB = f.NB;

@@ -19,6 +19,7 @@ constexpr int CF_MAXC = 8;        // covariates
 constexpr int CF_CAP = 2048;      // uint16 look-up indices staged per wave (entries x later covariates)
 constexpr int GU_BATCH = 8;       // blocks of 16 levels whose partial sums share one trip through LDS (k_gene_u_cnt)
 constexpr int PC4_PARTS = 16;     // ticket counters of k_col_paircnt4
+constexpr int CF_SQ_BLOCK = 36;     // doubles per gene and block of 16 levels of the level sums in k_col_paircnt4's order (ColFacArgs::sq): 16 of S, 16 of S^held, 4 zeros
 
 // the small dense products (insider_mm.hpp)
 constexpr int MM_SLAB = 128;          // rows per partial of the reduction products
