@@ -519,8 +519,9 @@ int insider_hip_residual_products(insider_hip_handle *h, double *const *A, const
  * its own row all open slots.
  * Score.  The plain sum over the whole depth of the products of the standardised values; an entry missing in either vector
  * contributes 0.  With a full selection this is Pearson's r.  With missing entries it is the ZERO-FILLED correlation: |score|
- * <= 1 and it shrinks with missingness.  It is NOT the pairwise-complete correlation (which would need six products where this
- * needs one).  Scores are not clipped: a correlation may exceed 1 by rounding.
+ * <= 1 and it shrinks with missingness.  It is NOT the pairwise-complete correlation: that is
+ * insider_hip_coexpression_pairwise() below (six products where this needs one).  Scores are not clipped: a correlation may
+ * exceed 1 by rounding.
  *   idx_out / score_out  N x k, vector-major: row i lists the partners of vector i (never i itself) in descending score, equal
  *   scores (-0.0 == 0.0) by ascending index; a row with fewer than k eligible partners ends in -1 / NaN: the rules of
  *   insider_hip_neighbors().  1 <= k <= 64.
@@ -540,6 +541,26 @@ int insider_hip_residual_products(insider_hip_handle *h, double *const *A, const
 int insider_hip_coexpression(insider_hip_handle *h, double *const *A, const double *C, int inc_continuous, int K,
                              int entries, const double *center, const double *scale, int axis, int k, int32_t *idx_out,
                              double *score_out);
+
+/*
+ * Pairwise-complete residual co-expression: insider_hip_coexpression() with Pearson's r of every pair taken over the entries
+ * selected in BOTH vectors (insider_amd/csrc/insider_coexpr_pc.hpp).  The residual, entries, center, scale, axis, the
+ * standardisation of a vector over its own selected entries and the rule for a DEAD vector are those of
+ * insider_hip_coexpression(); the definition of the score, the eligibility of a pair (min_overlap >= 3, the variance floor),
+ * the order and the open slots are those of insider_hip_gram_topk_pairwise() below, the depth being n (axis 0) or p (axis 1).
+ *   idx_out / score_out / overlap_out  N x k, vector-major; overlap_out holds the pair's N = the number of jointly selected
+ *   entries, -1 in an open slot.
+ * Status codes: those of insider_hip_coexpression(), and INSIDER_ERR_ARG for min_overlap < 3 or a NULL overlap_out; a sharded
+ * handle returns INSIDER_ERR_UNSUPPORTED.  Nothing is written to the caller's arrays unless the status is INSIDER_OK.  Works on
+ * clones and re-masked handles, on the handle's main stream: an optimize() after it is bit-identical to one without.  The
+ * staged buffer is that of insider_hip_coexpression(), an unselected entry and the padding held as NaN.
+ * insider_hip_get_info: "cx_stage_mb" and "cx_stage_ms" as for insider_hip_coexpression() (the staging kernels here are
+ * k_cx_stage and k_cx_std_pc), "cx_pc_ms" the HIP-event time of the product kernel k_cx_topk_pc in milliseconds.
+ */
+int insider_hip_coexpression_pairwise(insider_hip_handle *h, double *const *A, const double *C, int inc_continuous, int K,
+                                      int entries, const double *center, const double *scale, int axis,
+                                      int64_t min_overlap, int k,
+                                      int32_t *idx_out, double *score_out, int32_t *overlap_out);
 
 /*
  * Aberrant entries of a fitted model on the resident data set: the (sample, gene) entries whose standardised residual the
@@ -614,6 +635,34 @@ double insider_hip_last_neighbors_ms(void);
 int insider_hip_gram_topk(const double *V, int64_t depth, int64_t N, int metric, int k, int64_t first, int64_t count,
                           int device, int32_t *idx_out, double *score_out);
 double insider_hip_last_gram_topk_ms(void);
+
+/* Pairwise-complete top-k partners among N deep vectors with missing entries (insider_amd/csrc/insider_coexpr_pc.hpp).
+ * Handle-free, one device.  V, depth, N, k, the window and the outputs' layout as in insider_hip_gram_topk(); a NaN in V is a
+ * MISSING entry (+-inf is refused).
+ *   Definition.  A pair of vectors a, b has values v and selection indicators m in {0, 1} (m = 0 where missing).  With J = the
+ *   positions selected in both:  N = |J|,  Sa = sum_J a,  Sb = sum_J b,  Saa = sum_J a^2,  Sbb = sum_J b^2,  Sab = sum_J a b,
+ *       cov = Sab - Sa Sb / N,   va = Saa - Sa^2 / N,   vb = Sbb - Sb^2 / N,   score = cov / sqrt(va vb):
+ *   Pearson's r over the jointly selected positions, not clipped.
+ *   Staged values.  The sums are taken over the staged values: each vector is first standardised over its own selected entries
+ *   exactly as under metric 0 of insider_hip_gram_topk() (centred by the mean of its selected entries, divided by the root of
+ *   their centred sum of squares, sums in index order).  The score is invariant under that affine map, and the map keeps the
+ *   cancellation in va and vb mild.  A vector with fewer than two selected entries or no variance is DEAD, as there.
+ *   Eligibility.  A pair is eligible when both vectors are alive, a != b, N >= min_overlap, va > floor Saa and vb > floor Sbb
+ *   with floor = 16 (depth + 8) 2^-52.  The floor comes from the first-order rounding error of va computed this way, at most
+ *   (3 depth + 3) 2^-53 Saa: a vector that is exactly constant on J always lands under it, any other vector with Saa / va
+ *   below about 10^12 above it.  N is a sum of 0 / 1 products and is exact.
+ *   Order: descending score, equal scores (-0.0 == 0.0) by ascending index, never the vector itself; a row with fewer than k
+ *   eligible partners ends in -1 / NaN / -1.  overlap_out (count x k) holds the pair's N.
+ *   Bits.  Each of the six sums is one accumulator chain over the depth in ascending order and the final formula is symmetric
+ *   in a and b: score(a, b) and score(b, a) have the same bits, a window returns exactly the rows of the full call, repeated
+ *   calls return identical bits; no floating-point atomics.
+ *   INSIDER_ERR_ARG, nothing written: a NULL pointer, depth < 1 or > INT32_MAX, N < 1 or N > INT32_MAX, min_overlap < 3 (with
+ *   N = 2 every pair scores +-1), k outside 1..64, first < 0, count < 0 or first + count > N, an infinite value in V.
+ *   min_overlap above the depth is allowed and leaves every row open.  count = 0 returns INSIDER_OK and writes nothing; a
+ *   failed device allocation returns INSIDER_ERR_ALLOC and writes nothing.  insider_hip_last_gram_topk_ms covers this call too. */
+int insider_hip_gram_topk_pairwise(const double *V, int64_t depth, int64_t N, int64_t min_overlap, int k,
+                                   int64_t first, int64_t count, int device,
+                                   int32_t *idx_out, double *score_out, int32_t *overlap_out);
 
 /* Preranked gene-set enrichment with a permutation null (insider_amd/csrc/insider_enrich.hpp).  Handle-free, one device.
  *   Inputs.  scores is R x p, row-major: profile r is p contiguous doubles.  set_ptr (int64, S + 1) and set_genes (int32) hold S
@@ -784,7 +833,10 @@ int insider_hip_get_profile(insider_hip_handle *h, double *out12);
  * "rc_slabs" / "rc_ms" (of the last insider_hip_residual_products(): the gene slabs the grid of k_rc_fwd had, 0 = no forward
  * pass or none yet; and the HIP-event time in milliseconds of k_rc_back, k_rc_fwd and k_rc_reduce),
  * "cx_stage_mb" / "cx_stage_ms" / "cx_ms" (of the last insider_hip_coexpression(): the megabytes of the staged standardised
- * residual, the HIP-event time in milliseconds of k_cx_stage and k_cx_norm, and that of k_cx_topk; 0 = none yet),
+ * residual, the HIP-event time in milliseconds of k_cx_stage and k_cx_norm, and that of k_cx_topk; 0 = none yet; a call of
+ * insider_hip_coexpression_pairwise() fills the first two alike and leaves "cx_ms"),
+ * "cx_pc_ms" (of the last insider_hip_coexpression_pairwise(): the HIP-event time in milliseconds of k_cx_topk_pc; 0 = none
+ * yet),
  * "ls_form" / "fd_form" / "rc_form" / "cx_form" (the template instantiation of the heavy launch of the last
  * insider_hip_level_scores(), _factor_decomposition(), _residual_products() and _coexpression(), set on the host at the launch
  * site; 0 = none yet.  The first three are 10 QT + KS, KS = ceil(K / 16) blocks of 16 latent dimensions and QT tiles of 16

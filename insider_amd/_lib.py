@@ -34,6 +34,7 @@ SYMBOLS = (
     "insider_hip_kmeans", "insider_hip_last_kmeans_ms", "insider_hip_residual_products", "insider_hip_solve_sympd_form",
     "insider_hip_tsne", "insider_hip_last_tsne_ms",
     "insider_hip_gram_topk", "insider_hip_last_gram_topk_ms", "insider_hip_coexpression",
+    "insider_hip_gram_topk_pairwise", "insider_hip_coexpression_pairwise",
 )
 COMM_ID_BYTES = 128
 # insider_hip_outliers (insider_amd/csrc/insider_outliers.hpp): the samples a block of k_ol_flag covers per trip (OL_TRIP) and the
@@ -152,6 +153,10 @@ def load():
     lib.insider_hip_last_gram_topk_ms.restype = C.c_double
     lib.insider_hip_coexpression.argtypes = [C.c_void_p, C.POINTER(dp), dp, C.c_int, C.c_int, C.c_int, dp, dp, C.c_int, C.c_int,
                                              i32p, dp]
+    lib.insider_hip_gram_topk_pairwise.argtypes = [dp, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_int, i32p,
+                                                   dp, i32p]
+    lib.insider_hip_coexpression_pairwise.argtypes = [C.c_void_p, C.POINTER(dp), dp, C.c_int, C.c_int, C.c_int, dp, dp, C.c_int,
+                                                      C.c_int64, C.c_int, i32p, dp, i32p]
     lib.insider_hip_enrichment.argtypes = [dp, C.c_int64, C.c_int64, C.POINTER(C.c_int64), i32p, C.c_int64, C.c_int, C.c_int,
                                            C.c_uint64, C.c_int, dp, i32p, i32p, i32p, dp, i32p]
     lib.insider_hip_last_enrichment_ms.restype = C.c_double

@@ -419,7 +419,8 @@ class InsiderData:
         centred by its mean over its selected entries (the unselected ones stay 0) and divided by the root of its centred sum
         of squares; one with fewer than two selected entries or no variance is dead: nobody's partner, a row of open slots.
         The score is the plain sum of products over the whole depth.  With a full selection this is Pearson's r; with missing
-        entries it is the ZERO-FILLED correlation (|score| <= 1, shrinking with missingness), NOT the pairwise-complete one.
+        entries it is the ZERO-FILLED correlation (|score| <= 1, shrinking with missingness), NOT the pairwise-complete one:
+        that is coexpression_pairwise().
         -> dict(index=(N, k) int32, score=(N, k) float64): descending score, equal scores by ascending index, never the
         vector itself, -1 / NaN in open slots.  The standardised residual is staged once on the device (about 8 n p bytes,
         freed before the call returns); the N x N matrix never exists."""
@@ -438,6 +439,33 @@ class InsiderData:
                                                         None if sc is None else _lib.ptr(sc), self.COEXPR_AXES[axis], int(k),
                                                         _lib.ptr(index, C.c_int32), _lib.ptr(score)))
         return dict(index=index, score=score)
+
+    def coexpression_pairwise(self, cfd_factors, column_factor, axis="genes", k=10, min_overlap=None, entries="train",
+                              center=None, scale=None, inc_continuous=0):
+        """Pairwise-complete residual co-expression (insider_hip_coexpression_pairwise): coexpression() with the score of a
+        pair taken over the entries selected in BOTH vectors, which is Pearson's r of the pair whatever is missing.  The
+        residual, ``axis``, ``entries``, ``center`` / ``scale`` and the dead vectors are those of coexpression(); the score,
+        the eligibility of a pair and ``min_overlap`` (None = max(3, ceil(depth / 4)), depth = n for genes, p for samples)
+        are those of gram_topk_pairwise().  -> dict(index=(N, k) int32, score=(N, k) float64, overlap=(N, k) int32: the
+        number of jointly selected entries of the pair): descending score, equal scores by ascending index, never the vector
+        itself, -1 / NaN / -1 in open slots."""
+        self._entries_code(entries, inc_continuous)   # (reported before axis and k; the factors' shapes after them, as ever)
+        if axis not in self.COEXPR_AXES:
+            raise InsiderError(_lib.ERR_ARG, f"axis must be one of {sorted(self.COEXPR_AXES)}, got {axis!r}")
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= NEIGHBOR_MAX_K:
+            raise InsiderError(_lib.ERR_ARG, f"k must be an integer in 1..{NEIGHBOR_MAX_K}")
+        min_overlap = pairwise_min_overlap(min_overlap, self.n if axis == "genes" else self.p)
+        K, A, Cw, Aptrs, code, nb = self._fit_args(cfd_factors, column_factor, entries, inc_continuous)
+        ce, sc = self._center_scale(center, scale, "center and scale")
+        N = self.p if axis == "genes" else self.n
+        index = np.full((N, int(k)), -1, dtype=np.int32)
+        score = np.full((N, int(k)), np.nan)
+        overlap = np.full((N, int(k)), -1, dtype=np.int32)
+        _lib.check(_lib.load().insider_hip_coexpression_pairwise(
+            self._h, Aptrs, _lib.ptr(Cw), int(inc_continuous), K, code, None if ce is None else _lib.ptr(ce),
+            None if sc is None else _lib.ptr(sc), self.COEXPR_AXES[axis], min_overlap, int(k), _lib.ptr(index, C.c_int32),
+            _lib.ptr(score), _lib.ptr(overlap, C.c_int32)))
+        return dict(index=index, score=score, overlap=overlap)
 
     def outliers(self, cfd_factors, column_factor, scale, center=None, threshold=3.0, entries="train", inc_continuous=0,
                  cap=None):
@@ -841,6 +869,65 @@ def gram_topk(V, k=10, metric="correlation", first=0, count=None, device=0):
         _lib.check(_lib.load().insider_hip_gram_topk(_lib.ptr(V), depth, N, code, k, first, count, int(device),
                                                      _lib.ptr(index, C.c_int32), _lib.ptr(score)))
     return dict(index=index, score=score)
+
+
+PAIRWISE_MIN_OVERLAP = 3   # with two joint entries every pair scores +-1
+
+
+def pairwise_min_overlap(min_overlap, depth):
+    """The checked ``min_overlap`` of the pairwise-complete calls: None = max(3, ceil(depth / 4)); an integer >= 3 otherwise
+    (one above the depth is allowed: no pair is eligible then).  Raises InsiderError(ERR_ARG)."""
+    if min_overlap is None:
+        return max(PAIRWISE_MIN_OVERLAP, -(-int(depth) // 4))
+    if isinstance(min_overlap, bool) or not isinstance(min_overlap, (int, np.integer)) or min_overlap < PAIRWISE_MIN_OVERLAP:
+        raise InsiderError(_lib.ERR_ARG, f"min_overlap must be None or an integer >= {PAIRWISE_MIN_OVERLAP}")
+    return int(min_overlap)
+
+
+def gram_topk_pairwise_args(V, k, min_overlap, first, count):
+    """The checked arguments of gram_topk_pairwise() / posthoc.gram_topk_pairwise_host(): (V, k, min_overlap, first, count),
+    V column-major float64 (depth x N) in which a NaN is a missing entry.  Shape, k, min_overlap, window and infinite values
+    raise InsiderError(ERR_ARG)."""
+    V = _lib.f64(V)
+    if V.ndim != 2 or V.shape[0] < 1 or V.shape[1] < 1:
+        raise InsiderError(_lib.ERR_ARG, "V must be a depth x N array with depth >= 1 and N >= 1")
+    depth, N = V.shape
+    if N > 2 ** 31 - 1 or depth > 2 ** 31 - 1:
+        raise InsiderError(_lib.ERR_ARG, "depth and N must be < 2^31")
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= NEIGHBOR_MAX_K:
+        raise InsiderError(_lib.ERR_ARG, f"k must be an integer in 1..{NEIGHBOR_MAX_K}")
+    min_overlap = pairwise_min_overlap(min_overlap, depth)
+    if count is None:
+        count = N - first if isinstance(first, (int, np.integer)) and not isinstance(first, bool) else count
+    for name, v in (("first", first), ("count", count)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 0:
+            raise InsiderError(_lib.ERR_ARG, f"{name} must be an integer >= 0")
+    if first + count > N:
+        raise InsiderError(_lib.ERR_ARG, "the window first + count must lie within the N vectors")
+    if np.any(np.isinf(V)):
+        raise InsiderError(_lib.ERR_ARG, "V holds an infinite value (NaN is a missing entry)")
+    return V, int(k), min_overlap, int(first), int(count)
+
+
+def gram_topk_pairwise(V, k=10, min_overlap=None, first=0, count=None, device=0):
+    """The k best partners of deep vectors with missing entries on the device (insider_hip_gram_topk_pairwise): gram_topk()'s
+    correlation, but a NaN in ``V`` (depth x N, one vector per column) is a missing entry and the score of a pair is
+    Pearson's r over the positions present in BOTH vectors (the pairwise-complete correlation), not clipped.  A vector with
+    fewer than two entries or no variance is dead.  A pair is a candidate when both vectors are alive, it has at least
+    ``min_overlap`` joint entries (None = max(3, ceil(depth / 4)); at least 3) and neither vector is constant on them (its
+    joint variance must exceed 16 (depth + 8) 2^-52 of its joint sum of squares, taken on the standardised values).
+    ``first`` / ``count`` as in gram_topk().  -> dict(index=(count, k) int32, score=(count, k) float64, overlap=(count, k)
+    int32: the pair's joint entries): descending score, equal scores by ascending index, -1 / NaN / -1 in open slots."""
+    V, k, min_overlap, first, count = gram_topk_pairwise_args(V, k, min_overlap, first, count)
+    depth, N = V.shape
+    index = np.full((count, k), -1, dtype=np.int32)
+    score = np.full((count, k), np.nan)
+    overlap = np.full((count, k), -1, dtype=np.int32)
+    if count:
+        _lib.check(_lib.load().insider_hip_gram_topk_pairwise(_lib.ptr(V), depth, N, min_overlap, k, first, count, int(device),
+                                                              _lib.ptr(index, C.c_int32), _lib.ptr(score),
+                                                              _lib.ptr(overlap, C.c_int32)))
+    return dict(index=index, score=score, overlap=overlap)
 
 
 ENRICH_MAX_SET = 4096

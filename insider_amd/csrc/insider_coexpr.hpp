@@ -57,8 +57,8 @@ constexpr size_t cx_topk_lds(int k)
 }
 
 // Standardise the vector o[16 d], d < depth, in place (metric 0: correlation, 1: cosine; a NaN is an unselected entry and
-// becomes 0).  Returns whether the vector is alive.
-__device__ __forceinline__ int cx_standardise(double *o, int64_t depth, int metric)
+// becomes `fill`, as does every entry of a dead vector).  Returns whether the vector is alive.
+__device__ __forceinline__ int cx_standardise(double *o, int64_t depth, int metric, double fill = 0.0)
 {
     double sum = 0.0, mean = 0.0;
     int64_t m = 0;
@@ -82,7 +82,7 @@ __device__ __forceinline__ int cx_standardise(double *o, int64_t depth, int metr
     const double nrm = sqrt(ss);
     for (int64_t d = 0; d < depth; ++d) {
         const double v = o[16 * d];
-        o[16 * d] = ok && v == v ? (v - mean) / nrm : 0.0;
+        o[16 * d] = ok && v == v ? (v - mean) / nrm : fill;
     }
     return ok ? 1 : 0;
 }

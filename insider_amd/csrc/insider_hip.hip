@@ -15,6 +15,7 @@
 #include "insider_outliers.hpp"
 #include "insider_neighbors.hpp"
 #include "insider_coexpr.hpp"
+#include "insider_coexpr_pc.hpp"
 #include "insider_enrich.hpp"
 #include "insider_kmeans.hpp"
 #include "insider_tsne.hpp"
@@ -513,8 +514,8 @@ struct insider_hip_handle {
     int rc_slabs = 0;
     double rc_ms = 0.0;
     // of the last co-expression call: the staged megabytes and the HIP-event times of the staging kernels (k_cx_stage,
-    // k_cx_norm) and of the product kernel (k_cx_topk)
-    double cx_stage_mb = 0.0, cx_stage_ms = 0.0, cx_ms = 0.0;
+    // k_cx_norm / k_cx_std_pc) and of the product kernel (k_cx_topk: cx_ms; k_cx_topk_pc, the pairwise-complete form: cx_pc_ms)
+    double cx_stage_mb = 0.0, cx_stage_ms = 0.0, cx_ms = 0.0, cx_pc_ms = 0.0;
     // the form the flag pass of the last outlier call ran (1 = tables in LDS, 2 = from global)
     int ol_path = 0;
 
@@ -3222,6 +3223,63 @@ int insider_hip_gram_topk(const double *V, int64_t depth, int64_t N, int metric,
 
 double insider_hip_last_gram_topk_ms(void) { return g_last_gram_topk_ms; }
 
+// the launch of k_cx_topk_pc (insider_coexpr_pc.hpp) over the query groups that meet the window, on stream st
+static int launch_cx_topk_pc(const double *P, const int *alive, int64_t npad, int64_t Dpad, int64_t depth, int64_t min_overlap,
+                             int k, int64_t first, int64_t count, int32_t *idx, double *score, int32_t *overlap, hipStream_t st)
+{
+    const size_t lds = cx_topk_pc_lds(k);
+    // above 64 KB of dynamic LDS (k > 7) the launch needs the function attribute
+    HIPCHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_cx_topk_pc), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const int64_t groups = (first + count - 1) / CX_QB - first / CX_QB + 1;
+    const double vfloor = 16.0 * (double)(depth + 8) * 0x1p-52;
+    hipLaunchKernelGGL(k_cx_topk_pc, dim3((unsigned)groups), dim3(64 * CX_WAVES), lds, st, P, alive, npad, Dpad, min_overlap, vfloor,
+                       k, first, count, idx, score, overlap);
+    KCHECK();
+    return INSIDER_OK;
+}
+
+int insider_hip_gram_topk_pairwise(const double *V, int64_t depth, int64_t N, int64_t min_overlap, int k, int64_t first,
+                                   int64_t count, int device, int32_t *idx_out, double *score_out, int32_t *overlap_out)
+{
+    if (!V || !idx_out || !score_out || !overlap_out) return fail(INSIDER_ERR_ARG, "null argument");
+    if (depth < 1 || depth > (int64_t)std::numeric_limits<int32_t>::max())
+        return fail(INSIDER_ERR_ARG, "depth must be in 1..2^31-1");
+    if (N < 1 || N > (int64_t)std::numeric_limits<int32_t>::max()) return fail(INSIDER_ERR_ARG, "N must be in 1..2^31-1");
+    if (min_overlap < 3) return fail(INSIDER_ERR_ARG, "min_overlap must be >= 3");
+    if (k < 1 || k > NN_MAX_TOPK) return fail(INSIDER_ERR_ARG, "k must be in 1..64");
+    if (first < 0 || count < 0 || first > N || count > N - first)
+        return fail(INSIDER_ERR_ARG, "the window must satisfy 0 <= first, 0 <= count, first + count <= N");
+    if (depth > (int64_t)(std::numeric_limits<size_t>::max() / sizeof(double)) / N)
+        return fail(INSIDER_ERR_ARG, "depth x N does not fit the address space");
+    for (size_t e = 0, ne = (size_t)N * depth; e < ne; ++e)
+        if (std::isinf(V[e])) return fail(INSIDER_ERR_ARG, "V must be finite or NaN (a missing entry)");
+    int rc = cd_common_checks(1, count, device);
+    if (rc) return rc;
+    if (count == 0) return INSIDER_OK;
+    HIPCHECK(hipSetDevice(device));
+    const int64_t npad = round_up(N, CX_PAD), Dpad = round_up(depth, CX_DC);
+    DevBuf<double> dV, dP, dscore;
+    DevBuf<int> dalive;
+    DevBuf<int32_t> didx, dover;
+    if ((rc = dV.alloc((size_t)N * depth)) || (rc = dP.alloc((size_t)npad * Dpad)) || (rc = dalive.alloc((size_t)npad)) ||
+        (rc = dscore.alloc((size_t)count * k)) || (rc = didx.alloc((size_t)count * k)) || (rc = dover.alloc((size_t)count * k)))
+        return rc;
+    HIPCHECK(hipMemcpy(dV, V, (size_t)N * depth * sizeof(double), hipMemcpyHostToDevice));
+    Stopwatch watch;
+    if ((rc = watch.start(0))) return rc;
+    hipLaunchKernelGGL(k_cx_std_pc, dim3(cdiv(npad, 64)), dim3(64), 0, 0, (const double *)dV, depth, N, npad, Dpad, dP.get(),
+                       dalive.get());   // (writes every double of P)
+    KCHECK();
+    if ((rc = launch_cx_topk_pc(dP, dalive, npad, Dpad, depth, min_overlap, k, first, count, didx, dscore, dover, 0))) return rc;
+    float ms = 0.0f;
+    if ((rc = watch.stop_ms(0, &ms))) return rc;
+    g_last_gram_topk_ms = ms;
+    HIPCHECK(hipMemcpy(idx_out, didx, (size_t)count * k * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIPCHECK(hipMemcpy(score_out, dscore, (size_t)count * k * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHECK(hipMemcpy(overlap_out, dover, (size_t)count * k * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return INSIDER_OK;
+}
+
 // ---- k-means (insider_kmeans.hpp) -----------------------------------------------------------------------------------------
 int insider_hip_kmeans(const double *P, int64_t N, int D, int k, int metric, const double *init, int restarts, int max_iter,
                        uint64_t seed, int device, double *centers, int32_t *label, double *dist, int32_t *second, double *dist2,
@@ -3961,6 +4019,7 @@ int insider_hip_get_info(insider_hip_handle *h, const char *name, double *out)
     else if (s == "cx_stage_mb") *out = h->cx_stage_mb;             // last co-expression call: the staged megabytes,
     else if (s == "cx_stage_ms") *out = h->cx_stage_ms;             // ... the HIP-event time of its staging kernels (k_cx_stage, k_cx_norm)
     else if (s == "cx_ms") *out = h->cx_ms;                         // ... and of its product kernel (k_cx_topk)
+    else if (s == "cx_pc_ms") *out = h->cx_pc_ms;                   // last pairwise co-expression call: k_cx_topk_pc
     else if (s == "rc_ms") *out = h->rc_ms;                         // ... and the HIP-event time of its kernels (k_rc_back, k_rc_fwd, k_rc_reduce)
     else if (s == "fd_path") *out = h->fd_path;                     // last factor decomposition: 1 = one column window (X read once), 2 = several
     else if (s == "col_mfma_per_gene") {
@@ -4670,15 +4729,19 @@ int residual_products_body(insider_hip_handle *h, double *const *A, const double
 // U and C in the kernels' layout (ph_prepare with every block) and the pairs (centre, inverse scale) of the residual products;
 // the standardised residual staged once in operand order for the axis (k_cx_stage: one pass over X and the codes; k_cx_norm:
 // one over the staged buffer), in a buffer of this call alone; then the deep product with the fused selection.  Nothing is
-// written to the caller's arrays before every check passed and the kernels ran.
+// written to the caller's arrays before every check passed and the kernels ran.  pairwise: the pairwise-complete form
+// (insider_coexpr_pc.hpp: k_cx_std_pc keeps the unselected entries NaN, k_cx_topk_pc forms the six sums) with min_overlap and
+// overlap_out; otherwise neither is looked at.
 int coexpression_body(insider_hip_handle *h, double *const *A, const double *C, int inc_continuous, int K, int entries,
-                      const double *center, const double *scale, int axis, int k, int32_t *idx_out, double *score_out)
+                      const double *center, const double *scale, int axis, int k, int32_t *idx_out, double *score_out,
+                      bool pairwise = false, int64_t min_overlap = 0, int32_t *overlap_out = nullptr)
 {
     int rc = fit_check(h, A, C, inc_continuous, K, entries);
     if (rc) return rc;
     if (axis != 0 && axis != 1) return fail(INSIDER_ERR_ARG, "axis must be 0 (genes) or 1 (samples)");
     if (k < 1 || k > NN_MAX_TOPK) return fail(INSIDER_ERR_ARG, "k must be in 1..64");
-    if (!idx_out || !score_out) return fail(INSIDER_ERR_ARG, "null output");
+    if (!idx_out || !score_out || (pairwise && !overlap_out)) return fail(INSIDER_ERR_ARG, "null output");
+    if (pairwise && min_overlap < 3) return fail(INSIDER_ERR_ARG, "min_overlap must be >= 3");
     const DataSet &d = *h->ds;
     const int64_t n = d.n, p = d.p;
     const int64_t N = axis == 0 ? p : n, depth = axis == 0 ? n : p;
@@ -4691,9 +4754,10 @@ int coexpression_body(insider_hip_handle *h, double *const *A, const double *C, 
     const int64_t npad = round_up(N, CX_PAD), Dpad = round_up(depth, CX_DC);
     DevBuf<double> stage, dscore;
     DevBuf<int> dalive;
-    DevBuf<int32_t> didx;
+    DevBuf<int32_t> didx, dover;
     if ((rc = w.rin.grow(2 * (size_t)p)) || (rc = w.rcs.grow((size_t)2 * p)) || (rc = stage.alloc((size_t)npad * Dpad)) ||
-        (rc = dalive.alloc((size_t)npad)) || (rc = dscore.alloc((size_t)N * k)) || (rc = didx.alloc((size_t)N * k)))
+        (rc = dalive.alloc((size_t)npad)) || (rc = dscore.alloc((size_t)N * k)) || (rc = didx.alloc((size_t)N * k)) ||
+        (pairwise && (rc = dover.alloc((size_t)N * k))))
         return rc;
     double *c_in = w.rin, *s_in = c_in + p, *cs = w.rcs;
     const double *U = w.U, *cp = w.cp;
@@ -4719,19 +4783,26 @@ int coexpression_body(insider_hip_handle *h, double *const *A, const double *C, 
                            (const double *)cs, sel, slab_len, axis, Dpad, stage.get());
     });
     KCHECK();
-    hipLaunchKernelGGL(k_cx_norm, dim3(cdiv(npad, 64)), dim3(64), 0, st, stage.get(), depth, N, npad, Dpad, dalive.get());
+    if (pairwise)
+        hipLaunchKernelGGL(k_cx_std_pc, dim3(cdiv(npad, 64)), dim3(64), 0, st, (const double *)nullptr, depth, N, npad, Dpad,
+                           stage.get(), dalive.get());
+    else
+        hipLaunchKernelGGL(k_cx_norm, dim3(cdiv(npad, 64)), dim3(64), 0, st, stage.get(), depth, N, npad, Dpad, dalive.get());
     KCHECK();
     if ((rc = stage_watch.mark(st)) || (rc = watch.start(st))) return rc;
-    if ((rc = launch_cx_topk(stage, dalive, npad, Dpad, k, 0, N, didx, dscore, st))) return rc;
+    if ((rc = pairwise ? launch_cx_topk_pc(stage, dalive, npad, Dpad, depth, min_overlap, k, 0, N, didx, dscore, dover, st)
+                       : launch_cx_topk(stage, dalive, npad, Dpad, k, 0, N, didx, dscore, st)))
+        return rc;
     if ((rc = watch.mark(st))) return rc;
     HIPCHECK(hipStreamSynchronize(st));   // the caller's arrays are written only after the kernels ran
     float ms_stage = 0.f, ms = 0.f;
     if ((rc = stage_watch.stop_ms(st, &ms_stage)) || (rc = watch.stop_ms(st, &ms))) return rc;
     h->cx_stage_mb = (double)npad * (double)Dpad * sizeof(double) / 1048576.0;
     h->cx_stage_ms = ms_stage;
-    h->cx_ms = ms;
+    (pairwise ? h->cx_pc_ms : h->cx_ms) = ms;
     HIPCHECK(hipMemcpyAsync(idx_out, didx, (size_t)N * k * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     HIPCHECK(hipMemcpyAsync(score_out, dscore, (size_t)N * k * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (pairwise) HIPCHECK(hipMemcpyAsync(overlap_out, dover, (size_t)N * k * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     HIPCHECK(hipStreamSynchronize(st));
     return INSIDER_OK;
 }
@@ -4859,6 +4930,14 @@ int insider_hip_coexpression(insider_hip_handle *h, double *const *A, const doub
                              double *score_out)
 {
     return ph_finish(h, coexpression_body(h, A, C, inc_continuous, K, entries, center, scale, axis, k, idx_out, score_out));
+}
+
+int insider_hip_coexpression_pairwise(insider_hip_handle *h, double *const *A, const double *C, int inc_continuous, int K,
+                                      int entries, const double *center, const double *scale, int axis, int64_t min_overlap,
+                                      int k, int32_t *idx_out, double *score_out, int32_t *overlap_out)
+{
+    return ph_finish(h, coexpression_body(h, A, C, inc_continuous, K, entries, center, scale, axis, k, idx_out, score_out, true,
+                                          min_overlap, overlap_out));
 }
 
 int insider_hip_outliers(insider_hip_handle *h, double *const *A, const double *C, int inc_continuous, int K,

@@ -59,9 +59,11 @@ __global__ void __launch_bounds__(256) k_nn_prep(const double *__restrict__ src 
 __device__ __forceinline__ bool nn_before(double sa, int ia, double sb, int ib) { return sa > sb || (sa == sb && ia < ib); }
 
 // Merge the candidate buffers of the wave's 16 queries into their sorted lists.  cnt / nl / thr: the per-lane copies (group g,
-// register r: query g + 4 r) of buffer fill, list length and threshold.
-__device__ __forceinline__ void nn_merge(double *lst_s, int *lst_i, double *buf_s, int *buf_i, int k, int lane, int (&cnt)[4],
-                                         int (&nl)[4], double (&thr)[4])
+// register r: query g + 4 r) of buffer fill, list length and threshold.  PAY: every element carries an int of its own
+// (lst_p / buf_p, laid out as lst_i / buf_i) that moves with it and takes no part in the order.
+template <bool PAY>
+__device__ __forceinline__ void nn_merge_t(double *lst_s, int *lst_i, int *lst_p, double *buf_s, int *buf_i, int *buf_p, int k,
+                                           int lane, int (&cnt)[4], int (&nl)[4], double (&thr)[4])
 {
     const int g = lane >> 4;
     wave_sync();   // the appended candidates are visible to the whole wave
@@ -75,12 +77,17 @@ __device__ __forceinline__ void nn_merge(double *lst_s, int *lst_i, double *buf_
             const int q = gq + 4 * r, tot = n + c;
             double *ls = lst_s + q * k, *bs = buf_s + q * NN_CAP;
             int *li = lst_i + q * k, *bi = buf_i + q * NN_CAP;
+            int *lp = PAY ? lst_p + q * k : nullptr, *bp = PAY ? buf_p + q * NN_CAP : nullptr;
             const int e0 = lane, e1 = lane + 64;
             const bool v0 = e0 < tot, v1 = e1 < tot;
             double s0 = 0.0, s1 = 0.0;
-            int i0 = 0, i1 = 0;
+            int i0 = 0, i1 = 0, p0 = 0, p1 = 0;
             if (v0) { s0 = e0 < n ? ls[e0] : bs[e0 - n]; i0 = e0 < n ? li[e0] : bi[e0 - n]; }
             if (v1) { s1 = e1 < n ? ls[e1] : bs[e1 - n]; i1 = e1 < n ? li[e1] : bi[e1 - n]; }
+            if constexpr (PAY) {
+                if (v0) p0 = e0 < n ? lp[e0] : bp[e0 - n];
+                if (v1) p1 = e1 < n ? lp[e1] : bp[e1 - n];
+            }
             int r0 = 0, r1 = 0;
             for (int e = 0; e < n; ++e) {
                 const double se = ls[e];
@@ -97,6 +104,10 @@ __device__ __forceinline__ void nn_merge(double *lst_s, int *lst_i, double *buf_
             wave_sync();   // every lane has read before any lane writes
             if (v0 && r0 < k) { ls[r0] = s0; li[r0] = i0; }
             if (v1 && r1 < k) { ls[r1] = s1; li[r1] = i1; }
+            if constexpr (PAY) {
+                if (v0 && r0 < k) lp[r0] = p0;
+                if (v1 && r1 < k) lp[r1] = p1;
+            }
             wave_sync();
             const int nn = tot < k ? tot : k;
             const double th = ls[k - 1];   // (read by all, used when the list is full)
@@ -107,6 +118,13 @@ __device__ __forceinline__ void nn_merge(double *lst_s, int *lst_i, double *buf_
             }
         }
     }
+}
+
+// the merge without a payload
+__device__ __forceinline__ void nn_merge(double *lst_s, int *lst_i, double *buf_s, int *buf_i, int k, int lane, int (&cnt)[4],
+                                         int (&nl)[4], double (&thr)[4])
+{
+    nn_merge_t<false>(lst_s, lst_i, nullptr, buf_s, buf_i, nullptr, k, lane, cnt, nl, thr);
 }
 
 // grid = ceil(nq / (16 NW)) blocks of 64 NW threads.  Qp / Bp: k_nn_prep's output for the queries (padded to 16) and the base

@@ -12,6 +12,7 @@
     ... --outliers 3 [--outlier-entries train]  # then the entries whose standardised residual has |z| >= 3, on the device
     ... --gene-neighbors 10 --sample-neighbors 10 [--neighbor-metric cosine]   # then each gene's / sample's nearest in latent space
     ... --gene-coexpression 10 --sample-coexpression 10   # then each gene's / sample's most correlated partners in the residual
+    ... --gene-coexpression 10 --coexpression-missing pairwise [--coexpression-min-overlap 30]   # ... pairwise-complete
     ... --gene-modules 20 --sample-clusters 6 [--cluster-metric cosine]        # then k-means of the genes / samples in latent space
     ... --gene-map --sample-map [--map-perplexity 20] [--map-neighbors 60]     # then the t-SNE map of the genes / samples
     ... --level-scores 1 [--level-score-entries train]   # then every sample against every level of covariate column 1 (1-based)
@@ -36,9 +37,13 @@ samples by its row embedding (posthoc.gene_neighbors / sample_neighbors, --neigh
 nn_gene_score (p x N) and nn_sample_index / nn_sample_score (n x N), 0-based, descending score, ties by ascending index, open
 slots -1 / NaN; --gene-coexpression N / --sample-coexpression N add each gene's N most correlated genes and each sample's N most
 correlated samples in the residual of the fit over the entries it used (posthoc.gene_coexpression / sample_coexpression; the
-samples after every gene's residual is centred and scaled, posthoc.residual_center_scale; the zero-filled correlation, not the
-pairwise-complete one, where entries are missing): cx_gene_index / cx_gene_score (p x N) and cx_sample_index / cx_sample_score
-(n x N), indices int32 and 0-based, descending score, ties by ascending index, open slots -1 / NaN;
+samples after every gene's residual is centred and scaled, posthoc.residual_center_scale): cx_gene_index / cx_gene_score
+(p x N) and cx_sample_index / cx_sample_score (n x N), indices int32 and 0-based, descending score, ties by ascending index,
+open slots -1 / NaN; --coexpression-missing says what a missing entry does to them: "zero" (the default) the zero-filled
+correlation (a missing entry counts as the vector's mean, scores shrink towards 0 with missingness, one product), "pairwise"
+the pairwise-complete correlation (Pearson's r of each pair over the entries both have, six products; a pair needs
+--coexpression-min-overlap M joint entries, default max(3, ceil(depth / 4)), and variance in both on them), which also writes
+cx_gene_overlap / cx_sample_overlap (int32: the joint entries of each listed pair, -1 in open slots);
 --gene-modules K / --sample-clusters K add the k-means partition of the genes by their columns of C and of the
 samples by their row embeddings (posthoc.gene_modules / sample_clusters; --cluster-metric cosine or euclidean, the best of
 --cluster-restarts drawn starts from --cluster-seed, at most --cluster-iters updates each): km_gene_label / km_gene_second (p,
@@ -157,6 +162,14 @@ def parse(argv=None):
     ap.add_argument("--sample-coexpression", type=int, default=None, metavar="N",
                     help="after the fit, every sample's N most correlated samples in the residual (every gene's residual centred "
                          "and scaled first), on the device; writes cx_sample_index, cx_sample_score (n x N) next to the factors")
+    ap.add_argument("--coexpression-missing", choices=("zero", "pairwise"), default="zero",
+                    help="--gene-coexpression / --sample-coexpression: what a missing entry does.  zero (default): the "
+                         "zero-filled correlation, a missing entry counts as the vector's mean and scores shrink with "
+                         "missingness; pairwise: the pairwise-complete correlation, Pearson's r of each pair over the entries "
+                         "both have, which also writes cx_gene_overlap / cx_sample_overlap (int32)")
+    ap.add_argument("--coexpression-min-overlap", type=int, default=None, metavar="M",
+                    help="--coexpression-missing pairwise: the joint entries a pair needs, at least 3 (default "
+                         "max(3, ceil(depth / 4)))")
     ap.add_argument("--gene-modules", type=int, default=None, metavar="K",
                     help="after the fit, the k-means partition of the genes into K modules by their columns of C, on the device; "
                          "writes km_gene_label, km_gene_dist, km_gene_second, km_gene_dist2 (p), km_gene_center (rank x K), "
@@ -220,6 +233,13 @@ def parse(argv=None):
             ap.error(f"--{name.replace('_', '-')} must be in 1..64")
         if v is not None and a.tune and name.endswith("coexpression"):
             ap.error(f"--{name.replace('_', '-')} reads a fit: it does not go with --tune")
+    if a.coexpression_missing == "pairwise" and a.gene_coexpression is None and a.sample_coexpression is None:
+        ap.error("--coexpression-missing goes with --gene-coexpression or --sample-coexpression")
+    if a.coexpression_min_overlap is not None:
+        if a.coexpression_missing != "pairwise":
+            ap.error("--coexpression-min-overlap goes with --coexpression-missing pairwise")
+        if a.coexpression_min_overlap < 3:
+            ap.error("--coexpression-min-overlap must be >= 3")
     for name in ("gene_modules", "sample_clusters"):
         v = getattr(a, name)
         if v is not None and not 1 <= v <= 4096:
@@ -424,17 +444,25 @@ def main(argv=None):
         nn = sample_neighbors(list(res["row_matrices"].values()), ds_levels, Z, k=a.sample_neighbors, metric=a.neighbor_metric,
                               device=a.device)
         vd = dict(vd or {}, nn_sample_index=nn["index"], nn_sample_score=nn["score"])
+    pairwise = a.coexpression_missing == "pairwise"
+
+    def coexpression(axis, k, **kw):
+        """The cx_<axis>_* records of one axis: the zero-filled call, or the pairwise-complete one with its overlap."""
+        rows_, inc = list(res["row_matrices"].values()), 1 if Z is not None else 0
+        if pairwise:
+            cx = ds.coexpression_pairwise(rows_, res["column_factor"], axis=axis + "s", k=k, entries="train", inc_continuous=inc,
+                                          min_overlap=a.coexpression_min_overlap, **kw)
+        else:
+            cx = ds.coexpression(rows_, res["column_factor"], axis=axis + "s", k=k, entries="train", inc_continuous=inc, **kw)
+        return {f"cx_{axis}_{name}": v for name, v in cx.items()}
+
     if a.gene_coexpression is not None:
-        cx = ds.coexpression(list(res["row_matrices"].values()), res["column_factor"], axis="genes", k=a.gene_coexpression,
-                             entries="train", inc_continuous=1 if Z is not None else 0)
-        vd = dict(vd or {}, cx_gene_index=cx["index"], cx_gene_score=cx["score"])
+        vd = dict(vd or {}, **coexpression("gene", a.gene_coexpression))
     if a.sample_coexpression is not None:
         from .posthoc import residual_center_scale
         rows_, inc = list(res["row_matrices"].values()), 1 if Z is not None else 0
         ce, sc = residual_center_scale(ds.variance_decomposition(rows_, res["column_factor"], entries="train", inc_continuous=inc))
-        cx = ds.coexpression(rows_, res["column_factor"], axis="samples", k=a.sample_coexpression, entries="train", center=ce,
-                             scale=sc, inc_continuous=inc)
-        vd = dict(vd or {}, cx_sample_index=cx["index"], cx_sample_score=cx["score"])
+        vd = dict(vd or {}, **coexpression("sample", a.sample_coexpression, center=ce, scale=sc))
     km_gene = None
     km = dict(metric=a.cluster_metric, restarts=a.cluster_restarts, max_iter=a.cluster_iters, seed=a.cluster_seed, device=a.device)
     if a.gene_modules is not None:

@@ -40,7 +40,9 @@ covariate (misfit, a missing interaction) from one tied to none (an unknown fact
 gene_coexpression() / sample_coexpression() ask the pairwise question about the same residual: which genes still move
 together, which samples' residuals correlate (InsiderData.coexpression: the standardised residual staged once on the device,
 then an n- or p-deep product with the top-k selection fused behind it; the zero-filled correlation, not the pairwise-complete
-one, where entries are missing); coexpression_host() is the yardstick, gram_topk_host() that of the handle-free api.gram_topk().
+one, where entries are missing; missing="pairwise" asks for the pairwise-complete one, InsiderData.coexpression_pairwise: six
+products); coexpression_host() is the yardstick, gram_topk_host() / gram_topk_pairwise_host() those of the handle-free
+api.gram_topk() / api.gram_topk_pairwise().
 
 gene_neighbors() / sample_neighbors() ask the latent representations themselves which genes lie next to a gene and which
 samples next to a sample (api.neighbors: a K-deep product on the device with the top-k selection fused behind it, the
@@ -718,6 +720,57 @@ def gram_topk_host(V, k=10, metric="correlation", first=0, count=None, chunk=512
     return _gram_select(W, alive, k, first, count, chunk)
 
 
+def _pairwise_sums(Z, M, alive, min_overlap, c0, c1):
+    """The pairwise-complete score of the queries c0 .. c1 - 1 against every vector (include/insider_hip.h,
+    insider_hip_gram_topk_pairwise): ``Z`` (depth x N) the standardised vectors, 0 where unselected, ``M`` the selection as
+    0 / 1 doubles.  -> dict of (c1 - c0) x N arrays: score, eligible, N (int64) and the six sums' va, vb, Saa, Sbb."""
+    depth = Z.shape[0]
+    floor = 16.0 * (depth + 8) * 2.0 ** -52
+    Zc, Mc, Q = Z[:, c0:c1], M[:, c0:c1], Z * Z
+    N = Mc.T @ M
+    Sab, Sa, Sb, Saa, Sbb = Zc.T @ Z, Zc.T @ M, Mc.T @ Z, Q[:, c0:c1].T @ M, Mc.T @ Q
+    with np.errstate(divide="ignore", invalid="ignore"):
+        cov = Sab - Sa * Sb / N
+        va = Saa - Sa * Sa / N
+        vb = Sbb - Sb * Sb / N
+        score = cov / np.sqrt(va * vb)
+    own = np.arange(c0, c1)[:, None] == np.arange(Z.shape[1])[None, :]
+    eligible = (alive[c0:c1, None] & alive[None, :] & ~own & (N >= min_overlap) & (va > floor * Saa) & (vb > floor * Sbb))
+    return dict(score=score, eligible=eligible, N=np.rint(N).astype(np.int64), va=va, vb=vb, Saa=Saa, Sbb=Sbb)
+
+
+def _gram_select_pairwise(R, sel, k, min_overlap, first, count, chunk):
+    """The pairwise-complete selection on the columns of ``R`` (depth x N) with the boolean selection ``sel``: every vector
+    standardised over its own selected entries first (_gram_standardise), the six sums over the joint entries, the eligible
+    partners of every query of the window by descending score, equal scores (-0.0 == 0.0) by ascending index."""
+    Z, alive = _gram_standardise(R, sel, 0)
+    M = (np.asarray(sel, dtype=bool) & alive[None, :]).astype(np.float64)
+    index = np.full((count, k), -1, dtype=np.int32)
+    score = np.full((count, k), np.nan)
+    overlap = np.full((count, k), -1, dtype=np.int32)
+    ids = np.arange(Z.shape[1])
+    for c0 in range(first, first + count, chunk):
+        c1 = min(c0 + chunk, first + count)
+        t = _pairwise_sums(Z, M, alive, min_overlap, c0, c1)
+        for i in range(c1 - c0):
+            cand = ids[t["eligible"][i]]
+            sc = t["score"][i, cand] + 0.0                          # (-0.0 + 0.0 = 0.0: one zero for the sort key)
+            order = np.lexsort((cand, -sc))[:k]
+            index[c0 + i - first, :order.size] = cand[order]
+            score[c0 + i - first, :order.size] = sc[order]
+            overlap[c0 + i - first, :order.size] = t["N"][i, cand[order]]
+    return dict(index=index, score=score, overlap=overlap)
+
+
+def gram_topk_pairwise_host(V, k=10, min_overlap=None, first=0, count=None, chunk=512):
+    """api.gram_topk_pairwise() in plain numpy (the yardstick of the device path): the same arguments, checks, definition
+    (standardise first, the six sums, the variance floor 16 (depth + 8) 2^-52) and result."""
+    from . import api
+    V, k, min_overlap, first, count = api.gram_topk_pairwise_args(V, k, min_overlap, first, count)
+    sel = ~np.isnan(V)
+    return _gram_select_pairwise(np.where(sel, V, 0.0), sel, k, min_overlap, first, count, chunk)
+
+
 def coexpression_residual_host(X, levels, ctns, mask, A, C, center=None, scale=None):
     """The working residual of coexpression_host() and the entries that count: r = ((x - f) - center[j]) / scale[j], f the
     sum of the blocks in block order (residual_products_host()'s definition); a gene whose scale is not finite or not > 0 is
@@ -745,47 +798,73 @@ def coexpression_residual_host(X, levels, ctns, mask, A, C, center=None, scale=N
     return r, w
 
 
-def coexpression_host(X, levels, ctns, mask, A, C, axis, k, center=None, scale=None, chunk=512):
+def coexpression_host(X, levels, ctns, mask, A, C, axis, k, center=None, scale=None, chunk=512, missing="zero",
+                      min_overlap=None):
     """InsiderData.coexpression() in plain numpy (the yardstick of the device path); X, levels, ctns, mask, A, C, center and
     scale as in residual_products_host(), ``axis`` "genes" (the p columns of the residual, correlated over the samples) or
     "samples" (its n rows, over the genes).  Every vector is centred by its mean over its selected entries (unselected stay
     0) and divided by the root of its centred sum of squares; fewer than two selected entries or no variance: dead.  The
     score is the plain sum of products over the whole depth: Pearson's r under a full selection, the zero-filled correlation
     (NOT the pairwise-complete one) under a mask.  -> dict(index=(N, k) int32, score=(N, k)), the order and open slots of
-    neighbors_host()."""
+    neighbors_host().  missing="pairwise": InsiderData.coexpression_pairwise() instead, the pairwise-complete score of
+    gram_topk_pairwise_host() on the same standardised vectors with ``min_overlap`` (None = max(3, ceil(depth / 4))), and an
+    ``overlap`` (N, k) int32 in the result."""
     if axis not in ("genes", "samples"):
         raise ValueError(f"axis must be 'genes' or 'samples', got {axis!r}")
+    if missing not in COEXPR_MISSING:
+        raise ValueError(f"missing must be one of {COEXPR_MISSING}, got {missing!r}")
     if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= 64:
         raise ValueError("k must be an integer in 1..64")
     r, w = coexpression_residual_host(X, levels, ctns, mask, A, C, center, scale)
     if axis == "samples":
         r, w = r.T, w.T
+    if missing == "pairwise":
+        from . import api
+        return _gram_select_pairwise(r, w, int(k), api.pairwise_min_overlap(min_overlap, r.shape[0]), 0, r.shape[1], chunk)
     W, alive = _gram_standardise(r, w, 0)
     return _gram_select(W, alive, int(k), 0, W.shape[1], chunk)
 
 
-def gene_coexpression(obj, k=10, which="fit", entries="train"):
+COEXPR_MISSING = ("zero", "pairwise")
+
+
+def _coexpression(ds, cfd, col, axis, k, entries, inc, missing, min_overlap, **kw):
+    """ds.coexpression() (missing="zero": min_overlap must be None) or ds.coexpression_pairwise() (missing="pairwise")."""
+    if missing not in COEXPR_MISSING:
+        raise ValueError(f"missing must be one of {COEXPR_MISSING}, got {missing!r}")
+    if missing == "pairwise":
+        return ds.coexpression_pairwise(cfd, col, axis=axis, k=k, min_overlap=min_overlap, entries=entries, inc_continuous=inc,
+                                        **kw)
+    if min_overlap is not None:
+        raise ValueError('min_overlap belongs to missing="pairwise"')
+    return ds.coexpression(cfd, col, axis=axis, k=k, entries=entries, inc_continuous=inc, **kw)
+
+
+def gene_coexpression(obj, k=10, which="fit", entries="train", missing="zero", min_overlap=None):
     """The k most correlated genes of every gene in the residual of a fitted ``Insider`` object (InsiderData.coexpression,
     axis "genes"), with the ``which`` / ``entries`` of variance_decomposition(): the co-expression network on corrected
-    expression.  The correlation of two genes does not depend on their scales, so no centre or scale is passed.  Missing
-    entries make it the zero-filled correlation, not the pairwise-complete one.  -> dict(index=(p, k) int32 0-based genes,
+    expression.  The correlation of two genes does not depend on their scales, so no centre or scale is passed.
+    missing="zero": missing entries make it the zero-filled correlation; missing="pairwise": the pairwise-complete one
+    (InsiderData.coexpression_pairwise) over the samples both genes have, at least ``min_overlap`` of them (None =
+    max(3, ceil(n / 4))), with an ``overlap`` (p, k) int32 in the result.  -> dict(index=(p, k) int32 0-based genes,
     score=(p, k)); open slots -1 / NaN."""
     ds, cfd, col, inc = _fitted(obj, which)
-    return ds.coexpression(cfd, col, axis="genes", k=k, entries=entries, inc_continuous=inc)
+    return _coexpression(ds, cfd, col, "genes", k, entries, inc, missing, min_overlap)
 
 
-def sample_coexpression(obj, k=10, which="fit", entries="train", standardize=True):
+def sample_coexpression(obj, k=10, which="fit", entries="train", standardize=True, missing="zero", min_overlap=None):
     """The k most correlated samples of every sample in the residual of a fitted ``Insider`` object (InsiderData.coexpression,
     axis "samples"): duplicated libraries, cross-contamination, relatedness.  standardize=True centres and scales every
     gene's residual first (residual_center_scale() of a variance decomposition on the same entries), so that a few
-    high-variance genes do not own the sample correlation.  Zero-filled correlation under missing entries, as
-    gene_coexpression().  -> dict(index=(n, k) int32 0-based samples, score=(n, k)) plus the ``center`` and ``scale`` used
-    (None without standardize)."""
+    high-variance genes do not own the sample correlation.  ``missing`` / ``min_overlap`` as in gene_coexpression(): the
+    zero-filled correlation by default, the pairwise-complete one (and an ``overlap``) with "pairwise".
+    -> dict(index=(n, k) int32 0-based samples, score=(n, k)) plus the ``center`` and ``scale`` used (None without
+    standardize)."""
     ds, cfd, col, inc = _fitted(obj, which)
     center = scale = None
     if standardize:
         center, scale = residual_center_scale(ds.variance_decomposition(cfd, col, entries=entries, inc_continuous=inc))
-    out = ds.coexpression(cfd, col, axis="samples", k=k, entries=entries, center=center, scale=scale, inc_continuous=inc)
+    out = _coexpression(ds, cfd, col, "samples", k, entries, inc, missing, min_overlap, center=center, scale=scale)
     out["center"], out["scale"] = center, scale
     return out
 
