@@ -35,6 +35,7 @@ extern "C" {
 #define INSIDER_ERR_NO_DEVICE 5  /* no HIP device / extension unusable: no fallback exists */
 #define INSIDER_ERR_UNSUPPORTED 6 /* K > 63, n or p >= 2^23, ... */
 #define INSIDER_ERR_COMM 7       /* RCCL or the all-reduce callback reported failure, or world > 1 has neither */
+#define INSIDER_ERR_UNFINISHED 8 /* insider_hip_hclust: max_rounds was reached before one cluster was left */
 
 /* Largest latent dimension the kernels support (K + 1 augmented column <= 64). */
 #define INSIDER_MAX_K 63
@@ -746,6 +747,48 @@ int insider_hip_kmeans(const double *P, int64_t N, int D, int k, int metric, con
                        uint64_t seed, int device, double *centers, int32_t *label, double *dist, int32_t *second, double *dist2,
                        int32_t *sizes, double *traj, double *final_inertia, int32_t *iters, int32_t *converged, int32_t *best);
 double insider_hip_last_kmeans_ms(void);
+
+/* Agglomerative (hierarchical) clustering of embeddings (insider_amd/csrc/insider_hclust.hpp).  Handle-free, one device.
+ *   Layout.  P is D x N, column-major: one point is D contiguous doubles, the layout of column_factor.  merge is (N - 1) x 2
+ *   int32, row-major (row r = the two children of merge r); height and size have N - 1 entries, order has N.
+ *   Linkages.  Two are offered: those that are reducible and whose cluster-to-cluster distance is a function of the clusters'
+ *   sums.  n = the size, S = the sum of the member vectors, mu = S / n (one division per coordinate).
+ *     metric 0, linkage 0: cosine, average.  Members x = p / |p|, |p| the square root of the sum of squares (products and sums
+ *       rounded one by one in index order); a point whose sum of squares is 0 is DEAD: it is in no cluster.
+ *       d(A, B) = 1 - mu_A . mu_B, which is exactly the mean pairwise cosine distance (UPGMA).  height = d.
+ *     metric 1, linkage 1: Euclidean, Ward.  Members x = p - m, m = the grand mean (coordinate by coordinate: partial i < 256 adds
+ *       the points i, i + 256, ... in that order, the partials are added in order, one division by N): Ward is translation
+ *       invariant, and centring removes the cancellation of data far from the origin.  Every point is alive.
+ *       d(A, B) = max(0, n_A n_B / (n_A + n_B) * ((h_A + h_B) - 2 mu_A . mu_B)), h = |mu|^2.  height = sqrt(2 d), the
+ *       convention of scipy's linkage(method="ward").
+ *     Every other pair of codes is refused.  Single and complete linkage are not functions of the sums; centroid and median
+ *     linkage are not reducible.  None of them is offered.
+ *   Tie rule.  Candidates are ordered by (d ascending, cluster id ascending); d is bitwise symmetric in (A, B).  Ids of a run:
+ *   0 .. N - 1 are the points, the r-th merge the run emits is N + r.
+ *   Algorithm: rounds of reciprocal nearest neighbours.  A cluster is STALE when it has no stored neighbour or its stored
+ *   neighbour was merged.  A round (1) finds, for every stale cluster, its first candidate among all other clusters in the order
+ *   above (in round 1 every cluster is stale), (2) merges every pair a < b with nn[a] = b and nn[b] = a, emitting them in
+ *   ascending a: S_new = S_a + S_b, n_new = n_a + n_b.  Everybody else keeps its neighbour (reducibility).  A round that finds no
+ *   pair (rounding can break reducibility in the last bit) merges nothing, and in the next round every cluster is stale; such a
+ *   round always holds a pair (the lowest id on any minimal pair and its neighbour name each other).  The run ends when one
+ *   cluster is left; rounds = the rounds run, queries = the sum of their stale counts, alive = the points that are not dead.
+ *   When max_rounds rounds (>= 1; 2 N always suffices) did not finish the run: INSIDER_ERR_UNFINISHED, nothing written.
+ *   Result.  The height of a merge is raised to the larger height of its children where rounding left it below; the merges are
+ *   sorted by height, equal heights by emission (a stable sort: children come before parents), and renumbered as scipy's
+ *   linkage numbers them: row r creates id N + r; a leaf keeps its point index (with no dead point this is scipy's Z).  merge
+ *   holds the lower id first; size is the number of points under the merge.  alive - 1 rows are filled (none when alive <= 1);
+ *   the rows beyond hold -1 / NaN / -1.  order = the leaves of a depth-first walk from the last row, the lower id first, then
+ *   the dead points in ascending index.
+ *   Purity.  No floating-point atomics and no order that depends on the launch: the result is a pure function of the arguments
+ *   and repeated calls return identical bits.  The N x N distances never exist: device memory is O(N D).  Between the upload
+ *   and the final download the only thing that crosses the bus is one record of three ints per round.
+ *   INSIDER_ERR_ARG, nothing written: a NULL pointer, D outside 1..63, N < 1 or 2 N - 1 > INT32_MAX, a pair (metric, linkage)
+ *   other than the two above, max_rounds < 1, a non-finite value in P (all checked on the host, before a device is opened).
+ *   insider_hip_last_hclust_ms: of the calling THREAD's last call, the HIP-event time in ms from its first kernel to its last
+ *   (the per-round records included, the upload and the final download excluded); set by an unfinished run too. */
+int insider_hip_hclust(const double *P, int64_t N, int D, int metric, int linkage, int max_rounds, int device, int32_t *merge,
+                       double *height, int32_t *size, int32_t *order, int32_t *rounds, int64_t *queries, int32_t *alive);
+double insider_hip_last_hclust_ms(void);
 
 /* Exact t-SNE map of a neighbour graph (insider_amd/csrc/insider_tsne.hpp).  Handle-free, one device.
  *   Input: a graph, not points.  nbr_idx is N x k int32, point-major (row i = the k slots of point i), 0-based, -1 = an open

@@ -11,7 +11,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("INSIDER_HIP_LIB") or os.path.join(_HERE, "libinsider_hip.so")   # INSIDER_HIP_LIB: another build of the same C ABI
 
-OK, ERR_ARG, ERR_SOLVE, ERR_ALLOC, ERR_HIP, ERR_NO_DEVICE, ERR_UNSUPPORTED, ERR_COMM = range(8)
+OK, ERR_ARG, ERR_SOLVE, ERR_ALLOC, ERR_HIP, ERR_NO_DEVICE, ERR_UNSUPPORTED, ERR_COMM, ERR_UNFINISHED = range(9)
 TRAJ_STRIDE = 10
 MAX_K = 63
 
@@ -35,6 +35,7 @@ SYMBOLS = (
     "insider_hip_tsne", "insider_hip_last_tsne_ms",
     "insider_hip_gram_topk", "insider_hip_last_gram_topk_ms", "insider_hip_coexpression",
     "insider_hip_gram_topk_pairwise", "insider_hip_coexpression_pairwise",
+    "insider_hip_hclust", "insider_hip_last_hclust_ms",
 )
 COMM_ID_BYTES = 128
 # insider_hip_outliers (insider_amd/csrc/insider_outliers.hpp): the samples a block of k_ol_flag covers per trip (OL_TRIP) and the
@@ -164,6 +165,9 @@ def load():
     lib.insider_hip_kmeans.argtypes = [dp, C.c_int64, C.c_int, C.c_int, C.c_int, dp, C.c_int, C.c_int, C.c_uint64, C.c_int, dp, i32p,
                                        dp, i32p, dp, i32p, dp, dp, i32p, i32p, i32p]
     lib.insider_hip_last_kmeans_ms.restype = C.c_double
+    lib.insider_hip_hclust.argtypes = [dp, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, i32p, dp, i32p, i32p, i32p,
+                                       C.POINTER(C.c_int64), i32p]
+    lib.insider_hip_last_hclust_ms.restype = C.c_double
     lib.insider_hip_tsne.argtypes = [i32p, dp, C.c_int64, C.c_int, C.c_double, dp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double,
                                      C.c_uint64, C.c_int, C.c_int, dp, dp, dp, dp, dp, dp, dp]
     lib.insider_hip_last_tsne_ms.restype = C.c_double

@@ -1050,6 +1050,65 @@ def kmeans(points, k, metric="cosine", init=None, restarts=8, max_iter=100, seed
     return rec
 
 
+HCLUST_METRICS = {"cosine": 0, "euclidean": 1}
+HCLUST_LINKAGES = {"average": 0, "ward": 1}
+HCLUST_PAIRS = {"cosine": "average", "euclidean": "ward"}      # the one linkage offered under each metric
+HCLUST_MAX_D = 63                                               # HC_MAX_D of insider_amd/csrc/insider_hclust.hpp
+
+
+def hclust_args(points, metric="cosine", linkage=None, max_rounds=None):
+    """The checked arguments of hclust() / posthoc.hclust_host(): (P column-major float64 D x N, metric code, linkage code,
+    max_rounds).  linkage None picks the metric's only linkage; max_rounds None is 2 N.  Every argument error of
+    insider_hip_hclust (include/insider_hip.h) raises InsiderError(ERR_ARG) here, before the library is reached."""
+    def bad(msg):
+        return InsiderError(_lib.ERR_ARG, msg)
+    P = _lib.f64(points)
+    if P.ndim != 2:
+        raise bad("points must be a D x N array")
+    D, N = P.shape
+    if not 1 <= D <= HCLUST_MAX_D:
+        raise bad(f"D must be in 1..{HCLUST_MAX_D}")
+    if not (N >= 1 and 2 * N - 1 < 2 ** 31):
+        raise bad("points must hold 1..2^30 columns")
+    if metric not in HCLUST_METRICS:
+        raise bad(f"metric must be one of {sorted(HCLUST_METRICS)}")
+    if linkage is None:
+        linkage = HCLUST_PAIRS[metric]
+    if linkage not in HCLUST_LINKAGES:
+        raise bad(f"linkage must be one of {sorted(HCLUST_LINKAGES)} (single, complete, centroid and median are not offered)")
+    if HCLUST_PAIRS[metric] != linkage:
+        raise bad(f"metric {metric!r} with linkage {linkage!r} is not offered: {metric!r} goes with {HCLUST_PAIRS[metric]!r}")
+    if max_rounds is None:
+        max_rounds = min(2 * N, 2 ** 31 - 1)
+    if isinstance(max_rounds, bool) or not isinstance(max_rounds, (int, np.integer)) or not 1 <= max_rounds < 2 ** 31:
+        raise bad("max_rounds must be an integer in 1..2^31-1")
+    if not np.isfinite(P).all():
+        raise bad("points must be finite")
+    return P, HCLUST_METRICS[metric], HCLUST_LINKAGES[linkage], int(max_rounds)
+
+
+def hclust(points, metric="cosine", linkage=None, max_rounds=None, device=0):
+    """Agglomerative clustering of the columns of ``points`` (D x N, one point per column, as column_factor) on the device
+    (insider_hip_hclust; include/insider_hip.h states the definitions and the tie rule).  metric "cosine" goes with linkage
+    "average" (UPGMA of cosine distances; an all-zero column is dead: in no cluster), "euclidean" with "ward"; linkage None picks
+    that one, any other combination is refused.  -> dict(merge ((N - 1) x 2 int32: the children of every merge, lower id first,
+    leaves by point index, row r creates id N + r), height, size (N - 1), order (N int32: the leaf order, dead points last),
+    rounds, queries, alive, ms (the HIP-event time of the call's kernels)); rows beyond alive - 1 hold -1 / NaN.  A run that
+    max_rounds cuts short raises InsiderError(ERR_UNFINISHED)."""
+    P, mcode, lcode, max_rounds = hclust_args(points, metric, linkage, max_rounds)
+    D, N = P.shape
+    i32 = C.c_int32
+    rec = dict(merge=np.full((N - 1, 2), -1, dtype=np.int32), height=np.full(N - 1, np.nan), size=np.full(N - 1, -1, dtype=np.int32),
+               order=np.full(N, -1, dtype=np.int32))
+    rounds, alive, queries = np.zeros(1, dtype=np.int32), np.zeros(1, dtype=np.int32), np.zeros(1, dtype=np.int64)
+    lib = _lib.load()
+    _lib.check(lib.insider_hip_hclust(_lib.ptr(P), N, D, mcode, lcode, max_rounds, int(device), _lib.ptr(rec["merge"], i32),
+                                      _lib.ptr(rec["height"]), _lib.ptr(rec["size"], i32), _lib.ptr(rec["order"], i32),
+                                      _lib.ptr(rounds, i32), _lib.ptr(queries, C.c_int64), _lib.ptr(alive, i32)))
+    rec.update(rounds=int(rounds[0]), queries=int(queries[0]), alive=int(alive[0]), ms=float(lib.insider_hip_last_hclust_ms()))
+    return rec
+
+
 TSNE_MAX_N = 2 ** 20
 TSNE_MAX_K = NEIGHBOR_MAX_K
 TSNE_MAX_ITER = 10000

@@ -18,6 +18,7 @@
 #include "insider_coexpr_pc.hpp"
 #include "insider_enrich.hpp"
 #include "insider_kmeans.hpp"
+#include "insider_hclust.hpp"
 #include "insider_tsne.hpp"
 
 #include <rccl/rccl.h>
@@ -51,6 +52,7 @@ thread_local double g_last_neighbors_ms = 0.0;
 thread_local double g_last_gram_topk_ms = 0.0;
 thread_local double g_last_enrichment_ms = 0.0;
 thread_local double g_last_kmeans_ms = 0.0;
+thread_local double g_last_hclust_ms = 0.0;
 thread_local double g_last_tsne_ms = 0.0;
 
 int fail(int code, const std::string &msg)
@@ -3469,6 +3471,188 @@ int insider_hip_kmeans(const double *P, int64_t N, int D, int k, int metric, con
 }
 
 double insider_hip_last_kmeans_ms(void) { return g_last_kmeans_ms; }
+
+// ---- agglomerative clustering (insider_hclust.hpp) ------------------------------------------------------------------------
+namespace {
+
+// The records of a finished run (emission order: a, b ids of the run, d, size) brought into the order and the numbering of the
+// result (include/insider_hip.h): heights made monotone along the tree, a stable sort by height, row r creates id N + r.
+void hc_finish(int64_t N, const std::vector<int32_t> &pt_alive, int metric, const std::vector<int32_t> &ra,
+               const std::vector<int32_t> &rb, const std::vector<double> &rd, const std::vector<int32_t> &rn, int32_t *merge,
+               double *height, int32_t *size, int32_t *order)
+{
+    const int64_t R = (int64_t)ra.size();
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    std::vector<double> h((size_t)R);
+    for (int64_t r = 0; r < R; ++r) {
+        double v = metric == 1 ? std::sqrt(2.0 * rd[r]) : rd[r];
+        if (ra[r] >= N) v = std::max(v, h[ra[r] - N]);   // (a child was emitted before its parent)
+        if (rb[r] >= N) v = std::max(v, h[rb[r] - N]);
+        h[r] = v;
+    }
+    std::vector<int64_t> perm((size_t)R), row((size_t)R);
+    for (int64_t r = 0; r < R; ++r) perm[r] = r;
+    std::stable_sort(perm.begin(), perm.end(), [&](int64_t x, int64_t y) { return h[x] < h[y]; });
+    for (int64_t r = 0; r < R; ++r) row[perm[r]] = r;
+    for (int64_t r = 0; r < N - 1; ++r) {
+        if (r < R) {
+            const int64_t e = perm[r];
+            const int64_t x = ra[e] < N ? ra[e] : N + row[ra[e] - N], y = rb[e] < N ? rb[e] : N + row[rb[e] - N];
+            merge[2 * r] = (int32_t)std::min(x, y);
+            merge[2 * r + 1] = (int32_t)std::max(x, y);
+            height[r] = h[e];
+            size[r] = rn[e];
+        } else {
+            merge[2 * r] = merge[2 * r + 1] = -1;
+            height[r] = nan;
+            size[r] = -1;
+        }
+    }
+    // leaf order: depth first from the last row, the lower id first; a lone alive point is its own tree; dead points last
+    int64_t o = 0;
+    std::vector<int64_t> stack;
+    if (R > 0) stack.push_back(N + R - 1);
+    else
+        for (int64_t i = 0; i < N; ++i)
+            if (pt_alive[i]) stack.push_back(i);
+    while (!stack.empty()) {
+        const int64_t c = stack.back();
+        stack.pop_back();
+        if (c < N) {
+            order[o++] = (int32_t)c;
+        } else {
+            stack.push_back(merge[2 * (c - N) + 1]);
+            stack.push_back(merge[2 * (c - N)]);
+        }
+    }
+    for (int64_t i = 0; i < N; ++i)
+        if (!pt_alive[i]) order[o++] = (int32_t)i;
+}
+
+}  // namespace
+
+int insider_hip_hclust(const double *P, int64_t N, int D, int metric, int linkage, int max_rounds, int device, int32_t *merge,
+                       double *height, int32_t *size, int32_t *order, int32_t *rounds, int64_t *queries, int32_t *alive)
+{
+    if (!P || !merge || !height || !size || !order || !rounds || !queries || !alive)
+        return fail(INSIDER_ERR_ARG, "null argument");
+    if (D < 1 || D > HC_MAX_D) return fail(INSIDER_ERR_ARG, "D must be in 1..63");
+    if (N < 1 || 2 * N - 1 > (int64_t)std::numeric_limits<int32_t>::max()) return fail(INSIDER_ERR_ARG, "N must be in 1..2^30");
+    if (!((metric == 0 && linkage == 0) || (metric == 1 && linkage == 1)))
+        return fail(INSIDER_ERR_ARG, "metric / linkage must be 0 / 0 (cosine, average) or 1 / 1 (Euclidean, Ward)");
+    if (max_rounds < 1) return fail(INSIDER_ERR_ARG, "max_rounds must be at least 1");
+    if (!all_finite(P, (size_t)N * D)) return fail(INSIDER_ERR_ARG, "P must be finite");
+    int rc = cd_common_checks(D, N, device);
+    if (rc) return rc;
+    HIPCHECK(hipSetDevice(device));
+    const int K4 = (D + 3) & ~3, KS = (K4 + 15) / 16;
+    const int NT = K4 <= 32 ? 4 : 2;
+    const int64_t M = 2 * N - 1, npad = round_up(N, 16 * NT);
+    const int64_t nbmax = cdiv(M, 256);
+    const size_t lds = (size_t)(NT * 16 * K4 + 2 * NT * 16) * sizeof(double) + (size_t)NT * 16 * sizeof(int);
+    DevBuf<double> dS, dmean, dCp, dQp, dcn, dch, dqn, dqh, dnnd, drd;
+    DevBuf<int32_t> dsize, dalive, dnn, dact, dstale, dpairs, dcid, dqid, dra, drb, drn;
+    DevBuf<int> dbc, dtot;
+    if ((rc = dS.alloc((size_t)M * D)) || (rc = dmean.alloc((size_t)D)) || (rc = dCp.alloc((size_t)npad * K4)) ||
+        (rc = dQp.alloc((size_t)npad * K4)) || (rc = dcn.alloc((size_t)npad)) || (rc = dch.alloc((size_t)npad)) ||
+        (rc = dqn.alloc((size_t)npad)) || (rc = dqh.alloc((size_t)npad)) || (rc = dnnd.alloc((size_t)M)) ||
+        (rc = drd.alloc((size_t)N)) || (rc = dsize.alloc((size_t)M)) || (rc = dalive.alloc((size_t)M)) ||
+        (rc = dnn.alloc((size_t)M)) || (rc = dact.alloc((size_t)N)) || (rc = dstale.alloc((size_t)N)) ||
+        (rc = dpairs.alloc((size_t)N)) || (rc = dcid.alloc((size_t)npad)) || (rc = dqid.alloc((size_t)npad)) ||
+        (rc = dra.alloc((size_t)N)) || (rc = drb.alloc((size_t)N)) || (rc = drn.alloc((size_t)N)) ||
+        (rc = dbc.alloc((size_t)2 * nbmax)) || (rc = dtot.alloc(4)))
+        return rc;
+    HIPCHECK(hipMemcpy(dS, P, (size_t)N * D * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHECK(hipMemset(dalive, 0, (size_t)M * sizeof(int32_t)));
+    HIPCHECK(hipMemset(dnn, 0xFF, (size_t)M * sizeof(int32_t)));
+    Stopwatch watch;
+    if ((rc = watch.start(0))) return rc;
+    if (metric == 1) {
+        hipLaunchKernelGGL(k_hc_mean, dim3(D), dim3(256), 0, 0, (const double *)dS, N, D, dmean.get());
+        KCHECK();
+    }
+    hipLaunchKernelGGL(k_hc_points, dim3(cdiv(N, 256)), dim3(256), 0, 0, dS.get(), N, D, metric, (const double *)dmean,
+                       dsize.get(), dalive.get(), dnn.get());
+    KCHECK();
+    // the ordered lists of mode over the ids < top: totals to dtot[2 mode ..]
+    auto lists = [&](int mode, int force, int64_t top) -> int {
+        const int64_t nb = cdiv(top, 256);
+        hipLaunchKernelGGL(k_hc_count, dim3((unsigned)nb), dim3(256), 0, 0, mode, force, top, (const int32_t *)dalive, (const int32_t *)dnn,
+                           dbc.get());
+        KCHECK();
+        hipLaunchKernelGGL(k_hc_offsets, dim3(1), dim3(256), 0, 0, dbc.get(), nb, dtot.get() + 2 * mode);
+        KCHECK();
+        hipLaunchKernelGGL(k_hc_compact, dim3((unsigned)nb), dim3(256), 0, 0, mode, force, top, (const int32_t *)dalive,
+                           (const int32_t *)dnn, (const int *)dbc, mode == 0 ? dact.get() : dpairs.get(),
+                           mode == 0 ? dstale.get() : (int32_t *)nullptr);
+        KCHECK();
+        return INSIDER_OK;
+    };
+    int tot[4] = {0, 0, 0, 0};   // alive, stale, pairs of the last round
+    if ((rc = lists(0, 0, N))) return rc;
+    HIPCHECK(hipMemcpy(tot, dtot, sizeof(tot), hipMemcpyDeviceToHost));
+    std::vector<int32_t> pt_alive((size_t)N);   // (before any merge: the points that are not dead)
+    HIPCHECK(hipMemcpy(pt_alive.data(), dalive, (size_t)N * sizeof(int32_t), hipMemcpyDeviceToHost));
+    const int Na = tot[0];
+    int na = Na, ns = tot[1], base = 0, nround = 0;
+    int64_t nquery = 0;
+    bool unfinished = false;
+    while (na > 1) {
+        if (nround == max_rounds) {
+            unfinished = true;
+            break;
+        }
+        const int napad = (int)round_up(na, 16 * NT), nspad = (int)round_up(ns, 16);
+        hipLaunchKernelGGL(k_hc_cprep, dim3(cdiv(napad, 256)), dim3(256), 0, 0, (const int32_t *)dact, na, napad, (const double *)dS,
+                           (const int32_t *)dsize, D, K4, dCp.get(), dcid.get(), dcn.get(), dch.get());
+        KCHECK();
+        if (ns < 1) return fail(INSIDER_ERR_HIP, "hclust: a round without a stale cluster");   // (cannot happen: a merge makes one)
+        hipLaunchKernelGGL(k_hc_cprep, dim3(cdiv(nspad, 256)), dim3(256), 0, 0, (const int32_t *)dstale, ns, nspad,
+                           (const double *)dS, (const int32_t *)dsize, D, K4, dQp.get(), dqid.get(), dqn.get(), dqh.get());
+        KCHECK();
+        KT_DISPATCH(KS, hipLaunchKernelGGL((k_hc_nn<KT_>), dim3(cdiv(ns, 16 * HC_NW)), dim3(64 * HC_NW), lds, 0, (const double *)dQp,
+                                           (const int32_t *)dqid, (const double *)dqn, (const double *)dqh, ns, (const double *)dCp,
+                                           (const int32_t *)dcid, (const double *)dcn, (const double *)dch, na, napad, K4, NT, metric,
+                                           dnn.get(), dnnd.get()));
+        KCHECK();
+        const int64_t top = N + base;
+        if ((rc = lists(1, 0, top))) return rc;
+        hipLaunchKernelGGL(k_hc_merge, dim3(cdiv(na / 2, 4)), dim3(256), 0, 0, (const int32_t *)dpairs, (const int *)dtot.get() + 2, N,
+                           base, D, dS.get(), dsize.get(), dalive.get(), dnn.get(), (const double *)dnnd, dra.get(), drb.get(),
+                           drd.get(), drn.get());
+        KCHECK();
+        if ((rc = lists(0, 0, top + na / 2))) return rc;
+        HIPCHECK(hipMemcpy(tot, dtot, sizeof(tot), hipMemcpyDeviceToHost));   // the round's record: all the host reads
+        ++nround;
+        nquery += ns;
+        if (tot[2] == 0) {   // no reciprocal pair among kept and new neighbours: everything is asked again
+            if ((rc = lists(0, 1, top))) return rc;
+            HIPCHECK(hipMemcpy(tot, dtot, sizeof(tot), hipMemcpyDeviceToHost));
+        }
+        base += tot[2];
+        na = tot[0];
+        ns = tot[1];
+    }
+    float ms = 0.0f;
+    if ((rc = watch.stop_ms(0, &ms))) return rc;
+    g_last_hclust_ms = ms;
+    if (unfinished) return fail(INSIDER_ERR_UNFINISHED, "max_rounds reached before one cluster was left");
+    std::vector<int32_t> ra((size_t)base), rb((size_t)base), rn((size_t)base);
+    std::vector<double> rd((size_t)base);
+    if (base > 0) {
+        HIPCHECK(hipMemcpy(ra.data(), dra, (size_t)base * sizeof(int32_t), hipMemcpyDeviceToHost));
+        HIPCHECK(hipMemcpy(rb.data(), drb, (size_t)base * sizeof(int32_t), hipMemcpyDeviceToHost));
+        HIPCHECK(hipMemcpy(rn.data(), drn, (size_t)base * sizeof(int32_t), hipMemcpyDeviceToHost));
+        HIPCHECK(hipMemcpy(rd.data(), drd, (size_t)base * sizeof(double), hipMemcpyDeviceToHost));
+    }
+    hc_finish(N, pt_alive, metric, ra, rb, rd, rn, merge, height, size, order);
+    *rounds = nround;
+    *queries = nquery;
+    *alive = Na;
+    return INSIDER_OK;
+}
+
+double insider_hip_last_hclust_ms(void) { return g_last_hclust_ms; }
 
 // ---- t-SNE (insider_tsne.hpp) ---------------------------------------------------------------------------------------------
 int insider_hip_tsne(const int32_t *nbr_idx, const double *nbr_d2, int64_t N, int k, double perplexity, const double *init,

@@ -15,6 +15,7 @@
     ... --gene-coexpression 10 --coexpression-missing pairwise [--coexpression-min-overlap 30]   # ... pairwise-complete
     ... --gene-modules 20 --sample-clusters 6 [--cluster-metric cosine]        # then k-means of the genes / samples in latent space
     ... --gene-map --sample-map [--map-perplexity 20] [--map-neighbors 60]     # then the t-SNE map of the genes / samples
+    ... --gene-tree --sample-tree [--tree-metric cosine] [--tree-cut 20]       # then the dendrogram of the genes / samples
     ... --level-scores 1 [--level-score-entries train]   # then every sample against every level of covariate column 1 (1-based)
     ... --residual-components 5 [--rc-standardize] [--rc-entries train]   # then the hidden factors: what the model left behind
     ... --gene-sets SETS.gmt [--gene-names NAMES.txt] [--enrich-perms 1000] [--enrich-levels 1]   # then what each factor means
@@ -54,6 +55,12 @@ km_gene_size (k), km_gene_traj (the inertia before every update, NaN beyond the 
 (posthoc.gene_map / sample_map: the cosine neighbour graph of --map-neighbors neighbours, --map-perplexity, --map-iters
 iterations from the start drawn from --map-seed; the defaults follow posthoc.tsne_defaults): ts_gene_y (p x 2, NaN for an
 all-zero column), ts_gene_kl (KL every 50 iterations and at the end), ts_gene_beta (p) and the same under ts_sample_*;
+--gene-tree / --sample-tree add the dendrogram of the genes by their columns of C and of the samples by their row embeddings
+(posthoc.gene_tree / sample_tree; --tree-metric cosine: average linkage, the default, or euclidean: Ward's linkage):
+hc_gene_merge (p - 1 x 2 int32, scipy's numbering: row r creates id p + r), hc_gene_height, hc_gene_size (p - 1), hc_gene_order
+(p: the leaf order, points in no cluster last; rows beyond the alive points hold -1 / NaN), with --tree-cut K hc_gene_label (p,
+0-based by the lowest member, -1 = in no cluster) and the same under hc_sample_*; with --gene-sets and --tree-cut also
+hc_gene_overlap / hc_gene_hyper_p / hc_gene_hyper_fdr (K x S, posthoc.tree_overrepresentation);
 --level-scores COV adds, for covariate column COV (1-based), ls_sse (n x L: the residual sum of squares of every
 sample over the --level-score-entries with its embedding for COV replaced by each level's), ls_n, ls_best (1-based, 0 = no
 entry), ls_margin (n) and ls_confusion (L x L, assigned x best; posthoc.ls_derived) — a sample's own level was fitted with that
@@ -187,6 +194,20 @@ def parse(argv=None):
                     help="--gene-modules / --sample-clusters: updates per start at most (default 100)")
     ap.add_argument("--cluster-seed", type=int, default=0x1D5EED, metavar="S",
                     help="--gene-modules / --sample-clusters: the seed of the drawn starts")
+    ap.add_argument("--gene-tree", action="store_true",
+                    help="after the fit, the dendrogram of the genes by their columns of C (agglomerative clustering on the "
+                         "device); writes hc_gene_merge (p - 1 x 2), hc_gene_height, hc_gene_size (p - 1), hc_gene_order (p: the "
+                         "leaf order of a heat map) next to the factors; with --tree-cut K also hc_gene_label (p) and, with "
+                         "--gene-sets, hc_gene_overlap, hc_gene_hyper_p, hc_gene_hyper_fdr (K x S)")
+    ap.add_argument("--sample-tree", action="store_true",
+                    help="after the fit, the dendrogram of the samples by their row embeddings, on the device; writes the "
+                         "hc_sample_* records")
+    ap.add_argument("--tree-metric", choices=("cosine", "euclidean"), default=None,
+                    help="--gene-tree / --sample-tree: cosine (the default: average linkage, all-zero columns of C are in no "
+                         "cluster) or euclidean (Ward's linkage)")
+    ap.add_argument("--tree-cut", type=int, default=None, metavar="K",
+                    help="--gene-tree / --sample-tree: also the labels of the tree cut into K clusters (hc_gene_label / "
+                         "hc_sample_label, -1 for a point in no cluster)")
     ap.add_argument("--gene-map", action="store_true",
                     help="after the fit, the exact t-SNE map of the genes by their columns of C, on the device; writes ts_gene_y "
                          "(p x 2; NaN for an all-zero column), ts_gene_kl and ts_gene_beta (p) next to the factors")
@@ -246,6 +267,13 @@ def parse(argv=None):
             ap.error(f"--{name.replace('_', '-')} must be in 1..4096")
         if v is not None and a.tune:
             ap.error(f"--{name.replace('_', '-')} partitions a fit: it does not go with --tune")
+    if a.gene_tree or a.sample_tree:
+        if a.tune:
+            ap.error("--gene-tree / --sample-tree cluster a fit: they do not go with --tune")
+        if a.tree_cut is not None and a.tree_cut < 1:
+            ap.error("--tree-cut must be at least 1")
+    elif a.tree_metric is not None or a.tree_cut is not None:
+        ap.error("--tree-metric and --tree-cut go with --gene-tree or --sample-tree")
     if a.gene_map or a.sample_map:
         if a.tune:
             ap.error("--gene-map / --sample-map draw a fit: they do not go with --tune")
@@ -480,6 +508,26 @@ def main(argv=None):
     if a.sample_map:
         from .posthoc import sample_map
         vd = dict(vd or {}, **ts_records("ts_sample", sample_map(list(res["row_matrices"].values()), ds_levels, Z, **ts)))
+    hc_gene = None
+
+    def hc_records(prefix, rec):
+        """The hc_<axis>_* records of one tree, with the labels of --tree-cut."""
+        out = {f"{prefix}_{name}": rec[name] for name in ("merge", "height", "size", "order")}
+        if a.tree_cut is not None:
+            from .posthoc import cut_tree
+            if a.tree_cut > rec["alive"]:
+                raise SystemExit(f"--tree-cut {a.tree_cut}: the {prefix[3:]} tree has {rec['alive']} leaves")
+            out[f"{prefix}_label"] = cut_tree(rec, k=a.tree_cut)
+        return out
+
+    if a.gene_tree:
+        from .posthoc import gene_tree
+        hc_gene = gene_tree(res["column_factor"], metric=a.tree_metric or "cosine", device=a.device)
+        vd = dict(vd or {}, **hc_records("hc_gene", hc_gene))
+    if a.sample_tree:
+        from .posthoc import sample_tree
+        vd = dict(vd or {}, **hc_records("hc_sample", sample_tree(list(res["row_matrices"].values()), ds_levels, Z,
+                                                                  metric=a.tree_metric or "cosine", device=a.device)))
     gs_names = None
     if a.gene_sets is not None:
         from .posthoc import factor_enrichment, level_enrichment
@@ -504,6 +552,10 @@ def main(argv=None):
             from .posthoc import module_overrepresentation
             ora = module_overrepresentation(km_gene["label"], sets, k=a.gene_modules)
             vd.update(km_gene_overlap=ora["overlap"], km_gene_hyper_p=ora["hyper_p"], km_gene_hyper_fdr=ora["hyper_fdr"])
+        if hc_gene is not None and a.tree_cut is not None:
+            from .posthoc import tree_overrepresentation
+            ora = tree_overrepresentation(hc_gene, a.tree_cut, sets)
+            vd.update(hc_gene_overlap=ora["overlap"], hc_gene_hyper_p=ora["hyper_p"], hc_gene_hyper_fdr=ora["hyper_fdr"])
     ds.close()
     summary = dict(train_rmse=res["train_rmse"], test_rmse=None if np.isnan(res["test_rmse"]) else res["test_rmse"],
                    loss=res["loss"], iters=res["iters"], rank=K, **{"lambda": a.lam}, alpha=a.alpha, partition=partition,

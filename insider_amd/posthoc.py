@@ -52,6 +52,9 @@ Euclidean, restarts); kmeans_host() is the yardstick, module_overrepresentation(
 gene_map() / sample_map() draw them: the exact t-SNE map of the embeddings' cosine neighbour graph (embedding_graph(), api.tsne:
 the whole optimisation on the device, the all-pairs repulsion summed in fp64, the same map to the bit from run to run);
 tsne_host() is the yardstick.
+gene_tree() / sample_tree() / level_tree() build their dendrograms (api.hclust: average linkage of cosine distances or Ward's
+linkage, rounds of reciprocal nearest neighbours on the device, the N x N distances never exist); hclust_host() is the
+yardstick, cut_tree() cuts a tree into flat clusters, tree_overrepresentation() reads the modules of a cut.
 
 factor_enrichment() / level_enrichment() ask what a factor or a level effect means: a preranked gene-set enrichment of the
 rows of column_factor, or of A_b @ column_factor, with a permutation null of random gene sets of equal size
@@ -1466,6 +1469,229 @@ def module_overrepresentation(label, sets, k=None):
     if len(sets) == 3:
         rec["names"] = list(sets[0])
     return rec
+
+
+# ---- agglomerative clustering (include/insider_hip.h states the definitions and the tie rule) ---------------------------------
+def hclust_points(P, code):
+    """The working points of insider_hip_hclust -> (X D x N, alive): cosine x = p / |p| (a zero column is dead), Euclidean
+    x = p - m with the grand mean m summed in the header's order (256 interleaved partials, then the partials in order)."""
+    D, N = P.shape
+    if code == 0:
+        nrm = np.sqrt(_sumsq(P))
+        alive = nrm > 0
+        return np.where(alive, P / np.where(alive, nrm, 1.0), 0.0), alive
+    pad = np.zeros((D, -(-N // 256) * 256))
+    pad[:, :N] = P
+    pad = pad.reshape(D, -1, 256)
+    part = np.zeros((D, 256))
+    for r in range(pad.shape[1]):
+        part = part + pad[:, r, :]
+    tot = np.zeros(D)
+    for e in range(256):
+        tot = tot + part[:, e]
+    return P - (tot / float(N))[:, None], np.ones(N, dtype=bool)
+
+
+def hclust_state(X, alive):
+    """The state of a run before its first round: per cluster id (0 .. 2 N - 2) the sum S, the size n, alive, nn (-1: none) and
+    nn_d; the emitted records; the counters."""
+    D, N = X.shape
+    M = 2 * N - 1
+    S = np.zeros((M, D))
+    S[:N] = X.T
+    al = np.zeros(M, dtype=bool)
+    al[:N] = alive
+    n = np.zeros(M, dtype=np.int64)
+    n[:N] = 1
+    return dict(N=N, S=S, n=n, alive=al, nn=np.full(M, -1, dtype=np.int64), nn_d=np.full(M, np.inf), ra=[], rb=[], rd=[], rn=[],
+                scale=[], rounds=0, queries=0, min_gap=np.inf)
+
+
+def hclust_round(st, code, force=False, chunk=512, blas=False):
+    """One round of the run on the state ``st`` (hclust_state()), as include/insider_hip.h states it -> the number of merges.
+    Every stale cluster (every alive one when ``force``) takes its first candidate in the order (d ascending, id ascending);
+    the reciprocal pairs a < b are merged in ascending a.  A product adds its D terms in index order (blas=True: the matrix
+    product).  st["min_gap"] keeps the smallest (runner-up d - best d) / scale over all queries so far, scale = the larger
+    n_A n_B / (n_A + n_B) (h_A + h_B) of the two pairs under Ward and 1 under cosine: how far the run is from a choice that
+    rounding could make; st["scale"] the same scale of every merged pair."""
+    N, S, n, alive, nn = st["N"], st["S"], st["n"], st["alive"], st["nn"]
+    act = np.flatnonzero(alive)
+    stale_mask = np.ones(act.size, dtype=bool) if force else (nn[act] < 0) | ~alive[np.maximum(nn[act], 0)]
+    stale = act[stale_mask]
+    mu = S[act] / n[act][:, None].astype(np.float64)
+    h = _sumsq(mu.T)
+    nc = n[act].astype(np.float64)
+    pos = np.flatnonzero(stale_mask)
+    for c0 in range(0, stale.size, chunk):
+        qp = pos[c0:c0 + chunk]
+        Q = mu[qp]
+        if blas:
+            Pr = Q @ mu.T
+        else:
+            Pr = np.zeros((qp.size, act.size))
+            for d in range(mu.shape[1]):
+                Pr = Pr + Q[:, d][:, None] * mu[:, d][None, :]
+        if code == 1:
+            w = (nc[qp][:, None] * nc[None, :]) / (nc[qp][:, None] + nc[None, :])
+            sc = w * (h[qp][:, None] + h[None, :])
+            dist = np.maximum(0.0, w * ((h[qp][:, None] + h[None, :]) - 2.0 * Pr))
+        else:
+            sc = np.ones_like(Pr)
+            dist = 1.0 - Pr
+        rows = np.arange(qp.size)
+        dist[rows, qp] = np.inf                                    # (itself)
+        b1 = dist.argmin(axis=1)                                    # the first of equal distances: the lowest id
+        d1 = dist[rows, b1]
+        ok = np.isfinite(d1)
+        nn[act[qp]] = np.where(ok, act[b1], -1)
+        st["nn_d"][act[qp]] = d1
+        if act.size > 2:
+            s1 = sc[rows, b1]
+            dist[rows, b1] = np.inf
+            b2 = dist.argmin(axis=1)
+            gap = (dist[rows, b2] - d1) / np.maximum(np.maximum(s1, sc[rows, b2]), 1e-300)
+            st["min_gap"] = min(st["min_gap"], float(gap[ok].min()) if ok.any() else np.inf)
+    st["rounds"] += 1
+    st["queries"] += int(stale.size)
+    b = nn[act]
+    pair = (b > act) & (nn[np.maximum(b, 0)] == act)
+    base = len(st["ra"])
+    hpos = {int(c): i for i, c in enumerate(act)} if code == 1 else None
+    for r, a in enumerate(act[pair]):
+        a, bb = int(a), int(nn[a])
+        c = N + base + r
+        S[c] = S[a] + S[bb]
+        n[c] = n[a] + n[bb]
+        alive[a] = alive[bb] = False
+        alive[c] = True
+        nn[c] = -1
+        st["ra"].append(a), st["rb"].append(bb), st["rd"].append(float(st["nn_d"][a])), st["rn"].append(int(n[c]))
+        st["scale"].append(float(n[a] * n[bb]) / float(n[a] + n[bb]) * (h[hpos[a]] + h[hpos[bb]]) if code == 1 else 1.0)
+    return int(pair.sum())
+
+
+def hclust_finish(N, pt_alive, code, ra, rb, rd, rn):
+    """The emitted records in the order and the numbering of the result -> (merge, height, size, order, perm): heights made
+    monotone along the tree, a stable sort by height, row r creates id N + r, the lower id first; perm[r] = the emission index
+    of row r."""
+    R = len(ra)
+    h = np.zeros(R)
+    for r in range(R):
+        v = np.sqrt(2.0 * rd[r]) if code == 1 else rd[r]
+        for c in (ra[r], rb[r]):
+            if c >= N:
+                v = max(v, h[c - N])
+        h[r] = v
+    perm = np.argsort(h, kind="stable")
+    row = np.empty(R, dtype=np.int64)
+    row[perm] = np.arange(R)
+    merge = np.full((max(N - 1, 0), 2), -1, dtype=np.int32)
+    height, size = np.full(max(N - 1, 0), np.nan), np.full(max(N - 1, 0), -1, dtype=np.int32)
+    for r in range(R):
+        e = perm[r]
+        x, y = (c if c < N else N + row[c - N] for c in (ra[e], rb[e]))
+        merge[r] = min(x, y), max(x, y)
+        height[r], size[r] = h[e], rn[e]
+    order, stack = [], [N + R - 1] if R else [int(i) for i in np.flatnonzero(pt_alive)[::-1]]
+    while stack:
+        c = stack.pop()
+        if c < N:
+            order.append(c)
+        else:
+            stack.append(int(merge[c - N, 1]))
+            stack.append(int(merge[c - N, 0]))
+    order += [int(i) for i in np.flatnonzero(~np.asarray(pt_alive, dtype=bool))]
+    return merge, height, size, np.array(order, dtype=np.int32), perm
+
+
+def hclust_host(points, metric="cosine", linkage=None, max_rounds=None, chunk=512, blas=False):
+    """api.hclust() in plain numpy float64 (the yardstick of the device path): the same arguments, checks, rule and record,
+    following include/insider_hip.h line by line: rounds of reciprocal nearest neighbours over stale clusters only, sums and
+    merges in the device's order.  The record also holds ``min_gap`` (hclust_round()), ``scale`` (per row, what the error bound
+    of a height scales with) and ``d`` (per row, the linkage distance the height was made from).  A run that max_rounds cuts
+    short raises InsiderError(ERR_UNFINISHED).  ``ms`` is the wall time."""
+    import time
+    from . import api
+    t_start = time.perf_counter()
+    P, code, _, max_rounds = api.hclust_args(points, metric, linkage, max_rounds)
+    N = P.shape[1]
+    X, pt_alive = hclust_points(P, code)
+    st = hclust_state(X, pt_alive)
+    force = False
+    while int(st["alive"].sum()) > 1:
+        if st["rounds"] == max_rounds:
+            raise api.InsiderError(api._lib.ERR_UNFINISHED, "max_rounds reached before one cluster was left")
+        force = hclust_round(st, code, force=force, chunk=chunk, blas=blas) == 0
+    merge, height, size, order, perm = hclust_finish(N, pt_alive, code, st["ra"], st["rb"], st["rd"], st["rn"])
+    R = len(st["ra"])
+    scale, d = np.full(max(N - 1, 0), np.nan), np.full(max(N - 1, 0), np.nan)
+    scale[:R], d[:R] = np.asarray(st["scale"], dtype=np.float64)[perm], np.asarray(st["rd"], dtype=np.float64)[perm]
+    return dict(merge=merge, height=height, size=size, order=order, rounds=st["rounds"], queries=st["queries"],
+                alive=int(pt_alive.sum()), min_gap=st["min_gap"], scale=scale, d=d, ms=(time.perf_counter() - t_start) * 1e3)
+
+
+def cut_tree(rec, k=None, height=None):
+    """Flat clusters of an hclust() record, on the host: the first alive - k merges (``k`` clusters), or every merge of height
+    <= ``height``.  -> labels (N int32), 0-based in the order of every cluster's lowest point index, -1 for a dead point."""
+    from . import api
+    merge, hts = np.asarray(rec["merge"]), np.asarray(rec["height"])
+    N, alive = int(np.asarray(rec["order"]).size), int(rec["alive"])
+    R = max(alive - 1, 0)
+    if (k is None) == (height is None):
+        raise api.InsiderError(api._lib.ERR_ARG, "give exactly one of k and height")
+    if k is not None:
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not (1 <= k <= alive or (alive == 0 and k == 0)):
+            raise api.InsiderError(api._lib.ERR_ARG, f"k must be an integer in 1..{alive} (the alive points)")
+        take = alive - int(k)
+    else:
+        take = int(np.searchsorted(hts[:R], float(height), side="right"))
+    low = np.arange(N + R, dtype=np.int64)                          # the lowest point index under every id
+    parent = np.arange(N + R, dtype=np.int64)
+    for r in range(take):
+        x, y = int(merge[r, 0]), int(merge[r, 1])
+        low[N + r] = min(low[x], low[y])
+        parent[x] = parent[y] = N + r
+    label = np.full(N, -1, dtype=np.int32)
+    dead = np.ones(N, dtype=bool)
+    dead[np.asarray(rec["order"])[:alive]] = False
+    root = np.arange(N + R)
+    for c in range(N + take - 1, -1, -1):                           # (parents have higher ids: their roots are final)
+        if parent[c] != c:
+            root[c] = root[parent[c]]
+    lows = low[root[:N]]
+    lows[dead] = -1
+    _, inv = np.unique(lows[~dead], return_inverse=True)
+    label[~dead] = inv.astype(np.int32)
+    return label
+
+
+def tree_overrepresentation(rec, k, sets):
+    """Over-representation of gene sets in the k modules a gene tree is cut into: module_overrepresentation() of
+    cut_tree(rec, k)."""
+    return module_overrepresentation(cut_tree(rec, k=k), sets, k=k)
+
+
+def gene_tree(column_factor, metric="cosine", linkage=None, max_rounds=None, device=0):
+    """The dendrogram of the genes: api.hclust() on the columns of C (K x p).  Under cosine (the default) an all-zero column of
+    C is dead: in no cluster, last in ``order``.  -> the api.hclust() record (order: the gene order of a heat map)."""
+    from . import api
+    return api.hclust(column_factor, metric=metric, linkage=linkage, max_rounds=max_rounds, device=device)
+
+
+def sample_tree(cfd_factors, levels, ctns_confounder=None, metric="cosine", linkage=None, max_rounds=None, device=0):
+    """The dendrogram of the samples: api.hclust() on sample_embeddings().  Samples that share every level are equal points:
+    they merge first, at height 0, in ascending index (the tie rule).  -> the api.hclust() record."""
+    from . import api
+    return api.hclust(sample_embeddings(cfd_factors, levels, ctns_confounder), metric=metric, linkage=linkage,
+                      max_rounds=max_rounds, device=device)
+
+
+def level_tree(cfd_factor, metric="cosine", linkage=None, max_rounds=None, device=0):
+    """The dendrogram of one covariate's levels (which tissues, phenotypes or donors go together): api.hclust() on the rows of
+    its L x K matrix.  -> the api.hclust() record (leaves: 0-based levels)."""
+    from . import api
+    return api.hclust(np.asarray(cfd_factor, dtype=np.float64).T, metric=metric, linkage=linkage, max_rounds=max_rounds,
+                      device=device)
 
 
 def module_summary(rec, column_factor):
