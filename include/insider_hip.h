@@ -898,13 +898,46 @@ int insider_hip_get_profile(insider_hip_handle *h, double *out12);
  * (k_list_stats4, row side), 15 list_stats (k_list_stats<NB>, row side), 16 level_partial (k_level_partial + k_level_sum +
  * k_level_reduce), 17 level_solve (k_level_solve), 18 cont_cd (k_cont_cd).  Products of the row update (not the row prep):
  * V = C A' 19 mm_rows2 (k_mm_rows2), 20 mm_rows (k_mm_rows); Y = U'C 21 mm_reduce2_2 (k_mm_reduce2<NB,2>), 22 mm_reduce2_4
- * (k_mm_reduce2<NB,4>), 23 mm_reduce (k_mm_reduce)). */
+ * (k_mm_reduce2<NB,4>), 23 mm_reduce (k_mm_reduce)),
+ * the scalar facts of the resident data set (what insider_hip_create_ex / _remask / _remask_fold built; they describe the
+ * arrays of insider_hip_get_array "ds:<name>"): "ds_ldn" / "ds_ldp" (pitch of a gene-major / sample-major line: n / p rounded
+ * up to 128), "ds_SLP" (pitch of the level-sum tables: all levels + m, rounded up to 2), "ds_cnt_train" / "ds_cnt_test"
+ * (entries whose train / test bit is set), "ds_no_na" (1: every entry is train or test), "ds_merged" / "ds_cont_merged" (the
+ * tables of the merged row update exist; also for the continuous columns), "ds_cf_pair_ok" (the pair-count form's tables
+ * exist: no cell above 255), "ds_max_chunks", "ds_max_L", "ds_max_items", "ds_nitems:<i>" / "ds_npairs:<i>" (work items and
+ * (level, gene) pairs of covariate i's weighted lists),
+ * "ds_bytes:<name>" or "ds_bytes:<name>:<i>" (size in bytes of the data-set array of that name, 0 when this data set did not
+ * build it; an unknown name returns INSIDER_ERR_ARG; "ds_bytes:cf_geometry" and "ds_bytes:names" likewise). */
 int insider_hip_get_info(insider_hip_handle *h, const char *name, double *out);
 
 /* Diagnostics: copy an internal per-gene array to the host: "cd_pass_slot" (uint32 x p: what the last limited pass of a
  * multi-pass column solve left per gene: 0xFFFFFFFF = finished, else estimate bucket << 24 | rank), "gene_perm" (int32 x p:
  * the launch order), "order_table" (the sweep-order table of the last column solve: rows of 448 bytes, one per sweep of the
- * period; bytes 0..K-1 of row s = the coordinates of sweep s in visiting order, include/insider_perm.h). */
+ * period; bytes 0..K-1 of row s = the coordinates of sweep s in visiting order, include/insider_perm.h).
+ * bytes may be at most what exists (else INSIDER_ERR_ARG); the handle's stream is synchronised, nothing is written.
+ *
+ * "ds:<name>" or "ds:<name>:<i>": a device array of the resident data set, as it lies in memory (the whole allocation:
+ * "ds_bytes:<name>" of insider_hip_get_info gives its size).  An array this data set did not build returns INSIDER_ERR_ARG
+ * with a message that says so; so does an unknown name.  Names are those of the members:
+ *   X (f64, p lines of pitch ds_ldn, pad 0), codes (u8, same layout: bit 0 train, bit 1 test, pad = train), lev (i32, c x n,
+ *   0-based), lvl_off_d (i32, c + 1), members_all (i32, c x n: samples by level, ascending inside a level), lvl_ptr_all (i32,
+ *   covariate i's L_i + 1 pointers at lvl_off[i] + i), lvl_count_all (i32, per stacked level), Zc (f64, m x n), one_count,
+ *   ident_members (i32), S / Strain / Sheld (f64, p x ds_SLP: level sums of X over all / train / held-out entries, continuous
+ *   column k at SLcat + k: sums of x z), yy_all / yy_train (f64, p), col_ptr / row_ptr (u32, lines + 1), col_idx / row_idx
+ *   (i32), col_val / row_val (f64), col_flag (u8; only with NA entries): the held-out lists, ascending element index inside a
+ *   line, each line padded to a multiple of 32 entries with (0x7FFFFF, 0.0, 0); the 64 entries behind the last line are not
+ *   defined.  cf_cnt (u8), cf_hn (f32), cf_sq (f64), cf_zt (f64): the packed tables of the factored column statistics,
+ *   cont_cnt (f64, m), cont_pair:<k> (f64, SL), fold_id (u8, layout of codes, pad 0).
+ *   Per covariate i: chunk_level:<i>, chunk_begin:<i>, chunk_end:<i>, lvl_chunk_ptr:<i> (i32), grp:<i> (u32, p x (L_i + 1)),
+ *   slev:<i> (u16, max(c - 1, 1) planes of col_entries + 64; defined at the positions grp addresses), item_begin:<i>,
+ *   item_end:<i> (u32), lvl_item_ptr:<i> (i32, L_i + 1), wl_idx:<i> (i32), wl_w:<i> (f64), paircnt:<i> (f64, L_i rows of
+ *   pitch SL = all levels + m).  The same members of the continuous columns' tables are "cont.<member>",
+ *   "contm.<member>:<k>" (contm.paircnt:<k> is the allocation of cont_pair:<k>) and "contm_lists.<member>".
+ * "ds:names": every such name, one per line, ":#" behind a name that takes an index.
+ * "ds:cf_geometry": the static part of the factored statistics' arguments as 136 int32: c, nsteps, tab_skip_lo, tab_skip_n,
+ *   tab_rows, cnt_stride, hn_stride, zt_stride, sq_stride, m; then nine values each (positions 0..8, descending level count;
+ *   position c = the continuous columns) of L, off, nlater, cnt_off, hn_off, zt_off; then pos_cov[8]; then later_plane[8][8]
+ *   row by row.  All zero when the data set has no factored tables (more than 8 covariates, or no merged tables). */
 int insider_hip_get_array(insider_hip_handle *h, const char *name, void *out, int64_t bytes);
 
 /* Diagnostics: per-gene sweep counts of the last column update (p ints); of the calling THREAD's last

@@ -549,10 +549,27 @@ class InsiderData:
                     col_pair=bool(int(out[11]) & 4))
 
     def info(self, name):
-        """A fact about the handle (insider_hip_get_info): "col_stats_path", "col_mfma_per_gene", ..."""
+        """A fact about the handle (insider_hip_get_info): "col_stats_path", "col_mfma_per_gene", ...; of its resident data
+        set: "ds_ldn", "ds_SLP", "ds_no_na", "ds_merged", "ds_cf_pair_ok", "ds_nitems:<i>", ... and "ds_bytes:<name>[:<i>]",
+        the size of a data-set array (0: this data set did not build it)."""
         out = C.c_double()
         _lib.check(_lib.load().insider_hip_get_info(self._h, name.encode(), C.byref(out)))
         return out.value
+
+    def array(self, name, dtype=np.uint8):
+        """A device array of the resident data set as it lies in memory (insider_hip_get_array "ds:<name>" or
+        "ds:<name>:<i>"; include/insider_hip.h lists the names, layouts and element types), or None when this data set did not
+        build it.  "cf_geometry" is the static part of the factored statistics' arguments (int32), "names" the list of names
+        (bytes).  Diagnostics: the handle's stream is synchronised and the array copied; nothing is written."""
+        nbytes = int(self.info("ds_bytes:" + name))
+        if nbytes == 0:
+            return None
+        dtype = np.dtype(dtype)
+        if nbytes % dtype.itemsize:
+            raise InsiderError(_lib.ERR_ARG, f"{name}: {nbytes} bytes are no whole number of {dtype} elements")
+        out = np.zeros(nbytes // dtype.itemsize, dtype=dtype)
+        _lib.check(_lib.load().insider_hip_get_array(self._h, ("ds:" + name).encode(), out.ctypes.data_as(C.c_void_p), nbytes))
+        return out
 
     def comm_init(self, unique_id, rank, world):
         """Join the in-library RCCL communicator (insider_hip_comm_init) after set_shard(); collective over all ranks."""

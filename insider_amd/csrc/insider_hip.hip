@@ -208,7 +208,8 @@ struct CovTables {   // per covariate, device
     int64_t npairs = 0;               // (level, gene) pairs with held-out samples
     DevBuf<int> wl_idx;               // (gene, count) lists of every level, padded like the held-out lists
     DevBuf<double> wl_w;
-    DevBuf<double> paircnt;           // [L][SLcat] samples in (level of this covariate, stacked level of another one)
+    DevBuf<double> paircnt;           // [L][SL] samples in (level of this covariate, stacked level of another one); its own block
+                                      // is zero, columns SLcat .. SL - 1 hold sum_{r in l} z_rk (stage_pair_tables)
 };
 // continuous columns share one table: a single pseudo-level whose members are all samples, in 16-sample chunks
 
@@ -252,8 +253,10 @@ struct DataSet {
     DevBuf<int> ident_members;        // 0..n-1
     int max_chunks = 0, max_L = 0, max_items = 0;
     DevBuf<double> S, yy_train, yy_all;
-    DevBuf<double> Strain;            // per-level sums of X over TRAIN entries (p x SLP)
-    DevBuf<double> Sheld;             // S - Strain: per-level sums over the held-out entries
+    DevBuf<double> Strain;            // per-level sums of X over TRAIN entries (p x SLP).  Its continuous columns are written, and
+                                      // read, only with cont_merged (k_zt_build: S - S^held); zero otherwise
+    DevBuf<double> Sheld;             // S - Strain: per-level sums over the held-out entries (continuous columns, cont_merged:
+                                      // the sums of x z over the held-out list; without cont_merged they equal S and nothing reads them)
     double cnt_train = 0, cnt_test = 0;
     bool no_na = false;               // every entry is train or test: held-out == test
     // held-out lists (element index, value) of every gene (col) and of every sample (row); padded to LIST_ALIGN
@@ -2057,8 +2060,8 @@ int stage_sums(DataSet &d, hipStream_t st)
     const bool own_all = !d.yy_all;
     if ((rc = d.yy_train.alloc((size_t)p)) || (rc = (own_all ? d.yy_all : yy_scratch).alloc((size_t)p))) return rc;
     DevBuf<unsigned long long> cnt;
-    if ((rc = cnt.alloc(2))) return rc;
-    HIPCHECK(hipMemsetAsync(cnt, 0, 2 * sizeof(unsigned long long), st));
+    if ((rc = cnt.alloc(3))) return rc;
+    HIPCHECK(hipMemsetAsync(cnt, 0, 3 * sizeof(unsigned long long), st));
     hipLaunchKernelGGL(k_line_sumsq, dim3(cdiv(p, 4)), dim3(256), 0, st, (const double *)d.X, (const uint8_t *)d.codes, d.ldn, (int)n,
                        (int)p, d.yy_train, own_all ? d.yy_all.get() : yy_scratch.get(), cnt);
     // train-only sums for the merged masked row update / the factored column statistics (the categorical columns)
@@ -2068,12 +2071,12 @@ int stage_sums(DataSet &d, hipStream_t st)
                        d.ldn, (int)p, (const int *)d.members_all, (const int *)d.lvl_ptr_all, (const int *)d.lvl_off_d, c, (int)n,
                        d.SLcat, d.SLP, d.Strain);
     KCHECK();
-    unsigned long long hc[2];
+    unsigned long long hc[3];
     HIPCHECK(hipMemcpyAsync(hc, cnt, sizeof(hc), hipMemcpyDeviceToHost, st));
     HIPCHECK(hipStreamSynchronize(st));
     d.cnt_train = (double)hc[0];
     d.cnt_test = (double)hc[1];
-    d.no_na = hc[0] + hc[1] == (unsigned long long)n * (unsigned long long)p;
+    d.no_na = hc[2] == 0;   // (not cnt_train + cnt_test == n p: an entry that is train and test would hide an NA entry)
     return INSIDER_OK;
 }
 
@@ -4145,6 +4148,169 @@ int insider_hip_col_stats(insider_hip_handle *h, double *const *A, int inc_conti
 double insider_hip_last_cd_ms(void) { return g_last_cd_ms; }
 int insider_hip_last_cd_solver(void) { return g_last_cd_solver; }
 
+}  // extern "C"
+
+namespace {
+// ---- read-back of the resident data set (diagnostics: insider_hip_get_array "ds:<name>", insider_hip_get_info "ds_bytes:<name>") ----
+// Every DevBuf of DataSet, of its CovTables and of FoldIds under the member's name.  The members of CovTables are "<member>:<i>"
+// for cov[i], "cont.<member>" for cont, "contm.<member>:<k>" for contm[k] and "contm_lists.<member>" for contm_lists; cont_pair[k]
+// is "cont_pair:<k>" (contm[k].paircnt holds the same allocation) and FoldIds::id is "fold_id".
+constexpr const char *DS_COV_MEMBERS[] = {"chunk_level", "chunk_begin", "chunk_end", "lvl_chunk_ptr", "grp", "slev", "item_begin",
+                                          "item_end", "lvl_item_ptr", "wl_idx", "wl_w", "paircnt"};
+constexpr const char *DS_MEMBERS[] = {"X", "codes", "lev", "lvl_off_d", "members_all", "lvl_ptr_all", "lvl_count_all", "Zc",
+                                      "one_count", "ident_members", "S", "yy_train", "yy_all", "Strain", "Sheld", "col_ptr",
+                                      "row_ptr", "col_idx", "row_idx", "col_val", "row_val", "col_flag", "cf_cnt", "cf_hn",
+                                      "cf_sq", "cf_zt", "cont_cnt"};
+constexpr int DS_GEOMETRY_INTS = 10 + 6 * (CF_MAXC + 1) + CF_MAXC + CF_MAXC * CF_MAXC;
+
+struct DsView { const void *p = nullptr; size_t bytes = 0; };
+
+template <typename T>
+DsView ds_view(const DevBuf<T> &b) { return DsView{b.get(), b.bytes()}; }
+
+bool ds_cov_member(const CovTables &t, const std::string &f, DsView &v)
+{
+    if (f == "chunk_level") v = ds_view(t.chunk_level);
+    else if (f == "chunk_begin") v = ds_view(t.chunk_begin);
+    else if (f == "chunk_end") v = ds_view(t.chunk_end);
+    else if (f == "lvl_chunk_ptr") v = ds_view(t.lvl_chunk_ptr);
+    else if (f == "grp") v = ds_view(t.grp);
+    else if (f == "slev") v = ds_view(t.slev);
+    else if (f == "item_begin") v = ds_view(t.item_begin);
+    else if (f == "item_end") v = ds_view(t.item_end);
+    else if (f == "lvl_item_ptr") v = ds_view(t.lvl_item_ptr);
+    else if (f == "wl_idx") v = ds_view(t.wl_idx);
+    else if (f == "wl_w") v = ds_view(t.wl_w);
+    else if (f == "paircnt") v = ds_view(t.paircnt);
+    else return false;
+    return true;
+}
+
+bool ds_member(const DataSet &d, const std::string &f, DsView &v)
+{
+    if (f == "X") v = ds_view(d.X);
+    else if (f == "codes") v = ds_view(d.codes);
+    else if (f == "lev") v = ds_view(d.lev);
+    else if (f == "lvl_off_d") v = ds_view(d.lvl_off_d);
+    else if (f == "members_all") v = ds_view(d.members_all);
+    else if (f == "lvl_ptr_all") v = ds_view(d.lvl_ptr_all);
+    else if (f == "lvl_count_all") v = ds_view(d.lvl_count_all);
+    else if (f == "Zc") v = ds_view(d.Zc);
+    else if (f == "one_count") v = ds_view(d.one_count);
+    else if (f == "ident_members") v = ds_view(d.ident_members);
+    else if (f == "S") v = ds_view(d.S);
+    else if (f == "yy_train") v = ds_view(d.yy_train);
+    else if (f == "yy_all") v = ds_view(d.yy_all);
+    else if (f == "Strain") v = ds_view(d.Strain);
+    else if (f == "Sheld") v = ds_view(d.Sheld);
+    else if (f == "col_ptr") v = ds_view(d.col_ptr);
+    else if (f == "row_ptr") v = ds_view(d.row_ptr);
+    else if (f == "col_idx") v = ds_view(d.col_idx);
+    else if (f == "row_idx") v = ds_view(d.row_idx);
+    else if (f == "col_val") v = ds_view(d.col_val);
+    else if (f == "row_val") v = ds_view(d.row_val);
+    else if (f == "col_flag") v = ds_view(d.col_flag);
+    else if (f == "cf_cnt") v = ds_view(d.cf_cnt);
+    else if (f == "cf_hn") v = ds_view(d.cf_hn);
+    else if (f == "cf_sq") v = ds_view(d.cf_sq);
+    else if (f == "cf_zt") v = ds_view(d.cf_zt);
+    else if (f == "cont_cnt") v = ds_view(d.cont_cnt);
+    else return false;
+    return true;
+}
+
+// "<name>" or "<name>:<i>" -> the array (v.p null: the data set did not build it).  false: no such name.
+bool ds_lookup(const DataSet &d, const std::string &full, DsView &v)
+{
+    v = DsView{};
+    std::string name = full;
+    long idx = -1;
+    const size_t colon = full.find(':');
+    if (colon != std::string::npos) {
+        const std::string tail = full.substr(colon + 1);
+        if (tail.empty() || tail.size() > 6 || tail.find_first_not_of("0123456789") != std::string::npos) return false;
+        idx = std::stol(tail);
+        name = full.substr(0, colon);
+    }
+    if (name == "fold_id") {
+        if (idx >= 0) return false;
+        if (const std::shared_ptr<const FoldIds> f = d.get_folds()) v = ds_view(f->id);
+        return true;
+    }
+    if (name == "cont_pair") {
+        if (idx < 0 || idx >= std::max(d.m, 1)) return false;
+        if ((size_t)idx < d.cont_pair.size()) v = ds_view(d.cont_pair[idx]);
+        return true;
+    }
+    if (name.rfind("cont.", 0) == 0) return idx < 0 && ds_cov_member(d.cont, name.substr(5), v);
+    if (name.rfind("contm_lists.", 0) == 0) return idx < 0 && ds_cov_member(d.contm_lists, name.substr(12), v);
+    if (name.rfind("contm.", 0) == 0) {
+        if (idx < 0 || idx >= std::max(d.m, 1)) return false;
+        static const CovTables none;
+        return ds_cov_member((size_t)idx < d.contm.size() ? d.contm[idx] : none, name.substr(6), v);
+    }
+    if (idx >= 0) return idx < d.c && ds_cov_member(d.cov[idx], name, v);
+    return ds_member(d, name, v);
+}
+
+// every name ds_lookup knows, one per line; ":#" marks a name that takes an index (covariate, or continuous column)
+std::string ds_name_list()
+{
+    std::string s;
+    for (const char *f : DS_MEMBERS) s += std::string(f) + "\n";
+    s += "cont_pair:#\nfold_id\n";
+    for (const char *f : DS_COV_MEMBERS) s += std::string(f) + ":#\n";
+    for (const char *f : DS_COV_MEMBERS) s += std::string("cont.") + f + "\n";
+    for (const char *f : DS_COV_MEMBERS) s += std::string("contm.") + f + ":#\n";
+    for (const char *f : DS_COV_MEMBERS) s += std::string("contm_lists.") + f + "\n";
+    return s;
+}
+
+// the static part of ColFacArgs as int32 (order: include/insider_hip.h, "ds:cf_geometry")
+std::vector<int32_t> ds_geometry(const DataSet &d)
+{
+    const ColFacArgs &cf = d.cf;
+    std::vector<int32_t> g;
+    g.reserve(DS_GEOMETRY_INTS);
+    for (int x : {cf.c, cf.nsteps, cf.tab_skip_lo, cf.tab_skip_n, cf.tab_rows, cf.cnt_stride, cf.hn_stride, cf.zt_stride,
+                  cf.sq_stride, cf.m})
+        g.push_back(x);
+    for (const int *a : {cf.L, cf.off, cf.nlater, cf.cnt_off, cf.hn_off, cf.zt_off})
+        for (int t = 0; t <= CF_MAXC; ++t) g.push_back(a[t]);
+    for (int t = 0; t < CF_MAXC; ++t) g.push_back(cf.pos_cov[t]);
+    for (int t = 0; t < CF_MAXC; ++t)
+        for (int k = 0; k < CF_MAXC; ++k) g.push_back(cf.later_plane[t][k]);
+    return g;
+}
+
+// the scalar facts of the data set ("ds_..."); false: not one of them
+bool ds_info(const DataSet &d, const std::string &s, double *out)
+{
+    if (s == "ds_ldn") *out = (double)d.ldn;
+    else if (s == "ds_ldp") *out = (double)d.ldp;
+    else if (s == "ds_SLP") *out = d.SLP;
+    else if (s == "ds_cnt_train") *out = d.cnt_train;
+    else if (s == "ds_cnt_test") *out = d.cnt_test;
+    else if (s == "ds_no_na") *out = d.no_na ? 1.0 : 0.0;
+    else if (s == "ds_merged") *out = d.merged ? 1.0 : 0.0;
+    else if (s == "ds_cont_merged") *out = d.cont_merged ? 1.0 : 0.0;
+    else if (s == "ds_cf_pair_ok") *out = d.cf_pair_ok ? 1.0 : 0.0;
+    else if (s == "ds_max_chunks") *out = d.max_chunks;
+    else if (s == "ds_max_L") *out = d.max_L;
+    else if (s == "ds_max_items") *out = d.max_items;
+    else if (s.rfind("ds_nitems:", 0) == 0 || s.rfind("ds_npairs:", 0) == 0) {
+        const std::string tail = s.substr(10);
+        if (tail.empty() || tail.size() > 6 || tail.find_first_not_of("0123456789") != std::string::npos) return false;
+        const long i = std::stol(tail);
+        if (i >= d.c) return false;
+        *out = s[4] == 'i' ? (double)d.cov[i].nitems : (double)d.cov[i].npairs;
+    } else return false;
+    return true;
+}
+}  // namespace
+
+extern "C" {
+
 int insider_hip_get_sweeps(insider_hip_handle *h, int32_t *out)
 {
     if (!h || !out) return fail(INSIDER_ERR_ARG, "null");
@@ -4227,6 +4393,15 @@ int insider_hip_get_info(insider_hip_handle *h, const char *name, double *out)
             }
         if (path == 2 && h->ds->m > 0) v += std::ceil(h->ds->m / 4.0) * NB * NB + NB;                                 // the continuous position
         *out = v;
+    } else if (s.rfind("ds_bytes:", 0) == 0) {
+        // size in bytes of a data-set array (insider_hip_get_array "ds:<name>"); 0: this data set did not build it
+        const std::string a = s.substr(9);
+        DsView v;
+        if (a == "cf_geometry") *out = (double)(DS_GEOMETRY_INTS * sizeof(int32_t));
+        else if (a == "names") *out = (double)ds_name_list().size();
+        else if (ds_lookup(*h->ds, a, v)) *out = v.p ? (double)v.bytes : 0.0;
+        else return fail(INSIDER_ERR_ARG, "unknown data-set array " + a);
+    } else if (ds_info(*h->ds, s, out)) {
     } else return fail(INSIDER_ERR_ARG, "unknown info key " + s);
     return INSIDER_OK;
 }
@@ -4240,7 +4415,22 @@ int insider_hip_get_array(insider_hip_handle *h, const char *name, void *out, in
     if (s == "cd_pass_slot") { src = h->ws.cd_pass_slot; have = h->ds->p * (int64_t)sizeof(int); }
     else if (s == "gene_perm") { src = h->ws.gene_perm; have = h->ds->p * (int64_t)sizeof(int); }
     else if (s == "order_table") { src = h->ws.order; have = (int64_t)(h->ws.order_rows + 1) * ORDER_ROW; }   // rows of ORDER_ROW bytes: the last solve's
-    else return fail(INSIDER_ERR_ARG, "unknown array " + s);
+    else if (s == "ds:cf_geometry" || s == "ds:names") {   // host facts of the data set: nothing to wait for
+        const std::vector<int32_t> g = ds_geometry(*h->ds);
+        const std::string names = ds_name_list();
+        const bool geo = s == "ds:cf_geometry";
+        have = geo ? (int64_t)(g.size() * sizeof(int32_t)) : (int64_t)names.size();
+        if (bytes < 0 || bytes > have) return fail(INSIDER_ERR_ARG, "array not available or too short");
+        std::memcpy(out, geo ? (const void *)g.data() : (const void *)names.data(), (size_t)bytes);
+        return INSIDER_OK;
+    } else if (s.rfind("ds:", 0) == 0) {
+        DsView v;
+        if (!ds_lookup(*h->ds, s.substr(3), v)) return fail(INSIDER_ERR_ARG, "unknown data-set array " + s.substr(3));
+        if (!v.p) return fail(INSIDER_ERR_ARG, "this data set did not build " + s.substr(3));
+        if (bytes < 0) return fail(INSIDER_ERR_ARG, "negative size");
+        src = v.p;
+        have = (int64_t)v.bytes;
+    } else return fail(INSIDER_ERR_ARG, "unknown array " + s);
     if (!src || bytes > have) return fail(INSIDER_ERR_ARG, "array not available or too short");
     HIPCHECK(hipSetDevice(h->ds->device));
     HIPCHECK(hipStreamSynchronize(h->st.stream));

@@ -1685,7 +1685,8 @@ __global__ void __launch_bounds__(256) k_transpose(const T *__restrict__ in, int
     }
 }
 
-// per-line sums of squares: yy_train[j] = sum_{train} x^2, yy_all[j] = sum x^2; counts of train / test entries
+// per-line sums of squares: yy_train[j] = sum_{train} x^2, yy_all[j] = sum x^2; counts of train / test / NA entries (cnt[0..2];
+// an entry may be train and test at once, so the NA entries are counted themselves)
 __global__ void __launch_bounds__(256) k_line_sumsq(const double *__restrict__ vals, const uint8_t *__restrict__ codes,
                                                     int64_t pitch, int len, int lines, double *__restrict__ yy_train,
                                                     double *__restrict__ yy_all, unsigned long long *__restrict__ cnt)
@@ -1694,22 +1695,28 @@ __global__ void __launch_bounds__(256) k_line_sumsq(const double *__restrict__ v
     const int j = blockIdx.x * 4 + w;
     if (j >= lines) return;
     double st = 0.0, sa = 0.0;
-    unsigned long long ntr = 0, nte = 0;
+    unsigned long long ntr = 0, nte = 0, nna = 0;
     for (int i = lane; i < len; i += WAVE) {
         const double x = vals[(size_t)j * pitch + i];
         const int cd = codes[(size_t)j * pitch + i];
         sa += x * x;
         if (cd & CODE_TRAIN) { st += x * x; ++ntr; }
         if (cd & CODE_TEST) ++nte;
+        if (!(cd & (CODE_TRAIN | CODE_TEST))) ++nna;
     }
     st = wave_sum(st);
     sa = wave_sum(sa);
-    for (int o = 32; o >= 1; o >>= 1) { ntr += __shfl_xor(ntr, o, 64); nte += __shfl_xor(nte, o, 64); }
+    for (int o = 32; o >= 1; o >>= 1) {
+        ntr += __shfl_xor(ntr, o, 64);
+        nte += __shfl_xor(nte, o, 64);
+        nna += __shfl_xor(nna, o, 64);
+    }
     if (lane == 0) {
         yy_train[j] = st;
         yy_all[j] = sa;
         atomicAdd(&cnt[0], ntr);
         atomicAdd(&cnt[1], nte);
+        atomicAdd(&cnt[2], nna);
     }
 }
 
