@@ -478,6 +478,7 @@ struct insider_hip_handle {
     // state of the running optimize() (its pending stream joins: Streams)
     FitPlan plan;                     // the kernel path of the call that is running, or ran last (plan_call)
     bool w_ready = false;
+    bool prep_joined = false;         // the main stream is already ordered behind this iteration's ev_prep (join_side)
     // sharding
     int64_t gene_offset = 0;
     int rank = 0, world = 1;
@@ -1479,6 +1480,7 @@ int launch_wsyrk_side(insider_hip_handle *h)
     if (int rp = launch_gram(h, h->ws.C, h->ds->p, h->ws.CCt, h->st.side3, h->ws.gram_part2)) return rp;
     if (int rp = launch_mm_reduce_kp(h, h->ds->Strain, h->ds->SLP, h->ws.C, (int)h->ds->p, h->ds->SL, h->ws.sc_part2, h->ws.SC, h->st.side3)) return rp;
     HIPCHECK(hipEventRecord(h->st.ev_prep, h->st.side3));
+    h->prep_joined = false;
     row_mark(h, RK_GRAM_SIDE);
     const size_t plen = h->plan.plen;
     for (int i = 0; i < h->ds->c; ++i) {
@@ -1490,6 +1492,17 @@ int launch_wsyrk_side(insider_hip_handle *h)
         HIPCHECK(hipEventRecord(h->st.ev_w[h->ds->c + k], h->st.side2));
     }
     h->w_ready = true;
+    return INSIDER_OK;
+}
+
+// merged row update behind launch_wsyrk_side(): the main stream waits for the level sums of row-update w (side2) and, in the
+// FIRST update of the iteration only, for C'C and (S^train C') (side3).  ev_prep is recorded once per iteration and every later
+// update is ordered behind the first one's wait: another wait is a barrier packet on the serial chain for nothing.
+int join_side(insider_hip_handle *h, int w)
+{
+    HIPCHECK(hipStreamWaitEvent(h->st.stream, h->st.ev_w[w], 0));
+    if (!h->prep_joined) HIPCHECK(hipStreamWaitEvent(h->st.stream, h->st.ev_prep, 0));
+    h->prep_joined = true;
     return INSIDER_OK;
 }
 
@@ -1544,10 +1557,8 @@ int row_update(insider_hip_handle *h, int i, int cont_col, int masked, double la
         int ypart_n = 0;
         if (int rcy = launch_mm_reduce_kp(h, h->ws.U, 2, h->ws.C, (int)h->ds->p, 1, h->ws.sc_part, nullptr, nullptr, &ypart_n, &h->row_kernels))
             return rcy;
-        if (h->w_ready) {
-            HIPCHECK(hipStreamWaitEvent(h->st.stream, h->st.ev_w[h->ds->c + cont_col], 0));
-            HIPCHECK(hipStreamWaitEvent(h->st.stream, h->st.ev_prep, 0));
-        }
+        if (h->w_ready)
+            if (int rj = join_side(h, h->ds->c + cont_col)) return rj;
         double *rec = h->w_ready ? h->ws.lvl_sum_all + (size_t)row0 * plan.plen : h->ws.lvl_sum;
         if (!h->w_ready)
             if (int rg = launch_level_gram(h, 0, h->st.stream, rec, &cm)) return rg;
@@ -1588,10 +1599,8 @@ int row_update(insider_hip_handle *h, int i, int cont_col, int masked, double la
                                           &ypart_n, &h->row_kernels))
             return rcy;
         if (!plan.row_fused) ypart_n = 0;
-        if (h->w_ready) {   // wsyrk + level sums came from side2, C'C and (S^train C') from side3
-            HIPCHECK(hipStreamWaitEvent(h->st.stream, h->st.ev_w[i], 0));
-            HIPCHECK(hipStreamWaitEvent(h->st.stream, h->st.ev_prep, 0));
-        }
+        if (h->w_ready)   // wsyrk + level sums came from side2, C'C and (S^train C') from side3
+            if (int rj = join_side(h, i)) return rj;
         if (!h->w_ready)
             if (int rg = launch_level_gram(h, i, h->st.stream, h->ws.lvl_sum)) return rg;
         double *rec = h->w_ready ? h->ws.lvl_sum_all + (size_t)row0 * plan.plen : h->ws.lvl_sum;

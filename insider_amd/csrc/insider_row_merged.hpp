@@ -429,6 +429,12 @@ __global__ void __launch_bounds__(256) k_level_pack(const double *__restrict__ Y
 // Y: (U'C)[l], or — ypart_n > 0 — its per-slab partial sums part[slab][L][KP] straight from k_mm_reduce: the block then adds
 // them up itself, in k_sum_partials' order (16 strided groups, then the groups in order: the same bits), which takes that
 // kernel and its launch off the main chain of the row phase.
+// The block is alone on its CU and ten to a hundred blocks make a launch: its time is the latency of its global loads, not
+// their volume.  So every load is requested as early as its address is known and in batches held in registers — the level's
+// record, CC', SC and the count at the top (they depend on nothing the block computes), a cell's partial sums LM_YCH at a time
+// for two cells at once, the operands of sum_r s_r LM_SCH steps ahead of the fma chain — and every sum keeps its order.
+constexpr int LM_YCH = 32;   // partial sums of one (m, o) cell in flight together: slabs m, m + 16, ... (c3: 25 per cell)
+constexpr int LM_SCH = 16;   // steps of a wave's sum_r s_r chain whose operands are fetched together (two such sets in flight)
 template <int NB>
 __global__ void __launch_bounds__(256) k_level_merged(const double *__restrict__ rec /*[L][STAT + 2 KP + 2]: weighted-SYRK level sums*/,
                                                       const double *__restrict__ Y /*[L][KP]*/, int ypart_n,
@@ -440,32 +446,98 @@ __global__ void __launch_bounds__(256) k_level_merged(const double *__restrict__
                                                       const double *__restrict__ cnt_real = nullptr /*[L]: real-valued |l| (sum_r z_r^2 of a continuous column) instead of lvl_count*/)
 {
     constexpr int KP = Geo<NB>::KP, NBLK = Geo<NB>::NBLK, STAT = Geo<NB>::STAT;
+    constexpr bool STAGE = NB <= 2;   // CC' through LDS (K > 31: s_H alone is up to 32 KB, CC' stays in global memory)
+    constexpr int CPT = STAGE ? KP * KP / 256 : 1;
     __shared__ double red[4][64];
     __shared__ double s_H[KP * KP];
     __shared__ double s_A[NB <= 2 ? KP * KP : 1];   // the in-kernel solve is the register route (K <= 31); larger K: k_level_solve
+    __shared__ double s_C[STAGE ? KP * KP : 1];
     __shared__ double s_s[KP];
     __shared__ double s_y[16][KP];
     const int l = blockIdx.x, lane = threadIdx.x & 63, g = threadIdx.x >> 6;
     if (l >= L) return;
+    const bool valid = lane < K;
+    // what depends on nothing computed here: CC' (every thread its share), and in wave 0 the level's record, SC[l] and |l|
+    double ccr[CPT];
+    if constexpr (STAGE) {
+#pragma unroll
+        for (int t = 0; t < CPT; ++t) ccr[t] = CCt[threadIdx.x + 256 * t];
+    }
+    const int sub = lane >> 4, c16 = lane & 15;
+    d4 h[NBLK];
+    double scv = 0.0, cnt = 0.0;
+    int nl = 0;
+    if (g == 0) {   // wave-uniform
+        const double *src = rec + (size_t)l * (STAT + 2 * KP + 2);
+#pragma unroll
+        for (int b = 0; b < NBLK; ++b)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) h[b][q] = src[b * 256 + (sub + 4 * q) * 16 + c16];
+        if (valid) scv = SC[(size_t)l * KP + lane];
+        nl = lvl_count[l];
+        cnt = cnt_real ? cnt_real[l] : (double)nl;
+    }
+    // sum_r s_r: wave g takes the stacked levels q = g, g + 4, ...; an operand set holds the steps q0 + 4 i, i < LM_SCH.
+    // (every load of this phase is unconditional at a safe address — a step or slab past the end reads element 0 again, a
+    // lane past K reads lane 0's — and only the sums are predicated: no branch stands between the requests)
+    const double *pc = paircnt + (size_t)l * SL, *as = Astack + (valid ? lane : 0);
+    auto ss_fetch = [&](int q0, double (&a)[LM_SCH], double (&b)[LM_SCH]) {
+#pragma unroll
+        for (int i = 0; i < LM_SCH; ++i) {
+            const int q = q0 + 4 * i < SL ? q0 + 4 * i : 0;   // wave-uniform
+            a[i] = pc[q];
+            b[i] = as[(size_t)q * KP];
+        }
+    };
+    double pa0[LM_SCH], pb0[LM_SCH], pa1[LM_SCH], pb1[LM_SCH];
+    ss_fetch(g, pa0, pb0);
     if (ypart_n > 0) {   // wave-uniform.  k_sum_partials: s_m = sum_{b = m, m + 16, ...} part[b][o], then sum_m s_m in order
         const size_t len = (size_t)L * KP;
-        for (int c = threadIdx.x; c < 16 * KP; c += 256) {
-            const int m = c / KP, o = c % KP;
-            double sm = 0.0;
-#pragma unroll 8
-            for (int b = m; b < ypart_n; b += 16) sm += Y[(size_t)b * len + (size_t)l * KP + o];
-            s_y[m][o] = sm;
+        for (int c0 = threadIdx.x; c0 < 16 * KP; c0 += 512) {   // two cells per thread at a time: their loads fly together
+            const int c1 = c0 + 256 < 16 * KP ? c0 + 256 : c0;   // (KP = 16, 48: the last round has one cell; it is summed twice)
+            const int m0 = c0 / KP, m1 = c1 / KP;
+            // slab b0 + 16 i + m of cell (m, o): a wave-uniform slab base plus one offset per cell and thread
+            const uint32_t lo0 = (uint32_t)(l * KP + c0 % KP), lo1 = (uint32_t)(l * KP + c1 % KP);
+            const uint32_t of0 = (uint32_t)(m0 * len) + lo0, of1 = (uint32_t)(m1 * len) + lo1;
+            double sm0 = 0.0, sm1 = 0.0;
+            for (int b0 = 0; b0 < ypart_n; b0 += 16 * LM_YCH) {
+                double r0[LM_YCH], r1[LM_YCH];
+#pragma unroll
+                for (int i = 0; i < LM_YCH; ++i) {
+                    const int bu = b0 + 16 * i;
+                    const double *slab = Y + (bu < ypart_n ? (size_t)bu * len : 0);   // wave-uniform
+                    r0[i] = slab[bu + m0 < ypart_n ? of0 : lo0];
+                    r1[i] = slab[bu + m1 < ypart_n ? of1 : lo1];
+                }
+#pragma unroll
+                for (int i = 0; i < LM_YCH; ++i) sm0 = b0 + 16 * i + m0 < ypart_n ? sm0 + r0[i] : sm0;
+#pragma unroll
+                for (int i = 0; i < LM_YCH; ++i) sm1 = b0 + 16 * i + m1 < ypart_n ? sm1 + r1[i] : sm1;
+            }
+            s_y[m0][c0 % KP] = sm0;
+            s_y[m1][c1 % KP] = sm1;
         }
     }
     double ss = 0.0;
-    if (lane < K)
-        for (int q = g; q < SL; q += 4) ss = fma(paircnt[(size_t)l * SL + q], Astack[(size_t)q * KP + lane], ss);
+    auto ss_chain = [&](int q0, const double (&a)[LM_SCH], const double (&b)[LM_SCH]) {
+#pragma unroll
+        for (int i = 0; i < LM_SCH; ++i) ss = q0 + 4 * i < SL ? fma(a[i], b[i], ss) : ss;
+    };
+    for (int q0 = g; q0 < SL; q0 += 8 * LM_SCH) {
+        ss_fetch(q0 + 4 * LM_SCH, pa1, pb1);
+        ss_chain(q0, pa0, pb0);
+        ss_fetch(q0 + 8 * LM_SCH, pa0, pb0);
+        ss_chain(q0 + 4 * LM_SCH, pa1, pb1);
+    }
+    if (!valid) ss = 0.0;
+    if constexpr (STAGE) {
+#pragma unroll
+        for (int t = 0; t < CPT; ++t) s_C[threadIdx.x + 256 * t] = ccr[t];
+    }
     red[g][lane] = ss;
     __syncthreads();
     if (g != 0) return;
-    const bool valid = lane < K;
-    const int sub = lane >> 4, c16 = lane & 15;
-    const double cnt = cnt_real ? cnt_real[l] : (double)lvl_count[l];
+    const double *cc = STAGE ? s_C : CCt;
     double v = 0.0;
     if (valid) {
         if (ypart_n > 0) {
@@ -476,32 +548,26 @@ __global__ void __launch_bounds__(256) k_level_merged(const double *__restrict__
         }
     }
     const double ssum = ((red[0][lane] + red[1][lane]) + red[2][lane]) + red[3][lane];
-    const double *src = rec + (size_t)l * (STAT + 2 * KP + 2);
-    d4 h[NBLK];
-#pragma unroll
-    for (int b = 0; b < NBLK; ++b)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) h[b][q] = src[b * 256 + (sub + 4 * q) * 16 + c16];
     acc_to_lds<NB>(h, s_H, lane);
     if (lane < KP) s_s[lane] = ssum;
     wave_sync();
     double *eql = eq + (size_t)l * (KP * KP + KP);
     for (int i = lane; i < KP * KP; i += WAVE) {
         const int x = i / KP, y = i % KP;
-        const double e = (x < K && y < K) ? cnt * CCt[i] - s_H[i] : 0.0;
+        const double e = (x < K && y < K) ? cnt * cc[i] - s_H[i] : 0.0;
         eql[i] = e;
         if constexpr (NB <= 2) s_A[i] = e;
     }
     double yv = 0.0;
     if (lane < KP) {
         if (valid) {
-            yv = SC[(size_t)l * KP + lane] + v;
-            for (int b = 0; b < K; ++b) yv -= CCt[b * KP + lane] * s_s[b];      // CC' symmetric: coalesced
+            yv = scv + v;
+            for (int b = 0; b < K; ++b) yv -= cc[b * KP + lane] * s_s[b];      // CC' symmetric: lanes side by side
         }
         eql[KP * KP + lane] = yv;
     }
     if constexpr (NB <= 2) {
-        if (!do_solve || cnt_real || lvl_count[l] == 0) return;   // level without samples: the reference never visits it (:147)
+        if (!do_solve || cnt_real || nl == 0) return;   // level without samples: the reference never visits it (:147)
         wave_sync();
         double b = lane < KP ? yv : 0.0;
         double row[KP];
